@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — the bam2db hot path on MI355X, measured on BASELINE.json configs[2].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets the job up, warms up, times the K steps and prints the line: the headline (value, ms_per_step), the
+counters, the config and whole_path, which all come from the timed steps themselves.  --full adds everything that takes
+runs of its own: step_with_draw_generation, the per-kernel table and roofline, and (N=1) the device_path, cpu_baseline
+and e2e legs.  --dump-outputs DIR writes, after the timed steps, what the last of them computed (dump_outputs()).
 
 Workload (fastf_amd/workload.py): 200 M synthetic records, 50 k barcodes x 36 601 genes,
 --cell 0.5 --depth 0.5 --seed 926 (the shape of the reference's own benchmark/fastF_disk.sh).
@@ -14,15 +19,15 @@ owner in one all-to-all.
 
 The one JSON line carries
   value            records/s of the timed steps, inputs resident in HBM when the clock starts
-  roofline         the kernel that takes most of the step: algorithmic bytes / its HIP-event time
   whole_path       SURVEY 8d's B and B_read over the step time (nominal and executed radix passes)
-  device_path      N=1: pinned host SoA -> hipMemcpyAsync -> kernels -> COO on the host (PCIe-inclusive): SURVEY 8d's
-                   device-path scope; its rate is repeated at the top level as device_path_records_per_s
-  e2e              N=1: the real CLI on generated BAM files, process start to process EXIT (outputs-closed beside it);
-                   the Cell-Ranger-shaped rate is repeated at the top level as e2e_records_per_s_to_process_exit
+  roofline         (--full) the kernel that takes most of the step: algorithmic bytes / its HIP-event time
+  device_path      (--full, N=1) pinned host SoA -> hipMemcpyAsync -> kernels -> COO on the host (PCIe-inclusive): SURVEY
+                   8d's device-path scope; its rate is repeated at the top level as device_path_records_per_s
+  e2e              (--full, N=1) the real CLI on generated BAM files, process start to process EXIT (outputs-closed beside
+                   it); the Cell-Ranger-shaped rate is repeated at the top level as e2e_records_per_s_to_process_exit
   (`value` itself is the resident-input rate the bench contract asks for; the two rates above are what a caller of
   bam2db() sees and are never folded into it)
-  cpu_baseline     N=1: the CPU oracle on a bounded sample of the same records, 1 core (+ parity check)
+  cpu_baseline     (--full, N=1) the CPU oracle on a bounded sample of the same records, 1 core (+ parity check)
 """
 import argparse
 import json
@@ -81,7 +86,7 @@ def kernel_table(eng, N, H, K, Z, draw_bits, steps_timed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)   # 100 steps of configs[2] = 0.27 s timed
+    ap.add_argument("--steps", type=_positive, default=100)   # 100 steps of configs[2] = 0.27 s timed
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=["c3", "c2"], default="c3",
                     help="c3 = BASELINE configs[2] (the headline, default); c2 = BASELINE configs[1], 10 M keep-all records (round 1's workload)")
@@ -93,6 +98,11 @@ def main():
     ap.add_argument("--no-devpath", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--e2e-records", type=str, default="40000000,20000000", help="records of the skinny and the Cell-Ranger-shaped BAM")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: the step with its draw generation, the per-kernel "
+                         "table and roofline, and (N=1) the device_path, cpu_baseline and e2e legs (--no-cpu etc. apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, a seeded sample of the rows)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -185,12 +195,20 @@ def main():
 
     err = eng.dev_error_bits()
     hits, sampled, valid, _ = sp.global_counters()
+    K_local = int(sp.d_n.item())
+    Z_local = int(sp.nnz.item())
+    tot = torch.tensor([K_local, Z_local], dtype=torch.int64, device=dev)
+    if world > 1:
+        dist.all_reduce(tot)
+    K_job, Z_job = int(tot[0].item()), int(tot[1].item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sp, [N_total, hits, sampled, valid, K_job, Z_job, err] if rank == 0 else None)
 
     # ---- the step WITH its draw generation (N = 1): the job's draws — one per CB hit — made inside the clock by the device's own
     #      MT19937 (fastf_dev_mt_decisions: sub-streams seated by jump-ahead, generated side by side), then the same step ----
     with_draws = None
-    K_ref = int(sp.d_n.item())
-    if world == 1 and not args.draw_words:
+    K_ref = K_local
+    if args.full and world == 1 and not args.draw_words:
         n_gen_steps = max(3, min(args.steps, 20))
         bits = stages.mt_decisions(workload.SEED, lists.mt_skip, hits)         # (first call: polynomials up, buffers sized)
         torch.cuda.synchronize()
@@ -217,49 +235,44 @@ def main():
                       "draw_generation_ms": t_gen_only * 1e3, "draws_per_step": hits, "draws_per_s": hits / t_gen_only,
                       "same_counters_as_the_resident_stream": (h2, s2, v2) == (hits, sampled, valid) and int(sp.d_n.item()) == K_ref,
                       "scope": "fastf_dev_mt_decisions (host seeds and skips the stream, the device seats 624 x 256-draw sub-streams by jump-ahead and generates them side by side, draw_bits packs the decisions; the call synchronises) + the step above"}
-    K_local = int(sp.d_n.item())
-    Z_local = int(sp.nnz.item())
-    tot = torch.tensor([K_local, Z_local], dtype=torch.int64, device=dev)
-    if world > 1:
-        dist.all_reduce(tot)
-    K_job, Z_job = int(tot[0].item()), int(tot[1].item())
 
-    # ---- per-kernel HIP-event timing (events on the launch stream, a few extra steps after the timed region) ----
-    eng.set_timing(True)
-    STEPS_TIMED = 3
-    for _ in range(STEPS_TIMED):
-        step()
-        sp.st.rows_gather(sp.d_n, sp.feature, sp.cell, sp.count)      # concatenation of K3's row regions (timed as its own line)
-    torch.cuda.synchronize()
-    H_local = hits // G
-    ktab = kernel_table(eng, n_local, H_local, K_local, Z_local, not args.draw_words, STEPS_TIMED)
-    eng.set_timing(False)
+    ktab = None
     P_nom = (eng.key_bits + 7) // 8
     P_exe = eng.sort_passes(sp.st.skip_low)
-    per_step = {k: v["avg_ms"] * v["launches_per_step"] for k, v in ktab.items() if not k.startswith("rows_gather")}
-    dom = max(per_step, key=per_step.get)
-    # HBM bytes per launch of that kernel from the PMC passes of tools/profile_round.sh (FETCH_SIZE / WRITE_SIZE in runs of
-    # their own, gfx950 corrections applied there); only a profile of this very workload counts
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    kernels_of = {"reduce_hashed+giant_groups": ["reduce_hashed_kernel", "span_scan_kernel", "giant_groups_kernel"], "probe_cells": ["probe_cells_lds_kernel", "probe_cells_filtered_kernel", "probe_cells_kernel"],
-                  "filter_pack": ["filter_pack_stream_kernel", "filter_pack_kernel"], "tile_count": ["tile_count_kernel"],
-                  "scatter": ["scatter_kernel"], "reduce_windows+span_scan": ["reduce_hashed_kernel", "reduce_windows_kernel", "span_scan_kernel", "giant_groups_kernel"]}
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("workload_records") == N_total and G == 1:
-                names = kernels_of.get(dom.split(" ")[0], [])
-                got = [tj["kernels"][k]["hbm_bytes_per_launch"] for k in names if k in tj.get("kernels", {})]
-                if got:
-                    traffic = sum(got) if dom.startswith("reduce_") else got[0]
-        except Exception:
-            traffic = None
+    if args.full:
+        # ---- per-kernel HIP-event timing (events on the launch stream, a few extra steps after the timed region) ----
+        eng.set_timing(True)
+        STEPS_TIMED = 3
+        for _ in range(STEPS_TIMED):
+            step()
+            sp.st.rows_gather(sp.d_n, sp.feature, sp.cell, sp.count)      # concatenation of K3's row regions (timed as its own line)
+        torch.cuda.synchronize()
+        H_local = hits // G
+        ktab = kernel_table(eng, n_local, H_local, K_local, Z_local, not args.draw_words, STEPS_TIMED)
+        eng.set_timing(False)
+        per_step = {k: v["avg_ms"] * v["launches_per_step"] for k, v in ktab.items() if not k.startswith("rows_gather")}
+        dom = max(per_step, key=per_step.get)
+        # HBM bytes per launch of that kernel from the PMC passes of tools/profile_round.sh (FETCH_SIZE / WRITE_SIZE in runs of
+        # their own, gfx950 corrections applied there); only a profile of this very workload counts
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        kernels_of = {"reduce_hashed+giant_groups": ["reduce_hashed_kernel", "span_scan_kernel", "giant_groups_kernel"], "probe_cells": ["probe_cells_lds_kernel", "probe_cells_filtered_kernel", "probe_cells_kernel"],
+                      "filter_pack": ["filter_pack_stream_kernel", "filter_pack_kernel"], "tile_count": ["tile_count_kernel"],
+                      "scatter": ["scatter_kernel"], "reduce_windows+span_scan": ["reduce_hashed_kernel", "reduce_windows_kernel", "span_scan_kernel", "giant_groups_kernel"]}
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("workload_records") == N_total and G == 1:
+                    names = kernels_of.get(dom.split(" ")[0], [])
+                    got = [tj["kernels"][k]["hbm_bytes_per_launch"] for k in names if k in tj.get("kernels", {})]
+                    if got:
+                        traffic = sum(got) if dom.startswith("reduce_") else got[0]
+            except Exception:
+                traffic = None
 
     out = None
     if rank == 0:
         ms_step = dt / args.steps * 1e3
-        d = ktab[dom]
         # algorithmic bytes of one step of the whole job: B = 24N + 4H + 8K(3+2P) + 12Z — with the draw term at what
         # the step really reads: one decision bit per hit (H / 8 bytes) unless --draw-words hands it the 32-bit draws
         # (round 4 credited 4H = 0.36 GB of draws that no kernel read any more; B_8d keeps SURVEY's letter for comparison)
@@ -285,11 +298,6 @@ def main():
                        "radix_passes_executed": P_exe,
                        "sharding": ("cell-hash, one all-to-all, %s" % ("3-stream pipeline" if sp.pipelined else "single stream")) if G > 1 else "single GPU",
                        "lookup_tables": eng.table_modes},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": d["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": d["frac"], "traffic": traffic, "bytes_per_launch": d["bytes_per_launch"], "bytes_8d": d.get("bytes_8d"),
-                         "avg_launch_ms": d["avg_ms"], "launches_timed": d["launches_timed"],
-                         "share_of_step": per_step[dom] / sum(per_step.values())},
-            "kernels": ktab,
             "whole_path": {"per_gpu": True,
                            "B_nominal_P%d" % P_nom: B_of(P_nom), "B_executed_P%d" % P_exe: B_of(P_exe),
                            "B_read_nominal": Bread_of(P_nom), "B_read_executed": Bread_of(P_exe),
@@ -300,22 +308,29 @@ def main():
                            "read_frac_of_peak_nominal": gbs(Bread_of(P_nom)) / HBM_PEAK_GBS,
                            "draw_bytes_counted": draw_b,
                            "B_8d_executed": B_of(P_exe, 4 * hits), "B_read_8d_executed": Bread_of(P_exe, 4 * hits)},
-            "step_with_draw_generation": with_draws,
             "counters": {"total": N_total, "hits": hits, "sampled": sampled, "valid": valid,
                          "keys": K_job, "rows": Z_job, "device_error_bits": err},
         }
         if N_total == 200_000_000 and not c2:  # the job is the same for every rank count: so are its totals
             got = {k: out["counters"][k] for k in workload.EXPECTED_200M}
             out["counters"]["same_as_single_gpu_reference_run"] = got == workload.EXPECTED_200M
+        if args.full:
+            d = ktab[dom]
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": d["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": d["frac"], "traffic": traffic, "bytes_per_launch": d["bytes_per_launch"], "bytes_8d": d.get("bytes_8d"),
+                               "avg_launch_ms": d["avg_ms"], "launches_timed": d["launches_timed"],
+                               "share_of_step": per_step[dom] / sum(per_step.values())}
+            out["kernels"] = ktab
+            out["step_with_draw_generation"] = with_draws
 
     # free the resident job before the host-side legs
     del sp, cb, gx, umi, meta, d_draws, d_stream, blk
     eng.close()
     torch.cuda.empty_cache()
 
-    if rank == 0 and G == 1 and c2:
-        out["cpu_baseline"] = None             # the legs below are defined on the headline workload
-    elif rank == 0 and G == 1:
+    if rank == 0 and (G > 1 or c2 or not args.full):
+        out["cpu_baseline"] = None             # the legs below are defined on the headline workload, one GPU, --full
+    elif rank == 0:
         if not args.no_devpath:
             out["device_path"] = device_path_leg(job, dev, local, N_total, out["counters"])
         if not args.no_cpu:
@@ -328,13 +343,42 @@ def main():
         out["scopes"] = {"kernels_only_records_per_s": out["value"],
                          "device_path_records_per_s": (out.get("device_path") or {}).get("value"),
                          "e2e_records_per_s_to_process_exit": {k: v.get("value") for k, v in (out.get("e2e") or {}).items() if isinstance(v, dict)}}
-    elif rank == 0:
-        out["cpu_baseline"] = None
 
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _positive(s):
+    n = int(s)
+    if n < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return n
+
+
+DUMP_ROWS = 1 << 20        # rows of the matrix in a --dump-outputs: all of them up to this many, else a seeded sample
+DUMP_SEED = 926
+
+
+def dump_outputs(where, sp, counters):
+    """what a caller of the timed path receives from its last step, as <where>/<name>.npy (float64; every value is an integer
+    below 2**53): the COO rows in the reference order (cell, feature) — feature, cell, count, and row_index, their positions
+    among all rows (every row up to DUMP_ROWS, else a sorted sample of DUMP_ROWS drawn with DUMP_SEED) — the per-cell and
+    per-feature sums of count over ALL rows, and the job's counters (total, hits, sampled, valid, keys, rows, device error
+    bits).  At most 4 x 8 MiB + the sums.  gather_coo is collective: every rank calls this, the rank with counters writes."""
+    f, c, k = sp.gather_coo()
+    if counters is None:
+        return
+    z = len(f)
+    idx = np.arange(z) if z <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(z, DUMP_ROWS, replace=False))
+    arrays = {"row_index": idx, "feature": f[idx], "cell": c[idx], "count": k[idx],
+              "count_per_cell": np.bincount(c, weights=k), "count_per_feature": np.bincount(f, weights=k),
+              "counters": np.array(counters)}
+    os.makedirs(where, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(where, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log("bench: outputs of the last timed step written to %s (%d of %d rows)" % (where, len(idx), z))
 
 
 def device_path_leg(job, dev, local, N_total, want):

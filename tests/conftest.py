@@ -4,8 +4,9 @@ GPU tests run in CHILD processes, one per test file (and one per test for the te
 200 M / 1 B-record jobs): `pytest -m gpu` in the parent collects, orders and reports as usual, but the parent never touches
 the GPU — each unit's tests run in a fresh `python -m pytest <node ids>` child that the parent starts (an ordinary child
 process, never an exec of a process that has initialised the GPU) and whose per-test reports it replays.  A GPU fault, a
-hang or a leaked pin in one unit ends that unit's child; the other files' results are still there (round 5's single
-process lost 69 tests behind one fault).  The files run in the order of SURVEY section 8: the 8a parity tests first.
+hang or a leaked pin in one unit ends that unit's child, and no further child is started on the device after it: the
+units behind it fail as not run, the results of the units before it are kept.  The files run in the order of SURVEY
+section 8: the 8a parity tests first.
 
 FASTF_TEST_INPROCESS=1: everything in this process, as before (debugging one test under a tool).
 """
@@ -164,8 +165,6 @@ def _replay(item, res):
             longrepr = tuple(sk) if sk and len(sk) == 3 else (str(item.fspath), 0, ph["longrepr"] or "skipped")
         ihook.pytest_runtest_logreport(report=TestReport(item.nodeid, item.location, dict(item.keywords), ph["outcome"], longrepr, ph["when"], duration=ph["duration"]))
     if not complete:
-        if res.get("died_at") and item.nodeid not in res["died_at"] and not phases:
-            res = dict(res, tail=res.get("tail_more", res["tail"]))
         why = "the child process of this test's unit ended (rc=%s%s) before this test reported%s\n---- end of the child's output ----\n%s" % (
             res["rc"], (", " + res["note"]) if res["note"] else "", " its teardown" if phases else "", res["tail"])
         when = "call" if not any(ph["when"] == "call" for ph in phases) else "teardown"
@@ -189,20 +188,17 @@ def pytest_runtest_protocol(item, nextitem):
         for it in item.session.items:
             if _is_gpu(it):
                 units.setdefault(_unit_of(it), []).append(it.nodeid)
+        died = None
         for unit, nodeids in units.items():
+            if died is not None:
+                # a child that died (fault, abort, signal, time limit) may have left the device in a bad state: nothing more
+                # is started on it in this session; the tests of the units behind it fail as not run
+                config._fastf_units[unit] = dict(rc=None, note="not started: the child of unit %s died before it" % died,
+                                                 phases={}, tail="", seconds=0.0, n=len(nodeids))
+                continue
             res = _run_unit(config, unit, nodeids)
-            # a child that died took the test it was running with it — the tests behind that one get a fresh child (twice at most)
-            for _ in range(2):
-                seen = [n for n in nodeids if res["phases"].get(n)]
-                if res["rc"] in (0, 1) or not seen or res["note"]:
-                    break
-                rest = nodeids[nodeids.index(seen[-1]) + 1:]
-                if not rest:
-                    break
-                more = _run_unit(config, unit + " (after the child died)", rest)
-                res["phases"].update(more["phases"])
-                res["rc"], res["tail_more"] = more["rc"], more["tail"]
-                res["died_at"] = res.get("died_at", []) + [seen[-1]]
+            if res["rc"] not in (0, 1) or res["note"]:
+                died = unit
             config._fastf_units[unit] = res
     _replay(item, config._fastf_units[_unit_of(item)])
     return True

@@ -12,6 +12,11 @@ from oracle import oracle as O
 from helpers import Case
 
 FX = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "survey_8c.json")))
+# the reference's own answers to the pins below, recorded by tests/golden/make_ref_pins.py: the pins hold against them
+# everywhere, and against the reference itself too where oracle/_ref is built
+REF = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ref_pins.json")))
+MT_SEEDS = [926, 1, 20240501]
+SAMPLE_INT_CASES = [(6, 3, 926), (1000, 500, 926), (1000, 1000, 7), (1000, 0, 7), (17, 16, 3), (50000, 12345, 11)]
 
 
 def test_mt_known_answers():
@@ -59,9 +64,15 @@ ref = O.ref_lib()
 needs_ref = pytest.mark.skipif(ref is None, reason="oracle/_ref not built (reference sources absent)")
 
 
-@needs_ref
-@pytest.mark.parametrize("seed", [926, 1, 20240501])
+@pytest.mark.parametrize("seed", MT_SEEDS)
 def test_mt_matches_reference_sources(seed):
+    want = REF["mt"][str(seed)]
+    assert O.mt_stream(seed, 2000).tolist() == want["genrand_int32"]
+    L = O.lib()
+    L.oracle_init_genrand(seed)
+    assert [L.oracle_genrand_real1() for _ in range(100)] == want["genrand_real1"]
+    if ref is None:
+        return
     ref.init_genrand(seed)
     want = [ref.genrand_int32() & 0xFFFFFFFF for _ in range(2000)]
     assert O.mt_stream(seed, 2000).tolist() == want
@@ -72,9 +83,13 @@ def test_mt_matches_reference_sources(seed):
         assert L.oracle_genrand_real1() == ref.genrand_real1()
 
 
-@needs_ref
-@pytest.mark.parametrize("n,k,seed", [(6, 3, 926), (1000, 500, 926), (1000, 1000, 7), (1000, 0, 7), (17, 16, 3), (50000, 12345, 11)])
+@pytest.mark.parametrize("n,k,seed", SAMPLE_INT_CASES)
 def test_sample_int_matches_reference_sources(n, k, seed):
+    want = next(c for c in REF["sample_int"] if (c["n"], c["k"], c["seed"]) == (n, k, seed))
+    assert O.sample_cells(n, k, seed).tolist() == want["sorted"]
+    assert O.lib().oracle_genrand_int32() == want["next_genrand_int32"]
+    if ref is None:
+        return
     seq = ref.GetSeqInt(0, n - 1, 1)
     out = ref.SampleInt(seq, n, k, 0, seed)
     want = sorted(out[i] for i in range(k))

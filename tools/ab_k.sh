@@ -6,7 +6,7 @@ out=gpurun_out/r4/ab_$(echo "$@" | tr ' ' '_').txt
 mkdir -p gpurun_out/r4; : > $out.raw
 for r in $(seq $rounds); do for v in "$@"; do
   if [ $v = main ]; then lib=""; else lib="FASTF_LIB_OVERRIDE=$PWD/build/$v/libfastf_amd.so"; fi
-  env $lib python3 bench.py --steps 30 --no-e2e --no-cpu --no-devpath 2>/dev/null | python3 -c "
+  env $lib python3 bench.py --full --steps 30 --no-e2e --no-cpu --no-devpath 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'v':'$v','step':d['ms_per_step'],'ok':d['counters']['same_as_single_gpu_reference_run'],'k':{k.split()[0]:v['avg_ms'] for k,v in d['kernels'].items()}}))" >> $out.raw
 done; done
 python3 - $out.raw <<'PY' | tee $out
