@@ -271,6 +271,9 @@ struct fastf_engine {
     // layout and runs the streaming K1b; its regions are appended to the key store, which holds SLOTS (regions with gaps) until
     // fastf_engine_finish sorts out of them
     bool stream_mode = false, store_regions = false;
+    // NARROW blocked runs (umi_kernels.hpp, NBLK_GX): 10 instead of 18 bytes per record; decided once at create — stream mode,
+    // every listed feature in the LDS gene family, its numbers below 2^32 - 1, at most 12 UMI bases (FASTF_BLOCK_WIDE=1: never)
+    bool narrow = false, genes_one_family = false;
     u64 slots_used = 0, slot_cap = 0; u32 rgn_n = 0, rgn_cap = 0;
     DevBuf d_scanblk;                    // chunk totals of a scan over more than 16 384 tiles
     // K3: row regions (one slot per key: a workgroup's rows go to the slots of its own chunk), rows per chunk and their bases
@@ -516,13 +519,18 @@ static int build_gene_lds(fastf_engine* e, const u64* keys, u32 n) {
                              (const void*)filter_pack_stream_kernel<false, false, false, true>, (const void*)filter_pack_stream_kernel<false, false, true, true>,
                              (const void*)filter_pack_stream_kernel<false, true, false, true>, (const void*)filter_pack_stream_kernel<false, true, true, true>,
                              (const void*)filter_pack_stream_kernel<true, false, false, true>, (const void*)filter_pack_stream_kernel<true, false, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, true, false, true>, (const void*)filter_pack_stream_kernel<true, true, true, true>};
+                             (const void*)filter_pack_stream_kernel<true, true, false, true>, (const void*)filter_pack_stream_kernel<true, true, true, true>,
+                             (const void*)filter_pack_stream_kernel<false, false, false, true, true>, (const void*)filter_pack_stream_kernel<false, false, true, true, true>,
+                             (const void*)filter_pack_stream_kernel<false, true, false, true, true>, (const void*)filter_pack_stream_kernel<false, true, true, true, true>,
+                             (const void*)filter_pack_stream_kernel<true, false, false, true, true>, (const void*)filter_pack_stream_kernel<true, false, true, true, true>,
+                             (const void*)filter_pack_stream_kernel<true, true, false, true, true>, (const void*)filter_pack_stream_kernel<true, true, true, true, true>};
         for (const void* f : fns)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return 0;
     }
     const size_t per_block = bytes + 1024;                           // + the kernel's static LDS (about 0.5 KB)
     e->genes_blocks_per_cu = (u32)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / per_block));
     e->use_lds_genes = true;
+    e->genes_one_family = best_n == n;
     return 0;
 }
 
@@ -641,6 +649,11 @@ extern "C" int fastf_engine_create(const fastf_engine_config_t* cfg, fastf_engin
         // the push path stages blocked and runs the streaming K1b whenever the engine can (FASTF_PUSH_TILE_FORM=1: SoA staging and
         // the tile form, as lists that keep the gene table in L2, wide keys and sharded engines use)
         e->stream_mode = e->use_lds_genes && !e->wide && e->n_shards == 1 && !getenv("FASTF_NO_STREAM_K1B") && !getenv("FASTF_PUSH_TILE_FORM");
+        {
+            const char* bw = getenv("FASTF_BLOCK_WIDE");
+            e->narrow = e->stream_mode && e->genes_one_family && e->lds_genes.vmin + e->lds_genes.range <= 0xFFFFFFFFull &&
+                        e->L.umi_bits <= 24 && !(bw && bw[0] == '1');
+        }
     } while (0);
     if (rc) { fastf_engine_destroy(e); return 1; }
     *out = e;
@@ -822,7 +835,7 @@ static int launch_probe_cells(fastf_engine* e, const u64* cb, u64 n, u64* d_tota
                               u64* d_running = nullptr, u64* d_base_out = nullptr, void* blk = nullptr) {
     if (reserve_workspace(e, blk ? 0 : n, 0, n)) return 1;
     const u32 tiles = (u32)((n + K1_TILE - 1) / K1_TILE);
-    const CellOut cout = blk ? CellOut{blk, blk_run_bytes(e->cell16)} : CellOut{e->d_cellidx.p, 0u};
+    const CellOut cout = blk ? CellOut{blk, blk_run_bytes(e->cell16, e->narrow), blk_cell_off(e->narrow)} : CellOut{e->d_cellidx.p, 0u, 0u};
     t_begin(e, s);
     if (e->use_lds_cells) {                          // tile counts are all-zero here: scan_tiles_kernel clears what it reads
         const u32 grid = std::min<u32>(e->cells_blocks_per_cu * g_cu_count, (tiles + 1) / 2);
@@ -866,9 +879,19 @@ extern "C" int fastf_dev_block_bytes(const fastf_engine_t* e, uint64_t n, uint64
     if (!e || !bytes) return set_err("null argument");
     *bytes = 0;
     if (e->multi || e->wide || !stream_k1b_possible(e)) return 0;
-    *bytes = ((n + BLK_RECS - 1) / BLK_RECS) * (u64)blk_run_bytes(e->cell16);
+    *bytes = ((n + BLK_RECS - 1) / BLK_RECS) * (u64)blk_run_bytes(e->cell16, e->narrow);
     return 0;
 } FASTF_CATCH_INT
+
+// the engine's layout (wide or narrow runs) from device-resident SoA
+static void launch_block_records(const fastf_engine* e, const u64* gx, const u32* umi, const u32* meta, u64 n, void* blk, hipStream_t s) {
+    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
+    const dim3 grid((u32)std::min<u64>((units + 3) / 4, 16ull * g_cu_count));
+    if (e->narrow) hipLaunchKernelGGL(block_records_kernel<true>, grid, dim3(256), 0, s, gx, umi, meta, n, (unsigned char*)blk,
+                                      blk_run_bytes(e->cell16, true), e->lds_genes.family, e->L);
+    else hipLaunchKernelGGL(block_records_kernel<false>, grid, dim3(256), 0, s, gx, umi, meta, n, (unsigned char*)blk,
+                            blk_run_bytes(e->cell16, false), 0u, e->L);
+}
 
 extern "C" int fastf_dev_block_records(fastf_engine_t* e, const uint64_t* d_gx_key, const uint32_t* d_umi, const uint32_t* d_meta,
                                        uint64_t n, void* d_blocked, void* stream) FASTF_TRY {
@@ -876,9 +899,7 @@ extern "C" int fastf_dev_block_records(fastf_engine_t* e, const uint64_t* d_gx_k
     if (e->multi) return set_err("fastf_dev_block_records: device-level calls take a single-device engine");
     HIP_OK(hipSetDevice(e->device));
     if (n == 0) return 0;
-    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    hipLaunchKernelGGL(block_records_kernel, dim3((u32)std::min<u64>((units + 3) / 4, 16ull * g_cu_count)), dim3(256), 0, (hipStream_t)stream,
-                       (const u64*)d_gx_key, d_umi, d_meta, (u64)n, (unsigned char*)d_blocked, blk_run_bytes(e->cell16));
+    launch_block_records(e, (const u64*)d_gx_key, d_umi, d_meta, n, d_blocked, (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     dbg_sync((hipStream_t)stream, "block_records");
     return 0;
@@ -1087,7 +1108,8 @@ static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32
                         app ? app->slot0 : 0ull, e->skip_bits};
         // compile-time: roomy (one workgroup per CU: 128 VGPRs), width of the cell scratch, form of the gene image
         const int variant = (e->genes_blocks_per_cu >= 2 ? 0 : 4) | (e->cell16 ? 2 : 0) | (e->lds_genes.direct ? 1 : 0);
-#define FPS(R, C, D) do { if (blk) hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, true>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); \
+#define FPS(R, C, D) do { if (blk && e->narrow) hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, true, true>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); \
+                          else if (blk) hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, true>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); \
                           else hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, false>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); } while (0)
         switch (variant) {
         case 0: FPS(false, false, false); break; case 1: FPS(false, false, true); break;
@@ -1475,8 +1497,11 @@ static const char* err_bits_text(u64 bits) {
 }
 
 // SoA: cb | gx | umi | meta (+ 4: umi_ext of engines with umi_max_bases > 16); blocked: cb | one run of 4608 or 5120 bytes per 256
-// records (8 + 20 bytes per record at most, and the last run whole)
-static size_t stage_bytes(u64 cap) { return (size_t)cap * (8 + 8 + 4 + 4 + 4) + 8192; }
+// records (8 + 20 bytes per record at most, and the last run whole); narrow (device side): cb | runs of 2560 or 3072 bytes (12
+// bytes per record at most) | from cap * 20 + 4096 on a SoA landing area gx | umi | meta for host batches (block_records_kernel
+// reads it)
+static size_t stage_bytes(u64 cap, bool narrow = false) { return (size_t)cap * (8 + 8 + 4 + 4 + 4 + (narrow ? 8 : 0)) + 8192; }
+static size_t narrow_landing(u64 cap) { return (size_t)cap * 20 + 4096; }
 
 // Streaming push path.
 //   chunk i:  [host staging, pageable input only]  ->  H2D on s_copy  ->  K1a + scan + K1b on s_compute
@@ -1487,7 +1512,7 @@ static size_t stage_bytes(u64 cap) { return (size_t)cap * (8 + 8 + 4 + 4 + 4) + 
 
 static int slot_alloc(fastf_engine* e, fastf_engine::Slot& sl, bool need_host_stage) {
     if (!sl.h_small) HIP_OK(hipHostMalloc((void**)&sl.h_small, SM_WORDS * sizeof(u64), hipHostMallocDefault));
-    if (sl.d_stage.ensure(stage_bytes(e->batch_cap))) return 1;
+    if (sl.d_stage.ensure(stage_bytes(e->batch_cap, e->narrow))) return 1;
     if (need_host_stage && !sl.h_stage) HIP_OK(hipHostMalloc(&sl.h_stage, stage_bytes(e->batch_cap), hipHostMallocDefault));
     return 0;
 }
@@ -1677,7 +1702,27 @@ static int push_chunk(fastf_engine* e, const fastf_batch_t* b, size_t off, size_
     // (hipMemcpyDefault: a "pinned" batch may also be DEVICE memory — the records the device-side BAM front end packed)
     HIP_OK(hipMemcpyAsync(ds, s_cb, n * 8, hipMemcpyDefault, sc));
     char* const blk = ds + cap * 8;                                     // stream mode: the blocked runs behind the cb keys
-    if (e->stream_mode) {
+    if (e->stream_mode && e->narrow) {
+        // NARROW runs are not a copy of the batch: block_records_kernel<true> writes them, on the copy stream (ev_copy and
+        // fastf_engine_wait_input keep covering every read of the batch).  Device-resident batches (the GPU front end) are read
+        // where they are; host batches land as plain copies in the SoA landing area of the chunk first.
+        const u64* n_gx = (const u64*)s_gx; const u32* n_umi = (const u32*)s_umi; const u32* n_meta = (const u32*)s_meta;
+        bool on_device = false;
+        if (pinned) {
+            hipPointerAttribute_t a; memset(&a, 0, sizeof a);
+            if (hipPointerGetAttributes(&a, s_gx) == hipSuccess) on_device = a.type == hipMemoryTypeDevice;
+            else (void)hipGetLastError();
+        }
+        if (!on_device) {
+            char* const land = ds + narrow_landing(cap);
+            HIP_OK(hipMemcpyAsync(land, s_gx, n * 8, hipMemcpyDefault, sc));
+            HIP_OK(hipMemcpyAsync(land + cap * 8, s_umi, n * 4, hipMemcpyDefault, sc));
+            HIP_OK(hipMemcpyAsync(land + cap * 12, s_meta, n * 4, hipMemcpyDefault, sc));
+            n_gx = (const u64*)land; n_umi = (const u32*)(land + cap * 8); n_meta = (const u32*)(land + cap * 12);
+        }
+        launch_block_records(e, n_gx, n_umi, n_meta, n, blk, sc);
+        HIP_OK(hipGetLastError());
+    } else if (e->stream_mode) {
         // The batch lands in the BLOCKED layout (umi_kernels.hpp: per 256 records one run gx | umi | meta | cell scratch): three
         // pitched copies — a row is one unit's slice of an array, the destination pitch the run — and three plain ones for the
         // records of a last, partial unit.  Same rate as plain copies (tools/h2d_2d_probe.hip).

@@ -446,6 +446,12 @@ __device__ __forceinline__ bool umi_overflows_flat(const KeyLayout L, u32 umi, u
     const u32 len = (meta & META_LEN_MASK) >> META_LEN_SHIFT;
     return ((meta & META_UMI_TOOLONG) != 0) | (((meta & META_UMI_NONNULL) != 0) & ((len > L.umi_max_bytes) | ((umi & tail) != 0)));
 }
+// the same on a NARROW run's merged word um32: its low byte holds the flags, the tail test was folded into META_UMI_TOOLONG
+// when the run was written (block_records_kernel<true>)
+__device__ __forceinline__ bool umi_overflows_narrow(const KeyLayout L, u32 um) {
+    const u32 len = (um & META_LEN_MASK) >> META_LEN_SHIFT;
+    return ((um & META_UMI_TOOLONG) != 0) | (((um & META_UMI_NONNULL) != 0) & (len > L.umi_max_bytes));
+}
 
 // the rest of a wide key (everything below the group word) from a UMI of up to 32 bases in 64 bits (first base on top)
 __device__ __forceinline__ u64 make_val64(const KeyLayout L, u64 umi, u32 meta) {
@@ -625,13 +631,22 @@ static_assert(K1_THREADS == 512 && K1_IPT == 8, "K1a layout: 8 waves x 8 items x
 // four arrays (profiles/r4_notes/hbm_probe_blocked_layout.txt; a run with dead bytes in it — the cb slice kept inside —
 // loses the gain, which is why cb stays an array of its own).
 constexpr u32 BLK_RECS = 256, BLK_GX = 0, BLK_UMI = 2048, BLK_META = 3072, BLK_CELL = 4096;
-__host__ __device__ __forceinline__ u32 blk_run_bytes(bool c16) { return BLK_CELL + (c16 ? 2u : 4u) * BLK_RECS; }
-// where K1a leaves the cell index of record idx: a plain array (run == 0) or the scratch slices of a blocked buffer
-struct CellOut { void* p; u32 run; };
+// NARROW runs (engines whose listed features are one ID family with numbers below 2^32 - 1 and UMIs of at most 12 bases):
+//   gx32 u32[256] | um32 u32[256] | cell scratch   = 2560 (3072) bytes, 10 (12) instead of 18 (20) bytes per record.
+//   gx32  0: cannot match (key 0, a key of another family, a number of 2^32 - 1 or more); else the family key's number + 1
+//   um32  (umi & ~0xFF) | (meta & 0xFF): the UMI's top 24 bits (all a key of 12 bases reads) and the FASTF_META_* byte; a
+//         record whose UMI the wide form rejects (umi_overflows_flat) carries META_UMI_TOOLONG instead
+// block_records_kernel<true> writes them; K1b (filter_pack_stream_kernel<.., NARROW>) sees every record as the wide form does.
+constexpr u32 NBLK_GX = 0, NBLK_UM = 1024, NBLK_CELL = 2048;
+__host__ __device__ __forceinline__ u32 blk_cell_off(bool narrow) { return narrow ? NBLK_CELL : BLK_CELL; }
+__host__ __device__ __forceinline__ u32 blk_run_bytes(bool c16, bool narrow = false) { return blk_cell_off(narrow) + (c16 ? 2u : 4u) * BLK_RECS; }
+// where K1a leaves the cell index of record idx: a plain array (run == 0) or the scratch slices of a blocked buffer (at
+// byte `off` of each run)
+struct CellOut { void* p; u32 run; u32 off; };
 __device__ __forceinline__ void put_cell(const CellOut o, bool c16, u64 idx, u32 v) {
     unsigned char* at = reinterpret_cast<unsigned char*>(o.p);
     u64 i = idx;
-    if (o.run) { at += (idx / BLK_RECS) * o.run + BLK_CELL; i = idx % BLK_RECS; }
+    if (o.run) { at += (idx / BLK_RECS) * o.run + o.off; i = idx % BLK_RECS; }
     if (c16) reinterpret_cast<unsigned short*>(at)[i] = (unsigned short)v; else reinterpret_cast<u32*>(at)[i] = v;
 }
 __device__ __forceinline__ u32 get_cell(const void* __restrict__ in, bool c16, u64 idx) {
@@ -828,7 +843,7 @@ __global__ __launch_bounds__(1024, TWO_PER_CU ? 8 : 4) void probe_cells_lds_kern
         if (whole && cell_dst.run) {
             // blocked buffer: the chunk is two units; pairs 0, 1 lie in the first, pairs 2, 3 in the second (scalar unit base)
             static_assert(K1_IPT * WAVE == 2 * (int)BLK_RECS && PAIRS == 4, "a K1a chunk is two blocked units");
-            unsigned char* const u0 = reinterpret_cast<unsigned char*>(cell_out) + (base / BLK_RECS) * cell_dst.run + BLK_CELL;
+            unsigned char* const u0 = reinterpret_cast<unsigned char*>(cell_out) + (base / BLK_RECS) * cell_dst.run + cell_dst.off;
 #pragma unroll
             for (int j = 0; j < PAIRS; ++j) {
                 unsigned char* const ub = u0 + (j >> 1) * cell_dst.run;
@@ -1178,8 +1193,11 @@ __device__ __forceinline__ u32 row16_sum_lane15(u32 x) {
 // C16: the cell scratch holds u16 entries; DIRECT: the gene image is the dense u16 table.  Both are compile-time so that
 // the loop is straight-line code: with run-time flags every load sat in its own branch, with waits between them
 // (PMC on the configs[2] shape: 430 vector + 325 scalar instructions per 256 records, the vector ALU busy 60 % of the kernel).
-template <bool ROOMY, bool C16, bool DIRECT, bool BLOCKED = false>
+// NARROW (with BLOCKED): the runs are gx32 | um32 | scratch (see NBLK_GX): a 32-bit key per record whose family the blocking
+// step has checked, one word for UMI and flags — two registers fewer per record in each register set, no L2 table probe.
+template <bool ROOMY, bool C16, bool DIRECT, bool BLOCKED = false, bool NARROW = false>
 __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 : 2 * K1S_THREADS / (4 * WAVE)) void filter_pack_stream_kernel(const PackParams p, const StreamParams sp) {
+    static_assert(BLOCKED || !NARROW, "the narrow records exist as blocked runs only");
     constexpr int THREADS = ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, WAVES = THREADS / WAVE;
     __shared__ u64 s_tot[3];
     __shared__ u32 s_cursor[K1S_SUB], s_err;
@@ -1226,37 +1244,42 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
     u32 u = blockIdx.x * (u32)WAVES + (u32)w;                              // scalar
     // one unit's inputs apart from gx: the records' cell / umi / meta, the unit's decision words, and (wave-uniform) the
     // decisions left in the stream from its first rank on, that rank's bit in its word, the records the unit holds
-    struct UnitRegs { u32 cell[K1S_IPT], umi[K1S_IPT], meta[K1S_IPT], dw, avail, sbit, nvalid; };
+    // (NARROW: umi[] holds the merged word um32, meta[] is not used)
+    struct UnitRegs { u32 cell[K1S_IPT], umi[K1S_IPT], meta[NARROW ? 1 : K1S_IPT], dw, avail, sbit, nvalid; };
     UnitRegs ra, rb;                                                       // the unit in work and the one after it, by turns
-    u64 gxk[K1S_IPT];
+    using GxT = std::conditional_t<NARROW, u32, u64>;
+    GxT gxk[K1S_IPT];
     u64 tb = 0; u32 hha = 0;                                               // small inputs of the unit after it (tb: the same value in every lane)
     u32 zlane = 0;
     asm volatile("" : "+v"(zlane));                                        // an opaque zero per lane, see small_inputs
     // records a unit holds (0: none), and the unit whose memory stands in for it when it holds none
     auto records_of = [&](const u32 uu) { return uu < n_live ? (u32)(p.n - (u64)uu * K1S_UNIT < (u64)K1S_UNIT ? p.n - (u64)uu * K1S_UNIT : (u64)K1S_UNIT) : 0u; };
-    auto unit_run = [&](const u32 uu) { return BLOCKED ? p.blk + (u64)uu * blk_run_bytes(C16) : nullptr; };
+    auto unit_run = [&](const u32 uu) { return BLOCKED ? p.blk + (u64)uu * blk_run_bytes(C16, NARROW) : nullptr; };
+    auto meta_of = [&](const UnitRegs& r, const int j) -> u32 { if constexpr (NARROW) return r.umi[j]; else return r.meta[j]; };
     // (nv >= 1 records of unit uu exist; a blocked run is whole even when its unit is not)
-    auto load_gx = [&](u64 (&g)[K1S_IPT], const u32 uu, const u32 nv) {
-        const u64* const gx_u = BLOCKED ? reinterpret_cast<const u64*>(unit_run(uu) + BLK_GX) : p.gx + (u64)uu * K1S_UNIT;
+    auto load_gx = [&](GxT (&g)[K1S_IPT], const u32 uu, const u32 nv) {
+        const GxT* gx_u;
+        if constexpr (BLOCKED) gx_u = reinterpret_cast<const GxT*>(unit_run(uu) + (NARROW ? NBLK_GX : BLK_GX));
+        else gx_u = p.gx + (u64)uu * K1S_UNIT;
 #pragma unroll
         for (int j = 0; j < K1S_IPT; ++j) {
             const u32 o = (u32)j * WAVE + (u32)lane;
             g[j] = ld_once<NT>(gx_u + (BLOCKED || o < nv ? o : nv - 1u));
         }
     };
-    auto load_rest = [&](u32 (&c)[K1S_IPT], u32 (&um)[K1S_IPT], u32 (&me)[K1S_IPT], const u32 uu, const u32 nv) {
+    auto load_rest = [&](u32 (&c)[K1S_IPT], u32 (&um)[K1S_IPT], u32 (&me)[NARROW ? 1 : K1S_IPT], const u32 uu, const u32 nv) {
         const unsigned char* const run = unit_run(uu);
         const u64 base = (u64)uu * K1S_UNIT;
-        const u32* const umi_u = BLOCKED ? reinterpret_cast<const u32*>(run + BLK_UMI) : p.umi + base;
+        const u32* const umi_u = BLOCKED ? reinterpret_cast<const u32*>(run + (NARROW ? NBLK_UM : BLK_UMI)) : p.umi + base;
         const u32* const meta_u = BLOCKED ? reinterpret_cast<const u32*>(run + BLK_META) : p.meta + base;
-        const unsigned short* const c16_u = BLOCKED ? reinterpret_cast<const unsigned short*>(run + BLK_CELL) : reinterpret_cast<const unsigned short*>(p.cell) + base;
-        const u32* const c32_u = BLOCKED ? reinterpret_cast<const u32*>(run + BLK_CELL) : reinterpret_cast<const u32*>(p.cell) + base;
+        const unsigned short* const c16_u = BLOCKED ? reinterpret_cast<const unsigned short*>(run + blk_cell_off(NARROW)) : reinterpret_cast<const unsigned short*>(p.cell) + base;
+        const u32* const c32_u = BLOCKED ? reinterpret_cast<const u32*>(run + blk_cell_off(NARROW)) : reinterpret_cast<const u32*>(p.cell) + base;
 #pragma unroll
         for (int j = 0; j < K1S_IPT; ++j) {
             const u32 o = (u32)j * WAVE + (u32)lane, oc = BLOCKED || o < nv ? o : nv - 1u;
             c[j] = C16 ? (u32)ld_once<NT>(c16_u + oc) : ld_once<NT>(c32_u + oc);
             um[j] = ld_once<NT>(umi_u + oc);
-            me[j] = ld_once<NT>(meta_u + oc);
+            if constexpr (!NARROW) me[j] = ld_once<NT>(meta_u + oc);
         }
     };
     // place a unit in the decision stream from its tile's small inputs and ask for its decision words: bits rank0 .. rank0 +
@@ -1300,7 +1323,7 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
     // register sets exchanged — a copy at the end of the body would have to wait for the loads it copies
     auto one_unit = [&](UnitRegs& cur, UnitRegs& nxt, auto sub_c) {
         constexpr int SUB = decltype(sub_c)::value;                        // which of the workgroup's regions this unit's keys go to
-        u32 (&cell)[K1S_IPT] = cur.cell; u32 (&umi)[K1S_IPT] = cur.umi; u32 (&meta)[K1S_IPT] = cur.meta;
+        u32 (&cell)[K1S_IPT] = cur.cell; u32 (&umi)[K1S_IPT] = cur.umi;
         const u32 dw = cur.dw, avail = cur.avail, sbit = cur.sbit, nvalid = cur.nvalid;
         const u32 un = u + ustep;                                          // the unit after this one
         const u32 nv_n = un < n_units ? records_of(un) : 0u;
@@ -1342,12 +1365,20 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
         u32 feat[K1S_IPT];
 #pragma unroll
         for (int j = 0; j < K1S_IPT; ++j) {
-            const u64 k = gxk[j];
-            const bool want = (cell[j] != 0) & ((meta[j] & META_XF_OK) != 0) & (k != 0);
-            const bool fam = (u32)(k >> 44) == p.genes.family;
-            const u64 v = (k & 0xFFFFFFFFFFFull) - p.genes.vmin;                         // wraps to huge when below vmin
-            const bool in = want & fam & (v < p.genes.range);
-            const u32 vi = in ? (u32)v : 0u;
+            const GxT k = gxk[j];
+            const bool want = (cell[j] != 0) & ((meta_of(cur, j) & META_XF_OK) != 0) & (k != 0);
+            bool fam = true, in;
+            u32 vi;
+            if constexpr (NARROW) {                                                      // the family was checked when the run was written
+                const u32 v = (u32)k - 1u - (u32)p.genes.vmin;                           // (vmin + range < 2^32: wraps past range below vmin)
+                in = want & (v < (u32)p.genes.range);
+                vi = in ? v : 0u;
+            } else {
+                fam = (u32)(k >> 44) == p.genes.family;
+                const u64 v = (k & 0xFFFFFFFFFFFull) - p.genes.vmin;                     // wraps to huge when below vmin
+                in = want & fam & (v < p.genes.range);
+                vi = in ? (u32)v : 0u;
+            }
             u32 f;
             if (DIRECT) f = s_direct[vi];
             else {
@@ -1356,7 +1387,9 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
                 f = ((wd >> bit) & 1u) ? s_perm[pi] : 0u;
             }
             f = in ? f : 0u;
-            if (__ballot(want & !fam)) { if (want & !fam) f = table_probe(p.feats, k); }  // other id families / escaped strings
+            if constexpr (!NARROW) {
+                if (__ballot(want & !fam)) { if (want & !fam) f = table_probe(p.feats, k); }  // other id families / escaped strings
+            }
             feat[j] = f;
         }
         // gx has done its work: the gx of the unit after this one into its registers
@@ -1370,9 +1403,11 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
         for (int j = 0; j < K1S_IPT; ++j) {
             bool alive = (cell[j] != 0) & (keep[j] != 0);
             w_samp += (u32)__popcll(__ballot(alive));                                      // E6
-            alive = alive & (feat[j] != 0) & ((meta[j] & META_HAS_UB) != 0);
-            if (__ballot(alive & umi_overflows_flat(p.L, umi[j], meta[j]))) errs |= (u32)ERR_UMI_TOOLONG;      // (uniform branch, never taken on good data)
-            key[j] = make_key_flat(p.L, cell[j], feat[j], umi[j], meta[j]);                // (stored where alive only)
+            const u32 mj = meta_of(cur, j);                                                // (NARROW: the merged word, flags in its low byte)
+            alive = alive & (feat[j] != 0) & ((mj & META_HAS_UB) != 0);
+            const bool ovf = NARROW ? umi_overflows_narrow(p.L, umi[j]) : umi_overflows_flat(p.L, umi[j], mj);
+            if (__ballot(alive & ovf)) errs |= (u32)ERR_UMI_TOOLONG;                        // (uniform branch, never taken on good data)
+            key[j] = make_key_flat(p.L, cell[j], feat[j], umi[j], mj);                     // (stored where alive only; umi >> (32 - umi_bits) drops the flags)
             em[j] = __ballot(alive);
             n_keys += (u32)__popcll(em[j]);
         }
@@ -1431,9 +1466,11 @@ __global__ __launch_bounds__(ROOMY ? K1S_THREADS_ROOMY : K1S_THREADS, ROOMY ? 4 
 }
 
 // SoA on the device -> blocked runs (callers that hold device-resident SoA and want the blocked K1 path; the push path lands
-// its host batches in this layout with pitched copies instead).  One wave per unit and round.
+// its host batches in the wide layout with pitched copies instead, and runs this kernel for the narrow one).  One wave per unit
+// and round.  NARROW: gx32 / um32 (see NBLK_GX) from the family constant and the key layout only — no list lookup here.
+template <bool NARROW>
 __global__ __launch_bounds__(256) void block_records_kernel(const u64* __restrict__ gx, const u32* __restrict__ umi, const u32* __restrict__ meta,
-                                                            u64 n, unsigned char* __restrict__ blk, u32 run) {
+                                                            u64 n, unsigned char* __restrict__ blk, u32 run, u32 family, const KeyLayout L) {
     const u64 units = (n + BLK_RECS - 1) / BLK_RECS, waves = (u64)gridDim.x * (blockDim.x / WAVE);
     const int lane = lane_id();
     for (u64 u = (u64)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6); u < units; u += waves) {
@@ -1443,9 +1480,17 @@ __global__ __launch_bounds__(256) void block_records_kernel(const u64* __restric
             const u32 o = (u32)j * WAVE + (u32)lane;
             const u64 i = u * BLK_RECS + o;
             const bool in = i < n;
-            reinterpret_cast<u64*>(r + BLK_GX)[o] = in ? gx[i] : 0;
-            reinterpret_cast<u32*>(r + BLK_UMI)[o] = in ? umi[i] : 0;
-            reinterpret_cast<u32*>(r + BLK_META)[o] = in ? meta[i] : 0;
+            if constexpr (NARROW) {
+                const u64 k = in ? gx[i] : 0;
+                const u32 um = in ? umi[i] : 0, me = in ? meta[i] : 0;
+                const u64 v = k & 0xFFFFFFFFFFFull;
+                reinterpret_cast<u32*>(r + NBLK_GX)[o] = ((k != 0) & ((u32)(k >> 44) == family) & (v < 0xFFFFFFFFull)) ? (u32)v + 1u : 0u;
+                reinterpret_cast<u32*>(r + NBLK_UM)[o] = (um & ~0xFFu) | (me & 0xFFu) | (umi_overflows_flat(L, um, me) ? META_UMI_TOOLONG : 0u);
+            } else {
+                reinterpret_cast<u64*>(r + BLK_GX)[o] = in ? gx[i] : 0;
+                reinterpret_cast<u32*>(r + BLK_UMI)[o] = in ? umi[i] : 0;
+                reinterpret_cast<u32*>(r + BLK_META)[o] = in ? meta[i] : 0;
+            }
         }
     }
 }

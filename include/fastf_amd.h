@@ -311,8 +311,16 @@ int fastf_dev_probe_capacity(const fastf_engine_t *e, uint64_t n, uint64_t *key_
  * the run) plus three plain copies for a last partial unit, umi_engine.hip push_chunk — and run the same K1a + streaming K1b
  * on it as the device-level calls below; engines whose gene list stays in L2, keys wider than 64 bits and sharded engines
  * stage SoA and run the tile form of K1b.  Device-resident SoA gets here through fastf_dev_block_records.
- * fastf_dev_block_bytes: size of the buffer for n records; 0 = this engine cannot run the streaming K1b (gene list not in
- * LDS, FASTF_NO_STREAM_K1B): use the SoA form. */
+ * NARROW runs: an engine in stream mode whose listed features all belong to the one LDS gene family, with numbers below
+ * 2^32 - 1, and whose UMIs have at most 12 bases uses per unit
+ *     gx32 u32[256] | um32 u32[256] | cell scratch (u16[256] or u32[256])
+ * of 2560 (3072) bytes: gx32 = the family key's number + 1 (0: key 0, another family, a number of 2^32 - 1 or more),
+ * um32 = (umi & ~0xFF) | the FASTF_META_* byte (FASTF_META_UMI_TOOLONG also where the UMI has bits a 12-base key cannot hold).
+ * The runs are written by fastf_dev_block_records, and by the push path with a kernel on the copy stream after plain copies
+ * (host batches) or straight from device-resident batches.  The layout is fixed at fastf_engine_create; FASTF_BLOCK_WIDE=1
+ * keeps the wide runs.
+ * fastf_dev_block_bytes: size of the buffer for n records (a multiple of 2560, 3072, 4608 or 5120: the layout in use);
+ * 0 = this engine cannot run the streaming K1b (gene list not in LDS, FASTF_NO_STREAM_K1B): use the SoA form. */
 int fastf_dev_block_bytes(const fastf_engine_t *e, uint64_t n, uint64_t *bytes);
 int fastf_dev_block_records(fastf_engine_t *e, const uint64_t *d_gx_key, const uint32_t *d_umi, const uint32_t *d_meta,
                             uint64_t n, void *d_blocked, void *stream);

@@ -2,6 +2,7 @@
 // (gx 8 B, umi 4 B, meta 4 B, cell scratch 2 B = 18 B) and one 8-byte store for every fifth record, over N records:
 //   A  one record per lane and load (8-, 4-, 4- and 2-byte loads; what filter_pack_stream_kernel issues), R rows in flight
 //   B  four consecutive records per lane (two 16-byte loads of gx, one each of umi and meta, one 8-byte load of the scratch)
+//   C  the same 18 bytes from 4608-byte blocked runs;  D  K1b's blocked mix with its decision words, 18 B against 10 B runs
 // Best of 6 launches each.  hipcc --offload-arch=gfx950 -O3 -o build/hbm_probe_streams tools/hbm_probe_streams.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -94,6 +95,57 @@ __global__ __launch_bounds__(256) void k_blocked(const unsigned char* __restrict
         }
     }
 }
+// D: K1b's stream mix with the decision words, wide (18 B: 4608-byte runs gx u64 | umi u32 | meta u32 | cell u16) against
+//    narrow (10 B: 2560-byte runs gx32 u32 | um32 u32 | cell u16) — narrow loads, nt, row r of a unit = records 64 r + lane as
+//    in filter_pack_stream_kernel; each lane also reads one 32-bit decision word per unit (lanes 0..15 of a 16-word window, the
+//    way place_unit() asks for them: about one bit per record, H / 8 bytes) and the loads of the next unit are issued before
+//    the current one is consumed (two register sets)
+template <bool NARROW>
+__global__ __launch_bounds__(256) void k_blk_draw(const unsigned char* __restrict__ blk, const u32* __restrict__ dw, u64* __restrict__ out, size_t n) {
+    constexpr size_t RUN = NARROW ? 2560 : 4608;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 64, n_waves = (size_t)gridDim.x * blockDim.x / 64;
+    const int lane = threadIdx.x & 63;
+    const size_t units = n / 256;
+    struct R { u64 g[4]; u32 a[4], m[4], c[4], d; };
+    auto load = [&](R& x, size_t u) {
+        const unsigned char* b = blk + u * RUN;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = r * 64 + lane;
+            if constexpr (NARROW) {
+                x.g[r] = ld<true>((const u32*)b + o); x.a[r] = ld<true>((const u32*)(b + 1024) + o); x.m[r] = 0;
+                x.c[r] = ld<true>((const u16*)(b + 2048) + o);
+            } else {
+                x.g[r] = ld<true>((const u64*)b + o); x.a[r] = ld<true>((const u32*)(b + 2048) + o); x.m[r] = ld<true>((const u32*)(b + 3072) + o);
+                x.c[r] = ld<true>((const u16*)(b + 4096) + o);
+            }
+        }
+        x.d = dw[(u * 256 * 45 / 100) / 32 + (lane & 15)];                 // ~0.45 hits per record: one bit each
+    };
+    auto use = [&](const R& x, size_t u) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const size_t i = u * 256 + (size_t)r * 64 + lane;
+            if (i % 5 == 0) out[i / 5] = x.g[r] ^ ((u64)x.a[r] << 20) ^ x.m[r] ^ ((u64)x.c[r] << 40) ^ x.d;
+        }
+    };
+    if (wave >= units) return;
+    R ra, rb;
+    size_t u = wave;
+    load(ra, u);
+    while (u < units) {
+        const size_t un = u + n_waves;
+        load(rb, un < units ? un : u);
+        use(ra, u);
+        u = un;
+        if (u >= units) break;
+        const size_t un2 = u + n_waves;
+        load(ra, un2 < units ? un2 : u);
+        use(rb, u);
+        u = un2;
+    }
+}
+
 // K1a on the blocked layout: reads the unit's cb slice (2048 B at the front of a 6656-byte run), writes the 512-byte scratch over its front
 template <bool NT>
 __global__ __launch_bounds__(1024) void k_k1a_blocked(unsigned char* __restrict__ blk, size_t n, size_t run) {
@@ -165,6 +217,18 @@ int main() {
             timeit("C blocked 4608-B runs, wide loads, nt", bytes, [&] { hipLaunchKernelGGL((k_blocked<true, true>), dim3(grid), dim3(256), 0, 0, blk, out, n, BLK); }, e0, e1);
             timeit("C' 6656-B runs (1536 dead bytes), narrow, nt", bytes, [&] { hipLaunchKernelGGL((k_blocked<false, true, true>), dim3(grid), dim3(256), 0, 0, blk, out, n, (size_t)6656); }, e0, e1);
             timeit("C' 6656-B runs (1536 dead bytes), wide, nt", bytes, [&] { hipLaunchKernelGGL((k_blocked<true, true, true>), dim3(grid), dim3(256), 0, 0, blk, out, n, (size_t)6656); }, e0, e1);
+        }
+        {   // D: K1b's stream mix with its decision words, 18 against 10 bytes per record
+            u32* dw; const size_t n_dw = n * 45 / 100 / 32 + 64;
+            OK(hipMalloc(&dw, n_dw * 4)); OK(hipMemset(dw, 6, n_dw * 4));
+            const size_t dbytes = n * 45 / 100 / 8, bw = n * 18 + n / 5 * 8 + dbytes, bn = n * 10 + n / 5 * 8 + dbytes;
+            printf("D: K1b mix with decision words: wide 4608-B runs %.2f GB, narrow 2560-B runs %.2f GB per launch\n", bw / 1e9, bn / 1e9);
+            for (int grid : {1024, 2048, 4096, 8192}) {
+                printf(" grid %d x 256\n", grid);
+                timeit("D wide 4608-B runs (18 B), nt, pipelined", bw, [&] { hipLaunchKernelGGL((k_blk_draw<false>), dim3(grid), dim3(256), 0, 0, blk, dw, out, n); }, e0, e1);
+                timeit("D narrow 2560-B runs (10 B), nt, pipelined", bn, [&] { hipLaunchKernelGGL((k_blk_draw<true>), dim3(grid), dim3(256), 0, 0, blk, dw, out, n); }, e0, e1);
+            }
+            OK(hipFree(dw));
         }
         printf("K1a on the blocked layout (cb slice read, scratch written over its front; 6656-B runs): %.2f GB per launch\n", n * 10 / 1e9);
         for (int grid : {256, 512, 1024}) {
