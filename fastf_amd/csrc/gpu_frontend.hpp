@@ -1,38 +1,33 @@
 // gpu_frontend.hpp — device side of the BAM front end: BGZF inflate of a whole reader window on the GPU.
-// Included by umi_engine.hip; the decoder itself is gpu_inflate.hpp (one wavefront per BGZF block).
+// Included by umi_engine.hip.  The decoder runs as two kernels: bgzf_decode_kernel, one LANE per BGZF block (gpu_inflate2.hpp:
+// literals in place, matches as tokens), then bgzf_resolve_kernel, one wave per block (below: the matches' copies).
 //
 // Reference step replaced: sam_read1() -> bgzf_read -> inflate, bam2db_ds.c:360 (htslib/zlib on one core).  In the
 // host reader (host_io.c) inflate is the longest stage of an end-to-end run on real-shaped BAMs even on 16 threads;
-// the window's compressed bytes are a quarter of the inflated ones, so they cross PCIe cheaply, are decoded by as many
-// wavefronts as the window has blocks, and come back into the reader's (pinned) window buffer, where the host goes on
-// with the record hop and the tag packing.  Every block's CRC-32 is still checked on the host, and a block the device
-// declines or gets wrong is inflated again by zlib — the same referee rule as for the host's own decoder.
+// the window's compressed bytes are a quarter of the inflated ones, so they cross PCIe cheaply, are decoded by those two
+// kernels, and come back into the reader's (pinned) window buffer, where the host goes on with the record hop and the tag
+// packing.  Every block's CRC-32 is still checked on the host, and a block the device declines or gets wrong is inflated
+// again by zlib — the same referee rule as for the host's own decoder.
 //
-// The window is cut into slices that run H2D -> kernel -> D2H on alternating streams, so the three stages of
+// The window is cut into slices that run H2D -> kernels -> D2H on alternating streams, so the three stages of
 // neighbouring slices overlap.
-#include "gpu_inflate.hpp"
 #include "gpu_inflate2.hpp"
 #include "gpu_records.hpp"
 
 struct GiBlock { u64 coff; u32 clen, isize; u64 uoff; u64 toff; };   // offsets into the slice's compressed / inflated bytes / token lists
 
-#ifndef FASTF_GI_MINBLOCKS
-#define FASTF_GI_MINBLOCKS 5      // waves per SIMD: 96 VGPRs instead of 109, twenty blocks per CU as the LDS allows (25.6 -> 26.0 GB/s)
-#endif
-__global__ __launch_bounds__(64, FASTF_GI_MINBLOCKS) void bgzf_inflate_kernel(const GiBlock* __restrict__ blk, u32 n_blk, const uint8_t* __restrict__ comp,
-                                                          uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
-    __shared__ gi::Work w;
-    const u32 b = blockIdx.x;
-    if (b >= n_blk) return;
-    const GiBlock k = blk[b];
-    int rc = 0;
-    if (k.isize) rc = gi::inflate_block(w, comp + k.coff, k.clen, out + k.uoff, k.isize);
-    if (gi_lane0()) status[b] = (uint8_t)rc;
-}
-
 // an aligned dword past the CU's L1 (agent scope: this wave's own stores of a round ago are in L2, not necessarily in its L1)
 __device__ __forceinline__ u32 gi_l2_load32(const uint8_t* p) {
     return __hip_atomic_load(reinterpret_cast<const u32*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// byte read that must see what this wave stored earlier: agent-scope load of the containing dword (bypasses the CU's L1)
+// (the dword's address is formed by pointer arithmetic, not through an integer: a pointer that went through uintptr_t has lost
+//  its address space and the access becomes a FLAT one, which counts on the LDS counter too — every wait for an LDS read then
+//  also waits for these loads)
+__device__ __forceinline__ uint8_t gi_coherent_load8(const uint8_t* p) {
+    const uint32_t k = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+    const uint32_t w = __hip_atomic_load(reinterpret_cast<const uint32_t*>(p - k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (uint8_t)(w >> (8 * k));
 }
 
 // ---- the two-kernel inflate (round 5; gpu_inflate2.hpp has the why) ----
@@ -209,7 +204,6 @@ struct fastf_gpuinf {
     uint8_t* h_status[NS] = {nullptr, nullptr, nullptr};
     DevBuf d_comp[NS], d_out[NS], d_blk[NS], d_status[NS];
     DevBuf d_tok[NS], d_tokn[NS];                                  // two-kernel inflate: the blocks' token lists and their lengths
-    bool wave_kernel = false;                                      // FASTF_GI_KERNEL=wave: round 4's one-wavefront-per-block kernel
     hipEvent_t ev0 = nullptr, ev_done[NS] = {nullptr, nullptr, nullptr};
     size_t first[NS + 1] = {0, 0, 0, 0}; size_t pending_n = 0; int pending_slices = 0;
     u64 n_blocks = 0, n_declined = 0;
@@ -229,8 +223,7 @@ extern "C" fastf_gpuinf_t* fastf_gpuinf_create(int device) FASTF_TRY {
     if (hipSetDevice(device) != hipSuccess) return nullptr;
     fastf_gpuinf* g = new fastf_gpuinf();
     g->device = device;
-    { const char* kv = getenv("FASTF_GI_KERNEL"); g->wave_kernel = kv && !strcmp(kv, "wave"); }
-    if (!g->wave_kernel && hipFuncSetAttribute((const void*)bgzf_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GI2_LDS_BYTES) != hipSuccess) {
+    if (hipFuncSetAttribute((const void*)bgzf_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GI2_LDS_BYTES) != hipSuccess) {
         delete g; set_err("cannot raise the dynamic LDS limit of bgzf_decode_kernel to %zu bytes", GI2_LDS_BYTES); return nullptr;
     }
     bool ok = hipEventCreate(&g->ev0) == hipSuccess;
@@ -266,9 +259,12 @@ extern "C" void fastf_gpuinf_stats(const fastf_gpuinf_t* g, uint64_t* n_blocks, 
 } FASTF_CATCH_VOID
 
 // blocks [0, n): compressed payload of block i at comp + blk[i].coff (clen bytes), inflated to out + blk[i].uoff (isize
-// bytes).  `comp` (readable 64 bytes past the last block) and `out` must be pinned host memory (fastf_pinned_alloc /
-// fastf_pinned_register): both directions are plain asynchronous copies.
-// submit() only queues the work — up to three slices on alternating streams, so that the H2D of one slice, the kernel of
+// bytes).  `comp` and `out` must be pinned host memory (fastf_pinned_alloc / fastf_pinned_register): both directions are
+// plain asynchronous copies.  Nothing past the last block is read: a slice copies exactly its blocks' bytes into d_comp, which
+// has 512 bytes behind them.  The decoder reads up to 192 bytes past a block (gi2::bits_open); past a slice's last block those
+// are d_comp's own tail, stale device memory that a well-formed stream never consumes — a malformed one is stopped by the
+// decoder's `pos > n_words` check, and the host's CRC-32 check of every block still applies.
+// submit() only queues the work — up to three slices on alternating streams, so that the H2D of one slice, the kernels of
 // another and the D2H of a third overlap — and returns; the caller is free to inflate other blocks on the host
 // meanwhile.  wait() returns when everything has landed: status[i] != 0 means the device declined block i (the caller
 // inflates it on the host); *device_ms = time from the first copy to the last.
@@ -347,7 +343,7 @@ extern "C" int fastf_gpuinf_reserve(fastf_gpuinf_t* g, size_t window_bytes, size
             g->d_crc[q].ensure(cap * sizeof(GrCrcBlock)))
             return 1;
         // token lists of a slice (a third to a half of a window): at most a token per three bytes (gi2::token_cap)
-        if (!g->wave_kernel && (g->d_tok[q].ensure((window_bytes / 2 / 3 + window_bytes / 2 / 256 + 4 * cap) * sizeof(u32)) || g->d_tokn[q].ensure(cap * sizeof(u32)))) return 1;
+        if (g->d_tok[q].ensure((window_bytes / 2 / 3 + window_bytes / 2 / 256 + 4 * cap) * sizeof(u32)) || g->d_tokn[q].ensure(cap * sizeof(u32))) return 1;
     }
     return 0;
 } FASTF_CATCH_INT
@@ -372,8 +368,8 @@ static int gpuinf_submit_impl(fastf_gpuinf_t* g, const unsigned char* comp, cons
         if (gpuinf_crc_table(g)) return 1;
     }
     constexpr int NS = fastf_gpuinf::NS;
-    // A block takes one wave several milliseconds (the decode is a chain of dependent table look-ups), so throughput is
-    // the number of blocks in flight over that latency: slices of at least 4096 blocks, at most NS of them.
+    // A block is one lane's serial work for milliseconds (its tokens are decoded one after the other: gpu_inflate2.hpp), so
+    // throughput is the number of blocks in flight over that latency: slices of at least 4096 blocks, at most NS of them.
     const size_t per = std::max<size_t>(std::min<size_t>(4096, n), (n + NS - 1) / NS);
     int n_slices = 0;
     for (size_t a = 0; a < n; a += per) g->first[n_slices++] = a;
@@ -385,7 +381,7 @@ static int gpuinf_submit_impl(fastf_gpuinf_t* g, const unsigned char* comp, cons
         const u64 c0 = blk[a].coff & ~(u64)63, c1 = blk[b - 1].coff + blk[b - 1].clen;
         const u64 u0 = blk[a].uoff; u64 u1 = u0;
         for (size_t i = a; i < b; ++i) u1 = std::max<u64>(u1, blk[i].uoff + blk[i].isize);
-        const size_t cbytes = (size_t)(c1 - c0) + 64, ubytes = (size_t)(u1 - u0);
+        const size_t cbytes = (size_t)(c1 - c0), ubytes = (size_t)(u1 - u0);
         if (gpuinf_slice_host(g, q, nb)) return 1;
         u64 n_tok_cap = 0;
         for (size_t i = a; i < b; ++i) {
@@ -395,7 +391,7 @@ static int gpuinf_submit_impl(fastf_gpuinf_t* g, const unsigned char* comp, cons
         if (g->d_comp[q].ensure(cbytes + 512) || (!keep && g->d_out[q].ensure(std::max<size_t>(ubytes, 64) + 64)) || g->d_blk[q].ensure(nb * sizeof(GiBlock)) ||
             g->d_status[q].ensure(nb))
             return 1;
-        if (!g->wave_kernel && (g->d_tok[q].ensure((size_t)n_tok_cap * sizeof(u32)) || g->d_tokn[q].ensure(nb * sizeof(u32)))) return 1;
+        if (g->d_tok[q].ensure((size_t)n_tok_cap * sizeof(u32)) || g->d_tokn[q].ensure(nb * sizeof(u32))) return 1;
         uint8_t* const d_dst = keep ? (uint8_t*)g->d_win[keep_parity].p + u0 : (uint8_t*)g->d_out[q].p;     // block i lands at d_dst + (uoff - u0)
         hipStream_t s = g->s[q];
         if (q) HIP_OK(hipStreamWaitEvent(s, g->ev0, 0));
@@ -405,15 +401,10 @@ static int gpuinf_submit_impl(fastf_gpuinf_t* g, const unsigned char* comp, cons
         const uint8_t* d_src = (const uint8_t*)g->d_comp[q].p;
         HIP_OK(hipMemcpyAsync(g->d_comp[q].p, comp + c0, cbytes, hipMemcpyHostToDevice, s));
         HIP_OK(hipMemcpyAsync(g->d_blk[q].p, g->h_blk[q], nb * sizeof(GiBlock), hipMemcpyHostToDevice, s));
-        if (g->wave_kernel)
-            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((u32)nb), dim3(64), 0, s, (const GiBlock*)g->d_blk[q].p, (u32)nb,
-                               (const uint8_t*)g->d_comp[q].p, d_dst, (uint8_t*)g->d_status[q].p);
-        else {
-            hipLaunchKernelGGL(bgzf_decode_kernel, dim3((u32)((nb + GI2_LPW - 1) / GI2_LPW)), dim3(GI2_LPW), GI2_LDS_BYTES, s, (const GiBlock*)g->d_blk[q].p, (u32)nb,
-                               d_src, d_dst, (u32*)g->d_tok[q].p, (u32*)g->d_tokn[q].p, (uint8_t*)g->d_status[q].p);
-            hipLaunchKernelGGL(bgzf_resolve_kernel, dim3((u32)((nb + 3) / 4)), dim3(256), 0, s, (const GiBlock*)g->d_blk[q].p, (u32)nb, d_dst,
-                               (const u32*)g->d_tok[q].p, (const u32*)g->d_tokn[q].p, (const uint8_t*)g->d_status[q].p);
-        }
+        hipLaunchKernelGGL(bgzf_decode_kernel, dim3((u32)((nb + GI2_LPW - 1) / GI2_LPW)), dim3(GI2_LPW), GI2_LDS_BYTES, s, (const GiBlock*)g->d_blk[q].p, (u32)nb,
+                           d_src, d_dst, (u32*)g->d_tok[q].p, (u32*)g->d_tokn[q].p, (uint8_t*)g->d_status[q].p);
+        hipLaunchKernelGGL(bgzf_resolve_kernel, dim3((u32)((nb + 3) / 4)), dim3(256), 0, s, (const GiBlock*)g->d_blk[q].p, (u32)nb, d_dst,
+                           (const u32*)g->d_tok[q].p, (const u32*)g->d_tokn[q].p, (const uint8_t*)g->d_status[q].p);
         HIP_OK(hipGetLastError());
         if (keep) {
             for (size_t i = a; i < b; ++i) g->h_crc[q][i - a] = GrCrcBlock{blk[i].uoff - u0, blk[i].isize, crc[i]};
@@ -455,7 +446,7 @@ extern "C" int fastf_gpuinf_run(fastf_gpuinf_t* g, const unsigned char* comp, co
     //  is told about the ranges instead of pinning them on the fly behind our back — umi_engine.hip, "pageable host memory")
     size_t cend = 0, uend = 0;
     for (size_t i = 0; i < n; ++i) { cend = std::max<size_t>(cend, blk[i].coff + blk[i].clen); uend = std::max<size_t>(uend, blk[i].uoff + blk[i].isize); }
-    const bool reg_c = g && n && cend && pin_reg((void*)comp, cend + 64) == 0;   // (+ 64: the submit copies the readable slack behind the last block too)
+    const bool reg_c = g && n && cend && pin_reg((void*)comp, cend) == 0;
     const bool reg_u = g && n && uend && pin_reg((void*)out, uend) == 0;
     int rc = fastf_gpuinf_submit(g, comp, blk, n, out);
     if (!rc) rc = fastf_gpuinf_wait(g, status, nullptr);

@@ -1,7 +1,7 @@
 // gpu_inflate2.hpp — raw DEFLATE (RFC 1951) of one BGZF block by ONE LANE, into literals-in-place + match tokens.
 //
 // The step in front of the bam2db hot path is sam_read1() through htslib/zlib (bam2db_ds.c:360): inflate of independent
-// <= 64 KiB BGZF blocks.  Round 2-4 ran one wavefront per block (gpu_inflate.hpp): all 64 lanes walk the same symbol loop on
+// <= 64 KiB BGZF blocks.  Round 2-4 ran one wavefront per block (a kernel since removed): all 64 lanes walk the same symbol loop on
 // the same bit buffer, so a block costs a whole wave ~82 instructions per token, and the probe of round 5
 // (profiles/r5_notes/inflate_probe_decode_vs_copy.txt) says that loop — not the copying — is what a block's 14 ms are made of.
 // Huffman decoding is serial per block, so the way to make it cheap is to decode MANY blocks per wave: here a block is one

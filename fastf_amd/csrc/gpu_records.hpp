@@ -1,5 +1,5 @@
 // gpu_records.hpp — device side of the BAM front end, second stage: the record hop, the tag extraction and the key packing
-// on the bytes the device has just inflated (gpu_inflate.hpp), so that those bytes never travel back to the host.
+// on the bytes the device has just inflated (gpu_frontend.hpp's two-kernel inflate), so that those bytes never travel back to the host.
 //
 // Reference steps replaced (bam2db_ds.c:360-417): sam_read1() walking the block_size chain, bam_aux_get() x4 / bam_aux2Z /
 // bam_aux2i scanning the aux block, hash() + encode_DNA() on the tag strings — restated on the host in host_io.c
