@@ -102,6 +102,8 @@ ABI_SYMBOLS = [
     "extract_bam", "read_bam", "free_CB_node", "print_CB_node", "cmd_crb", "cmd_extract",
     "fastf_crb_text", "fastf_extract_text", "fastf_keydict_intern", "fastf_keydict_decode",
     "fastf_taghist_create", "fastf_taghist_destroy", "fastf_taghist_push", "fastf_taghist_finish",
+    # freq
+    "fastf_freq_text", "fastf_taghist_reserve_device", "fastf_taghist_stream", "fastf_taghist_push_device",
 ]
 
 
@@ -237,6 +239,12 @@ def lib():
     L.fastf_taghist_finish.argtypes = [vp, C.POINTER(TagHistResult)]
     L.fastf_crb_text.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]
     L.fastf_extract_text.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64), C.POINTER(u64)]
+    L.fastf_freq_text.argtypes = [C.c_char_p, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]
+    L.fastf_taghist_reserve_device.argtypes = [vp, sz]
+    L.fastf_taghist_reserve_device.restype = vp
+    L.fastf_taghist_stream.argtypes = [vp]
+    L.fastf_taghist_stream.restype = vp
+    L.fastf_taghist_push_device.argtypes = [vp, vp, sz]
     L.fastf_bam_read_tags.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_int, vp, vp, sz, C.POINTER(u64)]
     L.fastf_bam_read_tags.restype = C.c_long
     L.read_bam.argtypes = [C.c_char_p]

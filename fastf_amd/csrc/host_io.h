@@ -125,6 +125,26 @@ void print_CB_node(CB_node *root, gzFile fp);
 /* pre-order of the insertion-order BST of m distinct strings with first-occurrence positions first[] (tag_cmds.c) */
 void fastf_tag_tree_preorder(const char *const *strs, const uint64_t *first, uint32_t m, uint32_t *order);
 
+/* freq (fastq_cmds.c): the device parse of FASTQ text windows (fastq_kernels.hpp) */
+typedef struct { uint64_t s, r; } fastf_fq_esc_t;        /* sequence line at global text offset s of read r: escape-form key */
+typedef struct fastf_fqparse fastf_fqparse_t;
+int  fastf_fqparse_create(fastf_taghist_t *h, size_t window_bytes, uint32_t L, fastf_fqparse_t **out);
+void fastf_fqparse_destroy(fastf_fqparse_t *p);
+int  fastf_fqparse_submit(fastf_fqparse_t *p, const unsigned char *staging, size_t len, uint64_t a, int last, uint64_t key_bound);
+int  fastf_fqparse_wait(fastf_fqparse_t *p, int parity, const fastf_fq_esc_t **esc, uint32_t *n_esc, uint64_t *n_nl,
+                        double *h2d_ms, double *parse_ms);
+int  fastf_fqparse_end(fastf_fqparse_t *p, uint64_t *n_nl, uint64_t *line_start, uint32_t *err, uint64_t *err_rec);
+int  fastf_fqparse_scatter(fastf_fqparse_t *p, const uint64_t *rk, size_t n, uint64_t key_cap);
+
+/* count.c:3-21 — the reference's cell barcode + UMI tree of an R1 FASTQ, node for node (malloc'ed nodes; the reference's
+ * free_tree_node releases it).  Declared here because of zlib's gzFile; the file is read with gzread on the calling thread. */
+node *cell_counts(gzFile R1_file, size_t len_cellbarcode, size_t len_umi);
+
+/* the rows of print_tree (filter.c:139-148) for strs[order[k]] / count[order[k]], and the insertion-order tree itself as the
+ * reference's malloc'ed nodes (tag_cmds.c) */
+int   fastf_tag_rows_text_(const char *const *strs, const uint64_t *count, const uint32_t *order, size_t m, char **txt, size_t *txt_len);
+node *fastf_tag_tree_nodes_(const char *const *strs, const uint64_t *first, const uint64_t *count, uint32_t m);
+
 /* text → gzip file (chunk-parallel members) */
 int fastf_write_gz_text(const char *path, const char *text, size_t len);
 

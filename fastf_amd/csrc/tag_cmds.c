@@ -207,6 +207,36 @@ static int rows_text(const tag_ent *ent, const uint32_t *order, size_t m, char a
     return rc;
 }
 
+/* the same two steps for another command (freq, fastq_cmds.c): rows "<strs[order[k]]>,<count[order[k]]>\n" (malloc'ed text),
+ * and the reference's tree itself, node for node (malloc'ed nodes and strings) */
+int fastf_tag_rows_text_(const char *const *strs, const uint64_t *count, const uint32_t *order, size_t m, char **txt, size_t *txt_len)
+{
+    tag_ent *ent = (tag_ent *)malloc((m ? m : 1) * sizeof *ent);
+    if (!ent) return 1;
+    for (size_t i = 0; i < m; i++) { ent[i].s = strs[i]; ent[i].first = 0; ent[i].count = count[i]; }
+    tbuf out = {0};
+    tb_put(&out, "", 0);
+    const int rc = rows_text(ent, order, m, '\n', &out);
+    free(ent);
+    if (rc) { free(out.p); return 1; }
+    *txt = out.p; *txt_len = out.len;
+    return 0;
+}
+static node *build_nodes(const tag_ent *ent, uint32_t m, uint32_t *sorted, int32_t *left, int32_t *right);
+node *fastf_tag_tree_nodes_(const char *const *strs, const uint64_t *first, const uint64_t *count, uint32_t m)
+{
+    tag_ent *ent = (tag_ent *)malloc((m ? m : 1) * sizeof *ent);
+    uint32_t *sorted = (uint32_t *)malloc((m ? m : 1) * sizeof *sorted);
+    int32_t *left = (int32_t *)malloc((m ? m : 1) * sizeof *left), *right = (int32_t *)malloc((m ? m : 1) * sizeof *right);
+    node *r = NULL;
+    if (ent && sorted && left && right) {
+        for (uint32_t i = 0; i < m; i++) { ent[i].s = strs[i]; ent[i].first = first[i]; ent[i].count = count[i]; }
+        r = build_nodes(ent, m, sorted, left, right);
+    }
+    free(ent); free(sorted); free(left); free(right);
+    return r;
+}
+
 /* ------------------------------------------------------------------ */
 /* BAM → device histogram                                              */
 /* ------------------------------------------------------------------ */

@@ -64,6 +64,27 @@ __global__ __launch_bounds__(256) void th_first_index_kernel(const u64* __restri
     }
 }
 
+// OR / AND of the present (non-zero) keys of [0, n), their number and the first present index: what fastf_taghist_push sums up
+// on the host while it stages, reduced on the device for keys that are already there.  out: {or, and, count, first}
+__global__ __launch_bounds__(256) void th_summary_kernel(const u64* __restrict__ keys, u64 n, u64* __restrict__ out) {
+    u64 o = 0, a = ~0ull, c = 0, f = ~0ull;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+        const u64 k = keys[i];
+        if (k) { o |= k; a &= k; c++; f = min(f, i); }
+    }
+#pragma unroll
+    for (u32 d = 32; d; d >>= 1) {
+        o |= __shfl_xor(o, d, 64); a &= __shfl_xor(a, d, 64); c += __shfl_xor(c, d, 64);
+        const u64 g = __shfl_xor(f, d, 64); f = min(f, g);
+    }
+    if ((threadIdx.x & 63) == 0 && c) {
+        atomicOr(&out[0], o);
+        atomicAnd(&out[1], a);
+        atomicAdd(&out[2], c);
+        atomicMin(&out[3], f);
+    }
+}
+
 }  // namespace fastf
 
 using namespace fastf;
@@ -108,6 +129,7 @@ struct fastf_taghist {
     int device = 0;
     bool pair = false, mode_set = false;
     u64 n = 0, cap = 0;                  // records pushed / capacity of d_k1, d_k2
+    u64 dev_reserved = 0;                // keys the device may have written behind n (fastf_taghist_reserve_device)
     DevBuf d_k1, d_k2;
     u64 or1 = 0, and1 = ~0ull, or2 = 0, and2 = ~0ull;      // over the present keys
     u64 first_present1 = ~0ull, first_present2 = ~0ull, first_valid_pair = ~0ull;
@@ -157,7 +179,8 @@ static int th_grow(fastf_taghist* h, u64 need) {
         DevBuf& b = which ? h->d_k2 : h->d_k1;
         DevBuf nb;
         if (nb.ensure(ncap * sizeof(u64))) return 1;
-        if (h->n) HIP_OK(hipMemcpyAsync(nb.p, b.p, h->n * sizeof(u64), hipMemcpyDeviceToDevice, s));
+        const u64 keep = h->n + (which ? 0 : h->dev_reserved);
+        if (keep) HIP_OK(hipMemcpyAsync(nb.p, b.p, keep * sizeof(u64), hipMemcpyDeviceToDevice, s));
         HIP_OK(hipStreamSynchronize(s));
         b.release();
         b = nb;
@@ -203,6 +226,59 @@ extern "C" int fastf_taghist_push(fastf_taghist_t* h, const uint64_t* key1, cons
         if (key2) HIP_OK(hipMemcpyAsync((u64*)h->d_k2.p + h->n + off, st2, m * sizeof(u64), hipMemcpyHostToDevice, s));
     }
     h->n += n;
+    return 0;
+} FASTF_CATCH_INT
+
+// Device-resident keys (freq: the FASTQ parse packs them straight into the key array).  reserve_device makes room for n keys
+// behind the pushed ones and returns where they go (device memory of the histogram's device; valid until the next reserve or
+// push; keys already written into an earlier reservation move along when the array grows).  Kernels that write there run on
+// fastf_taghist_stream, the stream a growth copies on.
+extern "C" uint64_t* fastf_taghist_reserve_device(fastf_taghist_t* h, size_t n) FASTF_TRY {
+    if (!h) { set_err("null histogram"); return nullptr; }
+    if (h->mode_set && h->pair) { set_err("single-tag and tag-pair pushes cannot be mixed"); return nullptr; }
+    if (h->n + n >= (1ull << 32) - 1) { set_err("tag histogram: more than 2^32-2 records"); return nullptr; }
+    if (hipSetDevice(h->device) != hipSuccess) { set_err("hipSetDevice failed"); return nullptr; }
+    if (th_grow(h, h->n + n)) return nullptr;
+    h->dev_reserved = std::max<u64>(h->dev_reserved, n);
+    return (uint64_t*)h->d_k1.p + h->n;
+} FASTF_CATCH_ZERO
+extern "C" void* fastf_taghist_stream(fastf_taghist_t* h) { return h ? (void*)h->ws->s_compute : nullptr; }
+
+// Single-tag push of n keys in DEVICE memory (0 = absent), queued on fastf_taghist_stream before this call.  d_key1 may be the
+// pointer fastf_taghist_reserve_device returned (no copy) or any other device array.  The summary fastf_taghist_push keeps on the
+// host while it stages (OR / AND of the present keys, their number, the first present index) comes from one reduction kernel.
+extern "C" int fastf_taghist_push_device(fastf_taghist_t* h, const uint64_t* d_key1, size_t n) FASTF_TRY {
+    if (!h) return set_err("null histogram");
+    if (!d_key1 && n) return set_err("null keys");
+    if (h->mode_set && h->pair) return set_err("single-tag and tag-pair pushes cannot be mixed");
+    h->pair = false; h->mode_set = true;
+    if (n == 0) return 0;
+    if (h->n + n >= (1ull << 32) - 1) return set_err("tag histogram: more than 2^32-2 records");
+    HIP_OK(hipSetDevice(h->device));
+    hipStream_t s = h->ws->s_compute;
+    u64* dst = (u64*)h->d_k1.p + h->n;
+    if ((const u64*)d_key1 != dst || h->n + n > h->cap) {
+        if (th_grow(h, h->n + n)) return 1;
+        dst = (u64*)h->d_k1.p + h->n;
+        HIP_OK(hipMemcpyAsync(dst, d_key1, n * sizeof(u64), hipMemcpyDeviceToDevice, s));
+    }
+    u64* d_sum = (u64*)h->d_small.p + 3;                       // [3..6]; finish uses [0..2] and [7]
+    HIP_OK(hipMemsetAsync(d_sum, 0, sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(d_sum + 1, 0xff, sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(d_sum + 2, 0, sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(d_sum + 3, 0xff, sizeof(u64), s));
+    hipLaunchKernelGGL(th_summary_kernel, dim3((u32)std::min<u64>((n + 255) / 256, 2048)), dim3(256), 0, s, (const u64*)dst, (u64)n, d_sum);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 sum[4];
+    if (copy_d2h(sum, d_sum, sizeof sum)) return 1;
+    if (sum[2]) {
+        h->or1 |= sum[0]; h->and1 &= sum[1];
+        if (h->first_present1 == ~0ull) h->first_present1 = h->n + sum[3];
+    }
+    h->n_present1 += sum[2]; h->n_valid += sum[2];
+    h->n += n;
+    h->dev_reserved = 0;
     return 0;
 } FASTF_CATCH_INT
 

@@ -2297,6 +2297,11 @@ extern "C" int fastf_engine_reseed(fastf_engine_t* e, uint32_t seed, uint64_t sk
 #include "tag_hist.hpp"
 
 // ------------------------------------------------------------------------------------
+// freq: FASTQ text -> keys of the tag histogram, on the device
+// ------------------------------------------------------------------------------------
+#include "fastq_kernels.hpp"
+
+// ------------------------------------------------------------------------------------
 // one process, several devices: same translation unit, drives sub-engines through the launch_* functions above
 // ------------------------------------------------------------------------------------
 #include "multi_engine.hpp"

@@ -10,6 +10,8 @@
  *      and, for the tag-histogram commands,
  *        extract_bam / read_bam / print_CB_node / free_CB_node   replace  src/extract.c (decl. extract.h:15-26)
  *        cmd_crb / cmd_extract                                   replace  src/main.c:231-286, 364-402
+ *      and, for the FASTQ histogram,
+ *        cell_counts / cmd_freq                                  replace  src/count.c:3-21, src/main.c:30-92
  *
  *   2. INNER seam (host buffers in, COO out) — what replaces the reference's
  *      per-record loop + SQLite aggregate (bam2db_ds.c:360-438, 480-483):
@@ -78,6 +80,14 @@ int cmd_extract(int argc, const char **argv);   /* main.c:364-402; argv[0] == "e
 int fastf_crb_text(const char *bam_file, char **txt, size_t *txt_len, uint64_t *n_records);
 int fastf_extract_text(const char *bam_file, const char *tag, int type, char **csv, size_t *csv_len,
                        uint64_t *n_records, uint64_t *n_valid);
+
+/* --- freq: src/main.c:30-92, count.c.  cell_counts(gzFile, ...) (count.c:3-21) is exported too; it is declared in host_io.h
+ * because its first parameter is zlib's gzFile. --- */
+int cmd_freq(int argc, const char **argv);      /* main.c:30-92; argv[0] == "freq" */
+/* the bytes of whitelist.txt for an R1 FASTQ (plain, gzip or BGZF): "<first len_cb + len_umi bytes of the read>,<count>\n" in the
+ * pre-order of the reference's insertion-order tree (malloc'ed); *n_reads = reads in the file */
+int fastf_freq_text(const char *fastq_file, size_t len_cellbarcode, size_t len_umi, char **txt, size_t *txt_len,
+                    uint64_t *n_reads);
 
 const char *fastf_last_error(void);
 const char *fastf_version(void);
@@ -264,6 +274,13 @@ int  fastf_taghist_create(int device, fastf_taghist_t **out);
 void fastf_taghist_destroy(fastf_taghist_t *h);
 /* key2 == NULL: single-tag histogram; otherwise the two-level (key1 → key2) histogram.  One mode per object. */
 int  fastf_taghist_push(fastf_taghist_t *h, const uint64_t *key1, const uint64_t *key2, size_t n);
+/* single-tag keys already in DEVICE memory (freq packs them on the device): reserve_device returns where n more keys go in the
+ * object's own key array (valid until the next reserve / push; keys written into an earlier reservation are kept when the array
+ * grows), to be written by work queued on fastf_taghist_stream (a hipStream_t); push_device appends n keys from device memory —
+ * from that reservation without a copy — with the summary of the present keys reduced on the device */
+uint64_t *fastf_taghist_reserve_device(fastf_taghist_t *h, size_t n);
+void *fastf_taghist_stream(fastf_taghist_t *h);
+int  fastf_taghist_push_device(fastf_taghist_t *h, const uint64_t *d_key1, size_t n);
 /* result arrays are owned by the object and stay valid until the next finish / destroy */
 int  fastf_taghist_finish(fastf_taghist_t *h, fastf_taghist_result_t *result);
 
