@@ -104,6 +104,8 @@ ABI_SYMBOLS = [
     "fastf_taghist_create", "fastf_taghist_destroy", "fastf_taghist_push", "fastf_taghist_finish",
     # freq
     "fastf_freq_text", "fastf_taghist_reserve_device", "fastf_taghist_stream", "fastf_taghist_push_device",
+    # filter
+    "fastf_filter", "fastf_filter_draws", "fastf_filter_draws_host", "fastf_filter_rand_at", "fastf_filter_draw_passes",
 ]
 
 
@@ -240,6 +242,13 @@ def lib():
     L.fastf_crb_text.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]
     L.fastf_extract_text.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64), C.POINTER(u64)]
     L.fastf_freq_text.argtypes = [C.c_char_p, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]
+    L.fastf_filter.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_float,
+                               C.c_int, C.POINTER(u64), C.POINTER(u64)]
+    L.fastf_filter_draws.argtypes = [C.c_uint32, u64, u64, vp]
+    L.fastf_filter_draws_host.argtypes = [C.c_uint32, u64, u64, vp]
+    L.fastf_filter_rand_at.argtypes = [C.c_uint32, u64]
+    L.fastf_filter_rand_at.restype = C.c_uint32
+    L.fastf_filter_draw_passes.argtypes = [C.c_uint32, C.c_float]
     L.fastf_taghist_reserve_device.argtypes = [vp, sz]
     L.fastf_taghist_reserve_device.restype = vp
     L.fastf_taghist_stream.argtypes = [vp]

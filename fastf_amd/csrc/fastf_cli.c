@@ -1,5 +1,5 @@
 /* fastf_cli.c — `fastF` command line: dispatch table of the reference (main.c:404-443),
- * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract; the FASTQ histogram freq). */
+ * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract; the FASTQ ones: freq, filter). */
 #include "fastf_amd.h"
 
 #include <stdio.h>
@@ -9,7 +9,7 @@
 
 extern int fastf_process_is_exiting_;
 struct cmd_struct { const char *cmd; int (*fn)(int, const char **); };
-static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract} };
+static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"filter", cmd_filter}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract} };
 
 /* One command uses one GPU unless FASTF_DEVICES asks for more: hide the others from the HIP runtime before it loads,
  * so that its start-up (which opens every visible device) costs the same on an 8-GPU host as on a 1-GPU one.
@@ -29,10 +29,11 @@ int main(int argc, const char **argv)
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
         printf("Usage: fastF <command> [options]\n\nCommands:\n"
                "    freq      cell barcode + UMI prefixes of an R1 FASTQ and their frequencies -> whitelist.txt\n"
+               "    filter    FASTQ triples subsampled by cell barcode whitelist and read depth -> I1/R1/R2.fastq.gz\n"
                "    crb       CB/CR tags of a BAM and their frequencies -> gzip'ed rows\n"
                "    bam2db    BAM -> down-sampled, UMI-deduplicated gene x cell matrix (MI355X engine)\n"
                "    extract   frequencies of one BAM tag -> tag_summary.csv\n\n"
-               "(%s; the FASTQ command filter is not part of this engine)\n", fastf_version());
+               "(%s)\n", fastf_version());
         return argc < 2 ? 1 : 0;
     }
     for (size_t i = 0; i < sizeof commands / sizeof commands[0]; i++)

@@ -48,18 +48,7 @@ static void fq_err(const char *fmt, ...)
 /* ------------------------------------------------------------------ */
 /* decompressed text, whatever gzopen(path, "r") would read             */
 /* ------------------------------------------------------------------ */
-enum { FQ_PLAIN, FQ_GZIP, FQ_BGZF, FQ_GZFILE };
-typedef struct {
-    int kind;
-    int fd;
-    unsigned char *map; size_t map_len;       /* FQ_GZIP / FQ_BGZF: the compressed file */
-    uint64_t pos;                             /* FQ_PLAIN: file offset */
-    size_t coff;                              /* compressed cursor */
-    z_stream z; int z_live, z_member_done;
-    gzFile gz;
-    unsigned char spill[65536]; size_t spill_len, spill_off;   /* inflated bytes of a BGZF block that did not fit a window */
-    int nt;
-} fq_src;
+/* fq_src: host_io.h */
 
 /* BGZF block at o: 0 and its geometry, or 1 (not a BGZF member) */
 static int bgzf_block(const fq_src *s, size_t o, size_t *cdata, size_t *clen, size_t *bsize, uint32_t *isize)
@@ -81,7 +70,7 @@ static int bgzf_block(const fq_src *s, size_t o, size_t *cdata, size_t *clen, si
     return *isize > 65536;
 }
 
-static int fq_src_open(fq_src *s, const char *path)
+int fastf_fq_src_open(fq_src *s, const char *path)
 {
     memset(s, 0, sizeof *s);
     s->fd = open(path, O_RDONLY | O_CLOEXEC);
@@ -101,7 +90,7 @@ static int fq_src_open(fq_src *s, const char *path)
     return 0;
 }
 
-static void fq_src_close(fq_src *s)
+void fastf_fq_src_close(fq_src *s)
 {
     if (s->z_live) inflateEnd(&s->z);
     if (s->map) munmap(s->map, s->map_len);
@@ -237,7 +226,7 @@ done:
 }
 
 /* up to cap bytes of text; fewer only at the end of the data.  -1 on error. */
-static long fq_src_fill(fq_src *s, unsigned char *out, size_t cap)
+long fastf_fq_src_fill(fq_src *s, unsigned char *out, size_t cap)
 {
     size_t n = 0;
     switch (s->kind) {
@@ -363,7 +352,7 @@ static int fq_escapes(esc_tab *t, rk_list *l, const unsigned char *staging, uint
     return 0;
 }
 
-static size_t fq_window_bytes(void)
+size_t fastf_fq_window_bytes(void)
 {
     const char *e = getenv("FASTF_FQ_WINDOW");
     size_t w = (size_t)32 << 20;
@@ -398,7 +387,7 @@ static int fq_run(fq_src *src, size_t len_cb, size_t len_umi, fq_result *res)
     const int prof = tprof();
     const double t0 = fq_now();
     double t_fill = 0, t_wait_create = 0, t_escape = 0, h2d_ms = 0, parse_ms = 0;
-    const size_t W = fq_window_bytes();
+    const size_t W = fastf_fq_window_bytes();
     unsigned char *stage[2] = {NULL, NULL};
     fastf_fqparse_t *fp = NULL;
     fastf_taghist_t *hist = NULL;
@@ -430,7 +419,7 @@ static int fq_run(fq_src *src, size_t len_cb, size_t len_umi, fq_result *res)
         }
         if (k) memcpy(stage[par], stage[par ^ 1] + win_len[par ^ 1], FQ_HDR);
         const double tf = fq_now();
-        const long n = fq_src_fill(src, stage[par] + FQ_HDR, W);
+        const long n = fastf_fq_src_fill(src, stage[par] + FQ_HDR, W);
         t_fill += fq_now() - tf;
         if (n < 0) goto done;
         last = (size_t)n < W;
@@ -566,10 +555,10 @@ int fastf_freq_text(const char *fastq_file, size_t len_cellbarcode, size_t len_u
 {
     if (!fastq_file || !txt || !txt_len) { fq_err("null argument"); return 1; }
     fq_src src;
-    if (fq_src_open(&src, fastq_file)) return 1;
+    if (fastf_fq_src_open(&src, fastq_file)) return 1;
     fq_result r;
     int rc = fq_run(&src, len_cellbarcode, len_umi, &r);
-    fq_src_close(&src);
+    fastf_fq_src_close(&src);
     if (rc) return 1;
     if (n_reads) *n_reads = r.n_reads;
     rc = fq_text(&r, txt, txt_len);

@@ -136,9 +136,50 @@ int  fastf_fqparse_wait(fastf_fqparse_t *p, int parity, const fastf_fq_esc_t **e
 int  fastf_fqparse_end(fastf_fqparse_t *p, uint64_t *n_nl, uint64_t *line_start, uint32_t *err, uint64_t *err_rec);
 int  fastf_fqparse_scatter(fastf_fqparse_t *p, const uint64_t *rk, size_t n, uint64_t key_cap);
 
+/* filter (filter_cmds.c): the device path of FASTQ triples (filter_kernels.hpp) */
+typedef struct { uint32_t i, s1; } fastf_flt_esc_t;      /* read i of the window: its sequence line (buffer offset s1) goes to the host */
+typedef struct fastf_fltdev fastf_fltdev_t;
+int  fastf_fltdev_create(int device, size_t window_bytes, fastf_fltdev_t **out);
+void fastf_fltdev_destroy(fastf_fltdev_t *p);
+int  fastf_fltdev_set_whitelist(fastf_fltdev_t *p, const uint64_t *keys, size_t n);
+int  fastf_fltdev_reset(fastf_fltdev_t *p);
+int  fastf_fltdev_parse(fastf_fltdev_t *p, const unsigned char *staging, size_t len, uint64_t a, uint64_t tv, uint64_t limit,
+                        uint64_t *r_lo, uint64_t *n_rec);
+int  fastf_fltdev_decide(fastf_fltdev_t *p, int mode, int all, uint32_t L, float rate, const uint32_t *cs,
+                         const fastf_flt_esc_t **esc, uint32_t *n_esc);
+int  fastf_fltdev_emit(fastf_fltdev_t *p, const uint32_t *hit, uint32_t n_hit, const unsigned char **out, size_t *total);
+int  fastf_fltdev_end(fastf_fltdev_t *p, uint64_t *n_nl, uint64_t *kept, uint32_t *err, uint64_t *err_rec, double *dev_ms);
+int  fastf_flt_draws_dev(int device, const uint32_t *cs, uint64_t n, uint32_t *out);
+
+/* fastq_cmds.c: decompressed text of a FASTQ file, whatever gzopen(path, "r") would read (plain, BGZF on the host threads, other
+ * gzip, or a caller's gzFile) */
+enum { FQ_PLAIN, FQ_GZIP, FQ_BGZF, FQ_GZFILE };
+typedef struct {
+    int kind;
+    int fd;
+    unsigned char *map; size_t map_len;       /* FQ_GZIP / FQ_BGZF: the compressed file */
+    uint64_t pos;                             /* FQ_PLAIN: file offset */
+    size_t coff;                              /* compressed cursor */
+    z_stream z; int z_live, z_member_done;
+    gzFile gz;
+    unsigned char spill[65536]; size_t spill_len, spill_off;   /* inflated bytes of a BGZF block that did not fit a window */
+    int nt;
+} fq_src;
+int    fastf_fq_src_open(fq_src *s, const char *path) __attribute__((visibility("hidden")));
+void   fastf_fq_src_close(fq_src *s) __attribute__((visibility("hidden")));
+long   fastf_fq_src_fill(fq_src *s, unsigned char *out, size_t cap) __attribute__((visibility("hidden")));
+size_t fastf_fq_window_bytes(void) __attribute__((visibility("hidden")));
+
 /* count.c:3-21 — the reference's cell barcode + UMI tree of an R1 FASTQ, node for node (malloc'ed nodes; the reference's
  * free_tree_node releases it).  Declared here because of zlib's gzFile; the file is read with gzread on the calling thread. */
 node *cell_counts(gzFile R1_file, size_t len_cellbarcode, size_t len_umi);
+
+/* filter.c:286-350 — the reference's filter loop: the caller's gzFiles (I1 / R2 may be Z_NULL) read on the calling thread, the
+ * kept records written with gzwrite.  Declared here because of zlib's gzFile. */
+#ifndef __cplusplus
+void fastF(gzFile file_in[3], gzFile file_out[3], node *tree_whitelist, unsigned int len_cellbarcode, unsigned int seed, float rate,
+           _Bool all_cell);
+#endif
 
 /* the rows of print_tree (filter.c:139-148) for strs[order[k]] / count[order[k]], and the insertion-order tree itself as the
  * reference's malloc'ed nodes (tag_cmds.c) */

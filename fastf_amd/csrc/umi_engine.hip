@@ -2302,6 +2302,11 @@ extern "C" int fastf_engine_reseed(fastf_engine_t* e, uint32_t seed, uint64_t sk
 #include "fastq_kernels.hpp"
 
 // ------------------------------------------------------------------------------------
+// filter: FASTQ triples -> keep bitmap + compacted text windows, on the device
+// ------------------------------------------------------------------------------------
+#include "filter_kernels.hpp"
+
+// ------------------------------------------------------------------------------------
 // one process, several devices: same translation unit, drives sub-engines through the launch_* functions above
 // ------------------------------------------------------------------------------------
 #include "multi_engine.hpp"

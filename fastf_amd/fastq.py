@@ -1,7 +1,11 @@
 """Python mirror of `fastF freq` (include/fastf_amd.h: fastf_freq_text): the cell barcode + UMI prefixes of an R1 FASTQ
-(plain, gzip or BGZF) and their frequencies, counted on the device."""
+(plain, gzip or BGZF) and their frequencies, counted on the device; and of `fastF filter` (fastf_filter): FASTQ triples
+subsampled by cell barcode whitelist and read depth on the device."""
 import ctypes as C
+import os
 import re
+
+import numpy as np
 
 from . import _lib
 from .engine import _libc_free
@@ -27,3 +31,33 @@ def freq(path, len_cb: int = 16, len_umi: int = 10, device=None):
     them: a shorter sequence line keeps its newline, so rows are split at the first ",<count>\n" (a prefix that itself holds
     ",<digits>\n" cannot be told apart from a row end; use freq_text for such input)"""
     return [(m.group(1), int(m.group(2))) for m in _ROW.finditer(freq_text(path, len_cb, len_umi, device))]
+
+
+def filter(r1, i1=None, r2=None, out=".", whitelist=None, len_cb: int = 16, seed: int = 926, rate: float = 0.0,
+           all_cells: bool = False):
+    """`fastF filter -R r1 [-I i1] [-r r2] -o out [-w whitelist] -l len_cb -s seed -t rate [-a]`: writes out/R1.fastq.gz (and
+    I1 / R2) and returns (reads in R1, reads kept).  seed is taken modulo 2^32 (-1 is 4294967295, as the reference's
+    (unsigned) cast); runs on the process's device 0"""
+    if whitelist is None and not all_cells:
+        raise ValueError("filter needs a whitelist or all_cells=True")
+    if len_cb < 0:
+        raise ValueError("len_cb must not be negative")
+    enc = lambda p: None if p is None else os.fspath(p).encode()  # noqa: E731
+    nr, nk = C.c_uint64(), C.c_uint64()
+    _lib.check(_lib.lib().fastf_filter(enc(r1), enc(i1), enc(r2), enc(out), enc(whitelist), len_cb, seed % (1 << 32),
+                                       float(rate), int(bool(all_cells)), C.byref(nr), C.byref(nk)))
+    return nr.value, nk.value
+
+
+def filter_draws(seed: int, first: int, n: int, device: bool = True) -> np.ndarray:
+    """rand() outputs first .. first + n - 1 after srand(seed) (uint32): as filter's device kernel computes them, or
+    (device=False) by the host's jump-ahead and recurrence"""
+    out = np.empty(n, dtype=np.uint32)
+    fn = _lib.lib().fastf_filter_draws if device else _lib.lib().fastf_filter_draws_host
+    _lib.check(fn(seed % (1 << 32), first, n, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def filter_rand_at(seed: int, index: int) -> int:
+    """the rand() output with this index after srand(seed), by the host's jump-ahead"""
+    return _lib.lib().fastf_filter_rand_at(seed % (1 << 32), index)

@@ -12,6 +12,7 @@
  *        cmd_crb / cmd_extract                                   replace  src/main.c:231-286, 364-402
  *      and, for the FASTQ histogram,
  *        cell_counts / cmd_freq                                  replace  src/count.c:3-21, src/main.c:30-92
+ *        fastF / cmd_filter                                      replace  src/filter.c:286-350, src/main.c:94-228
  *
  *   2. INNER seam (host buffers in, COO out) — what replaces the reference's
  *      per-record loop + SQLite aggregate (bam2db_ds.c:360-438, 480-483):
@@ -88,6 +89,22 @@ int cmd_freq(int argc, const char **argv);      /* main.c:30-92; argv[0] == "fre
  * pre-order of the reference's insertion-order tree (malloc'ed); *n_reads = reads in the file */
 int fastf_freq_text(const char *fastq_file, size_t len_cellbarcode, size_t len_umi, char **txt, size_t *txt_len,
                     uint64_t *n_reads);
+
+/* --- filter: src/main.c:94-228, filter.c:286-350.  fastF(gzFile in[3], gzFile out[3], ...) (filter.c:286) is exported too; it
+ * is declared in host_io.h because of zlib's gzFile. --- */
+int cmd_filter(int argc, const char **argv);    /* main.c:94-228; argv[0] == "filter" */
+/* I1 / R2 may be NULL; out_dir NULL = "."; whitelist NULL needs all_cells.  Writes <out_dir>/R1.fastq.gz (and I1 / R2): the reads
+ * whose draw (float) rand() / RAND_MAX after srand(seed) is below rate and (all_cells, or whose first len_cellbarcode bytes of the
+ * R1 sequence line equal those of a whitelist line), as gzip members.  *n_reads = R1 reads, *n_kept = reads kept. */
+int fastf_filter(const char *r1, const char *i1, const char *r2, const char *out_dir, const char *whitelist, uint32_t len_cellbarcode,
+                 uint32_t seed, float rate, int all_cells, uint64_t *n_reads, uint64_t *n_kept);
+/* rand() outputs first .. first + n - 1 after srand(seed), computed by the device kernel of filter (out: n words) */
+int fastf_filter_draws(uint32_t seed, uint64_t first, uint64_t n, uint32_t *out);
+/* the same by the host: the jump-ahead to `first`, then the recurrence word by word; one output by the jump-ahead alone; the
+ * reference's keep rule for one draw */
+int fastf_filter_draws_host(uint32_t seed, uint64_t first, uint64_t n, uint32_t *out);
+uint32_t fastf_filter_rand_at(uint32_t seed, uint64_t index);
+int fastf_filter_draw_passes(uint32_t r, float rate);
 
 const char *fastf_last_error(void);
 const char *fastf_version(void);
