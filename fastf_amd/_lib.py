@@ -106,6 +106,9 @@ ABI_SYMBOLS = [
     "fastf_freq_text", "fastf_taghist_reserve_device", "fastf_taghist_stream", "fastf_taghist_push_device",
     # filter
     "fastf_filter", "fastf_filter_draws", "fastf_filter_draws_host", "fastf_filter_rand_at", "fastf_filter_draw_passes",
+    # sweep
+    "fastf_sweep", "fastf_sweep_parse_rates", "fastf_sweep_check_grid", "fastf_sweep_point_dir", "fastf_sweep_header",
+    "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
 ]
 
 
@@ -264,6 +267,16 @@ def lib():
     L.free_CB_node.restype = None
     L.extract_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.extract_bam.restype = None
+    fp = C.POINTER(C.c_float)
+    L.fastf_sweep.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, u32, u32]
+    L.fastf_sweep_parse_rates.argtypes = [C.c_char_p, C.c_int, fp, u32, C.POINTER(u32)]
+    L.fastf_sweep_check_grid.argtypes = [fp, u32, fp, u32]
+    L.fastf_sweep_point_dir.argtypes = [C.c_float, C.c_float, C.c_char_p, sz]
+    L.fastf_sweep_header.restype = C.c_char_p
+    L.fastf_sweep_cells_from_coo.argtypes = [C.POINTER(Coo), u32, vp, vp, C.POINTER(u64)]
+    L.fastf_sweep_summary_row.argtypes = [C.c_float, C.c_float, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, C.c_char_p, sz]
+    L.fastf_dev_mt_decisions_multi.argtypes = [vp, u32, u64, u64, vp, u32, vp, u64, vp]
+    L.fastf_dev_cell_summary.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -5,6 +5,7 @@
 // (finish) K2 LSD radix sort → K3 segmented unique/reduce → COO D2H.
 // There is NO CPU fallback: every entry point fails loudly when HIP is unusable.
 #include "umi_kernels.hpp"
+#include "sweep_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -923,9 +924,24 @@ static int launch_draw_bits(u64 threshold, const u32* d_draws, u64 n, u32* d_bit
     HIP_OK(hipGetLastError());
     return 0;
 }
+// the same for several thresholds at once: plane j of `planes` (plane_stride 64-bit words apart) = draws[i] < thresholds[j], the words
+// read once per PLANES_MAX thresholds (draw_planes_kernel, sweep_kernels.hpp)
+struct PlaneOut { const u64* thresholds; u32 n; u64* planes; u64 stride; };
+static int launch_draw_planes(const PlaneOut& po, const u32* d_draws, u64 n, hipStream_t s) {
+    if (n == 0) return 0;
+    const u32 grid = (u32)std::min<u64>((n + 255) / 256 + 1, 8ull * g_cu_count);
+    for (u32 j0 = 0; j0 < po.n; j0 += PLANES_MAX) {
+        PlaneSet ps{}; ps.n = std::min<u32>(PLANES_MAX, po.n - j0);
+        for (u32 j = 0; j < ps.n; ++j) ps.threshold[j] = po.thresholds[j0 + j];
+        hipLaunchKernelGGL(draw_planes_kernel, dim3(grid), dim3(256), 0, s, d_draws, n, ps, po.planes + (u64)j0 * po.stride, po.stride);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 // continue the MT19937 stream in d_mt by `count` draws and leave their DECISIONS at the ranks first .. first + count of the ring:
 // the generator writes words into `words` (grown to fit), draw_bits_kernel packs them behind it on the same stream
-static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold) {
+// (po: the decisions go to its planes instead — linear arrays from bit 0; d_ring, first, ring_mask and threshold are not used)
+static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr) {
     if (count == 0) return 0;
     if (words.bytes < count * 4) {
         // (the launches that read the old buffer are queued on this stream: let them finish before it is freed)
@@ -934,6 +950,7 @@ static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_r
     }
     hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(256), 0, s, d_mt, (u32*)words.p, 0ull, count, ~0ull);
     HIP_OK(hipGetLastError());
+    if (po) return launch_draw_planes(*po, (const u32*)words.p, count, s);
     return launch_draw_bits(threshold, (const u32*)words.p, count, d_ring, s, first, ring_mask);
 }
 // where a stream that stood at read index idx of its block stands after n more draws
@@ -948,12 +965,12 @@ static u32 mt_idx_after(u32 idx, u64 n) {
 // the sub-streams costs a handful of launches.
 constexpr u64 MT_PAR_MIN = 4ull * MT_SUB_DRAWS;
 static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u32* idx, DevBuf& words, u32* d_ring, u64 first, u64 count,
-                                   u64 ring_mask, u64 threshold) {
+                                   u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr) {
     if (count == 0) return 0;
     static const bool no_par = getenv("FASTF_MT_SERIAL") != nullptr;
     const u64 head = *idx < MT_N ? std::min<u64>(count, MT_N - *idx) : 0;          // to the next block boundary
     if (count < MT_PAR_MIN || no_par) {
-        if (launch_mt_decisions(s, d_mt, words, d_ring, first, count, ring_mask, threshold)) return 1;
+        if (launch_mt_decisions(s, d_mt, words, d_ring, first, count, ring_mask, threshold, po)) return 1;
         *idx = mt_idx_after(*idx, count);
         return 0;
     }
@@ -1003,6 +1020,7 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
         at += body;
     }
     *idx = mt_idx_after(MT_N, last);
+    if (po) return launch_draw_planes(*po, (const u32*)w, count, s);
     return launch_draw_bits(threshold, (const u32*)w, count, d_ring, s, first, ring_mask);
 }
 
@@ -1020,6 +1038,74 @@ extern "C" int fastf_dev_mt_decisions(fastf_engine_t* e, uint32_t seed, uint64_t
     u32 idx = (u32)mt.idx;
     if (launch_mt_decisions_par(e, (hipStream_t)stream, (u32*)e->d_mtseat.p, &idx, e->d_mtwords, d_bits_out, 0, n_draws, ~0ull, e->threshold)) return 1;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return set_err("the generator kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+} FASTF_CATCH_INT
+
+// The decision planes of a sweep: the stream of fastf_dev_mt_decisions generated ONCE and compared against n_thresholds
+// thresholds in the same pass — plane j (d_planes_out + j * plane_stride_words, the layout of fastf_dev_draw_bits) = draw i <
+// thresholds[j].  The engine's own threshold plays no part.  Synchronises the stream.
+extern "C" int fastf_dev_mt_decisions_multi(fastf_engine_t* e, uint32_t seed, uint64_t skip, uint64_t n_draws, const uint64_t* thresholds,
+                                            uint32_t n_thresholds, uint32_t* d_planes_out, uint64_t plane_stride_words, void* stream) FASTF_TRY {
+    if (!e || (n_thresholds && !thresholds) || (n_draws && n_thresholds && !d_planes_out)) return set_err("null argument");
+    if (e->multi) return set_err("fastf_dev_mt_decisions_multi: device-level calls take a single-device engine");
+    if (n_draws && n_thresholds && ((plane_stride_words & 1) || plane_stride_words < (n_draws + 63) / 64 * 2 || ((uintptr_t)d_planes_out & 7)))
+        return set_err("fastf_dev_mt_decisions_multi: planes are 8-byte aligned and an even number of 32-bit words apart, at least (n_draws + 63) / 64 * 2");
+    for (u32 j = 0; j < n_thresholds; ++j)
+        if (thresholds[j] > (1ull << 32)) return set_err("fastf_dev_mt_decisions_multi: threshold %u is above 2^32", j);
+    HIP_OK(hipSetDevice(e->device));
+    if (!n_draws || !n_thresholds) return 0;
+    fastf_mt_t mt; fastf_mt_seed(&mt, seed); fastf_mt_skip(&mt, skip);
+    if (e->d_mtseat.ensure(sizeof mt)) return 1;
+    if (copy_h2d_on(e->d_mtseat.p, &mt, sizeof mt, (hipStream_t)stream)) return 1;
+    u32 idx = (u32)mt.idx;
+    const PlaneOut po{(const u64*)thresholds, n_thresholds, (u64*)d_planes_out, plane_stride_words / 2};
+    if (launch_mt_decisions_par(e, (hipStream_t)stream, (u32*)e->d_mtseat.p, &idx, e->d_mtwords, nullptr, 0, n_draws, ~0ull, 0, &po)) return 1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return set_err("the generator kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+} FASTF_CATCH_INT
+
+// Per-cell summary of COO rows ascending by (cell, feature) (cell_summary_kernel): d_umis_per_cell[c - 1] = sum of the counts of
+// cell c, d_genes_per_cell[c - 1] = its rows with count >= 1, d_umis_per_cell[n_cells] = the sum of all counts.  Both arrays are
+// cleared here first; *d_nnz rows are read.
+extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_cells,
+                                      uint64_t* d_umis_per_cell, uint32_t* d_genes_per_cell, void* stream) FASTF_TRY {
+    if (!e || !d_nnz || !d_umis_per_cell || (n_cells && !d_genes_per_cell)) return set_err("null argument");
+    if (e->multi) return set_err("fastf_dev_cell_summary: device-level calls take a single-device engine");
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(hipMemsetAsync(d_umis_per_cell, 0, ((size_t)n_cells + 1) * sizeof(u64), s));
+    if (n_cells) HIP_OK(hipMemsetAsync(d_genes_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
+    if (!d_cell || !d_count) return 0;                  // (no row buffer: a reduce of nothing)
+    hipLaunchKernelGGL(cell_summary_kernel, dim3(2 * g_cu_count), dim3(256), 0, s, d_cell, d_count, (const u64*)d_nnz, n_cells,
+                       (u64*)d_umis_per_cell, d_genes_per_cell);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "cell summary");
+    return 0;
+} FASTF_CATCH_INT
+
+// device memory for the C side of the library (sweep_cmds.c keeps the records of a BAM resident); declared in host_io.h
+extern "C" void* fastf_devmem_alloc(int device, size_t bytes) FASTF_TRY {
+    void* p = nullptr;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
+        set_err("device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(hipGetLastError()));
+        return nullptr;
+    }
+    return p;
+} FASTF_CATCH_(return nullptr)
+extern "C" void fastf_devmem_free(void* p) { if (p) (void)hipFree(p); }
+// dst / src: device memory or host memory the runtime knows (pinned); synchronous
+extern "C" int fastf_devmem_copy(void* dst, const void* src, size_t bytes) FASTF_TRY {
+    if (!bytes) return 0;
+    HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+    return 0;
+} FASTF_CATCH_INT
+extern "C" int fastf_devmem_zero(void* dst, size_t bytes) FASTF_TRY {
+    if (!bytes) return 0;
+    HIP_OK(hipMemset(dst, 0, bytes));
+    return 0;
+} FASTF_CATCH_INT
+extern "C" int fastf_devmem_sync(void) FASTF_TRY {
+    HIP_OK(hipDeviceSynchronize());
     return 0;
 } FASTF_CATCH_INT
 
@@ -1479,7 +1565,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

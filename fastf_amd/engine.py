@@ -368,6 +368,19 @@ class Engine:
         counts: jump-ahead), bit i of d_bits_out; same size rule as dev_draw_bits"""
         check(self._L.fastf_dev_mt_decisions(self._h, seed, skip, n_draws, d_bits_out, stream))
 
+    def dev_mt_decisions_multi(self, seed, skip, n_draws, thresholds, d_planes_out, plane_stride_words, stream=0):
+        """the decision planes of a sweep: the stream of dev_mt_decisions generated once and compared against every threshold
+        (0 .. 2^32) in the same pass; plane j starts plane_stride_words 32-bit words behind plane j - 1 (even, at least
+        (n_draws + 63) // 64 * 2) and has the layout of dev_draw_bits.  The engine's own threshold plays no part."""
+        t = np.ascontiguousarray(thresholds, dtype=np.uint64)
+        check(self._L.fastf_dev_mt_decisions_multi(self._h, seed, skip, n_draws, t.ctypes.data, len(t), d_planes_out,
+                                                   plane_stride_words, stream))
+
+    def dev_cell_summary(self, d_cell, d_count, d_nnz, n_cells, d_umis_per_cell, d_genes_per_cell, stream=0):
+        """rows ascending by (cell, feature) -> d_umis_per_cell[c - 1] = sum of the counts of cell c (u64, n_cells + 1 entries:
+        the last is the sum of all counts), d_genes_per_cell[c - 1] = its rows with count >= 1 (u32); both cleared by the call"""
+        check(self._L.fastf_dev_cell_summary(self._h, d_cell, d_count, d_nnz, n_cells, d_umis_per_cell, d_genes_per_cell, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

@@ -1,0 +1,83 @@
+"""Python mirror of `fastF sweep` (include/fastf_amd.h: fastf_sweep and its host pieces): bam2db over a grid of
+(cell rate, depth rate) points from one decode of the BAM.  Nothing here computes results: every call lands in the library."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from ._lib import Coo
+
+SUMMARY_ONLY = 1      # FASTF_SWEEP_SUMMARY_ONLY
+COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
+           "saturation", "median_umis_per_cell", "median_genes_per_cell")
+
+
+def _floats(v):
+    a = np.ascontiguousarray(v, dtype=np.float32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False):
+    """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only]`; returns the
+    rows of out/sweep.tsv as dicts of strings (read_table)"""
+    rc, prc = _floats(rates_cell)
+    rd, prd = _floats(rates_depth)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
+                                      seed % (1 << 32), SUMMARY_ONLY if summary_only else 0))
+    return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
+
+
+def read_table(path):
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""
+    return [dict(zip(COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def parse_rates(text: str, cell_rates: bool = False):
+    """a comma-separated list of rates as the command reads -c (cell_rates) and -r; raises FastfError on what it refuses"""
+    out = np.zeros(64, dtype=np.float32)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().fastf_sweep_parse_rates(text.encode(), int(cell_rates), out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def check_grid(rates_cell, rates_depth):
+    rc, prc = _floats(rates_cell)
+    rd, prd = _floats(rates_depth)
+    _lib.check(_lib.lib().fastf_sweep_check_grid(prc, len(rc), prd, len(rd)))
+
+
+def point_dir(rate_cell: float, rate_depth: float) -> str:
+    buf = C.create_string_buffer(64)
+    _lib.check(_lib.lib().fastf_sweep_point_dir(float(rate_cell), float(rate_depth), buf, len(buf)))
+    return buf.value.decode()
+
+
+def header() -> str:
+    return _lib.lib().fastf_sweep_header().decode()
+
+
+def cells_from_coo(cell, count, n_cells: int):
+    """(umis per cell u64[n_cells], genes per cell u32[n_cells], umis) of rows ascending by cell: the host form of
+    Engine.dev_cell_summary"""
+    c = np.ascontiguousarray(cell, dtype=np.uint32)
+    k = np.ascontiguousarray(count, dtype=np.uint32)
+    f = np.zeros(len(c), dtype=np.uint32)
+    p32 = C.POINTER(C.c_uint32)
+    coo = Coo(f.ctypes.data_as(p32), c.ctypes.data_as(p32), k.ctypes.data_as(p32), len(c))
+    upc, gpc, tot = np.zeros(max(n_cells, 1), np.uint64), np.zeros(max(n_cells, 1), np.uint32), C.c_uint64()
+    _lib.check(_lib.lib().fastf_sweep_cells_from_coo(C.byref(coo), n_cells, upc.ctypes.data, gpc.ctypes.data, C.byref(tot)))
+    return upc[:n_cells], gpc[:n_cells], int(tot.value)
+
+
+def summary_row(rate_cell, rate_depth, seed, counters, nnz, umis, umis_per_cell, genes_per_cell) -> str:
+    """one row of sweep.tsv (with its newline)"""
+    upc = np.ascontiguousarray(umis_per_cell, dtype=np.uint64)
+    gpc = np.ascontiguousarray(genes_per_cell, dtype=np.uint32)
+    cnt = (C.c_uint64 * 3)(*[int(x) for x in counters])
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_sweep_summary_row(float(rate_cell), float(rate_depth), seed, C.byref(cnt), int(nnz), int(umis),
+                                                  upc.ctypes.data, gpc.ctypes.data, len(upc), buf, len(buf)))
+    return buf.value.decode()

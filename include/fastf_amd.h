@@ -106,6 +106,28 @@ int fastf_filter_draws_host(uint32_t seed, uint64_t first, uint64_t n, uint32_t 
 uint32_t fastf_filter_rand_at(uint32_t seed, uint64_t index);
 int fastf_filter_draw_passes(uint32_t r, float rate);
 
+/* --- sweep: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM (sweep_cmds.c; not a command of the
+ * reference).  Per point <out_dir>/c<rate_cell>_r<rate_depth>/ (rates printed %.3f) holds matrix.mtx.gz, barcodes.tsv.gz and
+ * features.tsv.gz with the bytes bam2db() writes for that point; <out_dir>/sweep.tsv holds a header and one row per point, cell
+ * rates major, depth rates minor:
+ *   rate_cell rate_depth seed n_cells total_reads sampled_reads sampled_valid_reads nnz umis saturation
+ *   median_umis_per_cell median_genes_per_cell
+ * umis = sum of the matrix counts; saturation = 1 - umis / sampled_valid_reads (0 when that is 0); genes of a cell = its rows with
+ * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
+ * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
+ * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] */
+#define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
+int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags);
+/* the host pieces of it: a comma-separated list of rates (strtof per element; empty elements, trailing characters, NaN and negative
+ * values are refused, cell rates above 1 too); the grid check; a point's directory name; the header line of sweep.tsv; per cell
+ * (index c -> slot c - 1) the sum of the counts and the rows with count >= 1 of a COO; one row of sweep.tsv from those */
+int fastf_sweep_parse_rates(const char *text, int cell_rates, float *out, uint32_t cap, uint32_t *n_out);
+int fastf_sweep_check_grid(const float *rates_cell, uint32_t n_c, const float *rates_depth, uint32_t n_r);
+int fastf_sweep_point_dir(float rate_cell, float rate_depth, char *buf, size_t cap);
+const char *fastf_sweep_header(void);
+
 const char *fastf_last_error(void);
 const char *fastf_version(void);
 
@@ -223,6 +245,12 @@ typedef struct fastf_umi_rows {     /* -u output, ascending (cell, feature, blob
     const uint8_t  *nonnull;
     size_t          n;
 } fastf_umi_rows_t;
+
+/* sweep (section 1): per cell the sum of the counts and the rows with count >= 1 of a COO ascending by (cell, feature) — the host
+ * form of fastf_dev_cell_summary — and one row of sweep.tsv (with its newline) from them */
+int fastf_sweep_cells_from_coo(const fastf_coo_t *coo, uint32_t n_cells, uint64_t *umis_per_cell, uint32_t *genes_per_cell, uint64_t *umis);
+int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                            const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -378,6 +406,20 @@ int fastf_dev_draw_bits(fastf_engine_t *e, const uint32_t *d_draws, uint64_t n_d
  * Large counts run on many workgroups at once: the stream's state is linear, sub-streams 624 x 256 draws apart are seated by
  * jump-ahead (mt_jump.c) and generated side by side.  Synchronises the stream. */
 int fastf_dev_mt_decisions(fastf_engine_t *e, uint32_t seed, uint64_t skip, uint64_t n_draws, uint32_t *d_bits_out, void *stream);
+
+/* The decision PLANES of a sweep over depth rates: the same stream generated ONCE and compared against n_thresholds thresholds
+ * (each 0 .. 2^32, fastf_draw_threshold) in the same pass — plane j starts at d_planes_out + j * plane_stride_words and has the
+ * layout of fastf_dev_draw_bits: bit i = draw i < thresholds[j], 8-byte aligned (plane_stride_words even, at least
+ * (n_draws + 63) / 64 * 2), the tail of the last 64 bits zero.  The engine's own threshold plays no part.  thresholds: host
+ * memory.  Synchronises the stream. */
+int fastf_dev_mt_decisions_multi(fastf_engine_t *e, uint32_t seed, uint64_t skip, uint64_t n_draws, const uint64_t *thresholds,
+                                 uint32_t n_thresholds, uint32_t *d_planes_out, uint64_t plane_stride_words, void *stream);
+/* Per-cell summary of matrix rows ascending by (cell, feature) — what fastf_dev_reduce / fastf_dev_rows_gather leave: *d_nnz rows
+ * of d_cell (1-based) and d_count.  d_umis_per_cell[c - 1] = sum of the counts of cell c, d_genes_per_cell[c - 1] = its rows with
+ * count >= 1, and d_umis_per_cell[n_cells] = the sum of all counts: n_cells + 1 (u64) and n_cells (u32) entries, cleared by the
+ * call.  d_cell / d_count may be NULL when there are no rows. */
+int fastf_dev_cell_summary(fastf_engine_t *e, const uint32_t *d_cell, const uint32_t *d_count, const uint64_t *d_nnz, uint32_t n_cells,
+                           uint64_t *d_umis_per_cell, uint32_t *d_genes_per_cell, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
