@@ -109,6 +109,9 @@ ABI_SYMBOLS = [
     # sweep
     "fastf_sweep", "fastf_sweep_parse_rates", "fastf_sweep_check_grid", "fastf_sweep_point_dir", "fastf_sweep_header",
     "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
+    # cap
+    "fastf_cap", "fastf_cap_parse_caps", "fastf_cap_check_grid", "fastf_cap_point_dir", "fastf_cap_header",
+    "fastf_cap_summary_row", "fastf_cap_thresholds", "fastf_cap_realised", "fastf_dev_cell_hits", "fastf_dev_cell_decisions",
 ]
 
 
@@ -277,6 +280,17 @@ def lib():
     L.fastf_sweep_summary_row.argtypes = [C.c_float, C.c_float, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, C.c_char_p, sz]
     L.fastf_dev_mt_decisions_multi.argtypes = [vp, u32, u64, u64, vp, u32, vp, u64, vp]
     L.fastf_dev_cell_summary.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
+    L.fastf_cap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
+    L.fastf_cap_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
+    L.fastf_cap_check_grid.argtypes = [fp, u32, vp, u32]
+    L.fastf_cap_point_dir.argtypes = [C.c_float, u64, C.c_char_p, sz]
+    L.fastf_cap_header.restype = C.c_char_p
+    L.fastf_cap_summary_row.argtypes = [C.c_float, u64, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, u64, u32, C.c_char_p, sz]
+    L.fastf_cap_thresholds.argtypes = [vp, u32, u64, vp]
+    L.fastf_cap_realised.argtypes = [u64, u64]
+    L.fastf_cap_realised.restype = C.c_float
+    L.fastf_dev_cell_hits.argtypes = [vp, u64, vp, vp, vp]
+    L.fastf_dev_cell_decisions.argtypes = [vp, u64, vp, u32, u64, u64, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -1,0 +1,77 @@
+"""Python mirror of `fastF cap` (include/fastf_amd.h: fastf_cap and its host pieces): every cell downsampled to at most N reads,
+over a grid of (cell rate, cap) points from one decode of the BAM.  Nothing here computes results: every call lands in the library."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+
+SUMMARY_ONLY = 1      # FASTF_CAP_SUMMARY_ONLY
+COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
+           "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
+
+
+def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False):
+    """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only]`; returns the rows of
+    out/cap.tsv as dicts of strings (read_table)"""
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    n = np.ascontiguousarray(caps, dtype=np.uint64)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                    n.ctypes.data, len(n), seed % (1 << 32), SUMMARY_ONLY if summary_only else 0))
+    return read_table(os.path.join(os.fspath(out), "cap.tsv"))
+
+
+def read_table(path):
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""
+    return [dict(zip(COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def parse_caps(text: str):
+    """a comma-separated list of caps as the command reads -n; raises FastfError on what it refuses"""
+    out = np.zeros(64, dtype=np.uint64)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().fastf_cap_parse_caps(text.encode(), out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def check_grid(rates_cell, caps):
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    n = np.ascontiguousarray(caps, dtype=np.uint64)
+    _lib.check(_lib.lib().fastf_cap_check_grid(rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc), n.ctypes.data, len(n)))
+
+
+def point_dir(rate_cell: float, reads_per_cell: int) -> str:
+    buf = C.create_string_buffer(64)
+    _lib.check(_lib.lib().fastf_cap_point_dir(float(rate_cell), int(reads_per_cell), buf, len(buf)))
+    return buf.value.decode()
+
+
+def header() -> str:
+    return _lib.lib().fastf_cap_header().decode()
+
+
+def thresholds(hits, reads_per_cell: int):
+    """T[k] of include/fastf_amd.h from the hits per cell: 2^32 where hits[k] <= reads_per_cell, else
+    fastf_draw_threshold((float)(reads_per_cell / hits[k]))"""
+    h = np.ascontiguousarray(hits, dtype=np.uint32)
+    t = np.zeros(max(len(h), 1), dtype=np.uint64)
+    _lib.check(_lib.lib().fastf_cap_thresholds(h.ctypes.data, len(h), int(reads_per_cell), t.ctypes.data))
+    return t[:len(h)]
+
+
+def realised(sampled: int, hits: int) -> float:
+    return float(_lib.lib().fastf_cap_realised(int(sampled), int(hits)))
+
+
+def summary_row(rate_cell, reads_per_cell, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, hits, cells_capped) -> str:
+    """one row of cap.tsv (with its newline)"""
+    upc = np.ascontiguousarray(umis_per_cell, dtype=np.uint64)
+    gpc = np.ascontiguousarray(genes_per_cell, dtype=np.uint32)
+    cnt = (C.c_uint64 * 3)(*[int(x) for x in counters])
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_cap_summary_row(float(rate_cell), int(reads_per_cell), seed, C.byref(cnt), int(nnz), int(umis),
+                                                upc.ctypes.data, gpc.ctypes.data, len(upc), int(hits), int(cells_capped), buf, len(buf)))
+    return buf.value.decode()

@@ -1,0 +1,278 @@
+/*
+ * cap_cmds.c — `fastF cap`: every cell downsampled to at most N reads, over a grid of (cell rate, cap) points from ONE decode of
+ * the BAM.
+ *
+ *   cmd_cap()    -b -a -f -o -c <list> -n <list> [-s seed] [--summary-only]; -d accepted and ignored, -u refused
+ *   fastf_cap()  the same in process
+ * Per point <out>/c<rate_cell>_n<N>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} and one row of <out>/cap.tsv.
+ *
+ * The resident pipeline of sweep (resident.c).  Per cell rate K1a once, the hits per cell counted on the device
+ * (fastf_dev_cell_hits) and copied to the host once; per cap the per-cell thresholds computed on the host (n_cells is small, the
+ * device does no floating point) and sent to the device, the decision plane made from the draw stream and the thresholds
+ * (fastf_dev_cell_decisions), then K1b on that plane and everything behind it as in bam2db.  A global depth rate cannot express a
+ * cap, so a job outside the resident form is refused: there is no point-by-point fallback.
+ */
+#define _GNU_SOURCE
+#include "resident.h"
+
+#include <errno.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+static int cp_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static int cp_err(const char *fmt, ...)
+{
+    char buf[480];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    fastf_set_error_(buf);
+    return 1;
+}
+
+/* ------------------------------------------------------------------ */
+/* the grid                                                            */
+/* ------------------------------------------------------------------ */
+/* "10,100,1000" -> integers >= 1: digits only (no sign, no blanks); refused: an empty list or element, 0, a value twice */
+int fastf_cap_parse_caps(const char *text, uint64_t *out, uint32_t cap, uint32_t *n_out)
+{
+    uint32_t n = 0;
+    if (n_out) *n_out = 0;
+    if (!text || !out || !n_out) return cp_err("null argument");
+    for (const char *p = text;;) {
+        const char *q = p;
+        uint64_t v = 0;
+        if (*q == ',' || !*q) return cp_err("reads per cell `%s`: empty element", text);
+        for (; *q && *q != ','; q++) {
+            if (*q < '0' || *q > '9') return cp_err("reads per cell `%s`: expects positive integers", text);
+            if (v > (UINT64_MAX - (uint64_t)(*q - '0')) / 10) return cp_err("reads per cell `%s`: numerical result out of range", text);
+            v = v * 10 + (uint64_t)(*q - '0');
+        }
+        if (v < 1) return cp_err("reads per cell `%s`: a cap is at least 1", text);
+        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return cp_err("reads per cell `%s`: %llu is listed twice", text, (unsigned long long)v);
+        if (n == cap) return cp_err("reads per cell `%s`: more than %u values", text, cap);
+        out[n++] = v;
+        if (!*q) break;
+        p = q + 1;
+    }
+    *n_out = n;
+    return 0;
+}
+
+int fastf_cap_point_dir(float rate_cell, uint64_t reads_per_cell, char *buf, size_t cap)
+{
+    const int n = snprintf(buf, cap, "c%.3f_n%llu", (double)rate_cell, (unsigned long long)reads_per_cell);
+    return (n < 0 || (size_t)n >= cap) ? cp_err("directory name too long") : 0;
+}
+
+int fastf_cap_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t *caps, uint32_t n_n)
+{
+    if (!n_c || !n_n || !rates_cell || !caps) return cp_err("cap: the grid needs at least one cell rate and one cap");
+    const float one = 1.0f;
+    if (fastf_sweep_check_grid(rates_cell, n_c, &one, 1)) {       /* the cell rates are sweep's */
+        char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+        return cp_err("cap: %s", !strncmp(keep, "sweep: ", 7) ? keep + 7 : keep);
+    }
+    for (uint32_t i = 0; i < n_n; i++) {
+        if (caps[i] < 1) return cp_err("cap: reads per cell %llu: a cap is at least 1", (unsigned long long)caps[i]);
+        for (uint32_t j = 0; j < i; j++) if (caps[j] == caps[i]) return cp_err("cap: reads per cell %llu is listed twice", (unsigned long long)caps[i]);
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* thresholds, the summary row                                         */
+/* ------------------------------------------------------------------ */
+int fastf_cap_thresholds(const uint32_t *hits, uint32_t n_cells, uint64_t cap, uint64_t *thresholds_out)
+{
+    if (n_cells && (!hits || !thresholds_out)) return cp_err("null argument");
+    if (cap < 1) return cp_err("cap: a cap is at least 1");
+    for (uint32_t k = 0; k < n_cells; k++)
+        thresholds_out[k] = hits[k] <= cap ? (uint64_t)1 << 32 : fastf_draw_threshold((float)((double)cap / (double)hits[k]));
+    return 0;
+}
+
+float fastf_cap_realised(uint64_t sampled, uint64_t hits) { return hits ? (float)((double)sampled / (double)hits) : 1.0f; }
+
+const char *fastf_cap_header(void)
+{
+    return "rate_cell\treads_per_cell\tseed\tn_cells\ttotal_reads\tsampled_reads\tsampled_valid_reads\tnnz\tumis\tsaturation\t"
+           "median_umis_per_cell\tmedian_genes_per_cell\thits\tcells_capped\trealised_depth\n";
+}
+
+int fastf_cap_summary_row(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                          const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
+                          char *buf, size_t cap)
+{
+    char tail[400];
+    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail)) return 1;
+    const int n = snprintf(buf, cap, "%.3f\t%llu\t%s\t%llu\t%u\t%.6f\n", (double)rate_cell, (unsigned long long)reads_per_cell, tail,
+                           (unsigned long long)hits, cells_capped, (double)fastf_cap_realised(counters[1], hits));
+    return (n < 0 || (size_t)n >= cap) ? cp_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* cap.tsv                                                             */
+/* ------------------------------------------------------------------ */
+static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "cap.tsv", fastf_cap_header()); }
+
+/* ------------------------------------------------------------------ */
+/* one cell rate                                                       */
+/* ------------------------------------------------------------------ */
+static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
+                         float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_times_t *T)
+{
+    int rc = RES_FAIL;
+    res_rate_t S;
+    void *d_plane = NULL, *d_hits = NULL, *d_thr = NULL;
+    uint32_t *h_hits = NULL; uint64_t *h_thr = NULL;
+    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, T)) != RES_OK) goto done;
+    rc = RES_FAIL;
+    const uint64_t H = S.H, N = R->n;
+    const uint32_t n_cells = S.n_cells;
+    double tt = fastf_res_now();
+
+    /* the hits per cell, counted where K1a left the cell indices; to the host once, through pinned memory */
+    const size_t nc1 = (size_t)n_cells + 1;
+    const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind the plane: K1b reads a unit's words unconditionally) */
+    if (!(d_hits = fastf_devmem_alloc(device, nc1 * 4)) || !(d_thr = fastf_devmem_alloc(device, nc1 * 8)) ||
+        !(h_hits = (uint32_t *)fastf_pinned_alloc(nc1 * 4)) || !(h_thr = (uint64_t *)fastf_pinned_alloc(nc1 * 8)) ||
+        !(d_plane = fastf_devmem_alloc(device, (size_t)plane_words * 4)) || fastf_devmem_zero(d_plane, (size_t)plane_words * 4)) goto done;
+    if (fastf_dev_cell_hits(S.e, N, S.blocked ? S.d_blk : NULL, (uint32_t *)d_hits, NULL) || fastf_devmem_sync() ||
+        fastf_devmem_copy(h_hits, d_hits, (size_t)n_cells * 4)) goto done;
+    {   uint64_t sum = 0;
+        for (uint32_t k = 0; k < n_cells; k++) sum += h_hits[k];
+        if (sum != H) { cp_err("internal error: %llu hits per cell in total, K1a counted %llu", (unsigned long long)sum, (unsigned long long)H); goto done; } }
+    T->planes += fastf_res_now() - tt;
+
+    for (uint32_t j = 0; j < n_n; j++) {
+        char name[64], dir[4096], row[640];
+        uint64_t counters[3], nnz = 0;
+        uint32_t capped = 0;
+        if (fastf_cap_point_dir(rate_cell, caps[j], name, sizeof name)) goto done;
+        tt = fastf_res_now();
+        if (fastf_cap_thresholds(h_hits, n_cells, caps[j], h_thr)) goto done;
+        for (uint32_t k = 0; k < n_cells; k++) capped += h_hits[k] > caps[j];
+        if (fastf_devmem_copy(d_thr, h_thr, (size_t)n_cells * 8) ||
+            fastf_dev_cell_decisions(S.e, N, S.blocked ? S.d_blk : NULL, seed, L->mt_skip, H, (const uint64_t *)d_thr, (uint32_t *)d_plane, NULL)) goto done;
+        T->planes += fastf_res_now() - tt;
+        const int prc = fastf_res_point_run(&S, (const uint32_t *)d_plane, name, counters, &nnz, T);
+        if (prc != RES_OK) { rc = prc; goto done; }
+        tt = fastf_res_now();
+        if (fastf_cap_summary_row(rate_cell, caps[j], seed, counters, nnz, S.h_upc[n_cells], S.h_upc, S.h_gpc, n_cells, H, capped, row, sizeof row)) goto done;
+        T->summary += fastf_res_now() - tt;
+        if (!summary_only) {
+            snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
+            if (fastf_res_point_write(&S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
+        }
+        fputs(row, tsv);
+    }
+    rc = RES_OK;
+done:
+    fastf_res_rate_close(&S);
+    fastf_devmem_free(d_plane); fastf_devmem_free(d_hits); fastf_devmem_free(d_thr);
+    if (h_hits) fastf_pinned_free(h_hits);
+    if (h_thr) fastf_pinned_free(h_thr);
+    return rc;
+}
+
+static int cap_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
+                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv)
+{
+    int rc = RES_FAIL;
+    const int prof = getenv("FASTF_PROFILE") != NULL;
+    res_times_t T; memset(&T, 0, sizeof T);
+    const double t0 = fastf_res_now();
+    double tt = t0;
+    res_lists_t LL;
+    resident_t R; memset(&R, 0, sizeof R);
+    if ((rc = fastf_res_lists_load(barcodes, features, rc_list, n_c, seed, &LL)) != RES_OK) goto done;
+    rc = RES_FAIL;
+    T.lists = fastf_res_now() - tt; tt = fastf_res_now();
+    if (fastf_res_decode("cap", bam_file, &LL.L[0], device, &R)) goto done;
+    T.decode = fastf_res_now() - tt;
+    printf("cap: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n);
+    for (uint32_t i = 0; i < n_c; i++) {
+        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, &T);
+        if (rc != RES_OK) goto done;
+    }
+    rc = RES_OK;
+    if (prof)
+        fprintf(stderr, "[cap] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, hits per cell + thresholds + planes %.3f s, "
+                        "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
+                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_n), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+done:
+    fastf_res_free(&R);
+    fastf_res_lists_free(&LL);
+    return rc;
+}
+
+/* ------------------------------------------------------------------ */
+/* the command                                                         */
+/* ------------------------------------------------------------------ */
+int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+              const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags)
+{
+    if (!bam || !barcodes || !features) return cp_err("cap: null argument");
+    if (!out_dir) out_dir = ".";
+    if (fastf_cap_check_grid(rates_cell, n_c, caps, n_n)) return 1;
+    if (flags & ~(uint32_t)FASTF_CAP_SUMMARY_ONLY) return cp_err("cap: unknown flags 0x%x", flags);
+    const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0;
+    if (access(bam, R_OK) == -1) return cp_err("bam file: %s does not exist.", bam);
+    int dev0 = 0, dev_second = -1;
+    {   const char *dvs = getenv("FASTF_DEVICES");
+        fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
+        if (dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2))
+            return cp_err("cap: this job is outside the resident form (several devices), and a cap has no point-by-point form"); }
+    if (fastf_res_make_dir(out_dir)) return 1;
+    res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
+    if (tsv_open(&tsv, out_dir)) return 1;
+    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f);
+    if (rc == RES_NOT_COVERED)
+        cp_err("cap: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_set_error_(keep); return 1; }
+    return fastf_res_tsv_close(&tsv, 1);
+}
+
+static void usage_cap(FILE *f)
+{
+    fprintf(f,
+            "Usage: fastF cap [options]\n\n"
+            "every cell downsampled to at most N reads, over a grid of cell rates and caps from one decode of the bam file: per point\n"
+            "<out>/c<cell>_n<N>/ with the three files of bam2db, and <out>/cap.tsv with one summary row per point.\n\n"
+            "    -h, --help            show this help message and exit\n"
+            "    -b, --bam=<str>       path to bam file\n"
+            "    -f, --feature=<str>   path to feature list file\n"
+            "    -a, --barcode=<str>   path to barcode list file\n"
+            "    -d, --dbname=<str>    name of database (accepted for compatibility, ignored)\n"
+            "    -c, --cell=<list>     rates of cell barcode, comma separated (default 1.0)\n"
+            "    -n, --reads=<list>    reads per cell at most, comma separated integers >= 1\n"
+            "    -o, --out=<str>       path to output directory (default .)\n"
+            "    -s, --seed=<int>      seed for random number generator (default 926)\n"
+            "        --summary-only    write cap.tsv alone\n");
+}
+
+#define CAP_MAX_POINTS 64
+int cmd_cap(int argc, const char **argv)
+{
+    res_args_t A;
+    const int prc = fastf_res_parse_args(argc, argv, 'n', "reads", usage_cap, "cap does not write umi.tsv.gz (-u).", &A);
+    if (prc) return prc == 2 ? 0 : 1;
+    const char *cells = A.cells, *reads = A.list;
+    float rc[CAP_MAX_POINTS]; uint64_t caps[CAP_MAX_POINTS];
+    uint32_t n_c = 0, n_n = 0;
+    if (!reads) { fprintf(stderr, "\x1b[31mError:\x1b[0m cap needs -n <list>: the reads per cell at most\n"); return 1; }
+    if (fastf_sweep_parse_rates(cells, 1, rc, CAP_MAX_POINTS, &n_c) || fastf_cap_parse_caps(reads, caps, CAP_MAX_POINTS, &n_n) ||
+        fastf_cap_check_grid(rc, n_c, caps, n_n)) {
+        fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error());
+        return 1;
+    }
+    if (fastf_res_check_inputs(&A)) return 1;
+    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0)) {
+        fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
+        return 1;
+    }
+    printf("cap.tsv is generated.\n");
+    return 0;
+}

@@ -1,0 +1,353 @@
+/*
+ * resident.c — the resident pipeline of `fastF sweep` and `fastF cap` (resident.h): list loading with one dictionary, the decode
+ * of the BAM into device-resident records, per cell rate the engine + the records in its layout + K1a, per point K1b / sort /
+ * reduce / gather / summary and the writers.
+ */
+#define _GNU_SOURCE
+#include "resident.h"
+
+#include <errno.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <time.h>
+#include <unistd.h>
+
+double fastf_res_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec * 1e-9; }
+static int rs_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static int rs_err(const char *fmt, ...)
+{
+    char buf[480];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    fastf_set_error_(buf);
+    return 1;
+}
+
+int fastf_res_make_dir(const char *path)
+{
+    if (mkdir(path, 0777) == 0 || errno == EEXIST) return 0;
+    return rs_err("cannot create directory %s: %s", path, strerror(errno));
+}
+
+static uint32_t bits_for(uint64_t v) { uint32_t b = 0; while (b < 64 && (v >> b)) b++; return b ? b : 1; }
+
+/* ------------------------------------------------------------------ */
+/* lists                                                               */
+/* ------------------------------------------------------------------ */
+void fastf_res_lists_free(res_lists_t *l)
+{
+    if (l->keys) for (uint32_t i = 0; i < l->n; i++) free(l->keys[i]);
+    free(l->keys);
+    if (l->L) for (uint32_t i = 0; i < l->n; i++) fastf_lists_free(&l->L[i]);
+    free(l->L);
+    memset(l, 0, sizeof *l);
+}
+
+int fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c, uint32_t seed, res_lists_t *out)
+{
+    memset(out, 0, sizeof *out);
+    fastf_lists_t *L = out->L = (fastf_lists_t *)calloc(n_c, sizeof *L);
+    uint64_t **keys = out->keys = (uint64_t **)calloc(n_c, sizeof *keys);
+    if (!L || !keys) { rs_err("out of memory"); return RES_FAIL; }
+    for (uint32_t i = 0; i < n_c; i++) {
+        if (fastf_lists_load(barcodes, features, rates_cell[i], seed, &L[i])) return RES_FAIL;
+        out->n = i + 1;
+    }
+    for (uint32_t i = 0; i < n_c; i++) {
+        if (L[i].n_features != L[0].n_features) { rs_err("internal error: the feature list changed between loads"); return RES_FAIL; }
+        if (!(keys[i] = (uint64_t *)malloc((L[i].n_cells ? L[i].n_cells : 1) * sizeof **keys))) { rs_err("out of memory"); return RES_FAIL; }
+        for (size_t k = 0; k < L[i].n_cells; k++) keys[i][k] = fastf_keydict_add(L[0].cell_dict, L[i].barcode[k], strlen(L[i].barcode[k]));
+        /* keys wider than 64 bits with the shortest UMI field: that cell rate would need the wide engine */
+        if (bits_for(L[i].n_cells) + bits_for(L[i].n_features) + 27 > 64) return RES_NOT_COVERED;
+    }
+    return RES_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* the records                                                         */
+/* ------------------------------------------------------------------ */
+void fastf_res_free(resident_t *r)
+{
+    fastf_devmem_free(r->cb); fastf_devmem_free(r->gx); fastf_devmem_free(r->umi); fastf_devmem_free(r->meta);
+    r->cb = r->gx = NULL; r->umi = r->meta = NULL; r->cap = 0;
+}
+static int resident_reserve(resident_t *r, uint64_t need)
+{
+    if (need <= r->cap) return 0;
+    uint64_t cap = r->cap ? r->cap : ((uint64_t)8 << 20);
+    while (cap < need) cap *= 2;
+    resident_t nr = *r;
+    nr.cap = cap;
+    nr.cb = (uint64_t *)fastf_devmem_alloc(r->device, cap * 8); nr.gx = (uint64_t *)fastf_devmem_alloc(r->device, cap * 8);
+    nr.umi = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4); nr.meta = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4);
+    if (!nr.cb || !nr.gx || !nr.umi || !nr.meta) {
+        fastf_res_free(&nr);
+        return rs_err("%s: the records do not fit the device: %llu bytes were needed for %llu records", r->verb, (unsigned long long)(cap * 24), (unsigned long long)need);
+    }
+    if (r->n && (fastf_devmem_copy(nr.cb, r->cb, r->n * 8) || fastf_devmem_copy(nr.gx, r->gx, r->n * 8) ||
+                 fastf_devmem_copy(nr.umi, r->umi, r->n * 4) || fastf_devmem_copy(nr.meta, r->meta, r->n * 4))) { fastf_res_free(&nr); return 1; }
+    fastf_res_free(r);
+    *r = nr;
+    return 0;
+}
+
+/* R->device is set by the caller through `device`; on failure the caller releases R */
+int fastf_res_decode(const char *verb, const char *bam_file, const fastf_lists_t *L0, int device, resident_t *R)
+{
+    int rc = 1;
+    fastf_bam_t *bam = NULL;
+    void *stage = NULL;
+    memset(R, 0, sizeof *R); R->device = device; R->verb = verb;
+    {   const char *gp = getenv("FASTF_GPU_PARSE");
+        bam = fastf_bam_open2(bam_file, 0, 1 | ((gp && gp[0] == '0') ? 0 : 4) | ((device + 1) << 8)); }
+    if (!bam) { rs_err("Fail to open BAM file %s (%s)", bam_file, fastf_last_error()); goto done; }
+    (void)fastf_bam_enable_device_parse(bam, L0->cell_dict, L0->feat_dict);
+    const size_t cap = (size_t)4 << 20;
+    if (!(stage = fastf_pinned_alloc(cap * 24))) { rs_err("%s: no pinned staging memory (%s)", verb, fastf_last_error()); goto done; }
+    uint64_t *s_cb = (uint64_t *)stage, *s_gx = s_cb + cap; uint32_t *s_umi = (uint32_t *)(s_gx + cap), *s_meta = s_umi + cap;
+    for (;;) {
+        int on_dev = 0; fastf_batch_t dev; memset(&dev, 0, sizeof dev);
+        const long n = fastf_bam_read_batch_dev(bam, L0->cell_dict, L0->feat_dict, s_cb, s_gx, s_umi, s_meta, cap, &on_dev, &dev);
+        if (n < 0) { rs_err("%s: %s", bam_file, fastf_last_error()); goto done; }
+        if (n == 0) break;
+        if (R->n + (uint64_t)n >= ((uint64_t)1 << 32) - 1) { rs_err("%s: more than 2^32 - 2 records: %llu bytes of records are beyond what the device-level calls take", verb, (unsigned long long)((R->n + (uint64_t)n) * 24)); goto done; }
+        if (resident_reserve(R, R->n + (uint64_t)n)) goto done;
+        const uint64_t *f_cb = on_dev ? dev.cb_key : s_cb, *f_gx = on_dev ? dev.gx_key : s_gx;
+        const uint32_t *f_umi = on_dev ? dev.umi : s_umi, *f_meta = on_dev ? dev.meta : s_meta;
+        if (fastf_devmem_copy(R->cb + R->n, f_cb, (size_t)n * 8) || fastf_devmem_copy(R->gx + R->n, f_gx, (size_t)n * 8) ||
+            fastf_devmem_copy(R->umi + R->n, f_umi, (size_t)n * 4) || fastf_devmem_copy(R->meta + R->n, f_meta, (size_t)n * 4)) goto done;
+        R->n += (uint64_t)n;
+    }
+    {   uint64_t no_xf = 0, no_gx = 0;
+        fastf_bam_stats(bam, NULL, &no_xf, &no_gx);
+        if (no_xf || no_gx)
+            fprintf(stderr, "Note: %llu records with a CB but no xf tag and %llu with a valid xf but no GX tag were skipped "
+                            "(the reference dereferences NULL on them).\n", (unsigned long long)no_xf, (unsigned long long)no_gx); }
+    fastf_bam_close(bam); bam = NULL;
+    fastf_pinned_free(stage); stage = NULL;
+    if (resident_reserve(R, 1)) goto done;               /* (an empty BAM: the arrays exist) */
+    rc = 0;
+done:
+    if (bam) fastf_bam_close(bam);
+    if (stage) fastf_pinned_free(stage);
+    return rc;
+}
+
+/* ------------------------------------------------------------------ */
+/* one cell rate                                                       */
+/* ------------------------------------------------------------------ */
+void fastf_res_rate_close(res_rate_t *S)
+{
+    if (S->e) fastf_engine_destroy(S->e);
+    fastf_devmem_free(S->d_blk); fastf_devmem_free(S->d_keys); fastf_devmem_free(S->d_tmp); fastf_devmem_free(S->d_small);
+    fastf_devmem_free(S->d_rows); fastf_devmem_free(S->d_upc); fastf_devmem_free(S->d_gpc);
+    if (S->h_small) fastf_pinned_free(S->h_small);
+    if (S->h_upc) fastf_pinned_free(S->h_upc);
+    if (S->h_gpc) fastf_pinned_free(S->h_gpc);
+    if (S->h_rows) fastf_pinned_free(S->h_rows);
+    memset(S, 0, sizeof *S);
+}
+
+/* on anything but RES_OK the caller still calls fastf_res_rate_close */
+int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
+                        uint32_t seed, int device, res_times_t *T)
+{
+    memset(S, 0, sizeof *S);
+    S->verb = verb; S->R = R; S->L = L; S->device = device; S->rate_cell = rate_cell; S->seed = seed;
+    const uint64_t N = R->n;
+    const uint32_t n_cells = S->n_cells = (uint32_t)L->n_cells;
+    double tt = fastf_res_now();
+
+    fastf_engine_config_t cfg; memset(&cfg, 0, sizeof cfg);
+    cfg.cell_keys = cell_keys; cfg.n_cells = n_cells;
+    cfg.feature_keys = L->feature_key; cfg.n_features = (uint32_t)L->n_features;
+    cfg.draw_threshold = fastf_draw_threshold(1.0f);        /* (no part in the planes: every point brings its own threshold) */
+    cfg.mt_seed = seed; cfg.mt_skip = L->mt_skip;
+    cfg.n_shards = 1; cfg.device = device;
+    cfg.batch_records = (uint64_t)1 << 16;                  /* (the push path is not used) */
+    {   /* the UMI field as bam2db chooses it */
+        const char *ul = getenv("FASTF_UMI_MAX_BASES");
+        const uint32_t group_bits = bits_for(cfg.n_cells) + bits_for(cfg.n_features);
+        cfg.umi_max_bases = ul ? (uint32_t)atoi(ul) : ((group_bits + 36 <= 64 || group_bits + 27 > 64) ? 16 : 12);
+    }
+    if (cfg.umi_max_bases > 16) return RES_NOT_COVERED;
+    if (fastf_engine_create(&cfg, &S->e)) return RES_FAIL;
+    if (fastf_engine_is_wide(S->e)) return RES_NOT_COVERED;
+    T->engine += fastf_res_now() - tt; tt = fastf_res_now();
+
+    {   uint32_t cb, fb, ub; if (fastf_engine_key_bits(S->e, &cb, &fb, &ub, &S->key_bits)) return RES_FAIL; }
+    uint64_t blk_bytes = 0, seg_slots = 0;
+    if (fastf_dev_block_bytes(S->e, N, &blk_bytes) || fastf_dev_probe_capacity(S->e, N, &seg_slots)) return RES_FAIL;
+    S->blocked = blk_bytes != 0 && seg_slots != 0; S->segmented = seg_slots != 0;
+    S->key_slots = (seg_slots > N ? seg_slots : N) + 64;
+    S->kflags = FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS | (S->blocked ? FASTF_PROBE_BLOCKED : 0) | (S->segmented ? FASTF_PROBE_SEGMENTED : 0);
+    const size_t need = (S->blocked ? blk_bytes : 0) + 2 * S->key_slots * 8 + N * 12 + ((size_t)n_cells + 1) * 12;
+    if (!(S->d_small = fastf_devmem_alloc(device, SM_WORDS_ * 8)) || !(S->h_small = (uint64_t *)fastf_pinned_alloc(SM_WORDS_ * 8)) ||
+        (S->blocked && !(S->d_blk = fastf_devmem_alloc(device, blk_bytes))) ||
+        !(S->d_keys = fastf_devmem_alloc(device, S->key_slots * 8)) || !(S->d_tmp = fastf_devmem_alloc(device, S->key_slots * 8)) ||
+        !(S->d_rows = fastf_devmem_alloc(device, (N ? N : 1) * 12)) ||
+        !(S->d_upc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 8)) || !(S->d_gpc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 4)) ||
+        !(S->h_upc = (uint64_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 8)) || !(S->h_gpc = (uint32_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 4))) {
+        rs_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
+        return RES_FAIL;
+    }
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    if (fastf_devmem_zero(S->d_small, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
+
+    /* the records into the engine's layout, K1a once: the cell scratch and the hit count serve every point */
+    if (S->blocked) {
+        if (fastf_dev_block_records(S->e, R->gx, R->umi, R->meta, N, S->d_blk, NULL) ||
+            fastf_dev_count_hits_blocked(S->e, R->cb, N, S->d_blk, sm + SM_HITS, NULL)) return RES_FAIL;
+    } else if (fastf_dev_count_hits(S->e, R->cb, N, sm + SM_HITS, NULL)) return RES_FAIL;
+    if (fastf_devmem_sync() || fastf_devmem_copy(S->h_small, S->d_small, SM_WORDS_ * 8)) return RES_FAIL;
+    S->H = S->h_small[SM_HITS];
+    T->block_k1a += fastf_res_now() - tt;
+    return RES_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* one point                                                           */
+/* ------------------------------------------------------------------ */
+int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t counters[3], uint64_t *nnz_out, res_times_t *T)
+{
+    const resident_t *R = S->R;
+    const uint64_t N = R->n;
+    fastf_engine_t *e = S->e;
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint32_t *const d_f = (uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    double tt = fastf_res_now();
+    if (fastf_devmem_zero(S->d_small, SM_HITS * 8)) return RES_FAIL;
+    if (fastf_dev_probe_pack(e, R->cb, S->blocked ? (const uint64_t *)S->d_blk : R->gx, R->umi, R->meta, N, d_plane, S->H, sm + SM_BASE,
+                             (uint64_t *)S->d_keys, S->key_slots, sm + SM_KEYS, sm + SM_CNT, S->kflags, NULL)) return RES_FAIL;
+    int in_tmp = 0;
+    if (fastf_dev_sort(e, (uint64_t *)S->d_keys, (uint64_t *)S->d_tmp, sm + SM_KEYS, N, S->key_bits, FASTF_SORT_SKIP_LOW | (S->segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) return RES_FAIL;
+    uint64_t *src = in_tmp ? (uint64_t *)S->d_tmp : (uint64_t *)S->d_keys, *other = in_tmp ? (uint64_t *)S->d_keys : (uint64_t *)S->d_tmp;
+    if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
+    uint64_t bits = 0;
+    if (fastf_dev_error_bits(e, &bits)) return RES_FAIL;
+    if (bits & FASTF_ERR_RUN_TOO_LONG) {
+        /* deep (cell, feature) groups: sort fully and reduce again, as fastf_engine_finish does (every key is still there, permuted) */
+        int in_other = 0;
+        if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
+            fastf_dev_sort(e, src, other, sm + SM_KEYS, N, S->key_bits, 0, &in_other, NULL)) return RES_FAIL;
+        if (in_other) src = other;
+        if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_REDUCE_SEGMENTED, NULL) || fastf_dev_error_bits(e, &bits)) return RES_FAIL;
+    }
+    if (fastf_devmem_copy(S->h_small, S->d_small, SM_HITS * 8)) return RES_FAIL;
+    bits |= S->h_small[SM_CNT + 3];
+    if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: bam2db() runs such a file again with wider keys */
+    if (bits) { rs_err("%s: device error bits 0x%llx at point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
+    counters[0] = N; counters[1] = S->h_small[SM_CNT + 1]; counters[2] = S->h_small[SM_CNT + 2];
+    const uint64_t nnz = *nnz_out = S->h_small[SM_NNZ];
+    if (nnz > N) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N); return RES_FAIL; }
+    /* the rows, concatenated on the device, and their per-cell summary */
+    if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
+        fastf_dev_cell_summary(e, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_cells, (uint64_t *)S->d_upc, (uint32_t *)S->d_gpc, NULL) ||
+        fastf_devmem_sync()) return RES_FAIL;
+    T->device += fastf_res_now() - tt; tt = fastf_res_now();
+    if (fastf_devmem_copy(S->h_upc, S->d_upc, ((size_t)S->n_cells + 1) * 8) || fastf_devmem_copy(S->h_gpc, S->d_gpc, (size_t)S->n_cells * 4)) return RES_FAIL;
+    T->summary += fastf_res_now() - tt;
+    return RES_OK;
+}
+
+int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz, res_times_t *T)
+{
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    double tt = fastf_res_now();
+    if (nnz > S->h_rows_cap) {
+        if (S->h_rows) fastf_pinned_free(S->h_rows);
+        S->h_rows_cap = nnz + nnz / 8 + 1024;
+        if (!(S->h_rows = (uint32_t *)fastf_pinned_alloc(S->h_rows_cap * 12))) { S->h_rows_cap = 0; return rs_err("%s: no pinned memory for %llu matrix rows", S->verb, (unsigned long long)nnz); }
+    }
+    uint32_t *const h_rows = S->h_rows; const uint64_t cap = S->h_rows_cap;
+    fastf_coo_t coo = { h_rows, h_rows + cap, h_rows + 2 * cap, (size_t)nnz };
+    /* (the gather kernel writes pinned host memory directly: it is the device-to-host copy of the rows) */
+    if (nnz && (fastf_dev_rows_gather(S->e, sm + SM_KEYS, h_rows, h_rows + cap, h_rows + 2 * cap, NULL) || fastf_devmem_sync())) return 1;
+    T->d2h += fastf_res_now() - tt; tt = fastf_res_now();
+    if (fastf_res_make_dir(dir) || fastf_write_outputs(dir, bam_label, S->rate_cell, rate_depth, counters, S->L, &coo, NULL)) return 1;
+    T->write += fastf_res_now() - tt;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* the summary table, the command line                                 */
+/* ------------------------------------------------------------------ */
+int fastf_res_tsv_open(res_tsv_t *t, const char *out_dir, const char *name, const char *header)
+{
+    snprintf(t->final, sizeof t->final, "%s/%s", out_dir, name);
+    snprintf(t->tmp, sizeof t->tmp, "%s/%s.partial", out_dir, name);
+    if (!(t->f = fopen(t->tmp, "w"))) return rs_err("cannot open %s: %s", t->tmp, strerror(errno));
+    fputs(header, t->f);
+    return 0;
+}
+int fastf_res_tsv_close(res_tsv_t *t, int ok)
+{
+    if (!t->f) return 0;
+    const int bad = ferror(t->f) | (fclose(t->f) != 0);
+    t->f = NULL;
+    if (ok && !bad && rename(t->tmp, t->final) == 0) return 0;
+    unlink(t->tmp);
+    return ok ? rs_err("cannot write %s", t->final) : 0;
+}
+
+struct ropt { char s; const char *l; int has_arg; };
+int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
+                         res_args_t *out)
+{
+    const struct ropt opts[] = {
+        {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {0, NULL, 0}};
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0;
+    for (int i = 1; i < argc; i++) {
+        const char *a = argv[i];
+        const struct ropt *o = NULL;
+        const char *val = NULL;
+        if (a[0] != '-' || !a[1]) break;
+        if (a[1] == '-') {
+            if (!a[2]) break;
+            const char *eq = strchr(a + 2, '=');
+            const size_t nl = eq ? (size_t)(eq - a - 2) : strlen(a + 2);
+            for (const struct ropt *k = opts; k->l; k++)
+                if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
+            if (o && eq) val = eq + 1;
+        } else {
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S') { o = k; break; }
+            if (o && o->has_arg && a[2]) val = a + 2;
+        }
+        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
+        char oname[32];
+        if (a[1] == '-') snprintf(oname, sizeof oname, "--%s", o->l); else snprintf(oname, sizeof oname, "-%c", o->s);
+        if (o->has_arg && !val) {
+            if (i + 1 >= argc) { fprintf(stderr, "error: option `%s` requires a value\n", oname); return 1; }
+            val = argv[++i];
+        }
+        char *end = NULL;
+        if (o->s == list_short) { out->list = val; continue; }
+        switch (o->s) {
+        case 'h': usage(stdout); return 2;
+        case 'b': out->bam = val; break;
+        case 'f': out->feat = val; break;
+        case 'a': out->bar = val; break;
+        case 'd': break;
+        case 'o': out->out = val; break;
+        case 'c': out->cells = val; break;
+        case 's': errno = 0; out->seed = (unsigned int)strtol(val, &end, 0);
+                  if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); return 1; }
+                  if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); return 1; }
+                  break;
+        case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", u_message); return 1;
+        case 'S': out->summary_only = 1; break;
+        }
+    }
+    return 0;
+}
+/* (after the verb has parsed its lists: the order of the messages of cmd_sweep) */
+int fastf_res_check_inputs(const res_args_t *a)
+{
+    if (!a->bam || access(a->bam, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m bam file: %s does not exist.\n", a->bam ? a->bam : "(null)"); return 1; }
+    if (!a->feat || access(a->feat, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m feature file: %s does not exist.\n", a->feat ? a->feat : "(null)"); return 1; }
+    if (!a->bar || access(a->bar, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m barcode file: %s does not exist.\n", a->bar ? a->bar : "(null)"); return 1; }
+    return 0;
+}

@@ -1,0 +1,83 @@
+/* resident.h — the resident pipeline `fastF sweep` and `fastF cap` share (resident.c): the packed records of a BAM stay in device
+ * memory after ONE decode; per cell rate one engine, the records in its layout and K1a once; per point K1b on that point's
+ * decision plane, sort, reduce, the per-cell summary and — when the matrices are wanted — the rows gathered into pinned memory
+ * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made. */
+#ifndef FASTF_RESIDENT_H
+#define FASTF_RESIDENT_H
+
+#include "host_io.h"
+
+#include <stdio.h>
+
+#define FASTF_HIDDEN __attribute__((visibility("hidden")))
+
+/* device memory for the C side of the library (umi_engine.hip) */
+void *fastf_devmem_alloc(int device, size_t bytes);
+void  fastf_devmem_free(void *p);
+int   fastf_devmem_copy(void *dst, const void *src, size_t bytes);
+int   fastf_devmem_zero(void *dst, size_t bytes);
+int   fastf_devmem_sync(void);
+
+enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys wider than 64 bits or UMIs beyond what a 64-bit key holds */
+/* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
+enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_WORDS_ = 160 };
+
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write; } res_times_t;
+
+double fastf_res_now(void) FASTF_HIDDEN;
+int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
+
+/* the lists of every cell rate, and ONE dictionary for the records: the first rate's, with the barcodes of the others registered
+ * in it — a key then means the same string whichever rate's table it is looked up in.  keys[i][k]: key of cell k + 1 at rate i */
+typedef struct { uint32_t n; fastf_lists_t *L; uint64_t **keys; } res_lists_t;
+int  fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c, uint32_t seed, res_lists_t *out) FASTF_HIDDEN;
+void fastf_res_lists_free(res_lists_t *l) FASTF_HIDDEN;
+
+/* the packed records (24 bytes each) in device memory */
+typedef struct {
+    int device; const char *verb;
+    uint64_t n, cap;                     /* records held, room */
+    uint64_t *cb, *gx; uint32_t *umi, *meta;   /* device arrays of cap entries */
+} resident_t;
+int  fastf_res_decode(const char *verb, const char *bam_file, const fastf_lists_t *L0, int device, resident_t *R) FASTF_HIDDEN;
+void fastf_res_free(resident_t *R) FASTF_HIDDEN;
+
+/* one cell rate: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point), the buffers
+ * of a point */
+typedef struct {
+    const char *verb; const resident_t *R; const fastf_lists_t *L; int device; float rate_cell; uint32_t seed;
+    fastf_engine_t *e;
+    uint32_t n_cells, key_bits, kflags; int blocked, segmented;
+    uint64_t key_slots, H;
+    void *d_blk, *d_keys, *d_tmp, *d_small, *d_rows, *d_upc, *d_gpc;
+    uint64_t *h_small, *h_upc; uint32_t *h_gpc, *h_rows; uint64_t h_rows_cap;
+} res_rate_t;
+int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
+                         uint32_t seed, int device, res_times_t *T) FASTF_HIDDEN;
+void fastf_res_rate_close(res_rate_t *S) FASTF_HIDDEN;
+/* one point: K1b on the decision plane (H decisions), sort, reduce, rows gathered on the device, per-cell summary to the host
+ * (S->h_upc[0 .. n_cells]: UMIs per cell and their sum, S->h_gpc: genes per cell); counters = {total, sampled, sampled_valid} */
+int  fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t counters[3], uint64_t *nnz, res_times_t *T) FASTF_HIDDEN;
+/* the rows of the last point into pinned memory, and the three files of bam2db into dir (created) */
+int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz,
+                           res_times_t *T) FASTF_HIDDEN;
+
+/* the summary table of a verb: written as <out_dir>/<name>.partial, renamed to <out_dir>/<name> by a close with ok != 0; otherwise
+ * nothing of it is left */
+typedef struct { FILE *f; char tmp[4096], final[4096]; } res_tsv_t;
+int fastf_res_tsv_open(res_tsv_t *t, const char *out_dir, const char *name, const char *header) FASTF_HIDDEN;
+int fastf_res_tsv_close(res_tsv_t *t, int ok) FASTF_HIDDEN;
+
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only and ONE list option of the verb's own (list_short /
+ * list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
+ * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists). */
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only; } res_args_t;
+int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
+                         res_args_t *a) FASTF_HIDDEN;
+int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;
+
+/* sweep_cmds.c: the columns of a summary row from `seed` on (no newline) */
+int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
+                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap) FASTF_HIDDEN;
+
+#endif

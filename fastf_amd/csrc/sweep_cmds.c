@@ -6,7 +6,7 @@
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
  * writes for that point — and one row of <out>/sweep.tsv.
  *
- * Resident form: the packed records (24 bytes each) stay in device memory.  Per cell rate one engine, the records in its
+ * Resident form (resident.c, shared with `fastF cap`): the packed records (24 bytes each) stay in device memory.  Per cell rate one engine, the records in its
  * layout, K1a once; the draw stream generated once and compared against every depth threshold in the same pass
  * (fastf_dev_mt_decisions_multi); per depth rate K1b on that point's decision plane, sort, reduce, the per-cell summary
  * (fastf_dev_cell_summary), and — unless --summary-only — the rows gathered into pinned memory for the writers of bam2db.
@@ -14,7 +14,7 @@
  * through bam2db() itself, the summary then read back from each point's matrix.
  */
 #define _GNU_SOURCE
-#include "host_io.h"
+#include "resident.h"
 
 #include <errno.h>
 #include <math.h>
@@ -26,14 +26,6 @@
 #include <time.h>
 #include <unistd.h>
 
-/* device memory for this file (umi_engine.hip) */
-void *fastf_devmem_alloc(int device, size_t bytes);
-void  fastf_devmem_free(void *p);
-int   fastf_devmem_copy(void *dst, const void *src, size_t bytes);
-int   fastf_devmem_zero(void *dst, size_t bytes);
-int   fastf_devmem_sync(void);
-
-static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec * 1e-9; }
 static int sw_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 static int sw_err(const char *fmt, ...)
 {
@@ -144,9 +136,9 @@ int fastf_sweep_cells_from_coo(const fastf_coo_t *coo, uint32_t n_cells, uint64_
     return 0;
 }
 
-/* one row of sweep.tsv (with its newline) */
-int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
-                            const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
+/* the columns from `seed` on (no newline): shared with cap.tsv */
+int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
+                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
 {
     if (!counters || !buf || (n_cells && (!umis_per_cell || !genes_per_cell))) return sw_err("null argument");
     uint64_t *tmp = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *tmp);
@@ -157,40 +149,25 @@ int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, co
     const double med_g = median_u64(tmp, n_cells);
     free(tmp);
     const double sat = counters[2] ? 1.0 - (double)umis / (double)counters[2] : 0.0;
-    const int n = snprintf(buf, cap, "%.3f\t%.3f\t%u\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\t%.1f\t%.1f\n", (double)rate_cell, (double)rate_depth,
-                           seed, n_cells, (unsigned long long)counters[0], (unsigned long long)counters[1], (unsigned long long)counters[2],
-                           (unsigned long long)nnz, (unsigned long long)umis, sat, med_u, med_g);
+    const int n = snprintf(buf, cap, "%u\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\t%.1f\t%.1f", seed, n_cells, (unsigned long long)counters[0],
+                           (unsigned long long)counters[1], (unsigned long long)counters[2], (unsigned long long)nnz, (unsigned long long)umis, sat, med_u, med_g);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+/* one row of sweep.tsv (with its newline) */
+int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                            const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
+{
+    char tail[400];
+    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail)) return 1;
+    const int n = snprintf(buf, cap, "%.3f\t%.3f\t%s\n", (double)rate_cell, (double)rate_depth, tail);
     return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
 }
 
 /* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
-static int make_dir(const char *path)
-{
-    if (mkdir(path, 0777) == 0 || errno == EEXIST) return 0;
-    return sw_err("cannot create directory %s: %s", path, strerror(errno));
-}
-
-typedef struct { FILE *f; char tmp[4096], final[4096]; } tsv_out;
-static int tsv_open(tsv_out *t, const char *out_dir)
-{
-    snprintf(t->final, sizeof t->final, "%s/sweep.tsv", out_dir);
-    snprintf(t->tmp, sizeof t->tmp, "%s/sweep.tsv.partial", out_dir);
-    if (!(t->f = fopen(t->tmp, "w"))) return sw_err("cannot open %s: %s", t->tmp, strerror(errno));
-    fputs(fastf_sweep_header(), t->f);
-    return 0;
-}
-/* ok: the table appears under its name; otherwise nothing of it is left */
-static int tsv_close(tsv_out *t, int ok)
-{
-    if (!t->f) return 0;
-    const int bad = ferror(t->f) | (fclose(t->f) != 0);
-    t->f = NULL;
-    if (ok && !bad && rename(t->tmp, t->final) == 0) return 0;
-    unlink(t->tmp);
-    return ok ? sw_err("cannot write %s", t->final) : 0;
-}
+static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
 
 /* ------------------------------------------------------------------ */
 /* point by point through bam2db()                                     */
@@ -237,7 +214,7 @@ done:
 }
 
 static int sweep_point_by_point(const char *bam, const char *out_dir, const char *barcodes, const char *features,
-                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, tsv_out *tsv)
+                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, res_tsv_t *tsv)
 {
     const int saved_u = _umi_copies_flag;
     _umi_copies_flag = 0;
@@ -248,7 +225,7 @@ static int sweep_point_by_point(const char *bam, const char *out_dir, const char
             if (fastf_sweep_point_dir(rc_list[i], rd_list[j], name, sizeof name)) goto done;
             if (summary_only) snprintf(dir, sizeof dir, "%s/.%s.partial", out_dir, name);      /* (removed again below) */
             else snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (make_dir(dir)) goto done;
+            if (fastf_res_make_dir(dir)) goto done;
             const int brc = bam2db((char *)bam, NULL, dir, (char *)barcodes, (char *)features, rc_list[i], rd_list[j], seed);
             uint64_t counters[3]; uint32_t n_cells = 0; fastf_coo_t coo; uint32_t *rows = NULL;
             snprintf(path, sizeof path, "%s/matrix.mtx.gz", dir);
@@ -277,179 +254,49 @@ done:
 }
 
 /* ------------------------------------------------------------------ */
-/* resident form                                                       */
+/* resident form (the pipeline itself: resident.c)                     */
 /* ------------------------------------------------------------------ */
-typedef struct {
-    int device;
-    uint64_t n, cap;                     /* records held, room */
-    uint64_t *cb, *gx; uint32_t *umi, *meta;   /* device arrays of cap entries */
-} resident_t;
-
-static void resident_free(resident_t *r)
-{
-    fastf_devmem_free(r->cb); fastf_devmem_free(r->gx); fastf_devmem_free(r->umi); fastf_devmem_free(r->meta);
-    r->cb = r->gx = NULL; r->umi = r->meta = NULL; r->cap = 0;
-}
-static int resident_reserve(resident_t *r, uint64_t need)
-{
-    if (need <= r->cap) return 0;
-    uint64_t cap = r->cap ? r->cap : ((uint64_t)8 << 20);
-    while (cap < need) cap *= 2;
-    resident_t nr = *r;
-    nr.cap = cap;
-    nr.cb = (uint64_t *)fastf_devmem_alloc(r->device, cap * 8); nr.gx = (uint64_t *)fastf_devmem_alloc(r->device, cap * 8);
-    nr.umi = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4); nr.meta = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4);
-    if (!nr.cb || !nr.gx || !nr.umi || !nr.meta) {
-        resident_free(&nr);
-        return sw_err("sweep: the records do not fit the device: %llu bytes were needed for %llu records", (unsigned long long)(cap * 24), (unsigned long long)need);
-    }
-    if (r->n && (fastf_devmem_copy(nr.cb, r->cb, r->n * 8) || fastf_devmem_copy(nr.gx, r->gx, r->n * 8) ||
-                 fastf_devmem_copy(nr.umi, r->umi, r->n * 4) || fastf_devmem_copy(nr.meta, r->meta, r->n * 4))) { resident_free(&nr); return 1; }
-    resident_free(r);
-    *r = nr;
-    return 0;
-}
-
-static uint32_t bits_for(uint64_t v) { uint32_t b = 0; while (b < 64 && (v >> b)) b++; return b ? b : 1; }
-
-enum { SW_OK = 0, SW_FAIL = 1, SW_NOT_COVERED = 2 };
-/* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
-enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_WORDS_ = 160 };
-
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write; } sweep_times;
-
 /* one cell rate: the engine, the records in its layout, K1a, the planes, then every depth rate */
 static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           sweep_times *T)
+                           res_times_t *T)
 {
-    int rc = SW_FAIL;
-    const uint64_t N = R->n;
-    const uint32_t n_cells = (uint32_t)L->n_cells;
-    fastf_engine_t *e = NULL;
-    void *d_blk = NULL, *d_keys = NULL, *d_tmp = NULL, *d_planes = NULL, *d_small = NULL, *d_rows = NULL, *d_upc = NULL, *d_gpc = NULL;
-    uint64_t *h_small = NULL, *h_upc = NULL; uint32_t *h_gpc = NULL, *h_rows = NULL; uint64_t h_rows_cap = 0;
+    int rc = RES_FAIL;
+    res_rate_t S;
+    void *d_planes = NULL;
     uint64_t *thr = (uint64_t *)malloc(n_r * sizeof *thr);
-    double tt = now_s();
-
-    fastf_engine_config_t cfg; memset(&cfg, 0, sizeof cfg);
-    cfg.cell_keys = cell_keys; cfg.n_cells = n_cells;
-    cfg.feature_keys = L->feature_key; cfg.n_features = (uint32_t)L->n_features;
-    cfg.draw_threshold = fastf_draw_threshold(1.0f);        /* (no part in the planes: every point brings its own threshold) */
-    cfg.mt_seed = seed; cfg.mt_skip = L->mt_skip;
-    cfg.n_shards = 1; cfg.device = device;
-    cfg.batch_records = (uint64_t)1 << 16;                  /* (the push path is not used) */
-    {   /* the UMI field as bam2db chooses it */
-        const char *ul = getenv("FASTF_UMI_MAX_BASES");
-        const uint32_t group_bits = bits_for(cfg.n_cells) + bits_for(cfg.n_features);
-        cfg.umi_max_bases = ul ? (uint32_t)atoi(ul) : ((group_bits + 36 <= 64 || group_bits + 27 > 64) ? 16 : 12);
-    }
-    if (!thr) { sw_err("out of memory"); goto done; }
-    if (cfg.umi_max_bases > 16) { rc = SW_NOT_COVERED; goto done; }
-    if (fastf_engine_create(&cfg, &e)) goto done;
-    if (fastf_engine_is_wide(e)) { rc = SW_NOT_COVERED; goto done; }
-    T->engine += now_s() - tt; tt = now_s();
-
-    uint32_t key_bits = 0;
-    {   uint32_t cb, fb, ub; if (fastf_engine_key_bits(e, &cb, &fb, &ub, &key_bits)) goto done; }
-    uint64_t blk_bytes = 0, seg_slots = 0;
-    if (fastf_dev_block_bytes(e, N, &blk_bytes) || fastf_dev_probe_capacity(e, N, &seg_slots)) goto done;
-    const int blocked = blk_bytes != 0 && seg_slots != 0, segmented = seg_slots != 0;
-    const uint64_t key_slots = (seg_slots > N ? seg_slots : N) + 64;
-    const uint32_t kflags = FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS | (blocked ? FASTF_PROBE_BLOCKED : 0) | (segmented ? FASTF_PROBE_SEGMENTED : 0);
-    const size_t need = (blocked ? blk_bytes : 0) + 2 * key_slots * 8 + N * 12 + ((size_t)n_cells + 1) * 12;
-    if (!(d_small = fastf_devmem_alloc(device, SM_WORDS_ * 8)) || !(h_small = (uint64_t *)fastf_pinned_alloc(SM_WORDS_ * 8)) ||
-        (blocked && !(d_blk = fastf_devmem_alloc(device, blk_bytes))) ||
-        !(d_keys = fastf_devmem_alloc(device, key_slots * 8)) || !(d_tmp = fastf_devmem_alloc(device, key_slots * 8)) ||
-        !(d_rows = fastf_devmem_alloc(device, (N ? N : 1) * 12)) ||
-        !(d_upc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 8)) || !(d_gpc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 4)) ||
-        !(h_upc = (uint64_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 8)) || !(h_gpc = (uint32_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 4))) {
-        sw_err("sweep: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", (double)rate_cell, need, fastf_last_error());
-        goto done;
-    }
-    uint64_t *const sm = (uint64_t *)d_small;
-    uint32_t *const d_f = (uint32_t *)d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
-    if (fastf_devmem_zero(d_small, SM_WORDS_ * 8) || fastf_dev_reserve(e, blocked ? 0 : N, N)) goto done;
-
-    /* the records into the engine's layout, K1a once: the cell scratch and the hit count serve every depth rate */
-    if (blocked) {
-        if (fastf_dev_block_records(e, R->gx, R->umi, R->meta, N, d_blk, NULL) ||
-            fastf_dev_count_hits_blocked(e, R->cb, N, d_blk, sm + SM_HITS, NULL)) goto done;
-    } else if (fastf_dev_count_hits(e, R->cb, N, sm + SM_HITS, NULL)) goto done;
-    if (fastf_devmem_sync() || fastf_devmem_copy(h_small, d_small, SM_WORDS_ * 8)) goto done;
-    const uint64_t H = h_small[SM_HITS];
-    T->block_k1a += now_s() - tt; tt = now_s();
+    if (!thr) { sw_err("out of memory"); memset(&S, 0, sizeof S); goto done; }
+    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, T)) != RES_OK) goto done;
+    rc = RES_FAIL;
+    const uint64_t H = S.H;
+    double tt = fastf_res_now();
 
     /* the decision planes: the draw stream once, every threshold in the same pass */
     const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
     if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_r * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_r * plane_words * 4)) goto done;
     for (uint32_t j = 0; j < n_r; j++) thr[j] = fastf_draw_threshold(rd_list[j]);
-    if (fastf_dev_mt_decisions_multi(e, seed, L->mt_skip, H, thr, n_r, (uint32_t *)d_planes, plane_words, NULL)) goto done;
-    T->planes += now_s() - tt;
+    if (fastf_dev_mt_decisions_multi(S.e, seed, L->mt_skip, H, thr, n_r, (uint32_t *)d_planes, plane_words, NULL)) goto done;
+    T->planes += fastf_res_now() - tt;
 
     for (uint32_t j = 0; j < n_r; j++) {
-        tt = now_s();
-        const uint32_t *plane = (const uint32_t *)d_planes + (size_t)j * plane_words;
-        if (fastf_devmem_zero(d_small, SM_HITS * 8)) goto done;
-        if (fastf_dev_probe_pack(e, R->cb, blocked ? (const uint64_t *)d_blk : R->gx, R->umi, R->meta, N, plane, H, sm + SM_BASE,
-                                 (uint64_t *)d_keys, key_slots, sm + SM_KEYS, sm + SM_CNT, kflags, NULL)) goto done;
-        int in_tmp = 0;
-        if (fastf_dev_sort(e, (uint64_t *)d_keys, (uint64_t *)d_tmp, sm + SM_KEYS, N, key_bits, FASTF_SORT_SKIP_LOW | (segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) goto done;
-        uint64_t *src = in_tmp ? (uint64_t *)d_tmp : (uint64_t *)d_keys, *other = in_tmp ? (uint64_t *)d_keys : (uint64_t *)d_tmp;
-        if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) goto done;
-        uint64_t bits = 0;
-        if (fastf_dev_error_bits(e, &bits)) goto done;
-        if (bits & FASTF_ERR_RUN_TOO_LONG) {
-            /* deep (cell, feature) groups: sort fully and reduce again, as fastf_engine_finish does (every key is still there, permuted) */
-            int in_other = 0;
-            if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
-                fastf_dev_sort(e, src, other, sm + SM_KEYS, N, key_bits, 0, &in_other, NULL)) goto done;
-            if (in_other) src = other;
-            if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_REDUCE_SEGMENTED, NULL) || fastf_dev_error_bits(e, &bits)) goto done;
-        }
-        if (fastf_devmem_copy(h_small, d_small, SM_HITS * 8)) goto done;
-        bits |= h_small[SM_CNT + 3];
-        if (bits & 4) { rc = SW_NOT_COVERED; goto done; }       /* UMIs longer than the key holds: bam2db() runs such a file again with wider keys */
-        if (bits) { sw_err("sweep: device error bits 0x%llx at point c%.3f_r%.3f", (unsigned long long)bits, (double)rate_cell, (double)rd_list[j]); goto done; }
-        const uint64_t counters[3] = { N, h_small[SM_CNT + 1], h_small[SM_CNT + 2] };
-        const uint64_t nnz = h_small[SM_NNZ];
-        if (nnz > N) { sw_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N); goto done; }
-        /* the rows, concatenated on the device, and their per-cell summary */
-        if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
-            fastf_dev_cell_summary(e, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, n_cells, (uint64_t *)d_upc, (uint32_t *)d_gpc, NULL) ||
-            fastf_devmem_sync()) goto done;
-        T->device += now_s() - tt; tt = now_s();
-        if (fastf_devmem_copy(h_upc, d_upc, ((size_t)n_cells + 1) * 8) || fastf_devmem_copy(h_gpc, d_gpc, (size_t)n_cells * 4)) goto done;
-        char row[512];
-        if (fastf_sweep_summary_row(rate_cell, rd_list[j], seed, counters, nnz, h_upc[n_cells], h_upc, h_gpc, n_cells, row, sizeof row)) goto done;
-        T->summary += now_s() - tt; tt = now_s();
+        char name[64], dir[4096], row[512];
+        uint64_t counters[3], nnz = 0;
+        if (fastf_sweep_point_dir(rate_cell, rd_list[j], name, sizeof name)) goto done;
+        const int prc = fastf_res_point_run(&S, (const uint32_t *)d_planes + (size_t)j * plane_words, name, counters, &nnz, T);
+        if (prc != RES_OK) { rc = prc; goto done; }
+        tt = fastf_res_now();
+        if (fastf_sweep_summary_row(rate_cell, rd_list[j], seed, counters, nnz, S.h_upc[S.n_cells], S.h_upc, S.h_gpc, S.n_cells, row, sizeof row)) goto done;
+        T->summary += fastf_res_now() - tt;
         if (!summary_only) {
-            if (nnz > h_rows_cap) {
-                if (h_rows) fastf_pinned_free(h_rows);
-                h_rows_cap = nnz + nnz / 8 + 1024;
-                if (!(h_rows = (uint32_t *)fastf_pinned_alloc(h_rows_cap * 12))) { h_rows_cap = 0; sw_err("sweep: no pinned memory for %llu matrix rows", (unsigned long long)nnz); goto done; }
-            }
-            fastf_coo_t coo = { h_rows, h_rows + h_rows_cap, h_rows + 2 * h_rows_cap, (size_t)nnz };
-            /* (the gather kernel writes pinned host memory directly: it is the device-to-host copy of the rows) */
-            if (nnz && (fastf_dev_rows_gather(e, sm + SM_KEYS, h_rows, h_rows + h_rows_cap, h_rows + 2 * h_rows_cap, NULL) || fastf_devmem_sync())) goto done;
-            T->d2h += now_s() - tt; tt = now_s();
-            char name[64], dir[4096];
-            if (fastf_sweep_point_dir(rate_cell, rd_list[j], name, sizeof name)) goto done;
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (make_dir(dir) || fastf_write_outputs(dir, bam_label, rate_cell, rd_list[j], counters, L, &coo, NULL)) goto done;
-            T->write += now_s() - tt;
+            if (fastf_res_point_write(&S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
         }
         fputs(row, tsv);
     }
-    rc = SW_OK;
+    rc = RES_OK;
 done:
-    if (e) fastf_engine_destroy(e);
-    fastf_devmem_free(d_blk); fastf_devmem_free(d_keys); fastf_devmem_free(d_tmp); fastf_devmem_free(d_planes); fastf_devmem_free(d_small);
-    fastf_devmem_free(d_rows); fastf_devmem_free(d_upc); fastf_devmem_free(d_gpc);
-    if (h_small) fastf_pinned_free(h_small);
-    if (h_upc) fastf_pinned_free(h_upc);
-    if (h_gpc) fastf_pinned_free(h_gpc);
-    if (h_rows) fastf_pinned_free(h_rows);
+    fastf_res_rate_close(&S);
+    fastf_devmem_free(d_planes);
     free(thr);
     return rc;
 }
@@ -457,79 +304,32 @@ done:
 static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
                           const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv)
 {
-    int rc = SW_FAIL;
+    int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
-    sweep_times T; memset(&T, 0, sizeof T);
-    const double t0 = now_s();
+    res_times_t T; memset(&T, 0, sizeof T);
+    const double t0 = fastf_res_now();
     double tt = t0;
-    fastf_lists_t *L = (fastf_lists_t *)calloc(n_c, sizeof *L);
-    uint64_t **keys = (uint64_t **)calloc(n_c, sizeof *keys);
-    fastf_bam_t *bam = NULL;
-    resident_t R; memset(&R, 0, sizeof R); R.device = device;
-    void *stage = NULL;
-    if (!L || !keys) { sw_err("out of memory"); goto done; }
-
-    /* the lists of every cell rate, and ONE dictionary for the records: the first rate's, with the barcodes of the others
-     * registered in it — a key then means the same string whichever rate's table it is looked up in */
-    for (uint32_t i = 0; i < n_c; i++)
-        if (fastf_lists_load(barcodes, features, rc_list[i], seed, &L[i])) { n_c = i; goto done; }
-    for (uint32_t i = 0; i < n_c; i++) {
-        if (L[i].n_features != L[0].n_features) { sw_err("internal error: the feature list changed between loads"); goto done; }
-        if (!(keys[i] = (uint64_t *)malloc((L[i].n_cells ? L[i].n_cells : 1) * sizeof **keys))) { sw_err("out of memory"); goto done; }
-        for (size_t k = 0; k < L[i].n_cells; k++) keys[i][k] = fastf_keydict_add(L[0].cell_dict, L[i].barcode[k], strlen(L[i].barcode[k]));
-        /* keys wider than 64 bits with the shortest UMI field: that cell rate would need the wide engine */
-        if (bits_for(L[i].n_cells) + bits_for(L[i].n_features) + 27 > 64) { rc = SW_NOT_COVERED; goto done; }
-    }
-    T.lists = now_s() - tt; tt = now_s();
-
-    {   const char *gp = getenv("FASTF_GPU_PARSE");
-        bam = fastf_bam_open2(bam_file, 0, 1 | ((gp && gp[0] == '0') ? 0 : 4) | ((device + 1) << 8)); }
-    if (!bam) { sw_err("Fail to open BAM file %s (%s)", bam_file, fastf_last_error()); goto done; }
-    (void)fastf_bam_enable_device_parse(bam, L[0].cell_dict, L[0].feat_dict);
-    const size_t cap = (size_t)4 << 20;
-    if (!(stage = fastf_pinned_alloc(cap * 24))) { sw_err("sweep: no pinned staging memory (%s)", fastf_last_error()); goto done; }
-    uint64_t *s_cb = (uint64_t *)stage, *s_gx = s_cb + cap; uint32_t *s_umi = (uint32_t *)(s_gx + cap), *s_meta = s_umi + cap;
-    for (;;) {
-        int on_dev = 0; fastf_batch_t dev; memset(&dev, 0, sizeof dev);
-        const long n = fastf_bam_read_batch_dev(bam, L[0].cell_dict, L[0].feat_dict, s_cb, s_gx, s_umi, s_meta, cap, &on_dev, &dev);
-        if (n < 0) { sw_err("%s: %s", bam_file, fastf_last_error()); goto done; }
-        if (n == 0) break;
-        if (R.n + (uint64_t)n >= ((uint64_t)1 << 32) - 1) { sw_err("sweep: more than 2^32 - 2 records: %llu bytes of records are beyond what the device-level calls take", (unsigned long long)((R.n + (uint64_t)n) * 24)); goto done; }
-        if (resident_reserve(&R, R.n + (uint64_t)n)) goto done;
-        const uint64_t *f_cb = on_dev ? dev.cb_key : s_cb, *f_gx = on_dev ? dev.gx_key : s_gx;
-        const uint32_t *f_umi = on_dev ? dev.umi : s_umi, *f_meta = on_dev ? dev.meta : s_meta;
-        if (fastf_devmem_copy(R.cb + R.n, f_cb, (size_t)n * 8) || fastf_devmem_copy(R.gx + R.n, f_gx, (size_t)n * 8) ||
-            fastf_devmem_copy(R.umi + R.n, f_umi, (size_t)n * 4) || fastf_devmem_copy(R.meta + R.n, f_meta, (size_t)n * 4)) goto done;
-        R.n += (uint64_t)n;
-    }
-    {   uint64_t no_xf = 0, no_gx = 0;
-        fastf_bam_stats(bam, NULL, &no_xf, &no_gx);
-        if (no_xf || no_gx)
-            fprintf(stderr, "Note: %llu records with a CB but no xf tag and %llu with a valid xf but no GX tag were skipped "
-                            "(the reference dereferences NULL on them).\n", (unsigned long long)no_xf, (unsigned long long)no_gx); }
-    fastf_bam_close(bam); bam = NULL;
-    fastf_pinned_free(stage); stage = NULL;
-    if (resident_reserve(&R, 1)) goto done;               /* (an empty BAM: the arrays exist) */
-    T.decode = now_s() - tt;
+    res_lists_t LL;
+    resident_t R; memset(&R, 0, sizeof R);
+    if ((rc = fastf_res_lists_load(barcodes, features, rc_list, n_c, seed, &LL)) != RES_OK) goto done;
+    rc = RES_FAIL;
+    T.lists = fastf_res_now() - tt; tt = fastf_res_now();
+    if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
+    T.decode = fastf_res_now() - tt;
     printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
 
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = sweep_cell_rate(&R, &L[i], keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, &T);
-        if (rc != SW_OK) goto done;
+        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, &T);
+        if (rc != RES_OK) goto done;
     }
-    rc = SW_OK;
+    rc = RES_OK;
     if (prof)
         fprintf(stderr, "[sweep] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, planes %.3f s, "
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
-                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r), T.summary, T.d2h, T.write, now_s() - t0);
+                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r), T.summary, T.d2h, T.write, fastf_res_now() - t0);
 done:
-    if (bam) fastf_bam_close(bam);
-    if (stage) fastf_pinned_free(stage);
-    resident_free(&R);
-    if (keys) for (uint32_t i = 0; i < n_c; i++) free(keys[i]);
-    free(keys);
-    if (L) for (uint32_t i = 0; i < n_c; i++) fastf_lists_free(&L[i]);
-    free(L);
+    fastf_res_free(&R);
+    fastf_res_lists_free(&LL);
     return rc;
 }
 
@@ -545,25 +345,25 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
     if (flags & ~(uint32_t)FASTF_SWEEP_SUMMARY_ONLY) return sw_err("sweep: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
-    if (make_dir(out_dir)) return 1;
-    tsv_out tsv; memset(&tsv, 0, sizeof tsv);
+    if (fastf_res_make_dir(out_dir)) return 1;
+    res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
 
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
-    int rc = several ? SW_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f);
-    if (rc == SW_NOT_COVERED) {
+    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f);
+    if (rc == RES_NOT_COVERED) {
         fprintf(stderr, "sweep: this job is outside the resident form (%s): running bam2db point by point\n",
                 several ? "several devices" : "keys wider than 64 bits or UMIs beyond what a 64-bit key holds");
         /* (rows a resident attempt had written are of no use: the table starts again) */
-        tsv_close(&tsv, 0);
+        fastf_res_tsv_close(&tsv, 0);
         if (tsv_open(&tsv, out_dir)) return 1;
         rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, &tsv);
     }
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); tsv_close(&tsv, 0); fastf_set_error_(keep); return 1; }
-    return tsv_close(&tsv, 1);
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_set_error_(keep); return 1; }
+    return fastf_res_tsv_close(&tsv, 1);
 }
 
 static void usage_sweep(FILE *f)
@@ -584,58 +384,13 @@ static void usage_sweep(FILE *f)
             "        --summary-only    write sweep.tsv alone\n");
 }
 
-struct sopt { char s; const char *l; int has_arg; };
-static const struct sopt k_sopts[] = {
-    {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {'r', "depth", 1},
-    {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {0, NULL, 0}};
-
 #define SWEEP_MAX_RATES 64
 int cmd_sweep(int argc, const char **argv)
 {
-    const char *bam = NULL, *feat = NULL, *bar = NULL, *out = ".", *cells = "1", *depths = "1";
-    unsigned int seed = 926;
-    int summary_only = 0;
-    for (int i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        const struct sopt *o = NULL;
-        const char *val = NULL;
-        if (a[0] != '-' || !a[1]) break;
-        if (a[1] == '-') {
-            if (!a[2]) break;
-            const char *eq = strchr(a + 2, '=');
-            const size_t nl = eq ? (size_t)(eq - a - 2) : strlen(a + 2);
-            for (const struct sopt *k = k_sopts; k->l; k++)
-                if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
-            if (o && eq) val = eq + 1;
-        } else {
-            for (const struct sopt *k = k_sopts; k->l; k++) if (k->s == a[1] && k->s != 'S') { o = k; break; }
-            if (o && o->has_arg && a[2]) val = a + 2;
-        }
-        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage_sweep(stderr); return 1; }
-        char oname[32];
-        if (a[1] == '-') snprintf(oname, sizeof oname, "--%s", o->l); else snprintf(oname, sizeof oname, "-%c", o->s);
-        if (o->has_arg && !val) {
-            if (i + 1 >= argc) { fprintf(stderr, "error: option `%s` requires a value\n", oname); return 1; }
-            val = argv[++i];
-        }
-        char *end = NULL;
-        switch (o->s) {
-        case 'h': usage_sweep(stdout); return 0;
-        case 'b': bam = val; break;
-        case 'f': feat = val; break;
-        case 'a': bar = val; break;
-        case 'd': break;
-        case 'o': out = val; break;
-        case 'c': cells = val; break;
-        case 'r': depths = val; break;
-        case 's': errno = 0; seed = (unsigned int)strtol(val, &end, 0);
-                  if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); return 1; }
-                  if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); return 1; }
-                  break;
-        case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m sweep does not write umi.tsv.gz (-u): run bam2db -u for the points that need it.\n"); return 1;
-        case 'S': summary_only = 1; break;
-        }
-    }
+    res_args_t A;
+    const int prc = fastf_res_parse_args(argc, argv, 'r', "depth", usage_sweep, "sweep does not write umi.tsv.gz (-u): run bam2db -u for the points that need it.", &A);
+    if (prc) return prc == 2 ? 0 : 1;
+    const char *cells = A.cells, *depths = A.list ? A.list : "1";
     float rc[SWEEP_MAX_RATES], rd[SWEEP_MAX_RATES];
     uint32_t n_c = 0, n_r = 0;
     if (fastf_sweep_parse_rates(cells, 1, rc, SWEEP_MAX_RATES, &n_c) || fastf_sweep_parse_rates(depths, 0, rd, SWEEP_MAX_RATES, &n_r) ||
@@ -643,10 +398,8 @@ int cmd_sweep(int argc, const char **argv)
         fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error());
         return 1;
     }
-    if (!bam || access(bam, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m bam file: %s does not exist.\n", bam ? bam : "(null)"); return 1; }
-    if (!feat || access(feat, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m feature file: %s does not exist.\n", feat ? feat : "(null)"); return 1; }
-    if (!bar || access(bar, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m barcode file: %s does not exist.\n", bar ? bar : "(null)"); return 1; }
-    if (fastf_sweep(bam, out, bar, feat, rc, n_c, rd, n_r, seed, summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0)) {
+    if (fastf_res_check_inputs(&A)) return 1;
+    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
     }

@@ -6,6 +6,7 @@
 // There is NO CPU fallback: every entry point fails loudly when HIP is unusable.
 #include "umi_kernels.hpp"
 #include "sweep_kernels.hpp"
+#include "cap_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -222,6 +223,10 @@ struct fastf_engine {
     u32 ring_carry = 0;                  // host-packed decisions: the bits of the word draws_up stands in (below bit draws_up & 31)
     DevBuf d_dbits;                      // device-level calls that bring 32-bit draws: their decisions (draw_bits_kernel)
     DevBuf d_mtwords;                    // the generator's words of one launch, between mt_fill_kernel and draw_bits_kernel
+    // fastf_dev_cell_decisions: which stream d_mtwords holds from its first word on (any other generator launch ends it), and
+    // whether cell_hits_kernel<true> has its dynamic-LDS attribute on this engine's device
+    bool mtwords_kept = false; u32 mtwords_seed = 0; u64 mtwords_skip = 0, mtwords_n = 0;
+    bool cap_lds_attr = false;
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
     DevBuf d_mtsub, d_mtpoly, d_mtseat, d_mtseq;   // parallel generator (jump-ahead): the sub-streams' states; the jump polynomials; the state fastf_dev_mt_decisions seats; the sources' sequences
@@ -941,7 +946,9 @@ static int launch_draw_planes(const PlaneOut& po, const u32* d_draws, u64 n, hip
 // continue the MT19937 stream in d_mt by `count` draws and leave their DECISIONS at the ranks first .. first + count of the ring:
 // the generator writes words into `words` (grown to fit), draw_bits_kernel packs them behind it on the same stream
 // (po: the decisions go to its planes instead — linear arrays from bit 0; d_ring, first, ring_mask and threshold are not used)
-static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr) {
+// (words_only: the raw draws stay in `words` and nothing is packed — fastf_dev_cell_decisions compares them per cell)
+static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr,
+                               bool words_only = false) {
     if (count == 0) return 0;
     if (words.bytes < count * 4) {
         // (the launches that read the old buffer are queued on this stream: let them finish before it is freed)
@@ -950,6 +957,7 @@ static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_r
     }
     hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(256), 0, s, d_mt, (u32*)words.p, 0ull, count, ~0ull);
     HIP_OK(hipGetLastError());
+    if (words_only) return 0;
     if (po) return launch_draw_planes(*po, (const u32*)words.p, count, s);
     return launch_draw_bits(threshold, (const u32*)words.p, count, d_ring, s, first, ring_mask);
 }
@@ -965,12 +973,13 @@ static u32 mt_idx_after(u32 idx, u64 n) {
 // the sub-streams costs a handful of launches.
 constexpr u64 MT_PAR_MIN = 4ull * MT_SUB_DRAWS;
 static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u32* idx, DevBuf& words, u32* d_ring, u64 first, u64 count,
-                                   u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr) {
+                                   u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr, bool words_only = false) {
     if (count == 0) return 0;
+    e->mtwords_kept = false;
     static const bool no_par = getenv("FASTF_MT_SERIAL") != nullptr;
     const u64 head = *idx < MT_N ? std::min<u64>(count, MT_N - *idx) : 0;          // to the next block boundary
     if (count < MT_PAR_MIN || no_par) {
-        if (launch_mt_decisions(s, d_mt, words, d_ring, first, count, ring_mask, threshold, po)) return 1;
+        if (launch_mt_decisions(s, d_mt, words, d_ring, first, count, ring_mask, threshold, po, words_only)) return 1;
         *idx = mt_idx_after(*idx, count);
         return 0;
     }
@@ -1020,6 +1029,7 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
         at += body;
     }
     *idx = mt_idx_after(MT_N, last);
+    if (words_only) return 0;
     if (po) return launch_draw_planes(*po, (const u32*)w, count, s);
     return launch_draw_bits(threshold, (const u32*)w, count, d_ring, s, first, ring_mask);
 }
@@ -1081,6 +1091,90 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
     HIP_OK(hipGetLastError());
     dbg_sync(s, "cell summary");
     return 0;
+} FASTF_CATCH_INT
+
+// cap: hits per cell from the cell scratch K1a left (cell_hits_kernel).  Valid right after fastf_dev_count_hits[_blocked] over the
+// same n records on the same stream (the FASTF_PROBE_REUSE_HITS contract); d_blocked: the blocked buffer of that call, or
+// nullptr for the SoA scratch.  d_hits_per_cell[c - 1] (u32, n_cells entries) is cleared here first.
+static CellIn cell_scratch_of(const fastf_engine* e, const void* blk) {
+    return blk ? CellIn{blk, blk_run_bytes(e->cell16, e->narrow), blk_cell_off(e->narrow)} : CellIn{e->d_cellidx.p, 0u, 0u};
+}
+extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t* d_hits_per_cell, void* stream) FASTF_TRY {
+    if (!e || (e && e->n_cells && !d_hits_per_cell)) return set_err("null argument");
+    if (e->multi) return set_err("fastf_dev_cell_hits: device-level calls take a single-device engine");
+    if (n >= (1ull << 32)) return set_err("fastf_dev_cell_hits: %llu records: the counters are 32 bits wide", (unsigned long long)n);
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->n_cells) return 0;
+    HIP_OK(hipMemsetAsync(d_hits_per_cell, 0, (size_t)e->n_cells * sizeof(u32), s));
+    if (n == 0) return 0;
+    if (!d_blocked && e->d_cellidx.bytes < n * (e->cell16 ? 2u : 4u)) return set_err("fastf_dev_cell_hits: no cell scratch for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
+    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
+    constexpr u32 WAVES = CAP_HITS_THREADS / WAVE;
+    const CellIn in = cell_scratch_of(e, d_blocked);
+    // up to CAP_LDS_RANGES ranges of CAP_LDS_CELLS cells take the LDS form, each range with its own share of the workgroups (every
+    // range reads the whole scratch); FASTF_CAP_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs)
+    const u32 n_ranges = (e->n_cells + CAP_LDS_CELLS - 1) / CAP_LDS_CELLS;
+    const char* mr = getenv("FASTF_CAP_LDS_RANGES");
+    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), CAP_LDS_RANGES) : CAP_LDS_RANGES;
+    if (n_ranges <= max_ranges) {
+        const size_t lds = (size_t)std::min<u32>(e->n_cells, CAP_LDS_CELLS) * sizeof(u32);
+        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
+        if (!e->cap_lds_attr) {                                  // (per engine, on first use: the attribute belongs to the current device's function)
+            HIP_OK(hipFuncSetAttribute((const void*)cell_hits_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CAP_LDS_CELLS * sizeof(u32))));
+            e->cap_lds_attr = true;
+        }
+        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)per_cu * g_cu_count / n_ranges));
+        hipLaunchKernelGGL(cell_hits_kernel<true>, dim3(groups * n_ranges), dim3(CAP_HITS_THREADS), lds, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, n_ranges);
+    } else {
+        const u32 grid = (u32)std::min<u64>((units + WAVES - 1) / WAVES, 2ull * g_cu_count);
+        hipLaunchKernelGGL(cell_hits_kernel<false>, dim3(grid), dim3(CAP_HITS_THREADS), 0, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, 1u);
+    }
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "cell hits");
+    return 0;
+} FASTF_CATCH_INT
+
+// cap: the decision plane of per-cell thresholds.  The stream init_genrand(seed) + skip is generated as fastf_dev_mt_decisions
+// generates it, the raw draws staying in the engine's word buffer; cell_decisions_kernel then sets bit i of d_bits_out =
+// draw i < d_thresholds[cell of the i-th CB hit - 1] (u64[n_cells] in device memory, each 0 .. 2^32: the caller's word, the values
+// are not read on the host).  The draws of the last (seed, skip) stay in the word buffer: a second call over the same stream — the
+// next cap of a cell rate — does not generate them again.  Same layout and size rule as
+// fastf_dev_draw_bits.  Valid where fastf_dev_cell_hits is, and leaves that contract intact: a fastf_dev_probe_pack with
+// FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS may follow.  Synchronises the stream.
+extern "C" int fastf_dev_cell_decisions(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t seed, uint64_t skip, uint64_t n_draws,
+                                        const uint64_t* d_thresholds, uint32_t* d_bits_out, void* stream) FASTF_TRY {
+    if (!e || (n_draws && (!d_bits_out || !d_thresholds))) return set_err("null argument");
+    if (e->multi) return set_err("fastf_dev_cell_decisions: device-level calls take a single-device engine");
+    if ((uintptr_t)d_bits_out & 7) return set_err("fastf_dev_cell_decisions: the plane is 8-byte aligned");
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    auto sync = [&]() -> int {
+        if (hipStreamSynchronize(s) != hipSuccess) return set_err("the generator or decision kernels failed: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    };
+    if (!n_draws) return sync();
+    HIP_OK(hipMemsetAsync(d_bits_out, 0, (size_t)((n_draws + 63) / 64) * 8, s));
+    if (n == 0 || !e->n_cells) return sync();
+    if (!d_blocked && e->d_cellidx.bytes < n * (e->cell16 ? 2u : 4u)) return set_err("fastf_dev_cell_decisions: no cell scratch for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
+    const u64 tiles = (n + K1_TILE - 1) / K1_TILE;
+    if (e->d_tilebase.bytes < tiles * sizeof(u64) || e->d_halfhits.bytes < tiles * 16 * sizeof(u32)) return set_err("fastf_dev_cell_decisions: no hit counts for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
+    // the raw draws: generated once per (seed, skip) — the caps of one cell rate share the stream — and kept while no other
+    // generator launch has used the word buffer
+    if (!(e->mtwords_kept && e->mtwords_seed == seed && e->mtwords_skip == skip && e->mtwords_n >= n_draws)) {
+        fastf_mt_t mt; fastf_mt_seed(&mt, seed); fastf_mt_skip(&mt, skip);
+        if (e->d_mtseat.ensure(sizeof mt)) return 1;
+        if (copy_h2d_on(e->d_mtseat.p, &mt, sizeof mt, s)) return 1;
+        u32 idx = (u32)mt.idx;
+        if (launch_mt_decisions_par(e, s, (u32*)e->d_mtseat.p, &idx, e->d_mtwords, nullptr, 0, n_draws, ~0ull, 0, nullptr, true)) return 1;
+        e->mtwords_kept = true; e->mtwords_seed = seed; e->mtwords_skip = skip; e->mtwords_n = n_draws;
+    }
+    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
+    const u32 grid = (u32)std::min<u64>((units + 3) / 4, 8ull * g_cu_count);
+    hipLaunchKernelGGL(cell_decisions_kernel, dim3(grid), dim3(256), 0, s, cell_scratch_of(e, d_blocked), e->cell16, n, (const u64*)e->d_tilebase.p,
+                       (const u32*)e->d_halfhits.p, (const u32*)e->d_mtwords.p, n_draws, (const u64*)d_thresholds, e->n_cells, (u64*)d_bits_out);
+    HIP_OK(hipGetLastError());
+    return sync();
 } FASTF_CATCH_INT
 
 // device memory for the C side of the library (sweep_cmds.c keeps the records of a BAM resident); declared in host_io.h
@@ -1565,7 +1659,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------
@@ -1929,6 +2023,7 @@ static int push_impl(fastf_engine_t* e, const fastf_batch_t* batch, const uint32
             HIP_OK(hipStreamSynchronize(e->s_mt));                          // (idle already: every chunk that waited for it is retired)
             // (the generator's scratch for the most ranks one launch can be asked for — everything the ring holds — so that no
             //  push stops to grow it)
+            e->mtwords_kept = false;
             if (e->d_mt.ensure(sizeof(fastf_mt_t)) || e->d_mtwords.ensure(e->ring_len * 4)) return 1;
             if (copy_h2d(e->d_mt.p, &e->mt, sizeof(fastf_mt_t))) return 1;
             e->mt_dev_idx = (u32)e->mt.idx;

@@ -381,6 +381,17 @@ class Engine:
         the last is the sum of all counts), d_genes_per_cell[c - 1] = its rows with count >= 1 (u32); both cleared by the call"""
         check(self._L.fastf_dev_cell_summary(self._h, d_cell, d_count, d_nnz, n_cells, d_umis_per_cell, d_genes_per_cell, stream))
 
+    def dev_cell_hits(self, n, d_blocked, d_hits_per_cell, stream=0):
+        """d_hits_per_cell[c - 1] (u32, n_cells entries, cleared by the call) = records of the last dev_count_hits[_blocked] over
+        these n records whose cell index is c; d_blocked: that call's blocked buffer, or 0 / None for the SoA scratch"""
+        check(self._L.fastf_dev_cell_hits(self._h, n, d_blocked or None, d_hits_per_cell, stream))
+
+    def dev_cell_decisions(self, n, d_blocked, seed, skip, n_draws, d_thresholds, d_bits_out, stream=0):
+        """bit i of d_bits_out = draw i of init_genrand(seed) + skip < d_thresholds[cell of the i-th CB hit - 1] (u64[n_cells] on
+        the device, 0 .. 2^32); layout and size rule of dev_draw_bits.  Valid where dev_cell_hits is; dev_probe_pack(reuse_hits,
+        draw_bits) over the plane may follow"""
+        check(self._L.fastf_dev_cell_decisions(self._h, n, d_blocked or None, seed, skip, n_draws, d_thresholds, d_bits_out, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

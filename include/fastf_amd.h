@@ -128,6 +128,35 @@ int fastf_sweep_check_grid(const float *rates_cell, uint32_t n_c, const float *r
 int fastf_sweep_point_dir(float rate_cell, float rate_depth, char *buf, size_t cap);
 const char *fastf_sweep_header(void);
 
+/* --- cap: every cell downsampled to at most N reads (cap_cmds.c; not a command of the reference).  For one point (cell rate c,
+ * cap N >= 1, seed s): the cells are sampled as `bam2db -c c -s s` samples them; h[k] = records whose CB is sampled cell k (counted
+ * before xf, as the reference's depth draw is), H = sum h; the i-th CB hit in file order consumes draw i of init_genrand(s)
+ * advanced by the draws SampleInt consumed — bam2db's own coupling; hit i of cell k is kept iff draw[i] < T[k], T[k] = 2^32 where
+ * h[k] <= N (the cell loses no read) and fastf_draw_threshold((float)((double)N / (double)h[k])) otherwise; everything behind the depth
+ * draw runs as in bam2db.  Per point <out_dir>/c<rate_cell>_n<N>/ holds the three files of bam2db, the matrix header's rate_depth
+ * carrying the realised fraction (float)((double)sampled / (double)H) (1.0 when H == 0); <out_dir>/cap.tsv holds a header and one row per
+ * point, cell rates major, caps minor: sweep.tsv's columns with rate_depth replaced by reads_per_cell, and hits, cells_capped
+ * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
+ * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
+ * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] */
+#define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
+int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+              const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags);
+/* the host pieces of it: a comma-separated list of caps (decimal integers >= 1; empty elements, signs, trailing characters and
+ * values twice are refused); the grid check; a point's directory name; the header line of cap.tsv; one row of it (with its
+ * newline; counters = {total, sampled, sampled_valid}); the per-cell thresholds T[] above from h[] */
+int fastf_cap_parse_caps(const char *text, uint64_t *out, uint32_t cap, uint32_t *n_out);
+int fastf_cap_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t *caps, uint32_t n_n);
+int fastf_cap_point_dir(float rate_cell, uint64_t reads_per_cell, char *buf, size_t cap);
+const char *fastf_cap_header(void);
+int fastf_cap_summary_row(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                          const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits,
+                          uint32_t cells_capped, char *buf, size_t cap);
+int fastf_cap_thresholds(const uint32_t *hits, uint32_t n_cells, uint64_t cap, uint64_t *thresholds_out);
+/* the realised fraction of a point as the matrix header carries it */
+float fastf_cap_realised(uint64_t sampled, uint64_t hits);
+
 const char *fastf_last_error(void);
 const char *fastf_version(void);
 
@@ -420,6 +449,22 @@ int fastf_dev_mt_decisions_multi(fastf_engine_t *e, uint32_t seed, uint64_t skip
  * call.  d_cell / d_count may be NULL when there are no rows. */
 int fastf_dev_cell_summary(fastf_engine_t *e, const uint32_t *d_cell, const uint32_t *d_count, const uint64_t *d_nnz, uint32_t n_cells,
                            uint64_t *d_umis_per_cell, uint32_t *d_genes_per_cell, void *stream);
+
+/* cap (section 1) on the device.  fastf_dev_cell_hits: d_hits_per_cell[c - 1] (u32, the engine's n_cells entries, cleared by the call)
+ * = records whose cell index in K1a's scratch is c.  Valid right after fastf_dev_count_hits (d_blocked NULL: the SoA scratch) or
+ * fastf_dev_count_hits_blocked (d_blocked: that call's buffer) over the same n records on the same stream — the
+ * FASTF_PROBE_REUSE_HITS contract.
+ * fastf_dev_cell_decisions: the decision plane of per-cell thresholds, in the layout and with the size rule of fastf_dev_draw_bits
+ * (8-byte aligned, (n_draws + 63) / 64 * 8 bytes, the tail of the last 64 bits zero, nothing behind it written): bit i = draw i of
+ * init_genrand(seed) advanced by `skip` draws < d_thresholds[c - 1], c = the cell of the i-th CB hit of the n records; d_thresholds:
+ * u64[n_cells] in DEVICE memory, each 0 .. 2^32 — the caller guarantees the range, the call does not read the values.  The engine keeps
+ * the raw draws of the last (seed, skip): further calls over the same stream (the other caps of a cell rate) skip the generator.
+ * n_draws is the hit count fastf_dev_count_hits reported; hits beyond it get no bit.
+ * Valid where fastf_dev_cell_hits is, and a fastf_dev_probe_pack(FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS [| _BLOCKED |
+ * _SEGMENTED]) over the plane may follow.  Synchronises the stream, on every path. */
+int fastf_dev_cell_hits(fastf_engine_t *e, uint64_t n, const void *d_blocked, uint32_t *d_hits_per_cell, void *stream);
+int fastf_dev_cell_decisions(fastf_engine_t *e, uint64_t n, const void *d_blocked, uint32_t seed, uint64_t skip, uint64_t n_draws,
+                             const uint64_t *d_thresholds, uint32_t *d_bits_out, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
