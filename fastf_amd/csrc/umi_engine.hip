@@ -2195,6 +2195,8 @@ static int finish_queue(fastf_engine* e) {
     return 0;
 }
 
+static int wide_rows_exact(fastf_engine* e, u64 n, hipStream_t s, std::vector<u32>& f, std::vector<u32>& c, std::vector<u32>& k);
+
 extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t counters[3]) FASTF_TRY {
     if (!e || !coo) return set_err("null argument");
     if (e->multi) return multi_finish(e, coo, counters);
@@ -2211,8 +2213,18 @@ extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t
         if (!e->finish_queued && finish_queue(e)) return 1;
         e->finish_queued = false;
         HIP_OK(hipStreamSynchronize(s));
-        if (n && e->wide && (e->h_small[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG))
-            return set_err("a (cell, feature) group of more than 4 M reads (or more than 6 M reads in groups beyond 2048) with keys wider than 64 bits: not supported");
+        std::vector<u32> ex_f, ex_c, ex_k;                 // wide keys: the rows of the exact fallback
+        bool exact_wide = false;
+        if (n && e->wide && (e->h_small[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG)) {
+            // the window set could not place a UMI (a probe chain of 63), or a group was beyond what giant_groups_kernel and its
+            // list take: finish the sort of the pairs — every pair is still in the store, permuted — and count the distinct
+            // non-NULL pairs of every group on the host (the rows of wide_pair_rows are what the -u output needs anyway)
+            const u64 keep = e->h_small[SM_COUNTERS + 3] & ~ERR_RUN_TOO_LONG;
+            if (copy_h2d_on(small + SM_COUNTERS + 3, &keep, sizeof(u64), s)) return 1;
+            if (wide_rows_exact(e, n, s, ex_f, ex_c, ex_k)) return 1;
+            e->h_small[SM_NNZ] = ex_f.size();
+            exact_wide = true;
+        } else
         if (n && (e->h_small[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG)) {
             // runs of keys that agree on the sorted bits are long in this data (very deep (cell, feature) groups):
             // finish the sort and reduce exactly; every key is still in the store, permuted
@@ -2257,7 +2269,9 @@ extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t
         lap("row buffer ready");
         if (nnz) {
             u32 *h_f = e->rows_at, *h_c = e->rows_at + e->rows_stride, *h_k = e->rows_at + 2 * e->rows_stride;
-            if (on_loan || e->h_coo_pinned) {
+            if (exact_wide) {
+                memcpy(h_f, ex_f.data(), nnz * 4); memcpy(h_c, ex_c.data(), nnz * 4); memcpy(h_k, ex_k.data(), nnz * 4);
+            } else if (on_loan || e->h_coo_pinned) {
                 // pinned row buffer: the gather of K3's row regions writes it directly — that kernel is the D2H copy
                 if (launch_rows_gather<false>(e, small + SM_KEYCOUNT, h_f, h_c, h_k, nullptr, s)) return 1;
             } else {
@@ -2278,57 +2292,75 @@ extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t
     return 0;
 } FASTF_CATCH_INT
 
-// -u rows with keys wider than 64 bits: sort the pairs fully (by the rest of the key, then by the group word: two stable LSD
-// sorts), one row per distinct pair (pair_*_kernel)
-static int umi_rows_wide(fastf_engine* e, fastf_umi_rows_t* rows) {
-    hipStream_t s = e->s_compute;
+// The distinct (group word, rest of the key) pairs of the n pairs in the store, in (group word, rest) order, with the copies of
+// each (e->h_ncopy): the pairs are sorted fully first (by the rest of the key, then stably by the group word: two LSD sorts),
+// then one row per pair that differs from the one in front (pair_*_kernel).  The -u rows of wide keys, and the exact fallback
+// of the matrix when the window set or the giant-group list could not hold a group.
+static int wide_pair_rows(fastf_engine* e, u64 n, hipStream_t s, std::vector<u64>& uk, std::vector<u64>& uv) {
     u64* small = (u64*)e->d_small.p;
-    const u64 n = e->n_sorted;
     u64 nrows = 0;
-    std::vector<u64> uk, uv;
-    if (n) {
-        u64 *kc = e->sorted_in_tmp ? (u64*)e->d_tmp.p : (u64*)e->d_keys.p, *ko = e->sorted_in_tmp ? (u64*)e->d_keys.p : (u64*)e->d_tmp.p;
-        u64 *vc = e->sorted_in_tmp ? (u64*)e->d_vtmp.p : (u64*)e->d_vals.p, *vo = e->sorted_in_tmp ? (u64*)e->d_vals.p : (u64*)e->d_vtmp.p;
-        if (!e->fully_sorted) {
-            int f = 0;
-            if (launch_sort(e, vc, vo, small + SM_KEYCOUNT, n, e->L.feat_shift, 0, &f, s, false, kc, ko)) return 1;   // by the rest of the key (the group words ride along)
-            if (f) { std::swap(kc, ko); std::swap(vc, vo); }
-            if (launch_sort(e, kc, ko, small + SM_KEYCOUNT, n, e->group_bits, 0, &f, s, false, vc, vo)) return 1;      // then, stably, by the group word
-            if (f) { std::swap(kc, ko); std::swap(vc, vo); }
-            e->sorted_in_tmp = kc == (u64*)e->d_tmp.p;
-            e->fully_sorted = true;
-        }
-        const u64 T = (n + UW_TILE - 1) / UW_TILE;
-        // rows: the group words into d_ukeys, the rests and the head positions into two halves of one scratch buffer
-        if (e->d_ukeys.ensure(n * 8) || e->d_ncopy.ensure(n * 4) || e->d_rg_ukeys.ensure(2 * n * 8) || e->d_scanblk.ensure(2 * 64 * sizeof(u64))) return 1;
-        DevBuf cnt, base;
-        if (cnt.ensure((T + 16) * 4) || base.ensure((T + 16) * 8)) { cnt.release(); base.release(); return 1; }
-        int rc = 0;
-        do {
-            if (hipMemsetAsync(cnt.p, 0, (T + 16) * 4, s) != hipSuccess) { rc = set_err("memset failed"); break; }
-            const u32 grid = (u32)std::min<u64>(T, 16ull * g_cu_count);
-            hipLaunchKernelGGL(pair_heads_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)kc, (const u64*)vc, (const u64*)(small + SM_KEYCOUNT), (u32*)cnt.p);
-            launch_scan_tiles(e, 1, s, (u32*)cnt.p, (u64*)base.p, (u32)T, small + SM_NROWS_U, nullptr, nullptr);
-            u64* uvals = (u64*)e->d_rg_ukeys.p; u64* hpos = uvals + n;
-            hipLaunchKernelGGL(pair_rows_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)kc, (const u64*)vc, (const u64*)(small + SM_KEYCOUNT),
-                               (const u64*)base.p, (u64*)e->d_ukeys.p, uvals, hpos);
-            hipLaunchKernelGGL(pair_copies_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)hpos, (const u64*)(small + SM_NROWS_U),
-                               (const u64*)(small + SM_KEYCOUNT), (u32*)e->d_ncopy.p);
-            if (hipGetLastError() != hipSuccess) { rc = set_err("kernel launch failed (-u rows of wide keys)"); break; }
-            if (hipMemcpyAsync(e->h_small, small, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = set_err("device error in the -u rows of wide keys"); break; }
-            if (e->h_small[SM_COUNTERS + 3]) { rc = set_err("%s", err_bits_text(e->h_small[SM_COUNTERS + 3])); break; }
-            nrows = e->h_small[SM_NROWS_U];
-            if (nrows > n) { rc = set_err("internal error: %llu -u rows out of %llu keys", (unsigned long long)nrows, (unsigned long long)n); break; }
-            uk.resize(nrows); uv.resize(nrows); e->h_ncopy.resize(nrows);
-            if (nrows) {
-                if (copy_d2h(uk.data(), e->d_ukeys.p, nrows * 8) || copy_d2h(uv.data(), uvals, nrows * 8) || copy_d2h(e->h_ncopy.data(), e->d_ncopy.p, nrows * 4)) { rc = 1; break; }
-            }
-        } while (0);
-        cnt.release(); base.release();
-        if (rc) return 1;
-    } else {
-        e->h_ncopy.clear();
+    uk.clear(); uv.clear(); e->h_ncopy.clear();
+    if (!n) return 0;
+    u64 *kc = e->sorted_in_tmp ? (u64*)e->d_tmp.p : (u64*)e->d_keys.p, *ko = e->sorted_in_tmp ? (u64*)e->d_keys.p : (u64*)e->d_tmp.p;
+    u64 *vc = e->sorted_in_tmp ? (u64*)e->d_vtmp.p : (u64*)e->d_vals.p, *vo = e->sorted_in_tmp ? (u64*)e->d_vals.p : (u64*)e->d_vtmp.p;
+    if (!e->fully_sorted) {
+        int f = 0;
+        if (launch_sort(e, vc, vo, small + SM_KEYCOUNT, n, e->L.feat_shift, 0, &f, s, false, kc, ko)) return 1;   // by the rest of the key (the group words ride along)
+        if (f) { std::swap(kc, ko); std::swap(vc, vo); }
+        if (launch_sort(e, kc, ko, small + SM_KEYCOUNT, n, e->group_bits, 0, &f, s, false, vc, vo)) return 1;      // then, stably, by the group word
+        if (f) { std::swap(kc, ko); std::swap(vc, vo); }
+        e->sorted_in_tmp = kc == (u64*)e->d_tmp.p;
+        e->fully_sorted = true;
     }
+    const u64 T = (n + UW_TILE - 1) / UW_TILE;
+    // rows: the group words into d_ukeys, the rests and the head positions into two halves of one scratch buffer
+    if (e->d_ukeys.ensure(n * 8) || e->d_ncopy.ensure(n * 4) || e->d_rg_ukeys.ensure(2 * n * 8) || e->d_scanblk.ensure(2 * 64 * sizeof(u64))) return 1;
+    DevBuf cnt, base;
+    if (cnt.ensure((T + 16) * 4) || base.ensure((T + 16) * 8)) { cnt.release(); base.release(); return 1; }
+    int rc = 0;
+    do {
+        if (hipMemsetAsync(cnt.p, 0, (T + 16) * 4, s) != hipSuccess) { rc = set_err("memset failed"); break; }
+        const u32 grid = (u32)std::min<u64>(T, 16ull * g_cu_count);
+        hipLaunchKernelGGL(pair_heads_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)kc, (const u64*)vc, (const u64*)(small + SM_KEYCOUNT), (u32*)cnt.p);
+        launch_scan_tiles(e, 1, s, (u32*)cnt.p, (u64*)base.p, (u32)T, small + SM_NROWS_U, nullptr, nullptr);
+        u64* uvals = (u64*)e->d_rg_ukeys.p; u64* hpos = uvals + n;
+        hipLaunchKernelGGL(pair_rows_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)kc, (const u64*)vc, (const u64*)(small + SM_KEYCOUNT),
+                           (const u64*)base.p, (u64*)e->d_ukeys.p, uvals, hpos);
+        hipLaunchKernelGGL(pair_copies_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)hpos, (const u64*)(small + SM_NROWS_U),
+                           (const u64*)(small + SM_KEYCOUNT), (u32*)e->d_ncopy.p);
+        if (hipGetLastError() != hipSuccess) { rc = set_err("kernel launch failed (distinct pairs of wide keys)"); break; }
+        if (hipMemcpyAsync(e->h_small, small, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = set_err("device error in the distinct pairs of wide keys"); break; }
+        if (e->h_small[SM_COUNTERS + 3]) { rc = set_err("%s", err_bits_text(e->h_small[SM_COUNTERS + 3])); break; }
+        nrows = e->h_small[SM_NROWS_U];
+        if (nrows > n) { rc = set_err("internal error: %llu distinct pairs out of %llu keys", (unsigned long long)nrows, (unsigned long long)n); break; }
+        uk.resize(nrows); uv.resize(nrows); e->h_ncopy.resize(nrows);
+        if (nrows) {
+            if (copy_d2h(uk.data(), e->d_ukeys.p, nrows * 8) || copy_d2h(uv.data(), uvals, nrows * 8) || copy_d2h(e->h_ncopy.data(), e->d_ncopy.p, nrows * 4)) { rc = 1; break; }
+        }
+    } while (0);
+    cnt.release(); base.release();
+    return rc;
+}
+
+// The matrix rows of wide keys from the distinct pairs (the exact fallback of fastf_engine_finish): one row per group word, in
+// the two halves K3 would have written (split at row_split), its count the number of its distinct non-NULL pairs
+static int wide_rows_exact(fastf_engine* e, u64 n, hipStream_t s, std::vector<u32>& f, std::vector<u32>& c, std::vector<u32>& k) {
+    std::vector<u64> uk, uv;
+    if (wide_pair_rows(e, n, s, uk, uv)) return 1;
+    const u32 fmask = (u32)((1ull << e->row_split) - 1), nn_shift = e->L.umi_bits + e->L.len_bits;
+    f.clear(); c.clear(); k.clear();
+    for (size_t i = 0; i < uk.size(); ++i) {
+        if (i == 0 || uk[i] != uk[i - 1]) { f.push_back((u32)uk[i] & fmask); c.push_back((u32)(uk[i] >> e->row_split)); k.push_back(0); }
+        k.back() += (u32)((uv[i] >> nn_shift) & 1);
+    }
+    return 0;
+}
+
+// -u rows with keys wider than 64 bits: one row per distinct pair (wide_pair_rows)
+static int umi_rows_wide(fastf_engine* e, fastf_umi_rows_t* rows) {
+    std::vector<u64> uk, uv;
+    if (wide_pair_rows(e, e->n_sorted, e->s_compute, uk, uv)) return 1;
+    const u64 nrows = uk.size();
     e->h_ufeature.resize(nrows); e->h_ucell.resize(nrows); e->h_uumi.resize(nrows); e->h_unonnull.resize(nrows);
     const u32 fmask = (u32)((1ull << e->feat_bits) - 1);
     const u64 umask = e->L.umi_bits >= 64 ? ~0ull : ((1ull << e->L.umi_bits) - 1);
