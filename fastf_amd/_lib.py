@@ -109,6 +109,8 @@ ABI_SYMBOLS = [
     # sweep
     "fastf_sweep", "fastf_sweep_parse_rates", "fastf_sweep_check_grid", "fastf_sweep_point_dir", "fastf_sweep_header",
     "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
+    # --genes of sweep and cap
+    "fastf_dev_gene_summary", "fastf_sweep_genes_from_coo", "fastf_genes_summary_row", "fastf_sweep_genes_header", "fastf_cap_genes_header",
     # cap
     "fastf_cap", "fastf_cap_parse_caps", "fastf_cap_check_grid", "fastf_cap_point_dir", "fastf_cap_header",
     "fastf_cap_summary_row", "fastf_cap_thresholds", "fastf_cap_realised", "fastf_dev_cell_hits", "fastf_dev_cell_decisions",
@@ -280,6 +282,11 @@ def lib():
     L.fastf_sweep_summary_row.argtypes = [C.c_float, C.c_float, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, C.c_char_p, sz]
     L.fastf_dev_mt_decisions_multi.argtypes = [vp, u32, u64, u64, vp, u32, vp, u64, vp]
     L.fastf_dev_cell_summary.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
+    L.fastf_dev_gene_summary.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
+    L.fastf_sweep_genes_from_coo.argtypes = [C.POINTER(Coo), u32, vp, vp]
+    L.fastf_genes_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, u32, C.c_char_p, sz]
+    L.fastf_sweep_genes_header.restype = C.c_char_p
+    L.fastf_cap_genes_header.restype = C.c_char_p
     L.fastf_cap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
     L.fastf_cap_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.fastf_cap_check_grid.argtypes = [fp, u32, vp, u32]

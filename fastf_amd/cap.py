@@ -8,18 +8,21 @@ import numpy as np
 from . import _lib
 
 SUMMARY_ONLY = 1      # FASTF_CAP_SUMMARY_ONLY
+GENES = 2             # FASTF_CAP_GENES
 COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
+GENES_COLUMNS = ("rate_cell", "reads_per_cell", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
 
 
-def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False):
-    """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only]`; returns the rows of
-    out/cap.tsv as dicts of strings (read_table)"""
+def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False):
+    """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes]`; returns the rows of
+    out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
+    out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), SUMMARY_ONLY if summary_only else 0))
+                                    n.ctypes.data, len(n), seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
@@ -27,6 +30,17 @@ def read_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""
     return [dict(zip(COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def read_genes_table(path):
+    """the rows of cap_genes.tsv as dicts of strings"""
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(GENES_COLUMNS) and lines[-1] == ""
+    return [dict(zip(GENES_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def genes_header() -> str:
+    return _lib.lib().fastf_cap_genes_header().decode()
 
 
 def parse_caps(text: str):

@@ -11,6 +11,7 @@
  * device does no floating point) and sent to the device, the decision plane made from the draw stream and the thresholds
  * (fastf_dev_cell_decisions), then K1b on that plane and everything behind it as in bam2db.  A global depth rate cannot express a
  * cap, so a job outside the resident form is refused: there is no point-by-point fallback.
+ * --genes: as in sweep (cap_genes.tsv, cap_gene_cells.tsv.gz, genes.tsv.gz per point; resident.c).
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -121,13 +122,14 @@ static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_op
 /* one cell rate                                                       */
 /* ------------------------------------------------------------------ */
 static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
-                         float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_times_t *T)
+                         float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
+                         res_times_t *T)
 {
     int rc = RES_FAIL;
     res_rate_t S;
     void *d_plane = NULL, *d_hits = NULL, *d_thr = NULL;
     uint32_t *h_hits = NULL; uint64_t *h_thr = NULL;
-    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, T)) != RES_OK) goto done;
+    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, G->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
     const uint64_t H = S.H, N = R->n;
     const uint32_t n_cells = S.n_cells;
@@ -166,6 +168,13 @@ static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_point_write(&S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
         }
+        if (G->on) {
+            char grow[256];
+            tt = fastf_res_now();
+            if (fastf_genes_summary_row(rate_cell, 0.0f, caps[j], seed, S.h_cpg, S.h_upg, S.n_features, grow, sizeof grow) ||
+                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
+            T->genes += fastf_res_now() - tt;
+        }
         fputs(row, tsv);
     }
     rc = RES_OK;
@@ -178,7 +187,7 @@ done:
 }
 
 static int cap_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
-                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv)
+                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -194,7 +203,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
     T.decode = fastf_res_now() - tt;
     printf("cap: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n);
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, &T);
+        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, G, &T);
         if (rc != RES_OK) goto done;
     }
     rc = RES_OK;
@@ -202,6 +211,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
         fprintf(stderr, "[cap] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, hits per cell + thresholds + planes %.3f s, "
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
                 T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_n), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+    if (prof && G->on) fprintf(stderr, "[cap] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
 done:
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
@@ -217,8 +227,8 @@ int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const 
     if (!bam || !barcodes || !features) return cp_err("cap: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_cap_check_grid(rates_cell, n_c, caps, n_n)) return 1;
-    if (flags & ~(uint32_t)FASTF_CAP_SUMMARY_ONLY) return cp_err("cap: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0;
+    if (flags & ~(uint32_t)(FASTF_CAP_SUMMARY_ONLY | FASTF_CAP_GENES)) return cp_err("cap: unknown flags 0x%x", flags);
+    const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_CAP_GENES) != 0;
     if (access(bam, R_OK) == -1) return cp_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1;
     {   const char *dvs = getenv("FASTF_DEVICES");
@@ -228,10 +238,13 @@ int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const 
     if (fastf_res_make_dir(out_dir)) return 1;
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
-    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f);
+    res_genes_t G;
+    if (fastf_res_genes_open(&G, genes, "cap", out_dir, fastf_cap_genes_header(), n_c * n_n)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f, &G);
     if (rc == RES_NOT_COVERED)
         cp_err("cap: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_set_error_(keep); return 1; }
+    if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_set_error_(keep); return 1; }
     return fastf_res_tsv_close(&tsv, 1);
 }
 
@@ -250,7 +263,8 @@ static void usage_cap(FILE *f)
             "    -n, --reads=<list>    reads per cell at most, comma separated integers >= 1\n"
             "    -o, --out=<str>       path to output directory (default .)\n"
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
-            "        --summary-only    write cap.tsv alone\n");
+            "        --summary-only    write cap.tsv alone\n"
+            "        --genes           per-gene detection too: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point\n");
 }
 
 #define CAP_MAX_POINTS 64
@@ -269,10 +283,11 @@ int cmd_cap(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0)) {
+    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0))) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
         return 1;
     }
+    if (A.genes) printf("cap_genes.tsv and cap_gene_cells.tsv.gz are generated.\n");
     printf("cap.tsv is generated.\n");
     return 0;
 }

@@ -147,14 +147,18 @@ void fastf_res_rate_close(res_rate_t *S)
     if (S->h_upc) fastf_pinned_free(S->h_upc);
     if (S->h_gpc) fastf_pinned_free(S->h_gpc);
     if (S->h_rows) fastf_pinned_free(S->h_rows);
+    fastf_devmem_free(S->d_cpg); fastf_devmem_free(S->d_upg);
+    if (S->h_cpg) fastf_pinned_free(S->h_cpg);
+    if (S->h_upg) fastf_pinned_free(S->h_upg);
     memset(S, 0, sizeof *S);
 }
 
 /* on anything but RES_OK the caller still calls fastf_res_rate_close */
 int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
-                        uint32_t seed, int device, res_times_t *T)
+                        uint32_t seed, int device, int genes, res_times_t *T)
 {
     memset(S, 0, sizeof *S);
+    S->genes = genes; S->n_features = (uint32_t)L->n_features;
     S->verb = verb; S->R = R; S->L = L; S->device = device; S->rate_cell = rate_cell; S->seed = seed;
     const uint64_t N = R->n;
     const uint32_t n_cells = S->n_cells = (uint32_t)L->n_cells;
@@ -192,6 +196,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         !(S->h_upc = (uint64_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 8)) || !(S->h_gpc = (uint32_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 4))) {
         rs_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
         return RES_FAIL;
+    }
+    if (genes) {                                            /* the per-gene arrays of a point and their pinned host copies, once */
+        const size_t nf1 = (size_t)S->n_features + 1;
+        if (!(S->d_cpg = fastf_devmem_alloc(device, nf1 * 4)) || !(S->d_upg = fastf_devmem_alloc(device, nf1 * 8)) ||
+            !(S->h_cpg = (uint32_t *)fastf_pinned_alloc(nf1 * 4)) || !(S->h_upg = (uint64_t *)fastf_pinned_alloc(nf1 * 8))) {
+            rs_err("%s: the per-gene arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, nf1 * 12, fastf_last_error());
+            return RES_FAIL;
+        }
     }
     uint64_t *const sm = (uint64_t *)S->d_small;
     if (fastf_devmem_zero(S->d_small, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
@@ -245,10 +257,16 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
     /* the rows, concatenated on the device, and their per-cell summary */
     if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
         fastf_dev_cell_summary(e, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_cells, (uint64_t *)S->d_upc, (uint32_t *)S->d_gpc, NULL) ||
+        (S->genes && fastf_dev_gene_summary(e, nnz ? d_f : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, (uint32_t *)S->d_cpg, (uint64_t *)S->d_upg, NULL)) ||
         fastf_devmem_sync()) return RES_FAIL;
     T->device += fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_devmem_copy(S->h_upc, S->d_upc, ((size_t)S->n_cells + 1) * 8) || fastf_devmem_copy(S->h_gpc, S->d_gpc, (size_t)S->n_cells * 4)) return RES_FAIL;
     T->summary += fastf_res_now() - tt;
+    if (S->genes) {
+        tt = fastf_res_now();
+        if (S->n_features && (fastf_devmem_copy(S->h_cpg, S->d_cpg, (size_t)S->n_features * 4) || fastf_devmem_copy(S->h_upg, S->d_upg, (size_t)S->n_features * 8))) return RES_FAIL;
+        T->genes += fastf_res_now() - tt;
+    }
     return RES_OK;
 }
 
@@ -292,14 +310,125 @@ int fastf_res_tsv_close(res_tsv_t *t, int ok)
     return ok ? rs_err("cannot write %s", t->final) : 0;
 }
 
+/* ------------------------------------------------------------------ */
+/* --genes: the table, the grid file, a point's file                   */
+/* ------------------------------------------------------------------ */
+static void genes_release(res_genes_t *G)
+{
+    if (G->feat_id) for (uint32_t i = 0; i < G->n_features; i++) free(G->feat_id[i]);
+    free(G->feat_id); free(G->cells); free(G->names);
+    G->feat_id = NULL; G->cells = NULL; G->names = NULL; G->n_features = G->n_points = 0;
+}
+
+int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points)
+{
+    memset(G, 0, sizeof *G);
+    if (!on) return 0;
+    G->verb = verb; G->max_points = max_points;
+    snprintf(G->out_dir, sizeof G->out_dir, "%s", out_dir);
+    char name[64];
+    snprintf(name, sizeof name, "%s_genes.tsv", verb);
+    if (!(G->names = calloc(max_points ? max_points : 1, sizeof *G->names))) return rs_err("out of memory");
+    if (fastf_res_tsv_open(&G->tsv, out_dir, name, header)) { genes_release(G); return 1; }
+    G->on = 1;
+    return 0;
+}
+
+/* text of n lines `id \t a[i] [\t b[i]]` */
+typedef struct { char *p; size_t len, cap; } gtext;
+static int gt_room(gtext *t, size_t more)
+{
+    if (t->len + more <= t->cap) return 0;
+    size_t cap = t->cap ? t->cap : ((size_t)1 << 16);
+    while (cap < t->len + more) cap *= 2;
+    char *np = (char *)realloc(t->p, cap);
+    if (!np) return rs_err("out of memory");
+    t->p = np; t->cap = cap;
+    return 0;
+}
+static int gt_str(gtext *t, const char *s) { const size_t n = strlen(s); if (gt_room(t, n)) return 1; memcpy(t->p + t->len, s, n); t->len += n; return 0; }
+static int gt_u64(gtext *t, char lead, uint64_t v)
+{
+    if (gt_room(t, 24)) return 1;
+    t->len += (size_t)snprintf(t->p + t->len, 24, "%c%llu", lead, (unsigned long long)v);
+    return 0;
+}
+/* a finished text through <path>.partial */
+static int gz_text_renamed(const char *path, const gtext *t)
+{
+    char tmp[4200];
+    snprintf(tmp, sizeof tmp, "%s.partial", path);
+    if (fastf_write_gz_text(tmp, t->p ? t->p : "", t->len) || rename(tmp, path) != 0) { unlink(tmp); return rs_err("cannot write %s", path); }
+    return 0;
+}
+
+int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *point_name, const char *dir, const char *row,
+                          const uint32_t *cells, const uint64_t *umis)
+{
+    if (!G->on) return 0;
+    if (!G->feat_id) {                                      /* the first point: the names and the room of the grid file */
+        const uint32_t nf = (uint32_t)L->n_features;
+        if (!(G->feat_id = (char **)calloc(nf ? nf : 1, sizeof *G->feat_id)) ||
+            !(G->cells = (uint32_t *)malloc(((size_t)G->max_points * nf + 1) * sizeof *G->cells))) return rs_err("out of memory");
+        for (uint32_t i = 0; i < nf; i++) { if (!(G->feat_id[i] = strdup(L->feat_id[i]))) return rs_err("out of memory"); G->n_features = i + 1; }
+    }
+    if ((uint32_t)L->n_features != G->n_features) return rs_err("internal error: the feature list changed between points");
+    if (G->n_points >= G->max_points) return rs_err("internal error: more points than the grid has");
+    const uint32_t nf = G->n_features;
+    snprintf(G->names[G->n_points], sizeof G->names[0], "%s", point_name);
+    if (nf) memcpy(G->cells + (size_t)G->n_points * nf, cells, (size_t)nf * sizeof *cells);
+    G->n_points++;
+    if (dir) {
+        char path[4200];
+        gtext t = { NULL, 0, 0 };
+        int bad = 0;
+        for (uint32_t i = 0; i < nf && !bad; i++)
+            bad = gt_str(&t, G->feat_id[i]) || gt_u64(&t, '\t', cells[i]) || gt_u64(&t, '\t', umis[i]) || gt_str(&t, "\n");
+        snprintf(path, sizeof path, "%s/genes.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+        if (bad) return 1;
+    }
+    fputs(row, G->tsv.f);
+    return 0;
+}
+
+/* ok: the grid file, then the table; otherwise nothing of either is left */
+int fastf_res_genes_close(res_genes_t *G, int ok)
+{
+    if (!G->on) return 0;
+    int rc = 0;
+    if (ok) {
+        char path[4200];
+        gtext t = { NULL, 0, 0 };
+        int bad = gt_str(&t, "feature");
+        for (uint32_t p = 0; p < G->n_points && !bad; p++) bad = gt_str(&t, "\t") || gt_str(&t, G->names[p]);
+        if (!bad) bad = gt_str(&t, "\n");
+        for (uint32_t i = 0; i < G->n_features && !bad; i++) {
+            bad = gt_str(&t, G->feat_id[i]);
+            for (uint32_t p = 0; p < G->n_points && !bad; p++) bad = gt_u64(&t, '\t', G->cells[(size_t)p * G->n_features + i]);
+            if (!bad) bad = gt_str(&t, "\n");
+        }
+        snprintf(path, sizeof path, "%s/%s_gene_cells.tsv.gz", G->out_dir, G->verb);
+        if (!bad) bad = gz_text_renamed(path, &t);
+        free(t.p);
+        rc = bad;
+    }
+    char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+    if (fastf_res_tsv_close(&G->tsv, ok && !rc)) rc = 1; else if (rc) fastf_set_error_(keep);
+    genes_release(G);
+    G->on = 0;
+    return rc;
+}
+
 struct ropt { char s; const char *l; int has_arg; };
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *out)
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {0, NULL, 0}};
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0;
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {0, NULL, 0}};
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -313,7 +442,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S') { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S' && k->s != 'G') { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -339,6 +468,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                   break;
         case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", u_message); return 1;
         case 'S': out->summary_only = 1; break;
+        case 'G': out->genes = 1; break;
         }
     }
     return 0;

@@ -22,7 +22,7 @@ enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys w
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
 enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_WORDS_ = 160 };
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write; } res_times_t;
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes; } res_times_t;   /* genes: --genes alone (D2H, rows, files) */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
@@ -51,12 +51,15 @@ typedef struct {
     uint64_t key_slots, H;
     void *d_blk, *d_keys, *d_tmp, *d_small, *d_rows, *d_upc, *d_gpc;
     uint64_t *h_small, *h_upc; uint32_t *h_gpc, *h_rows; uint64_t h_rows_cap;
+    int genes; uint32_t n_features;      /* --genes: the per-gene arrays of a point (n_features entries each), else NULL */
+    void *d_cpg, *d_upg; uint32_t *h_cpg; uint64_t *h_upg;
 } res_rate_t;
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
-                         uint32_t seed, int device, res_times_t *T) FASTF_HIDDEN;
+                         uint32_t seed, int device, int genes, res_times_t *T) FASTF_HIDDEN;
 void fastf_res_rate_close(res_rate_t *S) FASTF_HIDDEN;
 /* one point: K1b on the decision plane (H decisions), sort, reduce, rows gathered on the device, per-cell summary to the host
- * (S->h_upc[0 .. n_cells]: UMIs per cell and their sum, S->h_gpc: genes per cell); counters = {total, sampled, sampled_valid} */
+ * (S->h_upc[0 .. n_cells]: UMIs per cell and their sum, S->h_gpc: genes per cell) and, with S->genes, the per-gene summary on the
+ * same stream (S->h_cpg: cells per gene, S->h_upg: UMIs per gene); counters = {total, sampled, sampled_valid} */
 int  fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t counters[3], uint64_t *nnz, res_times_t *T) FASTF_HIDDEN;
 /* the rows of the last point into pinned memory, and the three files of bam2db into dir (created) */
 int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz,
@@ -68,10 +71,26 @@ typedef struct { FILE *f; char tmp[4096], final[4096]; } res_tsv_t;
 int fastf_res_tsv_open(res_tsv_t *t, const char *out_dir, const char *name, const char *header) FASTF_HIDDEN;
 int fastf_res_tsv_close(res_tsv_t *t, int ok) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only and ONE list option of the verb's own (list_short /
+/* --genes of a verb: <out_dir>/<verb>_genes.tsv (one row per point, through .partial), <out_dir>/<verb>_gene_cells.tsv.gz (the cells
+ * per gene of every point, written by a close with ok != 0) and <point dir>/genes.tsv.gz.  on == 0: every call does nothing */
+typedef struct {
+    int on; const char *verb; char out_dir[4096];
+    res_tsv_t tsv;
+    uint32_t n_features, n_points, max_points;
+    char **feat_id;                      /* copies: the lists of the first point */
+    uint32_t *cells;                     /* [max_points][n_features] */
+    char (*names)[64];                   /* the point directory names */
+} res_genes_t;
+int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points) FASTF_HIDDEN;
+/* one point: `row` (fastf_genes_summary_row) into the table, cells[] kept for the grid file, and — dir != NULL — dir/genes.tsv.gz */
+int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *point_name, const char *dir, const char *row,
+                          const uint32_t *cells, const uint64_t *umis) FASTF_HIDDEN;
+int fastf_res_genes_close(res_genes_t *G, int ok) FASTF_HIDDEN;
+
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes and ONE list option of the verb's own (list_short /
  * list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists). */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only; } res_args_t;
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes; } res_args_t;
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;
 int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;

@@ -12,6 +12,8 @@
  * (fastf_dev_cell_summary), and — unless --summary-only — the rows gathered into pinned memory for the writers of bam2db.
  * Jobs this form does not cover (keys wider than 64 bits, UMIs beyond 16 bases, several devices) run point by point
  * through bam2db() itself, the summary then read back from each point's matrix.
+ * --genes: per point the rows reduced along the gene axis too (fastf_dev_gene_summary; point by point fastf_sweep_genes_from_coo)
+ * into sweep_genes.tsv, sweep_gene_cells.tsv.gz and the point's genes.tsv.gz (resident.c).
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -165,6 +167,52 @@ int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, co
 }
 
 /* ------------------------------------------------------------------ */
+/* --genes: the host twin, the row                                     */
+/* ------------------------------------------------------------------ */
+/* per gene (1-based feature g -> slot g - 1) the rows with count >= 1 and the sum of the counts: the host form of
+ * fastf_dev_gene_summary (the point-by-point path, tests); a feature outside 1 .. n_features adds nothing, as there */
+int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint32_t *cells_per_gene, uint64_t *umis_per_gene)
+{
+    if (!coo || (n_features && (!cells_per_gene || !umis_per_gene)) || (coo->nnz && (!coo->feature || !coo->count))) return sw_err("null argument");
+    memset(cells_per_gene, 0, (size_t)n_features * sizeof *cells_per_gene);
+    memset(umis_per_gene, 0, (size_t)n_features * sizeof *umis_per_gene);
+    for (size_t i = 0; i < coo->nnz; i++) {
+        const uint32_t g = coo->feature[i] - 1u;
+        if (g >= n_features) continue;
+        cells_per_gene[g] += coo->count[i] >= 1;
+        umis_per_gene[g] += coo->count[i];
+    }
+    return 0;
+}
+
+const char *fastf_sweep_genes_header(void)
+{
+    return "rate_cell\trate_depth\tseed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n";
+}
+const char *fastf_cap_genes_header(void)
+{
+    return "rate_cell\treads_per_cell\tseed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n";
+}
+
+/* one row of sweep_genes.tsv (reads_per_cell == 0) or cap_genes.tsv (reads_per_cell >= 1: a cap is at least 1), with its newline */
+int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *cells_per_gene,
+                            const uint64_t *umis_per_gene, uint32_t n_features, char *buf, size_t cap)
+{
+    if (!buf || (n_features && (!cells_per_gene || !umis_per_gene))) return sw_err("null argument");
+    uint32_t d1 = 0, d3 = 0, d10 = 0;
+    uint64_t top = 0;
+    for (uint32_t g = 0; g < n_features; g++) {
+        d1 += cells_per_gene[g] >= 1; d3 += cells_per_gene[g] >= 3; d10 += cells_per_gene[g] >= 10;
+        if (umis_per_gene[g] > top) top = umis_per_gene[g];
+    }
+    char second[32];
+    if (reads_per_cell) snprintf(second, sizeof second, "%llu", (unsigned long long)reads_per_cell);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%llu\n", (double)rate_cell, second, seed, d1, d3, d10, (unsigned long long)top);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -173,7 +221,7 @@ static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_op
 /* point by point through bam2db()                                     */
 /* ------------------------------------------------------------------ */
 /* counters, dimensions and rows of a matrix.mtx.gz bam2db() wrote */
-static int read_matrix(const char *path, uint64_t counters[3], uint32_t *n_cells, fastf_coo_t *coo, uint32_t **rows_out)
+static int read_matrix(const char *path, uint64_t counters[3], uint32_t *n_features, uint32_t *n_cells, fastf_coo_t *coo, uint32_t **rows_out)
 {
     gzFile g = gzopen(path, "rb");
     if (!g) return sw_err("cannot read %s back", path);
@@ -193,7 +241,7 @@ static int read_matrix(const char *path, uint64_t counters[3], uint32_t *n_cells
         if (!have_dims) {
             size_t nf, nb;
             if (sscanf(line, "%zu %zu %zu", &nf, &nb, &nnz) != 3) { sw_err("%s: no dimension line", path); goto done; }
-            *n_cells = (uint32_t)nb;
+            *n_features = (uint32_t)nf; *n_cells = (uint32_t)nb;
             rows = (uint32_t *)malloc((nnz ? nnz : 1) * 12);
             if (!rows) { sw_err("out of memory"); goto done; }
             have_dims = 1;
@@ -214,11 +262,14 @@ done:
 }
 
 static int sweep_point_by_point(const char *bam, const char *out_dir, const char *barcodes, const char *features,
-                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, res_tsv_t *tsv)
+                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, res_tsv_t *tsv,
+                                res_genes_t *G)
 {
     const int saved_u = _umi_copies_flag;
     _umi_copies_flag = 0;
     int rc = 1;
+    fastf_lists_t GL; memset(&GL, 0, sizeof GL);           /* --genes: the feature names (bam2db() loads its own lists) */
+    if (G->on && fastf_lists_load(barcodes, features, 1.0f, seed, &GL)) goto done;
     for (uint32_t i = 0; i < n_c; i++)
         for (uint32_t j = 0; j < n_r; j++) {
             char name[64], dir[4096], path[4200];
@@ -227,9 +278,9 @@ static int sweep_point_by_point(const char *bam, const char *out_dir, const char
             else snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_make_dir(dir)) goto done;
             const int brc = bam2db((char *)bam, NULL, dir, (char *)barcodes, (char *)features, rc_list[i], rd_list[j], seed);
-            uint64_t counters[3]; uint32_t n_cells = 0; fastf_coo_t coo; uint32_t *rows = NULL;
+            uint64_t counters[3]; uint32_t n_features = 0, n_cells = 0; fastf_coo_t coo; uint32_t *rows = NULL;
             snprintf(path, sizeof path, "%s/matrix.mtx.gz", dir);
-            int prc = brc ? 1 : read_matrix(path, counters, &n_cells, &coo, &rows);
+            int prc = brc ? 1 : read_matrix(path, counters, &n_features, &n_cells, &coo, &rows);
             if (summary_only) {
                 static const char *const files[] = {"matrix.mtx.gz", "barcodes.tsv.gz", "features.tsv.gz"};
                 for (int k = 0; k < 3; k++) { snprintf(path, sizeof path, "%s/%s", dir, files[k]); unlink(path); }
@@ -243,12 +294,24 @@ static int sweep_point_by_point(const char *bam, const char *out_dir, const char
             char row[512];
             prc = !upc || !gpc || fastf_sweep_cells_from_coo(&coo, n_cells, upc, gpc, &umis) ||
                   fastf_sweep_summary_row(rc_list[i], rd_list[j], seed, counters, coo.nnz, umis, upc, gpc, n_cells, row, sizeof row);
-            free(upc); free(gpc); free(rows);
+            free(upc); free(gpc);
+            if (!prc && G->on) {
+                char grow[256];
+                uint32_t *cpg = (uint32_t *)calloc((size_t)n_features + 1, sizeof *cpg);
+                uint64_t *upg = (uint64_t *)calloc((size_t)n_features + 1, sizeof *upg);
+                prc = !cpg || !upg || (n_features != GL.n_features && sw_err("%s names %u features, the list has %zu", name, n_features, GL.n_features)) ||
+                      fastf_sweep_genes_from_coo(&coo, n_features, cpg, upg) ||
+                      fastf_genes_summary_row(rc_list[i], rd_list[j], 0, seed, cpg, upg, n_features, grow, sizeof grow) ||
+                      fastf_res_genes_point(G, &GL, name, summary_only ? NULL : dir, grow, cpg, upg);
+                free(cpg); free(upg);
+            }
+            free(rows);
             if (prc) goto done;
             fputs(row, tsv->f);
         }
     rc = 0;
 done:
+    if (G->on) fastf_lists_free(&GL);
     _umi_copies_flag = saved_u;
     return rc;
 }
@@ -259,14 +322,14 @@ done:
 /* one cell rate: the engine, the records in its layout, K1a, the planes, then every depth rate */
 static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           res_times_t *T)
+                           res_genes_t *G, res_times_t *T)
 {
     int rc = RES_FAIL;
     res_rate_t S;
     void *d_planes = NULL;
     uint64_t *thr = (uint64_t *)malloc(n_r * sizeof *thr);
     if (!thr) { sw_err("out of memory"); memset(&S, 0, sizeof S); goto done; }
-    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, T)) != RES_OK) goto done;
+    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
     const uint64_t H = S.H;
     double tt = fastf_res_now();
@@ -291,6 +354,13 @@ static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const ui
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_point_write(&S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
         }
+        if (G->on) {
+            char grow[256];
+            tt = fastf_res_now();
+            if (fastf_genes_summary_row(rate_cell, rd_list[j], 0, seed, S.h_cpg, S.h_upg, S.n_features, grow, sizeof grow) ||
+                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
+            T->genes += fastf_res_now() - tt;
+        }
         fputs(row, tsv);
     }
     rc = RES_OK;
@@ -302,7 +372,8 @@ done:
 }
 
 static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
-                          const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv)
+                          const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
+                          res_genes_t *G)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -319,7 +390,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
 
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, &T);
+        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, G, &T);
         if (rc != RES_OK) goto done;
     }
     rc = RES_OK;
@@ -327,6 +398,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
         fprintf(stderr, "[sweep] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, planes %.3f s, "
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
                 T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+    if (prof && G->on) fprintf(stderr, "[sweep] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
 done:
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
@@ -342,27 +414,32 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)FASTF_SWEEP_SUMMARY_ONLY) return sw_err("sweep: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0;
+    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES)) return sw_err("sweep: unknown flags 0x%x", flags);
+    const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
     if (fastf_res_make_dir(out_dir)) return 1;
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
+    res_genes_t G;
+    if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r)) { fastf_res_tsv_close(&tsv, 0); return 1; }
 
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
-    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f);
+    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f, &G);
     if (rc == RES_NOT_COVERED) {
         fprintf(stderr, "sweep: this job is outside the resident form (%s): running bam2db point by point\n",
                 several ? "several devices" : "keys wider than 64 bits or UMIs beyond what a 64-bit key holds");
         /* (rows a resident attempt had written are of no use: the table starts again) */
         fastf_res_tsv_close(&tsv, 0);
+        fastf_res_genes_close(&G, 0);
         if (tsv_open(&tsv, out_dir)) return 1;
-        rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, &tsv);
+        if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+        rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, &tsv, &G);
     }
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_set_error_(keep); return 1; }
+    if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_set_error_(keep); return 1; }
     return fastf_res_tsv_close(&tsv, 1);
 }
 
@@ -381,7 +458,8 @@ static void usage_sweep(FILE *f)
             "    -r, --depth=<list>    rates of depth, comma separated (default 1.0)\n"
             "    -o, --out=<str>       path to output directory (default .)\n"
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
-            "        --summary-only    write sweep.tsv alone\n");
+            "        --summary-only    write sweep.tsv alone\n"
+            "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n");
 }
 
 #define SWEEP_MAX_RATES 64
@@ -399,10 +477,11 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0)) {
+    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0))) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
     }
+    if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;
 }

@@ -7,6 +7,7 @@
 #include "umi_kernels.hpp"
 #include "sweep_kernels.hpp"
 #include "cap_kernels.hpp"
+#include "gene_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -227,6 +228,7 @@ struct fastf_engine {
     // whether cell_hits_kernel<true> has its dynamic-LDS attribute on this engine's device
     bool mtwords_kept = false; u32 mtwords_seed = 0; u64 mtwords_skip = 0, mtwords_n = 0;
     bool cap_lds_attr = false;
+    bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
     DevBuf d_mtsub, d_mtpoly, d_mtseat, d_mtseq;   // parallel generator (jump-ahead): the sub-streams' states; the jump polynomials; the state fastf_dev_mt_decisions seats; the sources' sequences
@@ -1093,6 +1095,44 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
     return 0;
 } FASTF_CATCH_INT
 
+// Per-gene summary of COO rows in any order (gene_summary_kernel): d_cells_per_gene[g - 1] = rows of gene g with count >= 1,
+// d_umis_per_gene[g - 1] = the sum of their counts.  Both arrays are cleared here first; *d_nnz rows are read.  The sum of all
+// counts is below 2^32 (the LDS form keeps both numbers of a gene in one 64-bit counter).
+extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_features,
+                                      uint32_t* d_cells_per_gene, uint64_t* d_umis_per_gene, void* stream) FASTF_TRY {
+    if (!e || !d_nnz || (n_features && (!d_cells_per_gene || !d_umis_per_gene))) return set_err("null argument");
+    if (e->multi) return set_err("fastf_dev_gene_summary: device-level calls take a single-device engine");
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!n_features) return 0;
+    HIP_OK(hipMemsetAsync(d_cells_per_gene, 0, (size_t)n_features * sizeof(u32), s));
+    HIP_OK(hipMemsetAsync(d_umis_per_gene, 0, (size_t)n_features * sizeof(u64), s));
+    if (!d_feature || !d_count) return 0;               // (no row buffer: a reduce of nothing)
+    // up to GENE_LDS_RANGES ranges of GENE_LDS_GENES genes take the LDS form, each range with its own share of the workgroups (every
+    // range reads all rows); FASTF_GENE_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs).  The row count
+    // lives on the device: the grid is sized by the device alone.
+    const u32 n_ranges = (n_features + GENE_LDS_GENES - 1) / GENE_LDS_GENES;
+    const char* mr = getenv("FASTF_GENE_LDS_RANGES");
+    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), GENE_LDS_RANGES) : GENE_LDS_RANGES;
+    if (n_ranges <= max_ranges) {
+        const size_t lds = (size_t)std::min<u32>(n_features, GENE_LDS_GENES) * sizeof(u64);
+        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
+        if (!e->gene_lds_attr) {                                 // (per engine, on first use: the attribute belongs to the current device's function)
+            HIP_OK(hipFuncSetAttribute((const void*)gene_summary_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GENE_LDS_GENES * sizeof(u64))));
+            e->gene_lds_attr = true;
+        }
+        const u32 groups = std::max<u32>(1u, per_cu * (u32)g_cu_count / n_ranges);
+        hipLaunchKernelGGL(gene_summary_kernel<true>, dim3(groups * n_ranges), dim3(GENE_THREADS), lds, s, d_feature, d_count, (const u64*)d_nnz, n_features,
+                           d_cells_per_gene, (u64*)d_umis_per_gene, n_ranges);
+    } else {
+        hipLaunchKernelGGL(gene_summary_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_count, (const u64*)d_nnz, n_features,
+                           d_cells_per_gene, (u64*)d_umis_per_gene, 1u);
+    }
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "gene summary");
+    return 0;
+} FASTF_CATCH_INT
+
 // cap: hits per cell from the cell scratch K1a left (cell_hits_kernel).  Valid right after fastf_dev_count_hits[_blocked] over the
 // same n records on the same stream (the FASTF_PROBE_REUSE_HITS contract); d_blocked: the blocked buffer of that call, or
 // nullptr for the SoA scratch.  d_hits_per_cell[c - 1] (u32, n_cells entries) is cleared here first.
@@ -1659,7 +1699,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

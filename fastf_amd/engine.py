@@ -381,6 +381,12 @@ class Engine:
         the last is the sum of all counts), d_genes_per_cell[c - 1] = its rows with count >= 1 (u32); both cleared by the call"""
         check(self._L.fastf_dev_cell_summary(self._h, d_cell, d_count, d_nnz, n_cells, d_umis_per_cell, d_genes_per_cell, stream))
 
+    def dev_gene_summary(self, d_feature, d_count, d_nnz, n_features, d_cells_per_gene, d_umis_per_gene, stream=0):
+        """rows in any order -> d_cells_per_gene[g - 1] = rows of feature g (1-based) with count >= 1 (u32), d_umis_per_gene[g - 1] =
+        the sum of their counts (u64); n_features entries each, cleared by the call; a feature outside 1 .. n_features adds nothing.
+        The sum of all counts is below 2^32"""
+        check(self._L.fastf_dev_gene_summary(self._h, d_feature, d_count, d_nnz, n_features, d_cells_per_gene, d_umis_per_gene, stream))
+
     def dev_cell_hits(self, n, d_blocked, d_hits_per_cell, stream=0):
         """d_hits_per_cell[c - 1] (u32, n_cells entries, cleared by the call) = records of the last dev_count_hits[_blocked] over
         these n records whose cell index is c; d_blocked: that call's blocked buffer, or 0 / None for the SoA scratch"""

@@ -9,8 +9,10 @@ from . import _lib
 from ._lib import Coo
 
 SUMMARY_ONLY = 1      # FASTF_SWEEP_SUMMARY_ONLY
+GENES = 2             # FASTF_SWEEP_GENES
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
+GENES_COLUMNS = ("rate_cell", "rate_depth", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
 
 
 def _floats(v):
@@ -18,14 +20,15 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False):
-    """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only]`; returns the
-    rows of out/sweep.tsv as dicts of strings (read_table)"""
+def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False):
+    """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes]`; returns
+    the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv (read_genes_table),
+    out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), SUMMARY_ONLY if summary_only else 0))
+                                      seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -33,6 +36,13 @@ def read_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""
     return [dict(zip(COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def read_genes_table(path):
+    """the rows of sweep_genes.tsv as dicts of strings"""
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(GENES_COLUMNS) and lines[-1] == ""
+    return [dict(zip(GENES_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
 
 
 def parse_rates(text: str, cell_rates: bool = False):
@@ -70,6 +80,33 @@ def cells_from_coo(cell, count, n_cells: int):
     upc, gpc, tot = np.zeros(max(n_cells, 1), np.uint64), np.zeros(max(n_cells, 1), np.uint32), C.c_uint64()
     _lib.check(_lib.lib().fastf_sweep_cells_from_coo(C.byref(coo), n_cells, upc.ctypes.data, gpc.ctypes.data, C.byref(tot)))
     return upc[:n_cells], gpc[:n_cells], int(tot.value)
+
+
+def genes_from_coo(feature, count, n_features: int):
+    """(cells per gene u32[n_features], umis per gene u64[n_features]) of rows in any order: the host form of
+    Engine.dev_gene_summary"""
+    f = np.ascontiguousarray(feature, dtype=np.uint32)
+    k = np.ascontiguousarray(count, dtype=np.uint32)
+    c = np.zeros(len(f), dtype=np.uint32)
+    p32 = C.POINTER(C.c_uint32)
+    coo = Coo(f.ctypes.data_as(p32), c.ctypes.data_as(p32), k.ctypes.data_as(p32), len(f))
+    cpg, upg = np.zeros(max(n_features, 1), np.uint32), np.zeros(max(n_features, 1), np.uint64)
+    _lib.check(_lib.lib().fastf_sweep_genes_from_coo(C.byref(coo), n_features, cpg.ctypes.data, upg.ctypes.data))
+    return cpg[:n_features], upg[:n_features]
+
+
+def genes_header() -> str:
+    return _lib.lib().fastf_sweep_genes_header().decode()
+
+
+def genes_summary_row(rate_cell, rate_depth, seed, cells_per_gene, umis_per_gene, reads_per_cell: int = 0) -> str:
+    """one row of sweep_genes.tsv (with its newline); reads_per_cell >= 1: a row of cap_genes.tsv"""
+    cpg = np.ascontiguousarray(cells_per_gene, dtype=np.uint32)
+    upg = np.ascontiguousarray(umis_per_gene, dtype=np.uint64)
+    buf = C.create_string_buffer(256)
+    _lib.check(_lib.lib().fastf_genes_summary_row(float(rate_cell), float(rate_depth), int(reads_per_cell), seed, cpg.ctypes.data, upg.ctypes.data,
+                                                  len(cpg), buf, len(buf)))
+    return buf.value.decode()
 
 
 def summary_row(rate_cell, rate_depth, seed, counters, nnz, umis, umis_per_cell, genes_per_cell) -> str:

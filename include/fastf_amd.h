@@ -118,6 +118,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
 int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
+#define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags);
 /* the host pieces of it: a comma-separated list of rates (strtof per element; empty elements, trailing characters, NaN and negative
@@ -127,6 +128,22 @@ int fastf_sweep_parse_rates(const char *text, int cell_rates, float *out, uint32
 int fastf_sweep_check_grid(const float *rates_cell, uint32_t n_c, const float *rates_depth, uint32_t n_r);
 int fastf_sweep_point_dir(float rate_cell, float rate_depth, char *buf, size_t cap);
 const char *fastf_sweep_header(void);
+/* --genes (FASTF_SWEEP_GENES, FASTF_CAP_GENES): per-gene detection across the grid.  For a point, cells[g - 1] = matrix rows of
+ * feature g with count >= 1 (the cells that detect the gene: the rule of genes per cell) and umis[g - 1] = the sum of their counts.
+ *   <out_dir>/sweep_genes.tsv (cap_genes.tsv): a header and one row per point in sweep.tsv's order, all integers but the rates:
+ *     rate_cell rate_depth|reads_per_cell seed genes_detected genes_min_cells_3 genes_min_cells_10 max_gene_umis
+ *     (genes with cells >= 1, >= 3, >= 10; the largest umis[]); written as .partial and renamed, as sweep.tsv is
+ *   <out_dir>/sweep_gene_cells.tsv.gz (cap_gene_cells.tsv.gz): header `feature` and the point directory names, then one row per
+ *     feature in list order — its id, the first field of its line in features.tsv.gz — with cells[] of every point; written with
+ *     --summary-only too, and left only when every point is done
+ *   <point dir>/genes.tsv.gz (not with --summary-only): `feature id \t cells \t umis` for every feature in list order
+ * Every other output is the bytes it is without the flag.  sweep's point-by-point path fills the same files from each point's matrix. */
+const char *fastf_sweep_genes_header(void);
+const char *fastf_cap_genes_header(void);
+/* one row of either table (with its newline): reads_per_cell == 0 prints rate_depth (%.3f) in the second column — a sweep row —
+ * and reads_per_cell >= 1 prints that integer — a cap row */
+int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *cells_per_gene,
+                            const uint64_t *umis_per_gene, uint32_t n_features, char *buf, size_t cap);
 
 /* --- cap: every cell downsampled to at most N reads (cap_cmds.c; not a command of the reference).  For one point (cell rate c,
  * cap N >= 1, seed s): the cells are sampled as `bam2db -c c -s s` samples them; h[k] = records whose CB is sampled cell k (counted
@@ -141,6 +158,7 @@ const char *fastf_sweep_header(void);
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
 int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
+#define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
               const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags);
 /* the host pieces of it: a comma-separated list of caps (decimal integers >= 1; empty elements, signs, trailing characters and
@@ -280,6 +298,10 @@ typedef struct fastf_umi_rows {     /* -u output, ascending (cell, feature, blob
 int fastf_sweep_cells_from_coo(const fastf_coo_t *coo, uint32_t n_cells, uint64_t *umis_per_cell, uint32_t *genes_per_cell, uint64_t *umis);
 int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                             const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap);
+
+/* --genes (section 1): per gene (1-based feature g -> slot g - 1) the rows with count >= 1 and the sum of the counts of a COO in any
+ * order — the host form of fastf_dev_gene_summary; a row whose feature is outside 1 .. n_features adds nothing, as there */
+int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint32_t *cells_per_gene, uint64_t *umis_per_gene);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -449,6 +471,14 @@ int fastf_dev_mt_decisions_multi(fastf_engine_t *e, uint32_t seed, uint64_t skip
  * call.  d_cell / d_count may be NULL when there are no rows. */
 int fastf_dev_cell_summary(fastf_engine_t *e, const uint32_t *d_cell, const uint32_t *d_count, const uint64_t *d_nnz, uint32_t n_cells,
                            uint64_t *d_umis_per_cell, uint32_t *d_genes_per_cell, void *stream);
+/* Per-gene summary of the same rows, in any order: *d_nnz rows of d_feature (1-based, the matrix's row number: what
+ * fastf_dev_reduce / fastf_dev_rows_gather leave) and d_count.  d_cells_per_gene[g - 1] = rows of feature g with count >= 1 (u32),
+ * d_umis_per_gene[g - 1] = the sum of their counts (u64): n_features entries each, cleared by the call, nothing behind them written.
+ * A row whose feature is outside 1 .. n_features adds nothing.  Precondition: the sum of ALL counts is below 2^32 (it is a number of
+ * records, and the device-level calls stop at 2^32 - 2 records) — up to 131 072 features both numbers of a gene share one 64-bit
+ * counter in LDS (FASTF_GENE_LDS_RANGES=0: global atomics always).  d_feature / d_count may be NULL when there are no rows. */
+int fastf_dev_gene_summary(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_count, const uint64_t *d_nnz,
+                           uint32_t n_features, uint32_t *d_cells_per_gene, uint64_t *d_umis_per_gene, void *stream);
 
 /* cap (section 1) on the device.  fastf_dev_cell_hits: d_hits_per_cell[c - 1] (u32, the engine's n_cells entries, cleared by the call)
  * = records whose cell index in K1a's scratch is c.  Valid right after fastf_dev_count_hits (d_blocked NULL: the SoA scratch) or
