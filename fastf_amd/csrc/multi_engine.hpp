@@ -237,6 +237,7 @@ static int multi_create(const fastf_engine_config_t* cfg, fastf_engine* e) {
     e->skip_bits = m->d[0].e->skip_bits; e->n_cells = cfg->n_cells; e->n_features = cfg->n_features;
     e->use_lds_cells = m->d[0].e->use_lds_cells; e->use_lds_genes = m->d[0].e->use_lds_genes; e->lds_genes = m->d[0].e->lds_genes;
     e->wide = m->d[0].e->wide; e->long_umi = m->d[0].e->long_umi; e->sub_bits = m->d[0].e->sub_bits; e->group_bits = m->d[0].e->group_bits;
+    decide_stream_k1b(e);                                  // (fastf_dev_probe_capacity on the handle: the answer of a single shard with these tables)
     return 0;
 }
 
@@ -285,8 +286,12 @@ static int multi_retire_chunk(fastf_multi* m) {
     u64* small = (u64*)se->d_small.p;
     char* ds = (char*)md.d_stage[c.slot].p;
     // wide keys: the values of destination h behind the keys of all destinations; UMIs beyond 16 bases: the chunk's fifth array
-    u64* const wide_vals = se->wide ? (u64*)md.d_shard.p + (u64)m->G * md.stride : nullptr;
-    const u32* const wide_ext = se->long_umi ? (const u32*)(ds + o_ext) : nullptr;
+    ProbeJob j{};                                          // (K1a ran at enqueue: its hit counts are what this chunk's draws hang on)
+    j.cb = (const u64*)ds; j.gx = (const u64*)(ds + o_gx); j.umi = (const u32*)(ds + o_umi); j.meta = (const u32*)(ds + o_meta); j.n = c.n;
+    j.keys = (u64*)md.d_shard.p; j.stride = md.stride; j.key_counts = small + SM_KEYCOUNT; j.counters = small + SM_COUNTERS;
+    j.reuse_hits = true;
+    if (se->wide) j.wide_vals = (u64*)md.d_shard.p + (u64)m->G * md.stride;
+    if (se->long_umi) j.wide_ext = (const u32*)(ds + o_ext);
     if (m->device_mt) {
         // every device moves the stream on by this chunk's hits (its own copy of the state, its own ring); the owner of the
         // chunk then runs K1b against its ring, hit ranks counted from the stream's start
@@ -313,11 +318,8 @@ static int multi_retire_chunk(fastf_multi* m) {
         if (md.k1b_queued[c.slot]) HIP_OK(hipEventSynchronize(md.ev_k1b[c.slot]));      // (the copy below that last read this word has long gone)
         *md.h_base[c.slot] = base;
         HIP_OK(hipMemcpyAsync(small + SM_DRAWBASE, md.h_base[c.slot], sizeof(u64), hipMemcpyHostToDevice, se->s_compute));
-        if (launch_probe(se, (const u64*)ds, (const u64*)(ds + o_gx), (const u32*)(ds + o_umi), (const u32*)(ds + o_meta), c.n,
-                         (const u32*)md.d_ring.p, base + hits, small + SM_DRAWBASE, (u64*)md.d_shard.p, md.stride, small + SM_KEYCOUNT,
-                         small + SM_COUNTERS, true, se->s_compute, md.ring_len ? md.ring_len - 1 : ~0ull, nullptr, false, nullptr, nullptr,
-                         wide_vals, wide_ext))
-            return 1;
+        j.dbits = (const u32*)md.d_ring.p; j.n_draws = base + hits; j.draw_base = small + SM_DRAWBASE;
+        if (md.ring_len) j.draw_mask = md.ring_len - 1;
     } else {
     if (md.d_draws[c.slot].ensure(std::max<u64>(cap, 1) * 4)) return 1;
     if (!md.h_draws[c.slot]) HIP_OK(hipHostMalloc((void**)&md.h_draws[c.slot], std::max<u64>(cap, 1) * 4, hipHostMallocDefault));
@@ -334,11 +336,9 @@ static int multi_retire_chunk(fastf_multi* m) {
         if (hits & 31) h[hits >> 5] = wcur;
     }
     if (hits) HIP_OK(hipMemcpyAsync(md.d_draws[c.slot].p, md.h_draws[c.slot], ((hits + 31) / 32) * 4, hipMemcpyHostToDevice, se->s_compute));
-    if (launch_probe(se, (const u64*)ds, (const u64*)(ds + o_gx), (const u32*)(ds + o_umi), (const u32*)(ds + o_meta), c.n,
-                     (const u32*)md.d_draws[c.slot].p, hits, nullptr, (u64*)md.d_shard.p, md.stride, small + SM_KEYCOUNT,
-                     small + SM_COUNTERS, true, se->s_compute, ~0ull, nullptr, false, nullptr, nullptr, wide_vals, wide_ext))
-        return 1;
+    j.dbits = (const u32*)md.d_draws[c.slot].p; j.n_draws = hits;
     }
+    if (launch_probe(se, j, se->s_compute)) return 1;
     HIP_OK(hipEventRecord(md.ev_k1b[c.slot], se->s_compute));
     md.k1b_queued[c.slot] = true;
     return 0;

@@ -20,6 +20,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 extern "C" {
@@ -89,6 +90,13 @@ extern "C" void fastf_set_error_(const char* msg) { set_err("%s", msg); }
         if (e_ != hipSuccess)                                                               \
             return set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// How the device-level entry points open.  DEV_SINGLE: the pointers of null_test (the engine `e` first) are there and the engine is a
+// single-device one; DEV_ENTRY: that, then the engine's device made current (entry points with more checks in between: DEV_SINGLE)
+#define DEV_SINGLE(null_test, null_text) do { if (null_test) return set_err(null_text); \
+        if (e->multi) return set_err("%s: device-level calls take a single-device engine", __func__); } while (0)
+#define DEV_ENTRY(null_test, null_text) do { DEV_SINGLE(null_test, null_text); HIP_OK(hipSetDevice(e->device)); } while (0)
+#define NO_WIDE(e, what) do { if ((e)->wide) return set_err(what ": this engine's keys are wider than 64 bits — this call moves one 64 bits word per key (fastf_dev_probe_pack_wide / fastf_dev_adopt_wide + fastf_engine_finish and the host-buffer API take wide keys)"); } while (0)
 
 static u32 bits_for(u64 max_value) {   // bits needed to hold 0..max_value
     u32 b = 0;
@@ -231,6 +239,7 @@ struct fastf_engine {
     bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
+    bool mt_par_ready = false;               // the parallel generator's one-time init went through: tables up, kernel attributes set, d_mtseq there
     DevBuf d_mtsub, d_mtpoly, d_mtseat, d_mtseq;   // parallel generator (jump-ahead): the sub-streams' states; the jump polynomials; the state fastf_dev_mt_decisions seats; the sources' sequences
     u64 draws_up = 0;                    // absolute ranks below this are (being) uploaded
     u64 draws_valid = 0;                 // ranks below this carry a real draw (caller-supplied streams can run short)
@@ -279,6 +288,9 @@ struct fastf_engine {
     // layout and runs the streaming K1b; its regions are appended to the key store, which holds SLOTS (regions with gaps) until
     // fastf_engine_finish sorts out of them
     bool stream_mode = false, store_regions = false;
+    // the streaming K1b, decided once at create (decide_stream_k1b): possible on this single shard (SEGMENTED / BLOCKED calls), in its
+    // sharded form (shard_partition_kernel deals its regions out), and the FASTF_NO_STREAM_K1B switch as it stood then
+    bool stream_single = false, stream_sharded = false, stream_off = false;
     // NARROW blocked runs (umi_kernels.hpp, NBLK_GX): 10 instead of 18 bytes per record; decided once at create — stream mode,
     // every listed feature in the LDS gene family, its numbers below 2^32 - 1, at most 12 UMI bases (FASTF_BLOCK_WIDE=1: never)
     bool narrow = false, genes_one_family = false;
@@ -473,6 +485,13 @@ extern "C" size_t fastf_debug_cell_image(const uint64_t* cell_keys, uint32_t n, 
     return ci.bytes;
 } FASTF_CATCH_ZERO
 
+// filter_pack_stream_kernel's instantiations by number (defined behind build_gene_lds): form (0 SoA, 1 BLOCKED, 2 BLOCKED + NARROW)
+// x 8 | roomy (one workgroup per CU: 128 VGPRs) x 4 | 16-bit cell scratch x 2 | direct gene image.  The one place that names them:
+// the LDS attribute (build_gene_lds) and the launch (launch_probe) both go through it.
+using StreamKernel = void (*)(const PackParams, const StreamParams);
+constexpr u32 N_STREAM_KERNELS = 24;
+static StreamKernel stream_kernel(u32 i);
+
 static int build_gene_lds(fastf_engine* e, const u64* keys, u32 n) {
     if (n == 0 || n > 65535) return 0;
     // most common ID-form family
@@ -519,21 +538,10 @@ static int build_gene_lds(fastf_engine* e, const u64* keys, u32 n) {
     e->lds_genes.image = (const u32*)e->img_genes.p; e->lds_genes.words = words; e->lds_genes.n_perm = (u32)best_n;
     e->lds_genes.family = (u32)best; e->lds_genes.vmin = vmin; e->lds_genes.range = range; e->lds_genes.bytes = (u32)bytes; e->lds_genes.direct = direct ? 1u : 0u;
     {
-        const void* fns[] = {(const void*)filter_pack_kernel<true, false>, (const void*)filter_pack_kernel<true, true>,
-                             (const void*)filter_pack_stream_kernel<false, false, false>, (const void*)filter_pack_stream_kernel<false, false, true>,
-                             (const void*)filter_pack_stream_kernel<false, true, false>, (const void*)filter_pack_stream_kernel<false, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, false, false>, (const void*)filter_pack_stream_kernel<true, false, true>,
-                             (const void*)filter_pack_stream_kernel<true, true, false>, (const void*)filter_pack_stream_kernel<true, true, true>,
-                             (const void*)filter_pack_stream_kernel<false, false, false, true>, (const void*)filter_pack_stream_kernel<false, false, true, true>,
-                             (const void*)filter_pack_stream_kernel<false, true, false, true>, (const void*)filter_pack_stream_kernel<false, true, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, false, false, true>, (const void*)filter_pack_stream_kernel<true, false, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, true, false, true>, (const void*)filter_pack_stream_kernel<true, true, true, true>,
-                             (const void*)filter_pack_stream_kernel<false, false, false, true, true>, (const void*)filter_pack_stream_kernel<false, false, true, true, true>,
-                             (const void*)filter_pack_stream_kernel<false, true, false, true, true>, (const void*)filter_pack_stream_kernel<false, true, true, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, false, false, true, true>, (const void*)filter_pack_stream_kernel<true, false, true, true, true>,
-                             (const void*)filter_pack_stream_kernel<true, true, false, true, true>, (const void*)filter_pack_stream_kernel<true, true, true, true, true>};
-        for (const void* f : fns)
+        for (const void* f : {(const void*)filter_pack_kernel<true, false>, (const void*)filter_pack_kernel<true, true>})
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return 0;
+        for (u32 i = 0; i < N_STREAM_KERNELS; ++i)
+            if (hipFuncSetAttribute((const void*)stream_kernel(i), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return 0;
     }
     const size_t per_block = bytes + 1024;                           // + the kernel's static LDS (about 0.5 KB)
     e->genes_blocks_per_cu = (u32)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / per_block));
@@ -541,10 +549,24 @@ static int build_gene_lds(fastf_engine* e, const u64* keys, u32 n) {
     e->genes_one_family = best_n == n;
     return 0;
 }
+template <size_t... I> static StreamKernel stream_kernel_of(u32 i, std::index_sequence<I...>) {
+    static const StreamKernel k[] = {filter_pack_stream_kernel<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, (I >> 3) >= 1, (I >> 3) == 2>...};
+    return k[i];
+}
+static StreamKernel stream_kernel(u32 i) { return stream_kernel_of(i, std::make_index_sequence<N_STREAM_KERNELS>{}); }
 
 // ------------------------------------------------------------------------------------
 // create / destroy
 // ------------------------------------------------------------------------------------
+// The streaming K1b needs the gene table in LDS and keys of at most 64 bits; FASTF_NO_STREAM_K1B=1 turns it off where the caller has
+// a choice.  Read here, once per engine: the buffer sizes an engine hands out and the launches it makes later cannot disagree.
+static void decide_stream_k1b(fastf_engine* e) {
+    const bool can = e->use_lds_genes && !e->wide;
+    e->stream_single = can && e->n_shards == 1;
+    e->stream_sharded = can && e->n_shards > 1 && e->n_shards <= (u32)MAX_SHARDS;
+    e->stream_off = getenv("FASTF_NO_STREAM_K1B") != nullptr;
+}
+
 extern "C" int fastf_engine_create(const fastf_engine_config_t* cfg, fastf_engine_t** out) FASTF_TRY {
     if (!cfg || !out) return set_err("null argument");
     *out = nullptr;
@@ -656,7 +678,8 @@ extern "C" int fastf_engine_create(const fastf_engine_config_t* cfg, fastf_engin
         e->key_cap = cfg->key_capacity;
         // the push path stages blocked and runs the streaming K1b whenever the engine can (FASTF_PUSH_TILE_FORM=1: SoA staging and
         // the tile form, as lists that keep the gene table in L2, wide keys and sharded engines use)
-        e->stream_mode = e->use_lds_genes && !e->wide && e->n_shards == 1 && !getenv("FASTF_NO_STREAM_K1B") && !getenv("FASTF_PUSH_TILE_FORM");
+        decide_stream_k1b(e);
+        e->stream_mode = e->stream_single && !e->stream_off && !getenv("FASTF_PUSH_TILE_FORM");
         {
             const char* bw = getenv("FASTF_BLOCK_WIDE");
             e->narrow = e->stream_mode && e->genes_one_family && e->lds_genes.vmin + e->lds_genes.range <= 0xFFFFFFFFull &&
@@ -772,9 +795,7 @@ static int reserve_workspace(fastf_engine* e, u64 max_records, u64 max_keys, u64
 }
 
 extern "C" int fastf_dev_reserve(fastf_engine_t* e, uint64_t max_records, uint64_t max_keys) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_reserve: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     return reserve_workspace(e, max_records, max_keys);
 } FASTF_CATCH_INT
 
@@ -799,8 +820,7 @@ static void t_end(fastf_engine* e, hipStream_t s, double* acc, u64* cnt) {
 }
 
 extern "C" int fastf_engine_set_timing(fastf_engine_t* e, int on) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_engine_set_timing: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     e->timing = on != 0;
     e->t_scatter_ms = e->t_k1_ms = e->t_k1b_ms = e->t_k3_ms = e->t_count_ms = e->t_gather_ms = 0;
     e->t_scatter_n = e->t_k1_n = e->t_k1b_n = e->t_k3_n = e->t_count_n = e->t_gather_n = 0;
@@ -871,22 +891,16 @@ static int launch_probe_cells(fastf_engine* e, const u64* cb, u64 n, u64* d_tota
 
 extern "C" int fastf_dev_count_hits(fastf_engine_t* e, const uint64_t* d_cb_key, uint64_t n,
                                     uint64_t* d_hits_out, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_count_hits: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) { HIP_OK(hipMemsetAsync(d_hits_out, 0, sizeof(u64), s)); return 0; }
     return launch_probe_cells(e, (const u64*)d_cb_key, n, (u64*)d_hits_out, s);
 } FASTF_CATCH_INT
 
-static bool stream_k1b_possible(const fastf_engine* e) {
-    return e->use_lds_genes && e->n_shards <= (u32)MAX_SHARDS && !getenv("FASTF_NO_STREAM_K1B");
-}
-
 extern "C" int fastf_dev_block_bytes(const fastf_engine_t* e, uint64_t n, uint64_t* bytes) FASTF_TRY {
     if (!e || !bytes) return set_err("null argument");
     *bytes = 0;
-    if (e->multi || e->wide || !stream_k1b_possible(e)) return 0;
+    if (e->multi || !(e->stream_single || e->stream_sharded) || e->stream_off) return 0;
     *bytes = ((n + BLK_RECS - 1) / BLK_RECS) * (u64)blk_run_bytes(e->cell16, e->narrow);
     return 0;
 } FASTF_CATCH_INT
@@ -903,9 +917,7 @@ static void launch_block_records(const fastf_engine* e, const u64* gx, const u32
 
 extern "C" int fastf_dev_block_records(fastf_engine_t* e, const uint64_t* d_gx_key, const uint32_t* d_umi, const uint32_t* d_meta,
                                        uint64_t n, void* d_blocked, void* stream) FASTF_TRY {
-    if (!e || !d_blocked) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_block_records: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || !d_blocked, "null argument");
     if (n == 0) return 0;
     launch_block_records(e, (const u64*)d_gx_key, d_umi, d_meta, n, d_blocked, (hipStream_t)stream);
     HIP_OK(hipGetLastError());
@@ -915,9 +927,7 @@ extern "C" int fastf_dev_block_records(fastf_engine_t* e, const uint64_t* d_gx_k
 
 extern "C" int fastf_dev_count_hits_blocked(fastf_engine_t* e, const uint64_t* d_cb_key, uint64_t n, void* d_blocked,
                                             uint64_t* d_hits_out, void* stream) FASTF_TRY {
-    if (!e || !d_blocked) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_count_hits_blocked: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || !d_blocked, "null argument");
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) { HIP_OK(hipMemsetAsync(d_hits_out, 0, sizeof(u64), s)); return 0; }
     return launch_probe_cells(e, (const u64*)d_cb_key, n, (u64*)d_hits_out, s, nullptr, nullptr, d_blocked);
@@ -989,13 +999,14 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
         if (words.p) HIP_OK(hipStreamSynchronize(s));
         if (words.ensure(std::max<u64>(count * 4, 1u << 20))) return 1;
     }
-    if (!e->d_mtpoly.p) {                                      // the polynomials: constants of the generator (mt_jump.c), once per engine
+    if (!e->mt_par_ready) {                                    // the polynomials: constants of the generator (mt_jump.c), once per engine
         static_assert(MT_POLY_WORDS == FASTF_MT_POLY_WORDS && MT_SUB_DRAWS == FASTF_MT_SUB_DRAWS && MT_JUMP_R == FASTF_MT_JUMP_R, "kernel and table agree");
         if (e->d_mtpoly.ensure((size_t)FASTF_MT_JUMP_POLYS * MT_POLY_WORDS * sizeof(u64))) return 1;
         if (copy_h2d(e->d_mtpoly.p, fastf_mt_jump_table(), (size_t)FASTF_MT_JUMP_POLYS * MT_POLY_WORDS * sizeof(u64))) return 1;
         HIP_OK(hipFuncSetAttribute((const void*)mt_seq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MT_SEQ_WORDS * sizeof(u32))));
         HIP_OK(hipFuncSetAttribute((const void*)mt_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MT_CONV_LDS_WORDS * sizeof(u32))));
         if (e->d_mtseq.ensure((size_t)MT_JUMP_R * MT_SEQ_STRIDE * sizeof(u32))) return 1;      // the sequences of up to R sources
+        e->mt_par_ready = true;                                // (only now: a call after a failed step runs the init again and fails there, not in a kernel)
     }
     u32* const w = (u32*)words.p;
     if (head) {                                                // the rest of the block the stream stands in
@@ -1040,9 +1051,7 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
 // one for large counts), as a linear array of bits — what a resident pass hands to fastf_dev_probe_pack with
 // FASTF_PROBE_DRAW_BITS (bench.py: the step with its draw generation inside the clock; tests).
 extern "C" int fastf_dev_mt_decisions(fastf_engine_t* e, uint32_t seed, uint64_t skip, uint64_t n_draws, uint32_t* d_bits_out, void* stream) FASTF_TRY {
-    if (!e || (n_draws && !d_bits_out)) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_mt_decisions: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || (n_draws && !d_bits_out), "null argument");
     fastf_mt_t mt; fastf_mt_seed(&mt, seed); fastf_mt_skip(&mt, skip);
     // (the seated state goes into the first slot of the sub-stream array's tail: a buffer the engine keeps)
     if (e->d_mtseat.ensure(sizeof mt)) return 1;
@@ -1058,8 +1067,7 @@ extern "C" int fastf_dev_mt_decisions(fastf_engine_t* e, uint32_t seed, uint64_t
 // thresholds[j].  The engine's own threshold plays no part.  Synchronises the stream.
 extern "C" int fastf_dev_mt_decisions_multi(fastf_engine_t* e, uint32_t seed, uint64_t skip, uint64_t n_draws, const uint64_t* thresholds,
                                             uint32_t n_thresholds, uint32_t* d_planes_out, uint64_t plane_stride_words, void* stream) FASTF_TRY {
-    if (!e || (n_thresholds && !thresholds) || (n_draws && n_thresholds && !d_planes_out)) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_mt_decisions_multi: device-level calls take a single-device engine");
+    DEV_SINGLE(!e || (n_thresholds && !thresholds) || (n_draws && n_thresholds && !d_planes_out), "null argument");
     if (n_draws && n_thresholds && ((plane_stride_words & 1) || plane_stride_words < (n_draws + 63) / 64 * 2 || ((uintptr_t)d_planes_out & 7)))
         return set_err("fastf_dev_mt_decisions_multi: planes are 8-byte aligned and an even number of 32-bit words apart, at least (n_draws + 63) / 64 * 2");
     for (u32 j = 0; j < n_thresholds; ++j)
@@ -1081,9 +1089,7 @@ extern "C" int fastf_dev_mt_decisions_multi(fastf_engine_t* e, uint32_t seed, ui
 // cleared here first; *d_nnz rows are read.
 extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_cells,
                                       uint64_t* d_umis_per_cell, uint32_t* d_genes_per_cell, void* stream) FASTF_TRY {
-    if (!e || !d_nnz || !d_umis_per_cell || (n_cells && !d_genes_per_cell)) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_cell_summary: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || !d_nnz || !d_umis_per_cell || (n_cells && !d_genes_per_cell), "null argument");
     hipStream_t s = (hipStream_t)stream;
     HIP_OK(hipMemsetAsync(d_umis_per_cell, 0, ((size_t)n_cells + 1) * sizeof(u64), s));
     if (n_cells) HIP_OK(hipMemsetAsync(d_genes_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
@@ -1100,9 +1106,7 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
 // counts is below 2^32 (the LDS form keeps both numbers of a gene in one 64-bit counter).
 extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_features,
                                       uint32_t* d_cells_per_gene, uint64_t* d_umis_per_gene, void* stream) FASTF_TRY {
-    if (!e || !d_nnz || (n_features && (!d_cells_per_gene || !d_umis_per_gene))) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_gene_summary: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || !d_nnz || (n_features && (!d_cells_per_gene || !d_umis_per_gene)), "null argument");
     hipStream_t s = (hipStream_t)stream;
     if (!n_features) return 0;
     HIP_OK(hipMemsetAsync(d_cells_per_gene, 0, (size_t)n_features * sizeof(u32), s));
@@ -1140,8 +1144,7 @@ static CellIn cell_scratch_of(const fastf_engine* e, const void* blk) {
     return blk ? CellIn{blk, blk_run_bytes(e->cell16, e->narrow), blk_cell_off(e->narrow)} : CellIn{e->d_cellidx.p, 0u, 0u};
 }
 extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t* d_hits_per_cell, void* stream) FASTF_TRY {
-    if (!e || (e && e->n_cells && !d_hits_per_cell)) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_cell_hits: device-level calls take a single-device engine");
+    DEV_SINGLE(!e || (e && e->n_cells && !d_hits_per_cell), "null argument");
     if (n >= (1ull << 32)) return set_err("fastf_dev_cell_hits: %llu records: the counters are 32 bits wide", (unsigned long long)n);
     HIP_OK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1184,8 +1187,7 @@ extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_
 // FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS may follow.  Synchronises the stream.
 extern "C" int fastf_dev_cell_decisions(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t seed, uint64_t skip, uint64_t n_draws,
                                         const uint64_t* d_thresholds, uint32_t* d_bits_out, void* stream) FASTF_TRY {
-    if (!e || (n_draws && (!d_bits_out || !d_thresholds))) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_cell_decisions: device-level calls take a single-device engine");
+    DEV_SINGLE(!e || (n_draws && (!d_bits_out || !d_thresholds)), "null argument");
     if ((uintptr_t)d_bits_out & 7) return set_err("fastf_dev_cell_decisions: the plane is 8-byte aligned");
     HIP_OK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1244,13 +1246,9 @@ extern "C" int fastf_devmem_sync(void) FASTF_TRY {
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_draw_bits(fastf_engine_t* e, const uint32_t* d_draws, uint64_t n_draws, uint32_t* d_bits_out, void* stream) FASTF_TRY {
-    if (!e || (n_draws && (!d_draws || !d_bits_out))) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_draw_bits: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e || (n_draws && (!d_draws || !d_bits_out)), "null argument");
     return launch_draw_bits(e->threshold, d_draws, n_draws, d_bits_out, (hipStream_t)stream);
 } FASTF_CATCH_INT
-
-#define NO_WIDE(e, what) do { if ((e)->wide) return set_err(what ": this engine's keys are wider than 64 bits — this call moves one 64 bits word per key (fastf_dev_probe_pack_wide / fastf_dev_adopt_wide + fastf_engine_finish and the host-buffer API take wide keys)"); } while (0)
 
 // the streaming K1b over `tiles` K1a tiles: workgroups (at most two per CU: 12 or 16 waves each) and the key slots of one
 // workgroup's region (every record of the units its waves walk: waves x rounds units)
@@ -1267,27 +1265,35 @@ static void stream_geometry(const fastf_engine* e, u64 tiles, u32* grid, u64* re
 // regions of several launches behind each other in one key store (the push path): where this launch's begin
 struct RegionAppend { u64 slot0; u32 rgn0; };
 
+// One K1 launch (launch_probe).  Value-initialised; a call site names what it sets and leaves the rest alone.
+struct ProbeJob {
+    const u64* cb = nullptr; u64 n = 0;          // the records: their barcode keys and the other three SoA arrays, or the blocked buffer
+    const u64* gx = nullptr; const u32* umi = nullptr; const u32* meta = nullptr; void* blk = nullptr;
+    // decisions: bit (*draw_base + hit rank) & draw_mask of dbits, n_draws of them real; d_running: K1a's scan leaves the running hit
+    // total of the earlier chunks at draw_base and adds this chunk's hits
+    const u32* dbits = nullptr; u64 n_draws = 0; const u64* draw_base = nullptr; u64 draw_mask = ~0ull; u64* d_running = nullptr;
+    u64* keys = nullptr; u64 stride = 0; u64* key_counts = nullptr; u64* counters = nullptr;   // output: keys[n_shards][stride]
+    bool reuse_hits = false;                     // no K1a: fastf_dev_count_hits just ran on these very records (same stream order)
+    bool segmented = false; const RegionAppend* app = nullptr;   // the streaming K1b, keys in workgroup regions; app: behind the store's
+    u64* wide_vals = nullptr; const u32* wide_ext = nullptr;     // wide keys to per-destination buffers: vals[n_shards][stride], bases 17..
+};
+
 static int grow_regions(fastf_engine* e, u32 need);
-static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32* umi, const u32* meta, u64 n,
-                        const u32* dbits, u64 n_draws, const u64* draw_base, u64* keys, u64 stride, u64* key_counts,
-                        u64* counters, bool reuse_hits, hipStream_t s, u64 draw_mask = ~0ull, u64* d_running = nullptr,
-                        bool segmented = false, void* blk = nullptr, const RegionAppend* app = nullptr,
-                        u64* wide_vals = nullptr, const u32* wide_ext = nullptr) {
+static int launch_probe(fastf_engine* e, const ProbeJob& j, hipStream_t s) {
+    const u64 n = j.n; void* const blk = j.blk; const RegionAppend* const app = j.app; const bool segmented = j.segmented;
     if (segmented && !app) { e->seg_n = 0; e->rgn_hist_n = 0; }
     if (n == 0) return 0;
-    // K1a, unless the caller states that fastf_dev_count_hits just ran on these very records (same stream order).
-    // d_running: the scan leaves the running hit total of the earlier chunks at draw_base and adds this chunk's hits.
-    if (!reuse_hits && launch_probe_cells(e, cb, n, nullptr, s, d_running, d_running ? const_cast<u64*>(draw_base) : nullptr, blk)) return 1;
+    if (!j.reuse_hits && launch_probe_cells(e, j.cb, n, nullptr, s, j.d_running, j.d_running ? const_cast<u64*>(j.draw_base) : nullptr, blk)) return 1;
     const u32 tiles = (u32)((n + K1_TILE - 1) / K1_TILE);
     PackParams p{};
-    p.cell = e->d_cellidx.p; p.cell16 = e->cell16; p.gx = gx; p.umi = umi; p.meta = meta; p.n = n;
+    p.cell = e->d_cellidx.p; p.cell16 = e->cell16; p.gx = j.gx; p.umi = j.umi; p.meta = j.meta; p.n = n;
     p.tile_base = (const u64*)e->d_tilebase.p;
     // (the streaming K1b reads a unit's decision words unconditionally: a stream without a decision still needs a word to read)
-    p.dbits = dbits && n_draws ? dbits : (const u32*)e->d_small.p; p.n_draws = dbits ? n_draws : 0; p.draw_base = draw_base; p.draw_mask = draw_mask;
+    p.dbits = j.dbits && j.n_draws ? j.dbits : (const u32*)e->d_small.p; p.n_draws = j.dbits ? j.n_draws : 0; p.draw_base = j.draw_base; p.draw_mask = j.draw_mask;
     p.feats = e->feats;
     p.L = e->L;
     p.n_shards = e->n_shards;
-    p.keys = keys; p.shard_stride = stride; p.key_counts = key_counts; p.counters = counters;
+    p.keys = j.keys; p.shard_stride = j.stride; p.key_counts = j.key_counts; p.counters = j.counters;
     p.stamps = g_k1_stamps;
     p.n_tiles = tiles;
     p.genes = e->lds_genes;
@@ -1296,14 +1302,14 @@ static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32
         // wide keys (tile form): group word into keys[], the rest into vals[] — the engine's own store (one shard), or
         // wide_vals[n_shards][stride] beside keys[n_shards][stride] (the multi-device engine's per-destination buffers)
         if (segmented || blk) return set_err("internal error: wide keys take the tile form");
-        if (!wide_vals && (e->n_shards != 1 || keys != (u64*)e->d_keys.p)) return set_err("internal error: wide keys go through the engine's own key store");
-        p.vals = wide_vals ? wide_vals : (u64*)e->d_vals.p; p.wide_feat_bits = e->feat_bits; p.wide_sub_bits = e->sub_bits;
-        p.umi_ext = wide_vals ? wide_ext : e->cur_umi_ext;
+        if (!j.wide_vals && (e->n_shards != 1 || j.keys != (u64*)e->d_keys.p)) return set_err("internal error: wide keys go through the engine's own key store");
+        p.vals = j.wide_vals ? j.wide_vals : (u64*)e->d_vals.p; p.wide_feat_bits = e->feat_bits; p.wide_sub_bits = e->sub_bits;
+        p.umi_ext = j.wide_vals ? j.wide_ext : e->cur_umi_ext;
     }
     // several shards: the streaming kernel writes unsharded into a scratch buffer of workgroup regions, shard_partition_kernel
     // deals the keys to the per-destination buffers (same interface as the tile form: keys[G][stride], key_counts[G] += ...)
-    const bool no_stream = getenv("FASTF_NO_STREAM_K1B") != nullptr;
-    const bool stream_shards = !segmented && !e->wide && e->n_shards > 1 && e->n_shards <= (u32)MAX_SHARDS && e->use_lds_genes && !no_stream;
+    // (a SEGMENTED call has asked for the streaming kernel: the switch is for the callers that leave the choice to the engine)
+    const bool stream_shards = !segmented && e->stream_sharded && !e->stream_off;
     if (blk && !(segmented || stream_shards)) return set_err("FASTF_PROBE_BLOCKED needs the streaming K1b (fastf_dev_block_bytes returns 0 otherwise)");
     t_begin(e, s);
     if (segmented || stream_shards) {
@@ -1314,8 +1320,8 @@ static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32
         if (stream_shards) {
             if (e->d_segkeys.ensure((size_t)n_rgn * region * sizeof(u64))) return 1;
             p.keys = (u64*)e->d_segkeys.p;
-        } else if ((u64)n_rgn * region > stride) return set_err("segmented key output needs %llu slots, the buffer has %llu (fastf_dev_probe_capacity)",
-                                                                (unsigned long long)((u64)n_rgn * region), (unsigned long long)stride);
+        } else if ((u64)n_rgn * region > j.stride) return set_err("segmented key output needs %llu slots, the buffer has %llu (fastf_dev_probe_capacity)",
+                                                                (unsigned long long)((u64)n_rgn * region), (unsigned long long)j.stride);
         if (app) {                                       // the push path has grown the tables (their contents stay)
             if (e->rgn_cap < rgn0 + n_rgn) return set_err("internal error: region tables too small");
         } else {
@@ -1326,26 +1332,17 @@ static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32
         StreamParams sp{(const u32*)e->d_halfhits.p, region, (u64*)e->d_segcount.p + rgn0,
                         stream_shards ? nullptr : (u32*)e->d_rgn_hist.p + (size_t)rgn0 * RADIX, (u64*)e->d_rgn_phys.p + rgn0,
                         app ? app->slot0 : 0ull, e->skip_bits};
-        // compile-time: roomy (one workgroup per CU: 128 VGPRs), width of the cell scratch, form of the gene image
-        const int variant = (e->genes_blocks_per_cu >= 2 ? 0 : 4) | (e->cell16 ? 2 : 0) | (e->lds_genes.direct ? 1 : 0);
-#define FPS(R, C, D) do { if (blk && e->narrow) hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, true, true>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); \
-                          else if (blk) hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, true>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); \
-                          else hipLaunchKernelGGL((filter_pack_stream_kernel<R, C, D, false>), dim3(grid), dim3(R ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp); } while (0)
-        switch (variant) {
-        case 0: FPS(false, false, false); break; case 1: FPS(false, false, true); break;
-        case 2: FPS(false, true, false); break;  case 3: FPS(false, true, true); break;
-        case 4: FPS(true, false, false); break;  case 5: FPS(true, false, true); break;
-        case 6: FPS(true, true, false); break;   default: FPS(true, true, true); break;
-        }
-#undef FPS
+        const bool roomy = e->genes_blocks_per_cu < 2;
+        const u32 variant = (blk ? (e->narrow ? 16u : 8u) : 0u) | (roomy ? 4u : 0u) | (e->cell16 ? 2u : 0u) | (e->lds_genes.direct ? 1u : 0u);
+        hipLaunchKernelGGL(stream_kernel(variant), dim3(grid), dim3(roomy ? K1S_THREADS_ROOMY : K1S_THREADS), e->lds_genes.bytes, s, p, sp);
         if (stream_shards) {
             hipLaunchKernelGGL(shard_partition_kernel, dim3(n_rgn), dim3(SP_THREADS), 0, s, (const u64*)e->d_segkeys.p, (const u64*)e->d_segcount.p,
-                               region, e->L.cell_shift, e->n_shards, keys, stride, key_counts, counters + 3);
+                               region, e->L.cell_shift, e->n_shards, j.keys, j.stride, j.key_counts, j.counters + 3);
         } else if (app) {
             // (the prefix sums are of no use here — the first sort pass walks the regions — the running key count is)
-            hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, s, (const u64*)e->d_segcount.p + rgn0, n_rgn, (u64*)e->d_segprefix.p, key_counts, true);
+            hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, s, (const u64*)e->d_segcount.p + rgn0, n_rgn, (u64*)e->d_segprefix.p, j.key_counts, true);
         } else {
-            hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, s, (const u64*)e->d_segcount.p, n_rgn, (u64*)e->d_segprefix.p, key_counts, false);
+            hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, s, (const u64*)e->d_segcount.p, n_rgn, (u64*)e->d_segprefix.p, j.key_counts, false);
             e->seg_n = n_rgn; e->seg_stride = region;
             e->rgn_hist_n = n_rgn; e->rgn_hist_shift = e->skip_bits;
         }
@@ -1362,31 +1359,38 @@ static int launch_probe(fastf_engine* e, const u64* cb, const u64* gx, const u32
     return 0;
 }
 
+// The decision stream of a fastf_dev_probe_pack[_wide] call that brings 32-bit draws: K1b reads decisions — one pass over the draws on
+// the caller's stream first, *d_draws then points at the bits (a caller that runs the same stream again and again converts it once
+// with fastf_dev_draw_bits and passes FASTF_PROBE_DRAW_BITS)
+static int draws_to_bits(fastf_engine* e, uint32_t flags, u64 n, const uint32_t** d_draws, u64 n_draws, hipStream_t s) {
+    if (n && n_draws && !*d_draws) return set_err("null d_draws");
+    if ((flags & FASTF_PROBE_DRAW_BITS) || !n || !n_draws) return 0;
+    if (e->d_dbits.ensure(((n_draws + 63) / 64) * 8)) return 1;
+    if (launch_draw_bits(e->threshold, *d_draws, n_draws, (u32*)e->d_dbits.p, s)) return 1;
+    *d_draws = (const uint32_t*)e->d_dbits.p;
+    return 0;
+}
+
 extern "C" int fastf_dev_probe_pack(fastf_engine_t* e, const uint64_t* d_cb_key, const uint64_t* d_gx_key,
                                     const uint32_t* d_umi, const uint32_t* d_meta, uint64_t n,
                                     const uint32_t* d_draws, uint64_t n_draws, const uint64_t* d_draw_base,
                                     uint64_t* d_keys_out, uint64_t shard_stride, uint64_t* d_key_counts,
                                     uint64_t* d_counters, uint32_t flags, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_probe_pack: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     NO_WIDE(e, "fastf_dev_probe_pack");
     const bool seg = (flags & FASTF_PROBE_SEGMENTED) != 0, blocked = (flags & FASTF_PROBE_BLOCKED) != 0;
-    if (seg && !(e->n_shards == 1 && e->use_lds_genes))
+    if (seg && !e->stream_single)
         return set_err("FASTF_PROBE_SEGMENTED needs a single shard and the gene table in LDS (fastf_dev_probe_capacity returns 0 otherwise)");
     if (blocked && !d_gx_key) return set_err("FASTF_PROBE_BLOCKED: d_gx_key must point at the blocked buffer");
-    if (n && n_draws && !d_draws) return set_err("null d_draws");
-    if (!(flags & FASTF_PROBE_DRAW_BITS) && n && n_draws) {
-        // 32-bit draws: K1b reads decisions — one pass over the draws on the caller's stream first (a caller that runs the same
-        // stream again and again converts it once with fastf_dev_draw_bits and passes FASTF_PROBE_DRAW_BITS)
-        if (e->d_dbits.ensure(((n_draws + 63) / 64) * 8)) return 1;
-        if (launch_draw_bits(e->threshold, d_draws, n_draws, (u32*)e->d_dbits.p, (hipStream_t)stream)) return 1;
-        d_draws = (const uint32_t*)e->d_dbits.p;
-    }
-    return launch_probe(e, (const u64*)d_cb_key, blocked ? nullptr : (const u64*)d_gx_key, d_umi, d_meta, n, d_draws, n_draws,
-                        (const u64*)d_draw_base, (u64*)d_keys_out, shard_stride, (u64*)d_key_counts, (u64*)d_counters,
-                        (flags & FASTF_PROBE_REUSE_HITS) != 0, (hipStream_t)stream, ~0ull, nullptr, seg,
-                        blocked ? const_cast<uint64_t*>(d_gx_key) : nullptr);
+    if (draws_to_bits(e, flags, n, &d_draws, n_draws, (hipStream_t)stream)) return 1;
+    ProbeJob j{};
+    j.cb = (const u64*)d_cb_key; j.n = n;
+    if (blocked) j.blk = const_cast<uint64_t*>(d_gx_key);
+    else { j.gx = (const u64*)d_gx_key; j.umi = d_umi; j.meta = d_meta; }
+    j.dbits = d_draws; j.n_draws = n_draws; j.draw_base = (const u64*)d_draw_base;
+    j.keys = (u64*)d_keys_out; j.stride = shard_stride; j.key_counts = (u64*)d_key_counts; j.counters = (u64*)d_counters;
+    j.reuse_hits = (flags & FASTF_PROBE_REUSE_HITS) != 0; j.segmented = seg;
+    return launch_probe(e, j, (hipStream_t)stream);
 } FASTF_CATCH_INT
 
 extern "C" int fastf_engine_is_wide(const fastf_engine_t* e) { return e && !e->multi && e->wide ? 1 : 0; }
@@ -1396,29 +1400,26 @@ extern "C" int fastf_dev_probe_pack_wide(fastf_engine_t* e, const uint64_t* d_cb
                                          const uint32_t* d_draws, uint64_t n_draws, const uint64_t* d_draw_base,
                                          uint64_t* d_keys_out, uint64_t* d_vals_out, uint64_t shard_stride, uint64_t* d_key_counts,
                                          uint64_t* d_counters, uint32_t flags, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_probe_pack_wide: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     if (!e->wide) return set_err("fastf_dev_probe_pack_wide: this engine's keys fit 64 bits (fastf_dev_probe_pack)");
     if (flags & (FASTF_PROBE_SEGMENTED | FASTF_PROBE_BLOCKED)) return set_err("fastf_dev_probe_pack_wide: wide keys take the tile form (no SEGMENTED / BLOCKED)");
     if (!d_keys_out || !d_vals_out) return set_err("null key or value output");
     if (e->long_umi && !d_umi_ext && n) return set_err("this engine was created with umi_max_bases > 16: d_umi_ext (bases 17.. of every UMI, zeros where none) is needed");
     HIP_OK(hipSetDevice(e->device));
-    if (n && n_draws && !d_draws) return set_err("null d_draws");
-    if (!(flags & FASTF_PROBE_DRAW_BITS) && n && n_draws) {
-        if (e->d_dbits.ensure(((n_draws + 63) / 64) * 8)) return 1;
-        if (launch_draw_bits(e->threshold, d_draws, n_draws, (u32*)e->d_dbits.p, (hipStream_t)stream)) return 1;
-        d_draws = (const uint32_t*)e->d_dbits.p;
-    }
-    return launch_probe(e, (const u64*)d_cb_key, (const u64*)d_gx_key, d_umi, d_meta, n, d_draws, n_draws, (const u64*)d_draw_base,
-                        (u64*)d_keys_out, shard_stride, (u64*)d_key_counts, (u64*)d_counters, (flags & FASTF_PROBE_REUSE_HITS) != 0,
-                        (hipStream_t)stream, ~0ull, nullptr, false, nullptr, nullptr, (u64*)d_vals_out, d_umi_ext);
+    if (draws_to_bits(e, flags, n, &d_draws, n_draws, (hipStream_t)stream)) return 1;
+    ProbeJob j{};
+    j.cb = (const u64*)d_cb_key; j.gx = (const u64*)d_gx_key; j.umi = d_umi; j.meta = d_meta; j.n = n;
+    j.dbits = d_draws; j.n_draws = n_draws; j.draw_base = (const u64*)d_draw_base;
+    j.keys = (u64*)d_keys_out; j.stride = shard_stride; j.key_counts = (u64*)d_key_counts; j.counters = (u64*)d_counters;
+    j.reuse_hits = (flags & FASTF_PROBE_REUSE_HITS) != 0;
+    j.wide_vals = (u64*)d_vals_out; j.wide_ext = d_umi_ext;
+    return launch_probe(e, j, (hipStream_t)stream);
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_probe_capacity(const fastf_engine_t* e, uint64_t n, uint64_t* key_slots) FASTF_TRY {
     if (!e || !key_slots) return set_err("null argument");
     *key_slots = 0;
-    if (e->wide) return 0;
-    if (!(e->n_shards == 1 && e->use_lds_genes) || getenv("FASTF_NO_STREAM_K1B")) return 0;
+    if (!e->stream_single || e->stream_off) return 0;
     u32 grid; u64 region;
     stream_geometry(e, (n + K1_TILE - 1) / K1_TILE, &grid, &region);
     *key_slots = (u64)grid * K1S_SUB * region;
@@ -1536,8 +1537,7 @@ static int launch_sort(fastf_engine* e, u64* keys, u64* tmp, const u64* d_n, u64
 
 extern "C" int fastf_dev_set_regions(fastf_engine_t* e, const uint64_t* d_counts, uint32_t n_regions, uint64_t stride,
                                      uint64_t* d_n_out, void* stream) FASTF_TRY {
-    if (!e || !d_counts || !d_n_out) return set_err("null argument");
-    if (e->multi) return set_err("fastf_dev_set_regions: device-level calls take a single-device engine");
+    DEV_SINGLE(!e || !d_counts || !d_n_out, "null argument");
     if (n_regions == 0 || stride == 0) return set_err("fastf_dev_set_regions: no regions");
     HIP_OK(hipSetDevice(e->device));
     if (e->d_segprefix.ensure(((size_t)n_regions + 1) * sizeof(u64))) return 1;
@@ -1549,8 +1549,7 @@ extern "C" int fastf_dev_set_regions(fastf_engine_t* e, const uint64_t* d_counts
 
 extern "C" int fastf_dev_sort(fastf_engine_t* e, uint64_t* d_keys, uint64_t* d_tmp, const uint64_t* d_n,
                               uint64_t max_n, uint32_t key_bits, uint32_t flags, int* sorted_in_tmp, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_sort: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     NO_WIDE(e, "fastf_dev_sort");
     HIP_OK(hipSetDevice(e->device));
     int dummy = 0;
@@ -1647,8 +1646,7 @@ static int launch_reduce(fastf_engine* e, const u64* sorted, const u64* d_n, u64
 extern "C" int fastf_dev_reduce(fastf_engine_t* e, const uint64_t* d_sorted, const uint64_t* d_n, uint64_t max_n,
                                 uint32_t* d_feature, uint32_t* d_cell, uint32_t* d_count, uint64_t* d_nnz, uint32_t flags,
                                 void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_reduce: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     NO_WIDE(e, "fastf_dev_reduce");
     HIP_OK(hipSetDevice(e->device));
     const u32 low = (flags & FASTF_SORT_SKIP_LOW) ? e->skip_bits : 0;
@@ -1660,17 +1658,14 @@ extern "C" int fastf_dev_reduce(fastf_engine_t* e, const uint64_t* d_sorted, con
 
 extern "C" int fastf_dev_rows_gather(fastf_engine_t* e, const uint64_t* d_n, uint32_t* feature, uint32_t* cell, uint32_t* count,
                                      void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_rows_gather: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     if (debug_known_memory(feature, 4, "fastf_dev_rows_gather feature") || debug_known_memory(cell, 4, "fastf_dev_rows_gather cell") || debug_known_memory(count, 4, "fastf_dev_rows_gather count")) return 1;
     return launch_rows_gather<false>(e, (const u64*)d_n, feature, cell, count, nullptr, (hipStream_t)stream);
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_umi_rows(fastf_engine_t* e, const uint64_t* d_sorted, const uint64_t* d_n, uint64_t max_n,
                                   uint64_t* d_ukeys, uint32_t* d_ncopy, uint64_t* d_nrows, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_umi_rows: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     NO_WIDE(e, "fastf_dev_umi_rows");
     HIP_OK(hipSetDevice(e->device));
     return launch_reduce<true>(e, (const u64*)d_sorted, (const u64*)d_n, max_n, nullptr, nullptr, d_ncopy,
@@ -1678,18 +1673,14 @@ extern "C" int fastf_dev_umi_rows(fastf_engine_t* e, const uint64_t* d_sorted, c
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_error_bits(fastf_engine_t* e, uint64_t* bits) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_error_bits: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     HIP_OK(hipDeviceSynchronize());
     if (copy_d2h(bits, (u64*)e->d_small.p + SM_COUNTERS + 3, sizeof(u64))) return 1;
     return 0;
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_clear_error_bits: device-level calls take a single-device engine");
-    HIP_OK(hipSetDevice(e->device));
+    DEV_ENTRY(!e, "null engine");
     // stream-ordered atomicAnd on the device: kernels raise bits with atomicOr, a host read-modify-write would race them
     hipLaunchKernelGGL(clear_bits_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (u64*)e->d_small.p + SM_COUNTERS + 3, (u64)mask);
     HIP_OK(hipGetLastError());
@@ -1974,20 +1965,24 @@ static int push_chunk(fastf_engine* e, const fastf_batch_t* b, size_t off, size_
     HIP_OK(hipEventRecord(sl.ev_copy, sc));
     HIP_OK(hipStreamWaitEvent(sk, sl.ev_copy, 0));
     u64* small = (u64*)e->d_small.p;
+    ProbeJob j{};                                                       // the ring of decisions by absolute hit rank, the store's counters
+    j.cb = (const u64*)ds; j.n = n;
+    j.dbits = (const u32*)e->d_ring.p; j.n_draws = std::min(e->draws_up, e->draws_valid); j.draw_base = small + SM_DRAWBASE;
+    j.draw_mask = e->ring_len - 1; j.d_running = small + SM_RUNNING;
+    j.key_counts = small + SM_KEYCOUNT; j.counters = small + SM_COUNTERS;
     if (e->stream_mode) {
         // K1a writes the cell indices into the runs' scratch slices, the streaming K1b reads the runs and appends this chunk's
         // regions (keys, counts, first-digit histograms) to the store: what bench.py's resident pass runs, chunk by chunk
         const RegionAppend app{e->slots_used, e->rgn_n};
-        if (launch_probe(e, (const u64*)ds, nullptr, nullptr, nullptr, n, (const u32*)e->d_ring.p, std::min(e->draws_up, e->draws_valid),
-                         small + SM_DRAWBASE, (u64*)e->d_keys.p + e->slots_used, s_slots, small + SM_KEYCOUNT, small + SM_COUNTERS, false, sk,
-                         e->ring_len - 1, small + SM_RUNNING, true, blk, &app))
-            return 1;
+        j.blk = blk; j.segmented = true; j.app = &app;
+        j.keys = (u64*)e->d_keys.p + e->slots_used; j.stride = s_slots;
+        if (launch_probe(e, j, sk)) return 1;
         e->slots_used += s_slots; e->rgn_n += s_grid * (u32)K1S_SUB; e->store_regions = true;
-    } else
-    if (launch_probe(e, (const u64*)ds, (const u64*)(ds + o_gx), (const u32*)(ds + o_umi), (const u32*)(ds + o_meta), n,
-                     (const u32*)e->d_ring.p, std::min(e->draws_up, e->draws_valid), small + SM_DRAWBASE, (u64*)e->d_keys.p, e->key_cap,
-                     small + SM_KEYCOUNT, small + SM_COUNTERS, false, sk, e->ring_len - 1, small + SM_RUNNING))
-        return 1;
+    } else {
+        j.gx = (const u64*)(ds + o_gx); j.umi = (const u32*)(ds + o_umi); j.meta = (const u32*)(ds + o_meta);
+        j.keys = (u64*)e->d_keys.p; j.stride = e->key_cap;
+        if (launch_probe(e, j, sk)) return 1;
+    }
     HIP_OK(hipMemcpyAsync(sl.h_small, small, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, sk));
     HIP_OK(hipEventRecord(sl.ev_done, sk));
     sl.busy = true; sl.n = n; sl.external = src.ext != nullptr;
@@ -2485,8 +2480,7 @@ extern "C" int fastf_engine_device_records(const fastf_engine_t* e, uint64_t* re
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_adopt_wide(fastf_engine_t* e, const uint64_t* d_keys, const uint64_t* d_vals, uint64_t n, void* stream) FASTF_TRY {
-    if (!e) return set_err("null engine");
-    if (e->multi) return set_err("fastf_dev_adopt_wide: device-level calls take a single-device engine");
+    DEV_SINGLE(!e, "null engine");
     if (!e->wide) return set_err("fastf_dev_adopt_wide: this engine's keys fit 64 bits");
     if (n && (!d_keys || !d_vals)) return set_err("null keys or values");
     HIP_OK(hipSetDevice(e->device));
