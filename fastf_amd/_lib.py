@@ -111,6 +111,8 @@ ABI_SYMBOLS = [
     "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
     # --genes of sweep and cap
     "fastf_dev_gene_summary", "fastf_sweep_genes_from_coo", "fastf_genes_summary_row", "fastf_sweep_genes_header", "fastf_cap_genes_header",
+    # --cells of sweep and cap
+    "fastf_dev_copy_summary", "fastf_copies_from_umi_rows", "fastf_cells_summary_row", "fastf_sweep_cells_header", "fastf_cap_cells_header",
     # cap
     "fastf_cap", "fastf_cap_parse_caps", "fastf_cap_check_grid", "fastf_cap_point_dir", "fastf_cap_header",
     "fastf_cap_summary_row", "fastf_cap_thresholds", "fastf_cap_realised", "fastf_dev_cell_hits", "fastf_dev_cell_decisions",
@@ -287,6 +289,11 @@ def lib():
     L.fastf_genes_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, u32, C.c_char_p, sz]
     L.fastf_sweep_genes_header.restype = C.c_char_p
     L.fastf_cap_genes_header.restype = C.c_char_p
+    L.fastf_dev_copy_summary.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.fastf_copies_from_umi_rows.argtypes = [C.POINTER(UmiRows), u32, vp, vp, vp, vp]
+    L.fastf_cells_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, vp, u32, vp, C.c_char_p, sz]
+    L.fastf_sweep_cells_header.restype = C.c_char_p
+    L.fastf_cap_cells_header.restype = C.c_char_p
     L.fastf_cap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
     L.fastf_cap_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.fastf_cap_check_grid.argtypes = [fp, u32, vp, u32]

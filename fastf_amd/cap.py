@@ -6,23 +6,28 @@ import os
 import numpy as np
 
 from . import _lib
+from . import sweep as _sweep
 
 SUMMARY_ONLY = 1      # FASTF_CAP_SUMMARY_ONLY
 GENES = 2             # FASTF_CAP_GENES
+CELLS = 8             # FASTF_CAP_CELLS
 COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
 GENES_COLUMNS = ("rate_cell", "reads_per_cell", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
+CELLS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.CELLS_TAIL_COLUMNS
+copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one function for both verbs)
 
 
-def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False):
-    """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes]`; returns the rows of
-    out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
-    out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory"""
+def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False):
+    """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
+    rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
+    out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
+    a cells.tsv.gz per point directory"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0)))
+                                    n.ctypes.data, len(n), seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
@@ -37,6 +42,20 @@ def read_genes_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(GENES_COLUMNS) and lines[-1] == ""
     return [dict(zip(GENES_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def read_cells_table(path):
+    """the rows of cap_cells.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, CELLS_COLUMNS)
+
+
+def cells_header() -> str:
+    return _lib.lib().fastf_cap_cells_header().decode()
+
+
+def cells_summary_row(rate_cell, reads_per_cell, seed, reads, null_reads, single, hist) -> str:
+    """one row of cap_cells.tsv (with its newline)"""
+    return _sweep.cells_summary_row(rate_cell, 0.0, seed, reads, null_reads, single, hist, reads_per_cell=int(reads_per_cell))
 
 
 def genes_header() -> str:

@@ -2,7 +2,7 @@
  * cap_cmds.c — `fastF cap`: every cell downsampled to at most N reads, over a grid of (cell rate, cap) points from ONE decode of
  * the BAM.
  *
- *   cmd_cap()    -b -a -f -o -c <list> -n <list> [-s seed] [--summary-only]; -d accepted and ignored, -u refused
+ *   cmd_cap()    -b -a -f -o -c <list> -n <list> [-s seed] [--summary-only] [--genes] [--cells]; -d accepted and ignored, -u refused
  *   fastf_cap()  the same in process
  * Per point <out>/c<rate_cell>_n<N>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} and one row of <out>/cap.tsv.
  *
@@ -12,6 +12,7 @@
  * (fastf_dev_cell_decisions), then K1b on that plane and everything behind it as in bam2db.  A global depth rate cannot express a
  * cap, so a job outside the resident form is refused: there is no point-by-point fallback.
  * --genes: as in sweep (cap_genes.tsv, cap_gene_cells.tsv.gz, genes.tsv.gz per point; resident.c).
+ * --cells: as in sweep (cap_cells.tsv, cells.tsv.gz per point; fastf_res_point_cells behind every point): the reads each cell kept.
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -123,13 +124,13 @@ static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_op
 /* ------------------------------------------------------------------ */
 static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                          float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                         res_times_t *T)
+                         res_cells_t *C, res_times_t *T)
 {
     int rc = RES_FAIL;
     res_rate_t S;
     void *d_plane = NULL, *d_hits = NULL, *d_thr = NULL;
     uint32_t *h_hits = NULL; uint64_t *h_thr = NULL;
-    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, G->on, T)) != RES_OK) goto done;
+    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
     const uint64_t H = S.H, N = R->n;
     const uint32_t n_cells = S.n_cells;
@@ -175,6 +176,14 @@ static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint
                 fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
             T->genes += fastf_res_now() - tt;
         }
+        if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
+            char crow[1024];
+            if (fastf_res_point_cells(&S, name, T)) goto done;
+            tt = fastf_res_now();
+            if (fastf_cells_summary_row(rate_cell, 0.0f, caps[j], seed, S.h_rpc, S.h_npc, S.h_spc, n_cells, S.h_hist, crow, sizeof crow) ||
+                fastf_res_cells_point(C, &S, summary_only ? NULL : dir, crow)) goto done;
+            T->cells += fastf_res_now() - tt;
+        }
         fputs(row, tsv);
     }
     rc = RES_OK;
@@ -187,7 +196,7 @@ done:
 }
 
 static int cap_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
-                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G)
+                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G, res_cells_t *C)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -203,7 +212,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
     T.decode = fastf_res_now() - tt;
     printf("cap: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n);
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, G, &T);
+        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, G, C, &T);
         if (rc != RES_OK) goto done;
     }
     rc = RES_OK;
@@ -212,6 +221,8 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
                 T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_n), T.summary, T.d2h, T.write, fastf_res_now() - t0);
     if (prof && G->on) fprintf(stderr, "[cap] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
+    if (prof && C->on) fprintf(stderr, "[cap] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
+                               T.cells_dev, T.cells_dev / (n_c * n_n), T.cells);
 done:
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
@@ -227,8 +238,8 @@ int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const 
     if (!bam || !barcodes || !features) return cp_err("cap: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_cap_check_grid(rates_cell, n_c, caps, n_n)) return 1;
-    if (flags & ~(uint32_t)(FASTF_CAP_SUMMARY_ONLY | FASTF_CAP_GENES)) return cp_err("cap: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_CAP_GENES) != 0;
+    if (flags & ~(uint32_t)(FASTF_CAP_SUMMARY_ONLY | FASTF_CAP_GENES | FASTF_CAP_CELLS)) return cp_err("cap: unknown flags 0x%x", flags);
+    const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_CAP_GENES) != 0, cells = (flags & FASTF_CAP_CELLS) != 0;
     if (access(bam, R_OK) == -1) return cp_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1;
     {   const char *dvs = getenv("FASTF_DEVICES");
@@ -240,11 +251,14 @@ int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const 
     if (tsv_open(&tsv, out_dir)) return 1;
     res_genes_t G;
     if (fastf_res_genes_open(&G, genes, "cap", out_dir, fastf_cap_genes_header(), n_c * n_n)) { fastf_res_tsv_close(&tsv, 0); return 1; }
-    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f, &G);
+    res_cells_t C;
+    if (fastf_res_cells_open(&C, cells, "cap", out_dir, fastf_cap_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
+    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f, &G, &C);
     if (rc == RES_NOT_COVERED)
         cp_err("cap: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_set_error_(keep); return 1; }
+    if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_set_error_(keep); return 1; }
     return fastf_res_tsv_close(&tsv, 1);
 }
 
@@ -264,7 +278,8 @@ static void usage_cap(FILE *f)
             "    -o, --out=<str>       path to output directory (default .)\n"
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
             "        --summary-only    write cap.tsv alone\n"
-            "        --genes           per-gene detection too: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point\n");
+            "        --genes           per-gene detection too: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point\n"
+            "        --cells           per-cell reads, saturation and UMI copy numbers too: cap_cells.tsv and cells.tsv.gz per point\n");
 }
 
 #define CAP_MAX_POINTS 64
@@ -283,11 +298,12 @@ int cmd_cap(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0))) {
+    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0))) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
         return 1;
     }
     if (A.genes) printf("cap_genes.tsv and cap_gene_cells.tsv.gz are generated.\n");
+    if (A.per_cell) printf("cap_cells.tsv is generated.\n");
     printf("cap.tsv is generated.\n");
     return 0;
 }

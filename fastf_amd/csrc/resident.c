@@ -150,15 +150,17 @@ void fastf_res_rate_close(res_rate_t *S)
     fastf_devmem_free(S->d_cpg); fastf_devmem_free(S->d_upg);
     if (S->h_cpg) fastf_pinned_free(S->h_cpg);
     if (S->h_upg) fastf_pinned_free(S->h_upg);
+    fastf_devmem_free(S->d_cellsum);
+    if (S->h_hist) fastf_pinned_free(S->h_hist);
     memset(S, 0, sizeof *S);
 }
 
 /* on anything but RES_OK the caller still calls fastf_res_rate_close */
 int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
-                        uint32_t seed, int device, int genes, res_times_t *T)
+                        uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     memset(S, 0, sizeof *S);
-    S->genes = genes; S->n_features = (uint32_t)L->n_features;
+    S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
     S->verb = verb; S->R = R; S->L = L; S->device = device; S->rate_cell = rate_cell; S->seed = seed;
     const uint64_t N = R->n;
     const uint32_t n_cells = S->n_cells = (uint32_t)L->n_cells;
@@ -205,6 +207,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
             return RES_FAIL;
         }
     }
+    if (cells) {                                            /* the histogram and the three per-cell arrays of a point and their pinned host copy, once */
+        const size_t bytes = RES_CELLS_HIST_BYTES + (size_t)n_cells * 12;
+        if (!(S->d_cellsum = fastf_devmem_alloc(device, bytes)) || !(S->h_hist = (uint64_t *)fastf_pinned_alloc(bytes))) {
+            rs_err("%s: the per-cell arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, bytes, fastf_last_error());
+            return RES_FAIL;
+        }
+        S->h_rpc = (uint32_t *)((char *)S->h_hist + RES_CELLS_HIST_BYTES); S->h_npc = S->h_rpc + n_cells; S->h_spc = S->h_npc + n_cells;
+    }
     uint64_t *const sm = (uint64_t *)S->d_small;
     if (fastf_devmem_zero(S->d_small, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
 
@@ -239,14 +249,17 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
     if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
     uint64_t bits = 0;
     if (fastf_dev_error_bits(e, &bits)) return RES_FAIL;
+    S->sorted_full = 0;
     if (bits & FASTF_ERR_RUN_TOO_LONG) {
         /* deep (cell, feature) groups: sort fully and reduce again, as fastf_engine_finish does (every key is still there, permuted) */
         int in_other = 0;
         if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
             fastf_dev_sort(e, src, other, sm + SM_KEYS, N, S->key_bits, 0, &in_other, NULL)) return RES_FAIL;
-        if (in_other) src = other;
+        if (in_other) { uint64_t *t = src; src = other; other = t; }
         if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_REDUCE_SEGMENTED, NULL) || fastf_dev_error_bits(e, &bits)) return RES_FAIL;
+        S->sorted_full = 1;
     }
+    S->sorted = src; S->sorted_other = other;
     if (fastf_devmem_copy(S->h_small, S->d_small, SM_HITS * 8)) return RES_FAIL;
     bits |= S->h_small[SM_CNT + 3];
     if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: bam2db() runs such a file again with wider keys */
@@ -286,6 +299,36 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
     T->d2h += fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_make_dir(dir) || fastf_write_outputs(dir, bam_label, S->rate_cell, rate_depth, counters, S->L, &coo, NULL)) return 1;
     T->write += fastf_res_now() - tt;
+    return 0;
+}
+
+/* --cells: behind the point.  The full sort and K3u use the engine's workspace, and K3u writes the engine's row regions — the count
+ * array and the span tables of the matrix rows — so this runs once fastf_res_point_write has gathered them (resident.h) */
+int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->cells) return 0;
+    const uint64_t N = S->R->n;
+    fastf_engine_t *e = S->e;
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    double tt = fastf_res_now();
+    if (!S->sorted) return rs_err("internal error: no sorted keys at point %s", point_name);
+    uint64_t *src = S->sorted;
+    if (!S->sorted_full) {                                  /* (every key is still there, sorted but for its low bits) */
+        int in_other = 0;
+        if (fastf_dev_sort(e, src, S->sorted_other, sm + SM_KEYS, N, S->key_bits, 0, &in_other, NULL)) return 1;
+        if (in_other) src = S->sorted_other;
+    }
+    S->sorted = NULL;                                       /* (one use: the next point brings its own) */
+    uint64_t *const d_uk = (uint64_t *)S->d_rows; uint32_t *const d_nc = (uint32_t *)(d_uk + N);
+    uint64_t *const d_hist = (uint64_t *)S->d_cellsum;
+    uint32_t *const d_rpc = (uint32_t *)((char *)S->d_cellsum + RES_CELLS_HIST_BYTES), *const d_npc = d_rpc + S->n_cells, *const d_spc = d_npc + S->n_cells;
+    uint64_t bits = 0;
+    if (fastf_dev_umi_rows(e, src, sm + SM_KEYS, N, d_uk, d_nc, sm + SM_UROWS, NULL) ||
+        fastf_dev_copy_summary(e, d_uk, d_nc, sm + SM_UROWS, S->n_cells, d_rpc, d_npc, d_spc, d_hist, NULL) ||
+        fastf_dev_error_bits(e, &bits)) return 1;
+    if (bits) return rs_err("%s: device error bits 0x%llx in the per-cell stage of point %s", S->verb, (unsigned long long)bits, point_name);
+    if (fastf_devmem_copy(S->h_hist, S->d_cellsum, RES_CELLS_HIST_BYTES + (size_t)S->n_cells * 12)) return 1;
+    T->cells_dev += fastf_res_now() - tt;
     return 0;
 }
 
@@ -421,14 +464,59 @@ int fastf_res_genes_close(res_genes_t *G, int ok)
     return rc;
 }
 
+/* ------------------------------------------------------------------ */
+/* --cells: the table, a point's file                                  */
+/* ------------------------------------------------------------------ */
+int fastf_res_cells_open(res_cells_t *C, int on, const char *verb, const char *out_dir, const char *header)
+{
+    memset(C, 0, sizeof *C);
+    if (!on) return 0;
+    char name[64];
+    snprintf(name, sizeof name, "%s_cells.tsv", verb);
+    C->verb = verb;
+    if (fastf_res_tsv_open(&C->tsv, out_dir, name, header)) return 1;
+    C->on = 1;
+    return 0;
+}
+
+int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row)
+{
+    if (!C->on) return 0;
+    if (dir) {
+        char path[4200];
+        gtext t = { NULL, 0, 0 };
+        int bad = gt_str(&t, "barcode\treads\tnull_umi_reads\tumis\tgenes\tsingleton_umis\tsaturation\n");
+        for (uint32_t k = 0; k < S->n_cells && !bad; k++) {
+            const uint64_t reads = S->h_rpc[k], umis = S->h_upc[k];
+            char sat[32];
+            snprintf(sat, sizeof sat, "\t%.6f\n", reads ? 1.0 - (double)umis / (double)reads : 0.0);
+            bad = gt_str(&t, S->L->barcode[k]) || gt_u64(&t, '\t', reads) || gt_u64(&t, '\t', S->h_npc[k]) || gt_u64(&t, '\t', umis) ||
+                  gt_u64(&t, '\t', S->h_gpc[k]) || gt_u64(&t, '\t', S->h_spc[k]) || gt_str(&t, sat);
+        }
+        snprintf(path, sizeof path, "%s/cells.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+        if (bad) return 1;
+    }
+    fputs(row, C->tsv.f);
+    return 0;
+}
+
+int fastf_res_cells_close(res_cells_t *C, int ok)
+{
+    if (!C->on) return 0;
+    C->on = 0;
+    return fastf_res_tsv_close(&C->tsv, ok);
+}
+
 struct ropt { char s; const char *l; int has_arg; };
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *out)
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {0, NULL, 0}};
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0;
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {0, NULL, 0}};
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -442,7 +530,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S' && k->s != 'G') { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S' && k->s != 'G' && k->s != 'C') { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -469,6 +557,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", u_message); return 1;
         case 'S': out->summary_only = 1; break;
         case 'G': out->genes = 1; break;
+        case 'C': out->per_cell = 1; break;
         }
     }
     return 0;

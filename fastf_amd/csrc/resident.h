@@ -1,7 +1,10 @@
 /* resident.h — the resident pipeline `fastF sweep` and `fastF cap` share (resident.c): the packed records of a BAM stay in device
  * memory after ONE decode; per cell rate one engine, the records in its layout and K1a once; per point K1b on that point's
  * decision plane, sort, reduce, the per-cell summary and — when the matrices are wanted — the rows gathered into pinned memory
- * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made. */
+ * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made.
+ * --cells adds a stage of its own behind a point (fastf_res_point_cells): the point's keys sorted fully, K3u's rows, their per-cell
+ * and copy-number summary.  It runs AFTER the point's matrix rows have left the device — K3u writes the engine's row regions
+ * (their count array and the span tables are the ones the matrix rows lie in) and fastf_res_point_write gathers from those. */
 #ifndef FASTF_RESIDENT_H
 #define FASTF_RESIDENT_H
 
@@ -20,9 +23,9 @@ int   fastf_devmem_sync(void);
 
 enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys wider than 64 bits or UMIs beyond what a 64-bit key holds */
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
-enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_WORDS_ = 160 };
+enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_WORDS_ = 192 };   /* SM_UROWS: --cells, K3u's row count */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes; } res_times_t;   /* genes: --genes alone (D2H, rows, files) */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells; } res_times_t;   /* genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files) */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
@@ -53,9 +56,15 @@ typedef struct {
     uint64_t *h_small, *h_upc; uint32_t *h_gpc, *h_rows; uint64_t h_rows_cap;
     int genes; uint32_t n_features;      /* --genes: the per-gene arrays of a point (n_features entries each), else NULL */
     void *d_cpg, *d_upg; uint32_t *h_cpg; uint64_t *h_upg;
+    /* --cells: where fastf_res_point_run left the point's sorted keys (sorted_full: by every bit, the FASTF_ERR_RUN_TOO_LONG branch
+     * ran) and the other buffer of the pair; one device block and its pinned copy, hist[FASTF_COPY_BINS + 1] then the three per-cell
+     * arrays (RES_CELLS_HIST_BYTES, then n_cells u32 each), else NULL */
+    int cells, sorted_full; uint64_t *sorted, *sorted_other;
+    void *d_cellsum; uint64_t *h_hist; uint32_t *h_rpc, *h_npc, *h_spc;
 } res_rate_t;
+#define RES_CELLS_HIST_BYTES 512u
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
-                         uint32_t seed, int device, int genes, res_times_t *T) FASTF_HIDDEN;
+                         uint32_t seed, int device, int genes, int cells, res_times_t *T) FASTF_HIDDEN;
 void fastf_res_rate_close(res_rate_t *S) FASTF_HIDDEN;
 /* one point: K1b on the decision plane (H decisions), sort, reduce, rows gathered on the device, per-cell summary to the host
  * (S->h_upc[0 .. n_cells]: UMIs per cell and their sum, S->h_gpc: genes per cell) and, with S->genes, the per-gene summary on the
@@ -64,6 +73,13 @@ int  fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poi
 /* the rows of the last point into pinned memory, and the three files of bam2db into dir (created) */
 int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz,
                            res_times_t *T) FASTF_HIDDEN;
+
+/* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
+ * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
+ * pinned memory and nothing else reads it before the next point's gather overwrites it — then fastf_dev_copy_summary and the four
+ * arrays to the host (S->h_hist, S->h_rpc, S->h_npc, S->h_spc).  Call it after fastf_res_point_write, or directly after
+ * fastf_res_point_run when no rows are written: K3u overwrites the row regions that call gathers from. */
+int  fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
 /* the summary table of a verb: written as <out_dir>/<name>.partial, renamed to <out_dir>/<name> by a close with ok != 0; otherwise
  * nothing of it is left */
@@ -87,10 +103,19 @@ int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *po
                           const uint32_t *cells, const uint64_t *umis) FASTF_HIDDEN;
 int fastf_res_genes_close(res_genes_t *G, int ok) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes and ONE list option of the verb's own (list_short /
+/* --cells of a verb: <out_dir>/<verb>_cells.tsv (one row per point, through .partial) and <point dir>/cells.tsv.gz.  on == 0: every
+ * call does nothing */
+typedef struct { int on; const char *verb; res_tsv_t tsv; } res_cells_t;
+int fastf_res_cells_open(res_cells_t *C, int on, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
+/* one point, after fastf_res_point_cells: `row` (fastf_cells_summary_row) into the table and — dir != NULL — dir/cells.tsv.gz from the
+ * arrays of S (h_rpc, h_npc, h_upc, h_gpc, h_spc) and the barcodes of its lists */
+int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row) FASTF_HIDDEN;
+int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
+
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells and ONE list option of the verb's own (list_short /
  * list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists). */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes; } res_args_t;
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;
 int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;

@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed] [--summary-only]; -d accepted and ignored, -u refused
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed] [--summary-only] [--genes] [--cells]; -d accepted and ignored, -u refused
  *   fastf_sweep()  the same in process
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
  * writes for that point — and one row of <out>/sweep.tsv.
@@ -14,6 +14,9 @@
  * through bam2db() itself, the summary then read back from each point's matrix.
  * --genes: per point the rows reduced along the gene axis too (fastf_dev_gene_summary; point by point fastf_sweep_genes_from_coo)
  * into sweep_genes.tsv, sweep_gene_cells.tsv.gz and the point's genes.tsv.gz (resident.c).
+ * --cells: behind every point its keys sorted fully, K3u's rows and their reduction along the cell axis and into the copy-number
+ * histogram (fastf_res_point_cells: fastf_dev_umi_rows, fastf_dev_copy_summary) into sweep_cells.tsv and the point's cells.tsv.gz;
+ * resident form only — a job outside it is refused with the flag.
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -213,6 +216,65 @@ int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
 }
 
 /* ------------------------------------------------------------------ */
+/* --cells: the host twin, the row                                     */
+/* ------------------------------------------------------------------ */
+/* the host form of fastf_dev_copy_summary, by its rules (tests; a reader of umi.tsv.gz) */
+int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, uint32_t *reads, uint32_t *null_reads, uint32_t *single, uint64_t *hist)
+{
+    if (!rows || !reads || !null_reads || !single || !hist || (rows->n && (!rows->cell || !rows->n_copy || !rows->nonnull))) return sw_err("null argument");
+    memset(reads, 0, (size_t)n_cells * sizeof *reads);
+    memset(null_reads, 0, (size_t)n_cells * sizeof *null_reads);
+    memset(single, 0, (size_t)n_cells * sizeof *single);
+    memset(hist, 0, (FASTF_COPY_BINS + 1) * sizeof *hist);
+    for (size_t i = 0; i < rows->n; i++) {
+        const uint32_t c = rows->cell[i] - 1u, k = rows->n_copy[i];
+        const int nn = rows->nonnull[i] != 0;
+        if (nn && k) {
+            hist[(k < FASTF_COPY_BINS ? k : FASTF_COPY_BINS) - 1u]++;
+            if (k >= FASTF_COPY_BINS) hist[FASTF_COPY_BINS] += k;
+        }
+        if (c >= n_cells) continue;
+        reads[c] += k;
+        if (!nn) null_reads[c] += k;
+        else single[c] += k == 1;
+    }
+    return 0;
+}
+
+#define CELLS_COLUMNS_TAIL "seed\tvalid_reads\tnull_umi_reads\tumis\tsingleton_umis\tmedian_reads_per_cell\t" \
+    "copies_1\tcopies_2\tcopies_3\tcopies_4\tcopies_5\tcopies_6\tcopies_7\tcopies_8\tcopies_9\tcopies_10\tcopies_11\tcopies_12\tcopies_13\t" \
+    "copies_14\tcopies_15\tcopies_16\tcopies_17\tcopies_18\tcopies_19\tcopies_20\tcopies_21\tcopies_22\tcopies_23\tcopies_24\tcopies_25\t" \
+    "copies_26\tcopies_27\tcopies_28\tcopies_29\tcopies_30\tcopies_31\tcopies_32_plus\treads_copies_32_plus\n"
+const char *fastf_sweep_cells_header(void) { return "rate_cell\trate_depth\t" CELLS_COLUMNS_TAIL; }
+const char *fastf_cap_cells_header(void) { return "rate_cell\treads_per_cell\t" CELLS_COLUMNS_TAIL; }
+
+/* one row of sweep_cells.tsv (reads_per_cell == 0) or cap_cells.tsv (reads_per_cell >= 1), with its newline */
+int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *reads,
+                            const uint32_t *null_reads, const uint32_t *single, uint32_t n_cells, const uint64_t *hist, char *buf, size_t cap)
+{
+    if (!buf || !hist || (n_cells && (!reads || !null_reads || !single))) return sw_err("null argument");
+    uint64_t *tmp = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *tmp);
+    if (!tmp) return sw_err("out of memory");
+    uint64_t valid = 0, nulls = 0, singles = 0, umis = 0;
+    for (uint32_t k = 0; k < n_cells; k++) { tmp[k] = reads[k]; valid += reads[k]; nulls += null_reads[k]; singles += single[k]; }
+    const double med = median_u64(tmp, n_cells);
+    free(tmp);
+    for (uint32_t k = 0; k < FASTF_COPY_BINS; k++) umis += hist[k];
+    char second[32];
+    if (reads_per_cell) snprintf(second, sizeof second, "%llu", (unsigned long long)reads_per_cell);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%llu\t%llu\t%llu\t%llu\t%.1f", (double)rate_cell, second, seed, (unsigned long long)valid,
+                     (unsigned long long)nulls, (unsigned long long)umis, (unsigned long long)singles, med);
+    for (uint32_t k = 0; k <= FASTF_COPY_BINS && n >= 0 && (size_t)n < cap; k++) {
+        const int m = snprintf(buf + n, cap - (size_t)n, "\t%llu", (unsigned long long)hist[k]);
+        n = m < 0 ? -1 : n + m;
+    }
+    if (n < 0 || (size_t)n + 1 >= cap) return sw_err("summary row too long");
+    buf[n] = '\n'; buf[n + 1] = '\0';
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -322,14 +384,14 @@ done:
 /* one cell rate: the engine, the records in its layout, K1a, the planes, then every depth rate */
 static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           res_genes_t *G, res_times_t *T)
+                           res_genes_t *G, res_cells_t *C, res_times_t *T)
 {
     int rc = RES_FAIL;
     res_rate_t S;
     void *d_planes = NULL;
     uint64_t *thr = (uint64_t *)malloc(n_r * sizeof *thr);
     if (!thr) { sw_err("out of memory"); memset(&S, 0, sizeof S); goto done; }
-    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, T)) != RES_OK) goto done;
+    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
     const uint64_t H = S.H;
     double tt = fastf_res_now();
@@ -361,6 +423,14 @@ static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const ui
                 fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
             T->genes += fastf_res_now() - tt;
         }
+        if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
+            char crow[1024];
+            if (fastf_res_point_cells(&S, name, T)) goto done;
+            tt = fastf_res_now();
+            if (fastf_cells_summary_row(rate_cell, rd_list[j], 0, seed, S.h_rpc, S.h_npc, S.h_spc, S.n_cells, S.h_hist, crow, sizeof crow) ||
+                fastf_res_cells_point(C, &S, summary_only ? NULL : dir, crow)) goto done;
+            T->cells += fastf_res_now() - tt;
+        }
         fputs(row, tsv);
     }
     rc = RES_OK;
@@ -373,7 +443,7 @@ done:
 
 static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
                           const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                          res_genes_t *G)
+                          res_genes_t *G, res_cells_t *C)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -390,7 +460,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
 
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, G, &T);
+        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, G, C, &T);
         if (rc != RES_OK) goto done;
     }
     rc = RES_OK;
@@ -399,6 +469,8 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
                 T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r), T.summary, T.d2h, T.write, fastf_res_now() - t0);
     if (prof && G->on) fprintf(stderr, "[sweep] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
+    if (prof && C->on) fprintf(stderr, "[sweep] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
+                               T.cells_dev, T.cells_dev / (n_c * n_r), T.cells);
 done:
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
@@ -414,20 +486,29 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES)) return sw_err("sweep: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0;
+    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS)) return sw_err("sweep: unknown flags 0x%x", flags);
+    const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0, cells = (flags & FASTF_SWEEP_CELLS) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
+    int dev0 = 0, dev_second = -1, several = 0;
+    {   const char *dvs = getenv("FASTF_DEVICES");
+        fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
+        several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
+    if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
     if (fastf_res_make_dir(out_dir)) return 1;
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
     res_genes_t G;
     if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+    res_cells_t C;
+    if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
 
-    int dev0 = 0, dev_second = -1, several = 0;
-    {   const char *dvs = getenv("FASTF_DEVICES");
-        fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
-        several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
-    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f, &G);
+    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f, &G, &C);
+    if (rc == RES_NOT_COVERED && cells) {
+        /* (the per-cell rows come from the device's keys alone: bam2db() point by point has none.  Wide keys and a UMI length set
+         * beyond the key are known before the first point; a UMI found too long among the records stops the point that meets it) */
+        sw_err("sweep: --cells needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
     if (rc == RES_NOT_COVERED) {
         fprintf(stderr, "sweep: this job is outside the resident form (%s): running bam2db point by point\n",
                 several ? "several devices" : "keys wider than 64 bits or UMIs beyond what a 64-bit key holds");
@@ -439,7 +520,8 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
         rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, &tsv, &G);
     }
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_set_error_(keep); return 1; }
+    if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
+    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_set_error_(keep); return 1; }
     return fastf_res_tsv_close(&tsv, 1);
 }
 
@@ -459,7 +541,8 @@ static void usage_sweep(FILE *f)
             "    -o, --out=<str>       path to output directory (default .)\n"
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
             "        --summary-only    write sweep.tsv alone\n"
-            "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n");
+            "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n"
+            "        --cells           per-cell reads, saturation and UMI copy numbers too: sweep_cells.tsv and cells.tsv.gz per point\n");
 }
 
 #define SWEEP_MAX_RATES 64
@@ -477,11 +560,12 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0))) {
+    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0))) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
     }
     if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
+    if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;
 }

@@ -8,6 +8,7 @@
 #include "sweep_kernels.hpp"
 #include "cap_kernels.hpp"
 #include "gene_kernels.hpp"
+#include "cells_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -1137,6 +1138,30 @@ extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_featu
     return 0;
 } FASTF_CATCH_INT
 
+// --cells: the -u rows of fastf_dev_umi_rows on this engine reduced along the cell axis and into the copy-number histogram
+// (copy_summary_kernel).  The cell field and the non-NULL flag are read from the engine's own key layout.  All four outputs are
+// cleared here first; *d_nrows rows are read.  Every per-cell number is below 2^32 (a number of records).
+static_assert(COPY_BINS == FASTF_COPY_BINS, "the histogram of copy_summary_kernel and the ABI's");
+extern "C" int fastf_dev_copy_summary(fastf_engine_t* e, const uint64_t* d_ukeys, const uint32_t* d_ncopy, const uint64_t* d_nrows, uint32_t n_cells,
+                                      uint32_t* d_reads_per_cell, uint32_t* d_null_reads_per_cell, uint32_t* d_single_per_cell, uint64_t* d_hist,
+                                      void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_ukeys || !d_ncopy || !d_nrows || !d_reads_per_cell || !d_null_reads_per_cell || !d_single_per_cell || !d_hist, "null argument");
+    NO_WIDE(e, "fastf_dev_copy_summary");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_cells) {
+        HIP_OK(hipMemsetAsync(d_reads_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
+        HIP_OK(hipMemsetAsync(d_null_reads_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
+        HIP_OK(hipMemsetAsync(d_single_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
+    }
+    HIP_OK(hipMemsetAsync(d_hist, 0, ((size_t)COPY_BINS + 1) * sizeof(u64), s));
+    const CopyOut out{d_reads_per_cell, d_null_reads_per_cell, d_single_per_cell};
+    hipLaunchKernelGGL(copy_summary_kernel, dim3(2 * g_cu_count), dim3(256), 0, s, (const u64*)d_ukeys, d_ncopy, (const u64*)d_nrows, n_cells,
+                       e->L.cell_shift, e->L.umi_bits + e->L.len_bits, out, (u64*)d_hist);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "copy summary");
+    return 0;
+} FASTF_CATCH_INT
+
 // cap: hits per cell from the cell scratch K1a left (cell_hits_kernel).  Valid right after fastf_dev_count_hits[_blocked] over the
 // same n records on the same stream (the FASTF_PROBE_REUSE_HITS contract); d_blocked: the blocked buffer of that call, or
 // nullptr for the SoA scratch.  d_hits_per_cell[c - 1] (u32, n_cells entries) is cleared here first.
@@ -1690,7 +1715,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

@@ -387,6 +387,15 @@ class Engine:
         The sum of all counts is below 2^32"""
         check(self._L.fastf_dev_gene_summary(self._h, d_feature, d_count, d_nnz, n_features, d_cells_per_gene, d_umis_per_gene, stream))
 
+    def dev_copy_summary(self, d_ukeys, d_ncopy, d_nrows, n_cells, d_reads_per_cell, d_null_reads_per_cell, d_single_per_cell, d_hist, stream=0):
+        """the rows of dev_umi_rows on this engine -> per cell (slot c - 1, u32, n_cells entries each) the sum of n_copy over all its
+        rows, that sum over its NULL-blob rows and its non-NULL rows with n_copy == 1; d_hist (u64, COPY_BINS + 1 entries): the
+        non-NULL rows with n_copy == k at k - 1, those with n_copy >= COPY_BINS at COPY_BINS - 1, the reads of those behind it.  All
+        cleared by the call; the cell and the NULL flag come from the engine's key layout; a cell outside 1 .. n_cells adds nothing
+        to the per-cell arrays.  Every per-cell number is below 2^32"""
+        check(self._L.fastf_dev_copy_summary(self._h, d_ukeys, d_ncopy, d_nrows, n_cells, d_reads_per_cell, d_null_reads_per_cell,
+                                             d_single_per_cell, d_hist, stream))
+
     def dev_cell_hits(self, n, d_blocked, d_hits_per_cell, stream=0):
         """d_hits_per_cell[c - 1] (u32, n_cells entries, cleared by the call) = records of the last dev_count_hits[_blocked] over
         these n records whose cell index is c; d_blocked: that call's blocked buffer, or 0 / None for the SoA scratch"""

@@ -6,13 +6,19 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Coo
+from ._lib import Coo, UmiRows
 
 SUMMARY_ONLY = 1      # FASTF_SWEEP_SUMMARY_ONLY
 GENES = 2             # FASTF_SWEEP_GENES
+CELLS = 8             # FASTF_SWEEP_CELLS
+COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
 GENES_COLUMNS = ("rate_cell", "rate_depth", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
+CELLS_TAIL_COLUMNS = (("seed", "valid_reads", "null_umi_reads", "umis", "singleton_umis", "median_reads_per_cell")
+                      + tuple("copies_%d" % k for k in range(1, COPY_BINS)) + ("copies_%d_plus" % COPY_BINS, "reads_copies_%d_plus" % COPY_BINS))
+CELLS_COLUMNS = ("rate_cell", "rate_depth") + CELLS_TAIL_COLUMNS
+POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
 def _floats(v):
@@ -20,15 +26,17 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False):
-    """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes]`; returns
-    the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv (read_genes_table),
-    out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory"""
+def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
+          cells: bool = False):
+    """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
+    returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
+    (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
+    out/sweep_cells.tsv (read_cells_table) and a cells.tsv.gz per point directory"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0)))
+                                      seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -43,6 +51,46 @@ def read_genes_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(GENES_COLUMNS) and lines[-1] == ""
     return [dict(zip(GENES_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def read_cells_table(path, columns=CELLS_COLUMNS):
+    """the rows of sweep_cells.tsv as dicts of strings"""
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(columns) and lines[-1] == ""
+    return [dict(zip(columns, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def cells_header() -> str:
+    return _lib.lib().fastf_sweep_cells_header().decode()
+
+
+def copies_from_umi_rows(cell, n_copy, nonnull, n_cells: int):
+    """(reads per cell, NULL-UMI reads per cell, singleton UMIs per cell — u32[n_cells] each — and hist u64[COPY_BINS + 1]) of -u
+    rows: the host form of Engine.dev_copy_summary"""
+    c = np.ascontiguousarray(cell, dtype=np.uint32)
+    k = np.ascontiguousarray(n_copy, dtype=np.uint32)
+    nn = np.ascontiguousarray(nonnull, dtype=np.uint8)
+    assert len(c) == len(k) == len(nn)
+    z = np.zeros(len(c), dtype=np.uint32)
+    p32 = C.POINTER(C.c_uint32)
+    rows = UmiRows(z.ctypes.data_as(p32), c.ctypes.data_as(p32), k.ctypes.data_as(p32), z.ctypes.data_as(p32), nn.ctypes.data_as(C.POINTER(C.c_uint8)), len(c))
+    r, nr, sg = (np.zeros(max(n_cells, 1), np.uint32) for _ in range(3))
+    hist = np.zeros(COPY_BINS + 1, np.uint64)
+    _lib.check(_lib.lib().fastf_copies_from_umi_rows(C.byref(rows), n_cells, r.ctypes.data, nr.ctypes.data, sg.ctypes.data, hist.ctypes.data))
+    return r[:n_cells], nr[:n_cells], sg[:n_cells], hist
+
+
+def cells_summary_row(rate_cell, rate_depth, seed, reads, null_reads, single, hist, reads_per_cell: int = 0) -> str:
+    """one row of sweep_cells.tsv (with its newline); reads_per_cell >= 1: a row of cap_cells.tsv"""
+    r = np.ascontiguousarray(reads, dtype=np.uint32)
+    nr = np.ascontiguousarray(null_reads, dtype=np.uint32)
+    sg = np.ascontiguousarray(single, dtype=np.uint32)
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    assert len(r) == len(nr) == len(sg) and len(h) == COPY_BINS + 1
+    buf = C.create_string_buffer(1024)
+    _lib.check(_lib.lib().fastf_cells_summary_row(float(rate_cell), float(rate_depth), int(reads_per_cell), seed, r.ctypes.data, nr.ctypes.data,
+                                                  sg.ctypes.data, len(r), h.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
 
 
 def parse_rates(text: str, cell_rates: bool = False):

@@ -116,9 +116,10 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
+#define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags);
 /* the host pieces of it: a comma-separated list of rates (strtof per element; empty elements, trailing characters, NaN and negative
@@ -144,6 +145,29 @@ const char *fastf_cap_genes_header(void);
  * and reads_per_cell >= 1 prints that integer — a cap row */
 int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *cells_per_gene,
                             const uint64_t *umis_per_gene, uint32_t n_features, char *buf, size_t cap);
+/* --cells (FASTF_SWEEP_CELLS, FASTF_CAP_CELLS): how deeply every cell was sequenced at a point, and the copy-number histogram of its
+ * UMIs.  A point's keys — one per sampled_valid read — sorted fully and run-length encoded (fastf_dev_umi_rows) give one row per
+ * distinct (cell, feature, blob) with its run length n_copy; a row whose blob is NULL is a NULL row.  For a point, reads[c - 1] =
+ * the sum of n_copy over all rows of cell c (its sampled_valid reads), null_reads[c - 1] = that sum over its NULL rows, single[c - 1]
+ * = its non-NULL rows with n_copy == 1, and hist[] (FASTF_COPY_BINS + 1 entries, below) counts the non-NULL rows by n_copy.
+ *   <out_dir>/sweep_cells.tsv (cap_cells.tsv): a header and one row per point in sweep.tsv's order, all integers but the rates:
+ *     rate_cell rate_depth|reads_per_cell seed valid_reads null_umi_reads umis singleton_umis median_reads_per_cell
+ *     copies_1 .. copies_31 copies_32_plus reads_copies_32_plus
+ *     (valid_reads = the sum of reads[], umis = the non-NULL rows = the sum of copies_*, the median over all sampled cells by the
+ *     rule of sweep.tsv's medians, printed %.1f; sum of k * copies_k (k < 32) + reads_copies_32_plus + null_umi_reads = valid_reads);
+ *     written as .partial and renamed, with --summary-only too
+ *   <point dir>/cells.tsv.gz (not with --summary-only): a header and one row per sampled cell in barcodes.tsv.gz's order:
+ *     barcode reads null_umi_reads umis genes singleton_umis saturation
+ *     (barcode = that file's line; umis, genes = the per-cell numbers behind sweep.tsv's medians; saturation = 1 - umis / reads
+ *     printed %.6f, 0.000000 when reads == 0)
+ * Every other output is the bytes it is without the flag.  A job outside the resident form (keys wider than 64 bits, UMIs beyond
+ * what a 64-bit key holds, several devices) is refused with the flag: sweep's point-by-point path has no such rows. */
+#define FASTF_COPY_BINS 32u
+const char *fastf_sweep_cells_header(void);
+const char *fastf_cap_cells_header(void);
+/* one row of either table (with its newline): the second column as fastf_genes_summary_row prints it; hist: FASTF_COPY_BINS + 1 */
+int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *reads,
+                            const uint32_t *null_reads, const uint32_t *single, uint32_t n_cells, const uint64_t *hist, char *buf, size_t cap);
 
 /* --- cap: every cell downsampled to at most N reads (cap_cmds.c; not a command of the reference).  For one point (cell rate c,
  * cap N >= 1, seed s): the cells are sampled as `bam2db -c c -s s` samples them; h[k] = records whose CB is sampled cell k (counted
@@ -156,9 +180,10 @@ int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
+#define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
 int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
               const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags);
 /* the host pieces of it: a comma-separated list of caps (decimal integers >= 1; empty elements, signs, trailing characters and
@@ -302,6 +327,11 @@ int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, co
 /* --genes (section 1): per gene (1-based feature g -> slot g - 1) the rows with count >= 1 and the sum of the counts of a COO in any
  * order — the host form of fastf_dev_gene_summary; a row whose feature is outside 1 .. n_features adds nothing, as there */
 int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint32_t *cells_per_gene, uint64_t *umis_per_gene);
+
+/* --cells (section 1): reads[], null_reads[], single[] (n_cells entries each) and hist[FASTF_COPY_BINS + 1] of -u rows — the host
+ * form of fastf_dev_copy_summary, by the same rules: a row with nonnull[i] == 0 is a NULL row, a row whose cell is outside
+ * 1 .. n_cells adds nothing to the per-cell arrays, a row with n_copy == 0 is in no bin */
+int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, uint32_t *reads, uint32_t *null_reads, uint32_t *single, uint64_t *hist);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -479,6 +509,18 @@ int fastf_dev_cell_summary(fastf_engine_t *e, const uint32_t *d_cell, const uint
  * counter in LDS (FASTF_GENE_LDS_RANGES=0: global atomics always).  d_feature / d_count may be NULL when there are no rows. */
 int fastf_dev_gene_summary(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_count, const uint64_t *d_nnz,
                            uint32_t n_features, uint32_t *d_cells_per_gene, uint64_t *d_umis_per_gene, void *stream);
+/* Per-cell reads and the copy-number histogram of -u rows: the output of fastf_dev_umi_rows on this engine — *d_nrows rows of
+ * d_ukeys (ascending, so the rows of one cell are neighbours) and d_ncopy.  The cell of a row and whether its blob is NULL are read
+ * from the engine's own key layout.  d_reads_per_cell[c - 1] = the sum of n_copy over all rows of cell c (NULL rows included),
+ * d_null_reads_per_cell[c - 1] = that sum over its NULL rows, d_single_per_cell[c - 1] = its non-NULL rows with n_copy == 1: n_cells
+ * entries each (u32).  d_hist[k - 1], k = 1 .. FASTF_COPY_BINS - 1, = the non-NULL rows with n_copy == k, d_hist[FASTF_COPY_BINS - 1] =
+ * those with n_copy >= FASTF_COPY_BINS, d_hist[FASTF_COPY_BINS] = the sum of n_copy over those tail rows: with it the histogram accounts
+ * for every read.  All four arrays are cleared by the call, nothing behind them is written.  A row whose cell is outside 1 .. n_cells
+ * adds nothing to the per-cell arrays (it is counted in d_hist).  Every per-cell number is below 2^32: it is a number of records,
+ * and the device-level calls stop at 2^32 - 2 records.  Refused: NULL arguments, an engine whose keys are wider than 64 bits. */
+int fastf_dev_copy_summary(fastf_engine_t *e, const uint64_t *d_ukeys, const uint32_t *d_ncopy, const uint64_t *d_nrows,
+                           uint32_t n_cells, uint32_t *d_reads_per_cell, uint32_t *d_null_reads_per_cell, uint32_t *d_single_per_cell,
+                           uint64_t *d_hist, void *stream);
 
 /* cap (section 1) on the device.  fastf_dev_cell_hits: d_hits_per_cell[c - 1] (u32, the engine's n_cells entries, cleared by the call)
  * = records whose cell index in K1a's scratch is c.  Valid right after fastf_dev_count_hits (d_blocked NULL: the SoA scratch) or
