@@ -116,6 +116,10 @@ ABI_SYMBOLS = [
     # cap
     "fastf_cap", "fastf_cap_parse_caps", "fastf_cap_check_grid", "fastf_cap_point_dir", "fastf_cap_header",
     "fastf_cap_summary_row", "fastf_cap_thresholds", "fastf_cap_realised", "fastf_dev_cell_hits", "fastf_dev_cell_decisions",
+    # replicate seeds of sweep and cap
+    "fastf_parse_seeds", "fastf_reps_seeds", "fastf_sweep_reps", "fastf_cap_reps", "fastf_reps_point_dir", "fastf_sweep_reps_header",
+    "fastf_cap_reps_header", "fastf_sweep_genes_reps_header", "fastf_cap_genes_reps_header", "fastf_reps_summary_row", "fastf_genes_reps_row",
+    "fastf_gene_reps_add_host", "fastf_dev_gene_reps_add", "fastf_dev_block_layout",
 ]
 
 
@@ -305,6 +309,18 @@ def lib():
     L.fastf_cap_realised.restype = C.c_float
     L.fastf_dev_cell_hits.argtypes = [vp, u64, vp, vp, vp]
     L.fastf_dev_cell_decisions.argtypes = [vp, u64, vp, u32, u64, u64, vp, vp, vp]
+    L.fastf_parse_seeds.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
+    L.fastf_reps_seeds.argtypes = [u32, u64, vp, u32, C.POINTER(u32)]
+    L.fastf_sweep_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32]
+    L.fastf_cap_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32]
+    L.fastf_reps_point_dir.argtypes = [C.c_char_p, u32, C.c_char_p, sz]
+    for name in ("fastf_sweep_reps_header", "fastf_cap_reps_header", "fastf_sweep_genes_reps_header", "fastf_cap_genes_reps_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_reps_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, u32, C.c_char_p, sz]
+    L.fastf_genes_reps_row.argtypes = [C.c_float, C.c_float, u64, vp, u32, vp, u32, C.c_char_p, sz]
+    L.fastf_gene_reps_add_host.argtypes = [vp, u32, vp, vp, vp]
+    L.fastf_dev_gene_reps_add.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.fastf_dev_block_layout.argtypes = [vp, u64, C.POINTER(u64)]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

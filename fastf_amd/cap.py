@@ -31,6 +31,48 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
+def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False):
+    """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
+    per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
+    out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    n = np.ascontiguousarray(caps, dtype=np.uint64)
+    sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_cap_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                         n.ctypes.data, len(n), sd.ctypes.data, len(sd),
+                                         (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+    return read_table(os.path.join(os.fspath(out), "cap.tsv"))
+
+
+REPS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.REPS_TAIL_COLUMNS
+GENES_REPS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.GENES_REPS_TAIL_COLUMNS
+parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for both verbs)
+
+
+def read_reps_table(path):
+    """the rows of cap_reps.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, REPS_COLUMNS)
+
+
+def read_genes_reps_table(path):
+    """the rows of cap_genes_reps.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, GENES_REPS_COLUMNS)
+
+
+def reps_header() -> str:
+    return _lib.lib().fastf_cap_reps_header().decode()
+
+
+def genes_reps_header() -> str:
+    return _lib.lib().fastf_cap_genes_reps_header().decode()
+
+
+def reps_summary_row(rate_cell, reads_per_cell, n_cells, metrics) -> str:
+    """one row of cap_reps.tsv (with its newline)"""
+    return _sweep.reps_summary_row(rate_cell, 0.0, n_cells, metrics, reads_per_cell=int(reads_per_cell))
+
+
 def read_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""

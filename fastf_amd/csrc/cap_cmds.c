@@ -2,8 +2,9 @@
  * cap_cmds.c — `fastF cap`: every cell downsampled to at most N reads, over a grid of (cell rate, cap) points from ONE decode of
  * the BAM.
  *
- *   cmd_cap()    -b -a -f -o -c <list> -n <list> [-s seed] [--summary-only] [--genes] [--cells]; -d accepted and ignored, -u refused
- *   fastf_cap()  the same in process
+ *   cmd_cap()    -b -a -f -o -c <list> -n <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells]; -d accepted and
+ *                ignored, -u refused
+ *   fastf_cap()  the same in process; fastf_cap_reps(): with a list of seeds, as sweep takes them (sweep_cmds.c)
  * Per point <out>/c<rate_cell>_n<N>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} and one row of <out>/cap.tsv.
  *
  * The resident pipeline of sweep (resident.c).  Per cell rate K1a once, the hits per cell counted on the device
@@ -103,12 +104,22 @@ const char *fastf_cap_header(void)
            "median_umis_per_cell\tmedian_genes_per_cell\thits\tcells_capped\trealised_depth\n";
 }
 
+static int cap_row_(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                    const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
+                    char *buf, size_t cap, double *metrics);
 int fastf_cap_summary_row(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                           const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
                           char *buf, size_t cap)
 {
+    return cap_row_(rate_cell, reads_per_cell, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, hits, cells_capped, buf, cap, NULL);
+}
+/* metrics: fastf_summary_tail_ */
+static int cap_row_(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                    const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
+                    char *buf, size_t cap, double *metrics)
+{
     char tail[400];
-    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail)) return 1;
+    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail, metrics)) return 1;
     const int n = snprintf(buf, cap, "%.3f\t%llu\t%s\t%llu\t%u\t%.6f\n", (double)rate_cell, (unsigned long long)reads_per_cell, tail,
                            (unsigned long long)hits, cells_capped, (double)fastf_cap_realised(counters[1], hits));
     return (n < 0 || (size_t)n >= cap) ? cp_err("summary row too long") : 0;
@@ -120,20 +131,19 @@ int fastf_cap_summary_row(float rate_cell, uint64_t reads_per_cell, uint32_t see
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "cap.tsv", fastf_cap_header()); }
 
 /* ------------------------------------------------------------------ */
-/* one cell rate                                                       */
+/* one (cell rate, seed) pair, on the run's res_rate_t               */
 /* ------------------------------------------------------------------ */
-static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
+static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                          float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                         res_cells_t *C, res_times_t *T)
+                         res_cells_t *C, res_reps_t *P, uint32_t k_seed, res_times_t *T)
 {
     int rc = RES_FAIL;
-    res_rate_t S;
     void *d_plane = NULL, *d_hits = NULL, *d_thr = NULL;
     uint32_t *h_hits = NULL; uint64_t *h_thr = NULL;
-    if ((rc = fastf_res_rate_open(&S, "cap", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
+    if ((rc = fastf_res_rate_open(S, "cap", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
-    const uint64_t H = S.H, N = R->n;
-    const uint32_t n_cells = S.n_cells;
+    const uint64_t H = S->H, N = R->n;
+    const uint32_t n_cells = S->n_cells;
     double tt = fastf_res_now();
 
     /* the hits per cell, counted where K1a left the cell indices; to the host once, through pinned memory */
@@ -142,7 +152,7 @@ static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint
     if (!(d_hits = fastf_devmem_alloc(device, nc1 * 4)) || !(d_thr = fastf_devmem_alloc(device, nc1 * 8)) ||
         !(h_hits = (uint32_t *)fastf_pinned_alloc(nc1 * 4)) || !(h_thr = (uint64_t *)fastf_pinned_alloc(nc1 * 8)) ||
         !(d_plane = fastf_devmem_alloc(device, (size_t)plane_words * 4)) || fastf_devmem_zero(d_plane, (size_t)plane_words * 4)) goto done;
-    if (fastf_dev_cell_hits(S.e, N, S.blocked ? S.d_blk : NULL, (uint32_t *)d_hits, NULL) || fastf_devmem_sync() ||
+    if (fastf_dev_cell_hits(S->e, N, S->blocked ? S->d_blk : NULL, (uint32_t *)d_hits, NULL) || fastf_devmem_sync() ||
         fastf_devmem_copy(h_hits, d_hits, (size_t)n_cells * 4)) goto done;
     {   uint64_t sum = 0;
         for (uint32_t k = 0; k < n_cells; k++) sum += h_hits[k];
@@ -150,45 +160,52 @@ static int cap_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint
     T->planes += fastf_res_now() - tt;
 
     for (uint32_t j = 0; j < n_n; j++) {
-        char name[64], dir[4096], row[640];
+        char base[64], name[96], dir[4096], row[640];
         uint64_t counters[3], nnz = 0;
         uint32_t capped = 0;
-        if (fastf_cap_point_dir(rate_cell, caps[j], name, sizeof name)) goto done;
+        double metrics[FASTF_REPS_METRICS];
+        if (fastf_cap_point_dir(rate_cell, caps[j], base, sizeof base)) goto done;
+        if (P->on ? fastf_reps_point_dir(base, seed, name, sizeof name) : (snprintf(name, sizeof name, "%s", base), 0)) goto done;
         tt = fastf_res_now();
         if (fastf_cap_thresholds(h_hits, n_cells, caps[j], h_thr)) goto done;
         for (uint32_t k = 0; k < n_cells; k++) capped += h_hits[k] > caps[j];
         if (fastf_devmem_copy(d_thr, h_thr, (size_t)n_cells * 8) ||
-            fastf_dev_cell_decisions(S.e, N, S.blocked ? S.d_blk : NULL, seed, L->mt_skip, H, (const uint64_t *)d_thr, (uint32_t *)d_plane, NULL)) goto done;
+            fastf_dev_cell_decisions(S->e, N, S->blocked ? S->d_blk : NULL, seed, L->mt_skip, H, (const uint64_t *)d_thr, (uint32_t *)d_plane, NULL)) goto done;
         T->planes += fastf_res_now() - tt;
-        const int prc = fastf_res_point_run(&S, (const uint32_t *)d_plane, name, counters, &nnz, T);
+        const int prc = fastf_res_point_run(S, (const uint32_t *)d_plane, name, counters, &nnz, T);
         if (prc != RES_OK) { rc = prc; goto done; }
         tt = fastf_res_now();
-        if (fastf_cap_summary_row(rate_cell, caps[j], seed, counters, nnz, S.h_upc[n_cells], S.h_upc, S.h_gpc, n_cells, H, capped, row, sizeof row)) goto done;
+        if (cap_row_(rate_cell, caps[j], seed, counters, nnz, S->h_upc[n_cells], S->h_upc, S->h_gpc, n_cells, H, capped, row, sizeof row, metrics) ||
+            fastf_res_reps_point(P, j, k_seed, n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
+        if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
+            tt = fastf_res_now();
+            if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
+            T->reps += fastf_res_now() - tt;
+        }
         if (!summary_only) {
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (fastf_res_point_write(&S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
+            if (fastf_res_point_write(S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
         }
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
-            if (fastf_genes_summary_row(rate_cell, 0.0f, caps[j], seed, S.h_cpg, S.h_upg, S.n_features, grow, sizeof grow) ||
-                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
+            if (fastf_genes_summary_row(rate_cell, 0.0f, caps[j], seed, S->h_cpg, S->h_upg, S->n_features, grow, sizeof grow) ||
+                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S->h_cpg, S->h_upg)) goto done;
             T->genes += fastf_res_now() - tt;
         }
         if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
             char crow[1024];
-            if (fastf_res_point_cells(&S, name, T)) goto done;
+            if (fastf_res_point_cells(S, name, T)) goto done;
             tt = fastf_res_now();
-            if (fastf_cells_summary_row(rate_cell, 0.0f, caps[j], seed, S.h_rpc, S.h_npc, S.h_spc, n_cells, S.h_hist, crow, sizeof crow) ||
-                fastf_res_cells_point(C, &S, summary_only ? NULL : dir, crow)) goto done;
+            if (fastf_cells_summary_row(rate_cell, 0.0f, caps[j], seed, S->h_rpc, S->h_npc, S->h_spc, n_cells, S->h_hist, crow, sizeof crow) ||
+                fastf_res_cells_point(C, S, summary_only ? NULL : dir, crow)) goto done;
             T->cells += fastf_res_now() - tt;
         }
         fputs(row, tsv);
     }
     rc = RES_OK;
 done:
-    fastf_res_rate_close(&S);
     fastf_devmem_free(d_plane); fastf_devmem_free(d_hits); fastf_devmem_free(d_thr);
     if (h_hits) fastf_pinned_free(h_hits);
     if (h_thr) fastf_pinned_free(h_thr);
@@ -196,44 +213,65 @@ done:
 }
 
 static int cap_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
-                        const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G, res_cells_t *C)
+                        const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_s, int summary_only, int device, FILE *tsv, res_genes_t *G,
+                        res_cells_t *C, res_reps_t *P)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
     res_times_t T; memset(&T, 0, sizeof T);
     const double t0 = fastf_res_now();
     double tt = t0;
-    res_lists_t LL;
+    res_lists_t LL; memset(&LL, 0, sizeof LL);
     resident_t R; memset(&R, 0, sizeof R);
-    if ((rc = fastf_res_lists_load(barcodes, features, rc_list, n_c, seed, &LL)) != RES_OK) goto done;
+    res_rate_t S; memset(&S, 0, sizeof S);
+    /* the (cell rate, seed) pairs: cell rates outer, the seeds as listed */
+    const uint32_t n_pairs = n_c * n_s;
+    float *pair_rate = (float *)malloc(n_pairs * sizeof *pair_rate);
+    uint32_t *pair_seed = (uint32_t *)malloc(n_pairs * sizeof *pair_seed);
+    if (!pair_rate || !pair_seed) { cp_err("out of memory"); goto done; }
+    for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = rc_list[i]; pair_seed[i * n_s + k] = seeds[k]; }
+    if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
+    S.max_cells = fastf_res_lists_max_cells(&LL);
+    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("cap", bam_file, &LL.L[0], device, &R)) goto done;
     T.decode = fastf_res_now() - tt;
-    printf("cap: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n);
+    if (P->on) printf("cap: %llu records resident on the device (%llu bytes), %u x %u points x %u seeds\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n, n_s);
+    else printf("cap: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_n);
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = cap_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], caps, n_n, seed, summary_only, device, tsv, G, C, &T);
-        if (rc != RES_OK) goto done;
+        if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
+        for (uint32_t k = 0; k < n_s; k++) {
+            const uint32_t at = i * n_s + k;
+            rc = cap_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_n, seeds[k], summary_only, device, tsv, G, C, P, k, &T);
+            if (rc != RES_OK) goto done;
+        }
+        if (fastf_res_reps_rate_end(P, rc_list[i], NULL, caps, &T)) { rc = RES_FAIL; goto done; }
     }
     rc = RES_OK;
     if (prof)
         fprintf(stderr, "[cap] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, hits per cell + thresholds + planes %.3f s, "
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
-                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_n), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_n * n_s), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+    if (prof && P->on) fprintf(stderr, "[cap] replicates: %u (cell rate, seed) pairs opened in %.3f s (engines %.3f s, buffers + layout + K1a %.3f s), the blocked copy "
+                                       "laid out %u times; replicate tables and per-gene accumulation %.3f s\n", T.opens, T.engine + T.block_k1a, T.engine, T.block_k1a, T.relays, T.reps);
     if (prof && G->on) fprintf(stderr, "[cap] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
     if (prof && C->on) fprintf(stderr, "[cap] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
-                               T.cells_dev, T.cells_dev / (n_c * n_n), T.cells);
+                               T.cells_dev, T.cells_dev / (n_c * n_n * n_s), T.cells);
 done:
+    fastf_res_rate_close(&S);
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
+    free(pair_rate); free(pair_seed);
     return rc;
 }
 
 /* ------------------------------------------------------------------ */
 /* the command                                                         */
 /* ------------------------------------------------------------------ */
-int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-              const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags)
+/* reps != 0: a replicate run (fastf_cap_reps) — the suffixed directories and the replicate tables, with one seed too */
+static int cap_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                   const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags)
 {
     if (!bam || !barcodes || !features) return cp_err("cap: null argument");
     if (!out_dir) out_dir = ".";
@@ -250,16 +288,41 @@ int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const 
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
     res_genes_t G;
-    if (fastf_res_genes_open(&G, genes, "cap", out_dir, fastf_cap_genes_header(), n_c * n_n)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+    if (fastf_res_genes_open(&G, genes, "cap", out_dir, fastf_cap_genes_header(), n_c * n_n, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "cap", out_dir, fastf_cap_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
-    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seed, summary_only, dev0, tsv.f, &G, &C);
+    res_reps_t P;
+    if (fastf_res_reps_open(&P, reps, "cap", out_dir, seeds, n_s, n_c, n_n, genes, dev0, fastf_cap_reps_header(), fastf_cap_genes_reps_header())) {
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1;
+    }
+    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &P);
     if (rc == RES_NOT_COVERED)
         cp_err("cap: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
     if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_set_error_(keep); return 1; }
-    return fastf_res_tsv_close(&tsv, 1);
+    if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, NULL, caps)) rc = 1;
+    if (rc) {
+        char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_reps_close(&P, 0);
+        if (reps) fastf_res_reps_unlink_tables(out_dir, "cap");      /* (the tables that were already renamed go too: none is left) */
+        fastf_set_error_(keep);
+        return 1;
+    }
+    if (fastf_res_tsv_close(&tsv, 1)) { if (reps) fastf_res_reps_unlink_tables(out_dir, "cap"); return 1; }
+    return 0;
+}
+
+int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+              const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags)
+{
+    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, &seed, 1, 0, flags);
+}
+
+int fastf_cap_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                   const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
+{
+    if (fastf_check_seeds_("cap", seeds, n_seeds)) return 1;
+    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_seeds, 1, flags);
 }
 
 static void usage_cap(FILE *f)
@@ -279,7 +342,12 @@ static void usage_cap(FILE *f)
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
             "        --summary-only    write cap.tsv alone\n"
             "        --genes           per-gene detection too: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point\n"
-            "        --cells           per-cell reads, saturation and UMI copy numbers too: cap_cells.tsv and cells.tsv.gz per point\n");
+            "        --cells           per-cell reads, saturation and UMI copy numbers too: cap_cells.tsv and cells.tsv.gz per point\n"
+            "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
+            "                          seed <out>/c<cell>_n<N>_s<seed>/, one cap.tsv row each, and cap_reps.tsv with mean, sd, min and max\n"
+            "                          of every metric per grid point (with --genes cap_genes_reps.tsv and cap_gene_reps.tsv.gz in\n"
+            "                          place of cap_gene_cells.tsv.gz); not with -s or --reps\n"
+            "        --reps=<int>      the same at the seeds s, s + 1, .. s + N - 1 (s: -s; N from 1 to 64)\n");
 }
 
 #define CAP_MAX_POINTS 64
@@ -298,12 +366,16 @@ int cmd_cap(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0))) {
+    const uint32_t flags = (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0);
+    if (A.n_seeds ? fastf_cap_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags)
+                  : fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
         return 1;
     }
-    if (A.genes) printf("cap_genes.tsv and cap_gene_cells.tsv.gz are generated.\n");
+    if (A.genes && A.n_seeds) printf("cap_genes.tsv, cap_genes_reps.tsv and cap_gene_reps.tsv.gz are generated.\n");
+    else if (A.genes) printf("cap_genes.tsv and cap_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("cap_cells.tsv is generated.\n");
+    if (A.n_seeds) printf("cap_reps.tsv is generated.\n");
     printf("cap.tsv is generated.\n");
     return 0;
 }

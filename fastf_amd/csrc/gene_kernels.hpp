@@ -3,6 +3,8 @@
 //
 //   gene_summary_kernel   rows (feature, count) in any order -> cells_per_gene[g - 1] = rows of gene g with count >= 1 (the rule of
 //                         genes_per_cell), umis_per_gene[g - 1] = the sum of their counts
+//   gene_reps_kernel      replicate runs (--seeds, --reps): the cells_per_gene of one (grid point, seed) added into the three u64
+//                         accumulators of its grid point
 #pragma once
 #include "umi_kernels.hpp"
 
@@ -81,6 +83,22 @@ __global__ __launch_bounds__(GENE_THREADS) void gene_summary_kernel(const u32* _
             if (v >> 32) atomicAdd(cells + i, (u32)(v >> 32));
             if (v & 0xFFFFFFFFull) atomicAdd(umis + i, v & 0xFFFFFFFFull);
         }
+    }
+}
+
+// Replicates: cells[g] of one seed's point into the accumulators of its grid point — detected[g] += (cells[g] >= 1), sum[g] += cells[g],
+// sumsq[g] += cells[g]^2, all u64.  The sum of squares is exact while it stays below 2^64: for the 64 seeds a run takes at most,
+// cell counts below 2^29 (5.4e8 cells) — far beyond any barcode list; three adds of 2^31 (3 * 2^62) still fit, a fifth would not.  Elementwise: gene g belongs to one thread, so
+// there are no atomics; per gene one 4-byte load of cells, the three accumulators read and written back.  The launch follows the
+// point's gene summary on the same stream and the accumulators of a point are touched by one launch at a time.
+constexpr u32 GENE_REPS_THREADS = 256;
+__global__ __launch_bounds__(GENE_REPS_THREADS) void gene_reps_kernel(const u32* __restrict__ cells, u32 n_features, u64* __restrict__ detected,
+                                                                      u64* __restrict__ sum, u64* __restrict__ sumsq) {
+    for (u64 g = (u64)blockIdx.x * GENE_REPS_THREADS + threadIdx.x; g < n_features; g += (u64)gridDim.x * GENE_REPS_THREADS) {
+        const u64 c = cells[g];
+        detected[g] += c != 0 ? 1ull : 0ull;
+        sum[g] += c;
+        sumsq[g] += c * c;
     }
 }
 

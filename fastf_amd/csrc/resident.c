@@ -7,6 +7,7 @@
 #include "resident.h"
 
 #include <errno.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -45,14 +46,14 @@ void fastf_res_lists_free(res_lists_t *l)
     memset(l, 0, sizeof *l);
 }
 
-int fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c, uint32_t seed, res_lists_t *out)
+int fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, const uint32_t *seeds, uint32_t n_c, res_lists_t *out)
 {
     memset(out, 0, sizeof *out);
     fastf_lists_t *L = out->L = (fastf_lists_t *)calloc(n_c, sizeof *L);
     uint64_t **keys = out->keys = (uint64_t **)calloc(n_c, sizeof *keys);
     if (!L || !keys) { rs_err("out of memory"); return RES_FAIL; }
     for (uint32_t i = 0; i < n_c; i++) {
-        if (fastf_lists_load(barcodes, features, rates_cell[i], seed, &L[i])) return RES_FAIL;
+        if (fastf_lists_load(barcodes, features, rates_cell[i], seeds[i], &L[i])) return RES_FAIL;
         out->n = i + 1;
     }
     for (uint32_t i = 0; i < n_c; i++) {
@@ -155,11 +156,34 @@ void fastf_res_rate_close(res_rate_t *S)
     memset(S, 0, sizeof *S);
 }
 
-/* on anything but RES_OK the caller still calls fastf_res_rate_close */
+/* room of at least `need` bytes in a buffer that outlives the pair: what is there is kept when it is large enough */
+static int dev_room(void **p, size_t *have, size_t need, int device)
+{
+    if (*p && *have >= need) return 0;
+    fastf_devmem_free(*p); *p = NULL; *have = 0;
+    if (!(*p = fastf_devmem_alloc(device, need))) return 1;
+    *have = need;
+    return 0;
+}
+static int pin_room(void **p, size_t *have, size_t need)
+{
+    if (*p && *have >= need) return 0;
+    if (*p) fastf_pinned_free(*p);
+    *p = NULL; *have = 0;
+    if (!(*p = fastf_pinned_alloc(need))) return 1;
+    *have = need;
+    return 0;
+}
+
+/* S: zeroed before the first open of a run, or as the open of the pair before left it (resident.h).  On anything but RES_OK the
+ * caller still calls fastf_res_rate_close */
 int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
-    memset(S, 0, sizeof *S);
+    if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; }
+    S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
+    T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
     S->verb = verb; S->R = R; S->L = L; S->device = device; S->rate_cell = rate_cell; S->seed = seed;
     const uint64_t N = R->n;
@@ -190,26 +214,34 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
     S->key_slots = (seg_slots > N ? seg_slots : N) + 64;
     S->kflags = FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS | (S->blocked ? FASTF_PROBE_BLOCKED : 0) | (S->segmented ? FASTF_PROBE_SEGMENTED : 0);
     const size_t need = (S->blocked ? blk_bytes : 0) + 2 * S->key_slots * 8 + N * 12 + ((size_t)n_cells + 1) * 12;
-    if (!(S->d_small = fastf_devmem_alloc(device, SM_WORDS_ * 8)) || !(S->h_small = (uint64_t *)fastf_pinned_alloc(SM_WORDS_ * 8)) ||
-        (S->blocked && !(S->d_blk = fastf_devmem_alloc(device, blk_bytes))) ||
-        !(S->d_keys = fastf_devmem_alloc(device, S->key_slots * 8)) || !(S->d_tmp = fastf_devmem_alloc(device, S->key_slots * 8)) ||
-        !(S->d_rows = fastf_devmem_alloc(device, (N ? N : 1) * 12)) ||
-        !(S->d_upc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 8)) || !(S->d_gpc = fastf_devmem_alloc(device, ((size_t)n_cells + 1) * 4)) ||
-        !(S->h_upc = (uint64_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 8)) || !(S->h_gpc = (uint32_t *)fastf_pinned_alloc(((size_t)n_cells + 1) * 4))) {
+    uint64_t layout = 0;
+    if (fastf_dev_block_layout(S->e, N, &layout)) return RES_FAIL;
+    /* room for the run's widest pair: its cells in the per-cell arrays, and a 32-bit cell scratch in the blocked runs where a later
+     * pair samples more than 65535 cells while this one has the 16-bit scratch (2 bytes more for each of a unit's 256 records) */
+    const size_t room_cells = (S->max_cells > n_cells ? S->max_cells : n_cells) + (size_t)1;
+    const size_t blk_room = blk_bytes + ((S->max_cells > 65535u && n_cells <= 65535u) ? ((N + 255) / 256) * 512 : 0);
+    if (S->blocked && (!S->d_blk || S->have.blk < blk_bytes)) S->blk_layout = 0;      /* (a new buffer holds no copy) */
+    if ((!S->d_small && !(S->d_small = fastf_devmem_alloc(device, SM_WORDS_ * 8))) || (!S->h_small && !(S->h_small = (uint64_t *)fastf_pinned_alloc(SM_WORDS_ * 8))) ||
+        (S->blocked && dev_room(&S->d_blk, &S->have.blk, (S->d_blk && S->have.blk >= blk_bytes) ? blk_bytes : blk_room, device)) ||
+        dev_room(&S->d_keys, &S->have.keys, S->key_slots * 8, device) || dev_room(&S->d_tmp, &S->have.tmp, S->key_slots * 8, device) ||
+        dev_room(&S->d_rows, &S->have.rows, (N ? N : 1) * 12, device) ||
+        dev_room(&S->d_upc, &S->have.upc, room_cells * 8, device) || dev_room(&S->d_gpc, &S->have.gpc, room_cells * 4, device) ||
+        pin_room((void **)&S->h_upc, &S->have.h_upc, room_cells * 8) || pin_room((void **)&S->h_gpc, &S->have.h_gpc, room_cells * 4)) {
         rs_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
         return RES_FAIL;
     }
     if (genes) {                                            /* the per-gene arrays of a point and their pinned host copies, once */
         const size_t nf1 = (size_t)S->n_features + 1;
-        if (!(S->d_cpg = fastf_devmem_alloc(device, nf1 * 4)) || !(S->d_upg = fastf_devmem_alloc(device, nf1 * 8)) ||
-            !(S->h_cpg = (uint32_t *)fastf_pinned_alloc(nf1 * 4)) || !(S->h_upg = (uint64_t *)fastf_pinned_alloc(nf1 * 8))) {
+        if (dev_room(&S->d_cpg, &S->have.cpg, nf1 * 4, device) || dev_room(&S->d_upg, &S->have.upg, nf1 * 8, device) ||
+            pin_room((void **)&S->h_cpg, &S->have.h_cpg, nf1 * 4) || pin_room((void **)&S->h_upg, &S->have.h_upg, nf1 * 8)) {
             rs_err("%s: the per-gene arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, nf1 * 12, fastf_last_error());
             return RES_FAIL;
         }
     }
     if (cells) {                                            /* the histogram and the three per-cell arrays of a point and their pinned host copy, once */
         const size_t bytes = RES_CELLS_HIST_BYTES + (size_t)n_cells * 12;
-        if (!(S->d_cellsum = fastf_devmem_alloc(device, bytes)) || !(S->h_hist = (uint64_t *)fastf_pinned_alloc(bytes))) {
+        const size_t room = RES_CELLS_HIST_BYTES + (room_cells - 1) * 12;
+        if (dev_room(&S->d_cellsum, &S->have.cellsum, room, device) || pin_room((void **)&S->h_hist, &S->have.h_hist, room)) {
             rs_err("%s: the per-cell arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, bytes, fastf_last_error());
             return RES_FAIL;
         }
@@ -220,8 +252,15 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
 
     /* the records into the engine's layout, K1a once: the cell scratch and the hit count serve every point */
     if (S->blocked) {
-        if (fastf_dev_block_records(S->e, R->gx, R->umi, R->meta, N, S->d_blk, NULL) ||
-            fastf_dev_count_hits_blocked(S->e, R->cb, N, S->d_blk, sm + SM_HITS, NULL)) return RES_FAIL;
+        /* the blocked copy is laid out again only where this engine's layout is not the one the copy is in (a new buffer holds none):
+         * otherwise K1a alone, which fills the cell scratch slices of every unit */
+        if (layout != S->blk_layout || !layout) {
+            S->blk_layout = 0;
+            if (fastf_dev_block_records(S->e, R->gx, R->umi, R->meta, N, S->d_blk, NULL)) return RES_FAIL;
+            S->blk_layout = layout;
+            T->relays++;
+        }
+        if (fastf_dev_count_hits_blocked(S->e, R->cb, N, S->d_blk, sm + SM_HITS, NULL)) return RES_FAIL;
     } else if (fastf_dev_count_hits(S->e, R->cb, N, sm + SM_HITS, NULL)) return RES_FAIL;
     if (fastf_devmem_sync() || fastf_devmem_copy(S->h_small, S->d_small, SM_WORDS_ * 8)) return RES_FAIL;
     S->H = S->h_small[SM_HITS];
@@ -363,15 +402,15 @@ static void genes_release(res_genes_t *G)
     G->feat_id = NULL; G->cells = NULL; G->names = NULL; G->n_features = G->n_points = 0;
 }
 
-int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points)
+int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points, int no_grid)
 {
     memset(G, 0, sizeof *G);
     if (!on) return 0;
-    G->verb = verb; G->max_points = max_points;
+    G->verb = verb; G->max_points = no_grid ? 0 : max_points; G->no_grid = no_grid;
     snprintf(G->out_dir, sizeof G->out_dir, "%s", out_dir);
     char name[64];
     snprintf(name, sizeof name, "%s_genes.tsv", verb);
-    if (!(G->names = calloc(max_points ? max_points : 1, sizeof *G->names))) return rs_err("out of memory");
+    if (!(G->names = calloc(G->max_points ? G->max_points : 1, sizeof *G->names))) return rs_err("out of memory");
     if (fastf_res_tsv_open(&G->tsv, out_dir, name, header)) { genes_release(G); return 1; }
     G->on = 1;
     return 0;
@@ -416,11 +455,13 @@ int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *po
         for (uint32_t i = 0; i < nf; i++) { if (!(G->feat_id[i] = strdup(L->feat_id[i]))) return rs_err("out of memory"); G->n_features = i + 1; }
     }
     if ((uint32_t)L->n_features != G->n_features) return rs_err("internal error: the feature list changed between points");
-    if (G->n_points >= G->max_points) return rs_err("internal error: more points than the grid has");
     const uint32_t nf = G->n_features;
-    snprintf(G->names[G->n_points], sizeof G->names[0], "%s", point_name);
-    if (nf) memcpy(G->cells + (size_t)G->n_points * nf, cells, (size_t)nf * sizeof *cells);
-    G->n_points++;
+    if (!G->no_grid) {
+        if (G->n_points >= G->max_points) return rs_err("internal error: more points than the grid has");
+        snprintf(G->names[G->n_points], sizeof G->names[0], "%s", point_name);
+        if (nf) memcpy(G->cells + (size_t)G->n_points * nf, cells, (size_t)nf * sizeof *cells);
+        G->n_points++;
+    }
     if (dir) {
         char path[4200];
         gtext t = { NULL, 0, 0 };
@@ -441,7 +482,7 @@ int fastf_res_genes_close(res_genes_t *G, int ok)
 {
     if (!G->on) return 0;
     int rc = 0;
-    if (ok) {
+    if (ok && !G->no_grid) {
         char path[4200];
         gtext t = { NULL, 0, 0 };
         int bad = gt_str(&t, "feature");
@@ -509,13 +550,314 @@ int fastf_res_cells_close(res_cells_t *C, int ok)
     return fastf_res_tsv_close(&C->tsv, ok);
 }
 
+/* ------------------------------------------------------------------ */
+/* replicate seeds: the lists, the names, the rows                     */
+/* ------------------------------------------------------------------ */
+int fastf_parse_seeds(const char *text, uint32_t *out, uint32_t cap, uint32_t *n_out)
+{
+    uint32_t n = 0;
+    if (n_out) *n_out = 0;
+    if (!text || !out || !n_out) return rs_err("null argument");
+    if (cap > FASTF_MAX_SEEDS) cap = FASTF_MAX_SEEDS;
+    for (const char *p = text;;) {
+        const char *q = p;
+        while (*q && *q != ',') q++;
+        char el[64];
+        const size_t len = (size_t)(q - p);
+        if (len == 0) return rs_err("--seeds `%s`: empty element", text);
+        if (len >= sizeof el) return rs_err("--seeds `%s`: element too long", text);
+        memcpy(el, p, len); el[len] = '\0';
+        char *end = NULL;
+        errno = 0;
+        const uint32_t v = (uint32_t)(unsigned int)strtol(el, &end, 0);      /* (the rule of -s) */
+        if (errno == ERANGE) return rs_err("--seeds `%s`: numerical result out of range", el);
+        if (end == el || *end) return rs_err("--seeds `%s`: expects an integer value", el);
+        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return rs_err("--seeds `%s`: %u is listed twice", text, v);
+        if (n == cap) return rs_err("--seeds `%s`: more than %u values", text, cap);
+        out[n++] = v;
+        if (!*q) break;
+        p = q + 1;
+    }
+    *n_out = n;
+    return 0;
+}
+
+int fastf_reps_seeds(uint32_t first, uint64_t n_reps, uint32_t *out, uint32_t cap, uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!out || !n_out) return rs_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS || n_reps > cap) return rs_err("--reps %llu: expects 1 to %u replicates", (unsigned long long)n_reps, cap < FASTF_MAX_SEEDS ? cap : FASTF_MAX_SEEDS);
+    if ((uint64_t)first + n_reps - 1 > 0xFFFFFFFFull)
+        return rs_err("--reps %llu from seed %u: the seeds would wrap past 4294967295", (unsigned long long)n_reps, first);
+    for (uint32_t k = 0; k < (uint32_t)n_reps; k++) out[k] = first + k;
+    *n_out = (uint32_t)n_reps;
+    return 0;
+}
+
+int fastf_reps_point_dir(const char *point_name, uint32_t seed, char *buf, size_t cap)
+{
+    if (!point_name || !buf) return rs_err("null argument");
+    const int n = snprintf(buf, cap, "%s_s%u", point_name, seed);
+    return (n < 0 || (size_t)n >= cap) ? rs_err("directory name too long") : 0;
+}
+
+#define REPS_STAT4(m) "\t" m "_mean\t" m "_sd\t" m "_min\t" m "_max"
+#define REPS_COLUMNS_TAIL "n_reps\tn_cells" REPS_STAT4("sampled_reads") REPS_STAT4("sampled_valid_reads") REPS_STAT4("nnz") REPS_STAT4("umis") \
+    REPS_STAT4("saturation") REPS_STAT4("median_umis_per_cell") REPS_STAT4("median_genes_per_cell") "\n"
+const char *fastf_sweep_reps_header(void) { return "rate_cell\trate_depth\t" REPS_COLUMNS_TAIL; }
+const char *fastf_cap_reps_header(void) { return "rate_cell\treads_per_cell\t" REPS_COLUMNS_TAIL; }
+#define GENES_REPS_COLUMNS_TAIL "n_reps" REPS_STAT4("genes_detected") "\tgenes_in_all_reps\tgenes_in_any_rep\n"
+const char *fastf_sweep_genes_reps_header(void) { return "rate_cell\trate_depth\t" GENES_REPS_COLUMNS_TAIL; }
+const char *fastf_cap_genes_reps_header(void) { return "rate_cell\treads_per_cell\t" GENES_REPS_COLUMNS_TAIL; }
+
+/* `\t mean \t sd \t min \t max` of v[0], v[stride], ..: two passes in list order, the sample sd; kind 0: integers, 1: %.6f, 2: %.1f */
+static int reps_stat4(const double *v, uint32_t stride, uint32_t n, int kind, char *buf, size_t cap)
+{
+    double sum = 0.0, ss = 0.0, lo = v[0], hi = v[0];
+    for (uint32_t k = 0; k < n; k++) { const double x = v[(size_t)k * stride]; sum += x; if (x < lo) lo = x; if (x > hi) hi = x; }
+    const double mean = sum / (double)n;
+    for (uint32_t k = 0; k < n; k++) { const double d = v[(size_t)k * stride] - mean; ss += d * d; }
+    char sd[40], a[40], b[40];
+    if (n > 1) snprintf(sd, sizeof sd, "%.6f", sqrt(ss / (double)(n - 1))); else snprintf(sd, sizeof sd, "NA");
+    if (kind == 0) { snprintf(a, sizeof a, "%llu", (unsigned long long)lo); snprintf(b, sizeof b, "%llu", (unsigned long long)hi); }
+    else if (kind == 1) { snprintf(a, sizeof a, "%.6f", lo); snprintf(b, sizeof b, "%.6f", hi); }
+    else { snprintf(a, sizeof a, "%.1f", lo); snprintf(b, sizeof b, "%.1f", hi); }
+    const int w = snprintf(buf, cap, "\t%.6f\t%s\t%s\t%s", mean, sd, a, b);
+    return (w < 0 || (size_t)w >= cap) ? -1 : w;
+}
+static int reps_row_head(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t n_reps, char *buf, size_t cap)
+{
+    char second[32];
+    if (reads_per_cell) snprintf(second, sizeof second, "%llu", (unsigned long long)reads_per_cell);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int w = snprintf(buf, cap, "%.3f\t%s\t%u", (double)rate_cell, second, n_reps);
+    return (w < 0 || (size_t)w >= cap) ? -1 : w;
+}
+
+int fastf_reps_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t n_cells, const double *metrics, uint32_t n_reps,
+                           char *buf, size_t cap)
+{
+    static const int kind[FASTF_REPS_METRICS] = {0, 0, 0, 0, 1, 2, 2};
+    if (!buf || !metrics) return rs_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return rs_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
+    int n = reps_row_head(rate_cell, rate_depth, reads_per_cell, n_reps, buf, cap);
+    if (n >= 0) { const int w = snprintf(buf + n, cap - (size_t)n, "\t%u", n_cells); n = (w < 0 || (size_t)w >= cap - (size_t)n) ? -1 : n + w; }
+    for (uint32_t m = 0; m < FASTF_REPS_METRICS && n >= 0; m++) {
+        const int w = reps_stat4(metrics + m, FASTF_REPS_METRICS, n_reps, kind[m], buf + n, cap - (size_t)n);
+        n = w < 0 ? -1 : n + w;
+    }
+    if (n < 0 || (size_t)n + 1 >= cap) return rs_err("summary row too long");
+    buf[n] = '\n'; buf[n + 1] = '\0';
+    return 0;
+}
+
+int fastf_genes_reps_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, const uint32_t *genes_detected, uint32_t n_reps,
+                         const uint64_t *reps_detected, uint32_t n_features, char *buf, size_t cap)
+{
+    if (!buf || !genes_detected || (n_features && !reps_detected)) return rs_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return rs_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
+    double v[FASTF_MAX_SEEDS];
+    for (uint32_t k = 0; k < n_reps; k++) v[k] = (double)genes_detected[k];
+    uint32_t all = 0, any = 0;
+    for (uint32_t g = 0; g < n_features; g++) { all += reps_detected[g] == n_reps; any += reps_detected[g] >= 1; }
+    int n = reps_row_head(rate_cell, rate_depth, reads_per_cell, n_reps, buf, cap);
+    if (n >= 0) { const int w = reps_stat4(v, 1, n_reps, 0, buf + n, cap - (size_t)n); n = w < 0 ? -1 : n + w; }
+    if (n >= 0) { const int w = snprintf(buf + n, cap - (size_t)n, "\t%u\t%u\n", all, any); n = (w < 0 || (size_t)w >= cap - (size_t)n) ? -1 : n + w; }
+    return n < 0 ? rs_err("summary row too long") : 0;
+}
+
+int fastf_gene_reps_add_host(const uint32_t *cells_per_gene, uint32_t n_features, uint64_t *detected, uint64_t *sum, uint64_t *sumsq)
+{
+    if (n_features && (!cells_per_gene || !detected || !sum || !sumsq)) return rs_err("null argument");
+    for (uint32_t g = 0; g < n_features; g++) {
+        const uint64_t c = cells_per_gene[g];
+        detected[g] += c != 0; sum[g] += c; sumsq[g] += c * c;
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* replicate runs: the tables of a run                                 */
+/* ------------------------------------------------------------------ */
+static void reps_release(res_reps_t *P)
+{
+    if (P->feat_id) for (uint32_t i = 0; i < P->n_features; i++) free(P->feat_id[i]);
+    free(P->feat_id); free(P->m); free(P->n_cells); free(P->gdet); free(P->seen); free(P->h_acc);
+    fastf_devmem_free(P->d_acc);
+    P->feat_id = NULL; P->m = NULL; P->n_cells = P->gdet = NULL; P->seen = NULL; P->h_acc = NULL; P->d_acc = NULL; P->n_features = 0;
+}
+
+int fastf_res_reps_open(res_reps_t *P, int on, const char *verb, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
+                        uint32_t n_list, int genes, int device, const char *header, const char *genes_header)
+{
+    memset(P, 0, sizeof *P);
+    if (!on) return 0;
+    P->verb = verb; P->seeds = seeds; P->n_seeds = n_seeds; P->n_rates = n_rates; P->n_list = n_list; P->genes = genes; P->device = device;
+    snprintf(P->out_dir, sizeof P->out_dir, "%s", out_dir);
+    const size_t cells = (size_t)n_list * n_seeds;
+    if (!(P->m = (double *)calloc(cells * FASTF_REPS_METRICS, sizeof *P->m)) || !(P->n_cells = (uint32_t *)calloc(cells, sizeof *P->n_cells)) ||
+        !(P->gdet = (uint32_t *)calloc(cells, sizeof *P->gdet)) || !(P->seen = (uint8_t *)calloc(cells, 1))) { reps_release(P); return rs_err("out of memory"); }
+    char name[64];
+    snprintf(name, sizeof name, "%s_reps.tsv", verb);
+    if (fastf_res_tsv_open(&P->tsv, out_dir, name, header)) { reps_release(P); return 1; }
+    snprintf(name, sizeof name, "%s_genes_reps.tsv", verb);
+    if (genes && fastf_res_tsv_open(&P->gtsv, out_dir, name, genes_header)) { fastf_res_tsv_close(&P->tsv, 0); reps_release(P); return 1; }
+    P->on = 1;
+    return 0;
+}
+
+int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_device)
+{
+    if (!P->on) return 0;
+    const size_t cells = (size_t)P->n_list * P->n_seeds;
+    memset(P->seen, 0, cells);
+    if (!P->genes) return 0;
+    const uint32_t nf = (uint32_t)L->n_features;
+    if (!P->feat_id) {                                      /* the first cell rate: the names, the room of the accumulators */
+        if (!(P->feat_id = (char **)calloc(nf ? nf : 1, sizeof *P->feat_id)) ||
+            !(P->h_acc = (uint64_t *)calloc((size_t)P->n_rates * P->n_list * 3 * nf + 1, sizeof *P->h_acc))) return rs_err("out of memory");
+        for (uint32_t i = 0; i < nf; i++) { if (!(P->feat_id[i] = strdup(L->feat_id[i]))) return rs_err("out of memory"); P->n_features = i + 1; }
+    }
+    if (nf != P->n_features) return rs_err("internal error: the feature list changed between cell rates");
+    const size_t bytes = (size_t)P->n_list * 3 * nf * 8;
+    if (on_device && nf) {
+        if (!P->d_acc && !(P->d_acc = fastf_devmem_alloc(P->device, bytes)))
+            return rs_err("%s: the per-gene accumulators of the replicates do not fit: %zu bytes (%s)", P->verb, bytes, fastf_last_error());
+        if (fastf_devmem_zero(P->d_acc, bytes)) return 1;
+    }
+    return 0;
+}
+
+int fastf_res_reps_point(res_reps_t *P, uint32_t j, uint32_t k, uint32_t n_cells, const double *metrics)
+{
+    if (!P->on) return 0;
+    if (j >= P->n_list || k >= P->n_seeds) return rs_err("internal error: replicate (%u, %u) outside the grid", j, k);
+    const size_t at = (size_t)j * P->n_seeds + k;
+    memcpy(P->m + at * FASTF_REPS_METRICS, metrics, FASTF_REPS_METRICS * sizeof *metrics);
+    P->n_cells[at] = n_cells; P->seen[at] = 1;
+    return 0;
+}
+
+int fastf_res_reps_genes(res_reps_t *P, res_rate_t *S, uint32_t j, uint32_t k, const uint32_t *cells_per_gene, uint32_t n_features)
+{
+    if (!P->on || !P->genes) return 0;
+    if (j >= P->n_list || k >= P->n_seeds || P->rate_at >= P->n_rates) return rs_err("internal error: replicate (%u, %u) outside the grid", j, k);
+    if (n_features != P->n_features) return rs_err("internal error: the feature list changed between points");
+    const uint32_t nf = P->n_features;
+    uint32_t d1 = 0;
+    for (uint32_t g = 0; g < nf; g++) d1 += cells_per_gene[g] >= 1;
+    P->gdet[(size_t)j * P->n_seeds + k] = d1;
+    if (S) {                                                /* the device's copy of the same array, behind the point's gene summary */
+        if (!nf) return 0;
+        if (!P->d_acc) return rs_err("internal error: no per-gene accumulators on the device");
+        uint64_t *const a = (uint64_t *)P->d_acc + (size_t)j * 3 * nf;
+        return fastf_dev_gene_reps_add(S->e, (const uint32_t *)S->d_cpg, nf, a, a + nf, a + 2 * (size_t)nf, NULL);
+    }
+    uint64_t *const a = P->h_acc + ((size_t)P->rate_at * P->n_list + j) * 3 * nf;
+    return fastf_gene_reps_add_host(cells_per_gene, nf, a, a + nf, a + 2 * (size_t)nf);
+}
+
+int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_depth, const uint64_t *caps, res_times_t *T)
+{
+    if (!P->on) return 0;
+    const double t0 = fastf_res_now();
+    if (P->rate_at >= P->n_rates) return rs_err("internal error: more cell rates than the grid has");
+    const uint32_t nf = P->n_features;
+    for (uint32_t j = 0; j < P->n_list; j++) {
+        const size_t at = (size_t)j * P->n_seeds;
+        char row[1536];
+        for (uint32_t k = 0; k < P->n_seeds; k++) {
+            if (!P->seen[at + k]) return rs_err("internal error: replicate (%u, %u) was not run", j, k);
+            if (P->n_cells[at + k] != P->n_cells[at])
+                return rs_err("%s: cell rate %.3f sampled %u cells at seed %u and %u at seed %u: the sample size depends on the rate alone", P->verb,
+                              (double)rate_cell, P->n_cells[at], P->seeds[0], P->n_cells[at + k], P->seeds[k]);
+        }
+        const float rd = rates_depth ? rates_depth[j] : 0.0f;
+        const uint64_t n = caps ? caps[j] : 0;
+        if (fastf_reps_summary_row(rate_cell, rd, n, P->n_cells[at], P->m + at * FASTF_REPS_METRICS, P->n_seeds, row, sizeof row)) return 1;
+        fputs(row, P->tsv.f);
+        if (P->genes) {
+            uint64_t *const a = P->h_acc + ((size_t)P->rate_at * P->n_list + j) * 3 * nf;
+            /* the three accumulators of the grid point come to the host once, after its last seed */
+            if (P->d_acc && nf && fastf_devmem_copy(a, (const uint64_t *)P->d_acc + (size_t)j * 3 * nf, (size_t)3 * nf * 8)) return 1;
+            if (fastf_genes_reps_row(rate_cell, rd, n, P->gdet + at, P->n_seeds, a, nf, row, sizeof row)) return 1;
+            fputs(row, P->gtsv.f);
+        }
+    }
+    P->rate_at++;
+    if (T) T->reps += fastf_res_now() - t0;
+    return 0;
+}
+
+/* <out_dir>/<verb>_gene_reps.tsv.gz: per feature and grid point the three accumulators */
+static int reps_gene_file(const res_reps_t *P, const float *rates_cell, const float *rates_depth, const uint64_t *caps)
+{
+    char path[4200];
+    gtext t = { NULL, 0, 0 };
+    const uint32_t nf = P->n_features, np = P->n_rates * P->n_list;
+    static const char *const col[3] = {":reps_detected", ":cells_sum", ":cells_sumsq"};
+    int bad = gt_str(&t, "feature");
+    for (uint32_t p = 0; p < np && !bad; p++) {
+        char name[64];
+        const uint32_t i = p / P->n_list, j = p % P->n_list;
+        bad = caps ? fastf_cap_point_dir(rates_cell[i], caps[j], name, sizeof name) : fastf_sweep_point_dir(rates_cell[i], rates_depth[j], name, sizeof name);
+        for (int c = 0; c < 3 && !bad; c++) bad = gt_str(&t, "\t") || gt_str(&t, name) || gt_str(&t, col[c]);
+    }
+    if (!bad) bad = gt_str(&t, "\n");
+    for (uint32_t g = 0; g < nf && !bad; g++) {
+        bad = gt_str(&t, P->feat_id[g]);
+        for (uint32_t p = 0; p < np && !bad; p++)
+            for (int c = 0; c < 3 && !bad; c++) bad = gt_u64(&t, '\t', P->h_acc[((size_t)p * 3 + (size_t)c) * nf + g]);
+        if (!bad) bad = gt_str(&t, "\n");
+    }
+    snprintf(path, sizeof path, "%s/%s_gene_reps.tsv.gz", P->out_dir, P->verb);
+    if (!bad) bad = gz_text_renamed(path, &t);
+    free(t.p);
+    return bad;
+}
+
+/* ok: the per-gene file (its columns named from the grid: rates_cell and ONE of rates_depth / caps), then the tables; otherwise
+ * nothing of either is left */
+int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, const float *rates_depth, const uint64_t *caps)
+{
+    if (!P->on) return 0;
+    int rc = 0;
+    if (ok && P->rate_at != P->n_rates) rc = rs_err("internal error: %u of %u cell rates were closed", P->rate_at, P->n_rates);
+    if (ok && !rc && P->genes) rc = reps_gene_file(P, rates_cell, rates_depth, caps);
+    char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+    const int bad = rc;
+    if (fastf_res_tsv_close(&P->tsv, ok && !rc)) rc = 1;
+    if (P->genes && fastf_res_tsv_close(&P->gtsv, ok && !rc)) rc = 1;
+    if (bad) fastf_set_error_(keep);
+    reps_release(P);
+    P->on = 0;
+    return rc;
+}
+int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_grid(P, ok, NULL, NULL, NULL); }
+
+void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
+{
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz"};
+    for (int k = 0; k < 5; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+}
+
+uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
+{
+    size_t m = 0;
+    for (uint32_t i = 0; i < l->n; i++) if (l->L[i].n_cells > m) m = l->L[i].n_cells;
+    return (uint32_t)m;
+}
+
 struct ropt { char s; const char *l; int has_arg; };
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *out)
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+    const char *seeds_text = NULL, *reps_text = NULL;
+    int have_s = 0;
+    out->n_seeds = 0;
     out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -530,7 +872,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && k->s != 'S' && k->s != 'G' && k->s != 'C') { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -550,7 +892,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'd': break;
         case 'o': out->out = val; break;
         case 'c': out->cells = val; break;
-        case 's': errno = 0; out->seed = (unsigned int)strtol(val, &end, 0);
+        case 's': have_s = 1; errno = 0; out->seed = (unsigned int)strtol(val, &end, 0);
                   if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); return 1; }
                   if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); return 1; }
                   break;
@@ -558,7 +900,23 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'S': out->summary_only = 1; break;
         case 'G': out->genes = 1; break;
         case 'C': out->per_cell = 1; break;
+        case 'E': seeds_text = val; break;
+        case 'R': reps_text = val; break;
         }
+    }
+    /* replicates: --seeds lists them, --reps counts them up from -s */
+    if (seeds_text && reps_text) { fprintf(stderr, "error: option `--seeds` cannot be combined with `--reps`\n"); return 1; }
+    if (seeds_text && have_s) { fprintf(stderr, "error: option `--seeds` cannot be combined with `-s`\n"); return 1; }
+    if (seeds_text && fastf_parse_seeds(seeds_text, out->seeds, FASTF_MAX_SEEDS, &out->n_seeds)) { fprintf(stderr, "error: option %s\n", fastf_last_error()); return 1; }
+    if (reps_text) {
+        char *end = NULL;
+        errno = 0;
+        const long n = strtol(reps_text, &end, 0);
+        if (errno == ERANGE || end == reps_text || *end || n < 1 || n > (long)FASTF_MAX_SEEDS) {
+            fprintf(stderr, "error: option `--reps` expects an integer from 1 to %u\n", FASTF_MAX_SEEDS);
+            return 1;
+        }
+        if (fastf_reps_seeds(out->seed, (uint64_t)n, out->seeds, FASTF_MAX_SEEDS, &out->n_seeds)) { fprintf(stderr, "error: option %s\n", fastf_last_error()); return 1; }
     }
     return 0;
 }

@@ -25,15 +25,16 @@ enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys w
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
 enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_WORDS_ = 192 };   /* SM_UROWS: --cells, K3u's row count */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells; } res_times_t;   /* genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files) */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps; uint32_t opens, relays; } res_times_t;   /* genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
 
-/* the lists of every cell rate, and ONE dictionary for the records: the first rate's, with the barcodes of the others registered
- * in it — a key then means the same string whichever rate's table it is looked up in.  keys[i][k]: key of cell k + 1 at rate i */
+/* the lists of every (cell rate, seed) pair, and ONE dictionary for the records: the first pair's, with the barcodes of the others
+ * registered in it — a key then means the same string whichever pair's table it is looked up in.  keys[i][k]: key of cell k + 1 of
+ * pair i.  L[i].mt_skip: the draws that pair's own SampleInt consumed of init_genrand(seeds[i]) */
 typedef struct { uint32_t n; fastf_lists_t *L; uint64_t **keys; } res_lists_t;
-int  fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c, uint32_t seed, res_lists_t *out) FASTF_HIDDEN;
+int  fastf_res_lists_load(const char *barcodes, const char *features, const float *rates_cell, const uint32_t *seeds, uint32_t n_pairs, res_lists_t *out) FASTF_HIDDEN;
 void fastf_res_lists_free(res_lists_t *l) FASTF_HIDDEN;
 
 /* the packed records (24 bytes each) in device memory */
@@ -45,8 +46,14 @@ typedef struct {
 int  fastf_res_decode(const char *verb, const char *bam_file, const fastf_lists_t *L0, int device, resident_t *R) FASTF_HIDDEN;
 void fastf_res_free(resident_t *R) FASTF_HIDDEN;
 
-/* one cell rate: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point), the buffers
- * of a point */
+/* one (cell rate, seed) pair: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point),
+ * the buffers of a point.  The buffers outlive the pair: a run keeps ONE res_rate_t, zeroed before its first open, and every later
+ * fastf_res_rate_open on it ends the pair before (its engine) and takes its buffers over — each is allocated again only where the
+ * new pair needs more (have: the bytes held).  The per-cell arrays and the cell scratch inside the blocked copy are sized for
+ * max_cells, the most cells any pair of the run samples, which the lists tell before the first open; the key pair and the rows
+ * follow the record count.  What is left to grow is a change from narrow to wide runs between cell rates.  blk_layout: the layout word (fastf_dev_block_layout) the
+ * blocked copy in d_blk was written for, 0: none — a pair whose engine has the same word runs K1a alone.  no_reuse (the verbs read
+ * FASTF_RES_NO_REUSE=1 once per run): fresh buffers and a fresh blocked copy for every pair (A/B runs, a test) */
 typedef struct {
     const char *verb; const resident_t *R; const fastf_lists_t *L; int device; float rate_cell; uint32_t seed;
     fastf_engine_t *e;
@@ -61,6 +68,9 @@ typedef struct {
      * arrays (RES_CELLS_HIST_BYTES, then n_cells u32 each), else NULL */
     int cells, sorted_full; uint64_t *sorted, *sorted_other;
     void *d_cellsum; uint64_t *h_hist; uint32_t *h_rpc, *h_npc, *h_spc;
+    uint64_t blk_layout;
+    uint32_t max_cells; int no_reuse;    /* set by the caller before the first open: the most cells any pair of the run samples (0: unknown); FASTF_RES_NO_REUSE */
+    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist; } have;
 } res_rate_t;
 #define RES_CELLS_HIST_BYTES 512u
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
@@ -90,14 +100,14 @@ int fastf_res_tsv_close(res_tsv_t *t, int ok) FASTF_HIDDEN;
 /* --genes of a verb: <out_dir>/<verb>_genes.tsv (one row per point, through .partial), <out_dir>/<verb>_gene_cells.tsv.gz (the cells
  * per gene of every point, written by a close with ok != 0) and <point dir>/genes.tsv.gz.  on == 0: every call does nothing */
 typedef struct {
-    int on; const char *verb; char out_dir[4096];
+    int on, no_grid; const char *verb; char out_dir[4096];   /* no_grid: a replicate run — no <verb>_gene_cells.tsv.gz, no cells[] kept */
     res_tsv_t tsv;
     uint32_t n_features, n_points, max_points;
     char **feat_id;                      /* copies: the lists of the first point */
     uint32_t *cells;                     /* [max_points][n_features] */
     char (*names)[64];                   /* the point directory names */
 } res_genes_t;
-int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points) FASTF_HIDDEN;
+int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points, int no_grid) FASTF_HIDDEN;
 /* one point: `row` (fastf_genes_summary_row) into the table, cells[] kept for the grid file, and — dir != NULL — dir/genes.tsv.gz */
 int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *point_name, const char *dir, const char *row,
                           const uint32_t *cells, const uint64_t *umis) FASTF_HIDDEN;
@@ -112,16 +122,57 @@ int fastf_res_cells_open(res_cells_t *C, int on, const char *verb, const char *o
 int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row) FASTF_HIDDEN;
 int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells and ONE list option of the verb's own (list_short /
- * list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
- * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists). */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell; } res_args_t;   /* cells: the -c list; per_cell: --cells */
+/* replicate runs (--seeds, --reps; fastf_sweep_reps, fastf_cap_reps): <verb>_reps.tsv, and with --genes <verb>_genes_reps.tsv and
+ * <verb>_gene_reps.tsv.gz.  The metrics of the cell rate in work are kept per (list value j, seed k) until its last seed is done;
+ * the per-gene accumulators of that cell rate live on the device (d_acc: [n_list][3][n_features] u64, fastf_dev_gene_reps_add behind
+ * every point) and come to the host once per grid point, in fastf_res_reps_rate_end; on the point-by-point path (no device arrays)
+ * the host twin adds into h_acc directly.  on == 0: every call does nothing */
+typedef struct {
+    int on, genes, device; const char *verb; char out_dir[4096];
+    uint32_t n_seeds, n_list, n_rates, rate_at; const uint32_t *seeds;
+    res_tsv_t tsv, gtsv;
+    double *m;                           /* [n_list][n_seeds][FASTF_REPS_METRICS] */
+    uint32_t *n_cells, *gdet;            /* [n_list][n_seeds]: the sampled cells, the genes detected */
+    uint8_t *seen;                       /* [n_list][n_seeds] */
+    uint32_t n_features; char **feat_id;
+    void *d_acc; uint64_t *h_acc;        /* h_acc: [n_rates * n_list][3][n_features] */
+} res_reps_t;
+int fastf_res_reps_open(res_reps_t *P, int on, const char *verb, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
+                        uint32_t n_list, int genes, int device, const char *header, const char *genes_header) FASTF_HIDDEN;
+/* a cell rate begins: the names of the features (first call), the accumulators cleared; on_device: d_acc is used */
+int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_device) FASTF_HIDDEN;
+/* point (list value j, seed k) of the cell rate in work: its metrics; with --genes its per-gene array — S != NULL: S->d_cpg on the
+ * device, right behind the point's fastf_res_point_run; else cells_per_gene on the host */
+int fastf_res_reps_point(res_reps_t *P, uint32_t j, uint32_t k, uint32_t n_cells, const double *metrics) FASTF_HIDDEN;
+int fastf_res_reps_genes(res_reps_t *P, res_rate_t *S, uint32_t j, uint32_t k, const uint32_t *cells_per_gene, uint32_t n_features) FASTF_HIDDEN;
+/* the last seed of the cell rate is done: its rows; rates_depth or caps names the verb's list (the other NULL) */
+int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_depth, const uint64_t *caps, res_times_t *T) FASTF_HIDDEN;
+/* ok != 0: <verb>_gene_reps.tsv.gz (its columns named from the grid: rates_cell and ONE of rates_depth / caps), then the tables
+ * renamed; otherwise nothing of them is left */
+int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, const float *rates_depth, const uint64_t *caps) FASTF_HIDDEN;
+int fastf_res_reps_close(res_reps_t *P, int ok) FASTF_HIDDEN;   /* ok == 0 only */
+/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,reps,genes_reps}.tsv and
+ * <verb>_gene_reps.tsv.gz is left */
+void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_HIDDEN;
+/* the most cells any pair of the lists samples */
+uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
+
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --seeds --reps and ONE list option of the verb's own
+ * (list_short / list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
+ * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
+ * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given */
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell;
+                 uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;
 int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;
 
-/* sweep_cmds.c: the columns of a summary row from `seed` on (no newline) */
+/* sweep_cmds.c: the columns of a summary row from `seed` on (no newline); metrics != NULL: the FASTF_REPS_METRICS numbers a replicate
+ * table takes from the row (sampled_reads, sampled_valid_reads, nnz, umis, saturation, the two medians) as the row printed them */
 int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
-                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap) FASTF_HIDDEN;
+                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
+
+/* sweep_cmds.c: the seeds of a _reps call — 1 .. FASTF_MAX_SEEDS distinct values */
+int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds) FASTF_HIDDEN;
 
 #endif

@@ -1,8 +1,9 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed] [--summary-only] [--genes] [--cells]; -d accepted and ignored, -u refused
- *   fastf_sweep()  the same in process
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells]; -d accepted
+ *                  and ignored, -u refused
+ *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
  * writes for that point — and one row of <out>/sweep.tsv.
  *
@@ -17,6 +18,10 @@
  * --cells: behind every point its keys sorted fully, K3u's rows and their reduction along the cell axis and into the copy-number
  * histogram (fastf_res_point_cells: fastf_dev_umi_rows, fastf_dev_copy_summary) into sweep_cells.tsv and the point's cells.tsv.gz;
  * resident form only — a job outside it is refused with the flag.
+ * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
+ * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
+ * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
+ * arrays are summed across the seeds on the device (fastf_dev_gene_reps_add).
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -143,7 +148,7 @@ int fastf_sweep_cells_from_coo(const fastf_coo_t *coo, uint32_t n_cells, uint64_
 
 /* the columns from `seed` on (no newline): shared with cap.tsv */
 int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
-                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
+                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics)
 {
     if (!counters || !buf || (n_cells && (!umis_per_cell || !genes_per_cell))) return sw_err("null argument");
     uint64_t *tmp = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *tmp);
@@ -154,19 +159,28 @@ int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz,
     const double med_g = median_u64(tmp, n_cells);
     free(tmp);
     const double sat = counters[2] ? 1.0 - (double)umis / (double)counters[2] : 0.0;
+    if (metrics) {
+        metrics[0] = (double)counters[1]; metrics[1] = (double)counters[2]; metrics[2] = (double)nnz; metrics[3] = (double)umis;
+        metrics[4] = sat; metrics[5] = med_u; metrics[6] = med_g;
+    }
     const int n = snprintf(buf, cap, "%u\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\t%.1f\t%.1f", seed, n_cells, (unsigned long long)counters[0],
                            (unsigned long long)counters[1], (unsigned long long)counters[2], (unsigned long long)nnz, (unsigned long long)umis, sat, med_u, med_g);
     return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
 }
 
-/* one row of sweep.tsv (with its newline) */
+/* one row of sweep.tsv (with its newline); metrics: fastf_summary_tail_ */
+static int summary_row_(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                        const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics)
+{
+    char tail[400];
+    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail, metrics)) return 1;
+    const int n = snprintf(buf, cap, "%.3f\t%.3f\t%s\n", (double)rate_cell, (double)rate_depth, tail);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
 int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                             const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
 {
-    char tail[400];
-    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail)) return 1;
-    const int n = snprintf(buf, cap, "%.3f\t%.3f\t%s\n", (double)rate_cell, (double)rate_depth, tail);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+    return summary_row_(rate_cell, rate_depth, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, buf, cap, NULL);
 }
 
 /* ------------------------------------------------------------------ */
@@ -324,18 +338,23 @@ done:
 }
 
 static int sweep_point_by_point(const char *bam, const char *out_dir, const char *barcodes, const char *features,
-                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, res_tsv_t *tsv,
-                                res_genes_t *G)
+                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int summary_only,
+                                res_tsv_t *tsv, res_genes_t *G, res_reps_t *P)
 {
     const int saved_u = _umi_copies_flag;
     _umi_copies_flag = 0;
     int rc = 1;
     fastf_lists_t GL; memset(&GL, 0, sizeof GL);           /* --genes: the feature names (bam2db() loads its own lists) */
-    if (G->on && fastf_lists_load(barcodes, features, 1.0f, seed, &GL)) goto done;
-    for (uint32_t i = 0; i < n_c; i++)
+    if (G->on && fastf_lists_load(barcodes, features, 1.0f, seeds[0], &GL)) goto done;
+    for (uint32_t i = 0; i < n_c; i++) {
+      if (fastf_res_reps_rate_begin(P, &GL, 0)) goto done;
+      for (uint32_t k = 0; k < n_s; k++)
         for (uint32_t j = 0; j < n_r; j++) {
-            char name[64], dir[4096], path[4200];
-            if (fastf_sweep_point_dir(rc_list[i], rd_list[j], name, sizeof name)) goto done;
+            char base[64], name[96], dir[4096], path[4200];
+            const uint32_t seed = seeds[k];
+            double metrics[FASTF_REPS_METRICS];
+            if (fastf_sweep_point_dir(rc_list[i], rd_list[j], base, sizeof base)) goto done;
+            if (P->on ? fastf_reps_point_dir(base, seed, name, sizeof name) : (snprintf(name, sizeof name, "%s", base), 0)) goto done;
             if (summary_only) snprintf(dir, sizeof dir, "%s/.%s.partial", out_dir, name);      /* (removed again below) */
             else snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_make_dir(dir)) goto done;
@@ -355,7 +374,8 @@ static int sweep_point_by_point(const char *bam, const char *out_dir, const char
             uint64_t umis = 0;
             char row[512];
             prc = !upc || !gpc || fastf_sweep_cells_from_coo(&coo, n_cells, upc, gpc, &umis) ||
-                  fastf_sweep_summary_row(rc_list[i], rd_list[j], seed, counters, coo.nnz, umis, upc, gpc, n_cells, row, sizeof row);
+                  summary_row_(rc_list[i], rd_list[j], seed, counters, coo.nnz, umis, upc, gpc, n_cells, row, sizeof row, metrics) ||
+                  fastf_res_reps_point(P, j, k, n_cells, metrics);
             free(upc); free(gpc);
             if (!prc && G->on) {
                 char grow[256];
@@ -364,13 +384,16 @@ static int sweep_point_by_point(const char *bam, const char *out_dir, const char
                 prc = !cpg || !upg || (n_features != GL.n_features && sw_err("%s names %u features, the list has %zu", name, n_features, GL.n_features)) ||
                       fastf_sweep_genes_from_coo(&coo, n_features, cpg, upg) ||
                       fastf_genes_summary_row(rc_list[i], rd_list[j], 0, seed, cpg, upg, n_features, grow, sizeof grow) ||
-                      fastf_res_genes_point(G, &GL, name, summary_only ? NULL : dir, grow, cpg, upg);
+                      fastf_res_genes_point(G, &GL, name, summary_only ? NULL : dir, grow, cpg, upg) ||
+                      fastf_res_reps_genes(P, NULL, j, k, cpg, n_features);
                 free(cpg); free(upg);
             }
             free(rows);
             if (prc) goto done;
             fputs(row, tsv->f);
         }
+      if (fastf_res_reps_rate_end(P, rc_list[i], rd_list, NULL, NULL)) goto done;
+    }
     rc = 0;
 done:
     if (G->on) fastf_lists_free(&GL);
@@ -381,107 +404,134 @@ done:
 /* ------------------------------------------------------------------ */
 /* resident form (the pipeline itself: resident.c)                     */
 /* ------------------------------------------------------------------ */
-/* one cell rate: the engine, the records in its layout, K1a, the planes, then every depth rate */
-static int sweep_cell_rate(const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
+/* one (cell rate, seed) pair — seed k of a replicate run (P->on) — on the run's res_rate_t: the engine, the records in its layout,
+ * K1a, the planes, then every depth rate */
+static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           res_genes_t *G, res_cells_t *C, res_times_t *T)
+                           res_genes_t *G, res_cells_t *C, res_reps_t *P, uint32_t k, res_times_t *T)
 {
     int rc = RES_FAIL;
-    res_rate_t S;
     void *d_planes = NULL;
     uint64_t *thr = (uint64_t *)malloc(n_r * sizeof *thr);
-    if (!thr) { sw_err("out of memory"); memset(&S, 0, sizeof S); goto done; }
-    if ((rc = fastf_res_rate_open(&S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
+    if (!thr) { sw_err("out of memory"); goto done; }
+    if ((rc = fastf_res_rate_open(S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
-    const uint64_t H = S.H;
+    const uint64_t H = S->H;
     double tt = fastf_res_now();
 
     /* the decision planes: the draw stream once, every threshold in the same pass */
     const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
     if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_r * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_r * plane_words * 4)) goto done;
     for (uint32_t j = 0; j < n_r; j++) thr[j] = fastf_draw_threshold(rd_list[j]);
-    if (fastf_dev_mt_decisions_multi(S.e, seed, L->mt_skip, H, thr, n_r, (uint32_t *)d_planes, plane_words, NULL)) goto done;
+    if (fastf_dev_mt_decisions_multi(S->e, seed, L->mt_skip, H, thr, n_r, (uint32_t *)d_planes, plane_words, NULL)) goto done;
     T->planes += fastf_res_now() - tt;
 
     for (uint32_t j = 0; j < n_r; j++) {
-        char name[64], dir[4096], row[512];
+        char base[64], name[96], dir[4096], row[512];
         uint64_t counters[3], nnz = 0;
-        if (fastf_sweep_point_dir(rate_cell, rd_list[j], name, sizeof name)) goto done;
-        const int prc = fastf_res_point_run(&S, (const uint32_t *)d_planes + (size_t)j * plane_words, name, counters, &nnz, T);
+        double metrics[FASTF_REPS_METRICS];
+        if (fastf_sweep_point_dir(rate_cell, rd_list[j], base, sizeof base)) goto done;
+        if (P->on ? fastf_reps_point_dir(base, seed, name, sizeof name) : (snprintf(name, sizeof name, "%s", base), 0)) goto done;
+        const int prc = fastf_res_point_run(S, (const uint32_t *)d_planes + (size_t)j * plane_words, name, counters, &nnz, T);
         if (prc != RES_OK) { rc = prc; goto done; }
         tt = fastf_res_now();
-        if (fastf_sweep_summary_row(rate_cell, rd_list[j], seed, counters, nnz, S.h_upc[S.n_cells], S.h_upc, S.h_gpc, S.n_cells, row, sizeof row)) goto done;
+        if (summary_row_(rate_cell, rd_list[j], seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, row, sizeof row, metrics) ||
+            fastf_res_reps_point(P, j, k, S->n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
+        if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
+            tt = fastf_res_now();
+            if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
+            T->reps += fastf_res_now() - tt;
+        }
         if (!summary_only) {
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (fastf_res_point_write(&S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
+            if (fastf_res_point_write(S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
         }
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
-            if (fastf_genes_summary_row(rate_cell, rd_list[j], 0, seed, S.h_cpg, S.h_upg, S.n_features, grow, sizeof grow) ||
-                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S.h_cpg, S.h_upg)) goto done;
+            if (fastf_genes_summary_row(rate_cell, rd_list[j], 0, seed, S->h_cpg, S->h_upg, S->n_features, grow, sizeof grow) ||
+                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S->h_cpg, S->h_upg)) goto done;
             T->genes += fastf_res_now() - tt;
         }
         if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
             char crow[1024];
-            if (fastf_res_point_cells(&S, name, T)) goto done;
+            if (fastf_res_point_cells(S, name, T)) goto done;
             tt = fastf_res_now();
-            if (fastf_cells_summary_row(rate_cell, rd_list[j], 0, seed, S.h_rpc, S.h_npc, S.h_spc, S.n_cells, S.h_hist, crow, sizeof crow) ||
-                fastf_res_cells_point(C, &S, summary_only ? NULL : dir, crow)) goto done;
+            if (fastf_cells_summary_row(rate_cell, rd_list[j], 0, seed, S->h_rpc, S->h_npc, S->h_spc, S->n_cells, S->h_hist, crow, sizeof crow) ||
+                fastf_res_cells_point(C, S, summary_only ? NULL : dir, crow)) goto done;
             T->cells += fastf_res_now() - tt;
         }
         fputs(row, tsv);
     }
     rc = RES_OK;
 done:
-    fastf_res_rate_close(&S);
     fastf_devmem_free(d_planes);
     free(thr);
     return rc;
 }
 
 static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
-                          const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                          res_genes_t *G, res_cells_t *C)
+                          const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int summary_only,
+                          int device, FILE *tsv, res_genes_t *G, res_cells_t *C, res_reps_t *P)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
     res_times_t T; memset(&T, 0, sizeof T);
     const double t0 = fastf_res_now();
     double tt = t0;
-    res_lists_t LL;
+    res_lists_t LL; memset(&LL, 0, sizeof LL);
     resident_t R; memset(&R, 0, sizeof R);
-    if ((rc = fastf_res_lists_load(barcodes, features, rc_list, n_c, seed, &LL)) != RES_OK) goto done;
+    res_rate_t S; memset(&S, 0, sizeof S);
+    /* the (cell rate, seed) pairs: cell rates outer, the seeds as listed */
+    const uint32_t n_pairs = n_c * n_s;
+    float *pair_rate = (float *)malloc(n_pairs * sizeof *pair_rate);
+    uint32_t *pair_seed = (uint32_t *)malloc(n_pairs * sizeof *pair_seed);
+    if (!pair_rate || !pair_seed) { sw_err("out of memory"); goto done; }
+    for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = rc_list[i]; pair_seed[i * n_s + k] = seeds[k]; }
+    if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
+    S.max_cells = fastf_res_lists_max_cells(&LL);
+    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
     T.decode = fastf_res_now() - tt;
-    printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
+    if (P->on) printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points x %u seeds\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r, n_s);
+    else printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
 
     for (uint32_t i = 0; i < n_c; i++) {
-        rc = sweep_cell_rate(&R, &LL.L[i], LL.keys[i], bam_file, out_dir, rc_list[i], rd_list, n_r, seed, summary_only, device, tsv, G, C, &T);
-        if (rc != RES_OK) goto done;
+        if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
+        for (uint32_t k = 0; k < n_s; k++) {
+            const uint32_t at = i * n_s + k;
+            rc = sweep_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], rd_list, n_r, seeds[k], summary_only, device, tsv, G, C, P, k, &T);
+            if (rc != RES_OK) goto done;
+        }
+        if (fastf_res_reps_rate_end(P, rc_list[i], rd_list, NULL, &T)) { rc = RES_FAIL; goto done; }
     }
     rc = RES_OK;
     if (prof)
         fprintf(stderr, "[sweep] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, planes %.3f s, "
                         "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
-                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r * n_s), T.summary, T.d2h, T.write, fastf_res_now() - t0);
+    if (prof && P->on) fprintf(stderr, "[sweep] replicates: %u (cell rate, seed) pairs opened in %.3f s (engines %.3f s, buffers + layout + K1a %.3f s), the blocked copy "
+                                       "laid out %u times; replicate tables and per-gene accumulation %.3f s\n", T.opens, T.engine + T.block_k1a, T.engine, T.block_k1a, T.relays, T.reps);
     if (prof && G->on) fprintf(stderr, "[sweep] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
     if (prof && C->on) fprintf(stderr, "[sweep] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
-                               T.cells_dev, T.cells_dev / (n_c * n_r), T.cells);
+                               T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
 done:
+    fastf_res_rate_close(&S);
     fastf_res_free(&R);
     fastf_res_lists_free(&LL);
+    free(pair_rate); free(pair_seed);
     return rc;
 }
 
 /* ------------------------------------------------------------------ */
 /* the command                                                         */
 /* ------------------------------------------------------------------ */
-int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
+/* reps != 0: a replicate run (fastf_sweep_reps) — the suffixed directories and the replicate tables, with one seed too */
+static int sweep_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags)
 {
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
@@ -498,11 +548,15 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
     res_genes_t G;
-    if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+    if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
+    res_reps_t P;
+    if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1;
+    }
 
-    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, dev0, tsv.f, &G, &C);
+    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &P);
     if (rc == RES_NOT_COVERED && cells) {
         /* (the per-cell rows come from the device's keys alone: bam2db() point by point has none.  Wide keys and a UMI length set
          * beyond the key are known before the first point; a UMI found too long among the records stops the point that meets it) */
@@ -515,14 +569,48 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
         /* (rows a resident attempt had written are of no use: the table starts again) */
         fastf_res_tsv_close(&tsv, 0);
         fastf_res_genes_close(&G, 0);
+        fastf_res_reps_close(&P, 0);
         if (tsv_open(&tsv, out_dir)) return 1;
-        if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r)) { fastf_res_tsv_close(&tsv, 0); return 1; }
-        rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seed, summary_only, &tsv, &G);
+        if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
+        if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
+            fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1;
+        }
+        rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, &tsv, &G, &P);
     }
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
     if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
-    if (rc) { char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_set_error_(keep); return 1; }
-    return fastf_res_tsv_close(&tsv, 1);
+    if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, rates_depth, NULL)) rc = 1;
+    if (rc) {
+        char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_reps_close(&P, 0);
+        if (reps) fastf_res_reps_unlink_tables(out_dir, "sweep");      /* (the tables that were already renamed go too: none is left) */
+        fastf_set_error_(keep);
+        return 1;
+    }
+    if (fastf_res_tsv_close(&tsv, 1)) { if (reps) fastf_res_reps_unlink_tables(out_dir, "sweep"); return 1; }
+    return 0;
+}
+
+int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
+{
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags);
+}
+
+/* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
+int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds)
+{
+    if (!seeds || n_seeds < 1 || n_seeds > FASTF_MAX_SEEDS) return sw_err("%s: a replicate run takes 1 to %u seeds", verb, FASTF_MAX_SEEDS);
+    for (uint32_t k = 0; k < n_seeds; k++)
+        for (uint32_t j = 0; j < k; j++) if (seeds[j] == seeds[k]) return sw_err("%s: seed %u is listed twice", verb, seeds[k]);
+    return 0;
+}
+
+int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
+{
+    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags);
 }
 
 static void usage_sweep(FILE *f)
@@ -542,7 +630,12 @@ static void usage_sweep(FILE *f)
             "    -s, --seed=<int>      seed for random number generator (default 926)\n"
             "        --summary-only    write sweep.tsv alone\n"
             "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n"
-            "        --cells           per-cell reads, saturation and UMI copy numbers too: sweep_cells.tsv and cells.tsv.gz per point\n");
+            "        --cells           per-cell reads, saturation and UMI copy numbers too: sweep_cells.tsv and cells.tsv.gz per point\n"
+            "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
+            "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
+            "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
+            "                          sweep_gene_reps.tsv.gz in place of sweep_gene_cells.tsv.gz); not with -s or --reps\n"
+            "        --reps=<int>      the same at the seeds s, s + 1, .. s + N - 1 (s: -s; N from 1 to 64)\n");
 }
 
 #define SWEEP_MAX_RATES 64
@@ -560,12 +653,16 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    if (fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0))) {
+    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0);
+    if (A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
+                  : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
     }
-    if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
+    if (A.genes && A.n_seeds) printf("sweep_genes.tsv, sweep_genes_reps.tsv and sweep_gene_reps.tsv.gz are generated.\n");
+    else if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
+    if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;
 }

@@ -1138,6 +1138,34 @@ extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_featu
     return 0;
 } FASTF_CATCH_INT
 
+// Replicate runs: d_cells_per_gene (what fastf_dev_gene_summary left, still on the device) added into the three u64[n_features]
+// accumulators of a grid point (gene_reps_kernel).  Nothing is cleared here: the caller zeroes the accumulators before the first seed.
+extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cells_per_gene, uint32_t n_features, uint64_t* d_detected,
+                                       uint64_t* d_sum, uint64_t* d_sumsq, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || (n_features && (!d_cells_per_gene || !d_detected || !d_sum || !d_sumsq)), "null argument");
+    if (!n_features) return 0;
+    const u32 grid = std::min<u32>((n_features + GENE_REPS_THREADS - 1) / GENE_REPS_THREADS, 4u * (u32)g_cu_count);
+    hipLaunchKernelGGL(gene_reps_kernel, dim3(grid), dim3(GENE_REPS_THREADS), 0, (hipStream_t)stream, d_cells_per_gene, n_features,
+                       (u64*)d_detected, (u64*)d_sum, (u64*)d_sumsq);
+    HIP_OK(hipGetLastError());
+    dbg_sync((hipStream_t)stream, "gene reps add");
+    return 0;
+} FASTF_CATCH_INT
+
+// the layout fastf_dev_block_records writes for this engine, as one word: 0 where the engine has no blocked form; two engines with
+// the same word lay the same records out in the same bytes (the K1a scratch slices aside, which fastf_dev_count_hits_blocked fills)
+extern "C" int fastf_dev_block_layout(const fastf_engine_t* e, uint64_t n, uint64_t* layout) FASTF_TRY {
+    if (!e || !layout) return set_err("null argument");
+    uint64_t bytes = 0;
+    *layout = 0;
+    if (fastf_dev_block_bytes(e, n, &bytes)) return 1;
+    if (!bytes) return 0;
+    *layout = 1ull | ((u64)e->narrow << 1) | ((u64)e->cell16 << 2);
+    // (narrow runs fold the family constant and the UMI field of the key layout into their words: block_records_kernel<true>)
+    if (e->narrow) *layout |= ((u64)e->lds_genes.family << 8) | ((u64)e->L.umi_bits << 40) | ((u64)e->L.umi_max_bytes << 48);
+    return 0;
+} FASTF_CATCH_INT
+
 // --cells: the -u rows of fastf_dev_umi_rows on this engine reduced along the cell axis and into the copy-number histogram
 // (copy_summary_kernel).  The cell field and the non-NULL flag are read from the engine's own key layout.  All four outputs are
 // cleared here first; *d_nrows rows are read.  Every per-cell number is below 2^32 (a number of records).
@@ -1715,7 +1743,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

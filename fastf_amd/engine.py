@@ -387,6 +387,11 @@ class Engine:
         The sum of all counts is below 2^32"""
         check(self._L.fastf_dev_gene_summary(self._h, d_feature, d_count, d_nnz, n_features, d_cells_per_gene, d_umis_per_gene, stream))
 
+    def dev_gene_reps_add(self, d_cells_per_gene, n_features, d_detected, d_sum, d_sumsq, stream=0):
+        """replicate runs: the cells per gene of one seed's point (u32[n_features], what dev_gene_summary left) added into the three
+        u64[n_features] accumulators of its grid point: detected += (cells >= 1), sum += cells, sumsq += cells^2; nothing is cleared"""
+        check(self._L.fastf_dev_gene_reps_add(self._h, d_cells_per_gene, n_features, d_detected, d_sum, d_sumsq, stream))
+
     def dev_copy_summary(self, d_ukeys, d_ncopy, d_nrows, n_cells, d_reads_per_cell, d_null_reads_per_cell, d_single_per_cell, d_hist, stream=0):
         """the rows of dev_umi_rows on this engine -> per cell (slot c - 1, u32, n_cells entries each) the sum of n_copy over all its
         rows, that sum over its NULL-blob rows and its non-NULL rows with n_copy == 1; d_hist (u64, COPY_BINS + 1 entries): the

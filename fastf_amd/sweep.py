@@ -40,6 +40,100 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
+def _seeds(seeds):
+    a = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
+    return a, a.ctypes.data
+
+
+def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
+               cells: bool = False):
+    """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
+    out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
+    genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
+    rc, prc = _floats(rates_cell)
+    rd, prd = _floats(rates_depth)
+    sd, psd = _seeds(seeds)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
+                                           (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+    return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
+
+
+REPS_METRICS = ("sampled_reads", "sampled_valid_reads", "nnz", "umis", "saturation", "median_umis_per_cell", "median_genes_per_cell")
+_STAT4 = lambda m: tuple("%s_%s" % (m, t) for t in ("mean", "sd", "min", "max"))  # noqa: E731
+REPS_TAIL_COLUMNS = ("n_reps", "n_cells") + sum((_STAT4(m) for m in REPS_METRICS), ())
+REPS_COLUMNS = ("rate_cell", "rate_depth") + REPS_TAIL_COLUMNS
+GENES_REPS_TAIL_COLUMNS = ("n_reps",) + _STAT4("genes_detected") + ("genes_in_all_reps", "genes_in_any_rep")
+GENES_REPS_COLUMNS = ("rate_cell", "rate_depth") + GENES_REPS_TAIL_COLUMNS
+
+
+def read_reps_table(path, columns=REPS_COLUMNS):
+    """the rows of sweep_reps.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_genes_reps_table(path, columns=GENES_REPS_COLUMNS):
+    """the rows of sweep_genes_reps.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def parse_seeds(text: str):
+    """a comma-separated list of seeds as the command reads --seeds; raises FastfError on what it refuses"""
+    out = np.zeros(64, dtype=np.uint32)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().fastf_parse_seeds(text.encode(), out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def reps_seeds(first: int, n_reps: int):
+    """the seeds of --reps n_reps with -s first; raises FastfError where they would wrap past 2^32 - 1"""
+    out = np.zeros(64, dtype=np.uint32)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().fastf_reps_seeds(int(first) % (1 << 32), int(n_reps), out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def reps_point_dir(point_name: str, seed: int) -> str:
+    buf = C.create_string_buffer(96)
+    _lib.check(_lib.lib().fastf_reps_point_dir(point_name.encode(), int(seed) % (1 << 32), buf, len(buf)))
+    return buf.value.decode()
+
+
+def reps_header() -> str:
+    return _lib.lib().fastf_sweep_reps_header().decode()
+
+
+def genes_reps_header() -> str:
+    return _lib.lib().fastf_sweep_genes_reps_header().decode()
+
+
+def reps_summary_row(rate_cell, rate_depth, n_cells, metrics, reads_per_cell: int = 0) -> str:
+    """one row of sweep_reps.tsv (with its newline) from metrics[k][m] (replicate k, metric m of REPS_METRICS);
+    reads_per_cell >= 1: a row of cap_reps.tsv"""
+    m = np.ascontiguousarray(metrics, dtype=np.float64).reshape(-1, len(REPS_METRICS))
+    buf = C.create_string_buffer(2048)
+    _lib.check(_lib.lib().fastf_reps_summary_row(float(rate_cell), float(rate_depth), int(reads_per_cell), int(n_cells), m.ctypes.data, len(m), buf, len(buf)))
+    return buf.value.decode()
+
+
+def genes_reps_row(rate_cell, rate_depth, genes_detected, reps_detected, reads_per_cell: int = 0) -> str:
+    """one row of sweep_genes_reps.tsv (with its newline); reads_per_cell >= 1: a row of cap_genes_reps.tsv"""
+    gd = np.ascontiguousarray(genes_detected, dtype=np.uint32)
+    rdt = np.ascontiguousarray(reps_detected, dtype=np.uint64)
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_genes_reps_row(float(rate_cell), float(rate_depth), int(reads_per_cell), gd.ctypes.data, len(gd), rdt.ctypes.data, len(rdt),
+                                               buf, len(buf)))
+    return buf.value.decode()
+
+
+def gene_reps_add_host(cells_per_gene, detected, total, sumsq):
+    """the host form of Engine.dev_gene_reps_add: the three u64 arrays are added to in place"""
+    c = np.ascontiguousarray(cells_per_gene, dtype=np.uint32)
+    for a in (detected, total, sumsq):
+        assert a.dtype == np.uint64 and a.flags.c_contiguous and len(a) == len(c)
+    _lib.check(_lib.lib().fastf_gene_reps_add_host(c.ctypes.data, len(c), detected.ctypes.data, total.ctypes.data, sumsq.ctypes.data))
+
+
 def read_table(path):
     lines = open(path).read().split("\n")
     assert lines[0].split("\t") == list(COLUMNS) and lines[-1] == ""

@@ -200,6 +200,54 @@ int fastf_cap_thresholds(const uint32_t *hits, uint32_t n_cells, uint64_t cap, u
 /* the realised fraction of a point as the matrix header carries it */
 float fastf_cap_realised(uint64_t sampled, uint64_t hits);
 
+/* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
+ * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
+ *   point directories   <point name>_s<seed> (c0.500_r0.100_s927): the bytes `bam2db -s <seed>` (cap: `cap -s <seed>`) writes
+ *   <verb>.tsv          today's header and rows, one per (cell rate, seed, depth | cap): cell rates outer, then the seeds as listed,
+ *                       then the verb's list
+ *   <verb>_reps.tsv     one row per grid point in grid order: rate_cell, rate_depth | reads_per_cell, n_reps, n_cells (the same at
+ *                       every seed — the sample size depends on the rate alone; a run whose replicates disagree fails), then
+ *                       <m>_mean <m>_sd <m>_min <m>_max for m = sampled_reads, sampled_valid_reads, nnz, umis, saturation,
+ *                       median_umis_per_cell, median_genes_per_cell.  Mean and sd in double, two passes over the seeds in list
+ *                       order, sd the sample sd (divisor n - 1), both %.6f, sd `NA` at one replicate; min and max in the
+ *                       metric's own format of <verb>.tsv
+ *   --genes             <verb>_genes.tsv one row per (point, seed), genes.tsv.gz per point directory; NO <verb>_gene_cells.tsv.gz;
+ *                       <verb>_gene_reps.tsv.gz: header `feature` and per grid point p `<p>:reps_detected <p>:cells_sum
+ *                       <p>:cells_sumsq`, one row per feature — the seeds at which at least one cell detects the gene, the sum and
+ *                       the sum of squares over the seeds of the cells that detect it (exact u64; summed on the device:
+ *                       fastf_dev_gene_reps_add); <verb>_genes_reps.tsv one row per grid point: rate_cell, rate_depth |
+ *                       reads_per_cell, n_reps, genes_detected_mean _sd _min _max (the rule above), genes_in_all_reps,
+ *                       genes_in_any_rep
+ *   --cells             <verb>_cells.tsv one row per (point, seed), the seed in its third column as ever; cells.tsv.gz per point directory
+ * Every table goes through .partial; on failure none is left.  sweep runs jobs outside the resident form point by point and seed by
+ * seed through bam2db() into the same names; --cells and cap refuse them as without replicates. --- */
+#define FASTF_MAX_SEEDS 64u
+/* a comma-separated list of 1 .. FASTF_MAX_SEEDS seeds, each by the rule of -s (strtol(.., 0): decimal, 0x.., 0..; the value taken
+ * modulo 2^32).  Refused, the message naming --seeds: an empty list or element, trailing characters, out of range, a value twice,
+ * more than `cap` (at most FASTF_MAX_SEEDS) values */
+int fastf_parse_seeds(const char *text, uint32_t *out, uint32_t cap, uint32_t *n_out);
+/* --reps N from -s first: first, first + 1, .. first + N - 1; refused: N outside 1 .. FASTF_MAX_SEEDS, a run that wraps past 2^32 - 1 */
+int fastf_reps_seeds(uint32_t first, uint64_t n_reps, uint32_t *out, uint32_t cap, uint32_t *n_out);
+/* the arguments of fastf_sweep / fastf_cap with a list of 1 .. FASTF_MAX_SEEDS distinct seeds in place of `seed` */
+int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags);
+int fastf_cap_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                   const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags);
+/* the host pieces: `<point>_s<seed>`; the header lines; one row of <verb>_reps.tsv (with its newline) from the metrics of the
+ * replicates — metrics[k * FASTF_REPS_METRICS + m], m in the order above, the integers as doubles (exact below 2^53);
+ * reads_per_cell == 0: a sweep row, >= 1: a cap row; one row of <verb>_genes_reps.tsv; the host form of fastf_dev_gene_reps_add */
+#define FASTF_REPS_METRICS 7u
+int fastf_reps_point_dir(const char *point_name, uint32_t seed, char *buf, size_t cap);
+const char *fastf_sweep_reps_header(void);
+const char *fastf_cap_reps_header(void);
+const char *fastf_sweep_genes_reps_header(void);
+const char *fastf_cap_genes_reps_header(void);
+int fastf_reps_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t n_cells, const double *metrics,
+                           uint32_t n_reps, char *buf, size_t cap);
+int fastf_genes_reps_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, const uint32_t *genes_detected, uint32_t n_reps,
+                         const uint64_t *reps_detected, uint32_t n_features, char *buf, size_t cap);
+int fastf_gene_reps_add_host(const uint32_t *cells_per_gene, uint32_t n_features, uint64_t *detected, uint64_t *sum, uint64_t *sumsq);
+
 const char *fastf_last_error(void);
 const char *fastf_version(void);
 
@@ -509,6 +557,15 @@ int fastf_dev_cell_summary(fastf_engine_t *e, const uint32_t *d_cell, const uint
  * counter in LDS (FASTF_GENE_LDS_RANGES=0: global atomics always).  d_feature / d_count may be NULL when there are no rows. */
 int fastf_dev_gene_summary(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_count, const uint64_t *d_nnz,
                            uint32_t n_features, uint32_t *d_cells_per_gene, uint64_t *d_umis_per_gene, void *stream);
+/* Replicate runs: d_cells_per_gene — what fastf_dev_gene_summary left, n_features entries on the device — added into the three
+ * u64[n_features] accumulators of a grid point on `stream`: d_detected[g] += (cells[g] >= 1), d_sum[g] += cells[g], d_sumsq[g] +=
+ * cells[g]^2.  Nothing is cleared: the caller zeroes the accumulators before the first seed.  Nothing behind the arrays is written. */
+int fastf_dev_gene_reps_add(fastf_engine_t *e, const uint32_t *d_cells_per_gene, uint32_t n_features, uint64_t *d_detected,
+                            uint64_t *d_sum, uint64_t *d_sumsq, void *stream);
+/* the layout fastf_dev_block_records writes for this engine over n records, as one word (0: no blocked form): engines with the same
+ * word write the same bytes for the same records — narrow or wide runs, the width of the cell scratch, and for narrow runs the
+ * constants folded into their words — so a blocked copy made for one serves the other, K1a's scratch slices aside */
+int fastf_dev_block_layout(const fastf_engine_t *e, uint64_t n, uint64_t *layout);
 /* Per-cell reads and the copy-number histogram of -u rows: the output of fastf_dev_umi_rows on this engine — *d_nrows rows of
  * d_ukeys (ascending, so the rows of one cell are neighbours) and d_ncopy.  The cell of a row and whether its blob is NULL are read
  * from the engine's own key layout.  d_reads_per_cell[c - 1] = the sum of n_copy over all rows of cell c (NULL rows included),
