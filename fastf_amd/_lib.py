@@ -120,6 +120,10 @@ ABI_SYMBOLS = [
     "fastf_parse_seeds", "fastf_reps_seeds", "fastf_sweep_reps", "fastf_cap_reps", "fastf_reps_point_dir", "fastf_sweep_reps_header",
     "fastf_cap_reps_header", "fastf_sweep_genes_reps_header", "fastf_cap_genes_reps_header", "fastf_reps_summary_row", "fastf_genes_reps_row",
     "fastf_gene_reps_add_host", "fastf_dev_gene_reps_add", "fastf_dev_block_layout",
+    # level
+    "fastf_level", "fastf_level_reps", "fastf_level_parse_caps", "fastf_level_check_grid", "fastf_level_point_dir", "fastf_level_header",
+    "fastf_level_genes_header", "fastf_level_cells_header", "fastf_level_reps_header", "fastf_level_genes_reps_header", "fastf_level_summary_row",
+    "fastf_dev_level_init", "fastf_dev_level_step",
 ]
 
 
@@ -321,6 +325,16 @@ def lib():
     L.fastf_gene_reps_add_host.argtypes = [vp, u32, vp, vp, vp]
     L.fastf_dev_gene_reps_add.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     L.fastf_dev_block_layout.argtypes = [vp, u64, C.POINTER(u64)]
+    L.fastf_level.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
+    L.fastf_level_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32]
+    L.fastf_level_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
+    L.fastf_level_check_grid.argtypes = [fp, u32, vp, u32]
+    L.fastf_level_point_dir.argtypes = [C.c_float, u64, C.c_char_p, sz]
+    for name in ("fastf_level_header", "fastf_level_genes_header", "fastf_level_cells_header", "fastf_level_reps_header", "fastf_level_genes_reps_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_level_summary_row.argtypes = [C.c_float, u64, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, u64, u32, C.c_char_p, sz]
+    L.fastf_dev_level_init.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp]
+    L.fastf_dev_level_step.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

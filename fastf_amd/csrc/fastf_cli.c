@@ -1,5 +1,5 @@
 /* fastf_cli.c — `fastF` command line: dispatch table of the reference (main.c:404-443),
- * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract, sweep — bam2db over a grid of rates — and cap — every cell downsampled to at most N reads; the FASTQ ones: freq, filter). */
+ * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract, sweep — bam2db over a grid of rates — cap — every cell downsampled to at most N reads — and level — every cell downsampled to at most M UMIs; the FASTQ ones: freq, filter). */
 #include "fastf_amd.h"
 
 #include <stdio.h>
@@ -9,7 +9,7 @@
 
 extern int fastf_process_is_exiting_;
 struct cmd_struct { const char *cmd; int (*fn)(int, const char **); };
-static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"filter", cmd_filter}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract}, {"sweep", cmd_sweep}, {"cap", cmd_cap} };
+static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"filter", cmd_filter}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract}, {"sweep", cmd_sweep}, {"cap", cmd_cap}, {"level", cmd_level} };
 
 /* One command uses one GPU unless FASTF_DEVICES asks for more: hide the others from the HIP runtime before it loads,
  * so that its start-up (which opens every visible device) costs the same on an 8-GPU host as on a 1-GPU one.
@@ -34,7 +34,8 @@ int main(int argc, const char **argv)
                "    bam2db    BAM -> down-sampled, UMI-deduplicated gene x cell matrix (MI355X engine)\n"
                "    extract   frequencies of one BAM tag -> tag_summary.csv\n"
                "    sweep     bam2db over a grid of cell and depth rates from one decode of the BAM -> matrices + sweep.tsv\n"
-               "    cap       every cell downsampled to at most N reads, over a grid of cell rates and caps -> matrices + cap.tsv\n\n"
+               "    cap       every cell downsampled to at most N reads, over a grid of cell rates and caps -> matrices + cap.tsv\n"
+               "    level     every cell downsampled to at most M UMIs, exactly, over a grid of cell rates and UMI caps -> matrices + level.tsv\n\n"
                "(%s)\n", fastf_version());
         return argc < 2 ? 1 : 0;
     }

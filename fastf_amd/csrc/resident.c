@@ -153,6 +153,7 @@ void fastf_res_rate_close(res_rate_t *S)
     if (S->h_upg) fastf_pinned_free(S->h_upg);
     fastf_devmem_free(S->d_cellsum);
     if (S->h_hist) fastf_pinned_free(S->h_hist);
+    fastf_devmem_free(S->d_level);
     memset(S, 0, sizeof *S);
 }
 
@@ -271,6 +272,40 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
 /* ------------------------------------------------------------------ */
 /* one point                                                           */
 /* ------------------------------------------------------------------ */
+/* K1b on the plane, the group-only sort and the reduce: what a point and a search pass begin with */
+static int point_sort_reduce_(res_rate_t *S, const uint32_t *d_plane, uint64_t **src_out, uint64_t **other_out)
+{
+    const resident_t *R = S->R;
+    const uint64_t N = R->n;
+    fastf_engine_t *e = S->e;
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    if (fastf_devmem_zero(S->d_small, SM_HITS * 8)) return RES_FAIL;
+    if (fastf_dev_probe_pack(e, R->cb, S->blocked ? (const uint64_t *)S->d_blk : R->gx, R->umi, R->meta, N, d_plane, S->H, sm + SM_BASE,
+                             (uint64_t *)S->d_keys, S->key_slots, sm + SM_KEYS, sm + SM_CNT, S->kflags, NULL)) return RES_FAIL;
+    int in_tmp = 0;
+    if (fastf_dev_sort(e, (uint64_t *)S->d_keys, (uint64_t *)S->d_tmp, sm + SM_KEYS, N, S->key_bits, FASTF_SORT_SKIP_LOW | (S->segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) return RES_FAIL;
+    uint64_t *src = in_tmp ? (uint64_t *)S->d_tmp : (uint64_t *)S->d_keys, *other = in_tmp ? (uint64_t *)S->d_keys : (uint64_t *)S->d_tmp;
+    if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
+    *src_out = src; *other_out = other;
+    return RES_OK;
+}
+/* deep (cell, feature) groups (FASTF_ERR_RUN_TOO_LONG): sort fully and reduce again, as fastf_engine_finish does (every key is still
+ * there, permuted) */
+static int point_full_again_(res_rate_t *S, uint64_t **src_io, uint64_t **other_io)
+{
+    const uint64_t N = S->R->n;
+    fastf_engine_t *e = S->e;
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint64_t *src = *src_io, *other = *other_io;
+    int in_other = 0;
+    if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
+        fastf_dev_sort(e, src, other, sm + SM_KEYS, N, S->key_bits, 0, &in_other, NULL)) return RES_FAIL;
+    if (in_other) { uint64_t *t = src; src = other; other = t; }
+    if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
+    *src_io = src; *other_io = other;
+    return RES_OK;
+}
+
 int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t counters[3], uint64_t *nnz_out, res_times_t *T)
 {
     const resident_t *R = S->R;
@@ -279,23 +314,13 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
     uint64_t *const sm = (uint64_t *)S->d_small;
     uint32_t *const d_f = (uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
     double tt = fastf_res_now();
-    if (fastf_devmem_zero(S->d_small, SM_HITS * 8)) return RES_FAIL;
-    if (fastf_dev_probe_pack(e, R->cb, S->blocked ? (const uint64_t *)S->d_blk : R->gx, R->umi, R->meta, N, d_plane, S->H, sm + SM_BASE,
-                             (uint64_t *)S->d_keys, S->key_slots, sm + SM_KEYS, sm + SM_CNT, S->kflags, NULL)) return RES_FAIL;
-    int in_tmp = 0;
-    if (fastf_dev_sort(e, (uint64_t *)S->d_keys, (uint64_t *)S->d_tmp, sm + SM_KEYS, N, S->key_bits, FASTF_SORT_SKIP_LOW | (S->segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) return RES_FAIL;
-    uint64_t *src = in_tmp ? (uint64_t *)S->d_tmp : (uint64_t *)S->d_keys, *other = in_tmp ? (uint64_t *)S->d_keys : (uint64_t *)S->d_tmp;
-    if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
+    uint64_t *src = NULL, *other = NULL;
+    if (point_sort_reduce_(S, d_plane, &src, &other)) return RES_FAIL;
     uint64_t bits = 0;
     if (fastf_dev_error_bits(e, &bits)) return RES_FAIL;
     S->sorted_full = 0;
     if (bits & FASTF_ERR_RUN_TOO_LONG) {
-        /* deep (cell, feature) groups: sort fully and reduce again, as fastf_engine_finish does (every key is still there, permuted) */
-        int in_other = 0;
-        if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
-            fastf_dev_sort(e, src, other, sm + SM_KEYS, N, S->key_bits, 0, &in_other, NULL)) return RES_FAIL;
-        if (in_other) { uint64_t *t = src; src = other; other = t; }
-        if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_REDUCE_SEGMENTED, NULL) || fastf_dev_error_bits(e, &bits)) return RES_FAIL;
+        if (point_full_again_(S, &src, &other) || fastf_dev_error_bits(e, &bits)) return RES_FAIL;
         S->sorted_full = 1;
     }
     S->sorted = src; S->sorted_other = other;
@@ -319,6 +344,83 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
         if (S->n_features && (fastf_devmem_copy(S->h_cpg, S->d_cpg, (size_t)S->n_features * 4) || fastf_devmem_copy(S->h_upg, S->d_upg, (size_t)S->n_features * 8))) return RES_FAIL;
         T->genes += fastf_res_now() - tt;
     }
+    return RES_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* level: the state arrays, a search pass                              */
+/* ------------------------------------------------------------------ */
+int fastf_res_level_room(res_rate_t *S)
+{
+    const size_t room_cells = (S->max_cells > S->n_cells ? S->max_cells : S->n_cells) + (size_t)1;
+    if (dev_room(&S->d_level, &S->have.level, 4 * room_cells * 8, S->device))
+        return rs_err("%s: the search state of cell rate %.3f does not fit: %zu bytes (%s)", S->verb, (double)S->rate_cell, 4 * room_cells * 8, fastf_last_error());
+    const size_t stride = S->have.level / 32;               /* (entries per array, of the block as it was allocated) */
+    S->d_lo = (uint64_t *)S->d_level; S->d_hi = S->d_lo + stride; S->d_probe = S->d_hi + stride; S->d_ufull = S->d_probe + stride;
+    return 0;
+}
+
+/* the small block to the host — the one copy of a pass — and what it says: RES_OK with *held = 0 (the state moved), *held = 1 (a
+ * run was too long for the group-only sort and nothing else is wrong: the caller sorts fully and steps again), or the end of the run */
+static int level_result_(res_rate_t *S, const char *point_name, int *held, uint64_t *open_out, uint64_t *capped_out)
+{
+    if (fastf_devmem_copy(S->h_small, S->d_small, SM_WORDS_ * 8)) return RES_FAIL;
+    const uint64_t *const r = S->h_small + SM_LEVEL;
+    const uint64_t bits = r[2] | S->h_small[SM_CNT + 3];
+    *held = 0;
+    if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: as in fastf_res_point_run */
+    if (bits == FASTF_ERR_RUN_TOO_LONG && r[3]) { *held = 1; return RES_OK; }
+    if (bits || r[3]) { rs_err("%s: device error bits 0x%llx in the search of point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
+    if (S->h_small[SM_NNZ] > S->R->n) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)S->h_small[SM_NNZ], (unsigned long long)S->R->n); return RES_FAIL; }
+    *open_out = r[0];
+    if (capped_out) *capped_out = r[1];
+    return RES_OK;
+}
+
+int fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t umi_cap, int first, uint64_t *open_out,
+                          uint64_t *capped_out, res_times_t *T)
+{
+    const uint64_t N = S->R->n;
+    fastf_engine_t *e = S->e;
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint32_t *const d_f = (uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    const double t0 = fastf_res_now();
+    if (!S->d_level) { rs_err("internal error: no search state at point %s", point_name); return RES_FAIL; }
+    uint64_t *src = NULL, *other = NULL;
+    if (point_sort_reduce_(S, d_plane, &src, &other)) return RES_FAIL;
+    S->sorted = NULL; S->sorted_full = 0;                   /* (a search pass leaves no keys for --cells: the point's own run does) */
+    for (int again = 0;; again++) {
+        /* the rows concatenated on the device, their per-cell summary, the step: the row count is read on the device (a reduce that
+         * raised an error bit leaves rows the step does not consume) */
+        if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
+            fastf_dev_cell_summary(e, d_c, d_k, sm + SM_NNZ, S->n_cells, (uint64_t *)S->d_upc, (uint32_t *)S->d_gpc, NULL) ||
+            (first ? fastf_dev_level_init(e, (const uint64_t *)S->d_upc, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)
+                   : fastf_dev_level_step(e, (const uint64_t *)S->d_upc, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)))
+            return RES_FAIL;
+        int held = 0;
+        const int rc = level_result_(S, point_name, &held, open_out, first ? capped_out : NULL);
+        if (rc != RES_OK) return rc;
+        if (!held) break;
+        if (again) { rs_err("%s: device error bits 0x%llx after the full sort in the search of point %s", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG, point_name); return RES_FAIL; }
+        if (point_full_again_(S, &src, &other)) return RES_FAIL;
+    }
+    if (first && fastf_devmem_copy(S->d_ufull, S->d_upc, ((size_t)S->n_cells + 1) * 8)) return RES_FAIL;
+    T->search += fastf_res_now() - t0; T->passes++;
+    return RES_OK;
+}
+
+int fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, uint64_t *capped_out, res_times_t *T)
+{
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    const double t0 = fastf_res_now();
+    int held = 0;
+    if (!S->d_level) { rs_err("internal error: no search state"); return RES_FAIL; }
+    if (fastf_devmem_zero(S->d_small, SM_HITS * 8) ||       /* (the counters of the point before: their error word is read again) */
+        fastf_dev_level_init(S->e, S->d_ufull, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, NULL, NULL)) return RES_FAIL;
+    const int rc = level_result_(S, "(the state of a cap)", &held, open_out, capped_out);
+    if (rc != RES_OK) return rc;
+    if (held) { rs_err("%s: device error bits 0x%llx before a search", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG); return RES_FAIL; }
+    T->search += fastf_res_now() - t0;
     return RES_OK;
 }
 
@@ -800,7 +902,7 @@ static int reps_gene_file(const res_reps_t *P, const float *rates_cell, const fl
     for (uint32_t p = 0; p < np && !bad; p++) {
         char name[64];
         const uint32_t i = p / P->n_list, j = p % P->n_list;
-        bad = caps ? fastf_cap_point_dir(rates_cell[i], caps[j], name, sizeof name) : fastf_sweep_point_dir(rates_cell[i], rates_depth[j], name, sizeof name);
+        bad = caps ? (!strcmp(P->verb, "level") ? fastf_level_point_dir : fastf_cap_point_dir)(rates_cell[i], caps[j], name, sizeof name) : fastf_sweep_point_dir(rates_cell[i], rates_depth[j], name, sizeof name);
         for (int c = 0; c < 3 && !bad; c++) bad = gt_str(&t, "\t") || gt_str(&t, name) || gt_str(&t, col[c]);
     }
     if (!bad) bad = gt_str(&t, "\n");

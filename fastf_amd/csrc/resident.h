@@ -23,9 +23,9 @@ int   fastf_devmem_sync(void);
 
 enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys wider than 64 bits or UMIs beyond what a 64-bit key holds */
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
-enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_WORDS_ = 192 };   /* SM_UROWS: --cells, K3u's row count */
+enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_LEVEL = 192, SM_WORDS_ = 224 };   /* SM_UROWS: --cells, K3u's row count; SM_LEVEL: level, the result block of a step (FASTF_LEVEL_OUT_WORDS) */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps; uint32_t opens, relays; } res_times_t;   /* genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search; uint32_t opens, relays, passes; } res_times_t;   /* search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
@@ -69,8 +69,11 @@ typedef struct {
     int cells, sorted_full; uint64_t *sorted, *sorted_other;
     void *d_cellsum; uint64_t *h_hist; uint32_t *h_rpc, *h_npc, *h_spc;
     uint64_t blk_layout;
+    /* level: lo, hi, the probes and U_k(2^32) of the search (four u64 arrays of level_cells entries in ONE block sized for max_cells,
+     * fastf_res_level_room), else NULL */
+    void *d_level; uint64_t *d_lo, *d_hi, *d_probe, *d_ufull;
     uint32_t max_cells; int no_reuse;    /* set by the caller before the first open: the most cells any pair of the run samples (0: unknown); FASTF_RES_NO_REUSE */
-    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist; } have;
+    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level; } have;
 } res_rate_t;
 #define RES_CELLS_HIST_BYTES 512u
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
@@ -83,6 +86,21 @@ int  fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poi
 /* the rows of the last point into pinned memory, and the three files of bam2db into dir (created) */
 int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz,
                            res_times_t *T) FASTF_HIDDEN;
+
+/* level (level_cmds.c): the search for the per-cell thresholds.  fastf_res_level_room: the state arrays of S, after every open.
+ * fastf_res_search_pass: the device half of fastf_res_point_run up to fastf_dev_cell_summary on the plane d_plane, then one step of the
+ * search on the device and ONE device-to-host copy, of the small block (counters, error bits, the step's result): no per-cell or
+ * per-gene array and no row leaves the device.  first != 0: the pass whose plane keeps every hit — its U_k(2^32) is kept in
+ * S->d_ufull for every cap of the pair and the state is initialised for umi_cap from it (*capped_out: the cells with
+ * U_k(2^32) > umi_cap); else S->d_upc is U_k(S->d_probe) and the state moves by the rules of fastf_dev_level_step.  Either way
+ * S->d_probe then holds the thresholds of the next pass and *open_out the cells still open.  The error bits of the pass are
+ * handled as fastf_res_point_run handles them (RES_NOT_COVERED; a run too long for the group-only sort is sorted fully and the
+ * step taken again, which costs that pass a second small copy).  fastf_res_level_init: the state for another cap of the same
+ * pair, from S->d_ufull. */
+int  fastf_res_level_room(res_rate_t *S) FASTF_HIDDEN;
+int  fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t umi_cap, int first, uint64_t *open_out,
+                           uint64_t *capped_out, res_times_t *T) FASTF_HIDDEN;
+int  fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, uint64_t *capped_out, res_times_t *T) FASTF_HIDDEN;
 
 /* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
  * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into

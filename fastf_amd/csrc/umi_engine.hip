@@ -7,6 +7,7 @@
 #include "umi_kernels.hpp"
 #include "sweep_kernels.hpp"
 #include "cap_kernels.hpp"
+#include "level_kernels.hpp"
 #include "gene_kernels.hpp"
 #include "cells_kernels.hpp"
 
@@ -1272,6 +1273,33 @@ extern "C" int fastf_dev_cell_decisions(fastf_engine_t* e, uint64_t n, const voi
     return sync();
 } FASTF_CATCH_INT
 
+// level: one step of the per-cell threshold search (level_step_kernel; the state rules are in include/fastf_amd.h).  d_out[0]
+// (and d_out[1] in the initialising form) are cleared here first; the engine's own error word is always one of the two the
+// kernel looks at, d_err_in (nullptr: none) the other.  Stream-ordered, no synchronisation.
+static_assert(LEVEL_OUT_WORDS == FASTF_LEVEL_OUT_WORDS, "the result block of level_step_kernel and the ABI's");
+template <bool INIT>
+static int launch_level_step(fastf_engine* e, const u64* d_umis, u32 n_cells, u64 umi_cap, u64* d_lo, u64* d_hi, u64* d_probe, u64* d_out,
+                             const u64* d_err_in, hipStream_t s) {
+    if (umi_cap < 1) return set_err("level: a UMI cap is at least 1");
+    HIP_OK(hipMemsetAsync(d_out, 0, (INIT ? 2 : 1) * sizeof(u64), s));
+    const u32 grid = std::max<u32>(1u, (n_cells + LEVEL_THREADS - 1) / LEVEL_THREADS);
+    hipLaunchKernelGGL(level_step_kernel<INIT>, dim3(grid), dim3(LEVEL_THREADS), 0, s, d_umis, n_cells, umi_cap, d_lo, d_hi, d_probe, d_out,
+                       (const u64*)e->d_small.p + SM_COUNTERS + 3, d_err_in);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, INIT ? "level init" : "level step");
+    return 0;
+}
+extern "C" int fastf_dev_level_init(fastf_engine_t* e, const uint64_t* d_umis_full, uint32_t n_cells, uint64_t umi_cap, uint64_t* d_lo, uint64_t* d_hi,
+                                    uint64_t* d_probe, uint64_t* d_out, const uint64_t* d_err_in, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_out || (n_cells && (!d_umis_full || !d_lo || !d_hi || !d_probe)), "null argument");
+    return launch_level_step<true>(e, (const u64*)d_umis_full, n_cells, umi_cap, (u64*)d_lo, (u64*)d_hi, (u64*)d_probe, (u64*)d_out, (const u64*)d_err_in, (hipStream_t)stream);
+} FASTF_CATCH_INT
+extern "C" int fastf_dev_level_step(fastf_engine_t* e, const uint64_t* d_umis_per_cell, uint32_t n_cells, uint64_t umi_cap, uint64_t* d_lo, uint64_t* d_hi,
+                                    uint64_t* d_probe, uint64_t* d_out, const uint64_t* d_err_in, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_out || (n_cells && (!d_umis_per_cell || !d_lo || !d_hi || !d_probe)), "null argument");
+    return launch_level_step<false>(e, (const u64*)d_umis_per_cell, n_cells, umi_cap, (u64*)d_lo, (u64*)d_hi, (u64*)d_probe, (u64*)d_out, (const u64*)d_err_in, (hipStream_t)stream);
+} FASTF_CATCH_INT
+
 // device memory for the C side of the library (sweep_cmds.c keeps the records of a BAM resident); declared in host_io.h
 extern "C" void* fastf_devmem_alloc(int device, size_t bytes) FASTF_TRY {
     void* p = nullptr;
@@ -1743,7 +1771,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

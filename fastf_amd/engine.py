@@ -412,6 +412,16 @@ class Engine:
         draw_bits) over the plane may follow"""
         check(self._L.fastf_dev_cell_decisions(self._h, n, d_blocked or None, seed, skip, n_draws, d_thresholds, d_bits_out, stream))
 
+    def dev_level_init(self, d_umis_full, n_cells, umi_cap, d_lo, d_hi, d_probe, d_out, d_err_in=0, stream=0):
+        """level: the state of the threshold search from U_k(2^32) (u64[n_cells] on the device) and the UMI cap: d_lo, d_hi, the first
+        probes d_probe (u64[n_cells] each), d_out[0] = cells open, d_out[1] = cells capped, d_out[2] = error bits found, d_out[3] = held"""
+        check(self._L.fastf_dev_level_init(self._h, d_umis_full, n_cells, int(umi_cap), d_lo, d_hi, d_probe, d_out, d_err_in or None, stream))
+
+    def dev_level_step(self, d_umis_per_cell, n_cells, umi_cap, d_lo, d_hi, d_probe, d_out, d_err_in=0, stream=0):
+        """level: one step of the search: d_umis_per_cell[k] = U_k(d_probe[k]); an open cell moves lo or hi to its probe; the next
+        probes into d_probe (0 for a cell that is not open), d_out[0] = cells still open"""
+        check(self._L.fastf_dev_level_step(self._h, d_umis_per_cell, n_cells, int(umi_cap), d_lo, d_hi, d_probe, d_out, d_err_in or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

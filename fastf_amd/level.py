@@ -1,0 +1,143 @@
+"""Python mirror of `fastF level` (include/fastf_amd.h: fastf_level and its host pieces): every cell downsampled to at most M UMIs,
+exactly, over a grid of (cell rate, UMI cap) points from one decode of the BAM.  Nothing here computes results: every call lands in
+the library."""
+import ctypes as C
+import gzip
+import os
+
+import numpy as np
+
+from . import _lib
+from . import cap as _cap
+from . import sweep as _sweep
+
+SUMMARY_ONLY = 1      # FASTF_LEVEL_SUMMARY_ONLY
+GENES = 2             # FASTF_LEVEL_GENES
+CELLS = 8             # FASTF_LEVEL_CELLS
+
+
+def _renamed(columns):
+    return tuple("umi_cap" if c == "reads_per_cell" else c for c in columns)
+
+
+COLUMNS = _renamed(_cap.COLUMNS)
+GENES_COLUMNS = _renamed(_cap.GENES_COLUMNS)
+CELLS_COLUMNS = _renamed(_cap.CELLS_COLUMNS)
+REPS_COLUMNS = _renamed(_cap.REPS_COLUMNS)
+GENES_REPS_COLUMNS = _renamed(_cap.GENES_REPS_COLUMNS)
+THRESHOLDS_COLUMNS = ("barcode", "threshold", "umis_full", "umis")
+parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for the three verbs)
+
+
+def _flags(summary_only, genes, cells):
+    return (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)
+
+
+def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False):
+    """`fastF level -b bam -a barcodes -f features -o out -c rates_cell -m umi_caps -s seed [--summary-only] [--genes] [--cells]`; returns
+    the rows of out/level.tsv as dicts of strings (read_table); genes / cells: the files cap.cap() leaves, under the names level_*"""
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_level(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                      m.ctypes.data, len(m), seed % (1 << 32), _flags(summary_only, genes, cells)))
+    return read_table(os.path.join(os.fspath(out), "level.tsv"))
+
+
+def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False):
+    """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
+    out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
+    sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
+    enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    _lib.check(_lib.lib().fastf_level_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                           m.ctypes.data, len(m), sd.ctypes.data, len(sd), _flags(summary_only, genes, cells)))
+    return read_table(os.path.join(os.fspath(out), "level.tsv"))
+
+
+def _read(path, columns):
+    lines = open(path).read().split("\n")
+    assert lines[0].split("\t") == list(columns) and lines[-1] == ""
+    return [dict(zip(columns, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def read_table(path):
+    """the rows of level.tsv as dicts of strings"""
+    return _read(path, COLUMNS)
+
+
+def read_genes_table(path):
+    return _read(path, GENES_COLUMNS)
+
+
+def read_cells_table(path):
+    return _sweep.read_cells_table(path, CELLS_COLUMNS)
+
+
+def read_reps_table(path):
+    return _sweep.read_cells_table(path, REPS_COLUMNS)
+
+
+def read_genes_reps_table(path):
+    return _sweep.read_cells_table(path, GENES_REPS_COLUMNS)
+
+
+def read_thresholds(path):
+    """thresholds.tsv.gz of a point: (barcodes, T[k], U_k(2^32), U_k(T[k])) — a list of str and three uint64 arrays"""
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(THRESHOLDS_COLUMNS) and lines[-1] == ""
+    rows = [ln.split("\t") for ln in lines[1:-1]]
+    col = lambda i: np.array([int(r[i]) for r in rows], dtype=np.uint64)  # noqa: E731
+    return [r[0] for r in rows], col(1), col(2), col(3)
+
+
+def header() -> str:
+    return _lib.lib().fastf_level_header().decode()
+
+
+def genes_header() -> str:
+    return _lib.lib().fastf_level_genes_header().decode()
+
+
+def cells_header() -> str:
+    return _lib.lib().fastf_level_cells_header().decode()
+
+
+def reps_header() -> str:
+    return _lib.lib().fastf_level_reps_header().decode()
+
+
+def genes_reps_header() -> str:
+    return _lib.lib().fastf_level_genes_reps_header().decode()
+
+
+def parse_caps(text: str):
+    """a comma-separated list of UMI caps as the command reads -m; raises FastfError on what it refuses"""
+    out = np.zeros(64, dtype=np.uint64)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().fastf_level_parse_caps(text.encode(), out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def check_grid(rates_cell, umi_caps):
+    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
+    m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
+    _lib.check(_lib.lib().fastf_level_check_grid(rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc), m.ctypes.data, len(m)))
+
+
+def point_dir(rate_cell: float, umi_cap: int) -> str:
+    buf = C.create_string_buffer(64)
+    _lib.check(_lib.lib().fastf_level_point_dir(float(rate_cell), int(umi_cap), buf, len(buf)))
+    return buf.value.decode()
+
+
+def summary_row(rate_cell, umi_cap, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, hits, cells_capped) -> str:
+    """one row of level.tsv (with its newline)"""
+    upc = np.ascontiguousarray(umis_per_cell, dtype=np.uint64)
+    gpc = np.ascontiguousarray(genes_per_cell, dtype=np.uint32)
+    cnt = (C.c_uint64 * 3)(*[int(x) for x in counters])
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_level_summary_row(float(rate_cell), int(umi_cap), seed, C.byref(cnt), int(nnz), int(umis),
+                                                  upc.ctypes.data, gpc.ctypes.data, len(upc), int(hits), int(cells_capped), buf, len(buf)))
+    return buf.value.decode()

@@ -200,6 +200,48 @@ int fastf_cap_thresholds(const uint32_t *hits, uint32_t n_cells, uint64_t cap, u
 /* the realised fraction of a point as the matrix header carries it */
 float fastf_cap_realised(uint64_t sampled, uint64_t hits);
 
+/* --- level: every cell downsampled to at most M UMIs, exactly (level_cmds.c; not a command of the reference).  One point is a cell
+ * rate c, a UMI cap M >= 1 and a seed s.  Cells are sampled as `bam2db -c c -s s` samples them; H and the coupling "hit i consumes
+ * draw i, advanced by SampleInt's draws" are cap's (above).
+ *   - For cell k and an integer T in [0, 2^32], U_k(T) is the sum of the counts of cell k's matrix column when hit i of cell k is kept
+ *     iff draw[i] < T.  Everything behind the depth draw runs as in bam2db.  It depends on cell k's hits alone.
+ *   - T[k] = max { T in [0, 2^32] : U_k(T) <= M }.  U_k(0) = 0, so it exists.  T[k] = 2^32 means the cell loses no read.
+ *   - cells_capped is the number of cells with U_k(2^32) > M.
+ *   - The point is cap's pipeline run with these T[k].  The matrix header's rate_depth carries fastf_cap_realised(sampled, H).
+ *   - Every column sum of the point's matrix is <= M.  It is exactly M for a capped cell, unless two of its hits that each start a new
+ *     UMI share one 32-bit draw.  The definition covers that case as it stands.
+ * The kept sets of a cell are nested in T, so U_k is a non-decreasing step function of T and T[k] is found by bisection, for all cells
+ * at once on the device (fastf_dev_level_init / fastf_dev_level_step below; at most 32 probing passes per point).
+ * Per point <out_dir>/c<rate_cell>_m<M>/ (replicate runs: .._s<seed>) holds the three files of bam2db and thresholds.tsv.gz: header
+ * `barcode threshold umis_full umis`, one row per sampled cell in barcodes.tsv.gz's order: T[k] as a decimal, U_k(2^32), U_k(T[k]).
+ * <out_dir>/level.tsv is cap.tsv with reads_per_cell named umi_cap (hits, cells_capped and realised_depth are kept); --genes, --cells
+ * and replicate runs write level_genes.tsv, level_gene_cells.tsv.gz, level_cells.tsv, level_reps.tsv, level_genes_reps.tsv,
+ * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
+ * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
+ * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] */
+#define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
+#define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
+#define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
+int fastf_level(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                const uint64_t *umi_caps, uint32_t n_m, uint32_t seed, uint32_t flags);
+int fastf_level_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags);
+/* the host pieces of it: the list of UMI caps and the grid check (fastf_cap_parse_caps's and fastf_cap_check_grid's rules, the
+ * messages naming this verb); a point's directory name; the header lines (cap's, with reads_per_cell named umi_cap); one row of
+ * level.tsv (with its newline; the arguments of fastf_cap_summary_row) */
+int fastf_level_parse_caps(const char *text, uint64_t *out, uint32_t cap, uint32_t *n_out);
+int fastf_level_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t *umi_caps, uint32_t n_m);
+int fastf_level_point_dir(float rate_cell, uint64_t umi_cap, char *buf, size_t cap);
+const char *fastf_level_header(void);
+const char *fastf_level_genes_header(void);
+const char *fastf_level_cells_header(void);
+const char *fastf_level_reps_header(void);
+const char *fastf_level_genes_reps_header(void);
+int fastf_level_summary_row(float rate_cell, uint64_t umi_cap, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                            const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits,
+                            uint32_t cells_capped, char *buf, size_t cap);
+
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
  *   point directories   <point name>_s<seed> (c0.500_r0.100_s927): the bytes `bam2db -s <seed>` (cap: `cap -s <seed>`) writes
@@ -594,6 +636,29 @@ int fastf_dev_copy_summary(fastf_engine_t *e, const uint64_t *d_ukeys, const uin
 int fastf_dev_cell_hits(fastf_engine_t *e, uint64_t n, const void *d_blocked, uint32_t *d_hits_per_cell, void *stream);
 int fastf_dev_cell_decisions(fastf_engine_t *e, uint64_t n, const void *d_blocked, uint32_t seed, uint64_t skip, uint64_t n_draws,
                              const uint64_t *d_thresholds, uint32_t *d_bits_out, void *stream);
+
+/* level (section 1) on the device: the search for the per-cell thresholds, one step per pass.  State of cell k, all u64[n_cells] in
+ * DEVICE memory with values 0 .. 2^32: d_lo, d_hi, and d_probe — the thresholds of the next pass, in the form
+ * fastf_dev_cell_decisions takes.
+ *   - An uncapped cell (U_k(2^32) <= umi_cap) is settled at lo = hi = 2^32.  A capped cell starts at lo = 0, hi = 2^32.
+ *   - The invariant is U_k(lo) <= umi_cap < U_k(hi).  A cell is open while hi - lo > 1.
+ *   - d_probe[k] = (lo + hi) / 2 for an open cell and 0 for every other cell: their U is not needed, so their reads drop out of
+ *     K1b's output and the pass sorts the open cells' keys alone.
+ *   - fastf_dev_level_init: d_umis_full[k] = U_k(2^32); writes the state, the first probes, d_out[0] = the cells open (= capped) and
+ *     d_out[1] = cells_capped.
+ *   - fastf_dev_level_step: d_umis_per_cell[k] = U_k(d_probe[k]) as fastf_dev_cell_summary left it after a pass on the probes this
+ *     state gave; an open cell sets lo = probe if U <= umi_cap, else hi = probe; writes the state, the next probes and d_out[0] = the
+ *     cells still open.  hi - lo halves per step from 2^32: no cell is open after 32 steps, and then d_lo holds T[k].
+ *   - d_out: FASTF_LEVEL_OUT_WORDS u64 in device memory.  d_out[2] = the error bits the step found: the engine's own error word
+ *     OR *d_err_in (a device word, e.g. the error word of the counters fastf_dev_probe_pack filled; NULL: none), read in stream
+ *     order.  If any is set the pass's U is not to be trusted: the step writes NO state and no probe, d_out[0] (and [1]) stay 0 and
+ *     d_out[3] = 1; else d_out[3] = 0.  So a pass needs one device-to-host copy, of d_out (and whatever lies next to it).
+ * Nothing behind the arrays is written.  Stream-ordered; no synchronisation.  Refused: NULL arguments, umi_cap < 1. */
+#define FASTF_LEVEL_OUT_WORDS 4u
+int fastf_dev_level_init(fastf_engine_t *e, const uint64_t *d_umis_full, uint32_t n_cells, uint64_t umi_cap, uint64_t *d_lo, uint64_t *d_hi,
+                         uint64_t *d_probe, uint64_t *d_out, const uint64_t *d_err_in, void *stream);
+int fastf_dev_level_step(fastf_engine_t *e, const uint64_t *d_umis_per_cell, uint32_t n_cells, uint64_t umi_cap, uint64_t *d_lo, uint64_t *d_hi,
+                         uint64_t *d_probe, uint64_t *d_out, const uint64_t *d_err_in, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
