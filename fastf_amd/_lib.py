@@ -124,6 +124,9 @@ ABI_SYMBOLS = [
     "fastf_level", "fastf_level_reps", "fastf_level_parse_caps", "fastf_level_check_grid", "fastf_level_point_dir", "fastf_level_header",
     "fastf_level_genes_header", "fastf_level_cells_header", "fastf_level_reps_header", "fastf_level_genes_reps_header", "fastf_level_summary_row",
     "fastf_dev_level_init", "fastf_dev_level_step",
+    # --fidelity of sweep, cap and level
+    "fastf_fidelity_header", "fastf_sweep_fidelity_header", "fastf_cap_fidelity_header", "fastf_level_fidelity_header", "fastf_fidelity_row",
+    "fastf_fidelity_metrics", "fastf_fidelity_summary_row", "fastf_fidelity_from_coo", "fastf_dev_fidelity",
 ]
 
 
@@ -335,6 +338,13 @@ def lib():
     L.fastf_level_summary_row.argtypes = [C.c_float, u64, u32, C.POINTER(u64 * 3), u64, u64, vp, vp, u32, u64, u32, C.c_char_p, sz]
     L.fastf_dev_level_init.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp]
     L.fastf_dev_level_step.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp]
+    for name in ("fastf_fidelity_header", "fastf_sweep_fidelity_header", "fastf_cap_fidelity_header", "fastf_level_fidelity_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_fidelity_row.argtypes = [C.c_char_p, u64, u64, u64, u64, u64, u64, u64, u64, C.c_char_p, sz]
+    L.fastf_fidelity_metrics.argtypes = [u64, u64, u64, u64, u64, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.fastf_fidelity_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, vp, vp, vp, vp, vp, u32, u64, C.c_char_p, sz]
+    L.fastf_fidelity_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, vp]
+    L.fastf_dev_fidelity.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -11,27 +11,33 @@ from . import sweep as _sweep
 SUMMARY_ONLY = 1      # FASTF_CAP_SUMMARY_ONLY
 GENES = 2             # FASTF_CAP_GENES
 CELLS = 8             # FASTF_CAP_CELLS
+FIDELITY = 32         # FASTF_CAP_FIDELITY
 COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
 GENES_COLUMNS = ("rate_cell", "reads_per_cell", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
 CELLS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.CELLS_TAIL_COLUMNS
+FIDELITY_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.FIDELITY_TAIL_COLUMNS
+fidelity_row, fidelity_from_coo, read_point_fidelity = _sweep.fidelity_row, _sweep.fidelity_from_coo, _sweep.read_point_fidelity
 copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one function for both verbs)
 
 
-def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False):
+def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
+        fidelity: bool = False):
     """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
     rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
     out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
-    a cells.tsv.gz per point directory"""
+    a cells.tsv.gz per point directory; fidelity=True also leaves out/cap_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per
+    point directory"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
-def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False):
+def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
+             fidelity: bool = False):
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
@@ -41,13 +47,27 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                          n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                         (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+                                         _sweep._flags(summary_only, genes, cells, fidelity)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
 REPS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.REPS_TAIL_COLUMNS
 GENES_REPS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.GENES_REPS_TAIL_COLUMNS
 parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for both verbs)
+
+
+def read_fidelity_table(path):
+    """the rows of cap_fidelity.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, FIDELITY_COLUMNS)
+
+
+def fidelity_header(verb: str = "cap") -> str:
+    return _sweep.fidelity_header(verb)
+
+
+def fidelity_summary_row(rate_cell, reads_per_cell, seed, umis_full, umis, genes_full, genes, sum_xx, sum_yy, sum_xy, n_features) -> str:
+    """one row of cap_fidelity.tsv (with its newline)"""
+    return _sweep.fidelity_summary_row(rate_cell, 0.0, seed, umis_full, umis, genes_full, genes, sum_xx, sum_yy, sum_xy, n_features, list_value=int(reads_per_cell))
 
 
 def read_reps_table(path):

@@ -135,7 +135,7 @@ static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_op
 /* ------------------------------------------------------------------ */
 static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                          float rate_cell, const uint64_t *caps, uint32_t n_n, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                         res_cells_t *C, res_reps_t *P, uint32_t k_seed, res_times_t *T)
+                         res_cells_t *C, res_fid_t *Fd, res_reps_t *P, uint32_t k_seed, res_times_t *T)
 {
     int rc = RES_FAIL;
     void *d_plane = NULL, *d_hits = NULL, *d_thr = NULL;
@@ -158,6 +158,15 @@ static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t
         for (uint32_t k = 0; k < n_cells; k++) sum += h_hits[k];
         if (sum != H) { cp_err("internal error: %llu hits per cell in total, K1a counted %llu", (unsigned long long)sum, (unsigned long long)H); goto done; } }
     T->planes += fastf_res_now() - tt;
+    if (Fd->on) {                                           /* the full rows of the pair, once: T = 2^32 for every cell */
+        tt = fastf_res_now();
+        for (uint32_t k = 0; k < n_cells; k++) h_thr[k] = (uint64_t)1 << 32;
+        if (fastf_devmem_copy(d_thr, h_thr, (size_t)n_cells * 8) ||
+            fastf_dev_cell_decisions(S->e, N, S->blocked ? S->d_blk : NULL, seed, L->mt_skip, H, (const uint64_t *)d_thr, (uint32_t *)d_plane, NULL)) goto done;
+        T->fidelity += fastf_res_now() - tt;
+        const int frc = fastf_res_full_run(S, (const uint32_t *)d_plane, T);
+        if (frc != RES_OK) { rc = frc; goto done; }
+    }
 
     for (uint32_t j = 0; j < n_n; j++) {
         char base[64], name[96], dir[4096], row[640];
@@ -178,6 +187,7 @@ static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t
         if (cap_row_(rate_cell, caps[j], seed, counters, nnz, S->h_upc[n_cells], S->h_upc, S->h_gpc, n_cells, H, capped, row, sizeof row, metrics) ||
             fastf_res_reps_point(P, j, k_seed, n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
+        if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
@@ -187,6 +197,7 @@ static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_point_write(S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
         }
+        if (fastf_res_fid_point(Fd, S, summary_only ? NULL : dir, 0.0f, caps[j], T)) goto done;
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
@@ -214,7 +225,7 @@ done:
 
 static int cap_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
                         const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_s, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                        res_cells_t *C, res_reps_t *P)
+                        res_cells_t *C, res_fid_t *Fd, res_reps_t *P)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -233,6 +244,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
+    S.fidelity = Fd->on;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("cap", bam_file, &LL.L[0], device, &R)) goto done;
@@ -243,7 +255,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
         if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
         for (uint32_t k = 0; k < n_s; k++) {
             const uint32_t at = i * n_s + k;
-            rc = cap_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_n, seeds[k], summary_only, device, tsv, G, C, P, k, &T);
+            rc = cap_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_n, seeds[k], summary_only, device, tsv, G, C, Fd, P, k, &T);
             if (rc != RES_OK) goto done;
         }
         if (fastf_res_reps_rate_end(P, rc_list[i], NULL, caps, &T)) { rc = RES_FAIL; goto done; }
@@ -258,6 +270,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
     if (prof && G->on) fprintf(stderr, "[cap] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
     if (prof && C->on) fprintf(stderr, "[cap] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
                                T.cells_dev, T.cells_dev / (n_c * n_n * n_s), T.cells);
+    if (prof && Fd->on) fprintf(stderr, "[cap] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
 done:
     fastf_res_rate_close(&S);
     fastf_res_free(&R);
@@ -276,8 +289,9 @@ static int cap_run(const char *bam, const char *out_dir, const char *barcodes, c
     if (!bam || !barcodes || !features) return cp_err("cap: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_cap_check_grid(rates_cell, n_c, caps, n_n)) return 1;
-    if (flags & ~(uint32_t)(FASTF_CAP_SUMMARY_ONLY | FASTF_CAP_GENES | FASTF_CAP_CELLS)) return cp_err("cap: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(FASTF_CAP_SUMMARY_ONLY | FASTF_CAP_GENES | FASTF_CAP_CELLS | FASTF_CAP_FIDELITY)) return cp_err("cap: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_CAP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_CAP_GENES) != 0, cells = (flags & FASTF_CAP_CELLS) != 0;
+    const int fidelity = (flags & FASTF_CAP_FIDELITY) != 0;
     if (access(bam, R_OK) == -1) return cp_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1;
     {   const char *dvs = getenv("FASTF_DEVICES");
@@ -291,19 +305,22 @@ static int cap_run(const char *bam, const char *out_dir, const char *barcodes, c
     if (fastf_res_genes_open(&G, genes, "cap", out_dir, fastf_cap_genes_header(), n_c * n_n, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "cap", out_dir, fastf_cap_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
+    res_fid_t Fd;
+    if (fastf_res_fid_open(&Fd, fidelity, "cap", out_dir, fastf_cap_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "cap", out_dir, seeds, n_s, n_c, n_n, genes, dev0, fastf_cap_reps_header(), fastf_cap_genes_reps_header())) {
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1;
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
-    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &P);
+    int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
     if (rc == RES_NOT_COVERED)
         cp_err("cap: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
     if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
+    if (!rc && fastf_res_fid_close(&Fd, 1)) rc = 1;
     if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, NULL, caps)) rc = 1;
     if (rc) {
         char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_reps_close(&P, 0);
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); fastf_res_reps_close(&P, 0);
         if (reps) fastf_res_reps_unlink_tables(out_dir, "cap");      /* (the tables that were already renamed go too: none is left) */
         fastf_set_error_(keep);
         return 1;
@@ -343,6 +360,9 @@ static void usage_cap(FILE *f)
             "        --summary-only    write cap.tsv alone\n"
             "        --genes           per-gene detection too: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point\n"
             "        --cells           per-cell reads, saturation and UMI copy numbers too: cap_cells.tsv and cells.tsv.gz per point\n"
+            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
+            "                          cap_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
+            "                          over ALL genes per cell (not log-normalised)\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_n<N>_s<seed>/, one cap.tsv row each, and cap_reps.tsv with mean, sd, min and max\n"
             "                          of every metric per grid point (with --genes cap_genes_reps.tsv and cap_gene_reps.tsv.gz in\n"
@@ -366,7 +386,7 @@ int cmd_cap(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0);
+    const uint32_t flags = (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0) | (A.fidelity ? FASTF_CAP_FIDELITY : 0);
     if (A.n_seeds ? fastf_cap_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags)
                   : fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
@@ -375,6 +395,7 @@ int cmd_cap(int argc, const char **argv)
     if (A.genes && A.n_seeds) printf("cap_genes.tsv, cap_genes_reps.tsv and cap_gene_reps.tsv.gz are generated.\n");
     else if (A.genes) printf("cap_genes.tsv and cap_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("cap_cells.tsv is generated.\n");
+    if (A.fidelity) printf("cap_fidelity.tsv is generated.\n");
     if (A.n_seeds) printf("cap_reps.tsv is generated.\n");
     printf("cap.tsv is generated.\n");
     return 0;

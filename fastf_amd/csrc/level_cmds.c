@@ -124,7 +124,7 @@ static int write_thresholds(const char *dir, const fastf_lists_t *L, uint32_t n_
 #define LEVEL_MAX_PASSES 32u                             /* hi - lo halves per probing pass, from 2^32 */
 static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const uint64_t *caps, uint32_t n_m, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                           res_cells_t *C, res_reps_t *P, uint32_t k_seed, res_times_t *T, int prof)
+                           res_cells_t *C, res_fid_t *Fd, res_reps_t *P, uint32_t k_seed, res_times_t *T, int prof)
 {
     int rc = RES_FAIL;
     void *d_plane = NULL;
@@ -152,6 +152,7 @@ static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
     {   char name0[64]; snprintf(name0, sizeof name0, "c%.3f (every hit)", (double)rate_cell);
         const int prc = fastf_res_search_pass(S, (const uint32_t *)d_plane, name0, caps[0], 1, &open, &capped, T);
         if (prc != RES_OK) { rc = prc; goto done; } }
+    if (fastf_res_full_keep(S, T)) goto done;               /* --fidelity: pass 0's rows are the full rows of the pair */
     if (h_ufull && fastf_devmem_copy(h_ufull, S->d_ufull, (size_t)n_cells * 8)) goto done;
 
     for (uint32_t j = 0; j < n_m; j++) {
@@ -183,6 +184,7 @@ static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         if (level_row_(rate_cell, caps[j], seed, counters, nnz, S->h_upc[n_cells], S->h_upc, S->h_gpc, n_cells, H, (uint32_t)capped, row, sizeof row, metrics) ||
             fastf_res_reps_point(P, j, k_seed, n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
+        if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
@@ -195,6 +197,7 @@ static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
             if (fastf_devmem_copy(h_thr, S->d_lo, (size_t)n_cells * 8) || write_thresholds(dir, L, n_cells, h_thr, h_ufull, S->h_upc)) goto done;
             T->write += fastf_res_now() - tt;
         }
+        if (fastf_res_fid_point(Fd, S, summary_only ? NULL : dir, 0.0f, caps[j], T)) goto done;
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
@@ -222,7 +225,7 @@ done:
 
 static int level_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
                           const uint64_t *caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_s, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                          res_cells_t *C, res_reps_t *P)
+                          res_cells_t *C, res_fid_t *Fd, res_reps_t *P)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -241,6 +244,7 @@ static int level_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
+    S.fidelity = Fd->on;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("level", bam_file, &LL.L[0], device, &R)) goto done;
@@ -251,7 +255,7 @@ static int level_resident(const char *bam_file, const char *out_dir, const char 
         if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
         for (uint32_t k = 0; k < n_s; k++) {
             const uint32_t at = i * n_s + k;
-            rc = level_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_m, seeds[k], summary_only, device, tsv, G, C, P, k, &T, prof);
+            rc = level_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_m, seeds[k], summary_only, device, tsv, G, C, Fd, P, k, &T, prof);
             if (rc != RES_OK) goto done;
         }
         if (fastf_res_reps_rate_end(P, rc_list[i], NULL, caps, &T)) { rc = RES_FAIL; goto done; }
@@ -271,6 +275,7 @@ static int level_resident(const char *bam_file, const char *out_dir, const char 
     if (prof && G->on) fprintf(stderr, "[level] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
     if (prof && C->on) fprintf(stderr, "[level] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
                                T.cells_dev, T.cells_dev / (n_c * n_m * n_s), T.cells);
+    if (prof && Fd->on) fprintf(stderr, "[level] --fidelity: the full rows kept from %u first passes, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
 done:
     fastf_res_rate_close(&S);
     fastf_res_free(&R);
@@ -289,8 +294,9 @@ static int level_run(const char *bam, const char *out_dir, const char *barcodes,
     if (!bam || !barcodes || !features) return lv_err("level: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_level_check_grid(rates_cell, n_c, caps, n_m)) return 1;
-    if (flags & ~(uint32_t)(FASTF_LEVEL_SUMMARY_ONLY | FASTF_LEVEL_GENES | FASTF_LEVEL_CELLS)) return lv_err("level: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(FASTF_LEVEL_SUMMARY_ONLY | FASTF_LEVEL_GENES | FASTF_LEVEL_CELLS | FASTF_LEVEL_FIDELITY)) return lv_err("level: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_LEVEL_SUMMARY_ONLY) != 0, genes = (flags & FASTF_LEVEL_GENES) != 0, cells = (flags & FASTF_LEVEL_CELLS) != 0;
+    const int fidelity = (flags & FASTF_LEVEL_FIDELITY) != 0;
     if (access(bam, R_OK) == -1) return lv_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1;
     {   const char *dvs = getenv("FASTF_DEVICES");
@@ -304,19 +310,22 @@ static int level_run(const char *bam, const char *out_dir, const char *barcodes,
     if (fastf_res_genes_open(&G, genes, "level", out_dir, fastf_level_genes_header(), n_c * n_m, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "level", out_dir, fastf_level_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
+    res_fid_t Fd;
+    if (fastf_res_fid_open(&Fd, fidelity, "level", out_dir, fastf_level_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "level", out_dir, seeds, n_s, n_c, n_m, genes, dev0, fastf_level_reps_header(), fastf_level_genes_reps_header())) {
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1;
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
-    int rc = level_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_m, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &P);
+    int rc = level_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_m, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
     if (rc == RES_NOT_COVERED)
         lv_err("level: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a UMI cap has no point-by-point form");
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
     if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
+    if (!rc && fastf_res_fid_close(&Fd, 1)) rc = 1;
     if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, NULL, caps)) rc = 1;
     if (rc) {
         char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_reps_close(&P, 0);
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); fastf_res_reps_close(&P, 0);
         fastf_res_reps_unlink_tables(out_dir, "level");     /* (the tables that were already renamed go too: none is left) */
         fastf_set_error_(keep);
         return 1;
@@ -357,6 +366,9 @@ static void usage_level(FILE *f)
             "        --summary-only    write level.tsv alone\n"
             "        --genes           per-gene detection too: level_genes.tsv, level_gene_cells.tsv.gz and genes.tsv.gz per point\n"
             "        --cells           per-cell reads, saturation and UMI copy numbers too: level_cells.tsv and cells.tsv.gz per point\n"
+            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
+            "                          level_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
+            "                          over ALL genes per cell (not log-normalised)\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_m<M>_s<seed>/, one level.tsv row each, and level_reps.tsv with mean, sd, min and\n"
             "                          max of every metric per grid point (with --genes level_genes_reps.tsv and level_gene_reps.tsv.gz\n"
@@ -379,7 +391,7 @@ int cmd_level(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_LEVEL_SUMMARY_ONLY : 0) | (A.genes ? FASTF_LEVEL_GENES : 0) | (A.per_cell ? FASTF_LEVEL_CELLS : 0);
+    const uint32_t flags = (A.summary_only ? FASTF_LEVEL_SUMMARY_ONLY : 0) | (A.genes ? FASTF_LEVEL_GENES : 0) | (A.per_cell ? FASTF_LEVEL_CELLS : 0) | (A.fidelity ? FASTF_LEVEL_FIDELITY : 0);
     if (A.n_seeds ? fastf_level_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags)
                   : fastf_level(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m level failed: %s\n", fastf_last_error());
@@ -388,6 +400,7 @@ int cmd_level(int argc, const char **argv)
     if (A.genes && A.n_seeds) printf("level_genes.tsv, level_genes_reps.tsv and level_gene_reps.tsv.gz are generated.\n");
     else if (A.genes) printf("level_genes.tsv and level_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("level_cells.tsv is generated.\n");
+    if (A.fidelity) printf("level_fidelity.tsv is generated.\n");
     if (A.n_seeds) printf("level_reps.tsv is generated.\n");
     printf("level.tsv is generated.\n");
     return 0;

@@ -154,6 +154,8 @@ void fastf_res_rate_close(res_rate_t *S)
     fastf_devmem_free(S->d_cellsum);
     if (S->h_hist) fastf_pinned_free(S->h_hist);
     fastf_devmem_free(S->d_level);
+    fastf_devmem_free(S->d_full); fastf_devmem_free(S->d_fid);
+    if (S->h_fid) fastf_pinned_free(S->h_fid);
     memset(S, 0, sizeof *S);
 }
 
@@ -182,7 +184,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; }
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; }
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -247,6 +249,18 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
             return RES_FAIL;
         }
         S->h_rpc = (uint32_t *)((char *)S->h_hist + RES_CELLS_HIST_BYTES); S->h_npc = S->h_rpc + n_cells; S->h_spc = S->h_npc + n_cells;
+    }
+    if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
+        const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
+        if (dev_room(&S->d_full, &S->have.full, (N ? N : 1) * 12, device) || dev_room(&S->d_fid, &S->have.fid, dev_bytes, device) ||
+            pin_room((void **)&S->h_fid, &S->have.h_fid, pin_bytes)) {
+            rs_err("%s: the full-depth rows of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 12 + dev_bytes), fastf_last_error());
+            return RES_FAIL;
+        }
+        S->fid_stride = S->have.fid / 24;
+        const size_t hs = S->have.h_fid / 36;               /* (entries per array, of the block as it was allocated) */
+        S->h_sxy = S->h_fid; S->h_syy = S->h_sxy + hs; S->h_sxx = S->h_syy + hs; S->h_ufull = S->h_sxx + hs; S->h_gfull = (uint32_t *)(S->h_ufull + hs);
+        S->full_nnz = 0;
     }
     uint64_t *const sm = (uint64_t *)S->d_small;
     if (fastf_devmem_zero(S->d_small, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
@@ -440,6 +454,64 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
     T->d2h += fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_make_dir(dir) || fastf_write_outputs(dir, bam_label, S->rate_cell, rate_depth, counters, S->L, &coo, NULL)) return 1;
     T->write += fastf_res_now() - tt;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* --fidelity: the full rows of a pair, the join behind a point        */
+/* ------------------------------------------------------------------ */
+int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
+{
+    if (!S->fidelity) return 0;
+    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    uint32_t *const x_f = (uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
+    uint64_t *const d_sxy = (uint64_t *)S->d_fid, *const d_sxx = d_sxy + 2 * S->fid_stride;
+    const double tt = fastf_res_now();
+    if (nnz > N) return rs_err("internal error: %llu full-depth rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N);
+    if (fastf_devmem_copy(x_f, d_f, (size_t)nnz * 4) || fastf_devmem_copy(x_c, d_c, (size_t)nnz * 4) || fastf_devmem_copy(x_k, d_k, (size_t)nnz * 4) ||
+        fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
+    S->full_nnz = nnz;
+    /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
+     * first point overwrites) */
+    if (fastf_dev_fidelity(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? x_f : NULL, nnz ? x_c : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_cells, d_sxy, d_sxx, NULL, NULL)) return 1;
+    if (fastf_devmem_copy(S->h_sxx, d_sxx, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_ufull, S->d_upc, ((size_t)S->n_cells + 1) * 8) ||
+        fastf_devmem_copy(S->h_gfull, S->d_gpc, (size_t)S->n_cells * 4)) return 1;
+    T->fidelity += fastf_res_now() - tt;
+    return 0;
+}
+
+int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
+{
+    if (!S->fidelity) return RES_OK;
+    char name[64];
+    uint64_t counters[3], nnz = 0;
+    const res_times_t before = *T;
+    const double tt = fastf_res_now();
+    snprintf(name, sizeof name, "c%.3f (every hit)", (double)S->rate_cell);
+    const int prc = fastf_res_point_run(S, d_plane, name, counters, &nnz, T);
+    if (prc != RES_OK) return prc;
+    *T = before;                                            /* (the stages of this point are the flag's own) */
+    T->fidelity += fastf_res_now() - tt;
+    return fastf_res_full_keep(S, T) ? RES_FAIL : RES_OK;
+}
+
+int fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->fidelity) return 0;
+    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    const uint32_t *const x_f = (const uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
+    uint64_t *const d_sxy = (uint64_t *)S->d_fid, *const d_syy = d_sxy + S->fid_stride;
+    const double tt = fastf_res_now();
+    if (fastf_dev_fidelity(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? d_f : NULL, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_cells, d_sxy, d_syy, NULL, NULL)) {
+        char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, keep);
+    }
+    if (fastf_devmem_copy(S->h_sxy, d_sxy, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_syy, d_syy, (size_t)S->n_cells * 8)) return 1;
+    T->fidelity += fastf_res_now() - tt;
     return 0;
 }
 
@@ -650,6 +722,52 @@ int fastf_res_cells_close(res_cells_t *C, int ok)
     if (!C->on) return 0;
     C->on = 0;
     return fastf_res_tsv_close(&C->tsv, ok);
+}
+
+/* ------------------------------------------------------------------ */
+/* --fidelity: the table, a point's file                               */
+/* ------------------------------------------------------------------ */
+int fastf_res_fid_open(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header)
+{
+    memset(F, 0, sizeof *F);
+    if (!on) return 0;
+    char name[64];
+    snprintf(name, sizeof name, "%s_fidelity.tsv", verb);
+    F->verb = verb;
+    if (fastf_res_tsv_open(&F->tsv, out_dir, name, header)) return 1;
+    F->on = 1;
+    return 0;
+}
+
+int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T)
+{
+    if (!F->on) return 0;
+    const double tt = fastf_res_now();
+    char row[640];
+    if (fastf_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->h_ufull, S->h_upc, S->h_gfull, S->h_gpc, S->h_sxx, S->h_syy, S->h_sxy,
+                                   S->n_cells, S->n_features, row, sizeof row)) return 1;
+    if (dir) {
+        char path[4200], line[512];
+        gtext t = { NULL, 0, 0 };
+        int bad = gt_str(&t, fastf_fidelity_header());
+        for (uint32_t k = 0; k < S->n_cells && !bad; k++)
+            bad = fastf_fidelity_row(S->L->barcode[k], S->h_ufull[k], S->h_upc[k], S->h_gfull[k], S->h_gpc[k], S->h_sxx[k], S->h_syy[k], S->h_sxy[k],
+                                     S->n_features, line, sizeof line) || gt_str(&t, line);
+        snprintf(path, sizeof path, "%s/fidelity.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+        if (bad) return 1;
+    }
+    fputs(row, F->tsv.f);
+    T->fidelity += fastf_res_now() - tt;
+    return 0;
+}
+
+int fastf_res_fid_close(res_fid_t *F, int ok)
+{
+    if (!F->on) return 0;
+    F->on = 0;
+    return fastf_res_tsv_close(&F->tsv, ok);
 }
 
 /* ------------------------------------------------------------------ */
@@ -939,8 +1057,8 @@ int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_gr
 
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
 {
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz"};
-    for (int k = 0; k < 5; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv"};
+    for (int k = 0; k < 6; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
 }
 
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
@@ -956,11 +1074,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -974,7 +1092,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1002,6 +1120,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'S': out->summary_only = 1; break;
         case 'G': out->genes = 1; break;
         case 'C': out->per_cell = 1; break;
+        case 'F': out->fidelity = 1; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
         }

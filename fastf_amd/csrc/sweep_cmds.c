@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells]; -d accepted
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity]; -d accepted
  *                  and ignored, -u refused
  *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
@@ -18,6 +18,9 @@
  * --cells: behind every point its keys sorted fully, K3u's rows and their reduction along the cell axis and into the copy-number
  * histogram (fastf_res_point_cells: fastf_dev_umi_rows, fastf_dev_copy_summary) into sweep_cells.tsv and the point's cells.tsv.gz;
  * resident form only — a job outside it is refused with the flag.
+ * --fidelity: behind every open the pair's full-depth rows — one more decision plane, every hit kept — stay on the device
+ * (fastf_res_full_run); behind every point its rows are joined with them (fastf_res_point_fidelity: fastf_dev_fidelity) into
+ * sweep_fidelity.tsv and the point's fidelity.tsv.gz; resident form only, as --cells.
  * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
  * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
  * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
@@ -289,6 +292,111 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
 }
 
 /* ------------------------------------------------------------------ */
+/* --fidelity: the host twin, the metrics, the rows                    */
+/* ------------------------------------------------------------------ */
+/* the host form of fastf_dev_fidelity: both COOs ascend by (cell, feature), so the partner of a point row lies behind the partner of
+ * the row before it — one forward walk of the full rows */
+int fastf_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, uint64_t *sum_xy, uint64_t *sum_yy)
+{
+    if (!full || !point || (n_cells && (!sum_xy || !sum_yy)) || (point->nnz && (!point->feature || !point->cell || !point->count)) ||
+        (full->nnz && (!full->feature || !full->cell || !full->count))) return sw_err("null argument");
+    memset(sum_xy, 0, (size_t)n_cells * sizeof *sum_xy);
+    memset(sum_yy, 0, (size_t)n_cells * sizeof *sum_yy);
+    size_t j = 0;
+    for (size_t i = 0; i < point->nnz; i++) {
+        const uint64_t key = ((uint64_t)point->cell[i] << 32) | point->feature[i];
+        while (j < full->nnz && (((uint64_t)full->cell[j] << 32) | full->feature[j]) < key) j++;
+        if (j == full->nnz || full->cell[j] != point->cell[i] || full->feature[j] != point->feature[i])
+            return sw_err("fidelity: point row %zu (cell %u, feature %u) has no partner among the full rows (device error bits 0x%x)", i, point->cell[i],
+                          point->feature[i], FASTF_ERR_NO_PARTNER);
+        const uint32_t c = point->cell[i] - 1u;
+        if (c >= n_cells) continue;
+        sum_xy[c] += (uint64_t)full->count[j] * point->count[i];
+        sum_yy[c] += (uint64_t)point->count[i] * point->count[i];
+    }
+    return 0;
+}
+
+int fastf_fidelity_metrics(uint64_t umis_full, uint64_t umis, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features,
+                           double *pearson, double *cosine)
+{
+    typedef __int128 i128;
+    const i128 G = (i128)n_features;
+    const i128 num = G * (i128)sum_xy - (i128)umis_full * (i128)umis;
+    const i128 dx = G * (i128)sum_xx - (i128)umis_full * (i128)umis_full, dy = G * (i128)sum_yy - (i128)umis * (i128)umis;
+    int defined = 0;
+    if (dx > 0 && dy > 0) {                                 /* (never negative for counts over G genes: Cauchy-Schwarz) */
+        if (pearson) *pearson = (double)num / (sqrt((double)dx) * sqrt((double)dy));
+        defined |= 1;
+    }
+    if (sum_xx && sum_yy) {
+        if (cosine) *cosine = (double)sum_xy / (sqrt((double)sum_xx) * sqrt((double)sum_yy));
+        defined |= 2;
+    }
+    return defined;
+}
+
+const char *fastf_fidelity_header(void) { return "barcode\tumis_full\tumis\tgenes_full\tgenes\tsum_xx\tsum_yy\tsum_xy\tpearson\tcosine\n"; }
+#define FIDELITY_COLUMNS_TAIL "seed\tn_cells\tcells_defined\tmedian_pearson\tp10_pearson\tmean_pearson\tmedian_cosine\tumis_kept\tgenes_kept\n"
+const char *fastf_sweep_fidelity_header(void) { return "rate_cell\trate_depth\t" FIDELITY_COLUMNS_TAIL; }
+const char *fastf_cap_fidelity_header(void) { return "rate_cell\treads_per_cell\t" FIDELITY_COLUMNS_TAIL; }
+const char *fastf_level_fidelity_header(void) { return "rate_cell\tumi_cap\t" FIDELITY_COLUMNS_TAIL; }
+
+int fastf_fidelity_row(const char *barcode, uint64_t umis_full, uint64_t umis, uint64_t genes_full, uint64_t genes, uint64_t sum_xx,
+                       uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features, char *buf, size_t cap)
+{
+    if (!barcode || !buf) return sw_err("null argument");
+    double p = 0.0, c = 0.0;
+    const int defined = fastf_fidelity_metrics(umis_full, umis, sum_xx, sum_yy, sum_xy, n_features, &p, &c);
+    char ps[40], cs[40];
+    if (defined & 1) snprintf(ps, sizeof ps, "%.6f", p); else snprintf(ps, sizeof ps, "NA");
+    if (defined & 2) snprintf(cs, sizeof cs, "%.6f", c); else snprintf(cs, sizeof cs, "NA");
+    const int n = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\t%s\n", barcode, (unsigned long long)umis_full, (unsigned long long)umis,
+                           (unsigned long long)genes_full, (unsigned long long)genes, (unsigned long long)sum_xx, (unsigned long long)sum_yy,
+                           (unsigned long long)sum_xy, ps, cs);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("fidelity row too long") : 0;
+}
+
+static int cmp_dbl(const void *a, const void *b) { const double x = *(const double *)a, y = *(const double *)b; return x < y ? -1 : x > y; }
+/* the rule of median_u64 on ascending values */
+static double median_sorted(const double *v, size_t n) { return (n & 1) ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0; }
+
+int fastf_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const uint64_t *umis_full,
+                               const uint64_t *umis, const uint32_t *genes_full, const uint32_t *genes, const uint64_t *sum_xx,
+                               const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_cells, uint64_t n_features, char *buf, size_t cap)
+{
+    if (!buf || (n_cells && (!umis_full || !umis || !genes_full || !genes || !sum_xx || !sum_yy || !sum_xy))) return sw_err("null argument");
+    double *pe = (double *)malloc(((size_t)n_cells + 1) * 2 * sizeof *pe), *co = pe ? pe + n_cells + 1 : NULL;
+    if (!pe) return sw_err("out of memory");
+    size_t nd = 0;
+    uint64_t su = 0, suf = 0, sg = 0, sgf = 0;
+    for (uint32_t k = 0; k < n_cells; k++) {
+        double p = 0.0, c = 0.0;
+        su += umis[k]; suf += umis_full[k]; sg += genes[k]; sgf += genes_full[k];
+        if (fastf_fidelity_metrics(umis_full[k], umis[k], sum_xx[k], sum_yy[k], sum_xy[k], n_features, &p, &c) & 1) { pe[nd] = p; co[nd] = c; nd++; }
+    }
+    char f[6][40];
+    if (nd) {
+        qsort(pe, nd, sizeof *pe, cmp_dbl);
+        qsort(co, nd, sizeof *co, cmp_dbl);
+        double sum = 0.0;
+        for (size_t k = 0; k < nd; k++) sum += pe[k];
+        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(pe, nd));
+        snprintf(f[1], sizeof f[1], "%.6f", pe[(size_t)floor(0.1 * (double)(nd - 1))]);
+        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
+        snprintf(f[3], sizeof f[3], "%.6f", median_sorted(co, nd));
+    } else for (int k = 0; k < 4; k++) snprintf(f[k], sizeof f[k], "NA");
+    free(pe);
+    if (suf) snprintf(f[4], sizeof f[4], "%.6f", (double)su / (double)suf); else snprintf(f[4], sizeof f[4], "NA");
+    if (sgf) snprintf(f[5], sizeof f[5], "%.6f", (double)sg / (double)sgf); else snprintf(f[5], sizeof f[5], "NA");
+    char second[32];
+    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, nd, f[0], f[1], f[2], f[3], f[4], f[5]);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -408,11 +516,12 @@ done:
  * K1a, the planes, then every depth rate */
 static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
                            float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           res_genes_t *G, res_cells_t *C, res_reps_t *P, uint32_t k, res_times_t *T)
+                           res_genes_t *G, res_cells_t *C, res_fid_t *Fd, res_reps_t *P, uint32_t k, res_times_t *T)
 {
     int rc = RES_FAIL;
     void *d_planes = NULL;
-    uint64_t *thr = (uint64_t *)malloc(n_r * sizeof *thr);
+    const uint32_t n_planes = n_r + (Fd->on ? 1u : 0u);     /* --fidelity: one more plane behind the grid's, every hit kept */
+    uint64_t *thr = (uint64_t *)malloc(n_planes * sizeof *thr);
     if (!thr) { sw_err("out of memory"); goto done; }
     if ((rc = fastf_res_rate_open(S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
     rc = RES_FAIL;
@@ -421,10 +530,15 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
 
     /* the decision planes: the draw stream once, every threshold in the same pass */
     const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
-    if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_r * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_r * plane_words * 4)) goto done;
+    if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_planes * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_planes * plane_words * 4)) goto done;
     for (uint32_t j = 0; j < n_r; j++) thr[j] = fastf_draw_threshold(rd_list[j]);
-    if (fastf_dev_mt_decisions_multi(S->e, seed, L->mt_skip, H, thr, n_r, (uint32_t *)d_planes, plane_words, NULL)) goto done;
+    if (Fd->on) thr[n_r] = (uint64_t)1 << 32;
+    if (fastf_dev_mt_decisions_multi(S->e, seed, L->mt_skip, H, thr, n_planes, (uint32_t *)d_planes, plane_words, NULL)) goto done;
     T->planes += fastf_res_now() - tt;
+    if (Fd->on) {                                           /* the full rows of the pair, once */
+        const int frc = fastf_res_full_run(S, (const uint32_t *)d_planes + (size_t)n_r * plane_words, T);
+        if (frc != RES_OK) { rc = frc; goto done; }
+    }
 
     for (uint32_t j = 0; j < n_r; j++) {
         char base[64], name[96], dir[4096], row[512];
@@ -438,6 +552,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         if (summary_row_(rate_cell, rd_list[j], seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, row, sizeof row, metrics) ||
             fastf_res_reps_point(P, j, k, S->n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
+        if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
@@ -447,6 +562,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
             snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
             if (fastf_res_point_write(S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
         }
+        if (fastf_res_fid_point(Fd, S, summary_only ? NULL : dir, rd_list[j], 0, T)) goto done;
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
@@ -473,7 +589,7 @@ done:
 
 static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
                           const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int summary_only,
-                          int device, FILE *tsv, res_genes_t *G, res_cells_t *C, res_reps_t *P)
+                          int device, FILE *tsv, res_genes_t *G, res_cells_t *C, res_fid_t *Fd, res_reps_t *P)
 {
     int rc = RES_FAIL;
     const int prof = getenv("FASTF_PROFILE") != NULL;
@@ -492,6 +608,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
+    S.fidelity = Fd->on;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
@@ -503,7 +620,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
         if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
         for (uint32_t k = 0; k < n_s; k++) {
             const uint32_t at = i * n_s + k;
-            rc = sweep_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], rd_list, n_r, seeds[k], summary_only, device, tsv, G, C, P, k, &T);
+            rc = sweep_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], rd_list, n_r, seeds[k], summary_only, device, tsv, G, C, Fd, P, k, &T);
             if (rc != RES_OK) goto done;
         }
         if (fastf_res_reps_rate_end(P, rc_list[i], rd_list, NULL, &T)) { rc = RES_FAIL; goto done; }
@@ -518,6 +635,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if (prof && G->on) fprintf(stderr, "[sweep] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
     if (prof && C->on) fprintf(stderr, "[sweep] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
                                T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
+    if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
 done:
     fastf_res_rate_close(&S);
     fastf_res_free(&R);
@@ -536,14 +654,16 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS)) return sw_err("sweep: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY)) return sw_err("sweep: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0, cells = (flags & FASTF_SWEEP_CELLS) != 0;
+    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
     if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
+    if (several && fidelity) return sw_err("sweep: --fidelity needs the resident form, and this job is outside it (several devices)");
     if (fastf_res_make_dir(out_dir)) return 1;
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
@@ -551,12 +671,18 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
+    res_fid_t Fd;
+    if (fastf_res_fid_open(&Fd, fidelity, "sweep", out_dir, fastf_sweep_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1;
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
 
-    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &P);
+    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
+    if (rc == RES_NOT_COVERED && fidelity) {                /* (the full rows live on the device alone: bam2db() point by point has none) */
+        sw_err("sweep: --fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
     if (rc == RES_NOT_COVERED && cells) {
         /* (the per-cell rows come from the device's keys alone: bam2db() point by point has none.  Wide keys and a UMI length set
          * beyond the key are known before the first point; a UMI found too long among the records stops the point that meets it) */
@@ -579,10 +705,11 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     }
     if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
     if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
+    if (!rc && fastf_res_fid_close(&Fd, 1)) rc = 1;
     if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, rates_depth, NULL)) rc = 1;
     if (rc) {
         char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_reps_close(&P, 0);
+        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); fastf_res_reps_close(&P, 0);
         if (reps) fastf_res_reps_unlink_tables(out_dir, "sweep");      /* (the tables that were already renamed go too: none is left) */
         fastf_set_error_(keep);
         return 1;
@@ -631,6 +758,9 @@ static void usage_sweep(FILE *f)
             "        --summary-only    write sweep.tsv alone\n"
             "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n"
             "        --cells           per-cell reads, saturation and UMI copy numbers too: sweep_cells.tsv and cells.tsv.gz per point\n"
+            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
+            "                          sweep_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
+            "                          over ALL genes per cell (not log-normalised); resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -653,7 +783,7 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0);
+    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0);
     if (A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
@@ -662,6 +792,7 @@ int cmd_sweep(int argc, const char **argv)
     if (A.genes && A.n_seeds) printf("sweep_genes.tsv, sweep_genes_reps.tsv and sweep_gene_reps.tsv.gz are generated.\n");
     else if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
+    if (A.fidelity) printf("sweep_fidelity.tsv is generated.\n");
     if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;

@@ -10,6 +10,7 @@
 #include "level_kernels.hpp"
 #include "gene_kernels.hpp"
 #include "cells_kernels.hpp"
+#include "fidelity_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -1103,6 +1104,34 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
     return 0;
 } FASTF_CATCH_INT
 
+// --fidelity: a point's rows joined with the full-depth rows of its (cell rate, seed) pair (fidelity_kernel).  Both row sets ascend
+// by (cell, feature) and every point row has its partner among the full rows; d_sum_xy[c - 1] = the sum of x * y over the point
+// rows of cell c, d_sum_yy[c - 1] = the sum of y * y.  Both arrays are cleared here first; *d_nnz_full and *d_nnz rows are read.
+// d_err: the word a missing partner raises FASTF_ERR_NO_PARTNER in (NULL: the engine's own error word).  Synchronises the stream
+// and fails when that bit is set in the word, whichever call raised it: clear it to go on.
+static_assert(ERR_NO_PARTNER == FASTF_ERR_NO_PARTNER, "the error bit of fidelity_kernel and the ABI's");
+extern "C" int fastf_dev_fidelity(fastf_engine_t* e, const uint32_t* d_feature_full, const uint32_t* d_cell_full, const uint32_t* d_count_full,
+                                  const uint64_t* d_nnz_full, const uint32_t* d_feature, const uint32_t* d_cell, const uint32_t* d_count,
+                                  const uint64_t* d_nnz, uint32_t n_cells, uint64_t* d_sum_xy, uint64_t* d_sum_yy, uint64_t* d_err, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_nnz_full || !d_nnz || (n_cells && (!d_sum_xy || !d_sum_yy)), "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_cells) {
+        HIP_OK(hipMemsetAsync(d_sum_xy, 0, (size_t)n_cells * sizeof(u64), s));
+        HIP_OK(hipMemsetAsync(d_sum_yy, 0, (size_t)n_cells * sizeof(u64), s));
+    }
+    if (!d_feature || !d_cell || !d_count) return 0;    // (no row buffer: a join of nothing)
+    if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_fidelity: point rows and no full rows");
+    u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
+    hipLaunchKernelGGL(fidelity_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
+                       (const u64*)d_nnz_full, d_feature, d_cell, d_count, (const u64*)d_nnz, n_cells, (u64*)d_sum_xy, (u64*)d_sum_yy, err);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 bits = 0;
+    if (copy_d2h(&bits, err, sizeof bits)) return 1;
+    if (bits & ERR_NO_PARTNER) return set_err("fastf_dev_fidelity: a point row has no partner among the full rows (device error bits 0x%llx)", (unsigned long long)bits);
+    return 0;
+} FASTF_CATCH_INT
+
 // Per-gene summary of COO rows in any order (gene_summary_kernel): d_cells_per_gene[g - 1] = rows of gene g with count >= 1,
 // d_umis_per_gene[g - 1] = the sum of their counts.  Both arrays are cleared here first; *d_nnz rows are read.  The sum of all
 // counts is below 2^32 (the LDS form keeps both numbers of a gene in one 64-bit counter).
@@ -1771,20 +1800,21 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------
 // host-buffer streaming API
 // ------------------------------------------------------------------------------------
 static const char* err_bits_text(u64 bits) {
-    static thread_local char buf[256];
-    snprintf(buf, sizeof buf, "device error bits 0x%llx:%s%s%s%s%s", (unsigned long long)bits,
+    static thread_local char buf[400];
+    snprintf(buf, sizeof buf, "device error bits 0x%llx:%s%s%s%s%s%s", (unsigned long long)bits,
              (bits & 1) ? " (unknown bit 0);" : "",
              (bits & ERR_DRAWS_SHORT) ? " draw stream shorter than CB hits;" : "",
              (bits & ERR_UMI_TOOLONG) ? " UMI longer than umi_max_bases (raise it: up to 32, with fastf_batch_t.umi_ext from 17 on);" : "",
              (bits & ERR_KEYS_FULL) ? " key store full;" : "",
-             (bits & ERR_RUN_TOO_LONG) ? " unsorted run longer than the group-only path handles: sort fully (drop FASTF_SORT_SKIP_LOW);" : "");
+             (bits & ERR_RUN_TOO_LONG) ? " unsorted run longer than the group-only path handles: sort fully (drop FASTF_SORT_SKIP_LOW);" : "",
+             (bits & ERR_NO_PARTNER) ? " a point row without a partner among the full rows (fastf_dev_fidelity);" : "");
     return buf;
 }
 

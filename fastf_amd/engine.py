@@ -422,6 +422,15 @@ class Engine:
         probes into d_probe (0 for a cell that is not open), d_out[0] = cells still open"""
         check(self._L.fastf_dev_level_step(self._h, d_umis_per_cell, n_cells, int(umi_cap), d_lo, d_hi, d_probe, d_out, d_err_in or None, stream))
 
+    def dev_fidelity(self, d_feature_full, d_cell_full, d_count_full, d_nnz_full, d_feature, d_cell, d_count, d_nnz, n_cells, d_sum_xy, d_sum_yy,
+                     d_err=0, stream=0):
+        """--fidelity: point rows joined with full rows, both ascending by (cell, feature) on the device -> d_sum_xy[c - 1] = the sum of
+        x * y over the point rows of cell c, d_sum_yy[c - 1] = the sum of y * y (u64[n_cells] each, cleared by the call).  A point row
+        without a partner among the full rows raises bit 32 in *d_err (u64 on the device; 0 / None: the engine's error word) and the
+        call raises FastfError; synchronises the stream"""
+        check(self._L.fastf_dev_fidelity(self._h, d_feature_full or None, d_cell_full or None, d_count_full or None, d_nnz_full, d_feature or None,
+                                         d_cell or None, d_count or None, d_nnz, n_cells, d_sum_xy, d_sum_yy, d_err or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

@@ -11,6 +11,7 @@ from ._lib import Coo, UmiRows
 SUMMARY_ONLY = 1      # FASTF_SWEEP_SUMMARY_ONLY
 GENES = 2             # FASTF_SWEEP_GENES
 CELLS = 8             # FASTF_SWEEP_CELLS
+FIDELITY = 32         # FASTF_SWEEP_FIDELITY
 COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
@@ -18,6 +19,9 @@ GENES_COLUMNS = ("rate_cell", "rate_depth", "seed", "genes_detected", "genes_min
 CELLS_TAIL_COLUMNS = (("seed", "valid_reads", "null_umi_reads", "umis", "singleton_umis", "median_reads_per_cell")
                       + tuple("copies_%d" % k for k in range(1, COPY_BINS)) + ("copies_%d_plus" % COPY_BINS, "reads_copies_%d_plus" % COPY_BINS))
 CELLS_COLUMNS = ("rate_cell", "rate_depth") + CELLS_TAIL_COLUMNS
+FIDELITY_TAIL_COLUMNS = ("seed", "n_cells", "cells_defined", "median_pearson", "p10_pearson", "mean_pearson", "median_cosine", "umis_kept", "genes_kept")
+FIDELITY_COLUMNS = ("rate_cell", "rate_depth") + FIDELITY_TAIL_COLUMNS
+POINT_FIDELITY_COLUMNS = ("barcode", "umis_full", "umis", "genes_full", "genes", "sum_xx", "sum_yy", "sum_xy", "pearson", "cosine")     # <point dir>/fidelity.tsv.gz
 POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
@@ -26,17 +30,23 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _flags(summary_only, genes, cells, fidelity):
+    return (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
+
+
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False):
+          cells: bool = False, fidelity: bool = False):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
-    out/sweep_cells.tsv (read_cells_table) and a cells.tsv.gz per point directory"""
+    out/sweep_cells.tsv (read_cells_table) and a cells.tsv.gz per point directory; fidelity=True also leaves out/sweep_fidelity.tsv
+    (read_fidelity_table) and a fidelity.tsv.gz per point directory (read_point_fidelity): every point against the full-depth data
+    of the same cells"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -46,7 +56,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False):
+               cells: bool = False, fidelity: bool = False):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -55,8 +65,62 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                           (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0)))
+                                           _flags(summary_only, genes, cells, fidelity)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
+
+
+def read_fidelity_table(path, columns=FIDELITY_COLUMNS):
+    """the rows of sweep_fidelity.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_fidelity(path):
+    """the rows of a point's fidelity.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_FIDELITY_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_FIDELITY_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def fidelity_header(verb: str = "") -> str:
+    """the header of fidelity.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_fidelity.tsv"""
+    return getattr(_lib.lib(), "fastf_%sfidelity_header" % (verb + "_" if verb else ""))().decode()
+
+
+def fidelity_row(barcode, umis_full, umis, genes_full, genes, sum_xx, sum_yy, sum_xy, n_features) -> str:
+    """one row of fidelity.tsv.gz (with its newline) from the seven integers of a cell and the number of features"""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_fidelity_row(barcode.encode() if isinstance(barcode, str) else barcode, int(umis_full), int(umis), int(genes_full),
+                                             int(genes), int(sum_xx), int(sum_yy), int(sum_xy), int(n_features), buf, len(buf)))
+    return buf.value.decode()
+
+
+def fidelity_summary_row(rate_cell, rate_depth, seed, umis_full, umis, genes_full, genes, sum_xx, sum_yy, sum_xy, n_features, list_value: int = 0) -> str:
+    """one row of <verb>_fidelity.tsv (with its newline); list_value >= 1: that integer in the second column (cap, level)"""
+    a64 = [np.ascontiguousarray(a, dtype=np.uint64) for a in (umis_full, umis, sum_xx, sum_yy, sum_xy)]
+    g = [np.ascontiguousarray(a, dtype=np.uint32) for a in (genes_full, genes)]
+    n = len(a64[0])
+    assert all(len(a) == n for a in a64 + g)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_fidelity_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), a64[0].ctypes.data,
+                                                     a64[1].ctypes.data, g[0].ctypes.data, g[1].ctypes.data, a64[2].ctypes.data, a64[3].ctypes.data,
+                                                     a64[4].ctypes.data, n, int(n_features), buf, len(buf)))
+    return buf.value.decode()
+
+
+def fidelity_from_coo(full, point, n_cells: int):
+    """(sum_xy u64[n_cells], sum_yy u64[n_cells]) of a point COO joined with the full COO — each a (feature, cell, count) triple ascending by
+    (cell, feature): the host form of Engine.dev_fidelity; raises FastfError on a point row without a partner"""
+    p32 = C.POINTER(C.c_uint32)
+    keep, coos = [], []
+    for f, c, k in (full, point):
+        arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (f, c, k)]
+        assert len(arrs[0]) == len(arrs[1]) == len(arrs[2])
+        keep.append(arrs)
+        coos.append(Coo(arrs[0].ctypes.data_as(p32), arrs[1].ctypes.data_as(p32), arrs[2].ctypes.data_as(p32), len(arrs[0])))
+    sxy, syy = np.zeros(max(n_cells, 1), np.uint64), np.zeros(max(n_cells, 1), np.uint64)
+    _lib.check(_lib.lib().fastf_fidelity_from_coo(C.byref(coos[0]), C.byref(coos[1]), n_cells, sxy.ctypes.data, syy.ctypes.data))
+    return sxy[:n_cells], syy[:n_cells]
 
 
 REPS_METRICS = ("sampled_reads", "sampled_valid_reads", "nnz", "umis", "saturation", "median_umis_per_cell", "median_genes_per_cell")

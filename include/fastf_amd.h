@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -241,6 +241,52 @@ const char *fastf_level_genes_reps_header(void);
 int fastf_level_summary_row(float rate_cell, uint64_t umi_cap, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                             const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits,
                             uint32_t cells_capped, char *buf, size_t cap);
+
+/* --- --fidelity on sweep, cap and level (FASTF_*_FIDELITY, flag 32; `fidelity=True` in Python): how well every grid point still
+ * reproduces the full-depth data of the same cells.
+ * For a (cell rate, seed) pair, the FULL MATRIX X is what a point gives when every CB hit of the pair's sampled cells is kept: the
+ * all-ones decision plane — cap's T = 2^32, level's pass 0.  It is not `-r 1.0`, which drops a draw of 0xFFFFFFFF.
+ * For a grid point with matrix Y, and every sampled cell k, in the order of barcodes.tsv.gz:
+ *   umis_full  = sum over g of x             umis  = sum over g of y
+ *   genes_full = rows of X with count >= 1   genes = rows of Y with count >= 1
+ *   sum_xx = sum of x^2      sum_yy = sum of y^2
+ *   sum_xy = sum of x * y, over the rows of Y, each joined with the row of X of the same (cell, feature)
+ * All seven are u64 and exact: every sum is at most (sum of x)^2 < 2^64, because the sum of all counts is below 2^32.  Every point of
+ * a pair keeps a subset of the pair's hits, so every row of Y has its partner in X; a row without one is an error
+ * (FASTF_ERR_NO_PARTNER).
+ * With G = the number of features, in exact 128-bit integers:
+ *   num = G * sum_xy - umis_full * umis      dx = G * sum_xx - umis_full^2      dy = G * sum_yy - umis^2
+ *   pearson = (double)num / (sqrt((double)dx) * sqrt((double)dy)), or NA when dx == 0 or dy == 0
+ *   cosine  = (double)sum_xy / (sqrt((double)sum_xx) * sqrt((double)sum_yy)), or NA when either sum is 0
+ * Both are printed %.6f.  They are correlations of the RAW counts over ALL G genes (the zeros included), not of log-normalised values.
+ *   <point dir>/fidelity.tsv.gz (not with --summary-only): a header and one row per sampled cell:
+ *     barcode umis_full umis genes_full genes sum_xx sum_yy sum_xy pearson cosine
+ *   <out_dir>/<verb>_fidelity.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), as <verb>.tsv —
+ *     through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells cells_defined median_pearson p10_pearson mean_pearson median_cosine umis_kept genes_kept
+ *     cells_defined = the cells whose pearson is not NA (their cosine is defined too); the four statistics run over those cells:
+ *     the median by the rule of <verb>.tsv's medians (the mean of the two middle values for an even number), p10 = the value at index
+ *     floor(0.1 * (n - 1)) of the ascending values, the mean summed in ascending order; all four NA when cells_defined == 0.
+ *     umis_kept = sum of umis / sum of umis_full, genes_kept likewise (NA when the denominator is 0).  All %.6f.
+ * Every other output is the bytes it is without the flag.  A job outside the resident form (keys wider than 64 bits, UMIs beyond what a
+ * 64-bit key holds, several devices) is refused with the flag, as with --cells. --- */
+#define FASTF_SWEEP_FIDELITY 32u             /* bits 4 and 16 are not assigned: tests/test_genes_host.py and tests/test_cells_host.py pin them as the unknown bits that are refused */
+#define FASTF_CAP_FIDELITY   32u
+#define FASTF_LEVEL_FIDELITY 32u
+const char *fastf_fidelity_header(void);          /* the header of fidelity.tsv.gz */
+const char *fastf_sweep_fidelity_header(void);    /* the headers of <verb>_fidelity.tsv */
+const char *fastf_cap_fidelity_header(void);
+const char *fastf_level_fidelity_header(void);
+/* one row of fidelity.tsv.gz (with its newline) from the seven integers of a cell */
+int fastf_fidelity_row(const char *barcode, uint64_t umis_full, uint64_t umis, uint64_t genes_full, uint64_t genes, uint64_t sum_xx,
+                       uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features, char *buf, size_t cap);
+/* the two metrics of a cell; returns bit 0: pearson is defined, bit 1: cosine is defined (an undefined one is left untouched) */
+int fastf_fidelity_metrics(uint64_t umis_full, uint64_t umis, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features,
+                           double *pearson, double *cosine);
+/* one row of <verb>_fidelity.tsv (with its newline); the second column as fastf_genes_summary_row prints it (list_value == 0: rate_depth) */
+int fastf_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const uint64_t *umis_full,
+                               const uint64_t *umis, const uint32_t *genes_full, const uint32_t *genes, const uint64_t *sum_xx,
+                               const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_cells, uint64_t n_features, char *buf, size_t cap);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -422,6 +468,11 @@ int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint
  * form of fastf_dev_copy_summary, by the same rules: a row with nonnull[i] == 0 is a NULL row, a row whose cell is outside
  * 1 .. n_cells adds nothing to the per-cell arrays, a row with n_copy == 0 is in no bin */
 int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, uint32_t *reads, uint32_t *null_reads, uint32_t *single, uint64_t *hist);
+
+/* --fidelity (section 1): sum_xy[c - 1] and sum_yy[c - 1] (n_cells entries each, cleared first) of a point COO joined with the full
+ * COO, both ascending by (cell, feature) — the host form of fastf_dev_fidelity; fails on a point row without a partner among the
+ * full rows (nothing is read outside the arrays).  A row whose cell is outside 1 .. n_cells adds nothing */
+int fastf_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, uint64_t *sum_xy, uint64_t *sum_yy);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -659,6 +710,17 @@ int fastf_dev_level_init(fastf_engine_t *e, const uint64_t *d_umis_full, uint32_
                          uint64_t *d_probe, uint64_t *d_out, const uint64_t *d_err_in, void *stream);
 int fastf_dev_level_step(fastf_engine_t *e, const uint64_t *d_umis_per_cell, uint32_t n_cells, uint64_t umi_cap, uint64_t *d_lo, uint64_t *d_hi,
                          uint64_t *d_probe, uint64_t *d_out, const uint64_t *d_err_in, void *stream);
+
+/* --fidelity (section 1): the join of a point's rows with the full rows of its pair (fidelity_kernel).  Both row sets lie on the
+ * device, ascending by (cell, feature): what fastf_dev_rows_gather leaves; *d_nnz_full and *d_nnz (device, u64) rows are read.
+ * d_sum_xy[c - 1] = the sum of x * y over the point rows of cell c, d_sum_yy[c - 1] = the sum of y * y (u64, n_cells entries each,
+ * cleared by the call).  The same call on (X, X) gives sum_xx.  A point row without a partner raises FASTF_ERR_NO_PARTNER in *d_err
+ * (device, u64; NULL: the engine's own error word) and counts with x = 0; nothing outside the arrays is read.  The call synchronises
+ * the stream and fails while that bit is set in the word.  A cell index outside 1 .. n_cells writes nothing. */
+#define FASTF_ERR_NO_PARTNER 32u
+int fastf_dev_fidelity(fastf_engine_t *e, const uint32_t *d_feature_full, const uint32_t *d_cell_full, const uint32_t *d_count_full,
+                       const uint64_t *d_nnz_full, const uint32_t *d_feature, const uint32_t *d_cell, const uint32_t *d_count,
+                       const uint64_t *d_nnz, uint32_t n_cells, uint64_t *d_sum_xy, uint64_t *d_sum_yy, uint64_t *d_err, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
