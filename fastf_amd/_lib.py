@@ -127,6 +127,10 @@ ABI_SYMBOLS = [
     # --fidelity of sweep, cap and level
     "fastf_fidelity_header", "fastf_sweep_fidelity_header", "fastf_cap_fidelity_header", "fastf_level_fidelity_header", "fastf_fidelity_row",
     "fastf_fidelity_metrics", "fastf_fidelity_summary_row", "fastf_fidelity_from_coo", "fastf_dev_fidelity",
+    # --gene-fidelity of sweep, cap and level
+    "fastf_gene_fidelity_header", "fastf_sweep_gene_fidelity_header", "fastf_cap_gene_fidelity_header", "fastf_level_gene_fidelity_header",
+    "fastf_gene_fidelity_row", "fastf_gene_fidelity_metrics", "fastf_gene_fidelity_summary_row", "fastf_gene_fidelity_from_coo",
+    "fastf_dev_partner_counts", "fastf_dev_gene_moments",
 ]
 
 
@@ -345,6 +349,14 @@ def lib():
     L.fastf_fidelity_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, vp, vp, vp, vp, vp, u32, u64, C.c_char_p, sz]
     L.fastf_fidelity_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, vp]
     L.fastf_dev_fidelity.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    for name in ("fastf_gene_fidelity_header", "fastf_sweep_gene_fidelity_header", "fastf_cap_gene_fidelity_header", "fastf_level_gene_fidelity_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_gene_fidelity_row.argtypes = [C.c_char_p, u64, u64, u64, u64, u64, u64, u64, u64, C.c_char_p, sz]
+    L.fastf_gene_fidelity_metrics.argtypes = [u64, u64, u64, u64, u64, u64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.fastf_gene_fidelity_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, vp, vp, vp, vp, vp, u32, C.c_char_p, sz]
+    L.fastf_gene_fidelity_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, vp, vp, vp, vp, vp, vp]
+    L.fastf_dev_partner_counts.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fastf_dev_gene_moments.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -38,6 +38,34 @@ __device__ __forceinline__ u64 fid_lower_bound(const u32* __restrict__ xc, const
     return lo;
 }
 
+// One turn of the join's walk (see fidelity_kernel): the partner's count of this lane's `key` into x and found = true; the chunk
+// state (cur, ckey, ccnt, have) goes on to the turn behind.  last_key: the largest key of the turn (uniform).
+__device__ __forceinline__ void fid_partner(const u32* __restrict__ xf, const u32* __restrict__ xc, const u32* __restrict__ xk, u64 m, u64 key, u64 last_key,
+                                            int lane, u64& cur, u64& ckey, u32& ccnt, bool& have, u32& x, bool& found) {
+    constexpr u64 KEY_END = ~0ull;                                         // above every key of a row
+    for (;;) {                                                             // (uniform)
+        if (!have) {
+            const u64 j = cur + (u64)lane;
+            const bool in = j < m;
+            ckey = in ? fid_key(xc, xf, j) : KEY_END;
+            ccnt = in ? xk[j] : 0u;
+            have = true;
+        }
+        int pos = 0;                                                       // the chunk lanes below `pos` hold keys below mine
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const u64 kk = __shfl(ckey, pos + s - 1, WAVE);
+            if (kk < key) pos += s;
+        }
+        const u64 kk = __shfl(ckey, pos, WAVE);
+        const u32 xx = __shfl(ccnt, pos, WAVE);
+        if (!found && kk == key) { x = xx; found = true; }
+        const u64 chunk_last = fid_readlane64(ckey, WAVE - 1);
+        if (chunk_last >= last_key) break;                                 // every key of the turn has met its place
+        cur += WAVE; have = false;
+    }
+}
+
 __device__ __forceinline__ void fid_emit(u32 c, u64 xy, u64 yy, u32 prev_c, u32 next_c, u32 n_cells, u64* __restrict__ sum_xy, u64* __restrict__ sum_yy) {
     if (c - 1u >= n_cells) return;                                         // (a cell index the caller did not size the arrays for: nothing is written)
     if (c == prev_c || c == next_c) { atomicAdd(sum_xy + (c - 1u), xy); atomicAdd(sum_yy + (c - 1u), yy); }
@@ -90,27 +118,7 @@ __global__ __launch_bounds__(FID_THREADS) void fidelity_kernel(const u32* __rest
         const int n_valid = (int)(b - base < (u64)WAVE ? b - base : (u64)WAVE);
         const u64 last_key = fid_readlane64(key, n_valid - 1);             // the largest key of the turn (uniform)
         u32 x = 0; bool found = !valid;
-        for (;;) {                                                         // (uniform)
-            if (!have) {
-                const u64 j = cur + (u64)lane;
-                const bool in = j < m;
-                ckey = in ? fid_key(xc, xf, j) : KEY_END;
-                ccnt = in ? xk[j] : 0u;
-                have = true;
-            }
-            int pos = 0;                                                   // the chunk lanes below `pos` hold keys below mine
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) {
-                const u64 kk = __shfl(ckey, pos + s - 1, WAVE);
-                if (kk < key) pos += s;
-            }
-            const u64 kk = __shfl(ckey, pos, WAVE);
-            const u32 xx = __shfl(ccnt, pos, WAVE);
-            if (!found && kk == key) { x = xx; found = true; }
-            const u64 chunk_last = fid_readlane64(ckey, WAVE - 1);
-            if (chunk_last >= last_key) break;                             // every key of the turn has met its place
-            cur += WAVE; have = false;
-        }
+        fid_partner(xf, xc, xk, m, key, last_key, lane, cur, ckey, ccnt, have, x, found);
         missing |= !found;
         u64 xy = (u64)x * (u64)y, yy = (u64)y * (u64)y;
 #pragma unroll

@@ -156,6 +156,8 @@ void fastf_res_rate_close(res_rate_t *S)
     fastf_devmem_free(S->d_level);
     fastf_devmem_free(S->d_full); fastf_devmem_free(S->d_fid);
     if (S->h_fid) fastf_pinned_free(S->h_fid);
+    fastf_devmem_free(S->d_gx); fastf_devmem_free(S->d_gfid);
+    if (S->h_gfid) fastf_pinned_free(S->h_gfid);
     memset(S, 0, sizeof *S);
 }
 
@@ -184,7 +186,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; }
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; }
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -249,6 +251,26 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
             return RES_FAIL;
         }
         S->h_rpc = (uint32_t *)((char *)S->h_hist + RES_CELLS_HIST_BYTES); S->h_npc = S->h_rpc + n_cells; S->h_spc = S->h_npc + n_cells;
+    }
+    if (S->gene_fid && !S->fidelity) {                      /* the full rows of the pair, for --gene-fidelity alone */
+        if (dev_room(&S->d_full, &S->have.full, (N ? N : 1) * 12, device)) {
+            rs_err("%s: the full-depth rows of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 12), fastf_last_error());
+            return RES_FAIL;
+        }
+        S->full_nnz = 0;
+    }
+    if (S->gene_fid) {                                      /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once */
+        const size_t nf1 = (size_t)S->n_features + 1, dev_bytes = nf1 * 48, pin_bytes = nf1 * 48;
+        if (dev_room(&S->d_gx, &S->have.gx, (N ? N : 1) * 4, device) || dev_room(&S->d_gfid, &S->have.gfid, dev_bytes, device) ||
+            pin_room((void **)&S->h_gfid, &S->have.h_gfid, pin_bytes)) {
+            rs_err("%s: the partner column and the per-gene sums of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 4 + dev_bytes), fastf_last_error());
+            return RES_FAIL;
+        }
+        S->gfid_stride = S->have.gfid / 48;
+        const size_t hs = S->have.h_gfid / 48;              /* (entries per array, of the block as it was allocated) */
+        S->h_gsx = S->h_gfid; S->h_gsxx = S->h_gsx + hs; S->h_gsy = S->h_gsxx + hs; S->h_gsyy = S->h_gsy + hs; S->h_gsxy = S->h_gsyy + hs;
+        S->h_gcf = (uint32_t *)(S->h_gsxy + hs); S->h_gc = S->h_gcf + hs;
+        if (genes) { S->h_gsy = S->h_upg; S->h_gc = S->h_cpg; }      /* (the point's own two are --genes') */
     }
     if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
         const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
@@ -462,17 +484,29 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
 /* ------------------------------------------------------------------ */
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
-    if (!S->fidelity) return 0;
+    if (!S->fidelity && !S->gene_fid) return 0;
     const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
     uint64_t *const sm = (uint64_t *)S->d_small;
     const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
     uint32_t *const x_f = (uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
     uint64_t *const d_sxy = (uint64_t *)S->d_fid, *const d_sxx = d_sxy + 2 * S->fid_stride;
-    const double tt = fastf_res_now();
+    double tt = fastf_res_now();
     if (nnz > N) return rs_err("internal error: %llu full-depth rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N);
     if (fastf_devmem_copy(x_f, d_f, (size_t)nnz * 4) || fastf_devmem_copy(x_c, d_c, (size_t)nnz * 4) || fastf_devmem_copy(x_k, d_k, (size_t)nnz * 4) ||
         fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
     S->full_nnz = nnz;
+    if (S->gene_fid) {                                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
+        const size_t gs = S->gfid_stride;
+        uint64_t *const g_sx = (uint64_t *)S->d_gfid, *const g_sxx = g_sx + gs;
+        uint32_t *const g_cf = (uint32_t *)(g_sx + 5 * gs);
+        if (fastf_dev_gene_summary(S->e, nnz ? x_f : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_features, g_cf, g_sx, NULL) ||
+            fastf_dev_gene_moments(S->e, nnz ? x_f : NULL, nnz ? x_k : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_features, NULL, g_sxx, NULL) ||
+            fastf_devmem_sync()) return 1;
+        if (S->n_features && (fastf_devmem_copy(S->h_gsx, g_sx, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gsxx, g_sxx, (size_t)S->n_features * 8) ||
+                              fastf_devmem_copy(S->h_gcf, g_cf, (size_t)S->n_features * 4))) return 1;
+        T->gene_fid += fastf_res_now() - tt; tt = fastf_res_now();
+    }
+    if (!S->fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
      * first point overwrites) */
     if (fastf_dev_fidelity(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? x_f : NULL, nnz ? x_c : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_cells, d_sxy, d_sxx, NULL, NULL)) return 1;
@@ -484,7 +518,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 
 int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
 {
-    if (!S->fidelity) return RES_OK;
+    if (!S->fidelity && !S->gene_fid) return RES_OK;
     char name[64];
     uint64_t counters[3], nnz = 0;
     const res_times_t before = *T;
@@ -493,7 +527,7 @@ int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
     const int prc = fastf_res_point_run(S, d_plane, name, counters, &nnz, T);
     if (prc != RES_OK) return prc;
     *T = before;                                            /* (the stages of this point are the flag's own) */
-    T->fidelity += fastf_res_now() - tt;
+    *(S->fidelity ? &T->fidelity : &T->gene_fid) += fastf_res_now() - tt;
     return fastf_res_full_keep(S, T) ? RES_FAIL : RES_OK;
 }
 
@@ -512,6 +546,31 @@ int fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t 
     }
     if (fastf_devmem_copy(S->h_sxy, d_sxy, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_syy, d_syy, (size_t)S->n_cells * 8)) return 1;
     T->fidelity += fastf_res_now() - tt;
+    return 0;
+}
+
+int fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->gene_fid) return 0;
+    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    const uint32_t *const x_f = (const uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
+    const size_t gs = S->gfid_stride;
+    uint64_t *const g_sy = (uint64_t *)S->d_gfid + 2 * gs, *const g_syy = g_sy + gs, *const g_sxy = g_syy + gs;
+    uint32_t *const g_c = (uint32_t *)((uint64_t *)S->d_gfid + 5 * gs) + gs, *const d_x = (uint32_t *)S->d_gx;
+    const double tt = fastf_res_now();
+    if (fastf_dev_partner_counts(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? d_f : NULL, nnz ? d_c : NULL, sm + SM_NNZ, d_x, NULL, NULL)) {
+        char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
+        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, keep);
+    }
+    /* (with --genes fastf_res_point_run has left the point's sum_y and cells in S->h_upg and S->h_cpg) */
+    if ((!S->genes && fastf_dev_gene_summary(S->e, nnz ? d_f : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, g_c, g_sy, NULL)) ||
+        fastf_dev_gene_moments(S->e, nnz ? d_f : NULL, nnz ? d_x : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, g_sxy, g_syy, NULL) ||
+        fastf_devmem_sync()) return 1;
+    if (S->n_features && (fastf_devmem_copy(S->h_gsyy, g_syy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gsxy, g_sxy, (size_t)S->n_features * 8) ||
+                          (!S->genes && (fastf_devmem_copy(S->h_gsy, g_sy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gc, g_c, (size_t)S->n_features * 4))))) return 1;
+    T->gene_fid += fastf_res_now() - tt;
     return 0;
 }
 
@@ -727,20 +786,53 @@ int fastf_res_cells_close(res_cells_t *C, int ok)
 /* ------------------------------------------------------------------ */
 /* --fidelity: the table, a point's file                               */
 /* ------------------------------------------------------------------ */
-int fastf_res_fid_open(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header)
+int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, const char *out_dir, const char *header, const char *gene_header)
 {
     memset(F, 0, sizeof *F);
-    if (!on) return 0;
+    if (!on && !gene_on) return 0;
     char name[64];
-    snprintf(name, sizeof name, "%s_fidelity.tsv", verb);
     F->verb = verb;
-    if (fastf_res_tsv_open(&F->tsv, out_dir, name, header)) return 1;
-    F->on = 1;
+    if (on) {
+        snprintf(name, sizeof name, "%s_fidelity.tsv", verb);
+        if (fastf_res_tsv_open(&F->tsv, out_dir, name, header)) return 1;
+    }
+    if (gene_on) {
+        snprintf(name, sizeof name, "%s_gene_fidelity.tsv", verb);
+        if (fastf_res_tsv_open(&F->gtsv, out_dir, name, gene_header)) { fastf_res_tsv_close(&F->tsv, 0); return 1; }
+    }
+    F->on = on; F->gene_on = gene_on; F->full = 1;
+    return 0;
+}
+
+/* --gene-fidelity: the row of the point and — dir != NULL — its gene_fidelity.tsv.gz */
+static int gene_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    char row[640];
+    if (fastf_gene_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->h_gsx, S->h_gsy, S->h_gsxx, S->h_gsyy, S->h_gsxy,
+                                        S->n_features, row, sizeof row)) return 1;
+    if (dir) {
+        char path[4200], line[640];
+        gtext t = { NULL, 0, 0 };
+        int bad = gt_str(&t, fastf_gene_fidelity_header());
+        for (uint32_t g = 0; g < S->n_features && !bad; g++)
+            bad = fastf_gene_fidelity_row(S->L->feat_id[g], S->n_cells, S->h_gsx[g], S->h_gsy[g], S->h_gcf[g], S->h_gc[g], S->h_gsxx[g], S->h_gsyy[g],
+                                          S->h_gsxy[g], line, sizeof line) || gt_str(&t, line);
+        snprintf(path, sizeof path, "%s/gene_fidelity.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+        if (bad) return 1;
+    }
+    fputs(row, F->gtsv.f);
     return 0;
 }
 
 int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T)
 {
+    if (F->gene_on) {
+        const double tt = fastf_res_now();
+        if (gene_fid_point(F, S, dir, rate_depth, list_value)) return 1;
+        T->gene_fid += fastf_res_now() - tt;
+    }
     if (!F->on) return 0;
     const double tt = fastf_res_now();
     char row[640];
@@ -765,9 +857,16 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
 
 int fastf_res_fid_close(res_fid_t *F, int ok)
 {
-    if (!F->on) return 0;
-    F->on = 0;
-    return fastf_res_tsv_close(&F->tsv, ok);
+    if (!F->on && !F->gene_on) return 0;
+    /* both tables are closed before either is renamed, and a rename that fails takes the other table back: none is left alone */
+    res_tsv_t *const t[2] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL};
+    int bad = 0, renamed = 0;
+    const char *failed = NULL;
+    for (int k = 0; k < 2; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
+    for (int k = 0; k < 2 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
+    if (!ok || bad) for (int k = 0; k < 2; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
+    F->on = F->gene_on = F->full = 0;
+    return ok && bad ? rs_err("cannot write %s", failed) : 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1057,8 +1156,8 @@ int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_gr
 
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
 {
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv"};
-    for (int k = 0; k < 6; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv"};
+    for (int k = 0; k < 7; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
 }
 
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
@@ -1074,11 +1173,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1092,7 +1191,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1121,6 +1220,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'G': out->genes = 1; break;
         case 'C': out->per_cell = 1; break;
         case 'F': out->fidelity = 1; break;
+        case 'Q': out->gene_fidelity = 1; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
         }

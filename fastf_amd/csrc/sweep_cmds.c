@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity]; -d accepted
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity]; -d accepted
  *                  and ignored, -u refused
  *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
@@ -21,6 +21,8 @@
  * --fidelity: behind every open the pair's full-depth rows — one more decision plane, every hit kept — stay on the device
  * (fastf_res_full_run); behind every point its rows are joined with them (fastf_res_point_fidelity: fastf_dev_fidelity) into
  * sweep_fidelity.tsv and the point's fidelity.tsv.gz; resident form only, as --cells.
+ * --gene-fidelity: the same pair of row sets per gene (fastf_res_point_gene_fidelity: fastf_dev_partner_counts, fastf_dev_gene_moments)
+ * into sweep_gene_fidelity.tsv and the point's gene_fidelity.tsv.gz; it keeps the full rows by itself.
  * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
  * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
  * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
@@ -397,6 +399,135 @@ int fastf_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_
 }
 
 /* ------------------------------------------------------------------ */
+/* --gene-fidelity: the host twin, the metrics, the rows, the ranking   */
+/* ------------------------------------------------------------------ */
+/* the host form of fastf_dev_partner_counts + fastf_dev_gene_moments + fastf_dev_gene_summary on both row sets: the walk of
+ * fastf_fidelity_from_coo, every sum kept per gene */
+int fastf_gene_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_features, uint64_t *sum_x, uint64_t *sum_y,
+                                 uint64_t *cells_full, uint64_t *cells, uint64_t *sum_xx, uint64_t *sum_yy, uint64_t *sum_xy)
+{
+    if (!full || !point || (n_features && (!sum_x || !sum_y || !cells_full || !cells || !sum_xx || !sum_yy || !sum_xy)) ||
+        (point->nnz && (!point->feature || !point->cell || !point->count)) || (full->nnz && (!full->feature || !full->cell || !full->count)))
+        return sw_err("null argument");
+    uint64_t *const all[7] = {sum_x, sum_y, cells_full, cells, sum_xx, sum_yy, sum_xy};
+    for (int k = 0; k < 7; k++) memset(all[k], 0, (size_t)n_features * sizeof(uint64_t));
+    for (size_t j = 0; j < full->nnz; j++) {
+        const uint32_t g = full->feature[j] - 1u;
+        if (g >= n_features) continue;
+        const uint64_t x = full->count[j];
+        sum_x[g] += x; cells_full[g] += x >= 1; sum_xx[g] += x * x;
+    }
+    size_t j = 0;
+    for (size_t i = 0; i < point->nnz; i++) {
+        const uint64_t key = ((uint64_t)point->cell[i] << 32) | point->feature[i];
+        while (j < full->nnz && (((uint64_t)full->cell[j] << 32) | full->feature[j]) < key) j++;
+        if (j == full->nnz || full->cell[j] != point->cell[i] || full->feature[j] != point->feature[i])
+            return sw_err("gene fidelity: point row %zu (cell %u, feature %u) has no partner among the full rows (device error bits 0x%x)", i, point->cell[i],
+                          point->feature[i], FASTF_ERR_NO_PARTNER);
+        const uint32_t g = point->feature[i] - 1u;
+        if (g >= n_features) continue;
+        const uint64_t y = point->count[i];
+        sum_y[g] += y; cells[g] += y >= 1; sum_yy[g] += y * y; sum_xy[g] += (uint64_t)full->count[j] * y;
+    }
+    return 0;
+}
+
+int fastf_gene_fidelity_metrics(uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy,
+                                double *pearson, double *disp_full, double *disp)
+{
+    typedef __int128 i128;
+    const i128 n = (i128)n_cells;
+    const i128 num = n * (i128)sum_xy - (i128)sum_x * (i128)sum_y;
+    const i128 dx = n * (i128)sum_xx - (i128)sum_x * (i128)sum_x, dy = n * (i128)sum_yy - (i128)sum_y * (i128)sum_y;
+    int defined = 0;
+    if (dx > 0 && dy > 0) {                                 /* (never negative for counts over n cells: Cauchy-Schwarz) */
+        if (pearson) *pearson = (double)num / (sqrt((double)dx) * sqrt((double)dy));
+        defined |= 1;
+    }
+    if (n_cells >= 2 && sum_x) {
+        if (disp_full) *disp_full = (double)dx / ((double)(n_cells - 1) * (double)sum_x);
+        defined |= 2;
+    }
+    if (n_cells >= 2 && sum_y) {
+        if (disp) *disp = (double)dy / ((double)(n_cells - 1) * (double)sum_y);
+        defined |= 4;
+    }
+    return defined;
+}
+
+const char *fastf_gene_fidelity_header(void) { return "feature\tsum_x\tsum_y\tcells_full\tcells\tsum_xx\tsum_yy\tsum_xy\tpearson\tdisp_full\tdisp\n"; }
+#define GENE_FIDELITY_COLUMNS_TAIL "seed\tn_cells\tgenes_full\tgenes_defined\tmedian_pearson\tp10_pearson\tmean_pearson\thvg_k\thvg_overlap\n"
+const char *fastf_sweep_gene_fidelity_header(void) { return "rate_cell\trate_depth\t" GENE_FIDELITY_COLUMNS_TAIL; }
+const char *fastf_cap_gene_fidelity_header(void) { return "rate_cell\treads_per_cell\t" GENE_FIDELITY_COLUMNS_TAIL; }
+const char *fastf_level_gene_fidelity_header(void) { return "rate_cell\tumi_cap\t" GENE_FIDELITY_COLUMNS_TAIL; }
+
+int fastf_gene_fidelity_row(const char *feature, uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t cells_full, uint64_t cells, uint64_t sum_xx,
+                            uint64_t sum_yy, uint64_t sum_xy, char *buf, size_t cap)
+{
+    if (!feature || !buf) return sw_err("null argument");
+    double v[3] = {0.0, 0.0, 0.0};
+    const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy, &v[0], &v[1], &v[2]);
+    char f[3][48];
+    for (int k = 0; k < 3; k++) if (defined & (1 << k)) snprintf(f[k], sizeof f[k], "%.6f", v[k]); else snprintf(f[k], sizeof f[k], "NA");
+    const int n = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\t%s\t%s\n", feature, (unsigned long long)sum_x, (unsigned long long)sum_y,
+                           (unsigned long long)cells_full, (unsigned long long)cells, (unsigned long long)sum_xx, (unsigned long long)sum_yy,
+                           (unsigned long long)sum_xy, f[0], f[1], f[2]);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("gene fidelity row too long") : 0;
+}
+
+/* the ranking of the highly variable genes: descending value, ties by ascending feature index */
+typedef struct { double v; uint32_t g; } hvg_item;
+static int cmp_hvg(const void *a, const void *b)
+{
+    const hvg_item *x = (const hvg_item *)a, *y = (const hvg_item *)b;
+    if (x->v != y->v) return x->v > y->v ? -1 : 1;
+    return x->g < y->g ? -1 : x->g > y->g;
+}
+
+int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, const uint64_t *sum_x,
+                                    const uint64_t *sum_y, const uint64_t *sum_xx, const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_features,
+                                    char *buf, size_t cap)
+{
+    if (!buf || (n_features && (!sum_x || !sum_y || !sum_xx || !sum_yy || !sum_xy))) return sw_err("null argument");
+    double *pe = (double *)malloc(((size_t)n_features + 1) * sizeof *pe);
+    hvg_item *A = (hvg_item *)malloc(((size_t)n_features + 1) * 2 * sizeof *A), *B = A ? A + n_features + 1 : NULL;
+    uint8_t *inA = (uint8_t *)calloc((size_t)n_features + 1, 1);
+    if (!pe || !A || !inA) { free(pe); free(A); free(inA); return sw_err("out of memory"); }
+    size_t nd = 0, na = 0, nb = 0;
+    uint32_t genes_full = 0;
+    for (uint32_t g = 0; g < n_features; g++) {
+        double p = 0.0, dfull = 0.0, d = 0.0;
+        const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x[g], sum_y[g], sum_xx[g], sum_yy[g], sum_xy[g], &p, &dfull, &d);
+        genes_full += sum_x[g] > 0;
+        if (defined & 1) pe[nd++] = p;
+        if (defined & 2) { A[na].v = dfull; A[na].g = g; na++; }
+        if (defined & 4) { B[nb].v = d; B[nb].g = g; nb++; }
+    }
+    const size_t K = na < FASTF_HVG_TOP ? na : FASTF_HVG_TOP, KB = nb < K ? nb : K;
+    size_t both = 0;
+    qsort(A, na, sizeof *A, cmp_hvg);
+    qsort(B, nb, sizeof *B, cmp_hvg);
+    for (size_t k = 0; k < K; k++) inA[A[k].g] = 1;
+    for (size_t k = 0; k < KB; k++) both += inA[B[k].g];
+    char f[4][40];
+    if (nd) {
+        qsort(pe, nd, sizeof *pe, cmp_dbl);
+        double sum = 0.0;
+        for (size_t k = 0; k < nd; k++) sum += pe[k];
+        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(pe, nd));
+        snprintf(f[1], sizeof f[1], "%.6f", pe[(size_t)floor(0.1 * (double)(nd - 1))]);
+        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
+    } else for (int k = 0; k < 3; k++) snprintf(f[k], sizeof f[k], "NA");
+    if (K) snprintf(f[3], sizeof f[3], "%.6f", (double)both / (double)K); else snprintf(f[3], sizeof f[3], "NA");
+    free(pe); free(A); free(inA);
+    char second[32];
+    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%zu\t%s\n", (double)rate_cell, second, seed, n_cells, genes_full, nd, f[0], f[1], f[2], K, f[3]);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -520,7 +651,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
 {
     int rc = RES_FAIL;
     void *d_planes = NULL;
-    const uint32_t n_planes = n_r + (Fd->on ? 1u : 0u);     /* --fidelity: one more plane behind the grid's, every hit kept */
+    const uint32_t n_planes = n_r + (Fd->full ? 1u : 0u);   /* --fidelity, --gene-fidelity: one more plane behind the grid's, every hit kept */
     uint64_t *thr = (uint64_t *)malloc(n_planes * sizeof *thr);
     if (!thr) { sw_err("out of memory"); goto done; }
     if ((rc = fastf_res_rate_open(S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
@@ -532,10 +663,10 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
     const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
     if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_planes * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_planes * plane_words * 4)) goto done;
     for (uint32_t j = 0; j < n_r; j++) thr[j] = fastf_draw_threshold(rd_list[j]);
-    if (Fd->on) thr[n_r] = (uint64_t)1 << 32;
+    if (Fd->full) thr[n_r] = (uint64_t)1 << 32;
     if (fastf_dev_mt_decisions_multi(S->e, seed, L->mt_skip, H, thr, n_planes, (uint32_t *)d_planes, plane_words, NULL)) goto done;
     T->planes += fastf_res_now() - tt;
-    if (Fd->on) {                                           /* the full rows of the pair, once */
+    if (Fd->full) {                                         /* the full rows of the pair, once */
         const int frc = fastf_res_full_run(S, (const uint32_t *)d_planes + (size_t)n_r * plane_words, T);
         if (frc != RES_OK) { rc = frc; goto done; }
     }
@@ -553,6 +684,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
             fastf_res_reps_point(P, j, k, S->n_cells, metrics)) goto done;
         T->summary += fastf_res_now() - tt;
         if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
+        if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
@@ -608,7 +740,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
@@ -636,6 +768,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if (prof && C->on) fprintf(stderr, "[sweep] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
                                T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
+    if (prof && Fd->gene_on) fprintf(stderr, "[sweep] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
 done:
     fastf_res_rate_close(&S);
     fastf_res_free(&R);
@@ -654,16 +787,18 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY)) return sw_err("sweep: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY)) return sw_err("sweep: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0, cells = (flags & FASTF_SWEEP_CELLS) != 0;
-    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0;
+    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0, gene_fidelity = (flags & FASTF_SWEEP_GENE_FIDELITY) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
     if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
+    if (several && fidelity && gene_fidelity) return sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (several devices)");
     if (several && fidelity) return sw_err("sweep: --fidelity needs the resident form, and this job is outside it (several devices)");
+    if (several && gene_fidelity) return sw_err("sweep: --gene-fidelity needs the resident form, and this job is outside it (several devices)");
     if (fastf_res_make_dir(out_dir)) return 1;
     res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
     if (tsv_open(&tsv, out_dir)) return 1;
@@ -672,15 +807,23 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     res_cells_t C;
     if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
     res_fid_t Fd;
-    if (fastf_res_fid_open(&Fd, fidelity, "sweep", out_dir, fastf_sweep_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
+    if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "sweep", out_dir, fastf_sweep_fidelity_header(), fastf_sweep_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
 
     int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
+    if (rc == RES_NOT_COVERED && fidelity && gene_fidelity) {
+        sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
     if (rc == RES_NOT_COVERED && fidelity) {                /* (the full rows live on the device alone: bam2db() point by point has none) */
         sw_err("sweep: --fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
+    if (rc == RES_NOT_COVERED && gene_fidelity && !fidelity) {
+        sw_err("sweep: --gene-fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
         rc = RES_FAIL;
     }
     if (rc == RES_NOT_COVERED && cells) {
@@ -761,6 +904,10 @@ static void usage_sweep(FILE *f)
             "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
             "                          sweep_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
             "                          over ALL genes per cell (not log-normalised); resident form only\n"
+            "        --gene-fidelity   every point against the full-depth data of the same cells, per GENE: sweep_gene_fidelity.tsv and\n"
+            "                          gene_fidelity.tsv.gz per point, with the Pearson of the RAW counts over ALL sampled cells per gene,\n"
+            "                          the dispersion (variance / mean) at full depth and at the point, and the overlap of the 2000\n"
+            "                          most variable genes; resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -783,7 +930,8 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0);
+    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0) |
+                           (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0);
     if (A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
@@ -793,6 +941,7 @@ int cmd_sweep(int argc, const char **argv)
     else if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
     if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
     if (A.fidelity) printf("sweep_fidelity.tsv is generated.\n");
+    if (A.gene_fidelity) printf("sweep_gene_fidelity.tsv is generated.\n");
     if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;

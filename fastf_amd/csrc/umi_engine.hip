@@ -11,6 +11,7 @@
 #include "gene_kernels.hpp"
 #include "cells_kernels.hpp"
 #include "fidelity_kernels.hpp"
+#include "gene_fidelity_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -240,6 +241,7 @@ struct fastf_engine {
     bool mtwords_kept = false; u32 mtwords_seed = 0; u64 mtwords_skip = 0, mtwords_n = 0;
     bool cap_lds_attr = false;
     bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
+    bool gmom_lds_attr = false;          // the same for gene_moments_kernel<true>
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
     bool mt_par_ready = false;               // the parallel generator's one-time init went through: tables up, kernel attributes set, d_mtseq there
@@ -1168,6 +1170,63 @@ extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_featu
     return 0;
 } FASTF_CATCH_INT
 
+// --gene-fidelity: d_x[i] = the count of the full row with the (cell, feature) of point row i (partner_counts_kernel): the join of
+// fastf_dev_fidelity, stored per row.  Both row sets ascend by (cell, feature); *d_nnz_full and *d_nnz rows are read, *d_nnz entries of
+// d_x are written.  d_err, the synchronisation and the failure on FASTF_ERR_NO_PARTNER: as fastf_dev_fidelity; such a row gets x = 0.
+extern "C" int fastf_dev_partner_counts(fastf_engine_t* e, const uint32_t* d_feature_full, const uint32_t* d_cell_full, const uint32_t* d_count_full,
+                                        const uint64_t* d_nnz_full, const uint32_t* d_feature, const uint32_t* d_cell, const uint64_t* d_nnz,
+                                        uint32_t* d_x, uint64_t* d_err, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_nnz_full || !d_nnz, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (!d_feature || !d_cell) return 0;                // (no row buffer: a join of nothing)
+    if (!d_x) return set_err("fastf_dev_partner_counts: point rows and no partner column");
+    if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_partner_counts: point rows and no full rows");
+    u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
+    hipLaunchKernelGGL(partner_counts_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
+                       (const u64*)d_nnz_full, d_feature, d_cell, (const u64*)d_nnz, d_x, err);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 bits = 0;
+    if (copy_d2h(&bits, err, sizeof bits)) return 1;
+    if (bits & ERR_NO_PARTNER) return set_err("fastf_dev_partner_counts: a point row has no partner among the full rows (device error bits 0x%llx)", (unsigned long long)bits);
+    return 0;
+} FASTF_CATCH_INT
+
+// --gene-fidelity: per gene the sums of a * b and of b * b over rows (feature, a, b) in any order (gene_moments_kernel):
+// d_sum_ab[g - 1] and d_sum_bb[g - 1], u64, n_features entries each, cleared here first; *d_nnz rows are read.  Every sum stays below
+// 2^64 (the sum of all counts is below 2^32).  d_sum_ab == NULL: sum_bb alone.  Stream-ordered.
+extern "C" int fastf_dev_gene_moments(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_a, const uint32_t* d_b, const uint64_t* d_nnz,
+                                      uint32_t n_features, uint64_t* d_sum_ab, uint64_t* d_sum_bb, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_nnz || (n_features && !d_sum_bb), "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (!n_features) return 0;
+    if (d_sum_ab) HIP_OK(hipMemsetAsync(d_sum_ab, 0, (size_t)n_features * sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(d_sum_bb, 0, (size_t)n_features * sizeof(u64), s));
+    if (!d_feature || !d_a || !d_b) return 0;           // (no row buffer: a reduce of nothing)
+    // as fastf_dev_gene_summary: up to GMOM_LDS_RANGES ranges of GMOM_LDS_GENES genes take the LDS form;
+    // FASTF_GENE_MOMENTS_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs)
+    const u32 n_ranges = (n_features + GMOM_LDS_GENES - 1) / GMOM_LDS_GENES;
+    const char* mr = getenv("FASTF_GENE_MOMENTS_LDS_RANGES");
+    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), GMOM_LDS_RANGES) : GMOM_LDS_RANGES;
+    if (n_ranges <= max_ranges) {
+        const size_t lds = (size_t)std::min<u32>(n_features, GMOM_LDS_GENES) * 2 * sizeof(u64);
+        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
+        if (!e->gmom_lds_attr) {                                 // (per engine, on first use: the attribute belongs to the current device's function)
+            HIP_OK(hipFuncSetAttribute((const void*)gene_moments_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GMOM_LDS_GENES * 2 * sizeof(u64))));
+            e->gmom_lds_attr = true;
+        }
+        const u32 groups = std::max<u32>(1u, per_cu * (u32)g_cu_count / n_ranges);
+        hipLaunchKernelGGL(gene_moments_kernel<true>, dim3(groups * n_ranges), dim3(GENE_THREADS), lds, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
+                           (u64*)d_sum_ab, (u64*)d_sum_bb, n_ranges);
+    } else {
+        hipLaunchKernelGGL(gene_moments_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
+                           (u64*)d_sum_ab, (u64*)d_sum_bb, 1u);
+    }
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "gene moments");
+    return 0;
+} FASTF_CATCH_INT
+
 // Replicate runs: d_cells_per_gene (what fastf_dev_gene_summary left, still on the device) added into the three u64[n_features]
 // accumulators of a grid point (gene_reps_kernel).  Nothing is cleared here: the caller zeroes the accumulators before the first seed.
 extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cells_per_gene, uint32_t n_features, uint64_t* d_detected,
@@ -1800,7 +1859,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

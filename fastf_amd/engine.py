@@ -431,6 +431,18 @@ class Engine:
         check(self._L.fastf_dev_fidelity(self._h, d_feature_full or None, d_cell_full or None, d_count_full or None, d_nnz_full, d_feature or None,
                                          d_cell or None, d_count or None, d_nnz, n_cells, d_sum_xy, d_sum_yy, d_err or None, stream))
 
+    def dev_partner_counts(self, d_feature_full, d_cell_full, d_count_full, d_nnz_full, d_feature, d_cell, d_nnz, d_x, d_err=0, stream=0):
+        """--gene-fidelity: d_x[i] (u32) = the count of the full row with the (cell, feature) of point row i; both row sets ascend by
+        (cell, feature) on the device.  A point row without a partner gets x = 0, raises bit 32 in *d_err (0 / None: the engine's error
+        word) and the call raises FastfError; synchronises the stream"""
+        check(self._L.fastf_dev_partner_counts(self._h, d_feature_full or None, d_cell_full or None, d_count_full or None, d_nnz_full, d_feature or None,
+                                               d_cell or None, d_nnz, d_x or None, d_err or None, stream))
+
+    def dev_gene_moments(self, d_feature, d_a, d_b, d_nnz, n_features, d_sum_ab, d_sum_bb, stream=0):
+        """--gene-fidelity: rows (feature 1-based, a, b) in any order on the device -> d_sum_ab[g - 1] = the sum of a * b, d_sum_bb[g - 1] =
+        the sum of b * b (u64[n_features] each, cleared by the call); stream-ordered"""
+        check(self._L.fastf_dev_gene_moments(self._h, d_feature or None, d_a or None, d_b or None, d_nnz, n_features, d_sum_ab or None, d_sum_bb or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

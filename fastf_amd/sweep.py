@@ -12,6 +12,8 @@ SUMMARY_ONLY = 1      # FASTF_SWEEP_SUMMARY_ONLY
 GENES = 2             # FASTF_SWEEP_GENES
 CELLS = 8             # FASTF_SWEEP_CELLS
 FIDELITY = 32         # FASTF_SWEEP_FIDELITY
+GENE_FIDELITY = 128   # FASTF_SWEEP_GENE_FIDELITY
+HVG_TOP = 2000        # FASTF_HVG_TOP
 COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
@@ -22,6 +24,9 @@ CELLS_COLUMNS = ("rate_cell", "rate_depth") + CELLS_TAIL_COLUMNS
 FIDELITY_TAIL_COLUMNS = ("seed", "n_cells", "cells_defined", "median_pearson", "p10_pearson", "mean_pearson", "median_cosine", "umis_kept", "genes_kept")
 FIDELITY_COLUMNS = ("rate_cell", "rate_depth") + FIDELITY_TAIL_COLUMNS
 POINT_FIDELITY_COLUMNS = ("barcode", "umis_full", "umis", "genes_full", "genes", "sum_xx", "sum_yy", "sum_xy", "pearson", "cosine")     # <point dir>/fidelity.tsv.gz
+GENE_FIDELITY_TAIL_COLUMNS = ("seed", "n_cells", "genes_full", "genes_defined", "median_pearson", "p10_pearson", "mean_pearson", "hvg_k", "hvg_overlap")
+GENE_FIDELITY_COLUMNS = ("rate_cell", "rate_depth") + GENE_FIDELITY_TAIL_COLUMNS
+POINT_GENE_FIDELITY_COLUMNS = ("feature", "sum_x", "sum_y", "cells_full", "cells", "sum_xx", "sum_yy", "sum_xy", "pearson", "disp_full", "disp")     # <point dir>/gene_fidelity.tsv.gz
 POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
@@ -30,23 +35,25 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _flags(summary_only, genes, cells, fidelity):
-    return (SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
+def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False):
+    return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
+            | (GENE_FIDELITY if gene_fidelity else 0))
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
     out/sweep_cells.tsv (read_cells_table) and a cells.tsv.gz per point directory; fidelity=True also leaves out/sweep_fidelity.tsv
     (read_fidelity_table) and a fidelity.tsv.gz per point directory (read_point_fidelity): every point against the full-depth data
-    of the same cells"""
+    of the same cells; gene_fidelity=True the same comparison per gene: out/sweep_gene_fidelity.tsv (read_gene_fidelity_table) and a
+    gene_fidelity.tsv.gz per point directory (read_point_gene_fidelity)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity)))
+                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -56,7 +63,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -65,7 +72,7 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                           _flags(summary_only, genes, cells, fidelity)))
+                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -121,6 +128,68 @@ def fidelity_from_coo(full, point, n_cells: int):
     sxy, syy = np.zeros(max(n_cells, 1), np.uint64), np.zeros(max(n_cells, 1), np.uint64)
     _lib.check(_lib.lib().fastf_fidelity_from_coo(C.byref(coos[0]), C.byref(coos[1]), n_cells, sxy.ctypes.data, syy.ctypes.data))
     return sxy[:n_cells], syy[:n_cells]
+
+
+def read_gene_fidelity_table(path, columns=GENE_FIDELITY_COLUMNS):
+    """the rows of sweep_gene_fidelity.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_gene_fidelity(path):
+    """the rows of a point's gene_fidelity.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_GENE_FIDELITY_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_GENE_FIDELITY_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def gene_fidelity_header(verb: str = "") -> str:
+    """the header of gene_fidelity.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_gene_fidelity.tsv"""
+    return getattr(_lib.lib(), "fastf_%sgene_fidelity_header" % (verb + "_" if verb else ""))().decode()
+
+
+def gene_fidelity_metrics(n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy):
+    """(pearson, disp_full, disp) of a gene over n_cells sampled cells, None where undefined"""
+    v = [C.c_double(), C.c_double(), C.c_double()]
+    d = _lib.lib().fastf_gene_fidelity_metrics(int(n_cells), int(sum_x), int(sum_y), int(sum_xx), int(sum_yy), int(sum_xy), *[C.byref(x) for x in v])
+    return tuple(v[k].value if d & (1 << k) else None for k in range(3))
+
+
+def gene_fidelity_row(feature, n_cells, sum_x, sum_y, cells_full, cells, sum_xx, sum_yy, sum_xy) -> str:
+    """one row of gene_fidelity.tsv.gz (with its newline) from the seven integers of a gene and the number of sampled cells"""
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_gene_fidelity_row(feature.encode() if isinstance(feature, str) else feature, int(n_cells), int(sum_x), int(sum_y),
+                                                  int(cells_full), int(cells), int(sum_xx), int(sum_yy), int(sum_xy), buf, len(buf)))
+    return buf.value.decode()
+
+
+def gene_fidelity_summary_row(rate_cell, rate_depth, seed, n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy, list_value: int = 0) -> str:
+    """one row of <verb>_gene_fidelity.tsv (with its newline), the ranking of the highly variable genes included; list_value >= 1: that
+    integer in the second column (cap, level)"""
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (sum_x, sum_y, sum_xx, sum_yy, sum_xy)]
+    n = len(a[0])
+    assert all(len(x) == n for x in a)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_gene_fidelity_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), int(n_cells),
+                                                          a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data, n,
+                                                          buf, len(buf)))
+    return buf.value.decode()
+
+
+def gene_fidelity_from_coo(full, point, n_features: int):
+    """the seven per-gene arrays (sum_x, sum_y, cells_full, cells, sum_xx, sum_yy, sum_xy: u64[n_features] each) of a point COO and the
+    full COO — each a (feature, cell, count) triple ascending by (cell, feature): the host form of Engine.dev_partner_counts,
+    Engine.dev_gene_moments and Engine.dev_gene_summary together; raises FastfError on a point row without a partner"""
+    p32 = C.POINTER(C.c_uint32)
+    keep, coos = [], []
+    for f, c, k in (full, point):
+        arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (f, c, k)]
+        assert len(arrs[0]) == len(arrs[1]) == len(arrs[2])
+        keep.append(arrs)
+        coos.append(Coo(arrs[0].ctypes.data_as(p32), arrs[1].ctypes.data_as(p32), arrs[2].ctypes.data_as(p32), len(arrs[0])))
+    out = [np.zeros(max(n_features, 1), np.uint64) for _ in range(7)]
+    _lib.check(_lib.lib().fastf_gene_fidelity_from_coo(C.byref(coos[0]), C.byref(coos[1]), n_features, *[x.ctypes.data for x in out]))
+    return tuple(x[:n_features] for x in out)
 
 
 REPS_METRICS = ("sampled_reads", "sampled_valid_reads", "nnz", "umis", "saturation", "median_umis_per_cell", "median_genes_per_cell")

@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -287,6 +287,56 @@ int fastf_fidelity_metrics(uint64_t umis_full, uint64_t umis, uint64_t sum_xx, u
 int fastf_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const uint64_t *umis_full,
                                const uint64_t *umis, const uint32_t *genes_full, const uint32_t *genes, const uint64_t *sum_xx,
                                const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_cells, uint64_t n_features, char *buf, size_t cap);
+
+/* --- --gene-fidelity on sweep, cap and level (FASTF_*_GENE_FIDELITY, flag 128; `gene_fidelity=True` in Python; the long option
+ * alone): the comparison of --fidelity along the other axis — does a gene's expression pattern across the cells survive the
+ * downsampling, and are the genes that full depth ranks as highly variable still ranked so at a point.
+ * For a (cell rate, seed) pair X is the full matrix exactly as --fidelity defines it (the all-ones decision plane, not `-r 1.0`), Y the
+ * matrix of a grid point, n the number of sampled cells (the lines of the point's barcodes.tsv.gz).  For every feature g, over ALL n
+ * sampled cells, zeros included:
+ *   sum_x  = sum of x      cells_full = rows of X of gene g with count >= 1      sum_xx = sum of x^2
+ *   sum_y  = sum of y      cells      = rows of Y of gene g with count >= 1      sum_yy = sum of y^2
+ *   sum_xy = sum of x * y over the rows of Y, each joined with the row of X of the same (cell, feature)
+ * All seven are u64 and exact: every sum is at most (sum of x)^2 < 2^64, because the sum of all counts is below 2^32.  A row of Y
+ * without a partner is an error (FASTF_ERR_NO_PARTNER).
+ * In exact 128-bit integers up to one conversion to double each:
+ *   num = n * sum_xy - sum_x * sum_y      dx = n * sum_xx - sum_x^2      dy = n * sum_yy - sum_y^2
+ *   pearson   = (double)num / (sqrt((double)dx) * sqrt((double)dy)), NA when dx == 0 or dy == 0
+ *   disp_full = (double)dx / ((double)(n - 1) * (double)sum_x), NA when n < 2 or sum_x == 0      (variance / mean of the raw counts)
+ *   disp      = (double)dy / ((double)(n - 1) * (double)sum_y), NA when n < 2 or sum_y == 0
+ * Highly variable genes: K = min(FASTF_HVG_TOP, genes whose disp_full is defined); A = the first K genes by descending disp_full, ties
+ * by ascending feature index; B = the first min(K, genes with disp defined) genes by descending disp, the same tie rule;
+ * hvg_overlap = |A and B| / K, NA when K == 0.  Both ranking values are IEEE doubles computed in the operation order above.
+ *   <point dir>/gene_fidelity.tsv.gz (not with --summary-only): a header and one row per feature in the order of features.tsv.gz, the
+ *     feature named by its id as genes.tsv.gz names it:
+ *     feature sum_x sum_y cells_full cells sum_xx sum_yy sum_xy pearson disp_full disp          (floats %.6f or NA)
+ *   <out_dir>/<verb>_gene_fidelity.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), in the
+ *     row order of <verb>_fidelity.tsv — through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells genes_full genes_defined median_pearson p10_pearson mean_pearson hvg_k hvg_overlap
+ *     genes_full = genes with sum_x > 0; genes_defined = genes whose pearson is not NA; median, p10 and mean by the rules of
+ *     <verb>_fidelity.tsv over those genes, NA when genes_defined == 0; hvg_k = K.
+ * The flag works without --fidelity and --genes and keeps the pair's full rows by itself.  Every other output is the bytes it is
+ * without the flag.  Jobs outside the resident form are refused as --fidelity refuses them.  No _reps aggregate is written. --- */
+#define FASTF_SWEEP_GENE_FIDELITY 128u       /* bits 4, 16 and 64 are not assigned: tests pin them as the unknown bits that are refused */
+#define FASTF_CAP_GENE_FIDELITY   128u
+#define FASTF_LEVEL_GENE_FIDELITY 128u
+#define FASTF_HVG_TOP 2000u
+const char *fastf_gene_fidelity_header(void);          /* the header of gene_fidelity.tsv.gz */
+const char *fastf_sweep_gene_fidelity_header(void);    /* the headers of <verb>_gene_fidelity.tsv */
+const char *fastf_cap_gene_fidelity_header(void);
+const char *fastf_level_gene_fidelity_header(void);
+/* the three metrics of a gene over n_cells sampled cells; returns bit 0: pearson is defined, bit 1: disp_full, bit 2: disp (an
+ * undefined one is left untouched) */
+int fastf_gene_fidelity_metrics(uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy,
+                                double *pearson, double *disp_full, double *disp);
+/* one row of gene_fidelity.tsv.gz (with its newline) from the seven integers of a gene */
+int fastf_gene_fidelity_row(const char *feature, uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t cells_full, uint64_t cells, uint64_t sum_xx,
+                            uint64_t sum_yy, uint64_t sum_xy, char *buf, size_t cap);
+/* one row of <verb>_gene_fidelity.tsv (with its newline), the ranking of the highly variable genes included; the second column as
+ * fastf_genes_summary_row prints it (list_value == 0: rate_depth) */
+int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, const uint64_t *sum_x,
+                                    const uint64_t *sum_y, const uint64_t *sum_xx, const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_features,
+                                    char *buf, size_t cap);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -473,6 +523,12 @@ int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, u
  * COO, both ascending by (cell, feature) — the host form of fastf_dev_fidelity; fails on a point row without a partner among the
  * full rows (nothing is read outside the arrays).  A row whose cell is outside 1 .. n_cells adds nothing */
 int fastf_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, uint64_t *sum_xy, uint64_t *sum_yy);
+
+/* --gene-fidelity (section 1): the seven per-gene arrays (n_features u64 entries each, cleared first) of a point COO and the full COO,
+ * both ascending by (cell, feature) — the host form of fastf_dev_partner_counts, fastf_dev_gene_moments and fastf_dev_gene_summary
+ * together; fails on a point row without a partner.  A row whose feature is outside 1 .. n_features adds nothing */
+int fastf_gene_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_features, uint64_t *sum_x, uint64_t *sum_y,
+                                 uint64_t *cells_full, uint64_t *cells, uint64_t *sum_xx, uint64_t *sum_yy, uint64_t *sum_xy);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -721,6 +777,21 @@ int fastf_dev_level_step(fastf_engine_t *e, const uint64_t *d_umis_per_cell, uin
 int fastf_dev_fidelity(fastf_engine_t *e, const uint32_t *d_feature_full, const uint32_t *d_cell_full, const uint32_t *d_count_full,
                        const uint64_t *d_nnz_full, const uint32_t *d_feature, const uint32_t *d_cell, const uint32_t *d_count,
                        const uint64_t *d_nnz, uint32_t n_cells, uint64_t *d_sum_xy, uint64_t *d_sum_yy, uint64_t *d_err, void *stream);
+
+/* --gene-fidelity (section 1).  fastf_dev_partner_counts (partner_counts_kernel): the join of fastf_dev_fidelity, kept per row —
+ * d_x[i] = the count of the full row with the (cell, feature) of point row i, *d_nnz entries (u32); the row sets, the error word, the
+ * synchronisation and the failure on FASTF_ERR_NO_PARTNER are fastf_dev_fidelity's, and a row without a partner gets x = 0.
+ * fastf_dev_gene_moments (gene_moments_kernel): rows (d_feature 1-based, d_a, d_b) in any order, *d_nnz of them -> d_sum_ab[g - 1] =
+ * the sum of a * b, d_sum_bb[g - 1] = the sum of b * b (u64, n_features entries each, cleared by the call; every sum below 2^64).  A
+ * feature outside 1 .. n_features adds nothing, a row with b == 0 issues no atomic.  d_sum_ab == NULL: d_sum_bb alone, at half the
+ * atomics.  On (X, x, x) it gives sum_xx, on (Y, x of y, y)
+ * sum_xy and sum_yy.  Stream-ordered.  Lists of up to 131 072 features are counted in LDS, range by range; longer ones, and every
+ * list under FASTF_GENE_MOMENTS_LDS_RANGES=0, with global atomics. */
+int fastf_dev_partner_counts(fastf_engine_t *e, const uint32_t *d_feature_full, const uint32_t *d_cell_full, const uint32_t *d_count_full,
+                             const uint64_t *d_nnz_full, const uint32_t *d_feature, const uint32_t *d_cell, const uint64_t *d_nnz,
+                             uint32_t *d_x, uint64_t *d_err, void *stream);
+int fastf_dev_gene_moments(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_a, const uint32_t *d_b, const uint64_t *d_nnz,
+                           uint32_t n_features, uint64_t *d_sum_ab, uint64_t *d_sum_bb, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
