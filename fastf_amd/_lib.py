@@ -131,6 +131,10 @@ ABI_SYMBOLS = [
     "fastf_gene_fidelity_header", "fastf_sweep_gene_fidelity_header", "fastf_cap_gene_fidelity_header", "fastf_level_gene_fidelity_header",
     "fastf_gene_fidelity_row", "fastf_gene_fidelity_metrics", "fastf_gene_fidelity_summary_row", "fastf_gene_fidelity_from_coo",
     "fastf_dev_partner_counts", "fastf_dev_gene_moments",
+    # --neighbors of sweep, cap and level
+    "fastf_neighbors_header", "fastf_sweep_neighbors_header", "fastf_cap_neighbors_header", "fastf_level_neighbors_header", "fastf_hvg_rank",
+    "fastf_neighbors_slot_map", "fastf_neighbors_pad", "fastf_neighbors_check_norm", "fastf_neighbors_row", "fastf_neighbors_summary_row",
+    "fastf_neighbors_from_coo", "fastf_neighbors_shared", "fastf_dev_neighbor_planes", "fastf_dev_neighbors", "fastf_dev_neighbors_shared",
 ]
 
 
@@ -357,6 +361,22 @@ def lib():
     L.fastf_gene_fidelity_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, vp, vp, vp, vp, vp, vp]
     L.fastf_dev_partner_counts.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fastf_dev_gene_moments.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    for name in ("fastf_neighbors_header", "fastf_sweep_neighbors_header", "fastf_cap_neighbors_header", "fastf_level_neighbors_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_hvg_rank.argtypes = [u32, vp, vp, u32, vp, vp]
+    L.fastf_hvg_rank.restype = u32
+    L.fastf_neighbors_slot_map.argtypes = [vp, u32, u32, vp]
+    L.fastf_neighbors_pad.argtypes = [u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.fastf_neighbors_pad.restype = None
+    L.fastf_neighbors_check_norm.argtypes = [u64]
+    L.fastf_neighbors_row.argtypes = [C.c_char_p, u32, u32, u32, C.c_char_p, sz]
+    L.fastf_neighbors_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_neighbors_from_coo.argtypes = [C.POINTER(Coo), u32, vp, u32, u32, vp, vp, vp]
+    L.fastf_neighbors_shared.argtypes = [vp, u32, vp, u32]
+    L.fastf_neighbors_shared.restype = u32
+    L.fastf_dev_neighbor_planes.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, sz, C.POINTER(u32), vp]
+    L.fastf_dev_neighbors.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, C.POINTER(u64), vp]
+    L.fastf_dev_neighbors_shared.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

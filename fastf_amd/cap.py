@@ -13,6 +13,7 @@ GENES = 2             # FASTF_CAP_GENES
 CELLS = 8             # FASTF_CAP_CELLS
 FIDELITY = 32         # FASTF_CAP_FIDELITY
 GENE_FIDELITY = 128   # FASTF_CAP_GENE_FIDELITY
+NEIGHBORS = 512       # FASTF_CAP_NEIGHBORS
 COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
 GENES_COLUMNS = ("rate_cell", "reads_per_cell", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
@@ -22,26 +23,29 @@ fidelity_row, fidelity_from_coo, read_point_fidelity = _sweep.fidelity_row, _swe
 GENE_FIDELITY_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.GENE_FIDELITY_TAIL_COLUMNS
 gene_fidelity_row, gene_fidelity_from_coo, read_point_gene_fidelity = _sweep.gene_fidelity_row, _sweep.gene_fidelity_from_coo, _sweep.read_point_gene_fidelity
 gene_fidelity_metrics = _sweep.gene_fidelity_metrics
+NEIGHBORS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.NEIGHBORS_TAIL_COLUMNS
+neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one function for both verbs)
 
 
 def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-        fidelity: bool = False, gene_fidelity: bool = False):
+        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
     """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
     rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
     out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
     a cells.tsv.gz per point directory; fidelity=True also leaves out/cap_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per
-    point directory; gene_fidelity=True out/cap_gene_fidelity.tsv (read_gene_fidelity_table) and a gene_fidelity.tsv.gz per point directory"""
+    point directory; gene_fidelity=True out/cap_gene_fidelity.tsv (read_gene_fidelity_table) and a gene_fidelity.tsv.gz per point directory;
+    neighbors=True out/cap_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity)))
+                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
 def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-             fidelity: bool = False, gene_fidelity: bool = False):
+             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
@@ -51,7 +55,7 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_cap_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                          n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                         _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity)))
+                                         _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
@@ -86,6 +90,20 @@ def gene_fidelity_header(verb: str = "cap") -> str:
 def gene_fidelity_summary_row(rate_cell, reads_per_cell, seed, n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy) -> str:
     """one row of cap_gene_fidelity.tsv (with its newline)"""
     return _sweep.gene_fidelity_summary_row(rate_cell, 0.0, seed, n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy, list_value=int(reads_per_cell))
+
+
+def read_neighbors_table(path):
+    """the rows of cap_neighbors.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def neighbors_header(verb: str = "cap") -> str:
+    return _sweep.neighbors_header(verb)
+
+
+def neighbors_summary_row(rate_cell, reads_per_cell, seed, hvg_k, k_full, k_point, shared) -> str:
+    """one row of cap_neighbors.tsv (with its newline)"""
+    return _sweep.neighbors_summary_row(rate_cell, 0.0, seed, hvg_k, k_full, k_point, shared, list_value=int(reads_per_cell))
 
 
 def read_reps_table(path):

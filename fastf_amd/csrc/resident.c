@@ -158,6 +158,8 @@ void fastf_res_rate_close(res_rate_t *S)
     if (S->h_fid) fastf_pinned_free(S->h_fid);
     fastf_devmem_free(S->d_gx); fastf_devmem_free(S->d_gfid);
     if (S->h_gfid) fastf_pinned_free(S->h_gfid);
+    fastf_devmem_free(S->d_nplanes); fastf_devmem_free(S->d_nbr);
+    if (S->h_nbr) fastf_pinned_free(S->h_nbr);
     memset(S, 0, sizeof *S);
 }
 
@@ -186,7 +188,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; }
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; }
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -252,16 +254,16 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         }
         S->h_rpc = (uint32_t *)((char *)S->h_hist + RES_CELLS_HIST_BYTES); S->h_npc = S->h_rpc + n_cells; S->h_spc = S->h_npc + n_cells;
     }
-    if (S->gene_fid && !S->fidelity) {                      /* the full rows of the pair, for --gene-fidelity alone */
+    if ((S->gene_fid || S->neighbors) && !S->fidelity) {    /* the full rows of the pair, for --gene-fidelity or --neighbors alone */
         if (dev_room(&S->d_full, &S->have.full, (N ? N : 1) * 12, device)) {
             rs_err("%s: the full-depth rows of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 12), fastf_last_error());
             return RES_FAIL;
         }
         S->full_nnz = 0;
     }
-    if (S->gene_fid) {                                      /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once */
+    if (S->gene_fid || S->neighbors) {                      /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once (--neighbors alone: the pair's sums, which rank A) */
         const size_t nf1 = (size_t)S->n_features + 1, dev_bytes = nf1 * 48, pin_bytes = nf1 * 48;
-        if (dev_room(&S->d_gx, &S->have.gx, (N ? N : 1) * 4, device) || dev_room(&S->d_gfid, &S->have.gfid, dev_bytes, device) ||
+        if ((S->gene_fid && dev_room(&S->d_gx, &S->have.gx, (N ? N : 1) * 4, device)) || dev_room(&S->d_gfid, &S->have.gfid, dev_bytes, device) ||
             pin_room((void **)&S->h_gfid, &S->have.h_gfid, pin_bytes)) {
             rs_err("%s: the partner column and the per-gene sums of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 4 + dev_bytes), fastf_last_error());
             return RES_FAIL;
@@ -271,6 +273,17 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         S->h_gsx = S->h_gfid; S->h_gsxx = S->h_gsx + hs; S->h_gsy = S->h_gsxx + hs; S->h_gsyy = S->h_gsy + hs; S->h_gsxy = S->h_gsyy + hs;
         S->h_gcf = (uint32_t *)(S->h_gsxy + hs); S->h_gc = S->h_gcf + hs;
         if (genes) { S->h_gsy = S->h_upg; S->h_gc = S->h_cpg; }      /* (the point's own two are --genes') */
+    }
+    if (S->neighbors) {                                     /* the slot map of A, both neighbour sets, their counts, the norms and the shared counts; pinned: the map, k_full, k_point, shared.  The planes wait for P (fastf_res_full_keep) */
+        const size_t nc = room_cells, k = FASTF_NEIGHBORS_K, map_bytes = (((size_t)S->n_features + 1) * 2 + 7) & ~(size_t)7;
+        const size_t dev_bytes = map_bytes + nc * (2 * k * 4 + 3 * 4 + 8), pin_bytes = map_bytes + nc * 12 + FASTF_HVG_TOP * 4;
+        if (dev_room(&S->d_nbr, &S->have.nbr, dev_bytes, device) || pin_room((void **)&S->h_nbr, &S->have.h_nbr, pin_bytes)) {
+            rs_err("%s: the neighbour sets of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, dev_bytes, fastf_last_error());
+            return RES_FAIL;
+        }
+        S->nbr_cells = nc; S->nbr_map_bytes = map_bytes;
+        S->h_nkf = (uint32_t *)((char *)S->h_nbr + map_bytes); S->h_nkp = S->h_nkf + nc; S->h_nsh = S->h_nkp + nc; S->h_ngenes = S->h_nsh + nc;
+        S->hvg_k = 0; S->nbr_planes = 0;
     }
     if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
         const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
@@ -482,9 +495,51 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
 /* ------------------------------------------------------------------ */
 /* --fidelity: the full rows of a pair, the join behind a point        */
 /* ------------------------------------------------------------------ */
+/* --neighbors: the device block behind the slot map — idx (n x k) and cnt (n) of the full rows, then of the point, shared (n), norms (n, u64) */
+static uint32_t *nbr_idx(const res_rate_t *S, int point) { return (uint32_t *)((char *)S->d_nbr + S->nbr_map_bytes + S->nbr_cells * 8) + (size_t)point * S->nbr_cells * FASTF_NEIGHBORS_K; }
+static uint32_t *nbr_cnt(const res_rate_t *S, int point) { return nbr_idx(S, 0) + 2 * S->nbr_cells * FASTF_NEIGHBORS_K + (size_t)point * S->nbr_cells; }
+static const char *fastf_last_error_copy(void) { static __thread char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); return keep; }
+
+/* the planes of one row set (P planes: what the largest count of the set needs) and its neighbour sets into the full (point == 0) or
+ * the point's half of the block */
+static int nbr_sets(res_rate_t *S, const uint32_t *d_f, const uint32_t *d_c, const uint32_t *d_k, const uint64_t *d_nnz, uint32_t P, int point)
+{
+    uint32_t n_pad = 0, K_pad = 0;
+    uint64_t max_norm = 0;
+    fastf_neighbors_pad(S->n_cells, S->hvg_k, &n_pad, &K_pad);
+    const size_t need = (size_t)P * n_pad * K_pad;
+    if (dev_room(&S->d_nplanes, &S->have.nplanes, need ? need : 1, S->device))
+        return rs_err("%s: --neighbors: %u planes of %u cells x %u genes do not fit: %zu bytes (%s)", S->verb, P, n_pad, K_pad, need, fastf_last_error_copy());
+    if (fastf_dev_neighbor_planes(S->e, d_f, d_c, d_k, d_nnz, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, S->d_nplanes, S->have.nplanes, &P, NULL) ||
+        fastf_dev_neighbors(S->e, S->d_nplanes, P, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, nbr_idx(S, point), nbr_cnt(S, point),
+                            (uint64_t *)((char *)S->d_nbr + S->nbr_map_bytes), &max_norm, NULL) || fastf_devmem_sync())
+        return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+    S->nbr_planes = P;
+    return 0;
+}
+
+int fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->neighbors) return 0;
+    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
+    uint64_t *const sm = (uint64_t *)S->d_small;
+    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    uint32_t *const d_sh = nbr_cnt(S, 0) + 2 * S->nbr_cells;
+    uint32_t P = 0;
+    const double tt = fastf_res_now();
+    /* (a point's counts are at most the full ones: P of the point never exceeds P of the pair) */
+    if (fastf_dev_neighbor_planes(S->e, nnz ? d_f : NULL, d_c, d_k, sm + SM_NNZ, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
+        return rs_err("%s: --neighbors at point %s: %s", S->verb, point_name, fastf_last_error_copy());
+    if (nbr_sets(S, nnz ? d_f : NULL, d_c, d_k, sm + SM_NNZ, P, 1)) return 1;
+    if (fastf_dev_neighbors_shared(S->e, nbr_idx(S, 0), nbr_cnt(S, 0), nbr_idx(S, 1), nbr_cnt(S, 1), S->n_cells, FASTF_NEIGHBORS_K, d_sh, NULL) || fastf_devmem_sync()) return 1;
+    if (S->n_cells && (fastf_devmem_copy(S->h_nkp, nbr_cnt(S, 1), (size_t)S->n_cells * 4) || fastf_devmem_copy(S->h_nsh, d_sh, (size_t)S->n_cells * 4))) return 1;
+    T->neighbors += fastf_res_now() - tt;
+    return 0;
+}
+
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
-    if (!S->fidelity && !S->gene_fid) return 0;
+    if (!S->fidelity && !S->gene_fid && !S->neighbors) return 0;
     const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
     uint64_t *const sm = (uint64_t *)S->d_small;
     const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
@@ -495,7 +550,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
     if (fastf_devmem_copy(x_f, d_f, (size_t)nnz * 4) || fastf_devmem_copy(x_c, d_c, (size_t)nnz * 4) || fastf_devmem_copy(x_k, d_k, (size_t)nnz * 4) ||
         fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
     S->full_nnz = nnz;
-    if (S->gene_fid) {                                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
+    if (S->gene_fid || S->neighbors) {                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
         const size_t gs = S->gfid_stride;
         uint64_t *const g_sx = (uint64_t *)S->d_gfid, *const g_sxx = g_sx + gs;
         uint32_t *const g_cf = (uint32_t *)(g_sx + 5 * gs);
@@ -504,7 +559,18 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
             fastf_devmem_sync()) return 1;
         if (S->n_features && (fastf_devmem_copy(S->h_gsx, g_sx, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gsxx, g_sxx, (size_t)S->n_features * 8) ||
                               fastf_devmem_copy(S->h_gcf, g_cf, (size_t)S->n_features * 4))) return 1;
-        T->gene_fid += fastf_res_now() - tt; tt = fastf_res_now();
+        *(S->gene_fid ? &T->gene_fid : &T->neighbors) += fastf_res_now() - tt; tt = fastf_res_now();
+    }
+    if (S->neighbors) {                                     /* A of the pair, its slot map, the planes of the full rows and their neighbour sets, which stay */
+        uint16_t *const h_map = (uint16_t *)S->h_nbr;
+        uint32_t P = 0;
+        S->hvg_k = fastf_hvg_rank(S->n_cells, S->h_gsx, S->h_gsxx, S->n_features, S->h_ngenes, NULL);
+        if (fastf_neighbors_slot_map(S->h_ngenes, S->hvg_k, S->n_features, h_map) || fastf_devmem_copy(S->d_nbr, h_map, S->nbr_map_bytes)) return 1;
+        if (fastf_dev_neighbor_planes(S->e, nnz ? x_f : NULL, x_c, x_k, sm + SM_FULL, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
+            return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+        if (nbr_sets(S, nnz ? x_f : NULL, x_c, x_k, sm + SM_FULL, P, 0)) return 1;
+        if (S->n_cells && fastf_devmem_copy(S->h_nkf, nbr_cnt(S, 0), (size_t)S->n_cells * 4)) return 1;
+        T->neighbors += fastf_res_now() - tt; tt = fastf_res_now();
     }
     if (!S->fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
@@ -518,7 +584,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 
 int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
 {
-    if (!S->fidelity && !S->gene_fid) return RES_OK;
+    if (!S->fidelity && !S->gene_fid && !S->neighbors) return RES_OK;
     char name[64];
     uint64_t counters[3], nnz = 0;
     const res_times_t before = *T;
@@ -527,7 +593,7 @@ int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
     const int prc = fastf_res_point_run(S, d_plane, name, counters, &nnz, T);
     if (prc != RES_OK) return prc;
     *T = before;                                            /* (the stages of this point are the flag's own) */
-    *(S->fidelity ? &T->fidelity : &T->gene_fid) += fastf_res_now() - tt;
+    *(S->fidelity ? &T->fidelity : S->gene_fid ? &T->gene_fid : &T->neighbors) += fastf_res_now() - tt;
     return fastf_res_full_keep(S, T) ? RES_FAIL : RES_OK;
 }
 
@@ -826,8 +892,44 @@ static int gene_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, fl
     return 0;
 }
 
+int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header)
+{
+    if (!on) return 0;
+    char name[64];
+    snprintf(name, sizeof name, "%s_neighbors.tsv", verb);
+    F->verb = verb;
+    if (fastf_res_tsv_open(&F->ntsv, out_dir, name, header)) return 1;
+    F->nbr_on = F->full = 1;
+    return 0;
+}
+
+/* --neighbors: the row of the point and — dir != NULL — its neighbors.tsv.gz */
+static int nbr_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    char row[640];
+    if (fastf_neighbors_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->h_nkf, S->h_nkp, S->h_nsh, row, sizeof row)) return 1;
+    if (dir) {
+        char path[4200], line[512];
+        gtext t = { NULL, 0, 0 };
+        int bad = gt_str(&t, fastf_neighbors_header());
+        for (uint32_t c = 0; c < S->n_cells && !bad; c++)
+            bad = fastf_neighbors_row(S->L->barcode[c], S->h_nkf[c], S->h_nkp[c], S->h_nsh[c], line, sizeof line) || gt_str(&t, line);
+        snprintf(path, sizeof path, "%s/neighbors.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+        if (bad) return 1;
+    }
+    fputs(row, F->ntsv.f);
+    return 0;
+}
+
 int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T)
 {
+    if (F->nbr_on) {
+        const double tt = fastf_res_now();
+        if (nbr_point(F, S, dir, rate_depth, list_value)) return 1;
+        T->neighbors += fastf_res_now() - tt;
+    }
     if (F->gene_on) {
         const double tt = fastf_res_now();
         if (gene_fid_point(F, S, dir, rate_depth, list_value)) return 1;
@@ -857,15 +959,15 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
 
 int fastf_res_fid_close(res_fid_t *F, int ok)
 {
-    if (!F->on && !F->gene_on) return 0;
-    /* both tables are closed before either is renamed, and a rename that fails takes the other table back: none is left alone */
-    res_tsv_t *const t[2] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL};
+    if (!F->on && !F->gene_on && !F->nbr_on) return 0;
+    /* the tables are closed before any is renamed, and a rename that fails takes the others back: none is left alone */
+    res_tsv_t *const t[3] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL};
     int bad = 0, renamed = 0;
     const char *failed = NULL;
-    for (int k = 0; k < 2; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
-    for (int k = 0; k < 2 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
-    if (!ok || bad) for (int k = 0; k < 2; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
-    F->on = F->gene_on = F->full = 0;
+    for (int k = 0; k < 3; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
+    for (int k = 0; k < 3 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
+    if (!ok || bad) for (int k = 0; k < 3; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
+    F->on = F->gene_on = F->nbr_on = F->full = 0;
     return ok && bad ? rs_err("cannot write %s", failed) : 0;
 }
 
@@ -1156,8 +1258,8 @@ int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_gr
 
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
 {
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv"};
-    for (int k = 0; k < 7; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv"};
+    for (int k = 0; k < 8; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
 }
 
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
@@ -1173,11 +1275,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1191,7 +1293,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1221,6 +1323,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'C': out->per_cell = 1; break;
         case 'F': out->fidelity = 1; break;
         case 'Q': out->gene_fidelity = 1; break;
+        case 'N': out->neighbors = 1; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
         }

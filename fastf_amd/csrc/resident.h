@@ -9,7 +9,9 @@
  * behind every point the join of its rows with them (fastf_res_point_fidelity) — BEFORE fastf_res_point_cells, whose K3u output
  * overwrites the point's rows in S->d_rows.
  * --gene-fidelity reduces the same pair of row sets along the gene axis (fastf_res_point_gene_fidelity, behind fastf_res_point_fidelity
- * and before fastf_res_point_cells too); alone it switches the full-depth rows on by itself. */
+ * and before fastf_res_point_cells too); alone it switches the full-depth rows on by itself.
+ * --neighbors compares the k-nearest-neighbour sets of the cells over the pair's highly variable genes (fastf_res_point_neighbors, behind
+ * the two above and before fastf_res_point_cells); alone it switches on the full-depth rows and the pair's per-gene sums that rank the genes. */
 #ifndef FASTF_RESIDENT_H
 #define FASTF_RESIDENT_H
 
@@ -30,7 +32,7 @@ enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys w
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
 enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_LEVEL = 192, SM_FULL = 224, SM_WORDS_ = 256 };   /* SM_UROWS: --cells, K3u's row count; SM_LEVEL: level, the result block of a step (FASTF_LEVEL_OUT_WORDS); SM_FULL: --fidelity, the row count of the pair's full rows (no point clears it) */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid; uint32_t opens, relays, passes; } res_times_t;   /* gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors; uint32_t opens, relays, passes; } res_times_t;   /* neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
@@ -88,8 +90,14 @@ typedef struct {
      * and cells are the arrays of --genes (h_gsy == h_upg, h_gc == h_cpg) */
     int gene_fid; void *d_gx, *d_gfid; size_t gfid_stride;
     uint64_t *h_gfid, *h_gsx, *h_gsxx, *h_gsy, *h_gsyy, *h_gsxy; uint32_t *h_gcf, *h_gc;
+    /* --neighbors (set by the caller before the first open; it keeps the full rows and the pair's per-gene sums as --gene-fidelity does):
+     * d_nbr: the slot map of A (u16[n_features + 1], nbr_map_bytes), the norms (u64), the neighbour indices of the full rows and of the
+     * point (u32, FASTF_NEIGHBORS_K a cell), their counts and the shared counts (u32), nbr_cells entries apart; d_nplanes: the byte planes
+     * of the row set at hand (nbr_planes of them); h_nbr: the pinned map, k_full, k_point, shared and the genes of A in rank order */
+    int neighbors; void *d_nbr, *d_nplanes, *h_nbr; size_t nbr_cells, nbr_map_bytes; uint32_t hvg_k, nbr_planes;
+    uint32_t *h_nkf, *h_nkp, *h_nsh, *h_ngenes;
     uint32_t max_cells; int no_reuse;    /* set by the caller before the first open: the most cells any pair of the run samples (0: unknown); FASTF_RES_NO_REUSE */
-    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level, full, fid, h_fid, gx, gfid, h_gfid; } have;
+    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level, full, fid, h_fid, gx, gfid, h_gfid, nbr, h_nbr, nplanes; } have;
 } res_rate_t;
 #define RES_CELLS_HIST_BYTES 512u
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
@@ -133,6 +141,12 @@ int  fastf_res_full_keep(res_rate_t *S, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
+/* --neighbors (S->neighbors).  fastf_res_full_keep also ranks A of the pair from S->h_gsx and S->h_gsxx (S->hvg_k genes), lays the slot
+ * map down, and leaves the neighbour sets of the full rows on the device and k_full in S->h_nkf.  fastf_res_point_neighbors: behind
+ * fastf_res_point_run, before fastf_res_point_cells — the planes and neighbour sets of the point's rows, the shared counts, k_point and
+ * shared to the host (S->h_nkp, S->h_nsh).  A count beyond three planes or a norm of 2^42 and beyond fails the pair by name.  Nothing
+ * without S->neighbors */
+int  fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
 /* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
  * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
@@ -176,8 +190,11 @@ int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
  * --gene-fidelity: <out_dir>/<verb>_gene_fidelity.tsv and <point dir>/gene_fidelity.tsv.gz likewise.  full: either is on — the pair's
  * full rows are needed.  on == 0 and gene_on == 0: every call does nothing.  fastf_res_fid_close closes both tables before it renames
  * either, and where a rename fails neither table is left */
-typedef struct { int on, gene_on, full; const char *verb; res_tsv_t tsv, gtsv; } res_fid_t;
+typedef struct { int on, gene_on, nbr_on, full; const char *verb; res_tsv_t tsv, gtsv, ntsv; } res_fid_t;
 int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, const char *out_dir, const char *header, const char *gene_header) FASTF_HIDDEN;
+/* --neighbors: <out_dir>/<verb>_neighbors.tsv and <point dir>/neighbors.tsv.gz likewise; called behind fastf_res_fid_open (which clears F).
+ * On failure the caller closes F with ok == 0 */
+int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
 /* one point, after fastf_res_point_fidelity / fastf_res_point_gene_fidelity: its row (list_value == 0: rate_depth in the second column)
  * into each table that is on and — dir != NULL — dir/fidelity.tsv.gz from the arrays of S (h_ufull, h_upc, h_gfull, h_gpc, h_sxx, h_syy,
  * h_sxy) and the barcodes of its lists, dir/gene_fidelity.tsv.gz from the per-gene arrays of S and the feature ids */
@@ -213,17 +230,17 @@ int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_d
  * renamed; otherwise nothing of them is left */
 int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, const float *rates_depth, const uint64_t *caps) FASTF_HIDDEN;
 int fastf_res_reps_close(res_reps_t *P, int ok) FASTF_HIDDEN;   /* ok == 0 only */
-/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,fidelity,gene_fidelity,reps,genes_reps}.tsv and
+/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,fidelity,gene_fidelity,neighbors,reps,genes_reps}.tsv and
  * <verb>_gene_reps.tsv.gz is left */
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_HIDDEN;
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --seeds --reps and ONE list option of the verb's own
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --seeds --reps and ONE list option of the verb's own
  * (list_short / list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
  * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity;
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors;
                  uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;

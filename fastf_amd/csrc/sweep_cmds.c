@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity]; -d accepted
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors]; -d accepted
  *                  and ignored, -u refused
  *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
@@ -23,6 +23,9 @@
  * sweep_fidelity.tsv and the point's fidelity.tsv.gz; resident form only, as --cells.
  * --gene-fidelity: the same pair of row sets per gene (fastf_res_point_gene_fidelity: fastf_dev_partner_counts, fastf_dev_gene_moments)
  * into sweep_gene_fidelity.tsv and the point's gene_fidelity.tsv.gz; it keeps the full rows by itself.
+ * --neighbors: the k-nearest-neighbour sets of the cells over the pair's highly variable genes, at full depth and at the point
+ * (fastf_res_point_neighbors: fastf_dev_neighbor_planes, fastf_dev_neighbors, fastf_dev_neighbors_shared) into sweep_neighbors.tsv and
+ * the point's neighbors.tsv.gz; it keeps the full rows and ranks the genes by itself.
  * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
  * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
  * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
@@ -484,31 +487,49 @@ static int cmp_hvg(const void *a, const void *b)
     return x->g < y->g ? -1 : x->g > y->g;
 }
 
+/* the dispersion of (sum, sum_sq) is disp_full of fastf_gene_fidelity_metrics — and its disp, which is the same expression on the other
+ * pair of sums.  Out of memory: UINT32_MAX, and *n_defined likewise */
+uint32_t fastf_hvg_rank(uint32_t n_cells, const uint64_t *sum, const uint64_t *sum_sq, uint32_t n_features, uint32_t *genes, uint32_t *n_defined)
+{
+    hvg_item *A = (hvg_item *)malloc(((size_t)n_features + 1) * sizeof *A);
+    if (!A) { if (n_defined) *n_defined = UINT32_MAX; return UINT32_MAX; }
+    size_t na = 0;
+    for (uint32_t g = 0; g < n_features; g++) {
+        double d = 0.0;
+        if (fastf_gene_fidelity_metrics(n_cells, sum[g], 0, sum_sq[g], 0, 0, NULL, &d, NULL) & 2) { A[na].v = d; A[na].g = g; na++; }
+    }
+    qsort(A, na, sizeof *A, cmp_hvg);
+    const uint32_t K = (uint32_t)(na < FASTF_HVG_TOP ? na : FASTF_HVG_TOP);
+    if (genes) for (uint32_t k = 0; k < K; k++) genes[k] = A[k].g;
+    if (n_defined) *n_defined = (uint32_t)na;
+    free(A);
+    return K;
+}
+
 int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, const uint64_t *sum_x,
                                     const uint64_t *sum_y, const uint64_t *sum_xx, const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_features,
                                     char *buf, size_t cap)
 {
     if (!buf || (n_features && (!sum_x || !sum_y || !sum_xx || !sum_yy || !sum_xy))) return sw_err("null argument");
     double *pe = (double *)malloc(((size_t)n_features + 1) * sizeof *pe);
-    hvg_item *A = (hvg_item *)malloc(((size_t)n_features + 1) * 2 * sizeof *A), *B = A ? A + n_features + 1 : NULL;
+    uint32_t *A = (uint32_t *)malloc(2 * FASTF_HVG_TOP * sizeof *A), *B = A ? A + FASTF_HVG_TOP : NULL;
     uint8_t *inA = (uint8_t *)calloc((size_t)n_features + 1, 1);
     if (!pe || !A || !inA) { free(pe); free(A); free(inA); return sw_err("out of memory"); }
-    size_t nd = 0, na = 0, nb = 0;
-    uint32_t genes_full = 0;
+    size_t nd = 0;
+    uint32_t genes_full = 0, nb = 0;
     for (uint32_t g = 0; g < n_features; g++) {
-        double p = 0.0, dfull = 0.0, d = 0.0;
-        const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x[g], sum_y[g], sum_xx[g], sum_yy[g], sum_xy[g], &p, &dfull, &d);
+        double p = 0.0;
+        const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x[g], sum_y[g], sum_xx[g], sum_yy[g], sum_xy[g], &p, NULL, NULL);
         genes_full += sum_x[g] > 0;
         if (defined & 1) pe[nd++] = p;
-        if (defined & 2) { A[na].v = dfull; A[na].g = g; na++; }
-        if (defined & 4) { B[nb].v = d; B[nb].g = g; nb++; }
     }
-    const size_t K = na < FASTF_HVG_TOP ? na : FASTF_HVG_TOP, KB = nb < K ? nb : K;
+    const size_t K = fastf_hvg_rank(n_cells, sum_x, sum_xx, n_features, A, NULL);
+    (void)fastf_hvg_rank(n_cells, sum_y, sum_yy, n_features, B, &nb);
+    const size_t KB = nb < K ? nb : K;
     size_t both = 0;
-    qsort(A, na, sizeof *A, cmp_hvg);
-    qsort(B, nb, sizeof *B, cmp_hvg);
-    for (size_t k = 0; k < K; k++) inA[A[k].g] = 1;
-    for (size_t k = 0; k < KB; k++) both += inA[B[k].g];
+    if (K == UINT32_MAX || nb == UINT32_MAX) { free(pe); free(A); free(inA); return sw_err("out of memory"); }
+    for (size_t k = 0; k < K; k++) inA[A[k]] = 1;
+    for (size_t k = 0; k < KB; k++) both += inA[B[k]];
     char f[4][40];
     if (nd) {
         qsort(pe, nd, sizeof *pe, cmp_dbl);
@@ -524,6 +545,160 @@ int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t 
     if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
     else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
     const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%zu\t%s\n", (double)rate_cell, second, seed, n_cells, genes_full, nd, f[0], f[1], f[2], K, f[3]);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* --neighbors: the host twin, the rows                                 */
+/* ------------------------------------------------------------------ */
+void fastf_neighbors_pad(uint32_t n_cells, uint32_t K, uint32_t *n_pad, uint32_t *K_pad)
+{
+    if (n_pad) *n_pad = n_cells ? (n_cells + 127u) & ~127u : 128u;
+    if (K_pad) *K_pad = K ? (K + 31u) & ~31u : 32u;
+}
+
+int fastf_neighbors_check_norm(uint64_t max_norm)
+{
+    if (max_norm >> 42)
+        return sw_err("FASTF_ERR_NEIGHBOR_NORM: a cell's squared norm over the highly variable genes is %llu, 2^42 or more: the 128-bit order of --neighbors does not hold it",
+                      (unsigned long long)max_norm);
+    return 0;
+}
+
+int fastf_neighbors_slot_map(const uint32_t *genes, uint32_t K, uint32_t n_features, uint16_t *slot_map)
+{
+    if (!slot_map || (K && !genes)) return sw_err("null argument");
+    if (K > FASTF_HVG_TOP) return sw_err("neighbors: %u genes, at most %u", K, FASTF_HVG_TOP);
+    for (size_t f = 0; f <= n_features; f++) slot_map[f] = FASTF_NEIGHBORS_NONE;
+    for (uint32_t k = 0; k < K; k++) {
+        if (genes[k] >= n_features || slot_map[genes[k] + 1] != FASTF_NEIGHBORS_NONE) return sw_err("neighbors: gene %u of the set is outside the list or named twice", genes[k]);
+        slot_map[genes[k] + 1] = (uint16_t)k;
+    }
+    return 0;
+}
+
+uint32_t fastf_neighbors_shared(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb)
+{
+    uint32_t x = 0, y = 0, both = 0;
+    while (x < na && y < nb) {
+        const uint32_t va = a[x], vb = b[y];
+        both += va == vb; x += va <= vb; y += vb <= va;
+    }
+    return both;
+}
+
+typedef unsigned __int128 u128;
+/* j precedes l among the candidates of one query cell */
+static int nbr_precedes(uint64_t dj, uint64_t nj, uint32_t j, uint64_t dl, uint64_t nl, uint32_t l)
+{
+    const u128 a = (u128)dj * dj * nl, b = (u128)dl * dl * nj;
+    return a > b || (a == b && j < l);
+}
+static int cmp_u32(const void *a, const void *b) { const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b; return x < y ? -1 : x > y; }
+
+int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
+                             uint32_t *idx, uint32_t *cnt, uint64_t *norms)
+{
+    if (!m || !slot_map || (n_cells && (!idx || !cnt)) || (m->nnz && (!m->feature || !m->cell || !m->count))) return sw_err("null argument");
+    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return sw_err("neighbors: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
+    int rc = 1;
+    /* the rows with a slot, cell by cell (a counting sort by cell): slot and count */
+    size_t *start = (size_t *)calloc((size_t)n_cells + 2, sizeof *start);
+    uint64_t *nn = (uint64_t *)calloc((size_t)n_cells + 1, sizeof *nn), *vec = (uint64_t *)calloc(FASTF_HVG_TOP, sizeof *vec), *bd = (uint64_t *)malloc(FASTF_NEIGHBORS_MAX_K * sizeof *bd);
+    uint32_t *rs = NULL, *rv = NULL;
+    if (!start || !nn || !vec || !bd) { sw_err("out of memory"); goto done; }
+    size_t kept = 0;
+    for (size_t r = 0; r < m->nnz; r++) {
+        const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
+        if (c >= n_cells || f - 1u >= n_features || slot_map[f] >= FASTF_HVG_TOP) continue;
+        start[c + 2]++; kept++;
+    }
+    for (uint32_t c = 0; c < n_cells; c++) start[c + 2] += start[c + 1];
+    rs = (uint32_t *)malloc((kept + 1) * sizeof *rs); rv = (uint32_t *)malloc((kept + 1) * sizeof *rv);
+    if (!rs || !rv) { sw_err("out of memory"); goto done; }
+    uint64_t max_norm = 0;
+    for (size_t r = 0; r < m->nnz; r++) {
+        const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
+        if (c >= n_cells || f - 1u >= n_features || slot_map[f] >= FASTF_HVG_TOP) continue;
+        const size_t at = start[c + 1]++;
+        rs[at] = slot_map[f]; rv[at] = m->count[r];
+        const u128 sq = (u128)nn[c] + (u128)m->count[r] * m->count[r];
+        nn[c] = sq >> 64 ? UINT64_MAX : (uint64_t)sq;
+    }
+    for (uint32_t c = 0; c < n_cells; c++) if (nn[c] > max_norm) max_norm = nn[c];      /* (start[c] .. start[c + 1]: the rows of cell c) */
+    if (fastf_neighbors_check_norm(max_norm)) goto done;
+    for (uint32_t i = 0; i < n_cells; i++) {
+        uint32_t *const out = idx + (size_t)i * k;
+        uint32_t have = 0;
+        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] += rv[r];
+        for (uint32_t j = 0; j < n_cells; j++) {
+            if (j == i) continue;
+            uint64_t d = 0;
+            for (size_t r = start[j]; r < start[j + 1]; r++) d += vec[rs[r]] * rv[r];
+            if (!d) continue;
+            /* out[0 .. have) in the order of the definition, best first; a later cell never precedes an equal earlier one */
+            uint32_t at = have;
+            while (at > 0 && nbr_precedes(d, nn[j], j, bd[at - 1], nn[out[at - 1]], out[at - 1])) at--;
+            if (at >= k) continue;
+            const uint32_t last = have < k ? have : k - 1;
+            for (uint32_t s = last; s > at; s--) { out[s] = out[s - 1]; bd[s] = bd[s - 1]; }
+            out[at] = j; bd[at] = d;
+            if (have < k) have++;
+        }
+        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] = 0;
+        qsort(out, have, sizeof *out, cmp_u32);
+        for (uint32_t s = have; s < k; s++) out[s] = UINT32_MAX;
+        cnt[i] = have;
+        if (norms) norms[i] = nn[i];
+    }
+    rc = 0;
+done:
+    free(start); free(nn); free(vec); free(bd); free(rs); free(rv);
+    return rc;
+}
+
+const char *fastf_neighbors_header(void) { return "barcode\tk_full\tk_point\tshared\toverlap\n"; }
+#define NEIGHBORS_COLUMNS_TAIL "seed\tn_cells\thvg_k\tk\tcells_defined\tmedian_overlap\tp10_overlap\tmean_overlap\tmean_k_point\n"
+const char *fastf_sweep_neighbors_header(void) { return "rate_cell\trate_depth\t" NEIGHBORS_COLUMNS_TAIL; }
+const char *fastf_cap_neighbors_header(void) { return "rate_cell\treads_per_cell\t" NEIGHBORS_COLUMNS_TAIL; }
+const char *fastf_level_neighbors_header(void) { return "rate_cell\tumi_cap\t" NEIGHBORS_COLUMNS_TAIL; }
+
+int fastf_neighbors_row(const char *barcode, uint32_t k_full, uint32_t k_point, uint32_t shared, char *buf, size_t cap)
+{
+    if (!barcode || !buf) return sw_err("null argument");
+    char f[48];
+    if (k_full) snprintf(f, sizeof f, "%.6f", (double)shared / (double)k_full); else snprintf(f, sizeof f, "NA");
+    const int n = snprintf(buf, cap, "%s\t%u\t%u\t%u\t%s\n", barcode, k_full, k_point, shared, f);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("neighbors row too long") : 0;
+}
+
+int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
+                                const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap)
+{
+    if (!buf || (n_cells && (!k_full || !k_point || !shared))) return sw_err("null argument");
+    double *ov = (double *)malloc(((size_t)n_cells + 1) * sizeof *ov);
+    if (!ov) return sw_err("out of memory");
+    size_t nd = 0;
+    uint64_t kp = 0;
+    for (uint32_t c = 0; c < n_cells; c++) {
+        kp += k_point[c];
+        if (k_full[c]) ov[nd++] = (double)shared[c] / (double)k_full[c];
+    }
+    char f[4][40];
+    if (nd) {
+        qsort(ov, nd, sizeof *ov, cmp_dbl);
+        double sum = 0.0;
+        for (size_t c = 0; c < nd; c++) sum += ov[c];
+        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(ov, nd));
+        snprintf(f[1], sizeof f[1], "%.6f", ov[(size_t)floor(0.1 * (double)(nd - 1))]);
+        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
+    } else for (int c = 0; c < 3; c++) snprintf(f[c], sizeof f[c], "NA");
+    if (n_cells) snprintf(f[3], sizeof f[3], "%.6f", (double)kp / (double)n_cells); else snprintf(f[3], sizeof f[3], "NA");
+    free(ov);
+    char second[32];
+    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, hvg_k, k, nd, f[0], f[1], f[2], f[3]);
     return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
 }
 
@@ -685,6 +860,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         T->summary += fastf_res_now() - tt;
         if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
+        if (fastf_res_point_neighbors(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
@@ -740,7 +916,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
@@ -769,6 +945,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
                                T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
     if (prof && Fd->gene_on) fprintf(stderr, "[sweep] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+    if (prof && Fd->nbr_on) fprintf(stderr, "[sweep] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
 done:
     fastf_res_rate_close(&S);
     fastf_res_free(&R);
@@ -787,15 +964,16 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
     if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY)) return sw_err("sweep: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS)) return sw_err("sweep: unknown flags 0x%x", flags);
     const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0, cells = (flags & FASTF_SWEEP_CELLS) != 0;
-    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0, gene_fidelity = (flags & FASTF_SWEEP_GENE_FIDELITY) != 0;
+    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0, gene_fidelity = (flags & FASTF_SWEEP_GENE_FIDELITY) != 0, neighbors = (flags & FASTF_SWEEP_NEIGHBORS) != 0;
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
     if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
+    if (several && neighbors) return sw_err("sweep: --neighbors needs the resident form, and this job is outside it (several devices)");
     if (several && fidelity && gene_fidelity) return sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (several devices)");
     if (several && fidelity) return sw_err("sweep: --fidelity needs the resident form, and this job is outside it (several devices)");
     if (several && gene_fidelity) return sw_err("sweep: --gene-fidelity needs the resident form, and this job is outside it (several devices)");
@@ -808,12 +986,17 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
     res_fid_t Fd;
     if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "sweep", out_dir, fastf_sweep_fidelity_header(), fastf_sweep_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
+    if (fastf_res_fid_open_neighbors(&Fd, neighbors, "sweep", out_dir, fastf_sweep_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
 
     int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
+    if (rc == RES_NOT_COVERED && neighbors) {
+        sw_err("sweep: --neighbors needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
     if (rc == RES_NOT_COVERED && fidelity && gene_fidelity) {
         sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
         rc = RES_FAIL;
@@ -908,6 +1091,9 @@ static void usage_sweep(FILE *f)
             "                          gene_fidelity.tsv.gz per point, with the Pearson of the RAW counts over ALL sampled cells per gene,\n"
             "                          the dispersion (variance / mean) at full depth and at the point, and the overlap of the 2000\n"
             "                          most variable genes; resident form only\n"
+            "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: sweep_neighbors.tsv and\n"
+            "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
+            "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps; resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -931,7 +1117,7 @@ int cmd_sweep(int argc, const char **argv)
     }
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0) |
-                           (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0);
+                           (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
     if (A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
@@ -942,6 +1128,7 @@ int cmd_sweep(int argc, const char **argv)
     if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
     if (A.fidelity) printf("sweep_fidelity.tsv is generated.\n");
     if (A.gene_fidelity) printf("sweep_gene_fidelity.tsv is generated.\n");
+    if (A.neighbors) printf("sweep_neighbors.tsv is generated.\n");
     if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;

@@ -12,6 +12,7 @@
 #include "cells_kernels.hpp"
 #include "fidelity_kernels.hpp"
 #include "gene_fidelity_kernels.hpp"
+#include "neighbors_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -242,6 +243,8 @@ struct fastf_engine {
     bool cap_lds_attr = false;
     bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
     bool gmom_lds_attr = false;          // the same for gene_moments_kernel<true>
+    bool nbr_lds_attr = false;           // the same for the six nbr_gram_kernel forms
+    DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
     bool mt_par_ready = false;               // the parallel generator's one-time init went through: tables up, kernel attributes set, d_mtseq there
@@ -713,7 +716,7 @@ extern "C" void fastf_engine_destroy(fastf_engine_t* e) FASTF_TRY {
     }
     if (e->h_small) (void)hipHostFree(e->h_small);
     if (e->h_coo) { if (e->h_coo_pinned) pin_unreg(e->h_coo); fastf_big_free(e->h_coo, (size_t)e->h_coo_cap * 12); }
-    e->d_ring.release(); e->d_mt.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
+    e->d_ring.release(); e->d_mt.release(); e->d_nbr.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
     DevBuf* all[] = {&e->tab_cells, &e->tab_feats, &e->img_cells, &e->img_genes, &e->d_cell_filter, &e->d_keys, &e->d_tmp, &e->d_small, &e->d_feature, &e->d_cell,
                      &e->d_count, &e->d_ukeys, &e->d_ncopy, &e->d_cellidx, &e->d_tilecnt, &e->d_tilebase, &e->d_binbase, &e->d_cnt, &e->d_rg_feature, &e->d_rg_cell, &e->d_rg_count, &e->d_rg_ukeys, &e->d_spanrows, &e->d_spanbase, &e->d_giant, &e->d_scanblk,
                      &e->d_halfhits, &e->d_segcount, &e->d_segprefix, &e->d_tileseg, &e->d_segkeys, &e->d_vals, &e->d_vtmp,
@@ -1224,6 +1227,116 @@ extern "C" int fastf_dev_gene_moments(fastf_engine_t* e, const uint32_t* d_featu
     }
     HIP_OK(hipGetLastError());
     dbg_sync(s, "gene moments");
+    return 0;
+} FASTF_CATCH_INT
+
+// --neighbors: the dense byte planes of the rows whose gene is in A (neighbors_kernels.hpp).  d_slot_map: u16[n_features + 1], the slot
+// of feature f in A (0 .. K - 1) or 0xFFFF.  The largest count among those rows decides P (one max reduction, read back here):
+// 1 plane below 2^7, 2 below 2^14, 3 below 2^21; beyond that the call fails by name.  d_planes == NULL: *planes_out = P alone.  Otherwise
+// P * n_pad * K_pad bytes (fastf_neighbors_pad) are zeroed and filled, and planes_bytes must hold them.  Synchronises the stream once.
+extern "C" int fastf_dev_neighbor_planes(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_cell, const uint32_t* d_count,
+                                         const uint64_t* d_nnz, const uint16_t* d_slot_map, uint32_t n_features, uint32_t n_cells, uint32_t K,
+                                         void* d_planes, size_t planes_bytes, uint32_t* planes_out, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_nnz || !planes_out, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (K > NBR_MAX_GENES) return set_err("fastf_dev_neighbor_planes: %u genes, at most %u", K, NBR_MAX_GENES);
+    const bool rows = d_feature && d_cell && d_count && d_slot_map;      // (no row buffer: planes of nothing)
+    u32 max_count = 0;
+    if (rows) {
+        if (e->d_nbr.ensure(64)) return 1;
+        u32* const d_max = (u32*)e->d_nbr.p;
+        HIP_OK(hipMemsetAsync(d_max, 0, 64, s));
+        hipLaunchKernelGGL(nbr_max_count_kernel, dim3(4 * g_cu_count), dim3(256), 0, s, d_feature, d_count, (const u64*)d_nnz, d_slot_map, n_features, d_max);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(s));
+        if (copy_d2h(&max_count, d_max, sizeof max_count)) return 1;
+    }
+    const u32 P = max_count < (1u << 7) ? 1u : max_count < (1u << 14) ? 2u : max_count < (1u << 21) ? 3u : 4u;
+    if (P > NBR_MAX_PLANES)
+        return set_err("fastf_dev_neighbor_planes: FASTF_ERR_NEIGHBOR_COUNT: a count of %u among the highly variable genes needs more than %u planes of 7 bits", max_count, NBR_MAX_PLANES);
+    *planes_out = P;
+    if (!d_planes) return 0;
+    uint32_t n_pad = 0, K_pad = 0;
+    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
+    const size_t need = (size_t)P * n_pad * K_pad;
+    if (need > planes_bytes) return set_err("fastf_dev_neighbor_planes: %u planes of %u x %u bytes need %zu bytes, the buffer has %zu", P, n_pad, K_pad, need, planes_bytes);
+    HIP_OK(hipMemsetAsync(d_planes, 0, need, s));
+    if (rows && K && n_cells) {
+        hipLaunchKernelGGL(nbr_planes_kernel, dim3(4 * g_cu_count), dim3(256), 0, s, d_feature, d_cell, d_count, (const u64*)d_nnz, d_slot_map, n_features,
+                           n_cells, K, n_pad, K_pad, P, (unsigned char*)d_planes);
+        HIP_OK(hipGetLastError());
+    }
+    dbg_sync(s, "neighbor planes");
+    return 0;
+} FASTF_CATCH_INT
+
+template <int P, bool MFMA>
+static int nbr_gram_launch(fastf_engine* e, hipStream_t s, const unsigned char* planes, u32 n, u32 n_pad, u32 K_pad, u32 k, const u64* norms, u32* idx, u32* cnt) {
+    const size_t lds = (size_t)NBR_WAVES * nbr_wave_words(k) * sizeof(u64);
+    HIP_OK(hipFuncSetAttribute((const void*)nbr_gram_kernel<P, MFMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NBR_WAVES * nbr_wave_words(NBR_MAX_K) * sizeof(u64))));
+    (void)e;
+    hipLaunchKernelGGL((nbr_gram_kernel<P, MFMA>), dim3((n + NBR_ROWS - 1) / NBR_ROWS), dim3(NBR_THREADS), lds, s, planes, n, n_pad, K_pad, k, norms, idx, cnt);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// --neighbors: the norms, then the Gram products and the selection (nbr_norms_kernel, nbr_gram_kernel).  d_planes: what
+// fastf_dev_neighbor_planes filled for (n_cells, K) with `planes` planes.  d_norms[i] = v_i . v_i (u64, n_cells); *max_norm_out its maximum,
+// read back before the selection starts: fastf_neighbors_check_norm refuses 2^42 and beyond and nothing more is launched.  Then
+// d_idx[i * k + s], s < d_cnt[i], are the neighbours of cell i (0-based indices, ascending; the other slots 0xFFFFFFFF), k from 1 to 64.
+// The dot products come from the i8 MFMA, under FASTF_NEIGHBORS_MFMA=0 from ordinary integer instructions: the same numbers.
+extern "C" int fastf_dev_neighbors(fastf_engine_t* e, const void* d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, uint32_t k,
+                                   uint32_t* d_idx, uint32_t* d_cnt, uint64_t* d_norms, uint64_t* max_norm_out, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > NBR_MAX_K) return set_err("fastf_dev_neighbors: k = %u, from 1 to %u", k, NBR_MAX_K);
+    if (planes < 1 || planes > NBR_MAX_PLANES) return set_err("fastf_dev_neighbors: %u planes, from 1 to %u", planes, NBR_MAX_PLANES);
+    if (K > NBR_MAX_GENES) return set_err("fastf_dev_neighbors: %u genes, at most %u", K, NBR_MAX_GENES);
+    if (max_norm_out) *max_norm_out = 0;
+    if (!n_cells) return 0;
+    if (!d_planes || !d_idx || !d_cnt || !d_norms) return set_err("fastf_dev_neighbors: null argument");
+    uint32_t n_pad = 0, K_pad = 0;
+    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
+    if (e->d_nbr.ensure(64)) return 1;
+    u64* const d_max = (u64*)e->d_nbr.p + 1;
+    HIP_OK(hipMemsetAsync(d_max, 0, sizeof(u64), s));
+    hipLaunchKernelGGL(nbr_norms_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * g_cu_count)), dim3(256), 0, s, (const unsigned char*)d_planes, n_cells, n_pad, K_pad,
+                       planes, (u64*)d_norms, d_max);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 max_norm = 0;
+    if (copy_d2h(&max_norm, d_max, sizeof max_norm)) return 1;
+    if (max_norm_out) *max_norm_out = max_norm;
+    if (fastf_neighbors_check_norm(max_norm)) return 1;
+    const char* mf = getenv("FASTF_NEIGHBORS_MFMA");
+    const bool mfma = !(mf && mf[0] == '0');
+    const unsigned char* const pl = (const unsigned char*)d_planes;
+    int rc = 1;
+    switch (planes * 2 + (mfma ? 1 : 0)) {
+    case 2: rc = nbr_gram_launch<1, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    case 3: rc = nbr_gram_launch<1, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    case 4: rc = nbr_gram_launch<2, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    case 5: rc = nbr_gram_launch<2, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    case 6: rc = nbr_gram_launch<3, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    case 7: rc = nbr_gram_launch<3, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
+    }
+    if (rc) return 1;
+    dbg_sync(s, "neighbors");
+    return 0;
+} FASTF_CATCH_INT
+
+// --neighbors: d_shared[i] = the number of cells in both neighbour sets of cell i (nbr_shared_kernel); the sets as fastf_dev_neighbors
+// leaves them, both with the same k.  Stream-ordered.
+extern "C" int fastf_dev_neighbors_shared(fastf_engine_t* e, const uint32_t* d_idx_a, const uint32_t* d_cnt_a, const uint32_t* d_idx_b,
+                                          const uint32_t* d_cnt_b, uint32_t n_cells, uint32_t k, uint32_t* d_shared, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > NBR_MAX_K) return set_err("fastf_dev_neighbors_shared: k = %u, from 1 to %u", k, NBR_MAX_K);
+    if (!n_cells) return 0;
+    if (!d_idx_a || !d_cnt_a || !d_idx_b || !d_cnt_b || !d_shared) return set_err("fastf_dev_neighbors_shared: null argument");
+    hipLaunchKernelGGL(nbr_shared_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, d_idx_a, d_cnt_a, d_idx_b, d_cnt_b, n_cells, k, d_shared);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "neighbors shared");
     return 0;
 } FASTF_CATCH_INT
 
@@ -1859,7 +1972,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

@@ -443,6 +443,26 @@ class Engine:
         the sum of b * b (u64[n_features] each, cleared by the call); stream-ordered"""
         check(self._L.fastf_dev_gene_moments(self._h, d_feature or None, d_a or None, d_b or None, d_nnz, n_features, d_sum_ab or None, d_sum_bb or None, stream))
 
+    def dev_neighbor_planes(self, d_feature, d_cell, d_count, d_nnz, d_slot_map, n_features, n_cells, n_genes, d_planes=0, planes_bytes=0, stream=0) -> int:
+        """--neighbors: the number of 7-bit planes P the largest count among the rows with a slot needs (FastfError beyond 3) and — d_planes
+        given — the P byte planes of sweep.neighbors_pad(n_cells, n_genes) zeroed and filled; synchronises the stream once"""
+        p = C.c_uint32()
+        check(self._L.fastf_dev_neighbor_planes(self._h, d_feature or None, d_cell or None, d_count or None, d_nnz, d_slot_map or None, n_features, n_cells,
+                                                n_genes, d_planes or None, planes_bytes, C.byref(p), stream))
+        return p.value
+
+    def dev_neighbors(self, d_planes, planes, n_cells, n_genes, k, d_idx, d_cnt, d_norms, stream=0) -> int:
+        """--neighbors: the planes -> d_norms (u64[n_cells]), d_idx (u32[n_cells * k], ascending within a row, 0xFFFFFFFF behind the
+        d_cnt[i] entries), d_cnt (u32[n_cells]); returns the largest norm; FastfError at 2^42 and beyond.  FASTF_NEIGHBORS_MFMA=0: the dot
+        products from ordinary integer instructions"""
+        m = C.c_uint64()
+        check(self._L.fastf_dev_neighbors(self._h, d_planes or None, planes, n_cells, n_genes, k, d_idx or None, d_cnt or None, d_norms or None, C.byref(m), stream))
+        return m.value
+
+    def dev_neighbors_shared(self, d_idx_a, d_cnt_a, d_idx_b, d_cnt_b, n_cells, k, d_shared, stream=0):
+        """--neighbors: d_shared[i] (u32) = the cells in both neighbour sets of cell i; stream-ordered"""
+        check(self._L.fastf_dev_neighbors_shared(self._h, d_idx_a or None, d_cnt_a or None, d_idx_b or None, d_cnt_b or None, n_cells, k, d_shared or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

@@ -14,6 +14,8 @@ CELLS = 8             # FASTF_SWEEP_CELLS
 FIDELITY = 32         # FASTF_SWEEP_FIDELITY
 GENE_FIDELITY = 128   # FASTF_SWEEP_GENE_FIDELITY
 HVG_TOP = 2000        # FASTF_HVG_TOP
+NEIGHBORS = 512       # FASTF_SWEEP_NEIGHBORS
+NEIGHBORS_K = 15      # FASTF_NEIGHBORS_K
 COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
@@ -27,6 +29,9 @@ POINT_FIDELITY_COLUMNS = ("barcode", "umis_full", "umis", "genes_full", "genes",
 GENE_FIDELITY_TAIL_COLUMNS = ("seed", "n_cells", "genes_full", "genes_defined", "median_pearson", "p10_pearson", "mean_pearson", "hvg_k", "hvg_overlap")
 GENE_FIDELITY_COLUMNS = ("rate_cell", "rate_depth") + GENE_FIDELITY_TAIL_COLUMNS
 POINT_GENE_FIDELITY_COLUMNS = ("feature", "sum_x", "sum_y", "cells_full", "cells", "sum_xx", "sum_yy", "sum_xy", "pearson", "disp_full", "disp")     # <point dir>/gene_fidelity.tsv.gz
+NEIGHBORS_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "cells_defined", "median_overlap", "p10_overlap", "mean_overlap", "mean_k_point")
+NEIGHBORS_COLUMNS = ("rate_cell", "rate_depth") + NEIGHBORS_TAIL_COLUMNS
+POINT_NEIGHBORS_COLUMNS = ("barcode", "k_full", "k_point", "shared", "overlap")     # <point dir>/neighbors.tsv.gz
 POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
@@ -35,25 +40,26 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False):
+def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=False):
     return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
-            | (GENE_FIDELITY if gene_fidelity else 0))
+            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0))
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
     out/sweep_cells.tsv (read_cells_table) and a cells.tsv.gz per point directory; fidelity=True also leaves out/sweep_fidelity.tsv
     (read_fidelity_table) and a fidelity.tsv.gz per point directory (read_point_fidelity): every point against the full-depth data
     of the same cells; gene_fidelity=True the same comparison per gene: out/sweep_gene_fidelity.tsv (read_gene_fidelity_table) and a
-    gene_fidelity.tsv.gz per point directory (read_point_gene_fidelity)"""
+    gene_fidelity.tsv.gz per point directory (read_point_gene_fidelity); neighbors=True the comparison between the cells:
+    out/sweep_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory (read_point_neighbors)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity)))
+                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -63,7 +69,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -72,7 +78,7 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity)))
+                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -190,6 +196,91 @@ def gene_fidelity_from_coo(full, point, n_features: int):
     out = [np.zeros(max(n_features, 1), np.uint64) for _ in range(7)]
     _lib.check(_lib.lib().fastf_gene_fidelity_from_coo(C.byref(coos[0]), C.byref(coos[1]), n_features, *[x.ctypes.data for x in out]))
     return tuple(x[:n_features] for x in out)
+
+
+def read_neighbors_table(path, columns=NEIGHBORS_COLUMNS):
+    """the rows of sweep_neighbors.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_neighbors(path):
+    """the rows of a point's neighbors.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_NEIGHBORS_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_NEIGHBORS_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def neighbors_header(verb: str = "") -> str:
+    """the header of neighbors.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_neighbors.tsv"""
+    return getattr(_lib.lib(), "fastf_%sneighbors_header" % (verb + "_" if verb else ""))().decode()
+
+
+def hvg_rank(n_cells, sums, sums_sq):
+    """(genes, n_defined): the highly variable genes (0-based, rank order, at most HVG_TOP) of per-gene sums and sums of squares over
+    n_cells cells — the ranking --gene-fidelity and --neighbors share — and the number of genes whose dispersion is defined"""
+    a = np.ascontiguousarray(sums, dtype=np.uint64)
+    b = np.ascontiguousarray(sums_sq, dtype=np.uint64)
+    assert len(a) == len(b)
+    genes = np.zeros(HVG_TOP, np.uint32)
+    nd = C.c_uint32()
+    K = _lib.lib().fastf_hvg_rank(int(n_cells), a.ctypes.data, b.ctypes.data, len(a), genes.ctypes.data, C.addressof(nd))
+    if K == 0xFFFFFFFF:
+        raise MemoryError("fastf_hvg_rank")
+    return genes[:K].copy(), nd.value
+
+
+def neighbors_slot_map(genes, n_features: int):
+    """u16[n_features + 1]: the rank of every feature (1-based) in genes, 0xFFFF where it has none"""
+    g = np.ascontiguousarray(genes, dtype=np.uint32)
+    out = np.zeros(n_features + 1, np.uint16)
+    _lib.check(_lib.lib().fastf_neighbors_slot_map(g.ctypes.data, len(g), n_features, out.ctypes.data))
+    return out
+
+
+def neighbors_pad(n_cells: int, n_genes: int):
+    """(n_pad, K_pad): the padded shape of the device's byte planes"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _lib.lib().fastf_neighbors_pad(n_cells, n_genes, C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def neighbors_check_norm(max_norm: int):
+    """raises FastfError naming FASTF_ERR_NEIGHBOR_NORM when max_norm >= 2^42"""
+    _lib.check(_lib.lib().fastf_neighbors_check_norm(int(max_norm)))
+
+
+def neighbors_from_coo(coo, n_cells: int, slot_map, k: int = NEIGHBORS_K):
+    """(idx u32[n_cells, k], cnt u32[n_cells], norms u64[n_cells]) of a (feature, cell, count) COO restricted to the features with a slot:
+    the host form of Engine.dev_neighbor_planes and Engine.dev_neighbors together"""
+    p32 = C.POINTER(C.c_uint32)
+    f, c, v = [np.ascontiguousarray(x, dtype=np.uint32) for x in coo]
+    assert len(f) == len(c) == len(v)
+    m = Coo(f.ctypes.data_as(p32), c.ctypes.data_as(p32), v.ctypes.data_as(p32), len(f))
+    sm = np.ascontiguousarray(slot_map, dtype=np.uint16)
+    idx = np.zeros((max(n_cells, 1), k), np.uint32)
+    cnt = np.zeros(max(n_cells, 1), np.uint32)
+    norms = np.zeros(max(n_cells, 1), np.uint64)
+    _lib.check(_lib.lib().fastf_neighbors_from_coo(C.byref(m), n_cells, sm.ctypes.data, len(sm) - 1, k, idx.ctypes.data, cnt.ctypes.data, norms.ctypes.data))
+    return idx[:n_cells], cnt[:n_cells], norms[:n_cells]
+
+
+def neighbors_row(barcode, k_full, k_point, shared) -> str:
+    """one row of neighbors.tsv.gz (with its newline)"""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_neighbors_row(barcode.encode() if isinstance(barcode, str) else barcode, int(k_full), int(k_point), int(shared), buf, len(buf)))
+    return buf.value.decode()
+
+
+def neighbors_summary_row(rate_cell, rate_depth, seed, hvg_k, k_full, k_point, shared, list_value: int = 0, k: int = NEIGHBORS_K) -> str:
+    """one row of <verb>_neighbors.tsv (with its newline); list_value >= 1: that integer in the second column (cap, level)"""
+    a = [np.ascontiguousarray(x, dtype=np.uint32) for x in (k_full, k_point, shared)]
+    n = len(a[0])
+    assert all(len(x) == n for x in a)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_neighbors_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(hvg_k), int(k),
+                                                      a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, buf, len(buf)))
+    return buf.value.decode()
 
 
 REPS_METRICS = ("sampled_reads", "sampled_valid_reads", "nnz", "umis", "saturation", "median_umis_per_cell", "median_genes_per_cell")

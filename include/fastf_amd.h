@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -337,6 +337,63 @@ int fastf_gene_fidelity_row(const char *feature, uint64_t n_cells, uint64_t sum_
 int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, const uint64_t *sum_x,
                                     const uint64_t *sum_y, const uint64_t *sum_xx, const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_features,
                                     char *buf, size_t cap);
+
+/* --- --neighbors on sweep, cap and level (FASTF_*_NEIGHBORS, flag 512; `neighbors=True` in Python; the long option alone): the third
+ * comparison with full depth, BETWEEN the cells — does a cell keep the nearest neighbours it has at full depth, on the genes a
+ * clustering would use.  For a (cell rate, seed) pair X is the full matrix exactly as --fidelity defines it, Y the matrix of a grid
+ * point, n the number of sampled cells.  A is the highly variable gene set of --gene-fidelity: the first
+ * K = min(FASTF_HVG_TOP, genes with disp_full defined) genes by descending disp_full, ties by ascending feature index (fastf_hvg_rank:
+ * the same doubles in the same operation order).  A is fixed per pair: it is used for X and for every Y of the pair.
+ * For a matrix M (X or Y) restricted to the genes of A, with v_i the count vector of cell i:
+ *   d_ij = v_i . v_j        n_i = d_ii
+ *   N_M(i) = the first min(k, #{j != i : d_ij > 0}) cells j != i with d_ij > 0 by descending cosine d_ij / sqrt(n_i n_j), ties by
+ *            ascending cell index.  Decided exactly: j precedes l iff d_ij^2 n_l > d_il^2 n_j, or the two products are equal and
+ *            j < l — in 128-bit unsigned integers; no floating point takes part in the selection.
+ * k = FASTF_NEIGHBORS_K = 15 in the three verbs; the device entry point and the host twin take k from 1 to 64.
+ * Range: the largest n_i is read back (one reduction) and a pair whose value is 2^42 or more is refused (FASTF_ERR_NEIGHBOR_NORM in
+ * the message: fastf_neighbors_check_norm).  Below it d_ij <= sqrt(n_i n_j) < 2^42, so every product stays below 2^126.  The counts go
+ * to the device's matrix cores as digits of 7 bits; a count of 2^21 or more among the genes of A is refused likewise
+ * (FASTF_ERR_NEIGHBOR_COUNT).
+ * Per cell at a point:  k_full = |N_X(i)|   k_point = |N_Y(i)|   shared = |N_X(i) and N_Y(i)|   overlap = shared / k_full (%.6f; NA when
+ * k_full == 0).
+ *   <point dir>/neighbors.tsv.gz (not with --summary-only): a header and one row per barcode in the order of barcodes.tsv.gz:
+ *     barcode k_full k_point shared overlap
+ *   <out_dir>/<verb>_neighbors.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), in the row
+ *     order of <verb>_fidelity.tsv — through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells hvg_k k cells_defined median_overlap p10_overlap mean_overlap mean_k_point
+ *     cells_defined = cells with k_full > 0; median, p10 and mean of the overlap by the rules of <verb>_fidelity.tsv over those cells, NA
+ *     when there is none; mean_k_point = the mean of k_point over all n cells (%.6f; NA when n == 0); hvg_k = K.
+ * The flag works without --fidelity, --gene-fidelity and --genes: it keeps the pair's full rows and ranks A by itself.  Every other
+ * output is the bytes it is without the flag.  Jobs outside the resident form are refused as --fidelity refuses them.  No _reps
+ * aggregate is written. --- */
+#define FASTF_SWEEP_NEIGHBORS 512u           /* bits 4, 16, 64 and 256 are not assigned: tests pin them as the unknown bits that are refused */
+#define FASTF_CAP_NEIGHBORS   512u
+#define FASTF_LEVEL_NEIGHBORS 512u
+#define FASTF_NEIGHBORS_K 15u
+#define FASTF_NEIGHBORS_MAX_K 64u
+#define FASTF_NEIGHBORS_NONE 0xFFFFu         /* the slot of a feature that is not in A */
+const char *fastf_neighbors_header(void);          /* the header of neighbors.tsv.gz */
+const char *fastf_sweep_neighbors_header(void);    /* the headers of <verb>_neighbors.tsv */
+const char *fastf_cap_neighbors_header(void);
+const char *fastf_level_neighbors_header(void);
+/* the ranking both --gene-fidelity and --neighbors use: genes[0 .. K) = the first K = min(FASTF_HVG_TOP, genes whose dispersion is
+ * defined) genes (0-based) by descending dispersion of (sum, sum_sq) over n_cells cells, ties by ascending index; genes holds
+ * FASTF_HVG_TOP entries (NULL: K alone); *n_defined (may be NULL) the genes whose dispersion is defined.  Returns K */
+uint32_t fastf_hvg_rank(uint32_t n_cells, const uint64_t *sum, const uint64_t *sum_sq, uint32_t n_features, uint32_t *genes, uint32_t *n_defined);
+/* slot_map[f] (u16, n_features + 1 entries, f the 1-based feature) = the rank of feature f in genes[0 .. K), FASTF_NEIGHBORS_NONE for
+ * every other feature and for f == 0; fails when K exceeds FASTF_HVG_TOP or a gene is outside the list or named twice */
+int fastf_neighbors_slot_map(const uint32_t *genes, uint32_t K, uint32_t n_features, uint16_t *slot_map);
+/* the padded shape of the device's byte planes for n_cells cells and K genes: n_pad rows (a multiple of 128) of K_pad bytes (a multiple
+ * of 32, at least 32) */
+void fastf_neighbors_pad(uint32_t n_cells, uint32_t K, uint32_t *n_pad, uint32_t *K_pad);
+/* the range rule: fails, naming FASTF_ERR_NEIGHBOR_NORM, when max_norm >= 2^42 */
+int fastf_neighbors_check_norm(uint64_t max_norm);
+/* one row of neighbors.tsv.gz (with its newline) */
+int fastf_neighbors_row(const char *barcode, uint32_t k_full, uint32_t k_point, uint32_t shared, char *buf, size_t cap);
+/* one row of <verb>_neighbors.tsv (with its newline); the second column as fastf_genes_summary_row prints it (list_value == 0:
+ * rate_depth) */
+int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
+                                const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -529,6 +586,16 @@ int fastf_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, u
  * together; fails on a point row without a partner.  A row whose feature is outside 1 .. n_features adds nothing */
 int fastf_gene_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_features, uint64_t *sum_x, uint64_t *sum_y,
                                  uint64_t *cells_full, uint64_t *cells, uint64_t *sum_xx, uint64_t *sum_yy, uint64_t *sum_xy);
+
+/* --neighbors (section 1): the neighbour sets of a COO matrix restricted to the features with a slot in slot_map
+ * (fastf_neighbors_slot_map) — the host form of fastf_dev_neighbor_planes and fastf_dev_neighbors together, in plain C with 128-bit
+ * compares.  idx[i * k + s], s < cnt[i]: the neighbours of cell i (0-based, ascending; the other slots 0xFFFFFFFF); norms[i] = n_i
+ * (may be NULL).  The rows may come in any order; one whose cell is outside 1 .. n_cells or whose feature is outside 1 .. n_features
+ * adds nothing.  Fails as the device does on a norm of 2^42 or more and on k outside 1 .. 64 */
+int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
+                             uint32_t *idx, uint32_t *cnt, uint64_t *norms);
+/* the number of values in both of two ascending lists */
+uint32_t fastf_neighbors_shared(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
@@ -792,6 +859,26 @@ int fastf_dev_partner_counts(fastf_engine_t *e, const uint32_t *d_feature_full, 
                              uint32_t *d_x, uint64_t *d_err, void *stream);
 int fastf_dev_gene_moments(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_a, const uint32_t *d_b, const uint64_t *d_nnz,
                            uint32_t n_features, uint64_t *d_sum_ab, uint64_t *d_sum_bb, void *stream);
+
+/* --neighbors (section 1), three calls on device pointers.
+ * fastf_dev_neighbor_planes (nbr_max_count_kernel, nbr_planes_kernel): rows (d_feature 1-based, d_cell 1-based, d_count), *d_nnz of
+ * them, each (cell, feature) at most once, and d_slot_map (u16[n_features + 1], fastf_neighbors_slot_map) -> *planes_out = P, the planes
+ * the largest count among the rows with a slot needs (1 below 2^7, 2 below 2^14, 3 below 2^21; beyond that the call fails, naming
+ * FASTF_ERR_NEIGHBOR_COUNT), and — d_planes != NULL — P byte planes of n_pad x K_pad (fastf_neighbors_pad), zeroed first: plane p holds
+ * bits 7p .. 7p+6 of the count of (cell, slot).  planes_bytes: the room behind d_planes.  Synchronises the stream once (the maximum).
+ * fastf_dev_neighbors (nbr_norms_kernel, nbr_gram_kernel): the planes -> d_norms[i] = n_i (u64), *max_norm_out their maximum (read
+ * back; 2^42 and beyond fails before anything else is launched), d_idx[i * k + s], s < d_cnt[i]: the neighbours of cell i (0-based,
+ * ascending; the other slots 0xFFFFFFFF), k from 1 to 64.  A workgroup owns 128 query rows, a wave 32 of them, and streams the column
+ * tiles; n x n is never stored.  The dot products come from the i8 MFMA (32x32x32), under FASTF_NEIGHBORS_MFMA=0 from ordinary integer
+ * instructions: the same numbers either way.
+ * fastf_dev_neighbors_shared (nbr_shared_kernel): two index / count sets of the same k -> d_shared[i] = the cells in both sets of i. */
+int fastf_dev_neighbor_planes(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_cell, const uint32_t *d_count, const uint64_t *d_nnz,
+                              const uint16_t *d_slot_map, uint32_t n_features, uint32_t n_cells, uint32_t K, void *d_planes, size_t planes_bytes,
+                              uint32_t *planes_out, void *stream);
+int fastf_dev_neighbors(fastf_engine_t *e, const void *d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, uint32_t k, uint32_t *d_idx,
+                        uint32_t *d_cnt, uint64_t *d_norms, uint64_t *max_norm_out, void *stream);
+int fastf_dev_neighbors_shared(fastf_engine_t *e, const uint32_t *d_idx_a, const uint32_t *d_cnt_a, const uint32_t *d_idx_b, const uint32_t *d_cnt_b,
+                               uint32_t n_cells, uint32_t k, uint32_t *d_shared, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
