@@ -135,6 +135,12 @@ ABI_SYMBOLS = [
     "fastf_neighbors_header", "fastf_sweep_neighbors_header", "fastf_cap_neighbors_header", "fastf_level_neighbors_header", "fastf_hvg_rank",
     "fastf_neighbors_slot_map", "fastf_neighbors_pad", "fastf_neighbors_check_norm", "fastf_neighbors_row", "fastf_neighbors_summary_row",
     "fastf_neighbors_from_coo", "fastf_neighbors_shared", "fastf_dev_neighbor_planes", "fastf_dev_neighbors", "fastf_dev_neighbors_shared",
+    # --labels of sweep, cap and level
+    "fastf_labels_load", "fastf_labels_free", "fastf_labels_count", "fastf_labels_name", "fastf_labels_unknown", "fastf_labels_known", "fastf_labels_id",
+    "fastf_labels_assign", "fastf_label_votes", "fastf_labels_header", "fastf_sweep_labels_header", "fastf_cap_labels_header", "fastf_level_labels_header",
+    "fastf_sweep_label_classes_header", "fastf_cap_label_classes_header", "fastf_level_label_classes_header", "fastf_labels_row",
+    "fastf_label_confusion_header", "fastf_label_confusion_row", "fastf_labels_summary_row", "fastf_label_classes_row",
+    "fastf_sweep_labels", "fastf_cap_labels", "fastf_level_labels", "fastf_dev_label_votes",
 ]
 
 
@@ -377,6 +383,33 @@ def lib():
     L.fastf_dev_neighbor_planes.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, sz, C.POINTER(u32), vp]
     L.fastf_dev_neighbors.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, C.POINTER(u64), vp]
     L.fastf_dev_neighbors_shared.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp]
+    for name in ("fastf_labels_header", "fastf_sweep_labels_header", "fastf_cap_labels_header", "fastf_level_labels_header",
+                 "fastf_sweep_label_classes_header", "fastf_cap_label_classes_header", "fastf_level_label_classes_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_labels_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
+    L.fastf_labels_free.argtypes = [vp]
+    L.fastf_labels_free.restype = None
+    L.fastf_labels_count.argtypes = [vp]
+    L.fastf_labels_count.restype = u32
+    L.fastf_labels_name.argtypes = [vp, u32]
+    L.fastf_labels_name.restype = C.c_char_p
+    L.fastf_labels_unknown.argtypes = [vp]
+    L.fastf_labels_unknown.restype = u64
+    L.fastf_labels_known.argtypes = [vp]
+    L.fastf_labels_known.restype = u64
+    L.fastf_labels_id.argtypes = [vp, C.c_char_p]
+    L.fastf_labels_id.restype = u32
+    L.fastf_labels_assign.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp]
+    L.fastf_label_votes.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.fastf_labels_row.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, u32, u32, u32, u32, C.c_char_p, sz]
+    L.fastf_label_confusion_header.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, sz]
+    L.fastf_label_confusion_row.argtypes = [C.c_char_p, u32, vp, u32, C.c_char_p, sz]
+    L.fastf_labels_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_label_classes_row.argtypes = [C.c_float, C.c_float, u64, u32, C.c_char_p, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_sweep_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p]
+    L.fastf_cap_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
+    L.fastf_level_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
+    L.fastf_dev_label_votes.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -190,6 +190,7 @@ static int cap_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t
         if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
         if (fastf_res_point_neighbors(S, name, T)) goto done;
+        if (fastf_res_point_labels(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
@@ -246,7 +247,7 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("cap", bam_file, &LL.L[0], device, &R)) goto done;
@@ -274,6 +275,8 @@ static int cap_resident(const char *bam_file, const char *out_dir, const char *b
                                T.cells_dev, T.cells_dev / (n_c * n_n * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[cap] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
     if (prof && Fd->gene_on) fprintf(stderr, "[cap] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+    if (prof && Fd->lab_on) fprintf(stderr, "[cap] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
+                                    (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
     if (prof && Fd->nbr_on) fprintf(stderr, "[cap] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
 done:
     fastf_res_rate_close(&S);
@@ -287,8 +290,8 @@ done:
 /* the command                                                         */
 /* ------------------------------------------------------------------ */
 /* reps != 0: a replicate run (fastf_cap_reps) — the suffixed directories and the replicate tables, with one seed too */
-static int cap_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                   const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags)
+static int cap_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                   const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels)
 {
     if (!bam || !barcodes || !features) return cp_err("cap: null argument");
     if (!out_dir) out_dir = ".";
@@ -301,7 +304,8 @@ static int cap_run(const char *bam, const char *out_dir, const char *barcodes, c
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         if (dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2))
-            return neighbors ? cp_err("cap: --neighbors needs the resident form, and this job is outside it (several devices), and a cap has no point-by-point form") :
+            return labels ? cp_err("cap: --labels needs the resident form, and this job is outside it (several devices), and a cap has no point-by-point form") :
+                   neighbors ? cp_err("cap: --neighbors needs the resident form, and this job is outside it (several devices), and a cap has no point-by-point form") :
                    gene_fidelity ? cp_err("cap: --gene-fidelity needs the resident form, and this job is outside it (several devices), and a cap has no point-by-point form")
                                  : cp_err("cap: this job is outside the resident form (several devices), and a cap has no point-by-point form"); }
     if (fastf_res_make_dir(out_dir)) return 1;
@@ -314,12 +318,15 @@ static int cap_run(const char *bam, const char *out_dir, const char *barcodes, c
     res_fid_t Fd;
     if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "cap", out_dir, fastf_cap_fidelity_header(), fastf_cap_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     if (fastf_res_fid_open_neighbors(&Fd, neighbors, "cap", out_dir, fastf_cap_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
+    if (fastf_res_fid_open_labels(&Fd, labels, "cap", out_dir, fastf_cap_labels_header(), fastf_cap_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "cap", out_dir, seeds, n_s, n_c, n_n, genes, dev0, fastf_cap_reps_header(), fastf_cap_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
     int rc = cap_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
-    if (rc == RES_NOT_COVERED && neighbors)
+    if (rc == RES_NOT_COVERED && labels)
+        cp_err("cap: --labels needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
+    else if (rc == RES_NOT_COVERED && neighbors)
         cp_err("cap: --neighbors needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
     else if (rc == RES_NOT_COVERED && gene_fidelity)
         cp_err("cap: --gene-fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a cap has no point-by-point form");
@@ -340,17 +347,39 @@ static int cap_run(const char *bam, const char *out_dir, const char *barcodes, c
     return 0;
 }
 
+/* labels_path != NULL: the labels file is read and checked before anything is written */
+static int cap_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                   const uint64_t *caps, uint32_t n_l, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path)
+{
+    if (!labels_path) return cap_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, NULL);
+    if (!bam || !barcodes || !features) return cp_err("cap: null argument");
+    if (access(bam, R_OK) == -1) return cp_err("bam file: %s does not exist.", bam);
+    fastf_labels_t *labels = NULL;
+    if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
+    const int rc = cap_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, labels);
+    fastf_labels_free(labels);
+    return rc;
+}
+
+int fastf_cap_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
+{
+    if (!n_seeds) return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, &seed, 1, 0, flags, labels_path);
+    if (fastf_check_seeds_("cap", seeds, n_seeds)) return 1;
+    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_seeds, 1, flags, labels_path);
+}
+
 int fastf_cap(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
               const uint64_t *caps, uint32_t n_n, uint32_t seed, uint32_t flags)
 {
-    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, &seed, 1, 0, flags);
+    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, &seed, 1, 0, flags, NULL);
 }
 
 int fastf_cap_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                    const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
     if (fastf_check_seeds_("cap", seeds, n_seeds)) return 1;
-    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_seeds, 1, flags);
+    return cap_run(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_seeds, 1, flags, NULL);
 }
 
 static void usage_cap(FILE *f)
@@ -381,6 +410,9 @@ static void usage_cap(FILE *f)
             "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: cap_neighbors.tsv and\n"
             "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
             "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps\n"
+            "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): cap_labels.tsv,\n"
+            "                          cap_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
+            "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_n<N>_s<seed>/, one cap.tsv row each, and cap_reps.tsv with mean, sd, min and max\n"
             "                          of every metric per grid point (with --genes cap_genes_reps.tsv and cap_gene_reps.tsv.gz in\n"
@@ -406,7 +438,8 @@ int cmd_cap(int argc, const char **argv)
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = (A.summary_only ? FASTF_CAP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_CAP_GENES : 0) | (A.per_cell ? FASTF_CAP_CELLS : 0) | (A.fidelity ? FASTF_CAP_FIDELITY : 0) |
                            (A.gene_fidelity ? FASTF_CAP_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_CAP_NEIGHBORS : 0);
-    if (A.n_seeds ? fastf_cap_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags)
+    if (A.labels ? fastf_cap_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
+        A.n_seeds ? fastf_cap_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags)
                   : fastf_cap(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cap failed: %s\n", fastf_last_error());
         return 1;
@@ -417,6 +450,7 @@ int cmd_cap(int argc, const char **argv)
     if (A.fidelity) printf("cap_fidelity.tsv is generated.\n");
     if (A.gene_fidelity) printf("cap_gene_fidelity.tsv is generated.\n");
     if (A.neighbors) printf("cap_neighbors.tsv is generated.\n");
+    if (A.labels) printf("cap_labels.tsv and cap_label_classes.tsv are generated.\n");
     if (A.n_seeds) printf("cap_reps.tsv is generated.\n");
     printf("cap.tsv is generated.\n");
     return 0;

@@ -193,6 +193,158 @@ void fastf_lists_free(fastf_lists_t *l)
     memset(l, 0, sizeof *l);
 }
 
+/* ------------------------------------------------------------------ */
+/* --labels: the labels file (include/fastf_amd.h)                     */
+/* ------------------------------------------------------------------ */
+typedef struct { const char *barcode; size_t line; uint32_t label; } lab_entry;   /* label: index into the labels as first seen, then the id; UINT32_MAX: NA */
+struct fastf_labels {
+    char *text;                          /* the file, fields cut in place */
+    lab_entry *e; size_t n;              /* ascending by barcode */
+    char (*name)[FASTF_LABEL_BYTES]; uint32_t n_labels;     /* name[0] = "NA", name[1 .. L] ascending */
+    uint64_t known, unknown;
+};
+
+static int cmp_lab_entry(const void *a, const void *b)
+{
+    const lab_entry *x = (const lab_entry *)a, *y = (const lab_entry *)b;
+    const int c = strcmp(x->barcode, y->barcode);
+    return c ? c : (x->line < y->line ? -1 : x->line > y->line);
+}
+static int cmp_str_ptr(const void *a, const void *b) { return strcmp(*(const char *const *)a, *(const char *const *)b); }
+typedef struct { char name[FASTF_LABEL_BYTES]; uint32_t seen; } lab_name;
+/* (bytewise order: strcmp compares as unsigned char, and the shorter of two strings with a common prefix comes first) */
+static int cmp_lab_name(const void *a, const void *b) { return strcmp(((const lab_name *)a)->name, ((const lab_name *)b)->name); }
+
+void fastf_labels_free(fastf_labels_t *t)
+{
+    if (!t) return;
+    free(t->text); free(t->e); free(t->name); free(t);
+}
+
+int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_labels_t **out)
+{
+    if (out) *out = NULL;
+    if (!labels_file || !barcodes_file || !out) return io_err("labels: null argument");
+    FILE *f = fopen(labels_file, "rb");
+    if (!f) return io_err("labels file: %s does not exist.", labels_file);
+    fastf_labels_t *t = (fastf_labels_t *)calloc(1, sizeof *t);
+    lab_name *names = (lab_name *)calloc(FASTF_LABELS_MAX + 1, sizeof *names);
+    char *btext = NULL, *barena = NULL; const char **blist = NULL;
+    uint32_t *id_of = NULL;
+    size_t len = 0, cap = 1 << 16, blen = 0;
+    int rc = 1;
+    if (!t || !names || !(t->text = (char *)malloc(cap + 1))) { io_err("labels: out of memory"); goto done; }
+    for (;;) {
+        if (len == cap) { cap *= 2; char *nt = (char *)realloc(t->text, cap + 1); if (!nt) { io_err("labels: out of memory"); goto done; } t->text = nt; }
+        const size_t r = fread(t->text + len, 1, cap - len, f);
+        if (!r) break;
+        len += r;
+    }
+    if (ferror(f)) { io_err("labels: read error on %s", labels_file); goto done; }
+    t->text[len] = '\0';
+    if (len >= 2 && (unsigned char)t->text[0] == 0x1f && (unsigned char)t->text[1] == 0x8b) {
+        io_err("labels: %s starts with the gzip magic: a labels file is plain text", labels_file); goto done;
+    }
+    {   size_t n_lines = 1;
+        for (size_t i = 0; i < len; i++) n_lines += t->text[i] == '\n';
+        if (!(t->e = (lab_entry *)malloc(n_lines * sizeof *t->e))) { io_err("labels: out of memory"); goto done; } }
+    uint32_t n_names = 0;
+    size_t line_no = 0;
+    for (size_t pos = 0; pos < len;) {
+        char *ln = t->text + pos;
+        char *nl = (char *)memchr(ln, '\n', len - pos);
+        size_t ll = nl ? (size_t)(nl - ln) : len - pos;
+        pos += ll + (nl ? 1 : 0);
+        line_no++;
+        if (ll && ln[ll - 1] == '\r') ll--;
+        ln[ll] = '\0';
+        if (!ll) continue;
+        if (memchr(ln, '\0', ll)) { io_err("labels: %s: line %zu holds a NUL byte", labels_file, line_no); goto done; }
+        size_t fields = 1;
+        for (size_t i = 0; i < ll; i++) fields += ln[i] == '\t';
+        if (fields != 2) { io_err("labels: %s: line %zu has %zu fields, not barcode<TAB>label", labels_file, line_no, fields); goto done; }
+        char *tab = (char *)memchr(ln, '\t', ll);
+        *tab = '\0';
+        const char *label = tab + 1;
+        const size_t lab_len = ll - (size_t)(label - ln);
+        if (line_no == 1 && strcmp(ln, "barcode") == 0) continue;
+        if (!lab_len) { io_err("labels: %s: line %zu: the label is empty", labels_file, line_no); goto done; }
+        if (lab_len >= FASTF_LABEL_BYTES) { io_err("labels: %s: line %zu: the label has %zu bytes, at most %u", labels_file, line_no, lab_len, FASTF_LABEL_BYTES - 1); goto done; }
+        uint32_t li = UINT32_MAX;
+        if (strcmp(label, "NA") != 0) {
+            for (li = 0; li < n_names && strcmp(names[li].name, label) != 0; li++) ;
+            if (li == n_names) {
+                if (n_names == FASTF_LABELS_MAX) {
+                    io_err("labels: %s: line %zu brings distinct label %u, at most %u (FASTF_LABELS_MAX)", labels_file, line_no, FASTF_LABELS_MAX + 1, FASTF_LABELS_MAX); goto done;
+                }
+                memcpy(names[n_names].name, label, lab_len + 1); names[n_names].seen = n_names; n_names++;
+            }
+        }
+        t->e[t->n].barcode = ln; t->e[t->n].line = line_no; t->e[t->n].label = li; t->n++;
+    }
+    qsort(t->e, t->n, sizeof *t->e, cmp_lab_entry);
+    {   size_t dup_line = 0, first_line = 0; const char *dup = NULL;
+        for (size_t i = 1; i < t->n; i++)
+            if (strcmp(t->e[i].barcode, t->e[i - 1].barcode) == 0 && (!dup_line || t->e[i].line < dup_line)) { dup_line = t->e[i].line; first_line = t->e[i - 1].line; dup = t->e[i].barcode; }
+        if (dup_line) { io_err("labels: %s: line %zu names barcode %s again (first on line %zu)", labels_file, dup_line, dup, first_line); goto done; } }
+    /* ids in bytewise order of the strings */
+    qsort(names, n_names, sizeof *names, cmp_lab_name);
+    if (!(id_of = (uint32_t *)malloc((n_names + 1) * sizeof *id_of)) || !(t->name = (char (*)[FASTF_LABEL_BYTES])calloc(n_names + 1, FASTF_LABEL_BYTES))) { io_err("labels: out of memory"); goto done; }
+    strcpy(t->name[0], "NA");
+    for (uint32_t k = 0; k < n_names; k++) { id_of[names[k].seen] = k + 1; memcpy(t->name[k + 1], names[k].name, FASTF_LABEL_BYTES); }
+    for (size_t i = 0; i < t->n; i++) t->e[i].label = t->e[i].label == UINT32_MAX ? 0 : id_of[t->e[i].label];
+    t->n_labels = n_names;
+    /* the barcode list, every line cut as fastf_lists_load_mem cuts it */
+    if (slurp_gz(barcodes_file, &btext, &blen)) goto done;
+    {   size_t pos = 0, n_b = 0, at = 0; char line[1024];
+        while (next_line(btext, blen, &pos, line)) n_b++;
+        barena = (char *)malloc(blen + n_b + 1); blist = (const char **)malloc((n_b + 1) * sizeof *blist);
+        if (!barena || !blist) { io_err("labels: out of memory"); goto done; }
+        pos = 0; n_b = 0;
+        while (next_line(btext, blen, &pos, line)) {
+            line[strcspn(line, "\n\r\t")] = '\0';
+            const size_t l = strlen(line) + 1;
+            memcpy(barena + at, line, l); blist[n_b++] = barena + at; at += l;
+        }
+        qsort(blist, n_b, sizeof *blist, cmp_str_ptr);
+        for (size_t i = 0; i < t->n; i++) {
+            const char *key = t->e[i].barcode;
+            if (bsearch(&key, blist, n_b, sizeof *blist, cmp_str_ptr)) t->known++; else t->unknown++;
+        } }
+    if (!t->known) { io_err("labels: %s: no line names a barcode of %s", labels_file, barcodes_file); goto done; }
+    rc = 0;
+done:
+    fclose(f);
+    free(names); free(btext); free(barena); free(blist); free(id_of);
+    if (rc) fastf_labels_free(t); else *out = t;
+    return rc;
+}
+
+uint32_t fastf_labels_count(const fastf_labels_t *t) { return t ? t->n_labels : 0; }
+const char *fastf_labels_name(const fastf_labels_t *t, uint32_t id) { return t && id <= t->n_labels ? t->name[id] : NULL; }
+uint64_t fastf_labels_unknown(const fastf_labels_t *t) { return t ? t->unknown : 0; }
+uint64_t fastf_labels_known(const fastf_labels_t *t) { return t ? t->known : 0; }
+
+uint32_t fastf_labels_id(const fastf_labels_t *t, const char *barcode)
+{
+    if (!t || !barcode) return 0;
+    size_t lo = 0, hi = t->n;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        const int c = strcmp(t->e[mid].barcode, barcode);
+        if (!c) return t->e[mid].label;
+        if (c < 0) lo = mid + 1; else hi = mid;
+    }
+    return 0;
+}
+
+int fastf_labels_assign(const fastf_labels_t *t, char *const *barcodes, uint32_t n, uint8_t *lab)
+{
+    if (!t || (n && (!barcodes || !lab))) return io_err("labels: null argument");
+    for (uint32_t i = 0; i < n; i++) lab[i] = (uint8_t)fastf_labels_id(t, barcodes[i]);
+    return 0;
+}
+
 /* ================================================================== */
 /* BAM reader — block-parallel BGZF inflate + parallel tag extraction  */
 /* ================================================================== */

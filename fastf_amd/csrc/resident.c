@@ -160,6 +160,8 @@ void fastf_res_rate_close(res_rate_t *S)
     if (S->h_gfid) fastf_pinned_free(S->h_gfid);
     fastf_devmem_free(S->d_nplanes); fastf_devmem_free(S->d_nbr);
     if (S->h_nbr) fastf_pinned_free(S->h_nbr);
+    fastf_devmem_free(S->d_lab);
+    if (S->h_lab) fastf_pinned_free(S->h_lab);
     memset(S, 0, sizeof *S);
 }
 
@@ -188,7 +190,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; }
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors, lb = S->labels; const fastf_labels_t *const lt = S->lab_t; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; S->labels = lb; S->lab_t = lt; }
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -284,6 +286,18 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         S->nbr_cells = nc; S->nbr_map_bytes = map_bytes;
         S->h_nkf = (uint32_t *)((char *)S->h_nbr + map_bytes); S->h_nkp = S->h_nkf + nc; S->h_nsh = S->h_nkp + nc; S->h_ngenes = S->h_nsh + nc;
         S->hvg_k = 0; S->nbr_planes = 0;
+    }
+    if (S->labels) {                                        /* lab[] of the pair's cells, the votes of the full rows and of a point, the two conf matrices and their pinned copy; lab[] goes up once per pair */
+        S->n_labels = fastf_labels_count(S->lab_t);
+        S->lab_cells = (room_cells + 3) & ~(size_t)3;
+        const size_t bytes = S->lab_cells + 2 * res_lab_half(S);
+        if (dev_room(&S->d_lab, &S->have.lab, bytes, device) || pin_room((void **)&S->h_lab, &S->have.h_lab, bytes)) {
+            rs_err("%s: the label arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, bytes, fastf_last_error());
+            return RES_FAIL;
+        }
+        const double tl = fastf_res_now();
+        if (fastf_labels_assign(S->lab_t, L->barcode, n_cells, S->h_lab) || (n_cells && fastf_devmem_copy(S->d_lab, S->h_lab, n_cells))) return RES_FAIL;
+        T->labels += fastf_res_now() - tl;
     }
     if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
         const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
@@ -537,6 +551,26 @@ int fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t
     return 0;
 }
 
+/* --labels: one vote call on the full (point == 0) or the point's neighbour sets, then that half of the block to the host in one copy */
+static int lab_votes(res_rate_t *S, int point)
+{
+    uint8_t *const d = (uint8_t *)S->d_lab + res_lab_off(S, point);
+    if (fastf_dev_label_votes(S->e, nbr_idx(S, point), nbr_cnt(S, point), (const uint8_t *)S->d_lab, S->n_cells, FASTF_NEIGHBORS_K, S->n_labels,
+                              d, d + S->lab_cells, d + 2 * S->lab_cells, (uint32_t *)(d + 3 * S->lab_cells), NULL) || fastf_devmem_sync())
+        return rs_err("%s: --labels at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+    return fastf_devmem_copy(S->h_lab + res_lab_off(S, point), d, res_lab_half(S));
+}
+
+int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->labels) return 0;
+    (void)point_name;
+    const double tt = fastf_res_now();
+    if (lab_votes(S, 1)) return 1;
+    T->labels += fastf_res_now() - tt;
+    return 0;
+}
+
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
     if (!S->fidelity && !S->gene_fid && !S->neighbors) return 0;
@@ -571,6 +605,10 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
         if (nbr_sets(S, nnz ? x_f : NULL, x_c, x_k, sm + SM_FULL, P, 0)) return 1;
         if (S->n_cells && fastf_devmem_copy(S->h_nkf, nbr_cnt(S, 0), (size_t)S->n_cells * 4)) return 1;
         T->neighbors += fastf_res_now() - tt; tt = fastf_res_now();
+    }
+    if (S->labels) {                                        /* the votes of the full sets, which stay for every point of the pair */
+        if (lab_votes(S, 0)) return 1;
+        T->labels += fastf_res_now() - tt; tt = fastf_res_now();
     }
     if (!S->fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
@@ -903,6 +941,63 @@ int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const c
     return 0;
 }
 
+int fastf_res_fid_open_labels(res_fid_t *F, const fastf_labels_t *labels, const char *verb, const char *out_dir, const char *header, const char *classes_header)
+{
+    if (!labels) return 0;
+    char name[64];
+    F->verb = verb;
+    snprintf(name, sizeof name, "%s_labels.tsv", verb);
+    if (fastf_res_tsv_open(&F->ltsv, out_dir, name, header)) return 1;
+    F->lab_on = 1;                                          /* (from here fastf_res_fid_close takes the table back) */
+    snprintf(name, sizeof name, "%s_label_classes.tsv", verb);
+    if (fastf_res_tsv_open(&F->ctsv, out_dir, name, classes_header)) return 1;
+    F->labels = labels; F->full = 1;
+    return 0;
+}
+
+/* --labels: the rows of the point and — dir != NULL — its labels.tsv.gz and label_confusion.tsv.gz */
+static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    const uint32_t L = S->n_labels;
+    const uint8_t *const lab = S->h_lab, *const pf = res_lab_pred(S, 0), *const pp = res_lab_pred(S, 1);
+    const uint32_t *const cx = res_lab_conf(S, 0), *const cy = res_lab_conf(S, 1);
+    char row[640];
+    if (fastf_labels_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, FASTF_NEIGHBORS_K, L, lab, pf, pp, res_lab_same(S, 0),
+                                 res_lab_labelled(S, 0), res_lab_same(S, 1), res_lab_labelled(S, 1), cx, cy, row, sizeof row)) return 1;
+    if (dir) {
+        char path[4200], line[512];
+        const size_t wide = 64 + (size_t)(L + 1) * FASTF_LABEL_BYTES;
+        char *const wl = (char *)malloc(wide);
+        const char **const names = (const char **)malloc(((size_t)L + 1) * sizeof *names);
+        uint32_t *const cells = (uint32_t *)calloc((size_t)L + 1, sizeof *cells);
+        gtext t = { NULL, 0, 0 }, u = { NULL, 0, 0 };
+        int bad = !wl || !names || !cells;
+        if (bad) rs_err("out of memory");
+        for (uint32_t l = 0; l <= L && !bad; l++) names[l] = fastf_labels_name(F->labels, l);
+        if (!bad) bad = gt_str(&t, fastf_labels_header());
+        for (uint32_t c = 0; c < S->n_cells && !bad; c++) {
+            cells[lab[c]]++;
+            bad = fastf_labels_row(S->L->barcode[c], names[lab[c]], names[pf[c]], names[pp[c]], res_lab_same(S, 0)[c], res_lab_labelled(S, 0)[c],
+                                   res_lab_same(S, 1)[c], res_lab_labelled(S, 1)[c], line, sizeof line) || gt_str(&t, line);
+        }
+        snprintf(path, sizeof path, "%s/labels.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        if (!bad) bad = fastf_label_confusion_header(names, L, wl, wide) || gt_str(&u, wl);
+        for (uint32_t a = 1; a <= L && !bad; a++)
+            bad = fastf_label_confusion_row(names[a], cells[a], cy + (size_t)(a - 1) * (L + 1), L, wl, wide) || gt_str(&u, wl);
+        snprintf(path, sizeof path, "%s/label_confusion.tsv.gz", dir);
+        if (!bad) bad = gz_text_renamed(path, &u);
+        free(t.p); free(u.p); free(wl); free(names); free(cells);
+        if (bad) return 1;
+    }
+    fputs(row, F->ltsv.f);
+    for (uint32_t a = 1; a <= L; a++) {
+        if (fastf_label_classes_row(S->rate_cell, rate_depth, list_value, S->seed, fastf_labels_name(F->labels, a), a, S->n_cells, L, lab, cx, cy, row, sizeof row)) return 1;
+        fputs(row, F->ctsv.f);
+    }
+    return 0;
+}
+
 /* --neighbors: the row of the point and — dir != NULL — its neighbors.tsv.gz */
 static int nbr_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
@@ -929,6 +1024,11 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
         const double tt = fastf_res_now();
         if (nbr_point(F, S, dir, rate_depth, list_value)) return 1;
         T->neighbors += fastf_res_now() - tt;
+    }
+    if (F->lab_on) {
+        const double tt = fastf_res_now();
+        if (lab_point(F, S, dir, rate_depth, list_value)) return 1;
+        T->labels += fastf_res_now() - tt;
     }
     if (F->gene_on) {
         const double tt = fastf_res_now();
@@ -959,15 +1059,16 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
 
 int fastf_res_fid_close(res_fid_t *F, int ok)
 {
-    if (!F->on && !F->gene_on && !F->nbr_on) return 0;
+    if (!F->on && !F->gene_on && !F->nbr_on && !F->lab_on) return 0;
     /* the tables are closed before any is renamed, and a rename that fails takes the others back: none is left alone */
-    res_tsv_t *const t[3] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL};
+    res_tsv_t *const t[5] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL, F->lab_on ? &F->ltsv : NULL,
+                             F->lab_on && F->labels ? &F->ctsv : NULL};
     int bad = 0, renamed = 0;
     const char *failed = NULL;
-    for (int k = 0; k < 3; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
-    for (int k = 0; k < 3 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
-    if (!ok || bad) for (int k = 0; k < 3; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
-    F->on = F->gene_on = F->nbr_on = F->full = 0;
+    for (int k = 0; k < 5; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
+    for (int k = 0; k < 5 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
+    if (!ok || bad) for (int k = 0; k < 5; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
+    F->on = F->gene_on = F->nbr_on = F->lab_on = F->full = 0; F->labels = NULL;
     return ok && bad ? rs_err("cannot write %s", failed) : 0;
 }
 
@@ -1258,8 +1359,8 @@ int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_gr
 
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
 {
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv"};
-    for (int k = 0; k < 8; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv", "labels.tsv", "label_classes.tsv"};
+    for (int k = 0; k < 10; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
 }
 
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
@@ -1275,11 +1376,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'L', "labels", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->labels = NULL;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1293,7 +1394,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNLER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1324,6 +1425,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'F': out->fidelity = 1; break;
         case 'Q': out->gene_fidelity = 1; break;
         case 'N': out->neighbors = 1; break;
+        case 'L': out->labels = val; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
         }

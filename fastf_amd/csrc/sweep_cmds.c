@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors]; -d accepted
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE]; -d accepted
  *                  and ignored, -u refused
  *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
@@ -26,6 +26,9 @@
  * --neighbors: the k-nearest-neighbour sets of the cells over the pair's highly variable genes, at full depth and at the point
  * (fastf_res_point_neighbors: fastf_dev_neighbor_planes, fastf_dev_neighbors, fastf_dev_neighbors_shared) into sweep_neighbors.tsv and
  * the point's neighbors.tsv.gz; it keeps the full rows and ranks the genes by itself.
+ * --labels FILE: the votes of those neighbour sets for the labels of the file (fastf_res_point_labels: fastf_dev_label_votes)
+ * into sweep_labels.tsv, sweep_label_classes.tsv and the point's labels.tsv.gz and label_confusion.tsv.gz; it switches the neighbour sets
+ * on by itself and writes no --neighbors file.
  * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
  * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
  * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
@@ -703,6 +706,121 @@ int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list
 }
 
 /* ------------------------------------------------------------------ */
+/* --labels: the host twin, the rows                                    */
+/* ------------------------------------------------------------------ */
+int fastf_label_votes(const uint32_t *idx, const uint32_t *cnt, const uint8_t *lab, uint32_t n_cells, uint32_t k, uint32_t n_labels,
+                      uint8_t *pred, uint8_t *same, uint8_t *labelled, uint32_t *conf)
+{
+    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return sw_err("label votes: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
+    if (n_labels > FASTF_LABELS_MAX) return sw_err("label votes: %u labels, at most %u", n_labels, FASTF_LABELS_MAX);
+    if ((n_labels && !conf) || (n_cells && (!idx || !cnt || !lab || !pred || !same || !labelled))) return sw_err("null argument");
+    if (n_labels) memset(conf, 0, (size_t)n_labels * (n_labels + 1) * sizeof *conf);
+    for (uint32_t i = 0; i < n_cells; i++) {
+        uint32_t votes[FASTF_LABELS_MAX + 1] = {0}, all = 0, best = 0;
+        const uint32_t c = cnt[i] < k ? cnt[i] : k, own = lab[i] <= n_labels ? lab[i] : 0;
+        for (uint32_t s = 0; s < c; s++) {
+            const uint32_t j = idx[(size_t)i * k + s];
+            const uint32_t l = j < n_cells && lab[j] <= n_labels ? lab[j] : 0;
+            if (l) { votes[l]++; all++; }
+        }
+        for (uint32_t l = 1; l <= n_labels; l++) if (votes[l] > votes[best]) best = l;     /* (votes[0] == 0: a first l needs one vote; ties keep the smaller l) */
+        pred[i] = (uint8_t)best; same[i] = (uint8_t)(own ? votes[own] : 0); labelled[i] = (uint8_t)all;
+        if (own) conf[(size_t)(own - 1) * (n_labels + 1) + best]++;
+    }
+    return 0;
+}
+
+const char *fastf_labels_header(void) { return "barcode\tlabel\tpred_full\tpred_point\tsame_full\tlabelled_full\tsame_point\tlabelled_point\n"; }
+#define LABELS_COLUMNS_TAIL "seed\tn_cells\tk\tn_labels\tcells_labelled\tagree_full\tagree_point\taccuracy_full\taccuracy_point\tkept\tpurity_full\tpurity_point\n"
+const char *fastf_sweep_labels_header(void) { return "rate_cell\trate_depth\t" LABELS_COLUMNS_TAIL; }
+const char *fastf_cap_labels_header(void) { return "rate_cell\treads_per_cell\t" LABELS_COLUMNS_TAIL; }
+const char *fastf_level_labels_header(void) { return "rate_cell\tumi_cap\t" LABELS_COLUMNS_TAIL; }
+#define LABEL_CLASSES_COLUMNS_TAIL "seed\tlabel\tcells\tcorrect_full\tcorrect_point\tpredicted_full\tpredicted_point\n"
+const char *fastf_sweep_label_classes_header(void) { return "rate_cell\trate_depth\t" LABEL_CLASSES_COLUMNS_TAIL; }
+const char *fastf_cap_label_classes_header(void) { return "rate_cell\treads_per_cell\t" LABEL_CLASSES_COLUMNS_TAIL; }
+const char *fastf_level_label_classes_header(void) { return "rate_cell\tumi_cap\t" LABEL_CLASSES_COLUMNS_TAIL; }
+
+int fastf_labels_row(const char *barcode, const char *label, const char *pred_full, const char *pred_point, uint32_t same_full, uint32_t labelled_full,
+                     uint32_t same_point, uint32_t labelled_point, char *buf, size_t cap)
+{
+    if (!barcode || !label || !pred_full || !pred_point || !buf) return sw_err("null argument");
+    const int n = snprintf(buf, cap, "%s\t%s\t%s\t%s\t%u\t%u\t%u\t%u\n", barcode, label, pred_full, pred_point, same_full, labelled_full, same_point, labelled_point);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("labels row too long") : 0;
+}
+
+int fastf_label_confusion_header(const char *const *names, uint32_t n_labels, char *buf, size_t cap)
+{
+    if (!buf || (n_labels && !names)) return sw_err("null argument");
+    int n = snprintf(buf, cap, "label\tcells\tNA");
+    for (uint32_t l = 1; l <= n_labels && n >= 0 && (size_t)n < cap; l++) {
+        const int m = snprintf(buf + n, cap - (size_t)n, "\t%s", names[l]);
+        n = m < 0 ? m : n + m;
+    }
+    if (n >= 0 && (size_t)n < cap) { const int m = snprintf(buf + n, cap - (size_t)n, "\n"); n = m < 0 ? m : n + m; }
+    return (n < 0 || (size_t)n >= cap) ? sw_err("confusion header too long") : 0;
+}
+
+int fastf_label_confusion_row(const char *label, uint32_t cells, const uint32_t *conf_row, uint32_t n_labels, char *buf, size_t cap)
+{
+    if (!label || !conf_row || !buf) return sw_err("null argument");
+    int n = snprintf(buf, cap, "%s\t%u", label, cells);
+    for (uint32_t b = 0; b <= n_labels && n >= 0 && (size_t)n < cap; b++) {
+        const int m = snprintf(buf + n, cap - (size_t)n, "\t%u", conf_row[b]);
+        n = m < 0 ? m : n + m;
+    }
+    if (n >= 0 && (size_t)n < cap) { const int m = snprintf(buf + n, cap - (size_t)n, "\n"); n = m < 0 ? m : n + m; }
+    return (n < 0 || (size_t)n >= cap) ? sw_err("confusion row too long") : 0;
+}
+
+static void lab_ratio(char *f, size_t cap, uint64_t num, uint64_t den)
+{
+    if (den) snprintf(f, cap, "%.6f", (double)num / (double)den); else snprintf(f, cap, "NA");
+}
+static void lab_second(char *f, size_t cap, float rate_depth, uint64_t list_value)
+{
+    if (list_value) snprintf(f, cap, "%llu", (unsigned long long)list_value); else snprintf(f, cap, "%.3f", (double)rate_depth);
+}
+
+int fastf_labels_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t k, uint32_t n_labels,
+                             const uint8_t *lab, const uint8_t *pred_full, const uint8_t *pred_point, const uint8_t *same_full, const uint8_t *labelled_full,
+                             const uint8_t *same_point, const uint8_t *labelled_point, const uint32_t *conf_full, const uint32_t *conf_point,
+                             char *buf, size_t cap)
+{
+    if (!buf || (n_cells && (!lab || !pred_full || !pred_point || !same_full || !labelled_full || !same_point || !labelled_point)) ||
+        (n_labels && (!conf_full || !conf_point))) return sw_err("null argument");
+    uint64_t cells_labelled = 0, kept = 0, sf = 0, lf = 0, sp = 0, lp = 0, agree_full = 0, agree_point = 0;
+    for (uint32_t i = 0; i < n_cells; i++) {
+        if (!lab[i] || lab[i] > n_labels) continue;
+        cells_labelled++;
+        kept += pred_full[i] == lab[i] && pred_point[i] == lab[i];
+        sf += same_full[i]; lf += labelled_full[i]; sp += same_point[i]; lp += labelled_point[i];
+    }
+    for (uint32_t a = 1; a <= n_labels; a++) { agree_full += conf_full[(size_t)(a - 1) * (n_labels + 1) + a]; agree_point += conf_point[(size_t)(a - 1) * (n_labels + 1) + a]; }
+    char f[5][40], second[32];
+    lab_ratio(f[0], sizeof f[0], agree_full, cells_labelled); lab_ratio(f[1], sizeof f[1], agree_point, cells_labelled);
+    lab_ratio(f[2], sizeof f[2], kept, agree_full); lab_ratio(f[3], sizeof f[3], sf, lf); lab_ratio(f[4], sizeof f[4], sp, lp);
+    lab_second(second, sizeof second, rate_depth, list_value);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%llu\t%llu\t%llu\t%s\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, k, n_labels,
+                           (unsigned long long)cells_labelled, (unsigned long long)agree_full, (unsigned long long)agree_point, f[0], f[1], f[2], f[3], f[4]);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
+}
+
+int fastf_label_classes_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *label, uint32_t a, uint32_t n_cells,
+                            uint32_t n_labels, const uint8_t *lab, const uint32_t *conf_full, const uint32_t *conf_point, char *buf, size_t cap)
+{
+    if (!buf || !label || !conf_full || !conf_point || (n_cells && !lab)) return sw_err("null argument");
+    if (a < 1 || a > n_labels) return sw_err("label classes: label %u, from 1 to %u", a, n_labels);
+    uint64_t cells = 0, pf = 0, pp = 0;
+    for (uint32_t i = 0; i < n_cells; i++) cells += lab[i] == a;
+    for (uint32_t r = 0; r < n_labels; r++) { pf += conf_full[(size_t)r * (n_labels + 1) + a]; pp += conf_point[(size_t)r * (n_labels + 1) + a]; }
+    char second[32];
+    lab_second(second, sizeof second, rate_depth, list_value);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%s\t%llu\t%u\t%u\t%llu\t%llu\n", (double)rate_cell, second, seed, label, (unsigned long long)cells,
+                           conf_full[(size_t)(a - 1) * (n_labels + 1) + a], conf_point[(size_t)(a - 1) * (n_labels + 1) + a], (unsigned long long)pf, (unsigned long long)pp);
+    return (n < 0 || (size_t)n >= cap) ? sw_err("classes row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -861,6 +979,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
         if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
         if (fastf_res_point_neighbors(S, name, T)) goto done;
+        if (fastf_res_point_labels(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
@@ -916,7 +1035,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
@@ -945,6 +1064,8 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
                                T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
     if (prof && Fd->gene_on) fprintf(stderr, "[sweep] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+    if (prof && Fd->lab_on) fprintf(stderr, "[sweep] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
+                                    (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
     if (prof && Fd->nbr_on) fprintf(stderr, "[sweep] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
 done:
     fastf_res_rate_close(&S);
@@ -958,8 +1079,8 @@ done:
 /* the command                                                         */
 /* ------------------------------------------------------------------ */
 /* reps != 0: a replicate run (fastf_sweep_reps) — the suffixed directories and the replicate tables, with one seed too */
-static int sweep_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags)
+static int sweep_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels)
 {
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
@@ -973,6 +1094,7 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
         several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
     if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
+    if (several && labels) return sw_err("sweep: --labels needs the resident form, and this job is outside it (several devices)");
     if (several && neighbors) return sw_err("sweep: --neighbors needs the resident form, and this job is outside it (several devices)");
     if (several && fidelity && gene_fidelity) return sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (several devices)");
     if (several && fidelity) return sw_err("sweep: --fidelity needs the resident form, and this job is outside it (several devices)");
@@ -987,12 +1109,17 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     res_fid_t Fd;
     if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "sweep", out_dir, fastf_sweep_fidelity_header(), fastf_sweep_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     if (fastf_res_fid_open_neighbors(&Fd, neighbors, "sweep", out_dir, fastf_sweep_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
+    if (fastf_res_fid_open_labels(&Fd, labels, "sweep", out_dir, fastf_sweep_labels_header(), fastf_sweep_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
     }
 
     int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
+    if (rc == RES_NOT_COVERED && labels) {
+        sw_err("sweep: --labels needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
+        rc = RES_FAIL;
+    }
     if (rc == RES_NOT_COVERED && neighbors) {
         sw_err("sweep: --neighbors needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
         rc = RES_FAIL;
@@ -1044,10 +1171,32 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
     return 0;
 }
 
+/* labels_path != NULL: the labels file is read and checked before anything is written */
+static int sweep_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path)
+{
+    if (!labels_path) return sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, NULL);
+    if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
+    if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
+    fastf_labels_t *labels = NULL;
+    if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
+    const int rc = sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, labels);
+    fastf_labels_free(labels);
+    return rc;
+}
+
+int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
+{
+    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path);
+    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path);
+}
+
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
 {
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags);
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, NULL);
 }
 
 /* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
@@ -1063,7 +1212,7 @@ int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes,
                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
     if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags);
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, NULL);
 }
 
 static void usage_sweep(FILE *f)
@@ -1094,6 +1243,10 @@ static void usage_sweep(FILE *f)
             "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: sweep_neighbors.tsv and\n"
             "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
             "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps; resident form only\n"
+            "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): sweep_labels.tsv,\n"
+            "                          sweep_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
+            "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point;\n"
+            "                          resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -1118,7 +1271,8 @@ int cmd_sweep(int argc, const char **argv)
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0) |
                            (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
-    if (A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
+    if (A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
+        A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
@@ -1129,6 +1283,7 @@ int cmd_sweep(int argc, const char **argv)
     if (A.fidelity) printf("sweep_fidelity.tsv is generated.\n");
     if (A.gene_fidelity) printf("sweep_gene_fidelity.tsv is generated.\n");
     if (A.neighbors) printf("sweep_neighbors.tsv is generated.\n");
+    if (A.labels) printf("sweep_labels.tsv and sweep_label_classes.tsv are generated.\n");
     if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;

@@ -13,6 +13,7 @@
 #include "fidelity_kernels.hpp"
 #include "gene_fidelity_kernels.hpp"
 #include "neighbors_kernels.hpp"
+#include "labels_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -244,6 +245,7 @@ struct fastf_engine {
     bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
     bool gmom_lds_attr = false;          // the same for gene_moments_kernel<true>
     bool nbr_lds_attr = false;           // the same for the six nbr_gram_kernel forms
+    bool lab_lds_attr = false;           // the same for the three label_votes_kernel<G, true> forms
     DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
@@ -1340,6 +1342,54 @@ extern "C" int fastf_dev_neighbors_shared(fastf_engine_t* e, const uint32_t* d_i
     return 0;
 } FASTF_CATCH_INT
 
+template <u32 G>
+static int label_votes_launch(fastf_engine* e, hipStream_t s, bool lds_form, const u32* idx, const u32* cnt, const unsigned char* lab, u32 n, u32 k, u32 n_labels,
+                              unsigned char* pred, unsigned char* same, unsigned char* labelled, u32* conf) {
+    const u32 per_pass = LAB_THREADS / G, blocks_all = (n + per_pass - 1) / per_pass;
+    if (lds_form) {
+        // one workgroup a CU at the most: each zeroes and flushes its own copy of the counts
+        hipLaunchKernelGGL((label_votes_kernel<G, true>), dim3(std::min<u32>(blocks_all, (u32)g_cu_count)), dim3(LAB_THREADS), (size_t)lab_conf_words(n_labels) * sizeof(u32), s,
+                           idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
+    } else {
+        hipLaunchKernelGGL((label_votes_kernel<G, false>), dim3(std::min<u32>(blocks_all, 8u * (u32)g_cu_count)), dim3(LAB_THREADS), 0, s,
+                           idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
+    }
+    (void)e;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// --labels: the label votes of the neighbour sets (label_votes_kernel).  d_idx, d_cnt: what fastf_dev_neighbors wrote for (n_cells, k);
+// d_lab: u8[n_cells], 0 unlabelled, 1 .. n_labels.  d_pred, d_same, d_labelled: u8[n_cells]; d_conf: u32[n_labels * (n_labels + 1)],
+// zeroed here.  The counts of a workgroup are added up in LDS where they fit it (201 labels and fewer); FASTF_LABELS_LDS=0 takes the
+// general form, global atomics alone, for every n_labels (tests, A/B runs).  Stream-ordered.
+extern "C" int fastf_dev_label_votes(fastf_engine_t* e, const uint32_t* d_idx, const uint32_t* d_cnt, const uint8_t* d_lab, uint32_t n_cells, uint32_t k,
+                                     uint32_t n_labels, uint8_t* d_pred, uint8_t* d_same, uint8_t* d_labelled, uint32_t* d_conf, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > LAB_MAX_K) return set_err("fastf_dev_label_votes: k = %u, from 1 to %u", k, LAB_MAX_K);
+    if (n_labels > LAB_MAX_LABELS) return set_err("fastf_dev_label_votes: %u labels, at most %u", n_labels, LAB_MAX_LABELS);
+    if (n_labels && !d_conf) return set_err("fastf_dev_label_votes: null argument");
+    if (n_labels) HIP_OK(hipMemsetAsync(d_conf, 0, (size_t)lab_conf_words(n_labels) * sizeof(u32), s));
+    if (!n_cells) return 0;
+    if (!d_idx || !d_cnt || !d_lab || !d_pred || !d_same || !d_labelled) return set_err("fastf_dev_label_votes: null argument");
+    const char* lf = getenv("FASTF_LABELS_LDS");
+    const bool lds_form = lab_conf_fits_lds(n_labels) && !(lf && lf[0] == '0');
+    if (lds_form && !e->lab_lds_attr) {                      // (per engine, on first use: the attribute belongs to the current device's function)
+        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
+        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
+        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
+        e->lab_lds_attr = true;
+    }
+    int rc;
+    if (k <= 16) rc = label_votes_launch<16>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
+    else if (k <= 32) rc = label_votes_launch<32>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
+    else rc = label_votes_launch<64>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
+    if (rc) return 1;
+    dbg_sync(s, "label votes");
+    return 0;
+} FASTF_CATCH_INT
+
 // Replicate runs: d_cells_per_gene (what fastf_dev_gene_summary left, still on the device) added into the three u64[n_features]
 // accumulators of a grid point (gene_reps_kernel).  Nothing is cleared here: the caller zeroes the accumulators before the first seed.
 extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cells_per_gene, uint32_t n_features, uint64_t* d_detected,
@@ -1972,7 +2022,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

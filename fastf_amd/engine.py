@@ -463,6 +463,13 @@ class Engine:
         """--neighbors: d_shared[i] (u32) = the cells in both neighbour sets of cell i; stream-ordered"""
         check(self._L.fastf_dev_neighbors_shared(self._h, d_idx_a or None, d_cnt_a or None, d_idx_b or None, d_cnt_b or None, n_cells, k, d_shared or None, stream))
 
+    def dev_label_votes(self, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf, stream=0):
+        """--labels: the neighbour sets Engine.dev_neighbors left (d_idx, d_cnt) and d_lab (u8[n_cells], 0 unlabelled) -> d_pred, d_same,
+        d_labelled (u8[n_cells]) and d_conf (u32[n_labels * (n_labels + 1)], zeroed by the call); FASTF_LABELS_LDS=0: the confusion counts
+        by global atomics alone; stream-ordered"""
+        check(self._L.fastf_dev_label_votes(self._h, d_idx or None, d_cnt or None, d_lab or None, n_cells, k, n_labels, d_pred or None, d_same or None,
+                                            d_labelled or None, d_conf or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

@@ -16,6 +16,7 @@ GENE_FIDELITY = 128   # FASTF_SWEEP_GENE_FIDELITY
 HVG_TOP = 2000        # FASTF_HVG_TOP
 NEIGHBORS = 512       # FASTF_SWEEP_NEIGHBORS
 NEIGHBORS_K = 15      # FASTF_NEIGHBORS_K
+LABELS_MAX = 255      # FASTF_LABELS_MAX
 COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
@@ -32,6 +33,12 @@ POINT_GENE_FIDELITY_COLUMNS = ("feature", "sum_x", "sum_y", "cells_full", "cells
 NEIGHBORS_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "cells_defined", "median_overlap", "p10_overlap", "mean_overlap", "mean_k_point")
 NEIGHBORS_COLUMNS = ("rate_cell", "rate_depth") + NEIGHBORS_TAIL_COLUMNS
 POINT_NEIGHBORS_COLUMNS = ("barcode", "k_full", "k_point", "shared", "overlap")     # <point dir>/neighbors.tsv.gz
+LABELS_TAIL_COLUMNS = ("seed", "n_cells", "k", "n_labels", "cells_labelled", "agree_full", "agree_point", "accuracy_full", "accuracy_point", "kept",
+                       "purity_full", "purity_point")
+LABELS_COLUMNS = ("rate_cell", "rate_depth") + LABELS_TAIL_COLUMNS
+LABEL_CLASSES_TAIL_COLUMNS = ("seed", "label", "cells", "correct_full", "correct_point", "predicted_full", "predicted_point")
+LABEL_CLASSES_COLUMNS = ("rate_cell", "rate_depth") + LABEL_CLASSES_TAIL_COLUMNS
+POINT_LABELS_COLUMNS = ("barcode", "label", "pred_full", "pred_point", "same_full", "labelled_full", "same_point", "labelled_point")     # <point dir>/labels.tsv.gz
 POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
@@ -46,7 +53,7 @@ def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
@@ -54,10 +61,16 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     (read_fidelity_table) and a fidelity.tsv.gz per point directory (read_point_fidelity): every point against the full-depth data
     of the same cells; gene_fidelity=True the same comparison per gene: out/sweep_gene_fidelity.tsv (read_gene_fidelity_table) and a
     gene_fidelity.tsv.gz per point directory (read_point_gene_fidelity); neighbors=True the comparison between the cells:
-    out/sweep_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory (read_point_neighbors)"""
+    out/sweep_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory (read_point_neighbors); labels=<path>
+    (`--labels`: one barcode<TAB>label per line) the label votes of those neighbours: out/sweep_labels.tsv (read_labels_table),
+    out/sweep_label_classes.tsv (read_label_classes_table) and labels.tsv.gz (read_point_labels), label_confusion.tsv.gz per point directory"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if labels is not None:
+        _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
+                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), seed % (1 << 32), enc(labels)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
                                       seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
@@ -69,7 +82,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -77,6 +90,10 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     rd, prd = _floats(rates_depth)
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if labels is not None:
+        _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
+                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0, enc(labels)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
                                            _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
@@ -280,6 +297,124 @@ def neighbors_summary_row(rate_cell, rate_depth, seed, hvg_k, k_full, k_point, s
     buf = C.create_string_buffer(640)
     _lib.check(_lib.lib().fastf_neighbors_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(hvg_k), int(k),
                                                       a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def read_labels_table(path, columns=LABELS_COLUMNS):
+    """the rows of sweep_labels.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_label_classes_table(path, columns=LABEL_CLASSES_COLUMNS):
+    """the rows of sweep_label_classes.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_labels(path):
+    """the rows of a point's labels.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_LABELS_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_LABELS_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def labels_header(verb: str = "", classes: bool = False) -> str:
+    """the header of labels.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_labels.tsv (classes: of <verb>_label_classes.tsv)"""
+    return getattr(_lib.lib(), "fastf_%slabel%s_header" % (verb + "_" if verb else "", "_classes" if classes else "s"))().decode()
+
+
+class Labels:
+    """a labels file loaded against a barcode list file (fastf_labels_load): names[0] == "NA", names[1 .. n_labels] ascending bytewise"""
+
+    def __init__(self, labels_file, barcodes_file):
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().fastf_labels_load(os.fspath(labels_file).encode(), os.fspath(barcodes_file).encode(), C.byref(self._h)))
+        L = _lib.lib()
+        self.n_labels = L.fastf_labels_count(self._h)
+        self.names = [L.fastf_labels_name(self._h, k) for k in range(self.n_labels + 1)]
+        self.known, self.unknown = L.fastf_labels_known(self._h), L.fastf_labels_unknown(self._h)
+
+    def id(self, barcode) -> int:
+        return _lib.lib().fastf_labels_id(self._h, barcode.encode() if isinstance(barcode, str) else barcode)
+
+    def assign(self, barcodes):
+        """lab (u8) of a list of barcodes"""
+        b = [x.encode() if isinstance(x, str) else x for x in barcodes]
+        arr = (C.c_char_p * max(len(b), 1))(*b)
+        lab = np.zeros(max(len(b), 1), np.uint8)
+        _lib.check(_lib.lib().fastf_labels_assign(self._h, arr, len(b), lab.ctypes.data))
+        return lab[:len(b)]
+
+    def close(self):
+        if self._h:
+            _lib.lib().fastf_labels_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+def label_votes(idx, cnt, lab, k: int, n_labels: int):
+    """(pred, same, labelled u8[n], conf u32[n_labels, n_labels + 1]) of neighbour sets idx (u32[n, k]), cnt (u32[n]) and labels lab
+    (u8[n]): the host form of Engine.dev_label_votes"""
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    n = len(cnt)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    lab = np.ascontiguousarray(lab, dtype=np.uint8)
+    assert len(idx) == n * k and len(lab) == n
+    out = [np.zeros(max(n, 1), np.uint8) for _ in range(3)]
+    conf = np.full(max(n_labels * (n_labels + 1), 1), 0xDEADBEEF, np.uint32)
+    _lib.check(_lib.lib().fastf_label_votes(idx.ctypes.data, cnt.ctypes.data, lab.ctypes.data, n, k, n_labels, out[0].ctypes.data, out[1].ctypes.data,
+                                            out[2].ctypes.data, conf.ctypes.data))
+    return out[0][:n], out[1][:n], out[2][:n], conf[:n_labels * (n_labels + 1)].reshape(n_labels, n_labels + 1)
+
+
+def _b(x):
+    return x.encode() if isinstance(x, str) else x
+
+
+def labels_row(barcode, label, pred_full, pred_point, same_full, labelled_full, same_point, labelled_point) -> str:
+    """one row of labels.tsv.gz (with its newline)"""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_labels_row(_b(barcode), _b(label), _b(pred_full), _b(pred_point), int(same_full), int(labelled_full), int(same_point),
+                                           int(labelled_point), buf, len(buf)))
+    return buf.value.decode()
+
+
+def label_confusion_header(names) -> str:
+    """names[0] is "NA" and not read; names[1:] the labels"""
+    arr = (C.c_char_p * len(names))(*[_b(x) for x in names])
+    buf = C.create_string_buffer(64 + 64 * len(names))
+    _lib.check(_lib.lib().fastf_label_confusion_header(arr, len(names) - 1, buf, len(buf)))
+    return buf.value.decode()
+
+
+def label_confusion_row(label, cells, conf_row) -> str:
+    c = np.ascontiguousarray(conf_row, dtype=np.uint32)
+    buf = C.create_string_buffer(128 + 12 * len(c))
+    _lib.check(_lib.lib().fastf_label_confusion_row(_b(label), int(cells), c.ctypes.data, len(c) - 1, buf, len(buf)))
+    return buf.value.decode()
+
+
+def labels_summary_row(rate_cell, rate_depth, seed, k, n_labels, lab, pred_full, pred_point, same_full, labelled_full, same_point, labelled_point,
+                       conf_full, conf_point, list_value: int = 0) -> str:
+    """one row of <verb>_labels.tsv (with its newline); list_value >= 1: that integer in the second column (cap, level)"""
+    a = [np.ascontiguousarray(x, dtype=np.uint8) for x in (lab, pred_full, pred_point, same_full, labelled_full, same_point, labelled_point)]
+    cf, cp = (np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (conf_full, conf_point))
+    n = len(a[0])
+    assert all(len(x) == n for x in a) and len(cf) == len(cp) == n_labels * (n_labels + 1)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_labels_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(k), int(n_labels),
+                                                   *[x.ctypes.data for x in a], cf.ctypes.data, cp.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def label_classes_row(rate_cell, rate_depth, seed, label, a, n_labels, lab, conf_full, conf_point, list_value: int = 0) -> str:
+    """one row of <verb>_label_classes.tsv (with its newline) for label a (1 .. n_labels)"""
+    lab = np.ascontiguousarray(lab, dtype=np.uint8)
+    cf, cp = (np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (conf_full, conf_point))
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_label_classes_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), _b(label), int(a), len(lab),
+                                                  int(n_labels), lab.ctypes.data, cf.ctypes.data, cp.ctypes.data, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -394,6 +394,91 @@ int fastf_neighbors_row(const char *barcode, uint32_t k_full, uint32_t k_point, 
  * rate_depth) */
 int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
                                 const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap);
+
+/* --- --labels FILE on sweep, cap and level (fastf_sweep_labels, fastf_cap_labels, fastf_level_labels; `labels=` in Python; the long
+ * option alone): do the cell types survive at this depth.  The user brings one label per barcode from the full-depth analysis; the
+ * neighbour sets of --neighbors turn them into votes.
+ * The file: plain text, one `barcode<TAB>label` per line, lines end in LF, one trailing CR is dropped, empty lines are skipped.  The
+ * first line is a header, and skipped, iff its first field is exactly `barcode`.  A barcode is matched as the exact string
+ * barcodes.tsv.gz prints for a cell; a label is 1 to 63 bytes without a tab; the label `NA` means unlabelled.  Refused by name, with the
+ * line number, before the output directory is made: a file that does not exist or starts with the gzip magic, a line without exactly
+ * two fields, a label that is empty or 64 bytes or longer, a barcode named twice, more than FASTF_LABELS_MAX distinct labels, and a
+ * file of which no line names a barcode of the barcode list.  A barcode that is not in the barcode list is counted (labels_unknown in
+ * the stage line) and ignored; a listed barcode without a line is unlabelled.
+ * Label ids: 1 .. L in ascending bytewise order of the label strings (on a common prefix the shorter first), whatever the order of the
+ * file; 0 is unlabelled.  Per (cell rate, seed) pair lab[i] (u8) for the n sampled cells in the order of barcodes.tsv.gz.
+ * X, Y, A, N_M(i) and k = FASTF_NEIGHBORS_K are exactly those of --neighbors.  For M in {X, Y}:
+ *   votes_M(i, l) = #{ j in N_M(i) : lab[j] == l } for l in 1 .. L (unlabelled neighbours do not vote)
+ *   labelled_M(i) = sum_l votes_M(i, l)
+ *   same_M(i)     = votes_M(i, lab[i]), 0 when lab[i] == 0
+ *   pred_M(i)     = the l with the most votes, ties to the smallest l; 0 when labelled_M(i) == 0 (cells with lab[i] == 0 are predicted too)
+ *   conf_M[a][b]  = #{ i : lab[i] == a, pred_M(i) == b } for a in 1 .. L, b in 0 .. L (u32)
+ * Everything is integers; no floating point is used before the printing.
+ *   <point dir>/labels.tsv.gz (not with --summary-only): a header and one row per barcode in the order of barcodes.tsv.gz:
+ *     barcode label pred_full pred_point same_full labelled_full same_point labelled_point     (labels as their strings, NA for 0)
+ *   <point dir>/label_confusion.tsv.gz (not with --summary-only): the header `label cells NA <label 1> ... <label L>` and one row per
+ *     label a: cells = #{i : lab[i] == a}, then conf_Y[a][0 .. L]
+ *   <out_dir>/<verb>_labels.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), in the row
+ *     order of <verb>_neighbors.tsv — through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells k n_labels cells_labelled agree_full agree_point accuracy_full accuracy_point kept purity_full purity_point
+ *     agree_M = sum_a conf_M[a][a]; accuracy_M = agree_M / cells_labelled; kept = #{i : lab[i] >= 1, pred_X(i) == lab[i],
+ *     pred_Y(i) == lab[i]} / agree_full; purity_M = sum same_M / sum labelled_M over the cells with lab[i] >= 1; the ratios %.6f, NA on a
+ *     zero denominator
+ *   <out_dir>/<verb>_label_classes.tsv likewise, one row per (point, label): the leading columns and seed, then
+ *     label cells correct_full correct_point predicted_full predicted_point
+ *     correct_M = conf_M[a][a], predicted_M = the column sum of conf_M over a
+ * No _reps aggregate is written.  The option switches on, by itself, the full-depth rows, the per-gene sums that rank A and the
+ * neighbour sets of --neighbors, and writes none of that option's files unless it is given too; every other output is the bytes it is
+ * without the option.  Jobs outside the resident form are refused as --neighbors refuses them, naming --labels. --- */
+#define FASTF_LABELS_MAX 255u
+#define FASTF_LABEL_BYTES 64u                /* a label with its terminator */
+typedef struct fastf_labels fastf_labels_t;
+/* the labels file against the barcode list file (every line of it, cut as the list loader cuts it); on failure *out is NULL and
+ * fastf_last_error() names the file and the line */
+int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_labels_t **out);
+void fastf_labels_free(fastf_labels_t *t);
+uint32_t fastf_labels_count(const fastf_labels_t *t);                        /* L */
+const char *fastf_labels_name(const fastf_labels_t *t, uint32_t id);         /* id 0: "NA"; beyond L: NULL */
+uint64_t fastf_labels_unknown(const fastf_labels_t *t);                      /* lines whose barcode is not in the barcode list */
+uint64_t fastf_labels_known(const fastf_labels_t *t);                        /* lines whose barcode is */
+uint32_t fastf_labels_id(const fastf_labels_t *t, const char *barcode);      /* 0: no line, or NA */
+/* lab[i] = fastf_labels_id(t, barcodes[i]) for n barcodes */
+int fastf_labels_assign(const fastf_labels_t *t, char *const *barcodes, uint32_t n, uint8_t *lab);
+/* the host twin of fastf_dev_label_votes: the same arguments on host arrays.  idx: k slots a cell, cnt[i] of them valid (more than k
+ * counts as k); no slot from cnt[i] on is read as an index, an index of n_cells and beyond and a label above n_labels count as
+ * unlabelled.  conf (n_labels * (n_labels + 1) u32) is zeroed by the call */
+int fastf_label_votes(const uint32_t *idx, const uint32_t *cnt, const uint8_t *lab, uint32_t n_cells, uint32_t k, uint32_t n_labels,
+                      uint8_t *pred, uint8_t *same, uint8_t *labelled, uint32_t *conf);
+const char *fastf_labels_header(void);             /* the header of labels.tsv.gz */
+const char *fastf_sweep_labels_header(void);       /* the headers of <verb>_labels.tsv */
+const char *fastf_cap_labels_header(void);
+const char *fastf_level_labels_header(void);
+const char *fastf_sweep_label_classes_header(void);    /* the headers of <verb>_label_classes.tsv */
+const char *fastf_cap_label_classes_header(void);
+const char *fastf_level_label_classes_header(void);
+/* one row of labels.tsv.gz (with its newline); the three labels as their strings */
+int fastf_labels_row(const char *barcode, const char *label, const char *pred_full, const char *pred_point, uint32_t same_full, uint32_t labelled_full,
+                     uint32_t same_point, uint32_t labelled_point, char *buf, size_t cap);
+/* the header of label_confusion.tsv.gz for names[1 .. n_labels] (names[0] is not read), and the row of one label: conf_row[0 .. n_labels] */
+int fastf_label_confusion_header(const char *const *names, uint32_t n_labels, char *buf, size_t cap);
+int fastf_label_confusion_row(const char *label, uint32_t cells, const uint32_t *conf_row, uint32_t n_labels, char *buf, size_t cap);
+/* one row of <verb>_labels.tsv (with its newline); the second column as fastf_genes_summary_row prints it (list_value == 0: rate_depth) */
+int fastf_labels_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t k, uint32_t n_labels,
+                             const uint8_t *lab, const uint8_t *pred_full, const uint8_t *pred_point, const uint8_t *same_full, const uint8_t *labelled_full,
+                             const uint8_t *same_point, const uint8_t *labelled_point, const uint32_t *conf_full, const uint32_t *conf_point,
+                             char *buf, size_t cap);
+/* one row of <verb>_label_classes.tsv (with its newline) for label a (1 .. n_labels) */
+int fastf_label_classes_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *label, uint32_t a, uint32_t n_cells,
+                            uint32_t n_labels, const uint8_t *lab, const uint32_t *conf_full, const uint32_t *conf_point, char *buf, size_t cap);
+/* sweep, cap and level with --labels: the arguments of the verb's _reps call, then seed and labels_path.  n_seeds == 0: the plain run at
+ * `seed` (the directories and tables fastf_sweep() writes; seeds is not read); n_seeds >= 1: the replicate run.  labels_path == NULL:
+ * exactly the existing call.  flags: the existing word, no new bit */
+int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path);
+int fastf_cap_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path);
+int fastf_level_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -879,6 +964,16 @@ int fastf_dev_neighbors(fastf_engine_t *e, const void *d_planes, uint32_t planes
                         uint32_t *d_cnt, uint64_t *d_norms, uint64_t *max_norm_out, void *stream);
 int fastf_dev_neighbors_shared(fastf_engine_t *e, const uint32_t *d_idx_a, const uint32_t *d_cnt_a, const uint32_t *d_idx_b, const uint32_t *d_cnt_b,
                                uint32_t n_cells, uint32_t k, uint32_t *d_shared, void *stream);
+
+/* --labels (section above), one call on device pointers (label_votes_kernel).  d_idx and d_cnt are what fastf_dev_neighbors writes: k
+ * slots a cell, d_cnt[i] of them valid; the other slots hold 0xFFFFFFFF and are never used as an index.  k from 1 to 64, n_labels up to
+ * FASTF_LABELS_MAX.  d_lab: u8[n_cells].  d_pred, d_same, d_labelled: u8[n_cells]; d_conf: n_labels x (n_labels + 1) u32, zeroed by the
+ * call.  A cell owns a lane group of 16, 32 or 64 lanes, the smallest that holds k; the confusion counts of a workgroup are added up
+ * in LDS where n_labels * (n_labels + 1) * 4 bytes fit it (201 labels and fewer) and flushed with one global atomic per non-zero
+ * entry, else every labelled cell adds with a global atomic; FASTF_LABELS_LDS=0 takes that general form always.  Asynchronous on
+ * `stream` */
+int fastf_dev_label_votes(fastf_engine_t *e, const uint32_t *d_idx, const uint32_t *d_cnt, const uint8_t *d_lab, uint32_t n_cells, uint32_t k,
+                          uint32_t n_labels, uint8_t *d_pred, uint8_t *d_same, uint8_t *d_labelled, uint32_t *d_conf, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
