@@ -141,6 +141,10 @@ ABI_SYMBOLS = [
     "fastf_sweep_label_classes_header", "fastf_cap_label_classes_header", "fastf_level_label_classes_header", "fastf_labels_row",
     "fastf_label_confusion_header", "fastf_label_confusion_row", "fastf_labels_summary_row", "fastf_label_classes_row",
     "fastf_sweep_labels", "fastf_cap_labels", "fastf_level_labels", "fastf_dev_label_votes",
+    # --markers of sweep, cap and level
+    "fastf_marker_auc", "fastf_marker_auc_form", "fastf_marker_rank", "fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header",
+    "fastf_level_markers_header", "fastf_markers_row", "fastf_markers_summary_rows", "fastf_sweep_markers", "fastf_cap_markers", "fastf_level_markers",
+    "fastf_dev_marker_auc",
 ]
 
 
@@ -410,6 +414,17 @@ def lib():
     L.fastf_cap_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
     L.fastf_level_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
     L.fastf_dev_label_votes.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
+    for name in ("fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header", "fastf_level_markers_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_marker_auc.argtypes = [vp, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.fastf_marker_auc_form.argtypes = [u32, u32]
+    L.fastf_marker_rank.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.fastf_markers_row.argtypes = [C.c_char_p, C.c_char_p, u32, u32, u32, u32, u64, u64, u32, u32, u32, u32, u64, C.c_char_p, sz]
+    L.fastf_markers_summary_rows.argtypes = [C.c_float, C.c_float, u64, u32, C.POINTER(C.c_char_p), u32, u32, u32, vp, vp, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_sweep_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32]
+    L.fastf_cap_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
+    L.fastf_level_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
+    L.fastf_dev_marker_auc.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

@@ -26,12 +26,13 @@ gene_fidelity_metrics = _sweep.gene_fidelity_metrics
 NEIGHBORS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.NEIGHBORS_TAIL_COLUMNS
 LABELS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.LABELS_TAIL_COLUMNS
 LABEL_CLASSES_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.LABEL_CLASSES_TAIL_COLUMNS
+MARKERS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.MARKERS_TAIL_COLUMNS
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one function for both verbs)
 
 
 def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
     rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
     out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
@@ -43,6 +44,11 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                                seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
@@ -54,7 +60,7 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
 
 
 def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
@@ -62,6 +68,12 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
+                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                None if labels is None else enc(labels), _sweep._markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
@@ -128,6 +140,11 @@ def read_labels_table(path):
 def read_label_classes_table(path):
     """the rows of cap_label_classes.tsv as dicts of strings"""
     return _sweep.read_cells_table(path, LABEL_CLASSES_COLUMNS)
+
+
+def read_markers_table(path):
+    """the rows of cap_markers.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, MARKERS_COLUMNS)
 
 
 def read_reps_table(path):

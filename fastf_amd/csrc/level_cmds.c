@@ -188,6 +188,7 @@ static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
         if (fastf_res_point_neighbors(S, name, T)) goto done;
         if (fastf_res_point_labels(S, name, T)) goto done;
+        if (fastf_res_point_markers(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
@@ -247,7 +248,7 @@ static int level_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels; S.markers = Fd->markers;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("level", bam_file, &LL.L[0], device, &R)) goto done;
@@ -280,6 +281,7 @@ static int level_resident(const char *bam_file, const char *out_dir, const char 
                                T.cells_dev, T.cells_dev / (n_c * n_m * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[level] --fidelity: the full rows kept from %u first passes, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
     if (prof && Fd->gene_on) fprintf(stderr, "[level] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+    if (prof && Fd->mk_on) fprintf(stderr, "[level] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", Fd->markers, T.markers);
     if (prof && Fd->lab_on) fprintf(stderr, "[level] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
                                     (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
     if (prof && Fd->nbr_on) fprintf(stderr, "[level] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
@@ -296,7 +298,7 @@ done:
 /* ------------------------------------------------------------------ */
 /* reps != 0: a replicate run (fastf_level_reps) — the suffixed directories and the replicate tables, with one seed too */
 static int level_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const uint64_t *caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels)
+                     const uint64_t *caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels, uint32_t markers)
 {
     if (!bam || !barcodes || !features) return lv_err("level: null argument");
     if (!out_dir) out_dir = ".";
@@ -324,6 +326,7 @@ static int level_run_(const char *bam, const char *out_dir, const char *barcodes
     if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "level", out_dir, fastf_level_fidelity_header(), fastf_level_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     if (fastf_res_fid_open_neighbors(&Fd, neighbors, "level", out_dir, fastf_level_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     if (fastf_res_fid_open_labels(&Fd, labels, "level", out_dir, fastf_level_labels_header(), fastf_level_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
+    if (fastf_res_fid_open_markers(&Fd, markers, "level", out_dir, fastf_level_markers_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "level", out_dir, seeds, n_s, n_c, n_m, genes, dev0, fastf_level_reps_header(), fastf_level_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
@@ -354,14 +357,14 @@ static int level_run_(const char *bam, const char *out_dir, const char *barcodes
 
 /* labels_path != NULL: the labels file is read and checked before anything is written */
 static int level_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                   const uint64_t *caps, uint32_t n_l, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path)
+                   const uint64_t *caps, uint32_t n_l, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path, uint32_t markers)
 {
-    if (!labels_path) return level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, NULL);
+    if (!labels_path) return level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, NULL, 0);
     if (!bam || !barcodes || !features) return lv_err("level: null argument");
     if (access(bam, R_OK) == -1) return lv_err("bam file: %s does not exist.", bam);
     fastf_labels_t *labels = NULL;
     if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
-    const int rc = level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, labels);
+    const int rc = level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, labels, markers);
     fastf_labels_free(labels);
     return rc;
 }
@@ -369,22 +372,34 @@ static int level_run(const char *bam, const char *out_dir, const char *barcodes,
 int fastf_level_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
 {
-    if (!n_seeds) return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, labels_path);
+    if (!n_seeds) return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, labels_path, 0);
     if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, labels_path);
+    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, labels_path, 0);
+}
+
+/* --markers N: the labels run with the marker tables beside it */
+int fastf_level_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers)
+{
+    if (markers < 1 || markers > FASTF_MARKERS_MAX) return lv_err("level: --markers: N = %u, from 1 to %u", markers, FASTF_MARKERS_MAX);
+    if (!labels_path) return lv_err("level: --markers needs --labels");
+    if (!n_seeds) return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, labels_path, markers);
+    if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
+    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, labels_path, markers);
 }
 
 int fastf_level(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const uint64_t *umi_caps, uint32_t n_m, uint32_t seed, uint32_t flags)
 {
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, NULL);
+    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, NULL, 0);
 }
 
 int fastf_level_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
     if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, NULL);
+    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, NULL, 0);
 }
 
 static void usage_level(FILE *f)
@@ -419,6 +434,9 @@ static void usage_level(FILE *f)
             "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): level_labels.tsv,\n"
             "                          level_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
             "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point\n"
+            "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
+            "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
+            "                          level_markers.tsv and markers.tsv.gz per point\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_m<M>_s<seed>/, one level.tsv row each, and level_reps.tsv with mean, sd, min and\n"
             "                          max of every metric per grid point (with --genes level_genes_reps.tsv and level_gene_reps.tsv.gz\n"
@@ -443,7 +461,8 @@ int cmd_level(int argc, const char **argv)
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = (A.summary_only ? FASTF_LEVEL_SUMMARY_ONLY : 0) | (A.genes ? FASTF_LEVEL_GENES : 0) | (A.per_cell ? FASTF_LEVEL_CELLS : 0) | (A.fidelity ? FASTF_LEVEL_FIDELITY : 0) |
                            (A.gene_fidelity ? FASTF_LEVEL_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_LEVEL_NEIGHBORS : 0);
-    if (A.labels ? fastf_level_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
+    if (A.markers ? fastf_level_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
+        A.labels ? fastf_level_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_level_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags)
                   : fastf_level(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m level failed: %s\n", fastf_last_error());
@@ -456,6 +475,7 @@ int cmd_level(int argc, const char **argv)
     if (A.gene_fidelity) printf("level_gene_fidelity.tsv is generated.\n");
     if (A.neighbors) printf("level_neighbors.tsv is generated.\n");
     if (A.labels) printf("level_labels.tsv and level_label_classes.tsv are generated.\n");
+    if (A.markers) printf("level_markers.tsv is generated.\n");
     if (A.n_seeds) printf("level_reps.tsv is generated.\n");
     printf("level.tsv is generated.\n");
     return 0;

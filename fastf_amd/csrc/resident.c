@@ -162,6 +162,9 @@ void fastf_res_rate_close(res_rate_t *S)
     if (S->h_nbr) fastf_pinned_free(S->h_nbr);
     fastf_devmem_free(S->d_lab);
     if (S->h_lab) fastf_pinned_free(S->h_lab);
+    fastf_devmem_free(S->d_mk);
+    if (S->h_mk) fastf_pinned_free(S->h_mk);
+    free(S->mk_rank);
     memset(S, 0, sizeof *S);
 }
 
@@ -190,7 +193,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors, lb = S->labels; const fastf_labels_t *const lt = S->lab_t; fastf_res_rate_close(S); S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; S->labels = lb; S->lab_t = lt; }
+    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors, lb = S->labels; const uint32_t mk = S->markers; const fastf_labels_t *const lt = S->lab_t; fastf_res_rate_close(S); S->markers = mk; S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; S->labels = lb; S->lab_t = lt; }
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -298,6 +301,20 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         const double tl = fastf_res_now();
         if (fastf_labels_assign(S->lab_t, L->barcode, n_cells, S->h_lab) || (n_cells && fastf_devmem_copy(S->d_lab, S->h_lab, n_cells))) return RES_FAIL;
         T->labels += fastf_res_now() - tl;
+    }
+    if (S->markers) {                                       /* the four tables of one row set on the device, of both row sets pinned, and the two rank tables */
+        S->mk_set = (res_mk_bytes(S->n_labels, FASTF_HVG_TOP) + 7) & ~(size_t)7;
+        const size_t rank_bytes = 2 * (size_t)S->n_labels * FASTF_HVG_TOP * sizeof *S->mk_rank;
+        if (dev_room(&S->d_mk, &S->have.mk, S->mk_set, device) || pin_room((void **)&S->h_mk, &S->have.h_mk, 2 * S->mk_set)) {
+            rs_err("%s: the marker tables of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, S->mk_set, fastf_last_error());
+            return RES_FAIL;
+        }
+        if (S->have.mk_rank < rank_bytes) {
+            free(S->mk_rank);
+            S->have.mk_rank = 0;
+            if (!(S->mk_rank = (uint32_t *)malloc(rank_bytes ? rank_bytes : 1))) { rs_err("%s: out of memory", verb); return RES_FAIL; }
+            S->have.mk_rank = rank_bytes;
+        }
     }
     if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
         const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
@@ -571,6 +588,30 @@ int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T
     return 0;
 }
 
+/* --markers: one kernel call on the planes at hand (S->nbr_planes of them: the full rows', point == 0, or the point's), the four tables
+ * to the host in one copy, then the ranks */
+static int mk_tables(res_rate_t *S, int point)
+{
+    const size_t W = res_mk_words(S);
+    uint64_t *const d_s2u = (uint64_t *)S->d_mk, *const d_sum = d_s2u + W;
+    uint32_t *const d_det = (uint32_t *)(d_sum + W), *const d_npl = d_det + W;
+    if (fastf_dev_marker_auc(S->e, S->d_nplanes, S->nbr_planes, S->n_cells, S->hvg_k, (const uint8_t *)S->d_lab, S->n_labels, d_s2u, d_det, d_sum, d_npl, NULL) ||
+        fastf_devmem_sync())
+        return rs_err("%s: --markers at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+    if (fastf_devmem_copy(S->h_mk + (size_t)point * S->mk_set, S->d_mk, res_mk_bytes(S->n_labels, S->hvg_k))) return 1;
+    return fastf_marker_rank(res_mk_s2u(S, point), res_mk_npl(S, point), S->h_ngenes, S->hvg_k, S->n_labels, S->mk_rank + (size_t)point * S->n_labels * FASTF_HVG_TOP);
+}
+
+int fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->markers) return 0;
+    (void)point_name;
+    const double tt = fastf_res_now();
+    if (mk_tables(S, 1)) return 1;
+    T->markers += fastf_res_now() - tt;
+    return 0;
+}
+
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
     if (!S->fidelity && !S->gene_fid && !S->neighbors) return 0;
@@ -609,6 +650,10 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
     if (S->labels) {                                        /* the votes of the full sets, which stay for every point of the pair */
         if (lab_votes(S, 0)) return 1;
         T->labels += fastf_res_now() - tt; tt = fastf_res_now();
+    }
+    if (S->markers) {                                       /* the tables and ranks of the full rows, while their planes are still in the plane buffer */
+        if (mk_tables(S, 0)) return 1;
+        T->markers += fastf_res_now() - tt; tt = fastf_res_now();
     }
     if (!S->fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
@@ -955,6 +1000,59 @@ int fastf_res_fid_open_labels(res_fid_t *F, const fastf_labels_t *labels, const 
     return 0;
 }
 
+int fastf_res_fid_open_markers(res_fid_t *F, uint32_t markers, const char *verb, const char *out_dir, const char *header)
+{
+    if (!markers) return 0;
+    char name[64];
+    F->verb = verb;
+    snprintf(name, sizeof name, "%s_markers.tsv", verb);
+    if (fastf_res_tsv_open(&F->mtsv, out_dir, name, header)) return 1;
+    F->mk_on = 1; F->markers = markers;
+    return 0;
+}
+
+/* --markers: the rows of the point and — dir != NULL — its markers.tsv.gz: per label the genes in the top N_eff of the full rows or of
+ * the point, in the order of their full ranks */
+static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    const uint32_t L = S->n_labels, K = S->hvg_k, top = F->markers < K ? F->markers : K;
+    const uint32_t *const npl = res_mk_npl(S, 0), *const rf = res_mk_rank(S, 0), *const rp = res_mk_rank(S, 1);
+    const uint32_t *const df = res_mk_det(S, 0), *const dp = res_mk_det(S, 1);
+    const size_t rows_cap = ((size_t)L + 1) * (FASTF_LABEL_BYTES + 160);
+    char *const rows = (char *)malloc(rows_cap);
+    const char **const names = (const char **)malloc(((size_t)L + 1) * sizeof *names);
+    uint32_t *const by_rank = (uint32_t *)malloc(((size_t)K + 1) * sizeof *by_rank), *const det_all = (uint32_t *)calloc(2 * (size_t)K + 1, sizeof *det_all);
+    int bad = !rows || !names || !by_rank || !det_all;
+    if (bad) rs_err("out of memory");
+    for (uint32_t l = 0; l <= L && !bad; l++) names[l] = fastf_labels_name(F->labels, l);
+    if (!bad) bad = fastf_markers_summary_rows(S->rate_cell, rate_depth, list_value, S->seed, names, L, K, F->markers, npl, rf, rp, res_mk_s2u(S, 0), res_mk_s2u(S, 1), rows, rows_cap);
+    if (dir && !bad) {
+        char path[4200], line[512];
+        gtext t = { NULL, 0, 0 };
+        uint64_t n_lab = 0;
+        for (uint32_t a = 0; a < L; a++) { n_lab += npl[a]; for (uint32_t g = 0; g < K; g++) { det_all[g] += df[(size_t)a * K + g]; det_all[K + g] += dp[(size_t)a * K + g]; } }
+        bad = gt_str(&t, fastf_markers_header());
+        for (uint32_t a = 0; a < L && !bad; a++) {
+            const size_t at = (size_t)a * K;
+            const uint32_t n_in = npl[a], n_out = (uint32_t)(n_lab - n_in);
+            if (!n_in || !n_out) { bad = fastf_markers_row(names[a + 1], NULL, n_in, n_out, 0, 0, 0, 0, 0, 0, 0, 0, 0, line, sizeof line) || gt_str(&t, line); continue; }
+            for (uint32_t g = 0; g < K; g++) by_rank[rf[at + g] - 1] = g;
+            for (uint32_t r = 0; r < K && !bad; r++) {
+                const uint32_t g = by_rank[r];
+                if (r >= top && rp[at + g] > top) continue;
+                bad = fastf_markers_row(names[a + 1], S->L->feat_id[S->h_ngenes[g]], n_in, n_out, rf[at + g], rp[at + g], res_mk_s2u(S, 0)[at + g], res_mk_s2u(S, 1)[at + g],
+                                        df[at + g], det_all[g] - df[at + g], dp[at + g], det_all[K + g] - dp[at + g], res_mk_sum(S, 1)[at + g], line, sizeof line) || gt_str(&t, line);
+            }
+        }
+        snprintf(path, sizeof path, "%s/markers.tsv.gz", dir);
+        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
+        free(t.p);
+    }
+    if (!bad) fputs(rows, F->mtsv.f);
+    free(rows); free(names); free(by_rank); free(det_all);
+    return bad;
+}
+
 /* --labels: the rows of the point and — dir != NULL — its labels.tsv.gz and label_confusion.tsv.gz */
 static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
@@ -1030,6 +1128,11 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
         if (lab_point(F, S, dir, rate_depth, list_value)) return 1;
         T->labels += fastf_res_now() - tt;
     }
+    if (F->mk_on) {
+        const double tt = fastf_res_now();
+        if (mk_point(F, S, dir, rate_depth, list_value)) return 1;
+        T->markers += fastf_res_now() - tt;
+    }
     if (F->gene_on) {
         const double tt = fastf_res_now();
         if (gene_fid_point(F, S, dir, rate_depth, list_value)) return 1;
@@ -1059,16 +1162,16 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
 
 int fastf_res_fid_close(res_fid_t *F, int ok)
 {
-    if (!F->on && !F->gene_on && !F->nbr_on && !F->lab_on) return 0;
+    if (!F->on && !F->gene_on && !F->nbr_on && !F->lab_on && !F->mk_on) return 0;
     /* the tables are closed before any is renamed, and a rename that fails takes the others back: none is left alone */
-    res_tsv_t *const t[5] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL, F->lab_on ? &F->ltsv : NULL,
-                             F->lab_on && F->labels ? &F->ctsv : NULL};
+    res_tsv_t *const t[6] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL, F->lab_on ? &F->ltsv : NULL,
+                             F->lab_on && F->labels ? &F->ctsv : NULL, F->mk_on ? &F->mtsv : NULL};
     int bad = 0, renamed = 0;
     const char *failed = NULL;
-    for (int k = 0; k < 5; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
-    for (int k = 0; k < 5 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
-    if (!ok || bad) for (int k = 0; k < 5; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
-    F->on = F->gene_on = F->nbr_on = F->lab_on = F->full = 0; F->labels = NULL;
+    for (int k = 0; k < 6; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
+    for (int k = 0; k < 6 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
+    if (!ok || bad) for (int k = 0; k < 6; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
+    F->on = F->gene_on = F->nbr_on = F->lab_on = F->mk_on = F->full = 0; F->labels = NULL; F->markers = 0;
     return ok && bad ? rs_err("cannot write %s", failed) : 0;
 }
 
@@ -1359,8 +1462,8 @@ int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_gr
 
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
 {
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv", "labels.tsv", "label_classes.tsv"};
-    for (int k = 0; k < 10; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
+    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv", "labels.tsv", "label_classes.tsv", "markers.tsv"};
+    for (int k = 0; k < 11; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
 }
 
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
@@ -1376,11 +1479,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'L', "labels", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
-    const char *seeds_text = NULL, *reps_text = NULL;
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+    const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->labels = NULL;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->labels = NULL; out->markers = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1394,7 +1497,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNLER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNLMER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1426,9 +1529,21 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'Q': out->gene_fidelity = 1; break;
         case 'N': out->neighbors = 1; break;
         case 'L': out->labels = val; break;
+        case 'M': markers_text = val; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
         }
+    }
+    if (markers_text) {                                     /* (refused here: before the verb makes its output directory) */
+        char *end = NULL;
+        errno = 0;
+        const long n = strtol(markers_text, &end, 10);
+        if (errno == ERANGE || end == markers_text || *end || n < 1 || n > (long)FASTF_MARKERS_MAX) {
+            fprintf(stderr, "error: option `--markers` expects an integer from 1 to %u\n", FASTF_MARKERS_MAX);
+            return 1;
+        }
+        if (!out->labels) { fprintf(stderr, "error: option `--markers` needs `--labels`\n"); return 1; }
+        out->markers = (uint32_t)n;
     }
     /* replicates: --seeds lists them, --reps counts them up from -s */
     if (seeds_text && reps_text) { fprintf(stderr, "error: option `--seeds` cannot be combined with `--reps`\n"); return 1; }

@@ -13,7 +13,9 @@
  * --neighbors compares the k-nearest-neighbour sets of the cells over the pair's highly variable genes (fastf_res_point_neighbors, behind
  * the two above and before fastf_res_point_cells); alone it switches on the full-depth rows and the pair's per-gene sums that rank the genes.
  * --labels turns those neighbour sets into label votes (fastf_res_point_labels, directly behind fastf_res_point_neighbors); alone it
- * switches on everything --neighbors needs on the device and writes none of its files. */
+ * switches on everything --neighbors needs on the device and writes none of its files.
+ * --markers N (with --labels) ranks the genes of A per label by the exact AUC of the label against the other labelled cells, from the
+ * byte planes the neighbour sets were made of (fastf_res_point_markers, directly behind fastf_res_point_labels). */
 #ifndef FASTF_RESIDENT_H
 #define FASTF_RESIDENT_H
 
@@ -34,7 +36,7 @@ enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys w
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
 enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_LEVEL = 192, SM_FULL = 224, SM_WORDS_ = 256 };   /* SM_UROWS: --cells, K3u's row count; SM_LEVEL: level, the result block of a step (FASTF_LEVEL_OUT_WORDS); SM_FULL: --fidelity, the row count of the pair's full rows (no point clears it) */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors, labels; uint32_t opens, relays, passes; } res_times_t;   /* labels: --labels alone — the label arrays of every pair, the vote calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors, labels, markers; uint32_t opens, relays, passes; } res_times_t;   /* markers: --markers alone — the kernel calls on the planes, their D2H, the ranks, rows and files; labels: --labels alone — the label arrays of every pair, the vote calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
@@ -102,8 +104,12 @@ typedef struct {
      * lab (u8, lab_cells entries: a multiple of 4), pred, same and labelled of the full rows, conf_X (u32, n_labels x (n_labels + 1)),
      * then pred, same and labelled of the point and conf_Y — each half leaves in one copy; h_lab: its pinned copy, the same layout */
     int labels; const fastf_labels_t *lab_t; void *d_lab; uint8_t *h_lab; size_t lab_cells; uint32_t n_labels;
+    /* --markers (markers = N set by the caller before the first open, with labels): d_mk: the four tables of ONE row set — s2u, sum (u64),
+     * det (u32), n_labels x hvg_k each, then n_per_label (u32) — which leave in one copy; h_mk: the pinned copies of the full rows' set
+     * and of the point's, mk_set bytes apart; mk_rank: the ranks of the full rows and of the point (u32, n_labels x hvg_k each, host) */
+    uint32_t markers; void *d_mk; uint8_t *h_mk; size_t mk_set; uint32_t *mk_rank;
     uint32_t max_cells; int no_reuse;    /* set by the caller before the first open: the most cells any pair of the run samples (0: unknown); FASTF_RES_NO_REUSE */
-    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level, full, fid, h_fid, gx, gfid, h_gfid, nbr, h_nbr, nplanes, lab, h_lab; } have;
+    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level, full, fid, h_fid, gx, gfid, h_gfid, nbr, h_nbr, nplanes, lab, h_lab, mk, h_mk, mk_rank; } have;
 } res_rate_t;
 #define RES_CELLS_HIST_BYTES 512u
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
@@ -165,6 +171,18 @@ static inline const uint8_t *res_lab_pred(const res_rate_t *S, int point) { retu
 static inline const uint8_t *res_lab_same(const res_rate_t *S, int point) { return S->h_lab + res_lab_off(S, point) + S->lab_cells; }
 static inline const uint8_t *res_lab_labelled(const res_rate_t *S, int point) { return S->h_lab + res_lab_off(S, point) + 2 * S->lab_cells; }
 static inline const uint32_t *res_lab_conf(const res_rate_t *S, int point) { return (const uint32_t *)(S->h_lab + res_lab_off(S, point) + 3 * S->lab_cells); }
+/* --markers (S->markers).  fastf_res_full_keep runs fastf_dev_marker_auc once per pair on the planes of the full rows, before the first
+ * point overwrites the plane buffer, brings the four tables to the host and ranks them (the full ranks stay for every point of the
+ * pair).  fastf_res_point_markers: directly behind fastf_res_point_labels — the same on the point's planes (with the point's own P).
+ * A row set with three planes fails the pair by name (FASTF_ERR_MARKER_COUNT).  Nothing without S->markers.  The tables of S: */
+int  fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
+static inline size_t res_mk_words(const res_rate_t *S) { return (size_t)S->n_labels * S->hvg_k; }
+static inline size_t res_mk_bytes(uint32_t n_labels, uint32_t K) { return (size_t)n_labels * K * 20 + (((size_t)n_labels + 1) & ~(size_t)1) * 4; }
+static inline const uint64_t *res_mk_s2u(const res_rate_t *S, int point) { return (const uint64_t *)(S->h_mk + (size_t)point * S->mk_set); }
+static inline const uint64_t *res_mk_sum(const res_rate_t *S, int point) { return res_mk_s2u(S, point) + res_mk_words(S); }
+static inline const uint32_t *res_mk_det(const res_rate_t *S, int point) { return (const uint32_t *)(res_mk_s2u(S, point) + 2 * res_mk_words(S)); }
+static inline const uint32_t *res_mk_npl(const res_rate_t *S, int point) { return res_mk_det(S, point) + res_mk_words(S); }
+static inline const uint32_t *res_mk_rank(const res_rate_t *S, int point) { return S->mk_rank + (size_t)point * S->n_labels * FASTF_HVG_TOP; }
 
 /* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
  * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
@@ -208,7 +226,7 @@ int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
  * --gene-fidelity: <out_dir>/<verb>_gene_fidelity.tsv and <point dir>/gene_fidelity.tsv.gz likewise.  full: either is on — the pair's
  * full rows are needed.  on == 0 and gene_on == 0: every call does nothing.  fastf_res_fid_close closes both tables before it renames
  * either, and where a rename fails neither table is left */
-typedef struct { int on, gene_on, nbr_on, lab_on, full; const char *verb; res_tsv_t tsv, gtsv, ntsv, ltsv, ctsv; const fastf_labels_t *labels; } res_fid_t;
+typedef struct { int on, gene_on, nbr_on, lab_on, mk_on, full; const char *verb; res_tsv_t tsv, gtsv, ntsv, ltsv, ctsv, mtsv; const fastf_labels_t *labels; uint32_t markers; } res_fid_t;
 int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, const char *out_dir, const char *header, const char *gene_header) FASTF_HIDDEN;
 /* --neighbors: <out_dir>/<verb>_neighbors.tsv and <point dir>/neighbors.tsv.gz likewise; called behind fastf_res_fid_open (which clears F).
  * On failure the caller closes F with ok == 0 */
@@ -216,6 +234,9 @@ int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const c
 /* --labels (labels != NULL): the fourth table set — <out_dir>/<verb>_labels.tsv, <out_dir>/<verb>_label_classes.tsv, and per point
  * labels.tsv.gz and label_confusion.tsv.gz; called behind the two opens above.  On failure the caller closes F with ok == 0 */
 int fastf_res_fid_open_labels(res_fid_t *F, const fastf_labels_t *labels, const char *verb, const char *out_dir, const char *header, const char *classes_header) FASTF_HIDDEN;
+/* --markers N (markers != 0; behind fastf_res_fid_open_labels, which it needs): the fifth table set — <out_dir>/<verb>_markers.tsv and per
+ * point markers.tsv.gz.  On failure the caller closes F with ok == 0 */
+int fastf_res_fid_open_markers(res_fid_t *F, uint32_t markers, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
 /* one point, after fastf_res_point_fidelity / fastf_res_point_gene_fidelity: its row (list_value == 0: rate_depth in the second column)
  * into each table that is on and — dir != NULL — dir/fidelity.tsv.gz from the arrays of S (h_ufull, h_upc, h_gfull, h_gpc, h_sxx, h_syy,
  * h_sxy) and the barcodes of its lists, dir/gene_fidelity.tsv.gz from the per-gene arrays of S and the feature ids */
@@ -251,17 +272,17 @@ int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_d
  * renamed; otherwise nothing of them is left */
 int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, const float *rates_depth, const uint64_t *caps) FASTF_HIDDEN;
 int fastf_res_reps_close(res_reps_t *P, int ok) FASTF_HIDDEN;   /* ok == 0 only */
-/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,fidelity,gene_fidelity,neighbors,labels,label_classes,reps,genes_reps}.tsv and
+/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,fidelity,gene_fidelity,neighbors,labels,label_classes,markers,reps,genes_reps}.tsv and
  * <verb>_gene_reps.tsv.gz is left */
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_HIDDEN;
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --labels --seeds --reps and ONE list option of the verb's own
+/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --labels --markers --seeds --reps and ONE list option of the verb's own
  * (list_short / list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
  * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors; const char *labels;
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors; const char *labels; uint32_t markers;   /* markers: N of --markers, 0 without */
                  uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;

@@ -821,6 +821,147 @@ int fastf_label_classes_row(float rate_cell, float rate_depth, uint64_t list_val
 }
 
 /* ------------------------------------------------------------------ */
+/* --markers: the host twin, the ranks, the rows                        */
+/* ------------------------------------------------------------------ */
+int fastf_marker_auc(const void *planes, uint32_t n_planes, uint32_t n_cells, uint32_t K, const uint8_t *lab, uint32_t n_labels,
+                     uint64_t *s2u, uint32_t *det, uint64_t *sum, uint32_t *n_per_label)
+{
+    if (n_planes < 1 || n_planes > FASTF_MARKER_MAX_PLANES)
+        return sw_err("fastf_marker_auc: FASTF_ERR_MARKER_COUNT: %u planes — a count of 2^14 or more among the highly variable genes: the rank table of a gene does not fit the LDS", n_planes);
+    if (n_labels < 1 || n_labels > FASTF_LABELS_MAX) return sw_err("fastf_marker_auc: %u labels, from 1 to %u", n_labels, FASTF_LABELS_MAX);
+    if (K > 4096) return sw_err("fastf_marker_auc: %u genes, at most 4096", K);
+    if (!n_per_label || (K && (!s2u || !det || !sum)) || (n_cells && (!lab || (K && !planes)))) return sw_err("null argument");
+    const size_t words = (size_t)n_labels * K;
+    memset(n_per_label, 0, (size_t)n_labels * sizeof *n_per_label);
+    if (words) { memset(s2u, 0, words * sizeof *s2u); memset(det, 0, words * sizeof *det); memset(sum, 0, words * sizeof *sum); }
+    uint32_t n_pad = 0, K_pad = 0, n_lab = 0;
+    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
+    for (uint32_t i = 0; i < n_cells; i++) if (lab[i] - 1u < n_labels) { n_per_label[lab[i] - 1u]++; n_lab++; }
+    if (!n_cells || !K) return 0;
+    const uint32_t bins = n_planes == 1 ? 128u : 16384u;
+    const size_t plane_bytes = (size_t)n_pad * K_pad;
+    const uint8_t *const pl = (const uint8_t *)planes;
+    uint32_t *const E = (uint32_t *)malloc(((size_t)bins + n_cells) * sizeof *E), *const x = E ? E + bins : NULL;
+    if (!E) return sw_err("out of memory");
+    for (uint32_t g = 0; g < K; g++) {
+        memset(E, 0, bins * sizeof *E);
+        for (uint32_t i = 0; i < n_cells; i++) {
+            uint32_t v = pl[(size_t)i * K_pad + g] & 127u;
+            if (n_planes == 2) v |= (uint32_t)(pl[plane_bytes + (size_t)i * K_pad + g] & 127u) << 7;
+            x[i] = v;
+            if (lab[i] - 1u < n_labels) E[v]++;
+        }
+        uint32_t c = 0;
+        for (uint32_t v = 0; v < bins; v++) { const uint32_t e = E[v]; E[v] = 2u * c + e; c += e; }     /* 2 C(v) + E(v) */
+        for (uint32_t i = 0; i < n_cells; i++) {
+            const uint32_t a = lab[i] - 1u;
+            if (a >= n_labels) continue;
+            const size_t at = (size_t)a * K + g;
+            s2u[at] += E[x[i]];
+            if (x[i]) { det[at]++; sum[at] += x[i]; }
+        }
+        for (uint32_t a = 0; a < n_labels; a++) s2u[(size_t)a * K + g] -= (uint64_t)n_per_label[a] * n_per_label[a];
+    }
+    (void)n_lab;
+    free(E);
+    return 0;
+}
+
+typedef struct { uint64_t s2u; uint32_t gene, slot; } mk_key;
+static int cmp_mk_key(const void *a, const void *b)
+{
+    const mk_key *x = (const mk_key *)a, *y = (const mk_key *)b;
+    if (x->s2u != y->s2u) return x->s2u > y->s2u ? -1 : 1;
+    return x->gene < y->gene ? -1 : x->gene > y->gene;
+}
+
+int fastf_marker_rank(const uint64_t *s2u, const uint32_t *n_per_label, const uint32_t *genes, uint32_t K, uint32_t n_labels, uint32_t *rank)
+{
+    if (n_labels > FASTF_LABELS_MAX) return sw_err("fastf_marker_rank: %u labels, at most %u", n_labels, FASTF_LABELS_MAX);
+    if ((n_labels && !n_per_label) || (n_labels && K && (!s2u || !rank))) return sw_err("null argument");
+    if (!n_labels || !K) return 0;
+    uint64_t n_lab = 0;
+    for (uint32_t a = 0; a < n_labels; a++) n_lab += n_per_label[a];
+    mk_key *const key = (mk_key *)malloc((size_t)K * sizeof *key);
+    if (!key) return sw_err("out of memory");
+    for (uint32_t a = 0; a < n_labels; a++) {
+        uint32_t *const r = rank + (size_t)a * K;
+        if (!n_per_label[a] || n_lab == n_per_label[a]) { memset(r, 0, (size_t)K * sizeof *r); continue; }     /* no ranking */
+        for (uint32_t g = 0; g < K; g++) { key[g].s2u = s2u[(size_t)a * K + g]; key[g].gene = genes ? genes[g] : g; key[g].slot = g; }
+        qsort(key, K, sizeof *key, cmp_mk_key);
+        for (uint32_t k = 0; k < K; k++) r[key[k].slot] = k + 1;
+    }
+    free(key);
+    return 0;
+}
+
+const char *fastf_markers_header(void) { return "label\tgene\trank_full\trank_point\tauc_full\tauc_point\tdet_in_full\tdet_out_full\tdet_in_point\tdet_out_point\tmean_in_point\n"; }
+#define MARKERS_COLUMNS_TAIL "seed\tlabel\tn_in\tn_out\ttop\tkept\tauc_full_mean\tauc_point_mean\n"
+const char *fastf_sweep_markers_header(void) { return "rate_cell\trate_depth\t" MARKERS_COLUMNS_TAIL; }
+const char *fastf_cap_markers_header(void) { return "rate_cell\treads_per_cell\t" MARKERS_COLUMNS_TAIL; }
+const char *fastf_level_markers_header(void) { return "rate_cell\tumi_cap\t" MARKERS_COLUMNS_TAIL; }
+
+int fastf_markers_row(const char *label, const char *gene, uint32_t n_in, uint32_t n_out, uint32_t rank_full, uint32_t rank_point, uint64_t s2u_full,
+                      uint64_t s2u_point, uint32_t det_in_full, uint32_t det_out_full, uint32_t det_in_point, uint32_t det_out_point, uint64_t sum_in_point,
+                      char *buf, size_t cap)
+{
+    if (!label || !buf) return sw_err("null argument");
+    int n;
+    if (!gene || !n_in || !n_out) n = snprintf(buf, cap, "%s\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n", label);
+    else {
+        const double den = 2.0 * (double)n_in * (double)n_out;
+        n = snprintf(buf, cap, "%s\t%s\t%u\t%u\t%.6f\t%.6f\t%u\t%u\t%u\t%u\t%.6f\n", label, gene, rank_full, rank_point, (double)s2u_full / den, (double)s2u_point / den,
+                     det_in_full, det_out_full, det_in_point, det_out_point, (double)sum_in_point / (double)n_in);
+    }
+    return (n < 0 || (size_t)n >= cap) ? sw_err("markers row too long") : 0;
+}
+
+int fastf_markers_summary_rows(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *const *names, uint32_t n_labels, uint32_t K,
+                               uint32_t top_n, const uint32_t *n_per_label, const uint32_t *rank_full, const uint32_t *rank_point, const uint64_t *s2u_full,
+                               const uint64_t *s2u_point, char *buf, size_t cap)
+{
+    if (!buf || (n_labels && (!names || !n_per_label)) || (n_labels && K && (!rank_full || !rank_point || !s2u_full || !s2u_point))) return sw_err("null argument");
+    const uint32_t top = top_n < K ? top_n : K;
+    uint64_t n_lab = 0, all_out = 0, all_top = 0, all_kept = 0;
+    double all_full = 0.0, all_point = 0.0;
+    char second[32], f[2][40];
+    size_t at = 0;
+    lab_second(second, sizeof second, rate_depth, list_value);
+    for (uint32_t a = 0; a < n_labels; a++) n_lab += n_per_label[a];
+    for (uint32_t a = 0; a <= n_labels; a++) {
+        int n;
+        if (a == n_labels) {
+            if (all_top) { snprintf(f[0], sizeof f[0], "%.6f", all_full / (double)all_top); snprintf(f[1], sizeof f[1], "%.6f", all_point / (double)all_top); }
+            else { snprintf(f[0], sizeof f[0], "NA"); snprintf(f[1], sizeof f[1], "NA"); }
+            n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\tall\t%llu\t%llu\t%llu\t%llu\t%s\t%s\n", (double)rate_cell, second, seed, (unsigned long long)n_lab,
+                         (unsigned long long)all_out, (unsigned long long)all_top, (unsigned long long)all_kept, f[0], f[1]);
+        } else {
+            const uint64_t n_in = n_per_label[a], n_out = n_lab - n_in;
+            all_out += n_out;
+            if (!n_in || !n_out || !top)
+                n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\t%s\t%llu\t%llu\t%u\tNA\tNA\tNA\n", (double)rate_cell, second, seed, names[a + 1], (unsigned long long)n_in,
+                             (unsigned long long)n_out, top);
+            else {
+                uint64_t kept = 0, sf = 0, sp = 0;
+                for (uint32_t g = 0; g < K; g++) {
+                    const size_t w = (size_t)a * K + g;
+                    if (rank_full[w] < 1 || rank_full[w] > top) continue;
+                    kept += rank_point[w] >= 1 && rank_point[w] <= top;
+                    sf += s2u_full[w]; sp += s2u_point[w];
+                }
+                const double den = 2.0 * (double)n_in * (double)n_out, mf = (double)sf / den, mp = (double)sp / den;
+                all_top += top; all_kept += kept; all_full += mf; all_point += mp;
+                n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\t%s\t%llu\t%llu\t%u\t%llu\t%.6f\t%.6f\n", (double)rate_cell, second, seed, names[a + 1], (unsigned long long)n_in,
+                             (unsigned long long)n_out, top, (unsigned long long)kept, mf / (double)top, mp / (double)top);
+            }
+        }
+        if (n < 0 || (size_t)n >= cap - at) return sw_err("markers summary rows too long");
+        at += (size_t)n;
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* directories, sweep.tsv                                              */
 /* ------------------------------------------------------------------ */
 static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
@@ -980,6 +1121,7 @@ static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists
         if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
         if (fastf_res_point_neighbors(S, name, T)) goto done;
         if (fastf_res_point_labels(S, name, T)) goto done;
+        if (fastf_res_point_markers(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
             if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
@@ -1035,7 +1177,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
     if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels;
+    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels; S.markers = Fd->markers;
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
@@ -1064,6 +1206,7 @@ static int sweep_resident(const char *bam_file, const char *out_dir, const char 
                                T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
     if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
     if (prof && Fd->gene_on) fprintf(stderr, "[sweep] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+    if (prof && Fd->mk_on) fprintf(stderr, "[sweep] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", Fd->markers, T.markers);
     if (prof && Fd->lab_on) fprintf(stderr, "[sweep] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
                                     (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
     if (prof && Fd->nbr_on) fprintf(stderr, "[sweep] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
@@ -1080,7 +1223,7 @@ done:
 /* ------------------------------------------------------------------ */
 /* reps != 0: a replicate run (fastf_sweep_reps) — the suffixed directories and the replicate tables, with one seed too */
 static int sweep_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels)
+                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels, uint32_t markers)
 {
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (!out_dir) out_dir = ".";
@@ -1110,6 +1253,7 @@ static int sweep_run_(const char *bam, const char *out_dir, const char *barcodes
     if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "sweep", out_dir, fastf_sweep_fidelity_header(), fastf_sweep_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
     if (fastf_res_fid_open_neighbors(&Fd, neighbors, "sweep", out_dir, fastf_sweep_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     if (fastf_res_fid_open_labels(&Fd, labels, "sweep", out_dir, fastf_sweep_labels_header(), fastf_sweep_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
+    if (fastf_res_fid_open_markers(&Fd, markers, "sweep", out_dir, fastf_sweep_markers_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
     res_reps_t P;
     if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
         fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
@@ -1173,14 +1317,14 @@ static int sweep_run_(const char *bam, const char *out_dir, const char *barcodes
 
 /* labels_path != NULL: the labels file is read and checked before anything is written */
 static int sweep_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path)
+                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path, uint32_t markers)
 {
-    if (!labels_path) return sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, NULL);
+    if (!labels_path) return sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, NULL, 0);
     if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
     if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
     fastf_labels_t *labels = NULL;
     if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
-    const int rc = sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, labels);
+    const int rc = sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, labels, markers);
     fastf_labels_free(labels);
     return rc;
 }
@@ -1188,15 +1332,27 @@ static int sweep_run(const char *bam, const char *out_dir, const char *barcodes,
 int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
 {
-    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path);
+    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path, 0);
     if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path);
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path, 0);
+}
+
+/* --markers N: the labels run with the marker tables beside it */
+int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers)
+{
+    if (markers < 1 || markers > FASTF_MARKERS_MAX) return sw_err("sweep: --markers: N = %u, from 1 to %u", markers, FASTF_MARKERS_MAX);
+    if (!labels_path) return sw_err("sweep: --markers needs --labels");
+    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path, markers);
+    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path, markers);
 }
 
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
 {
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, NULL);
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, NULL, 0);
 }
 
 /* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
@@ -1212,7 +1368,7 @@ int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes,
                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
     if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, NULL);
+    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, NULL, 0);
 }
 
 static void usage_sweep(FILE *f)
@@ -1247,6 +1403,9 @@ static void usage_sweep(FILE *f)
             "                          sweep_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
             "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point;\n"
             "                          resident form only\n"
+            "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
+            "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
+            "                          sweep_markers.tsv and markers.tsv.gz per point; resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -1271,7 +1430,8 @@ int cmd_sweep(int argc, const char **argv)
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0) |
                            (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
-    if (A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
+    if (A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
+        A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
@@ -1284,6 +1444,7 @@ int cmd_sweep(int argc, const char **argv)
     if (A.gene_fidelity) printf("sweep_gene_fidelity.tsv is generated.\n");
     if (A.neighbors) printf("sweep_neighbors.tsv is generated.\n");
     if (A.labels) printf("sweep_labels.tsv and sweep_label_classes.tsv are generated.\n");
+    if (A.markers) printf("sweep_markers.tsv is generated.\n");
     if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
     printf("sweep.tsv is generated.\n");
     return 0;

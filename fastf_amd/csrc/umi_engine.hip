@@ -14,6 +14,7 @@
 #include "gene_fidelity_kernels.hpp"
 #include "neighbors_kernels.hpp"
 #include "labels_kernels.hpp"
+#include "markers_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -246,6 +247,7 @@ struct fastf_engine {
     bool gmom_lds_attr = false;          // the same for gene_moments_kernel<true>
     bool nbr_lds_attr = false;           // the same for the six nbr_gram_kernel forms
     bool lab_lds_attr = false;           // the same for the three label_votes_kernel<G, true> forms
+    bool mk_lds_attr = false;            // the same for the four marker_auc_kernel forms
     DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
@@ -1390,6 +1392,72 @@ extern "C" int fastf_dev_label_votes(fastf_engine_t* e, const uint32_t* d_idx, c
     return 0;
 } FASTF_CATCH_INT
 
+static_assert(MK_MAX_LABELS == FASTF_LABELS_MAX && MK_MAX_PLANES == FASTF_MARKER_MAX_PLANES, "the limits of marker_auc_kernel and the ABI's");
+
+// --markers: the accumulator form one call takes for (planes, n_labels): 1 — in LDS beside the bins, 0 — global atomics (what does not
+// fit, and everything under FASTF_MARKERS_LDS=0), -1 — the call is refused
+extern "C" int fastf_marker_auc_form(uint32_t planes, uint32_t n_labels) FASTF_TRY {
+    if (planes < 1 || planes > MK_MAX_PLANES || n_labels < 1 || n_labels > MK_MAX_LABELS) return -1;
+    const char* lf = getenv("FASTF_MARKERS_LDS");
+    return mk_fits_lds(planes, n_labels) && !(lf && lf[0] == '0') ? 1 : 0;
+} FASTF_CATCH_(return -1)
+
+template <u32 P, bool LDS>
+static int marker_auc_launch(hipStream_t s, const unsigned char* planes, const unsigned char* lab, const u32* npl, u32 n_cells, u32 n_pad, u32 K, u32 K_pad,
+                             u32 n_labels, u64* s2u, u32* det, u64* sum) {
+    hipLaunchKernelGGL((marker_auc_kernel<P, LDS>), dim3((K + mk_tile(P) - 1) / mk_tile(P)), dim3(MK_THREADS), (size_t)mk_lds_bytes(P, n_labels, LDS), s,
+                       planes, lab, npl, n_cells, n_pad, K, K_pad, n_labels, s2u, det, sum);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// --markers: per (label, slot of A) 2U, det and sum (marker_auc_kernel) and the cells per label.  d_planes: what fastf_dev_neighbor_planes
+// filled for (n_cells, K) with `planes` planes; d_lab: u8[n_cells].  d_s2u, d_sum: u64[n_labels * K]; d_det: u32[n_labels * K];
+// d_n_per_label: u32[n_labels]; the four are cleared here.  Three planes (a count of 2^14 and beyond in A) and n_labels outside
+// 1 .. FASTF_LABELS_MAX are refused before anything is launched.  FASTF_MARKERS_LDS=0 takes the global-atomic form for every n_labels.
+// Stream-ordered.
+extern "C" int fastf_dev_marker_auc(fastf_engine_t* e, const void* d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, const uint8_t* d_lab,
+                                    uint32_t n_labels, uint64_t* d_s2u, uint32_t* d_det, uint64_t* d_sum, uint32_t* d_n_per_label, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (planes < 1 || planes > MK_MAX_PLANES)
+        return set_err("fastf_dev_marker_auc: FASTF_ERR_MARKER_COUNT: %u planes — a count of 2^14 or more among the highly variable genes: the rank table of a gene does not fit the LDS", planes);
+    if (n_labels < 1 || n_labels > MK_MAX_LABELS) return set_err("fastf_dev_marker_auc: %u labels, from 1 to %u", n_labels, MK_MAX_LABELS);
+    if (K > NBR_MAX_GENES) return set_err("fastf_dev_marker_auc: %u genes, at most %u", K, NBR_MAX_GENES);
+    if (!d_n_per_label || (K && (!d_s2u || !d_det || !d_sum))) return set_err("fastf_dev_marker_auc: null argument");
+    const size_t words = (size_t)n_labels * K;
+    HIP_OK(hipMemsetAsync(d_n_per_label, 0, (size_t)n_labels * sizeof(u32), s));
+    if (words) {
+        HIP_OK(hipMemsetAsync(d_s2u, 0, words * sizeof(u64), s));
+        HIP_OK(hipMemsetAsync(d_det, 0, words * sizeof(u32), s));
+        HIP_OK(hipMemsetAsync(d_sum, 0, words * sizeof(u64), s));
+    }
+    if (!n_cells) return 0;
+    if (!d_lab || (K && !d_planes)) return set_err("fastf_dev_marker_auc: null argument");
+    hipLaunchKernelGGL(marker_labels_kernel, dim3(std::min<u32>((n_cells + 255u) / 256u, (u32)g_cu_count)), dim3(256), 0, s, (const unsigned char*)d_lab, n_cells, n_labels, d_n_per_label);
+    HIP_OK(hipGetLastError());
+    if (!K) return 0;
+    const bool lds_form = fastf_marker_auc_form(planes, n_labels) == 1;
+    if (!e->mk_lds_attr) {                                   // (per engine, on first use: the attribute belongs to the current device's function)
+        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
+        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
+        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
+        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
+        e->mk_lds_attr = true;
+    }
+    uint32_t n_pad = 0, K_pad = 0;
+    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
+    const unsigned char* const pl = (const unsigned char*)d_planes;
+    int rc;
+    if (planes == 1) rc = lds_form ? marker_auc_launch<1, true>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum)
+                                   : marker_auc_launch<1, false>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum);
+    else rc = lds_form ? marker_auc_launch<2, true>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum)
+                       : marker_auc_launch<2, false>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum);
+    if (rc) return 1;
+    dbg_sync(s, "marker auc");
+    return 0;
+} FASTF_CATCH_INT
+
 // Replicate runs: d_cells_per_gene (what fastf_dev_gene_summary left, still on the device) added into the three u64[n_features]
 // accumulators of a grid point (gene_reps_kernel).  Nothing is cleared here: the caller zeroes the accumulators before the first seed.
 extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cells_per_gene, uint32_t n_features, uint64_t* d_detected,
@@ -2022,7 +2090,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel,marker_labels_kernel,marker_auc_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

@@ -470,6 +470,13 @@ class Engine:
         check(self._L.fastf_dev_label_votes(self._h, d_idx or None, d_cnt or None, d_lab or None, n_cells, k, n_labels, d_pred or None, d_same or None,
                                             d_labelled or None, d_conf or None, stream))
 
+    def dev_marker_auc(self, d_planes, planes, n_cells, K, d_lab, n_labels, d_s2u, d_det, d_sum, d_n_per_label, stream=0):
+        """--markers: the byte planes Engine.dev_neighbor_planes left (d_planes, `planes` of them) and d_lab (u8[n_cells]) -> d_s2u, d_sum
+        (u64[n_labels * K]), d_det (u32[n_labels * K]) and d_n_per_label (u32[n_labels]), all cleared by the call; FASTF_MARKERS_LDS=0:
+        the accumulators by global atomics alone; three planes are refused; stream-ordered"""
+        check(self._L.fastf_dev_marker_auc(self._h, d_planes or None, planes, n_cells, K, d_lab or None, n_labels, d_s2u or None, d_det or None,
+                                           d_sum or None, d_n_per_label or None, stream))
+
     def probe_capacity(self, n) -> int:
         """key slots a segmented probe_pack over n records needs; 0 = the streaming form is not available"""
         v = C.c_uint64()

@@ -36,6 +36,7 @@ gene_fidelity_metrics = _sweep.gene_fidelity_metrics
 NEIGHBORS_COLUMNS = _renamed(_cap.NEIGHBORS_COLUMNS)
 LABELS_COLUMNS = _renamed(_cap.LABELS_COLUMNS)
 LABEL_CLASSES_COLUMNS = _renamed(_cap.LABEL_CLASSES_COLUMNS)
+MARKERS_COLUMNS = _renamed(_cap.MARKERS_COLUMNS)
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 THRESHOLDS_COLUMNS = ("barcode", "threshold", "umis_full", "umis")
 parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for the three verbs)
@@ -47,7 +48,7 @@ def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neig
 
 
 def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF level -b bam -a barcodes -f features -o out -c rates_cell -m umi_caps -s seed [--summary-only] [--genes] [--cells]`; returns
     the rows of out/level.tsv as dicts of strings (read_table); genes / cells: the files cap.cap() leaves, under the names level_*; fidelity:
     out/level_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per point directory; gene_fidelity: out/level_gene_fidelity.tsv
@@ -57,6 +58,11 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                                seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                  m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
@@ -68,13 +74,19 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
 
 
 def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
+                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                None if labels is None else enc(labels), _sweep._markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                  m.ctypes.data, len(m), sd.ctypes.data, len(sd),
@@ -149,6 +161,10 @@ def read_labels_table(path):
 
 def read_label_classes_table(path):
     return _sweep.read_cells_table(path, LABEL_CLASSES_COLUMNS)
+
+
+def read_markers_table(path):
+    return _sweep.read_cells_table(path, MARKERS_COLUMNS)
 
 
 def read_reps_table(path):

@@ -17,6 +17,7 @@ HVG_TOP = 2000        # FASTF_HVG_TOP
 NEIGHBORS = 512       # FASTF_SWEEP_NEIGHBORS
 NEIGHBORS_K = 15      # FASTF_NEIGHBORS_K
 LABELS_MAX = 255      # FASTF_LABELS_MAX
+MARKERS_MAX = 2000    # FASTF_MARKERS_MAX
 COPY_BINS = 32        # FASTF_COPY_BINS
 COLUMNS = ("rate_cell", "rate_depth", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell")
@@ -39,6 +40,10 @@ LABELS_COLUMNS = ("rate_cell", "rate_depth") + LABELS_TAIL_COLUMNS
 LABEL_CLASSES_TAIL_COLUMNS = ("seed", "label", "cells", "correct_full", "correct_point", "predicted_full", "predicted_point")
 LABEL_CLASSES_COLUMNS = ("rate_cell", "rate_depth") + LABEL_CLASSES_TAIL_COLUMNS
 POINT_LABELS_COLUMNS = ("barcode", "label", "pred_full", "pred_point", "same_full", "labelled_full", "same_point", "labelled_point")     # <point dir>/labels.tsv.gz
+MARKERS_TAIL_COLUMNS = ("seed", "label", "n_in", "n_out", "top", "kept", "auc_full_mean", "auc_point_mean")
+MARKERS_COLUMNS = ("rate_cell", "rate_depth") + MARKERS_TAIL_COLUMNS
+POINT_MARKERS_COLUMNS = ("label", "gene", "rank_full", "rank_point", "auc_full", "auc_point", "det_in_full", "det_out_full", "det_in_point", "det_out_point",
+                         "mean_in_point")     # <point dir>/markers.tsv.gz
 POINT_CELLS_COLUMNS = ("barcode", "reads", "null_umi_reads", "umis", "genes", "singleton_umis", "saturation")     # <point dir>/cells.tsv.gz
 
 
@@ -52,8 +57,17 @@ def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=
             | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0))
 
 
+def _markers_n(markers) -> int:
+    """N of markers=N as the u32 the C call takes: what is no integer or does not fit goes over as 0, which the call refuses by name"""
+    try:
+        n = int(markers)
+    except (TypeError, ValueError):
+        return 0
+    return n if 0 <= n < (1 << 32) and n == markers else 0
+
+
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
@@ -63,10 +77,17 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     gene_fidelity.tsv.gz per point directory (read_point_gene_fidelity); neighbors=True the comparison between the cells:
     out/sweep_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory (read_point_neighbors); labels=<path>
     (`--labels`: one barcode<TAB>label per line) the label votes of those neighbours: out/sweep_labels.tsv (read_labels_table),
-    out/sweep_label_classes.tsv (read_label_classes_table) and labels.tsv.gz (read_point_labels), label_confusion.tsv.gz per point directory"""
+    out/sweep_label_classes.tsv (read_label_classes_table) and labels.tsv.gz (read_point_labels), label_confusion.tsv.gz per point directory;
+    markers=N (`--markers`, with labels) the N best marker genes per label by exact AUC: out/sweep_markers.tsv (read_markers_table) and a
+    markers.tsv.gz per point directory (read_point_markers)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), seed % (1 << 32),
+                                                  None if labels is None else enc(labels), _markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), seed % (1 << 32), enc(labels)))
@@ -82,7 +103,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -90,6 +111,11 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     rd, prd = _floats(rates_depth)
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if markers is not None:
+        _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                  None if labels is None else enc(labels), _markers_n(markers)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0, enc(labels)))
@@ -415,6 +441,95 @@ def label_classes_row(rate_cell, rate_depth, seed, label, a, n_labels, lab, conf
     buf = C.create_string_buffer(640)
     _lib.check(_lib.lib().fastf_label_classes_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), _b(label), int(a), len(lab),
                                                   int(n_labels), lab.ctypes.data, cf.ctypes.data, cp.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def read_markers_table(path, columns=MARKERS_COLUMNS):
+    """the rows of sweep_markers.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_markers(path):
+    """the rows of a point's markers.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_MARKERS_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_MARKERS_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def markers_header(verb: str = "") -> str:
+    """the header of markers.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_markers.tsv"""
+    return getattr(_lib.lib(), "fastf_%smarkers_header" % (verb + "_" if verb else ""))().decode()
+
+
+def marker_planes(counts, n_planes: int, pad_byte: int = 0):
+    """the byte planes of a dense count array (n_cells x K, values below 128 ** n_planes) in the layout of Engine.dev_neighbor_planes:
+    u8[n_planes, n_pad, K_pad], plane p holds bits 7p .. 7p+6; the padding rows and slots hold pad_byte"""
+    counts = np.asarray(counts, dtype=np.uint64)
+    n, K = counts.shape
+    n_pad, K_pad = neighbors_pad(n, K)
+    pl = np.full((n_planes, n_pad, K_pad), pad_byte, np.uint8)
+    for p in range(n_planes):
+        pl[p, :n, :K] = ((counts >> np.uint64(7 * p)) & np.uint64(127)).astype(np.uint8)
+    return pl
+
+
+def marker_auc(planes, n_planes: int, n_cells: int, K: int, lab, n_labels: int):
+    """(s2u u64[n_labels, K], det u32[n_labels, K], sum u64[n_labels, K], n_per_label u32[n_labels]) of byte planes (marker_planes) and
+    labels lab (u8[n_cells]): the host form of Engine.dev_marker_auc"""
+    planes = np.ascontiguousarray(planes, dtype=np.uint8)
+    lab = np.ascontiguousarray(lab, dtype=np.uint8)
+    n_pad, K_pad = neighbors_pad(n_cells, K)
+    assert len(lab) == n_cells and (n_planes > 3 or planes.size >= n_planes * n_pad * K_pad)
+    words = max(n_labels * K, 1)
+    s2u, det, sm = np.full(words, 0xDEADBEEF, np.uint64), np.full(words, 0xDEADBEEF, np.uint32), np.full(words, 0xDEADBEEF, np.uint64)
+    npl = np.full(max(n_labels, 1), 0xDEADBEEF, np.uint32)
+    _lib.check(_lib.lib().fastf_marker_auc(planes.ctypes.data, n_planes, n_cells, K, lab.ctypes.data if n_cells else None, n_labels, s2u.ctypes.data,
+                                           det.ctypes.data, sm.ctypes.data, npl.ctypes.data))
+    W = n_labels * K
+    return s2u[:W].reshape(n_labels, K), det[:W].reshape(n_labels, K), sm[:W].reshape(n_labels, K), npl[:n_labels]
+
+
+def marker_auc_form(n_planes: int, n_labels: int) -> int:
+    """1: a device call keeps its accumulators in LDS, 0: it adds by global atomics (FASTF_MARKERS_LDS=0 included), -1: it is refused"""
+    return int(_lib.lib().fastf_marker_auc_form(n_planes, n_labels))
+
+
+def marker_rank(s2u, n_per_label, genes=None):
+    """rank u32[n_labels, K] (from 1; 0: the label has no ranking) of s2u (u64[n_labels, K]) by descending s2u, ties by ascending
+    genes[slot] (None: by slot)"""
+    s2u = np.ascontiguousarray(s2u, dtype=np.uint64)
+    n_labels, K = s2u.shape
+    npl = np.ascontiguousarray(n_per_label, dtype=np.uint32)
+    assert len(npl) == n_labels
+    g = None if genes is None else np.ascontiguousarray(genes, dtype=np.uint32)
+    assert g is None or len(g) == K
+    rank = np.full(max(n_labels * K, 1), 0xDEADBEEF, np.uint32)
+    _lib.check(_lib.lib().fastf_marker_rank(s2u.ctypes.data, npl.ctypes.data, None if g is None else g.ctypes.data, K, n_labels, rank.ctypes.data))
+    return rank[:n_labels * K].reshape(n_labels, K)
+
+
+def markers_row(label, gene, n_in, n_out, rank_full, rank_point, s2u_full, s2u_point, det_in_full, det_out_full, det_in_point, det_out_point,
+                sum_in_point) -> str:
+    """one row of markers.tsv.gz (with its newline); gene None: the NA row of a label without a ranking"""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_markers_row(_b(label), None if gene is None else _b(gene), int(n_in), int(n_out), int(rank_full), int(rank_point), int(s2u_full),
+                                            int(s2u_point), int(det_in_full), int(det_out_full), int(det_in_point), int(det_out_point), int(sum_in_point),
+                                            buf, len(buf)))
+    return buf.value.decode()
+
+
+def markers_summary_rows(rate_cell, rate_depth, seed, names, top_n, n_per_label, rank_full, rank_point, s2u_full, s2u_point, list_value: int = 0) -> str:
+    """the n_labels + 1 rows of one point of <verb>_markers.tsv; names[0] is "NA" and not read"""
+    npl = np.ascontiguousarray(n_per_label, dtype=np.uint32)
+    rf, rp = (np.ascontiguousarray(x, dtype=np.uint32) for x in (rank_full, rank_point))
+    sf, sp = (np.ascontiguousarray(x, dtype=np.uint64) for x in (s2u_full, s2u_point))
+    L, K = sf.shape
+    assert len(names) == L + 1 and len(npl) == L and rf.shape == rp.shape == sp.shape == (L, K)
+    arr = (C.c_char_p * len(names))(*[_b(x) for x in names])
+    buf = C.create_string_buffer(256 * (L + 1))
+    _lib.check(_lib.lib().fastf_markers_summary_rows(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), arr, L, K, int(top_n),
+                                                     npl.ctypes.data, rf.ctypes.data, rp.ctypes.data, sf.ctypes.data, sp.ctypes.data, buf, len(buf)))
     return buf.value.decode()
 
 

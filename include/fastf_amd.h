@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -479,6 +479,74 @@ int fastf_cap_labels(const char *bam, const char *out_dir, const char *barcodes,
                      const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path);
 int fastf_level_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path);
+
+/* --- --markers N on sweep, cap and level, with --labels (fastf_sweep_markers, fastf_cap_markers, fastf_level_markers; `markers=N` in
+ * Python; the long option alone; no new flag bit): do the marker genes of the cell types survive at this depth.  X, Y, A (K genes, slot
+ * g of A is the gene of rank g of fastf_hvg_rank) and lab[] are those of --neighbors and --labels.  Only labelled sampled cells take
+ * part (lab[i] in 1 .. L): n_lab of them, n_a with label a, n_out = n_lab - n_a.  For a matrix M (X or Y) and a gene g of A, x_i is the
+ * raw count of cell i (0 without a row).  The statistic is the Mann-Whitney U of label a against all other labelled cells, doubled:
+ *   2U_M[a][g] = sum over i in a, j labelled and not in a, of 2 * (x_i > x_j) + (x_i == x_j)
+ * computed per gene from E(v) = #{labelled cells with x == v} and C(v) = #{labelled cells with x < v} as
+ *   2U_M[a][g] = sum over i in a of (2 C(x_i) + E(x_i)) - n_a^2        (the same sum over the pairs inside a is exactly n_a^2)
+ * in integers alone; AUC = 2U / (2 n_a n_out) is formed only where it is printed.  Beside it, per (label, gene):
+ *   det_M[a][g] = #{i in a : x_i > 0} (u32)        sum_M[a][g] = sum over i in a of x_i (u64)
+ * Ranking: for a label with n_a >= 1 and n_out >= 1 the genes of A by descending 2U, ties by ascending feature number; rank 1 is the
+ * best.  Its markers are the first N_eff = min(N, K).  A label with n_a == 0 or n_out == 0 has no ranking (rank 0) and prints NA.
+ * Range: counts of the genes of A below 2^14 (one or two byte planes).  A (cell rate, seed) pair whose full rows need three planes is
+ * refused for this option by name (FASTF_ERR_MARKER_COUNT in the message), as --neighbors refuses 2^21: the rank table of a gene — E,
+ * then 2C + E, one u32 per possible count — lives in the LDS of the device, 64 KB a gene at 2^14 counts.
+ *   <point dir>/markers.tsv.gz (not with --summary-only): a header and, per label in id order, one row per gene in the union of the
+ *     label's markers at full depth and at the point, by ascending rank_full:
+ *     label gene rank_full rank_point auc_full auc_point det_in_full det_out_full det_in_point det_out_point mean_in_point
+ *     gene: the feature id; auc_M = 2U_M / (2 n_a n_out) (%.6f); det_in_M = det_M[a][g], det_out_M = sum over b != a of det_M[b][g];
+ *     mean_in_point = sum_Y[a][g] / n_a (%.6f).  A label without a ranking has one row, NA in every column behind the label.
+ *   <out_dir>/<verb>_markers.tsv: a header and per point — in replicate runs per (cell rate, seed, list value), in the row order of
+ *     <verb>_labels.tsv — one row per label in id order and one row `all`, through .partial, with --summary-only too: the verb's two
+ *     leading columns, then   seed label n_in n_out top kept auc_full_mean auc_point_mean
+ *     n_in = n_a, n_out as above, top = N_eff, kept = the genes in the label's markers at full depth AND at the point,
+ *     auc_M_mean = the mean of auc_M over the label's markers AT FULL DEPTH: (sum of 2U_M over them) / (2 n_a n_out) / N_eff (%.6f);
+ *     a label without a ranking prints NA in the last three.  The `all` row: n_in, n_out, top and kept summed over the labels (top and
+ *     kept over those with a ranking), the two means pooled over every (label, marker) pair of those labels, NA when there is none.
+ * The option needs --labels (refused without it, and for N outside 1 .. FASTF_MARKERS_MAX, before the output directory is made) and
+ * switches on what --labels switches on; every other output is the bytes it is without the option.  No _reps aggregate is written. --- */
+#define FASTF_MARKERS_MAX 2000u              /* N of --markers: 1 .. FASTF_HVG_TOP */
+#define FASTF_MARKER_MAX_PLANES 2u
+/* the host twin of fastf_dev_marker_auc: the same arguments on host arrays.  planes: n_planes byte planes of n_pad x K_pad
+ * (fastf_neighbors_pad), plane p holds bits 7p .. 7p+6 of the count of (cell, slot); rows from n_cells on, slots from K on and bit 7 of
+ * a byte are never used.  s2u, sum (u64) and det (u32): n_labels x K, [a - 1][slot]; n_per_label (u32, n_labels): the cells per label.
+ * The call clears all four.  Refused: n_planes outside 1 .. 2 (FASTF_ERR_MARKER_COUNT), n_labels outside 1 .. FASTF_LABELS_MAX */
+int fastf_marker_auc(const void *planes, uint32_t n_planes, uint32_t n_cells, uint32_t K, const uint8_t *lab, uint32_t n_labels,
+                     uint64_t *s2u, uint32_t *det, uint64_t *sum, uint32_t *n_per_label);
+/* which accumulator form one device call takes: 1 — in LDS beside the bins, 0 — global atomics (n_labels that do not fit: 226 and
+ * more at one plane, none at two; and every call under FASTF_MARKERS_LDS=0), -1 — a call with these arguments is refused */
+int fastf_marker_auc_form(uint32_t n_planes, uint32_t n_labels);
+/* rank[(a - 1) * K + slot] (u32) = the rank, from 1, of the slot among the K slots of label a by descending s2u, ties by ascending
+ * genes[slot] (genes == NULL: by ascending slot); 0 in every slot of a label with n_a == 0 or n_out == 0 */
+int fastf_marker_rank(const uint64_t *s2u, const uint32_t *n_per_label, const uint32_t *genes, uint32_t K, uint32_t n_labels, uint32_t *rank);
+const char *fastf_markers_header(void);            /* the header of markers.tsv.gz */
+const char *fastf_sweep_markers_header(void);      /* the headers of <verb>_markers.tsv */
+const char *fastf_cap_markers_header(void);
+const char *fastf_level_markers_header(void);
+/* one row of markers.tsv.gz (with its newline); gene == NULL, n_in == 0 or n_out == 0: the NA row of a label without a ranking */
+int fastf_markers_row(const char *label, const char *gene, uint32_t n_in, uint32_t n_out, uint32_t rank_full, uint32_t rank_point, uint64_t s2u_full,
+                      uint64_t s2u_point, uint32_t det_in_full, uint32_t det_out_full, uint32_t det_in_point, uint32_t det_out_point, uint64_t sum_in_point,
+                      char *buf, size_t cap);
+/* the n_labels + 1 rows of one point of <verb>_markers.tsv (with their newlines) into buf; names[1 .. n_labels] the labels (names[0] is
+ * not read); top_n: N; the tables [a - 1][slot] over K slots; the second column as fastf_genes_summary_row prints it */
+int fastf_markers_summary_rows(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *const *names, uint32_t n_labels, uint32_t K,
+                               uint32_t top_n, const uint32_t *n_per_label, const uint32_t *rank_full, const uint32_t *rank_point, const uint64_t *s2u_full,
+                               const uint64_t *s2u_point, char *buf, size_t cap);
+/* sweep, cap and level with --labels and --markers: the arguments of the verb's _labels call, then N.  labels_path == NULL and N outside
+ * 1 .. FASTF_MARKERS_MAX are refused */
+int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers);
+int fastf_cap_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                      const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                      uint32_t markers);
+int fastf_level_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -974,6 +1042,16 @@ int fastf_dev_neighbors_shared(fastf_engine_t *e, const uint32_t *d_idx_a, const
  * `stream` */
 int fastf_dev_label_votes(fastf_engine_t *e, const uint32_t *d_idx, const uint32_t *d_cnt, const uint8_t *d_lab, uint32_t n_cells, uint32_t k,
                           uint32_t n_labels, uint8_t *d_pred, uint8_t *d_same, uint8_t *d_labelled, uint32_t *d_conf, void *stream);
+
+/* --markers (section above), one call on device pointers (marker_labels_kernel, marker_auc_kernel).  d_planes: what
+ * fastf_dev_neighbor_planes filled for (n_cells, K) with `planes` planes; d_lab: u8[n_cells].  d_s2u, d_sum: u64[n_labels * K]; d_det:
+ * u32[n_labels * K]; d_n_per_label: u32[n_labels]; the call clears all four.  A workgroup owns a tile of adjacent slots (32 at one plane,
+ * 2 at two) and walks the rows twice: E per slot in LDS, a scan in place to 2C + E, then each non-zero entry's term, detection and count;
+ * the zero counts enter in closed form.  The accumulators of a tile sit in LDS where they fit beside the bins
+ * (fastf_marker_auc_form), else, and always under FASTF_MARKERS_LDS=0, they go by global atomics: the same numbers.  planes == 3
+ * (FASTF_ERR_MARKER_COUNT) and n_labels outside 1 .. FASTF_LABELS_MAX are refused before anything is launched.  Asynchronous on `stream` */
+int fastf_dev_marker_auc(fastf_engine_t *e, const void *d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, const uint8_t *d_lab,
+                         uint32_t n_labels, uint64_t *d_s2u, uint32_t *d_det, uint64_t *d_sum, uint32_t *d_n_per_label, void *stream);
 
 /* Keys wider than 64 bits on a SHARDED engine (n_shards > 1; one process per GPU: fastf_amd/dist.py).  The calls above take
  * 64-bit keys; an engine whose keys are wider (fastf_engine_is_wide: many barcodes x many features x long UMIs, or
