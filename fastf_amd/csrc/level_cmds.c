@@ -18,7 +18,6 @@
 #define _GNU_SOURCE
 #include "resident.h"
 
-#include <errno.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -64,36 +63,12 @@ int fastf_level_point_dir(float rate_cell, uint64_t umi_cap, char *buf, size_t c
     return (n < 0 || (size_t)n >= cap) ? lv_err("directory name too long") : 0;
 }
 
-/* cap's header with its second column named umi_cap (every call writes the same bytes) */
-static const char *renamed_(char *buf, size_t cap, const char *cap_header)
-{
-    static const char from[] = "rate_cell\treads_per_cell\t", to[] = "rate_cell\tumi_cap\t";
-    if (strncmp(cap_header, from, sizeof from - 1)) return cap_header;
-    snprintf(buf, cap, "%s%s", to, cap_header + sizeof from - 1);
-    return buf;
-}
-const char *fastf_level_header(void) { static char b[512]; return renamed_(b, sizeof b, fastf_cap_header()); }
-const char *fastf_level_genes_header(void) { static char b[512]; return renamed_(b, sizeof b, fastf_cap_genes_header()); }
-const char *fastf_level_cells_header(void) { static char b[1024]; return renamed_(b, sizeof b, fastf_cap_cells_header()); }
-const char *fastf_level_reps_header(void) { static char b[2048]; return renamed_(b, sizeof b, fastf_cap_reps_header()); }
-const char *fastf_level_genes_reps_header(void) { static char b[512]; return renamed_(b, sizeof b, fastf_cap_genes_reps_header()); }
-
-/* metrics: fastf_summary_tail_ */
-static int level_row_(float rate_cell, uint64_t umi_cap, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
-                      const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
-                      char *buf, size_t cap, double *metrics)
-{
-    char tail[400];
-    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail, metrics)) return 1;
-    const int n = snprintf(buf, cap, "%.3f\t%llu\t%s\t%llu\t%u\t%.6f\n", (double)rate_cell, (unsigned long long)umi_cap, tail,
-                           (unsigned long long)hits, cells_capped, (double)fastf_cap_realised(counters[1], hits));
-    return (n < 0 || (size_t)n >= cap) ? lv_err("summary row too long") : 0;
-}
+/* level.tsv has cap.tsv's columns, its second named umi_cap (the headers: beside cap's) */
 int fastf_level_summary_row(float rate_cell, uint64_t umi_cap, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                             const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
                             char *buf, size_t cap)
 {
-    return level_row_(rate_cell, umi_cap, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, hits, cells_capped, buf, cap, NULL);
+    return fastf_cap_row_(rate_cell, umi_cap, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, hits, cells_capped, buf, cap, NULL);
 }
 
 /* ------------------------------------------------------------------ */
@@ -119,262 +94,154 @@ static int write_thresholds(const char *dir, const fastf_lists_t *L, uint32_t n_
 }
 
 /* ------------------------------------------------------------------ */
-/* one (cell rate, seed) pair, on the run's res_rate_t               */
+/* the verb (resident.h: res_verb_t; the driver: grid_run.c)           */
 /* ------------------------------------------------------------------ */
 #define LEVEL_MAX_PASSES 32u                             /* hi - lo halves per probing pass, from 2^32 */
-static int level_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
-                           float rate_cell, const uint64_t *caps, uint32_t n_m, uint32_t seed, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                           res_cells_t *C, res_fid_t *Fd, res_reps_t *P, uint32_t k_seed, res_times_t *T, int prof)
+/* what a (cell rate, seed) pair keeps: ONE plane, made again for every pass; the state of the search (on the device: S->d_lo ..);
+ * of the point in work its probing passes and where the clocks stood before them */
+typedef struct { void *d_plane; uint64_t *h_thr, *h_ufull; uint64_t open, capped; uint32_t passes; double search0, device0; } level_pair_t;
+
+static void level_pair_end(void *ctx)
 {
-    int rc = RES_FAIL;
-    void *d_plane = NULL;
-    uint64_t *h_thr = NULL, *h_ufull = NULL;
-    if ((rc = fastf_res_rate_open(S, "level", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
-    rc = RES_FAIL;
-    const uint64_t H = S->H, N = R->n;
+    level_pair_t *c = (level_pair_t *)ctx;
+    if (!c) return;
+    fastf_devmem_free(c->d_plane);
+    if (c->h_thr) fastf_pinned_free(c->h_thr);
+    if (c->h_ufull) fastf_pinned_free(c->h_ufull);
+    free(c);
+}
+
+/* the plane of the thresholds thr (on the device) */
+static int level_plane(level_pair_t *c, const res_pair_t *p, const uint64_t *thr)
+{
+    const res_rate_t *S = p->S;
+    return fastf_dev_cell_decisions(S->e, p->R->n, S->blocked ? S->d_blk : NULL, p->seed, p->L->mt_skip, S->H, thr, (uint32_t *)c->d_plane, NULL);
+}
+
+static int level_pair_begin(const res_pair_t *p, void **ctx)
+{
+    res_rate_t *S = p->S;
+    res_times_t *T = p->T;
     const uint32_t n_cells = S->n_cells;
-    const void *const blk = S->blocked ? S->d_blk : NULL;
+    level_pair_t *c = (level_pair_t *)calloc(1, sizeof *c);
+    if (!(*ctx = c)) return lv_err("out of memory");
     double tt = fastf_res_now();
     const size_t nc1 = (size_t)n_cells + 1;
-    const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind the plane: K1b reads a unit's words unconditionally) */
-    if (fastf_res_level_room(S)) goto done;
-    if (!(h_thr = (uint64_t *)fastf_pinned_alloc(nc1 * 8)) || (!summary_only && !(h_ufull = (uint64_t *)fastf_pinned_alloc(nc1 * 8))) ||
-        !(d_plane = fastf_devmem_alloc(device, (size_t)plane_words * 4)) || fastf_devmem_zero(d_plane, (size_t)plane_words * 4)) goto done;
+    const uint64_t plane_words = ((S->H + 63) / 64) * 2 + 64;   /* (zeroed slack behind the plane: K1b reads a unit's words unconditionally) */
+    if (fastf_res_level_room(S)) return RES_FAIL;
+    if (!(c->h_thr = (uint64_t *)fastf_pinned_alloc(nc1 * 8)) || (!p->summary_only && !(c->h_ufull = (uint64_t *)fastf_pinned_alloc(nc1 * 8))) ||
+        !(c->d_plane = fastf_devmem_alloc(p->device, (size_t)plane_words * 4)) || fastf_devmem_zero(c->d_plane, (size_t)plane_words * 4)) return RES_FAIL;
     T->planes += fastf_res_now() - tt;
 
     /* pass 0: every hit kept.  U_k(2^32) stays on the device for every cap of the list; the state of the first cap comes with it */
-    uint64_t open = 0, capped = 0;
     tt = fastf_res_now();
-    for (uint32_t k = 0; k < n_cells; k++) h_thr[k] = (uint64_t)1 << 32;
-    if (fastf_devmem_copy(S->d_probe, h_thr, (size_t)n_cells * 8) ||
-        fastf_dev_cell_decisions(S->e, N, blk, seed, L->mt_skip, H, S->d_probe, (uint32_t *)d_plane, NULL)) goto done;
+    for (uint32_t k = 0; k < n_cells; k++) c->h_thr[k] = (uint64_t)1 << 32;
+    if (fastf_devmem_copy(S->d_probe, c->h_thr, (size_t)n_cells * 8) || level_plane(c, p, S->d_probe)) return RES_FAIL;
     T->search += fastf_res_now() - tt;
-    {   char name0[64]; snprintf(name0, sizeof name0, "c%.3f (every hit)", (double)rate_cell);
-        const int prc = fastf_res_search_pass(S, (const uint32_t *)d_plane, name0, caps[0], 1, &open, &capped, T);
-        if (prc != RES_OK) { rc = prc; goto done; } }
-    if (fastf_res_full_keep(S, T)) goto done;               /* --fidelity: pass 0's rows are the full rows of the pair */
-    if (h_ufull && fastf_devmem_copy(h_ufull, S->d_ufull, (size_t)n_cells * 8)) goto done;
-
-    for (uint32_t j = 0; j < n_m; j++) {
-        char base[64], name[96], dir[4096], row[640];
-        uint64_t counters[3], nnz = 0;
-        double metrics[FASTF_REPS_METRICS];
-        if (fastf_level_point_dir(rate_cell, caps[j], base, sizeof base)) goto done;
-        if (P->on ? fastf_reps_point_dir(base, seed, name, sizeof name) : (snprintf(name, sizeof name, "%s", base), 0)) goto done;
-        const double search0 = T->search, device0 = T->device;
-        uint32_t passes = 0;
-        if (j) { const int irc = fastf_res_level_init(S, caps[j], &open, &capped, T); if (irc != RES_OK) { rc = irc; goto done; } }
-        while (open) {                                      /* open cells are probed at (lo + hi) / 2, every other cell at 0 */
-            if (passes == LEVEL_MAX_PASSES) { lv_err("internal error: %llu cells still open after %u passes at point %s", (unsigned long long)open, passes, name); goto done; }
-            tt = fastf_res_now();
-            if (fastf_dev_cell_decisions(S->e, N, blk, seed, L->mt_skip, H, S->d_probe, (uint32_t *)d_plane, NULL)) goto done;
-            T->search += fastf_res_now() - tt;
-            const int prc = fastf_res_search_pass(S, (const uint32_t *)d_plane, name, caps[j], 0, &open, NULL, T);
-            if (prc != RES_OK) { rc = prc; goto done; }
-            passes++;
-        }
-        /* the point: T = lo */
-        tt = fastf_res_now();
-        if (fastf_dev_cell_decisions(S->e, N, blk, seed, L->mt_skip, H, S->d_lo, (uint32_t *)d_plane, NULL)) goto done;
-        T->planes += fastf_res_now() - tt;
-        const int prc = fastf_res_point_run(S, (const uint32_t *)d_plane, name, counters, &nnz, T);
-        if (prc != RES_OK) { rc = prc; goto done; }
-        if (prof) fprintf(stderr, "[level] point %s: %u probing passes, search %.4f s, the point's own pass %.4f s\n", name, passes, T->search - search0, T->device - device0);
-        tt = fastf_res_now();
-        if (level_row_(rate_cell, caps[j], seed, counters, nnz, S->h_upc[n_cells], S->h_upc, S->h_gpc, n_cells, H, (uint32_t)capped, row, sizeof row, metrics) ||
-            fastf_res_reps_point(P, j, k_seed, n_cells, metrics)) goto done;
-        T->summary += fastf_res_now() - tt;
-        if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
-        if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
-        if (fastf_res_point_neighbors(S, name, T)) goto done;
-        if (fastf_res_point_labels(S, name, T)) goto done;
-        if (fastf_res_point_markers(S, name, T)) goto done;
-        if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
-            tt = fastf_res_now();
-            if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
-            T->reps += fastf_res_now() - tt;
-        }
-        if (!summary_only) {
-            snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (fastf_res_point_write(S, dir, bam_label, fastf_cap_realised(counters[1], H), counters, nnz, T)) goto done;
-            tt = fastf_res_now();
-            if (fastf_devmem_copy(h_thr, S->d_lo, (size_t)n_cells * 8) || write_thresholds(dir, L, n_cells, h_thr, h_ufull, S->h_upc)) goto done;
-            T->write += fastf_res_now() - tt;
-        }
-        if (fastf_res_fid_point(Fd, S, summary_only ? NULL : dir, 0.0f, caps[j], T)) goto done;
-        if (G->on) {
-            char grow[256];
-            tt = fastf_res_now();
-            if (fastf_genes_summary_row(rate_cell, 0.0f, caps[j], seed, S->h_cpg, S->h_upg, S->n_features, grow, sizeof grow) ||
-                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S->h_cpg, S->h_upg)) goto done;
-            T->genes += fastf_res_now() - tt;
-        }
-        if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
-            char crow[1024];
-            if (fastf_res_point_cells(S, name, T)) goto done;
-            tt = fastf_res_now();
-            if (fastf_cells_summary_row(rate_cell, 0.0f, caps[j], seed, S->h_rpc, S->h_npc, S->h_spc, n_cells, S->h_hist, crow, sizeof crow) ||
-                fastf_res_cells_point(C, S, summary_only ? NULL : dir, crow)) goto done;
-            T->cells += fastf_res_now() - tt;
-        }
-        fputs(row, tsv);
-    }
-    rc = RES_OK;
-done:
-    fastf_devmem_free(d_plane);
-    if (h_thr) fastf_pinned_free(h_thr);
-    if (h_ufull) fastf_pinned_free(h_ufull);
-    return rc;
+    char name0[64]; snprintf(name0, sizeof name0, "c%.3f (every hit)", (double)p->rate_cell);
+    const int prc = fastf_res_search_pass(S, (const uint32_t *)c->d_plane, name0, p->job->caps[0], 1, &c->open, &c->capped, T);
+    if (prc != RES_OK) return prc;
+    if (fastf_res_full_keep(S, T)) return RES_FAIL;         /* --fidelity: pass 0's rows are the full rows of the pair */
+    if (c->h_ufull && fastf_devmem_copy(c->h_ufull, S->d_ufull, (size_t)n_cells * 8)) return RES_FAIL;
+    return RES_OK;
 }
 
-static int level_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features, const float *rc_list, uint32_t n_c,
-                          const uint64_t *caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_s, int summary_only, int device, FILE *tsv, res_genes_t *G,
-                          res_cells_t *C, res_fid_t *Fd, res_reps_t *P)
+static int level_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const char *point_name, const uint32_t **d_plane)
 {
-    int rc = RES_FAIL;
-    const int prof = getenv("FASTF_PROFILE") != NULL;
-    res_times_t T; memset(&T, 0, sizeof T);
-    const double t0 = fastf_res_now();
-    double tt = t0;
-    res_lists_t LL; memset(&LL, 0, sizeof LL);
-    resident_t R; memset(&R, 0, sizeof R);
-    res_rate_t S; memset(&S, 0, sizeof S);
-    /* the (cell rate, seed) pairs: cell rates outer, the seeds as listed */
-    const uint32_t n_pairs = n_c * n_s;
-    float *pair_rate = (float *)malloc(n_pairs * sizeof *pair_rate);
-    uint32_t *pair_seed = (uint32_t *)malloc(n_pairs * sizeof *pair_seed);
-    if (!pair_rate || !pair_seed) { lv_err("out of memory"); goto done; }
-    for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = rc_list[i]; pair_seed[i * n_s + k] = seeds[k]; }
-    if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
-    rc = RES_FAIL;
-    S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels; S.markers = Fd->markers;
-    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
-    T.lists = fastf_res_now() - tt; tt = fastf_res_now();
-    if (fastf_res_decode("level", bam_file, &LL.L[0], device, &R)) goto done;
-    T.decode = fastf_res_now() - tt;
-    if (P->on) printf("level: %llu records resident on the device (%llu bytes), %u x %u points x %u seeds\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_m, n_s);
-    else printf("level: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_m);
-    for (uint32_t i = 0; i < n_c; i++) {
-        if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
-        for (uint32_t k = 0; k < n_s; k++) {
-            const uint32_t at = i * n_s + k;
-            rc = level_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], caps, n_m, seeds[k], summary_only, device, tsv, G, C, Fd, P, k, &T, prof);
-            if (rc != RES_OK) goto done;
-        }
-        if (fastf_res_reps_rate_end(P, rc_list[i], NULL, caps, &T)) { rc = RES_FAIL; goto done; }
+    level_pair_t *c = (level_pair_t *)ctx;
+    res_rate_t *S = p->S;
+    res_times_t *T = p->T;
+    const uint64_t umi_cap = p->job->caps[j];
+    c->search0 = T->search; c->device0 = T->device; c->passes = 0;
+    if (j) { const int irc = fastf_res_level_init(S, umi_cap, &c->open, &c->capped, T); if (irc != RES_OK) return irc; }
+    while (c->open) {                                       /* open cells are probed at (lo + hi) / 2, every other cell at 0 */
+        if (c->passes == LEVEL_MAX_PASSES)
+            return lv_err("internal error: %llu cells still open after %u passes at point %s", (unsigned long long)c->open, c->passes, point_name);
+        const double tt = fastf_res_now();
+        if (level_plane(c, p, S->d_probe)) return RES_FAIL;
+        T->search += fastf_res_now() - tt;
+        const int prc = fastf_res_search_pass(S, (const uint32_t *)c->d_plane, point_name, umi_cap, 0, &c->open, NULL, T);
+        if (prc != RES_OK) return prc;
+        c->passes++;
     }
-    rc = RES_OK;
-    if (prof) {
-        const uint32_t points = n_c * n_m * n_s;
-        fprintf(stderr, "[level] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, planes of the points %.3f s, "
-                        "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
-                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / points, T.summary, T.d2h, T.write, fastf_res_now() - t0);
-        fprintf(stderr, "[level] search: %u passes in all (%u with every hit kept, one per cell rate and seed; %.1f probing passes a point), %.3f s "
-                        "(%.4f s a point, %.4f s a pass with its plane and step)\n",
-                T.passes, n_c * n_s, (double)(T.passes - n_c * n_s) / points, T.search, T.search / points, T.passes ? T.search / T.passes : 0.0);
-    }
-    if (prof && P->on) fprintf(stderr, "[level] replicates: %u (cell rate, seed) pairs opened in %.3f s (engines %.3f s, buffers + layout + K1a %.3f s), the blocked copy "
-                                       "laid out %u times; replicate tables and per-gene accumulation %.3f s\n", T.opens, T.engine + T.block_k1a, T.engine, T.block_k1a, T.relays, T.reps);
-    if (prof && G->on) fprintf(stderr, "[level] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
-    if (prof && C->on) fprintf(stderr, "[level] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
-                               T.cells_dev, T.cells_dev / (n_c * n_m * n_s), T.cells);
-    if (prof && Fd->on) fprintf(stderr, "[level] --fidelity: the full rows kept from %u first passes, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
-    if (prof && Fd->gene_on) fprintf(stderr, "[level] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
-    if (prof && Fd->mk_on) fprintf(stderr, "[level] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", Fd->markers, T.markers);
-    if (prof && Fd->lab_on) fprintf(stderr, "[level] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
-                                    (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
-    if (prof && Fd->nbr_on) fprintf(stderr, "[level] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
-done:
-    fastf_res_rate_close(&S);
-    fastf_res_free(&R);
-    fastf_res_lists_free(&LL);
-    free(pair_rate); free(pair_seed);
-    return rc;
+    /* the point: T = lo */
+    const double tt = fastf_res_now();
+    if (level_plane(c, p, S->d_lo)) return RES_FAIL;
+    T->planes += fastf_res_now() - tt;
+    *d_plane = (const uint32_t *)c->d_plane;
+    return RES_OK;
 }
 
-/* ------------------------------------------------------------------ */
-/* the command                                                         */
-/* ------------------------------------------------------------------ */
-/* reps != 0: a replicate run (fastf_level_reps) — the suffixed directories and the replicate tables, with one seed too */
-static int level_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const uint64_t *caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels, uint32_t markers)
+static void level_point_done(void *ctx, const res_pair_t *p, const char *point_name)
 {
-    if (!bam || !barcodes || !features) return lv_err("level: null argument");
-    if (!out_dir) out_dir = ".";
-    if (fastf_level_check_grid(rates_cell, n_c, caps, n_m)) return 1;
-    if (flags & ~(uint32_t)(FASTF_LEVEL_SUMMARY_ONLY | FASTF_LEVEL_GENES | FASTF_LEVEL_CELLS | FASTF_LEVEL_FIDELITY | FASTF_LEVEL_GENE_FIDELITY | FASTF_LEVEL_NEIGHBORS)) return lv_err("level: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_LEVEL_SUMMARY_ONLY) != 0, genes = (flags & FASTF_LEVEL_GENES) != 0, cells = (flags & FASTF_LEVEL_CELLS) != 0;
-    const int fidelity = (flags & FASTF_LEVEL_FIDELITY) != 0, gene_fidelity = (flags & FASTF_LEVEL_GENE_FIDELITY) != 0, neighbors = (flags & FASTF_LEVEL_NEIGHBORS) != 0;
-    if (access(bam, R_OK) == -1) return lv_err("bam file: %s does not exist.", bam);
-    int dev0 = 0, dev_second = -1;
-    {   const char *dvs = getenv("FASTF_DEVICES");
-        fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
-        if (dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2))
-            return labels ? lv_err("level: --labels needs the resident form, and this job is outside it (several devices), and a UMI cap has no point-by-point form") :
-                   neighbors ? lv_err("level: --neighbors needs the resident form, and this job is outside it (several devices), and a UMI cap has no point-by-point form") :
-                   gene_fidelity ? lv_err("level: --gene-fidelity needs the resident form, and this job is outside it (several devices), and a UMI cap has no point-by-point form")
-                                 : lv_err("level: this job is outside the resident form (several devices), and a UMI cap has no point-by-point form"); }
-    if (fastf_res_make_dir(out_dir)) return 1;
-    res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
-    if (fastf_res_tsv_open(&tsv, out_dir, "level.tsv", fastf_level_header())) return 1;
-    res_genes_t G;
-    if (fastf_res_genes_open(&G, genes, "level", out_dir, fastf_level_genes_header(), n_c * n_m, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
-    res_cells_t C;
-    if (fastf_res_cells_open(&C, cells, "level", out_dir, fastf_level_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
-    res_fid_t Fd;
-    if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "level", out_dir, fastf_level_fidelity_header(), fastf_level_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
-    if (fastf_res_fid_open_neighbors(&Fd, neighbors, "level", out_dir, fastf_level_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    if (fastf_res_fid_open_labels(&Fd, labels, "level", out_dir, fastf_level_labels_header(), fastf_level_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    if (fastf_res_fid_open_markers(&Fd, markers, "level", out_dir, fastf_level_markers_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    res_reps_t P;
-    if (fastf_res_reps_open(&P, reps, "level", out_dir, seeds, n_s, n_c, n_m, genes, dev0, fastf_level_reps_header(), fastf_level_genes_reps_header())) {
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
-    }
-    int rc = level_resident(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_m, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
-    if (rc == RES_NOT_COVERED && labels)
-        lv_err("level: --labels needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a UMI cap has no point-by-point form");
-    else if (rc == RES_NOT_COVERED && neighbors)
-        lv_err("level: --neighbors needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a UMI cap has no point-by-point form");
-    else if (rc == RES_NOT_COVERED && gene_fidelity)
-        lv_err("level: --gene-fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a UMI cap has no point-by-point form");
-    else if (rc == RES_NOT_COVERED)
-        lv_err("level: this job is outside the resident form (keys wider than 64 bits or UMIs beyond what a 64-bit key holds), and a UMI cap has no point-by-point form");
-    if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
-    if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
-    if (!rc && fastf_res_fid_close(&Fd, 1)) rc = 1;
-    if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, NULL, caps)) rc = 1;
-    if (rc) {
-        char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); fastf_res_reps_close(&P, 0);
-        fastf_res_reps_unlink_tables(out_dir, "level");     /* (the tables that were already renamed go too: none is left) */
-        fastf_set_error_(keep);
-        return 1;
-    }
-    if (fastf_res_tsv_close(&tsv, 1)) { fastf_res_reps_unlink_tables(out_dir, "level"); return 1; }
+    const level_pair_t *c = (const level_pair_t *)ctx;
+    if (p->prof) fprintf(stderr, "[level] point %s: %u probing passes, search %.4f s, the point's own pass %.4f s\n", point_name, c->passes, p->T->search - c->search0, p->T->device - c->device0);
+}
+
+static int level_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uint64_t counters[3], uint64_t nnz, char *row, size_t cap, double *metrics)
+{
+    const res_rate_t *S = p->S;
+    return fastf_cap_row_(p->rate_cell, p->job->caps[j], p->seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, S->H,
+                          (uint32_t)((const level_pair_t *)ctx)->capped, row, cap, metrics);
+}
+
+static int level_point_files(void *ctx, const res_pair_t *p, const char *dir)
+{
+    level_pair_t *c = (level_pair_t *)ctx;
+    const res_rate_t *S = p->S;
+    const double tt = fastf_res_now();
+    if (fastf_devmem_copy(c->h_thr, S->d_lo, (size_t)S->n_cells * 8) || write_thresholds(dir, p->L, S->n_cells, c->h_thr, c->h_ufull, S->h_upc)) return 1;
+    p->T->write += fastf_res_now() - tt;
     return 0;
 }
 
-/* labels_path != NULL: the labels file is read and checked before anything is written */
-static int level_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                   const uint64_t *caps, uint32_t n_l, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path, uint32_t markers)
+static void level_run_profile(const res_job_t *job, const res_times_t *T)
 {
-    if (!labels_path) return level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, NULL, 0);
-    if (!bam || !barcodes || !features) return lv_err("level: null argument");
-    if (access(bam, R_OK) == -1) return lv_err("bam file: %s does not exist.", bam);
-    fastf_labels_t *labels = NULL;
-    if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
-    const int rc = level_run_(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_l, seeds, n_s, reps, flags, labels, markers);
-    fastf_labels_free(labels);
-    return rc;
+    const uint32_t pairs = job->n_c * job->n_s, points = pairs * job->n_list;
+    fprintf(stderr, "[level] search: %u passes in all (%u with every hit kept, one per cell rate and seed; %.1f probing passes a point), %.3f s "
+                    "(%.4f s a point, %.4f s a pass with its plane and step)\n",
+            T->passes, pairs, (double)(T->passes - pairs) / points, T->search, T->search / points, T->passes ? T->search / T->passes : 0.0);
 }
 
+static const res_verb_t level_verb = {
+    .name = "level",
+    .header = { fastf_level_header, fastf_level_genes_header, fastf_level_cells_header, fastf_level_fidelity_header, fastf_level_gene_fidelity_header, fastf_level_neighbors_header,
+                fastf_level_labels_header, fastf_level_label_classes_header, fastf_level_markers_header, fastf_level_reps_header, fastf_level_genes_reps_header },
+    .check_caps = fastf_level_check_grid, .caps_point_dir = fastf_level_point_dir,
+    .refusal_tail = ", and a UMI cap has no point-by-point form",
+    .planes_words = "planes of the points", .fid_before = "the full rows kept from ", .fid_after = " first passes",
+    .unlink_reps_always = 1,
+    .pair_begin = level_pair_begin, .point_plane = level_point_plane, .point_done = level_point_done, .point_row = level_point_row,
+    .point_files = level_point_files, .pair_end = level_pair_end, .run_profile = level_run_profile,
+};
+
+/* ------------------------------------------------------------------ */
+/* the entry points, the command                                       */
+/* ------------------------------------------------------------------ */
+int fastf_level(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                const uint64_t *umi_caps, uint32_t n_m, uint32_t seed, uint32_t flags)
+{
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .caps = umi_caps, .n_list = n_m, .seeds = &seed, .n_s = 1, .flags = flags };
+    return fastf_res_grid_run(&level_verb, &job);
+}
+
+int fastf_level_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                     const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
+{
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .caps = umi_caps, .n_list = n_m, .seeds = seeds, .n_s = n_seeds, .reps = 1, .flags = flags };
+    return fastf_res_grid_run(&level_verb, &job);
+}
+
+/* n_seeds == 0: the one seed `seed`, no replicate run */
 int fastf_level_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
 {
-    if (!n_seeds) return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, labels_path, 0);
-    if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, labels_path, 0);
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .caps = umi_caps, .n_list = n_m, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
+                            .labels_path = labels_path };
+    return fastf_res_grid_run(&level_verb, &job);
 }
 
 /* --markers N: the labels run with the marker tables beside it */
@@ -382,24 +249,10 @@ int fastf_level_markers(const char *bam, const char *out_dir, const char *barcod
                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
                        uint32_t markers)
 {
-    if (markers < 1 || markers > FASTF_MARKERS_MAX) return lv_err("level: --markers: N = %u, from 1 to %u", markers, FASTF_MARKERS_MAX);
-    if (!labels_path) return lv_err("level: --markers needs --labels");
-    if (!n_seeds) return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, labels_path, markers);
-    if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, labels_path, markers);
-}
-
-int fastf_level(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                const uint64_t *umi_caps, uint32_t n_m, uint32_t seed, uint32_t flags)
-{
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, &seed, 1, 0, flags, NULL, 0);
-}
-
-int fastf_level_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
-{
-    if (fastf_check_seeds_("level", seeds, n_seeds)) return 1;
-    return level_run(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, 1, flags, NULL, 0);
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .caps = umi_caps, .n_list = n_m, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
+                            .labels_path = labels_path, .markers = markers };
+    return fastf_res_check_markers("level", markers, labels_path) || fastf_res_grid_run(&level_verb, &job);
 }
 
 static void usage_level(FILE *f)
@@ -459,8 +312,7 @@ int cmd_level(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_LEVEL_SUMMARY_ONLY : 0) | (A.genes ? FASTF_LEVEL_GENES : 0) | (A.per_cell ? FASTF_LEVEL_CELLS : 0) | (A.fidelity ? FASTF_LEVEL_FIDELITY : 0) |
-                           (A.gene_fidelity ? FASTF_LEVEL_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_LEVEL_NEIGHBORS : 0);
+    const uint32_t flags = fastf_res_args_flags(&A);
     if (A.markers ? fastf_level_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
         A.labels ? fastf_level_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_level_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags)
@@ -468,15 +320,6 @@ int cmd_level(int argc, const char **argv)
         fprintf(stderr, "\x1b[31mError:\x1b[0m level failed: %s\n", fastf_last_error());
         return 1;
     }
-    if (A.genes && A.n_seeds) printf("level_genes.tsv, level_genes_reps.tsv and level_gene_reps.tsv.gz are generated.\n");
-    else if (A.genes) printf("level_genes.tsv and level_gene_cells.tsv.gz are generated.\n");
-    if (A.per_cell) printf("level_cells.tsv is generated.\n");
-    if (A.fidelity) printf("level_fidelity.tsv is generated.\n");
-    if (A.gene_fidelity) printf("level_gene_fidelity.tsv is generated.\n");
-    if (A.neighbors) printf("level_neighbors.tsv is generated.\n");
-    if (A.labels) printf("level_labels.tsv and level_label_classes.tsv are generated.\n");
-    if (A.markers) printf("level_markers.tsv is generated.\n");
-    if (A.n_seeds) printf("level_reps.tsv is generated.\n");
-    printf("level.tsv is generated.\n");
+    fastf_res_print_generated("level", &A);
     return 0;
 }

@@ -1,7 +1,8 @@
 /*
- * resident.c — the resident pipeline of `fastF sweep` and `fastF cap` (resident.h): list loading with one dictionary, the decode
- * of the BAM into device-resident records, per cell rate the engine + the records in its layout + K1a, per point K1b / sort /
- * reduce / gather / summary and the writers.
+ * resident.c — the resident pipeline of `fastF sweep`, `fastF cap` and `fastF level` (resident.h): list loading with one dictionary,
+ * the decode of the BAM into device-resident records, per cell rate the engine + the records in its layout + K1a, per point K1b /
+ * sort / reduce / gather / summary and the writers, the tables of a run and the command line of the three verbs.  The driver that
+ * runs a verb's grid on it: grid_run.c.
  */
 #define _GNU_SOURCE
 #include "resident.h"
@@ -723,6 +724,15 @@ int fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_tim
     return 0;
 }
 
+int fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (fastf_res_point_fidelity(S, point_name, T)) return 1;     /* (the point's rows are still in the row buffer) */
+    if (fastf_res_point_gene_fidelity(S, point_name, T)) return 1;
+    if (fastf_res_point_neighbors(S, point_name, T)) return 1;
+    if (fastf_res_point_labels(S, point_name, T)) return 1;       /* (directly behind the neighbour sets it votes with) */
+    return fastf_res_point_markers(S, point_name, T);            /* (on the byte planes those sets were made of) */
+}
+
 /* --cells: behind the point.  The full sort and K3u use the engine's workspace, and K3u writes the engine's row regions — the count
  * array and the span tables of the matrix rows — so this runs once fastf_res_point_write has gathered them (resident.h) */
 int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
@@ -1231,9 +1241,11 @@ int fastf_reps_point_dir(const char *point_name, uint32_t seed, char *buf, size_
     REPS_STAT4("saturation") REPS_STAT4("median_umis_per_cell") REPS_STAT4("median_genes_per_cell") "\n"
 const char *fastf_sweep_reps_header(void) { return "rate_cell\trate_depth\t" REPS_COLUMNS_TAIL; }
 const char *fastf_cap_reps_header(void) { return "rate_cell\treads_per_cell\t" REPS_COLUMNS_TAIL; }
+const char *fastf_level_reps_header(void) { return "rate_cell\tumi_cap\t" REPS_COLUMNS_TAIL; }
 #define GENES_REPS_COLUMNS_TAIL "n_reps" REPS_STAT4("genes_detected") "\tgenes_in_all_reps\tgenes_in_any_rep\n"
 const char *fastf_sweep_genes_reps_header(void) { return "rate_cell\trate_depth\t" GENES_REPS_COLUMNS_TAIL; }
 const char *fastf_cap_genes_reps_header(void) { return "rate_cell\treads_per_cell\t" GENES_REPS_COLUMNS_TAIL; }
+const char *fastf_level_genes_reps_header(void) { return "rate_cell\tumi_cap\t" GENES_REPS_COLUMNS_TAIL; }
 
 /* `\t mean \t sd \t min \t max` of v[0], v[stride], ..: two passes in list order, the sample sd; kind 0: integers, 1: %.6f, 2: %.1f */
 static int reps_stat4(const double *v, uint32_t stride, uint32_t n, int kind, char *buf, size_t cap)
@@ -1568,4 +1580,29 @@ int fastf_res_check_inputs(const res_args_t *a)
     if (!a->feat || access(a->feat, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m feature file: %s does not exist.\n", a->feat ? a->feat : "(null)"); return 1; }
     if (!a->bar || access(a->bar, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m barcode file: %s does not exist.\n", a->bar ? a->bar : "(null)"); return 1; }
     return 0;
+}
+
+_Static_assert(FASTF_CAP_SUMMARY_ONLY == FASTF_SWEEP_SUMMARY_ONLY && FASTF_LEVEL_SUMMARY_ONLY == FASTF_SWEEP_SUMMARY_ONLY && FASTF_CAP_GENES == FASTF_SWEEP_GENES &&
+               FASTF_LEVEL_GENES == FASTF_SWEEP_GENES && FASTF_CAP_CELLS == FASTF_SWEEP_CELLS && FASTF_LEVEL_CELLS == FASTF_SWEEP_CELLS &&
+               FASTF_CAP_FIDELITY == FASTF_SWEEP_FIDELITY && FASTF_LEVEL_FIDELITY == FASTF_SWEEP_FIDELITY && FASTF_CAP_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY &&
+               FASTF_LEVEL_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY && FASTF_CAP_NEIGHBORS == FASTF_SWEEP_NEIGHBORS && FASTF_LEVEL_NEIGHBORS == FASTF_SWEEP_NEIGHBORS,
+               "the three verbs share one flag word");
+uint32_t fastf_res_args_flags(const res_args_t *a)
+{
+    return (a->summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (a->genes ? FASTF_SWEEP_GENES : 0) | (a->per_cell ? FASTF_SWEEP_CELLS : 0) | (a->fidelity ? FASTF_SWEEP_FIDELITY : 0) |
+           (a->gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (a->neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
+}
+
+void fastf_res_print_generated(const char *verb, const res_args_t *a)
+{
+    if (a->genes && a->n_seeds) printf("%s_genes.tsv, %s_genes_reps.tsv and %s_gene_reps.tsv.gz are generated.\n", verb, verb, verb);
+    else if (a->genes) printf("%s_genes.tsv and %s_gene_cells.tsv.gz are generated.\n", verb, verb);
+    if (a->per_cell) printf("%s_cells.tsv is generated.\n", verb);
+    if (a->fidelity) printf("%s_fidelity.tsv is generated.\n", verb);
+    if (a->gene_fidelity) printf("%s_gene_fidelity.tsv is generated.\n", verb);
+    if (a->neighbors) printf("%s_neighbors.tsv is generated.\n", verb);
+    if (a->labels) printf("%s_labels.tsv and %s_label_classes.tsv are generated.\n", verb, verb);
+    if (a->markers) printf("%s_markers.tsv is generated.\n", verb);
+    if (a->n_seeds) printf("%s_reps.tsv is generated.\n", verb);
+    printf("%s.tsv is generated.\n", verb);
 }

@@ -1,7 +1,9 @@
-/* resident.h — the resident pipeline `fastF sweep` and `fastF cap` share (resident.c): the packed records of a BAM stay in device
- * memory after ONE decode; per cell rate one engine, the records in its layout and K1a once; per point K1b on that point's
+/* resident.h — the resident pipeline `fastF sweep`, `fastF cap` and `fastF level` share (resident.c): the packed records of a BAM stay
+ * in device memory after ONE decode; per cell rate one engine, the records in its layout and K1a once; per point K1b on that point's
  * decision plane, sort, reduce, the per-cell summary and — when the matrices are wanted — the rows gathered into pinned memory
- * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made.
+ * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made: each verb describes itself in
+ * ONE res_verb_t (its name, headers, wording and the hooks that make the planes), and ONE driver (grid_run.c: fastf_res_grid_run) runs
+ * the checks, the tables, the (cell rate, seed) pairs and the body of every point for all three.
  * --cells adds a stage of its own behind a point (fastf_res_point_cells): the point's keys sorted fully, K3u's rows, their per-cell
  * and copy-number summary.  It runs AFTER the point's matrix rows have left the device — K3u writes the engine's row regions
  * (their count array and the span tables are the ones the matrix rows lie in) and fastf_res_point_write gathers from those.
@@ -183,6 +185,9 @@ static inline const uint64_t *res_mk_sum(const res_rate_t *S, int point) { retur
 static inline const uint32_t *res_mk_det(const res_rate_t *S, int point) { return (const uint32_t *)(res_mk_s2u(S, point) + 2 * res_mk_words(S)); }
 static inline const uint32_t *res_mk_npl(const res_rate_t *S, int point) { return res_mk_det(S, point) + res_mk_words(S); }
 static inline const uint32_t *res_mk_rank(const res_rate_t *S, int point) { return S->mk_rank + (size_t)point * S->n_labels * FASTF_HVG_TOP; }
+/* the five above in their order (fidelity, gene fidelity, neighbors, labels, markers), behind fastf_res_point_run and before
+ * fastf_res_point_write and fastf_res_point_cells: the one place a further comparison of a point is called from */
+int  fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
 /* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
  * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
@@ -278,20 +283,86 @@ void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_H
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
 
-/* the command line both verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --labels --markers --seeds --reps and ONE list option of the verb's own
- * (list_short / list_long: -r/--depth, -n/--reads).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
+/* the command line the three verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --labels --markers --seeds --reps and ONE list option of the verb's own
+ * (list_short / list_long: -r/--depth, -n/--reads, -m/--umis).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
- * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given */
+ * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given.
+ * fastf_res_args_flags: the flag word of the options (the bits of FASTF_SWEEP_*, which FASTF_CAP_* and FASTF_LEVEL_* repeat);
+ * fastf_res_print_generated: the "... is generated." lines of a run that succeeded */
 typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors; const char *labels; uint32_t markers;   /* markers: N of --markers, 0 without */
                  uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;
 int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;
+uint32_t fastf_res_args_flags(const res_args_t *a) FASTF_HIDDEN;
+void fastf_res_print_generated(const char *verb, const res_args_t *a) FASTF_HIDDEN;
+
+/* ---- the grid driver (grid_run.c) ----
+ * res_job_t: what an entry point of a verb was asked for.  The verb's list is rates_depth (sweep) or caps (cap, level), the other NULL —
+ * the convention of fastf_res_reps_rate_end and of the *_summary_row(rate_depth, list_value) functions.  reps != 0: a replicate run
+ * (the suffixed directories and the replicate tables, with one seed too), its seeds checked by the driver */
+typedef struct {
+    const char *bam, *out_dir, *barcodes, *features;
+    const float *rates_cell; uint32_t n_c;
+    const float *rates_depth; const uint64_t *caps; uint32_t n_list;
+    const uint32_t *seeds; uint32_t n_s; int reps;
+    uint32_t flags; const char *labels_path; uint32_t markers;
+} res_job_t;
+/* the tables of a run, zeroed before the first open: every close is safe on a table that was never opened */
+typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_fid_t Fd; res_reps_t P; } res_tables_t;
+/* one (cell rate, seed) pair as the hooks see it: S is open (fastf_res_rate_open) */
+typedef struct {
+    const res_job_t *job; res_rate_t *S; const resident_t *R; const fastf_lists_t *L; const res_fid_t *Fd; res_times_t *T;
+    float rate_cell; uint32_t seed; int device, summary_only, prof;   /* prof: FASTF_PROFILE is set */
+} res_pair_t;
+/* a verb: ONE static const instance in its file.  The hooks (ctx: what pair_begin made, handed to the others; a hook that is NULL is
+ * not called):
+ *   pair_begin   what a pair needs before its first point — sweep: every plane of the pair in one fastf_dev_mt_decisions_multi call and
+ *                the full rows from the extra plane; cap: the hits per cell, and the full rows from an all-ones plane; level: the
+ *                search state, pass 0 with every hit kept, the full rows kept from it.  RES_*
+ *   point_plane  the decision plane of list value j — sweep: an offset into the planes; cap: the thresholds of the cap and their plane;
+ *                level: the probing passes, then the plane of the thresholds found.  RES_*
+ *   point_done   level: its profile line of the point, directly behind fastf_res_point_run
+ *   point_row    the row of the verb's summary table and the metrics of fastf_summary_tail_
+ *   point_files  level: thresholds.tsv.gz into the point's directory, behind fastf_res_point_write
+ *   pair_end     frees what pair_begin made (ctx may be NULL or half built)
+ *   run_profile  level: its search line under FASTF_PROFILE, behind the stage line
+ *   point_by_point  sweep: the grid through bam2db() for a job outside the resident form; the tables were opened afresh */
+typedef struct {
+    const char *name;
+    struct { const char *(*summary)(void), *(*genes)(void), *(*cells)(void), *(*fidelity)(void), *(*gene_fidelity)(void), *(*neighbors)(void),
+                        *(*labels)(void), *(*label_classes)(void), *(*markers)(void), *(*reps)(void), *(*genes_reps)(void); } header;
+    /* cap, level: the grid check and the directory name of a point of a caps list; NULL: sweep's, of a depth-rate list */
+    int (*check_caps)(const float *rates_cell, uint32_t n_c, const uint64_t *caps, uint32_t n);
+    int (*caps_point_dir)(float rate_cell, uint64_t cap_value, char *buf, size_t cap);
+    const char *refusal_tail;            /* behind the refusal of a job outside the resident form; NULL with point_by_point */
+    const char *planes_words;            /* the stage line: what T->planes holds */
+    const char *fid_before, *fid_after;  /* the --fidelity line: around the number of pairs */
+    int unlink_reps_always;              /* a failed run removes the replicate tables even when it is no replicate run */
+    int  (*pair_begin)(const res_pair_t *p, void **ctx);
+    int  (*point_plane)(void *ctx, const res_pair_t *p, uint32_t j, const char *point_name, const uint32_t **d_plane);
+    void (*point_done)(void *ctx, const res_pair_t *p, const char *point_name);
+    int  (*point_row)(void *ctx, const res_pair_t *p, uint32_t j, const uint64_t counters[3], uint64_t nnz, char *row, size_t cap, double *metrics);
+    int  (*point_files)(void *ctx, const res_pair_t *p, const char *dir);
+    void (*pair_end)(void *ctx);
+    void (*run_profile)(const res_job_t *job, const res_times_t *T);
+    int  (*point_by_point)(const res_job_t *job, int summary_only, res_tables_t *tb);
+} res_verb_t;
+/* the run of an entry point: the seeds of a replicate run, null arguments, with labels_path the bam file and the labels (before anything
+ * is written), the grid, the flags, the bam file, the devices, the output directory, the tables, the pairs, the close */
+int fastf_res_grid_run(const res_verb_t *V, const res_job_t *job) FASTF_HIDDEN;
+/* the first two checks of a fastf_*_markers entry point */
+int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path) FASTF_HIDDEN;
 
 /* sweep_cmds.c: the columns of a summary row from `seed` on (no newline); metrics != NULL: the FASTF_REPS_METRICS numbers a replicate
  * table takes from the row (sampled_reads, sampled_valid_reads, nnz, umis, saturation, the two medians) as the row printed them */
 int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
                         const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
+
+/* cap_cmds.c: one row of cap.tsv or level.tsv (with its newline); metrics: fastf_summary_tail_ */
+int fastf_cap_row_(float rate_cell, uint64_t list_value, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                   const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
+                   char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
 
 /* sweep_cmds.c: the seeds of a _reps call — 1 .. FASTF_MAX_SEEDS distinct values */
 int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds) FASTF_HIDDEN;

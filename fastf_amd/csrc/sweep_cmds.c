@@ -7,7 +7,7 @@
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
  * writes for that point — and one row of <out>/sweep.tsv.
  *
- * Resident form (resident.c, shared with `fastF cap`): the packed records (24 bytes each) stay in device memory.  Per cell rate one engine, the records in its
+ * Resident form (resident.c and the driver grid_run.c, shared with `fastF cap` and `fastF level`): the packed records (24 bytes each) stay in device memory.  Per cell rate one engine, the records in its
  * layout, K1a once; the draw stream generated once and compared against every depth threshold in the same pass
  * (fastf_dev_mt_decisions_multi); per depth rate K1b on that point's decision plane, sort, reduce, the per-cell summary
  * (fastf_dev_cell_summary), and — unless --summary-only — the rows gathered into pinned memory for the writers of bam2db.
@@ -213,14 +213,10 @@ int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint
     return 0;
 }
 
-const char *fastf_sweep_genes_header(void)
-{
-    return "rate_cell\trate_depth\tseed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n";
-}
-const char *fastf_cap_genes_header(void)
-{
-    return "rate_cell\treads_per_cell\tseed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n";
-}
+#define GENES_COLUMNS_TAIL "seed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n"
+const char *fastf_sweep_genes_header(void) { return "rate_cell\trate_depth\t" GENES_COLUMNS_TAIL; }
+const char *fastf_cap_genes_header(void) { return "rate_cell\treads_per_cell\t" GENES_COLUMNS_TAIL; }
+const char *fastf_level_genes_header(void) { return "rate_cell\tumi_cap\t" GENES_COLUMNS_TAIL; }
 
 /* one row of sweep_genes.tsv (reads_per_cell == 0) or cap_genes.tsv (reads_per_cell >= 1: a cap is at least 1), with its newline */
 int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *cells_per_gene,
@@ -272,6 +268,7 @@ int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, u
     "copies_26\tcopies_27\tcopies_28\tcopies_29\tcopies_30\tcopies_31\tcopies_32_plus\treads_copies_32_plus\n"
 const char *fastf_sweep_cells_header(void) { return "rate_cell\trate_depth\t" CELLS_COLUMNS_TAIL; }
 const char *fastf_cap_cells_header(void) { return "rate_cell\treads_per_cell\t" CELLS_COLUMNS_TAIL; }
+const char *fastf_level_cells_header(void) { return "rate_cell\tumi_cap\t" CELLS_COLUMNS_TAIL; }
 
 /* one row of sweep_cells.tsv (reads_per_cell == 0) or cap_cells.tsv (reads_per_cell >= 1), with its newline */
 int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *reads,
@@ -962,11 +959,6 @@ int fastf_markers_summary_rows(float rate_cell, float rate_depth, uint64_t list_
 }
 
 /* ------------------------------------------------------------------ */
-/* directories, sweep.tsv                                              */
-/* ------------------------------------------------------------------ */
-static int tsv_open(res_tsv_t *t, const char *out_dir) { return fastf_res_tsv_open(t, out_dir, "sweep.tsv", fastf_sweep_header()); }
-
-/* ------------------------------------------------------------------ */
 /* point by point through bam2db()                                     */
 /* ------------------------------------------------------------------ */
 /* counters, dimensions and rows of a matrix.mtx.gz bam2db() wrote */
@@ -1010,10 +1002,13 @@ done:
     return rc;
 }
 
-static int sweep_point_by_point(const char *bam, const char *out_dir, const char *barcodes, const char *features,
-                                const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int summary_only,
-                                res_tsv_t *tsv, res_genes_t *G, res_reps_t *P)
+/* the hook of a job outside the resident form (res_verb_t.point_by_point) */
+static int sweep_point_by_point(const res_job_t *job, int summary_only, res_tables_t *tb)
 {
+    const char *bam = job->bam, *out_dir = job->out_dir, *barcodes = job->barcodes, *features = job->features;
+    const float *rc_list = job->rates_cell, *rd_list = job->rates_depth;
+    const uint32_t n_c = job->n_c, n_r = job->n_list, n_s = job->n_s, *seeds = job->seeds;
+    res_tsv_t *tsv = &tb->tsv; res_genes_t *G = &tb->G; res_reps_t *P = &tb->P;
     const int saved_u = _umi_copies_flag;
     _umi_copies_flag = 0;
     int rc = 1;
@@ -1075,284 +1070,71 @@ done:
 }
 
 /* ------------------------------------------------------------------ */
-/* resident form (the pipeline itself: resident.c)                     */
+/* the verb (resident.h: res_verb_t; the driver: grid_run.c)           */
 /* ------------------------------------------------------------------ */
-/* one (cell rate, seed) pair — seed k of a replicate run (P->on) — on the run's res_rate_t: the engine, the records in its layout,
- * K1a, the planes, then every depth rate */
-static int sweep_cell_rate(res_rate_t *S, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, const char *bam_label, const char *out_dir,
-                           float rate_cell, const float *rd_list, uint32_t n_r, uint32_t seed, int summary_only, int device, FILE *tsv,
-                           res_genes_t *G, res_cells_t *C, res_fid_t *Fd, res_reps_t *P, uint32_t k, res_times_t *T)
+/* what a (cell rate, seed) pair keeps: every plane of the pair, plane_words apart, and the thresholds they were made from */
+typedef struct { void *d_planes; uint64_t *thr; uint64_t plane_words; } sweep_pair_t;
+
+static void sweep_pair_end(void *ctx)
 {
-    int rc = RES_FAIL;
-    void *d_planes = NULL;
-    const uint32_t n_planes = n_r + (Fd->full ? 1u : 0u);   /* --fidelity, --gene-fidelity: one more plane behind the grid's, every hit kept */
-    uint64_t *thr = (uint64_t *)malloc(n_planes * sizeof *thr);
-    if (!thr) { sw_err("out of memory"); goto done; }
-    if ((rc = fastf_res_rate_open(S, "sweep", R, L, cell_keys, rate_cell, seed, device, G->on, C->on, T)) != RES_OK) goto done;
-    rc = RES_FAIL;
-    const uint64_t H = S->H;
-    double tt = fastf_res_now();
-
-    /* the decision planes: the draw stream once, every threshold in the same pass */
-    const uint64_t plane_words = ((H + 63) / 64) * 2 + 64;      /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
-    if (!(d_planes = fastf_devmem_alloc(device, (size_t)n_planes * plane_words * 4)) || fastf_devmem_zero(d_planes, (size_t)n_planes * plane_words * 4)) goto done;
-    for (uint32_t j = 0; j < n_r; j++) thr[j] = fastf_draw_threshold(rd_list[j]);
-    if (Fd->full) thr[n_r] = (uint64_t)1 << 32;
-    if (fastf_dev_mt_decisions_multi(S->e, seed, L->mt_skip, H, thr, n_planes, (uint32_t *)d_planes, plane_words, NULL)) goto done;
-    T->planes += fastf_res_now() - tt;
-    if (Fd->full) {                                         /* the full rows of the pair, once */
-        const int frc = fastf_res_full_run(S, (const uint32_t *)d_planes + (size_t)n_r * plane_words, T);
-        if (frc != RES_OK) { rc = frc; goto done; }
-    }
-
-    for (uint32_t j = 0; j < n_r; j++) {
-        char base[64], name[96], dir[4096], row[512];
-        uint64_t counters[3], nnz = 0;
-        double metrics[FASTF_REPS_METRICS];
-        if (fastf_sweep_point_dir(rate_cell, rd_list[j], base, sizeof base)) goto done;
-        if (P->on ? fastf_reps_point_dir(base, seed, name, sizeof name) : (snprintf(name, sizeof name, "%s", base), 0)) goto done;
-        const int prc = fastf_res_point_run(S, (const uint32_t *)d_planes + (size_t)j * plane_words, name, counters, &nnz, T);
-        if (prc != RES_OK) { rc = prc; goto done; }
-        tt = fastf_res_now();
-        if (summary_row_(rate_cell, rd_list[j], seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, row, sizeof row, metrics) ||
-            fastf_res_reps_point(P, j, k, S->n_cells, metrics)) goto done;
-        T->summary += fastf_res_now() - tt;
-        if (fastf_res_point_fidelity(S, name, T)) goto done;     /* (the point's rows are still in the row buffer) */
-        if (fastf_res_point_gene_fidelity(S, name, T)) goto done;
-        if (fastf_res_point_neighbors(S, name, T)) goto done;
-        if (fastf_res_point_labels(S, name, T)) goto done;
-        if (fastf_res_point_markers(S, name, T)) goto done;
-        if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
-            tt = fastf_res_now();
-            if (fastf_res_reps_genes(P, S, j, k, S->h_cpg, S->n_features)) goto done;
-            T->reps += fastf_res_now() - tt;
-        }
-        if (!summary_only) {
-            snprintf(dir, sizeof dir, "%s/%s", out_dir, name);
-            if (fastf_res_point_write(S, dir, bam_label, rd_list[j], counters, nnz, T)) goto done;
-        }
-        if (fastf_res_fid_point(Fd, S, summary_only ? NULL : dir, rd_list[j], 0, T)) goto done;
-        if (G->on) {
-            char grow[256];
-            tt = fastf_res_now();
-            if (fastf_genes_summary_row(rate_cell, rd_list[j], 0, seed, S->h_cpg, S->h_upg, S->n_features, grow, sizeof grow) ||
-                fastf_res_genes_point(G, L, name, summary_only ? NULL : dir, grow, S->h_cpg, S->h_upg)) goto done;
-            T->genes += fastf_res_now() - tt;
-        }
-        if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
-            char crow[1024];
-            if (fastf_res_point_cells(S, name, T)) goto done;
-            tt = fastf_res_now();
-            if (fastf_cells_summary_row(rate_cell, rd_list[j], 0, seed, S->h_rpc, S->h_npc, S->h_spc, S->n_cells, S->h_hist, crow, sizeof crow) ||
-                fastf_res_cells_point(C, S, summary_only ? NULL : dir, crow)) goto done;
-            T->cells += fastf_res_now() - tt;
-        }
-        fputs(row, tsv);
-    }
-    rc = RES_OK;
-done:
-    fastf_devmem_free(d_planes);
-    free(thr);
-    return rc;
+    sweep_pair_t *c = (sweep_pair_t *)ctx;
+    if (!c) return;
+    fastf_devmem_free(c->d_planes);
+    free(c->thr); free(c);
 }
 
-static int sweep_resident(const char *bam_file, const char *out_dir, const char *barcodes, const char *features,
-                          const float *rc_list, uint32_t n_c, const float *rd_list, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int summary_only,
-                          int device, FILE *tsv, res_genes_t *G, res_cells_t *C, res_fid_t *Fd, res_reps_t *P)
+/* the decision planes: the draw stream once, every threshold in the same pass */
+static int sweep_pair_begin(const res_pair_t *p, void **ctx)
 {
-    int rc = RES_FAIL;
-    const int prof = getenv("FASTF_PROFILE") != NULL;
-    res_times_t T; memset(&T, 0, sizeof T);
-    const double t0 = fastf_res_now();
-    double tt = t0;
-    res_lists_t LL; memset(&LL, 0, sizeof LL);
-    resident_t R; memset(&R, 0, sizeof R);
-    res_rate_t S; memset(&S, 0, sizeof S);
-    /* the (cell rate, seed) pairs: cell rates outer, the seeds as listed */
-    const uint32_t n_pairs = n_c * n_s;
-    float *pair_rate = (float *)malloc(n_pairs * sizeof *pair_rate);
-    uint32_t *pair_seed = (uint32_t *)malloc(n_pairs * sizeof *pair_seed);
-    if (!pair_rate || !pair_seed) { sw_err("out of memory"); goto done; }
-    for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = rc_list[i]; pair_seed[i * n_s + k] = seeds[k]; }
-    if ((rc = fastf_res_lists_load(barcodes, features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
-    rc = RES_FAIL;
-    S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels; S.markers = Fd->markers;
-    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
-    T.lists = fastf_res_now() - tt; tt = fastf_res_now();
-    if (fastf_res_decode("sweep", bam_file, &LL.L[0], device, &R)) goto done;
-    T.decode = fastf_res_now() - tt;
-    if (P->on) printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points x %u seeds\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r, n_s);
-    else printf("sweep: %llu records resident on the device (%llu bytes), %u x %u points\n", (unsigned long long)R.n, (unsigned long long)(R.n * 24), n_c, n_r);
-
-    for (uint32_t i = 0; i < n_c; i++) {
-        if (fastf_res_reps_rate_begin(P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
-        for (uint32_t k = 0; k < n_s; k++) {
-            const uint32_t at = i * n_s + k;
-            rc = sweep_cell_rate(&S, &R, &LL.L[at], LL.keys[at], bam_file, out_dir, rc_list[i], rd_list, n_r, seeds[k], summary_only, device, tsv, G, C, Fd, P, k, &T);
-            if (rc != RES_OK) goto done;
-        }
-        if (fastf_res_reps_rate_end(P, rc_list[i], rd_list, NULL, &T)) { rc = RES_FAIL; goto done; }
-    }
-    rc = RES_OK;
-    if (prof)
-        fprintf(stderr, "[sweep] lists %.3f s, decode to resident records %.3f s, engines %.3f s, layout+K1a %.3f s, planes %.3f s, "
-                        "per-point device work %.3f s (%.4f s a point), summary D2H+medians %.3f s, rows D2H %.3f s, writers %.3f s, total %.3f s\n",
-                T.lists, T.decode, T.engine, T.block_k1a, T.planes, T.device, T.device / (n_c * n_r * n_s), T.summary, T.d2h, T.write, fastf_res_now() - t0);
-    if (prof && P->on) fprintf(stderr, "[sweep] replicates: %u (cell rate, seed) pairs opened in %.3f s (engines %.3f s, buffers + layout + K1a %.3f s), the blocked copy "
-                                       "laid out %u times; replicate tables and per-gene accumulation %.3f s\n", T.opens, T.engine + T.block_k1a, T.engine, T.block_k1a, T.relays, T.reps);
-    if (prof && G->on) fprintf(stderr, "[sweep] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", T.genes);
-    if (prof && C->on) fprintf(stderr, "[sweep] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n",
-                               T.cells_dev, T.cells_dev / (n_c * n_r * n_s), T.cells);
-    if (prof && Fd->on) fprintf(stderr, "[sweep] --fidelity: %u full-depth points, the joins, their D2H, rows and files %.3f s\n", n_c * n_s, T.fidelity);
-    if (prof && Fd->gene_on) fprintf(stderr, "[sweep] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
-    if (prof && Fd->mk_on) fprintf(stderr, "[sweep] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", Fd->markers, T.markers);
-    if (prof && Fd->lab_on) fprintf(stderr, "[sweep] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", fastf_labels_count(Fd->labels),
-                                    (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
-    if (prof && Fd->nbr_on) fprintf(stderr, "[sweep] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
-done:
-    fastf_res_rate_close(&S);
-    fastf_res_free(&R);
-    fastf_res_lists_free(&LL);
-    free(pair_rate); free(pair_seed);
-    return rc;
+    res_rate_t *S = p->S;
+    const uint32_t n_r = p->job->n_list;
+    const uint32_t n_planes = n_r + (p->Fd->full ? 1u : 0u);   /* --fidelity, --gene-fidelity: one more plane behind the grid's, every hit kept */
+    sweep_pair_t *c = (sweep_pair_t *)calloc(1, sizeof *c);
+    if (!(*ctx = c) || !(c->thr = (uint64_t *)malloc(n_planes * sizeof *c->thr))) return sw_err("out of memory");
+    const double tt = fastf_res_now();
+    c->plane_words = ((S->H + 63) / 64) * 2 + 64;           /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
+    if (!(c->d_planes = fastf_devmem_alloc(p->device, (size_t)n_planes * c->plane_words * 4)) || fastf_devmem_zero(c->d_planes, (size_t)n_planes * c->plane_words * 4)) return RES_FAIL;
+    for (uint32_t j = 0; j < n_r; j++) c->thr[j] = fastf_draw_threshold(p->job->rates_depth[j]);
+    if (p->Fd->full) c->thr[n_r] = (uint64_t)1 << 32;
+    if (fastf_dev_mt_decisions_multi(S->e, p->seed, p->L->mt_skip, S->H, c->thr, n_planes, (uint32_t *)c->d_planes, c->plane_words, NULL)) return RES_FAIL;
+    p->T->planes += fastf_res_now() - tt;
+    /* the full rows of the pair, once */
+    return p->Fd->full ? fastf_res_full_run(S, (const uint32_t *)c->d_planes + (size_t)n_r * c->plane_words, p->T) : RES_OK;
 }
+
+static int sweep_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const char *point_name, const uint32_t **d_plane)
+{
+    const sweep_pair_t *c = (const sweep_pair_t *)ctx;
+    (void)p; (void)point_name;
+    *d_plane = (const uint32_t *)c->d_planes + (size_t)j * c->plane_words;
+    return RES_OK;
+}
+
+static int sweep_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uint64_t counters[3], uint64_t nnz, char *row, size_t cap, double *metrics)
+{
+    const res_rate_t *S = p->S;
+    (void)ctx;
+    return summary_row_(p->rate_cell, p->job->rates_depth[j], p->seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, row, cap, metrics);
+}
+
+static const res_verb_t sweep_verb = {
+    .name = "sweep",
+    .header = { fastf_sweep_header, fastf_sweep_genes_header, fastf_sweep_cells_header, fastf_sweep_fidelity_header, fastf_sweep_gene_fidelity_header, fastf_sweep_neighbors_header,
+                fastf_sweep_labels_header, fastf_sweep_label_classes_header, fastf_sweep_markers_header, fastf_sweep_reps_header, fastf_sweep_genes_reps_header },
+    .planes_words = "planes", .fid_before = "", .fid_after = " full-depth points",
+    .pair_begin = sweep_pair_begin, .point_plane = sweep_point_plane, .point_row = sweep_point_row, .pair_end = sweep_pair_end,
+    .point_by_point = sweep_point_by_point,
+};
 
 /* ------------------------------------------------------------------ */
-/* the command                                                         */
+/* the entry points, the command                                       */
 /* ------------------------------------------------------------------ */
-/* reps != 0: a replicate run (fastf_sweep_reps) — the suffixed directories and the replicate tables, with one seed too */
-static int sweep_run_(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const fastf_labels_t *labels, uint32_t markers)
-{
-    if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
-    if (!out_dir) out_dir = ".";
-    if (fastf_sweep_check_grid(rates_cell, n_c, rates_depth, n_r)) return 1;
-    if (flags & ~(uint32_t)(FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS)) return sw_err("sweep: unknown flags 0x%x", flags);
-    const int summary_only = (flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, genes = (flags & FASTF_SWEEP_GENES) != 0, cells = (flags & FASTF_SWEEP_CELLS) != 0;
-    const int fidelity = (flags & FASTF_SWEEP_FIDELITY) != 0, gene_fidelity = (flags & FASTF_SWEEP_GENE_FIDELITY) != 0, neighbors = (flags & FASTF_SWEEP_NEIGHBORS) != 0;
-    if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
-    int dev0 = 0, dev_second = -1, several = 0;
-    {   const char *dvs = getenv("FASTF_DEVICES");
-        fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
-        several = dvs && *dvs && (strchr(dvs, ',') || atoi(dvs) >= 2); }
-    if (several && cells) return sw_err("sweep: --cells needs the resident form, and this job is outside it (several devices)");
-    if (several && labels) return sw_err("sweep: --labels needs the resident form, and this job is outside it (several devices)");
-    if (several && neighbors) return sw_err("sweep: --neighbors needs the resident form, and this job is outside it (several devices)");
-    if (several && fidelity && gene_fidelity) return sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (several devices)");
-    if (several && fidelity) return sw_err("sweep: --fidelity needs the resident form, and this job is outside it (several devices)");
-    if (several && gene_fidelity) return sw_err("sweep: --gene-fidelity needs the resident form, and this job is outside it (several devices)");
-    if (fastf_res_make_dir(out_dir)) return 1;
-    res_tsv_t tsv; memset(&tsv, 0, sizeof tsv);
-    if (tsv_open(&tsv, out_dir)) return 1;
-    res_genes_t G;
-    if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
-    res_cells_t C;
-    if (fastf_res_cells_open(&C, cells, "sweep", out_dir, fastf_sweep_cells_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1; }
-    res_fid_t Fd;
-    if (fastf_res_fid_open(&Fd, fidelity, gene_fidelity, "sweep", out_dir, fastf_sweep_fidelity_header(), fastf_sweep_gene_fidelity_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); return 1; }
-    if (fastf_res_fid_open_neighbors(&Fd, neighbors, "sweep", out_dir, fastf_sweep_neighbors_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    if (fastf_res_fid_open_labels(&Fd, labels, "sweep", out_dir, fastf_sweep_labels_header(), fastf_sweep_label_classes_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    if (fastf_res_fid_open_markers(&Fd, markers, "sweep", out_dir, fastf_sweep_markers_header())) { fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1; }
-    res_reps_t P;
-    if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); return 1;
-    }
-
-    int rc = several ? RES_NOT_COVERED : sweep_resident(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, dev0, tsv.f, &G, &C, &Fd, &P);
-    if (rc == RES_NOT_COVERED && labels) {
-        sw_err("sweep: --labels needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED && neighbors) {
-        sw_err("sweep: --neighbors needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED && fidelity && gene_fidelity) {
-        sw_err("sweep: --fidelity and --gene-fidelity need the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED && fidelity) {                /* (the full rows live on the device alone: bam2db() point by point has none) */
-        sw_err("sweep: --fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED && gene_fidelity && !fidelity) {
-        sw_err("sweep: --gene-fidelity needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED && cells) {
-        /* (the per-cell rows come from the device's keys alone: bam2db() point by point has none.  Wide keys and a UMI length set
-         * beyond the key are known before the first point; a UMI found too long among the records stops the point that meets it) */
-        sw_err("sweep: --cells needs the resident form, and this job is outside it (keys wider than 64 bits or UMIs beyond what a 64-bit key holds)");
-        rc = RES_FAIL;
-    }
-    if (rc == RES_NOT_COVERED) {
-        fprintf(stderr, "sweep: this job is outside the resident form (%s): running bam2db point by point\n",
-                several ? "several devices" : "keys wider than 64 bits or UMIs beyond what a 64-bit key holds");
-        /* (rows a resident attempt had written are of no use: the table starts again) */
-        fastf_res_tsv_close(&tsv, 0);
-        fastf_res_genes_close(&G, 0);
-        fastf_res_reps_close(&P, 0);
-        if (tsv_open(&tsv, out_dir)) return 1;
-        if (fastf_res_genes_open(&G, genes, "sweep", out_dir, fastf_sweep_genes_header(), n_c * n_r, reps)) { fastf_res_tsv_close(&tsv, 0); return 1; }
-        if (fastf_res_reps_open(&P, reps, "sweep", out_dir, seeds, n_s, n_c, n_r, genes, dev0, fastf_sweep_reps_header(), fastf_sweep_genes_reps_header())) {
-            fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); return 1;
-        }
-        rc = sweep_point_by_point(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, summary_only, &tsv, &G, &P);
-    }
-    if (!rc && fastf_res_genes_close(&G, 1)) rc = 1;
-    if (!rc && fastf_res_cells_close(&C, 1)) rc = 1;
-    if (!rc && fastf_res_fid_close(&Fd, 1)) rc = 1;
-    if (!rc && fastf_res_reps_close_grid(&P, 1, rates_cell, rates_depth, NULL)) rc = 1;
-    if (rc) {
-        char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        fastf_res_tsv_close(&tsv, 0); fastf_res_genes_close(&G, 0); fastf_res_cells_close(&C, 0); fastf_res_fid_close(&Fd, 0); fastf_res_reps_close(&P, 0);
-        if (reps) fastf_res_reps_unlink_tables(out_dir, "sweep");      /* (the tables that were already renamed go too: none is left) */
-        fastf_set_error_(keep);
-        return 1;
-    }
-    if (fastf_res_tsv_close(&tsv, 1)) { if (reps) fastf_res_reps_unlink_tables(out_dir, "sweep"); return 1; }
-    return 0;
-}
-
-/* labels_path != NULL: the labels file is read and checked before anything is written */
-static int sweep_run(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_s, int reps, uint32_t flags, const char *labels_path, uint32_t markers)
-{
-    if (!labels_path) return sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, NULL, 0);
-    if (!bam || !barcodes || !features) return sw_err("sweep: null argument");
-    if (access(bam, R_OK) == -1) return sw_err("bam file: %s does not exist.", bam);
-    fastf_labels_t *labels = NULL;
-    if (fastf_labels_load(labels_path, barcodes, &labels)) return 1;
-    const int rc = sweep_run_(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_s, reps, flags, labels, markers);
-    fastf_labels_free(labels);
-    return rc;
-}
-
-int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
-{
-    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path, 0);
-    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path, 0);
-}
-
-/* --markers N: the labels run with the marker tables beside it */
-int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers)
-{
-    if (markers < 1 || markers > FASTF_MARKERS_MAX) return sw_err("sweep: --markers: N = %u, from 1 to %u", markers, FASTF_MARKERS_MAX);
-    if (!labels_path) return sw_err("sweep: --markers needs --labels");
-    if (!n_seeds) return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, labels_path, markers);
-    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, labels_path, markers);
-}
-
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
 {
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, &seed, 1, 0, flags, NULL, 0);
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .n_list = n_r, .seeds = &seed, .n_s = 1, .flags = flags };
+    return fastf_res_grid_run(&sweep_verb, &job);
 }
 
 /* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
@@ -1367,8 +1149,30 @@ int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds
 int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
-    if (fastf_check_seeds_("sweep", seeds, n_seeds)) return 1;
-    return sweep_run(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, 1, flags, NULL, 0);
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .n_list = n_r, .seeds = seeds, .n_s = n_seeds, .reps = 1, .flags = flags };
+    return fastf_res_grid_run(&sweep_verb, &job);
+}
+
+/* n_seeds == 0: the one seed `seed`, no replicate run */
+int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
+{
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
+                            .labels_path = labels_path };
+    return fastf_res_grid_run(&sweep_verb, &job);
+}
+
+/* --markers N: the labels run with the marker tables beside it */
+int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers)
+{
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
+                            .labels_path = labels_path, .markers = markers };
+    return fastf_res_check_markers("sweep", markers, labels_path) || fastf_res_grid_run(&sweep_verb, &job);
 }
 
 static void usage_sweep(FILE *f)
@@ -1428,8 +1232,7 @@ int cmd_sweep(int argc, const char **argv)
         return 1;
     }
     if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = (A.summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (A.genes ? FASTF_SWEEP_GENES : 0) | (A.per_cell ? FASTF_SWEEP_CELLS : 0) | (A.fidelity ? FASTF_SWEEP_FIDELITY : 0) |
-                           (A.gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (A.neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
+    const uint32_t flags = fastf_res_args_flags(&A);
     if (A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
         A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
@@ -1437,15 +1240,6 @@ int cmd_sweep(int argc, const char **argv)
         fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
         return 1;
     }
-    if (A.genes && A.n_seeds) printf("sweep_genes.tsv, sweep_genes_reps.tsv and sweep_gene_reps.tsv.gz are generated.\n");
-    else if (A.genes) printf("sweep_genes.tsv and sweep_gene_cells.tsv.gz are generated.\n");
-    if (A.per_cell) printf("sweep_cells.tsv is generated.\n");
-    if (A.fidelity) printf("sweep_fidelity.tsv is generated.\n");
-    if (A.gene_fidelity) printf("sweep_gene_fidelity.tsv is generated.\n");
-    if (A.neighbors) printf("sweep_neighbors.tsv is generated.\n");
-    if (A.labels) printf("sweep_labels.tsv and sweep_label_classes.tsv are generated.\n");
-    if (A.markers) printf("sweep_markers.tsv is generated.\n");
-    if (A.n_seeds) printf("sweep_reps.tsv is generated.\n");
-    printf("sweep.tsv is generated.\n");
+    fastf_res_print_generated("sweep", &A);
     return 0;
 }
