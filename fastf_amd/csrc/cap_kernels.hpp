@@ -6,7 +6,7 @@
 //   cell_decisions_kernel   cell scratch + raw draws + per-cell thresholds -> the decision plane of fastf_dev_draw_bits:
 //                           bit i = draws[i] < threshold[cell of the i-th hit]
 #pragma once
-#include "umi_kernels.hpp"
+#include "ranged_hist.hpp"
 
 namespace fastf {
 
@@ -16,22 +16,14 @@ struct CellIn { const void* p; u32 run; u32 off; };
 // ------------------------------------------------------------------------------------
 // hits per cell
 // ------------------------------------------------------------------------------------
-// A wave takes one 256-record unit per turn; a lane reads four neighbouring entries with one load (the order inside a unit
-// does not matter to a histogram).  Index 0 = no hit.
-//
-// Contention (cell sizes are log-normal; a test has one cell that owns every hit):
-//   LDS = true    workgroup-private counters, CAP_LDS_CELLS of them = 128 KiB of the CU's 160 KiB: one 1024-thread workgroup per
-//                 CU (16 waves, 4 per SIMD); from 20 480 cells down (80 KiB) two of them share a CU and the CU is full at 32
-//                 waves.  LDS atomics; flushed with one global atomic per non-zero counter.  A table of up to CAP_LDS_RANGES
-//                 times as many cells is cut into ranges, each with its own share of the workgroups: every range reads the
-//                 whole scratch, which is cheap next to what the general form costs.
-//   LDS = false   beyond that: equal cells are aggregated inside the wave (a leader per distinct cell adds the population
-//                 count of its ballot), one global atomic per distinct cell and 64 records.
+// A ranged histogram (ranged_hist.hpp) over the cell scratch with one u32 counter per cell.  A wave takes one 256-record unit
+// per turn; a lane reads four neighbouring entries with one load (the order inside a unit does not matter to a histogram).
+// Index 0 = no hit.
+// In the general form equal cells are aggregated inside the wave (a leader per distinct cell adds the population count of its
+// ballot): one global atomic per distinct cell and 64 records.
 // Measured on 200 M resident records (profiles/cap_notes): 25 000 cells in LDS 212 us (1.9 TB/s of scratch: bound
 // by the LDS atomics, not by HBM); 50 000 cells in two ranges 394 us; the same 50 000 cells in the general form 9.85 ms — about
 // 50 distinct cells per 64 records, bound by device-scope atomics.  Hence the ranges.
-// In both forms a 64-record item whose hits all name ONE cell (the uniform case: a cell that owns a stretch of the file)
-// costs one atomic.
 constexpr u32 CAP_LDS_CELLS = 32768, CAP_HITS_THREADS = 1024, CAP_LDS_RANGES = 8;
 
 typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
@@ -40,48 +32,37 @@ typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
 template <bool LDS>
 __device__ __forceinline__ void cell_hits_add(u32 c, u32 n_cells, u32* __restrict__ s_cnt, u32* __restrict__ hits, int lane) {
     const bool hit = c - 1u < n_cells;                                     // (0: no hit; an index beyond the table is not counted)
-    u64 rem = __ballot(hit);
-    if (!rem) return;
-    u32* const dst = LDS ? s_cnt : hits;
     if constexpr (LDS) {
-        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)rem) - 1);
-        const u32 c0 = (u32)__builtin_amdgcn_readlane((int)c, leader);
-        if (__ballot(hit && c == c0) == rem) { if (lane == leader) atomicAdd(dst + (c0 - 1u), (u32)__popcll(rem)); }
-        else if (hit) atomicAdd(dst + (c - 1u), 1u);
+        const WaveHits h = wave_hits<false>(hit, c);
+        if (!h.mask) return;
+        if (h.one_bin) { if (lane == h.leader) atomicAdd(s_cnt + (h.bin - 1u), (u32)__popcll(h.mask)); }
+        else if (hit) atomicAdd(s_cnt + (c - 1u), 1u);
     } else {
+        u64 rem = __ballot(hit);
         while (rem) {                                                      // (uniform) one turn per distinct cell of the item
             const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)rem) - 1);
             const u32 c0 = (u32)__builtin_amdgcn_readlane((int)c, leader);
             const u64 m = __ballot(hit && c == c0);
-            if (lane == leader) atomicAdd(dst + (c0 - 1u), (u32)__popcll(m));
+            if (lane == leader) atomicAdd(hits + (c0 - 1u), (u32)__popcll(m));
             rem &= ~m;
         }
     }
 }
 
-// n_ranges (LDS form; the grid is a multiple of it): workgroup b counts the cells of range b % n_ranges — CAP_LDS_CELLS cells each —
-// and the workgroups of one range share the units among them; 1 in the general form.
-template <bool LDS>
-__global__ __launch_bounds__(CAP_HITS_THREADS) void cell_hits_kernel(const CellIn in, bool c16, u64 n, u32 n_cells_all, u32* __restrict__ hits_all, u32 n_ranges) {
-    extern __shared__ u32 s_cnt[];
-    const int tid = threadIdx.x, lane = lane_id();
-    constexpr u32 WAVES = CAP_HITS_THREADS / WAVE;
-    const u32 lo = LDS ? (blockIdx.x % n_ranges) * CAP_LDS_CELLS : 0u;      // first cell (0-based) of this workgroup's range
-    const u32 n_cells = LDS ? (n_cells_all - lo < CAP_LDS_CELLS ? n_cells_all - lo : CAP_LDS_CELLS) : n_cells_all;
-    u32* const hits = hits_all + lo;
-    const u32 group = blockIdx.x / n_ranges, groups = gridDim.x / n_ranges;
-    if constexpr (LDS) {
-        for (u32 i = tid; i < n_cells; i += CAP_HITS_THREADS) s_cnt[i] = 0;
-        __syncthreads();
-    }
-    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    const unsigned char* const p = reinterpret_cast<const unsigned char*>(in.p);
-    for (u64 u = (u64)group * WAVES + (u32)(tid >> 6); u < units; u += (u64)groups * WAVES) {
+struct CellHitsHist {
+    typedef u32 word;
+    static constexpr u32 WORDS = 1, BINS = CAP_LDS_CELLS, THREADS = CAP_HITS_THREADS;
+    static constexpr u64 TURN = 1;                                          // (counted in units)
+    CellIn in; bool c16; u64 n_recs, n; u32* __restrict__ hits;
+    __device__ __forceinline__ void shift(u32 lo) { hits += lo; }
+    template <bool LDS>
+    __device__ __forceinline__ void turn(u64 u, u32 lo, u32 n_cells, u32* __restrict__ s_cnt, int lane) const {
+        const unsigned char* const p = reinterpret_cast<const unsigned char*>(in.p);
         const unsigned char* const at = in.run ? p + u * in.run + in.off : p + u * BLK_RECS * (c16 ? 2u : 4u);
         const u64 first = u * BLK_RECS + 4u * (u32)lane;
         u32 c[4];
         // (a blocked run is whole even when its unit is not; the entries of records that do not exist are not defined)
-        if (in.run || (u + 1) * BLK_RECS <= n) {
+        if (in.run || (u + 1) * BLK_RECS <= n_recs) {
             if (c16) {
                 const u32x2_t v = ld_once<FASTF_NT_K1B != 0>(reinterpret_cast<const u32x2_t*>(at) + lane);
                 c[0] = v.x & 0xFFFFu; c[1] = v.x >> 16; c[2] = v.y & 0xFFFFu; c[3] = v.y >> 16;
@@ -91,18 +72,18 @@ __global__ __launch_bounds__(CAP_HITS_THREADS) void cell_hits_kernel(const CellI
             }
         } else {
 #pragma unroll
-            for (u32 k = 0; k < 4; ++k) c[k] = first + k < n ? get_cell(at, c16, 4u * (u32)lane + k) : 0u;
+            for (u32 k = 0; k < 4; ++k) c[k] = first + k < n_recs ? get_cell(at, c16, 4u * (u32)lane + k) : 0u;
         }
 #pragma unroll
-        for (u32 k = 0; k < 4; ++k) cell_hits_add<LDS>(first + k < n && c[k] ? c[k] - lo : 0u, n_cells, s_cnt, hits, lane);   // (a cell below the range wraps beyond it)
+        for (u32 k = 0; k < 4; ++k) cell_hits_add<LDS>(first + k < n_recs && c[k] ? c[k] - lo : 0u, n_cells, s_cnt, hits, lane);
     }
-    if constexpr (LDS) {
-        __syncthreads();
-        for (u32 i = tid; i < n_cells; i += CAP_HITS_THREADS) {
-            const u32 v = s_cnt[i];
-            if (v) atomicAdd(hits + i, v);
-        }
-    }
+    __device__ __forceinline__ void flush(u32 i, u32 v) const { atomicAdd(hits + i, v); }
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(CAP_HITS_THREADS) void cell_hits_kernel(const CellIn in, bool c16, u64 n, u32 n_cells_all, u32* __restrict__ hits_all, u32 n_ranges) {
+    extern __shared__ u32 s_cnt[];
+    ranged_hist<LDS>(CellHitsHist{in, c16, n, (n + BLK_RECS - 1) / BLK_RECS, hits_all}, n_cells_all, n_ranges, s_cnt);
 }
 
 // ------------------------------------------------------------------------------------

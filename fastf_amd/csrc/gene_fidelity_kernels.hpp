@@ -48,31 +48,21 @@ __global__ __launch_bounds__(FID_THREADS) void partner_counts_kernel(const u32* 
     if (__ballot(missing) && lane == 0) atomicOr(err, ERR_NO_PARTNER);
 }
 
-// A histogram shaped as gene_summary_kernel is (gene_kernels.hpp), with two 64-bit numbers per gene that do not share a word: a * b
-// and b * b both reach 2^64 - 1 under the ABI's precondition (the sum of all counts below 2^32).
-//
-//   LDS = true    workgroup-private counters, two u64 a gene side by side (sum_ab, sum_bb), one ds_add_u64 each per counted row.
-//                 GMOM_LDS_GENES genes = 128 KiB of the CU's 160 KiB: one 1024-thread workgroup per CU; from 5 120 genes down
-//                 (80 KiB) two.  A list of up to GMOM_LDS_RANGES times as many genes is cut into ranges: workgroup b counts range
-//                 b % n_ranges, the workgroups of a range share the rows, every range reads all rows.  Flushed with one global
-//                 atomic per non-zero counter.
-//   LDS = false   beyond that: global atomics, two per counted row.
-// A row with b == 0 adds nothing to either sum and issues no atomic; one with a == 0 issues none for sum_ab.  In both forms a 64-row
-// item whose counted rows all name ONE gene is summed across the wave and costs one atomic per array (gene_add's shortcut).
-// A feature outside 1 .. n_features writes nothing.
+// A ranged histogram (ranged_hist.hpp) with two 64-bit numbers per gene that do not share a word, side by side (sum_ab, sum_bb):
+// a * b and b * b both reach 2^64 - 1 under the ABI's precondition (the sum of all counts below 2^32).  One ds_add_u64 (LDS form) or
+// global atomic (general form) per word and counted row.
+// A row with b == 0 adds nothing to either sum and issues no atomic; one with a == 0 issues none for sum_ab.  Equal genes among 64
+// rows short of all of them are left to the atomic unit, as in gene_add.  A feature outside 1 .. n_features writes nothing.
 constexpr u32 GMOM_LDS_GENES = GENE_LDS_GENES / 2, GMOM_LDS_RANGES = 2 * GENE_LDS_RANGES;
 
 template <bool LDS>
 __device__ __forceinline__ void gmom_add(u32 idx, u32 a, u32 b, u32 n_genes, u64* __restrict__ s_cnt, u64* __restrict__ sum_ab, u64* __restrict__ sum_bb, int lane) {
-    const bool hit = idx < n_genes && b != 0u;                              // (a gene below the range wrapped beyond it)
-    const u64 rem = __ballot(hit);
-    if (!rem) return;                                                      // (uniform)
-    const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)rem) - 1);
-    const u32 g0 = (u32)__builtin_amdgcn_readlane((int)idx, leader);
+    const bool hit = idx < n_genes && b != 0u;
+    const WaveHits h = wave_hits<true>(hit, idx);
+    if (!h.mask) return;                                                   // (uniform)
     u64 ab = hit && sum_ab ? (u64)a * (u64)b : 0ull, bb = hit ? (u64)b * (u64)b : 0ull;   // (no sum_ab asked for: its counters stay 0)
-    const bool one_gene = (rem & (rem - 1)) && __ballot(hit && idx == g0) == rem;   // (uniform) several rows, all of one gene
-    if (one_gene) { ab = wave_sum64(ab); bb = wave_sum64(bb); }            // (neither can carry: precondition)
-    if (one_gene ? lane == leader : hit) {
+    if (h.one_bin) { ab = wave_sum64(ab); bb = wave_sum64(bb); }           // (neither can carry: precondition)
+    if (h.one_bin ? lane == h.leader : hit) {
         if constexpr (LDS) {
             if (ab) (void)__hip_atomic_fetch_add(s_cnt + 2u * idx, ab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             (void)__hip_atomic_fetch_add(s_cnt + 2u * idx + 1u, bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -83,28 +73,14 @@ __device__ __forceinline__ void gmom_add(u32 idx, u32 a, u32 b, u32 n_genes, u64
     }
 }
 
-// feature[i] (1-based), a[i], b[i]; *n_ptr rows.  The caller has cleared ab_all[0 .. n_features_all) and bb_all[0 .. n_features_all).
-// ab_all == nullptr: sum_bb alone — no a * b is formed, added or flushed (sum_xx of the full rows needs one sum, not two equal ones).
-// n_ranges (LDS form; the grid is a multiple of it): see above; 1 in the general form.  Dynamic LDS (LDS form):
-// min(n_features_all, GMOM_LDS_GENES) * 16 bytes.
-template <bool LDS>
-__global__ __launch_bounds__(GENE_THREADS) void gene_moments_kernel(const u32* __restrict__ feature, const u32* __restrict__ va, const u32* __restrict__ vb,
-                                                                    const u64* __restrict__ n_ptr, u32 n_features_all, u64* __restrict__ ab_all,
-                                                                    u64* __restrict__ bb_all, u32 n_ranges) {
-    extern __shared__ u64 s_gmom[];
-    const int tid = threadIdx.x, lane = lane_id();
-    constexpr u32 WAVES = GENE_THREADS / WAVE;
-    const u64 n = *n_ptr;
-    const u32 lo = LDS ? (blockIdx.x % n_ranges) * GMOM_LDS_GENES : 0u;     // first gene (0-based) of this workgroup's range
-    const u32 n_genes = LDS ? (n_features_all - lo < GMOM_LDS_GENES ? n_features_all - lo : GMOM_LDS_GENES) : n_features_all;
-    u64* const sum_ab = ab_all ? ab_all + lo : nullptr; u64* const sum_bb = bb_all + lo;
-    const u32 group = blockIdx.x / n_ranges, groups = gridDim.x / n_ranges;
-    if constexpr (LDS) {
-        for (u32 i = tid; i < 2u * n_genes; i += GENE_THREADS) s_gmom[i] = 0;
-        __syncthreads();
-    }
-    constexpr u64 TURN = (u64)GENE_ITEMS * WAVE;
-    for (u64 base = ((u64)group * WAVES + (u32)(tid >> 6)) * TURN; base < n; base += (u64)groups * WAVES * TURN) {
+struct GeneMomentsHist {
+    typedef u64 word;
+    static constexpr u32 WORDS = 2, BINS = GMOM_LDS_GENES, THREADS = GENE_THREADS;
+    static constexpr u64 TURN = (u64)GENE_ITEMS * WAVE;
+    const u32* __restrict__ feature; const u32* __restrict__ va; const u32* __restrict__ vb; u64 n; u64* __restrict__ sum_ab; u64* __restrict__ sum_bb;
+    __device__ __forceinline__ void shift(u32 lo) { if (sum_ab) sum_ab += lo; sum_bb += lo; }
+    template <bool LDS>
+    __device__ __forceinline__ void turn(u64 base, u32 lo, u32 n_genes, u64* __restrict__ s_cnt, int lane) const {
         u32 f[GENE_ITEMS], a[GENE_ITEMS], b[GENE_ITEMS];
 #pragma unroll
         for (u32 j = 0; j < GENE_ITEMS; ++j) {
@@ -115,15 +91,19 @@ __global__ __launch_bounds__(GENE_THREADS) void gene_moments_kernel(const u32* _
             b[j] = valid ? ld_once<FASTF_NT_K3 != 0>(vb + i) : 0u;
         }
 #pragma unroll
-        for (u32 j = 0; j < GENE_ITEMS; ++j) gmom_add<LDS>(f[j] - 1u - lo, a[j], b[j], n_genes, s_gmom, sum_ab, sum_bb, lane);   // (feature 0 wraps beyond every range)
+        for (u32 j = 0; j < GENE_ITEMS; ++j) gmom_add<LDS>(f[j] - 1u - lo, a[j], b[j], n_genes, s_cnt, sum_ab, sum_bb, lane);   // (feature 0 wraps beyond every range)
     }
-    if constexpr (LDS) {
-        __syncthreads();
-        for (u32 i = tid; i < 2u * n_genes; i += GENE_THREADS) {
-            const u64 v = s_gmom[i];
-            if (v) atomicAdd(((i & 1u) ? sum_bb : sum_ab) + (i >> 1), v);
-        }
-    }
+    __device__ __forceinline__ void flush(u32 i, u64 v) const { atomicAdd(((i & 1u) ? sum_bb : sum_ab) + (i >> 1), v); }
+};
+
+// feature[i] (1-based), a[i], b[i]; *n_ptr rows.  The caller has cleared ab_all[0 .. n_features_all) and bb_all[0 .. n_features_all).
+// ab_all == nullptr: sum_bb alone — no a * b is formed, added or flushed (sum_xx of the full rows needs one sum, not two equal ones).
+template <bool LDS>
+__global__ __launch_bounds__(GENE_THREADS) void gene_moments_kernel(const u32* __restrict__ feature, const u32* __restrict__ va, const u32* __restrict__ vb,
+                                                                    const u64* __restrict__ n_ptr, u32 n_features_all, u64* __restrict__ ab_all,
+                                                                    u64* __restrict__ bb_all, u32 n_ranges) {
+    extern __shared__ u64 s_gmom[];
+    ranged_hist<LDS>(GeneMomentsHist{feature, va, vb, *n_ptr, ab_all, bb_all}, n_features_all, n_ranges, s_gmom);
 }
 
 }  // namespace fastf

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -240,7 +241,7 @@ struct fastf_engine {
     DevBuf d_dbits;                      // device-level calls that bring 32-bit draws: their decisions (draw_bits_kernel)
     DevBuf d_mtwords;                    // the generator's words of one launch, between mt_fill_kernel and draw_bits_kernel
     // fastf_dev_cell_decisions: which stream d_mtwords holds from its first word on (any other generator launch ends it), and
-    // whether cell_hits_kernel<true> has its dynamic-LDS attribute on this engine's device
+    // whether cell_hits_kernel<true> has its dynamic-LDS attribute on this engine's device (lds_attr_once)
     bool mtwords_kept = false; u32 mtwords_seed = 0; u64 mtwords_skip = 0, mtwords_n = 0;
     bool cap_lds_attr = false;
     bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
@@ -1113,6 +1114,38 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
     return 0;
 } FASTF_CATCH_INT
 
+// The dynamic-LDS limit of `kernels`, set on the engine's first use of them: the attribute belongs to the current device's function,
+// so `done` is a flag of the engine.
+static int lds_attr_once(bool& done, size_t bytes, std::initializer_list<const void*> kernels) {
+    if (done) return 0;
+    for (const void* k : kernels) HIP_OK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done = true;
+    return 0;
+}
+
+// The launch plan of a ranged histogram (ranged_hist.hpp) over n_bins bins: up to max_ranges ranges of bins_per_range bins take the
+// LDS form, each range with its own share of the workgroups (every range reads all rows); <env>=<k> lowers that (0: the general
+// form always — tests, A/B runs) and is read at each call.  per_cu: the workgroups a CU holds with lds_bytes of counters each.
+struct HistPlan { bool lds_form; u32 n_ranges; size_t lds_bytes; u32 per_cu; };
+static HistPlan hist_plan(u32 n_bins, u32 bins_per_range, u32 max_ranges, const char* env, size_t bytes_per_bin) {
+    const char* mr = getenv(env);
+    if (mr) max_ranges = std::min<u32>((u32)atoi(mr), max_ranges);
+    const u32 n_ranges = (n_bins + bins_per_range - 1) / bins_per_range;
+    const size_t lds_bytes = (size_t)std::min<u32>(n_bins, bins_per_range) * bytes_per_bin;
+    return {n_ranges <= max_ranges, n_ranges, lds_bytes, lds_bytes <= 80u * 1024u ? 2u : 1u};
+}
+
+// The end of the two joins (fastf_dev_fidelity, fastf_dev_partner_counts): waits for the stream, reads the error word back and fails
+// in `fn`'s name when a point row had no partner.
+static int join_end(const char* fn, hipStream_t s, const u64* err) {
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 bits = 0;
+    if (copy_d2h(&bits, err, sizeof bits)) return 1;
+    if (bits & ERR_NO_PARTNER) return set_err("%s: a point row has no partner among the full rows (device error bits 0x%llx)", fn, (unsigned long long)bits);
+    return 0;
+}
+
 // --fidelity: a point's rows joined with the full-depth rows of its (cell rate, seed) pair (fidelity_kernel).  Both row sets ascend
 // by (cell, feature) and every point row has its partner among the full rows; d_sum_xy[c - 1] = the sum of x * y over the point
 // rows of cell c, d_sum_yy[c - 1] = the sum of y * y.  Both arrays are cleared here first; *d_nnz_full and *d_nnz rows are read.
@@ -1133,12 +1166,7 @@ extern "C" int fastf_dev_fidelity(fastf_engine_t* e, const uint32_t* d_feature_f
     u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
     hipLaunchKernelGGL(fidelity_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
                        (const u64*)d_nnz_full, d_feature, d_cell, d_count, (const u64*)d_nnz, n_cells, (u64*)d_sum_xy, (u64*)d_sum_yy, err);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(s));
-    u64 bits = 0;
-    if (copy_d2h(&bits, err, sizeof bits)) return 1;
-    if (bits & ERR_NO_PARTNER) return set_err("fastf_dev_fidelity: a point row has no partner among the full rows (device error bits 0x%llx)", (unsigned long long)bits);
-    return 0;
+    return join_end("fastf_dev_fidelity", s, err);
 } FASTF_CATCH_INT
 
 // Per-gene summary of COO rows in any order (gene_summary_kernel): d_cells_per_gene[g - 1] = rows of gene g with count >= 1,
@@ -1152,22 +1180,13 @@ extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_featu
     HIP_OK(hipMemsetAsync(d_cells_per_gene, 0, (size_t)n_features * sizeof(u32), s));
     HIP_OK(hipMemsetAsync(d_umis_per_gene, 0, (size_t)n_features * sizeof(u64), s));
     if (!d_feature || !d_count) return 0;               // (no row buffer: a reduce of nothing)
-    // up to GENE_LDS_RANGES ranges of GENE_LDS_GENES genes take the LDS form, each range with its own share of the workgroups (every
-    // range reads all rows); FASTF_GENE_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs).  The row count
-    // lives on the device: the grid is sized by the device alone.
-    const u32 n_ranges = (n_features + GENE_LDS_GENES - 1) / GENE_LDS_GENES;
-    const char* mr = getenv("FASTF_GENE_LDS_RANGES");
-    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), GENE_LDS_RANGES) : GENE_LDS_RANGES;
-    if (n_ranges <= max_ranges) {
-        const size_t lds = (size_t)std::min<u32>(n_features, GENE_LDS_GENES) * sizeof(u64);
-        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
-        if (!e->gene_lds_attr) {                                 // (per engine, on first use: the attribute belongs to the current device's function)
-            HIP_OK(hipFuncSetAttribute((const void*)gene_summary_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GENE_LDS_GENES * sizeof(u64))));
-            e->gene_lds_attr = true;
-        }
-        const u32 groups = std::max<u32>(1u, per_cu * (u32)g_cu_count / n_ranges);
-        hipLaunchKernelGGL(gene_summary_kernel<true>, dim3(groups * n_ranges), dim3(GENE_THREADS), lds, s, d_feature, d_count, (const u64*)d_nnz, n_features,
-                           d_cells_per_gene, (u64*)d_umis_per_gene, n_ranges);
+    // (the row count lives on the device: the grid is sized by the device alone)
+    const HistPlan pl = hist_plan(n_features, GENE_LDS_GENES, GENE_LDS_RANGES, "FASTF_GENE_LDS_RANGES", sizeof(u64));
+    if (pl.lds_form) {
+        if (lds_attr_once(e->gene_lds_attr, GENE_LDS_GENES * sizeof(u64), {(const void*)gene_summary_kernel<true>})) return 1;
+        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)g_cu_count / pl.n_ranges);
+        hipLaunchKernelGGL(gene_summary_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_count, (const u64*)d_nnz, n_features,
+                           d_cells_per_gene, (u64*)d_umis_per_gene, pl.n_ranges);
     } else {
         hipLaunchKernelGGL(gene_summary_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_count, (const u64*)d_nnz, n_features,
                            d_cells_per_gene, (u64*)d_umis_per_gene, 1u);
@@ -1191,12 +1210,7 @@ extern "C" int fastf_dev_partner_counts(fastf_engine_t* e, const uint32_t* d_fea
     u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
     hipLaunchKernelGGL(partner_counts_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
                        (const u64*)d_nnz_full, d_feature, d_cell, (const u64*)d_nnz, d_x, err);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(s));
-    u64 bits = 0;
-    if (copy_d2h(&bits, err, sizeof bits)) return 1;
-    if (bits & ERR_NO_PARTNER) return set_err("fastf_dev_partner_counts: a point row has no partner among the full rows (device error bits 0x%llx)", (unsigned long long)bits);
-    return 0;
+    return join_end("fastf_dev_partner_counts", s, err);
 } FASTF_CATCH_INT
 
 // --gene-fidelity: per gene the sums of a * b and of b * b over rows (feature, a, b) in any order (gene_moments_kernel):
@@ -1210,21 +1224,12 @@ extern "C" int fastf_dev_gene_moments(fastf_engine_t* e, const uint32_t* d_featu
     if (d_sum_ab) HIP_OK(hipMemsetAsync(d_sum_ab, 0, (size_t)n_features * sizeof(u64), s));
     HIP_OK(hipMemsetAsync(d_sum_bb, 0, (size_t)n_features * sizeof(u64), s));
     if (!d_feature || !d_a || !d_b) return 0;           // (no row buffer: a reduce of nothing)
-    // as fastf_dev_gene_summary: up to GMOM_LDS_RANGES ranges of GMOM_LDS_GENES genes take the LDS form;
-    // FASTF_GENE_MOMENTS_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs)
-    const u32 n_ranges = (n_features + GMOM_LDS_GENES - 1) / GMOM_LDS_GENES;
-    const char* mr = getenv("FASTF_GENE_MOMENTS_LDS_RANGES");
-    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), GMOM_LDS_RANGES) : GMOM_LDS_RANGES;
-    if (n_ranges <= max_ranges) {
-        const size_t lds = (size_t)std::min<u32>(n_features, GMOM_LDS_GENES) * 2 * sizeof(u64);
-        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
-        if (!e->gmom_lds_attr) {                                 // (per engine, on first use: the attribute belongs to the current device's function)
-            HIP_OK(hipFuncSetAttribute((const void*)gene_moments_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GMOM_LDS_GENES * 2 * sizeof(u64))));
-            e->gmom_lds_attr = true;
-        }
-        const u32 groups = std::max<u32>(1u, per_cu * (u32)g_cu_count / n_ranges);
-        hipLaunchKernelGGL(gene_moments_kernel<true>, dim3(groups * n_ranges), dim3(GENE_THREADS), lds, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
-                           (u64*)d_sum_ab, (u64*)d_sum_bb, n_ranges);
+    const HistPlan pl = hist_plan(n_features, GMOM_LDS_GENES, GMOM_LDS_RANGES, "FASTF_GENE_MOMENTS_LDS_RANGES", 2 * sizeof(u64));
+    if (pl.lds_form) {
+        if (lds_attr_once(e->gmom_lds_attr, GMOM_LDS_GENES * 2 * sizeof(u64), {(const void*)gene_moments_kernel<true>})) return 1;
+        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)g_cu_count / pl.n_ranges);
+        hipLaunchKernelGGL(gene_moments_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
+                           (u64*)d_sum_ab, (u64*)d_sum_bb, pl.n_ranges);
     } else {
         hipLaunchKernelGGL(gene_moments_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
                            (u64*)d_sum_ab, (u64*)d_sum_bb, 1u);
@@ -1377,12 +1382,8 @@ extern "C" int fastf_dev_label_votes(fastf_engine_t* e, const uint32_t* d_idx, c
     if (!d_idx || !d_cnt || !d_lab || !d_pred || !d_same || !d_labelled) return set_err("fastf_dev_label_votes: null argument");
     const char* lf = getenv("FASTF_LABELS_LDS");
     const bool lds_form = lab_conf_fits_lds(n_labels) && !(lf && lf[0] == '0');
-    if (lds_form && !e->lab_lds_attr) {                      // (per engine, on first use: the attribute belongs to the current device's function)
-        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
-        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
-        HIP_OK(hipFuncSetAttribute((const void*)label_votes_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LAB_LDS_BYTES));
-        e->lab_lds_attr = true;
-    }
+    if (lds_form && lds_attr_once(e->lab_lds_attr, LAB_LDS_BYTES, {(const void*)label_votes_kernel<16, true>, (const void*)label_votes_kernel<32, true>,
+                                                                   (const void*)label_votes_kernel<64, true>})) return 1;
     int rc;
     if (k <= 16) rc = label_votes_launch<16>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
     else if (k <= 32) rc = label_votes_launch<32>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
@@ -1438,13 +1439,8 @@ extern "C" int fastf_dev_marker_auc(fastf_engine_t* e, const void* d_planes, uin
     HIP_OK(hipGetLastError());
     if (!K) return 0;
     const bool lds_form = fastf_marker_auc_form(planes, n_labels) == 1;
-    if (!e->mk_lds_attr) {                                   // (per engine, on first use: the attribute belongs to the current device's function)
-        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
-        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
-        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
-        HIP_OK(hipFuncSetAttribute((const void*)marker_auc_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MK_LDS_BYTES));
-        e->mk_lds_attr = true;
-    }
+    if (lds_attr_once(e->mk_lds_attr, MK_LDS_BYTES, {(const void*)marker_auc_kernel<1, true>, (const void*)marker_auc_kernel<1, false>,
+                                                     (const void*)marker_auc_kernel<2, true>, (const void*)marker_auc_kernel<2, false>})) return 1;
     uint32_t n_pad = 0, K_pad = 0;
     fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
     const unsigned char* const pl = (const unsigned char*)d_planes;
@@ -1528,20 +1524,11 @@ extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_
     const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
     constexpr u32 WAVES = CAP_HITS_THREADS / WAVE;
     const CellIn in = cell_scratch_of(e, d_blocked);
-    // up to CAP_LDS_RANGES ranges of CAP_LDS_CELLS cells take the LDS form, each range with its own share of the workgroups (every
-    // range reads the whole scratch); FASTF_CAP_LDS_RANGES=<k> lowers that (0: the general form always — tests, A/B runs)
-    const u32 n_ranges = (e->n_cells + CAP_LDS_CELLS - 1) / CAP_LDS_CELLS;
-    const char* mr = getenv("FASTF_CAP_LDS_RANGES");
-    const u32 max_ranges = mr ? std::min<u32>((u32)atoi(mr), CAP_LDS_RANGES) : CAP_LDS_RANGES;
-    if (n_ranges <= max_ranges) {
-        const size_t lds = (size_t)std::min<u32>(e->n_cells, CAP_LDS_CELLS) * sizeof(u32);
-        const u32 per_cu = lds <= 80u * 1024u ? 2u : 1u;
-        if (!e->cap_lds_attr) {                                  // (per engine, on first use: the attribute belongs to the current device's function)
-            HIP_OK(hipFuncSetAttribute((const void*)cell_hits_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CAP_LDS_CELLS * sizeof(u32))));
-            e->cap_lds_attr = true;
-        }
-        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)per_cu * g_cu_count / n_ranges));
-        hipLaunchKernelGGL(cell_hits_kernel<true>, dim3(groups * n_ranges), dim3(CAP_HITS_THREADS), lds, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, n_ranges);
+    const HistPlan pl = hist_plan(e->n_cells, CAP_LDS_CELLS, CAP_LDS_RANGES, "FASTF_CAP_LDS_RANGES", sizeof(u32));
+    if (pl.lds_form) {
+        if (lds_attr_once(e->cap_lds_attr, CAP_LDS_CELLS * sizeof(u32), {(const void*)cell_hits_kernel<true>})) return 1;
+        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)pl.per_cu * g_cu_count / pl.n_ranges));
+        hipLaunchKernelGGL(cell_hits_kernel<true>, dim3(groups * pl.n_ranges), dim3(CAP_HITS_THREADS), pl.lds_bytes, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, pl.n_ranges);
     } else {
         const u32 grid = (u32)std::min<u64>((units + WAVES - 1) / WAVES, 2ull * g_cu_count);
         hipLaunchKernelGGL(cell_hits_kernel<false>, dim3(grid), dim3(CAP_HITS_THREADS), 0, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, 1u);

@@ -1,5 +1,6 @@
 """`fastF cap`, the parts that need no device: the per-cell thresholds against their numpy restatement, list parsing, directory
-names, the cap.tsv header and a row, and the error exits of the command line."""
+names, the cap.tsv header and a row, and the error exits of the command line — and the builder of the records
+tests/test_gpu_cap.py counts at the last LDS range, with its census."""
 import subprocess
 
 import numpy as np
@@ -8,6 +9,39 @@ import pytest
 import fastf_amd as F
 from fastf_amd import _lib, cap
 from cap_ref import draw_threshold, realised, thresholds
+
+
+CAP_LDS_CELLS, CAP_LDS_RANGES = 32768, 8                                 # cap_kernels.hpp
+
+
+def last_range_cells(n_cells):
+    """the cell index (0: no hit) of every record for a table of n_cells cells, 8 x 32 768 or one more — the most the LDS form of
+    cell_hits_kernel takes, and the first table of the general form: 600 records in a row on the last cell of the seventh range
+    (two whole 256-record units of one cell), then, shuffled, 3000 random records, a third of them misses, and seven records each
+    on the first and the last cell of every range and on no cell at all"""
+    rng = np.random.default_rng(n_cells)
+    special = [0]
+    for lo in range(0, n_cells, CAP_LDS_CELLS):
+        special += [lo + 1, min(lo + CAP_LDS_CELLS, n_cells)]
+    c = np.concatenate([rng.integers(1, n_cells + 1, size=3000), np.repeat(np.array(special, np.int64), 7)])
+    c[:3000][rng.random(3000) < 1 / 3] = 0
+    return np.concatenate([np.full(600, 7 * CAP_LDS_CELLS), rng.permutation(c)])
+
+
+@pytest.mark.parametrize("n_cells", [CAP_LDS_CELLS * CAP_LDS_RANGES, CAP_LDS_CELLS * CAP_LDS_RANGES + 1])
+def test_census_of_the_last_range_records(n_cells):
+    """np.bincount alone, against a plain loop over the records: every edge cell has its hits, a miss adds nothing"""
+    cell = last_range_cells(n_cells)
+    assert 3000 < len(cell) < 4000 and (cell[:600] == 7 * CAP_LDS_CELLS).all() and 800 < (cell == 0).sum() < 1300
+    want = [0] * n_cells
+    for c in cell.tolist():
+        if c:
+            want[c - 1] += 1
+    assert np.bincount(cell[cell > 0] - 1, minlength=n_cells).tolist() == want
+    for lo in range(0, n_cells, CAP_LDS_CELLS):                           # 8 ranges, or 8 and a ninth of one cell
+        for c in (lo + 1, min(lo + CAP_LDS_CELLS, n_cells)):
+            assert want[c - 1] >= (607 if c == 7 * CAP_LDS_CELLS else 7)
+    assert (n_cells + CAP_LDS_CELLS - 1) // CAP_LDS_CELLS == (8 if n_cells == CAP_LDS_CELLS * CAP_LDS_RANGES else 9)
 
 
 def test_draw_threshold_restatement_is_the_library_function():

@@ -102,6 +102,41 @@ def moments_fixture(name):
     return f, a, b, nf
 
 
+def last_range_fixture(nf):
+    """(feature, a, b) for a list of nf genes, 16 x 8192 or one more — the most the LDS form takes, and the first list of the general
+    form: 200 rows in a row on the last gene of the seventh range (whole 64-row items of one gene), then, shuffled, 3000 random rows
+    and seven rows each (two with b == 0) on the first and the last gene of every range and on the features 0, nf + 1 and 2^32 - 1"""
+    rng = np.random.default_rng(nf)
+    special = [0, nf + 1, 0xFFFFFFFF]
+    for lo in range(0, nf, GMOM_LDS_GENES):
+        special += [lo + 1, min(lo + GMOM_LDS_GENES, nf)]
+    f = np.concatenate([rng.integers(1, nf + 1, size=3000), np.repeat(np.array(special, np.int64), 7)])
+    a = np.concatenate([rng.integers(0, 3000, size=3000), np.tile([5, 0, 1, 2, 9, 3, 1], len(special))])
+    b = np.concatenate([rng.integers(0, 3000, size=3000), np.tile([3, 0, 1, 2, 0, 5, 1], len(special))])
+    order = rng.permutation(len(f))
+    stretch = 200
+    return (np.concatenate([np.full(stretch, 7 * GMOM_LDS_GENES), f[order]]), np.concatenate([rng.integers(0, 1000, size=stretch), a[order]]),
+            np.concatenate([rng.integers(1, 1000, size=stretch), b[order]]))
+
+
+@pytest.mark.parametrize("nf", [LDS_LIMIT, LDS_LIMIT + 1])
+def test_census_of_the_last_range_fixture(nf):
+    """the reference alone, against a plain loop over the rows: every edge gene has its sums, the features outside the list add nothing"""
+    f, a, b = last_range_fixture(nf)
+    assert 3000 < len(f) < 4000 and (f[:200] == 7 * GMOM_LDS_GENES).all() and (b[:200] > 0).all()
+    want_ab, want_bb = [0] * nf, [0] * nf
+    for g, x, y in zip(f.tolist(), a.tolist(), b.tolist()):
+        if 1 <= g <= nf:
+            want_ab[g - 1] += x * y
+            want_bb[g - 1] += y * y
+    assert G.gene_sums(f, a, b, nf) == (want_ab, want_bb)
+    assert sum((f == g).sum() for g in (0, nf + 1, 0xFFFFFFFF)) == 21
+    for lo in range(0, nf, GMOM_LDS_GENES):                 # 16 ranges, or 16 and a seventeenth of one gene
+        for g in (lo + 1, min(lo + GMOM_LDS_GENES, nf)):
+            assert want_bb[g - 1] >= 40 and want_ab[g - 1] >= 21 and ((f == g) & (b == 0)).sum() >= 2
+    assert (nf + GMOM_LDS_GENES - 1) // GMOM_LDS_GENES == (16 if nf == LDS_LIMIT else 17)
+
+
 def test_census_of_the_device_fixtures():
     src = open(os.path.join(os.path.dirname(__file__), "..", "fastf_amd", "csrc", "gene_fidelity_kernels.hpp")).read()
     assert "GMOM_LDS_GENES = GENE_LDS_GENES / 2, GMOM_LDS_RANGES = 2 * GENE_LDS_RANGES" in src

@@ -14,6 +14,7 @@ from helpers import Case
 from oracle import oracle as O
 import cap_ref
 from test_gpu_sweep import _Edge, _write
+import test_cap_host as H
 
 pytestmark = pytest.mark.gpu
 
@@ -132,6 +133,26 @@ def test_cell_hits_with_lds_counters_at_the_budget(layout):
         d_h = torch.zeros(n_cells, dtype=torch.int32, device="cuda")
         eng.dev_cell_hits(len(cell), dev.blk_ptr, d_h.data_ptr())
         np.testing.assert_array_equal(hostmem.to_host(d_h).view(np.uint32).astype(np.int64), np.bincount(cell[cell > 0] - 1, minlength=n_cells))
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("n_cells", [H.CAP_LDS_CELLS * H.CAP_LDS_RANGES, H.CAP_LDS_CELLS * H.CAP_LDS_RANGES + 1])
+def test_cell_hits_at_the_last_lds_range(layout, n_cells, monkeypatch):
+    """262 144 cells: eight ranges, the most the LDS form takes; one cell more goes to the general form"""
+    monkeypatch.delenv("FASTF_CAP_LDS_RANGES", raising=False)
+    lists = _lists(n_cells)
+    eng = F.Engine.from_lists(lists, umi_max_bases=12)
+    import torch
+    try:
+        cell = H.last_range_cells(n_cells)
+        dev = _Dev(eng, lists, layout, cell)
+        d_h = torch.full((n_cells + 2,), 0x55555555, dtype=torch.int32, device="cuda")
+        eng.dev_cell_hits(len(cell), dev.blk_ptr, d_h.data_ptr())
+        torch.cuda.synchronize()
+        got = hostmem.to_host(d_h).view(np.uint32)
+        np.testing.assert_array_equal(got[:n_cells].astype(np.int64), np.bincount(cell[cell > 0] - 1, minlength=n_cells))
+        assert (got[n_cells:] == 0x55555555).all(), "entries behind the counters were written"
     finally:
         eng.close()
 

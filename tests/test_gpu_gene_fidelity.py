@@ -147,6 +147,19 @@ def test_gene_moments_without_sum_ab(eng, name, form, monkeypatch):
     assert _moments(eng, f, a, b, nf, want_ab=False)[1] == G.gene_sums(f, a, b, nf)[1]
 
 
+@pytest.mark.parametrize("want_ab", [True, False])
+@pytest.mark.parametrize("n_features", [H.LDS_LIMIT, H.LDS_LIMIT + 1])
+def test_gene_moments_at_the_last_lds_range(eng, n_features, want_ab, monkeypatch):
+    """131 072 genes: sixteen ranges, the most the LDS form takes; one gene more goes to the general form"""
+    monkeypatch.delenv("FASTF_GENE_MOMENTS_LDS_RANGES", raising=False)
+    f, a, b = H.last_range_fixture(n_features)
+    if n_features not in _MOMENT_REFS:
+        _MOMENT_REFS[n_features] = G.gene_sums(f, a, b, n_features)
+    want = _MOMENT_REFS[n_features]
+    got = _moments(eng, f, a, b, n_features, want_ab=want_ab)
+    assert got == want if want_ab else got[1] == want[1]
+
+
 def test_the_three_calls_give_the_seven_arrays_of_the_host_twin(eng):
     """partner counts, then the moments on (Y, x of y, y) and (X, x, x): what resident.c chains behind a point"""
     import torch
