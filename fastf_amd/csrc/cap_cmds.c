@@ -140,7 +140,7 @@ static int cap_plane(cap_pair_t *c, const res_pair_t *p)
 {
     const res_rate_t *S = p->S;
     return fastf_devmem_copy(c->d_thr, c->h_thr, (size_t)S->n_cells * 8) ||
-           fastf_dev_cell_decisions(S->e, p->R->n, S->blocked ? S->d_blk : NULL, p->seed, p->L->mt_skip, S->H, (const uint64_t *)c->d_thr, (uint32_t *)c->d_plane, NULL);
+           fastf_dev_cell_decisions(S->e, p->R->n, S->blocked ? S->buf.blk.p : NULL, p->seed, p->L->mt_skip, S->H, (const uint64_t *)c->d_thr, (uint32_t *)c->d_plane, NULL);
 }
 
 static int cap_pair_begin(const res_pair_t *p, void **ctx)
@@ -160,7 +160,7 @@ static int cap_pair_begin(const res_pair_t *p, void **ctx)
     if (!(c->d_hits = fastf_devmem_alloc(p->device, nc1 * 4)) || !(c->d_thr = fastf_devmem_alloc(p->device, nc1 * 8)) ||
         !(c->h_hits = (uint32_t *)fastf_pinned_alloc(nc1 * 4)) || !(c->h_thr = (uint64_t *)fastf_pinned_alloc(nc1 * 8)) ||
         !(c->d_plane = fastf_devmem_alloc(p->device, (size_t)plane_words * 4)) || fastf_devmem_zero(c->d_plane, (size_t)plane_words * 4)) return RES_FAIL;
-    if (fastf_dev_cell_hits(S->e, p->R->n, S->blocked ? S->d_blk : NULL, (uint32_t *)c->d_hits, NULL) || fastf_devmem_sync() ||
+    if (fastf_dev_cell_hits(S->e, p->R->n, S->blocked ? S->buf.blk.p : NULL, (uint32_t *)c->d_hits, NULL) || fastf_devmem_sync() ||
         fastf_devmem_copy(c->h_hits, c->d_hits, (size_t)n_cells * 4)) return RES_FAIL;
     uint64_t sum = 0;
     for (uint32_t k = 0; k < n_cells; k++) sum += c->h_hits[k];
@@ -193,7 +193,7 @@ static int cap_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const cha
 static int cap_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uint64_t counters[3], uint64_t nnz, char *row, size_t cap, double *metrics)
 {
     const res_rate_t *S = p->S;
-    return fastf_cap_row_(p->rate_cell, p->job->caps[j], p->seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, S->H,
+    return fastf_cap_row_(p->rate_cell, p->job->caps[j], p->seed, counters, nnz, S->buf.h_upc.u64[S->n_cells], S->buf.h_upc.u64, S->buf.h_gpc.u32, S->n_cells, S->H,
                           ((const cap_pair_t *)ctx)->capped, row, cap, metrics);
 }
 

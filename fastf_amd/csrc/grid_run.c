@@ -116,7 +116,7 @@ static int grid_pair(const res_verb_t *V, const res_pair_t *p, const uint64_t *c
         if (fastf_res_point_compare(S, name, T)) goto done;
         if (G->on && P->on) {                               /* (the point's per-gene array is still on the device) */
             tt = fastf_res_now();
-            if (fastf_res_reps_genes(P, S, j, k_seed, S->h_cpg, S->n_features)) goto done;
+            if (fastf_res_reps_genes(P, S, j, k_seed, S->buf.h_cpg.u32, S->n_features)) goto done;
             T->reps += fastf_res_now() - tt;
         }
         if (!p->summary_only) {
@@ -128,15 +128,15 @@ static int grid_pair(const res_verb_t *V, const res_pair_t *p, const uint64_t *c
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
-            if (fastf_genes_summary_row(p->rate_cell, rd, lv, p->seed, S->h_cpg, S->h_upg, S->n_features, grow, sizeof grow) ||
-                fastf_res_genes_point(G, p->L, name, p->summary_only ? NULL : dir, grow, S->h_cpg, S->h_upg)) goto done;
+            if (fastf_genes_summary_row(p->rate_cell, rd, lv, p->seed, S->buf.h_cpg.u32, S->buf.h_upg.u64, S->n_features, grow, sizeof grow) ||
+                fastf_res_genes_point(G, p->L, name, p->summary_only ? NULL : dir, grow, S->buf.h_cpg.u32, S->buf.h_upg.u64)) goto done;
             T->genes += fastf_res_now() - tt;
         }
         if (C->on) {                                        /* (behind the point's rows: K3u overwrites the regions they were gathered from) */
             char crow[1024];
             if (fastf_res_point_cells(S, name, T)) goto done;
             tt = fastf_res_now();
-            if (fastf_cells_summary_row(p->rate_cell, rd, lv, p->seed, S->h_rpc, S->h_npc, S->h_spc, S->n_cells, S->h_hist, crow, sizeof crow) ||
+            if (fastf_cells_summary_row(p->rate_cell, rd, lv, p->seed, S->h_cs.rpc, S->h_cs.npc, S->h_cs.spc, S->n_cells, S->h_cs.hist, crow, sizeof crow) ||
                 fastf_res_cells_point(C, S, p->summary_only ? NULL : dir, crow)) goto done;
             T->cells += fastf_res_now() - tt;
         }
@@ -171,9 +171,9 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
     for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = job->rates_cell[i]; pair_seed[i * n_s + k] = job->seeds[k]; }
     if ((rc = fastf_res_lists_load(job->barcodes, job->features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
-    S.max_cells = fastf_res_lists_max_cells(&LL);
-    S.fidelity = Fd->on; S.gene_fid = Fd->gene_on; S.neighbors = Fd->nbr_on || Fd->lab_on; S.labels = Fd->lab_on; S.lab_t = Fd->labels; S.markers = Fd->markers;
-    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.no_reuse = nr && nr[0] == '1'; }
+    S.cfg.max_cells = fastf_res_lists_max_cells(&LL);
+    S.cfg.fidelity = Fd->on; S.cfg.gene_fid = Fd->gene_on; S.cfg.neighbors = Fd->nbr_on || Fd->lab_on; S.cfg.labels = Fd->lab_on; S.cfg.lab_t = Fd->labels; S.cfg.markers = Fd->markers;
+    {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.cfg.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode(V->name, job->bam, &LL.L[0], device, &R)) goto done;
     T.decode = fastf_res_now() - tt;

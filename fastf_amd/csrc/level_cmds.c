@@ -97,7 +97,7 @@ static int write_thresholds(const char *dir, const fastf_lists_t *L, uint32_t n_
 /* the verb (resident.h: res_verb_t; the driver: grid_run.c)           */
 /* ------------------------------------------------------------------ */
 #define LEVEL_MAX_PASSES 32u                             /* hi - lo halves per probing pass, from 2^32 */
-/* what a (cell rate, seed) pair keeps: ONE plane, made again for every pass; the state of the search (on the device: S->d_lo ..);
+/* what a (cell rate, seed) pair keeps: ONE plane, made again for every pass; the state of the search (on the device: S->lv.lo ..);
  * of the point in work its probing passes and where the clocks stood before them */
 typedef struct { void *d_plane; uint64_t *h_thr, *h_ufull; uint64_t open, capped; uint32_t passes; double search0, device0; } level_pair_t;
 
@@ -115,7 +115,7 @@ static void level_pair_end(void *ctx)
 static int level_plane(level_pair_t *c, const res_pair_t *p, const uint64_t *thr)
 {
     const res_rate_t *S = p->S;
-    return fastf_dev_cell_decisions(S->e, p->R->n, S->blocked ? S->d_blk : NULL, p->seed, p->L->mt_skip, S->H, thr, (uint32_t *)c->d_plane, NULL);
+    return fastf_dev_cell_decisions(S->e, p->R->n, S->blocked ? S->buf.blk.p : NULL, p->seed, p->L->mt_skip, S->H, thr, (uint32_t *)c->d_plane, NULL);
 }
 
 static int level_pair_begin(const res_pair_t *p, void **ctx)
@@ -136,13 +136,13 @@ static int level_pair_begin(const res_pair_t *p, void **ctx)
     /* pass 0: every hit kept.  U_k(2^32) stays on the device for every cap of the list; the state of the first cap comes with it */
     tt = fastf_res_now();
     for (uint32_t k = 0; k < n_cells; k++) c->h_thr[k] = (uint64_t)1 << 32;
-    if (fastf_devmem_copy(S->d_probe, c->h_thr, (size_t)n_cells * 8) || level_plane(c, p, S->d_probe)) return RES_FAIL;
+    if (fastf_devmem_copy(S->lv.probe, c->h_thr, (size_t)n_cells * 8) || level_plane(c, p, S->lv.probe)) return RES_FAIL;
     T->search += fastf_res_now() - tt;
     char name0[64]; snprintf(name0, sizeof name0, "c%.3f (every hit)", (double)p->rate_cell);
     const int prc = fastf_res_search_pass(S, (const uint32_t *)c->d_plane, name0, p->job->caps[0], 1, &c->open, &c->capped, T);
     if (prc != RES_OK) return prc;
     if (fastf_res_full_keep(S, T)) return RES_FAIL;         /* --fidelity: pass 0's rows are the full rows of the pair */
-    if (c->h_ufull && fastf_devmem_copy(c->h_ufull, S->d_ufull, (size_t)n_cells * 8)) return RES_FAIL;
+    if (c->h_ufull && fastf_devmem_copy(c->h_ufull, S->lv.ufull, (size_t)n_cells * 8)) return RES_FAIL;
     return RES_OK;
 }
 
@@ -158,7 +158,7 @@ static int level_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const c
         if (c->passes == LEVEL_MAX_PASSES)
             return lv_err("internal error: %llu cells still open after %u passes at point %s", (unsigned long long)c->open, c->passes, point_name);
         const double tt = fastf_res_now();
-        if (level_plane(c, p, S->d_probe)) return RES_FAIL;
+        if (level_plane(c, p, S->lv.probe)) return RES_FAIL;
         T->search += fastf_res_now() - tt;
         const int prc = fastf_res_search_pass(S, (const uint32_t *)c->d_plane, point_name, umi_cap, 0, &c->open, NULL, T);
         if (prc != RES_OK) return prc;
@@ -166,7 +166,7 @@ static int level_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const c
     }
     /* the point: T = lo */
     const double tt = fastf_res_now();
-    if (level_plane(c, p, S->d_lo)) return RES_FAIL;
+    if (level_plane(c, p, S->lv.lo)) return RES_FAIL;
     T->planes += fastf_res_now() - tt;
     *d_plane = (const uint32_t *)c->d_plane;
     return RES_OK;
@@ -181,7 +181,7 @@ static void level_point_done(void *ctx, const res_pair_t *p, const char *point_n
 static int level_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uint64_t counters[3], uint64_t nnz, char *row, size_t cap, double *metrics)
 {
     const res_rate_t *S = p->S;
-    return fastf_cap_row_(p->rate_cell, p->job->caps[j], p->seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, S->H,
+    return fastf_cap_row_(p->rate_cell, p->job->caps[j], p->seed, counters, nnz, S->buf.h_upc.u64[S->n_cells], S->buf.h_upc.u64, S->buf.h_gpc.u32, S->n_cells, S->H,
                           (uint32_t)((const level_pair_t *)ctx)->capped, row, cap, metrics);
 }
 
@@ -190,7 +190,7 @@ static int level_point_files(void *ctx, const res_pair_t *p, const char *dir)
     level_pair_t *c = (level_pair_t *)ctx;
     const res_rate_t *S = p->S;
     const double tt = fastf_res_now();
-    if (fastf_devmem_copy(c->h_thr, S->d_lo, (size_t)S->n_cells * 8) || write_thresholds(dir, p->L, S->n_cells, c->h_thr, c->h_ufull, S->h_upc)) return 1;
+    if (fastf_devmem_copy(c->h_thr, S->lv.lo, (size_t)S->n_cells * 8) || write_thresholds(dir, p->L, S->n_cells, c->h_thr, c->h_ufull, S->buf.h_upc.u64)) return 1;
     p->T->write += fastf_res_now() - tt;
     return 0;
 }

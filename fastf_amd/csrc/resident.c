@@ -140,61 +140,52 @@ done:
 /* ------------------------------------------------------------------ */
 /* one cell rate                                                       */
 /* ------------------------------------------------------------------ */
+static void res_buf_free(res_buf_t *b)
+{
+    if (b->kind == RES_DEV) fastf_devmem_free(b->p);
+    else if (b->kind == RES_PIN) { if (b->p) fastf_pinned_free(b->p); }
+    else free(b->p);
+    memset(b, 0, sizeof *b);
+}
 void fastf_res_rate_close(res_rate_t *S)
 {
+    const res_cfg_t cfg = S->cfg;                           /* (the caller's: it outlives the pairs) */
     if (S->e) fastf_engine_destroy(S->e);
-    fastf_devmem_free(S->d_blk); fastf_devmem_free(S->d_keys); fastf_devmem_free(S->d_tmp); fastf_devmem_free(S->d_small);
-    fastf_devmem_free(S->d_rows); fastf_devmem_free(S->d_upc); fastf_devmem_free(S->d_gpc);
-    if (S->h_small) fastf_pinned_free(S->h_small);
-    if (S->h_upc) fastf_pinned_free(S->h_upc);
-    if (S->h_gpc) fastf_pinned_free(S->h_gpc);
-    if (S->h_rows) fastf_pinned_free(S->h_rows);
-    fastf_devmem_free(S->d_cpg); fastf_devmem_free(S->d_upg);
-    if (S->h_cpg) fastf_pinned_free(S->h_cpg);
-    if (S->h_upg) fastf_pinned_free(S->h_upg);
-    fastf_devmem_free(S->d_cellsum);
-    if (S->h_hist) fastf_pinned_free(S->h_hist);
-    fastf_devmem_free(S->d_level);
-    fastf_devmem_free(S->d_full); fastf_devmem_free(S->d_fid);
-    if (S->h_fid) fastf_pinned_free(S->h_fid);
-    fastf_devmem_free(S->d_gx); fastf_devmem_free(S->d_gfid);
-    if (S->h_gfid) fastf_pinned_free(S->h_gfid);
-    fastf_devmem_free(S->d_nplanes); fastf_devmem_free(S->d_nbr);
-    if (S->h_nbr) fastf_pinned_free(S->h_nbr);
-    fastf_devmem_free(S->d_lab);
-    if (S->h_lab) fastf_pinned_free(S->h_lab);
-    fastf_devmem_free(S->d_mk);
-    if (S->h_mk) fastf_pinned_free(S->h_mk);
-    free(S->mk_rank);
+    for (res_buf_t *b = (res_buf_t *)&S->buf, *const end = b + sizeof S->buf / sizeof *b; b < end; b++) res_buf_free(b);
     memset(S, 0, sizeof *S);
+    S->cfg = cfg;
 }
 
 /* room of at least `need` bytes in a buffer that outlives the pair: what is there is kept when it is large enough */
-static int dev_room(void **p, size_t *have, size_t need, int device)
+static int res_room(res_buf_t *b, int kind, size_t need, int device)
 {
-    if (*p && *have >= need) return 0;
-    fastf_devmem_free(*p); *p = NULL; *have = 0;
-    if (!(*p = fastf_devmem_alloc(device, need))) return 1;
-    *have = need;
+    if (b->p && b->have >= need) return 0;
+    res_buf_free(b);
+    b->p = kind == RES_DEV ? fastf_devmem_alloc(device, need) : kind == RES_PIN ? fastf_pinned_alloc(need) : malloc(need ? need : 1);
+    if (!b->p) return 1;
+    b->kind = kind; b->have = need;
     return 0;
 }
-static int pin_room(void **p, size_t *have, size_t need)
+/* the same for a carved block of `bytes` for n entries per array: a block that stays is carved by the n it was allocated for */
+static int res_block_room(res_buf_t *b, int kind, size_t bytes, size_t n, int device)
 {
-    if (*p && *have >= need) return 0;
-    if (*p) fastf_pinned_free(*p);
-    *p = NULL; *have = 0;
-    if (!(*p = fastf_pinned_alloc(need))) return 1;
-    *have = need;
+    if (res_room(b, kind, bytes, device)) return 1;
+    if (!b->n) b->n = n;                                    /* (allocated just now: res_buf_free cleared it) */
     return 0;
+}
+static int no_room(const res_rate_t *S, const char *what, size_t bytes)
+{
+    rs_err("%s: %s of cell rate %.3f do not fit: %zu bytes (%s)", S->verb, what, (double)S->rate_cell, bytes, fastf_last_error());
+    return RES_FAIL;
 }
 
-/* S: zeroed before the first open of a run, or as the open of the pair before left it (resident.h).  On anything but RES_OK the
- * caller still calls fastf_res_rate_close */
+/* S: zeroed before the first open of a run but for S->cfg, or as the open of the pair before left it (resident.h).  On anything but
+ * RES_OK the caller still calls fastf_res_rate_close */
 int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
                         uint32_t seed, int device, int genes, int cells, res_times_t *T)
 {
     if (S->e) { fastf_engine_destroy(S->e); S->e = NULL; }     /* (the pair before: its buffers stay) */
-    if (S->no_reuse) { const uint32_t mc = S->max_cells; const int fid = S->fidelity, gf = S->gene_fid, nb = S->neighbors, lb = S->labels; const uint32_t mk = S->markers; const fastf_labels_t *const lt = S->lab_t; fastf_res_rate_close(S); S->markers = mk; S->no_reuse = 1; S->max_cells = mc; S->fidelity = fid; S->gene_fid = gf; S->neighbors = nb; S->labels = lb; S->lab_t = lt; }
+    if (S->cfg.no_reuse) fastf_res_rate_close(S);
     S->sorted = S->sorted_other = NULL; S->sorted_full = 0; S->H = 0;
     T->opens++;
     S->genes = genes; S->n_features = (uint32_t)L->n_features; S->cells = cells;
@@ -203,20 +194,20 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
     const uint32_t n_cells = S->n_cells = (uint32_t)L->n_cells;
     double tt = fastf_res_now();
 
-    fastf_engine_config_t cfg; memset(&cfg, 0, sizeof cfg);
-    cfg.cell_keys = cell_keys; cfg.n_cells = n_cells;
-    cfg.feature_keys = L->feature_key; cfg.n_features = (uint32_t)L->n_features;
-    cfg.draw_threshold = fastf_draw_threshold(1.0f);        /* (no part in the planes: every point brings its own threshold) */
-    cfg.mt_seed = seed; cfg.mt_skip = L->mt_skip;
-    cfg.n_shards = 1; cfg.device = device;
-    cfg.batch_records = (uint64_t)1 << 16;                  /* (the push path is not used) */
+    fastf_engine_config_t ec; memset(&ec, 0, sizeof ec);
+    ec.cell_keys = cell_keys; ec.n_cells = n_cells;
+    ec.feature_keys = L->feature_key; ec.n_features = (uint32_t)L->n_features;
+    ec.draw_threshold = fastf_draw_threshold(1.0f);        /* (no part in the planes: every point brings its own threshold) */
+    ec.mt_seed = seed; ec.mt_skip = L->mt_skip;
+    ec.n_shards = 1; ec.device = device;
+    ec.batch_records = (uint64_t)1 << 16;                  /* (the push path is not used) */
     {   /* the UMI field as bam2db chooses it */
         const char *ul = getenv("FASTF_UMI_MAX_BASES");
-        const uint32_t group_bits = bits_for(cfg.n_cells) + bits_for(cfg.n_features);
-        cfg.umi_max_bases = ul ? (uint32_t)atoi(ul) : ((group_bits + 36 <= 64 || group_bits + 27 > 64) ? 16 : 12);
+        const uint32_t group_bits = bits_for(ec.n_cells) + bits_for(ec.n_features);
+        ec.umi_max_bases = ul ? (uint32_t)atoi(ul) : ((group_bits + 36 <= 64 || group_bits + 27 > 64) ? 16 : 12);
     }
-    if (cfg.umi_max_bases > 16) return RES_NOT_COVERED;
-    if (fastf_engine_create(&cfg, &S->e)) return RES_FAIL;
+    if (ec.umi_max_bases > 16) return RES_NOT_COVERED;
+    if (fastf_engine_create(&ec, &S->e)) return RES_FAIL;
     if (fastf_engine_is_wide(S->e)) return RES_NOT_COVERED;
     T->engine += fastf_res_now() - tt; tt = fastf_res_now();
 
@@ -231,106 +222,72 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
     if (fastf_dev_block_layout(S->e, N, &layout)) return RES_FAIL;
     /* room for the run's widest pair: its cells in the per-cell arrays, and a 32-bit cell scratch in the blocked runs where a later
      * pair samples more than 65535 cells while this one has the 16-bit scratch (2 bytes more for each of a unit's 256 records) */
-    const size_t room_cells = (S->max_cells > n_cells ? S->max_cells : n_cells) + (size_t)1;
-    const size_t blk_room = blk_bytes + ((S->max_cells > 65535u && n_cells <= 65535u) ? ((N + 255) / 256) * 512 : 0);
-    if (S->blocked && (!S->d_blk || S->have.blk < blk_bytes)) S->blk_layout = 0;      /* (a new buffer holds no copy) */
-    if ((!S->d_small && !(S->d_small = fastf_devmem_alloc(device, SM_WORDS_ * 8))) || (!S->h_small && !(S->h_small = (uint64_t *)fastf_pinned_alloc(SM_WORDS_ * 8))) ||
-        (S->blocked && dev_room(&S->d_blk, &S->have.blk, (S->d_blk && S->have.blk >= blk_bytes) ? blk_bytes : blk_room, device)) ||
-        dev_room(&S->d_keys, &S->have.keys, S->key_slots * 8, device) || dev_room(&S->d_tmp, &S->have.tmp, S->key_slots * 8, device) ||
-        dev_room(&S->d_rows, &S->have.rows, (N ? N : 1) * 12, device) ||
-        dev_room(&S->d_upc, &S->have.upc, room_cells * 8, device) || dev_room(&S->d_gpc, &S->have.gpc, room_cells * 4, device) ||
-        pin_room((void **)&S->h_upc, &S->have.h_upc, room_cells * 8) || pin_room((void **)&S->h_gpc, &S->have.h_gpc, room_cells * 4)) {
+    const size_t room_cells = (S->cfg.max_cells > n_cells ? S->cfg.max_cells : n_cells) + (size_t)1;
+    const size_t blk_room = blk_bytes + ((S->cfg.max_cells > 65535u && n_cells <= 65535u) ? ((N + 255) / 256) * 512 : 0);
+    const int blk_fits = S->buf.blk.p && S->buf.blk.have >= blk_bytes;
+    if (S->blocked && !blk_fits) S->blk_layout = 0;         /* (a new buffer holds no copy) */
+    if (res_room(&S->buf.small, RES_DEV, SM_WORDS_ * 8, device) || res_room(&S->buf.h_small, RES_PIN, SM_WORDS_ * 8, device) ||
+        (S->blocked && res_room(&S->buf.blk, RES_DEV, blk_fits ? blk_bytes : blk_room, device)) ||
+        res_room(&S->buf.keys, RES_DEV, S->key_slots * 8, device) || res_room(&S->buf.tmp, RES_DEV, S->key_slots * 8, device) ||
+        res_room(&S->buf.rows, RES_DEV, (N ? N : 1) * 12, device) ||
+        res_room(&S->buf.upc, RES_DEV, room_cells * 8, device) || res_room(&S->buf.gpc, RES_DEV, room_cells * 4, device) ||
+        res_room(&S->buf.h_upc, RES_PIN, room_cells * 8, device) || res_room(&S->buf.h_gpc, RES_PIN, room_cells * 4, device)) {
         rs_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
         return RES_FAIL;
     }
     if (genes) {                                            /* the per-gene arrays of a point and their pinned host copies, once */
         const size_t nf1 = (size_t)S->n_features + 1;
-        if (dev_room(&S->d_cpg, &S->have.cpg, nf1 * 4, device) || dev_room(&S->d_upg, &S->have.upg, nf1 * 8, device) ||
-            pin_room((void **)&S->h_cpg, &S->have.h_cpg, nf1 * 4) || pin_room((void **)&S->h_upg, &S->have.h_upg, nf1 * 8)) {
-            rs_err("%s: the per-gene arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, nf1 * 12, fastf_last_error());
-            return RES_FAIL;
-        }
+        if (res_room(&S->buf.cpg, RES_DEV, nf1 * 4, device) || res_room(&S->buf.upg, RES_DEV, nf1 * 8, device) ||
+            res_room(&S->buf.h_cpg, RES_PIN, nf1 * 4, device) || res_room(&S->buf.h_upg, RES_PIN, nf1 * 8, device)) return no_room(S, "the per-gene arrays", nf1 * 12);
     }
     if (cells) {                                            /* the histogram and the three per-cell arrays of a point and their pinned host copy, once */
-        const size_t bytes = RES_CELLS_HIST_BYTES + (size_t)n_cells * 12;
-        const size_t room = RES_CELLS_HIST_BYTES + (room_cells - 1) * 12;
-        if (dev_room(&S->d_cellsum, &S->have.cellsum, room, device) || pin_room((void **)&S->h_hist, &S->have.h_hist, room)) {
-            rs_err("%s: the per-cell arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, bytes, fastf_last_error());
-            return RES_FAIL;
-        }
-        S->h_rpc = (uint32_t *)((char *)S->h_hist + RES_CELLS_HIST_BYTES); S->h_npc = S->h_rpc + n_cells; S->h_spc = S->h_npc + n_cells;
+        const size_t room = res_cellsum_layout(NULL, room_cells - 1).bytes;
+        if (res_room(&S->buf.cellsum, RES_DEV, room, device) || res_room(&S->buf.h_cellsum, RES_PIN, room, device))
+            return no_room(S, "the per-cell arrays", res_cellsum_layout(NULL, n_cells).bytes);
+        S->h_cs = res_cellsum_layout(S->buf.h_cellsum.p, n_cells);
     }
-    if ((S->gene_fid || S->neighbors) && !S->fidelity) {    /* the full rows of the pair, for --gene-fidelity or --neighbors alone */
-        if (dev_room(&S->d_full, &S->have.full, (N ? N : 1) * 12, device)) {
-            rs_err("%s: the full-depth rows of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 12), fastf_last_error());
-            return RES_FAIL;
-        }
+    if ((S->cfg.gene_fid || S->cfg.neighbors) && !S->cfg.fidelity) {    /* the full rows of the pair, for --gene-fidelity or --neighbors alone */
+        if (res_room(&S->buf.full, RES_DEV, (N ? N : 1) * 12, device)) return no_room(S, "the full-depth rows", (size_t)(N * 12));
         S->full_nnz = 0;
     }
-    if (S->gene_fid || S->neighbors) {                      /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once (--neighbors alone: the pair's sums, which rank A) */
-        const size_t nf1 = (size_t)S->n_features + 1, dev_bytes = nf1 * 48, pin_bytes = nf1 * 48;
-        if ((S->gene_fid && dev_room(&S->d_gx, &S->have.gx, (N ? N : 1) * 4, device)) || dev_room(&S->d_gfid, &S->have.gfid, dev_bytes, device) ||
-            pin_room((void **)&S->h_gfid, &S->have.h_gfid, pin_bytes)) {
-            rs_err("%s: the partner column and the per-gene sums of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 4 + dev_bytes), fastf_last_error());
-            return RES_FAIL;
-        }
-        S->gfid_stride = S->have.gfid / 48;
-        const size_t hs = S->have.h_gfid / 48;              /* (entries per array, of the block as it was allocated) */
-        S->h_gsx = S->h_gfid; S->h_gsxx = S->h_gsx + hs; S->h_gsy = S->h_gsxx + hs; S->h_gsyy = S->h_gsy + hs; S->h_gsxy = S->h_gsyy + hs;
-        S->h_gcf = (uint32_t *)(S->h_gsxy + hs); S->h_gc = S->h_gcf + hs;
-        if (genes) { S->h_gsy = S->h_upg; S->h_gc = S->h_cpg; }      /* (the point's own two are --genes') */
+    if (S->cfg.gene_fid || S->cfg.neighbors) {              /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once (--neighbors alone: the pair's sums, which rank A) */
+        const size_t nf1 = (size_t)S->n_features + 1, bytes = res_gfid_layout(NULL, nf1).bytes;
+        if ((S->cfg.gene_fid && res_room(&S->buf.gx, RES_DEV, (N ? N : 1) * 4, device)) || res_block_room(&S->buf.gfid, RES_DEV, bytes, nf1, device) ||
+            res_block_room(&S->buf.h_gfid, RES_PIN, bytes, nf1, device)) return no_room(S, "the partner column and the per-gene sums", (size_t)(N * 4 + bytes));
+        S->d_gfid = res_gfid_layout(S->buf.gfid.p, S->buf.gfid.n); S->h_gfid = res_gfid_layout(S->buf.h_gfid.p, S->buf.h_gfid.n);
+        if (genes) { S->h_gfid.sy = S->buf.h_upg.u64; S->h_gfid.c = S->buf.h_cpg.u32; }      /* (the point's own two are --genes') */
     }
-    if (S->neighbors) {                                     /* the slot map of A, both neighbour sets, their counts, the norms and the shared counts; pinned: the map, k_full, k_point, shared.  The planes wait for P (fastf_res_full_keep) */
-        const size_t nc = room_cells, k = FASTF_NEIGHBORS_K, map_bytes = (((size_t)S->n_features + 1) * 2 + 7) & ~(size_t)7;
-        const size_t dev_bytes = map_bytes + nc * (2 * k * 4 + 3 * 4 + 8), pin_bytes = map_bytes + nc * 12 + FASTF_HVG_TOP * 4;
-        if (dev_room(&S->d_nbr, &S->have.nbr, dev_bytes, device) || pin_room((void **)&S->h_nbr, &S->have.h_nbr, pin_bytes)) {
-            rs_err("%s: the neighbour sets of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, dev_bytes, fastf_last_error());
-            return RES_FAIL;
-        }
-        S->nbr_cells = nc; S->nbr_map_bytes = map_bytes;
-        S->h_nkf = (uint32_t *)((char *)S->h_nbr + map_bytes); S->h_nkp = S->h_nkf + nc; S->h_nsh = S->h_nkp + nc; S->h_ngenes = S->h_nsh + nc;
+    if (S->cfg.neighbors) {                                 /* the device and the pinned block of the neighbour sets.  The planes wait for P (fastf_res_full_keep) */
+        const size_t nc = room_cells, map_bytes = S->nbr_map_bytes = res_nbr_map_bytes(S->n_features);
+        const size_t dev_bytes = res_nbr_layout(NULL, map_bytes, FASTF_NEIGHBORS_K, nc).bytes;
+        if (res_room(&S->buf.nbr, RES_DEV, dev_bytes, device) || res_room(&S->buf.h_nbr, RES_PIN, res_nbr_pin_layout(NULL, map_bytes, nc, FASTF_HVG_TOP).bytes, device))
+            return no_room(S, "the neighbour sets", dev_bytes);
+        S->d_nbr = res_nbr_layout(S->buf.nbr.p, map_bytes, FASTF_NEIGHBORS_K, nc); S->h_nbr = res_nbr_pin_layout(S->buf.h_nbr.p, map_bytes, nc, FASTF_HVG_TOP);
         S->hvg_k = 0; S->nbr_planes = 0;
     }
-    if (S->labels) {                                        /* lab[] of the pair's cells, the votes of the full rows and of a point, the two conf matrices and their pinned copy; lab[] goes up once per pair */
-        S->n_labels = fastf_labels_count(S->lab_t);
-        S->lab_cells = (room_cells + 3) & ~(size_t)3;
-        const size_t bytes = S->lab_cells + 2 * res_lab_half(S);
-        if (dev_room(&S->d_lab, &S->have.lab, bytes, device) || pin_room((void **)&S->h_lab, &S->have.h_lab, bytes)) {
-            rs_err("%s: the label arrays of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, bytes, fastf_last_error());
-            return RES_FAIL;
-        }
+    if (S->cfg.labels) {                                    /* the label block and its pinned copy; lab[] goes up once per pair */
+        S->n_labels = fastf_labels_count(S->cfg.lab_t);
+        const size_t lab_cells = res_lab_cells(room_cells), bytes = res_lab_layout(NULL, lab_cells, S->n_labels).bytes;
+        if (res_room(&S->buf.lab, RES_DEV, bytes, device) || res_room(&S->buf.h_lab, RES_PIN, bytes, device)) return no_room(S, "the label arrays", bytes);
+        S->d_lab = res_lab_layout(S->buf.lab.p, lab_cells, S->n_labels); S->h_lab = res_lab_layout(S->buf.h_lab.p, lab_cells, S->n_labels);
         const double tl = fastf_res_now();
-        if (fastf_labels_assign(S->lab_t, L->barcode, n_cells, S->h_lab) || (n_cells && fastf_devmem_copy(S->d_lab, S->h_lab, n_cells))) return RES_FAIL;
+        if (fastf_labels_assign(S->cfg.lab_t, L->barcode, n_cells, S->h_lab.lab) || (n_cells && fastf_devmem_copy(S->d_lab.lab, S->h_lab.lab, n_cells))) return RES_FAIL;
         T->labels += fastf_res_now() - tl;
     }
-    if (S->markers) {                                       /* the four tables of one row set on the device, of both row sets pinned, and the two rank tables */
-        S->mk_set = (res_mk_bytes(S->n_labels, FASTF_HVG_TOP) + 7) & ~(size_t)7;
-        const size_t rank_bytes = 2 * (size_t)S->n_labels * FASTF_HVG_TOP * sizeof *S->mk_rank;
-        if (dev_room(&S->d_mk, &S->have.mk, S->mk_set, device) || pin_room((void **)&S->h_mk, &S->have.h_mk, 2 * S->mk_set)) {
-            rs_err("%s: the marker tables of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, S->mk_set, fastf_last_error());
-            return RES_FAIL;
-        }
-        if (S->have.mk_rank < rank_bytes) {
-            free(S->mk_rank);
-            S->have.mk_rank = 0;
-            if (!(S->mk_rank = (uint32_t *)malloc(rank_bytes ? rank_bytes : 1))) { rs_err("%s: out of memory", verb); return RES_FAIL; }
-            S->have.mk_rank = rank_bytes;
-        }
+    if (S->cfg.markers) {                                   /* the four tables of one row set on the device, of both row sets pinned, and the two rank tables */
+        S->mk_set = res_mk_set_bytes(S->n_labels, FASTF_HVG_TOP);
+        if (res_room(&S->buf.mk, RES_DEV, S->mk_set, device) || res_room(&S->buf.h_mk, RES_PIN, 2 * S->mk_set, device)) return no_room(S, "the marker tables", S->mk_set);
+        if (res_room(&S->buf.mk_rank, RES_HOST, 2 * (size_t)S->n_labels * FASTF_HVG_TOP * sizeof(uint32_t), device)) { rs_err("%s: out of memory", verb); return RES_FAIL; }
     }
-    if (S->fidelity) {                                      /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
-        const size_t dev_bytes = room_cells * 24, pin_bytes = room_cells * 36;
-        if (dev_room(&S->d_full, &S->have.full, (N ? N : 1) * 12, device) || dev_room(&S->d_fid, &S->have.fid, dev_bytes, device) ||
-            pin_room((void **)&S->h_fid, &S->have.h_fid, pin_bytes)) {
-            rs_err("%s: the full-depth rows of cell rate %.3f do not fit: %zu bytes (%s)", verb, (double)rate_cell, (size_t)(N * 12 + dev_bytes), fastf_last_error());
-            return RES_FAIL;
-        }
-        S->fid_stride = S->have.fid / 24;
-        const size_t hs = S->have.h_fid / 36;               /* (entries per array, of the block as it was allocated) */
-        S->h_sxy = S->h_fid; S->h_syy = S->h_sxy + hs; S->h_sxx = S->h_syy + hs; S->h_ufull = S->h_sxx + hs; S->h_gfull = (uint32_t *)(S->h_ufull + hs);
+    if (S->cfg.fidelity) {                                  /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
+        const size_t dev_bytes = res_fid_layout(NULL, room_cells, 0).bytes;
+        if (res_room(&S->buf.full, RES_DEV, (N ? N : 1) * 12, device) || res_block_room(&S->buf.fid, RES_DEV, dev_bytes, room_cells, device) ||
+            res_block_room(&S->buf.h_fid, RES_PIN, res_fid_layout(NULL, room_cells, 1).bytes, room_cells, device)) return no_room(S, "the full-depth rows", (size_t)(N * 12 + dev_bytes));
+        S->d_fid = res_fid_layout(S->buf.fid.p, S->buf.fid.n, 0); S->h_fid = res_fid_layout(S->buf.h_fid.p, S->buf.h_fid.n, 1);
         S->full_nnz = 0;
     }
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    if (fastf_devmem_zero(S->d_small, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
+    uint64_t *const sm = S->buf.small.u64;
+    if (fastf_devmem_zero(S->buf.small.p, SM_WORDS_ * 8) || fastf_dev_reserve(S->e, S->blocked ? 0 : N, N)) return RES_FAIL;
 
     /* the records into the engine's layout, K1a once: the cell scratch and the hit count serve every point */
     if (S->blocked) {
@@ -338,14 +295,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
          * otherwise K1a alone, which fills the cell scratch slices of every unit */
         if (layout != S->blk_layout || !layout) {
             S->blk_layout = 0;
-            if (fastf_dev_block_records(S->e, R->gx, R->umi, R->meta, N, S->d_blk, NULL)) return RES_FAIL;
+            if (fastf_dev_block_records(S->e, R->gx, R->umi, R->meta, N, S->buf.blk.p, NULL)) return RES_FAIL;
             S->blk_layout = layout;
             T->relays++;
         }
-        if (fastf_dev_count_hits_blocked(S->e, R->cb, N, S->d_blk, sm + SM_HITS, NULL)) return RES_FAIL;
+        if (fastf_dev_count_hits_blocked(S->e, R->cb, N, S->buf.blk.p, sm + SM_HITS, NULL)) return RES_FAIL;
     } else if (fastf_dev_count_hits(S->e, R->cb, N, sm + SM_HITS, NULL)) return RES_FAIL;
-    if (fastf_devmem_sync() || fastf_devmem_copy(S->h_small, S->d_small, SM_WORDS_ * 8)) return RES_FAIL;
-    S->H = S->h_small[SM_HITS];
+    if (fastf_devmem_sync() || fastf_devmem_copy(S->buf.h_small.u64, S->buf.small.p, SM_WORDS_ * 8)) return RES_FAIL;
+    S->H = S->buf.h_small.u64[SM_HITS];
     T->block_k1a += fastf_res_now() - tt;
     return RES_OK;
 }
@@ -359,13 +316,13 @@ static int point_sort_reduce_(res_rate_t *S, const uint32_t *d_plane, uint64_t *
     const resident_t *R = S->R;
     const uint64_t N = R->n;
     fastf_engine_t *e = S->e;
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    if (fastf_devmem_zero(S->d_small, SM_HITS * 8)) return RES_FAIL;
-    if (fastf_dev_probe_pack(e, R->cb, S->blocked ? (const uint64_t *)S->d_blk : R->gx, R->umi, R->meta, N, d_plane, S->H, sm + SM_BASE,
-                             (uint64_t *)S->d_keys, S->key_slots, sm + SM_KEYS, sm + SM_CNT, S->kflags, NULL)) return RES_FAIL;
+    uint64_t *const sm = S->buf.small.u64;
+    if (fastf_devmem_zero(S->buf.small.p, SM_HITS * 8)) return RES_FAIL;
+    if (fastf_dev_probe_pack(e, R->cb, S->blocked ? S->buf.blk.u64 : R->gx, R->umi, R->meta, N, d_plane, S->H, sm + SM_BASE,
+                             S->buf.keys.u64, S->key_slots, sm + SM_KEYS, sm + SM_CNT, S->kflags, NULL)) return RES_FAIL;
     int in_tmp = 0;
-    if (fastf_dev_sort(e, (uint64_t *)S->d_keys, (uint64_t *)S->d_tmp, sm + SM_KEYS, N, S->key_bits, FASTF_SORT_SKIP_LOW | (S->segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) return RES_FAIL;
-    uint64_t *src = in_tmp ? (uint64_t *)S->d_tmp : (uint64_t *)S->d_keys, *other = in_tmp ? (uint64_t *)S->d_keys : (uint64_t *)S->d_tmp;
+    if (fastf_dev_sort(e, S->buf.keys.u64, S->buf.tmp.u64, sm + SM_KEYS, N, S->key_bits, FASTF_SORT_SKIP_LOW | (S->segmented ? FASTF_SORT_SEGMENTED : 0), &in_tmp, NULL)) return RES_FAIL;
+    uint64_t *src = in_tmp ? S->buf.tmp.u64 : S->buf.keys.u64, *other = in_tmp ? S->buf.keys.u64 : S->buf.tmp.u64;
     if (fastf_dev_reduce(e, src, sm + SM_KEYS, N, NULL, NULL, NULL, sm + SM_NNZ, FASTF_SORT_SKIP_LOW | FASTF_REDUCE_SEGMENTED, NULL)) return RES_FAIL;
     *src_out = src; *other_out = other;
     return RES_OK;
@@ -376,7 +333,7 @@ static int point_full_again_(res_rate_t *S, uint64_t **src_io, uint64_t **other_
 {
     const uint64_t N = S->R->n;
     fastf_engine_t *e = S->e;
-    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint64_t *const sm = S->buf.small.u64;
     uint64_t *src = *src_io, *other = *other_io;
     int in_other = 0;
     if (fastf_dev_clear_error_bits(e, FASTF_ERR_RUN_TOO_LONG, NULL) ||
@@ -392,8 +349,8 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
     const resident_t *R = S->R;
     const uint64_t N = R->n;
     fastf_engine_t *e = S->e;
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    uint32_t *const d_f = (uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S);
     double tt = fastf_res_now();
     uint64_t *src = NULL, *other = NULL;
     if (point_sort_reduce_(S, d_plane, &src, &other)) return RES_FAIL;
@@ -405,24 +362,24 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
         S->sorted_full = 1;
     }
     S->sorted = src; S->sorted_other = other;
-    if (fastf_devmem_copy(S->h_small, S->d_small, SM_HITS * 8)) return RES_FAIL;
-    bits |= S->h_small[SM_CNT + 3];
+    if (fastf_devmem_copy(S->buf.h_small.u64, S->buf.small.p, SM_HITS * 8)) return RES_FAIL;
+    bits |= S->buf.h_small.u64[SM_CNT + 3];
     if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: bam2db() runs such a file again with wider keys */
     if (bits) { rs_err("%s: device error bits 0x%llx at point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
-    counters[0] = N; counters[1] = S->h_small[SM_CNT + 1]; counters[2] = S->h_small[SM_CNT + 2];
-    const uint64_t nnz = *nnz_out = S->h_small[SM_NNZ];
+    counters[0] = N; counters[1] = S->buf.h_small.u64[SM_CNT + 1]; counters[2] = S->buf.h_small.u64[SM_CNT + 2];
+    const uint64_t nnz = *nnz_out = S->buf.h_small.u64[SM_NNZ];
     if (nnz > N) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N); return RES_FAIL; }
     /* the rows, concatenated on the device, and their per-cell summary */
-    if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
-        fastf_dev_cell_summary(e, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_cells, (uint64_t *)S->d_upc, (uint32_t *)S->d_gpc, NULL) ||
-        (S->genes && fastf_dev_gene_summary(e, nnz ? d_f : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, (uint32_t *)S->d_cpg, (uint64_t *)S->d_upg, NULL)) ||
+    if (fastf_dev_rows_gather(e, sm + SM_KEYS, d.f, d.c, d.k, NULL) ||
+        fastf_dev_cell_summary(e, nnz ? d.c : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_cells, S->buf.upc.u64, S->buf.gpc.u32, NULL) ||
+        (S->genes && fastf_dev_gene_summary(e, nnz ? d.f : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_features, S->buf.cpg.u32, S->buf.upg.u64, NULL)) ||
         fastf_devmem_sync()) return RES_FAIL;
     T->device += fastf_res_now() - tt; tt = fastf_res_now();
-    if (fastf_devmem_copy(S->h_upc, S->d_upc, ((size_t)S->n_cells + 1) * 8) || fastf_devmem_copy(S->h_gpc, S->d_gpc, (size_t)S->n_cells * 4)) return RES_FAIL;
+    if (fastf_devmem_copy(S->buf.h_upc.u64, S->buf.upc.p, ((size_t)S->n_cells + 1) * 8) || fastf_devmem_copy(S->buf.h_gpc.u32, S->buf.gpc.p, (size_t)S->n_cells * 4)) return RES_FAIL;
     T->summary += fastf_res_now() - tt;
     if (S->genes) {
         tt = fastf_res_now();
-        if (S->n_features && (fastf_devmem_copy(S->h_cpg, S->d_cpg, (size_t)S->n_features * 4) || fastf_devmem_copy(S->h_upg, S->d_upg, (size_t)S->n_features * 8))) return RES_FAIL;
+        if (S->n_features && (fastf_devmem_copy(S->buf.h_cpg.u32, S->buf.cpg.p, (size_t)S->n_features * 4) || fastf_devmem_copy(S->buf.h_upg.u64, S->buf.upg.p, (size_t)S->n_features * 8))) return RES_FAIL;
         T->genes += fastf_res_now() - tt;
     }
     return RES_OK;
@@ -433,11 +390,11 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
 /* ------------------------------------------------------------------ */
 int fastf_res_level_room(res_rate_t *S)
 {
-    const size_t room_cells = (S->max_cells > S->n_cells ? S->max_cells : S->n_cells) + (size_t)1;
-    if (dev_room(&S->d_level, &S->have.level, 4 * room_cells * 8, S->device))
-        return rs_err("%s: the search state of cell rate %.3f does not fit: %zu bytes (%s)", S->verb, (double)S->rate_cell, 4 * room_cells * 8, fastf_last_error());
-    const size_t stride = S->have.level / 32;               /* (entries per array, of the block as it was allocated) */
-    S->d_lo = (uint64_t *)S->d_level; S->d_hi = S->d_lo + stride; S->d_probe = S->d_hi + stride; S->d_ufull = S->d_probe + stride;
+    const size_t room_cells = (S->cfg.max_cells > S->n_cells ? S->cfg.max_cells : S->n_cells) + (size_t)1;
+    const size_t bytes = res_level_layout(NULL, room_cells).bytes;
+    if (res_block_room(&S->buf.level, RES_DEV, bytes, room_cells, S->device))
+        return rs_err("%s: the search state of cell rate %.3f does not fit: %zu bytes (%s)", S->verb, (double)S->rate_cell, bytes, fastf_last_error());
+    S->lv = res_level_layout(S->buf.level.p, S->buf.level.n);
     return 0;
 }
 
@@ -445,14 +402,14 @@ int fastf_res_level_room(res_rate_t *S)
  * run was too long for the group-only sort and nothing else is wrong: the caller sorts fully and steps again), or the end of the run */
 static int level_result_(res_rate_t *S, const char *point_name, int *held, uint64_t *open_out, uint64_t *capped_out)
 {
-    if (fastf_devmem_copy(S->h_small, S->d_small, SM_WORDS_ * 8)) return RES_FAIL;
-    const uint64_t *const r = S->h_small + SM_LEVEL;
-    const uint64_t bits = r[2] | S->h_small[SM_CNT + 3];
+    if (fastf_devmem_copy(S->buf.h_small.u64, S->buf.small.p, SM_WORDS_ * 8)) return RES_FAIL;
+    const uint64_t *const r = S->buf.h_small.u64 + SM_LEVEL;
+    const uint64_t bits = r[2] | S->buf.h_small.u64[SM_CNT + 3];
     *held = 0;
     if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: as in fastf_res_point_run */
     if (bits == FASTF_ERR_RUN_TOO_LONG && r[3]) { *held = 1; return RES_OK; }
     if (bits || r[3]) { rs_err("%s: device error bits 0x%llx in the search of point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
-    if (S->h_small[SM_NNZ] > S->R->n) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)S->h_small[SM_NNZ], (unsigned long long)S->R->n); return RES_FAIL; }
+    if (S->buf.h_small.u64[SM_NNZ] > S->R->n) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)S->buf.h_small.u64[SM_NNZ], (unsigned long long)S->R->n); return RES_FAIL; }
     *open_out = r[0];
     if (capped_out) *capped_out = r[1];
     return RES_OK;
@@ -461,22 +418,21 @@ static int level_result_(res_rate_t *S, const char *point_name, int *held, uint6
 int fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t umi_cap, int first, uint64_t *open_out,
                           uint64_t *capped_out, res_times_t *T)
 {
-    const uint64_t N = S->R->n;
     fastf_engine_t *e = S->e;
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    uint32_t *const d_f = (uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S);
     const double t0 = fastf_res_now();
-    if (!S->d_level) { rs_err("internal error: no search state at point %s", point_name); return RES_FAIL; }
+    if (!S->buf.level.p) { rs_err("internal error: no search state at point %s", point_name); return RES_FAIL; }
     uint64_t *src = NULL, *other = NULL;
     if (point_sort_reduce_(S, d_plane, &src, &other)) return RES_FAIL;
     S->sorted = NULL; S->sorted_full = 0;                   /* (a search pass leaves no keys for --cells: the point's own run does) */
     for (int again = 0;; again++) {
         /* the rows concatenated on the device, their per-cell summary, the step: the row count is read on the device (a reduce that
          * raised an error bit leaves rows the step does not consume) */
-        if (fastf_dev_rows_gather(e, sm + SM_KEYS, d_f, d_c, d_k, NULL) ||
-            fastf_dev_cell_summary(e, d_c, d_k, sm + SM_NNZ, S->n_cells, (uint64_t *)S->d_upc, (uint32_t *)S->d_gpc, NULL) ||
-            (first ? fastf_dev_level_init(e, (const uint64_t *)S->d_upc, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)
-                   : fastf_dev_level_step(e, (const uint64_t *)S->d_upc, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)))
+        if (fastf_dev_rows_gather(e, sm + SM_KEYS, d.f, d.c, d.k, NULL) ||
+            fastf_dev_cell_summary(e, d.c, d.k, sm + SM_NNZ, S->n_cells, S->buf.upc.u64, S->buf.gpc.u32, NULL) ||
+            (first ? fastf_dev_level_init(e, S->buf.upc.u64, S->n_cells, umi_cap, S->lv.lo, S->lv.hi, S->lv.probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)
+                   : fastf_dev_level_step(e, S->buf.upc.u64, S->n_cells, umi_cap, S->lv.lo, S->lv.hi, S->lv.probe, sm + SM_LEVEL, sm + SM_CNT + 3, NULL)))
             return RES_FAIL;
         int held = 0;
         const int rc = level_result_(S, point_name, &held, open_out, first ? capped_out : NULL);
@@ -485,19 +441,19 @@ int fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *po
         if (again) { rs_err("%s: device error bits 0x%llx after the full sort in the search of point %s", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG, point_name); return RES_FAIL; }
         if (point_full_again_(S, &src, &other)) return RES_FAIL;
     }
-    if (first && fastf_devmem_copy(S->d_ufull, S->d_upc, ((size_t)S->n_cells + 1) * 8)) return RES_FAIL;
+    if (first && fastf_devmem_copy(S->lv.ufull, S->buf.upc.p, ((size_t)S->n_cells + 1) * 8)) return RES_FAIL;
     T->search += fastf_res_now() - t0; T->passes++;
     return RES_OK;
 }
 
 int fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, uint64_t *capped_out, res_times_t *T)
 {
-    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint64_t *const sm = S->buf.small.u64;
     const double t0 = fastf_res_now();
     int held = 0;
-    if (!S->d_level) { rs_err("internal error: no search state"); return RES_FAIL; }
-    if (fastf_devmem_zero(S->d_small, SM_HITS * 8) ||       /* (the counters of the point before: their error word is read again) */
-        fastf_dev_level_init(S->e, S->d_ufull, S->n_cells, umi_cap, S->d_lo, S->d_hi, S->d_probe, sm + SM_LEVEL, NULL, NULL)) return RES_FAIL;
+    if (!S->buf.level.p) { rs_err("internal error: no search state"); return RES_FAIL; }
+    if (fastf_devmem_zero(S->buf.small.p, SM_HITS * 8) ||       /* (the counters of the point before: their error word is read again) */
+        fastf_dev_level_init(S->e, S->lv.ufull, S->n_cells, umi_cap, S->lv.lo, S->lv.hi, S->lv.probe, sm + SM_LEVEL, NULL, NULL)) return RES_FAIL;
     const int rc = level_result_(S, "(the state of a cap)", &held, open_out, capped_out);
     if (rc != RES_OK) return rc;
     if (held) { rs_err("%s: device error bits 0x%llx before a search", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG); return RES_FAIL; }
@@ -507,14 +463,13 @@ int fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, ui
 
 int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz, res_times_t *T)
 {
-    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint64_t *const sm = S->buf.small.u64;
     double tt = fastf_res_now();
-    if (nnz > S->h_rows_cap) {
-        if (S->h_rows) fastf_pinned_free(S->h_rows);
-        S->h_rows_cap = nnz + nnz / 8 + 1024;
-        if (!(S->h_rows = (uint32_t *)fastf_pinned_alloc(S->h_rows_cap * 12))) { S->h_rows_cap = 0; return rs_err("%s: no pinned memory for %llu matrix rows", S->verb, (unsigned long long)nnz); }
+    if (nnz > S->buf.h_rows.n) {                            /* (more than there is room for: the need below is beyond what is held) */
+        const size_t room = nnz + nnz / 8 + 1024;
+        if (res_block_room(&S->buf.h_rows, RES_PIN, room * 12, room, S->device)) return rs_err("%s: no pinned memory for %llu matrix rows", S->verb, (unsigned long long)nnz);
     }
-    uint32_t *const h_rows = S->h_rows; const uint64_t cap = S->h_rows_cap;
+    uint32_t *const h_rows = S->buf.h_rows.u32; const uint64_t cap = S->buf.h_rows.n;
     fastf_coo_t coo = { h_rows, h_rows + cap, h_rows + 2 * cap, (size_t)nnz };
     /* (the gather kernel writes pinned host memory directly: it is the device-to-host copy of the rows) */
     if (nnz && (fastf_dev_rows_gather(S->e, sm + SM_KEYS, h_rows, h_rows + cap, h_rows + 2 * cap, NULL) || fastf_devmem_sync())) return 1;
@@ -527,24 +482,21 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
 /* ------------------------------------------------------------------ */
 /* --fidelity: the full rows of a pair, the join behind a point        */
 /* ------------------------------------------------------------------ */
-/* --neighbors: the device block behind the slot map — idx (n x k) and cnt (n) of the full rows, then of the point, shared (n), norms (n, u64) */
-static uint32_t *nbr_idx(const res_rate_t *S, int point) { return (uint32_t *)((char *)S->d_nbr + S->nbr_map_bytes + S->nbr_cells * 8) + (size_t)point * S->nbr_cells * FASTF_NEIGHBORS_K; }
-static uint32_t *nbr_cnt(const res_rate_t *S, int point) { return nbr_idx(S, 0) + 2 * S->nbr_cells * FASTF_NEIGHBORS_K + (size_t)point * S->nbr_cells; }
 static const char *fastf_last_error_copy(void) { static __thread char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error()); return keep; }
 
 /* the planes of one row set (P planes: what the largest count of the set needs) and its neighbour sets into the full (point == 0) or
  * the point's half of the block */
-static int nbr_sets(res_rate_t *S, const uint32_t *d_f, const uint32_t *d_c, const uint32_t *d_k, const uint64_t *d_nnz, uint32_t P, int point)
+static int nbr_sets(res_rate_t *S, const uint32_t *r_f, const uint32_t *r_c, const uint32_t *r_k, const uint64_t *d_nnz, uint32_t P, int point)
 {
     uint32_t n_pad = 0, K_pad = 0;
     uint64_t max_norm = 0;
     fastf_neighbors_pad(S->n_cells, S->hvg_k, &n_pad, &K_pad);
     const size_t need = (size_t)P * n_pad * K_pad;
-    if (dev_room(&S->d_nplanes, &S->have.nplanes, need ? need : 1, S->device))
+    if (res_room(&S->buf.nplanes, RES_DEV, need ? need : 1, S->device))
         return rs_err("%s: --neighbors: %u planes of %u cells x %u genes do not fit: %zu bytes (%s)", S->verb, P, n_pad, K_pad, need, fastf_last_error_copy());
-    if (fastf_dev_neighbor_planes(S->e, d_f, d_c, d_k, d_nnz, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, S->d_nplanes, S->have.nplanes, &P, NULL) ||
-        fastf_dev_neighbors(S->e, S->d_nplanes, P, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, nbr_idx(S, point), nbr_cnt(S, point),
-                            (uint64_t *)((char *)S->d_nbr + S->nbr_map_bytes), &max_norm, NULL) || fastf_devmem_sync())
+    if (fastf_dev_neighbor_planes(S->e, r_f, r_c, r_k, d_nnz, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, S->buf.nplanes.p, S->buf.nplanes.have, &P, NULL) ||
+        fastf_dev_neighbors(S->e, S->buf.nplanes.p, P, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->d_nbr.idx[point], S->d_nbr.cnt[point],
+                            S->d_nbr.norms, &max_norm, NULL) || fastf_devmem_sync())
         return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
     S->nbr_planes = P;
     return 0;
@@ -552,19 +504,18 @@ static int nbr_sets(res_rate_t *S, const uint32_t *d_f, const uint32_t *d_c, con
 
 int fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t *T)
 {
-    if (!S->neighbors) return 0;
-    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
-    uint32_t *const d_sh = nbr_cnt(S, 0) + 2 * S->nbr_cells;
+    if (!S->cfg.neighbors) return 0;
+    const uint64_t nnz = S->buf.h_small.u64[SM_NNZ];
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S);
     uint32_t P = 0;
     const double tt = fastf_res_now();
     /* (a point's counts are at most the full ones: P of the point never exceeds P of the pair) */
-    if (fastf_dev_neighbor_planes(S->e, nnz ? d_f : NULL, d_c, d_k, sm + SM_NNZ, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
+    if (fastf_dev_neighbor_planes(S->e, nnz ? d.f : NULL, d.c, d.k, sm + SM_NNZ, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
         return rs_err("%s: --neighbors at point %s: %s", S->verb, point_name, fastf_last_error_copy());
-    if (nbr_sets(S, nnz ? d_f : NULL, d_c, d_k, sm + SM_NNZ, P, 1)) return 1;
-    if (fastf_dev_neighbors_shared(S->e, nbr_idx(S, 0), nbr_cnt(S, 0), nbr_idx(S, 1), nbr_cnt(S, 1), S->n_cells, FASTF_NEIGHBORS_K, d_sh, NULL) || fastf_devmem_sync()) return 1;
-    if (S->n_cells && (fastf_devmem_copy(S->h_nkp, nbr_cnt(S, 1), (size_t)S->n_cells * 4) || fastf_devmem_copy(S->h_nsh, d_sh, (size_t)S->n_cells * 4))) return 1;
+    if (nbr_sets(S, nnz ? d.f : NULL, d.c, d.k, sm + SM_NNZ, P, 1)) return 1;
+    if (fastf_dev_neighbors_shared(S->e, S->d_nbr.idx[0], S->d_nbr.cnt[0], S->d_nbr.idx[1], S->d_nbr.cnt[1], S->n_cells, FASTF_NEIGHBORS_K, S->d_nbr.shared, NULL) || fastf_devmem_sync()) return 1;
+    if (S->n_cells && (fastf_devmem_copy(S->h_nbr.kp, S->d_nbr.cnt[1], (size_t)S->n_cells * 4) || fastf_devmem_copy(S->h_nbr.sh, S->d_nbr.shared, (size_t)S->n_cells * 4))) return 1;
     T->neighbors += fastf_res_now() - tt;
     return 0;
 }
@@ -572,16 +523,15 @@ int fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t
 /* --labels: one vote call on the full (point == 0) or the point's neighbour sets, then that half of the block to the host in one copy */
 static int lab_votes(res_rate_t *S, int point)
 {
-    uint8_t *const d = (uint8_t *)S->d_lab + res_lab_off(S, point);
-    if (fastf_dev_label_votes(S->e, nbr_idx(S, point), nbr_cnt(S, point), (const uint8_t *)S->d_lab, S->n_cells, FASTF_NEIGHBORS_K, S->n_labels,
-                              d, d + S->lab_cells, d + 2 * S->lab_cells, (uint32_t *)(d + 3 * S->lab_cells), NULL) || fastf_devmem_sync())
+    if (fastf_dev_label_votes(S->e, S->d_nbr.idx[point], S->d_nbr.cnt[point], S->d_lab.lab, S->n_cells, FASTF_NEIGHBORS_K, S->n_labels,
+                              S->d_lab.half[point].pred, S->d_lab.half[point].same, S->d_lab.half[point].labelled, S->d_lab.half[point].conf, NULL) || fastf_devmem_sync())
         return rs_err("%s: --labels at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
-    return fastf_devmem_copy(S->h_lab + res_lab_off(S, point), d, res_lab_half(S));
+    return fastf_devmem_copy(S->h_lab.half[point].pred, S->d_lab.half[point].pred, S->d_lab.half_bytes);
 }
 
 int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T)
 {
-    if (!S->labels) return 0;
+    if (!S->cfg.labels) return 0;
     (void)point_name;
     const double tt = fastf_res_now();
     if (lab_votes(S, 1)) return 1;
@@ -593,19 +543,17 @@ int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T
  * to the host in one copy, then the ranks */
 static int mk_tables(res_rate_t *S, int point)
 {
-    const size_t W = res_mk_words(S);
-    uint64_t *const d_s2u = (uint64_t *)S->d_mk, *const d_sum = d_s2u + W;
-    uint32_t *const d_det = (uint32_t *)(d_sum + W), *const d_npl = d_det + W;
-    if (fastf_dev_marker_auc(S->e, S->d_nplanes, S->nbr_planes, S->n_cells, S->hvg_k, (const uint8_t *)S->d_lab, S->n_labels, d_s2u, d_det, d_sum, d_npl, NULL) ||
+    const res_mk_v dm = res_mk_layout(S->buf.mk.p, S->n_labels, S->hvg_k), hm = res_mk_host(S, point);
+    if (fastf_dev_marker_auc(S->e, S->buf.nplanes.p, S->nbr_planes, S->n_cells, S->hvg_k, S->d_lab.lab, S->n_labels, dm.s2u, dm.det, dm.sum, dm.npl, NULL) ||
         fastf_devmem_sync())
         return rs_err("%s: --markers at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
-    if (fastf_devmem_copy(S->h_mk + (size_t)point * S->mk_set, S->d_mk, res_mk_bytes(S->n_labels, S->hvg_k))) return 1;
-    return fastf_marker_rank(res_mk_s2u(S, point), res_mk_npl(S, point), S->h_ngenes, S->hvg_k, S->n_labels, S->mk_rank + (size_t)point * S->n_labels * FASTF_HVG_TOP);
+    if (fastf_devmem_copy(hm.s2u, dm.s2u, dm.bytes)) return 1;
+    return fastf_marker_rank(hm.s2u, hm.npl, S->h_nbr.genes, S->hvg_k, S->n_labels, S->buf.mk_rank.u32 + (size_t)point * S->n_labels * FASTF_HVG_TOP);
 }
 
 int fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *T)
 {
-    if (!S->markers) return 0;
+    if (!S->cfg.markers) return 0;
     (void)point_name;
     const double tt = fastf_res_now();
     if (mk_tables(S, 1)) return 1;
@@ -613,62 +561,65 @@ int fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *
     return 0;
 }
 
+/* where the full-depth work of a pair is booked: under the first flag that is on, in the order fidelity, gene fidelity, neighbours;
+ * per_gene: the per-gene sums of the pair, which --fidelity has no part in */
+static double *full_timer(const res_rate_t *S, res_times_t *T, int per_gene)
+{
+    return S->cfg.fidelity && !per_gene ? &T->fidelity : S->cfg.gene_fid ? &T->gene_fid : &T->neighbors;
+}
+
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
-    if (!S->fidelity && !S->gene_fid && !S->neighbors) return 0;
-    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
-    uint32_t *const x_f = (uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
-    uint64_t *const d_sxy = (uint64_t *)S->d_fid, *const d_sxx = d_sxy + 2 * S->fid_stride;
+    if (!S->cfg.fidelity && !S->cfg.gene_fid && !S->cfg.neighbors) return 0;
+    const uint64_t N = S->R->n, nnz = S->buf.h_small.u64[SM_NNZ];
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
     double tt = fastf_res_now();
     if (nnz > N) return rs_err("internal error: %llu full-depth rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N);
-    if (fastf_devmem_copy(x_f, d_f, (size_t)nnz * 4) || fastf_devmem_copy(x_c, d_c, (size_t)nnz * 4) || fastf_devmem_copy(x_k, d_k, (size_t)nnz * 4) ||
+    if (fastf_devmem_copy(x.f, d.f, (size_t)nnz * 4) || fastf_devmem_copy(x.c, d.c, (size_t)nnz * 4) || fastf_devmem_copy(x.k, d.k, (size_t)nnz * 4) ||
         fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
     S->full_nnz = nnz;
-    if (S->gene_fid || S->neighbors) {                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
-        const size_t gs = S->gfid_stride;
-        uint64_t *const g_sx = (uint64_t *)S->d_gfid, *const g_sxx = g_sx + gs;
-        uint32_t *const g_cf = (uint32_t *)(g_sx + 5 * gs);
-        if (fastf_dev_gene_summary(S->e, nnz ? x_f : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_features, g_cf, g_sx, NULL) ||
-            fastf_dev_gene_moments(S->e, nnz ? x_f : NULL, nnz ? x_k : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_features, NULL, g_sxx, NULL) ||
+    if (S->cfg.gene_fid || S->cfg.neighbors) {                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
+        uint64_t *const g_sx = S->d_gfid.sx, *const g_sxx = S->d_gfid.sxx;
+        uint32_t *const g_cf = S->d_gfid.cf;
+        if (fastf_dev_gene_summary(S->e, nnz ? x.f : NULL, nnz ? x.k : NULL, sm + SM_FULL, S->n_features, g_cf, g_sx, NULL) ||
+            fastf_dev_gene_moments(S->e, nnz ? x.f : NULL, nnz ? x.k : NULL, nnz ? x.k : NULL, sm + SM_FULL, S->n_features, NULL, g_sxx, NULL) ||
             fastf_devmem_sync()) return 1;
-        if (S->n_features && (fastf_devmem_copy(S->h_gsx, g_sx, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gsxx, g_sxx, (size_t)S->n_features * 8) ||
-                              fastf_devmem_copy(S->h_gcf, g_cf, (size_t)S->n_features * 4))) return 1;
-        *(S->gene_fid ? &T->gene_fid : &T->neighbors) += fastf_res_now() - tt; tt = fastf_res_now();
+        if (S->n_features && (fastf_devmem_copy(S->h_gfid.sx, g_sx, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gfid.sxx, g_sxx, (size_t)S->n_features * 8) ||
+                              fastf_devmem_copy(S->h_gfid.cf, g_cf, (size_t)S->n_features * 4))) return 1;
+        *full_timer(S, T, 1) += fastf_res_now() - tt; tt = fastf_res_now();
     }
-    if (S->neighbors) {                                     /* A of the pair, its slot map, the planes of the full rows and their neighbour sets, which stay */
-        uint16_t *const h_map = (uint16_t *)S->h_nbr;
+    if (S->cfg.neighbors) {                                     /* A of the pair, its slot map, the planes of the full rows and their neighbour sets, which stay */
         uint32_t P = 0;
-        S->hvg_k = fastf_hvg_rank(S->n_cells, S->h_gsx, S->h_gsxx, S->n_features, S->h_ngenes, NULL);
-        if (fastf_neighbors_slot_map(S->h_ngenes, S->hvg_k, S->n_features, h_map) || fastf_devmem_copy(S->d_nbr, h_map, S->nbr_map_bytes)) return 1;
-        if (fastf_dev_neighbor_planes(S->e, nnz ? x_f : NULL, x_c, x_k, sm + SM_FULL, (const uint16_t *)S->d_nbr, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
+        S->hvg_k = fastf_hvg_rank(S->n_cells, S->h_gfid.sx, S->h_gfid.sxx, S->n_features, S->h_nbr.genes, NULL);
+        if (fastf_neighbors_slot_map(S->h_nbr.genes, S->hvg_k, S->n_features, S->h_nbr.map) || fastf_devmem_copy(S->d_nbr.map, S->h_nbr.map, S->nbr_map_bytes)) return 1;
+        if (fastf_dev_neighbor_planes(S->e, nnz ? x.f : NULL, x.c, x.k, sm + SM_FULL, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
             return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
-        if (nbr_sets(S, nnz ? x_f : NULL, x_c, x_k, sm + SM_FULL, P, 0)) return 1;
-        if (S->n_cells && fastf_devmem_copy(S->h_nkf, nbr_cnt(S, 0), (size_t)S->n_cells * 4)) return 1;
+        if (nbr_sets(S, nnz ? x.f : NULL, x.c, x.k, sm + SM_FULL, P, 0)) return 1;
+        if (S->n_cells && fastf_devmem_copy(S->h_nbr.kf, S->d_nbr.cnt[0], (size_t)S->n_cells * 4)) return 1;
         T->neighbors += fastf_res_now() - tt; tt = fastf_res_now();
     }
-    if (S->labels) {                                        /* the votes of the full sets, which stay for every point of the pair */
+    if (S->cfg.labels) {                                        /* the votes of the full sets, which stay for every point of the pair */
         if (lab_votes(S, 0)) return 1;
         T->labels += fastf_res_now() - tt; tt = fastf_res_now();
     }
-    if (S->markers) {                                       /* the tables and ranks of the full rows, while their planes are still in the plane buffer */
+    if (S->cfg.markers) {                                       /* the tables and ranks of the full rows, while their planes are still in the plane buffer */
         if (mk_tables(S, 0)) return 1;
         T->markers += fastf_res_now() - tt; tt = fastf_res_now();
     }
-    if (!S->fidelity) return 0;
+    if (!S->cfg.fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
      * first point overwrites) */
-    if (fastf_dev_fidelity(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? x_f : NULL, nnz ? x_c : NULL, nnz ? x_k : NULL, sm + SM_FULL, S->n_cells, d_sxy, d_sxx, NULL, NULL)) return 1;
-    if (fastf_devmem_copy(S->h_sxx, d_sxx, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_ufull, S->d_upc, ((size_t)S->n_cells + 1) * 8) ||
-        fastf_devmem_copy(S->h_gfull, S->d_gpc, (size_t)S->n_cells * 4)) return 1;
+    if (fastf_dev_fidelity(S->e, x.f, x.c, x.k, sm + SM_FULL, nnz ? x.f : NULL, nnz ? x.c : NULL, nnz ? x.k : NULL, sm + SM_FULL, S->n_cells, S->d_fid.sxy, S->d_fid.sxx, NULL, NULL)) return 1;
+    if (fastf_devmem_copy(S->h_fid.sxx, S->d_fid.sxx, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_fid.ufull, S->buf.upc.p, ((size_t)S->n_cells + 1) * 8) ||
+        fastf_devmem_copy(S->h_fid.gfull, S->buf.gpc.p, (size_t)S->n_cells * 4)) return 1;
     T->fidelity += fastf_res_now() - tt;
     return 0;
 }
 
 int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
 {
-    if (!S->fidelity && !S->gene_fid && !S->neighbors) return RES_OK;
+    if (!S->cfg.fidelity && !S->cfg.gene_fid && !S->cfg.neighbors) return RES_OK;
     char name[64];
     uint64_t counters[3], nnz = 0;
     const res_times_t before = *T;
@@ -677,49 +628,41 @@ int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
     const int prc = fastf_res_point_run(S, d_plane, name, counters, &nnz, T);
     if (prc != RES_OK) return prc;
     *T = before;                                            /* (the stages of this point are the flag's own) */
-    *(S->fidelity ? &T->fidelity : S->gene_fid ? &T->gene_fid : &T->neighbors) += fastf_res_now() - tt;
+    *full_timer(S, T, 0) += fastf_res_now() - tt;
     return fastf_res_full_keep(S, T) ? RES_FAIL : RES_OK;
 }
 
 int fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t *T)
 {
-    if (!S->fidelity) return 0;
-    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
-    const uint32_t *const x_f = (const uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
-    uint64_t *const d_sxy = (uint64_t *)S->d_fid, *const d_syy = d_sxy + S->fid_stride;
+    if (!S->cfg.fidelity) return 0;
+    const uint64_t nnz = S->buf.h_small.u64[SM_NNZ];
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
     const double tt = fastf_res_now();
-    if (fastf_dev_fidelity(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? d_f : NULL, nnz ? d_c : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_cells, d_sxy, d_syy, NULL, NULL)) {
-        char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, keep);
-    }
-    if (fastf_devmem_copy(S->h_sxy, d_sxy, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_syy, d_syy, (size_t)S->n_cells * 8)) return 1;
+    if (fastf_dev_fidelity(S->e, x.f, x.c, x.k, sm + SM_FULL, nnz ? d.f : NULL, nnz ? d.c : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_cells, S->d_fid.sxy, S->d_fid.syy, NULL, NULL))
+        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
+    if (fastf_devmem_copy(S->h_fid.sxy, S->d_fid.sxy, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_fid.syy, S->d_fid.syy, (size_t)S->n_cells * 8)) return 1;
     T->fidelity += fastf_res_now() - tt;
     return 0;
 }
 
 int fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_times_t *T)
 {
-    if (!S->gene_fid) return 0;
-    const uint64_t N = S->R->n, nnz = S->h_small[SM_NNZ];
-    uint64_t *const sm = (uint64_t *)S->d_small;
-    const uint32_t *const d_f = (const uint32_t *)S->d_rows, *const d_c = d_f + N, *const d_k = d_c + N;
-    const uint32_t *const x_f = (const uint32_t *)S->d_full, *const x_c = x_f + N, *const x_k = x_c + N;
-    const size_t gs = S->gfid_stride;
-    uint64_t *const g_sy = (uint64_t *)S->d_gfid + 2 * gs, *const g_syy = g_sy + gs, *const g_sxy = g_syy + gs;
-    uint32_t *const g_c = (uint32_t *)((uint64_t *)S->d_gfid + 5 * gs) + gs, *const d_x = (uint32_t *)S->d_gx;
+    if (!S->cfg.gene_fid) return 0;
+    const uint64_t nnz = S->buf.h_small.u64[SM_NNZ];
+    uint64_t *const sm = S->buf.small.u64;
+    const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
+    uint64_t *const g_sy = S->d_gfid.sy, *const g_syy = S->d_gfid.syy, *const g_sxy = S->d_gfid.sxy;
+    uint32_t *const g_c = S->d_gfid.c, *const d_x = S->buf.gx.u32;
     const double tt = fastf_res_now();
-    if (fastf_dev_partner_counts(S->e, x_f, x_c, x_k, sm + SM_FULL, nnz ? d_f : NULL, nnz ? d_c : NULL, sm + SM_NNZ, d_x, NULL, NULL)) {
-        char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, keep);
-    }
-    /* (with --genes fastf_res_point_run has left the point's sum_y and cells in S->h_upg and S->h_cpg) */
-    if ((!S->genes && fastf_dev_gene_summary(S->e, nnz ? d_f : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, g_c, g_sy, NULL)) ||
-        fastf_dev_gene_moments(S->e, nnz ? d_f : NULL, nnz ? d_x : NULL, nnz ? d_k : NULL, sm + SM_NNZ, S->n_features, g_sxy, g_syy, NULL) ||
+    if (fastf_dev_partner_counts(S->e, x.f, x.c, x.k, sm + SM_FULL, nnz ? d.f : NULL, nnz ? d.c : NULL, sm + SM_NNZ, d_x, NULL, NULL))
+        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
+    /* (with --genes fastf_res_point_run has left the point's sum_y and cells in S->buf.h_upg and S->buf.h_cpg) */
+    if ((!S->genes && fastf_dev_gene_summary(S->e, nnz ? d.f : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_features, g_c, g_sy, NULL)) ||
+        fastf_dev_gene_moments(S->e, nnz ? d.f : NULL, nnz ? d_x : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_features, g_sxy, g_syy, NULL) ||
         fastf_devmem_sync()) return 1;
-    if (S->n_features && (fastf_devmem_copy(S->h_gsyy, g_syy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gsxy, g_sxy, (size_t)S->n_features * 8) ||
-                          (!S->genes && (fastf_devmem_copy(S->h_gsy, g_sy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gc, g_c, (size_t)S->n_features * 4))))) return 1;
+    if (S->n_features && (fastf_devmem_copy(S->h_gfid.syy, g_syy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gfid.sxy, g_sxy, (size_t)S->n_features * 8) ||
+                          (!S->genes && (fastf_devmem_copy(S->h_gfid.sy, g_sy, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gfid.c, g_c, (size_t)S->n_features * 4))))) return 1;
     T->gene_fid += fastf_res_now() - tt;
     return 0;
 }
@@ -740,7 +683,7 @@ int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
     if (!S->cells) return 0;
     const uint64_t N = S->R->n;
     fastf_engine_t *e = S->e;
-    uint64_t *const sm = (uint64_t *)S->d_small;
+    uint64_t *const sm = S->buf.small.u64;
     double tt = fastf_res_now();
     if (!S->sorted) return rs_err("internal error: no sorted keys at point %s", point_name);
     uint64_t *src = S->sorted;
@@ -750,15 +693,14 @@ int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
         if (in_other) src = S->sorted_other;
     }
     S->sorted = NULL;                                       /* (one use: the next point brings its own) */
-    uint64_t *const d_uk = (uint64_t *)S->d_rows; uint32_t *const d_nc = (uint32_t *)(d_uk + N);
-    uint64_t *const d_hist = (uint64_t *)S->d_cellsum;
-    uint32_t *const d_rpc = (uint32_t *)((char *)S->d_cellsum + RES_CELLS_HIST_BYTES), *const d_npc = d_rpc + S->n_cells, *const d_spc = d_npc + S->n_cells;
+    uint64_t *const d_uk = (uint64_t *)S->buf.rows.p; uint32_t *const d_nc = (uint32_t *)(d_uk + N);
+    const res_cellsum_v cs = res_cellsum_layout(S->buf.cellsum.p, S->n_cells);
     uint64_t bits = 0;
     if (fastf_dev_umi_rows(e, src, sm + SM_KEYS, N, d_uk, d_nc, sm + SM_UROWS, NULL) ||
-        fastf_dev_copy_summary(e, d_uk, d_nc, sm + SM_UROWS, S->n_cells, d_rpc, d_npc, d_spc, d_hist, NULL) ||
+        fastf_dev_copy_summary(e, d_uk, d_nc, sm + SM_UROWS, S->n_cells, cs.rpc, cs.npc, cs.spc, cs.hist, NULL) ||
         fastf_dev_error_bits(e, &bits)) return 1;
     if (bits) return rs_err("%s: device error bits 0x%llx in the per-cell stage of point %s", S->verb, (unsigned long long)bits, point_name);
-    if (fastf_devmem_copy(S->h_hist, S->d_cellsum, RES_CELLS_HIST_BYTES + (size_t)S->n_cells * 12)) return 1;
+    if (fastf_devmem_copy(S->h_cs.hist, cs.hist, cs.bytes)) return 1;
     T->cells_dev += fastf_res_now() - tt;
     return 0;
 }
@@ -920,11 +862,11 @@ int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, 
         gtext t = { NULL, 0, 0 };
         int bad = gt_str(&t, "barcode\treads\tnull_umi_reads\tumis\tgenes\tsingleton_umis\tsaturation\n");
         for (uint32_t k = 0; k < S->n_cells && !bad; k++) {
-            const uint64_t reads = S->h_rpc[k], umis = S->h_upc[k];
+            const uint64_t reads = S->h_cs.rpc[k], umis = S->buf.h_upc.u64[k];
             char sat[32];
             snprintf(sat, sizeof sat, "\t%.6f\n", reads ? 1.0 - (double)umis / (double)reads : 0.0);
-            bad = gt_str(&t, S->L->barcode[k]) || gt_u64(&t, '\t', reads) || gt_u64(&t, '\t', S->h_npc[k]) || gt_u64(&t, '\t', umis) ||
-                  gt_u64(&t, '\t', S->h_gpc[k]) || gt_u64(&t, '\t', S->h_spc[k]) || gt_str(&t, sat);
+            bad = gt_str(&t, S->L->barcode[k]) || gt_u64(&t, '\t', reads) || gt_u64(&t, '\t', S->h_cs.npc[k]) || gt_u64(&t, '\t', umis) ||
+                  gt_u64(&t, '\t', S->buf.h_gpc.u32[k]) || gt_u64(&t, '\t', S->h_cs.spc[k]) || gt_str(&t, sat);
         }
         snprintf(path, sizeof path, "%s/cells.tsv.gz", dir);
         if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
@@ -967,15 +909,15 @@ int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, cons
 static int gene_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
     char row[640];
-    if (fastf_gene_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->h_gsx, S->h_gsy, S->h_gsxx, S->h_gsyy, S->h_gsxy,
+    if (fastf_gene_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->h_gfid.sx, S->h_gfid.sy, S->h_gfid.sxx, S->h_gfid.syy, S->h_gfid.sxy,
                                         S->n_features, row, sizeof row)) return 1;
     if (dir) {
         char path[4200], line[640];
         gtext t = { NULL, 0, 0 };
         int bad = gt_str(&t, fastf_gene_fidelity_header());
         for (uint32_t g = 0; g < S->n_features && !bad; g++)
-            bad = fastf_gene_fidelity_row(S->L->feat_id[g], S->n_cells, S->h_gsx[g], S->h_gsy[g], S->h_gcf[g], S->h_gc[g], S->h_gsxx[g], S->h_gsyy[g],
-                                          S->h_gsxy[g], line, sizeof line) || gt_str(&t, line);
+            bad = fastf_gene_fidelity_row(S->L->feat_id[g], S->n_cells, S->h_gfid.sx[g], S->h_gfid.sy[g], S->h_gfid.cf[g], S->h_gfid.c[g], S->h_gfid.sxx[g], S->h_gfid.syy[g],
+                                          S->h_gfid.sxy[g], line, sizeof line) || gt_str(&t, line);
         snprintf(path, sizeof path, "%s/gene_fidelity.tsv.gz", dir);
         if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
         free(t.p);
@@ -1026,8 +968,9 @@ int fastf_res_fid_open_markers(res_fid_t *F, uint32_t markers, const char *verb,
 static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
     const uint32_t L = S->n_labels, K = S->hvg_k, top = F->markers < K ? F->markers : K;
-    const uint32_t *const npl = res_mk_npl(S, 0), *const rf = res_mk_rank(S, 0), *const rp = res_mk_rank(S, 1);
-    const uint32_t *const df = res_mk_det(S, 0), *const dp = res_mk_det(S, 1);
+    const res_mk_v mf = res_mk_host(S, 0), mp = res_mk_host(S, 1);
+    const uint32_t *const npl = mf.npl, *const rf = res_mk_rank(S, 0), *const rp = res_mk_rank(S, 1);
+    const uint32_t *const df = mf.det, *const dp = mp.det;
     const size_t rows_cap = ((size_t)L + 1) * (FASTF_LABEL_BYTES + 160);
     char *const rows = (char *)malloc(rows_cap);
     const char **const names = (const char **)malloc(((size_t)L + 1) * sizeof *names);
@@ -1035,7 +978,7 @@ static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float ra
     int bad = !rows || !names || !by_rank || !det_all;
     if (bad) rs_err("out of memory");
     for (uint32_t l = 0; l <= L && !bad; l++) names[l] = fastf_labels_name(F->labels, l);
-    if (!bad) bad = fastf_markers_summary_rows(S->rate_cell, rate_depth, list_value, S->seed, names, L, K, F->markers, npl, rf, rp, res_mk_s2u(S, 0), res_mk_s2u(S, 1), rows, rows_cap);
+    if (!bad) bad = fastf_markers_summary_rows(S->rate_cell, rate_depth, list_value, S->seed, names, L, K, F->markers, npl, rf, rp, mf.s2u, mp.s2u, rows, rows_cap);
     if (dir && !bad) {
         char path[4200], line[512];
         gtext t = { NULL, 0, 0 };
@@ -1050,8 +993,8 @@ static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float ra
             for (uint32_t r = 0; r < K && !bad; r++) {
                 const uint32_t g = by_rank[r];
                 if (r >= top && rp[at + g] > top) continue;
-                bad = fastf_markers_row(names[a + 1], S->L->feat_id[S->h_ngenes[g]], n_in, n_out, rf[at + g], rp[at + g], res_mk_s2u(S, 0)[at + g], res_mk_s2u(S, 1)[at + g],
-                                        df[at + g], det_all[g] - df[at + g], dp[at + g], det_all[K + g] - dp[at + g], res_mk_sum(S, 1)[at + g], line, sizeof line) || gt_str(&t, line);
+                bad = fastf_markers_row(names[a + 1], S->L->feat_id[S->h_nbr.genes[g]], n_in, n_out, rf[at + g], rp[at + g], mf.s2u[at + g], mp.s2u[at + g],
+                                        df[at + g], det_all[g] - df[at + g], dp[at + g], det_all[K + g] - dp[at + g], mp.sum[at + g], line, sizeof line) || gt_str(&t, line);
             }
         }
         snprintf(path, sizeof path, "%s/markers.tsv.gz", dir);
@@ -1067,11 +1010,11 @@ static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float ra
 static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
     const uint32_t L = S->n_labels;
-    const uint8_t *const lab = S->h_lab, *const pf = res_lab_pred(S, 0), *const pp = res_lab_pred(S, 1);
-    const uint32_t *const cx = res_lab_conf(S, 0), *const cy = res_lab_conf(S, 1);
+    const uint8_t *const lab = S->h_lab.lab, *const pf = S->h_lab.half[0].pred, *const pp = S->h_lab.half[1].pred;
+    const uint32_t *const cx = S->h_lab.half[0].conf, *const cy = S->h_lab.half[1].conf;
     char row[640];
-    if (fastf_labels_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, FASTF_NEIGHBORS_K, L, lab, pf, pp, res_lab_same(S, 0),
-                                 res_lab_labelled(S, 0), res_lab_same(S, 1), res_lab_labelled(S, 1), cx, cy, row, sizeof row)) return 1;
+    if (fastf_labels_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, FASTF_NEIGHBORS_K, L, lab, pf, pp, S->h_lab.half[0].same,
+                                 S->h_lab.half[0].labelled, S->h_lab.half[1].same, S->h_lab.half[1].labelled, cx, cy, row, sizeof row)) return 1;
     if (dir) {
         char path[4200], line[512];
         const size_t wide = 64 + (size_t)(L + 1) * FASTF_LABEL_BYTES;
@@ -1085,8 +1028,8 @@ static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float r
         if (!bad) bad = gt_str(&t, fastf_labels_header());
         for (uint32_t c = 0; c < S->n_cells && !bad; c++) {
             cells[lab[c]]++;
-            bad = fastf_labels_row(S->L->barcode[c], names[lab[c]], names[pf[c]], names[pp[c]], res_lab_same(S, 0)[c], res_lab_labelled(S, 0)[c],
-                                   res_lab_same(S, 1)[c], res_lab_labelled(S, 1)[c], line, sizeof line) || gt_str(&t, line);
+            bad = fastf_labels_row(S->L->barcode[c], names[lab[c]], names[pf[c]], names[pp[c]], S->h_lab.half[0].same[c], S->h_lab.half[0].labelled[c],
+                                   S->h_lab.half[1].same[c], S->h_lab.half[1].labelled[c], line, sizeof line) || gt_str(&t, line);
         }
         snprintf(path, sizeof path, "%s/labels.tsv.gz", dir);
         if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
@@ -1110,13 +1053,13 @@ static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float r
 static int nbr_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
 {
     char row[640];
-    if (fastf_neighbors_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->h_nkf, S->h_nkp, S->h_nsh, row, sizeof row)) return 1;
+    if (fastf_neighbors_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->h_nbr.kf, S->h_nbr.kp, S->h_nbr.sh, row, sizeof row)) return 1;
     if (dir) {
         char path[4200], line[512];
         gtext t = { NULL, 0, 0 };
         int bad = gt_str(&t, fastf_neighbors_header());
         for (uint32_t c = 0; c < S->n_cells && !bad; c++)
-            bad = fastf_neighbors_row(S->L->barcode[c], S->h_nkf[c], S->h_nkp[c], S->h_nsh[c], line, sizeof line) || gt_str(&t, line);
+            bad = fastf_neighbors_row(S->L->barcode[c], S->h_nbr.kf[c], S->h_nbr.kp[c], S->h_nbr.sh[c], line, sizeof line) || gt_str(&t, line);
         snprintf(path, sizeof path, "%s/neighbors.tsv.gz", dir);
         if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
         free(t.p);
@@ -1151,14 +1094,14 @@ int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, floa
     if (!F->on) return 0;
     const double tt = fastf_res_now();
     char row[640];
-    if (fastf_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->h_ufull, S->h_upc, S->h_gfull, S->h_gpc, S->h_sxx, S->h_syy, S->h_sxy,
+    if (fastf_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->h_fid.ufull, S->buf.h_upc.u64, S->h_fid.gfull, S->buf.h_gpc.u32, S->h_fid.sxx, S->h_fid.syy, S->h_fid.sxy,
                                    S->n_cells, S->n_features, row, sizeof row)) return 1;
     if (dir) {
         char path[4200], line[512];
         gtext t = { NULL, 0, 0 };
         int bad = gt_str(&t, fastf_fidelity_header());
         for (uint32_t k = 0; k < S->n_cells && !bad; k++)
-            bad = fastf_fidelity_row(S->L->barcode[k], S->h_ufull[k], S->h_upc[k], S->h_gfull[k], S->h_gpc[k], S->h_sxx[k], S->h_syy[k], S->h_sxy[k],
+            bad = fastf_fidelity_row(S->L->barcode[k], S->h_fid.ufull[k], S->buf.h_upc.u64[k], S->h_fid.gfull[k], S->buf.h_gpc.u32[k], S->h_fid.sxx[k], S->h_fid.syy[k], S->h_fid.sxy[k],
                                      S->n_features, line, sizeof line) || gt_str(&t, line);
         snprintf(path, sizeof path, "%s/fidelity.tsv.gz", dir);
         if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
@@ -1388,7 +1331,7 @@ int fastf_res_reps_genes(res_reps_t *P, res_rate_t *S, uint32_t j, uint32_t k, c
         if (!nf) return 0;
         if (!P->d_acc) return rs_err("internal error: no per-gene accumulators on the device");
         uint64_t *const a = (uint64_t *)P->d_acc + (size_t)j * 3 * nf;
-        return fastf_dev_gene_reps_add(S->e, (const uint32_t *)S->d_cpg, nf, a, a + nf, a + 2 * (size_t)nf, NULL);
+        return fastf_dev_gene_reps_add(S->e, S->buf.cpg.u32, nf, a, a + nf, a + 2 * (size_t)nf, NULL);
     }
     uint64_t *const a = P->h_acc + ((size_t)P->rate_at * P->n_list + j) * 3 * nf;
     return fastf_gene_reps_add_host(cells_per_gene, nf, a, a + nf, a + 2 * (size_t)nf);

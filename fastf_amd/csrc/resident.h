@@ -9,7 +9,7 @@
  * (their count array and the span tables are the ones the matrix rows lie in) and fastf_res_point_write gathers from those.
  * --fidelity adds the full-depth rows of the pair, kept on the device behind every open (fastf_res_full_run / fastf_res_full_keep), and
  * behind every point the join of its rows with them (fastf_res_point_fidelity) — BEFORE fastf_res_point_cells, whose K3u output
- * overwrites the point's rows in S->d_rows.
+ * overwrites the point's rows in S->buf.rows.
  * --gene-fidelity reduces the same pair of row sets along the gene axis (fastf_res_point_gene_fidelity, behind fastf_res_point_fidelity
  * and before fastf_res_point_cells too); alone it switches the full-depth rows on by itself.
  * --neighbors compares the k-nearest-neighbour sets of the cells over the pair's highly variable genes (fastf_res_point_neighbors, behind
@@ -22,6 +22,7 @@
 #define FASTF_RESIDENT_H
 
 #include "host_io.h"
+#include "res_layout.h"
 
 #include <stdio.h>
 
@@ -60,66 +61,50 @@ int  fastf_res_decode(const char *verb, const char *bam_file, const fastf_lists_
 void fastf_res_free(resident_t *R) FASTF_HIDDEN;
 
 /* one (cell rate, seed) pair: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point),
- * the buffers of a point.  The buffers outlive the pair: a run keeps ONE res_rate_t, zeroed before its first open, and every later
- * fastf_res_rate_open on it ends the pair before (its engine) and takes its buffers over — each is allocated again only where the
- * new pair needs more (have: the bytes held).  The per-cell arrays and the cell scratch inside the blocked copy are sized for
- * max_cells, the most cells any pair of the run samples, which the lists tell before the first open; the key pair and the rows
- * follow the record count.  What is left to grow is a change from narrow to wide runs between cell rates.  blk_layout: the layout word (fastf_dev_block_layout) the
- * blocked copy in d_blk was written for, 0: none — a pair whose engine has the same word runs K1a alone.  no_reuse (the verbs read
- * FASTF_RES_NO_REUSE=1 once per run): fresh buffers and a fresh blocked copy for every pair (A/B runs, a test) */
+ * the buffers of a point.  DESIGN.md section 10q describes this state once; in short:
+ * cfg   what the caller sets before the first open and no open or close touches: the comparisons that are on (neighbors is set with
+ *       labels too; markers = N needs labels), max_cells, the most cells any pair of the run samples (0: unknown), which the lists tell,
+ *       and no_reuse (the verbs read FASTF_RES_NO_REUSE=1 once per run): fresh buffers and a fresh blocked copy for every pair.
+ * buf   the buffer table: every device, pinned or host buffer of the state.  The buffers outlive the pair: a run keeps ONE res_rate_t,
+ *       zeroed before its first open, and every later fastf_res_rate_open on it ends the pair before (its engine) and takes its buffers
+ *       over — each is allocated again only where the new pair needs more (have: the bytes held; n: the entries per array a carved
+ *       block was allocated for, by which it is carved while it lives).  fastf_res_rate_close frees the table in a loop.
+ * the views (res_layout.h)   the typed arrays inside the carved blocks, set by the open that made room for them.
+ * blk_layout: the layout word (fastf_dev_block_layout) the blocked copy in buf.blk was written for, 0: none — a pair whose engine has
+ * the same word runs K1a alone */
+typedef struct { union { void *p; uint8_t *u8; uint32_t *u32; uint64_t *u64; }; size_t have, n; int kind; } res_buf_t;
+enum { RES_DEV = 1, RES_PIN, RES_HOST };             /* the kinds of a buffer: device, pinned, plain host memory */
+typedef struct { int fidelity, gene_fid, neighbors, labels; const fastf_labels_t *lab_t; uint32_t markers, max_cells; int no_reuse; } res_cfg_t;
 typedef struct {
+    res_cfg_t cfg;
     const char *verb; const resident_t *R; const fastf_lists_t *L; int device; float rate_cell; uint32_t seed;
     fastf_engine_t *e;
     uint32_t n_cells, key_bits, kflags; int blocked, segmented;
-    uint64_t key_slots, H;
-    void *d_blk, *d_keys, *d_tmp, *d_small, *d_rows, *d_upc, *d_gpc;
-    uint64_t *h_small, *h_upc; uint32_t *h_gpc, *h_rows; uint64_t h_rows_cap;
-    int genes; uint32_t n_features;      /* --genes: the per-gene arrays of a point (n_features entries each), else NULL */
-    void *d_cpg, *d_upg; uint32_t *h_cpg; uint64_t *h_upg;
+    uint64_t key_slots, H, blk_layout;
+    int genes; uint32_t n_features;      /* --genes: the per-gene arrays of a point (buf.cpg, buf.upg and their pinned copies, n_features entries each) */
     /* --cells: where fastf_res_point_run left the point's sorted keys (sorted_full: by every bit, the FASTF_ERR_RUN_TOO_LONG branch
-     * ran) and the other buffer of the pair; one device block and its pinned copy, hist[FASTF_COPY_BINS + 1] then the three per-cell
-     * arrays (RES_CELLS_HIST_BYTES, then n_cells u32 each), else NULL */
+     * ran) and the other buffer of the pair */
     int cells, sorted_full; uint64_t *sorted, *sorted_other;
-    void *d_cellsum; uint64_t *h_hist; uint32_t *h_rpc, *h_npc, *h_spc;
-    uint64_t blk_layout;
-    /* level: lo, hi, the probes and U_k(2^32) of the search (four u64 arrays of level_cells entries in ONE block sized for max_cells,
-     * fastf_res_level_room), else NULL */
-    void *d_level; uint64_t *d_lo, *d_hi, *d_probe, *d_ufull;
-    /* --fidelity (set by the caller before the first open, as max_cells is): the pair's full rows, 12 bytes each, in d_full (feature,
-     * cell, count: R->n entries each; their number in d_small[SM_FULL] and full_nnz); d_fid: sum_xy, sum_yy, sum_xx on the device (u64,
-     * fid_stride entries apart); h_fid: their pinned copies, then umis_full (n_cells + 1) and genes_full of the pair */
-    int fidelity; void *d_full, *d_fid; uint64_t full_nnz; size_t fid_stride;
-    uint64_t *h_fid, *h_sxy, *h_syy, *h_sxx, *h_ufull; uint32_t *h_gfull;
-    /* --gene-fidelity (set by the caller before the first open; it keeps the full rows as --fidelity does): d_gx: the partner column,
-     * x of every point row (u32, R->n entries); d_gfid: per gene sum_x, sum_xx, sum_y, sum_yy, sum_xy
-     * (u64) then cells_full, cells (u32), gfid_stride entries apart; h_gfid: their pinned copies.  With S->genes the point's sum_y
-     * and cells are the arrays of --genes (h_gsy == h_upg, h_gc == h_cpg) */
-    int gene_fid; void *d_gx, *d_gfid; size_t gfid_stride;
-    uint64_t *h_gfid, *h_gsx, *h_gsxx, *h_gsy, *h_gsyy, *h_gsxy; uint32_t *h_gcf, *h_gc;
-    /* --neighbors (set by the caller before the first open; it keeps the full rows and the pair's per-gene sums as --gene-fidelity does):
-     * d_nbr: the slot map of A (u16[n_features + 1], nbr_map_bytes), the norms (u64), the neighbour indices of the full rows and of the
-     * point (u32, FASTF_NEIGHBORS_K a cell), their counts and the shared counts (u32), nbr_cells entries apart; d_nplanes: the byte planes
-     * of the row set at hand (nbr_planes of them); h_nbr: the pinned map, k_full, k_point, shared and the genes of A in rank order */
-    int neighbors; void *d_nbr, *d_nplanes, *h_nbr; size_t nbr_cells, nbr_map_bytes; uint32_t hvg_k, nbr_planes;
-    uint32_t *h_nkf, *h_nkp, *h_nsh, *h_ngenes;
-    /* --labels (labels and lab_t set by the caller before the first open; the caller sets neighbors too): d_lab: one device block of
-     * lab (u8, lab_cells entries: a multiple of 4), pred, same and labelled of the full rows, conf_X (u32, n_labels x (n_labels + 1)),
-     * then pred, same and labelled of the point and conf_Y — each half leaves in one copy; h_lab: its pinned copy, the same layout */
-    int labels; const fastf_labels_t *lab_t; void *d_lab; uint8_t *h_lab; size_t lab_cells; uint32_t n_labels;
-    /* --markers (markers = N set by the caller before the first open, with labels): d_mk: the four tables of ONE row set — s2u, sum (u64),
-     * det (u32), n_labels x hvg_k each, then n_per_label (u32) — which leave in one copy; h_mk: the pinned copies of the full rows' set
-     * and of the point's, mk_set bytes apart; mk_rank: the ranks of the full rows and of the point (u32, n_labels x hvg_k each, host) */
-    uint32_t markers; void *d_mk; uint8_t *h_mk; size_t mk_set; uint32_t *mk_rank;
-    uint32_t max_cells; int no_reuse;    /* set by the caller before the first open: the most cells any pair of the run samples (0: unknown); FASTF_RES_NO_REUSE */
-    struct { size_t blk, keys, tmp, rows, upc, gpc, h_upc, h_gpc, cpg, upg, h_cpg, h_upg, cellsum, h_hist, level, full, fid, h_fid, gx, gfid, h_gfid, nbr, h_nbr, nplanes, lab, h_lab, mk, h_mk, mk_rank; } have;
+    uint64_t full_nnz;                   /* the pair's full rows in buf.full (their number in buf.small[SM_FULL] too) */
+    size_t nbr_map_bytes, mk_set;        /* the bytes of the slot map; of one set of marker tables in buf.h_mk */
+    uint32_t hvg_k, nbr_planes, n_labels;   /* the genes of A and the byte planes of the row set at hand (fastf_res_full_keep) */
+    struct {
+        res_buf_t blk, keys, tmp, small, rows, upc, gpc, h_small, h_upc, h_gpc, h_rows;   /* h_rows.n: the rows there is room for */
+        res_buf_t cpg, upg, h_cpg, h_upg, cellsum, h_cellsum, level;
+        res_buf_t full, fid, h_fid, gx, gfid, h_gfid;   /* gx: the partner column, x of every point row (u32, R->n entries) */
+        res_buf_t nbr, h_nbr, nplanes, lab, h_lab, mk, h_mk, mk_rank;   /* mk_rank: the ranks of the full rows and of the point (host) */
+    } buf;
+    res_cellsum_v h_cs; res_level_v lv; res_fid_v d_fid, h_fid; res_gfid_v d_gfid, h_gfid;   /* with --genes h_gfid.sy and h_gfid.c are buf.h_upg and buf.h_cpg */
+    res_nbr_v d_nbr; res_nbr_pin_v h_nbr; res_lab_v d_lab, h_lab;
 } res_rate_t;
-#define RES_CELLS_HIST_BYTES 512u
+static inline res_rows_t res_rows_point(const res_rate_t *S) { return res_rows(S->buf.rows.p, S->R->n); }   /* the rows of the last point */
+static inline res_rows_t res_rows_full(const res_rate_t *S) { return res_rows(S->buf.full.p, S->R->n); }     /* the full rows of the pair */
 int  fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, const fastf_lists_t *L, const uint64_t *cell_keys, float rate_cell,
                          uint32_t seed, int device, int genes, int cells, res_times_t *T) FASTF_HIDDEN;
 void fastf_res_rate_close(res_rate_t *S) FASTF_HIDDEN;
 /* one point: K1b on the decision plane (H decisions), sort, reduce, rows gathered on the device, per-cell summary to the host
- * (S->h_upc[0 .. n_cells]: UMIs per cell and their sum, S->h_gpc: genes per cell) and, with S->genes, the per-gene summary on the
- * same stream (S->h_cpg: cells per gene, S->h_upg: UMIs per gene); counters = {total, sampled, sampled_valid} */
+ * (S->buf.h_upc[0 .. n_cells]: UMIs per cell and their sum, S->buf.h_gpc: genes per cell) and, with S->genes, the per-gene summary on the
+ * same stream (S->buf.h_cpg: cells per gene, S->buf.h_upg: UMIs per gene); counters = {total, sampled, sampled_valid} */
 int  fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t counters[3], uint64_t *nnz, res_times_t *T) FASTF_HIDDEN;
 /* the rows of the last point into pinned memory, and the three files of bam2db into dir (created) */
 int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label, float rate_depth, const uint64_t counters[3], uint64_t nnz,
@@ -129,70 +114,58 @@ int  fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label
  * fastf_res_search_pass: the device half of fastf_res_point_run up to fastf_dev_cell_summary on the plane d_plane, then one step of the
  * search on the device and ONE device-to-host copy, of the small block (counters, error bits, the step's result): no per-cell or
  * per-gene array and no row leaves the device.  first != 0: the pass whose plane keeps every hit — its U_k(2^32) is kept in
- * S->d_ufull for every cap of the pair and the state is initialised for umi_cap from it (*capped_out: the cells with
- * U_k(2^32) > umi_cap); else S->d_upc is U_k(S->d_probe) and the state moves by the rules of fastf_dev_level_step.  Either way
- * S->d_probe then holds the thresholds of the next pass and *open_out the cells still open.  The error bits of the pass are
+ * S->lv.ufull for every cap of the pair and the state is initialised for umi_cap from it (*capped_out: the cells with
+ * U_k(2^32) > umi_cap); else S->buf.upc is U_k(S->lv.probe) and the state moves by the rules of fastf_dev_level_step.  Either way
+ * S->lv.probe then holds the thresholds of the next pass and *open_out the cells still open.  The error bits of the pass are
  * handled as fastf_res_point_run handles them (RES_NOT_COVERED; a run too long for the group-only sort is sorted fully and the
  * step taken again, which costs that pass a second small copy).  fastf_res_level_init: the state for another cap of the same
- * pair, from S->d_ufull. */
+ * pair, from S->lv.ufull. */
 int  fastf_res_level_room(res_rate_t *S) FASTF_HIDDEN;
 int  fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *point_name, uint64_t umi_cap, int first, uint64_t *open_out,
                            uint64_t *capped_out, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, uint64_t *capped_out, res_times_t *T) FASTF_HIDDEN;
 
-/* --fidelity (S->fidelity).  fastf_res_full_keep: behind a pass on the all-ones plane that left its gathered rows in S->d_rows, their
- * count in S->h_small[SM_NNZ] and their per-cell summary in S->d_upc / S->d_gpc (fastf_res_point_run, or level's first
- * fastf_res_search_pass) — the rows copied into S->d_full, sum_xx by the join of the full rows with themselves, umis_full and
+/* --fidelity (S->cfg.fidelity).  fastf_res_full_keep: behind a pass on the all-ones plane that left its gathered rows in S->buf.rows, their
+ * count in S->buf.h_small[SM_NNZ] and their per-cell summary in S->buf.upc / S->buf.gpc (fastf_res_point_run, or level's first
+ * fastf_res_search_pass) — the rows copied into S->buf.full, sum_xx by the join of the full rows with themselves, umis_full and
  * genes_full to the host: once per pair.  fastf_res_full_run: fastf_res_point_run on d_plane (every hit kept) and that.
- * fastf_res_point_fidelity: behind fastf_res_point_run, the join of the point's rows (still in S->d_rows) with the full rows, S->h_sxy
- * and S->h_syy to the host; a row without a partner fails the point.  fastf_res_full_keep and fastf_res_full_run do nothing without
- * S->fidelity or S->gene_fid, fastf_res_point_fidelity nothing without S->fidelity.
- * --gene-fidelity (S->gene_fid).  fastf_res_full_keep also leaves the pair's sum_x, cells_full and sum_xx per gene in S->h_gsx, S->h_gcf
- * and S->h_gsxx.  fastf_res_point_gene_fidelity: behind fastf_res_point_run (and fastf_res_point_fidelity), before fastf_res_point_cells —
- * every point row's partner count into S->d_gx, then sum_y, cells, sum_yy and sum_xy per gene to the host (S->h_gsy, S->h_gc,
- * S->h_gsyy, S->h_gsxy); a row without a partner fails the point.  Nothing without S->gene_fid */
+ * fastf_res_point_fidelity: behind fastf_res_point_run, the join of the point's rows (still in S->buf.rows) with the full rows, S->h_fid.sxy
+ * and S->h_fid.syy to the host; a row without a partner fails the point.  fastf_res_full_keep and fastf_res_full_run do nothing without
+ * S->cfg.fidelity or S->cfg.gene_fid, fastf_res_point_fidelity nothing without S->cfg.fidelity.
+ * --gene-fidelity (S->cfg.gene_fid).  fastf_res_full_keep also leaves the pair's sum_x, cells_full and sum_xx per gene in S->h_gfid.sx, S->h_gfid.cf
+ * and S->h_gfid.sxx.  fastf_res_point_gene_fidelity: behind fastf_res_point_run (and fastf_res_point_fidelity), before fastf_res_point_cells —
+ * every point row's partner count into S->buf.gx, then sum_y, cells, sum_yy and sum_xy per gene to the host (S->h_gfid.sy, S->h_gfid.c,
+ * S->h_gfid.syy, S->h_gfid.sxy); a row without a partner fails the point.  Nothing without S->cfg.gene_fid */
 int  fastf_res_full_keep(res_rate_t *S, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
-/* --neighbors (S->neighbors).  fastf_res_full_keep also ranks A of the pair from S->h_gsx and S->h_gsxx (S->hvg_k genes), lays the slot
- * map down, and leaves the neighbour sets of the full rows on the device and k_full in S->h_nkf.  fastf_res_point_neighbors: behind
+/* --neighbors (S->cfg.neighbors).  fastf_res_full_keep also ranks A of the pair from S->h_gfid.sx and S->h_gfid.sxx (S->hvg_k genes), lays the slot
+ * map down, and leaves the neighbour sets of the full rows on the device and k_full in S->h_nbr.kf.  fastf_res_point_neighbors: behind
  * fastf_res_point_run, before fastf_res_point_cells — the planes and neighbour sets of the point's rows, the shared counts, k_point and
- * shared to the host (S->h_nkp, S->h_nsh).  A count beyond three planes or a norm of 2^42 and beyond fails the pair by name.  Nothing
- * without S->neighbors */
+ * shared to the host (S->h_nbr.kp, S->h_nbr.sh).  A count beyond three planes or a norm of 2^42 and beyond fails the pair by name.  Nothing
+ * without S->cfg.neighbors */
 int  fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
-/* --labels (S->labels).  fastf_res_rate_open lays lab[] of the pair's cells down and uploads it, once per pair; fastf_res_full_keep votes
+/* --labels (S->cfg.labels).  fastf_res_rate_open lays lab[] of the pair's cells down and uploads it, once per pair; fastf_res_full_keep votes
  * on the full sets and brings pred, same, labelled and conf_X to the host, once per pair.  fastf_res_point_labels: directly behind
  * fastf_res_point_neighbors, before fastf_res_point_cells — one vote call on the point's sets, then pred_point, same_point,
- * labelled_point and conf_Y to the host in one copy.  Nothing without S->labels.  The arrays of S, lab_cells entries apart: */
+ * labelled_point and conf_Y to the host in one copy.  Nothing without S->cfg.labels */
 int  fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
-static inline size_t res_lab_conf_bytes(const res_rate_t *S) { return (size_t)S->n_labels * (S->n_labels + 1) * 4; }
-static inline size_t res_lab_half(const res_rate_t *S) { return 3 * S->lab_cells + res_lab_conf_bytes(S); }      /* pred, same, labelled, conf */
-static inline size_t res_lab_off(const res_rate_t *S, int point) { return S->lab_cells + (size_t)point * res_lab_half(S); }
-static inline const uint8_t *res_lab_pred(const res_rate_t *S, int point) { return S->h_lab + res_lab_off(S, point); }
-static inline const uint8_t *res_lab_same(const res_rate_t *S, int point) { return S->h_lab + res_lab_off(S, point) + S->lab_cells; }
-static inline const uint8_t *res_lab_labelled(const res_rate_t *S, int point) { return S->h_lab + res_lab_off(S, point) + 2 * S->lab_cells; }
-static inline const uint32_t *res_lab_conf(const res_rate_t *S, int point) { return (const uint32_t *)(S->h_lab + res_lab_off(S, point) + 3 * S->lab_cells); }
-/* --markers (S->markers).  fastf_res_full_keep runs fastf_dev_marker_auc once per pair on the planes of the full rows, before the first
+/* --markers (S->cfg.markers).  fastf_res_full_keep runs fastf_dev_marker_auc once per pair on the planes of the full rows, before the first
  * point overwrites the plane buffer, brings the four tables to the host and ranks them (the full ranks stay for every point of the
  * pair).  fastf_res_point_markers: directly behind fastf_res_point_labels — the same on the point's planes (with the point's own P).
- * A row set with three planes fails the pair by name (FASTF_ERR_MARKER_COUNT).  Nothing without S->markers.  The tables of S: */
+ * A row set with three planes fails the pair by name (FASTF_ERR_MARKER_COUNT).  Nothing without S->cfg.markers.  The pinned tables and the ranks of the full rows (0) and of the point (1): */
 int  fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
-static inline size_t res_mk_words(const res_rate_t *S) { return (size_t)S->n_labels * S->hvg_k; }
-static inline size_t res_mk_bytes(uint32_t n_labels, uint32_t K) { return (size_t)n_labels * K * 20 + (((size_t)n_labels + 1) & ~(size_t)1) * 4; }
-static inline const uint64_t *res_mk_s2u(const res_rate_t *S, int point) { return (const uint64_t *)(S->h_mk + (size_t)point * S->mk_set); }
-static inline const uint64_t *res_mk_sum(const res_rate_t *S, int point) { return res_mk_s2u(S, point) + res_mk_words(S); }
-static inline const uint32_t *res_mk_det(const res_rate_t *S, int point) { return (const uint32_t *)(res_mk_s2u(S, point) + 2 * res_mk_words(S)); }
-static inline const uint32_t *res_mk_npl(const res_rate_t *S, int point) { return res_mk_det(S, point) + res_mk_words(S); }
-static inline const uint32_t *res_mk_rank(const res_rate_t *S, int point) { return S->mk_rank + (size_t)point * S->n_labels * FASTF_HVG_TOP; }
+static inline res_mk_v res_mk_host(const res_rate_t *S, int point) { return res_mk_layout(S->buf.h_mk.u8 + (size_t)point * S->mk_set, S->n_labels, S->hvg_k); }
+static inline const uint32_t *res_mk_rank(const res_rate_t *S, int point) { return S->buf.mk_rank.u32 + (size_t)point * S->n_labels * FASTF_HVG_TOP; }
 /* the five above in their order (fidelity, gene fidelity, neighbors, labels, markers), behind fastf_res_point_run and before
  * fastf_res_point_write and fastf_res_point_cells: the one place a further comparison of a point is called from */
 int  fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
 /* --cells, behind a point (S->cells): the keys fastf_res_point_run left sorted fully (skipped where that call already did), K3u
- * into S->d_rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
+ * into S->buf.rows — 12 bytes a record, free once the summaries of fastf_res_point_run have run: fastf_res_point_write gathers into
  * pinned memory and nothing else reads it before the next point's gather overwrites it — then fastf_dev_copy_summary and the four
- * arrays to the host (S->h_hist, S->h_rpc, S->h_npc, S->h_spc).  Call it after fastf_res_point_write, or directly after
+ * arrays to the host (S->h_cs.hist, S->h_cs.rpc, S->h_cs.npc, S->h_cs.spc).  Call it after fastf_res_point_write, or directly after
  * fastf_res_point_run when no rows are written: K3u overwrites the row regions that call gathers from. */
 int  fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
@@ -267,7 +240,7 @@ int fastf_res_reps_open(res_reps_t *P, int on, const char *verb, const char *out
                         uint32_t n_list, int genes, int device, const char *header, const char *genes_header) FASTF_HIDDEN;
 /* a cell rate begins: the names of the features (first call), the accumulators cleared; on_device: d_acc is used */
 int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_device) FASTF_HIDDEN;
-/* point (list value j, seed k) of the cell rate in work: its metrics; with --genes its per-gene array — S != NULL: S->d_cpg on the
+/* point (list value j, seed k) of the cell rate in work: its metrics; with --genes its per-gene array — S != NULL: S->buf.cpg on the
  * device, right behind the point's fastf_res_point_run; else cells_per_gene on the host */
 int fastf_res_reps_point(res_reps_t *P, uint32_t j, uint32_t k, uint32_t n_cells, const double *metrics) FASTF_HIDDEN;
 int fastf_res_reps_genes(res_reps_t *P, res_rate_t *S, uint32_t j, uint32_t k, const uint32_t *cells_per_gene, uint32_t n_features) FASTF_HIDDEN;

@@ -1114,7 +1114,7 @@ static int sweep_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uin
 {
     const res_rate_t *S = p->S;
     (void)ctx;
-    return summary_row_(p->rate_cell, p->job->rates_depth[j], p->seed, counters, nnz, S->h_upc[S->n_cells], S->h_upc, S->h_gpc, S->n_cells, row, cap, metrics);
+    return summary_row_(p->rate_cell, p->job->rates_depth[j], p->seed, counters, nnz, S->buf.h_upc.u64[S->n_cells], S->buf.h_upc.u64, S->buf.h_gpc.u32, S->n_cells, row, cap, metrics);
 }
 
 static const res_verb_t sweep_verb = {

@@ -16,6 +16,8 @@ from sweep_ref import expected_row
 import cap_ref
 import reps_ref
 from test_gpu_sweep import _case, _write
+import test_gpu_markers as TM
+import test_labels_host as LH
 
 pytestmark = pytest.mark.gpu
 
@@ -203,7 +205,8 @@ def test_reps_one_writes_the_files_of_the_plain_run_under_suffixed_names(work, t
 
 def test_summary_only_and_buffer_reuse_give_the_same_tables(work, tmp_path):
     """--summary-only: the two tables alone; FASTF_RES_NO_REUSE=1 (fresh buffers and a fresh blocked copy for every pair) and one
-    env-forced general path (no streaming K1b: SoA records) give the same bytes"""
+    env-forced general path (no streaming K1b: SoA records) give the same bytes; FASTF_RES_NO_REUSE=1 against buffer reuse again with
+    every option of sweep, cap and level on"""
     _, cases, _ = work
     case, bam, b, f = cases["mixed"]
     out = tmp_path / "out"
@@ -220,6 +223,23 @@ def test_summary_only_and_buffer_reuse_give_the_same_tables(work, tmp_path):
             assert open(o / t).read() == open(out / t).read(), (env, t)
         if k == 0:
             assert "laid out 6 times" in r2.stderr
+    # every comparison on, all three verbs, two seeds, the cell rates ascending: the buffers the first pair leaves serve the larger
+    # pairs behind it, the carved blocks by the capacity they were allocated for — the same trees and the same stdout as with fresh
+    # buffers for every pair (each run in a directory of its own, under the same relative -o)
+    lcase = LH.labcase()
+    for verb in ("sweep", "cap", "level"):
+        got = []
+        for k, env in enumerate(({}, {"FASTF_RES_NO_REUSE": "1"})):
+            d = tmp_path / ("%s%d" % (verb, k))
+            d.mkdir()
+            lbam, lb, lfeat, labels = TM._write(d, lcase)
+            r3 = subprocess.run(TM._args(verb, "in.bam", lb.name, lfeat.name, "out", [0.5, 1], TM.GRID[verb]) +
+                                ["--seeds", "926,5", "--genes", "--cells", "--fidelity", "--gene-fidelity", "--neighbors", "--labels", labels.name, "--markers", "5"],
+                                capture_output=True, text=True, timeout=600, cwd=d, env=dict(os.environ, **env))
+            assert r3.returncode == 0, r3.stderr
+            got.append((TM._tree(d / "out"), r3.stdout))
+        assert sorted(got[0][0]) == sorted(got[1][0]) and len(got[0][0]) >= 8 * 11, verb      # (8 points, 11 files each at the least)
+        assert got[0] == got[1], verb
 
 
 def test_cap_seeds_against_the_masked_oracle_per_seed(work, tmp_path):

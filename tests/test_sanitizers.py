@@ -82,3 +82,16 @@ def test_reader_refuses_or_parses_mutated_bams_cleanly(tmp_path):
     findings, outcomes = mod.run(60, seed=3, workdir=str(tmp_path))
     assert not findings, findings[:2]
     assert 0 not in outcomes["container"] and outcomes["records"].get(0, 0) > 10
+
+
+def test_resident_block_layouts_hold_at_their_boundary_counts(tmp_path):
+    """tools/res_layout_check.c under AddressSanitizer + UBSan: every carved block of the resident pair state (res_layout.h alone, no
+    device code) at its boundary counts — aligned arrays that do not overlap, end inside the reported bytes, can be written through
+    the view inside a malloc of exactly those bytes, and lie where the formulas written out in the program put them"""
+    exe = tmp_path / "res_layout_check"
+    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-I" + os.path.join(ROOT, "fastf_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "res_layout_check.c"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    assert "layouts hold" in r.stdout
