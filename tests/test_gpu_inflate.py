@@ -292,3 +292,56 @@ def test_keep_mode_fixtures_crc_and_fetch():
     finally:
         L.fastf_gpuinf_destroy(g)
         pin.free()
+
+
+CRC_SIZES = (1, 63, 64, 65, 127, 4032, 4033, 65280, 65535)
+
+
+def _crc_flip_at(isize, where):
+    """the byte a flip lands on: byte 0, the last byte, or an end of lane 31's slice of gr_crc_kernel (blocks of 63 bytes or fewer:
+    lane (isize - 1) // 2, since lane 31 holds nothing there)"""
+    per = (isize + 63) // 64
+    lane = 31 if isize > 63 else (isize - 1) // 2
+    lo, hi = lane * per, min(lane * per + per, isize)
+    assert lo < hi
+    return {"first": 0, "last": isize - 1, "slice-first": lo, "slice-last": hi - 1}[where]
+
+
+def test_keep_mode_crc_covers_every_slice_and_the_short_last_lanes():
+    """blocks of 1 to 65535 bytes in one keep-mode launch: with the true CRC-32 every block reports 0; with the CRC-32 of its bytes
+    with ONE byte flipped (the first, the last, either end of lane 31's slice) every block reports exactly the CRC bit.  A slice
+    that the device left out of its CRC, or a short last lane it read too far, would let one of these pass."""
+    import torch  # noqa: F401
+    L = _api()
+    pin = _Pinned(L)
+    rng = np.random.default_rng(31)
+    data = [rng.integers(0, 256, size=n, dtype=np.uint8).tobytes() for n in CRC_SIZES]
+    entries = []
+    for d in data:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        entries.append(("crc%d" % len(d), co.compress(d) + co.flush(), len(d)))
+    uoffs = [4099 + sum(CRC_SIZES[:i]) for i in range(len(CRC_SIZES))]
+    assert {CRC_SIZES[i] - _crc_flip_at(CRC_SIZES[i], "last") for i in range(len(CRC_SIZES))} == {1}
+    assert _crc_flip_at(4033, "slice-first") == 31 * 64 and _crc_flip_at(65, "slice-last") == 63 and _crc_flip_at(63, "slice-first") == 31
+    g = L.fastf_gpuinf_create(0); assert g, L.fastf_last_error()
+    try:
+        cbuf, desc = _pack(pin, entries, uoffs)
+
+        def keep(crc):
+            status = (C.c_uint8 * len(entries))(*([0xFF] * len(entries)))
+            crc = np.asarray(crc, dtype=np.uint32)
+            assert L.fastf_gpuinf_submit_keep(g, cbuf, desc, len(entries), 0, crc.ctypes.data) == 0, L.fastf_last_error()
+            assert L.fastf_gpuinf_wait(g, status, None) == 0, L.fastf_last_error()
+            return list(status)
+
+        assert keep([zlib.crc32(d) for d in data]) == [0] * len(data)
+        for where in ("first", "last", "slice-first", "slice-last"):
+            crc = []
+            for d in data:
+                m = bytearray(d); m[_crc_flip_at(len(d), where)] ^= 0x01
+                assert zlib.crc32(bytes(m)) != zlib.crc32(d)
+                crc.append(zlib.crc32(bytes(m)))
+            assert keep(crc) == [2] * len(data), where
+    finally:
+        L.fastf_gpuinf_destroy(g)
+        pin.free()
