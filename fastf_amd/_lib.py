@@ -94,7 +94,7 @@ ABI_SYMBOLS = [
     "fastf_engine_push_pinned", "fastf_engine_wait_input",
     "fastf_pinned_alloc", "fastf_pinned_free", "fastf_pinned_register", "fastf_pinned_unregister", "fastf_debug_live_registrations", "fastf_pick_devices",
     "fastf_engine_finish", "fastf_engine_lend_rows", "fastf_engine_umi_rows", "fastf_engine_reset", "fastf_engine_key_bits",
-    "fastf_engine_skip_bits", "fastf_engine_sort_passes", "fastf_engine_table_modes", "fastf_engine_cell_scratch_bytes",
+    "fastf_engine_skip_bits", "fastf_engine_sort_passes", "fastf_engine_grids", "fastf_dev_scan_tiles", "fastf_engine_table_modes", "fastf_engine_cell_scratch_bytes",
     "fastf_dev_count_hits", "fastf_dev_count_hits_blocked", "fastf_dev_block_bytes", "fastf_dev_block_records", "fastf_dev_set_regions", "fastf_dev_draw_bits", "fastf_dev_mt_decisions", "fastf_dev_probe_pack", "fastf_dev_probe_pack_wide", "fastf_dev_adopt_wide", "fastf_engine_is_wide", "fastf_dev_probe_capacity", "fastf_dev_sort", "fastf_dev_reduce", "fastf_dev_rows_gather", "fastf_engine_device_records",
     "fastf_dev_umi_rows", "fastf_dev_reserve", "fastf_dev_error_bits",
     "fastf_dev_clear_error_bits", "fastf_kernel_names",
@@ -249,6 +249,8 @@ def lib():
     L.fastf_dev_rows_gather.argtypes = [vp, vp, vp, vp, vp, vp]
     L.fastf_engine_skip_bits.argtypes = [vp, C.POINTER(u32)]
     L.fastf_engine_sort_passes.argtypes = [vp, u32, C.POINTER(u32)]
+    L.fastf_engine_grids.argtypes = [vp, u64, u64, C.POINTER(u32)]
+    L.fastf_dev_scan_tiles.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp]
     L.fastf_engine_table_modes.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fastf_dev_umi_rows.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
     L.fastf_dev_reserve.argtypes = [vp, u64, u64]

@@ -309,6 +309,10 @@ struct fastf_engine {
     bool narrow = false, genes_one_family = false;
     u64 slots_used = 0, slot_cap = 0; u32 rgn_n = 0, rgn_cap = 0;
     DevBuf d_scanblk;                    // chunk totals of a scan over more than 16 384 tiles
+    // grid widths, read once at create ("Grid switches"): the CU count every capped grid is cut from (FASTF_GRID_CUS,
+    // 1 .. the device's; unset: the device's), the cap of the sort's tile grids (FASTF_TILE_GRID_CAP; 0: 32 per CU) and K3's
+    // workgroups per CU (FASTF_K3_PER_CU).  Test and diagnostic switches: they narrow the grids so that workgroups walk many tiles.
+    u32 grid_cus = 256; int tile_grid_cap = 0; u32 k3_per_cu = 4;
     // K3: row regions (one slot per key: a workgroup's rows go to the slots of its own chunk), rows per chunk and their bases
     DevBuf d_rg_feature, d_rg_cell, d_rg_count, d_rg_ukeys, d_spanrows, d_spanbase, d_giant;
     u32 rg_n = 0; bool rg_umi = false;   // chunks of the last reduce (0: none) and its kind
@@ -336,7 +340,24 @@ struct fastf_engine {
 enum { SM_KEYCOUNT = 0, SM_COUNTERS = 32, SM_NNZ = 64, SM_NROWS_U = 65, SM_N = 66, SM_RUNNING = 96, SM_DRAWBASE = 128, SM_WORDS = 160 };
 
 static int set_scatter_lds_limit();
-static u32 g_cu_count = 256;
+static u32 g_cu_count = 256;             // the device of the engine created last (choose_sort_ipt); the grids read fastf_engine::grid_cus
+// ---- grids of the step: every capped grid is one of these (fastf_engine_grids reports them) ----
+// K1a: LDS form (two tiles per turn), filtered L2 form
+static u32 k1a_lds_grid(const fastf_engine* e, u32 tiles) { return std::min<u32>(e->cells_blocks_per_cu * e->grid_cus, (tiles + 1) / 2); }
+static u32 k1a_filtered_grid(const fastf_engine* e, u32 tiles) { return std::min<u32>(tiles, 4 * e->grid_cus); }
+// block_records_kernel: four waves per workgroup, a wave walks units
+static u32 block_records_grid(const fastf_engine* e, u64 units) { return (u32)std::min<u64>((units + 3) / 4, 16ull * e->grid_cus); }
+// draw_bits_kernel / draw_planes_kernel: a wave walks 64-draw words (never 0: + 1)
+// (cus: the engine's grid_cus; the engine-less test hook passes the device's)
+static u32 draw_bits_grid(u32 cus, u64 n) { return (u32)std::min<u64>((n + 255) / 256 + 1, 8ull * cus); }
+// K1b tile form with the gene table in LDS
+static u32 k1b_tile_grid(const fastf_engine* e, u32 tiles) { return std::min<u32>(tiles, e->genes_blocks_per_cu * e->grid_cus); }
+// rgn_hist_kernel: a workgroup walks regions
+static u32 rgn_hist_grid(const fastf_engine* e, u32 R) { return std::min<u32>(R, 8 * e->grid_cus); }
+// giant_groups_kernel: the last workgroup scans the chunks' rows, the others walk the items with stride grid - 1 (>= 1)
+static u32 giant_grid(const fastf_engine* e) { return e->grid_cus + 1; }
+// pair_heads / pair_rows / pair_copies (distinct pairs of wide keys): a workgroup walks UW_TILE tiles
+static u32 pair_grid(const fastf_engine* e, u64 T) { return (u32)std::min<u64>(T, 16ull * e->grid_cus); }
 // multi-device engine (multi_engine.hpp, included at the end of this file)
 static int multi_create(const fastf_engine_config_t* cfg, fastf_engine* e);
 static void multi_destroy(fastf_engine* e);
@@ -607,6 +628,15 @@ extern "C" int fastf_engine_create(const fastf_engine_config_t* cfg, fastf_engin
 
     fastf_engine* e = new fastf_engine();
     e->device = cfg->device;
+    {   // grid switches (tests and diagnosis): this engine's alone, read here like the other switches
+        e->grid_cus = g_cu_count;
+        const char* gc = getenv("FASTF_GRID_CUS");
+        if (gc) e->grid_cus = (u32)std::min<long>(std::max<long>(atol(gc), 1), (long)g_cu_count);
+        const char* tc = getenv("FASTF_TILE_GRID_CAP");
+        e->tile_grid_cap = tc ? std::max(atoi(tc), 8) : 0;
+        const char* kc = getenv("FASTF_K3_PER_CU");
+        e->k3_per_cu = kc ? (u32)std::max(atoi(kc), 1) : 4u;
+    }
     e->n_cells = cfg->n_cells; e->n_features = cfg->n_features;
     e->cell16 = cfg->n_cells <= 65535u && !getenv("FASTF_CELL_SCRATCH_32");
     e->cell_bits = bits_for(cfg->n_cells);
@@ -879,7 +909,7 @@ static int launch_probe_cells(fastf_engine* e, const u64* cb, u64 n, u64* d_tota
     const CellOut cout = blk ? CellOut{blk, blk_run_bytes(e->cell16, e->narrow), blk_cell_off(e->narrow)} : CellOut{e->d_cellidx.p, 0u, 0u};
     t_begin(e, s);
     if (e->use_lds_cells) {                          // tile counts are all-zero here: scan_tiles_kernel clears what it reads
-        const u32 grid = std::min<u32>(e->cells_blocks_per_cu * g_cu_count, (tiles + 1) / 2);
+        const u32 grid = k1a_lds_grid(e, tiles);
         if (e->cells_blocks_per_cu >= 2)
             hipLaunchKernelGGL(probe_cells_lds_kernel<true>, dim3(grid), dim3(1024), e->lds_cells.bytes, s, cb, n, e->lds_cells,
                                cout, e->cell16, (u32*)e->d_tilecnt.p, (u32*)e->d_halfhits.p, tiles);
@@ -887,7 +917,7 @@ static int launch_probe_cells(fastf_engine* e, const u64* cb, u64 n, u64* d_tota
             hipLaunchKernelGGL(probe_cells_lds_kernel<false>, dim3(grid), dim3(1024), e->lds_cells.bytes, s, cb, n, e->lds_cells,
                                cout, e->cell16, (u32*)e->d_tilecnt.p, (u32*)e->d_halfhits.p, tiles);
     } else if (e->cell_filter.bits) {
-        const u32 grid = std::min<u32>(tiles, 4 * g_cu_count);
+        const u32 grid = k1a_filtered_grid(e, tiles);
         hipLaunchKernelGGL(probe_cells_filtered_kernel, dim3(grid), dim3(K1_THREADS), (e->cell_filter.mask + 1u) / 8u, s, cb, n,
                            e->cells, e->cell_filter, cout, e->cell16, (u32*)e->d_tilecnt.p, (u32*)e->d_halfhits.p, tiles);
     } else {
@@ -921,7 +951,7 @@ extern "C" int fastf_dev_block_bytes(const fastf_engine_t* e, uint64_t n, uint64
 // the engine's layout (wide or narrow runs) from device-resident SoA
 static void launch_block_records(const fastf_engine* e, const u64* gx, const u32* umi, const u32* meta, u64 n, void* blk, hipStream_t s) {
     const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    const dim3 grid((u32)std::min<u64>((units + 3) / 4, 16ull * g_cu_count));
+    const dim3 grid(block_records_grid(e, units));
     if (e->narrow) hipLaunchKernelGGL(block_records_kernel<true>, grid, dim3(256), 0, s, gx, umi, meta, n, (unsigned char*)blk,
                                       blk_run_bytes(e->cell16, true), e->lds_genes.family, e->L);
     else hipLaunchKernelGGL(block_records_kernel<false>, grid, dim3(256), 0, s, gx, umi, meta, n, (unsigned char*)blk,
@@ -947,9 +977,9 @@ extern "C" int fastf_dev_count_hits_blocked(fastf_engine_t* e, const uint64_t* d
 } FASTF_CATCH_INT
 
 // draws[i] < threshold as bit (first + i) of a ring of decisions (ring_mask = bits - 1; ~0: a linear array that starts at bit 0)
-static int launch_draw_bits(u64 threshold, const u32* d_draws, u64 n, u32* d_bits, hipStream_t s, u64 first = 0, u64 ring_mask = ~0ull) {
+static int launch_draw_bits(u32 cus, u64 threshold, const u32* d_draws, u64 n, u32* d_bits, hipStream_t s, u64 first = 0, u64 ring_mask = ~0ull) {
     if (n == 0) return 0;
-    const u32 grid = (u32)std::min<u64>((n + 255) / 256 + 1, 8ull * g_cu_count);
+    const u32 grid = draw_bits_grid(cus, n);
     hipLaunchKernelGGL(draw_bits_kernel, dim3(grid), dim3(256), 0, s, d_draws, n, threshold, d_bits, first, ring_mask);
     HIP_OK(hipGetLastError());
     return 0;
@@ -957,9 +987,9 @@ static int launch_draw_bits(u64 threshold, const u32* d_draws, u64 n, u32* d_bit
 // the same for several thresholds at once: plane j of `planes` (plane_stride 64-bit words apart) = draws[i] < thresholds[j], the words
 // read once per PLANES_MAX thresholds (draw_planes_kernel, sweep_kernels.hpp)
 struct PlaneOut { const u64* thresholds; u32 n; u64* planes; u64 stride; };
-static int launch_draw_planes(const PlaneOut& po, const u32* d_draws, u64 n, hipStream_t s) {
+static int launch_draw_planes(u32 cus, const PlaneOut& po, const u32* d_draws, u64 n, hipStream_t s) {
     if (n == 0) return 0;
-    const u32 grid = (u32)std::min<u64>((n + 255) / 256 + 1, 8ull * g_cu_count);
+    const u32 grid = draw_bits_grid(cus, n);
     for (u32 j0 = 0; j0 < po.n; j0 += PLANES_MAX) {
         PlaneSet ps{}; ps.n = std::min<u32>(PLANES_MAX, po.n - j0);
         for (u32 j = 0; j < ps.n; ++j) ps.threshold[j] = po.thresholds[j0 + j];
@@ -972,7 +1002,7 @@ static int launch_draw_planes(const PlaneOut& po, const u32* d_draws, u64 n, hip
 // the generator writes words into `words` (grown to fit), draw_bits_kernel packs them behind it on the same stream
 // (po: the decisions go to its planes instead — linear arrays from bit 0; d_ring, first, ring_mask and threshold are not used)
 // (words_only: the raw draws stay in `words` and nothing is packed — fastf_dev_cell_decisions compares them per cell)
-static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr,
+static int launch_mt_decisions(u32 cus, hipStream_t s, u32* d_mt, DevBuf& words, u32* d_ring, u64 first, u64 count, u64 ring_mask, u64 threshold, const PlaneOut* po = nullptr,
                                bool words_only = false) {
     if (count == 0) return 0;
     if (words.bytes < count * 4) {
@@ -983,8 +1013,8 @@ static int launch_mt_decisions(hipStream_t s, u32* d_mt, DevBuf& words, u32* d_r
     hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(256), 0, s, d_mt, (u32*)words.p, 0ull, count, ~0ull);
     HIP_OK(hipGetLastError());
     if (words_only) return 0;
-    if (po) return launch_draw_planes(*po, (const u32*)words.p, count, s);
-    return launch_draw_bits(threshold, (const u32*)words.p, count, d_ring, s, first, ring_mask);
+    if (po) return launch_draw_planes(cus, *po, (const u32*)words.p, count, s);
+    return launch_draw_bits(cus, threshold, (const u32*)words.p, count, d_ring, s, first, ring_mask);
 }
 // where a stream that stood at read index idx of its block stands after n more draws
 static u32 mt_idx_after(u32 idx, u64 n) {
@@ -1004,7 +1034,7 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
     static const bool no_par = getenv("FASTF_MT_SERIAL") != nullptr;
     const u64 head = *idx < MT_N ? std::min<u64>(count, MT_N - *idx) : 0;          // to the next block boundary
     if (count < MT_PAR_MIN || no_par) {
-        if (launch_mt_decisions(s, d_mt, words, d_ring, first, count, ring_mask, threshold, po, words_only)) return 1;
+        if (launch_mt_decisions(e->grid_cus, s, d_mt, words, d_ring, first, count, ring_mask, threshold, po, words_only)) return 1;
         *idx = mt_idx_after(*idx, count);
         return 0;
     }
@@ -1056,8 +1086,8 @@ static int launch_mt_decisions_par(fastf_engine* e, hipStream_t s, u32* d_mt, u3
     }
     *idx = mt_idx_after(MT_N, last);
     if (words_only) return 0;
-    if (po) return launch_draw_planes(*po, (const u32*)w, count, s);
-    return launch_draw_bits(threshold, (const u32*)w, count, d_ring, s, first, ring_mask);
+    if (po) return launch_draw_planes(e->grid_cus, *po, (const u32*)w, count, s);
+    return launch_draw_bits(e->grid_cus, threshold, (const u32*)w, count, d_ring, s, first, ring_mask);
 }
 
 // The decisions of `n_draws` draws of the stream init_genrand(seed) + skip, from the device's own generator (the parallel
@@ -1107,7 +1137,7 @@ extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell,
     HIP_OK(hipMemsetAsync(d_umis_per_cell, 0, ((size_t)n_cells + 1) * sizeof(u64), s));
     if (n_cells) HIP_OK(hipMemsetAsync(d_genes_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
     if (!d_cell || !d_count) return 0;                  // (no row buffer: a reduce of nothing)
-    hipLaunchKernelGGL(cell_summary_kernel, dim3(2 * g_cu_count), dim3(256), 0, s, d_cell, d_count, (const u64*)d_nnz, n_cells,
+    hipLaunchKernelGGL(cell_summary_kernel, dim3(2 * e->grid_cus), dim3(256), 0, s, d_cell, d_count, (const u64*)d_nnz, n_cells,
                        (u64*)d_umis_per_cell, d_genes_per_cell);
     HIP_OK(hipGetLastError());
     dbg_sync(s, "cell summary");
@@ -1164,7 +1194,7 @@ extern "C" int fastf_dev_fidelity(fastf_engine_t* e, const uint32_t* d_feature_f
     if (!d_feature || !d_cell || !d_count) return 0;    // (no row buffer: a join of nothing)
     if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_fidelity: point rows and no full rows");
     u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
-    hipLaunchKernelGGL(fidelity_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
+    hipLaunchKernelGGL(fidelity_kernel, dim3(FID_BLOCKS_PER_CU * e->grid_cus), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
                        (const u64*)d_nnz_full, d_feature, d_cell, d_count, (const u64*)d_nnz, n_cells, (u64*)d_sum_xy, (u64*)d_sum_yy, err);
     return join_end("fastf_dev_fidelity", s, err);
 } FASTF_CATCH_INT
@@ -1184,11 +1214,11 @@ extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_featu
     const HistPlan pl = hist_plan(n_features, GENE_LDS_GENES, GENE_LDS_RANGES, "FASTF_GENE_LDS_RANGES", sizeof(u64));
     if (pl.lds_form) {
         if (lds_attr_once(e->gene_lds_attr, GENE_LDS_GENES * sizeof(u64), {(const void*)gene_summary_kernel<true>})) return 1;
-        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)g_cu_count / pl.n_ranges);
+        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)e->grid_cus / pl.n_ranges);
         hipLaunchKernelGGL(gene_summary_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_count, (const u64*)d_nnz, n_features,
                            d_cells_per_gene, (u64*)d_umis_per_gene, pl.n_ranges);
     } else {
-        hipLaunchKernelGGL(gene_summary_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_count, (const u64*)d_nnz, n_features,
+        hipLaunchKernelGGL(gene_summary_kernel<false>, dim3(2 * e->grid_cus), dim3(GENE_THREADS), 0, s, d_feature, d_count, (const u64*)d_nnz, n_features,
                            d_cells_per_gene, (u64*)d_umis_per_gene, 1u);
     }
     HIP_OK(hipGetLastError());
@@ -1208,7 +1238,7 @@ extern "C" int fastf_dev_partner_counts(fastf_engine_t* e, const uint32_t* d_fea
     if (!d_x) return set_err("fastf_dev_partner_counts: point rows and no partner column");
     if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_partner_counts: point rows and no full rows");
     u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
-    hipLaunchKernelGGL(partner_counts_kernel, dim3(FID_BLOCKS_PER_CU * g_cu_count), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
+    hipLaunchKernelGGL(partner_counts_kernel, dim3(FID_BLOCKS_PER_CU * e->grid_cus), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
                        (const u64*)d_nnz_full, d_feature, d_cell, (const u64*)d_nnz, d_x, err);
     return join_end("fastf_dev_partner_counts", s, err);
 } FASTF_CATCH_INT
@@ -1227,11 +1257,11 @@ extern "C" int fastf_dev_gene_moments(fastf_engine_t* e, const uint32_t* d_featu
     const HistPlan pl = hist_plan(n_features, GMOM_LDS_GENES, GMOM_LDS_RANGES, "FASTF_GENE_MOMENTS_LDS_RANGES", 2 * sizeof(u64));
     if (pl.lds_form) {
         if (lds_attr_once(e->gmom_lds_attr, GMOM_LDS_GENES * 2 * sizeof(u64), {(const void*)gene_moments_kernel<true>})) return 1;
-        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)g_cu_count / pl.n_ranges);
+        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)e->grid_cus / pl.n_ranges);
         hipLaunchKernelGGL(gene_moments_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
                            (u64*)d_sum_ab, (u64*)d_sum_bb, pl.n_ranges);
     } else {
-        hipLaunchKernelGGL(gene_moments_kernel<false>, dim3(2 * g_cu_count), dim3(GENE_THREADS), 0, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
+        hipLaunchKernelGGL(gene_moments_kernel<false>, dim3(2 * e->grid_cus), dim3(GENE_THREADS), 0, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
                            (u64*)d_sum_ab, (u64*)d_sum_bb, 1u);
     }
     HIP_OK(hipGetLastError());
@@ -1255,7 +1285,7 @@ extern "C" int fastf_dev_neighbor_planes(fastf_engine_t* e, const uint32_t* d_fe
         if (e->d_nbr.ensure(64)) return 1;
         u32* const d_max = (u32*)e->d_nbr.p;
         HIP_OK(hipMemsetAsync(d_max, 0, 64, s));
-        hipLaunchKernelGGL(nbr_max_count_kernel, dim3(4 * g_cu_count), dim3(256), 0, s, d_feature, d_count, (const u64*)d_nnz, d_slot_map, n_features, d_max);
+        hipLaunchKernelGGL(nbr_max_count_kernel, dim3(4 * e->grid_cus), dim3(256), 0, s, d_feature, d_count, (const u64*)d_nnz, d_slot_map, n_features, d_max);
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(s));
         if (copy_d2h(&max_count, d_max, sizeof max_count)) return 1;
@@ -1271,7 +1301,7 @@ extern "C" int fastf_dev_neighbor_planes(fastf_engine_t* e, const uint32_t* d_fe
     if (need > planes_bytes) return set_err("fastf_dev_neighbor_planes: %u planes of %u x %u bytes need %zu bytes, the buffer has %zu", P, n_pad, K_pad, need, planes_bytes);
     HIP_OK(hipMemsetAsync(d_planes, 0, need, s));
     if (rows && K && n_cells) {
-        hipLaunchKernelGGL(nbr_planes_kernel, dim3(4 * g_cu_count), dim3(256), 0, s, d_feature, d_cell, d_count, (const u64*)d_nnz, d_slot_map, n_features,
+        hipLaunchKernelGGL(nbr_planes_kernel, dim3(4 * e->grid_cus), dim3(256), 0, s, d_feature, d_cell, d_count, (const u64*)d_nnz, d_slot_map, n_features,
                            n_cells, K, n_pad, K_pad, P, (unsigned char*)d_planes);
         HIP_OK(hipGetLastError());
     }
@@ -1309,7 +1339,7 @@ extern "C" int fastf_dev_neighbors(fastf_engine_t* e, const void* d_planes, uint
     if (e->d_nbr.ensure(64)) return 1;
     u64* const d_max = (u64*)e->d_nbr.p + 1;
     HIP_OK(hipMemsetAsync(d_max, 0, sizeof(u64), s));
-    hipLaunchKernelGGL(nbr_norms_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * g_cu_count)), dim3(256), 0, s, (const unsigned char*)d_planes, n_cells, n_pad, K_pad,
+    hipLaunchKernelGGL(nbr_norms_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_planes, n_cells, n_pad, K_pad,
                        planes, (u64*)d_norms, d_max);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(s));
@@ -1355,10 +1385,10 @@ static int label_votes_launch(fastf_engine* e, hipStream_t s, bool lds_form, con
     const u32 per_pass = LAB_THREADS / G, blocks_all = (n + per_pass - 1) / per_pass;
     if (lds_form) {
         // one workgroup a CU at the most: each zeroes and flushes its own copy of the counts
-        hipLaunchKernelGGL((label_votes_kernel<G, true>), dim3(std::min<u32>(blocks_all, (u32)g_cu_count)), dim3(LAB_THREADS), (size_t)lab_conf_words(n_labels) * sizeof(u32), s,
+        hipLaunchKernelGGL((label_votes_kernel<G, true>), dim3(std::min<u32>(blocks_all, (u32)e->grid_cus)), dim3(LAB_THREADS), (size_t)lab_conf_words(n_labels) * sizeof(u32), s,
                            idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
     } else {
-        hipLaunchKernelGGL((label_votes_kernel<G, false>), dim3(std::min<u32>(blocks_all, 8u * (u32)g_cu_count)), dim3(LAB_THREADS), 0, s,
+        hipLaunchKernelGGL((label_votes_kernel<G, false>), dim3(std::min<u32>(blocks_all, 8u * (u32)e->grid_cus)), dim3(LAB_THREADS), 0, s,
                            idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
     }
     (void)e;
@@ -1435,7 +1465,7 @@ extern "C" int fastf_dev_marker_auc(fastf_engine_t* e, const void* d_planes, uin
     }
     if (!n_cells) return 0;
     if (!d_lab || (K && !d_planes)) return set_err("fastf_dev_marker_auc: null argument");
-    hipLaunchKernelGGL(marker_labels_kernel, dim3(std::min<u32>((n_cells + 255u) / 256u, (u32)g_cu_count)), dim3(256), 0, s, (const unsigned char*)d_lab, n_cells, n_labels, d_n_per_label);
+    hipLaunchKernelGGL(marker_labels_kernel, dim3(std::min<u32>((n_cells + 255u) / 256u, (u32)e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_lab, n_cells, n_labels, d_n_per_label);
     HIP_OK(hipGetLastError());
     if (!K) return 0;
     const bool lds_form = fastf_marker_auc_form(planes, n_labels) == 1;
@@ -1460,7 +1490,7 @@ extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cell
                                        uint64_t* d_sum, uint64_t* d_sumsq, void* stream) FASTF_TRY {
     DEV_ENTRY(!e || (n_features && (!d_cells_per_gene || !d_detected || !d_sum || !d_sumsq)), "null argument");
     if (!n_features) return 0;
-    const u32 grid = std::min<u32>((n_features + GENE_REPS_THREADS - 1) / GENE_REPS_THREADS, 4u * (u32)g_cu_count);
+    const u32 grid = std::min<u32>((n_features + GENE_REPS_THREADS - 1) / GENE_REPS_THREADS, 4u * (u32)e->grid_cus);
     hipLaunchKernelGGL(gene_reps_kernel, dim3(grid), dim3(GENE_REPS_THREADS), 0, (hipStream_t)stream, d_cells_per_gene, n_features,
                        (u64*)d_detected, (u64*)d_sum, (u64*)d_sumsq);
     HIP_OK(hipGetLastError());
@@ -1499,7 +1529,7 @@ extern "C" int fastf_dev_copy_summary(fastf_engine_t* e, const uint64_t* d_ukeys
     }
     HIP_OK(hipMemsetAsync(d_hist, 0, ((size_t)COPY_BINS + 1) * sizeof(u64), s));
     const CopyOut out{d_reads_per_cell, d_null_reads_per_cell, d_single_per_cell};
-    hipLaunchKernelGGL(copy_summary_kernel, dim3(2 * g_cu_count), dim3(256), 0, s, (const u64*)d_ukeys, d_ncopy, (const u64*)d_nrows, n_cells,
+    hipLaunchKernelGGL(copy_summary_kernel, dim3(2 * e->grid_cus), dim3(256), 0, s, (const u64*)d_ukeys, d_ncopy, (const u64*)d_nrows, n_cells,
                        e->L.cell_shift, e->L.umi_bits + e->L.len_bits, out, (u64*)d_hist);
     HIP_OK(hipGetLastError());
     dbg_sync(s, "copy summary");
@@ -1527,10 +1557,10 @@ extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_
     const HistPlan pl = hist_plan(e->n_cells, CAP_LDS_CELLS, CAP_LDS_RANGES, "FASTF_CAP_LDS_RANGES", sizeof(u32));
     if (pl.lds_form) {
         if (lds_attr_once(e->cap_lds_attr, CAP_LDS_CELLS * sizeof(u32), {(const void*)cell_hits_kernel<true>})) return 1;
-        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)pl.per_cu * g_cu_count / pl.n_ranges));
+        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)pl.per_cu * e->grid_cus / pl.n_ranges));
         hipLaunchKernelGGL(cell_hits_kernel<true>, dim3(groups * pl.n_ranges), dim3(CAP_HITS_THREADS), pl.lds_bytes, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, pl.n_ranges);
     } else {
-        const u32 grid = (u32)std::min<u64>((units + WAVES - 1) / WAVES, 2ull * g_cu_count);
+        const u32 grid = (u32)std::min<u64>((units + WAVES - 1) / WAVES, 2ull * e->grid_cus);
         hipLaunchKernelGGL(cell_hits_kernel<false>, dim3(grid), dim3(CAP_HITS_THREADS), 0, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, 1u);
     }
     HIP_OK(hipGetLastError());
@@ -1572,7 +1602,7 @@ extern "C" int fastf_dev_cell_decisions(fastf_engine_t* e, uint64_t n, const voi
         e->mtwords_kept = true; e->mtwords_seed = seed; e->mtwords_skip = skip; e->mtwords_n = n_draws;
     }
     const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    const u32 grid = (u32)std::min<u64>((units + 3) / 4, 8ull * g_cu_count);
+    const u32 grid = (u32)std::min<u64>((units + 3) / 4, 8ull * e->grid_cus);
     hipLaunchKernelGGL(cell_decisions_kernel, dim3(grid), dim3(256), 0, s, cell_scratch_of(e, d_blocked), e->cell16, n, (const u64*)e->d_tilebase.p,
                        (const u32*)e->d_halfhits.p, (const u32*)e->d_mtwords.p, n_draws, (const u64*)d_thresholds, e->n_cells, (u64*)d_bits_out);
     HIP_OK(hipGetLastError());
@@ -1634,7 +1664,7 @@ extern "C" int fastf_devmem_sync(void) FASTF_TRY {
 
 extern "C" int fastf_dev_draw_bits(fastf_engine_t* e, const uint32_t* d_draws, uint64_t n_draws, uint32_t* d_bits_out, void* stream) FASTF_TRY {
     DEV_ENTRY(!e || (n_draws && (!d_draws || !d_bits_out)), "null argument");
-    return launch_draw_bits(e->threshold, d_draws, n_draws, d_bits_out, (hipStream_t)stream);
+    return launch_draw_bits(e->grid_cus, e->threshold, d_draws, n_draws, d_bits_out, (hipStream_t)stream);
 } FASTF_CATCH_INT
 
 // the streaming K1b over `tiles` K1a tiles: workgroups (at most two per CU: 12 or 16 waves each) and the key slots of one
@@ -1645,7 +1675,7 @@ extern "C" int fastf_dev_draw_bits(fastf_engine_t* e, const uint32_t* d_draws, u
 static void stream_geometry(const fastf_engine* e, u64 tiles, u32* grid, u64* region) {
     const u32 waves = (e->genes_blocks_per_cu >= 2 ? K1S_THREADS : K1S_THREADS_ROOMY) / WAVE;
     const u64 units = std::max<u64>(tiles, 1) * (K1_TILE / K1S_UNIT);
-    const u64 g = std::max<u64>(1, std::min<u64>((units + 4 * waves - 1) / (4 * waves), (u64)std::min<u32>(e->genes_blocks_per_cu, 2) * g_cu_count));
+    const u64 g = std::max<u64>(1, std::min<u64>((units + 4 * waves - 1) / (4 * waves), (u64)std::min<u32>(e->genes_blocks_per_cu, 2) * e->grid_cus));
     const u64 rounds = (units + g * waves - 1) / (g * waves);
     *grid = (u32)g; *region = ((rounds + K1S_SUB - 1) / K1S_SUB) * waves * K1S_UNIT;
 }
@@ -1734,7 +1764,7 @@ static int launch_probe(fastf_engine* e, const ProbeJob& j, hipStream_t s) {
             e->rgn_hist_n = n_rgn; e->rgn_hist_shift = e->skip_bits;
         }
     } else if (e->use_lds_genes) {
-        const u32 grid = std::min<u32>(tiles, e->genes_blocks_per_cu * g_cu_count);
+        const u32 grid = k1b_tile_grid(e, tiles);
         if (e->genes_blocks_per_cu >= 2) hipLaunchKernelGGL((filter_pack_kernel<true, false>), dim3(grid), dim3(K1B_THREADS), e->lds_genes.bytes, s, p);
         else hipLaunchKernelGGL((filter_pack_kernel<true, true>), dim3(grid), dim3(K1B_THREADS), e->lds_genes.bytes, s, p);
     } else {
@@ -1753,7 +1783,7 @@ static int draws_to_bits(fastf_engine* e, uint32_t flags, u64 n, const uint32_t*
     if (n && n_draws && !*d_draws) return set_err("null d_draws");
     if ((flags & FASTF_PROBE_DRAW_BITS) || !n || !n_draws) return 0;
     if (e->d_dbits.ensure(((n_draws + 63) / 64) * 8)) return 1;
-    if (launch_draw_bits(e->threshold, *d_draws, n_draws, (u32*)e->d_dbits.p, s)) return 1;
+    if (launch_draw_bits(e->grid_cus, e->threshold, *d_draws, n_draws, (u32*)e->d_dbits.p, s)) return 1;
     *d_draws = (const uint32_t*)e->d_dbits.p;
     return 0;
 }
@@ -1816,16 +1846,17 @@ extern "C" int fastf_dev_probe_capacity(const fastf_engine_t* e, uint64_t n, uin
 static u64* g_stamps = nullptr;   // diagnostic builds only (-DFASTF_STAMPS): per-tile phase timestamps of the last scatter
 extern "C" void fastf_debug_set_stamps(void* p) { g_stamps = (u64*)p; }
 // grid of the tile kernels: whole rounds over the 8 XCDs, capped — beyond the cap the workgroups walk their tiles
-static u32 tile_grid(u32 T) {
-    static int cap = -1;
-    if (cap < 0) { const char* c = getenv("FASTF_TILE_GRID_CAP"); cap = c ? atoi(c) : 32 * (int)g_cu_count; if (cap < 8) cap = 8; }
-    return std::min<u32>((T + 7u) & ~7u, (u32)cap & ~7u);
+// (xcd_tile strides by gridDim.x >> 3: the grid is a multiple of 8 and at least 8 whatever the cap says)
+static u32 tile_grid(const fastf_engine* e, u32 T) {
+    int cap = e->tile_grid_cap ? e->tile_grid_cap : 32 * (int)e->grid_cus;
+    if (cap < 8) cap = 8;
+    return std::max<u32>(8u, std::min<u32>((T + 7u) & ~7u, (u32)cap & ~7u));
 }
 static size_t scatter_smem_bytes_vals(u32 ipt) { return scatter_smem_bytes(ipt) + (size_t)ipt * SORT_THREADS * 8; }
-static void launch_scatter(u32 shift, u32 T, hipStream_t s, const u64* src, u64* dst, const u64* d_n, const u32* cnt,
+static void launch_scatter(const fastf_engine* e, u32 shift, u32 T, hipStream_t s, const u64* src, u64* dst, const u64* d_n, const u32* cnt,
                            const u32* bin_tot, u32 ipt, const SegMap seg = SegMap{nullptr, nullptr, 0, 0},
                            const u64* vsrc = nullptr, u64* vdst = nullptr) {
-    T = tile_grid(T);
+    T = tile_grid(e, T);
     if (vsrc) {                         // keys with values (wide keys): one instantiation, run-time shift
         hipLaunchKernelGGL((scatter_kernel<-1, false, true>), dim3(T), dim3(SORT_THREADS), scatter_smem_bytes_vals(ipt), s, src, dst, d_n, cnt, bin_tot, ipt, shift,
                            SegMap{nullptr, nullptr, 0, 0}, (u64*)nullptr, vsrc, vdst);
@@ -1899,7 +1930,7 @@ static int launch_sort(fastf_engine* e, u64* keys, u64* tmp, const u64* d_n, u64
             hipLaunchKernelGGL(rgn_scan_blocks_kernel, dim3(n_blk), dim3(RADIX), 0, s, (u32*)e->d_rgn_hist.p, R, (u32*)e->d_rgn_blk.p);
             hipLaunchKernelGGL(rgn_scan_fix_kernel, dim3(n_blk), dim3(RADIX), 0, s, (u32*)e->d_rgn_hist.p, R, (const u32*)e->d_rgn_blk.p, n_blk, bintot);
             t_begin(e, s);
-            hipLaunchKernelGGL(scatter_regions_kernel, dim3(tile_grid(R)), dim3(SORT_THREADS), scatter_smem_bytes(ipt), s, src, dst,
+            hipLaunchKernelGGL(scatter_regions_kernel, dim3(tile_grid(e, R)), dim3(SORT_THREADS), scatter_smem_bytes(ipt), s, src, dst,
                                (const u64*)e->d_rgn_phys.p, (const u64*)e->d_segcount.p, (const u32*)e->d_rgn_hist.p, (const u32*)bintot, R, ipt, shift,
                                max_n >= (24ull << 20));
             t_end(e, s, &e->t_scatter_ms, &e->t_scatter_n);
@@ -1908,13 +1939,13 @@ static int launch_sort(fastf_engine* e, u64* keys, u64* tmp, const u64* d_n, u64
             continue;
         }
         t_begin(e, s);
-        if (q == 0 && seg.prefix) hipLaunchKernelGGL(tile_count_kernel<true>, dim3(tile_grid(T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, seg);
-        else hipLaunchKernelGGL(tile_count_kernel<false>, dim3(tile_grid(T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, none);
+        if (q == 0 && seg.prefix) hipLaunchKernelGGL(tile_count_kernel<true>, dim3(tile_grid(e, T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, seg);
+        else hipLaunchKernelGGL(tile_count_kernel<false>, dim3(tile_grid(e, T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, none);
         t_end(e, s, &e->t_count_ms, &e->t_count_n);
         hipLaunchKernelGGL(row_scan_kernel, dim3(RADIX), dim3(1024), 0, s, cnt, d_n, bintot, ipt);
         t_begin(e, s);
-        if (vals) launch_scatter(shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, none, (q & 1) ? vtmp : vals, (q & 1) ? vals : vtmp);
-        else launch_scatter(shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, q == 0 ? seg : none);
+        if (vals) launch_scatter(e, shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, none, (q & 1) ? vtmp : vals, (q & 1) ? vals : vtmp);
+        else launch_scatter(e, shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, q == 0 ? seg : none);
         t_end(e, s, &e->t_scatter_ms, &e->t_scatter_n);
         dbg_sync(s, "K2 sort pass");
     }
@@ -1947,15 +1978,11 @@ extern "C" int fastf_dev_sort(fastf_engine_t* e, uint64_t* d_keys, uint64_t* d_t
 
 // K3 grid: every workgroup owns one contiguous chunk of the keys, so the launch is one round of resident workgroups
 // (LDS: 21 KB per workgroup, 37 KB with the hash set of DEDUP 2; 64 VGPRs: eight waves per SIMD, four workgroups per CU)
-static u32 k3_grid(u64 max_n, int dedup) {
-    static int per_cu[3] = {-1, -1, -1};
-    if (per_cu[dedup] < 0) {
-        const char* c = getenv("FASTF_K3_PER_CU");
-        per_cu[dedup] = c ? atoi(c) : 4;
-        if (per_cu[dedup] < 1) per_cu[dedup] = 1;
-    }
+// dedup 2 (reduce_hashed_kernel): 40-58 KB of LDS and 80+ VGPRs, three workgroups per CU (wide keys: two)
+static u32 k3_grid(const fastf_engine* e, u64 max_n, int dedup, bool wide_vals) {
     const u64 tiles = (max_n + K3_TILE - 1) / K3_TILE;
-    return (u32)std::min<u64>(std::max<u64>(tiles, 1), std::min<u64>((u64)per_cu[dedup] * g_cu_count, 4096));
+    const u32 G = (u32)std::min<u64>(std::max<u64>(tiles, 1), std::min<u64>((u64)e->k3_per_cu * e->grid_cus, 4096));
+    return dedup == 2 ? std::min<u32>(G, (wide_vals ? 2u : 3u) * e->grid_cus) : G;
 }
 
 // rows into the engine's row regions (one per workgroup chunk), chunk row counts -> bases, total -> *nrows
@@ -1967,8 +1994,7 @@ static int launch_reduce_regions(fastf_engine* e, const u64* sorted, const u64* 
     if (max_n == 0) { HIP_OK(hipMemsetAsync(nrows, 0, sizeof(u64), s)); return 0; }
     if (wide_vals && UMI_ROWS) return set_err("internal error: -u rows of wide keys");
     const int dedup = wide_vals ? 2 : (UMI_ROWS || low_skip == 0) ? 0 : 2;      // 2: keys sorted on (cell, feature) only (reduce_hashed_kernel)
-    u32 G = k3_grid(max_n, dedup);
-    if (dedup == 2) G = std::min<u32>(G, (wide_vals ? 2u : 3u) * g_cu_count);      // reduce_hashed_kernel: 40-58 KB of LDS and 80+ VGPRs, three workgroups per CU (wide keys: two)
+    const u32 G = k3_grid(e, max_n, dedup, wide_vals != nullptr);
     if (e->d_rg_count.ensure(max_n * 4)) return 1;
     if (UMI_ROWS ? e->d_rg_ukeys.ensure(max_n * 8) : (e->d_rg_feature.ensure(max_n * 4) || e->d_rg_cell.ensure(max_n * 4))) return 1;
     if (e->d_spanrows.ensure(4096 * sizeof(u32)) || e->d_spanbase.ensure(4097 * sizeof(u64))) return 1;
@@ -1997,7 +2023,7 @@ static int launch_reduce_regions(fastf_engine* e, const u64* sorted, const u64* 
     else if (e->L.feat_shift > 27) hipLaunchKernelGGL((reduce_hashed_kernel<true>), dim3(G), dim3(K3H_THREADS), 0, s, p);    // UMIs beyond 12 bases: 64-bit slots
     else hipLaunchKernelGGL((reduce_hashed_kernel<false>), dim3(G), dim3(K3H_THREADS), 0, s, p);
     if (dedup == 2)       // (its last workgroup scans the chunks' row counts: no span_scan launch of its own)
-        hipLaunchKernelGGL(giant_groups_kernel, dim3(g_cu_count + 1), dim3(512), 0, s, wide_vals ? wide_vals : sorted, (const u64*)e->d_giant.p, giant_cnt, parity, e->L,
+        hipLaunchKernelGGL(giant_groups_kernel, dim3(giant_grid(e)), dim3(512), 0, s, wide_vals ? wide_vals : sorted, (const u64*)e->d_giant.p, giant_cnt, parity, e->L,
                            (u32*)e->d_rg_count.p, (u64*)e->d_small.p + SM_COUNTERS + 3, (const u32*)e->d_spanrows.p, G, (u64*)e->d_spanbase.p, nrows);
     else
         hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(1024), 0, s, (const u32*)e->d_spanrows.p, G, (u64*)e->d_spanbase.p, nrows);
@@ -2398,7 +2424,7 @@ static int rebase_store(fastf_engine* e) {
     for (u32 i = 0; i < R; ++i) { phys[i] = (u64)i * RUN; cnt[i] = std::min<u64>(RUN, n - phys[i]); }
     if (copy_h2d(e->d_rgn_phys.p, phys.data(), R * sizeof(u64))) return 1;
     if (copy_h2d(e->d_segcount.p, cnt.data(), R * sizeof(u64))) return 1;
-    hipLaunchKernelGGL(rgn_hist_kernel, dim3(std::min<u32>(R, 8 * g_cu_count)), dim3(256), 0, e->s_compute, (const u64*)e->d_keys.p, (const u64*)e->d_rgn_phys.p,
+    hipLaunchKernelGGL(rgn_hist_kernel, dim3(rgn_hist_grid(e, R)), dim3(256), 0, e->s_compute, (const u64*)e->d_keys.p, (const u64*)e->d_rgn_phys.p,
                        (const u64*)e->d_segcount.p, R, e->skip_bits, (u32*)e->d_rgn_hist.p);
     HIP_OK(hipGetLastError());
     e->rgn_n = R; e->slots_used = n; e->store_regions = true;
@@ -2507,7 +2533,7 @@ extern "C" int fastf_debug_mt_fill_bits(int device, uint32_t seed, uint64_t skip
         if (copy_h2d(st.p, &mt, sizeof mt) || hipMemset(buf.p, 0xFF, ring_bits / 8) != hipSuccess) { rc = set_err("copy failed"); break; }
         u64 at = first;
         for (u32 i = 0; i < n_calls; ++i) {
-            if (launch_mt_decisions((hipStream_t)0, (u32*)st.p, words, (u32*)buf.p, at, counts[i], ring_bits - 1, threshold)) { rc = 1; break; }
+            if (launch_mt_decisions(g_cu_count, (hipStream_t)0, (u32*)st.p, words, (u32*)buf.p, at, counts[i], ring_bits - 1, threshold)) { rc = 1; break; }
             at += counts[i];
         }
         if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { rc = set_err("mt_fill_kernel failed"); break; }
@@ -2743,7 +2769,7 @@ static int wide_pair_rows(fastf_engine* e, u64 n, hipStream_t s, std::vector<u64
     int rc = 0;
     do {
         if (hipMemsetAsync(cnt.p, 0, (T + 16) * 4, s) != hipSuccess) { rc = set_err("memset failed"); break; }
-        const u32 grid = (u32)std::min<u64>(T, 16ull * g_cu_count);
+        const u32 grid = pair_grid(e, T);
         hipLaunchKernelGGL(pair_heads_kernel, dim3(grid), dim3(UW_THREADS), 0, s, (const u64*)kc, (const u64*)vc, (const u64*)(small + SM_KEYCOUNT), (u32*)cnt.p);
         launch_scan_tiles(e, 1, s, (u32*)cnt.p, (u64*)base.p, (u32)T, small + SM_NROWS_U, nullptr, nullptr);
         u64* uvals = (u64*)e->d_rg_ukeys.p; u64* hpos = uvals + n;
@@ -2935,6 +2961,65 @@ extern "C" int fastf_engine_reseed(fastf_engine_t* e, uint32_t seed, uint64_t sk
 // freq: FASTQ text -> keys of the tag histogram, on the device
 // ------------------------------------------------------------------------------------
 #include "fastq_kernels.hpp"
+
+// ------------------------------------------------------------------------------------
+// the grids of the step, as this engine would launch them (include/fastf_amd.h: FASTF_GRID_*)
+// ------------------------------------------------------------------------------------
+extern "C" int fastf_engine_grids(const fastf_engine_t* e, uint64_t n_records, uint64_t n_keys, uint32_t* out) FASTF_TRY {
+    if (!e || !out) return set_err("null argument");
+    if (e->multi) return set_err("fastf_engine_grids: a single-device engine's grids");
+    if (n_keys >= (1ull << 32)) return set_err("fastf_engine_grids: at most 2^32 - 1 keys");
+    for (int i = 0; i < 2 * FASTF_GRID_FAMILIES; ++i) out[i] = 0;
+    auto put = [&](int fam, u64 wg, u64 tiles) { out[2 * fam] = (u32)wg; out[2 * fam + 1] = (u32)std::min<u64>(tiles, 0xFFFFFFFFull); };
+    if (n_records) {
+        const u32 tiles = (u32)((n_records + K1_TILE - 1) / K1_TILE);
+        if (e->use_lds_cells) put(FASTF_GRID_K1A, k1a_lds_grid(e, tiles), (tiles + 1) / 2);                 // two tiles per turn
+        else if (e->cell_filter.bits) put(FASTF_GRID_K1A, k1a_filtered_grid(e, tiles), tiles);
+        else put(FASTF_GRID_K1A, tiles, tiles);
+        const u64 units = (n_records + BLK_RECS - 1) / BLK_RECS;
+        put(FASTF_GRID_BLOCK_RECORDS, block_records_grid(e, units), (units + 3) / 4);                         // four waves, a unit each
+        put(FASTF_GRID_DRAW_BITS, draw_bits_grid(e->grid_cus, n_records), (((n_records + 63) >> 6) + 15) / 16);   // four waves, four words each
+        if (e->use_lds_genes) put(FASTF_GRID_K1B_TILES, k1b_tile_grid(e, tiles), tiles);
+        else put(FASTF_GRID_K1B_TILES, tiles, tiles);
+        if (e->stream_single || e->stream_sharded) {
+            u32 grid; u64 region;
+            stream_geometry(e, tiles, &grid, &region);
+            const u32 waves = (e->genes_blocks_per_cu >= 2 ? K1S_THREADS : K1S_THREADS_ROOMY) / WAVE;
+            put(FASTF_GRID_K1B_STREAM, grid, ((u64)tiles * (K1_TILE / K1S_UNIT) + waves - 1) / waves);      // a unit per wave and turn
+            put(FASTF_GRID_SCATTER_REGIONS, tile_grid(e, grid * (u32)K1S_SUB), grid * (u32)K1S_SUB);
+        }
+    }
+    if (n_keys) {
+        const u32 ipt = choose_sort_ipt(n_keys);
+        const u32 T = (u32)((n_keys + (u64)ipt * SORT_THREADS - 1) / ((u64)ipt * SORT_THREADS));
+        put(FASTF_GRID_SORT_TILES, tile_grid(e, T), T);
+        const u32 R = (u32)((n_keys + (1u << 16) - 1) >> 16);                                               // adopted keys: 65 536 a region
+        put(FASTF_GRID_RGN_HIST, rgn_hist_grid(e, R), R);
+        const u64 w = (n_keys + K3_TILE - 1) / K3_TILE;
+        put(FASTF_GRID_K3_WINDOWS, k3_grid(e, n_keys, 0, false), w);
+        put(FASTF_GRID_K3_HASHED, k3_grid(e, n_keys, 2, e->wide), w);
+        put(FASTF_GRID_GIANT, giant_grid(e), 0);                                                            // (its items: as the keys have them)
+        put(FASTF_GRID_PAIRS, pair_grid(e, (n_keys + UW_TILE - 1) / UW_TILE), (n_keys + UW_TILE - 1) / UW_TILE);
+        const u32 G = out[2 * (e->skip_bits || e->wide ? FASTF_GRID_K3_HASHED : FASTF_GRID_K3_WINDOWS)];   // the matrix rows' K3
+        put(FASTF_GRID_ROWS_GATHER, G, G);                                                                  // a chunk each
+    }
+    return 0;
+} FASTF_CATCH_INT
+
+// the tile scan on the caller's arrays: d_out[i] = d_in[0] + .. + d_in[i - 1] (u64), d_in[0 .. T) cleared; *d_total = the sum;
+// *d_base = *d_running, then *d_running += the sum.  d_total, d_running, d_base may be null (d_base without d_running is not written).
+// Entries of at most 4096 (a K1 tile's hits): a round's partial sums are 32-bit.  slot 0 / 1: the K1 and the K3 scan's chunk totals.
+extern "C" int fastf_dev_scan_tiles(fastf_engine_t* e, uint32_t* d_in, uint32_t T, uint64_t* d_out, uint64_t* d_total, uint64_t* d_running,
+                                    uint64_t* d_base, uint32_t slot, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_in || !d_out, "null argument");
+    if (slot > 1) return set_err("fastf_dev_scan_tiles: slot 0 or 1");
+    if ((reinterpret_cast<uintptr_t>(d_in) & 15u) || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return set_err("fastf_dev_scan_tiles: 16-byte aligned arrays");
+    if (T == 0) return set_err("fastf_dev_scan_tiles: no entries");
+    if (e->d_scanblk.ensure(2 * 64 * sizeof(u64))) return 1;       // (before the launch: both slots' totals stay where they are)
+    launch_scan_tiles(e, (int)slot, (hipStream_t)stream, d_in, (u64*)d_out, T, (u64*)d_total, (u64*)d_running, (u64*)d_base);
+    HIP_OK(hipGetLastError());
+    return 0;
+} FASTF_CATCH_INT
 
 // ------------------------------------------------------------------------------------
 // filter: FASTQ triples -> keep bitmap + compacted text windows, on the device

@@ -594,7 +594,7 @@ __global__ __launch_bounds__(1024) void scan_tiles_kernel(u32* __restrict__ in, 
     }
     if (blk_tot) { if (threadIdx.x == 0) blk_tot[blockIdx.x] = s_carry; return; }
     if (threadIdx.x == 0 && total_out) *total_out = s_carry;
-    if (threadIdx.x == 0 && running) { const u64 r = *running; *base_out = r; *running = r + s_carry; }
+    if (threadIdx.x == 0 && running) { const u64 r = *running; if (base_out) *base_out = r; *running = r + s_carry; }
 }
 
 // second half of the chunked scan: chunk b's entries get the totals of the chunks in front; workgroup 0 hands out the total
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(1024) void scan_fix_kernel(u64* __restrict__ out, u
     for (u32 i = 0; i < n_blk; ++i) { const u64 v = blk_tot[i]; if (i < blockIdx.x) off += v; total += v; }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (total_out) *total_out = total;
-        if (running) { const u64 r = *running; *base_out = r; *running = r + total; }
+        if (running) { const u64 r = *running; if (base_out) *base_out = r; *running = r + total; }
     }
     if (blockIdx.x == 0 || off == 0) return;
     const u32 t_first = blockIdx.x * PER * 1024u;

@@ -527,6 +527,18 @@ class Engine:
         check(self._L.fastf_engine_sort_passes(self._h, 2 if skip_low else 0, C.byref(b)))
         return b.value
 
+    GRID_FAMILIES = ("k1a", "block_records", "draw_bits", "k1b_tiles", "k1b_stream", "scatter_regions", "sort_tiles", "rgn_hist",
+                     "k3_windows", "k3_hashed", "giant", "pairs", "rows_gather")
+
+    def grids(self, n_records=0, n_keys=0) -> dict:
+        """{family: (workgroups, tiles)} of the step's capped grids for these counts (fastf_engine_grids)"""
+        out = (C.c_uint32 * (2 * len(self.GRID_FAMILIES)))()
+        check(self._L.fastf_engine_grids(self._h, n_records, n_keys, out))
+        return {f: (out[2 * i], out[2 * i + 1]) for i, f in enumerate(self.GRID_FAMILIES)}
+
+    def dev_scan_tiles(self, d_in, T, d_out, d_total=None, d_running=None, d_base=None, slot=0, stream=0):
+        check(self._L.fastf_dev_scan_tiles(self._h, d_in, T, d_out, d_total, d_running, d_base, slot, stream))
+
     def dev_umi_rows(self, d_sorted, d_n, max_n, d_ukeys, d_ncopy, d_nrows, stream=0):
         check(self._L.fastf_dev_umi_rows(self._h, d_sorted, d_n, max_n, d_ukeys, d_ncopy, d_nrows, stream))
 

@@ -1087,6 +1087,38 @@ int fastf_engine_skip_bits(const fastf_engine_t *e, uint32_t *bits);
 /* number of 8-bit LSD passes fastf_dev_sort runs for this engine's keys with the given flags: the digit grid starts at
  * the skip bit (not necessarily a byte boundary) when FASTF_SORT_SKIP_LOW is set, at bit 0 otherwise */
 int fastf_engine_sort_passes(const fastf_engine_t *e, uint32_t flags, uint32_t *passes);
+/* The grids of the step as this engine launches them for n_records records and n_keys keys: out[2 f] = workgroups and
+ * out[2 f + 1] = the turns' worth of work they share ("tiles": a workgroup goes round ceil(tiles / workgroups) times), for
+ * the kernel families f below.  K1A, K1B_TILES, K1B_STREAM and SCATTER_REGIONS are the forms this engine's tables select (0, 0
+ * for the streaming form where the engine has none); every other family is reported as the engine WOULD launch it, whether or
+ * not its paths reach that kernel (PAIRS: wide keys only; K3_HASHED: engines that leave low bits unsorted, and wide keys).  A
+ * count of 0 reports 0, 0.  The widths come from
+ * FASTF_GRID_CUS (the CU count every capped grid is cut from, 1 .. the device's), FASTF_TILE_GRID_CAP and FASTF_K3_PER_CU
+ * as they stood when the engine was created: test and diagnostic switches.
+ *   K1A             probe_cells_lds_kernel (tiles: pairs of K1 tiles), probe_cells_filtered_kernel or probe_cells_kernel
+ *   BLOCK_RECORDS   block_records_kernel (tiles: four 256-record units)
+ *   DRAW_BITS       draw_bits_kernel over n_records draws (tiles: sixteen 64-draw words)
+ *   K1B_TILES       filter_pack_kernel (K1 tiles)
+ *   K1B_STREAM      filter_pack_stream_kernel (tiles: one 256-record unit per wave)
+ *   SCATTER_REGIONS scatter_regions_kernel over the regions K1B_STREAM leaves (tiles: regions)
+ *   SORT_TILES      tile_count_kernel and scatter_kernel (sort tiles)
+ *   RGN_HIST        rgn_hist_kernel over adopted keys (tiles: regions of 65 536 keys)
+ *   K3_WINDOWS      reduce_windows_kernel<false / true> (tiles: 2048-key windows; a workgroup owns one chunk of them)
+ *   K3_HASHED       reduce_hashed_kernel, the form this engine's keys take (the same)
+ *   GIANT           giant_groups_kernel (tiles 0: its work items are as the keys have them)
+ *   PAIRS           pair_heads_kernel, pair_rows_kernel, pair_copies_kernel (2048-key tiles)
+ *   ROWS_GATHER     rows_gather_kernel after the matrix rows' K3 (tiles: chunks) */
+enum { FASTF_GRID_K1A = 0, FASTF_GRID_BLOCK_RECORDS, FASTF_GRID_DRAW_BITS, FASTF_GRID_K1B_TILES, FASTF_GRID_K1B_STREAM,
+       FASTF_GRID_SCATTER_REGIONS, FASTF_GRID_SORT_TILES, FASTF_GRID_RGN_HIST, FASTF_GRID_K3_WINDOWS, FASTF_GRID_K3_HASHED,
+       FASTF_GRID_GIANT, FASTF_GRID_PAIRS, FASTF_GRID_ROWS_GATHER, FASTF_GRID_FAMILIES };
+int fastf_engine_grids(const fastf_engine_t *e, uint64_t n_records, uint64_t n_keys, uint32_t *out /* [2 * FASTF_GRID_FAMILIES] */);
+/* The engine's tile scan on the caller's device arrays (16-byte aligned): d_out[i] = d_in[0] + .. + d_in[i - 1] in 64 bits,
+ * d_in[0 .. T) is left all zero, *d_total = the sum, *d_base = *d_running and then *d_running += the sum.  d_total,
+ * d_running and d_base may each be null.  Entries are at most 4096 (the hits of a K1 tile): the sums inside a round of
+ * 16 384 entries are 32-bit.  slot 0 or 1: scans of more than 16 384 entries keep chunk totals per slot, so that two scans
+ * may run side by side on two streams. */
+int fastf_dev_scan_tiles(fastf_engine_t *e, uint32_t *d_in, uint32_t T, uint64_t *d_out, uint64_t *d_total,
+                         uint64_t *d_running, uint64_t *d_base, uint32_t slot, void *stream);
 /* which lookup structure the lists qualified for: 1 = LDS-resident (barcodes: perfect hash of 32-bit codes; genes:
  * bitmap + rank + permutation over one id family; genes: 2 = direct index table over a dense id range),
  * 0 = open-addressed table in L2 */
