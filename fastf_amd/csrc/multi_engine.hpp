@@ -451,7 +451,7 @@ static int multi_exchange(fastf_multi* m) {
         HIP_OK(hipMemcpyAsync(md.h_info, md.e->d_small.p, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, md.e->s_compute));
         HIP_OK(hipStreamSynchronize(md.e->s_compute));
         for (u32 h = 0; h < G; ++h) md.cnt[h] = md.h_info[SM_KEYCOUNT + h];
-        if (md.h_info[SM_COUNTERS + 3]) return set_err("%s", err_bits_text(md.h_info[SM_COUNTERS + 3]));
+        if (md.h_info[SM_ERR]) return set_err("%s", err_bits_text(md.h_info[SM_ERR]));
         multi_free_old_shards(md);                                          // the compute stream has just been waited for
     }
     m->c_sampled = m->c_valid = 0;
@@ -588,7 +588,7 @@ static int multi_finish(fastf_engine* e, fastf_coo_t* coo, uint64_t counters[3])
         const u32 skip = m->d[0].e->skip_bits;
         if (multi_sort_reduce(m, skip, false)) return 1;
         bool too_long = false;
-        for (u32 h = 0; h < G; ++h) too_long = too_long || (m->d[h].h_info[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG);
+        for (u32 h = 0; h < G; ++h) too_long = too_long || (m->d[h].h_info[SM_ERR] & ERR_RUN_TOO_LONG);
         if (too_long) {                                  // deep (cell, feature) groups: finish the sort everywhere and reduce exactly
             for (u32 h = 0; h < G; ++h) {
                 MultiDev& mh = m->d[h];
@@ -599,7 +599,7 @@ static int multi_finish(fastf_engine* e, fastf_coo_t* coo, uint64_t counters[3])
         }
         for (u32 h = 0; h < G; ++h) {
             MultiDev& mh = m->d[h];
-            if (mh.h_info[SM_COUNTERS + 3]) return set_err("%s", err_bits_text(mh.h_info[SM_COUNTERS + 3]));
+            if (mh.h_info[SM_ERR]) return set_err("%s", err_bits_text(mh.h_info[SM_ERR]));
             const u64 nnz = mh.n_recv ? mh.h_info[SM_NNZ] : 0;
             if (mh.rows.ensure(std::max<u64>(nnz, 1))) return 1;
             mh.pf = mh.rows.f(); mh.pc = mh.rows.c(); mh.pk = mh.rows.k(); mh.nnz = nnz;
@@ -680,7 +680,7 @@ static int multi_umi_rows(fastf_engine* e, fastf_umi_rows_t* rows) {
         if (!mh.n_recv) continue;
         HIP_OK(hipSetDevice(mh.dev));
         HIP_OK(hipStreamSynchronize(mh.e->s_compute));
-        if (mh.h_info[SM_COUNTERS + 3]) return set_err("%s", err_bits_text(mh.h_info[SM_COUNTERS + 3]));
+        if (mh.h_info[SM_ERR]) return set_err("%s", err_bits_text(mh.h_info[SM_ERR]));
         const u64 nr = mh.h_info[SM_NROWS_U];
         mh.ukeys.resize(nr); mh.ncopy.resize(nr);
         if (nr) {

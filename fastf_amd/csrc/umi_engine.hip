@@ -6,15 +6,6 @@
 // There is NO CPU fallback: every entry point fails loudly when HIP is unusable.
 #include "umi_kernels.hpp"
 #include "sweep_kernels.hpp"
-#include "cap_kernels.hpp"
-#include "level_kernels.hpp"
-#include "gene_kernels.hpp"
-#include "cells_kernels.hpp"
-#include "fidelity_kernels.hpp"
-#include "gene_fidelity_kernels.hpp"
-#include "neighbors_kernels.hpp"
-#include "labels_kernels.hpp"
-#include "markers_kernels.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -212,6 +203,17 @@ struct KernelTimer {           // optional per-kernel HIP-event timing (bench ro
     size_t used = 0;
 };
 
+// Engine state of the grid verbs' analyses (analysis_entry.hpp).  attr[f]: the kernels of family f have their dynamic-LDS limit on
+// this engine's device (lds_attr_once).
+enum { AN_CAP_HITS, AN_GENE_SUMMARY, AN_GENE_MOMENTS, AN_NBR_GRAM, AN_LABEL_VOTES, AN_MARKER_AUC, AN_FAMILIES };
+struct AnalysisState {
+    bool attr[AN_FAMILIES] = {};
+    DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
+};
+
+// per-kernel timers, in the order of fastf_engine_get_timing's `which`
+enum { T_K1A, T_SCATTER, T_K3, T_COUNT, T_K1B, T_GATHER, T_TIMERS };
+
 struct fastf_multi;
 struct fastf_engine {
     fastf_multi* multi = nullptr;        // n_devices > 1: this handle only dispatches (multi_engine.hpp)
@@ -240,16 +242,9 @@ struct fastf_engine {
     u32 ring_carry = 0;                  // host-packed decisions: the bits of the word draws_up stands in (below bit draws_up & 31)
     DevBuf d_dbits;                      // device-level calls that bring 32-bit draws: their decisions (draw_bits_kernel)
     DevBuf d_mtwords;                    // the generator's words of one launch, between mt_fill_kernel and draw_bits_kernel
-    // fastf_dev_cell_decisions: which stream d_mtwords holds from its first word on (any other generator launch ends it), and
-    // whether cell_hits_kernel<true> has its dynamic-LDS attribute on this engine's device (lds_attr_once)
+    // fastf_dev_cell_decisions: which stream d_mtwords holds from its first word on (any other generator launch ends it)
     bool mtwords_kept = false; u32 mtwords_seed = 0; u64 mtwords_skip = 0, mtwords_n = 0;
-    bool cap_lds_attr = false;
-    bool gene_lds_attr = false;          // the same for gene_summary_kernel<true>
-    bool gmom_lds_attr = false;          // the same for gene_moments_kernel<true>
-    bool nbr_lds_attr = false;           // the same for the six nbr_gram_kernel forms
-    bool lab_lds_attr = false;           // the same for the three label_votes_kernel<G, true> forms
-    bool mk_lds_attr = false;            // the same for the four marker_auc_kernel forms
-    DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
+    AnalysisState an;                    // what the grid verbs' analyses keep (analysis_entry.hpp); the core never reads it
     DevBuf d_mt; bool mt_on_device = false;  // the engine-owned stream continues on the device (mt_fill_kernel): state words + read index
     u32 mt_dev_idx = MT_N;                   // ... and where in its block that stream stands, as the host knows it (the parallel generator starts at a block boundary)
     bool mt_par_ready = false;               // the parallel generator's one-time init went through: tables up, kernel attributes set, d_mtseq there
@@ -328,16 +323,13 @@ struct fastf_engine {
     // timing
     bool timing = false;
     hipEvent_t t_ev[2] = {nullptr, nullptr};
-    double t_scatter_ms = 0; u64 t_scatter_n = 0;
-    double t_k1_ms = 0; u64 t_k1_n = 0;
-    double t_k1b_ms = 0; u64 t_k1b_n = 0;
-    double t_k3_ms = 0; u64 t_k3_n = 0;
-    double t_count_ms = 0; u64 t_count_n = 0;
-    double t_gather_ms = 0; u64 t_gather_n = 0;
+    struct { double ms; u64 n; } timer[T_TIMERS] = {};
 };
 
-// key_counts (one returning atomic per tile) and counters (three atomics per tile) sit on different 256-B segments
-enum { SM_KEYCOUNT = 0, SM_COUNTERS = 32, SM_NNZ = 64, SM_NROWS_U = 65, SM_N = 66, SM_RUNNING = 96, SM_DRAWBASE = 128, SM_WORDS = 160 };
+// key_counts (one returning atomic per tile) and counters (three atomics per tile) sit on different 256-B segments; SM_ERR: the
+// engine's error word (the ERR_* bits the kernels raise), the fourth of the counters
+enum { SM_KEYCOUNT = 0, SM_COUNTERS = 32, SM_ERR = SM_COUNTERS + 3, SM_NNZ = 64, SM_NROWS_U = 65, SM_N = 66, SM_RUNNING = 96, SM_DRAWBASE = 128, SM_WORDS = 160 };
+static u64* err_word(const fastf_engine* e) { return (u64*)e->d_small.p + SM_ERR; }
 
 static int set_scatter_lds_limit();
 static u32 g_cu_count = 256;             // the device of the engine created last (choose_sort_ipt); the grids read fastf_engine::grid_cus
@@ -751,7 +743,7 @@ extern "C" void fastf_engine_destroy(fastf_engine_t* e) FASTF_TRY {
     }
     if (e->h_small) (void)hipHostFree(e->h_small);
     if (e->h_coo) { if (e->h_coo_pinned) pin_unreg(e->h_coo); fastf_big_free(e->h_coo, (size_t)e->h_coo_cap * 12); }
-    e->d_ring.release(); e->d_mt.release(); e->d_nbr.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
+    e->d_ring.release(); e->d_mt.release(); e->an.d_nbr.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
     DevBuf* all[] = {&e->tab_cells, &e->tab_feats, &e->img_cells, &e->img_genes, &e->d_cell_filter, &e->d_keys, &e->d_tmp, &e->d_small, &e->d_feature, &e->d_cell,
                      &e->d_count, &e->d_ukeys, &e->d_ncopy, &e->d_cellidx, &e->d_tilecnt, &e->d_tilebase, &e->d_binbase, &e->d_cnt, &e->d_rg_feature, &e->d_rg_cell, &e->d_rg_count, &e->d_rg_ukeys, &e->d_spanrows, &e->d_spanbase, &e->d_giant, &e->d_scanblk,
                      &e->d_halfhits, &e->d_segcount, &e->d_segprefix, &e->d_tileseg, &e->d_segkeys, &e->d_vals, &e->d_vtmp,
@@ -854,29 +846,26 @@ static void dbg_sync(hipStream_t s, const char* what) {
 
 // per-kernel timing helpers (only active in timing mode; adds event records to the stream)
 static void t_begin(fastf_engine* e, hipStream_t s) { if (e->timing) (void)hipEventRecord(e->t_ev[0], s); }
-static void t_end(fastf_engine* e, hipStream_t s, double* acc, u64* cnt) {
+static void t_end(fastf_engine* e, hipStream_t s, int which) {
     if (!e->timing) return;
     (void)hipEventRecord(e->t_ev[1], s);
     (void)hipEventSynchronize(e->t_ev[1]);
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e->t_ev[0], e->t_ev[1]) == hipSuccess) { *acc += ms; *cnt += 1; }
+    if (hipEventElapsedTime(&ms, e->t_ev[0], e->t_ev[1]) == hipSuccess) { e->timer[which].ms += ms; e->timer[which].n += 1; }
 }
 
 extern "C" int fastf_engine_set_timing(fastf_engine_t* e, int on) FASTF_TRY {
     DEV_SINGLE(!e, "null engine");
     e->timing = on != 0;
-    e->t_scatter_ms = e->t_k1_ms = e->t_k1b_ms = e->t_k3_ms = e->t_count_ms = e->t_gather_ms = 0;
-    e->t_scatter_n = e->t_k1_n = e->t_k1b_n = e->t_k3_n = e->t_count_n = e->t_gather_n = 0;
+    for (auto& t : e->timer) t = {};
     return 0;
 } FASTF_CATCH_INT
 // which: 0 = K1a probe_cells, 1 = K2 scatter, 2 = K3 (reduce_windows + span_scan), 3 = K2 tile_count,
 //        4 = K1b filter_pack, 5 = rows_gather (concatenation of K3's row regions)
 extern "C" int fastf_engine_get_timing(fastf_engine_t* e, int which, double* total_ms, uint64_t* launches) FASTF_TRY {
     if (!e) return set_err("null engine");
-    const double ms[6] = {e->t_k1_ms, e->t_scatter_ms, e->t_k3_ms, e->t_count_ms, e->t_k1b_ms, e->t_gather_ms};
-    const u64 n[6] = {e->t_k1_n, e->t_scatter_n, e->t_k3_n, e->t_count_n, e->t_k1b_n, e->t_gather_n};
-    if (which < 0 || which > 5) return set_err("bad timer index");
-    *total_ms = ms[which]; *launches = n[which];
+    if (which < 0 || which >= T_TIMERS) return set_err("bad timer index");
+    *total_ms = e->timer[which].ms; *launches = e->timer[which].n;
     return 0;
 } FASTF_CATCH_INT
 
@@ -924,7 +913,7 @@ static int launch_probe_cells(fastf_engine* e, const u64* cb, u64 n, u64* d_tota
         hipLaunchKernelGGL(probe_cells_kernel<0>, dim3(tiles), dim3(K1_THREADS), 0, s, cb, n, e->cells,
                            cout, e->cell16, (u32*)e->d_tilecnt.p, (u32*)e->d_halfhits.p);
     }
-    t_end(e, s, &e->t_k1_ms, &e->t_k1_n);
+    t_end(e, s, T_K1A);
     dbg_sync(s, "K1a probe_cells");
     launch_scan_tiles(e, 0, s, (u32*)e->d_tilecnt.p, (u64*)e->d_tilebase.p, tiles, d_total_out, d_running, d_base_out);
     dbg_sync(s, "K1a tile scan");
@@ -945,6 +934,20 @@ extern "C" int fastf_dev_block_bytes(const fastf_engine_t* e, uint64_t n, uint64
     *bytes = 0;
     if (e->multi || !(e->stream_single || e->stream_sharded) || e->stream_off) return 0;
     *bytes = ((n + BLK_RECS - 1) / BLK_RECS) * (u64)blk_run_bytes(e->cell16, e->narrow);
+    return 0;
+} FASTF_CATCH_INT
+
+// the layout fastf_dev_block_records writes for this engine, as one word: 0 where the engine has no blocked form; two engines with
+// the same word lay the same records out in the same bytes (the K1a scratch slices aside, which fastf_dev_count_hits_blocked fills)
+extern "C" int fastf_dev_block_layout(const fastf_engine_t* e, uint64_t n, uint64_t* layout) FASTF_TRY {
+    if (!e || !layout) return set_err("null argument");
+    uint64_t bytes = 0;
+    *layout = 0;
+    if (fastf_dev_block_bytes(e, n, &bytes)) return 1;
+    if (!bytes) return 0;
+    *layout = 1ull | ((u64)e->narrow << 1) | ((u64)e->cell16 << 2);
+    // (narrow runs fold the family constant and the UMI field of the key layout into their words: block_records_kernel<true>)
+    if (e->narrow) *layout |= ((u64)e->lds_genes.family << 8) | ((u64)e->L.umi_bits << 40) | ((u64)e->L.umi_max_bytes << 48);
     return 0;
 } FASTF_CATCH_INT
 
@@ -1127,515 +1130,6 @@ extern "C" int fastf_dev_mt_decisions_multi(fastf_engine_t* e, uint32_t seed, ui
     return 0;
 } FASTF_CATCH_INT
 
-// Per-cell summary of COO rows ascending by (cell, feature) (cell_summary_kernel): d_umis_per_cell[c - 1] = sum of the counts of
-// cell c, d_genes_per_cell[c - 1] = its rows with count >= 1, d_umis_per_cell[n_cells] = the sum of all counts.  Both arrays are
-// cleared here first; *d_nnz rows are read.
-extern "C" int fastf_dev_cell_summary(fastf_engine_t* e, const uint32_t* d_cell, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_cells,
-                                      uint64_t* d_umis_per_cell, uint32_t* d_genes_per_cell, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz || !d_umis_per_cell || (n_cells && !d_genes_per_cell), "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_OK(hipMemsetAsync(d_umis_per_cell, 0, ((size_t)n_cells + 1) * sizeof(u64), s));
-    if (n_cells) HIP_OK(hipMemsetAsync(d_genes_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
-    if (!d_cell || !d_count) return 0;                  // (no row buffer: a reduce of nothing)
-    hipLaunchKernelGGL(cell_summary_kernel, dim3(2 * e->grid_cus), dim3(256), 0, s, d_cell, d_count, (const u64*)d_nnz, n_cells,
-                       (u64*)d_umis_per_cell, d_genes_per_cell);
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "cell summary");
-    return 0;
-} FASTF_CATCH_INT
-
-// The dynamic-LDS limit of `kernels`, set on the engine's first use of them: the attribute belongs to the current device's function,
-// so `done` is a flag of the engine.
-static int lds_attr_once(bool& done, size_t bytes, std::initializer_list<const void*> kernels) {
-    if (done) return 0;
-    for (const void* k : kernels) HIP_OK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    done = true;
-    return 0;
-}
-
-// The launch plan of a ranged histogram (ranged_hist.hpp) over n_bins bins: up to max_ranges ranges of bins_per_range bins take the
-// LDS form, each range with its own share of the workgroups (every range reads all rows); <env>=<k> lowers that (0: the general
-// form always — tests, A/B runs) and is read at each call.  per_cu: the workgroups a CU holds with lds_bytes of counters each.
-struct HistPlan { bool lds_form; u32 n_ranges; size_t lds_bytes; u32 per_cu; };
-static HistPlan hist_plan(u32 n_bins, u32 bins_per_range, u32 max_ranges, const char* env, size_t bytes_per_bin) {
-    const char* mr = getenv(env);
-    if (mr) max_ranges = std::min<u32>((u32)atoi(mr), max_ranges);
-    const u32 n_ranges = (n_bins + bins_per_range - 1) / bins_per_range;
-    const size_t lds_bytes = (size_t)std::min<u32>(n_bins, bins_per_range) * bytes_per_bin;
-    return {n_ranges <= max_ranges, n_ranges, lds_bytes, lds_bytes <= 80u * 1024u ? 2u : 1u};
-}
-
-// The end of the two joins (fastf_dev_fidelity, fastf_dev_partner_counts): waits for the stream, reads the error word back and fails
-// in `fn`'s name when a point row had no partner.
-static int join_end(const char* fn, hipStream_t s, const u64* err) {
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(s));
-    u64 bits = 0;
-    if (copy_d2h(&bits, err, sizeof bits)) return 1;
-    if (bits & ERR_NO_PARTNER) return set_err("%s: a point row has no partner among the full rows (device error bits 0x%llx)", fn, (unsigned long long)bits);
-    return 0;
-}
-
-// --fidelity: a point's rows joined with the full-depth rows of its (cell rate, seed) pair (fidelity_kernel).  Both row sets ascend
-// by (cell, feature) and every point row has its partner among the full rows; d_sum_xy[c - 1] = the sum of x * y over the point
-// rows of cell c, d_sum_yy[c - 1] = the sum of y * y.  Both arrays are cleared here first; *d_nnz_full and *d_nnz rows are read.
-// d_err: the word a missing partner raises FASTF_ERR_NO_PARTNER in (NULL: the engine's own error word).  Synchronises the stream
-// and fails when that bit is set in the word, whichever call raised it: clear it to go on.
-static_assert(ERR_NO_PARTNER == FASTF_ERR_NO_PARTNER, "the error bit of fidelity_kernel and the ABI's");
-extern "C" int fastf_dev_fidelity(fastf_engine_t* e, const uint32_t* d_feature_full, const uint32_t* d_cell_full, const uint32_t* d_count_full,
-                                  const uint64_t* d_nnz_full, const uint32_t* d_feature, const uint32_t* d_cell, const uint32_t* d_count,
-                                  const uint64_t* d_nnz, uint32_t n_cells, uint64_t* d_sum_xy, uint64_t* d_sum_yy, uint64_t* d_err, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz_full || !d_nnz || (n_cells && (!d_sum_xy || !d_sum_yy)), "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (n_cells) {
-        HIP_OK(hipMemsetAsync(d_sum_xy, 0, (size_t)n_cells * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(d_sum_yy, 0, (size_t)n_cells * sizeof(u64), s));
-    }
-    if (!d_feature || !d_cell || !d_count) return 0;    // (no row buffer: a join of nothing)
-    if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_fidelity: point rows and no full rows");
-    u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
-    hipLaunchKernelGGL(fidelity_kernel, dim3(FID_BLOCKS_PER_CU * e->grid_cus), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
-                       (const u64*)d_nnz_full, d_feature, d_cell, d_count, (const u64*)d_nnz, n_cells, (u64*)d_sum_xy, (u64*)d_sum_yy, err);
-    return join_end("fastf_dev_fidelity", s, err);
-} FASTF_CATCH_INT
-
-// Per-gene summary of COO rows in any order (gene_summary_kernel): d_cells_per_gene[g - 1] = rows of gene g with count >= 1,
-// d_umis_per_gene[g - 1] = the sum of their counts.  Both arrays are cleared here first; *d_nnz rows are read.  The sum of all
-// counts is below 2^32 (the LDS form keeps both numbers of a gene in one 64-bit counter).
-extern "C" int fastf_dev_gene_summary(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_count, const uint64_t* d_nnz, uint32_t n_features,
-                                      uint32_t* d_cells_per_gene, uint64_t* d_umis_per_gene, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz || (n_features && (!d_cells_per_gene || !d_umis_per_gene)), "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (!n_features) return 0;
-    HIP_OK(hipMemsetAsync(d_cells_per_gene, 0, (size_t)n_features * sizeof(u32), s));
-    HIP_OK(hipMemsetAsync(d_umis_per_gene, 0, (size_t)n_features * sizeof(u64), s));
-    if (!d_feature || !d_count) return 0;               // (no row buffer: a reduce of nothing)
-    // (the row count lives on the device: the grid is sized by the device alone)
-    const HistPlan pl = hist_plan(n_features, GENE_LDS_GENES, GENE_LDS_RANGES, "FASTF_GENE_LDS_RANGES", sizeof(u64));
-    if (pl.lds_form) {
-        if (lds_attr_once(e->gene_lds_attr, GENE_LDS_GENES * sizeof(u64), {(const void*)gene_summary_kernel<true>})) return 1;
-        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)e->grid_cus / pl.n_ranges);
-        hipLaunchKernelGGL(gene_summary_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_count, (const u64*)d_nnz, n_features,
-                           d_cells_per_gene, (u64*)d_umis_per_gene, pl.n_ranges);
-    } else {
-        hipLaunchKernelGGL(gene_summary_kernel<false>, dim3(2 * e->grid_cus), dim3(GENE_THREADS), 0, s, d_feature, d_count, (const u64*)d_nnz, n_features,
-                           d_cells_per_gene, (u64*)d_umis_per_gene, 1u);
-    }
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "gene summary");
-    return 0;
-} FASTF_CATCH_INT
-
-// --gene-fidelity: d_x[i] = the count of the full row with the (cell, feature) of point row i (partner_counts_kernel): the join of
-// fastf_dev_fidelity, stored per row.  Both row sets ascend by (cell, feature); *d_nnz_full and *d_nnz rows are read, *d_nnz entries of
-// d_x are written.  d_err, the synchronisation and the failure on FASTF_ERR_NO_PARTNER: as fastf_dev_fidelity; such a row gets x = 0.
-extern "C" int fastf_dev_partner_counts(fastf_engine_t* e, const uint32_t* d_feature_full, const uint32_t* d_cell_full, const uint32_t* d_count_full,
-                                        const uint64_t* d_nnz_full, const uint32_t* d_feature, const uint32_t* d_cell, const uint64_t* d_nnz,
-                                        uint32_t* d_x, uint64_t* d_err, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz_full || !d_nnz, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (!d_feature || !d_cell) return 0;                // (no row buffer: a join of nothing)
-    if (!d_x) return set_err("fastf_dev_partner_counts: point rows and no partner column");
-    if (!d_feature_full || !d_cell_full || !d_count_full) return set_err("fastf_dev_partner_counts: point rows and no full rows");
-    u64* const err = d_err ? (u64*)d_err : (u64*)e->d_small.p + SM_COUNTERS + 3;
-    hipLaunchKernelGGL(partner_counts_kernel, dim3(FID_BLOCKS_PER_CU * e->grid_cus), dim3(FID_THREADS), 0, s, d_feature_full, d_cell_full, d_count_full,
-                       (const u64*)d_nnz_full, d_feature, d_cell, (const u64*)d_nnz, d_x, err);
-    return join_end("fastf_dev_partner_counts", s, err);
-} FASTF_CATCH_INT
-
-// --gene-fidelity: per gene the sums of a * b and of b * b over rows (feature, a, b) in any order (gene_moments_kernel):
-// d_sum_ab[g - 1] and d_sum_bb[g - 1], u64, n_features entries each, cleared here first; *d_nnz rows are read.  Every sum stays below
-// 2^64 (the sum of all counts is below 2^32).  d_sum_ab == NULL: sum_bb alone.  Stream-ordered.
-extern "C" int fastf_dev_gene_moments(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_a, const uint32_t* d_b, const uint64_t* d_nnz,
-                                      uint32_t n_features, uint64_t* d_sum_ab, uint64_t* d_sum_bb, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz || (n_features && !d_sum_bb), "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (!n_features) return 0;
-    if (d_sum_ab) HIP_OK(hipMemsetAsync(d_sum_ab, 0, (size_t)n_features * sizeof(u64), s));
-    HIP_OK(hipMemsetAsync(d_sum_bb, 0, (size_t)n_features * sizeof(u64), s));
-    if (!d_feature || !d_a || !d_b) return 0;           // (no row buffer: a reduce of nothing)
-    const HistPlan pl = hist_plan(n_features, GMOM_LDS_GENES, GMOM_LDS_RANGES, "FASTF_GENE_MOMENTS_LDS_RANGES", 2 * sizeof(u64));
-    if (pl.lds_form) {
-        if (lds_attr_once(e->gmom_lds_attr, GMOM_LDS_GENES * 2 * sizeof(u64), {(const void*)gene_moments_kernel<true>})) return 1;
-        const u32 groups = std::max<u32>(1u, pl.per_cu * (u32)e->grid_cus / pl.n_ranges);
-        hipLaunchKernelGGL(gene_moments_kernel<true>, dim3(groups * pl.n_ranges), dim3(GENE_THREADS), pl.lds_bytes, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
-                           (u64*)d_sum_ab, (u64*)d_sum_bb, pl.n_ranges);
-    } else {
-        hipLaunchKernelGGL(gene_moments_kernel<false>, dim3(2 * e->grid_cus), dim3(GENE_THREADS), 0, s, d_feature, d_a, d_b, (const u64*)d_nnz, n_features,
-                           (u64*)d_sum_ab, (u64*)d_sum_bb, 1u);
-    }
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "gene moments");
-    return 0;
-} FASTF_CATCH_INT
-
-// --neighbors: the dense byte planes of the rows whose gene is in A (neighbors_kernels.hpp).  d_slot_map: u16[n_features + 1], the slot
-// of feature f in A (0 .. K - 1) or 0xFFFF.  The largest count among those rows decides P (one max reduction, read back here):
-// 1 plane below 2^7, 2 below 2^14, 3 below 2^21; beyond that the call fails by name.  d_planes == NULL: *planes_out = P alone.  Otherwise
-// P * n_pad * K_pad bytes (fastf_neighbors_pad) are zeroed and filled, and planes_bytes must hold them.  Synchronises the stream once.
-extern "C" int fastf_dev_neighbor_planes(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_cell, const uint32_t* d_count,
-                                         const uint64_t* d_nnz, const uint16_t* d_slot_map, uint32_t n_features, uint32_t n_cells, uint32_t K,
-                                         void* d_planes, size_t planes_bytes, uint32_t* planes_out, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_nnz || !planes_out, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (K > NBR_MAX_GENES) return set_err("fastf_dev_neighbor_planes: %u genes, at most %u", K, NBR_MAX_GENES);
-    const bool rows = d_feature && d_cell && d_count && d_slot_map;      // (no row buffer: planes of nothing)
-    u32 max_count = 0;
-    if (rows) {
-        if (e->d_nbr.ensure(64)) return 1;
-        u32* const d_max = (u32*)e->d_nbr.p;
-        HIP_OK(hipMemsetAsync(d_max, 0, 64, s));
-        hipLaunchKernelGGL(nbr_max_count_kernel, dim3(4 * e->grid_cus), dim3(256), 0, s, d_feature, d_count, (const u64*)d_nnz, d_slot_map, n_features, d_max);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipStreamSynchronize(s));
-        if (copy_d2h(&max_count, d_max, sizeof max_count)) return 1;
-    }
-    const u32 P = max_count < (1u << 7) ? 1u : max_count < (1u << 14) ? 2u : max_count < (1u << 21) ? 3u : 4u;
-    if (P > NBR_MAX_PLANES)
-        return set_err("fastf_dev_neighbor_planes: FASTF_ERR_NEIGHBOR_COUNT: a count of %u among the highly variable genes needs more than %u planes of 7 bits", max_count, NBR_MAX_PLANES);
-    *planes_out = P;
-    if (!d_planes) return 0;
-    uint32_t n_pad = 0, K_pad = 0;
-    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
-    const size_t need = (size_t)P * n_pad * K_pad;
-    if (need > planes_bytes) return set_err("fastf_dev_neighbor_planes: %u planes of %u x %u bytes need %zu bytes, the buffer has %zu", P, n_pad, K_pad, need, planes_bytes);
-    HIP_OK(hipMemsetAsync(d_planes, 0, need, s));
-    if (rows && K && n_cells) {
-        hipLaunchKernelGGL(nbr_planes_kernel, dim3(4 * e->grid_cus), dim3(256), 0, s, d_feature, d_cell, d_count, (const u64*)d_nnz, d_slot_map, n_features,
-                           n_cells, K, n_pad, K_pad, P, (unsigned char*)d_planes);
-        HIP_OK(hipGetLastError());
-    }
-    dbg_sync(s, "neighbor planes");
-    return 0;
-} FASTF_CATCH_INT
-
-template <int P, bool MFMA>
-static int nbr_gram_launch(fastf_engine* e, hipStream_t s, const unsigned char* planes, u32 n, u32 n_pad, u32 K_pad, u32 k, const u64* norms, u32* idx, u32* cnt) {
-    const size_t lds = (size_t)NBR_WAVES * nbr_wave_words(k) * sizeof(u64);
-    HIP_OK(hipFuncSetAttribute((const void*)nbr_gram_kernel<P, MFMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NBR_WAVES * nbr_wave_words(NBR_MAX_K) * sizeof(u64))));
-    (void)e;
-    hipLaunchKernelGGL((nbr_gram_kernel<P, MFMA>), dim3((n + NBR_ROWS - 1) / NBR_ROWS), dim3(NBR_THREADS), lds, s, planes, n, n_pad, K_pad, k, norms, idx, cnt);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// --neighbors: the norms, then the Gram products and the selection (nbr_norms_kernel, nbr_gram_kernel).  d_planes: what
-// fastf_dev_neighbor_planes filled for (n_cells, K) with `planes` planes.  d_norms[i] = v_i . v_i (u64, n_cells); *max_norm_out its maximum,
-// read back before the selection starts: fastf_neighbors_check_norm refuses 2^42 and beyond and nothing more is launched.  Then
-// d_idx[i * k + s], s < d_cnt[i], are the neighbours of cell i (0-based indices, ascending; the other slots 0xFFFFFFFF), k from 1 to 64.
-// The dot products come from the i8 MFMA, under FASTF_NEIGHBORS_MFMA=0 from ordinary integer instructions: the same numbers.
-extern "C" int fastf_dev_neighbors(fastf_engine_t* e, const void* d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, uint32_t k,
-                                   uint32_t* d_idx, uint32_t* d_cnt, uint64_t* d_norms, uint64_t* max_norm_out, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (k < 1 || k > NBR_MAX_K) return set_err("fastf_dev_neighbors: k = %u, from 1 to %u", k, NBR_MAX_K);
-    if (planes < 1 || planes > NBR_MAX_PLANES) return set_err("fastf_dev_neighbors: %u planes, from 1 to %u", planes, NBR_MAX_PLANES);
-    if (K > NBR_MAX_GENES) return set_err("fastf_dev_neighbors: %u genes, at most %u", K, NBR_MAX_GENES);
-    if (max_norm_out) *max_norm_out = 0;
-    if (!n_cells) return 0;
-    if (!d_planes || !d_idx || !d_cnt || !d_norms) return set_err("fastf_dev_neighbors: null argument");
-    uint32_t n_pad = 0, K_pad = 0;
-    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
-    if (e->d_nbr.ensure(64)) return 1;
-    u64* const d_max = (u64*)e->d_nbr.p + 1;
-    HIP_OK(hipMemsetAsync(d_max, 0, sizeof(u64), s));
-    hipLaunchKernelGGL(nbr_norms_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_planes, n_cells, n_pad, K_pad,
-                       planes, (u64*)d_norms, d_max);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(s));
-    u64 max_norm = 0;
-    if (copy_d2h(&max_norm, d_max, sizeof max_norm)) return 1;
-    if (max_norm_out) *max_norm_out = max_norm;
-    if (fastf_neighbors_check_norm(max_norm)) return 1;
-    const char* mf = getenv("FASTF_NEIGHBORS_MFMA");
-    const bool mfma = !(mf && mf[0] == '0');
-    const unsigned char* const pl = (const unsigned char*)d_planes;
-    int rc = 1;
-    switch (planes * 2 + (mfma ? 1 : 0)) {
-    case 2: rc = nbr_gram_launch<1, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    case 3: rc = nbr_gram_launch<1, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    case 4: rc = nbr_gram_launch<2, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    case 5: rc = nbr_gram_launch<2, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    case 6: rc = nbr_gram_launch<3, false>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    case 7: rc = nbr_gram_launch<3, true>(e, s, pl, n_cells, n_pad, K_pad, k, (const u64*)d_norms, d_idx, d_cnt); break;
-    }
-    if (rc) return 1;
-    dbg_sync(s, "neighbors");
-    return 0;
-} FASTF_CATCH_INT
-
-// --neighbors: d_shared[i] = the number of cells in both neighbour sets of cell i (nbr_shared_kernel); the sets as fastf_dev_neighbors
-// leaves them, both with the same k.  Stream-ordered.
-extern "C" int fastf_dev_neighbors_shared(fastf_engine_t* e, const uint32_t* d_idx_a, const uint32_t* d_cnt_a, const uint32_t* d_idx_b,
-                                          const uint32_t* d_cnt_b, uint32_t n_cells, uint32_t k, uint32_t* d_shared, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (k < 1 || k > NBR_MAX_K) return set_err("fastf_dev_neighbors_shared: k = %u, from 1 to %u", k, NBR_MAX_K);
-    if (!n_cells) return 0;
-    if (!d_idx_a || !d_cnt_a || !d_idx_b || !d_cnt_b || !d_shared) return set_err("fastf_dev_neighbors_shared: null argument");
-    hipLaunchKernelGGL(nbr_shared_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, d_idx_a, d_cnt_a, d_idx_b, d_cnt_b, n_cells, k, d_shared);
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "neighbors shared");
-    return 0;
-} FASTF_CATCH_INT
-
-template <u32 G>
-static int label_votes_launch(fastf_engine* e, hipStream_t s, bool lds_form, const u32* idx, const u32* cnt, const unsigned char* lab, u32 n, u32 k, u32 n_labels,
-                              unsigned char* pred, unsigned char* same, unsigned char* labelled, u32* conf) {
-    const u32 per_pass = LAB_THREADS / G, blocks_all = (n + per_pass - 1) / per_pass;
-    if (lds_form) {
-        // one workgroup a CU at the most: each zeroes and flushes its own copy of the counts
-        hipLaunchKernelGGL((label_votes_kernel<G, true>), dim3(std::min<u32>(blocks_all, (u32)e->grid_cus)), dim3(LAB_THREADS), (size_t)lab_conf_words(n_labels) * sizeof(u32), s,
-                           idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
-    } else {
-        hipLaunchKernelGGL((label_votes_kernel<G, false>), dim3(std::min<u32>(blocks_all, 8u * (u32)e->grid_cus)), dim3(LAB_THREADS), 0, s,
-                           idx, cnt, lab, n, k, n_labels, pred, same, labelled, conf);
-    }
-    (void)e;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// --labels: the label votes of the neighbour sets (label_votes_kernel).  d_idx, d_cnt: what fastf_dev_neighbors wrote for (n_cells, k);
-// d_lab: u8[n_cells], 0 unlabelled, 1 .. n_labels.  d_pred, d_same, d_labelled: u8[n_cells]; d_conf: u32[n_labels * (n_labels + 1)],
-// zeroed here.  The counts of a workgroup are added up in LDS where they fit it (201 labels and fewer); FASTF_LABELS_LDS=0 takes the
-// general form, global atomics alone, for every n_labels (tests, A/B runs).  Stream-ordered.
-extern "C" int fastf_dev_label_votes(fastf_engine_t* e, const uint32_t* d_idx, const uint32_t* d_cnt, const uint8_t* d_lab, uint32_t n_cells, uint32_t k,
-                                     uint32_t n_labels, uint8_t* d_pred, uint8_t* d_same, uint8_t* d_labelled, uint32_t* d_conf, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (k < 1 || k > LAB_MAX_K) return set_err("fastf_dev_label_votes: k = %u, from 1 to %u", k, LAB_MAX_K);
-    if (n_labels > LAB_MAX_LABELS) return set_err("fastf_dev_label_votes: %u labels, at most %u", n_labels, LAB_MAX_LABELS);
-    if (n_labels && !d_conf) return set_err("fastf_dev_label_votes: null argument");
-    if (n_labels) HIP_OK(hipMemsetAsync(d_conf, 0, (size_t)lab_conf_words(n_labels) * sizeof(u32), s));
-    if (!n_cells) return 0;
-    if (!d_idx || !d_cnt || !d_lab || !d_pred || !d_same || !d_labelled) return set_err("fastf_dev_label_votes: null argument");
-    const char* lf = getenv("FASTF_LABELS_LDS");
-    const bool lds_form = lab_conf_fits_lds(n_labels) && !(lf && lf[0] == '0');
-    if (lds_form && lds_attr_once(e->lab_lds_attr, LAB_LDS_BYTES, {(const void*)label_votes_kernel<16, true>, (const void*)label_votes_kernel<32, true>,
-                                                                   (const void*)label_votes_kernel<64, true>})) return 1;
-    int rc;
-    if (k <= 16) rc = label_votes_launch<16>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
-    else if (k <= 32) rc = label_votes_launch<32>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
-    else rc = label_votes_launch<64>(e, s, lds_form, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
-    if (rc) return 1;
-    dbg_sync(s, "label votes");
-    return 0;
-} FASTF_CATCH_INT
-
-static_assert(MK_MAX_LABELS == FASTF_LABELS_MAX && MK_MAX_PLANES == FASTF_MARKER_MAX_PLANES, "the limits of marker_auc_kernel and the ABI's");
-
-// --markers: the accumulator form one call takes for (planes, n_labels): 1 — in LDS beside the bins, 0 — global atomics (what does not
-// fit, and everything under FASTF_MARKERS_LDS=0), -1 — the call is refused
-extern "C" int fastf_marker_auc_form(uint32_t planes, uint32_t n_labels) FASTF_TRY {
-    if (planes < 1 || planes > MK_MAX_PLANES || n_labels < 1 || n_labels > MK_MAX_LABELS) return -1;
-    const char* lf = getenv("FASTF_MARKERS_LDS");
-    return mk_fits_lds(planes, n_labels) && !(lf && lf[0] == '0') ? 1 : 0;
-} FASTF_CATCH_(return -1)
-
-template <u32 P, bool LDS>
-static int marker_auc_launch(hipStream_t s, const unsigned char* planes, const unsigned char* lab, const u32* npl, u32 n_cells, u32 n_pad, u32 K, u32 K_pad,
-                             u32 n_labels, u64* s2u, u32* det, u64* sum) {
-    hipLaunchKernelGGL((marker_auc_kernel<P, LDS>), dim3((K + mk_tile(P) - 1) / mk_tile(P)), dim3(MK_THREADS), (size_t)mk_lds_bytes(P, n_labels, LDS), s,
-                       planes, lab, npl, n_cells, n_pad, K, K_pad, n_labels, s2u, det, sum);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// --markers: per (label, slot of A) 2U, det and sum (marker_auc_kernel) and the cells per label.  d_planes: what fastf_dev_neighbor_planes
-// filled for (n_cells, K) with `planes` planes; d_lab: u8[n_cells].  d_s2u, d_sum: u64[n_labels * K]; d_det: u32[n_labels * K];
-// d_n_per_label: u32[n_labels]; the four are cleared here.  Three planes (a count of 2^14 and beyond in A) and n_labels outside
-// 1 .. FASTF_LABELS_MAX are refused before anything is launched.  FASTF_MARKERS_LDS=0 takes the global-atomic form for every n_labels.
-// Stream-ordered.
-extern "C" int fastf_dev_marker_auc(fastf_engine_t* e, const void* d_planes, uint32_t planes, uint32_t n_cells, uint32_t K, const uint8_t* d_lab,
-                                    uint32_t n_labels, uint64_t* d_s2u, uint32_t* d_det, uint64_t* d_sum, uint32_t* d_n_per_label, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (planes < 1 || planes > MK_MAX_PLANES)
-        return set_err("fastf_dev_marker_auc: FASTF_ERR_MARKER_COUNT: %u planes — a count of 2^14 or more among the highly variable genes: the rank table of a gene does not fit the LDS", planes);
-    if (n_labels < 1 || n_labels > MK_MAX_LABELS) return set_err("fastf_dev_marker_auc: %u labels, from 1 to %u", n_labels, MK_MAX_LABELS);
-    if (K > NBR_MAX_GENES) return set_err("fastf_dev_marker_auc: %u genes, at most %u", K, NBR_MAX_GENES);
-    if (!d_n_per_label || (K && (!d_s2u || !d_det || !d_sum))) return set_err("fastf_dev_marker_auc: null argument");
-    const size_t words = (size_t)n_labels * K;
-    HIP_OK(hipMemsetAsync(d_n_per_label, 0, (size_t)n_labels * sizeof(u32), s));
-    if (words) {
-        HIP_OK(hipMemsetAsync(d_s2u, 0, words * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(d_det, 0, words * sizeof(u32), s));
-        HIP_OK(hipMemsetAsync(d_sum, 0, words * sizeof(u64), s));
-    }
-    if (!n_cells) return 0;
-    if (!d_lab || (K && !d_planes)) return set_err("fastf_dev_marker_auc: null argument");
-    hipLaunchKernelGGL(marker_labels_kernel, dim3(std::min<u32>((n_cells + 255u) / 256u, (u32)e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_lab, n_cells, n_labels, d_n_per_label);
-    HIP_OK(hipGetLastError());
-    if (!K) return 0;
-    const bool lds_form = fastf_marker_auc_form(planes, n_labels) == 1;
-    if (lds_attr_once(e->mk_lds_attr, MK_LDS_BYTES, {(const void*)marker_auc_kernel<1, true>, (const void*)marker_auc_kernel<1, false>,
-                                                     (const void*)marker_auc_kernel<2, true>, (const void*)marker_auc_kernel<2, false>})) return 1;
-    uint32_t n_pad = 0, K_pad = 0;
-    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
-    const unsigned char* const pl = (const unsigned char*)d_planes;
-    int rc;
-    if (planes == 1) rc = lds_form ? marker_auc_launch<1, true>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum)
-                                   : marker_auc_launch<1, false>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum);
-    else rc = lds_form ? marker_auc_launch<2, true>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum)
-                       : marker_auc_launch<2, false>(s, pl, d_lab, d_n_per_label, n_cells, n_pad, K, K_pad, n_labels, (u64*)d_s2u, d_det, (u64*)d_sum);
-    if (rc) return 1;
-    dbg_sync(s, "marker auc");
-    return 0;
-} FASTF_CATCH_INT
-
-// Replicate runs: d_cells_per_gene (what fastf_dev_gene_summary left, still on the device) added into the three u64[n_features]
-// accumulators of a grid point (gene_reps_kernel).  Nothing is cleared here: the caller zeroes the accumulators before the first seed.
-extern "C" int fastf_dev_gene_reps_add(fastf_engine_t* e, const uint32_t* d_cells_per_gene, uint32_t n_features, uint64_t* d_detected,
-                                       uint64_t* d_sum, uint64_t* d_sumsq, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || (n_features && (!d_cells_per_gene || !d_detected || !d_sum || !d_sumsq)), "null argument");
-    if (!n_features) return 0;
-    const u32 grid = std::min<u32>((n_features + GENE_REPS_THREADS - 1) / GENE_REPS_THREADS, 4u * (u32)e->grid_cus);
-    hipLaunchKernelGGL(gene_reps_kernel, dim3(grid), dim3(GENE_REPS_THREADS), 0, (hipStream_t)stream, d_cells_per_gene, n_features,
-                       (u64*)d_detected, (u64*)d_sum, (u64*)d_sumsq);
-    HIP_OK(hipGetLastError());
-    dbg_sync((hipStream_t)stream, "gene reps add");
-    return 0;
-} FASTF_CATCH_INT
-
-// the layout fastf_dev_block_records writes for this engine, as one word: 0 where the engine has no blocked form; two engines with
-// the same word lay the same records out in the same bytes (the K1a scratch slices aside, which fastf_dev_count_hits_blocked fills)
-extern "C" int fastf_dev_block_layout(const fastf_engine_t* e, uint64_t n, uint64_t* layout) FASTF_TRY {
-    if (!e || !layout) return set_err("null argument");
-    uint64_t bytes = 0;
-    *layout = 0;
-    if (fastf_dev_block_bytes(e, n, &bytes)) return 1;
-    if (!bytes) return 0;
-    *layout = 1ull | ((u64)e->narrow << 1) | ((u64)e->cell16 << 2);
-    // (narrow runs fold the family constant and the UMI field of the key layout into their words: block_records_kernel<true>)
-    if (e->narrow) *layout |= ((u64)e->lds_genes.family << 8) | ((u64)e->L.umi_bits << 40) | ((u64)e->L.umi_max_bytes << 48);
-    return 0;
-} FASTF_CATCH_INT
-
-// --cells: the -u rows of fastf_dev_umi_rows on this engine reduced along the cell axis and into the copy-number histogram
-// (copy_summary_kernel).  The cell field and the non-NULL flag are read from the engine's own key layout.  All four outputs are
-// cleared here first; *d_nrows rows are read.  Every per-cell number is below 2^32 (a number of records).
-static_assert(COPY_BINS == FASTF_COPY_BINS, "the histogram of copy_summary_kernel and the ABI's");
-extern "C" int fastf_dev_copy_summary(fastf_engine_t* e, const uint64_t* d_ukeys, const uint32_t* d_ncopy, const uint64_t* d_nrows, uint32_t n_cells,
-                                      uint32_t* d_reads_per_cell, uint32_t* d_null_reads_per_cell, uint32_t* d_single_per_cell, uint64_t* d_hist,
-                                      void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_ukeys || !d_ncopy || !d_nrows || !d_reads_per_cell || !d_null_reads_per_cell || !d_single_per_cell || !d_hist, "null argument");
-    NO_WIDE(e, "fastf_dev_copy_summary");
-    hipStream_t s = (hipStream_t)stream;
-    if (n_cells) {
-        HIP_OK(hipMemsetAsync(d_reads_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
-        HIP_OK(hipMemsetAsync(d_null_reads_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
-        HIP_OK(hipMemsetAsync(d_single_per_cell, 0, (size_t)n_cells * sizeof(u32), s));
-    }
-    HIP_OK(hipMemsetAsync(d_hist, 0, ((size_t)COPY_BINS + 1) * sizeof(u64), s));
-    const CopyOut out{d_reads_per_cell, d_null_reads_per_cell, d_single_per_cell};
-    hipLaunchKernelGGL(copy_summary_kernel, dim3(2 * e->grid_cus), dim3(256), 0, s, (const u64*)d_ukeys, d_ncopy, (const u64*)d_nrows, n_cells,
-                       e->L.cell_shift, e->L.umi_bits + e->L.len_bits, out, (u64*)d_hist);
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "copy summary");
-    return 0;
-} FASTF_CATCH_INT
-
-// cap: hits per cell from the cell scratch K1a left (cell_hits_kernel).  Valid right after fastf_dev_count_hits[_blocked] over the
-// same n records on the same stream (the FASTF_PROBE_REUSE_HITS contract); d_blocked: the blocked buffer of that call, or
-// nullptr for the SoA scratch.  d_hits_per_cell[c - 1] (u32, n_cells entries) is cleared here first.
-static CellIn cell_scratch_of(const fastf_engine* e, const void* blk) {
-    return blk ? CellIn{blk, blk_run_bytes(e->cell16, e->narrow), blk_cell_off(e->narrow)} : CellIn{e->d_cellidx.p, 0u, 0u};
-}
-extern "C" int fastf_dev_cell_hits(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t* d_hits_per_cell, void* stream) FASTF_TRY {
-    DEV_SINGLE(!e || (e && e->n_cells && !d_hits_per_cell), "null argument");
-    if (n >= (1ull << 32)) return set_err("fastf_dev_cell_hits: %llu records: the counters are 32 bits wide", (unsigned long long)n);
-    HIP_OK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (!e->n_cells) return 0;
-    HIP_OK(hipMemsetAsync(d_hits_per_cell, 0, (size_t)e->n_cells * sizeof(u32), s));
-    if (n == 0) return 0;
-    if (!d_blocked && e->d_cellidx.bytes < n * (e->cell16 ? 2u : 4u)) return set_err("fastf_dev_cell_hits: no cell scratch for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
-    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    constexpr u32 WAVES = CAP_HITS_THREADS / WAVE;
-    const CellIn in = cell_scratch_of(e, d_blocked);
-    const HistPlan pl = hist_plan(e->n_cells, CAP_LDS_CELLS, CAP_LDS_RANGES, "FASTF_CAP_LDS_RANGES", sizeof(u32));
-    if (pl.lds_form) {
-        if (lds_attr_once(e->cap_lds_attr, CAP_LDS_CELLS * sizeof(u32), {(const void*)cell_hits_kernel<true>})) return 1;
-        const u32 groups = (u32)std::max<u64>(1, std::min<u64>((units + WAVES - 1) / WAVES, (u64)pl.per_cu * e->grid_cus / pl.n_ranges));
-        hipLaunchKernelGGL(cell_hits_kernel<true>, dim3(groups * pl.n_ranges), dim3(CAP_HITS_THREADS), pl.lds_bytes, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, pl.n_ranges);
-    } else {
-        const u32 grid = (u32)std::min<u64>((units + WAVES - 1) / WAVES, 2ull * e->grid_cus);
-        hipLaunchKernelGGL(cell_hits_kernel<false>, dim3(grid), dim3(CAP_HITS_THREADS), 0, s, in, e->cell16, n, e->n_cells, d_hits_per_cell, 1u);
-    }
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, "cell hits");
-    return 0;
-} FASTF_CATCH_INT
-
-// cap: the decision plane of per-cell thresholds.  The stream init_genrand(seed) + skip is generated as fastf_dev_mt_decisions
-// generates it, the raw draws staying in the engine's word buffer; cell_decisions_kernel then sets bit i of d_bits_out =
-// draw i < d_thresholds[cell of the i-th CB hit - 1] (u64[n_cells] in device memory, each 0 .. 2^32: the caller's word, the values
-// are not read on the host).  The draws of the last (seed, skip) stay in the word buffer: a second call over the same stream — the
-// next cap of a cell rate — does not generate them again.  Same layout and size rule as
-// fastf_dev_draw_bits.  Valid where fastf_dev_cell_hits is, and leaves that contract intact: a fastf_dev_probe_pack with
-// FASTF_PROBE_REUSE_HITS | FASTF_PROBE_DRAW_BITS may follow.  Synchronises the stream.
-extern "C" int fastf_dev_cell_decisions(fastf_engine_t* e, uint64_t n, const void* d_blocked, uint32_t seed, uint64_t skip, uint64_t n_draws,
-                                        const uint64_t* d_thresholds, uint32_t* d_bits_out, void* stream) FASTF_TRY {
-    DEV_SINGLE(!e || (n_draws && (!d_bits_out || !d_thresholds)), "null argument");
-    if ((uintptr_t)d_bits_out & 7) return set_err("fastf_dev_cell_decisions: the plane is 8-byte aligned");
-    HIP_OK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    auto sync = [&]() -> int {
-        if (hipStreamSynchronize(s) != hipSuccess) return set_err("the generator or decision kernels failed: %s", hipGetErrorString(hipGetLastError()));
-        return 0;
-    };
-    if (!n_draws) return sync();
-    HIP_OK(hipMemsetAsync(d_bits_out, 0, (size_t)((n_draws + 63) / 64) * 8, s));
-    if (n == 0 || !e->n_cells) return sync();
-    if (!d_blocked && e->d_cellidx.bytes < n * (e->cell16 ? 2u : 4u)) return set_err("fastf_dev_cell_decisions: no cell scratch for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
-    const u64 tiles = (n + K1_TILE - 1) / K1_TILE;
-    if (e->d_tilebase.bytes < tiles * sizeof(u64) || e->d_halfhits.bytes < tiles * 16 * sizeof(u32)) return set_err("fastf_dev_cell_decisions: no hit counts for %llu records: fastf_dev_count_hits comes first", (unsigned long long)n);
-    // the raw draws: generated once per (seed, skip) — the caps of one cell rate share the stream — and kept while no other
-    // generator launch has used the word buffer
-    if (!(e->mtwords_kept && e->mtwords_seed == seed && e->mtwords_skip == skip && e->mtwords_n >= n_draws)) {
-        fastf_mt_t mt; fastf_mt_seed(&mt, seed); fastf_mt_skip(&mt, skip);
-        if (e->d_mtseat.ensure(sizeof mt)) return 1;
-        if (copy_h2d_on(e->d_mtseat.p, &mt, sizeof mt, s)) return 1;
-        u32 idx = (u32)mt.idx;
-        if (launch_mt_decisions_par(e, s, (u32*)e->d_mtseat.p, &idx, e->d_mtwords, nullptr, 0, n_draws, ~0ull, 0, nullptr, true)) return 1;
-        e->mtwords_kept = true; e->mtwords_seed = seed; e->mtwords_skip = skip; e->mtwords_n = n_draws;
-    }
-    const u64 units = (n + BLK_RECS - 1) / BLK_RECS;
-    const u32 grid = (u32)std::min<u64>((units + 3) / 4, 8ull * e->grid_cus);
-    hipLaunchKernelGGL(cell_decisions_kernel, dim3(grid), dim3(256), 0, s, cell_scratch_of(e, d_blocked), e->cell16, n, (const u64*)e->d_tilebase.p,
-                       (const u32*)e->d_halfhits.p, (const u32*)e->d_mtwords.p, n_draws, (const u64*)d_thresholds, e->n_cells, (u64*)d_bits_out);
-    HIP_OK(hipGetLastError());
-    return sync();
-} FASTF_CATCH_INT
-
-// level: one step of the per-cell threshold search (level_step_kernel; the state rules are in include/fastf_amd.h).  d_out[0]
-// (and d_out[1] in the initialising form) are cleared here first; the engine's own error word is always one of the two the
-// kernel looks at, d_err_in (nullptr: none) the other.  Stream-ordered, no synchronisation.
-static_assert(LEVEL_OUT_WORDS == FASTF_LEVEL_OUT_WORDS, "the result block of level_step_kernel and the ABI's");
-template <bool INIT>
-static int launch_level_step(fastf_engine* e, const u64* d_umis, u32 n_cells, u64 umi_cap, u64* d_lo, u64* d_hi, u64* d_probe, u64* d_out,
-                             const u64* d_err_in, hipStream_t s) {
-    if (umi_cap < 1) return set_err("level: a UMI cap is at least 1");
-    HIP_OK(hipMemsetAsync(d_out, 0, (INIT ? 2 : 1) * sizeof(u64), s));
-    const u32 grid = std::max<u32>(1u, (n_cells + LEVEL_THREADS - 1) / LEVEL_THREADS);
-    hipLaunchKernelGGL(level_step_kernel<INIT>, dim3(grid), dim3(LEVEL_THREADS), 0, s, d_umis, n_cells, umi_cap, d_lo, d_hi, d_probe, d_out,
-                       (const u64*)e->d_small.p + SM_COUNTERS + 3, d_err_in);
-    HIP_OK(hipGetLastError());
-    dbg_sync(s, INIT ? "level init" : "level step");
-    return 0;
-}
-extern "C" int fastf_dev_level_init(fastf_engine_t* e, const uint64_t* d_umis_full, uint32_t n_cells, uint64_t umi_cap, uint64_t* d_lo, uint64_t* d_hi,
-                                    uint64_t* d_probe, uint64_t* d_out, const uint64_t* d_err_in, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_out || (n_cells && (!d_umis_full || !d_lo || !d_hi || !d_probe)), "null argument");
-    return launch_level_step<true>(e, (const u64*)d_umis_full, n_cells, umi_cap, (u64*)d_lo, (u64*)d_hi, (u64*)d_probe, (u64*)d_out, (const u64*)d_err_in, (hipStream_t)stream);
-} FASTF_CATCH_INT
-extern "C" int fastf_dev_level_step(fastf_engine_t* e, const uint64_t* d_umis_per_cell, uint32_t n_cells, uint64_t umi_cap, uint64_t* d_lo, uint64_t* d_hi,
-                                    uint64_t* d_probe, uint64_t* d_out, const uint64_t* d_err_in, void* stream) FASTF_TRY {
-    DEV_ENTRY(!e || !d_out || (n_cells && (!d_umis_per_cell || !d_lo || !d_hi || !d_probe)), "null argument");
-    return launch_level_step<false>(e, (const u64*)d_umis_per_cell, n_cells, umi_cap, (u64*)d_lo, (u64*)d_hi, (u64*)d_probe, (u64*)d_out, (const u64*)d_err_in, (hipStream_t)stream);
-} FASTF_CATCH_INT
-
 // device memory for the C side of the library (sweep_cmds.c keeps the records of a BAM resident); declared in host_io.h
 extern "C" void* fastf_devmem_alloc(int device, size_t bytes) FASTF_TRY {
     void* p = nullptr;
@@ -1771,7 +1265,7 @@ static int launch_probe(fastf_engine* e, const ProbeJob& j, hipStream_t s) {
         hipLaunchKernelGGL(filter_pack_kernel<false>, dim3(tiles), dim3(K1B_THREADS), 0, s, p);
     }
     HIP_OK(hipGetLastError());
-    t_end(e, s, &e->t_k1b_ms, &e->t_k1b_n);
+    t_end(e, s, T_K1B);
     dbg_sync(s, blk ? "K1b filter_pack (blocked)" : "K1b filter_pack");
     return 0;
 }
@@ -1933,7 +1427,7 @@ static int launch_sort(fastf_engine* e, u64* keys, u64* tmp, const u64* d_n, u64
             hipLaunchKernelGGL(scatter_regions_kernel, dim3(tile_grid(e, R)), dim3(SORT_THREADS), scatter_smem_bytes(ipt), s, src, dst,
                                (const u64*)e->d_rgn_phys.p, (const u64*)e->d_segcount.p, (const u32*)e->d_rgn_hist.p, (const u32*)bintot, R, ipt, shift,
                                max_n >= (24ull << 20));
-            t_end(e, s, &e->t_scatter_ms, &e->t_scatter_n);
+            t_end(e, s, T_SCATTER);
             e->rgn_hist_n = 0;                           // (the histograms are offsets now: consumed)
             dbg_sync(s, "K2 sort pass (region walk)");
             continue;
@@ -1941,12 +1435,12 @@ static int launch_sort(fastf_engine* e, u64* keys, u64* tmp, const u64* d_n, u64
         t_begin(e, s);
         if (q == 0 && seg.prefix) hipLaunchKernelGGL(tile_count_kernel<true>, dim3(tile_grid(e, T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, seg);
         else hipLaunchKernelGGL(tile_count_kernel<false>, dim3(tile_grid(e, T)), dim3(SORT_THREADS), 0, s, src, d_n, shift, cnt, ipt, none);
-        t_end(e, s, &e->t_count_ms, &e->t_count_n);
+        t_end(e, s, T_COUNT);
         hipLaunchKernelGGL(row_scan_kernel, dim3(RADIX), dim3(1024), 0, s, cnt, d_n, bintot, ipt);
         t_begin(e, s);
         if (vals) launch_scatter(e, shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, none, (q & 1) ? vtmp : vals, (q & 1) ? vals : vtmp);
         else launch_scatter(e, shift, T, s, src, dst, d_n, (const u32*)cnt, (const u32*)bintot, ipt, q == 0 ? seg : none);
-        t_end(e, s, &e->t_scatter_ms, &e->t_scatter_n);
+        t_end(e, s, T_SCATTER);
         dbg_sync(s, "K2 sort pass");
     }
     HIP_OK(hipGetLastError());
@@ -2008,7 +1502,7 @@ static int launch_reduce_regions(fastf_engine* e, const u64* sorted, const u64* 
     u32* const giant_n = giant_cnt ? giant_cnt + parity : nullptr;
     ReduceParams p{};
     p.keys = sorted; p.n_ptr = d_n; p.L = e->L; p.feat_mask = (u32)((1ull << (wide_vals ? e->row_split : e->feat_bits)) - 1);
-    p.err = (u64*)e->d_small.p + SM_COUNTERS + 3;
+    p.err = err_word(e);
     p.feature = (u32*)e->d_rg_feature.p; p.cell = (u32*)e->d_rg_cell.p; p.count = (u32*)e->d_rg_count.p; p.ukeys = (u64*)e->d_rg_ukeys.p;
     p.span_rows = (u32*)e->d_spanrows.p;
     p.giant_list = (u64*)e->d_giant.p; p.giant_n = giant_n;
@@ -2024,11 +1518,11 @@ static int launch_reduce_regions(fastf_engine* e, const u64* sorted, const u64* 
     else hipLaunchKernelGGL((reduce_hashed_kernel<false>), dim3(G), dim3(K3H_THREADS), 0, s, p);
     if (dedup == 2)       // (its last workgroup scans the chunks' row counts: no span_scan launch of its own)
         hipLaunchKernelGGL(giant_groups_kernel, dim3(giant_grid(e)), dim3(512), 0, s, wide_vals ? wide_vals : sorted, (const u64*)e->d_giant.p, giant_cnt, parity, e->L,
-                           (u32*)e->d_rg_count.p, (u64*)e->d_small.p + SM_COUNTERS + 3, (const u32*)e->d_spanrows.p, G, (u64*)e->d_spanbase.p, nrows);
+                           (u32*)e->d_rg_count.p, err_word(e), (const u32*)e->d_spanrows.p, G, (u64*)e->d_spanbase.p, nrows);
     else
         hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(1024), 0, s, (const u32*)e->d_spanrows.p, G, (u64*)e->d_spanbase.p, nrows);
     HIP_OK(hipGetLastError());
-    if (!UMI_ROWS) t_end(e, s, &e->t_k3_ms, &e->t_k3_n);
+    if (!UMI_ROWS) t_end(e, s, T_K3);
     dbg_sync(s, "K3 reduce + span scan + giant groups");
     e->rg_n = G; e->rg_umi = UMI_ROWS;
     return 0;
@@ -2045,7 +1539,7 @@ static int launch_rows_gather(fastf_engine* e, const u64* d_n, u32* feature, u32
                        (const u32*)e->d_rg_count.p, (const u64*)e->d_rg_ukeys.p, (const u32*)e->d_spanrows.p, (const u64*)e->d_spanbase.p,
                        d_n, e->rg_n, feature, cell, count, ukeys);
     HIP_OK(hipGetLastError());
-    if (!UMI_ROWS) t_end(e, s, &e->t_gather_ms, &e->t_gather_n);
+    if (!UMI_ROWS) t_end(e, s, T_GATHER);
     return 0;
 }
 
@@ -2088,14 +1582,14 @@ extern "C" int fastf_dev_umi_rows(fastf_engine_t* e, const uint64_t* d_sorted, c
 extern "C" int fastf_dev_error_bits(fastf_engine_t* e, uint64_t* bits) FASTF_TRY {
     DEV_ENTRY(!e, "null engine");
     HIP_OK(hipDeviceSynchronize());
-    if (copy_d2h(bits, (u64*)e->d_small.p + SM_COUNTERS + 3, sizeof(u64))) return 1;
+    if (copy_d2h(bits, err_word(e), sizeof(u64))) return 1;
     return 0;
 } FASTF_CATCH_INT
 
 extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void* stream) FASTF_TRY {
     DEV_ENTRY(!e, "null engine");
     // stream-ordered atomicAnd on the device: kernels raise bits with atomicOr, a host read-modify-write would race them
-    hipLaunchKernelGGL(clear_bits_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (u64*)e->d_small.p + SM_COUNTERS + 3, (u64)mask);
+    hipLaunchKernelGGL(clear_bits_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, err_word(e), (u64)mask);
     HIP_OK(hipGetLastError());
     return 0;
 } FASTF_CATCH_INT
@@ -2117,7 +1611,7 @@ static const char* err_bits_text(u64 bits) {
              (bits & ERR_UMI_TOOLONG) ? " UMI longer than umi_max_bases (raise it: up to 32, with fastf_batch_t.umi_ext from 17 on);" : "",
              (bits & ERR_KEYS_FULL) ? " key store full;" : "",
              (bits & ERR_RUN_TOO_LONG) ? " unsorted run longer than the group-only path handles: sort fully (drop FASTF_SORT_SKIP_LOW);" : "",
-             (bits & ERR_NO_PARTNER) ? " a point row without a partner among the full rows (fastf_dev_fidelity);" : "");
+             (bits & FASTF_ERR_NO_PARTNER) ? " a point row without a partner among the full rows (fastf_dev_fidelity);" : "");
     return buf;
 }
 
@@ -2664,24 +2158,24 @@ extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t
         HIP_OK(hipStreamSynchronize(s));
         std::vector<u32> ex_f, ex_c, ex_k;                 // wide keys: the rows of the exact fallback
         bool exact_wide = false;
-        if (n && e->wide && (e->h_small[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG)) {
+        if (n && e->wide && (e->h_small[SM_ERR] & ERR_RUN_TOO_LONG)) {
             // the window set could not place a UMI (a probe chain of 63), or a group was beyond what giant_groups_kernel and its
             // list take: finish the sort of the pairs — every pair is still in the store, permuted — and count the distinct
             // non-NULL pairs of every group on the host (the rows of wide_pair_rows are what the -u output needs anyway)
-            const u64 keep = e->h_small[SM_COUNTERS + 3] & ~ERR_RUN_TOO_LONG;
-            if (copy_h2d_on(small + SM_COUNTERS + 3, &keep, sizeof(u64), s)) return 1;
+            const u64 keep = e->h_small[SM_ERR] & ~ERR_RUN_TOO_LONG;
+            if (copy_h2d_on(small + SM_ERR, &keep, sizeof(u64), s)) return 1;
             if (wide_rows_exact(e, n, s, ex_f, ex_c, ex_k)) return 1;
             e->h_small[SM_NNZ] = ex_f.size();
             exact_wide = true;
         } else
-        if (n && (e->h_small[SM_COUNTERS + 3] & ERR_RUN_TOO_LONG)) {
+        if (n && (e->h_small[SM_ERR] & ERR_RUN_TOO_LONG)) {
             // runs of keys that agree on the sorted bits are long in this data (very deep (cell, feature) groups):
             // finish the sort and reduce exactly; every key is still in the store, permuted
             u64* from = e->sorted_in_tmp ? (u64*)e->d_tmp.p : (u64*)e->d_keys.p;
             u64* other = e->sorted_in_tmp ? (u64*)e->d_keys.p : (u64*)e->d_tmp.p;
             int in_other = 0;
-            const u64 keep = e->h_small[SM_COUNTERS + 3] & ~ERR_RUN_TOO_LONG;
-            if (copy_h2d_on(small + SM_COUNTERS + 3, &keep, sizeof(u64), s)) return 1;
+            const u64 keep = e->h_small[SM_ERR] & ~ERR_RUN_TOO_LONG;
+            if (copy_h2d_on(small + SM_ERR, &keep, sizeof(u64), s)) return 1;
             if (launch_sort(e, from, other, small + SM_KEYCOUNT, n, e->L.total_bits, 0, &in_other, s)) return 1;
             if (in_other) e->sorted_in_tmp = !e->sorted_in_tmp;
             e->fully_sorted = true; e->store_regions = false;
@@ -2691,7 +2185,7 @@ extern "C" int fastf_engine_finish(fastf_engine_t* e, fastf_coo_t* coo, uint64_t
             HIP_OK(hipStreamSynchronize(s));
         }
         lap("sorted and reduced");
-        if (e->h_small[SM_COUNTERS + 3]) return set_err("%s", err_bits_text(e->h_small[SM_COUNTERS + 3]));
+        if (e->h_small[SM_ERR]) return set_err("%s", err_bits_text(e->h_small[SM_ERR]));
         const u64 nnz = e->h_small[SM_NNZ];
         if (nnz > n) return set_err("internal error: %llu matrix rows out of %llu keys", (unsigned long long)nnz, (unsigned long long)n);
         // The row buffer is ordinary memory the first time it is used: pinning 23 MB takes 15 ms, the pageable copy of
@@ -2779,7 +2273,7 @@ static int wide_pair_rows(fastf_engine* e, u64 n, hipStream_t s, std::vector<u64
                            (const u64*)(small + SM_KEYCOUNT), (u32*)e->d_ncopy.p);
         if (hipGetLastError() != hipSuccess) { rc = set_err("kernel launch failed (distinct pairs of wide keys)"); break; }
         if (hipMemcpyAsync(e->h_small, small, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = set_err("device error in the distinct pairs of wide keys"); break; }
-        if (e->h_small[SM_COUNTERS + 3]) { rc = set_err("%s", err_bits_text(e->h_small[SM_COUNTERS + 3])); break; }
+        if (e->h_small[SM_ERR]) { rc = set_err("%s", err_bits_text(e->h_small[SM_ERR])); break; }
         nrows = e->h_small[SM_NROWS_U];
         if (nrows > n) { rc = set_err("internal error: %llu distinct pairs out of %llu keys", (unsigned long long)nrows, (unsigned long long)n); break; }
         uk.resize(nrows); uv.resize(nrows); e->h_ncopy.resize(nrows);
@@ -2860,7 +2354,7 @@ extern "C" int fastf_engine_umi_rows(fastf_engine_t* e, fastf_umi_rows_t* rows) 
             return 1;
         HIP_OK(hipMemcpyAsync(e->h_small, small, SM_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
-        if (e->h_small[SM_COUNTERS + 3]) return set_err("%s", err_bits_text(e->h_small[SM_COUNTERS + 3]));
+        if (e->h_small[SM_ERR]) return set_err("%s", err_bits_text(e->h_small[SM_ERR]));
         nrows = e->h_small[SM_NROWS_U];
         if (nrows > n) return set_err("internal error: %llu -u rows out of %llu keys", (unsigned long long)nrows, (unsigned long long)n);
         ukeys.resize(nrows);
@@ -2951,6 +2445,11 @@ extern "C" int fastf_engine_reseed(fastf_engine_t* e, uint32_t seed, uint64_t sk
     e->mt_live = false;
     return 0;
 } FASTF_CATCH_INT
+
+// ------------------------------------------------------------------------------------
+// the analyses of the grid verbs (sweep, cap, level): their kernels' headers and the fastf_dev_* entry points that launch them
+// ------------------------------------------------------------------------------------
+#include "analysis_entry.hpp"
 
 // ------------------------------------------------------------------------------------
 // tag histogram (crb / extract): same translation unit, reuses K2 and K3u

@@ -8,7 +8,7 @@ import numpy as np
 
 from sweep_ref import parse_matrix
 
-# the launch of fastf_dev_gene_summary as umi_engine.hip sizes it (gene_kernels.hpp), on the 256 CUs of an MI355X
+# the launch of fastf_dev_gene_summary as analysis_entry.hpp sizes it (gene_kernels.hpp), on the 256 CUs of an MI355X
 LDS_GENES, THREADS, MAX_RANGES, ITEMS, CUS = 16384, 1024, 8, 4, 256
 N_FEATURES = [1, 3, 16384, 16385, 36601, 140_000]
 PAD = 1000                                                   # rows behind *d_nnz that must not be read

@@ -114,7 +114,7 @@ def test_every_extern_c_body_in_the_cpp_unit_is_behind_the_barrier():
     allocation) or is a function-try-block closed by FASTF_CATCH_*"""
     csrc = os.path.join(ROOT, "fastf_amd", "csrc")
     n = 0
-    for name in ("umi_engine.hip", "multi_engine.hpp", "tag_hist.hpp", "gpu_frontend.hpp", "gpu_records.hpp"):
+    for name in ("umi_engine.hip", "analysis_entry.hpp", "multi_engine.hpp", "tag_hist.hpp", "gpu_frontend.hpp", "gpu_records.hpp"):
         path = os.path.join(csrc, name)
         if not os.path.exists(path):
             continue
