@@ -145,6 +145,10 @@ ABI_SYMBOLS = [
     "fastf_marker_auc", "fastf_marker_auc_form", "fastf_marker_rank", "fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header",
     "fastf_level_markers_header", "fastf_markers_row", "fastf_markers_summary_rows", "fastf_sweep_markers", "fastf_cap_markers", "fastf_level_markers",
     "fastf_dev_marker_auc",
+    # co-expression partners against full depth
+    "fastf_coexpr_header", "fastf_sweep_coexpr_header", "fastf_cap_coexpr_header", "fastf_level_coexpr_header",
+    "fastf_coexpr_check_range", "fastf_coexpr_check_gram", "fastf_coexpr_row", "fastf_coexpr_summary_row", "fastf_coexpr_from_coo",
+    "fastf_coexpr_select",
 ]
 
 
@@ -427,6 +431,14 @@ def lib():
     L.fastf_cap_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
     L.fastf_level_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
     L.fastf_dev_marker_auc.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    for name in ("fastf_coexpr_header", "fastf_sweep_coexpr_header", "fastf_cap_coexpr_header", "fastf_level_coexpr_header"):
+        getattr(L, name).restype = C.c_char_p
+    L.fastf_coexpr_check_range.argtypes = [u32, u64]
+    L.fastf_coexpr_check_gram.argtypes = [u32, u32]
+    L.fastf_coexpr_row.argtypes = [C.c_char_p, u32, u32, u32, C.c_char_p, sz]
+    L.fastf_coexpr_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_coexpr_from_coo.argtypes = [C.POINTER(Coo), u32, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.fastf_coexpr_select.argtypes = [vp, vp, u32, u32, u32, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

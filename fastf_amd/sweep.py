@@ -16,6 +16,7 @@ GENE_FIDELITY = 128   # FASTF_SWEEP_GENE_FIDELITY
 HVG_TOP = 2000        # FASTF_HVG_TOP
 NEIGHBORS = 512       # FASTF_SWEEP_NEIGHBORS
 NEIGHBORS_K = 15      # FASTF_NEIGHBORS_K
+COEXPRESSION_K = 15   # FASTF_COEXPR_K
 LABELS_MAX = 255      # FASTF_LABELS_MAX
 MARKERS_MAX = 2000    # FASTF_MARKERS_MAX
 COPY_BINS = 32        # FASTF_COPY_BINS
@@ -34,6 +35,9 @@ POINT_GENE_FIDELITY_COLUMNS = ("feature", "sum_x", "sum_y", "cells_full", "cells
 NEIGHBORS_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "cells_defined", "median_overlap", "p10_overlap", "mean_overlap", "mean_k_point")
 NEIGHBORS_COLUMNS = ("rate_cell", "rate_depth") + NEIGHBORS_TAIL_COLUMNS
 POINT_NEIGHBORS_COLUMNS = ("barcode", "k_full", "k_point", "shared", "overlap")     # <point dir>/neighbors.tsv.gz
+COEXPRESSION_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "genes_defined", "sum_k_full", "sum_k_point", "sum_shared", "mean_kept", "genes_half_kept")
+COEXPRESSION_COLUMNS = ("rate_cell", "rate_depth") + COEXPRESSION_TAIL_COLUMNS
+POINT_COEXPRESSION_COLUMNS = ("gene", "k_full", "k_point", "shared")     # the per-gene rows
 LABELS_TAIL_COLUMNS = ("seed", "n_cells", "k", "n_labels", "cells_labelled", "agree_full", "agree_point", "accuracy_full", "accuracy_point", "kept",
                        "purity_full", "purity_point")
 LABELS_COLUMNS = ("rate_cell", "rate_depth") + LABELS_TAIL_COLUMNS
@@ -323,6 +327,77 @@ def neighbors_summary_row(rate_cell, rate_depth, seed, hvg_k, k_full, k_point, s
     buf = C.create_string_buffer(640)
     _lib.check(_lib.lib().fastf_neighbors_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(hvg_k), int(k),
                                                       a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def read_coexpression_table(path, columns=COEXPRESSION_COLUMNS):
+    """the per-point co-expression rows of a table as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_coexpression(path):
+    """the per-gene co-expression rows of a gzipped table as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_COEXPRESSION_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_COEXPRESSION_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def coexpression_header(verb: str = "") -> str:
+    """the header of the per-gene rows, or with verb "sweep" / "cap" / "level" of the per-point rows"""
+    return getattr(_lib.lib(), "fastf_%scoexpr_header" % (verb + "_" if verb else ""))().decode()
+
+
+def coexpression_check_range(n_cells: int, max_q: int):
+    """raises FastfError naming FASTF_ERR_COEXPR_RANGE when n_cells * max_q >= 2^63"""
+    _lib.check(_lib.lib().fastf_coexpr_check_range(int(n_cells), int(max_q)))
+
+
+def coexpression_from_coo(coo, n_cells: int, slot_map, n_genes: int, k: int = COEXPRESSION_K):
+    """(idx u32[n_genes, k], cnt u32[n_genes], D u64[n_genes, n_genes], S u64[n_genes]) of a (feature, cell, count) COO restricted to the
+    features with a slot below n_genes: the definition in plain C on the host"""
+    p32 = C.POINTER(C.c_uint32)
+    f, c, v = [np.ascontiguousarray(x, dtype=np.uint32) for x in coo]
+    assert len(f) == len(c) == len(v)
+    m = Coo(f.ctypes.data_as(p32), c.ctypes.data_as(p32), v.ctypes.data_as(p32), len(f))
+    sm = np.ascontiguousarray(slot_map, dtype=np.uint16)
+    K = int(n_genes)
+    idx = np.zeros((max(K, 1), k), np.uint32)
+    cnt = np.zeros(max(K, 1), np.uint32)
+    D = np.zeros((max(K, 1), max(K, 1)), np.uint64)
+    S = np.zeros(max(K, 1), np.uint64)
+    _lib.check(_lib.lib().fastf_coexpr_from_coo(C.byref(m), n_cells, sm.ctypes.data, len(sm) - 1, K, k, idx.ctypes.data, cnt.ctypes.data,
+                                                D.ctypes.data if K else None, S.ctypes.data if K else None))
+    return idx[:K], cnt[:K], D[:K, :K], S[:K]
+
+
+def coexpression_select(D, S, n_cells: int, k: int = COEXPRESSION_K):
+    """(idx, cnt): the partner sets of the sums of products D (u64[K, K]) and the sums S (u64[K]) over n_cells cells, on the host"""
+    D = np.ascontiguousarray(D, dtype=np.uint64)
+    S = np.ascontiguousarray(S, dtype=np.uint64)
+    K = len(S)
+    assert D.shape == (K, K) or (K == 0 and D.size == 0)
+    idx = np.zeros((max(K, 1), k), np.uint32)
+    cnt = np.zeros(max(K, 1), np.uint32)
+    _lib.check(_lib.lib().fastf_coexpr_select(D.ctypes.data if K else None, S.ctypes.data if K else None, int(n_cells), K, k, idx.ctypes.data, cnt.ctypes.data))
+    return idx[:K], cnt[:K]
+
+
+def coexpression_row(gene, k_full, k_point, shared) -> str:
+    """one per-gene row (with its newline)"""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_coexpr_row(gene.encode() if isinstance(gene, str) else gene, int(k_full), int(k_point), int(shared), buf, len(buf)))
+    return buf.value.decode()
+
+
+def coexpression_summary_row(rate_cell, rate_depth, seed, n_cells, k_full, k_point, shared, list_value: int = 0, k: int = COEXPRESSION_K) -> str:
+    """one per-point row (with its newline) over the genes of the three arrays; list_value >= 1: that integer in the second column"""
+    a = [np.ascontiguousarray(x, dtype=np.uint32) for x in (k_full, k_point, shared)]
+    K = len(a[0])
+    assert all(len(x) == K for x in a)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_coexpr_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), int(n_cells), K, int(k),
+                                                   a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -395,6 +395,47 @@ int fastf_neighbors_row(const char *barcode, uint32_t k_full, uint32_t k_point, 
 int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
                                 const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap);
 
+/* --- co-expression partners against full depth: the fourth comparison, BETWEEN THE GENES — does a gene keep the partners
+ * it is co-expressed with at full depth.  X is the full-depth rows of a (cell rate, seed) pair, Y the rows of a grid point, A the K
+ * highly variable genes --neighbors uses (slot g of A is the gene of rank g of fastf_hvg_rank), n the sampled cells of the pair; cells
+ * without a count are included.  For M in {X, Y} and slots g, h of A, with m_ig the raw count of cell i (0 without a row):
+ *   S_g = sum_i m_ig      Q_g = sum_i m_ig^2      D_gh = sum_i m_ig m_ih      (Q_g = D_gg)
+ *   c_gh = n D_gh - S_g S_h (signed)              V_g = n Q_g - S_g^2 (>= 0)
+ *   P_M(g) = the first min(k, #{h != g : c_gh > 0}) slots h != g with c_gh > 0 by descending Pearson c_gh / sqrt(V_g V_h).  Decided
+ *            exactly: for fixed g, h precedes l iff c_gh^2 V_l > c_gl^2 V_h, or the two products are equal and h < l — in unsigned
+ *            integers of 256 bits (coexpr_order.h); no floating point takes part in the selection.  A gene with V = 0 is nobody's
+ *            partner and has none: c > 0 implies both V > 0.
+ * k = FASTF_COEXPR_K = 15; the host calls take k from 1 to 64.
+ * Range: a pair with n * max_g Q_g >= 2^63 is refused by name (FASTF_ERR_COEXPR_RANGE in the message: fastf_coexpr_check_range).  Below
+ * it |c| <= n sqrt(Q_g Q_h) < 2^63 and V < 2^63, so every product stays below 2^189.  A count of 2^21 or more among the genes of A is
+ * refused as --neighbors refuses it (FASTF_ERR_NEIGHBOR_COUNT): the three 7-bit digit planes of that option are the range of this one.
+ * This is the definition, its host implementation and its rows; no verb computes it yet and no device code exists for it.
+ * Per gene at a point:  k_full = |P_X(g)|   k_point = |P_Y(g)|   shared = |P_X(g) and P_Y(g)|.
+ *   one row per gene of A in rank order (fastf_coexpr_header, fastf_coexpr_row):   gene k_full k_point shared      (gene: the feature id)
+ *   one row per point (fastf_<verb>_coexpr_header, fastf_coexpr_summary_row): the verb's two leading columns, then
+ *     seed n_cells hvg_k k genes_defined sum_k_full sum_k_point sum_shared mean_kept genes_half_kept
+ *     genes_defined = genes with k_full > 0; mean_kept = the mean of shared / k_full over those genes (%.6f; NA when there is none);
+ *     genes_half_kept = those of them with 2 shared >= k_full.  Ratios are formed only where they are printed. --- */
+#define FASTF_COEXPR_K 15u
+#define FASTF_COEXPR_MAX_K 64u
+#define FASTF_COEXPR_MAX_PLANES 3u
+#define FASTF_COEXPR_MAX_GENES 4096u
+const char *fastf_coexpr_header(void);             /* the header of the per-gene rows */
+const char *fastf_sweep_coexpr_header(void);       /* the headers of the per-point rows */
+const char *fastf_cap_coexpr_header(void);
+const char *fastf_level_coexpr_header(void);
+/* the range rule of the selection: fails, naming FASTF_ERR_COEXPR_RANGE, when n_cells * max_q >= 2^63 */
+int fastf_coexpr_check_range(uint32_t n_cells, uint64_t max_q);
+/* the bound of the sums of products alone: fails, naming FASTF_ERR_COEXPR_CELLS, when n_cells * (2^(7 planes) - 1)^2 >= 2^64 — D_gh would leave
+ * u64 — and for planes outside 1 .. 3 */
+int fastf_coexpr_check_gram(uint32_t n_cells, uint32_t planes);
+/* one per-gene row (with its newline) */
+int fastf_coexpr_row(const char *gene, uint32_t k_full, uint32_t k_point, uint32_t shared, char *buf, size_t cap);
+/* one per-point row (with its newline) over the hvg_k genes of A; the second column as fastf_genes_summary_row prints it (list_value == 0:
+ * rate_depth) */
+int fastf_coexpr_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
+                             const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap);
+
 /* --- --labels FILE on sweep, cap and level (fastf_sweep_labels, fastf_cap_labels, fastf_level_labels; `labels=` in Python; the long
  * option alone): do the cell types survive at this depth.  The user brings one label per barcode from the full-depth analysis; the
  * neighbour sets of --neighbors turn them into votes.
@@ -749,6 +790,15 @@ int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint1
                              uint32_t *idx, uint32_t *cnt, uint64_t *norms);
 /* the number of values in both of two ascending lists */
 uint32_t fastf_neighbors_shared(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb);
+
+/* co-expression partners (section above) in plain C.  m: a COO matrix, rows in any order, restricted to the features with a slot below K in slot_map
+ * (fastf_neighbors_slot_map); a row whose cell is outside 1 .. n_cells or whose feature is outside 1 .. n_features adds nothing.
+ * idx[g * k + s], s < cnt[g]: the partners of slot g (slots, ascending; the other slots 0xFFFFFFFF).  D (u64[K * K]) and S (u64[K])
+ * may be NULL.  Fails on a count of 2^21 or more, on the range rule and on k outside 1 .. 64 */
+int fastf_coexpr_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t K, uint32_t k,
+                          uint32_t *idx, uint32_t *cnt, uint64_t *D, uint64_t *S);
+/* the selection alone: D, S over n_cells cells -> the partner sets */
+int fastf_coexpr_select(const uint64_t *D, const uint64_t *S, uint32_t n_cells, uint32_t K, uint32_t k, uint32_t *idx, uint32_t *cnt);
 
 int  fastf_engine_create(const fastf_engine_config_t *cfg, fastf_engine_t **out);
 void fastf_engine_destroy(fastf_engine_t *e);
