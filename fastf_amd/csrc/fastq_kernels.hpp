@@ -273,6 +273,7 @@ struct fastf_fqparse {
     hipEvent_t ev_h2d0[2] = {}, ev_h2d1[2] = {}, ev_p0[2] = {}, ev_p1[2] = {};
     int submitted[2] = {0, 0};
     u32 next_parity = 0;
+    u64 key_reserved = 0;                          // the last key_bound / key_cap the key array was reserved for
 };
 static constexpr size_t FQ_RK_CHUNK = (size_t)1 << 20;
 
@@ -334,6 +335,7 @@ extern "C" int fastf_fqparse_submit(fastf_fqparse_t* p, const unsigned char* sta
     HIP_OK(hipSetDevice(p->device));
     u64* keys = (u64*)fastf_taghist_reserve_device(p->h, key_bound);
     if (!keys) return 1;
+    p->key_reserved = key_bound;
     hipStream_t sc = p->h->ws->s_compute, sy = p->h->ws->s_copy;
     HIP_OK(hipEventRecord(p->ev_h2d0[par], sy));
     HIP_OK(hipMemcpyAsync(p->d_buf[par].p, staging, FQ_HDR + len, hipMemcpyHostToDevice, sy));
@@ -412,6 +414,7 @@ extern "C" int fastf_fqparse_scatter(fastf_fqparse_t* p, const uint64_t* rk, siz
     hipStream_t sc = p->h->ws->s_compute;
     u64* keys = (u64*)fastf_taghist_reserve_device(p->h, key_cap);
     if (!keys) return 1;
+    p->key_reserved = key_cap;
     for (size_t o = 0; o < n; o += FQ_RK_CHUNK) {
         const size_t m = std::min(FQ_RK_CHUNK, n - o);
         HIP_OK(hipStreamSynchronize(sc));                     // the chunk buffers are free again
@@ -426,5 +429,18 @@ extern "C" int fastf_fqparse_scatter(fastf_fqparse_t* p, const uint64_t* rk, siz
     if (copy_d2h(&st, p->d_state.p, sizeof st)) return 1;
     if (st.err & FQ_ERR_KEY_CAP) return set_err("fastq parse: escape key out of range");
     return 0;
+} FASTF_CATCH_INT
+
+// keys[r_lo .. r_lo + n) of the key array into dst (pinned or not), after everything queued on the histogram's stream; the
+// range lies within the last key_bound / key_cap a submit or a scatter reserved (the tests' view of the per-read keys)
+extern "C" int fastf_fqparse_fetch_keys(fastf_fqparse_t* p, uint64_t* dst, uint64_t r_lo, uint64_t n) FASTF_TRY {
+    if (!p || (!dst && n)) return set_err("null argument");
+    if (r_lo > p->key_reserved || n > p->key_reserved - r_lo)
+        return set_err("fastf_fqparse_fetch_keys: reads [%llu, %llu + %llu) lie beyond the %llu keys reserved", (unsigned long long)r_lo,
+                       (unsigned long long)r_lo, (unsigned long long)n, (unsigned long long)p->key_reserved);
+    HIP_OK(hipSetDevice(p->device));
+    HIP_OK(hipStreamSynchronize(p->h->ws->s_compute));
+    if (n == 0) return 0;
+    return copy_d2h(dst, (const u64*)p->h->d_k1.p + p->h->n + r_lo, (size_t)n * sizeof(u64));
 } FASTF_CATCH_INT
 #endif

@@ -135,6 +135,7 @@ int  fastf_fqparse_wait(fastf_fqparse_t *p, int parity, const fastf_fq_esc_t **e
                         double *h2d_ms, double *parse_ms);
 int  fastf_fqparse_end(fastf_fqparse_t *p, uint64_t *n_nl, uint64_t *line_start, uint32_t *err, uint64_t *err_rec);
 int  fastf_fqparse_scatter(fastf_fqparse_t *p, const uint64_t *rk, size_t n, uint64_t key_cap);
+int  fastf_fqparse_fetch_keys(fastf_fqparse_t *p, uint64_t *dst, uint64_t r_lo, uint64_t n);
 
 /* filter (filter_cmds.c): the device path of FASTQ triples (filter_kernels.hpp) */
 typedef struct { uint32_t i, s1; } fastf_flt_esc_t;      /* read i of the window: its sequence line (buffer offset s1) goes to the host */
