@@ -18,19 +18,9 @@
 #define _GNU_SOURCE
 #include "resident.h"
 
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-
-static int cp_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static int cp_err(const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    fastf_set_error_(buf);
-    return 1;
-}
 
 /* ------------------------------------------------------------------ */
 /* the grid                                                            */
@@ -40,19 +30,19 @@ int fastf_cap_parse_caps(const char *text, uint64_t *out, uint32_t cap, uint32_t
 {
     uint32_t n = 0;
     if (n_out) *n_out = 0;
-    if (!text || !out || !n_out) return cp_err("null argument");
+    if (!text || !out || !n_out) return fastf_res_err("null argument");
     for (const char *p = text;;) {
         const char *q = p;
         uint64_t v = 0;
-        if (*q == ',' || !*q) return cp_err("reads per cell `%s`: empty element", text);
+        if (*q == ',' || !*q) return fastf_res_err("reads per cell `%s`: empty element", text);
         for (; *q && *q != ','; q++) {
-            if (*q < '0' || *q > '9') return cp_err("reads per cell `%s`: expects positive integers", text);
-            if (v > (UINT64_MAX - (uint64_t)(*q - '0')) / 10) return cp_err("reads per cell `%s`: numerical result out of range", text);
+            if (*q < '0' || *q > '9') return fastf_res_err("reads per cell `%s`: expects positive integers", text);
+            if (v > (UINT64_MAX - (uint64_t)(*q - '0')) / 10) return fastf_res_err("reads per cell `%s`: numerical result out of range", text);
             v = v * 10 + (uint64_t)(*q - '0');
         }
-        if (v < 1) return cp_err("reads per cell `%s`: a cap is at least 1", text);
-        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return cp_err("reads per cell `%s`: %llu is listed twice", text, (unsigned long long)v);
-        if (n == cap) return cp_err("reads per cell `%s`: more than %u values", text, cap);
+        if (v < 1) return fastf_res_err("reads per cell `%s`: a cap is at least 1", text);
+        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return fastf_res_err("reads per cell `%s`: %llu is listed twice", text, (unsigned long long)v);
+        if (n == cap) return fastf_res_err("reads per cell `%s`: more than %u values", text, cap);
         out[n++] = v;
         if (!*q) break;
         p = q + 1;
@@ -64,20 +54,20 @@ int fastf_cap_parse_caps(const char *text, uint64_t *out, uint32_t cap, uint32_t
 int fastf_cap_point_dir(float rate_cell, uint64_t reads_per_cell, char *buf, size_t cap)
 {
     const int n = snprintf(buf, cap, "c%.3f_n%llu", (double)rate_cell, (unsigned long long)reads_per_cell);
-    return (n < 0 || (size_t)n >= cap) ? cp_err("directory name too long") : 0;
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("directory name too long") : 0;
 }
 
 int fastf_cap_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t *caps, uint32_t n_n)
 {
-    if (!n_c || !n_n || !rates_cell || !caps) return cp_err("cap: the grid needs at least one cell rate and one cap");
+    if (!n_c || !n_n || !rates_cell || !caps) return fastf_res_err("cap: the grid needs at least one cell rate and one cap");
     const float one = 1.0f;
     if (fastf_sweep_check_grid(rates_cell, n_c, &one, 1)) {       /* the cell rates are sweep's */
         char keep[400]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-        return cp_err("cap: %s", !strncmp(keep, "sweep: ", 7) ? keep + 7 : keep);
+        return fastf_res_err("cap: %s", !strncmp(keep, "sweep: ", 7) ? keep + 7 : keep);
     }
     for (uint32_t i = 0; i < n_n; i++) {
-        if (caps[i] < 1) return cp_err("cap: reads per cell %llu: a cap is at least 1", (unsigned long long)caps[i]);
-        for (uint32_t j = 0; j < i; j++) if (caps[j] == caps[i]) return cp_err("cap: reads per cell %llu is listed twice", (unsigned long long)caps[i]);
+        if (caps[i] < 1) return fastf_res_err("cap: reads per cell %llu: a cap is at least 1", (unsigned long long)caps[i]);
+        for (uint32_t j = 0; j < i; j++) if (caps[j] == caps[i]) return fastf_res_err("cap: reads per cell %llu is listed twice", (unsigned long long)caps[i]);
     }
     return 0;
 }
@@ -87,8 +77,8 @@ int fastf_cap_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t *
 /* ------------------------------------------------------------------ */
 int fastf_cap_thresholds(const uint32_t *hits, uint32_t n_cells, uint64_t cap, uint64_t *thresholds_out)
 {
-    if (n_cells && (!hits || !thresholds_out)) return cp_err("null argument");
-    if (cap < 1) return cp_err("cap: a cap is at least 1");
+    if (n_cells && (!hits || !thresholds_out)) return fastf_res_err("null argument");
+    if (cap < 1) return fastf_res_err("cap: a cap is at least 1");
     for (uint32_t k = 0; k < n_cells; k++)
         thresholds_out[k] = hits[k] <= cap ? (uint64_t)1 << 32 : fastf_draw_threshold((float)((double)cap / (double)hits[k]));
     return 0;
@@ -110,7 +100,7 @@ int fastf_cap_row_(float rate_cell, uint64_t list_value, uint32_t seed, const ui
     if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail, metrics)) return 1;
     const int n = snprintf(buf, cap, "%.3f\t%llu\t%s\t%llu\t%u\t%.6f\n", (double)rate_cell, (unsigned long long)list_value, tail,
                            (unsigned long long)hits, cells_capped, (double)fastf_cap_realised(counters[1], hits));
-    return (n < 0 || (size_t)n >= cap) ? cp_err("summary row too long") : 0;
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("summary row too long") : 0;
 }
 int fastf_cap_summary_row(float rate_cell, uint64_t reads_per_cell, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                           const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
@@ -147,11 +137,10 @@ static int cap_pair_begin(const res_pair_t *p, void **ctx)
 {
     res_rate_t *S = p->S;
     res_times_t *T = p->T;
-    const res_fid_t *Fd = p->Fd;
     const uint64_t H = S->H;
     const uint32_t n_cells = S->n_cells;
     cap_pair_t *c = (cap_pair_t *)calloc(1, sizeof *c);
-    if (!(*ctx = c)) return cp_err("out of memory");
+    if (!(*ctx = c)) return fastf_res_err("out of memory");
     double tt = fastf_res_now();
 
     /* the hits per cell, counted where K1a left the cell indices; to the host once, through pinned memory */
@@ -164,13 +153,13 @@ static int cap_pair_begin(const res_pair_t *p, void **ctx)
         fastf_devmem_copy(c->h_hits, c->d_hits, (size_t)n_cells * 4)) return RES_FAIL;
     uint64_t sum = 0;
     for (uint32_t k = 0; k < n_cells; k++) sum += c->h_hits[k];
-    if (sum != H) return cp_err("internal error: %llu hits per cell in total, K1a counted %llu", (unsigned long long)sum, (unsigned long long)H);
+    if (sum != H) return fastf_res_err("internal error: %llu hits per cell in total, K1a counted %llu", (unsigned long long)sum, (unsigned long long)H);
     T->planes += fastf_res_now() - tt;
-    if (!Fd->full) return RES_OK;
+    if (!res_cfg_full(&S->cfg)) return RES_OK;
     tt = fastf_res_now();                                   /* the full rows of the pair, once: T = 2^32 for every cell */
     for (uint32_t k = 0; k < n_cells; k++) c->h_thr[k] = (uint64_t)1 << 32;
     if (cap_plane(c, p)) return RES_FAIL;
-    *(Fd->on ? &T->fidelity : Fd->gene_on ? &T->gene_fid : &T->neighbors) += fastf_res_now() - tt;
+    *fastf_res_full_timer(S, T, 0) += fastf_res_now() - tt;
     return fastf_res_full_run(S, (const uint32_t *)c->d_plane, T);
 }
 
@@ -198,9 +187,7 @@ static int cap_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uint6
 }
 
 static const res_verb_t cap_verb = {
-    .name = "cap",
-    .header = { fastf_cap_header, fastf_cap_genes_header, fastf_cap_cells_header, fastf_cap_fidelity_header, fastf_cap_gene_fidelity_header, fastf_cap_neighbors_header,
-                fastf_cap_labels_header, fastf_cap_label_classes_header, fastf_cap_markers_header, fastf_cap_reps_header, fastf_cap_genes_reps_header },
+    .name = "cap", .index = VERB_CAP, .header = fastf_cap_header,
     .check_caps = fastf_cap_check_grid, .caps_point_dir = fastf_cap_point_dir,
     .refusal_tail = ", and a cap has no point-by-point form",     /* (a global depth rate cannot express a cap) */
     .planes_words = "hits per cell + thresholds + planes", .fid_before = "", .fid_after = " full-depth points",

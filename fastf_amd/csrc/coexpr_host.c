@@ -130,11 +130,7 @@ done:
 /* ------------------------------------------------------------------ */
 /* the rows                                                            */
 /* ------------------------------------------------------------------ */
-const char *fastf_coexpr_header(void) { return "gene\tk_full\tk_point\tshared\n"; }
-#define COEXPR_COLUMNS_TAIL "seed\tn_cells\thvg_k\tk\tgenes_defined\tsum_k_full\tsum_k_point\tsum_shared\tmean_kept\tgenes_half_kept\n"
-const char *fastf_sweep_coexpr_header(void) { return "rate_cell\trate_depth\t" COEXPR_COLUMNS_TAIL; }
-const char *fastf_cap_coexpr_header(void) { return "rate_cell\treads_per_cell\t" COEXPR_COLUMNS_TAIL; }
-const char *fastf_level_coexpr_header(void) { return "rate_cell\tumi_cap\t" COEXPR_COLUMNS_TAIL; }
+const char *fastf_coexpr_header(void) { return "gene\tk_full\tk_point\tshared\n"; }   /* (the per-verb headers: grid_rows.c, GRID_TABLES) */
 
 int fastf_coexpr_row(const char *gene, uint32_t k_full, uint32_t k_point, uint32_t shared, char *buf, size_t cap)
 {

@@ -1,34 +1,24 @@
 /*
  * grid_run.c — the driver of `fastF sweep`, `fastF cap` and `fastF level` (resident.h: res_job_t, res_verb_t): the checks of an entry
  * point, the tables of the run, the (cell rate, seed) pairs on ONE res_rate_t, the body of every point, the close.  A verb hands in
- * its descriptor; what it does by itself — making the decision plane of a point — it does in the hooks.  A further per-point option is
- * wired here and nowhere else: its table in grid_open / grid_close, its device stage in fastf_res_point_compare (resident.c), its
- * rows in fastf_res_fid_point.
+ * its descriptor; what it does by itself — making the decision plane of a point — it does in the hooks.  A further comparison of a
+ * point against full depth is a descriptor and a writer in res_tables.c and a device stage in fastf_res_point_compare (resident.c);
+ * here it has only its option and its profile line.
  */
 #define _GNU_SOURCE
 #include "resident.h"
 
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
-static int gr_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static int gr_err(const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    fastf_set_error_(buf);
-    return 1;
-}
-
 #define GRID_FLAGS (FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS)
 
 int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path)
 {
-    if (markers < 1 || markers > FASTF_MARKERS_MAX) return gr_err("%s: --markers: N = %u, from 1 to %u", verb, markers, FASTF_MARKERS_MAX);
-    return labels_path ? 0 : gr_err("%s: --markers needs --labels", verb);
+    if (markers < 1 || markers > FASTF_MARKERS_MAX) return fastf_res_err("%s: --markers: N = %u, from 1 to %u", verb, markers, FASTF_MARKERS_MAX);
+    return labels_path ? 0 : fastf_res_err("%s: --markers needs --labels", verb);
 }
 
 /* ------------------------------------------------------------------ */
@@ -51,8 +41,8 @@ static int grid_refuse(const res_verb_t *V, const res_job_t *job, int labels, in
     else if (fallback && (f & FASTF_SWEEP_FIDELITY)) opt = "--fidelity";      /* (the full rows live on the device alone: bam2db() point by point has none) */
     else if (f & FASTF_SWEEP_GENE_FIDELITY) opt = "--gene-fidelity";
     else if (fallback && (f & FASTF_SWEEP_CELLS)) opt = "--cells";            /* (the per-cell rows come from the device's keys alone) */
-    if (opt) return gr_err("%s: %s %s the resident form, and this job is outside it (%s)%s", V->name, opt, needs, why, tail);
-    return fallback ? 0 : gr_err("%s: this job is outside the resident form (%s)%s", V->name, why, tail);
+    if (opt) return fastf_res_err("%s: %s %s the resident form, and this job is outside it (%s)%s", V->name, opt, needs, why, tail);
+    return fallback ? 0 : fastf_res_err("%s: this job is outside the resident form (%s)%s", V->name, why, tail);
 }
 
 /* ------------------------------------------------------------------ */
@@ -60,7 +50,7 @@ static int grid_refuse(const res_verb_t *V, const res_job_t *job, int labels, in
 /* ------------------------------------------------------------------ */
 static void grid_close(res_tables_t *tb)
 {
-    fastf_res_tsv_close(&tb->tsv, 0); fastf_res_genes_close(&tb->G, 0); fastf_res_cells_close(&tb->C, 0); fastf_res_fid_close(&tb->Fd, 0); fastf_res_reps_close(&tb->P, 0);
+    fastf_res_tsv_close(&tb->tsv, 0); fastf_res_genes_close(&tb->G, 0); fastf_res_cells_close(&tb->C, 0); fastf_res_cmp_close(&tb->Fd, 0); fastf_res_reps_close(&tb->P, 0);
 }
 
 /* on failure the caller closes what was opened (grid_close) */
@@ -72,14 +62,11 @@ static int grid_open(const res_verb_t *V, const res_job_t *job, const fastf_labe
     char name[64];
     memset(tb, 0, sizeof *tb);
     snprintf(name, sizeof name, "%s.tsv", V->name);
-    return fastf_res_tsv_open(&tb->tsv, out, name, V->header.summary()) ||
-           fastf_res_genes_open(&tb->G, genes, V->name, out, V->header.genes(), job->n_c * job->n_list, job->reps) ||
-           fastf_res_cells_open(&tb->C, (f & FASTF_SWEEP_CELLS) != 0, V->name, out, V->header.cells()) ||
-           fastf_res_fid_open(&tb->Fd, (f & FASTF_SWEEP_FIDELITY) != 0, (f & FASTF_SWEEP_GENE_FIDELITY) != 0, V->name, out, V->header.fidelity(), V->header.gene_fidelity()) ||
-           fastf_res_fid_open_neighbors(&tb->Fd, (f & FASTF_SWEEP_NEIGHBORS) != 0, V->name, out, V->header.neighbors()) ||
-           fastf_res_fid_open_labels(&tb->Fd, labels, V->name, out, V->header.labels(), V->header.label_classes()) ||
-           fastf_res_fid_open_markers(&tb->Fd, job->markers, V->name, out, V->header.markers()) ||
-           fastf_res_reps_open(&tb->P, job->reps, V->name, out, job->seeds, job->n_s, job->n_c, job->n_list, genes, device, V->header.reps(), V->header.genes_reps());
+    return fastf_res_tsv_open(&tb->tsv, out, name, V->header()) ||
+           fastf_res_genes_open(&tb->G, genes, V, out, job->n_c * job->n_list, job->reps) ||
+           fastf_res_cells_open(&tb->C, (f & FASTF_SWEEP_CELLS) != 0, V, out) ||
+           fastf_res_cmp_open(&tb->Fd, V, out, f, labels, job->markers) ||
+           fastf_res_reps_open(&tb->P, job->reps, V, out, job->seeds, job->n_s, job->n_c, job->n_list, genes, device);
 }
 
 /* ------------------------------------------------------------------ */
@@ -124,7 +111,7 @@ static int grid_pair(const res_verb_t *V, const res_pair_t *p, const uint64_t *c
             if (fastf_res_point_write(S, dir, job->bam, job->caps ? fastf_cap_realised(counters[1], S->H) : rd, counters, nnz, T)) goto done;
             if (V->point_files && V->point_files(ctx, p, dir)) goto done;
         }
-        if (fastf_res_fid_point(&tb->Fd, S, p->summary_only ? NULL : dir, rd, lv, T)) goto done;
+        if (fastf_res_cmp_point(&tb->Fd, S, p->summary_only ? NULL : dir, rd, lv, T)) goto done;
         if (G->on) {
             char grow[256];
             tt = fastf_res_now();
@@ -154,7 +141,7 @@ done:
 static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, res_tables_t *tb)
 {
     int rc = RES_FAIL;
-    const res_fid_t *const Fd = &tb->Fd;
+    const res_cmp_t *const Fd = &tb->Fd;
     const uint32_t n_c = job->n_c, n_s = job->n_s, points = n_c * job->n_list * n_s;
     const int prof = getenv("FASTF_PROFILE") != NULL;
     res_times_t T; memset(&T, 0, sizeof T);
@@ -167,12 +154,12 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
     const uint32_t n_pairs = n_c * n_s;
     float *pair_rate = (float *)malloc(n_pairs * sizeof *pair_rate);
     uint32_t *pair_seed = (uint32_t *)malloc(n_pairs * sizeof *pair_seed);
-    if (!pair_rate || !pair_seed) { gr_err("out of memory"); goto done; }
+    if (!pair_rate || !pair_seed) { fastf_res_err("out of memory"); goto done; }
     for (uint32_t i = 0; i < n_c; i++) for (uint32_t k = 0; k < n_s; k++) { pair_rate[i * n_s + k] = job->rates_cell[i]; pair_seed[i * n_s + k] = job->seeds[k]; }
     if ((rc = fastf_res_lists_load(job->barcodes, job->features, pair_rate, pair_seed, n_pairs, &LL)) != RES_OK) goto done;
     rc = RES_FAIL;
     S.cfg.max_cells = fastf_res_lists_max_cells(&LL);
-    S.cfg.fidelity = Fd->on; S.cfg.gene_fid = Fd->gene_on; S.cfg.neighbors = Fd->nbr_on || Fd->lab_on; S.cfg.labels = Fd->lab_on; S.cfg.lab_t = Fd->labels; S.cfg.markers = Fd->markers;
+    fastf_res_cmp_cfg(Fd, &S.cfg);
     {   const char *nr = getenv("FASTF_RES_NO_REUSE"); S.cfg.no_reuse = nr && nr[0] == '1'; }
     T.lists = fastf_res_now() - tt; tt = fastf_res_now();
     if (fastf_res_decode(V->name, job->bam, &LL.L[0], device, &R)) goto done;
@@ -185,7 +172,7 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
         if (fastf_res_reps_rate_begin(&tb->P, &LL.L[i * n_s], 1)) { rc = RES_FAIL; goto done; }
         for (uint32_t k = 0; k < n_s; k++) {
             const uint32_t at = i * n_s + k;
-            const res_pair_t pair = { job, &S, &R, &LL.L[at], Fd, &T, job->rates_cell[i], job->seeds[k], device, (job->flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, prof };
+            const res_pair_t pair = { job, &S, &R, &LL.L[at], &T, job->rates_cell[i], job->seeds[k], device, (job->flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, prof };
             if ((rc = grid_pair(V, &pair, LL.keys[at], tb, k)) != RES_OK) goto done;
         }
         if (fastf_res_reps_rate_end(&tb->P, job->rates_cell[i], job->rates_depth, job->caps, &T)) { rc = RES_FAIL; goto done; }
@@ -201,12 +188,13 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
                                       "laid out %u times; replicate tables and per-gene accumulation %.3f s\n", v, T.opens, T.engine + T.block_k1a, T.engine, T.block_k1a, T.relays, T.reps);
         if (tb->G.on) fprintf(stderr, "[%s] --genes: per-gene D2H, rows and files %.3f s (the kernel is part of the per-point device work)\n", v, T.genes);
         if (tb->C.on) fprintf(stderr, "[%s] --cells: full sort + K3u + copy summary + D2H %.3f s (%.4f s a point), rows and files %.3f s\n", v, T.cells_dev, T.cells_dev / points, T.cells);
-        if (Fd->on) fprintf(stderr, "[%s] --fidelity: %s%u%s, the joins, their D2H, rows and files %.3f s\n", v, V->fid_before, n_pairs, V->fid_after, T.fidelity);
-        if (Fd->gene_on) fprintf(stderr, "[%s] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", v, Fd->on ? "" : "the full-depth rows of every pair, ", T.gene_fid);
-        if (Fd->mk_on) fprintf(stderr, "[%s] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", v, Fd->markers, T.markers);
-        if (Fd->lab_on) fprintf(stderr, "[%s] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", v, fastf_labels_count(Fd->labels),
-                                (unsigned long long)fastf_labels_unknown(Fd->labels), Fd->nbr_on ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (Fd->nbr_on ? 0.0 : T.neighbors));
-        if (Fd->nbr_on) fprintf(stderr, "[%s] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", v, Fd->on || Fd->gene_on ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
+        const int fid = res_cmp_on(Fd, CMP_FIDELITY), gene_fid = res_cmp_on(Fd, CMP_GENE_FID), nbr = res_cmp_on(Fd, CMP_NEIGHBORS);
+        if (fid) fprintf(stderr, "[%s] --fidelity: %s%u%s, the joins, their D2H, rows and files %.3f s\n", v, V->fid_before, n_pairs, V->fid_after, T.fidelity);
+        if (gene_fid) fprintf(stderr, "[%s] --gene-fidelity: %sthe partner counts, the per-gene sums, their D2H, rows and files %.3f s\n", v, fid ? "" : "the full-depth rows of every pair, ", T.gene_fid);
+        if (res_cmp_on(Fd, CMP_MARKERS)) fprintf(stderr, "[%s] --markers: top %u of the genes per label; the kernel calls on the planes, their D2H, the ranks, rows and files %.3f s\n", v, Fd->markers, T.markers);
+        if (res_cmp_on(Fd, CMP_LABELS)) fprintf(stderr, "[%s] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", v, fastf_labels_count(Fd->labels),
+                                (unsigned long long)fastf_labels_unknown(Fd->labels), nbr ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (nbr ? 0.0 : T.neighbors));
+        if (nbr) fprintf(stderr, "[%s] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", v, fid || gene_fid ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
     }
 done:
     fastf_res_rate_close(&S);
@@ -223,8 +211,8 @@ done:
 static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labels_t *labels)
 {
     if (V->check_caps ? V->check_caps(job->rates_cell, job->n_c, job->caps, job->n_list) : fastf_sweep_check_grid(job->rates_cell, job->n_c, job->rates_depth, job->n_list)) return 1;
-    if (job->flags & ~(uint32_t)GRID_FLAGS) return gr_err("%s: unknown flags 0x%x", V->name, job->flags);
-    if (access(job->bam, R_OK) == -1) return gr_err("bam file: %s does not exist.", job->bam);
+    if (job->flags & ~(uint32_t)GRID_FLAGS) return fastf_res_err("%s: unknown flags 0x%x", V->name, job->flags);
+    if (access(job->bam, R_OK) == -1) return fastf_res_err("bam file: %s does not exist.", job->bam);
     int dev0 = 0, dev_second = -1, several = 0;
     {   const char *dvs = getenv("FASTF_DEVICES");
         fastf_pick_devices(dvs, getenv("FASTF_DEVICE"), &dev0, &dev_second);
@@ -247,7 +235,7 @@ static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labe
         ran = 1;
         rc = V->point_by_point(job, (job->flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, &tb);
     }
-    if (rc || fastf_res_genes_close(&tb.G, 1) || fastf_res_cells_close(&tb.C, 1) || fastf_res_fid_close(&tb.Fd, 1) ||
+    if (rc || fastf_res_genes_close(&tb.G, 1) || fastf_res_cells_close(&tb.C, 1) || fastf_res_cmp_close(&tb.Fd, 1) ||
         fastf_res_reps_close_grid(&tb.P, 1, job->rates_cell, job->rates_depth, job->caps) || fastf_res_tsv_close(&tb.tsv, 1)) goto fail;
     return 0;
 fail:
@@ -262,11 +250,11 @@ int fastf_res_grid_run(const res_verb_t *V, const res_job_t *asked)
 {
     res_job_t job = *asked;
     if (job.reps && fastf_check_seeds_(V->name, job.seeds, job.n_s)) return 1;
-    if (!job.bam || !job.barcodes || !job.features) return gr_err("%s: null argument", V->name);
+    if (!job.bam || !job.barcodes || !job.features) return fastf_res_err("%s: null argument", V->name);
     if (!job.out_dir) job.out_dir = ".";
     fastf_labels_t *labels = NULL;                          /* the labels file is read and checked before anything is written */
     if (job.labels_path) {
-        if (access(job.bam, R_OK) == -1) return gr_err("bam file: %s does not exist.", job.bam);
+        if (access(job.bam, R_OK) == -1) return fastf_res_err("bam file: %s does not exist.", job.bam);
         if (fastf_labels_load(job.labels_path, job.barcodes, &labels)) return 1;
     }
     const int rc = grid_run_(V, &job, labels);

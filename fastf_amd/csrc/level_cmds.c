@@ -18,20 +18,11 @@
 #define _GNU_SOURCE
 #include "resident.h"
 
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
-static int lv_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static int lv_err(const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    fastf_set_error_(buf);
-    return 1;
-}
 /* a message of cap's list rules, speaking of this verb's list */
 static int lv_from_cap(void)
 {
@@ -60,7 +51,7 @@ int fastf_level_check_grid(const float *rates_cell, uint32_t n_c, const uint64_t
 int fastf_level_point_dir(float rate_cell, uint64_t umi_cap, char *buf, size_t cap)
 {
     const int n = snprintf(buf, cap, "c%.3f_m%llu", (double)rate_cell, (unsigned long long)umi_cap);
-    return (n < 0 || (size_t)n >= cap) ? lv_err("directory name too long") : 0;
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("directory name too long") : 0;
 }
 
 /* level.tsv has cap.tsv's columns, its second named umi_cap (the headers: beside cap's) */
@@ -76,21 +67,11 @@ int fastf_level_summary_row(float rate_cell, uint64_t umi_cap, uint32_t seed, co
 /* ------------------------------------------------------------------ */
 static int write_thresholds(const char *dir, const fastf_lists_t *L, uint32_t n_cells, const uint64_t *thr, const uint64_t *umis_full, const uint64_t *umis)
 {
-    static const char head[] = "barcode\tthreshold\tumis_full\tumis\n";
-    size_t room = sizeof head;
-    for (uint32_t k = 0; k < n_cells; k++) room += strlen(L->barcode[k]) + 3 * 21 + 2;
-    char *text = (char *)malloc(room), path[4200], tmp[4300];
-    if (!text) return lv_err("out of memory");
-    size_t len = (size_t)snprintf(text, room, "%s", head);
-    for (uint32_t k = 0; k < n_cells; k++)
-        len += (size_t)snprintf(text + len, room - len, "%s\t%llu\t%llu\t%llu\n", L->barcode[k], (unsigned long long)thr[k],
-                                (unsigned long long)umis_full[k], (unsigned long long)umis[k]);
-    snprintf(path, sizeof path, "%s/thresholds.tsv.gz", dir);
-    snprintf(tmp, sizeof tmp, "%s.partial", path);
-    int bad = fastf_res_make_dir(dir);
-    if (!bad && (fastf_write_gz_text(tmp, text, len) || rename(tmp, path) != 0)) { unlink(tmp); bad = lv_err("cannot write %s", path); }
-    free(text);
-    return bad;
+    gtext t = { NULL, 0, 0 };
+    int bad = fastf_gt_str(&t, "barcode\tthreshold\tumis_full\tumis\n");
+    for (uint32_t k = 0; k < n_cells && !bad; k++)
+        bad = fastf_gt_str(&t, L->barcode[k]) || fastf_gt_u64(&t, '\t', thr[k]) || fastf_gt_u64(&t, '\t', umis_full[k]) || fastf_gt_u64(&t, '\t', umis[k]) || fastf_gt_str(&t, "\n");
+    return fastf_res_text_file(dir, "thresholds.tsv.gz", &t, bad);
 }
 
 /* ------------------------------------------------------------------ */
@@ -124,7 +105,7 @@ static int level_pair_begin(const res_pair_t *p, void **ctx)
     res_times_t *T = p->T;
     const uint32_t n_cells = S->n_cells;
     level_pair_t *c = (level_pair_t *)calloc(1, sizeof *c);
-    if (!(*ctx = c)) return lv_err("out of memory");
+    if (!(*ctx = c)) return fastf_res_err("out of memory");
     double tt = fastf_res_now();
     const size_t nc1 = (size_t)n_cells + 1;
     const uint64_t plane_words = ((S->H + 63) / 64) * 2 + 64;   /* (zeroed slack behind the plane: K1b reads a unit's words unconditionally) */
@@ -156,7 +137,7 @@ static int level_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const c
     if (j) { const int irc = fastf_res_level_init(S, umi_cap, &c->open, &c->capped, T); if (irc != RES_OK) return irc; }
     while (c->open) {                                       /* open cells are probed at (lo + hi) / 2, every other cell at 0 */
         if (c->passes == LEVEL_MAX_PASSES)
-            return lv_err("internal error: %llu cells still open after %u passes at point %s", (unsigned long long)c->open, c->passes, point_name);
+            return fastf_res_err("internal error: %llu cells still open after %u passes at point %s", (unsigned long long)c->open, c->passes, point_name);
         const double tt = fastf_res_now();
         if (level_plane(c, p, S->lv.probe)) return RES_FAIL;
         T->search += fastf_res_now() - tt;
@@ -204,9 +185,7 @@ static void level_run_profile(const res_job_t *job, const res_times_t *T)
 }
 
 static const res_verb_t level_verb = {
-    .name = "level",
-    .header = { fastf_level_header, fastf_level_genes_header, fastf_level_cells_header, fastf_level_fidelity_header, fastf_level_gene_fidelity_header, fastf_level_neighbors_header,
-                fastf_level_labels_header, fastf_level_label_classes_header, fastf_level_markers_header, fastf_level_reps_header, fastf_level_genes_reps_header },
+    .name = "level", .index = VERB_LEVEL, .header = fastf_level_header,
     .check_caps = fastf_level_check_grid, .caps_point_dir = fastf_level_point_dir,
     .refusal_tail = ", and a UMI cap has no point-by-point form",
     .planes_words = "planes of the points", .fid_before = "the full rows kept from ", .fid_after = " first passes",

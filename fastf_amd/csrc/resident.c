@@ -1,37 +1,18 @@
 /*
  * resident.c — the resident pipeline of `fastF sweep`, `fastF cap` and `fastF level` (resident.h): list loading with one dictionary,
  * the decode of the BAM into device-resident records, per cell rate the engine + the records in its layout + K1a, per point K1b /
- * sort / reduce / gather / summary and the writers, the tables of a run and the command line of the three verbs.  The driver that
- * runs a verb's grid on it: grid_run.c.
+ * sort / reduce / gather / summary and the matrix writers, the replicate accumulators and the command line of the three verbs.  The
+ * tables and point files of a run: res_tables.c; the driver that runs a verb's grid: grid_run.c.
  */
 #define _GNU_SOURCE
 #include "resident.h"
 
 #include <errno.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <time.h>
 #include <unistd.h>
-
-double fastf_res_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec * 1e-9; }
-static int rs_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static int rs_err(const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    fastf_set_error_(buf);
-    return 1;
-}
-
-int fastf_res_make_dir(const char *path)
-{
-    if (mkdir(path, 0777) == 0 || errno == EEXIST) return 0;
-    return rs_err("cannot create directory %s: %s", path, strerror(errno));
-}
 
 static uint32_t bits_for(uint64_t v) { uint32_t b = 0; while (b < 64 && (v >> b)) b++; return b ? b : 1; }
 
@@ -52,14 +33,14 @@ int fastf_res_lists_load(const char *barcodes, const char *features, const float
     memset(out, 0, sizeof *out);
     fastf_lists_t *L = out->L = (fastf_lists_t *)calloc(n_c, sizeof *L);
     uint64_t **keys = out->keys = (uint64_t **)calloc(n_c, sizeof *keys);
-    if (!L || !keys) { rs_err("out of memory"); return RES_FAIL; }
+    if (!L || !keys) { fastf_res_err("out of memory"); return RES_FAIL; }
     for (uint32_t i = 0; i < n_c; i++) {
         if (fastf_lists_load(barcodes, features, rates_cell[i], seeds[i], &L[i])) return RES_FAIL;
         out->n = i + 1;
     }
     for (uint32_t i = 0; i < n_c; i++) {
-        if (L[i].n_features != L[0].n_features) { rs_err("internal error: the feature list changed between loads"); return RES_FAIL; }
-        if (!(keys[i] = (uint64_t *)malloc((L[i].n_cells ? L[i].n_cells : 1) * sizeof **keys))) { rs_err("out of memory"); return RES_FAIL; }
+        if (L[i].n_features != L[0].n_features) { fastf_res_err("internal error: the feature list changed between loads"); return RES_FAIL; }
+        if (!(keys[i] = (uint64_t *)malloc((L[i].n_cells ? L[i].n_cells : 1) * sizeof **keys))) { fastf_res_err("out of memory"); return RES_FAIL; }
         for (size_t k = 0; k < L[i].n_cells; k++) keys[i][k] = fastf_keydict_add(L[0].cell_dict, L[i].barcode[k], strlen(L[i].barcode[k]));
         /* keys wider than 64 bits with the shortest UMI field: that cell rate would need the wide engine */
         if (bits_for(L[i].n_cells) + bits_for(L[i].n_features) + 27 > 64) return RES_NOT_COVERED;
@@ -86,7 +67,7 @@ static int resident_reserve(resident_t *r, uint64_t need)
     nr.umi = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4); nr.meta = (uint32_t *)fastf_devmem_alloc(r->device, cap * 4);
     if (!nr.cb || !nr.gx || !nr.umi || !nr.meta) {
         fastf_res_free(&nr);
-        return rs_err("%s: the records do not fit the device: %llu bytes were needed for %llu records", r->verb, (unsigned long long)(cap * 24), (unsigned long long)need);
+        return fastf_res_err("%s: the records do not fit the device: %llu bytes were needed for %llu records", r->verb, (unsigned long long)(cap * 24), (unsigned long long)need);
     }
     if (r->n && (fastf_devmem_copy(nr.cb, r->cb, r->n * 8) || fastf_devmem_copy(nr.gx, r->gx, r->n * 8) ||
                  fastf_devmem_copy(nr.umi, r->umi, r->n * 4) || fastf_devmem_copy(nr.meta, r->meta, r->n * 4))) { fastf_res_free(&nr); return 1; }
@@ -104,17 +85,17 @@ int fastf_res_decode(const char *verb, const char *bam_file, const fastf_lists_t
     memset(R, 0, sizeof *R); R->device = device; R->verb = verb;
     {   const char *gp = getenv("FASTF_GPU_PARSE");
         bam = fastf_bam_open2(bam_file, 0, 1 | ((gp && gp[0] == '0') ? 0 : 4) | ((device + 1) << 8)); }
-    if (!bam) { rs_err("Fail to open BAM file %s (%s)", bam_file, fastf_last_error()); goto done; }
+    if (!bam) { fastf_res_err("Fail to open BAM file %s (%s)", bam_file, fastf_last_error()); goto done; }
     (void)fastf_bam_enable_device_parse(bam, L0->cell_dict, L0->feat_dict);
     const size_t cap = (size_t)4 << 20;
-    if (!(stage = fastf_pinned_alloc(cap * 24))) { rs_err("%s: no pinned staging memory (%s)", verb, fastf_last_error()); goto done; }
+    if (!(stage = fastf_pinned_alloc(cap * 24))) { fastf_res_err("%s: no pinned staging memory (%s)", verb, fastf_last_error()); goto done; }
     uint64_t *s_cb = (uint64_t *)stage, *s_gx = s_cb + cap; uint32_t *s_umi = (uint32_t *)(s_gx + cap), *s_meta = s_umi + cap;
     for (;;) {
         int on_dev = 0; fastf_batch_t dev; memset(&dev, 0, sizeof dev);
         const long n = fastf_bam_read_batch_dev(bam, L0->cell_dict, L0->feat_dict, s_cb, s_gx, s_umi, s_meta, cap, &on_dev, &dev);
-        if (n < 0) { rs_err("%s: %s", bam_file, fastf_last_error()); goto done; }
+        if (n < 0) { fastf_res_err("%s: %s", bam_file, fastf_last_error()); goto done; }
         if (n == 0) break;
-        if (R->n + (uint64_t)n >= ((uint64_t)1 << 32) - 1) { rs_err("%s: more than 2^32 - 2 records: %llu bytes of records are beyond what the device-level calls take", verb, (unsigned long long)((R->n + (uint64_t)n) * 24)); goto done; }
+        if (R->n + (uint64_t)n >= ((uint64_t)1 << 32) - 1) { fastf_res_err("%s: more than 2^32 - 2 records: %llu bytes of records are beyond what the device-level calls take", verb, (unsigned long long)((R->n + (uint64_t)n) * 24)); goto done; }
         if (resident_reserve(R, R->n + (uint64_t)n)) goto done;
         const uint64_t *f_cb = on_dev ? dev.cb_key : s_cb, *f_gx = on_dev ? dev.gx_key : s_gx;
         const uint32_t *f_umi = on_dev ? dev.umi : s_umi, *f_meta = on_dev ? dev.meta : s_meta;
@@ -175,7 +156,7 @@ static int res_block_room(res_buf_t *b, int kind, size_t bytes, size_t n, int de
 }
 static int no_room(const res_rate_t *S, const char *what, size_t bytes)
 {
-    rs_err("%s: %s of cell rate %.3f do not fit: %zu bytes (%s)", S->verb, what, (double)S->rate_cell, bytes, fastf_last_error());
+    fastf_res_err("%s: %s of cell rate %.3f do not fit: %zu bytes (%s)", S->verb, what, (double)S->rate_cell, bytes, fastf_last_error());
     return RES_FAIL;
 }
 
@@ -232,7 +213,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         res_room(&S->buf.rows, RES_DEV, (N ? N : 1) * 12, device) ||
         res_room(&S->buf.upc, RES_DEV, room_cells * 8, device) || res_room(&S->buf.gpc, RES_DEV, room_cells * 4, device) ||
         res_room(&S->buf.h_upc, RES_PIN, room_cells * 8, device) || res_room(&S->buf.h_gpc, RES_PIN, room_cells * 4, device)) {
-        rs_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
+        fastf_res_err("%s: the working set of cell rate %.3f does not fit: %zu bytes were needed beside the records (%s)", verb, (double)rate_cell, need, fastf_last_error());
         return RES_FAIL;
     }
     if (genes) {                                            /* the per-gene arrays of a point and their pinned host copies, once */
@@ -277,7 +258,7 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
     if (S->cfg.markers) {                                   /* the four tables of one row set on the device, of both row sets pinned, and the two rank tables */
         S->mk_set = res_mk_set_bytes(S->n_labels, FASTF_HVG_TOP);
         if (res_room(&S->buf.mk, RES_DEV, S->mk_set, device) || res_room(&S->buf.h_mk, RES_PIN, 2 * S->mk_set, device)) return no_room(S, "the marker tables", S->mk_set);
-        if (res_room(&S->buf.mk_rank, RES_HOST, 2 * (size_t)S->n_labels * FASTF_HVG_TOP * sizeof(uint32_t), device)) { rs_err("%s: out of memory", verb); return RES_FAIL; }
+        if (res_room(&S->buf.mk_rank, RES_HOST, 2 * (size_t)S->n_labels * FASTF_HVG_TOP * sizeof(uint32_t), device)) { fastf_res_err("%s: out of memory", verb); return RES_FAIL; }
     }
     if (S->cfg.fidelity) {                                  /* the full rows of the pair, the three sums and their pinned copies with umis_full and genes_full, once */
         const size_t dev_bytes = res_fid_layout(NULL, room_cells, 0).bytes;
@@ -365,10 +346,10 @@ int fastf_res_point_run(res_rate_t *S, const uint32_t *d_plane, const char *poin
     if (fastf_devmem_copy(S->buf.h_small.u64, S->buf.small.p, SM_HITS * 8)) return RES_FAIL;
     bits |= S->buf.h_small.u64[SM_CNT + 3];
     if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: bam2db() runs such a file again with wider keys */
-    if (bits) { rs_err("%s: device error bits 0x%llx at point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
+    if (bits) { fastf_res_err("%s: device error bits 0x%llx at point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
     counters[0] = N; counters[1] = S->buf.h_small.u64[SM_CNT + 1]; counters[2] = S->buf.h_small.u64[SM_CNT + 2];
     const uint64_t nnz = *nnz_out = S->buf.h_small.u64[SM_NNZ];
-    if (nnz > N) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N); return RES_FAIL; }
+    if (nnz > N) { fastf_res_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N); return RES_FAIL; }
     /* the rows, concatenated on the device, and their per-cell summary */
     if (fastf_dev_rows_gather(e, sm + SM_KEYS, d.f, d.c, d.k, NULL) ||
         fastf_dev_cell_summary(e, nnz ? d.c : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_cells, S->buf.upc.u64, S->buf.gpc.u32, NULL) ||
@@ -393,7 +374,7 @@ int fastf_res_level_room(res_rate_t *S)
     const size_t room_cells = (S->cfg.max_cells > S->n_cells ? S->cfg.max_cells : S->n_cells) + (size_t)1;
     const size_t bytes = res_level_layout(NULL, room_cells).bytes;
     if (res_block_room(&S->buf.level, RES_DEV, bytes, room_cells, S->device))
-        return rs_err("%s: the search state of cell rate %.3f does not fit: %zu bytes (%s)", S->verb, (double)S->rate_cell, bytes, fastf_last_error());
+        return fastf_res_err("%s: the search state of cell rate %.3f does not fit: %zu bytes (%s)", S->verb, (double)S->rate_cell, bytes, fastf_last_error());
     S->lv = res_level_layout(S->buf.level.p, S->buf.level.n);
     return 0;
 }
@@ -408,8 +389,8 @@ static int level_result_(res_rate_t *S, const char *point_name, int *held, uint6
     *held = 0;
     if (bits & 4) return RES_NOT_COVERED;                   /* UMIs longer than the key holds: as in fastf_res_point_run */
     if (bits == FASTF_ERR_RUN_TOO_LONG && r[3]) { *held = 1; return RES_OK; }
-    if (bits || r[3]) { rs_err("%s: device error bits 0x%llx in the search of point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
-    if (S->buf.h_small.u64[SM_NNZ] > S->R->n) { rs_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)S->buf.h_small.u64[SM_NNZ], (unsigned long long)S->R->n); return RES_FAIL; }
+    if (bits || r[3]) { fastf_res_err("%s: device error bits 0x%llx in the search of point %s", S->verb, (unsigned long long)bits, point_name); return RES_FAIL; }
+    if (S->buf.h_small.u64[SM_NNZ] > S->R->n) { fastf_res_err("internal error: %llu matrix rows out of %llu records", (unsigned long long)S->buf.h_small.u64[SM_NNZ], (unsigned long long)S->R->n); return RES_FAIL; }
     *open_out = r[0];
     if (capped_out) *capped_out = r[1];
     return RES_OK;
@@ -422,7 +403,7 @@ int fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *po
     uint64_t *const sm = S->buf.small.u64;
     const res_rows_t d = res_rows_point(S);
     const double t0 = fastf_res_now();
-    if (!S->buf.level.p) { rs_err("internal error: no search state at point %s", point_name); return RES_FAIL; }
+    if (!S->buf.level.p) { fastf_res_err("internal error: no search state at point %s", point_name); return RES_FAIL; }
     uint64_t *src = NULL, *other = NULL;
     if (point_sort_reduce_(S, d_plane, &src, &other)) return RES_FAIL;
     S->sorted = NULL; S->sorted_full = 0;                   /* (a search pass leaves no keys for --cells: the point's own run does) */
@@ -438,7 +419,7 @@ int fastf_res_search_pass(res_rate_t *S, const uint32_t *d_plane, const char *po
         const int rc = level_result_(S, point_name, &held, open_out, first ? capped_out : NULL);
         if (rc != RES_OK) return rc;
         if (!held) break;
-        if (again) { rs_err("%s: device error bits 0x%llx after the full sort in the search of point %s", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG, point_name); return RES_FAIL; }
+        if (again) { fastf_res_err("%s: device error bits 0x%llx after the full sort in the search of point %s", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG, point_name); return RES_FAIL; }
         if (point_full_again_(S, &src, &other)) return RES_FAIL;
     }
     if (first && fastf_devmem_copy(S->lv.ufull, S->buf.upc.p, ((size_t)S->n_cells + 1) * 8)) return RES_FAIL;
@@ -451,12 +432,12 @@ int fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, ui
     uint64_t *const sm = S->buf.small.u64;
     const double t0 = fastf_res_now();
     int held = 0;
-    if (!S->buf.level.p) { rs_err("internal error: no search state"); return RES_FAIL; }
+    if (!S->buf.level.p) { fastf_res_err("internal error: no search state"); return RES_FAIL; }
     if (fastf_devmem_zero(S->buf.small.p, SM_HITS * 8) ||       /* (the counters of the point before: their error word is read again) */
         fastf_dev_level_init(S->e, S->lv.ufull, S->n_cells, umi_cap, S->lv.lo, S->lv.hi, S->lv.probe, sm + SM_LEVEL, NULL, NULL)) return RES_FAIL;
     const int rc = level_result_(S, "(the state of a cap)", &held, open_out, capped_out);
     if (rc != RES_OK) return rc;
-    if (held) { rs_err("%s: device error bits 0x%llx before a search", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG); return RES_FAIL; }
+    if (held) { fastf_res_err("%s: device error bits 0x%llx before a search", S->verb, (unsigned long long)FASTF_ERR_RUN_TOO_LONG); return RES_FAIL; }
     T->search += fastf_res_now() - t0;
     return RES_OK;
 }
@@ -467,7 +448,7 @@ int fastf_res_point_write(res_rate_t *S, const char *dir, const char *bam_label,
     double tt = fastf_res_now();
     if (nnz > S->buf.h_rows.n) {                            /* (more than there is room for: the need below is beyond what is held) */
         const size_t room = nnz + nnz / 8 + 1024;
-        if (res_block_room(&S->buf.h_rows, RES_PIN, room * 12, room, S->device)) return rs_err("%s: no pinned memory for %llu matrix rows", S->verb, (unsigned long long)nnz);
+        if (res_block_room(&S->buf.h_rows, RES_PIN, room * 12, room, S->device)) return fastf_res_err("%s: no pinned memory for %llu matrix rows", S->verb, (unsigned long long)nnz);
     }
     uint32_t *const h_rows = S->buf.h_rows.u32; const uint64_t cap = S->buf.h_rows.n;
     fastf_coo_t coo = { h_rows, h_rows + cap, h_rows + 2 * cap, (size_t)nnz };
@@ -493,11 +474,11 @@ static int nbr_sets(res_rate_t *S, const uint32_t *r_f, const uint32_t *r_c, con
     fastf_neighbors_pad(S->n_cells, S->hvg_k, &n_pad, &K_pad);
     const size_t need = (size_t)P * n_pad * K_pad;
     if (res_room(&S->buf.nplanes, RES_DEV, need ? need : 1, S->device))
-        return rs_err("%s: --neighbors: %u planes of %u cells x %u genes do not fit: %zu bytes (%s)", S->verb, P, n_pad, K_pad, need, fastf_last_error_copy());
+        return fastf_res_err("%s: --neighbors: %u planes of %u cells x %u genes do not fit: %zu bytes (%s)", S->verb, P, n_pad, K_pad, need, fastf_last_error_copy());
     if (fastf_dev_neighbor_planes(S->e, r_f, r_c, r_k, d_nnz, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, S->buf.nplanes.p, S->buf.nplanes.have, &P, NULL) ||
         fastf_dev_neighbors(S->e, S->buf.nplanes.p, P, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->d_nbr.idx[point], S->d_nbr.cnt[point],
                             S->d_nbr.norms, &max_norm, NULL) || fastf_devmem_sync())
-        return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+        return fastf_res_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
     S->nbr_planes = P;
     return 0;
 }
@@ -512,7 +493,7 @@ int fastf_res_point_neighbors(res_rate_t *S, const char *point_name, res_times_t
     const double tt = fastf_res_now();
     /* (a point's counts are at most the full ones: P of the point never exceeds P of the pair) */
     if (fastf_dev_neighbor_planes(S->e, nnz ? d.f : NULL, d.c, d.k, sm + SM_NNZ, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
-        return rs_err("%s: --neighbors at point %s: %s", S->verb, point_name, fastf_last_error_copy());
+        return fastf_res_err("%s: --neighbors at point %s: %s", S->verb, point_name, fastf_last_error_copy());
     if (nbr_sets(S, nnz ? d.f : NULL, d.c, d.k, sm + SM_NNZ, P, 1)) return 1;
     if (fastf_dev_neighbors_shared(S->e, S->d_nbr.idx[0], S->d_nbr.cnt[0], S->d_nbr.idx[1], S->d_nbr.cnt[1], S->n_cells, FASTF_NEIGHBORS_K, S->d_nbr.shared, NULL) || fastf_devmem_sync()) return 1;
     if (S->n_cells && (fastf_devmem_copy(S->h_nbr.kp, S->d_nbr.cnt[1], (size_t)S->n_cells * 4) || fastf_devmem_copy(S->h_nbr.sh, S->d_nbr.shared, (size_t)S->n_cells * 4))) return 1;
@@ -525,7 +506,7 @@ static int lab_votes(res_rate_t *S, int point)
 {
     if (fastf_dev_label_votes(S->e, S->d_nbr.idx[point], S->d_nbr.cnt[point], S->d_lab.lab, S->n_cells, FASTF_NEIGHBORS_K, S->n_labels,
                               S->d_lab.half[point].pred, S->d_lab.half[point].same, S->d_lab.half[point].labelled, S->d_lab.half[point].conf, NULL) || fastf_devmem_sync())
-        return rs_err("%s: --labels at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+        return fastf_res_err("%s: --labels at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
     return fastf_devmem_copy(S->h_lab.half[point].pred, S->d_lab.half[point].pred, S->d_lab.half_bytes);
 }
 
@@ -546,7 +527,7 @@ static int mk_tables(res_rate_t *S, int point)
     const res_mk_v dm = res_mk_layout(S->buf.mk.p, S->n_labels, S->hvg_k), hm = res_mk_host(S, point);
     if (fastf_dev_marker_auc(S->e, S->buf.nplanes.p, S->nbr_planes, S->n_cells, S->hvg_k, S->d_lab.lab, S->n_labels, dm.s2u, dm.det, dm.sum, dm.npl, NULL) ||
         fastf_devmem_sync())
-        return rs_err("%s: --markers at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+        return fastf_res_err("%s: --markers at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
     if (fastf_devmem_copy(hm.s2u, dm.s2u, dm.bytes)) return 1;
     return fastf_marker_rank(hm.s2u, hm.npl, S->h_nbr.genes, S->hvg_k, S->n_labels, S->buf.mk_rank.u32 + (size_t)point * S->n_labels * FASTF_HVG_TOP);
 }
@@ -563,7 +544,7 @@ int fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *
 
 /* where the full-depth work of a pair is booked: under the first flag that is on, in the order fidelity, gene fidelity, neighbours;
  * per_gene: the per-gene sums of the pair, which --fidelity has no part in */
-static double *full_timer(const res_rate_t *S, res_times_t *T, int per_gene)
+double *fastf_res_full_timer(const res_rate_t *S, res_times_t *T, int per_gene)
 {
     return S->cfg.fidelity && !per_gene ? &T->fidelity : S->cfg.gene_fid ? &T->gene_fid : &T->neighbors;
 }
@@ -575,7 +556,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
     uint64_t *const sm = S->buf.small.u64;
     const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
     double tt = fastf_res_now();
-    if (nnz > N) return rs_err("internal error: %llu full-depth rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N);
+    if (nnz > N) return fastf_res_err("internal error: %llu full-depth rows out of %llu records", (unsigned long long)nnz, (unsigned long long)N);
     if (fastf_devmem_copy(x.f, d.f, (size_t)nnz * 4) || fastf_devmem_copy(x.c, d.c, (size_t)nnz * 4) || fastf_devmem_copy(x.k, d.k, (size_t)nnz * 4) ||
         fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
     S->full_nnz = nnz;
@@ -587,14 +568,14 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
             fastf_devmem_sync()) return 1;
         if (S->n_features && (fastf_devmem_copy(S->h_gfid.sx, g_sx, (size_t)S->n_features * 8) || fastf_devmem_copy(S->h_gfid.sxx, g_sxx, (size_t)S->n_features * 8) ||
                               fastf_devmem_copy(S->h_gfid.cf, g_cf, (size_t)S->n_features * 4))) return 1;
-        *full_timer(S, T, 1) += fastf_res_now() - tt; tt = fastf_res_now();
+        *fastf_res_full_timer(S, T, 1) += fastf_res_now() - tt; tt = fastf_res_now();
     }
     if (S->cfg.neighbors) {                                     /* A of the pair, its slot map, the planes of the full rows and their neighbour sets, which stay */
         uint32_t P = 0;
         S->hvg_k = fastf_hvg_rank(S->n_cells, S->h_gfid.sx, S->h_gfid.sxx, S->n_features, S->h_nbr.genes, NULL);
         if (fastf_neighbors_slot_map(S->h_nbr.genes, S->hvg_k, S->n_features, S->h_nbr.map) || fastf_devmem_copy(S->d_nbr.map, S->h_nbr.map, S->nbr_map_bytes)) return 1;
         if (fastf_dev_neighbor_planes(S->e, nnz ? x.f : NULL, x.c, x.k, sm + SM_FULL, S->d_nbr.map, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
-            return rs_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
+            return fastf_res_err("%s: --neighbors at cell rate %.3f, seed %u: %s", S->verb, (double)S->rate_cell, S->seed, fastf_last_error_copy());
         if (nbr_sets(S, nnz ? x.f : NULL, x.c, x.k, sm + SM_FULL, P, 0)) return 1;
         if (S->n_cells && fastf_devmem_copy(S->h_nbr.kf, S->d_nbr.cnt[0], (size_t)S->n_cells * 4)) return 1;
         T->neighbors += fastf_res_now() - tt; tt = fastf_res_now();
@@ -628,7 +609,7 @@ int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
     const int prc = fastf_res_point_run(S, d_plane, name, counters, &nnz, T);
     if (prc != RES_OK) return prc;
     *T = before;                                            /* (the stages of this point are the flag's own) */
-    *full_timer(S, T, 0) += fastf_res_now() - tt;
+    *fastf_res_full_timer(S, T, 0) += fastf_res_now() - tt;
     return fastf_res_full_keep(S, T) ? RES_FAIL : RES_OK;
 }
 
@@ -640,7 +621,7 @@ int fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t 
     const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
     const double tt = fastf_res_now();
     if (fastf_dev_fidelity(S->e, x.f, x.c, x.k, sm + SM_FULL, nnz ? d.f : NULL, nnz ? d.c : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_cells, S->d_fid.sxy, S->d_fid.syy, NULL, NULL))
-        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
+        return fastf_res_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
     if (fastf_devmem_copy(S->h_fid.sxy, S->d_fid.sxy, (size_t)S->n_cells * 8) || fastf_devmem_copy(S->h_fid.syy, S->d_fid.syy, (size_t)S->n_cells * 8)) return 1;
     T->fidelity += fastf_res_now() - tt;
     return 0;
@@ -656,7 +637,7 @@ int fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_tim
     uint32_t *const g_c = S->d_gfid.c, *const d_x = S->buf.gx.u32;
     const double tt = fastf_res_now();
     if (fastf_dev_partner_counts(S->e, x.f, x.c, x.k, sm + SM_FULL, nnz ? d.f : NULL, nnz ? d.c : NULL, sm + SM_NNZ, d_x, NULL, NULL))
-        return rs_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
+        return fastf_res_err("%s: point %s against the full-depth rows of its cell rate and seed: %s", S->verb, point_name, fastf_last_error_copy());
     /* (with --genes fastf_res_point_run has left the point's sum_y and cells in S->buf.h_upg and S->buf.h_cpg) */
     if ((!S->genes && fastf_dev_gene_summary(S->e, nnz ? d.f : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_features, g_c, g_sy, NULL)) ||
         fastf_dev_gene_moments(S->e, nnz ? d.f : NULL, nnz ? d_x : NULL, nnz ? d.k : NULL, sm + SM_NNZ, S->n_features, g_sxy, g_syy, NULL) ||
@@ -685,7 +666,7 @@ int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
     fastf_engine_t *e = S->e;
     uint64_t *const sm = S->buf.small.u64;
     double tt = fastf_res_now();
-    if (!S->sorted) return rs_err("internal error: no sorted keys at point %s", point_name);
+    if (!S->sorted) return fastf_res_err("internal error: no sorted keys at point %s", point_name);
     uint64_t *src = S->sorted;
     if (!S->sorted_full) {                                  /* (every key is still there, sorted but for its low bits) */
         int in_other = 0;
@@ -699,433 +680,10 @@ int fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T)
     if (fastf_dev_umi_rows(e, src, sm + SM_KEYS, N, d_uk, d_nc, sm + SM_UROWS, NULL) ||
         fastf_dev_copy_summary(e, d_uk, d_nc, sm + SM_UROWS, S->n_cells, cs.rpc, cs.npc, cs.spc, cs.hist, NULL) ||
         fastf_dev_error_bits(e, &bits)) return 1;
-    if (bits) return rs_err("%s: device error bits 0x%llx in the per-cell stage of point %s", S->verb, (unsigned long long)bits, point_name);
+    if (bits) return fastf_res_err("%s: device error bits 0x%llx in the per-cell stage of point %s", S->verb, (unsigned long long)bits, point_name);
     if (fastf_devmem_copy(S->h_cs.hist, cs.hist, cs.bytes)) return 1;
     T->cells_dev += fastf_res_now() - tt;
     return 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* the summary table, the command line                                 */
-/* ------------------------------------------------------------------ */
-int fastf_res_tsv_open(res_tsv_t *t, const char *out_dir, const char *name, const char *header)
-{
-    snprintf(t->final, sizeof t->final, "%s/%s", out_dir, name);
-    snprintf(t->tmp, sizeof t->tmp, "%s/%s.partial", out_dir, name);
-    if (!(t->f = fopen(t->tmp, "w"))) return rs_err("cannot open %s: %s", t->tmp, strerror(errno));
-    fputs(header, t->f);
-    return 0;
-}
-int fastf_res_tsv_close(res_tsv_t *t, int ok)
-{
-    if (!t->f) return 0;
-    const int bad = ferror(t->f) | (fclose(t->f) != 0);
-    t->f = NULL;
-    if (ok && !bad && rename(t->tmp, t->final) == 0) return 0;
-    unlink(t->tmp);
-    return ok ? rs_err("cannot write %s", t->final) : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --genes: the table, the grid file, a point's file                   */
-/* ------------------------------------------------------------------ */
-static void genes_release(res_genes_t *G)
-{
-    if (G->feat_id) for (uint32_t i = 0; i < G->n_features; i++) free(G->feat_id[i]);
-    free(G->feat_id); free(G->cells); free(G->names);
-    G->feat_id = NULL; G->cells = NULL; G->names = NULL; G->n_features = G->n_points = 0;
-}
-
-int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points, int no_grid)
-{
-    memset(G, 0, sizeof *G);
-    if (!on) return 0;
-    G->verb = verb; G->max_points = no_grid ? 0 : max_points; G->no_grid = no_grid;
-    snprintf(G->out_dir, sizeof G->out_dir, "%s", out_dir);
-    char name[64];
-    snprintf(name, sizeof name, "%s_genes.tsv", verb);
-    if (!(G->names = calloc(G->max_points ? G->max_points : 1, sizeof *G->names))) return rs_err("out of memory");
-    if (fastf_res_tsv_open(&G->tsv, out_dir, name, header)) { genes_release(G); return 1; }
-    G->on = 1;
-    return 0;
-}
-
-/* text of n lines `id \t a[i] [\t b[i]]` */
-typedef struct { char *p; size_t len, cap; } gtext;
-static int gt_room(gtext *t, size_t more)
-{
-    if (t->len + more <= t->cap) return 0;
-    size_t cap = t->cap ? t->cap : ((size_t)1 << 16);
-    while (cap < t->len + more) cap *= 2;
-    char *np = (char *)realloc(t->p, cap);
-    if (!np) return rs_err("out of memory");
-    t->p = np; t->cap = cap;
-    return 0;
-}
-static int gt_str(gtext *t, const char *s) { const size_t n = strlen(s); if (gt_room(t, n)) return 1; memcpy(t->p + t->len, s, n); t->len += n; return 0; }
-static int gt_u64(gtext *t, char lead, uint64_t v)
-{
-    if (gt_room(t, 24)) return 1;
-    t->len += (size_t)snprintf(t->p + t->len, 24, "%c%llu", lead, (unsigned long long)v);
-    return 0;
-}
-/* a finished text through <path>.partial */
-static int gz_text_renamed(const char *path, const gtext *t)
-{
-    char tmp[4200];
-    snprintf(tmp, sizeof tmp, "%s.partial", path);
-    if (fastf_write_gz_text(tmp, t->p ? t->p : "", t->len) || rename(tmp, path) != 0) { unlink(tmp); return rs_err("cannot write %s", path); }
-    return 0;
-}
-
-int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *point_name, const char *dir, const char *row,
-                          const uint32_t *cells, const uint64_t *umis)
-{
-    if (!G->on) return 0;
-    if (!G->feat_id) {                                      /* the first point: the names and the room of the grid file */
-        const uint32_t nf = (uint32_t)L->n_features;
-        if (!(G->feat_id = (char **)calloc(nf ? nf : 1, sizeof *G->feat_id)) ||
-            !(G->cells = (uint32_t *)malloc(((size_t)G->max_points * nf + 1) * sizeof *G->cells))) return rs_err("out of memory");
-        for (uint32_t i = 0; i < nf; i++) { if (!(G->feat_id[i] = strdup(L->feat_id[i]))) return rs_err("out of memory"); G->n_features = i + 1; }
-    }
-    if ((uint32_t)L->n_features != G->n_features) return rs_err("internal error: the feature list changed between points");
-    const uint32_t nf = G->n_features;
-    if (!G->no_grid) {
-        if (G->n_points >= G->max_points) return rs_err("internal error: more points than the grid has");
-        snprintf(G->names[G->n_points], sizeof G->names[0], "%s", point_name);
-        if (nf) memcpy(G->cells + (size_t)G->n_points * nf, cells, (size_t)nf * sizeof *cells);
-        G->n_points++;
-    }
-    if (dir) {
-        char path[4200];
-        gtext t = { NULL, 0, 0 };
-        int bad = 0;
-        for (uint32_t i = 0; i < nf && !bad; i++)
-            bad = gt_str(&t, G->feat_id[i]) || gt_u64(&t, '\t', cells[i]) || gt_u64(&t, '\t', umis[i]) || gt_str(&t, "\n");
-        snprintf(path, sizeof path, "%s/genes.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-        if (bad) return 1;
-    }
-    fputs(row, G->tsv.f);
-    return 0;
-}
-
-/* ok: the grid file, then the table; otherwise nothing of either is left */
-int fastf_res_genes_close(res_genes_t *G, int ok)
-{
-    if (!G->on) return 0;
-    int rc = 0;
-    if (ok && !G->no_grid) {
-        char path[4200];
-        gtext t = { NULL, 0, 0 };
-        int bad = gt_str(&t, "feature");
-        for (uint32_t p = 0; p < G->n_points && !bad; p++) bad = gt_str(&t, "\t") || gt_str(&t, G->names[p]);
-        if (!bad) bad = gt_str(&t, "\n");
-        for (uint32_t i = 0; i < G->n_features && !bad; i++) {
-            bad = gt_str(&t, G->feat_id[i]);
-            for (uint32_t p = 0; p < G->n_points && !bad; p++) bad = gt_u64(&t, '\t', G->cells[(size_t)p * G->n_features + i]);
-            if (!bad) bad = gt_str(&t, "\n");
-        }
-        snprintf(path, sizeof path, "%s/%s_gene_cells.tsv.gz", G->out_dir, G->verb);
-        if (!bad) bad = gz_text_renamed(path, &t);
-        free(t.p);
-        rc = bad;
-    }
-    char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
-    if (fastf_res_tsv_close(&G->tsv, ok && !rc)) rc = 1; else if (rc) fastf_set_error_(keep);
-    genes_release(G);
-    G->on = 0;
-    return rc;
-}
-
-/* ------------------------------------------------------------------ */
-/* --cells: the table, a point's file                                  */
-/* ------------------------------------------------------------------ */
-int fastf_res_cells_open(res_cells_t *C, int on, const char *verb, const char *out_dir, const char *header)
-{
-    memset(C, 0, sizeof *C);
-    if (!on) return 0;
-    char name[64];
-    snprintf(name, sizeof name, "%s_cells.tsv", verb);
-    C->verb = verb;
-    if (fastf_res_tsv_open(&C->tsv, out_dir, name, header)) return 1;
-    C->on = 1;
-    return 0;
-}
-
-int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row)
-{
-    if (!C->on) return 0;
-    if (dir) {
-        char path[4200];
-        gtext t = { NULL, 0, 0 };
-        int bad = gt_str(&t, "barcode\treads\tnull_umi_reads\tumis\tgenes\tsingleton_umis\tsaturation\n");
-        for (uint32_t k = 0; k < S->n_cells && !bad; k++) {
-            const uint64_t reads = S->h_cs.rpc[k], umis = S->buf.h_upc.u64[k];
-            char sat[32];
-            snprintf(sat, sizeof sat, "\t%.6f\n", reads ? 1.0 - (double)umis / (double)reads : 0.0);
-            bad = gt_str(&t, S->L->barcode[k]) || gt_u64(&t, '\t', reads) || gt_u64(&t, '\t', S->h_cs.npc[k]) || gt_u64(&t, '\t', umis) ||
-                  gt_u64(&t, '\t', S->buf.h_gpc.u32[k]) || gt_u64(&t, '\t', S->h_cs.spc[k]) || gt_str(&t, sat);
-        }
-        snprintf(path, sizeof path, "%s/cells.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-        if (bad) return 1;
-    }
-    fputs(row, C->tsv.f);
-    return 0;
-}
-
-int fastf_res_cells_close(res_cells_t *C, int ok)
-{
-    if (!C->on) return 0;
-    C->on = 0;
-    return fastf_res_tsv_close(&C->tsv, ok);
-}
-
-/* ------------------------------------------------------------------ */
-/* --fidelity: the table, a point's file                               */
-/* ------------------------------------------------------------------ */
-int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, const char *out_dir, const char *header, const char *gene_header)
-{
-    memset(F, 0, sizeof *F);
-    if (!on && !gene_on) return 0;
-    char name[64];
-    F->verb = verb;
-    if (on) {
-        snprintf(name, sizeof name, "%s_fidelity.tsv", verb);
-        if (fastf_res_tsv_open(&F->tsv, out_dir, name, header)) return 1;
-    }
-    if (gene_on) {
-        snprintf(name, sizeof name, "%s_gene_fidelity.tsv", verb);
-        if (fastf_res_tsv_open(&F->gtsv, out_dir, name, gene_header)) { fastf_res_tsv_close(&F->tsv, 0); return 1; }
-    }
-    F->on = on; F->gene_on = gene_on; F->full = 1;
-    return 0;
-}
-
-/* --gene-fidelity: the row of the point and — dir != NULL — its gene_fidelity.tsv.gz */
-static int gene_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
-{
-    char row[640];
-    if (fastf_gene_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->h_gfid.sx, S->h_gfid.sy, S->h_gfid.sxx, S->h_gfid.syy, S->h_gfid.sxy,
-                                        S->n_features, row, sizeof row)) return 1;
-    if (dir) {
-        char path[4200], line[640];
-        gtext t = { NULL, 0, 0 };
-        int bad = gt_str(&t, fastf_gene_fidelity_header());
-        for (uint32_t g = 0; g < S->n_features && !bad; g++)
-            bad = fastf_gene_fidelity_row(S->L->feat_id[g], S->n_cells, S->h_gfid.sx[g], S->h_gfid.sy[g], S->h_gfid.cf[g], S->h_gfid.c[g], S->h_gfid.sxx[g], S->h_gfid.syy[g],
-                                          S->h_gfid.sxy[g], line, sizeof line) || gt_str(&t, line);
-        snprintf(path, sizeof path, "%s/gene_fidelity.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-        if (bad) return 1;
-    }
-    fputs(row, F->gtsv.f);
-    return 0;
-}
-
-int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header)
-{
-    if (!on) return 0;
-    char name[64];
-    snprintf(name, sizeof name, "%s_neighbors.tsv", verb);
-    F->verb = verb;
-    if (fastf_res_tsv_open(&F->ntsv, out_dir, name, header)) return 1;
-    F->nbr_on = F->full = 1;
-    return 0;
-}
-
-int fastf_res_fid_open_labels(res_fid_t *F, const fastf_labels_t *labels, const char *verb, const char *out_dir, const char *header, const char *classes_header)
-{
-    if (!labels) return 0;
-    char name[64];
-    F->verb = verb;
-    snprintf(name, sizeof name, "%s_labels.tsv", verb);
-    if (fastf_res_tsv_open(&F->ltsv, out_dir, name, header)) return 1;
-    F->lab_on = 1;                                          /* (from here fastf_res_fid_close takes the table back) */
-    snprintf(name, sizeof name, "%s_label_classes.tsv", verb);
-    if (fastf_res_tsv_open(&F->ctsv, out_dir, name, classes_header)) return 1;
-    F->labels = labels; F->full = 1;
-    return 0;
-}
-
-int fastf_res_fid_open_markers(res_fid_t *F, uint32_t markers, const char *verb, const char *out_dir, const char *header)
-{
-    if (!markers) return 0;
-    char name[64];
-    F->verb = verb;
-    snprintf(name, sizeof name, "%s_markers.tsv", verb);
-    if (fastf_res_tsv_open(&F->mtsv, out_dir, name, header)) return 1;
-    F->mk_on = 1; F->markers = markers;
-    return 0;
-}
-
-/* --markers: the rows of the point and — dir != NULL — its markers.tsv.gz: per label the genes in the top N_eff of the full rows or of
- * the point, in the order of their full ranks */
-static int mk_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
-{
-    const uint32_t L = S->n_labels, K = S->hvg_k, top = F->markers < K ? F->markers : K;
-    const res_mk_v mf = res_mk_host(S, 0), mp = res_mk_host(S, 1);
-    const uint32_t *const npl = mf.npl, *const rf = res_mk_rank(S, 0), *const rp = res_mk_rank(S, 1);
-    const uint32_t *const df = mf.det, *const dp = mp.det;
-    const size_t rows_cap = ((size_t)L + 1) * (FASTF_LABEL_BYTES + 160);
-    char *const rows = (char *)malloc(rows_cap);
-    const char **const names = (const char **)malloc(((size_t)L + 1) * sizeof *names);
-    uint32_t *const by_rank = (uint32_t *)malloc(((size_t)K + 1) * sizeof *by_rank), *const det_all = (uint32_t *)calloc(2 * (size_t)K + 1, sizeof *det_all);
-    int bad = !rows || !names || !by_rank || !det_all;
-    if (bad) rs_err("out of memory");
-    for (uint32_t l = 0; l <= L && !bad; l++) names[l] = fastf_labels_name(F->labels, l);
-    if (!bad) bad = fastf_markers_summary_rows(S->rate_cell, rate_depth, list_value, S->seed, names, L, K, F->markers, npl, rf, rp, mf.s2u, mp.s2u, rows, rows_cap);
-    if (dir && !bad) {
-        char path[4200], line[512];
-        gtext t = { NULL, 0, 0 };
-        uint64_t n_lab = 0;
-        for (uint32_t a = 0; a < L; a++) { n_lab += npl[a]; for (uint32_t g = 0; g < K; g++) { det_all[g] += df[(size_t)a * K + g]; det_all[K + g] += dp[(size_t)a * K + g]; } }
-        bad = gt_str(&t, fastf_markers_header());
-        for (uint32_t a = 0; a < L && !bad; a++) {
-            const size_t at = (size_t)a * K;
-            const uint32_t n_in = npl[a], n_out = (uint32_t)(n_lab - n_in);
-            if (!n_in || !n_out) { bad = fastf_markers_row(names[a + 1], NULL, n_in, n_out, 0, 0, 0, 0, 0, 0, 0, 0, 0, line, sizeof line) || gt_str(&t, line); continue; }
-            for (uint32_t g = 0; g < K; g++) by_rank[rf[at + g] - 1] = g;
-            for (uint32_t r = 0; r < K && !bad; r++) {
-                const uint32_t g = by_rank[r];
-                if (r >= top && rp[at + g] > top) continue;
-                bad = fastf_markers_row(names[a + 1], S->L->feat_id[S->h_nbr.genes[g]], n_in, n_out, rf[at + g], rp[at + g], mf.s2u[at + g], mp.s2u[at + g],
-                                        df[at + g], det_all[g] - df[at + g], dp[at + g], det_all[K + g] - dp[at + g], mp.sum[at + g], line, sizeof line) || gt_str(&t, line);
-            }
-        }
-        snprintf(path, sizeof path, "%s/markers.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-    }
-    if (!bad) fputs(rows, F->mtsv.f);
-    free(rows); free(names); free(by_rank); free(det_all);
-    return bad;
-}
-
-/* --labels: the rows of the point and — dir != NULL — its labels.tsv.gz and label_confusion.tsv.gz */
-static int lab_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
-{
-    const uint32_t L = S->n_labels;
-    const uint8_t *const lab = S->h_lab.lab, *const pf = S->h_lab.half[0].pred, *const pp = S->h_lab.half[1].pred;
-    const uint32_t *const cx = S->h_lab.half[0].conf, *const cy = S->h_lab.half[1].conf;
-    char row[640];
-    if (fastf_labels_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, FASTF_NEIGHBORS_K, L, lab, pf, pp, S->h_lab.half[0].same,
-                                 S->h_lab.half[0].labelled, S->h_lab.half[1].same, S->h_lab.half[1].labelled, cx, cy, row, sizeof row)) return 1;
-    if (dir) {
-        char path[4200], line[512];
-        const size_t wide = 64 + (size_t)(L + 1) * FASTF_LABEL_BYTES;
-        char *const wl = (char *)malloc(wide);
-        const char **const names = (const char **)malloc(((size_t)L + 1) * sizeof *names);
-        uint32_t *const cells = (uint32_t *)calloc((size_t)L + 1, sizeof *cells);
-        gtext t = { NULL, 0, 0 }, u = { NULL, 0, 0 };
-        int bad = !wl || !names || !cells;
-        if (bad) rs_err("out of memory");
-        for (uint32_t l = 0; l <= L && !bad; l++) names[l] = fastf_labels_name(F->labels, l);
-        if (!bad) bad = gt_str(&t, fastf_labels_header());
-        for (uint32_t c = 0; c < S->n_cells && !bad; c++) {
-            cells[lab[c]]++;
-            bad = fastf_labels_row(S->L->barcode[c], names[lab[c]], names[pf[c]], names[pp[c]], S->h_lab.half[0].same[c], S->h_lab.half[0].labelled[c],
-                                   S->h_lab.half[1].same[c], S->h_lab.half[1].labelled[c], line, sizeof line) || gt_str(&t, line);
-        }
-        snprintf(path, sizeof path, "%s/labels.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        if (!bad) bad = fastf_label_confusion_header(names, L, wl, wide) || gt_str(&u, wl);
-        for (uint32_t a = 1; a <= L && !bad; a++)
-            bad = fastf_label_confusion_row(names[a], cells[a], cy + (size_t)(a - 1) * (L + 1), L, wl, wide) || gt_str(&u, wl);
-        snprintf(path, sizeof path, "%s/label_confusion.tsv.gz", dir);
-        if (!bad) bad = gz_text_renamed(path, &u);
-        free(t.p); free(u.p); free(wl); free(names); free(cells);
-        if (bad) return 1;
-    }
-    fputs(row, F->ltsv.f);
-    for (uint32_t a = 1; a <= L; a++) {
-        if (fastf_label_classes_row(S->rate_cell, rate_depth, list_value, S->seed, fastf_labels_name(F->labels, a), a, S->n_cells, L, lab, cx, cy, row, sizeof row)) return 1;
-        fputs(row, F->ctsv.f);
-    }
-    return 0;
-}
-
-/* --neighbors: the row of the point and — dir != NULL — its neighbors.tsv.gz */
-static int nbr_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
-{
-    char row[640];
-    if (fastf_neighbors_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_NEIGHBORS_K, S->h_nbr.kf, S->h_nbr.kp, S->h_nbr.sh, row, sizeof row)) return 1;
-    if (dir) {
-        char path[4200], line[512];
-        gtext t = { NULL, 0, 0 };
-        int bad = gt_str(&t, fastf_neighbors_header());
-        for (uint32_t c = 0; c < S->n_cells && !bad; c++)
-            bad = fastf_neighbors_row(S->L->barcode[c], S->h_nbr.kf[c], S->h_nbr.kp[c], S->h_nbr.sh[c], line, sizeof line) || gt_str(&t, line);
-        snprintf(path, sizeof path, "%s/neighbors.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-        if (bad) return 1;
-    }
-    fputs(row, F->ntsv.f);
-    return 0;
-}
-
-int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T)
-{
-    if (F->nbr_on) {
-        const double tt = fastf_res_now();
-        if (nbr_point(F, S, dir, rate_depth, list_value)) return 1;
-        T->neighbors += fastf_res_now() - tt;
-    }
-    if (F->lab_on) {
-        const double tt = fastf_res_now();
-        if (lab_point(F, S, dir, rate_depth, list_value)) return 1;
-        T->labels += fastf_res_now() - tt;
-    }
-    if (F->mk_on) {
-        const double tt = fastf_res_now();
-        if (mk_point(F, S, dir, rate_depth, list_value)) return 1;
-        T->markers += fastf_res_now() - tt;
-    }
-    if (F->gene_on) {
-        const double tt = fastf_res_now();
-        if (gene_fid_point(F, S, dir, rate_depth, list_value)) return 1;
-        T->gene_fid += fastf_res_now() - tt;
-    }
-    if (!F->on) return 0;
-    const double tt = fastf_res_now();
-    char row[640];
-    if (fastf_fidelity_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->h_fid.ufull, S->buf.h_upc.u64, S->h_fid.gfull, S->buf.h_gpc.u32, S->h_fid.sxx, S->h_fid.syy, S->h_fid.sxy,
-                                   S->n_cells, S->n_features, row, sizeof row)) return 1;
-    if (dir) {
-        char path[4200], line[512];
-        gtext t = { NULL, 0, 0 };
-        int bad = gt_str(&t, fastf_fidelity_header());
-        for (uint32_t k = 0; k < S->n_cells && !bad; k++)
-            bad = fastf_fidelity_row(S->L->barcode[k], S->h_fid.ufull[k], S->buf.h_upc.u64[k], S->h_fid.gfull[k], S->buf.h_gpc.u32[k], S->h_fid.sxx[k], S->h_fid.syy[k], S->h_fid.sxy[k],
-                                     S->n_features, line, sizeof line) || gt_str(&t, line);
-        snprintf(path, sizeof path, "%s/fidelity.tsv.gz", dir);
-        if (!bad) bad = fastf_res_make_dir(dir) || gz_text_renamed(path, &t);
-        free(t.p);
-        if (bad) return 1;
-    }
-    fputs(row, F->tsv.f);
-    T->fidelity += fastf_res_now() - tt;
-    return 0;
-}
-
-int fastf_res_fid_close(res_fid_t *F, int ok)
-{
-    if (!F->on && !F->gene_on && !F->nbr_on && !F->lab_on && !F->mk_on) return 0;
-    /* the tables are closed before any is renamed, and a rename that fails takes the others back: none is left alone */
-    res_tsv_t *const t[6] = {F->on ? &F->tsv : NULL, F->gene_on ? &F->gtsv : NULL, F->nbr_on ? &F->ntsv : NULL, F->lab_on ? &F->ltsv : NULL,
-                             F->lab_on && F->labels ? &F->ctsv : NULL, F->mk_on ? &F->mtsv : NULL};
-    int bad = 0, renamed = 0;
-    const char *failed = NULL;
-    for (int k = 0; k < 6; k++) if (t[k] && t[k]->f) { if (ferror(t[k]->f) | (fclose(t[k]->f) != 0)) { bad = 1; failed = t[k]->final; } t[k]->f = NULL; }
-    for (int k = 0; k < 6 && ok && !bad; k++) if (t[k]) { if (rename(t[k]->tmp, t[k]->final) == 0) renamed |= 1 << k; else { bad = 1; failed = t[k]->final; } }
-    if (!ok || bad) for (int k = 0; k < 6; k++) if (t[k]) { unlink(t[k]->tmp); if (renamed & (1 << k)) unlink(t[k]->final); }
-    F->on = F->gene_on = F->nbr_on = F->lab_on = F->mk_on = F->full = 0; F->labels = NULL; F->markers = 0;
-    return ok && bad ? rs_err("cannot write %s", failed) : 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1135,23 +693,23 @@ int fastf_parse_seeds(const char *text, uint32_t *out, uint32_t cap, uint32_t *n
 {
     uint32_t n = 0;
     if (n_out) *n_out = 0;
-    if (!text || !out || !n_out) return rs_err("null argument");
+    if (!text || !out || !n_out) return fastf_res_err("null argument");
     if (cap > FASTF_MAX_SEEDS) cap = FASTF_MAX_SEEDS;
     for (const char *p = text;;) {
         const char *q = p;
         while (*q && *q != ',') q++;
         char el[64];
         const size_t len = (size_t)(q - p);
-        if (len == 0) return rs_err("--seeds `%s`: empty element", text);
-        if (len >= sizeof el) return rs_err("--seeds `%s`: element too long", text);
+        if (len == 0) return fastf_res_err("--seeds `%s`: empty element", text);
+        if (len >= sizeof el) return fastf_res_err("--seeds `%s`: element too long", text);
         memcpy(el, p, len); el[len] = '\0';
         char *end = NULL;
         errno = 0;
         const uint32_t v = (uint32_t)(unsigned int)strtol(el, &end, 0);      /* (the rule of -s) */
-        if (errno == ERANGE) return rs_err("--seeds `%s`: numerical result out of range", el);
-        if (end == el || *end) return rs_err("--seeds `%s`: expects an integer value", el);
-        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return rs_err("--seeds `%s`: %u is listed twice", text, v);
-        if (n == cap) return rs_err("--seeds `%s`: more than %u values", text, cap);
+        if (errno == ERANGE) return fastf_res_err("--seeds `%s`: numerical result out of range", el);
+        if (end == el || *end) return fastf_res_err("--seeds `%s`: expects an integer value", el);
+        for (uint32_t j = 0; j < n; j++) if (out[j] == v) return fastf_res_err("--seeds `%s`: %u is listed twice", text, v);
+        if (n == cap) return fastf_res_err("--seeds `%s`: more than %u values", text, cap);
         out[n++] = v;
         if (!*q) break;
         p = q + 1;
@@ -1163,10 +721,10 @@ int fastf_parse_seeds(const char *text, uint32_t *out, uint32_t cap, uint32_t *n
 int fastf_reps_seeds(uint32_t first, uint64_t n_reps, uint32_t *out, uint32_t cap, uint32_t *n_out)
 {
     if (n_out) *n_out = 0;
-    if (!out || !n_out) return rs_err("null argument");
-    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS || n_reps > cap) return rs_err("--reps %llu: expects 1 to %u replicates", (unsigned long long)n_reps, cap < FASTF_MAX_SEEDS ? cap : FASTF_MAX_SEEDS);
+    if (!out || !n_out) return fastf_res_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS || n_reps > cap) return fastf_res_err("--reps %llu: expects 1 to %u replicates", (unsigned long long)n_reps, cap < FASTF_MAX_SEEDS ? cap : FASTF_MAX_SEEDS);
     if ((uint64_t)first + n_reps - 1 > 0xFFFFFFFFull)
-        return rs_err("--reps %llu from seed %u: the seeds would wrap past 4294967295", (unsigned long long)n_reps, first);
+        return fastf_res_err("--reps %llu from seed %u: the seeds would wrap past 4294967295", (unsigned long long)n_reps, first);
     for (uint32_t k = 0; k < (uint32_t)n_reps; k++) out[k] = first + k;
     *n_out = (uint32_t)n_reps;
     return 0;
@@ -1174,21 +732,10 @@ int fastf_reps_seeds(uint32_t first, uint64_t n_reps, uint32_t *out, uint32_t ca
 
 int fastf_reps_point_dir(const char *point_name, uint32_t seed, char *buf, size_t cap)
 {
-    if (!point_name || !buf) return rs_err("null argument");
+    if (!point_name || !buf) return fastf_res_err("null argument");
     const int n = snprintf(buf, cap, "%s_s%u", point_name, seed);
-    return (n < 0 || (size_t)n >= cap) ? rs_err("directory name too long") : 0;
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("directory name too long") : 0;
 }
-
-#define REPS_STAT4(m) "\t" m "_mean\t" m "_sd\t" m "_min\t" m "_max"
-#define REPS_COLUMNS_TAIL "n_reps\tn_cells" REPS_STAT4("sampled_reads") REPS_STAT4("sampled_valid_reads") REPS_STAT4("nnz") REPS_STAT4("umis") \
-    REPS_STAT4("saturation") REPS_STAT4("median_umis_per_cell") REPS_STAT4("median_genes_per_cell") "\n"
-const char *fastf_sweep_reps_header(void) { return "rate_cell\trate_depth\t" REPS_COLUMNS_TAIL; }
-const char *fastf_cap_reps_header(void) { return "rate_cell\treads_per_cell\t" REPS_COLUMNS_TAIL; }
-const char *fastf_level_reps_header(void) { return "rate_cell\tumi_cap\t" REPS_COLUMNS_TAIL; }
-#define GENES_REPS_COLUMNS_TAIL "n_reps" REPS_STAT4("genes_detected") "\tgenes_in_all_reps\tgenes_in_any_rep\n"
-const char *fastf_sweep_genes_reps_header(void) { return "rate_cell\trate_depth\t" GENES_REPS_COLUMNS_TAIL; }
-const char *fastf_cap_genes_reps_header(void) { return "rate_cell\treads_per_cell\t" GENES_REPS_COLUMNS_TAIL; }
-const char *fastf_level_genes_reps_header(void) { return "rate_cell\tumi_cap\t" GENES_REPS_COLUMNS_TAIL; }
 
 /* `\t mean \t sd \t min \t max` of v[0], v[stride], ..: two passes in list order, the sample sd; kind 0: integers, 1: %.6f, 2: %.1f */
 static int reps_stat4(const double *v, uint32_t stride, uint32_t n, int kind, char *buf, size_t cap)
@@ -1218,15 +765,15 @@ int fastf_reps_summary_row(float rate_cell, float rate_depth, uint64_t reads_per
                            char *buf, size_t cap)
 {
     static const int kind[FASTF_REPS_METRICS] = {0, 0, 0, 0, 1, 2, 2};
-    if (!buf || !metrics) return rs_err("null argument");
-    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return rs_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
+    if (!buf || !metrics) return fastf_res_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return fastf_res_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
     int n = reps_row_head(rate_cell, rate_depth, reads_per_cell, n_reps, buf, cap);
     if (n >= 0) { const int w = snprintf(buf + n, cap - (size_t)n, "\t%u", n_cells); n = (w < 0 || (size_t)w >= cap - (size_t)n) ? -1 : n + w; }
     for (uint32_t m = 0; m < FASTF_REPS_METRICS && n >= 0; m++) {
         const int w = reps_stat4(metrics + m, FASTF_REPS_METRICS, n_reps, kind[m], buf + n, cap - (size_t)n);
         n = w < 0 ? -1 : n + w;
     }
-    if (n < 0 || (size_t)n + 1 >= cap) return rs_err("summary row too long");
+    if (n < 0 || (size_t)n + 1 >= cap) return fastf_res_err("summary row too long");
     buf[n] = '\n'; buf[n + 1] = '\0';
     return 0;
 }
@@ -1234,8 +781,8 @@ int fastf_reps_summary_row(float rate_cell, float rate_depth, uint64_t reads_per
 int fastf_genes_reps_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, const uint32_t *genes_detected, uint32_t n_reps,
                          const uint64_t *reps_detected, uint32_t n_features, char *buf, size_t cap)
 {
-    if (!buf || !genes_detected || (n_features && !reps_detected)) return rs_err("null argument");
-    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return rs_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
+    if (!buf || !genes_detected || (n_features && !reps_detected)) return fastf_res_err("null argument");
+    if (n_reps < 1 || n_reps > FASTF_MAX_SEEDS) return fastf_res_err("a replicate row takes 1 to %u replicates", FASTF_MAX_SEEDS);
     double v[FASTF_MAX_SEEDS];
     for (uint32_t k = 0; k < n_reps; k++) v[k] = (double)genes_detected[k];
     uint32_t all = 0, any = 0;
@@ -1243,12 +790,12 @@ int fastf_genes_reps_row(float rate_cell, float rate_depth, uint64_t reads_per_c
     int n = reps_row_head(rate_cell, rate_depth, reads_per_cell, n_reps, buf, cap);
     if (n >= 0) { const int w = reps_stat4(v, 1, n_reps, 0, buf + n, cap - (size_t)n); n = w < 0 ? -1 : n + w; }
     if (n >= 0) { const int w = snprintf(buf + n, cap - (size_t)n, "\t%u\t%u\n", all, any); n = (w < 0 || (size_t)w >= cap - (size_t)n) ? -1 : n + w; }
-    return n < 0 ? rs_err("summary row too long") : 0;
+    return n < 0 ? fastf_res_err("summary row too long") : 0;
 }
 
 int fastf_gene_reps_add_host(const uint32_t *cells_per_gene, uint32_t n_features, uint64_t *detected, uint64_t *sum, uint64_t *sumsq)
 {
-    if (n_features && (!cells_per_gene || !detected || !sum || !sumsq)) return rs_err("null argument");
+    if (n_features && (!cells_per_gene || !detected || !sum || !sumsq)) return fastf_res_err("null argument");
     for (uint32_t g = 0; g < n_features; g++) {
         const uint64_t c = cells_per_gene[g];
         detected[g] += c != 0; sum[g] += c; sumsq[g] += c * c;
@@ -1267,21 +814,18 @@ static void reps_release(res_reps_t *P)
     P->feat_id = NULL; P->m = NULL; P->n_cells = P->gdet = NULL; P->seen = NULL; P->h_acc = NULL; P->d_acc = NULL; P->n_features = 0;
 }
 
-int fastf_res_reps_open(res_reps_t *P, int on, const char *verb, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
-                        uint32_t n_list, int genes, int device, const char *header, const char *genes_header)
+int fastf_res_reps_open(res_reps_t *P, int on, const res_verb_t *V, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
+                        uint32_t n_list, int genes, int device)
 {
     memset(P, 0, sizeof *P);
     if (!on) return 0;
-    P->verb = verb; P->seeds = seeds; P->n_seeds = n_seeds; P->n_rates = n_rates; P->n_list = n_list; P->genes = genes; P->device = device;
+    P->verb = V->name; P->seeds = seeds; P->n_seeds = n_seeds; P->n_rates = n_rates; P->n_list = n_list; P->genes = genes; P->device = device;
     snprintf(P->out_dir, sizeof P->out_dir, "%s", out_dir);
     const size_t cells = (size_t)n_list * n_seeds;
     if (!(P->m = (double *)calloc(cells * FASTF_REPS_METRICS, sizeof *P->m)) || !(P->n_cells = (uint32_t *)calloc(cells, sizeof *P->n_cells)) ||
-        !(P->gdet = (uint32_t *)calloc(cells, sizeof *P->gdet)) || !(P->seen = (uint8_t *)calloc(cells, 1))) { reps_release(P); return rs_err("out of memory"); }
-    char name[64];
-    snprintf(name, sizeof name, "%s_reps.tsv", verb);
-    if (fastf_res_tsv_open(&P->tsv, out_dir, name, header)) { reps_release(P); return 1; }
-    snprintf(name, sizeof name, "%s_genes_reps.tsv", verb);
-    if (genes && fastf_res_tsv_open(&P->gtsv, out_dir, name, genes_header)) { fastf_res_tsv_close(&P->tsv, 0); reps_release(P); return 1; }
+        !(P->gdet = (uint32_t *)calloc(cells, sizeof *P->gdet)) || !(P->seen = (uint8_t *)calloc(cells, 1))) { reps_release(P); return fastf_res_err("out of memory"); }
+    if (fastf_res_table_open(&P->tsv, V, out_dir, TB_REPS)) { reps_release(P); return 1; }
+    if (genes && fastf_res_table_open(&P->gtsv, V, out_dir, TB_GENES_REPS)) { fastf_res_tsv_close(&P->tsv, 0); reps_release(P); return 1; }
     P->on = 1;
     return 0;
 }
@@ -1295,14 +839,14 @@ int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_devi
     const uint32_t nf = (uint32_t)L->n_features;
     if (!P->feat_id) {                                      /* the first cell rate: the names, the room of the accumulators */
         if (!(P->feat_id = (char **)calloc(nf ? nf : 1, sizeof *P->feat_id)) ||
-            !(P->h_acc = (uint64_t *)calloc((size_t)P->n_rates * P->n_list * 3 * nf + 1, sizeof *P->h_acc))) return rs_err("out of memory");
-        for (uint32_t i = 0; i < nf; i++) { if (!(P->feat_id[i] = strdup(L->feat_id[i]))) return rs_err("out of memory"); P->n_features = i + 1; }
+            !(P->h_acc = (uint64_t *)calloc((size_t)P->n_rates * P->n_list * 3 * nf + 1, sizeof *P->h_acc))) return fastf_res_err("out of memory");
+        for (uint32_t i = 0; i < nf; i++) { if (!(P->feat_id[i] = strdup(L->feat_id[i]))) return fastf_res_err("out of memory"); P->n_features = i + 1; }
     }
-    if (nf != P->n_features) return rs_err("internal error: the feature list changed between cell rates");
+    if (nf != P->n_features) return fastf_res_err("internal error: the feature list changed between cell rates");
     const size_t bytes = (size_t)P->n_list * 3 * nf * 8;
     if (on_device && nf) {
         if (!P->d_acc && !(P->d_acc = fastf_devmem_alloc(P->device, bytes)))
-            return rs_err("%s: the per-gene accumulators of the replicates do not fit: %zu bytes (%s)", P->verb, bytes, fastf_last_error());
+            return fastf_res_err("%s: the per-gene accumulators of the replicates do not fit: %zu bytes (%s)", P->verb, bytes, fastf_last_error());
         if (fastf_devmem_zero(P->d_acc, bytes)) return 1;
     }
     return 0;
@@ -1311,7 +855,7 @@ int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_devi
 int fastf_res_reps_point(res_reps_t *P, uint32_t j, uint32_t k, uint32_t n_cells, const double *metrics)
 {
     if (!P->on) return 0;
-    if (j >= P->n_list || k >= P->n_seeds) return rs_err("internal error: replicate (%u, %u) outside the grid", j, k);
+    if (j >= P->n_list || k >= P->n_seeds) return fastf_res_err("internal error: replicate (%u, %u) outside the grid", j, k);
     const size_t at = (size_t)j * P->n_seeds + k;
     memcpy(P->m + at * FASTF_REPS_METRICS, metrics, FASTF_REPS_METRICS * sizeof *metrics);
     P->n_cells[at] = n_cells; P->seen[at] = 1;
@@ -1321,15 +865,15 @@ int fastf_res_reps_point(res_reps_t *P, uint32_t j, uint32_t k, uint32_t n_cells
 int fastf_res_reps_genes(res_reps_t *P, res_rate_t *S, uint32_t j, uint32_t k, const uint32_t *cells_per_gene, uint32_t n_features)
 {
     if (!P->on || !P->genes) return 0;
-    if (j >= P->n_list || k >= P->n_seeds || P->rate_at >= P->n_rates) return rs_err("internal error: replicate (%u, %u) outside the grid", j, k);
-    if (n_features != P->n_features) return rs_err("internal error: the feature list changed between points");
+    if (j >= P->n_list || k >= P->n_seeds || P->rate_at >= P->n_rates) return fastf_res_err("internal error: replicate (%u, %u) outside the grid", j, k);
+    if (n_features != P->n_features) return fastf_res_err("internal error: the feature list changed between points");
     const uint32_t nf = P->n_features;
     uint32_t d1 = 0;
     for (uint32_t g = 0; g < nf; g++) d1 += cells_per_gene[g] >= 1;
     P->gdet[(size_t)j * P->n_seeds + k] = d1;
     if (S) {                                                /* the device's copy of the same array, behind the point's gene summary */
         if (!nf) return 0;
-        if (!P->d_acc) return rs_err("internal error: no per-gene accumulators on the device");
+        if (!P->d_acc) return fastf_res_err("internal error: no per-gene accumulators on the device");
         uint64_t *const a = (uint64_t *)P->d_acc + (size_t)j * 3 * nf;
         return fastf_dev_gene_reps_add(S->e, S->buf.cpg.u32, nf, a, a + nf, a + 2 * (size_t)nf, NULL);
     }
@@ -1341,15 +885,15 @@ int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_d
 {
     if (!P->on) return 0;
     const double t0 = fastf_res_now();
-    if (P->rate_at >= P->n_rates) return rs_err("internal error: more cell rates than the grid has");
+    if (P->rate_at >= P->n_rates) return fastf_res_err("internal error: more cell rates than the grid has");
     const uint32_t nf = P->n_features;
     for (uint32_t j = 0; j < P->n_list; j++) {
         const size_t at = (size_t)j * P->n_seeds;
         char row[1536];
         for (uint32_t k = 0; k < P->n_seeds; k++) {
-            if (!P->seen[at + k]) return rs_err("internal error: replicate (%u, %u) was not run", j, k);
+            if (!P->seen[at + k]) return fastf_res_err("internal error: replicate (%u, %u) was not run", j, k);
             if (P->n_cells[at + k] != P->n_cells[at])
-                return rs_err("%s: cell rate %.3f sampled %u cells at seed %u and %u at seed %u: the sample size depends on the rate alone", P->verb,
+                return fastf_res_err("%s: cell rate %.3f sampled %u cells at seed %u and %u at seed %u: the sample size depends on the rate alone", P->verb,
                               (double)rate_cell, P->n_cells[at], P->seeds[0], P->n_cells[at + k], P->seeds[k]);
         }
         const float rd = rates_depth ? rates_depth[j] : 0.0f;
@@ -1372,28 +916,26 @@ int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_d
 /* <out_dir>/<verb>_gene_reps.tsv.gz: per feature and grid point the three accumulators */
 static int reps_gene_file(const res_reps_t *P, const float *rates_cell, const float *rates_depth, const uint64_t *caps)
 {
-    char path[4200];
+    char file[64];
     gtext t = { NULL, 0, 0 };
     const uint32_t nf = P->n_features, np = P->n_rates * P->n_list;
     static const char *const col[3] = {":reps_detected", ":cells_sum", ":cells_sumsq"};
-    int bad = gt_str(&t, "feature");
+    int bad = fastf_gt_str(&t, "feature");
     for (uint32_t p = 0; p < np && !bad; p++) {
         char name[64];
         const uint32_t i = p / P->n_list, j = p % P->n_list;
         bad = caps ? (!strcmp(P->verb, "level") ? fastf_level_point_dir : fastf_cap_point_dir)(rates_cell[i], caps[j], name, sizeof name) : fastf_sweep_point_dir(rates_cell[i], rates_depth[j], name, sizeof name);
-        for (int c = 0; c < 3 && !bad; c++) bad = gt_str(&t, "\t") || gt_str(&t, name) || gt_str(&t, col[c]);
+        for (int c = 0; c < 3 && !bad; c++) bad = fastf_gt_str(&t, "\t") || fastf_gt_str(&t, name) || fastf_gt_str(&t, col[c]);
     }
-    if (!bad) bad = gt_str(&t, "\n");
+    if (!bad) bad = fastf_gt_str(&t, "\n");
     for (uint32_t g = 0; g < nf && !bad; g++) {
-        bad = gt_str(&t, P->feat_id[g]);
+        bad = fastf_gt_str(&t, P->feat_id[g]);
         for (uint32_t p = 0; p < np && !bad; p++)
-            for (int c = 0; c < 3 && !bad; c++) bad = gt_u64(&t, '\t', P->h_acc[((size_t)p * 3 + (size_t)c) * nf + g]);
-        if (!bad) bad = gt_str(&t, "\n");
+            for (int c = 0; c < 3 && !bad; c++) bad = fastf_gt_u64(&t, '\t', P->h_acc[((size_t)p * 3 + (size_t)c) * nf + g]);
+        if (!bad) bad = fastf_gt_str(&t, "\n");
     }
-    snprintf(path, sizeof path, "%s/%s_gene_reps.tsv.gz", P->out_dir, P->verb);
-    if (!bad) bad = gz_text_renamed(path, &t);
-    free(t.p);
-    return bad;
+    snprintf(file, sizeof file, "%s_gene_reps.tsv.gz", P->verb);
+    return fastf_res_text_file(P->out_dir, file, &t, bad);
 }
 
 /* ok: the per-gene file (its columns named from the grid: rates_cell and ONE of rates_depth / caps), then the tables; otherwise
@@ -1402,7 +944,7 @@ int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, co
 {
     if (!P->on) return 0;
     int rc = 0;
-    if (ok && P->rate_at != P->n_rates) rc = rs_err("internal error: %u of %u cell rates were closed", P->rate_at, P->n_rates);
+    if (ok && P->rate_at != P->n_rates) rc = fastf_res_err("internal error: %u of %u cell rates were closed", P->rate_at, P->n_rates);
     if (ok && !rc && P->genes) rc = reps_gene_file(P, rates_cell, rates_depth, caps);
     char keep[512]; snprintf(keep, sizeof keep, "%s", fastf_last_error());
     const int bad = rc;
@@ -1415,12 +957,6 @@ int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, co
 }
 int fastf_res_reps_close(res_reps_t *P, int ok) { return fastf_res_reps_close_grid(P, ok, NULL, NULL, NULL); }
 
-void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb)
-{
-    static const char *const tail[] = {"genes.tsv", "cells.tsv", "reps.tsv", "genes_reps.tsv", "gene_reps.tsv.gz", "fidelity.tsv", "gene_fidelity.tsv", "neighbors.tsv", "labels.tsv", "label_classes.tsv", "markers.tsv"};
-    for (int k = 0; k < 11; k++) { char path[4200]; snprintf(path, sizeof path, "%s/%s_%s", out_dir, verb, tail[k]); unlink(path); }
-}
-
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
 {
     size_t m = 0;
@@ -1428,6 +964,9 @@ uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
     return (uint32_t)m;
 }
 
+/* ------------------------------------------------------------------ */
+/* the command line                                                    */
+/* ------------------------------------------------------------------ */
 struct ropt { char s; const char *l; int has_arg; };
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *out)

@@ -2,8 +2,11 @@
  * in device memory after ONE decode; per cell rate one engine, the records in its layout and K1a once; per point K1b on that point's
  * decision plane, sort, reduce, the per-cell summary and — when the matrices are wanted — the rows gathered into pinned memory
  * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made: each verb describes itself in
- * ONE res_verb_t (its name, headers, wording and the hooks that make the planes), and ONE driver (grid_run.c: fastf_res_grid_run) runs
- * the checks, the tables, the (cell rate, seed) pairs and the body of every point for all three.
+ * ONE res_verb_t (its name, index, summary header, wording and the hooks that make the planes), and ONE driver (grid_run.c:
+ * fastf_res_grid_run) runs the checks, the tables, the (cell rate, seed) pairs and the body of every point for all three.
+ * The files: resident.c has the device side, the lists, the replicate accumulators and the command line; res_tables.c every table and
+ * point file of a run — the comparisons against full depth below are ONE descriptor each there (res_cmp_t); grid_rows.c the host
+ * analysis, the rows and the headers of the per-verb tables, defined once (fastf_res_table_header).  The last two touch no device.
  * --cells adds a stage of its own behind a point (fastf_res_point_cells): the point's keys sorted fully, K3u's rows, their per-cell
  * and copy-number summary.  It runs AFTER the point's matrix rows have left the device — K3u writes the engine's row regions
  * (their count array and the span tables are the ones the matrix rows lie in) and fastf_res_point_write gathers from those.
@@ -41,6 +44,8 @@ enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UR
 
 typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors, labels, markers; uint32_t opens, relays, passes; } res_times_t;   /* markers: --markers alone — the kernel calls on the planes, their D2H, the ranks, rows and files; labels: --labels alone — the label arrays of every pair, the vote calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
+/* the error message of the grid files, set as printf formats it; returns 1 (grid_rows.c) */
+int    fastf_res_err(const char *fmt, ...) __attribute__((format(printf, 1, 2))) FASTF_HIDDEN;
 double fastf_res_now(void) FASTF_HIDDEN;
 int    fastf_res_make_dir(const char *path) FASTF_HIDDEN;
 
@@ -62,8 +67,8 @@ void fastf_res_free(resident_t *R) FASTF_HIDDEN;
 
 /* one (cell rate, seed) pair: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point),
  * the buffers of a point.  DESIGN.md section 10q describes this state once; in short:
- * cfg   what the caller sets before the first open and no open or close touches: the comparisons that are on (neighbors is set with
- *       labels too; markers = N needs labels), max_cells, the most cells any pair of the run samples (0: unknown), which the lists tell,
+ * cfg   what the caller sets before the first open and no open or close touches: the comparisons that are on (fastf_res_cmp_cfg, from
+ *       the mask of the run's res_cmp_t: neighbors is set with labels too; markers = N needs labels), max_cells, the most cells any pair of the run samples (0: unknown), which the lists tell,
  *       and no_reuse (the verbs read FASTF_RES_NO_REUSE=1 once per run): fresh buffers and a fresh blocked copy for every pair.
  * buf   the buffer table: every device, pinned or host buffer of the state.  The buffers outlive the pair: a run keeps ONE res_rate_t,
  *       zeroed before its first open, and every later fastf_res_rate_open on it ends the pair before (its engine) and takes its buffers
@@ -137,6 +142,10 @@ int  fastf_res_level_init(res_rate_t *S, uint64_t umi_cap, uint64_t *open_out, u
  * every point row's partner count into S->buf.gx, then sum_y, cells, sum_yy and sum_xy per gene to the host (S->h_gfid.sy, S->h_gfid.c,
  * S->h_gfid.syy, S->h_gfid.sxy); a row without a partner fails the point.  Nothing without S->cfg.gene_fid */
 int  fastf_res_full_keep(res_rate_t *S, res_times_t *T) FASTF_HIDDEN;
+/* a pair needs its full rows: any of the three is on (labels and markers come with neighbors).  fastf_res_full_timer: where the
+ * full-depth work of a pair is booked (per_gene: its per-gene sums, which --fidelity has no part in) */
+static inline int res_cfg_full(const res_cfg_t *cfg) { return cfg->fidelity || cfg->gene_fid || cfg->neighbors; }
+double *fastf_res_full_timer(const res_rate_t *S, res_times_t *T, int per_gene) FASTF_HIDDEN;
 int  fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_point_gene_fidelity(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
@@ -169,11 +178,28 @@ int  fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t 
  * fastf_res_point_run when no rows are written: K3u overwrites the row regions that call gathers from. */
 int  fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
-/* the summary table of a verb: written as <out_dir>/<name>.partial, renamed to <out_dir>/<name> by a close with ok != 0; otherwise
- * nothing of it is left */
+/* ---- the tables and point files of a run (res_tables.c) ----
+ * the per-verb tables <out_dir>/<verb>_<stem>.tsv: their stems and headers are defined once (grid_rows.c: GRID_TABLES, from which the
+ * exported fastf_<verb>_<stem>_header getters come too) and looked up by (verb index, table id) */
+typedef struct res_verb res_verb_t;
+enum { VERB_SWEEP, VERB_CAP, VERB_LEVEL };
+enum { TB_GENES, TB_CELLS, TB_FIDELITY, TB_GENE_FIDELITY, TB_NEIGHBORS, TB_LABELS, TB_LABEL_CLASSES, TB_MARKERS, TB_COEXPR, TB_REPS, TB_GENES_REPS, TB_N_ };
+const char *fastf_res_table_stem(int table) FASTF_HIDDEN;
+const char *fastf_res_table_header(int verb, int table) FASTF_HIDDEN;
+
+/* a table: written as <out_dir>/<name>.partial, renamed to <out_dir>/<name> by a close with ok != 0; otherwise nothing of it is left.
+ * fastf_res_table_open: the per-verb table `table` of V, under its name and header */
 typedef struct { FILE *f; char tmp[4096], final[4096]; } res_tsv_t;
 int fastf_res_tsv_open(res_tsv_t *t, const char *out_dir, const char *name, const char *header) FASTF_HIDDEN;
+int fastf_res_table_open(res_tsv_t *t, const res_verb_t *V, const char *out_dir, int table) FASTF_HIDDEN;
 int fastf_res_tsv_close(res_tsv_t *t, int ok) FASTF_HIDDEN;
+
+/* a text that grows, and its file: fastf_res_text_file writes the finished text t, gzipped, as dir/name through dir/name.partial (dir is
+ * created) unless bad != 0 — the text was not finished — and frees it either way; returns bad, or 1 after its own error */
+typedef struct { char *p; size_t len, cap; } gtext;
+int fastf_gt_str(gtext *t, const char *s) FASTF_HIDDEN;
+int fastf_gt_u64(gtext *t, char lead, uint64_t v) FASTF_HIDDEN;       /* `lead`, then v in decimal */
+int fastf_res_text_file(const char *dir, const char *name, gtext *t, int bad) FASTF_HIDDEN;
 
 /* --genes of a verb: <out_dir>/<verb>_genes.tsv (one row per point, through .partial), <out_dir>/<verb>_gene_cells.tsv.gz (the cells
  * per gene of every point, written by a close with ok != 0) and <point dir>/genes.tsv.gz.  on == 0: every call does nothing */
@@ -185,7 +211,7 @@ typedef struct {
     uint32_t *cells;                     /* [max_points][n_features] */
     char (*names)[64];                   /* the point directory names */
 } res_genes_t;
-int fastf_res_genes_open(res_genes_t *G, int on, const char *verb, const char *out_dir, const char *header, uint32_t max_points, int no_grid) FASTF_HIDDEN;
+int fastf_res_genes_open(res_genes_t *G, int on, const res_verb_t *V, const char *out_dir, uint32_t max_points, int no_grid) FASTF_HIDDEN;
 /* one point: `row` (fastf_genes_summary_row) into the table, cells[] kept for the grid file, and — dir != NULL — dir/genes.tsv.gz */
 int fastf_res_genes_point(res_genes_t *G, const fastf_lists_t *L, const char *point_name, const char *dir, const char *row,
                           const uint32_t *cells, const uint64_t *umis) FASTF_HIDDEN;
@@ -194,32 +220,30 @@ int fastf_res_genes_close(res_genes_t *G, int ok) FASTF_HIDDEN;
 /* --cells of a verb: <out_dir>/<verb>_cells.tsv (one row per point, through .partial) and <point dir>/cells.tsv.gz.  on == 0: every
  * call does nothing */
 typedef struct { int on; const char *verb; res_tsv_t tsv; } res_cells_t;
-int fastf_res_cells_open(res_cells_t *C, int on, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
+int fastf_res_cells_open(res_cells_t *C, int on, const res_verb_t *V, const char *out_dir) FASTF_HIDDEN;
 /* one point, after fastf_res_point_cells: `row` (fastf_cells_summary_row) into the table and — dir != NULL — dir/cells.tsv.gz from the
  * arrays of S (h_rpc, h_npc, h_upc, h_gpc, h_spc) and the barcodes of its lists */
 int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row) FASTF_HIDDEN;
 int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
 
-/* --fidelity of a verb: <out_dir>/<verb>_fidelity.tsv (one row per point, through .partial) and <point dir>/fidelity.tsv.gz;
- * --gene-fidelity: <out_dir>/<verb>_gene_fidelity.tsv and <point dir>/gene_fidelity.tsv.gz likewise.  full: either is on — the pair's
- * full rows are needed.  on == 0 and gene_on == 0: every call does nothing.  fastf_res_fid_close closes both tables before it renames
- * either, and where a rename fails neither table is left */
-typedef struct { int on, gene_on, nbr_on, lab_on, mk_on, full; const char *verb; res_tsv_t tsv, gtsv, ntsv, ltsv, ctsv, mtsv; const fastf_labels_t *labels; uint32_t markers; } res_fid_t;
-int fastf_res_fid_open(res_fid_t *F, int on, int gene_on, const char *verb, const char *out_dir, const char *header, const char *gene_header) FASTF_HIDDEN;
-/* --neighbors: <out_dir>/<verb>_neighbors.tsv and <point dir>/neighbors.tsv.gz likewise; called behind fastf_res_fid_open (which clears F).
- * On failure the caller closes F with ok == 0 */
-int fastf_res_fid_open_neighbors(res_fid_t *F, int on, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
-/* --labels (labels != NULL): the fourth table set — <out_dir>/<verb>_labels.tsv, <out_dir>/<verb>_label_classes.tsv, and per point
- * labels.tsv.gz and label_confusion.tsv.gz; called behind the two opens above.  On failure the caller closes F with ok == 0 */
-int fastf_res_fid_open_labels(res_fid_t *F, const fastf_labels_t *labels, const char *verb, const char *out_dir, const char *header, const char *classes_header) FASTF_HIDDEN;
-/* --markers N (markers != 0; behind fastf_res_fid_open_labels, which it needs): the fifth table set — <out_dir>/<verb>_markers.tsv and per
- * point markers.tsv.gz.  On failure the caller closes F with ok == 0 */
-int fastf_res_fid_open_markers(res_fid_t *F, uint32_t markers, const char *verb, const char *out_dir, const char *header) FASTF_HIDDEN;
-/* one point, after fastf_res_point_fidelity / fastf_res_point_gene_fidelity: its row (list_value == 0: rate_depth in the second column)
- * into each table that is on and — dir != NULL — dir/fidelity.tsv.gz from the arrays of S (h_ufull, h_upc, h_gfull, h_gpc, h_sxx, h_syy,
- * h_sxy) and the barcodes of its lists, dir/gene_fidelity.tsv.gz from the per-gene arrays of S and the feature ids */
-int fastf_res_fid_point(res_fid_t *F, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T) FASTF_HIDDEN;
-int fastf_res_fid_close(res_fid_t *F, int ok) FASTF_HIDDEN;
+/* the comparisons of a point against full depth: --neighbors, --labels FILE, --markers N, --gene-fidelity, --fidelity, in the order a
+ * point writes them.  Each is ONE descriptor in res_tables.c — its tables (labels has two: labels and label_classes), its timer in
+ * res_times_t, its point writer, which puts the point's row(s) into the table(s) and, with a directory, <point dir>/<name>.tsv.gz
+ * (labels: labels.tsv.gz and label_confusion.tsv.gz) from the host views of S.  on: bit c set — comparison c is on; tsv: the tables
+ * TB_FIDELITY .. TB_MARKERS at [table - TB_FIDELITY], which is the order they are opened and renamed in.
+ * fastf_res_cmp_open clears C and opens the tables of the comparisons the flag word (FASTF_SWEEP_*), labels != NULL and markers != 0
+ * switch on; on failure nothing of them is left.  fastf_res_cmp_cfg: what the device side is to compute for them (S->cfg).
+ * fastf_res_cmp_point: one point, behind fastf_res_point_compare — every writer that is on, timed into its timer (list_value == 0:
+ * rate_depth in the second column).  fastf_res_cmp_close closes every table before it renames any, and where a rename fails no
+ * table is left and the message names the file.  A C that is all zero is closed: every call on it does nothing */
+enum { CMP_NEIGHBORS, CMP_LABELS, CMP_MARKERS, CMP_GENE_FID, CMP_FIDELITY, CMP_N_ };
+#define RES_CMP_TABLES (TB_MARKERS - TB_FIDELITY + 1)
+typedef struct { uint32_t on; res_tsv_t tsv[RES_CMP_TABLES]; const fastf_labels_t *labels; uint32_t markers; } res_cmp_t;
+static inline int res_cmp_on(const res_cmp_t *C, int c) { return (int)(C->on >> c & 1); }
+int  fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers) FASTF_HIDDEN;
+void fastf_res_cmp_cfg(const res_cmp_t *C, res_cfg_t *cfg) FASTF_HIDDEN;
+int  fastf_res_cmp_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T) FASTF_HIDDEN;
+int  fastf_res_cmp_close(res_cmp_t *C, int ok) FASTF_HIDDEN;
 
 /* replicate runs (--seeds, --reps; fastf_sweep_reps, fastf_cap_reps): <verb>_reps.tsv, and with --genes <verb>_genes_reps.tsv and
  * <verb>_gene_reps.tsv.gz.  The metrics of the cell rate in work are kept per (list value j, seed k) until its last seed is done;
@@ -236,8 +260,8 @@ typedef struct {
     uint32_t n_features; char **feat_id;
     void *d_acc; uint64_t *h_acc;        /* h_acc: [n_rates * n_list][3][n_features] */
 } res_reps_t;
-int fastf_res_reps_open(res_reps_t *P, int on, const char *verb, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
-                        uint32_t n_list, int genes, int device, const char *header, const char *genes_header) FASTF_HIDDEN;
+int fastf_res_reps_open(res_reps_t *P, int on, const res_verb_t *V, const char *out_dir, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_rates,
+                        uint32_t n_list, int genes, int device) FASTF_HIDDEN;
 /* a cell rate begins: the names of the features (first call), the accumulators cleared; on_device: d_acc is used */
 int fastf_res_reps_rate_begin(res_reps_t *P, const fastf_lists_t *L, int on_device) FASTF_HIDDEN;
 /* point (list value j, seed k) of the cell rate in work: its metrics; with --genes its per-gene array — S != NULL: S->buf.cpg on the
@@ -250,8 +274,8 @@ int fastf_res_reps_rate_end(res_reps_t *P, float rate_cell, const float *rates_d
  * renamed; otherwise nothing of them is left */
 int fastf_res_reps_close_grid(res_reps_t *P, int ok, const float *rates_cell, const float *rates_depth, const uint64_t *caps) FASTF_HIDDEN;
 int fastf_res_reps_close(res_reps_t *P, int ok) FASTF_HIDDEN;   /* ok == 0 only */
-/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,fidelity,gene_fidelity,neighbors,labels,label_classes,markers,reps,genes_reps}.tsv and
- * <verb>_gene_reps.tsv.gz is left */
+/* a replicate run failed after tables were renamed into place: none of <verb>_{genes,cells,reps,genes_reps}.tsv, of the tables of
+ * res_cmp_t and <verb>_gene_reps.tsv.gz is left (res_tables.c) */
 void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_HIDDEN;
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
@@ -282,10 +306,10 @@ typedef struct {
     uint32_t flags; const char *labels_path; uint32_t markers;
 } res_job_t;
 /* the tables of a run, zeroed before the first open: every close is safe on a table that was never opened */
-typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_fid_t Fd; res_reps_t P; } res_tables_t;
+typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_cmp_t Fd; res_reps_t P; } res_tables_t;
 /* one (cell rate, seed) pair as the hooks see it: S is open (fastf_res_rate_open) */
 typedef struct {
-    const res_job_t *job; res_rate_t *S; const resident_t *R; const fastf_lists_t *L; const res_fid_t *Fd; res_times_t *T;
+    const res_job_t *job; res_rate_t *S; const resident_t *R; const fastf_lists_t *L; res_times_t *T;
     float rate_cell; uint32_t seed; int device, summary_only, prof;   /* prof: FASTF_PROFILE is set */
 } res_pair_t;
 /* a verb: ONE static const instance in its file.  The hooks (ctx: what pair_begin made, handed to the others; a hook that is NULL is
@@ -301,10 +325,9 @@ typedef struct {
  *   pair_end     frees what pair_begin made (ctx may be NULL or half built)
  *   run_profile  level: its search line under FASTF_PROFILE, behind the stage line
  *   point_by_point  sweep: the grid through bam2db() for a job outside the resident form; the tables were opened afresh */
-typedef struct {
-    const char *name;
-    struct { const char *(*summary)(void), *(*genes)(void), *(*cells)(void), *(*fidelity)(void), *(*gene_fidelity)(void), *(*neighbors)(void),
-                        *(*labels)(void), *(*label_classes)(void), *(*markers)(void), *(*reps)(void), *(*genes_reps)(void); } header;
+struct res_verb {
+    const char *name; int index;         /* index: VERB_*, which picks the verb's headers of the per-verb tables */
+    const char *(*header)(void);         /* of <verb>.tsv */
     /* cap, level: the grid check and the directory name of a point of a caps list; NULL: sweep's, of a depth-rate list */
     int (*check_caps)(const float *rates_cell, uint32_t n_c, const uint64_t *caps, uint32_t n);
     int (*caps_point_dir)(float rate_cell, uint64_t cap_value, char *buf, size_t cap);
@@ -320,17 +343,21 @@ typedef struct {
     void (*pair_end)(void *ctx);
     void (*run_profile)(const res_job_t *job, const res_times_t *T);
     int  (*point_by_point)(const res_job_t *job, int summary_only, res_tables_t *tb);
-} res_verb_t;
+};
 /* the run of an entry point: the seeds of a replicate run, null arguments, with labels_path the bam file and the labels (before anything
  * is written), the grid, the flags, the bam file, the devices, the output directory, the tables, the pairs, the close */
 int fastf_res_grid_run(const res_verb_t *V, const res_job_t *job) FASTF_HIDDEN;
 /* the first two checks of a fastf_*_markers entry point */
 int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path) FASTF_HIDDEN;
 
-/* sweep_cmds.c: the columns of a summary row from `seed` on (no newline); metrics != NULL: the FASTF_REPS_METRICS numbers a replicate
+/* grid_rows.c: the columns of a summary row from `seed` on (no newline); metrics != NULL: the FASTF_REPS_METRICS numbers a replicate
  * table takes from the row (sampled_reads, sampled_valid_reads, nnz, umis, saturation, the two medians) as the row printed them */
 int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
                         const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
+
+/* grid_rows.c: one row of sweep.tsv (with its newline); metrics: fastf_summary_tail_ */
+int fastf_sweep_row_(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
+                     const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
 
 /* cap_cmds.c: one row of cap.tsv or level.tsv (with its newline); metrics: fastf_summary_tail_ */
 int fastf_cap_row_(float rate_cell, uint64_t list_value, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,

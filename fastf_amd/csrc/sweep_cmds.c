@@ -14,7 +14,7 @@
  * Jobs this form does not cover (keys wider than 64 bits, UMIs beyond 16 bases, several devices) run point by point
  * through bam2db() itself, the summary then read back from each point's matrix.
  * --genes: per point the rows reduced along the gene axis too (fastf_dev_gene_summary; point by point fastf_sweep_genes_from_coo)
- * into sweep_genes.tsv, sweep_gene_cells.tsv.gz and the point's genes.tsv.gz (resident.c).
+ * into sweep_genes.tsv, sweep_gene_cells.tsv.gz and the point's genes.tsv.gz (res_tables.c).
  * --cells: behind every point its keys sorted fully, K3u's rows and their reduction along the cell axis and into the copy-number
  * histogram (fastf_res_point_cells: fastf_dev_umi_rows, fastf_dev_copy_summary) into sweep_cells.tsv and the point's cells.tsv.gz;
  * resident form only — a job outside it is refused with the flag.
@@ -39,22 +39,12 @@
 
 #include <errno.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
-
-static int sw_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static int sw_err(const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    fastf_set_error_(buf);
-    return 1;
-}
 
 /* ------------------------------------------------------------------ */
 /* the grid                                                            */
@@ -66,24 +56,24 @@ int fastf_sweep_parse_rates(const char *text, int cell_rates, float *out, uint32
     const char *what = cell_rates ? "cell" : "depth";
     uint32_t n = 0;
     if (n_out) *n_out = 0;
-    if (!text || !out || !n_out) return sw_err("null argument");
+    if (!text || !out || !n_out) return fastf_res_err("null argument");
     for (const char *p = text;;) {
         const char *q = p;
         while (*q && *q != ',') q++;
         char el[64];
         const size_t len = (size_t)(q - p);
-        if (len == 0) return sw_err("%s rates `%s`: empty element", what, text);
-        if (len >= sizeof el) return sw_err("%s rates `%s`: element too long", what, text);
+        if (len == 0) return fastf_res_err("%s rates `%s`: empty element", what, text);
+        if (len >= sizeof el) return fastf_res_err("%s rates `%s`: element too long", what, text);
         memcpy(el, p, len); el[len] = '\0';
         char *end = NULL;
         errno = 0;
         const float v = strtof(el, &end);
-        if (errno == ERANGE) return sw_err("%s rate `%s`: numerical result out of range", what, el);
-        if (end == el || *end) return sw_err("%s rate `%s`: expects a numerical value", what, el);
-        if (isnan(v)) return sw_err("%s rate `%s`: not a number", what, el);
-        if (v < 0 || signbit(v)) return sw_err("%s rate `%s`: negative", what, el);
-        if (cell_rates && v > 1.0f) return sw_err("cell rate `%s`: sample size must lie in [0, number of barcodes]", el);
-        if (n == cap) return sw_err("%s rates `%s`: more than %u values", what, text, cap);
+        if (errno == ERANGE) return fastf_res_err("%s rate `%s`: numerical result out of range", what, el);
+        if (end == el || *end) return fastf_res_err("%s rate `%s`: expects a numerical value", what, el);
+        if (isnan(v)) return fastf_res_err("%s rate `%s`: not a number", what, el);
+        if (v < 0 || signbit(v)) return fastf_res_err("%s rate `%s`: negative", what, el);
+        if (cell_rates && v > 1.0f) return fastf_res_err("cell rate `%s`: sample size must lie in [0, number of barcodes]", el);
+        if (n == cap) return fastf_res_err("%s rates `%s`: more than %u values", what, text, cap);
         out[n++] = v;
         if (!*q) break;
         p = q + 1;
@@ -95,865 +85,26 @@ int fastf_sweep_parse_rates(const char *text, int cell_rates, float *out, uint32
 int fastf_sweep_point_dir(float rate_cell, float rate_depth, char *buf, size_t cap)
 {
     const int n = snprintf(buf, cap, "c%.3f_r%.3f", (double)rate_cell, (double)rate_depth);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("directory name too long") : 0;
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("directory name too long") : 0;
 }
 
 /* two values of one list that print the same at %.3f would share their directories and header lines */
 int fastf_sweep_check_grid(const float *rates_cell, uint32_t n_c, const float *rates_depth, uint32_t n_r)
 {
-    if (!n_c || !n_r || !rates_cell || !rates_depth) return sw_err("sweep: the grid needs at least one cell rate and one depth rate");
+    if (!n_c || !n_r || !rates_cell || !rates_depth) return fastf_res_err("sweep: the grid needs at least one cell rate and one depth rate");
     for (int pass = 0; pass < 2; pass++) {
         const float *v = pass ? rates_depth : rates_cell;
         const uint32_t n = pass ? n_r : n_c;
         for (uint32_t i = 0; i < n; i++) {
-            if (isnan(v[i]) || v[i] < 0) return sw_err("sweep: %s rate %g is negative or not a number", pass ? "depth" : "cell", (double)v[i]);
-            if (!pass && v[i] > 1.0f) return sw_err("sweep: cell rate %g: sample size must lie in [0, number of barcodes]", (double)v[i]);
+            if (isnan(v[i]) || v[i] < 0) return fastf_res_err("sweep: %s rate %g is negative or not a number", pass ? "depth" : "cell", (double)v[i]);
+            if (!pass && v[i] > 1.0f) return fastf_res_err("sweep: cell rate %g: sample size must lie in [0, number of barcodes]", (double)v[i]);
             char a[32], b[32];
             snprintf(a, sizeof a, "%.3f", (double)v[i]);
             for (uint32_t j = 0; j < i; j++) {
                 snprintf(b, sizeof b, "%.3f", (double)v[j]);
-                if (!strcmp(a, b)) return sw_err("sweep: %s rates %g and %g both print as %s", pass ? "depth" : "cell", (double)v[j], (double)v[i], a);
+                if (!strcmp(a, b)) return fastf_res_err("sweep: %s rates %g and %g both print as %s", pass ? "depth" : "cell", (double)v[j], (double)v[i], a);
             }
         }
-    }
-    return 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* the summary row                                                     */
-/* ------------------------------------------------------------------ */
-const char *fastf_sweep_header(void)
-{
-    return "rate_cell\trate_depth\tseed\tn_cells\ttotal_reads\tsampled_reads\tsampled_valid_reads\tnnz\tumis\tsaturation\t"
-           "median_umis_per_cell\tmedian_genes_per_cell\n";
-}
-
-static int cmp_u64(const void *a, const void *b) { const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b; return x < y ? -1 : x > y; }
-
-/* median over all n values (a cell without rows is a 0 among them); the mean of the two middle values when n is even */
-static double median_u64(uint64_t *v, size_t n)
-{
-    if (!n) return 0.0;
-    qsort(v, n, sizeof *v, cmp_u64);
-    return (n & 1) ? (double)v[n / 2] : ((double)v[n / 2 - 1] + (double)v[n / 2]) / 2.0;
-}
-
-/* per cell (1-based index c -> slot c - 1) the sum of the counts and the rows with count >= 1, and the sum of all counts: the host
- * form of fastf_dev_cell_summary (the point-by-point path, tests) */
-int fastf_sweep_cells_from_coo(const fastf_coo_t *coo, uint32_t n_cells, uint64_t *umis_per_cell, uint32_t *genes_per_cell, uint64_t *umis)
-{
-    if (!coo || !umis || (n_cells && (!umis_per_cell || !genes_per_cell))) return sw_err("null argument");
-    memset(umis_per_cell, 0, (size_t)n_cells * sizeof *umis_per_cell);
-    memset(genes_per_cell, 0, (size_t)n_cells * sizeof *genes_per_cell);
-    uint64_t total = 0;
-    for (size_t i = 0; i < coo->nnz; i++) {
-        const uint32_t c = coo->cell[i];
-        if (c == 0 || c > n_cells) return sw_err("matrix row %zu names cell %u of %u", i, c, n_cells);
-        umis_per_cell[c - 1] += coo->count[i];
-        genes_per_cell[c - 1] += coo->count[i] >= 1;
-        total += coo->count[i];
-    }
-    *umis = total;
-    return 0;
-}
-
-/* the columns from `seed` on (no newline): shared with cap.tsv */
-int fastf_summary_tail_(uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis, const uint64_t *umis_per_cell,
-                        const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics)
-{
-    if (!counters || !buf || (n_cells && (!umis_per_cell || !genes_per_cell))) return sw_err("null argument");
-    uint64_t *tmp = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *tmp);
-    if (!tmp) return sw_err("out of memory");
-    memcpy(tmp, umis_per_cell, (size_t)n_cells * sizeof *tmp);
-    const double med_u = median_u64(tmp, n_cells);
-    for (uint32_t i = 0; i < n_cells; i++) tmp[i] = genes_per_cell[i];
-    const double med_g = median_u64(tmp, n_cells);
-    free(tmp);
-    const double sat = counters[2] ? 1.0 - (double)umis / (double)counters[2] : 0.0;
-    if (metrics) {
-        metrics[0] = (double)counters[1]; metrics[1] = (double)counters[2]; metrics[2] = (double)nnz; metrics[3] = (double)umis;
-        metrics[4] = sat; metrics[5] = med_u; metrics[6] = med_g;
-    }
-    const int n = snprintf(buf, cap, "%u\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6f\t%.1f\t%.1f", seed, n_cells, (unsigned long long)counters[0],
-                           (unsigned long long)counters[1], (unsigned long long)counters[2], (unsigned long long)nnz, (unsigned long long)umis, sat, med_u, med_g);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-/* one row of sweep.tsv (with its newline); metrics: fastf_summary_tail_ */
-static int summary_row_(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
-                        const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap, double *metrics)
-{
-    char tail[400];
-    if (fastf_summary_tail_(seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, tail, sizeof tail, metrics)) return 1;
-    const int n = snprintf(buf, cap, "%.3f\t%.3f\t%s\n", (double)rate_cell, (double)rate_depth, tail);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-int fastf_sweep_summary_row(float rate_cell, float rate_depth, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
-                            const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, char *buf, size_t cap)
-{
-    return summary_row_(rate_cell, rate_depth, seed, counters, nnz, umis, umis_per_cell, genes_per_cell, n_cells, buf, cap, NULL);
-}
-
-/* ------------------------------------------------------------------ */
-/* --genes: the host twin, the row                                     */
-/* ------------------------------------------------------------------ */
-/* per gene (1-based feature g -> slot g - 1) the rows with count >= 1 and the sum of the counts: the host form of
- * fastf_dev_gene_summary (the point-by-point path, tests); a feature outside 1 .. n_features adds nothing, as there */
-int fastf_sweep_genes_from_coo(const fastf_coo_t *coo, uint32_t n_features, uint32_t *cells_per_gene, uint64_t *umis_per_gene)
-{
-    if (!coo || (n_features && (!cells_per_gene || !umis_per_gene)) || (coo->nnz && (!coo->feature || !coo->count))) return sw_err("null argument");
-    memset(cells_per_gene, 0, (size_t)n_features * sizeof *cells_per_gene);
-    memset(umis_per_gene, 0, (size_t)n_features * sizeof *umis_per_gene);
-    for (size_t i = 0; i < coo->nnz; i++) {
-        const uint32_t g = coo->feature[i] - 1u;
-        if (g >= n_features) continue;
-        cells_per_gene[g] += coo->count[i] >= 1;
-        umis_per_gene[g] += coo->count[i];
-    }
-    return 0;
-}
-
-#define GENES_COLUMNS_TAIL "seed\tgenes_detected\tgenes_min_cells_3\tgenes_min_cells_10\tmax_gene_umis\n"
-const char *fastf_sweep_genes_header(void) { return "rate_cell\trate_depth\t" GENES_COLUMNS_TAIL; }
-const char *fastf_cap_genes_header(void) { return "rate_cell\treads_per_cell\t" GENES_COLUMNS_TAIL; }
-const char *fastf_level_genes_header(void) { return "rate_cell\tumi_cap\t" GENES_COLUMNS_TAIL; }
-
-/* one row of sweep_genes.tsv (reads_per_cell == 0) or cap_genes.tsv (reads_per_cell >= 1: a cap is at least 1), with its newline */
-int fastf_genes_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *cells_per_gene,
-                            const uint64_t *umis_per_gene, uint32_t n_features, char *buf, size_t cap)
-{
-    if (!buf || (n_features && (!cells_per_gene || !umis_per_gene))) return sw_err("null argument");
-    uint32_t d1 = 0, d3 = 0, d10 = 0;
-    uint64_t top = 0;
-    for (uint32_t g = 0; g < n_features; g++) {
-        d1 += cells_per_gene[g] >= 1; d3 += cells_per_gene[g] >= 3; d10 += cells_per_gene[g] >= 10;
-        if (umis_per_gene[g] > top) top = umis_per_gene[g];
-    }
-    char second[32];
-    if (reads_per_cell) snprintf(second, sizeof second, "%llu", (unsigned long long)reads_per_cell);
-    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%llu\n", (double)rate_cell, second, seed, d1, d3, d10, (unsigned long long)top);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --cells: the host twin, the row                                     */
-/* ------------------------------------------------------------------ */
-/* the host form of fastf_dev_copy_summary, by its rules (tests; a reader of umi.tsv.gz) */
-int fastf_copies_from_umi_rows(const fastf_umi_rows_t *rows, uint32_t n_cells, uint32_t *reads, uint32_t *null_reads, uint32_t *single, uint64_t *hist)
-{
-    if (!rows || !reads || !null_reads || !single || !hist || (rows->n && (!rows->cell || !rows->n_copy || !rows->nonnull))) return sw_err("null argument");
-    memset(reads, 0, (size_t)n_cells * sizeof *reads);
-    memset(null_reads, 0, (size_t)n_cells * sizeof *null_reads);
-    memset(single, 0, (size_t)n_cells * sizeof *single);
-    memset(hist, 0, (FASTF_COPY_BINS + 1) * sizeof *hist);
-    for (size_t i = 0; i < rows->n; i++) {
-        const uint32_t c = rows->cell[i] - 1u, k = rows->n_copy[i];
-        const int nn = rows->nonnull[i] != 0;
-        if (nn && k) {
-            hist[(k < FASTF_COPY_BINS ? k : FASTF_COPY_BINS) - 1u]++;
-            if (k >= FASTF_COPY_BINS) hist[FASTF_COPY_BINS] += k;
-        }
-        if (c >= n_cells) continue;
-        reads[c] += k;
-        if (!nn) null_reads[c] += k;
-        else single[c] += k == 1;
-    }
-    return 0;
-}
-
-#define CELLS_COLUMNS_TAIL "seed\tvalid_reads\tnull_umi_reads\tumis\tsingleton_umis\tmedian_reads_per_cell\t" \
-    "copies_1\tcopies_2\tcopies_3\tcopies_4\tcopies_5\tcopies_6\tcopies_7\tcopies_8\tcopies_9\tcopies_10\tcopies_11\tcopies_12\tcopies_13\t" \
-    "copies_14\tcopies_15\tcopies_16\tcopies_17\tcopies_18\tcopies_19\tcopies_20\tcopies_21\tcopies_22\tcopies_23\tcopies_24\tcopies_25\t" \
-    "copies_26\tcopies_27\tcopies_28\tcopies_29\tcopies_30\tcopies_31\tcopies_32_plus\treads_copies_32_plus\n"
-const char *fastf_sweep_cells_header(void) { return "rate_cell\trate_depth\t" CELLS_COLUMNS_TAIL; }
-const char *fastf_cap_cells_header(void) { return "rate_cell\treads_per_cell\t" CELLS_COLUMNS_TAIL; }
-const char *fastf_level_cells_header(void) { return "rate_cell\tumi_cap\t" CELLS_COLUMNS_TAIL; }
-
-/* one row of sweep_cells.tsv (reads_per_cell == 0) or cap_cells.tsv (reads_per_cell >= 1), with its newline */
-int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_per_cell, uint32_t seed, const uint32_t *reads,
-                            const uint32_t *null_reads, const uint32_t *single, uint32_t n_cells, const uint64_t *hist, char *buf, size_t cap)
-{
-    if (!buf || !hist || (n_cells && (!reads || !null_reads || !single))) return sw_err("null argument");
-    uint64_t *tmp = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *tmp);
-    if (!tmp) return sw_err("out of memory");
-    uint64_t valid = 0, nulls = 0, singles = 0, umis = 0;
-    for (uint32_t k = 0; k < n_cells; k++) { tmp[k] = reads[k]; valid += reads[k]; nulls += null_reads[k]; singles += single[k]; }
-    const double med = median_u64(tmp, n_cells);
-    free(tmp);
-    for (uint32_t k = 0; k < FASTF_COPY_BINS; k++) umis += hist[k];
-    char second[32];
-    if (reads_per_cell) snprintf(second, sizeof second, "%llu", (unsigned long long)reads_per_cell);
-    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
-    int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%llu\t%llu\t%llu\t%llu\t%.1f", (double)rate_cell, second, seed, (unsigned long long)valid,
-                     (unsigned long long)nulls, (unsigned long long)umis, (unsigned long long)singles, med);
-    for (uint32_t k = 0; k <= FASTF_COPY_BINS && n >= 0 && (size_t)n < cap; k++) {
-        const int m = snprintf(buf + n, cap - (size_t)n, "\t%llu", (unsigned long long)hist[k]);
-        n = m < 0 ? -1 : n + m;
-    }
-    if (n < 0 || (size_t)n + 1 >= cap) return sw_err("summary row too long");
-    buf[n] = '\n'; buf[n + 1] = '\0';
-    return 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --fidelity: the host twin, the metrics, the rows                    */
-/* ------------------------------------------------------------------ */
-/* the host form of fastf_dev_fidelity: both COOs ascend by (cell, feature), so the partner of a point row lies behind the partner of
- * the row before it — one forward walk of the full rows */
-int fastf_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, uint64_t *sum_xy, uint64_t *sum_yy)
-{
-    if (!full || !point || (n_cells && (!sum_xy || !sum_yy)) || (point->nnz && (!point->feature || !point->cell || !point->count)) ||
-        (full->nnz && (!full->feature || !full->cell || !full->count))) return sw_err("null argument");
-    memset(sum_xy, 0, (size_t)n_cells * sizeof *sum_xy);
-    memset(sum_yy, 0, (size_t)n_cells * sizeof *sum_yy);
-    size_t j = 0;
-    for (size_t i = 0; i < point->nnz; i++) {
-        const uint64_t key = ((uint64_t)point->cell[i] << 32) | point->feature[i];
-        while (j < full->nnz && (((uint64_t)full->cell[j] << 32) | full->feature[j]) < key) j++;
-        if (j == full->nnz || full->cell[j] != point->cell[i] || full->feature[j] != point->feature[i])
-            return sw_err("fidelity: point row %zu (cell %u, feature %u) has no partner among the full rows (device error bits 0x%x)", i, point->cell[i],
-                          point->feature[i], FASTF_ERR_NO_PARTNER);
-        const uint32_t c = point->cell[i] - 1u;
-        if (c >= n_cells) continue;
-        sum_xy[c] += (uint64_t)full->count[j] * point->count[i];
-        sum_yy[c] += (uint64_t)point->count[i] * point->count[i];
-    }
-    return 0;
-}
-
-int fastf_fidelity_metrics(uint64_t umis_full, uint64_t umis, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features,
-                           double *pearson, double *cosine)
-{
-    typedef __int128 i128;
-    const i128 G = (i128)n_features;
-    const i128 num = G * (i128)sum_xy - (i128)umis_full * (i128)umis;
-    const i128 dx = G * (i128)sum_xx - (i128)umis_full * (i128)umis_full, dy = G * (i128)sum_yy - (i128)umis * (i128)umis;
-    int defined = 0;
-    if (dx > 0 && dy > 0) {                                 /* (never negative for counts over G genes: Cauchy-Schwarz) */
-        if (pearson) *pearson = (double)num / (sqrt((double)dx) * sqrt((double)dy));
-        defined |= 1;
-    }
-    if (sum_xx && sum_yy) {
-        if (cosine) *cosine = (double)sum_xy / (sqrt((double)sum_xx) * sqrt((double)sum_yy));
-        defined |= 2;
-    }
-    return defined;
-}
-
-const char *fastf_fidelity_header(void) { return "barcode\tumis_full\tumis\tgenes_full\tgenes\tsum_xx\tsum_yy\tsum_xy\tpearson\tcosine\n"; }
-#define FIDELITY_COLUMNS_TAIL "seed\tn_cells\tcells_defined\tmedian_pearson\tp10_pearson\tmean_pearson\tmedian_cosine\tumis_kept\tgenes_kept\n"
-const char *fastf_sweep_fidelity_header(void) { return "rate_cell\trate_depth\t" FIDELITY_COLUMNS_TAIL; }
-const char *fastf_cap_fidelity_header(void) { return "rate_cell\treads_per_cell\t" FIDELITY_COLUMNS_TAIL; }
-const char *fastf_level_fidelity_header(void) { return "rate_cell\tumi_cap\t" FIDELITY_COLUMNS_TAIL; }
-
-int fastf_fidelity_row(const char *barcode, uint64_t umis_full, uint64_t umis, uint64_t genes_full, uint64_t genes, uint64_t sum_xx,
-                       uint64_t sum_yy, uint64_t sum_xy, uint64_t n_features, char *buf, size_t cap)
-{
-    if (!barcode || !buf) return sw_err("null argument");
-    double p = 0.0, c = 0.0;
-    const int defined = fastf_fidelity_metrics(umis_full, umis, sum_xx, sum_yy, sum_xy, n_features, &p, &c);
-    char ps[40], cs[40];
-    if (defined & 1) snprintf(ps, sizeof ps, "%.6f", p); else snprintf(ps, sizeof ps, "NA");
-    if (defined & 2) snprintf(cs, sizeof cs, "%.6f", c); else snprintf(cs, sizeof cs, "NA");
-    const int n = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\t%s\n", barcode, (unsigned long long)umis_full, (unsigned long long)umis,
-                           (unsigned long long)genes_full, (unsigned long long)genes, (unsigned long long)sum_xx, (unsigned long long)sum_yy,
-                           (unsigned long long)sum_xy, ps, cs);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("fidelity row too long") : 0;
-}
-
-static int cmp_dbl(const void *a, const void *b) { const double x = *(const double *)a, y = *(const double *)b; return x < y ? -1 : x > y; }
-/* the rule of median_u64 on ascending values */
-static double median_sorted(const double *v, size_t n) { return (n & 1) ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0; }
-
-int fastf_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const uint64_t *umis_full,
-                               const uint64_t *umis, const uint32_t *genes_full, const uint32_t *genes, const uint64_t *sum_xx,
-                               const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_cells, uint64_t n_features, char *buf, size_t cap)
-{
-    if (!buf || (n_cells && (!umis_full || !umis || !genes_full || !genes || !sum_xx || !sum_yy || !sum_xy))) return sw_err("null argument");
-    double *pe = (double *)malloc(((size_t)n_cells + 1) * 2 * sizeof *pe), *co = pe ? pe + n_cells + 1 : NULL;
-    if (!pe) return sw_err("out of memory");
-    size_t nd = 0;
-    uint64_t su = 0, suf = 0, sg = 0, sgf = 0;
-    for (uint32_t k = 0; k < n_cells; k++) {
-        double p = 0.0, c = 0.0;
-        su += umis[k]; suf += umis_full[k]; sg += genes[k]; sgf += genes_full[k];
-        if (fastf_fidelity_metrics(umis_full[k], umis[k], sum_xx[k], sum_yy[k], sum_xy[k], n_features, &p, &c) & 1) { pe[nd] = p; co[nd] = c; nd++; }
-    }
-    char f[6][40];
-    if (nd) {
-        qsort(pe, nd, sizeof *pe, cmp_dbl);
-        qsort(co, nd, sizeof *co, cmp_dbl);
-        double sum = 0.0;
-        for (size_t k = 0; k < nd; k++) sum += pe[k];
-        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(pe, nd));
-        snprintf(f[1], sizeof f[1], "%.6f", pe[(size_t)floor(0.1 * (double)(nd - 1))]);
-        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
-        snprintf(f[3], sizeof f[3], "%.6f", median_sorted(co, nd));
-    } else for (int k = 0; k < 4; k++) snprintf(f[k], sizeof f[k], "NA");
-    free(pe);
-    if (suf) snprintf(f[4], sizeof f[4], "%.6f", (double)su / (double)suf); else snprintf(f[4], sizeof f[4], "NA");
-    if (sgf) snprintf(f[5], sizeof f[5], "%.6f", (double)sg / (double)sgf); else snprintf(f[5], sizeof f[5], "NA");
-    char second[32];
-    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
-    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, nd, f[0], f[1], f[2], f[3], f[4], f[5]);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --gene-fidelity: the host twin, the metrics, the rows, the ranking   */
-/* ------------------------------------------------------------------ */
-/* the host form of fastf_dev_partner_counts + fastf_dev_gene_moments + fastf_dev_gene_summary on both row sets: the walk of
- * fastf_fidelity_from_coo, every sum kept per gene */
-int fastf_gene_fidelity_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_features, uint64_t *sum_x, uint64_t *sum_y,
-                                 uint64_t *cells_full, uint64_t *cells, uint64_t *sum_xx, uint64_t *sum_yy, uint64_t *sum_xy)
-{
-    if (!full || !point || (n_features && (!sum_x || !sum_y || !cells_full || !cells || !sum_xx || !sum_yy || !sum_xy)) ||
-        (point->nnz && (!point->feature || !point->cell || !point->count)) || (full->nnz && (!full->feature || !full->cell || !full->count)))
-        return sw_err("null argument");
-    uint64_t *const all[7] = {sum_x, sum_y, cells_full, cells, sum_xx, sum_yy, sum_xy};
-    for (int k = 0; k < 7; k++) memset(all[k], 0, (size_t)n_features * sizeof(uint64_t));
-    for (size_t j = 0; j < full->nnz; j++) {
-        const uint32_t g = full->feature[j] - 1u;
-        if (g >= n_features) continue;
-        const uint64_t x = full->count[j];
-        sum_x[g] += x; cells_full[g] += x >= 1; sum_xx[g] += x * x;
-    }
-    size_t j = 0;
-    for (size_t i = 0; i < point->nnz; i++) {
-        const uint64_t key = ((uint64_t)point->cell[i] << 32) | point->feature[i];
-        while (j < full->nnz && (((uint64_t)full->cell[j] << 32) | full->feature[j]) < key) j++;
-        if (j == full->nnz || full->cell[j] != point->cell[i] || full->feature[j] != point->feature[i])
-            return sw_err("gene fidelity: point row %zu (cell %u, feature %u) has no partner among the full rows (device error bits 0x%x)", i, point->cell[i],
-                          point->feature[i], FASTF_ERR_NO_PARTNER);
-        const uint32_t g = point->feature[i] - 1u;
-        if (g >= n_features) continue;
-        const uint64_t y = point->count[i];
-        sum_y[g] += y; cells[g] += y >= 1; sum_yy[g] += y * y; sum_xy[g] += (uint64_t)full->count[j] * y;
-    }
-    return 0;
-}
-
-int fastf_gene_fidelity_metrics(uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t sum_xx, uint64_t sum_yy, uint64_t sum_xy,
-                                double *pearson, double *disp_full, double *disp)
-{
-    typedef __int128 i128;
-    const i128 n = (i128)n_cells;
-    const i128 num = n * (i128)sum_xy - (i128)sum_x * (i128)sum_y;
-    const i128 dx = n * (i128)sum_xx - (i128)sum_x * (i128)sum_x, dy = n * (i128)sum_yy - (i128)sum_y * (i128)sum_y;
-    int defined = 0;
-    if (dx > 0 && dy > 0) {                                 /* (never negative for counts over n cells: Cauchy-Schwarz) */
-        if (pearson) *pearson = (double)num / (sqrt((double)dx) * sqrt((double)dy));
-        defined |= 1;
-    }
-    if (n_cells >= 2 && sum_x) {
-        if (disp_full) *disp_full = (double)dx / ((double)(n_cells - 1) * (double)sum_x);
-        defined |= 2;
-    }
-    if (n_cells >= 2 && sum_y) {
-        if (disp) *disp = (double)dy / ((double)(n_cells - 1) * (double)sum_y);
-        defined |= 4;
-    }
-    return defined;
-}
-
-const char *fastf_gene_fidelity_header(void) { return "feature\tsum_x\tsum_y\tcells_full\tcells\tsum_xx\tsum_yy\tsum_xy\tpearson\tdisp_full\tdisp\n"; }
-#define GENE_FIDELITY_COLUMNS_TAIL "seed\tn_cells\tgenes_full\tgenes_defined\tmedian_pearson\tp10_pearson\tmean_pearson\thvg_k\thvg_overlap\n"
-const char *fastf_sweep_gene_fidelity_header(void) { return "rate_cell\trate_depth\t" GENE_FIDELITY_COLUMNS_TAIL; }
-const char *fastf_cap_gene_fidelity_header(void) { return "rate_cell\treads_per_cell\t" GENE_FIDELITY_COLUMNS_TAIL; }
-const char *fastf_level_gene_fidelity_header(void) { return "rate_cell\tumi_cap\t" GENE_FIDELITY_COLUMNS_TAIL; }
-
-int fastf_gene_fidelity_row(const char *feature, uint64_t n_cells, uint64_t sum_x, uint64_t sum_y, uint64_t cells_full, uint64_t cells, uint64_t sum_xx,
-                            uint64_t sum_yy, uint64_t sum_xy, char *buf, size_t cap)
-{
-    if (!feature || !buf) return sw_err("null argument");
-    double v[3] = {0.0, 0.0, 0.0};
-    const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x, sum_y, sum_xx, sum_yy, sum_xy, &v[0], &v[1], &v[2]);
-    char f[3][48];
-    for (int k = 0; k < 3; k++) if (defined & (1 << k)) snprintf(f[k], sizeof f[k], "%.6f", v[k]); else snprintf(f[k], sizeof f[k], "NA");
-    const int n = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\t%s\t%s\n", feature, (unsigned long long)sum_x, (unsigned long long)sum_y,
-                           (unsigned long long)cells_full, (unsigned long long)cells, (unsigned long long)sum_xx, (unsigned long long)sum_yy,
-                           (unsigned long long)sum_xy, f[0], f[1], f[2]);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("gene fidelity row too long") : 0;
-}
-
-/* the ranking of the highly variable genes: descending value, ties by ascending feature index */
-typedef struct { double v; uint32_t g; } hvg_item;
-static int cmp_hvg(const void *a, const void *b)
-{
-    const hvg_item *x = (const hvg_item *)a, *y = (const hvg_item *)b;
-    if (x->v != y->v) return x->v > y->v ? -1 : 1;
-    return x->g < y->g ? -1 : x->g > y->g;
-}
-
-/* the dispersion of (sum, sum_sq) is disp_full of fastf_gene_fidelity_metrics — and its disp, which is the same expression on the other
- * pair of sums.  Out of memory: UINT32_MAX, and *n_defined likewise */
-uint32_t fastf_hvg_rank(uint32_t n_cells, const uint64_t *sum, const uint64_t *sum_sq, uint32_t n_features, uint32_t *genes, uint32_t *n_defined)
-{
-    hvg_item *A = (hvg_item *)malloc(((size_t)n_features + 1) * sizeof *A);
-    if (!A) { if (n_defined) *n_defined = UINT32_MAX; return UINT32_MAX; }
-    size_t na = 0;
-    for (uint32_t g = 0; g < n_features; g++) {
-        double d = 0.0;
-        if (fastf_gene_fidelity_metrics(n_cells, sum[g], 0, sum_sq[g], 0, 0, NULL, &d, NULL) & 2) { A[na].v = d; A[na].g = g; na++; }
-    }
-    qsort(A, na, sizeof *A, cmp_hvg);
-    const uint32_t K = (uint32_t)(na < FASTF_HVG_TOP ? na : FASTF_HVG_TOP);
-    if (genes) for (uint32_t k = 0; k < K; k++) genes[k] = A[k].g;
-    if (n_defined) *n_defined = (uint32_t)na;
-    free(A);
-    return K;
-}
-
-int fastf_gene_fidelity_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, const uint64_t *sum_x,
-                                    const uint64_t *sum_y, const uint64_t *sum_xx, const uint64_t *sum_yy, const uint64_t *sum_xy, uint32_t n_features,
-                                    char *buf, size_t cap)
-{
-    if (!buf || (n_features && (!sum_x || !sum_y || !sum_xx || !sum_yy || !sum_xy))) return sw_err("null argument");
-    double *pe = (double *)malloc(((size_t)n_features + 1) * sizeof *pe);
-    uint32_t *A = (uint32_t *)malloc(2 * FASTF_HVG_TOP * sizeof *A), *B = A ? A + FASTF_HVG_TOP : NULL;
-    uint8_t *inA = (uint8_t *)calloc((size_t)n_features + 1, 1);
-    if (!pe || !A || !inA) { free(pe); free(A); free(inA); return sw_err("out of memory"); }
-    size_t nd = 0;
-    uint32_t genes_full = 0, nb = 0;
-    for (uint32_t g = 0; g < n_features; g++) {
-        double p = 0.0;
-        const int defined = fastf_gene_fidelity_metrics(n_cells, sum_x[g], sum_y[g], sum_xx[g], sum_yy[g], sum_xy[g], &p, NULL, NULL);
-        genes_full += sum_x[g] > 0;
-        if (defined & 1) pe[nd++] = p;
-    }
-    const size_t K = fastf_hvg_rank(n_cells, sum_x, sum_xx, n_features, A, NULL);
-    (void)fastf_hvg_rank(n_cells, sum_y, sum_yy, n_features, B, &nb);
-    const size_t KB = nb < K ? nb : K;
-    size_t both = 0;
-    if (K == UINT32_MAX || nb == UINT32_MAX) { free(pe); free(A); free(inA); return sw_err("out of memory"); }
-    for (size_t k = 0; k < K; k++) inA[A[k]] = 1;
-    for (size_t k = 0; k < KB; k++) both += inA[B[k]];
-    char f[4][40];
-    if (nd) {
-        qsort(pe, nd, sizeof *pe, cmp_dbl);
-        double sum = 0.0;
-        for (size_t k = 0; k < nd; k++) sum += pe[k];
-        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(pe, nd));
-        snprintf(f[1], sizeof f[1], "%.6f", pe[(size_t)floor(0.1 * (double)(nd - 1))]);
-        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
-    } else for (int k = 0; k < 3; k++) snprintf(f[k], sizeof f[k], "NA");
-    if (K) snprintf(f[3], sizeof f[3], "%.6f", (double)both / (double)K); else snprintf(f[3], sizeof f[3], "NA");
-    free(pe); free(A); free(inA);
-    char second[32];
-    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
-    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%zu\t%s\n", (double)rate_cell, second, seed, n_cells, genes_full, nd, f[0], f[1], f[2], K, f[3]);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --neighbors: the host twin, the rows                                 */
-/* ------------------------------------------------------------------ */
-void fastf_neighbors_pad(uint32_t n_cells, uint32_t K, uint32_t *n_pad, uint32_t *K_pad)
-{
-    if (n_pad) *n_pad = n_cells ? (n_cells + 127u) & ~127u : 128u;
-    if (K_pad) *K_pad = K ? (K + 31u) & ~31u : 32u;
-}
-
-int fastf_neighbors_check_norm(uint64_t max_norm)
-{
-    if (max_norm >> 42)
-        return sw_err("FASTF_ERR_NEIGHBOR_NORM: a cell's squared norm over the highly variable genes is %llu, 2^42 or more: the 128-bit order of --neighbors does not hold it",
-                      (unsigned long long)max_norm);
-    return 0;
-}
-
-int fastf_neighbors_slot_map(const uint32_t *genes, uint32_t K, uint32_t n_features, uint16_t *slot_map)
-{
-    if (!slot_map || (K && !genes)) return sw_err("null argument");
-    if (K > FASTF_HVG_TOP) return sw_err("neighbors: %u genes, at most %u", K, FASTF_HVG_TOP);
-    for (size_t f = 0; f <= n_features; f++) slot_map[f] = FASTF_NEIGHBORS_NONE;
-    for (uint32_t k = 0; k < K; k++) {
-        if (genes[k] >= n_features || slot_map[genes[k] + 1] != FASTF_NEIGHBORS_NONE) return sw_err("neighbors: gene %u of the set is outside the list or named twice", genes[k]);
-        slot_map[genes[k] + 1] = (uint16_t)k;
-    }
-    return 0;
-}
-
-uint32_t fastf_neighbors_shared(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb)
-{
-    uint32_t x = 0, y = 0, both = 0;
-    while (x < na && y < nb) {
-        const uint32_t va = a[x], vb = b[y];
-        both += va == vb; x += va <= vb; y += vb <= va;
-    }
-    return both;
-}
-
-typedef unsigned __int128 u128;
-/* j precedes l among the candidates of one query cell */
-static int nbr_precedes(uint64_t dj, uint64_t nj, uint32_t j, uint64_t dl, uint64_t nl, uint32_t l)
-{
-    const u128 a = (u128)dj * dj * nl, b = (u128)dl * dl * nj;
-    return a > b || (a == b && j < l);
-}
-static int cmp_u32(const void *a, const void *b) { const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b; return x < y ? -1 : x > y; }
-
-int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
-                             uint32_t *idx, uint32_t *cnt, uint64_t *norms)
-{
-    if (!m || !slot_map || (n_cells && (!idx || !cnt)) || (m->nnz && (!m->feature || !m->cell || !m->count))) return sw_err("null argument");
-    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return sw_err("neighbors: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
-    int rc = 1;
-    /* the rows with a slot, cell by cell (a counting sort by cell): slot and count */
-    size_t *start = (size_t *)calloc((size_t)n_cells + 2, sizeof *start);
-    uint64_t *nn = (uint64_t *)calloc((size_t)n_cells + 1, sizeof *nn), *vec = (uint64_t *)calloc(FASTF_HVG_TOP, sizeof *vec), *bd = (uint64_t *)malloc(FASTF_NEIGHBORS_MAX_K * sizeof *bd);
-    uint32_t *rs = NULL, *rv = NULL;
-    if (!start || !nn || !vec || !bd) { sw_err("out of memory"); goto done; }
-    size_t kept = 0;
-    for (size_t r = 0; r < m->nnz; r++) {
-        const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
-        if (c >= n_cells || f - 1u >= n_features || slot_map[f] >= FASTF_HVG_TOP) continue;
-        start[c + 2]++; kept++;
-    }
-    for (uint32_t c = 0; c < n_cells; c++) start[c + 2] += start[c + 1];
-    rs = (uint32_t *)malloc((kept + 1) * sizeof *rs); rv = (uint32_t *)malloc((kept + 1) * sizeof *rv);
-    if (!rs || !rv) { sw_err("out of memory"); goto done; }
-    uint64_t max_norm = 0;
-    for (size_t r = 0; r < m->nnz; r++) {
-        const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
-        if (c >= n_cells || f - 1u >= n_features || slot_map[f] >= FASTF_HVG_TOP) continue;
-        const size_t at = start[c + 1]++;
-        rs[at] = slot_map[f]; rv[at] = m->count[r];
-        const u128 sq = (u128)nn[c] + (u128)m->count[r] * m->count[r];
-        nn[c] = sq >> 64 ? UINT64_MAX : (uint64_t)sq;
-    }
-    for (uint32_t c = 0; c < n_cells; c++) if (nn[c] > max_norm) max_norm = nn[c];      /* (start[c] .. start[c + 1]: the rows of cell c) */
-    if (fastf_neighbors_check_norm(max_norm)) goto done;
-    for (uint32_t i = 0; i < n_cells; i++) {
-        uint32_t *const out = idx + (size_t)i * k;
-        uint32_t have = 0;
-        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] += rv[r];
-        for (uint32_t j = 0; j < n_cells; j++) {
-            if (j == i) continue;
-            uint64_t d = 0;
-            for (size_t r = start[j]; r < start[j + 1]; r++) d += vec[rs[r]] * rv[r];
-            if (!d) continue;
-            /* out[0 .. have) in the order of the definition, best first; a later cell never precedes an equal earlier one */
-            uint32_t at = have;
-            while (at > 0 && nbr_precedes(d, nn[j], j, bd[at - 1], nn[out[at - 1]], out[at - 1])) at--;
-            if (at >= k) continue;
-            const uint32_t last = have < k ? have : k - 1;
-            for (uint32_t s = last; s > at; s--) { out[s] = out[s - 1]; bd[s] = bd[s - 1]; }
-            out[at] = j; bd[at] = d;
-            if (have < k) have++;
-        }
-        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] = 0;
-        qsort(out, have, sizeof *out, cmp_u32);
-        for (uint32_t s = have; s < k; s++) out[s] = UINT32_MAX;
-        cnt[i] = have;
-        if (norms) norms[i] = nn[i];
-    }
-    rc = 0;
-done:
-    free(start); free(nn); free(vec); free(bd); free(rs); free(rv);
-    return rc;
-}
-
-const char *fastf_neighbors_header(void) { return "barcode\tk_full\tk_point\tshared\toverlap\n"; }
-#define NEIGHBORS_COLUMNS_TAIL "seed\tn_cells\thvg_k\tk\tcells_defined\tmedian_overlap\tp10_overlap\tmean_overlap\tmean_k_point\n"
-const char *fastf_sweep_neighbors_header(void) { return "rate_cell\trate_depth\t" NEIGHBORS_COLUMNS_TAIL; }
-const char *fastf_cap_neighbors_header(void) { return "rate_cell\treads_per_cell\t" NEIGHBORS_COLUMNS_TAIL; }
-const char *fastf_level_neighbors_header(void) { return "rate_cell\tumi_cap\t" NEIGHBORS_COLUMNS_TAIL; }
-
-int fastf_neighbors_row(const char *barcode, uint32_t k_full, uint32_t k_point, uint32_t shared, char *buf, size_t cap)
-{
-    if (!barcode || !buf) return sw_err("null argument");
-    char f[48];
-    if (k_full) snprintf(f, sizeof f, "%.6f", (double)shared / (double)k_full); else snprintf(f, sizeof f, "NA");
-    const int n = snprintf(buf, cap, "%s\t%u\t%u\t%u\t%s\n", barcode, k_full, k_point, shared, f);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("neighbors row too long") : 0;
-}
-
-int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
-                                const uint32_t *k_full, const uint32_t *k_point, const uint32_t *shared, char *buf, size_t cap)
-{
-    if (!buf || (n_cells && (!k_full || !k_point || !shared))) return sw_err("null argument");
-    double *ov = (double *)malloc(((size_t)n_cells + 1) * sizeof *ov);
-    if (!ov) return sw_err("out of memory");
-    size_t nd = 0;
-    uint64_t kp = 0;
-    for (uint32_t c = 0; c < n_cells; c++) {
-        kp += k_point[c];
-        if (k_full[c]) ov[nd++] = (double)shared[c] / (double)k_full[c];
-    }
-    char f[4][40];
-    if (nd) {
-        qsort(ov, nd, sizeof *ov, cmp_dbl);
-        double sum = 0.0;
-        for (size_t c = 0; c < nd; c++) sum += ov[c];
-        snprintf(f[0], sizeof f[0], "%.6f", median_sorted(ov, nd));
-        snprintf(f[1], sizeof f[1], "%.6f", ov[(size_t)floor(0.1 * (double)(nd - 1))]);
-        snprintf(f[2], sizeof f[2], "%.6f", sum / (double)nd);
-    } else for (int c = 0; c < 3; c++) snprintf(f[c], sizeof f[c], "NA");
-    if (n_cells) snprintf(f[3], sizeof f[3], "%.6f", (double)kp / (double)n_cells); else snprintf(f[3], sizeof f[3], "NA");
-    free(ov);
-    char second[32];
-    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
-    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, hvg_k, k, nd, f[0], f[1], f[2], f[3]);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --labels: the host twin, the rows                                    */
-/* ------------------------------------------------------------------ */
-int fastf_label_votes(const uint32_t *idx, const uint32_t *cnt, const uint8_t *lab, uint32_t n_cells, uint32_t k, uint32_t n_labels,
-                      uint8_t *pred, uint8_t *same, uint8_t *labelled, uint32_t *conf)
-{
-    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return sw_err("label votes: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
-    if (n_labels > FASTF_LABELS_MAX) return sw_err("label votes: %u labels, at most %u", n_labels, FASTF_LABELS_MAX);
-    if ((n_labels && !conf) || (n_cells && (!idx || !cnt || !lab || !pred || !same || !labelled))) return sw_err("null argument");
-    if (n_labels) memset(conf, 0, (size_t)n_labels * (n_labels + 1) * sizeof *conf);
-    for (uint32_t i = 0; i < n_cells; i++) {
-        uint32_t votes[FASTF_LABELS_MAX + 1] = {0}, all = 0, best = 0;
-        const uint32_t c = cnt[i] < k ? cnt[i] : k, own = lab[i] <= n_labels ? lab[i] : 0;
-        for (uint32_t s = 0; s < c; s++) {
-            const uint32_t j = idx[(size_t)i * k + s];
-            const uint32_t l = j < n_cells && lab[j] <= n_labels ? lab[j] : 0;
-            if (l) { votes[l]++; all++; }
-        }
-        for (uint32_t l = 1; l <= n_labels; l++) if (votes[l] > votes[best]) best = l;     /* (votes[0] == 0: a first l needs one vote; ties keep the smaller l) */
-        pred[i] = (uint8_t)best; same[i] = (uint8_t)(own ? votes[own] : 0); labelled[i] = (uint8_t)all;
-        if (own) conf[(size_t)(own - 1) * (n_labels + 1) + best]++;
-    }
-    return 0;
-}
-
-const char *fastf_labels_header(void) { return "barcode\tlabel\tpred_full\tpred_point\tsame_full\tlabelled_full\tsame_point\tlabelled_point\n"; }
-#define LABELS_COLUMNS_TAIL "seed\tn_cells\tk\tn_labels\tcells_labelled\tagree_full\tagree_point\taccuracy_full\taccuracy_point\tkept\tpurity_full\tpurity_point\n"
-const char *fastf_sweep_labels_header(void) { return "rate_cell\trate_depth\t" LABELS_COLUMNS_TAIL; }
-const char *fastf_cap_labels_header(void) { return "rate_cell\treads_per_cell\t" LABELS_COLUMNS_TAIL; }
-const char *fastf_level_labels_header(void) { return "rate_cell\tumi_cap\t" LABELS_COLUMNS_TAIL; }
-#define LABEL_CLASSES_COLUMNS_TAIL "seed\tlabel\tcells\tcorrect_full\tcorrect_point\tpredicted_full\tpredicted_point\n"
-const char *fastf_sweep_label_classes_header(void) { return "rate_cell\trate_depth\t" LABEL_CLASSES_COLUMNS_TAIL; }
-const char *fastf_cap_label_classes_header(void) { return "rate_cell\treads_per_cell\t" LABEL_CLASSES_COLUMNS_TAIL; }
-const char *fastf_level_label_classes_header(void) { return "rate_cell\tumi_cap\t" LABEL_CLASSES_COLUMNS_TAIL; }
-
-int fastf_labels_row(const char *barcode, const char *label, const char *pred_full, const char *pred_point, uint32_t same_full, uint32_t labelled_full,
-                     uint32_t same_point, uint32_t labelled_point, char *buf, size_t cap)
-{
-    if (!barcode || !label || !pred_full || !pred_point || !buf) return sw_err("null argument");
-    const int n = snprintf(buf, cap, "%s\t%s\t%s\t%s\t%u\t%u\t%u\t%u\n", barcode, label, pred_full, pred_point, same_full, labelled_full, same_point, labelled_point);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("labels row too long") : 0;
-}
-
-int fastf_label_confusion_header(const char *const *names, uint32_t n_labels, char *buf, size_t cap)
-{
-    if (!buf || (n_labels && !names)) return sw_err("null argument");
-    int n = snprintf(buf, cap, "label\tcells\tNA");
-    for (uint32_t l = 1; l <= n_labels && n >= 0 && (size_t)n < cap; l++) {
-        const int m = snprintf(buf + n, cap - (size_t)n, "\t%s", names[l]);
-        n = m < 0 ? m : n + m;
-    }
-    if (n >= 0 && (size_t)n < cap) { const int m = snprintf(buf + n, cap - (size_t)n, "\n"); n = m < 0 ? m : n + m; }
-    return (n < 0 || (size_t)n >= cap) ? sw_err("confusion header too long") : 0;
-}
-
-int fastf_label_confusion_row(const char *label, uint32_t cells, const uint32_t *conf_row, uint32_t n_labels, char *buf, size_t cap)
-{
-    if (!label || !conf_row || !buf) return sw_err("null argument");
-    int n = snprintf(buf, cap, "%s\t%u", label, cells);
-    for (uint32_t b = 0; b <= n_labels && n >= 0 && (size_t)n < cap; b++) {
-        const int m = snprintf(buf + n, cap - (size_t)n, "\t%u", conf_row[b]);
-        n = m < 0 ? m : n + m;
-    }
-    if (n >= 0 && (size_t)n < cap) { const int m = snprintf(buf + n, cap - (size_t)n, "\n"); n = m < 0 ? m : n + m; }
-    return (n < 0 || (size_t)n >= cap) ? sw_err("confusion row too long") : 0;
-}
-
-static void lab_ratio(char *f, size_t cap, uint64_t num, uint64_t den)
-{
-    if (den) snprintf(f, cap, "%.6f", (double)num / (double)den); else snprintf(f, cap, "NA");
-}
-static void lab_second(char *f, size_t cap, float rate_depth, uint64_t list_value)
-{
-    if (list_value) snprintf(f, cap, "%llu", (unsigned long long)list_value); else snprintf(f, cap, "%.3f", (double)rate_depth);
-}
-
-int fastf_labels_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t k, uint32_t n_labels,
-                             const uint8_t *lab, const uint8_t *pred_full, const uint8_t *pred_point, const uint8_t *same_full, const uint8_t *labelled_full,
-                             const uint8_t *same_point, const uint8_t *labelled_point, const uint32_t *conf_full, const uint32_t *conf_point,
-                             char *buf, size_t cap)
-{
-    if (!buf || (n_cells && (!lab || !pred_full || !pred_point || !same_full || !labelled_full || !same_point || !labelled_point)) ||
-        (n_labels && (!conf_full || !conf_point))) return sw_err("null argument");
-    uint64_t cells_labelled = 0, kept = 0, sf = 0, lf = 0, sp = 0, lp = 0, agree_full = 0, agree_point = 0;
-    for (uint32_t i = 0; i < n_cells; i++) {
-        if (!lab[i] || lab[i] > n_labels) continue;
-        cells_labelled++;
-        kept += pred_full[i] == lab[i] && pred_point[i] == lab[i];
-        sf += same_full[i]; lf += labelled_full[i]; sp += same_point[i]; lp += labelled_point[i];
-    }
-    for (uint32_t a = 1; a <= n_labels; a++) { agree_full += conf_full[(size_t)(a - 1) * (n_labels + 1) + a]; agree_point += conf_point[(size_t)(a - 1) * (n_labels + 1) + a]; }
-    char f[5][40], second[32];
-    lab_ratio(f[0], sizeof f[0], agree_full, cells_labelled); lab_ratio(f[1], sizeof f[1], agree_point, cells_labelled);
-    lab_ratio(f[2], sizeof f[2], kept, agree_full); lab_ratio(f[3], sizeof f[3], sf, lf); lab_ratio(f[4], sizeof f[4], sp, lp);
-    lab_second(second, sizeof second, rate_depth, list_value);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%llu\t%llu\t%llu\t%s\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, k, n_labels,
-                           (unsigned long long)cells_labelled, (unsigned long long)agree_full, (unsigned long long)agree_point, f[0], f[1], f[2], f[3], f[4]);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("summary row too long") : 0;
-}
-
-int fastf_label_classes_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *label, uint32_t a, uint32_t n_cells,
-                            uint32_t n_labels, const uint8_t *lab, const uint32_t *conf_full, const uint32_t *conf_point, char *buf, size_t cap)
-{
-    if (!buf || !label || !conf_full || !conf_point || (n_cells && !lab)) return sw_err("null argument");
-    if (a < 1 || a > n_labels) return sw_err("label classes: label %u, from 1 to %u", a, n_labels);
-    uint64_t cells = 0, pf = 0, pp = 0;
-    for (uint32_t i = 0; i < n_cells; i++) cells += lab[i] == a;
-    for (uint32_t r = 0; r < n_labels; r++) { pf += conf_full[(size_t)r * (n_labels + 1) + a]; pp += conf_point[(size_t)r * (n_labels + 1) + a]; }
-    char second[32];
-    lab_second(second, sizeof second, rate_depth, list_value);
-    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%s\t%llu\t%u\t%u\t%llu\t%llu\n", (double)rate_cell, second, seed, label, (unsigned long long)cells,
-                           conf_full[(size_t)(a - 1) * (n_labels + 1) + a], conf_point[(size_t)(a - 1) * (n_labels + 1) + a], (unsigned long long)pf, (unsigned long long)pp);
-    return (n < 0 || (size_t)n >= cap) ? sw_err("classes row too long") : 0;
-}
-
-/* ------------------------------------------------------------------ */
-/* --markers: the host twin, the ranks, the rows                        */
-/* ------------------------------------------------------------------ */
-int fastf_marker_auc(const void *planes, uint32_t n_planes, uint32_t n_cells, uint32_t K, const uint8_t *lab, uint32_t n_labels,
-                     uint64_t *s2u, uint32_t *det, uint64_t *sum, uint32_t *n_per_label)
-{
-    if (n_planes < 1 || n_planes > FASTF_MARKER_MAX_PLANES)
-        return sw_err("fastf_marker_auc: FASTF_ERR_MARKER_COUNT: %u planes — a count of 2^14 or more among the highly variable genes: the rank table of a gene does not fit the LDS", n_planes);
-    if (n_labels < 1 || n_labels > FASTF_LABELS_MAX) return sw_err("fastf_marker_auc: %u labels, from 1 to %u", n_labels, FASTF_LABELS_MAX);
-    if (K > 4096) return sw_err("fastf_marker_auc: %u genes, at most 4096", K);
-    if (!n_per_label || (K && (!s2u || !det || !sum)) || (n_cells && (!lab || (K && !planes)))) return sw_err("null argument");
-    const size_t words = (size_t)n_labels * K;
-    memset(n_per_label, 0, (size_t)n_labels * sizeof *n_per_label);
-    if (words) { memset(s2u, 0, words * sizeof *s2u); memset(det, 0, words * sizeof *det); memset(sum, 0, words * sizeof *sum); }
-    uint32_t n_pad = 0, K_pad = 0, n_lab = 0;
-    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
-    for (uint32_t i = 0; i < n_cells; i++) if (lab[i] - 1u < n_labels) { n_per_label[lab[i] - 1u]++; n_lab++; }
-    if (!n_cells || !K) return 0;
-    const uint32_t bins = n_planes == 1 ? 128u : 16384u;
-    const size_t plane_bytes = (size_t)n_pad * K_pad;
-    const uint8_t *const pl = (const uint8_t *)planes;
-    uint32_t *const E = (uint32_t *)malloc(((size_t)bins + n_cells) * sizeof *E), *const x = E ? E + bins : NULL;
-    if (!E) return sw_err("out of memory");
-    for (uint32_t g = 0; g < K; g++) {
-        memset(E, 0, bins * sizeof *E);
-        for (uint32_t i = 0; i < n_cells; i++) {
-            uint32_t v = pl[(size_t)i * K_pad + g] & 127u;
-            if (n_planes == 2) v |= (uint32_t)(pl[plane_bytes + (size_t)i * K_pad + g] & 127u) << 7;
-            x[i] = v;
-            if (lab[i] - 1u < n_labels) E[v]++;
-        }
-        uint32_t c = 0;
-        for (uint32_t v = 0; v < bins; v++) { const uint32_t e = E[v]; E[v] = 2u * c + e; c += e; }     /* 2 C(v) + E(v) */
-        for (uint32_t i = 0; i < n_cells; i++) {
-            const uint32_t a = lab[i] - 1u;
-            if (a >= n_labels) continue;
-            const size_t at = (size_t)a * K + g;
-            s2u[at] += E[x[i]];
-            if (x[i]) { det[at]++; sum[at] += x[i]; }
-        }
-        for (uint32_t a = 0; a < n_labels; a++) s2u[(size_t)a * K + g] -= (uint64_t)n_per_label[a] * n_per_label[a];
-    }
-    (void)n_lab;
-    free(E);
-    return 0;
-}
-
-typedef struct { uint64_t s2u; uint32_t gene, slot; } mk_key;
-static int cmp_mk_key(const void *a, const void *b)
-{
-    const mk_key *x = (const mk_key *)a, *y = (const mk_key *)b;
-    if (x->s2u != y->s2u) return x->s2u > y->s2u ? -1 : 1;
-    return x->gene < y->gene ? -1 : x->gene > y->gene;
-}
-
-int fastf_marker_rank(const uint64_t *s2u, const uint32_t *n_per_label, const uint32_t *genes, uint32_t K, uint32_t n_labels, uint32_t *rank)
-{
-    if (n_labels > FASTF_LABELS_MAX) return sw_err("fastf_marker_rank: %u labels, at most %u", n_labels, FASTF_LABELS_MAX);
-    if ((n_labels && !n_per_label) || (n_labels && K && (!s2u || !rank))) return sw_err("null argument");
-    if (!n_labels || !K) return 0;
-    uint64_t n_lab = 0;
-    for (uint32_t a = 0; a < n_labels; a++) n_lab += n_per_label[a];
-    mk_key *const key = (mk_key *)malloc((size_t)K * sizeof *key);
-    if (!key) return sw_err("out of memory");
-    for (uint32_t a = 0; a < n_labels; a++) {
-        uint32_t *const r = rank + (size_t)a * K;
-        if (!n_per_label[a] || n_lab == n_per_label[a]) { memset(r, 0, (size_t)K * sizeof *r); continue; }     /* no ranking */
-        for (uint32_t g = 0; g < K; g++) { key[g].s2u = s2u[(size_t)a * K + g]; key[g].gene = genes ? genes[g] : g; key[g].slot = g; }
-        qsort(key, K, sizeof *key, cmp_mk_key);
-        for (uint32_t k = 0; k < K; k++) r[key[k].slot] = k + 1;
-    }
-    free(key);
-    return 0;
-}
-
-const char *fastf_markers_header(void) { return "label\tgene\trank_full\trank_point\tauc_full\tauc_point\tdet_in_full\tdet_out_full\tdet_in_point\tdet_out_point\tmean_in_point\n"; }
-#define MARKERS_COLUMNS_TAIL "seed\tlabel\tn_in\tn_out\ttop\tkept\tauc_full_mean\tauc_point_mean\n"
-const char *fastf_sweep_markers_header(void) { return "rate_cell\trate_depth\t" MARKERS_COLUMNS_TAIL; }
-const char *fastf_cap_markers_header(void) { return "rate_cell\treads_per_cell\t" MARKERS_COLUMNS_TAIL; }
-const char *fastf_level_markers_header(void) { return "rate_cell\tumi_cap\t" MARKERS_COLUMNS_TAIL; }
-
-int fastf_markers_row(const char *label, const char *gene, uint32_t n_in, uint32_t n_out, uint32_t rank_full, uint32_t rank_point, uint64_t s2u_full,
-                      uint64_t s2u_point, uint32_t det_in_full, uint32_t det_out_full, uint32_t det_in_point, uint32_t det_out_point, uint64_t sum_in_point,
-                      char *buf, size_t cap)
-{
-    if (!label || !buf) return sw_err("null argument");
-    int n;
-    if (!gene || !n_in || !n_out) n = snprintf(buf, cap, "%s\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n", label);
-    else {
-        const double den = 2.0 * (double)n_in * (double)n_out;
-        n = snprintf(buf, cap, "%s\t%s\t%u\t%u\t%.6f\t%.6f\t%u\t%u\t%u\t%u\t%.6f\n", label, gene, rank_full, rank_point, (double)s2u_full / den, (double)s2u_point / den,
-                     det_in_full, det_out_full, det_in_point, det_out_point, (double)sum_in_point / (double)n_in);
-    }
-    return (n < 0 || (size_t)n >= cap) ? sw_err("markers row too long") : 0;
-}
-
-int fastf_markers_summary_rows(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, const char *const *names, uint32_t n_labels, uint32_t K,
-                               uint32_t top_n, const uint32_t *n_per_label, const uint32_t *rank_full, const uint32_t *rank_point, const uint64_t *s2u_full,
-                               const uint64_t *s2u_point, char *buf, size_t cap)
-{
-    if (!buf || (n_labels && (!names || !n_per_label)) || (n_labels && K && (!rank_full || !rank_point || !s2u_full || !s2u_point))) return sw_err("null argument");
-    const uint32_t top = top_n < K ? top_n : K;
-    uint64_t n_lab = 0, all_out = 0, all_top = 0, all_kept = 0;
-    double all_full = 0.0, all_point = 0.0;
-    char second[32], f[2][40];
-    size_t at = 0;
-    lab_second(second, sizeof second, rate_depth, list_value);
-    for (uint32_t a = 0; a < n_labels; a++) n_lab += n_per_label[a];
-    for (uint32_t a = 0; a <= n_labels; a++) {
-        int n;
-        if (a == n_labels) {
-            if (all_top) { snprintf(f[0], sizeof f[0], "%.6f", all_full / (double)all_top); snprintf(f[1], sizeof f[1], "%.6f", all_point / (double)all_top); }
-            else { snprintf(f[0], sizeof f[0], "NA"); snprintf(f[1], sizeof f[1], "NA"); }
-            n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\tall\t%llu\t%llu\t%llu\t%llu\t%s\t%s\n", (double)rate_cell, second, seed, (unsigned long long)n_lab,
-                         (unsigned long long)all_out, (unsigned long long)all_top, (unsigned long long)all_kept, f[0], f[1]);
-        } else {
-            const uint64_t n_in = n_per_label[a], n_out = n_lab - n_in;
-            all_out += n_out;
-            if (!n_in || !n_out || !top)
-                n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\t%s\t%llu\t%llu\t%u\tNA\tNA\tNA\n", (double)rate_cell, second, seed, names[a + 1], (unsigned long long)n_in,
-                             (unsigned long long)n_out, top);
-            else {
-                uint64_t kept = 0, sf = 0, sp = 0;
-                for (uint32_t g = 0; g < K; g++) {
-                    const size_t w = (size_t)a * K + g;
-                    if (rank_full[w] < 1 || rank_full[w] > top) continue;
-                    kept += rank_point[w] >= 1 && rank_point[w] <= top;
-                    sf += s2u_full[w]; sp += s2u_point[w];
-                }
-                const double den = 2.0 * (double)n_in * (double)n_out, mf = (double)sf / den, mp = (double)sp / den;
-                all_top += top; all_kept += kept; all_full += mf; all_point += mp;
-                n = snprintf(buf + at, cap - at, "%.3f\t%s\t%u\t%s\t%llu\t%llu\t%u\t%llu\t%.6f\t%.6f\n", (double)rate_cell, second, seed, names[a + 1], (unsigned long long)n_in,
-                             (unsigned long long)n_out, top, (unsigned long long)kept, mf / (double)top, mp / (double)top);
-            }
-        }
-        if (n < 0 || (size_t)n >= cap - at) return sw_err("markers summary rows too long");
-        at += (size_t)n;
     }
     return 0;
 }
@@ -965,7 +116,7 @@ int fastf_markers_summary_rows(float rate_cell, float rate_depth, uint64_t list_
 static int read_matrix(const char *path, uint64_t counters[3], uint32_t *n_features, uint32_t *n_cells, fastf_coo_t *coo, uint32_t **rows_out)
 {
     gzFile g = gzopen(path, "rb");
-    if (!g) return sw_err("cannot read %s back", path);
+    if (!g) return fastf_res_err("cannot read %s back", path);
     char line[8192];
     int rc = 1, have_dims = 0;
     size_t nnz = 0, at = 0;
@@ -981,18 +132,18 @@ static int read_matrix(const char *path, uint64_t counters[3], uint32_t *n_featu
         }
         if (!have_dims) {
             size_t nf, nb;
-            if (sscanf(line, "%zu %zu %zu", &nf, &nb, &nnz) != 3) { sw_err("%s: no dimension line", path); goto done; }
+            if (sscanf(line, "%zu %zu %zu", &nf, &nb, &nnz) != 3) { fastf_res_err("%s: no dimension line", path); goto done; }
             *n_features = (uint32_t)nf; *n_cells = (uint32_t)nb;
             rows = (uint32_t *)malloc((nnz ? nnz : 1) * 12);
-            if (!rows) { sw_err("out of memory"); goto done; }
+            if (!rows) { fastf_res_err("out of memory"); goto done; }
             have_dims = 1;
             continue;
         }
         unsigned f, c, k;
-        if (at >= nnz || sscanf(line, "%u %u %u", &f, &c, &k) != 3) { sw_err("%s: malformed row", path); goto done; }
+        if (at >= nnz || sscanf(line, "%u %u %u", &f, &c, &k) != 3) { fastf_res_err("%s: malformed row", path); goto done; }
         rows[at] = f; rows[nnz + at] = c; rows[2 * nnz + at] = k; at++;
     }
-    if (!have_dims || at != nnz) { sw_err("%s: %zu rows of %zu", path, at, nnz); goto done; }
+    if (!have_dims || at != nnz) { fastf_res_err("%s: %zu rows of %zu", path, at, nnz); goto done; }
     coo->feature = rows; coo->cell = rows + nnz; coo->count = rows + 2 * nnz; coo->nnz = nnz;
     *rows_out = rows; rows = NULL;
     rc = 0;
@@ -1035,21 +186,21 @@ static int sweep_point_by_point(const res_job_t *job, int summary_only, res_tabl
                 for (int k = 0; k < 3; k++) { snprintf(path, sizeof path, "%s/%s", dir, files[k]); unlink(path); }
                 rmdir(dir);
             }
-            if (brc) { if (!strstr(fastf_last_error(), "bam2db")) sw_err("bam2db failed at point %s: %s", name, fastf_last_error()); goto done; }
+            if (brc) { if (!strstr(fastf_last_error(), "bam2db")) fastf_res_err("bam2db failed at point %s: %s", name, fastf_last_error()); goto done; }
             if (prc) goto done;
             uint64_t *upc = (uint64_t *)calloc((size_t)n_cells + 1, sizeof *upc);
             uint32_t *gpc = (uint32_t *)calloc((size_t)n_cells + 1, sizeof *gpc);
             uint64_t umis = 0;
             char row[512];
             prc = !upc || !gpc || fastf_sweep_cells_from_coo(&coo, n_cells, upc, gpc, &umis) ||
-                  summary_row_(rc_list[i], rd_list[j], seed, counters, coo.nnz, umis, upc, gpc, n_cells, row, sizeof row, metrics) ||
+                  fastf_sweep_row_(rc_list[i], rd_list[j], seed, counters, coo.nnz, umis, upc, gpc, n_cells, row, sizeof row, metrics) ||
                   fastf_res_reps_point(P, j, k, n_cells, metrics);
             free(upc); free(gpc);
             if (!prc && G->on) {
                 char grow[256];
                 uint32_t *cpg = (uint32_t *)calloc((size_t)n_features + 1, sizeof *cpg);
                 uint64_t *upg = (uint64_t *)calloc((size_t)n_features + 1, sizeof *upg);
-                prc = !cpg || !upg || (n_features != GL.n_features && sw_err("%s names %u features, the list has %zu", name, n_features, GL.n_features)) ||
+                prc = !cpg || !upg || (n_features != GL.n_features && fastf_res_err("%s names %u features, the list has %zu", name, n_features, GL.n_features)) ||
                       fastf_sweep_genes_from_coo(&coo, n_features, cpg, upg) ||
                       fastf_genes_summary_row(rc_list[i], rd_list[j], 0, seed, cpg, upg, n_features, grow, sizeof grow) ||
                       fastf_res_genes_point(G, &GL, name, summary_only ? NULL : dir, grow, cpg, upg) ||
@@ -1088,18 +239,18 @@ static int sweep_pair_begin(const res_pair_t *p, void **ctx)
 {
     res_rate_t *S = p->S;
     const uint32_t n_r = p->job->n_list;
-    const uint32_t n_planes = n_r + (p->Fd->full ? 1u : 0u);   /* --fidelity, --gene-fidelity: one more plane behind the grid's, every hit kept */
+    const uint32_t n_planes = n_r + (res_cfg_full(&S->cfg) ? 1u : 0u);   /* --fidelity, --gene-fidelity: one more plane behind the grid's, every hit kept */
     sweep_pair_t *c = (sweep_pair_t *)calloc(1, sizeof *c);
-    if (!(*ctx = c) || !(c->thr = (uint64_t *)malloc(n_planes * sizeof *c->thr))) return sw_err("out of memory");
+    if (!(*ctx = c) || !(c->thr = (uint64_t *)malloc(n_planes * sizeof *c->thr))) return fastf_res_err("out of memory");
     const double tt = fastf_res_now();
     c->plane_words = ((S->H + 63) / 64) * 2 + 64;           /* (zeroed slack behind each plane: K1b reads a unit's words unconditionally) */
     if (!(c->d_planes = fastf_devmem_alloc(p->device, (size_t)n_planes * c->plane_words * 4)) || fastf_devmem_zero(c->d_planes, (size_t)n_planes * c->plane_words * 4)) return RES_FAIL;
     for (uint32_t j = 0; j < n_r; j++) c->thr[j] = fastf_draw_threshold(p->job->rates_depth[j]);
-    if (p->Fd->full) c->thr[n_r] = (uint64_t)1 << 32;
+    if (res_cfg_full(&S->cfg)) c->thr[n_r] = (uint64_t)1 << 32;
     if (fastf_dev_mt_decisions_multi(S->e, p->seed, p->L->mt_skip, S->H, c->thr, n_planes, (uint32_t *)c->d_planes, c->plane_words, NULL)) return RES_FAIL;
     p->T->planes += fastf_res_now() - tt;
     /* the full rows of the pair, once */
-    return p->Fd->full ? fastf_res_full_run(S, (const uint32_t *)c->d_planes + (size_t)n_r * c->plane_words, p->T) : RES_OK;
+    return res_cfg_full(&S->cfg) ? fastf_res_full_run(S, (const uint32_t *)c->d_planes + (size_t)n_r * c->plane_words, p->T) : RES_OK;
 }
 
 static int sweep_point_plane(void *ctx, const res_pair_t *p, uint32_t j, const char *point_name, const uint32_t **d_plane)
@@ -1114,13 +265,11 @@ static int sweep_point_row(void *ctx, const res_pair_t *p, uint32_t j, const uin
 {
     const res_rate_t *S = p->S;
     (void)ctx;
-    return summary_row_(p->rate_cell, p->job->rates_depth[j], p->seed, counters, nnz, S->buf.h_upc.u64[S->n_cells], S->buf.h_upc.u64, S->buf.h_gpc.u32, S->n_cells, row, cap, metrics);
+    return fastf_sweep_row_(p->rate_cell, p->job->rates_depth[j], p->seed, counters, nnz, S->buf.h_upc.u64[S->n_cells], S->buf.h_upc.u64, S->buf.h_gpc.u32, S->n_cells, row, cap, metrics);
 }
 
 static const res_verb_t sweep_verb = {
-    .name = "sweep",
-    .header = { fastf_sweep_header, fastf_sweep_genes_header, fastf_sweep_cells_header, fastf_sweep_fidelity_header, fastf_sweep_gene_fidelity_header, fastf_sweep_neighbors_header,
-                fastf_sweep_labels_header, fastf_sweep_label_classes_header, fastf_sweep_markers_header, fastf_sweep_reps_header, fastf_sweep_genes_reps_header },
+    .name = "sweep", .index = VERB_SWEEP, .header = fastf_sweep_header,
     .planes_words = "planes", .fid_before = "", .fid_after = " full-depth points",
     .pair_begin = sweep_pair_begin, .point_plane = sweep_point_plane, .point_row = sweep_point_row, .pair_end = sweep_pair_end,
     .point_by_point = sweep_point_by_point,
@@ -1140,9 +289,9 @@ int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, cons
 /* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
 int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds)
 {
-    if (!seeds || n_seeds < 1 || n_seeds > FASTF_MAX_SEEDS) return sw_err("%s: a replicate run takes 1 to %u seeds", verb, FASTF_MAX_SEEDS);
+    if (!seeds || n_seeds < 1 || n_seeds > FASTF_MAX_SEEDS) return fastf_res_err("%s: a replicate run takes 1 to %u seeds", verb, FASTF_MAX_SEEDS);
     for (uint32_t k = 0; k < n_seeds; k++)
-        for (uint32_t j = 0; j < k; j++) if (seeds[j] == seeds[k]) return sw_err("%s: seed %u is listed twice", verb, seeds[k]);
+        for (uint32_t j = 0; j < k; j++) if (seeds[j] == seeds[k]) return fastf_res_err("%s: seed %u is listed twice", verb, seeds[k]);
     return 0;
 }
 

@@ -95,3 +95,21 @@ def test_resident_block_layouts_hold_at_their_boundary_counts(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
     assert "layouts hold" in r.stdout
+
+
+def test_grid_tables_and_point_files_hold_on_hand_filled_views(tmp_path):
+    """tools/res_tables_check.c under AddressSanitizer + UBSan: the tables and point files of a grid run (res_tables.c, grid_rows.c; no
+    device code, no Python in the process) driven through open, point and close on host views filled by hand — every table and point
+    file is its header plus the rows of the public row functions, at 0, 1 and 5 cells, 0, 1 and 4 features, 1 and 3 labels and
+    --markers N on either side of hvg_k; summary only writes no point file, a failed run leaves nothing, a rename that cannot succeed
+    fails the close by the file's name and leaves no table, and every subset of the comparisons opens its own files only"""
+    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "fastf_amd", "csrc"), "-I" + os.path.join(ROOT, "tools")]
+    exe, work = tmp_path / "res_tables_check", tmp_path / "work"
+    work.mkdir()
+    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined"] + inc + [os.path.join(ROOT, "tools", "res_tables_check.c")] +
+                          [os.path.join(ROOT, "fastf_amd", "csrc", f) for f in ("res_tables.c", "grid_rows.c")] + SRC + ["-lz", "-lpthread", "-lm", "-o", str(exe)])
+    r = subprocess.run([str(exe), str(work)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    assert "tables hold: 36 runs" in r.stdout
+    assert os.listdir(work) == []

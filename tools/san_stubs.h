@@ -8,8 +8,14 @@
 #ifndef SAN_PINNED_REGISTER_RC
 #define SAN_PINNED_REGISTER_RC 1      /* fastf_pinned_register: 1 = "cannot pin" (the reader harness), 0 = pretend it worked */
 #endif
+#ifdef SAN_KEEP_ERROR                 /* a harness that reads the message back (tools/res_tables_check.c) */
+static char san_error_[512];
+void fastf_set_error_(const char *m) { snprintf(san_error_, sizeof san_error_, "%s", m); }
+const char *fastf_last_error(void) { return san_error_; }
+#else
 void fastf_set_error_(const char *m) { fprintf(stderr, "err: %s\n", m); }
 const char *fastf_last_error(void) { return ""; }
+#endif
 /* the HIP side of the library is not part of this build: no device, nothing pinned */
 fastf_gpuinf_t *fastf_gpuinf_create(int d) { (void)d; return NULL; }
 int fastf_gpuinf_reserve(fastf_gpuinf_t *g, size_t w, size_t c, size_t n) { (void)g; (void)w; (void)c; (void)n; return 1; }
