@@ -148,7 +148,7 @@ ABI_SYMBOLS = [
     # co-expression partners against full depth
     "fastf_coexpr_header", "fastf_sweep_coexpr_header", "fastf_cap_coexpr_header", "fastf_level_coexpr_header",
     "fastf_coexpr_check_range", "fastf_coexpr_check_gram", "fastf_coexpr_row", "fastf_coexpr_summary_row", "fastf_coexpr_from_coo",
-    "fastf_coexpr_select",
+    "fastf_coexpr_select", "fastf_coexpr_pad", "fastf_coexpr_work_bytes", "fastf_dev_coexpr_sums", "fastf_dev_coexpr_select",
 ]
 
 
@@ -439,6 +439,12 @@ def lib():
     L.fastf_coexpr_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
     L.fastf_coexpr_from_coo.argtypes = [C.POINTER(Coo), u32, vp, u32, u32, u32, vp, vp, vp, vp]
     L.fastf_coexpr_select.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+    L.fastf_coexpr_pad.argtypes = [u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.fastf_coexpr_pad.restype = None
+    L.fastf_coexpr_work_bytes.argtypes = [u32, u32, u32]
+    L.fastf_coexpr_work_bytes.restype = sz
+    L.fastf_dev_coexpr_sums.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, sz, vp, vp, vp]
+    L.fastf_dev_coexpr_select.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
     L.bam2db.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_float, C.c_uint]
     _lib = L
     return L

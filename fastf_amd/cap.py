@@ -14,6 +14,7 @@ CELLS = 8             # FASTF_CAP_CELLS
 FIDELITY = 32         # FASTF_CAP_FIDELITY
 GENE_FIDELITY = 128   # FASTF_CAP_GENE_FIDELITY
 NEIGHBORS = 512       # FASTF_CAP_NEIGHBORS
+COEXPRESSION = 4096   # FASTF_CAP_COEXPRESSION
 COLUMNS = ("rate_cell", "reads_per_cell", "seed", "n_cells", "total_reads", "sampled_reads", "sampled_valid_reads", "nnz", "umis",
            "saturation", "median_umis_per_cell", "median_genes_per_cell", "hits", "cells_capped", "realised_depth")
 GENES_COLUMNS = ("rate_cell", "reads_per_cell", "seed", "genes_detected", "genes_min_cells_3", "genes_min_cells_10", "max_gene_umis")
@@ -27,12 +28,14 @@ NEIGHBORS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.NEIGHBORS_TAIL_COLU
 LABELS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.LABELS_TAIL_COLUMNS
 LABEL_CLASSES_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.LABEL_CLASSES_TAIL_COLUMNS
 MARKERS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.MARKERS_TAIL_COLUMNS
+COEXPRESSION_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.COEXPRESSION_TAIL_COLUMNS
+read_point_coexpression = _sweep.read_point_coexpression
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one function for both verbs)
 
 
 def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
     rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
     out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
@@ -46,21 +49,21 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     if markers is not None:
         _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
                                                 seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                               n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                               n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
                                                seed % (1 << 32), enc(labels)))
         return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
 def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
@@ -71,17 +74,17 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     if markers is not None:
         _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
                                                 None if labels is None else enc(labels), _sweep._markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                               _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0, enc(labels)))
+                                               _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
         return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     _lib.check(_lib.lib().fastf_cap_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                          n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                         _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                         _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
@@ -121,6 +124,11 @@ def gene_fidelity_summary_row(rate_cell, reads_per_cell, seed, n_cells, sum_x, s
 def read_neighbors_table(path):
     """the rows of cap_neighbors.tsv as dicts of strings"""
     return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def read_coexpression_table(path):
+    """the rows of cap_coexpr.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, COEXPRESSION_COLUMNS)
 
 
 def neighbors_header(verb: str = "cap") -> str:

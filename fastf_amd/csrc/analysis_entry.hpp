@@ -9,6 +9,7 @@
 #include "fidelity_kernels.hpp"
 #include "gene_fidelity_kernels.hpp"
 #include "neighbors_kernels.hpp"
+#include "coexpr_kernels.hpp"
 #include "labels_kernels.hpp"
 #include "markers_kernels.hpp"
 
@@ -249,6 +250,102 @@ extern "C" int fastf_dev_neighbors_shared(fastf_engine_t* e, const uint32_t* d_i
     hipLaunchKernelGGL(nbr_shared_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, d_idx_a, d_cnt_a, d_idx_b, d_cnt_b, n_cells, k, d_shared);
     HIP_OK(hipGetLastError());
     dbg_sync(s, "neighbors shared");
+    return 0;
+} FASTF_CATCH_INT
+
+static_assert(COEX_MAX_K == FASTF_COEXPR_MAX_K && COEX_MAX_PLANES == FASTF_COEXPR_MAX_PLANES && COEX_MAX_GENES == FASTF_COEXPR_MAX_GENES && COEX_CHUNK == FASTF_COEXPR_CHUNK,
+              "the limits of the co-expression kernels and the ABI's");
+
+// --coexpression: the chunk of cells in effect — FASTF_COEXPR_CHUNK=<cells> lowers the default: 32 .. default - 1 is rounded down to a
+// multiple of 32, every other value is ignored (read at each call, it changes no result) — and with it the padded shape of the gene-major planes (coex_pad)
+static u32 coex_chunk_knob() {
+    const char* ck = getenv("FASTF_COEXPR_CHUNK");
+    const long v = ck ? atol(ck) : 0;
+    return v >= 32 && v < (long)COEX_CHUNK ? (u32)v & ~31u : COEX_CHUNK;
+}
+extern "C" void fastf_coexpr_pad(uint32_t n_cells, uint32_t K, uint32_t* K_pad, uint32_t* n_pad, uint32_t* chunk) FASTF_TRY {
+    u32 kp = 0, np = 0, ce = 0;
+    coex_pad(n_cells, K, coex_chunk_knob(), &kp, &np, &ce);
+    if (K_pad) *K_pad = kp;
+    if (n_pad) *n_pad = np;
+    if (chunk) *chunk = ce;
+} FASTF_CATCH_(return)
+extern "C" size_t fastf_coexpr_work_bytes(uint32_t n_cells, uint32_t K, uint32_t planes) FASTF_TRY {
+    u32 kp = 0, np = 0, ce = 0;
+    coex_pad(n_cells, K, coex_chunk_knob(), &kp, &np, &ce);
+    return (size_t)planes * kp * np;
+} FASTF_CATCH_(return 0)
+
+// --coexpression: the sums of one row set (coexpr_kernels.hpp).  The rows and d_slot_map as fastf_dev_neighbor_planes takes them, `planes`
+// what that call returned for them.  d_work: fastf_coexpr_work_bytes(n_cells, K, planes) bytes, 16-byte aligned — the gene-major planes,
+// zeroed and filled here.  d_D: u64[K * K], D_gh = sum_i m_ig m_ih, dense, row-major; d_S: u64[K]; both zeroed here.  fastf_coexpr_check_gram
+// refuses (n_cells, planes) whose D would leave 64 bits before anything is launched.  The dot products come from the i8 MFMA, under
+// FASTF_COEXPR_MFMA=0 from ordinary integer instructions: the same numbers.  Stream-ordered.
+extern "C" int fastf_dev_coexpr_sums(fastf_engine_t* e, const uint32_t* d_feature, const uint32_t* d_cell, const uint32_t* d_count, const uint64_t* d_nnz,
+                                     const uint16_t* d_slot_map, uint32_t n_features, uint32_t n_cells, uint32_t K, uint32_t planes, void* d_work,
+                                     size_t work_bytes, uint64_t* d_D, uint64_t* d_S, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_nnz, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (K > COEX_MAX_GENES) return set_err("fastf_dev_coexpr_sums: %u genes, at most %u", K, COEX_MAX_GENES);
+    if (n_cells > 0xFFFE0000u) return set_err("fastf_dev_coexpr_sums: %u cells: the padded row of a gene does not fit 32 bits", n_cells);
+    if (fastf_coexpr_check_gram(n_cells, planes)) return 1;
+    if (!K) return 0;
+    if (!d_D || !d_S) return set_err("fastf_dev_coexpr_sums: null argument");
+    u32 K_pad = 0, n_pad = 0, chunk = 0;
+    coex_pad(n_cells, K, coex_chunk_knob(), &K_pad, &n_pad, &chunk);
+    const size_t need = (size_t)planes * K_pad * n_pad;
+    if (need > work_bytes) return set_err("fastf_dev_coexpr_sums: %u planes of %u x %u bytes need %zu bytes, the buffer has %zu", planes, K_pad, n_pad, need, work_bytes);
+    if (!d_work || ((uintptr_t)d_work & 15)) return set_err("fastf_dev_coexpr_sums: the work buffer is 16-byte aligned");
+    HIP_OK(hipMemsetAsync(d_D, 0, (size_t)K * K * sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(d_S, 0, (size_t)K * sizeof(u64), s));
+    if (!n_cells || !d_feature || !d_cell || !d_count || !d_slot_map) return 0;      // (no row buffer: sums of nothing)
+    HIP_OK(hipMemsetAsync(d_work, 0, need, s));
+    hipLaunchKernelGGL(coex_planes_kernel, dim3(4 * e->grid_cus), dim3(256), 0, s, d_feature, d_cell, d_count, (const u64*)d_nnz, d_slot_map, n_features,
+                       n_cells, K, K_pad, n_pad, planes, (unsigned char*)d_work);
+    HIP_OK(hipGetLastError());
+    const char* mf = getenv("FASTF_COEXPR_MFMA");
+    const bool mfma = !(mf && mf[0] == '0');
+    static constexpr decltype(&coex_gram_kernel<1, false>) gram[COEX_MAX_PLANES][2] = {   // [planes - 1][mfma]
+        {coex_gram_kernel<1, false>, coex_gram_kernel<1, true>}, {coex_gram_kernel<2, false>, coex_gram_kernel<2, true>}, {coex_gram_kernel<3, false>, coex_gram_kernel<3, true>}};
+    const u32 n32 = (n_cells + 31u) & ~31u, n_tiles = K_pad / COEX_TILE, n_chunks = n_pad / chunk;
+    const u64 n_pairs = (u64)n_tiles * (n_tiles + 1) / 2, n_items = n_pairs * n_chunks, groups = (n_items + COEX_WAVES - 1) / COEX_WAVES;
+    if (groups > 0x7FFFFFFFull) return set_err("fastf_dev_coexpr_sums: %llu tiles of %u cells are more than one launch takes", (unsigned long long)n_items, chunk);
+    hipLaunchKernelGGL(gram[planes - 1][mfma], dim3((u32)groups), dim3(COEX_THREADS), 0, s, (const unsigned char*)d_work, K, K_pad, n_pad, n32, chunk, n_tiles,
+                       n_pairs, n_items, (u64*)d_D);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(coex_sums_kernel, dim3(std::min<u32>((K + 3) / 4, 8 * e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_work, K, K_pad, n_pad, n32, planes,
+                       (u64*)d_S);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "coexpr sums");
+    return 0;
+} FASTF_CATCH_INT
+
+// --coexpression: the partner sets of D and S over n_cells cells (coex_var_kernel, coex_select_kernel).  V_h = n D_hh - S_h^2 goes into the
+// engine's own buffer; the largest D_hh is read back and fastf_coexpr_check_range refuses n_cells * max Q >= 2^63 before the selection is
+// launched.  Then d_idx[g * k + s], s < d_cnt[g], are the partners of gene g (slots, ascending; the other slots 0xFFFFFFFF), k from 1 to
+// 64, K at most 4096.  Synchronises the stream once, before the selection.  Not re-entrant per engine: V and the maximum share one engine buffer.
+extern "C" int fastf_dev_coexpr_select(fastf_engine_t* e, const uint64_t* d_D, const uint64_t* d_S, uint32_t n_cells, uint32_t K, uint32_t k,
+                                       uint32_t* d_idx, uint32_t* d_cnt, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > COEX_MAX_K) return set_err("fastf_dev_coexpr_select: k = %u, from 1 to %u", k, COEX_MAX_K);
+    if (K > COEX_MAX_GENES) return set_err("fastf_dev_coexpr_select: %u genes, at most %u", K, COEX_MAX_GENES);
+    if (!K) return 0;
+    if (!d_D || !d_S || !d_idx || !d_cnt) return set_err("fastf_dev_coexpr_select: null argument");
+    if (e->an.d_coex.ensure(64 + (size_t)COEX_MAX_GENES * sizeof(u64))) return 1;
+    u64* const d_max = (u64*)e->an.d_coex.p;
+    u64* const d_V = d_max + 8;
+    HIP_OK(hipMemsetAsync(d_max, 0, 64, s));
+    hipLaunchKernelGGL(coex_var_kernel, dim3((K + 255) / 256), dim3(256), 0, s, (const u64*)d_D, (const u64*)d_S, n_cells, K, d_V, d_max);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 max_q = 0;
+    if (copy_d2h(&max_q, d_max, sizeof max_q)) return 1;
+    if (fastf_coexpr_check_range(n_cells, max_q)) return 1;
+    hipLaunchKernelGGL(coex_select_kernel, dim3((K + COEX_SEL_THREADS - 1) / COEX_SEL_THREADS), dim3(COEX_SEL_THREADS), (size_t)coex_select_lds(k), s,
+                       (const u64*)d_D, (const u64*)d_S, (const u64*)d_V, n_cells, K, k, d_idx, d_cnt);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "coexpr select");
     return 0;
 } FASTF_CATCH_INT
 

@@ -13,7 +13,7 @@
 #include <string.h>
 #include <unistd.h>
 
-#define GRID_FLAGS (FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS)
+#define GRID_FLAGS (FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS | FASTF_SWEEP_COEXPRESSION)
 
 int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path)
 {
@@ -37,6 +37,7 @@ static int grid_refuse(const res_verb_t *V, const res_job_t *job, int labels, in
     if (fallback && cells_first && (f & FASTF_SWEEP_CELLS)) opt = "--cells";
     else if (labels) opt = "--labels";
     else if (f & FASTF_SWEEP_NEIGHBORS) opt = "--neighbors";
+    else if (f & FASTF_SWEEP_COEXPRESSION) opt = "--coexpression";
     else if (fallback && (f & FASTF_SWEEP_FIDELITY) && (f & FASTF_SWEEP_GENE_FIDELITY)) { opt = "--fidelity and --gene-fidelity"; needs = "need"; }
     else if (fallback && (f & FASTF_SWEEP_FIDELITY)) opt = "--fidelity";      /* (the full rows live on the device alone: bam2db() point by point has none) */
     else if (f & FASTF_SWEEP_GENE_FIDELITY) opt = "--gene-fidelity";
@@ -195,6 +196,8 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
         if (res_cmp_on(Fd, CMP_LABELS)) fprintf(stderr, "[%s] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", v, fastf_labels_count(Fd->labels),
                                 (unsigned long long)fastf_labels_unknown(Fd->labels), nbr ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (nbr ? 0.0 : T.neighbors));
         if (nbr) fprintf(stderr, "[%s] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", v, fid || gene_fid ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
+        if (res_cmp_on(Fd, CMP_COEXPR)) fprintf(stderr, "[%s] --coexpression: %sthe gene-major planes, the Gram sums and selections, the shared counts, their D2H, rows and files %.3f s\n", v,
+                                                fid || gene_fid || nbr || res_cmp_on(Fd, CMP_LABELS) ? "" : "the full-depth rows and per-gene sums of every pair, ", T.coexpr);
     }
 done:
     fastf_res_rate_close(&S);

@@ -263,6 +263,9 @@ static void usage_level(FILE *f)
             "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: level_neighbors.tsv and\n"
             "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
             "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps\n"
+            "        --coexpression    every point against the full-depth data of the same cells, BETWEEN the genes: level_coexpr.tsv and\n"
+            "                          coexpr.tsv.gz per point, with the share of a gene's 15 strongest co-expression partners at full depth\n"
+            "                          (Pearson of the RAW counts among the 2000 most variable genes, decided in exact integers) that it keeps\n"
             "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): level_labels.tsv,\n"
             "                          level_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
             "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point\n"

@@ -76,6 +76,26 @@ static inline res_nbr_pin_v res_nbr_pin_layout(void *base, size_t map_bytes, siz
     v.bytes = c.off; return v;
 }
 
+/* --coexpression, over the K genes of A (FASTF_HVG_TOP at the most).  The device block: D (K x K) and S of the row set at hand, the slot
+ * map of A (map_bytes, as above: the option keeps its own, so that it runs without --neighbors), the partner slots (k a gene) of the full
+ * rows [0] and of the point [1], their counts, the shared counts.  The pinned block: the map, k_full, k_point, shared and the genes of A
+ * in rank order */
+typedef struct { uint64_t *D, *S; uint16_t *map; uint32_t *idx[2], *cnt[2], *shared; size_t bytes; } res_cx_v;
+static inline res_cx_v res_cx_layout(void *base, size_t map_bytes, size_t k, size_t K)
+{
+    res_carve_t c = { (char *)base, 0 }; res_cx_v v;
+    RES_CARVE(c, v.D, K * K); RES_CARVE(c, v.S, K); RES_CARVE(c, v.map, map_bytes / sizeof *v.map); RES_CARVE(c, v.idx[0], K * k); RES_CARVE(c, v.idx[1], K * k);
+    RES_CARVE(c, v.cnt[0], K); RES_CARVE(c, v.cnt[1], K); RES_CARVE(c, v.shared, K);
+    v.bytes = c.off; return v;
+}
+typedef struct { uint16_t *map; uint32_t *kf, *kp, *sh, *genes; size_t bytes; } res_cx_pin_v;
+static inline res_cx_pin_v res_cx_pin_layout(void *base, size_t map_bytes, size_t K)
+{
+    res_carve_t c = { (char *)base, 0 }; res_cx_pin_v v;
+    RES_CARVE(c, v.map, map_bytes / sizeof *v.map); RES_CARVE(c, v.kf, K); RES_CARVE(c, v.kp, K); RES_CARVE(c, v.sh, K); RES_CARVE(c, v.genes, K);
+    v.bytes = c.off; return v;
+}
+
 /* --labels: lab of the pair's cells, then one half for the full rows [0] and one for the point [1] — pred, same, labelled (u8) and conf
  * (u32, n_labels x (n_labels + 1)); a half starts at its pred and leaves in one copy of half_bytes.  lab_cells: res_lab_cells(cells), a
  * multiple of 4, which keeps conf aligned.  The device block and its pinned copy alike */

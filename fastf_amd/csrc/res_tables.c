@@ -353,6 +353,22 @@ static int mk_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float ra
     return bad;
 }
 
+/* --coexpression: one row per gene of A in rank order, the gene named by its feature id */
+static int cx_line(gtext *t, const void *ctx, uint32_t g)
+{
+    const res_rate_t *S = (const res_rate_t *)ctx;
+    char line[512];
+    return fastf_coexpr_row(S->L->feat_id[S->h_cx.genes[g]], S->h_cx.kf[g], S->h_cx.kp[g], S->h_cx.sh[g], line, sizeof line) || fastf_gt_str(t, line);
+}
+static int cx_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    char row[640];
+    if (fastf_coexpr_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_COEXPR_K, S->h_cx.kf, S->h_cx.kp, S->h_cx.sh, row, sizeof row)) return 1;
+    if (dir && flat_file(dir, "coexpr.tsv.gz", fastf_coexpr_header(), S->hvg_k, cx_line, S)) return 1;
+    fputs(row, cmp_tsv(C, TB_COEXPR));
+    return 0;
+}
+
 /* ------------------------------------------------------------------ */
 /* the comparisons against full depth: the descriptors, open, point, close */
 /* ------------------------------------------------------------------ */
@@ -366,6 +382,7 @@ static const struct {
     [CMP_NEIGHBORS] = { FASTF_SWEEP_NEIGHBORS,     { TB_NEIGHBORS, -1 },            offsetof(res_times_t, neighbors), nbr_point },
     [CMP_LABELS]    = { 0,                         { TB_LABELS, TB_LABEL_CLASSES }, offsetof(res_times_t, labels),    lab_point },
     [CMP_MARKERS]   = { 0,                         { TB_MARKERS, -1 },              offsetof(res_times_t, markers),   mk_point },
+    [CMP_COEXPR]    = { FASTF_SWEEP_COEXPRESSION,  { TB_COEXPR, -1 },               offsetof(res_times_t, coexpr),    cx_point },
     [CMP_GENE_FID]  = { FASTF_SWEEP_GENE_FIDELITY, { TB_GENE_FIDELITY, -1 },        offsetof(res_times_t, gene_fid),  gene_fid_point },
     [CMP_FIDELITY]  = { FASTF_SWEEP_FIDELITY,      { TB_FIDELITY, -1 },             offsetof(res_times_t, fidelity),  fid_point },
 };
@@ -391,6 +408,7 @@ void fastf_res_cmp_cfg(const res_cmp_t *C, res_cfg_t *cfg)
 {
     cfg->fidelity = res_cmp_on(C, CMP_FIDELITY); cfg->gene_fid = res_cmp_on(C, CMP_GENE_FID); cfg->labels = res_cmp_on(C, CMP_LABELS);
     cfg->neighbors = res_cmp_on(C, CMP_NEIGHBORS) || cfg->labels;
+    cfg->coexpr = res_cmp_on(C, CMP_COEXPR);
     cfg->lab_t = C->labels; cfg->markers = C->markers;
 }
 

@@ -227,11 +227,11 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
             return no_room(S, "the per-cell arrays", res_cellsum_layout(NULL, n_cells).bytes);
         S->h_cs = res_cellsum_layout(S->buf.h_cellsum.p, n_cells);
     }
-    if ((S->cfg.gene_fid || S->cfg.neighbors) && !S->cfg.fidelity) {    /* the full rows of the pair, for --gene-fidelity or --neighbors alone */
+    if (res_cfg_per_gene(&S->cfg) && !S->cfg.fidelity) {    /* the full rows of the pair, for --gene-fidelity, --neighbors or --coexpression alone */
         if (res_room(&S->buf.full, RES_DEV, (N ? N : 1) * 12, device)) return no_room(S, "the full-depth rows", (size_t)(N * 12));
         S->full_nnz = 0;
     }
-    if (S->cfg.gene_fid || S->cfg.neighbors) {              /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once (--neighbors alone: the pair's sums, which rank A) */
+    if (res_cfg_per_gene(&S->cfg)) {                        /* the partner column, the per-gene sums of the pair and of a point and their pinned copies, once (--neighbors or --coexpression alone: the pair's sums, which rank A) */
         const size_t nf1 = (size_t)S->n_features + 1, bytes = res_gfid_layout(NULL, nf1).bytes;
         if ((S->cfg.gene_fid && res_room(&S->buf.gx, RES_DEV, (N ? N : 1) * 4, device)) || res_block_room(&S->buf.gfid, RES_DEV, bytes, nf1, device) ||
             res_block_room(&S->buf.h_gfid, RES_PIN, bytes, nf1, device)) return no_room(S, "the partner column and the per-gene sums", (size_t)(N * 4 + bytes));
@@ -245,6 +245,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
             return no_room(S, "the neighbour sets", dev_bytes);
         S->d_nbr = res_nbr_layout(S->buf.nbr.p, map_bytes, FASTF_NEIGHBORS_K, nc); S->h_nbr = res_nbr_pin_layout(S->buf.h_nbr.p, map_bytes, nc, FASTF_HVG_TOP);
         S->hvg_k = 0; S->nbr_planes = 0;
+    }
+    if (S->cfg.coexpr) {                                    /* the device and the pinned block of the partner sets.  The planes wait for P (fastf_res_full_keep) */
+        const size_t map_bytes = S->nbr_map_bytes = res_nbr_map_bytes(S->n_features);
+        const size_t dev_bytes = res_cx_layout(NULL, map_bytes, FASTF_COEXPR_K, FASTF_HVG_TOP).bytes;
+        if (res_room(&S->buf.cx, RES_DEV, dev_bytes, device) || res_room(&S->buf.h_cx, RES_PIN, res_cx_pin_layout(NULL, map_bytes, FASTF_HVG_TOP).bytes, device))
+            return no_room(S, "the co-expression sums and partner sets", dev_bytes);
+        S->d_cx = res_cx_layout(S->buf.cx.p, map_bytes, FASTF_COEXPR_K, FASTF_HVG_TOP); S->h_cx = res_cx_pin_layout(S->buf.h_cx.p, map_bytes, FASTF_HVG_TOP);
+        S->hvg_k = 0;
     }
     if (S->cfg.labels) {                                    /* the label block and its pinned copy; lab[] goes up once per pair */
         S->n_labels = fastf_labels_count(S->cfg.lab_t);
@@ -542,16 +550,49 @@ int fastf_res_point_markers(res_rate_t *S, const char *point_name, res_times_t *
     return 0;
 }
 
+/* --coexpression: the gene-major planes of one row set (P planes: what the largest count of the set needs), its D and S and its partner
+ * sets into the full (point == 0) or the point's half of the block; `where` names the pair or the point in a failure */
+static int cx_sets(res_rate_t *S, const uint32_t *r_f, const uint32_t *r_c, const uint32_t *r_k, const uint64_t *d_nnz, int point, const char *where)
+{
+    uint32_t P = 0;
+    if (fastf_dev_neighbor_planes(S->e, r_f, r_c, r_k, d_nnz, S->d_cx.map, S->n_features, S->n_cells, S->hvg_k, NULL, 0, &P, NULL))
+        return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+    const size_t need = fastf_coexpr_work_bytes(S->n_cells, S->hvg_k, P);
+    if (res_room(&S->buf.cxwork, RES_DEV, need ? need : 1, S->device))
+        return fastf_res_err("%s: --coexpression at %s: %u planes of %u genes x %u cells do not fit: %zu bytes (%s)", S->verb, where, P, S->hvg_k, S->n_cells, need, fastf_last_error_copy());
+    if (fastf_dev_coexpr_sums(S->e, r_f, r_c, r_k, d_nnz, S->d_cx.map, S->n_features, S->n_cells, S->hvg_k, P, S->buf.cxwork.p, S->buf.cxwork.have, S->d_cx.D, S->d_cx.S, NULL) ||
+        fastf_dev_coexpr_select(S->e, S->d_cx.D, S->d_cx.S, S->n_cells, S->hvg_k, FASTF_COEXPR_K, S->d_cx.idx[point], S->d_cx.cnt[point], NULL) || fastf_devmem_sync())
+        return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+    return 0;
+}
+
+int fastf_res_point_coexpr(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->cfg.coexpr) return 0;
+    const uint64_t nnz = S->buf.h_small.u64[SM_NNZ];
+    const res_rows_t d = res_rows_point(S);
+    char where[128];
+    const double tt = fastf_res_now();
+    snprintf(where, sizeof where, "point %s", point_name);
+    if (cx_sets(S, nnz ? d.f : NULL, d.c, d.k, S->buf.small.u64 + SM_NNZ, 1, where)) return 1;
+    if (fastf_dev_neighbors_shared(S->e, S->d_cx.idx[0], S->d_cx.cnt[0], S->d_cx.idx[1], S->d_cx.cnt[1], S->hvg_k, FASTF_COEXPR_K, S->d_cx.shared, NULL) || fastf_devmem_sync())
+        return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+    if (S->hvg_k && (fastf_devmem_copy(S->h_cx.kp, S->d_cx.cnt[1], (size_t)S->hvg_k * 4) || fastf_devmem_copy(S->h_cx.sh, S->d_cx.shared, (size_t)S->hvg_k * 4)))
+        return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+    T->coexpr += fastf_res_now() - tt;
+    return 0;
+}
+
 /* where the full-depth work of a pair is booked: under the first flag that is on, in the order fidelity, gene fidelity, neighbours;
- * per_gene: the per-gene sums of the pair, which --fidelity has no part in */
+ * then co-expression; per_gene: the per-gene sums of the pair, which --fidelity has no part in */
 double *fastf_res_full_timer(const res_rate_t *S, res_times_t *T, int per_gene)
 {
-    return S->cfg.fidelity && !per_gene ? &T->fidelity : S->cfg.gene_fid ? &T->gene_fid : &T->neighbors;
+    return S->cfg.fidelity && !per_gene ? &T->fidelity : S->cfg.gene_fid ? &T->gene_fid : S->cfg.neighbors ? &T->neighbors : &T->coexpr;
 }
 
 int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 {
-    if (!S->cfg.fidelity && !S->cfg.gene_fid && !S->cfg.neighbors) return 0;
+    if (!res_cfg_full(&S->cfg)) return 0;
     const uint64_t N = S->R->n, nnz = S->buf.h_small.u64[SM_NNZ];
     uint64_t *const sm = S->buf.small.u64;
     const res_rows_t d = res_rows_point(S), x = res_rows_full(S);
@@ -560,7 +601,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
     if (fastf_devmem_copy(x.f, d.f, (size_t)nnz * 4) || fastf_devmem_copy(x.c, d.c, (size_t)nnz * 4) || fastf_devmem_copy(x.k, d.k, (size_t)nnz * 4) ||
         fastf_devmem_copy(sm + SM_FULL, sm + SM_NNZ, 8)) return 1;
     S->full_nnz = nnz;
-    if (S->cfg.gene_fid || S->cfg.neighbors) {                      /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
+    if (res_cfg_per_gene(&S->cfg)) {                                /* per gene sum_x and cells_full (the per-gene summary of the full rows), sum_xx (their moments with themselves) */
         uint64_t *const g_sx = S->d_gfid.sx, *const g_sxx = S->d_gfid.sxx;
         uint32_t *const g_cf = S->d_gfid.cf;
         if (fastf_dev_gene_summary(S->e, nnz ? x.f : NULL, nnz ? x.k : NULL, sm + SM_FULL, S->n_features, g_cf, g_sx, NULL) ||
@@ -588,6 +629,19 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
         if (mk_tables(S, 0)) return 1;
         T->markers += fastf_res_now() - tt; tt = fastf_res_now();
     }
+    if (S->cfg.coexpr) {                                        /* A of the pair as --neighbors ranks it (its own ranking and slot map without that option), the partner sets of the full rows, which stay */
+        char where[96];
+        snprintf(where, sizeof where, "cell rate %.3f, seed %u", (double)S->rate_cell, S->seed);
+        if (S->cfg.neighbors) { memcpy(S->h_cx.genes, S->h_nbr.genes, (size_t)S->hvg_k * 4); memcpy(S->h_cx.map, S->h_nbr.map, S->nbr_map_bytes); }
+        else {
+            S->hvg_k = fastf_hvg_rank(S->n_cells, S->h_gfid.sx, S->h_gfid.sxx, S->n_features, S->h_cx.genes, NULL);
+            if (fastf_neighbors_slot_map(S->h_cx.genes, S->hvg_k, S->n_features, S->h_cx.map)) return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+        }
+        if (fastf_devmem_copy(S->d_cx.map, S->h_cx.map, S->nbr_map_bytes)) return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+        if (cx_sets(S, nnz ? x.f : NULL, x.c, x.k, sm + SM_FULL, 0, where)) return 1;
+        if (S->hvg_k && fastf_devmem_copy(S->h_cx.kf, S->d_cx.cnt[0], (size_t)S->hvg_k * 4)) return fastf_res_err("%s: --coexpression at %s: %s", S->verb, where, fastf_last_error_copy());
+        T->coexpr += fastf_res_now() - tt; tt = fastf_res_now();
+    }
     if (!S->cfg.fidelity) return 0;
     /* sum_xx: the full rows joined with themselves (sum_xy == sum_yy; the first of the two lands in the point's own slot, which the
      * first point overwrites) */
@@ -600,7 +654,7 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
 
 int fastf_res_full_run(res_rate_t *S, const uint32_t *d_plane, res_times_t *T)
 {
-    if (!S->cfg.fidelity && !S->cfg.gene_fid && !S->cfg.neighbors) return RES_OK;
+    if (!res_cfg_full(&S->cfg)) return RES_OK;
     char name[64];
     uint64_t counters[3], nnz = 0;
     const res_times_t before = *T;
@@ -654,7 +708,8 @@ int fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *
     if (fastf_res_point_gene_fidelity(S, point_name, T)) return 1;
     if (fastf_res_point_neighbors(S, point_name, T)) return 1;
     if (fastf_res_point_labels(S, point_name, T)) return 1;       /* (directly behind the neighbour sets it votes with) */
-    return fastf_res_point_markers(S, point_name, T);            /* (on the byte planes those sets were made of) */
+    if (fastf_res_point_markers(S, point_name, T)) return 1;      /* (on the byte planes those sets were made of) */
+    return fastf_res_point_coexpr(S, point_name, T);             /* (on planes of its own) */
 }
 
 /* --cells: behind the point.  The full sort and K3u use the engine's workspace, and K3u writes the engine's row regions — the count
@@ -973,11 +1028,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->labels = NULL; out->markers = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->labels = NULL; out->markers = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -991,7 +1046,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNLMER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXLMER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1022,6 +1077,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'F': out->fidelity = 1; break;
         case 'Q': out->gene_fidelity = 1; break;
         case 'N': out->neighbors = 1; break;
+        case 'X': out->coexpression = 1; break;
         case 'L': out->labels = val; break;
         case 'M': markers_text = val; break;
         case 'E': seeds_text = val; break;
@@ -1067,12 +1123,13 @@ int fastf_res_check_inputs(const res_args_t *a)
 _Static_assert(FASTF_CAP_SUMMARY_ONLY == FASTF_SWEEP_SUMMARY_ONLY && FASTF_LEVEL_SUMMARY_ONLY == FASTF_SWEEP_SUMMARY_ONLY && FASTF_CAP_GENES == FASTF_SWEEP_GENES &&
                FASTF_LEVEL_GENES == FASTF_SWEEP_GENES && FASTF_CAP_CELLS == FASTF_SWEEP_CELLS && FASTF_LEVEL_CELLS == FASTF_SWEEP_CELLS &&
                FASTF_CAP_FIDELITY == FASTF_SWEEP_FIDELITY && FASTF_LEVEL_FIDELITY == FASTF_SWEEP_FIDELITY && FASTF_CAP_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY &&
-               FASTF_LEVEL_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY && FASTF_CAP_NEIGHBORS == FASTF_SWEEP_NEIGHBORS && FASTF_LEVEL_NEIGHBORS == FASTF_SWEEP_NEIGHBORS,
+               FASTF_LEVEL_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY && FASTF_CAP_NEIGHBORS == FASTF_SWEEP_NEIGHBORS && FASTF_LEVEL_NEIGHBORS == FASTF_SWEEP_NEIGHBORS &&
+               FASTF_CAP_COEXPRESSION == FASTF_SWEEP_COEXPRESSION && FASTF_LEVEL_COEXPRESSION == FASTF_SWEEP_COEXPRESSION,
                "the three verbs share one flag word");
 uint32_t fastf_res_args_flags(const res_args_t *a)
 {
     return (a->summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (a->genes ? FASTF_SWEEP_GENES : 0) | (a->per_cell ? FASTF_SWEEP_CELLS : 0) | (a->fidelity ? FASTF_SWEEP_FIDELITY : 0) |
-           (a->gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (a->neighbors ? FASTF_SWEEP_NEIGHBORS : 0);
+           (a->gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (a->neighbors ? FASTF_SWEEP_NEIGHBORS : 0) | (a->coexpression ? FASTF_SWEEP_COEXPRESSION : 0);
 }
 
 void fastf_res_print_generated(const char *verb, const res_args_t *a)
@@ -1085,6 +1142,7 @@ void fastf_res_print_generated(const char *verb, const res_args_t *a)
     if (a->neighbors) printf("%s_neighbors.tsv is generated.\n", verb);
     if (a->labels) printf("%s_labels.tsv and %s_label_classes.tsv are generated.\n", verb, verb);
     if (a->markers) printf("%s_markers.tsv is generated.\n", verb);
+    if (a->coexpression) printf("%s_coexpr.tsv is generated.\n", verb);
     if (a->n_seeds) printf("%s_reps.tsv is generated.\n", verb);
     printf("%s.tsv is generated.\n", verb);
 }

@@ -1,7 +1,7 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE]; -d accepted
+ *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE]; -d accepted
  *                  and ignored, -u refused
  *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
@@ -29,6 +29,9 @@
  * --labels FILE: the votes of those neighbour sets for the labels of the file (fastf_res_point_labels: fastf_dev_label_votes)
  * into sweep_labels.tsv, sweep_label_classes.tsv and the point's labels.tsv.gz and label_confusion.tsv.gz; it switches the neighbour sets
  * on by itself and writes no --neighbors file.
+ * --coexpression: the co-expression partners of the genes of A, at full depth and at the point (fastf_res_point_coexpr:
+ * fastf_dev_coexpr_sums, fastf_dev_coexpr_select, fastf_dev_neighbors_shared) into sweep_coexpr.tsv and the point's coexpr.tsv.gz; it
+ * keeps the full rows and ranks the genes by itself, and computes nothing of the neighbour sets.
  * --seeds / --reps: the same records at several seeds — per cell rate every seed opens its own (cell rate, seed) pair on
  * the run's one res_rate_t (its buffers are handed on, the blocked copy laid out again only where the layout changes), the points
  * go to <point>_s<seed>/, and per grid point the metrics of the seeds are reduced into sweep_reps.tsv; with --genes the per-gene
@@ -352,6 +355,10 @@ static void usage_sweep(FILE *f)
             "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: sweep_neighbors.tsv and\n"
             "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
             "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps; resident form only\n"
+            "        --coexpression    every point against the full-depth data of the same cells, BETWEEN the genes: sweep_coexpr.tsv and\n"
+            "                          coexpr.tsv.gz per point, with the share of a gene's 15 strongest co-expression partners at full depth\n"
+            "                          (Pearson of the RAW counts among the 2000 most variable genes, decided in exact integers) that it keeps;\n"
+            "                          resident form only\n"
             "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): sweep_labels.tsv,\n"
             "                          sweep_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
             "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point;\n"

@@ -209,6 +209,7 @@ enum { AN_CAP_HITS, AN_GENE_SUMMARY, AN_GENE_MOMENTS, AN_NBR_GRAM, AN_LABEL_VOTE
 struct AnalysisState {
     bool attr[AN_FAMILIES] = {};
     DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
+    DevBuf d_coex;                       // --coexpression: the word of its max reduction (64 bytes), then V (u64 per gene of A)
 };
 
 // per-kernel timers, in the order of fastf_engine_get_timing's `which`
@@ -743,7 +744,7 @@ extern "C" void fastf_engine_destroy(fastf_engine_t* e) FASTF_TRY {
     }
     if (e->h_small) (void)hipHostFree(e->h_small);
     if (e->h_coo) { if (e->h_coo_pinned) pin_unreg(e->h_coo); fastf_big_free(e->h_coo, (size_t)e->h_coo_cap * 12); }
-    e->d_ring.release(); e->d_mt.release(); e->an.d_nbr.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
+    e->d_ring.release(); e->d_mt.release(); e->an.d_nbr.release(); e->an.d_coex.release(); e->d_dbits.release(); e->d_mtwords.release(); e->d_mtsub.release(); e->d_mtpoly.release(); e->d_mtseat.release(); e->d_mtseq.release();
     DevBuf* all[] = {&e->tab_cells, &e->tab_feats, &e->img_cells, &e->img_genes, &e->d_cell_filter, &e->d_keys, &e->d_tmp, &e->d_small, &e->d_feature, &e->d_cell,
                      &e->d_count, &e->d_ukeys, &e->d_ncopy, &e->d_cellidx, &e->d_tilecnt, &e->d_tilebase, &e->d_binbase, &e->d_cnt, &e->d_rg_feature, &e->d_rg_cell, &e->d_rg_count, &e->d_rg_ukeys, &e->d_spanrows, &e->d_spanbase, &e->d_giant, &e->d_scanblk,
                      &e->d_halfhits, &e->d_segcount, &e->d_segprefix, &e->d_tileseg, &e->d_segkeys, &e->d_vals, &e->d_vtmp,
@@ -1597,7 +1598,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel,marker_labels_kernel,marker_auc_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel,marker_labels_kernel,marker_auc_kernel,coex_planes_kernel,coex_gram_kernel,coex_sums_kernel,coex_var_kernel,coex_select_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------

@@ -463,6 +463,18 @@ class Engine:
         """--neighbors: d_shared[i] (u32) = the cells in both neighbour sets of cell i; stream-ordered"""
         check(self._L.fastf_dev_neighbors_shared(self._h, d_idx_a or None, d_cnt_a or None, d_idx_b or None, d_cnt_b or None, n_cells, k, d_shared or None, stream))
 
+    def dev_coexpr_sums(self, d_feature, d_cell, d_count, d_nnz, d_slot_map, n_features, n_cells, n_genes, planes, d_work, work_bytes, d_D, d_S, stream=0):
+        """--coexpression: the rows and the slot map as dev_neighbor_planes takes them, `planes` what it returned -> the gene-major planes in
+        d_work (sweep.coexpression_work_bytes), d_D (u64[n_genes * n_genes], dense) and d_S (u64[n_genes]), both zeroed by the call;
+        FASTF_COEXPR_MFMA=0: the dot products from ordinary integer instructions, FASTF_COEXPR_CHUNK=<cells>: a shorter chunk; stream-ordered"""
+        check(self._L.fastf_dev_coexpr_sums(self._h, d_feature or None, d_cell or None, d_count or None, d_nnz, d_slot_map or None, n_features, n_cells, n_genes,
+                                            planes, d_work or None, work_bytes, d_D or None, d_S or None, stream))
+
+    def dev_coexpr_select(self, d_D, d_S, n_cells, n_genes, k, d_idx, d_cnt, stream=0):
+        """--coexpression: D and S over n_cells cells -> d_idx (u32[n_genes * k], ascending within a row, 0xFFFFFFFF behind the d_cnt[g]
+        entries) and d_cnt (u32[n_genes]); FastfError naming FASTF_ERR_COEXPR_RANGE when n_cells * max D_gg >= 2^63; synchronises the stream once"""
+        check(self._L.fastf_dev_coexpr_select(self._h, d_D or None, d_S or None, n_cells, n_genes, k, d_idx or None, d_cnt or None, stream))
+
     def dev_label_votes(self, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf, stream=0):
         """--labels: the neighbour sets Engine.dev_neighbors left (d_idx, d_cnt) and d_lab (u8[n_cells], 0 unlabelled) -> d_pred, d_same,
         d_labelled (u8[n_cells]) and d_conf (u32[n_labels * (n_labels + 1)], zeroed by the call); FASTF_LABELS_LDS=0: the confusion counts

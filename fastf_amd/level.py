@@ -17,6 +17,7 @@ CELLS = 8             # FASTF_LEVEL_CELLS
 FIDELITY = 32         # FASTF_LEVEL_FIDELITY
 GENE_FIDELITY = 128   # FASTF_LEVEL_GENE_FIDELITY
 NEIGHBORS = 512       # FASTF_LEVEL_NEIGHBORS
+COEXPRESSION = 4096   # FASTF_LEVEL_COEXPRESSION
 
 
 def _renamed(columns):
@@ -37,18 +38,20 @@ NEIGHBORS_COLUMNS = _renamed(_cap.NEIGHBORS_COLUMNS)
 LABELS_COLUMNS = _renamed(_cap.LABELS_COLUMNS)
 LABEL_CLASSES_COLUMNS = _renamed(_cap.LABEL_CLASSES_COLUMNS)
 MARKERS_COLUMNS = _renamed(_cap.MARKERS_COLUMNS)
+COEXPRESSION_COLUMNS = _renamed(_cap.COEXPRESSION_COLUMNS)
+read_point_coexpression = _sweep.read_point_coexpression
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 THRESHOLDS_COLUMNS = ("barcode", "threshold", "umis_full", "umis")
 parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for the three verbs)
 
 
-def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neighbors=False):
+def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neighbors=False, coexpression=False):
     return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
-            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0))
+            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0) | (COEXPRESSION if coexpression else 0))
 
 
 def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF level -b bam -a barcodes -f features -o out -c rates_cell -m umi_caps -s seed [--summary-only] [--genes] [--cells]`; returns
     the rows of out/level.tsv as dicts of strings (read_table); genes / cells: the files cap.cap() leaves, under the names level_*; fidelity:
     out/level_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per point directory; gene_fidelity: out/level_gene_fidelity.tsv
@@ -60,21 +63,21 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     if markers is not None:
         _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
                                                 seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                 m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors),
+                                                 m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
                                                  seed % (1 << 32), enc(labels)))
         return read_table(os.path.join(os.fspath(out), "level.tsv"))
     _lib.check(_lib.lib().fastf_level(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                      m.ctypes.data, len(m), seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                      m.ctypes.data, len(m), seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "level.tsv"))
 
 
 def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
@@ -84,16 +87,16 @@ def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summar
     if markers is not None:
         _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
                                                 None if labels is None else enc(labels), _sweep._markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                  m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0, enc(labels)))
+                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
         return read_table(os.path.join(os.fspath(out), "level.tsv"))
     _lib.check(_lib.lib().fastf_level_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                           m.ctypes.data, len(m), sd.ctypes.data, len(sd), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                           m.ctypes.data, len(m), sd.ctypes.data, len(sd), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "level.tsv"))
 
 
@@ -144,6 +147,10 @@ def gene_fidelity_summary_row(rate_cell, umi_cap, seed, n_cells, sum_x, sum_y, s
 
 def read_neighbors_table(path):
     return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def read_coexpression_table(path):
+    return _sweep.read_cells_table(path, COEXPRESSION_COLUMNS)
 
 
 def neighbors_header(verb: str = "level") -> str:

@@ -16,7 +16,9 @@ GENE_FIDELITY = 128   # FASTF_SWEEP_GENE_FIDELITY
 HVG_TOP = 2000        # FASTF_HVG_TOP
 NEIGHBORS = 512       # FASTF_SWEEP_NEIGHBORS
 NEIGHBORS_K = 15      # FASTF_NEIGHBORS_K
+COEXPRESSION = 4096   # FASTF_SWEEP_COEXPRESSION
 COEXPRESSION_K = 15   # FASTF_COEXPR_K
+COEXPRESSION_CHUNK = 8192   # FASTF_COEXPR_CHUNK
 LABELS_MAX = 255      # FASTF_LABELS_MAX
 MARKERS_MAX = 2000    # FASTF_MARKERS_MAX
 COPY_BINS = 32        # FASTF_COPY_BINS
@@ -56,9 +58,9 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=False):
+def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=False, coexpression=False):
     return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
-            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0))
+            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0) | (COEXPRESSION if coexpression else 0))
 
 
 def _markers_n(markers) -> int:
@@ -71,7 +73,7 @@ def _markers_n(markers) -> int:
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
@@ -83,21 +85,22 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     (`--labels`: one barcode<TAB>label per line) the label votes of those neighbours: out/sweep_labels.tsv (read_labels_table),
     out/sweep_label_classes.tsv (read_label_classes_table) and labels.tsv.gz (read_point_labels), label_confusion.tsv.gz per point directory;
     markers=N (`--markers`, with labels) the N best marker genes per label by exact AUC: out/sweep_markers.tsv (read_markers_table) and a
-    markers.tsv.gz per point directory (read_point_markers)"""
+    markers.tsv.gz per point directory (read_point_markers); coexpression=True (`--coexpression`) the comparison between the genes:
+    out/sweep_coexpr.tsv (read_coexpression_table) and a coexpr.tsv.gz per point directory (read_point_coexpression)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     if markers is not None:
         _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), seed % (1 << 32),
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
                                                   None if labels is None else enc(labels), _markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), seed % (1 << 32), enc(labels)))
+                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32), enc(labels)))
         return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -107,7 +110,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -117,15 +120,15 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
     if markers is not None:
         _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0,
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
                                                   None if labels is None else enc(labels), _markers_n(markers)))
         return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if labels is not None:
         _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors), 0, enc(labels)))
+                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
         return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors)))
+                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
@@ -346,6 +349,19 @@ def read_point_coexpression(path):
 def coexpression_header(verb: str = "") -> str:
     """the header of the per-gene rows, or with verb "sweep" / "cap" / "level" of the per-point rows"""
     return getattr(_lib.lib(), "fastf_%scoexpr_header" % (verb + "_" if verb else ""))().decode()
+
+
+def coexpression_pad(n_cells: int, n_genes: int):
+    """(K_pad, n_pad, chunk): the shape of the gene-major byte planes of Engine.dev_coexpr_sums and the cells of a chunk, under the
+    FASTF_COEXPR_CHUNK in effect"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _lib.lib().fastf_coexpr_pad(n_cells, n_genes, C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def coexpression_work_bytes(n_cells: int, n_genes: int, planes: int) -> int:
+    """the bytes of the work buffer of Engine.dev_coexpr_sums"""
+    return int(_lib.lib().fastf_coexpr_work_bytes(n_cells, n_genes, planes))
 
 
 def coexpression_check_range(n_cells: int, max_q: int):

@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--labels FILE] [--markers N] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -409,14 +409,23 @@ int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list
  * Range: a pair with n * max_g Q_g >= 2^63 is refused by name (FASTF_ERR_COEXPR_RANGE in the message: fastf_coexpr_check_range).  Below
  * it |c| <= n sqrt(Q_g Q_h) < 2^63 and V < 2^63, so every product stays below 2^189.  A count of 2^21 or more among the genes of A is
  * refused as --neighbors refuses it (FASTF_ERR_NEIGHBOR_COUNT): the three 7-bit digit planes of that option are the range of this one.
- * This is the definition, its host implementation and its rows; no verb computes it yet and no device code exists for it.
+ * --coexpression on sweep, cap and level (FASTF_*_COEXPRESSION, flag 4096; `coexpression=True` in Python; the long option alone) computes
+ * it on the device (fastf_dev_coexpr_sums, fastf_dev_coexpr_select below) for the full rows of every pair and for every point, and writes
+ * <out_dir>/<verb>_coexpr.tsv (one row per point, through .partial, with --summary-only too; in replicate runs one row per (cell rate,
+ * seed, list value) and no _reps table) and <point dir>/coexpr.tsv.gz (not with --summary-only).  Alone it keeps the full rows, the
+ * pair's per-gene sums and the slot map of A, and nothing of the neighbour sets; every other output is the bytes it is without the
+ * option.  Jobs outside the resident form are refused as --neighbors refuses them, naming --coexpression.
  * Per gene at a point:  k_full = |P_X(g)|   k_point = |P_Y(g)|   shared = |P_X(g) and P_Y(g)|.
  *   one row per gene of A in rank order (fastf_coexpr_header, fastf_coexpr_row):   gene k_full k_point shared      (gene: the feature id)
  *   one row per point (fastf_<verb>_coexpr_header, fastf_coexpr_summary_row): the verb's two leading columns, then
  *     seed n_cells hvg_k k genes_defined sum_k_full sum_k_point sum_shared mean_kept genes_half_kept
  *     genes_defined = genes with k_full > 0; mean_kept = the mean of shared / k_full over those genes (%.6f; NA when there is none);
  *     genes_half_kept = those of them with 2 shared >= k_full.  Ratios are formed only where they are printed. --- */
+#define FASTF_SWEEP_COEXPRESSION 4096u       /* bits 1024 and 2048 are not assigned: tests pin them as the unknown bits that are refused */
+#define FASTF_CAP_COEXPRESSION   4096u
+#define FASTF_LEVEL_COEXPRESSION 4096u
 #define FASTF_COEXPR_K 15u
+#define FASTF_COEXPR_CHUNK 8192u             /* the cells a wave of the Gram kernel reduces before it adds into D; FASTF_COEXPR_CHUNK lowers it */
 #define FASTF_COEXPR_MAX_K 64u
 #define FASTF_COEXPR_MAX_PLANES 3u
 #define FASTF_COEXPR_MAX_GENES 4096u
@@ -1082,6 +1091,35 @@ int fastf_dev_neighbors(fastf_engine_t *e, const void *d_planes, uint32_t planes
                         uint32_t *d_cnt, uint64_t *d_norms, uint64_t *max_norm_out, void *stream);
 int fastf_dev_neighbors_shared(fastf_engine_t *e, const uint32_t *d_idx_a, const uint32_t *d_cnt_a, const uint32_t *d_idx_b, const uint32_t *d_cnt_b,
                                uint32_t n_cells, uint32_t k, uint32_t *d_shared, void *stream);
+
+/* --coexpression (section above), on device pointers (coexpr_kernels.hpp).
+ * fastf_coexpr_pad: the shape of the GENE-MAJOR byte planes of (n_cells, K): K_pad rows (K rounded up to 32) of n_pad bytes — n_cells rounded
+ * up to 32, then to a multiple of *chunk, the cells a wave reduces at a time: FASTF_COEXPR_CHUNK cells (the environment variable of that
+ * name lowers it: a value from 32 to below the default is rounded down to a multiple of 32, any other value is ignored and the default
+ * holds; read at each call, it changes no result) or the rounded cells where they are fewer.
+ * Plane p holds bits 7p .. 7p+6 of the count of (slot, cell) at [(p * K_pad + slot) * n_pad + cell].  fastf_coexpr_work_bytes: the bytes of
+ * `planes` such planes.
+ * fastf_dev_coexpr_sums (coex_planes_kernel, coex_gram_kernel, coex_sums_kernel): rows and d_slot_map as fastf_dev_neighbor_planes takes them,
+ * `planes` what that call returned for them (its FASTF_ERR_NEIGHBOR_COUNT is this option's too) -> the planes in d_work (work_bytes of
+ * room, 16-byte aligned; too little fails by name), d_D[g * K + h] = D_gh (u64, dense, both halves) and d_S[g] = S_g; D and S are zeroed
+ * by the call.  fastf_coexpr_check_gram refuses (n_cells, planes) before anything is launched.  A wave owns one 32 x 32 tile of D for one
+ * chunk of cells, one i32 accumulator tile per digit sum (3 * chunk * 127^2 < 2^31), and adds sum_t 2^(7t) acc_t into D with 64-bit
+ * integer atomics.  The dot products come from the i8 MFMA (32x32x32), under FASTF_COEXPR_MFMA=0 from ordinary integer instructions: the
+ * same numbers either way.  Asynchronous on `stream`.
+ * fastf_dev_coexpr_select (coex_var_kernel, coex_select_kernel): D, S over n_cells cells -> d_idx[g * k + s], s < d_cnt[g]: the partners
+ * of gene g (slots, ascending; the other slots 0xFFFFFFFF), k from 1 to 64, K at most 4096.  The largest D_gg is read back and
+ * fastf_coexpr_check_range refuses the call (FASTF_ERR_COEXPR_RANGE) before the selection is launched.  One thread per gene walks the
+ * slots in ascending order and keeps its best k by the rule of fastf_coexpr_select: the same sets.  Synchronises the stream once.  V and the
+ * word of the maximum live in ONE buffer of the engine: the call is not re-entrant per engine — two selections on one engine run one
+ * after the other, whatever their streams (the buffer is freed by fastf_engine_destroy).
+ * The shared counts of two sets: fastf_dev_neighbors_shared with n_cells := K (the layout of the sets is the same). */
+void fastf_coexpr_pad(uint32_t n_cells, uint32_t K, uint32_t *K_pad, uint32_t *n_pad, uint32_t *chunk);
+size_t fastf_coexpr_work_bytes(uint32_t n_cells, uint32_t K, uint32_t planes);
+int fastf_dev_coexpr_sums(fastf_engine_t *e, const uint32_t *d_feature, const uint32_t *d_cell, const uint32_t *d_count, const uint64_t *d_nnz,
+                          const uint16_t *d_slot_map, uint32_t n_features, uint32_t n_cells, uint32_t K, uint32_t planes, void *d_work,
+                          size_t work_bytes, uint64_t *d_D, uint64_t *d_S, void *stream);
+int fastf_dev_coexpr_select(fastf_engine_t *e, const uint64_t *d_D, const uint64_t *d_S, uint32_t n_cells, uint32_t K, uint32_t k,
+                            uint32_t *d_idx, uint32_t *d_cnt, void *stream);
 
 /* --labels (section above), one call on device pointers (label_votes_kernel).  d_idx and d_cnt are what fastf_dev_neighbors writes: k
  * slots a cell, d_cnt[i] of them valid; the other slots hold 0xFFFFFFFF and are never used as an index.  k from 1 to 64, n_labels up to

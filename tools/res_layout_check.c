@@ -104,6 +104,18 @@ int main(void)
         if (res_mk_set_bytes(L, K) != ((want + 7) & ~(size_t)7)) fail("mk", "the bytes of a pinned set moved", NULL, L, K, 0);
         check("mk", base, bytes, want, a, 4, L, K, 0); free(base);
     }
+    for (size_t fi = 0; fi < sizeof FEATURES / sizeof *FEATURES; fi++) for (size_t ki = 0; ki < sizeof KS / sizeof *KS; ki++) {      /* --coexpression: K genes of A */
+        const size_t nf = FEATURES[fi], K = KS[ki], map = res_nbr_map_bytes(nf), ix = K * K * 8 + K * 8 + map;
+        {   const size_t bytes = res_cx_layout(NULL, map, k, K).bytes; ALLOC(bytes);
+            res_cx_v v = res_cx_layout(base, map, k, K);
+            span_t a[] = { SPAN(v, D, K * K, 0), SPAN(v, S, K, K * K * 8), SPAN(v, map, nf + 1, K * K * 8 + K * 8), SPAN(v, idx[0], K * k, ix), SPAN(v, idx[1], K * k, ix + K * k * 4),
+                           SPAN(v, cnt[0], K, ix + 2 * K * k * 4), SPAN(v, cnt[1], K, ix + 2 * K * k * 4 + K * 4), SPAN(v, shared, K, ix + 2 * K * k * 4 + 2 * K * 4) };
+            check("cx", base, bytes, ix + K * (2 * k * 4 + 3 * 4), a, 8, map, k, K); free(base); }
+        {   const size_t bytes = res_cx_pin_layout(NULL, map, K).bytes; ALLOC(bytes);
+            res_cx_pin_v v = res_cx_pin_layout(base, map, K);
+            span_t a[] = { SPAN(v, map, nf + 1, 0), SPAN(v, kf, K, map), SPAN(v, kp, K, map + 4 * K), SPAN(v, sh, K, map + 8 * K), SPAN(v, genes, K, map + 12 * K) };
+            check("cx pinned", base, bytes, map + 16 * K, a, 5, map, K, 0); free(base); }
+    }
     {   uint32_t rows[3 * 5]; const res_rows_t r = res_rows(rows, 5);      /* the row triple: N entries apart */
         if (r.f != rows || r.c != rows + 5 || r.k != rows + 10) fail("rows", "the row arrays moved", NULL, 5, 0, 0); }
     printf("res_layout_check: %lu layouts hold\n", n_checked);

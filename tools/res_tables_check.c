@@ -18,6 +18,7 @@
 #include "fastf_amd.h"
 #include "resident.h"
 #include "san_stubs.h"
+#include "../fastf_amd/csrc/coexpr_host.c"       /* the rows of --coexpression live in coexpr_host.c; tests/test_sanitizers.py::test_grid_tables_and_point_files_hold_on_hand_filled_views compiles this program with res_tables.c, grid_rows.c and the host_io sources only, so the file is compiled in here and the gcc line of the comment above needs no coexpr_host.c */
 #include <dirent.h>
 #include <string.h>
 #include <sys/stat.h>
@@ -132,6 +133,9 @@ static void state_make(state_t *st, const char *tmp, uint32_t nc, uint32_t nf, u
     OWN(st, S->h_nbr.kf, nc); OWN(st, S->h_nbr.kp, nc); OWN(st, S->h_nbr.sh, nc); OWN(st, S->h_nbr.genes, K);
     for (uint32_t c = 0; c < nc; c++) { S->h_nbr.kf[c] = nc - 1; S->h_nbr.kp[c] = c ? nc - 2 : 0; S->h_nbr.sh[c] = c / 2; }
     for (uint32_t g = 0; g < K; g++) S->h_nbr.genes[g] = nf - 1 - g;
+    /* --coexpression: per gene of A (its own copy of the genes: the option runs without --neighbors) */
+    OWN(st, S->h_cx.kf, K); OWN(st, S->h_cx.kp, K); OWN(st, S->h_cx.sh, K); OWN(st, S->h_cx.genes, K);
+    for (uint32_t g = 0; g < K; g++) { S->h_cx.genes[g] = nf - 1 - g; S->h_cx.kf[g] = K - 1; S->h_cx.kp[g] = g ? K - 1 : 0; S->h_cx.sh[g] = g; }
     /* --labels */
     OWN(st, S->h_lab.lab, nc);
     for (int h = 0; h < 2; h++) { OWN(st, S->h_lab.half[h].pred, nc); OWN(st, S->h_lab.half[h].same, nc); OWN(st, S->h_lab.half[h].labelled, nc); OWN(st, S->h_lab.half[h].conf, (size_t)L * (L + 1)); }
@@ -171,10 +175,10 @@ static void add(text_t *t, const char *s)
     if (t->len + n + 1 > t->cap) CHECK((t->p = (char *)realloc(t->p, t->cap = (t->cap + n + 1) * 2)));
     memcpy(t->p + t->len, s, n + 1); t->len += n;
 }
-enum { W_SUMMARY, W_GENES, W_CELLS, W_FID, W_GFID, W_NBR, W_LAB, W_CLASSES, W_MK, W_TABLES, P_GENES = W_TABLES, P_CELLS, P_FID, P_GFID, P_NBR, P_LAB, P_CONF, P_MK, W_N };
+enum { W_SUMMARY, W_GENES, W_CELLS, W_FID, W_GFID, W_NBR, W_LAB, W_CLASSES, W_MK, W_CX, W_TABLES, P_GENES = W_TABLES, P_CELLS, P_FID, P_GFID, P_NBR, P_LAB, P_CONF, P_MK, P_CX, W_N };
 static const char *const point_file[W_N] = { [P_GENES] = "genes.tsv.gz", [P_CELLS] = "cells.tsv.gz", [P_FID] = "fidelity.tsv.gz", [P_GFID] = "gene_fidelity.tsv.gz",
-                                             [P_NBR] = "neighbors.tsv.gz", [P_LAB] = "labels.tsv.gz", [P_CONF] = "label_confusion.tsv.gz", [P_MK] = "markers.tsv.gz" };
-static const int table_of[W_TABLES] = { -1, TB_GENES, TB_CELLS, TB_FIDELITY, TB_GENE_FIDELITY, TB_NEIGHBORS, TB_LABELS, TB_LABEL_CLASSES, TB_MARKERS };
+                                             [P_NBR] = "neighbors.tsv.gz", [P_LAB] = "labels.tsv.gz", [P_CONF] = "label_confusion.tsv.gz", [P_MK] = "markers.tsv.gz", [P_CX] = "coexpr.tsv.gz" };
+static const int table_of[W_TABLES] = { -1, TB_GENES, TB_CELLS, TB_FIDELITY, TB_GENE_FIDELITY, TB_NEIGHBORS, TB_LABELS, TB_LABEL_CLASSES, TB_MARKERS, TB_COEXPR };
 
 /* the rows of one point into want[W_*] (the tables), the texts of its files into want[P_*] (started afresh) */
 static void want_point(const state_t *st, uint32_t markers, float rd, uint64_t lv, text_t *want)
@@ -211,6 +215,9 @@ static void want_point(const state_t *st, uint32_t markers, float rd, uint64_t l
     CHECK(!fastf_neighbors_summary_row(S->rate_cell, rd, lv, S->seed, nc, K, FASTF_NEIGHBORS_K, S->h_nbr.kf, S->h_nbr.kp, S->h_nbr.sh, row, sizeof row));
     add(&want[W_NBR], row); add(&want[P_NBR], fastf_neighbors_header());
     for (uint32_t c = 0; c < nc; c++) { CHECK(!fastf_neighbors_row(st->L.barcode[c], S->h_nbr.kf[c], S->h_nbr.kp[c], S->h_nbr.sh[c], row, sizeof row)); add(&want[P_NBR], row); }
+    CHECK(!fastf_coexpr_summary_row(S->rate_cell, rd, lv, S->seed, nc, K, FASTF_COEXPR_K, S->h_cx.kf, S->h_cx.kp, S->h_cx.sh, row, sizeof row));
+    add(&want[W_CX], row); add(&want[P_CX], fastf_coexpr_header());
+    for (uint32_t g = 0; g < K; g++) { CHECK(!fastf_coexpr_row(st->L.feat_id[S->h_cx.genes[g]], S->h_cx.kf[g], S->h_cx.kp[g], S->h_cx.sh[g], row, sizeof row)); add(&want[P_CX], row); }
     /* labels: the row, the classes, the cells, the confusion of the point */
     const uint8_t *const lab = S->h_lab.lab;
     const uint32_t *const cx = S->h_lab.half[0].conf, *const cy = S->h_lab.half[1].conf;
@@ -253,7 +260,7 @@ static void want_point(const state_t *st, uint32_t markers, float rd, uint64_t l
 
 /* ---- the runs ---- */
 typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_cmp_t Fd; } tables_t;
-#define ALL_FLAGS (FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS)
+#define ALL_FLAGS (FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS | FASTF_SWEEP_COEXPRESSION)
 static void tables_open(tables_t *tb, const res_verb_t *V, const char *out, const state_t *st, uint32_t markers)
 {
     memset(tb, 0, sizeof *tb);
@@ -315,12 +322,12 @@ static int run_case(const char *tmp, int verb, uint32_t nc, uint32_t nf, uint32_
             want_point(&st, markers, rd[p], lv[p], want);
             if (summary_only) continue;
             for (int k = W_TABLES; k < W_N; k++) expect_file(dir, point_file[k], want[k].p, 1);
-            CHECK(!strcmp(listing(dir), "cells.tsv.gz fidelity.tsv.gz gene_fidelity.tsv.gz genes.tsv.gz label_confusion.tsv.gz labels.tsv.gz markers.tsv.gz neighbors.tsv.gz"));
+            CHECK(!strcmp(listing(dir), "cells.tsv.gz coexpr.tsv.gz fidelity.tsv.gz gene_fidelity.tsv.gz genes.tsv.gz label_confusion.tsv.gz labels.tsv.gz markers.tsv.gz neighbors.tsv.gz"));
         }
         CHECK(!fastf_res_genes_close(&tb.G, 1) && !fastf_res_cells_close(&tb.C, 1) && !fastf_res_cmp_close(&tb.Fd, 1));
         for (int k = 1; k < W_TABLES; k++) expect_file(out, table_name(&V, table_of[k], ""), want[k].p, 0);
         CHECK(!strcmp(listing(out), left[summary_only]));
-        CHECK(T.neighbors > 0 && T.labels > 0 && T.markers > 0 && T.gene_fid > 0 && T.fidelity > 0);
+        CHECK(T.neighbors > 0 && T.labels > 0 && T.markers > 0 && T.coexpr > 0 && T.gene_fid > 0 && T.fidelity > 0);
         remove_tree(out);
     }
 
@@ -350,6 +357,7 @@ static int run_case(const char *tmp, int verb, uint32_t nc, uint32_t nf, uint32_
     /* subsets: each comparison alone, labels without markers */
     static const struct { uint32_t flags; int labels; uint32_t markers; int table[3]; } sub[] = {
         { FASTF_SWEEP_FIDELITY, 0, 0, { TB_FIDELITY, -1, -1 } }, { FASTF_SWEEP_GENE_FIDELITY, 0, 0, { TB_GENE_FIDELITY, -1, -1 } }, { FASTF_SWEEP_NEIGHBORS, 0, 0, { TB_NEIGHBORS, -1, -1 } },
+        { FASTF_SWEEP_COEXPRESSION, 0, 0, { TB_COEXPR, -1, -1 } },
         { 0, 1, 0, { TB_LABEL_CLASSES, TB_LABELS, -1 } }, { 0, 1, 1, { TB_LABEL_CLASSES, TB_LABELS, TB_MARKERS } }, { 0, 0, 0, { -1, -1, -1 } } };
     for (size_t s = 0; s < sizeof sub / sizeof *sub; s++) {
         char names[256] = "";
