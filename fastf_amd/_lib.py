@@ -141,6 +141,9 @@ ABI_SYMBOLS = [
     "fastf_sweep_label_classes_header", "fastf_cap_label_classes_header", "fastf_level_label_classes_header", "fastf_labels_row",
     "fastf_label_confusion_header", "fastf_label_confusion_row", "fastf_labels_summary_row", "fastf_label_classes_row",
     "fastf_sweep_labels", "fastf_cap_labels", "fastf_level_labels", "fastf_dev_label_votes",
+    # --mapping of sweep, cap and level
+    "fastf_mapping_header", "fastf_sweep_mapping_header", "fastf_cap_mapping_header", "fastf_level_mapping_header", "fastf_mapping_row",
+    "fastf_mapping_summary_row", "fastf_mapping_from_coo", "fastf_dev_mapping", "fastf_sweep_mapping", "fastf_cap_mapping", "fastf_level_mapping",
     # --markers of sweep, cap and level
     "fastf_marker_auc", "fastf_marker_auc_form", "fastf_marker_rank", "fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header",
     "fastf_level_markers_header", "fastf_markers_row", "fastf_markers_summary_rows", "fastf_sweep_markers", "fastf_cap_markers", "fastf_level_markers",
@@ -431,6 +434,16 @@ def lib():
     L.fastf_cap_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
     L.fastf_level_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
     L.fastf_dev_marker_auc.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    for name in ("fastf_mapping_header", "fastf_sweep_mapping_header", "fastf_cap_mapping_header", "fastf_level_mapping_header"):
+        getattr(L, name).restype = C.c_char_p
+        getattr(L, name).argtypes = []
+    L.fastf_mapping_row.argtypes = [C.c_char_p, u64, u32, u32, u32, u32, C.c_char_p, C.c_char_p, sz]
+    L.fastf_mapping_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_mapping_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, u32, u32, vp, vp, vp, vp]
+    L.fastf_dev_mapping.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    L.fastf_sweep_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
+    L.fastf_cap_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
+    L.fastf_level_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
     for name in ("fastf_coexpr_header", "fastf_sweep_coexpr_header", "fastf_cap_coexpr_header", "fastf_level_coexpr_header"):
         getattr(L, name).restype = C.c_char_p
     L.fastf_coexpr_check_range.argtypes = [u32, u64]

@@ -1,5 +1,5 @@
 // analysis_entry.hpp — the fastf_dev_* entry points of the grid verbs' analyses (--genes, --cells, --fidelity, --gene-fidelity,
-// --neighbors, --labels, --markers, cap's hit counts and decision plane, level's search step): launch wrappers around the kernels
+// --neighbors, --mapping, --labels, --markers, cap's hit counts and decision plane, level's search step): launch wrappers around the kernels
 // of the headers below.  Included by umi_engine.hip behind the engine core; what they keep on an engine is its AnalysisState.
 #pragma once
 #include "cap_kernels.hpp"
@@ -9,6 +9,7 @@
 #include "fidelity_kernels.hpp"
 #include "gene_fidelity_kernels.hpp"
 #include "neighbors_kernels.hpp"
+#include "mapping_kernels.hpp"
 #include "coexpr_kernels.hpp"
 #include "labels_kernels.hpp"
 #include "markers_kernels.hpp"
@@ -250,6 +251,59 @@ extern "C" int fastf_dev_neighbors_shared(fastf_engine_t* e, const uint32_t* d_i
     hipLaunchKernelGGL(nbr_shared_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, d_idx_a, d_cnt_a, d_idx_b, d_cnt_b, n_cells, k, d_shared);
     HIP_OK(hipGetLastError());
     dbg_sync(s, "neighbors shared");
+    return 0;
+} FASTF_CATCH_INT
+
+// --mapping: the cells of a point looked up among the full-depth cells (mapping_kernels.hpp).  d_planes_point (planes_point planes) and
+// d_planes_full (planes_full planes, at least as many: the point's counts are a subsample of the pair's): what fastf_dev_neighbor_planes
+// filled for (n_cells, K) from the two row sets; d_norms_full: the norms fastf_dev_neighbors left for the full rows.  First the largest
+// point norm (*max_norm_point_out) and the largest full norm are reduced and read back: fastf_neighbors_check_norm refuses either at 2^42
+// and beyond and nothing more is launched.  Then d_self_dot[i] = e_ii (u64), and d_idx, d_cnt in the layout fastf_dev_neighbors writes —
+// M(i), k from 1 to 64 — and d_self_rank[i] (u32; 0xFFFFFFFF where e_ii == 0).  The dot products come from the i8 MFMA, under
+// FASTF_MAPPING_MFMA=0 from ordinary integer instructions: the same numbers.  Synchronises the stream once, before the two kernels.
+extern "C" int fastf_dev_mapping(fastf_engine_t* e, const void* d_planes_point, uint32_t planes_point, const void* d_planes_full, uint32_t planes_full,
+                                 uint32_t n_cells, uint32_t K, uint32_t k, const uint64_t* d_norms_full, uint32_t* d_idx, uint32_t* d_cnt,
+                                 uint64_t* d_self_dot, uint32_t* d_self_rank, uint64_t* max_norm_point_out, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > NBR_MAX_K) return set_err("fastf_dev_mapping: k = %u, from 1 to %u", k, NBR_MAX_K);
+    if (planes_full < 1 || planes_full > NBR_MAX_PLANES) return set_err("fastf_dev_mapping: %u planes of the full rows, from 1 to %u", planes_full, NBR_MAX_PLANES);
+    if (planes_point < 1 || planes_point > planes_full) return set_err("fastf_dev_mapping: %u planes of the point, from 1 to the %u of the full rows", planes_point, planes_full);
+    if (K > NBR_MAX_GENES) return set_err("fastf_dev_mapping: %u genes, at most %u", K, NBR_MAX_GENES);
+    if (max_norm_point_out) *max_norm_point_out = 0;
+    if (!n_cells) return 0;
+    if (!d_planes_point || !d_planes_full || !d_norms_full || !d_idx || !d_cnt || !d_self_dot || !d_self_rank) return set_err("fastf_dev_mapping: null argument");
+    uint32_t n_pad = 0, K_pad = 0;
+    fastf_neighbors_pad(n_cells, K, &n_pad, &K_pad);
+    if (e->an.d_nbr.ensure(64)) return 1;
+    u64* const d_max = (u64*)e->an.d_nbr.p + 2;                            // (words 2 and 3: the point's, the full rows')
+    HIP_OK(hipMemsetAsync(d_max, 0, 2 * sizeof(u64), s));
+    hipLaunchKernelGGL(nbr_norms_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_planes_point, n_cells, n_pad, K_pad,
+                       planes_point, (u64*)nullptr, d_max);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(map_max_kernel, dim3(std::min<u32>((n_cells + 255) / 256, 4 * e->grid_cus)), dim3(256), 0, s, (const u64*)d_norms_full, n_cells, d_max + 1);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 max_norm[2] = {0, 0};
+    if (copy_d2h(max_norm, d_max, sizeof max_norm)) return 1;
+    if (max_norm_point_out) *max_norm_point_out = max_norm[0];
+    if (fastf_neighbors_check_norm(max_norm[1]) || fastf_neighbors_check_norm(max_norm[0])) return 1;
+    hipLaunchKernelGGL(map_diag_kernel, dim3(std::min<u32>((n_cells + 3) / 4, 8 * e->grid_cus)), dim3(256), 0, s, (const unsigned char*)d_planes_point, planes_point,
+                       (const unsigned char*)d_planes_full, planes_full, n_cells, n_pad, K_pad, (u64*)d_self_dot);
+    HIP_OK(hipGetLastError());
+    const char* mf = getenv("FASTF_MAPPING_MFMA");
+    const bool mfma = !(mf && mf[0] == '0');
+    using gram_t = decltype(&map_gram_kernel<1, 1, false>);
+    static constexpr gram_t gram[6][2] = {                                  // [pair (PQ, PF), PQ <= PF: PF (PF - 1) / 2 + PQ - 1][mfma]
+        {map_gram_kernel<1, 1, false>, map_gram_kernel<1, 1, true>}, {map_gram_kernel<1, 2, false>, map_gram_kernel<1, 2, true>},
+        {map_gram_kernel<2, 2, false>, map_gram_kernel<2, 2, true>}, {map_gram_kernel<1, 3, false>, map_gram_kernel<1, 3, true>},
+        {map_gram_kernel<2, 3, false>, map_gram_kernel<2, 3, true>}, {map_gram_kernel<3, 3, false>, map_gram_kernel<3, 3, true>}};
+    if (lds_attr_once(e->an.attr[AN_MAP_GRAM], (size_t)NBR_WAVES * nbr_wave_words(NBR_MAX_K) * sizeof(u64), gram[0], 12)) return 1;
+    hipLaunchKernelGGL(gram[planes_full * (planes_full - 1) / 2 + planes_point - 1][mfma], dim3((n_cells + NBR_ROWS - 1) / NBR_ROWS), dim3(NBR_THREADS),
+                       (size_t)NBR_WAVES * nbr_wave_words(k) * sizeof(u64), s, (const unsigned char*)d_planes_point, (const unsigned char*)d_planes_full, n_cells, n_pad, K_pad, k,
+                       (const u64*)d_norms_full, (const u64*)d_self_dot, d_idx, d_cnt, d_self_rank);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "mapping");
     return 0;
 } FASTF_CATCH_INT
 

@@ -39,6 +39,7 @@ int fastf_res_err(const char *fmt, ...)
     X(TB_LABEL_CLASSES, label_classes, "seed\tlabel\tcells\tcorrect_full\tcorrect_point\tpredicted_full\tpredicted_point\n") \
     X(TB_MARKERS, markers, "seed\tlabel\tn_in\tn_out\ttop\tkept\tauc_full_mean\tauc_point_mean\n") \
     X(TB_COEXPR, coexpr, "seed\tn_cells\thvg_k\tk\tgenes_defined\tsum_k_full\tsum_k_point\tsum_shared\tmean_kept\tgenes_half_kept\n") \
+    X(TB_MAPPING, mapping, "seed\tn_cells\thvg_k\tk\tcells_defined\tself_top1\tself_topk\tmedian_self_rank\tp90_self_rank\tmean_hood\tcells_labelled\taccuracy_map\n") \
     X(TB_REPS, reps, "n_reps\tn_cells" REPS_STAT4("sampled_reads") REPS_STAT4("sampled_valid_reads") REPS_STAT4("nnz") REPS_STAT4("umis") \
         REPS_STAT4("saturation") REPS_STAT4("median_umis_per_cell") REPS_STAT4("median_genes_per_cell") "\n") \
     X(TB_GENES_REPS, genes_reps, "n_reps" REPS_STAT4("genes_detected") "\tgenes_in_all_reps\tgenes_in_any_rep\n")
@@ -515,17 +516,17 @@ static int nbr_precedes(uint64_t dj, uint64_t nj, uint32_t j, uint64_t dl, uint6
 }
 static int cmp_u32(const void *a, const void *b) { const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b; return x < y ? -1 : x > y; }
 
-int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
-                             uint32_t *idx, uint32_t *cnt, uint64_t *norms)
+/* the rows of a COO matrix with a slot in slot_map, cell by cell (a counting sort by cell): rs, rv = slot and count of the rows
+ * start[c] .. start[c + 1] of cell c (0-based), nn[c] the squared norm (saturating), max_norm their maximum.  Rows in any order */
+typedef struct { size_t *start; uint32_t *rs, *rv; uint64_t *nn, max_norm; } nbr_rows_t;
+static void nbr_rows_free(nbr_rows_t *o) { free(o->start); free(o->rs); free(o->rv); free(o->nn); memset(o, 0, sizeof *o); }
+static int nbr_rows_build(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, nbr_rows_t *o)
 {
-    if (!m || !slot_map || (n_cells && (!idx || !cnt)) || (m->nnz && (!m->feature || !m->cell || !m->count))) return fastf_res_err("null argument");
-    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return fastf_res_err("neighbors: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
-    int rc = 1;
-    /* the rows with a slot, cell by cell (a counting sort by cell): slot and count */
-    size_t *start = (size_t *)calloc((size_t)n_cells + 2, sizeof *start);
-    uint64_t *nn = (uint64_t *)calloc((size_t)n_cells + 1, sizeof *nn), *vec = (uint64_t *)calloc(FASTF_HVG_TOP, sizeof *vec), *bd = (uint64_t *)malloc(FASTF_NEIGHBORS_MAX_K * sizeof *bd);
-    uint32_t *rs = NULL, *rv = NULL;
-    if (!start || !nn || !vec || !bd) { fastf_res_err("out of memory"); goto done; }
+    memset(o, 0, sizeof *o);
+    o->start = (size_t *)calloc((size_t)n_cells + 2, sizeof *o->start);
+    o->nn = (uint64_t *)calloc((size_t)n_cells + 1, sizeof *o->nn);
+    if (!o->start || !o->nn) return fastf_res_err("out of memory");
+    size_t *const start = o->start;
     size_t kept = 0;
     for (size_t r = 0; r < m->nnz; r++) {
         const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
@@ -533,46 +534,63 @@ int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint1
         start[c + 2]++; kept++;
     }
     for (uint32_t c = 0; c < n_cells; c++) start[c + 2] += start[c + 1];
-    rs = (uint32_t *)malloc((kept + 1) * sizeof *rs); rv = (uint32_t *)malloc((kept + 1) * sizeof *rv);
-    if (!rs || !rv) { fastf_res_err("out of memory"); goto done; }
-    uint64_t max_norm = 0;
+    o->rs = (uint32_t *)malloc((kept + 1) * sizeof *o->rs); o->rv = (uint32_t *)malloc((kept + 1) * sizeof *o->rv);
+    if (!o->rs || !o->rv) return fastf_res_err("out of memory");
     for (size_t r = 0; r < m->nnz; r++) {
         const uint32_t c = m->cell[r] - 1u, f = m->feature[r];
         if (c >= n_cells || f - 1u >= n_features || slot_map[f] >= FASTF_HVG_TOP) continue;
         const size_t at = start[c + 1]++;
-        rs[at] = slot_map[f]; rv[at] = m->count[r];
-        const u128 sq = (u128)nn[c] + (u128)m->count[r] * m->count[r];
-        nn[c] = sq >> 64 ? UINT64_MAX : (uint64_t)sq;
+        o->rs[at] = slot_map[f]; o->rv[at] = m->count[r];
+        const u128 sq = (u128)o->nn[c] + (u128)m->count[r] * m->count[r];
+        o->nn[c] = sq >> 64 ? UINT64_MAX : (uint64_t)sq;
     }
-    for (uint32_t c = 0; c < n_cells; c++) if (nn[c] > max_norm) max_norm = nn[c];      /* (start[c] .. start[c + 1]: the rows of cell c) */
-    if (fastf_neighbors_check_norm(max_norm)) goto done;
+    for (uint32_t c = 0; c < n_cells; c++) if (o->nn[c] > o->max_norm) o->max_norm = o->nn[c];      /* (start[c] .. start[c + 1]: the rows of cell c) */
+    return 0;
+}
+
+/* candidate (d, j) into out[0 .. *have) — kept in the order of the definition, best first, bd[] their d, nn[] the candidates' norms; a
+ * later cell never precedes an equal earlier one */
+static void nbr_list_insert(uint32_t *out, uint64_t *bd, uint32_t *have, uint32_t k, const uint64_t *nn, uint64_t d, uint32_t j)
+{
+    uint32_t at = *have;
+    while (at > 0 && nbr_precedes(d, nn[j], j, bd[at - 1], nn[out[at - 1]], out[at - 1])) at--;
+    if (at >= k) return;
+    const uint32_t last = *have < k ? *have : k - 1;
+    for (uint32_t s = last; s > at; s--) { out[s] = out[s - 1]; bd[s] = bd[s - 1]; }
+    out[at] = j; bd[at] = d;
+    if (*have < k) ++*have;
+}
+
+int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
+                             uint32_t *idx, uint32_t *cnt, uint64_t *norms)
+{
+    if (!m || !slot_map || (n_cells && (!idx || !cnt)) || (m->nnz && (!m->feature || !m->cell || !m->count))) return fastf_res_err("null argument");
+    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return fastf_res_err("neighbors: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
+    int rc = 1;
+    nbr_rows_t R;
+    uint64_t *vec = (uint64_t *)calloc(FASTF_HVG_TOP, sizeof *vec), *bd = (uint64_t *)malloc(FASTF_NEIGHBORS_MAX_K * sizeof *bd);
+    if (nbr_rows_build(m, n_cells, slot_map, n_features, &R)) goto done;
+    if (!vec || !bd) { fastf_res_err("out of memory"); goto done; }
+    if (fastf_neighbors_check_norm(R.max_norm)) goto done;
     for (uint32_t i = 0; i < n_cells; i++) {
         uint32_t *const out = idx + (size_t)i * k;
         uint32_t have = 0;
-        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] += rv[r];
+        for (size_t r = R.start[i]; r < R.start[i + 1]; r++) vec[R.rs[r]] += R.rv[r];
         for (uint32_t j = 0; j < n_cells; j++) {
             if (j == i) continue;
             uint64_t d = 0;
-            for (size_t r = start[j]; r < start[j + 1]; r++) d += vec[rs[r]] * rv[r];
-            if (!d) continue;
-            /* out[0 .. have) in the order of the definition, best first; a later cell never precedes an equal earlier one */
-            uint32_t at = have;
-            while (at > 0 && nbr_precedes(d, nn[j], j, bd[at - 1], nn[out[at - 1]], out[at - 1])) at--;
-            if (at >= k) continue;
-            const uint32_t last = have < k ? have : k - 1;
-            for (uint32_t s = last; s > at; s--) { out[s] = out[s - 1]; bd[s] = bd[s - 1]; }
-            out[at] = j; bd[at] = d;
-            if (have < k) have++;
+            for (size_t r = R.start[j]; r < R.start[j + 1]; r++) d += vec[R.rs[r]] * R.rv[r];
+            if (d) nbr_list_insert(out, bd, &have, k, R.nn, d, j);
         }
-        for (size_t r = start[i]; r < start[i + 1]; r++) vec[rs[r]] = 0;
+        for (size_t r = R.start[i]; r < R.start[i + 1]; r++) vec[R.rs[r]] = 0;
         qsort(out, have, sizeof *out, cmp_u32);
         for (uint32_t s = have; s < k; s++) out[s] = UINT32_MAX;
         cnt[i] = have;
-        if (norms) norms[i] = nn[i];
+        if (norms) norms[i] = R.nn[i];
     }
     rc = 0;
 done:
-    free(start); free(nn); free(vec); free(bd); free(rs); free(rv);
+    nbr_rows_free(&R); free(vec); free(bd);
     return rc;
 }
 
@@ -614,6 +632,96 @@ int fastf_neighbors_summary_row(float rate_cell, float rate_depth, uint64_t list
     if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
     else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
     const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, hvg_k, k, nd, f[0], f[1], f[2], f[3]);
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("summary row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* --mapping: the host twin, the rows                                   */
+/* ------------------------------------------------------------------ */
+int fastf_mapping_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
+                           uint32_t *idx, uint32_t *cnt, uint64_t *self_dot, uint32_t *self_rank)
+{
+    if (!full || !point || !slot_map || (n_cells && (!idx || !cnt || !self_dot || !self_rank)) || (full->nnz && (!full->feature || !full->cell || !full->count)) ||
+        (point->nnz && (!point->feature || !point->cell || !point->count))) return fastf_res_err("null argument");
+    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return fastf_res_err("mapping: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
+    int rc = 1;
+    nbr_rows_t X, Y;
+    uint64_t *vec = (uint64_t *)calloc(FASTF_HVG_TOP, sizeof *vec), *bd = (uint64_t *)malloc(FASTF_NEIGHBORS_MAX_K * sizeof *bd);
+    uint64_t *e = (uint64_t *)malloc(((size_t)n_cells + 1) * sizeof *e);
+    memset(&Y, 0, sizeof Y);
+    if (nbr_rows_build(full, n_cells, slot_map, n_features, &X) || nbr_rows_build(point, n_cells, slot_map, n_features, &Y)) goto done;
+    if (!vec || !bd || !e) { fastf_res_err("out of memory"); goto done; }
+    if (fastf_neighbors_check_norm(X.max_norm) || fastf_neighbors_check_norm(Y.max_norm)) goto done;
+    for (uint32_t i = 0; i < n_cells; i++) {
+        uint32_t *const out = idx + (size_t)i * k;
+        uint32_t have = 0, rank = 0;
+        for (size_t r = Y.start[i]; r < Y.start[i + 1]; r++) vec[Y.rs[r]] += Y.rv[r];
+        for (uint32_t j = 0; j < n_cells; j++) {
+            uint64_t d = 0;
+            for (size_t r = X.start[j]; r < X.start[j + 1]; r++) d += vec[X.rs[r]] * X.rv[r];
+            e[j] = d;
+        }
+        for (size_t r = Y.start[i]; r < Y.start[i + 1]; r++) vec[Y.rs[r]] = 0;
+        const uint64_t sd = e[i];
+        for (uint32_t j = 0; j < n_cells; j++) {
+            if (j == i || !e[j]) continue;
+            if (sd) rank += (uint32_t)nbr_precedes(e[j], X.nn[j], j, sd, X.nn[i], i);
+            nbr_list_insert(out, bd, &have, k, X.nn, e[j], j);
+        }
+        qsort(out, have, sizeof *out, cmp_u32);
+        for (uint32_t s = have; s < k; s++) out[s] = UINT32_MAX;
+        cnt[i] = have; self_dot[i] = sd; self_rank[i] = sd ? rank : FASTF_MAPPING_NO_RANK;
+    }
+    rc = 0;
+done:
+    nbr_rows_free(&X); nbr_rows_free(&Y); free(vec); free(bd); free(e);
+    return rc;
+}
+
+const char *fastf_mapping_header(void) { return "barcode\tself_dot\tself_rank\tk_map\tk_full\thood\tpred_map\n"; }
+
+int fastf_mapping_row(const char *barcode, uint64_t self_dot, uint32_t self_rank, uint32_t k_map, uint32_t k_full, uint32_t hood, const char *pred_map,
+                      char *buf, size_t cap)
+{
+    if (!barcode || !buf) return fastf_res_err("null argument");
+    char f[24];
+    if (self_rank != FASTF_MAPPING_NO_RANK) snprintf(f, sizeof f, "%u", self_rank); else snprintf(f, sizeof f, "NA");
+    const int n = snprintf(buf, cap, "%s\t%llu\t%s\t%u\t%u\t%u\t%s\n", barcode, (unsigned long long)self_dot, f, k_map, k_full, hood, pred_map ? pred_map : "NA");
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("mapping row too long") : 0;
+}
+
+int fastf_mapping_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
+                              const uint64_t *self_dot, const uint32_t *self_rank, const uint32_t *k_full, const uint32_t *hood, const uint8_t *lab,
+                              const uint8_t *same_map, const uint8_t *labelled_map, char *buf, size_t cap)
+{
+    if (!buf || (n_cells && (!self_dot || !self_rank || !k_full || !hood)) || (lab && n_cells && (!same_map || !labelled_map))) return fastf_res_err("null argument");
+    double *rk = (double *)malloc(((size_t)n_cells + 1) * sizeof *rk);
+    if (!rk) return fastf_res_err("out of memory");
+    size_t nd = 0, top1 = 0, topk = 0, n_hood = 0;
+    uint64_t cells_labelled = 0, same = 0, labelled = 0;
+    double hood_sum = 0.0;
+    for (uint32_t c = 0; c < n_cells; c++) {
+        if (self_dot[c] > 0) { rk[nd++] = (double)self_rank[c]; top1 += self_rank[c] == 0; topk += self_rank[c] < k; }
+        if (k_full[c]) { hood_sum += (double)hood[c] / (double)k_full[c]; n_hood++; }
+        if (lab && lab[c]) { cells_labelled++; same += same_map[c]; labelled += labelled_map[c]; }
+    }
+    char f[7][40];
+    if (nd) {
+        qsort(rk, nd, sizeof *rk, cmp_dbl);
+        snprintf(f[0], sizeof f[0], "%.6f", (double)top1 / (double)nd);
+        snprintf(f[1], sizeof f[1], "%.6f", (double)topk / (double)nd);
+        snprintf(f[2], sizeof f[2], "%.6f", median_sorted(rk, nd));
+        snprintf(f[3], sizeof f[3], "%.0f", rk[(size_t)floor(0.9 * (double)(nd - 1))]);
+    } else for (int c = 0; c < 4; c++) snprintf(f[c], sizeof f[c], "NA");
+    if (n_hood) snprintf(f[4], sizeof f[4], "%.6f", hood_sum / (double)n_hood); else snprintf(f[4], sizeof f[4], "NA");
+    if (lab) snprintf(f[5], sizeof f[5], "%llu", (unsigned long long)cells_labelled); else snprintf(f[5], sizeof f[5], "NA");
+    if (lab && labelled) snprintf(f[6], sizeof f[6], "%.6f", (double)same / (double)labelled); else snprintf(f[6], sizeof f[6], "NA");
+    free(rk);
+    char second[32];
+    if (list_value) snprintf(second, sizeof second, "%llu", (unsigned long long)list_value);
+    else snprintf(second, sizeof second, "%.3f", (double)rate_depth);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%zu\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, hvg_k, k, nd, f[0], f[1], f[2], f[3],
+                           f[4], f[5], f[6]);
     return (n < 0 || (size_t)n >= cap) ? fastf_res_err("summary row too long") : 0;
 }
 

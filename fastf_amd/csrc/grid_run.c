@@ -37,6 +37,7 @@ static int grid_refuse(const res_verb_t *V, const res_job_t *job, int labels, in
     if (fallback && cells_first && (f & FASTF_SWEEP_CELLS)) opt = "--cells";
     else if (labels) opt = "--labels";
     else if (f & FASTF_SWEEP_NEIGHBORS) opt = "--neighbors";
+    else if (job->mapping) opt = "--mapping";
     else if (f & FASTF_SWEEP_COEXPRESSION) opt = "--coexpression";
     else if (fallback && (f & FASTF_SWEEP_FIDELITY) && (f & FASTF_SWEEP_GENE_FIDELITY)) { opt = "--fidelity and --gene-fidelity"; needs = "need"; }
     else if (fallback && (f & FASTF_SWEEP_FIDELITY)) opt = "--fidelity";      /* (the full rows live on the device alone: bam2db() point by point has none) */
@@ -66,7 +67,7 @@ static int grid_open(const res_verb_t *V, const res_job_t *job, const fastf_labe
     return fastf_res_tsv_open(&tb->tsv, out, name, V->header()) ||
            fastf_res_genes_open(&tb->G, genes, V, out, job->n_c * job->n_list, job->reps) ||
            fastf_res_cells_open(&tb->C, (f & FASTF_SWEEP_CELLS) != 0, V, out) ||
-           fastf_res_cmp_open(&tb->Fd, V, out, f, labels, job->markers) ||
+           fastf_res_cmp_open(&tb->Fd, V, out, f, labels, job->markers, job->mapping) ||
            fastf_res_reps_open(&tb->P, job->reps, V, out, job->seeds, job->n_s, job->n_c, job->n_list, genes, device);
 }
 
@@ -196,6 +197,9 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
         if (res_cmp_on(Fd, CMP_LABELS)) fprintf(stderr, "[%s] --labels: %u labels, labels_unknown %llu; %sthe label arrays of every pair, the vote calls, their D2H, rows and files %.3f s\n", v, fastf_labels_count(Fd->labels),
                                 (unsigned long long)fastf_labels_unknown(Fd->labels), nbr ? "" : "the neighbour sets of --neighbors and what they need, ", T.labels + (nbr ? 0.0 : T.neighbors));
         if (nbr) fprintf(stderr, "[%s] --neighbors: %sthe planes, the Gram products and selections, the shared counts, their D2H, rows and files %.3f s\n", v, fid || gene_fid ? "" : "the full-depth rows and per-gene sums of every pair, ", T.neighbors);
+        if (res_cmp_on(Fd, CMP_MAPPING)) fprintf(stderr, "[%s] --mapping: %sthe copy of the full planes, the mapping calls, the shared counts%s, their D2H, rows and files %.3f s\n", v,
+                                                 nbr || res_cmp_on(Fd, CMP_LABELS) ? "" : "the neighbour sets of --neighbors and what they need, ", res_cmp_on(Fd, CMP_LABELS) ? " and votes" : "",
+                                                 T.mapping + (nbr || res_cmp_on(Fd, CMP_LABELS) ? 0.0 : T.neighbors));
         if (res_cmp_on(Fd, CMP_COEXPR)) fprintf(stderr, "[%s] --coexpression: %sthe gene-major planes, the Gram sums and selections, the shared counts, their D2H, rows and files %.3f s\n", v,
                                                 fid || gene_fid || nbr || res_cmp_on(Fd, CMP_LABELS) ? "" : "the full-depth rows and per-gene sums of every pair, ", T.coexpr);
     }

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void nbr_planes_kernel(const u32* __restrict__
     }
 }
 
-// One wave per row.  *max_out was cleared by the caller.
+// One wave per row.  *max_out was cleared by the caller.  norms == nullptr: the maximum alone (mapping_kernels.hpp).
 __global__ __launch_bounds__(256) void nbr_norms_kernel(const unsigned char* __restrict__ planes, u32 n, u32 n_pad, u32 K_pad, u32 P,
                                                         u64* __restrict__ norms, u64* __restrict__ max_out) {
     const int lane = lane_id();
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void nbr_norms_kernel(const unsigned char* __r
             }
         }
         sum = wave_sum64(sum);
-        if (lane == 0) { norms[i] = sum; if (sum) atomicMax(reinterpret_cast<unsigned long long*>(max_out), (unsigned long long)sum); }
+        if (lane == 0) { if (norms) norms[i] = sum; if (sum) atomicMax(reinterpret_cast<unsigned long long*>(max_out), (unsigned long long)sum); }
     }
 }
 
@@ -108,6 +108,88 @@ __device__ __forceinline__ u32 nbr_dot16(const uint4 a, const uint4 b) {
 #endif
 }
 
+// The list of one query row in the wave's LDS slots (column r of s_d and s_i): its entries and the worst of a full list — slot, index, d, norm.
+struct NbrList { u32 cnt = 0, ws = 0, wi = 0; u64 wd = 0, wn = 0; };
+
+// Candidate (d, nj, j) offered to the list of k slots; the candidates of a row come in ascending j (step 2 of nbr_gram_kernel).
+__device__ __forceinline__ void nbr_list_offer(NbrList& L, u64* s_d, u32* s_i, u32 r, u32 k, const u64* __restrict__ norms, u64 d, u64 nj, u32 j) {
+    bool changed = false;
+    if (L.cnt < k) { s_d[L.cnt * NBR_TILE + r] = d; s_i[L.cnt * NBR_TILE + r] = j; ++L.cnt; changed = L.cnt == k; }
+    else if (nbr_precedes(d, nj, j, L.wd, L.wn, L.wi)) { s_d[L.ws * NBR_TILE + r] = d; s_i[L.ws * NBR_TILE + r] = j; changed = true; }
+    if (changed) {                                                         // the list is full: its worst entry
+        L.ws = 0; L.wd = s_d[r]; L.wi = s_i[r]; L.wn = norms[L.wi];
+        for (u32 s = 1; s < k; ++s) {
+            const u64 ds = s_d[s * NBR_TILE + r]; const u32 is = s_i[s * NBR_TILE + r]; const u64 ns = norms[is];
+            if (nbr_precedes(L.wd, L.wn, L.wi, ds, ns, is)) { L.ws = s; L.wd = ds; L.wi = is; L.wn = ns; }
+        }
+    }
+}
+
+// The slots sorted by cell index and written: row[s], s < *cnt_out; the other slots of the row get NBR_NONE.
+__device__ __forceinline__ void nbr_list_write(const NbrList& L, u32* s_i, u32 r, u32 k, u32* __restrict__ row, u32* __restrict__ cnt_out) {
+    for (u32 s = 1; s < L.cnt; ++s) {                                      // by ascending cell index (insertion sort of at most 64 slots)
+        const u32 v = s_i[s * NBR_TILE + r];
+        u32 t = s;
+        for (; t > 0 && s_i[(t - 1) * NBR_TILE + r] > v; --t) s_i[t * NBR_TILE + r] = s_i[(t - 1) * NBR_TILE + r];
+        s_i[t * NBR_TILE + r] = v;
+    }
+    for (u32 s = 0; s < k; ++s) row[s] = s < L.cnt ? s_i[s * NBR_TILE + r] : NBR_NONE;
+    *cnt_out = L.cnt;
+}
+
+// Step 1 of nbr_gram_kernel for one column tile, and its d into the LDS tile: the 32 x 32 dot products of the rows row0 .. row0 + 31 of
+// planes_a (PA planes) with the rows jt .. jt + 31 of planes_b (PB planes), both sets n_pad x K_pad a plane, as u64 in s_tile[row][column].
+// The at most min(PA, PB) products with the same a + b share one i32 accumulator.
+template <int PA, int PB, bool MFMA>
+__device__ __forceinline__ void nbr_tile_dots(const unsigned char* __restrict__ planes_a, const unsigned char* __restrict__ planes_b, u64 plane_bytes, u32 K_pad,
+                                              u32 row0, u32 jt, u32 r, u32 h, u64* s_tile) {
+    constexpr int T = PA + PB - 1;
+    nbr_v16i acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0;
+    if constexpr (MFMA) {
+        const unsigned char* const pa = planes_a + (u64)(row0 + r) * K_pad + 16u * h;
+        const unsigned char* const pb = planes_b + (u64)(jt + r) * K_pad + 16u * h;
+        for (u32 s = 0; s < K_pad; s += NBR_KSTEP) {
+            nbr_v4i a[PA], b[PB];
+#pragma unroll
+            for (int p = 0; p < PA; ++p) a[p] = *reinterpret_cast<const nbr_v4i*>(pa + p * plane_bytes + s);
+#pragma unroll
+            for (int p = 0; p < PB; ++p) b[p] = *reinterpret_cast<const nbr_v4i*>(pb + p * plane_bytes + s);
+#pragma unroll
+            for (int x = 0; x < PA; ++x)
+#pragma unroll
+                for (int y = 0; y < PB; ++y) acc[x + y] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[x], b[y], acc[x + y], 0, 0, 0);
+        }
+    } else {
+        const unsigned char* const pb = planes_b + (u64)(jt + r) * K_pad;
+        for (u32 s = 0; s < K_pad; s += 16) {
+            uint4 b[PB];
+#pragma unroll
+            for (int p = 0; p < PB; ++p) b[p] = *reinterpret_cast<const uint4*>(pb + p * plane_bytes + s);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const u32 row = row0 + (u32)(e & 3) + 8u * (u32)(e >> 2) + 4u * h;
+#pragma unroll
+                for (int x = 0; x < PA; ++x) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(planes_a + x * plane_bytes + (u64)row * K_pad + s);
+#pragma unroll
+                    for (int y = 0; y < PB; ++y) acc[x + y][e] += (int)nbr_dot16(a, b[y]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        u64 d = 0;
+#pragma unroll
+        for (int t = 0; t < T; ++t) d += (u64)(u32)acc[t][e] << (7 * t);
+        s_tile[((u32)(e & 3) + 8u * (u32)(e >> 2) + 4u * h) * NBR_TILE_PITCH + r] = d;
+    }
+}
+
 // A wave owns NBR_TILE query rows (a workgroup NBR_ROWS) and streams the column tiles 0, 32, .. in ascending order; the waves of a
 // workgroup never wait for each other.  Per column tile:
 //   1. the 32 x 32 dot products, one i32 accumulator tile per a + b.  Lane l of both forms ends with column (l & 31) and the rows
@@ -126,7 +208,6 @@ template <int P, bool MFMA>
 __global__ __launch_bounds__(NBR_THREADS) void nbr_gram_kernel(const unsigned char* __restrict__ planes, u32 n, u32 n_pad, u32 K_pad, u32 k,
                                                                const u64* __restrict__ norms, u32* __restrict__ idx_out, u32* __restrict__ cnt_out) {
     extern __shared__ u64 s_nbr[];
-    constexpr int T = 2 * P - 1;
     const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const u32 row0 = (blockIdx.x * NBR_WAVES + (u32)w) * NBR_TILE;
     if (row0 >= n) return;                                                 // (uniform per wave; the kernel has no workgroup barrier)
@@ -137,54 +218,10 @@ __global__ __launch_bounds__(NBR_THREADS) void nbr_gram_kernel(const unsigned ch
     const u32 r = (u32)lane & 31u, h = (u32)lane >> 5;
     const u32 me = row0 + r;                                               // the query row of lanes 0 .. 31 in step 2
     const bool sel = lane < 32 && me < n;
-    u32 cnt = 0, ws = 0, wi = 0; u64 wd = 0, wn = 0;                         // entries; the worst of a full list: slot, index, d, norm
+    NbrList L;
 
     for (u32 jt = 0; jt < n; jt += NBR_TILE) {
-        nbr_v16i acc[T];
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[t][e] = 0;
-        if constexpr (MFMA) {
-            const unsigned char* const pa = planes + (u64)(row0 + r) * K_pad + 16u * h;
-            const unsigned char* const pb = planes + (u64)(jt + r) * K_pad + 16u * h;
-            for (u32 s = 0; s < K_pad; s += NBR_KSTEP) {
-                nbr_v4i a[P], b[P];
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    a[p] = *reinterpret_cast<const nbr_v4i*>(pa + p * plane_bytes + s);
-                    b[p] = *reinterpret_cast<const nbr_v4i*>(pb + p * plane_bytes + s);
-                }
-#pragma unroll
-                for (int x = 0; x < P; ++x)
-#pragma unroll
-                    for (int y = 0; y < P; ++y) acc[x + y] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[x], b[y], acc[x + y], 0, 0, 0);
-            }
-        } else {
-            const unsigned char* const pb = planes + (u64)(jt + r) * K_pad;
-            for (u32 s = 0; s < K_pad; s += 16) {
-                uint4 b[P];
-#pragma unroll
-                for (int p = 0; p < P; ++p) b[p] = *reinterpret_cast<const uint4*>(pb + p * plane_bytes + s);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const u32 row = row0 + (u32)(e & 3) + 8u * (u32)(e >> 2) + 4u * h;
-#pragma unroll
-                    for (int x = 0; x < P; ++x) {
-                        const uint4 a = *reinterpret_cast<const uint4*>(planes + x * plane_bytes + (u64)row * K_pad + s);
-#pragma unroll
-                        for (int y = 0; y < P; ++y) acc[x + y][e] += (int)nbr_dot16(a, b[y]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            u64 d = 0;
-#pragma unroll
-            for (int t = 0; t < T; ++t) d += (u64)(u32)acc[t][e] << (7 * t);
-            s_tile[((u32)(e & 3) + 8u * (u32)(e >> 2) + 4u * h) * NBR_TILE_PITCH + r] = d;
-        }
+        nbr_tile_dots<P, P, MFMA>(planes, planes, plane_bytes, K_pad, row0, jt, r, h, s_tile);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (sel) {
             const u32 cols = n - jt < NBR_TILE ? n - jt : NBR_TILE;
@@ -192,30 +229,13 @@ __global__ __launch_bounds__(NBR_THREADS) void nbr_gram_kernel(const unsigned ch
                 const u32 j = jt + c;
                 const u64 d = s_tile[r * NBR_TILE_PITCH + c];
                 if (j == me || d == 0) continue;
-                const u64 nj = norms[j];
-                bool changed = false;
-                if (cnt < k) { s_d[cnt * NBR_TILE + r] = d; s_i[cnt * NBR_TILE + r] = j; ++cnt; changed = cnt == k; }
-                else if (nbr_precedes(d, nj, j, wd, wn, wi)) { s_d[ws * NBR_TILE + r] = d; s_i[ws * NBR_TILE + r] = j; changed = true; }
-                if (changed) {                                             // the list is full: its worst entry
-                    ws = 0; wd = s_d[r]; wi = s_i[r]; wn = norms[wi];
-                    for (u32 s = 1; s < k; ++s) {
-                        const u64 ds = s_d[s * NBR_TILE + r]; const u32 is = s_i[s * NBR_TILE + r]; const u64 ns = norms[is];
-                        if (nbr_precedes(wd, wn, wi, ds, ns, is)) { ws = s; wd = ds; wi = is; wn = ns; }
-                    }
-                }
+                nbr_list_offer(L, s_d, s_i, r, k, norms, d, norms[j], j);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     if (sel) {
-        for (u32 s = 1; s < cnt; ++s) {                                    // by ascending cell index (insertion sort of at most 64 slots)
-            const u32 v = s_i[s * NBR_TILE + r];
-            u32 t = s;
-            for (; t > 0 && s_i[(t - 1) * NBR_TILE + r] > v; --t) s_i[t * NBR_TILE + r] = s_i[(t - 1) * NBR_TILE + r];
-            s_i[t * NBR_TILE + r] = v;
-        }
-        for (u32 s = 0; s < k; ++s) idx_out[(u64)me * k + s] = s < cnt ? s_i[s * NBR_TILE + r] : NBR_NONE;
-        cnt_out[me] = cnt;
+        nbr_list_write(L, s_i, r, k, idx_out + (u64)me * k, cnt_out + me);
     }
 }
 

@@ -76,6 +76,22 @@ static inline res_nbr_pin_v res_nbr_pin_layout(void *base, size_t map_bytes, siz
     v.bytes = c.off; return v;
 }
 
+/* --mapping.  The device block: the norms of the full rows (the norms of res_nbr_v are the row set's at hand: every point overwrites
+ * them) M(i) (k a cell) and the confusion counts the vote call fills beside its
+ * votes (n_labels x (n_labels + 1), not used further), then — 8-byte aligned — the part that leaves in ONE copy of out_bytes from `sd` on, into the pinned block,
+ * which is that part alone: self_dot, self_rank, k_map (the counts of M), hood, and pred, same, labelled (u8, lab_cells each:
+ * res_lab_cells; 0 without --labels) */
+typedef struct { uint64_t *norms; uint32_t *idx, *conf; uint64_t *sd; uint32_t *rank, *km, *hood; uint8_t *pred, *same, *labelled; size_t out_bytes, bytes; } res_map_v;
+static inline res_map_v res_map_layout(void *base, size_t k, size_t nc, size_t lab_cells, size_t n_labels, int pinned)
+{
+    res_carve_t c = { (char *)base, 0 }; res_map_v v;
+    RES_CARVE(c, v.norms, pinned ? 0 : nc); RES_CARVE(c, v.idx, pinned ? 0 : nc * k); RES_CARVE(c, v.conf, pinned ? 0 : n_labels * (n_labels + 1));
+    const size_t out = c.off = (c.off + 7) & ~(size_t)7;
+    RES_CARVE(c, v.sd, nc); RES_CARVE(c, v.rank, nc); RES_CARVE(c, v.km, nc); RES_CARVE(c, v.hood, nc);
+    RES_CARVE(c, v.pred, lab_cells); RES_CARVE(c, v.same, lab_cells); RES_CARVE(c, v.labelled, lab_cells);
+    v.out_bytes = c.off - out; v.bytes = c.off; return v;
+}
+
 /* --coexpression, over the K genes of A (FASTF_HVG_TOP at the most).  The device block: D (K x K) and S of the row set at hand, the slot
  * map of A (map_bytes, as above: the option keeps its own, so that it runs without --neighbors), the partner slots (k a gene) of the full
  * rows [0] and of the point [1], their counts, the shared counts.  The pinned block: the map, k_full, k_point, shared and the genes of A

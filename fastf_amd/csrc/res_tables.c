@@ -369,11 +369,33 @@ static int cx_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float ra
     return 0;
 }
 
+/* --mapping: one row per barcode; pred_map as the label string with --labels */
+typedef struct { const res_rate_t *S; const fastf_labels_t *labels; } map_lines_t;
+static int map_line(gtext *t, const void *ctx, uint32_t c)
+{
+    const map_lines_t *x = (const map_lines_t *)ctx;
+    const res_rate_t *S = x->S;
+    const uint8_t pred = x->labels ? S->h_map.pred[c] : 0;
+    char line[512];
+    return fastf_mapping_row(S->L->barcode[c], S->h_map.sd[c], S->h_map.rank[c], S->h_map.km[c], S->h_nbr.kf[c], S->h_map.hood[c], pred ? fastf_labels_name(x->labels, pred) : NULL,
+                             line, sizeof line) || fastf_gt_str(t, line);
+}
+static int map_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    const map_lines_t lines = { S, C->labels };
+    char row[640];
+    if (fastf_mapping_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, S->hvg_k, FASTF_MAPPING_K, S->h_map.sd, S->h_map.rank, S->h_nbr.kf, S->h_map.hood,
+                                  C->labels ? S->h_lab.lab : NULL, S->h_map.same, S->h_map.labelled, row, sizeof row)) return 1;
+    if (dir && flat_file(dir, "mapping.tsv.gz", fastf_mapping_header(), S->n_cells, map_line, &lines)) return 1;
+    fputs(row, cmp_tsv(C, TB_MAPPING));
+    return 0;
+}
+
 /* ------------------------------------------------------------------ */
 /* the comparisons against full depth: the descriptors, open, point, close */
 /* ------------------------------------------------------------------ */
-/* ONE descriptor per comparison, in the order a point writes them: the flag bit of the verbs' flag word that switches it on (0: --labels
- * and --markers come with their argument), its tables (-1: none), its timer in res_times_t, its point writer.  A further comparison
+/* ONE descriptor per comparison, in the order a point writes them: the flag bit of the verbs' flag word that switches it on (0: --labels,
+ * --markers and --mapping come with an argument of their own), its tables (-1: none), its timer in res_times_t, its point writer.  A further comparison
  * is an entry here, its writer above and its table in GRID_TABLES (grid_rows.c) */
 static const struct {
     uint32_t flag; int table[2]; size_t timer;
@@ -383,18 +405,19 @@ static const struct {
     [CMP_LABELS]    = { 0,                         { TB_LABELS, TB_LABEL_CLASSES }, offsetof(res_times_t, labels),    lab_point },
     [CMP_MARKERS]   = { 0,                         { TB_MARKERS, -1 },              offsetof(res_times_t, markers),   mk_point },
     [CMP_COEXPR]    = { FASTF_SWEEP_COEXPRESSION,  { TB_COEXPR, -1 },               offsetof(res_times_t, coexpr),    cx_point },
+    [CMP_MAPPING]   = { 0,                         { TB_MAPPING, -1 },              offsetof(res_times_t, mapping),   map_point },
     [CMP_GENE_FID]  = { FASTF_SWEEP_GENE_FIDELITY, { TB_GENE_FIDELITY, -1 },        offsetof(res_times_t, gene_fid),  gene_fid_point },
     [CMP_FIDELITY]  = { FASTF_SWEEP_FIDELITY,      { TB_FIDELITY, -1 },             offsetof(res_times_t, fidelity),  fid_point },
 };
 
 /* the tables are opened in the order of their ids, which is the order of the renames */
-int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers)
+int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers, uint32_t mapping)
 {
     uint32_t want = 0;
     memset(C, 0, sizeof *C);
     C->labels = labels; C->markers = markers;
     for (int c = 0; c < CMP_N_; c++) {
-        if (!(c == CMP_LABELS ? labels != NULL : c == CMP_MARKERS ? markers != 0 : (flags & cmp_desc[c].flag) != 0)) continue;
+        if (!(c == CMP_LABELS ? labels != NULL : c == CMP_MARKERS ? markers != 0 : c == CMP_MAPPING ? mapping != 0 : (flags & cmp_desc[c].flag) != 0)) continue;
         C->on |= 1u << c;
         for (int k = 0; k < 2; k++) if (cmp_desc[c].table[k] >= 0) want |= 1u << (cmp_desc[c].table[k] - TB_FIDELITY);
     }
@@ -403,11 +426,12 @@ int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, u
     return 0;
 }
 
-/* what the device side computes for the comparisons that are on: the neighbour sets for --labels too */
+/* what the device side computes for the comparisons that are on: the neighbour sets for --labels and --mapping too */
 void fastf_res_cmp_cfg(const res_cmp_t *C, res_cfg_t *cfg)
 {
     cfg->fidelity = res_cmp_on(C, CMP_FIDELITY); cfg->gene_fid = res_cmp_on(C, CMP_GENE_FID); cfg->labels = res_cmp_on(C, CMP_LABELS);
-    cfg->neighbors = res_cmp_on(C, CMP_NEIGHBORS) || cfg->labels;
+    cfg->mapping = res_cmp_on(C, CMP_MAPPING);
+    cfg->neighbors = res_cmp_on(C, CMP_NEIGHBORS) || cfg->labels || cfg->mapping;
     cfg->coexpr = res_cmp_on(C, CMP_COEXPR);
     cfg->lab_t = C->labels; cfg->markers = C->markers;
 }

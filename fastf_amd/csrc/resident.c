@@ -263,6 +263,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         if (fastf_labels_assign(S->cfg.lab_t, L->barcode, n_cells, S->h_lab.lab) || (n_cells && fastf_devmem_copy(S->d_lab.lab, S->h_lab.lab, n_cells))) return RES_FAIL;
         T->labels += fastf_res_now() - tl;
     }
+    if (S->cfg.mapping) {                                   /* the device and the pinned block of the mapping.  The copy of the full planes waits for P (fastf_res_full_keep) */
+        const size_t lab_cells = S->cfg.labels ? res_lab_cells(room_cells) : 0, n_labels = S->cfg.labels ? S->n_labels : 0;
+        const size_t dev_bytes = res_map_layout(NULL, FASTF_MAPPING_K, room_cells, lab_cells, n_labels, 0).bytes;
+        if (res_room(&S->buf.map, RES_DEV, dev_bytes, device) || res_room(&S->buf.h_map, RES_PIN, res_map_layout(NULL, FASTF_MAPPING_K, room_cells, lab_cells, n_labels, 1).bytes, device))
+            return no_room(S, "the mapping arrays", dev_bytes);
+        S->d_map = res_map_layout(S->buf.map.p, FASTF_MAPPING_K, room_cells, lab_cells, n_labels, 0); S->h_map = res_map_layout(S->buf.h_map.p, FASTF_MAPPING_K, room_cells, lab_cells, n_labels, 1);
+        S->full_planes = 0;
+    }
     if (S->cfg.markers) {                                   /* the four tables of one row set on the device, of both row sets pinned, and the two rank tables */
         S->mk_set = res_mk_set_bytes(S->n_labels, FASTF_HVG_TOP);
         if (res_room(&S->buf.mk, RES_DEV, S->mk_set, device) || res_room(&S->buf.h_mk, RES_PIN, 2 * S->mk_set, device)) return no_room(S, "the marker tables", S->mk_set);
@@ -528,6 +536,25 @@ int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T
     return 0;
 }
 
+_Static_assert(FASTF_MAPPING_K == FASTF_NEIGHBORS_K, "hood compares M(i) with the full neighbour set of the same k");
+int fastf_res_point_mapping(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->cfg.mapping) return 0;
+    const res_map_v d = S->d_map;
+    uint64_t max_norm = 0;
+    const double tt = fastf_res_now();
+    /* (the point's planes are still in the plane buffer, S->nbr_planes of them: fastf_res_point_neighbors ran directly before) */
+    if (fastf_dev_mapping(S->e, S->buf.nplanes.p, S->nbr_planes, S->buf.fplanes.p, S->full_planes, S->n_cells, S->hvg_k, FASTF_MAPPING_K, d.norms, d.idx, d.km, d.sd, d.rank,
+                          &max_norm, NULL) ||
+        fastf_dev_neighbors_shared(S->e, d.idx, d.km, S->d_nbr.idx[0], S->d_nbr.cnt[0], S->n_cells, FASTF_MAPPING_K, d.hood, NULL) ||
+        (S->cfg.labels && fastf_dev_label_votes(S->e, d.idx, d.km, S->d_lab.lab, S->n_cells, FASTF_MAPPING_K, S->n_labels, d.pred, d.same, d.labelled, d.conf, NULL)) ||
+        fastf_devmem_sync())
+        return fastf_res_err("%s: --mapping at point %s: %s", S->verb, point_name, fastf_last_error_copy());
+    if (S->n_cells && fastf_devmem_copy(S->h_map.sd, d.sd, d.out_bytes)) return 1;
+    T->mapping += fastf_res_now() - tt;
+    return 0;
+}
+
 /* --markers: one kernel call on the planes at hand (S->nbr_planes of them: the full rows', point == 0, or the point's), the four tables
  * to the host in one copy, then the ranks */
 static int mk_tables(res_rate_t *S, int point)
@@ -629,6 +656,16 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
         if (mk_tables(S, 0)) return 1;
         T->markers += fastf_res_now() - tt; tt = fastf_res_now();
     }
+    if (S->cfg.mapping) {                                       /* the planes and the norms of the full rows, before the first point overwrites the plane buffer and the norms */
+        uint32_t n_pad = 0, K_pad = 0;
+        fastf_neighbors_pad(S->n_cells, S->hvg_k, &n_pad, &K_pad);
+        const size_t bytes = (size_t)S->nbr_planes * n_pad * K_pad;
+        if (res_room(&S->buf.fplanes, RES_DEV, bytes, S->device))
+            return fastf_res_err("%s: --mapping: the %u planes of the full-depth rows, %u cells x %u genes, do not fit: %zu bytes (%s)", S->verb, S->nbr_planes, n_pad, K_pad, bytes, fastf_last_error_copy());
+        if (fastf_devmem_copy(S->buf.fplanes.p, S->buf.nplanes.p, bytes) || (S->n_cells && fastf_devmem_copy(S->d_map.norms, S->d_nbr.norms, (size_t)S->n_cells * 8))) return 1;
+        S->full_planes = S->nbr_planes;
+        T->mapping += fastf_res_now() - tt; tt = fastf_res_now();
+    }
     if (S->cfg.coexpr) {                                        /* A of the pair as --neighbors ranks it (its own ranking and slot map without that option), the partner sets of the full rows, which stay */
         char where[96];
         snprintf(where, sizeof where, "cell rate %.3f, seed %u", (double)S->rate_cell, S->seed);
@@ -708,6 +745,7 @@ int fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *
     if (fastf_res_point_gene_fidelity(S, point_name, T)) return 1;
     if (fastf_res_point_neighbors(S, point_name, T)) return 1;
     if (fastf_res_point_labels(S, point_name, T)) return 1;       /* (directly behind the neighbour sets it votes with) */
+    if (fastf_res_point_mapping(S, point_name, T)) return 1;      /* (the point's byte planes against the full rows' planes) */
     if (fastf_res_point_markers(S, point_name, T)) return 1;      /* (on the byte planes those sets were made of) */
     return fastf_res_point_coexpr(S, point_name, T);             /* (on planes of its own) */
 }
@@ -1028,11 +1066,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'P', "mapping", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->labels = NULL; out->markers = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->mapping = 0; out->labels = NULL; out->markers = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1046,7 +1084,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXLMER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXPLMER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1078,6 +1116,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'Q': out->gene_fidelity = 1; break;
         case 'N': out->neighbors = 1; break;
         case 'X': out->coexpression = 1; break;
+        case 'P': out->mapping = 1; break;
         case 'L': out->labels = val; break;
         case 'M': markers_text = val; break;
         case 'E': seeds_text = val; break;
@@ -1143,6 +1182,7 @@ void fastf_res_print_generated(const char *verb, const res_args_t *a)
     if (a->labels) printf("%s_labels.tsv and %s_label_classes.tsv are generated.\n", verb, verb);
     if (a->markers) printf("%s_markers.tsv is generated.\n", verb);
     if (a->coexpression) printf("%s_coexpr.tsv is generated.\n", verb);
+    if (a->mapping) printf("%s_mapping.tsv is generated.\n", verb);
     if (a->n_seeds) printf("%s_reps.tsv is generated.\n", verb);
     printf("%s.tsv is generated.\n", verb);
 }

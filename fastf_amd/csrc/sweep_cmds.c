@@ -327,6 +327,18 @@ int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcod
     return fastf_res_check_markers("sweep", markers, labels_path) || fastf_res_grid_run(&sweep_verb, &job);
 }
 
+/* --mapping: the most general call — labels_path may be NULL and markers 0 */
+int fastf_sweep_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers, uint32_t mapping)
+{
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
+                            .labels_path = labels_path, .markers = markers, .mapping = mapping };
+    if (mapping > 1) return fastf_res_err("sweep: --mapping: %u, 0 or 1", mapping);
+    return (markers && fastf_res_check_markers("sweep", markers, labels_path)) || fastf_res_grid_run(&sweep_verb, &job);
+}
+
 static void usage_sweep(FILE *f)
 {
     fprintf(f,
@@ -366,6 +378,10 @@ static void usage_sweep(FILE *f)
             "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
             "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
             "                          sweep_markers.tsv and markers.tsv.gz per point; resident form only\n"
+            "        --mapping         every cell of a point looked up among ALL full-depth cells of the same sample (cosine of the RAW counts over\n"
+            "                          the 2000 most variable genes, decided in exact integers): sweep_mapping.tsv and mapping.tsv.gz per point, with\n"
+            "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
+            "                          full-depth neighbours and, with --labels, the label they vote for; resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -389,7 +405,8 @@ int cmd_sweep(int argc, const char **argv)
     }
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = fastf_res_args_flags(&A);
-    if (A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
+    if (A.mapping ? fastf_sweep_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
+        A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
         A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
                   : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {

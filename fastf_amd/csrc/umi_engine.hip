@@ -205,10 +205,10 @@ struct KernelTimer {           // optional per-kernel HIP-event timing (bench ro
 
 // Engine state of the grid verbs' analyses (analysis_entry.hpp).  attr[f]: the kernels of family f have their dynamic-LDS limit on
 // this engine's device (lds_attr_once).
-enum { AN_CAP_HITS, AN_GENE_SUMMARY, AN_GENE_MOMENTS, AN_NBR_GRAM, AN_LABEL_VOTES, AN_MARKER_AUC, AN_FAMILIES };
+enum { AN_CAP_HITS, AN_GENE_SUMMARY, AN_GENE_MOMENTS, AN_NBR_GRAM, AN_MAP_GRAM, AN_LABEL_VOTES, AN_MARKER_AUC, AN_FAMILIES };
 struct AnalysisState {
     bool attr[AN_FAMILIES] = {};
-    DevBuf d_nbr;                        // --neighbors: the two words of its max reductions
+    DevBuf d_nbr;                        // --neighbors: the two words of its max reductions; --mapping: two more behind them
     DevBuf d_coex;                       // --coexpression: the word of its max reduction (64 bytes), then V (u64 per gene of A)
 };
 

@@ -463,6 +463,16 @@ class Engine:
         """--neighbors: d_shared[i] (u32) = the cells in both neighbour sets of cell i; stream-ordered"""
         check(self._L.fastf_dev_neighbors_shared(self._h, d_idx_a or None, d_cnt_a or None, d_idx_b or None, d_cnt_b or None, n_cells, k, d_shared or None, stream))
 
+    def dev_mapping(self, d_planes_point, planes_point, d_planes_full, planes_full, n_cells, n_genes, k, d_norms_full, d_idx, d_cnt, d_self_dot, d_self_rank, stream=0) -> int:
+        """--mapping: the planes Engine.dev_neighbor_planes filled from the point's and from the full rows (planes_point <= planes_full) and
+        the norms Engine.dev_neighbors left for the full rows -> d_self_dot (u64[n_cells]), d_idx (u32[n_cells * k]) and d_cnt in the layout
+        of dev_neighbors, d_self_rank (u32[n_cells], 0xFFFFFFFF where self_dot is 0); returns the largest point norm.  Either largest norm
+        at 2^42 and beyond raises FastfError (FASTF_ERR_NEIGHBOR_NORM) before the kernels run.  FASTF_MAPPING_MFMA=0: plain integer form"""
+        m = C.c_uint64()
+        check(self._L.fastf_dev_mapping(self._h, d_planes_point or None, planes_point, d_planes_full or None, planes_full, n_cells, n_genes, k, d_norms_full or None,
+                                        d_idx or None, d_cnt or None, d_self_dot or None, d_self_rank or None, C.byref(m), stream))
+        return m.value
+
     def dev_coexpr_sums(self, d_feature, d_cell, d_count, d_nnz, d_slot_map, n_features, n_cells, n_genes, planes, d_work, work_bytes, d_D, d_S, stream=0):
         """--coexpression: the rows and the slot map as dev_neighbor_planes takes them, `planes` what it returned -> the gene-major planes in
         d_work (sweep.coexpression_work_bytes), d_D (u64[n_genes * n_genes], dense) and d_S (u64[n_genes]), both zeroed by the call;

@@ -39,6 +39,9 @@ LABELS_COLUMNS = _renamed(_cap.LABELS_COLUMNS)
 LABEL_CLASSES_COLUMNS = _renamed(_cap.LABEL_CLASSES_COLUMNS)
 MARKERS_COLUMNS = _renamed(_cap.MARKERS_COLUMNS)
 COEXPRESSION_COLUMNS = _renamed(_cap.COEXPRESSION_COLUMNS)
+MAPPING_COLUMNS = _renamed(_cap.MAPPING_COLUMNS)
+POINT_MAPPING_COLUMNS = _sweep.POINT_MAPPING_COLUMNS
+mapping_from_coo, mapping_row, read_point_mapping = _sweep.mapping_from_coo, _sweep.mapping_row, _sweep.read_point_mapping
 read_point_coexpression = _sweep.read_point_coexpression
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 THRESHOLDS_COLUMNS = ("barcode", "threshold", "umis_full", "umis")
@@ -51,7 +54,7 @@ def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neig
 
 
 def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
+          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
     """`fastF level -b bam -a barcodes -f features -o out -c rates_cell -m umi_caps -s seed [--summary-only] [--genes] [--cells]`; returns
     the rows of out/level.tsv as dicts of strings (read_table); genes / cells: the files cap.cap() leaves, under the names level_*; fidelity:
     out/level_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per point directory; gene_fidelity: out/level_gene_fidelity.tsv
@@ -61,6 +64,11 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._mapping_call(mapping, markers):
+        _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
+                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if markers is not None:
         _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
@@ -77,13 +85,19 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
 
 
 def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
+               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
     """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._mapping_call(mapping, markers):
+        _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
+                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
+                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if markers is not None:
         _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 m.ctypes.data, len(m), sd.ctypes.data, len(sd),
@@ -147,6 +161,20 @@ def gene_fidelity_summary_row(rate_cell, umi_cap, seed, n_cells, sum_x, sum_y, s
 
 def read_neighbors_table(path):
     return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def read_mapping_table(path):
+    """the rows of level_mapping.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, MAPPING_COLUMNS)
+
+
+def mapping_header(verb: str = "level") -> str:
+    return _sweep.mapping_header(verb)
+
+
+def mapping_summary_row(rate_cell, umi_cap, seed, hvg_k, self_dot, self_rank, k_full, hood, lab=None, same_map=None, labelled_map=None) -> str:
+    """one row of level_mapping.tsv (with its newline)"""
+    return _sweep.mapping_summary_row(rate_cell, 0.0, seed, hvg_k, self_dot, self_rank, k_full, hood, lab, same_map, labelled_map, list_value=int(umi_cap))
 
 
 def read_coexpression_table(path):

@@ -40,6 +40,12 @@ POINT_NEIGHBORS_COLUMNS = ("barcode", "k_full", "k_point", "shared", "overlap") 
 COEXPRESSION_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "genes_defined", "sum_k_full", "sum_k_point", "sum_shared", "mean_kept", "genes_half_kept")
 COEXPRESSION_COLUMNS = ("rate_cell", "rate_depth") + COEXPRESSION_TAIL_COLUMNS
 POINT_COEXPRESSION_COLUMNS = ("gene", "k_full", "k_point", "shared")     # the per-gene rows
+MAPPING_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "cells_defined", "self_top1", "self_topk", "median_self_rank", "p90_self_rank", "mean_hood",
+                        "cells_labelled", "accuracy_map")
+MAPPING_COLUMNS = ("rate_cell", "rate_depth") + MAPPING_TAIL_COLUMNS
+POINT_MAPPING_COLUMNS = ("barcode", "self_dot", "self_rank", "k_map", "k_full", "hood", "pred_map")     # <point dir>/mapping.tsv.gz
+MAPPING_K = 15
+MAPPING_NO_RANK = 0xFFFFFFFF
 LABELS_TAIL_COLUMNS = ("seed", "n_cells", "k", "n_labels", "cells_labelled", "agree_full", "agree_point", "accuracy_full", "accuracy_point", "kept",
                        "purity_full", "purity_point")
 LABELS_COLUMNS = ("rate_cell", "rate_depth") + LABELS_TAIL_COLUMNS
@@ -63,6 +69,11 @@ def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=
             | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0) | (COEXPRESSION if coexpression else 0))
 
 
+def _mapping_call(mapping, markers) -> bool:
+    """the _mapping entry point is taken: mapping=True, unless markers=N is given and no N the C call takes (the _markers call refuses it by name)"""
+    return bool(mapping) and (markers is None or _markers_n(markers) != 0)
+
+
 def _markers_n(markers) -> int:
     """N of markers=N as the u32 the C call takes: what is no integer or does not fit goes over as 0, which the call refuses by name"""
     try:
@@ -73,7 +84,7 @@ def _markers_n(markers) -> int:
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
@@ -86,10 +97,17 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     out/sweep_label_classes.tsv (read_label_classes_table) and labels.tsv.gz (read_point_labels), label_confusion.tsv.gz per point directory;
     markers=N (`--markers`, with labels) the N best marker genes per label by exact AUC: out/sweep_markers.tsv (read_markers_table) and a
     markers.tsv.gz per point directory (read_point_markers); coexpression=True (`--coexpression`) the comparison between the genes:
-    out/sweep_coexpr.tsv (read_coexpression_table) and a coexpr.tsv.gz per point directory (read_point_coexpression)"""
+    out/sweep_coexpr.tsv (read_coexpression_table) and a coexpr.tsv.gz per point directory (read_point_coexpression); mapping=True
+    (`--mapping`) every point cell looked up among the full-depth cells: out/sweep_mapping.tsv (read_mapping_table) and a mapping.tsv.gz
+    per point directory (read_point_mapping)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _mapping_call(mapping, markers):
+        _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
+                                                  None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), 1))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if markers is not None:
         _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
                                                   _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
@@ -110,7 +128,7 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -118,6 +136,11 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     rd, prd = _floats(rates_depth)
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _mapping_call(mapping, markers):
+        _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
+                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
+                                                  None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), 1))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if markers is not None:
         _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
                                                   _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
@@ -330,6 +353,69 @@ def neighbors_summary_row(rate_cell, rate_depth, seed, hvg_k, k_full, k_point, s
     buf = C.create_string_buffer(640)
     _lib.check(_lib.lib().fastf_neighbors_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(hvg_k), int(k),
                                                       a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def read_mapping_table(path, columns=MAPPING_COLUMNS):
+    """the rows of sweep_mapping.tsv as dicts of strings"""
+    return read_cells_table(path, columns)
+
+
+def read_point_mapping(path):
+    """the rows of a point's mapping.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_MAPPING_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_MAPPING_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def mapping_header(verb: str = "") -> str:
+    """the header of mapping.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_mapping.tsv"""
+    return getattr(_lib.lib(), "fastf_%smapping_header" % (verb + "_" if verb else ""))().decode()
+
+
+def mapping_from_coo(full, point, n_cells: int, slot_map, k: int = MAPPING_K):
+    """(idx u32[n_cells, k], cnt u32[n_cells], self_dot u64[n_cells], self_rank u32[n_cells]) of the point's (feature, cell, count) COO
+    looked up among the cells of the full one, both restricted to the features with a slot: the host form of Engine.dev_neighbor_planes
+    on both and Engine.dev_mapping together.  self_rank is MAPPING_NO_RANK where self_dot is 0"""
+    p32 = C.POINTER(C.c_uint32)
+    keep, coos = [], []
+    for coo in (full, point):
+        arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in coo]
+        assert len(arrs[0]) == len(arrs[1]) == len(arrs[2])
+        keep.append(arrs)
+        coos.append(Coo(arrs[0].ctypes.data_as(p32), arrs[1].ctypes.data_as(p32), arrs[2].ctypes.data_as(p32), len(arrs[0])))
+    sm = np.ascontiguousarray(slot_map, dtype=np.uint16)
+    idx = np.zeros((max(n_cells, 1), max(k, 1)), np.uint32)
+    cnt = np.zeros(max(n_cells, 1), np.uint32)
+    sd = np.zeros(max(n_cells, 1), np.uint64)
+    rank = np.zeros(max(n_cells, 1), np.uint32)
+    _lib.check(_lib.lib().fastf_mapping_from_coo(C.byref(coos[0]), C.byref(coos[1]), n_cells, sm.ctypes.data, len(sm) - 1, k, idx.ctypes.data, cnt.ctypes.data,
+                                                 sd.ctypes.data, rank.ctypes.data))
+    return idx[:n_cells], cnt[:n_cells], sd[:n_cells], rank[:n_cells]
+
+
+def mapping_row(barcode, self_dot, self_rank, k_map, k_full, hood, pred_map=None) -> str:
+    """one row of mapping.tsv.gz (with its newline); self_rank None or MAPPING_NO_RANK and pred_map None print NA"""
+    _b = lambda x: x.encode() if isinstance(x, str) else x  # noqa: E731
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.lib().fastf_mapping_row(_b(barcode), int(self_dot), MAPPING_NO_RANK if self_rank is None else int(self_rank), int(k_map), int(k_full), int(hood),
+                                            None if pred_map is None else _b(pred_map), buf, len(buf)))
+    return buf.value.decode()
+
+
+def mapping_summary_row(rate_cell, rate_depth, seed, hvg_k, self_dot, self_rank, k_full, hood, lab=None, same_map=None, labelled_map=None, list_value: int = 0,
+                        k: int = MAPPING_K) -> str:
+    """one row of <verb>_mapping.tsv (with its newline); lab None: a run without labels; list_value >= 1: that integer in the second column"""
+    sd = np.ascontiguousarray(self_dot, dtype=np.uint64)
+    a = [np.ascontiguousarray(x, dtype=np.uint32) for x in (self_rank, k_full, hood)]
+    n = len(sd)
+    assert all(len(x) == n for x in a)
+    b = [None, None, None] if lab is None else [np.ascontiguousarray(x, dtype=np.uint8) for x in (lab, same_map, labelled_map)]
+    assert lab is None or all(len(x) == n for x in b)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_mapping_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), n, int(hvg_k), int(k), sd.ctypes.data,
+                                                    a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, *[None if x is None else x.ctypes.data for x in b], buf, len(buf)))
     return buf.value.decode()
 
 

@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -598,6 +598,68 @@ int fastf_level_markers(const char *bam, const char *out_dir, const char *barcod
                         const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
                         uint32_t markers);
 
+/* --- --mapping on sweep, cap and level (fastf_sweep_mapping, fastf_cap_mapping, fastf_level_mapping; `mapping=True` in Python; the long
+ * option alone; no flag bit): the cells of a point looked up in the full-depth data — the comparison that CROSSES the two depths.  Is a
+ * point cell's own full-depth profile still its nearest full-depth cell; if not, how many got in front of it; does it land in the
+ * neighbourhood its full-depth self has; do the labels around it still give its own label.  Per (cell rate, seed) pair:
+ * X = the full-depth rows, Y = the point's rows, A and its slot map as --neighbors has them, n = the pair's cells; x_j, y_i the count
+ * vectors over A;  e_ij = <y_i, x_j>  and  m_j = <x_j, x_j> (the full norms), both u64.
+ * The query is y_i.  The candidates are ALL full-depth cells j with e_ij > 0.  Order: j precedes l iff e_ij^2 m_l > e_il^2 m_j, or these are
+ * equal and j < l (|y_i| cancels) — in 128-bit unsigned integers, the compare of --neighbors; no floating point takes part until a ratio
+ * is printed.
+ *   M(i)         = the first k candidates j != i in that order; k = FASTF_MAPPING_K = 15 in the verbs, the device call and the host twin
+ *                  take k from 1 to 64.  Written ascending by index, unused slots 0xFFFFFFFF, cnt[i] valid: the layout fastf_dev_neighbors
+ *                  writes, so fastf_dev_neighbors_shared and fastf_dev_label_votes take it unchanged.
+ *   self_dot(i)  = e_ii
+ *   self_rank(i) = the number of candidates j != i that precede i, when e_ii > 0; FASTF_MAPPING_NO_RANK (printed NA) otherwise.  Rank 0:
+ *                  the cell's own full-depth profile is its nearest.
+ *   hood(i)      = |M(i) and N_X(i)|, N_X the full-depth neighbour set of --neighbors at the same k.
+ *   with --labels: pred_map(i), same_map(i), labelled_map(i) are the vote of fastf_label_votes over M(i) with the pair's lab[], as that
+ *                  call defines them.  Self is never in M, so the vote does not leak.
+ * Range: the largest m_j AND the largest <y_i, y_i> are read back and a pair with either at 2^42 or beyond is refused
+ * (FASTF_ERR_NEIGHBOR_NORM, through fastf_neighbors_check_norm); below that e_ij < 2^42 and every product stays under 2^126.  Counts of
+ * 2^21 and beyond among A are refused as --neighbors refuses them.
+ *   <point dir>/mapping.tsv.gz (not with --summary-only): a header and one row per barcode in the order of barcodes.tsv.gz:
+ *     barcode self_dot self_rank k_map k_full hood pred_map      (k_map = |M(i)|, k_full = |N_X(i)|; pred_map the label string, NA without
+ *     --labels or without a labelled neighbour)
+ *   <out_dir>/<verb>_mapping.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), as
+ *     <verb>_neighbors.tsv — through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells hvg_k k cells_defined self_top1 self_topk median_self_rank p90_self_rank mean_hood cells_labelled accuracy_map
+ *     cells_defined = cells with self_dot > 0; self_top1, self_topk = the share of them with rank 0, rank < k (%.6f); median (%.6f, the mean
+ *     of the two middle values) and p90 (the value at floor(0.9 (cells_defined - 1)) of the ascending ranks: the quantile rule of
+ *     <verb>_fidelity.tsv) of the rank over them; mean_hood = the mean of hood / k_full over the cells with k_full > 0 (%.6f);
+ *     cells_labelled = the cells with lab[i] >= 1; accuracy_map = sum same_map / sum labelled_map over those cells (%.6f): the share of the
+ *     labelled full-depth cells a labelled cell maps among that carry its own label.  The last two are NA without --labels; NA wherever
+ *     a denominator is 0.
+ * The option switches on what --labels alone switches on — the full rows, the sums that rank A, both neighbour sets — and writes none of
+ * the files of --neighbors unless that option is given too; every other output is the bytes it is without it.  Jobs outside the resident
+ * form (several devices, the wide-UMI layout) are refused as --neighbors refuses them, naming --mapping.  No _reps aggregate. --- */
+#define FASTF_MAPPING_K 15u
+#define FASTF_MAPPING_NO_RANK 0xFFFFFFFFu
+const char *fastf_mapping_header(void);            /* the header of mapping.tsv.gz */
+const char *fastf_sweep_mapping_header(void);      /* the headers of <verb>_mapping.tsv */
+const char *fastf_cap_mapping_header(void);
+const char *fastf_level_mapping_header(void);
+/* one row of mapping.tsv.gz (with its newline); self_rank == FASTF_MAPPING_NO_RANK and pred_map == NULL print NA */
+int fastf_mapping_row(const char *barcode, uint64_t self_dot, uint32_t self_rank, uint32_t k_map, uint32_t k_full, uint32_t hood, const char *pred_map,
+                      char *buf, size_t cap);
+/* one row of <verb>_mapping.tsv (with its newline); the second column as fastf_genes_summary_row prints it (list_value == 0: rate_depth);
+ * lab == NULL: a run without --labels (same_map and labelled_map are not read) */
+int fastf_mapping_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t hvg_k, uint32_t k,
+                              const uint64_t *self_dot, const uint32_t *self_rank, const uint32_t *k_full, const uint32_t *hood, const uint8_t *lab,
+                              const uint8_t *same_map, const uint8_t *labelled_map, char *buf, size_t cap);
+/* sweep, cap and level with --mapping: the arguments of the verb's _markers call, then mapping (0 / 1).  labels_path may be NULL and
+ * markers 0 here (markers != 0 still needs labels_path); mapping == 0: what the _markers, _labels or _reps call of the same arguments does */
+int fastf_sweep_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers, uint32_t mapping);
+int fastf_cap_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                      const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                      uint32_t markers, uint32_t mapping);
+int fastf_level_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers, uint32_t mapping);
+
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
  *   point directories   <point name>_s<seed> (c0.500_r0.100_s927): the bytes `bam2db -s <seed>` (cap: `cap -s <seed>`) writes
@@ -799,6 +861,12 @@ int fastf_neighbors_from_coo(const fastf_coo_t *m, uint32_t n_cells, const uint1
                              uint32_t *idx, uint32_t *cnt, uint64_t *norms);
 /* the number of values in both of two ascending lists */
 uint32_t fastf_neighbors_shared(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb);
+/* --mapping (its section above): M(i), self_dot and self_rank of the point's rows against the full rows, both restricted to the features
+ * with a slot in slot_map — the host form of fastf_dev_neighbor_planes on both row sets and fastf_dev_mapping together, in plain C with
+ * 128-bit compares; rows in any order; idx (n_cells * k), cnt, self_dot, self_rank (n_cells) as the device call writes them.  Refused: k
+ * outside 1 .. 64, and a squared norm of 2^42 or more on either side (FASTF_ERR_NEIGHBOR_NORM) */
+int fastf_mapping_from_coo(const fastf_coo_t *full, const fastf_coo_t *point, uint32_t n_cells, const uint16_t *slot_map, uint32_t n_features, uint32_t k,
+                           uint32_t *idx, uint32_t *cnt, uint64_t *self_dot, uint32_t *self_rank);
 
 /* co-expression partners (section above) in plain C.  m: a COO matrix, rows in any order, restricted to the features with a slot below K in slot_map
  * (fastf_neighbors_slot_map); a row whose cell is outside 1 .. n_cells or whose feature is outside 1 .. n_features adds nothing.
@@ -1091,6 +1159,20 @@ int fastf_dev_neighbors(fastf_engine_t *e, const void *d_planes, uint32_t planes
                         uint32_t *d_cnt, uint64_t *d_norms, uint64_t *max_norm_out, void *stream);
 int fastf_dev_neighbors_shared(fastf_engine_t *e, const uint32_t *d_idx_a, const uint32_t *d_cnt_a, const uint32_t *d_idx_b, const uint32_t *d_cnt_b,
                                uint32_t n_cells, uint32_t k, uint32_t *d_shared, void *stream);
+
+/* --mapping (its section above), one call on device pointers (map_diag_kernel, map_gram_kernel; mapping_kernels.hpp).  d_planes_point
+ * (planes_point planes) and d_planes_full (planes_full planes; planes_point <= planes_full, what a subsample gives — another pair is
+ * refused) are what fastf_dev_neighbor_planes filled for (n_cells, K) from the point's and from the full rows; d_norms_full (u64[n_cells])
+ * is what fastf_dev_neighbors left for the full rows.  The largest point norm (*max_norm_point_out, may be NULL) and the largest full norm
+ * are reduced and read back first; either at 2^42 or beyond fails the call (FASTF_ERR_NEIGHBOR_NORM) before anything else is launched.
+ * Then d_self_dot (u64[n_cells]), d_idx (u32[n_cells * k]) and d_cnt (u32[n_cells]) in the layout of fastf_dev_neighbors, and d_self_rank
+ * (u32[n_cells], FASTF_MAPPING_NO_RANK where self_dot is 0); k from 1 to 64.  The dot products come from the i8 MFMA (32x32x32), under
+ * FASTF_MAPPING_MFMA=0 from ordinary integer instructions: the same numbers.  hood is fastf_dev_neighbors_shared on (d_idx, d_cnt) and the
+ * full sets, the vote fastf_dev_label_votes on (d_idx, d_cnt).  Synchronises the stream once.  Not re-entrant per engine: the two maxima
+ * share one engine buffer. */
+int fastf_dev_mapping(fastf_engine_t *e, const void *d_planes_point, uint32_t planes_point, const void *d_planes_full, uint32_t planes_full, uint32_t n_cells,
+                      uint32_t K, uint32_t k, const uint64_t *d_norms_full, uint32_t *d_idx, uint32_t *d_cnt, uint64_t *d_self_dot, uint32_t *d_self_rank,
+                      uint64_t *max_norm_point_out, void *stream);
 
 /* --coexpression (section above), on device pointers (coexpr_kernels.hpp).
  * fastf_coexpr_pad: the shape of the GENE-MAJOR byte planes of (n_cells, K): K_pad rows (K rounded up to 32) of n_pad bytes — n_cells rounded
