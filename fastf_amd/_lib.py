@@ -141,6 +141,10 @@ ABI_SYMBOLS = [
     "fastf_sweep_label_classes_header", "fastf_cap_label_classes_header", "fastf_level_label_classes_header", "fastf_labels_row",
     "fastf_label_confusion_header", "fastf_label_confusion_row", "fastf_labels_summary_row", "fastf_label_classes_row",
     "fastf_sweep_labels", "fastf_cap_labels", "fastf_level_labels", "fastf_dev_label_votes",
+    # --pseudotime of sweep, cap and level
+    "fastf_ptime_load", "fastf_ptime_free", "fastf_ptime_known", "fastf_ptime_unknown", "fastf_ptime_valued", "fastf_ptime_assign", "fastf_ptime_medians",
+    "fastf_ptime_census", "fastf_ptime_header", "fastf_sweep_pseudotime_header", "fastf_cap_pseudotime_header", "fastf_level_pseudotime_header", "fastf_ptime_row",
+    "fastf_ptime_summary_row", "fastf_sweep_pseudotime", "fastf_cap_pseudotime", "fastf_level_pseudotime", "fastf_dev_ptime_medians", "fastf_dev_ptime_census",
     # --mapping of sweep, cap and level
     "fastf_mapping_header", "fastf_sweep_mapping_header", "fastf_cap_mapping_header", "fastf_level_mapping_header", "fastf_mapping_row",
     "fastf_mapping_summary_row", "fastf_mapping_from_coo", "fastf_dev_mapping", "fastf_sweep_mapping", "fastf_cap_mapping", "fastf_level_mapping",
@@ -423,6 +427,25 @@ def lib():
     L.fastf_cap_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
     L.fastf_level_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
     L.fastf_dev_label_votes.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
+    for name in ("fastf_ptime_header", "fastf_sweep_pseudotime_header", "fastf_cap_pseudotime_header", "fastf_level_pseudotime_header"):
+        getattr(L, name).restype = C.c_char_p
+        getattr(L, name).argtypes = []
+    L.fastf_ptime_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
+    L.fastf_ptime_free.argtypes = [vp]
+    L.fastf_ptime_free.restype = None
+    for name in ("fastf_ptime_known", "fastf_ptime_unknown", "fastf_ptime_valued"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = u64
+    L.fastf_ptime_assign.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp, C.POINTER(u32)]
+    L.fastf_ptime_medians.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    L.fastf_ptime_census.argtypes = [vp, vp, u32, vp]
+    L.fastf_ptime_row.argtypes = [C.c_char_p, u32, u32, u32, u32, u32, u32, u32, C.c_int, C.c_char_p, sz]
+    L.fastf_ptime_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
+    L.fastf_sweep_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
+    L.fastf_cap_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
+    L.fastf_level_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
+    L.fastf_dev_ptime_medians.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp]
+    L.fastf_dev_ptime_census.argtypes = [vp, vp, vp, u32, vp, vp]
     for name in ("fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header", "fastf_level_markers_header"):
         getattr(L, name).restype = C.c_char_p
     L.fastf_marker_auc.argtypes = [vp, u32, u32, u32, vp, u32, vp, vp, vp, vp]

@@ -30,6 +30,8 @@ LABEL_CLASSES_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.LABEL_CLASSES_T
 MARKERS_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.MARKERS_TAIL_COLUMNS
 COEXPRESSION_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.COEXPRESSION_TAIL_COLUMNS
 MAPPING_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.MAPPING_TAIL_COLUMNS
+PSEUDOTIME_COLUMNS = ("rate_cell", "reads_per_cell") + _sweep.PSEUDOTIME_TAIL_COLUMNS
+read_point_pseudotime = _sweep.read_point_pseudotime
 POINT_MAPPING_COLUMNS = _sweep.POINT_MAPPING_COLUMNS
 mapping_from_coo, mapping_row, read_point_mapping = _sweep.mapping_from_coo, _sweep.mapping_row, _sweep.read_point_mapping
 read_point_coexpression = _sweep.read_point_coexpression
@@ -38,7 +40,8 @@ copies_from_umi_rows = _sweep.copies_from_umi_rows      # (the host twin is one 
 
 
 def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+        fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+        pseudotime=None):
     """`fastF cap -b bam -a barcodes -f features -o out -c rates_cell -n caps -s seed [--summary-only] [--genes] [--cells]`; returns the
     rows of out/cap.tsv as dicts of strings (read_table); genes=True also leaves out/cap_genes.tsv (read_genes_table),
     out/cap_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves out/cap_cells.tsv (read_cells_table) and
@@ -50,6 +53,12 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_cap_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
+                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
+                                                int(bool(mapping)), enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if _sweep._mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_cap_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
@@ -71,7 +80,8 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
 
 
 def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+             fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+        pseudotime=None):
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
@@ -79,6 +89,13 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     n = np.ascontiguousarray(caps, dtype=np.uint64)
     sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_cap_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
+                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
+                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
+                                                int(bool(mapping)), enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
     if _sweep._mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_cap_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 n.ctypes.data, len(n), sd.ctypes.data, len(sd),
@@ -138,6 +155,11 @@ def gene_fidelity_summary_row(rate_cell, reads_per_cell, seed, n_cells, sum_x, s
 def read_neighbors_table(path):
     """the rows of cap_neighbors.tsv as dicts of strings"""
     return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def read_pseudotime_table(path):
+    """the rows of cap_pseudotime.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, PSEUDOTIME_COLUMNS)
 
 
 def read_mapping_table(path):

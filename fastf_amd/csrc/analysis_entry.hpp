@@ -1,5 +1,5 @@
 // analysis_entry.hpp — the fastf_dev_* entry points of the grid verbs' analyses (--genes, --cells, --fidelity, --gene-fidelity,
-// --neighbors, --mapping, --labels, --markers, cap's hit counts and decision plane, level's search step): launch wrappers around the kernels
+// --neighbors, --mapping, --labels, --pseudotime, --markers, cap's hit counts and decision plane, level's search step): launch wrappers around the kernels
 // of the headers below.  Included by umi_engine.hip behind the engine core; what they keep on an engine is its AnalysisState.
 #pragma once
 #include "cap_kernels.hpp"
@@ -12,6 +12,7 @@
 #include "mapping_kernels.hpp"
 #include "coexpr_kernels.hpp"
 #include "labels_kernels.hpp"
+#include "ptime_kernels.hpp"
 #include "markers_kernels.hpp"
 
 // Per-cell summary of COO rows ascending by (cell, feature) (cell_summary_kernel): d_umis_per_cell[c - 1] = sum of the counts of
@@ -430,6 +431,42 @@ extern "C" int fastf_dev_label_votes(fastf_engine_t* e, const uint32_t* d_idx, c
                        lds_form ? (size_t)lab_conf_words(n_labels) * sizeof(u32) : 0, s, d_idx, d_cnt, d_lab, n_cells, k, n_labels, d_pred, d_same, d_labelled, d_conf);
     HIP_OK(hipGetLastError());
     dbg_sync(s, "label votes");
+    return 0;
+} FASTF_CATCH_INT
+
+// --pseudotime: per cell the lower median of the ranks its neighbours carry (pt_median_kernel).  d_idx, d_cnt: what fastf_dev_neighbors or
+// fastf_dev_mapping wrote for (n_cells, k); d_t: u32[n_cells], 0 without a value.  d_est, d_valued: u32[n_cells].  Stream-ordered.
+extern "C" int fastf_dev_ptime_medians(fastf_engine_t* e, const uint32_t* d_idx, const uint32_t* d_cnt, const uint32_t* d_t, uint32_t n_cells, uint32_t k,
+                                       uint32_t* d_est, uint32_t* d_valued, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (k < 1 || k > PT_MAX_K) return set_err("fastf_dev_ptime_medians: k = %u, from 1 to %u", k, PT_MAX_K);
+    if (!n_cells) return 0;
+    if (!d_idx || !d_cnt || !d_t || !d_est || !d_valued) return set_err("fastf_dev_ptime_medians: null argument");
+    static constexpr decltype(&pt_median_kernel<16>) medians[3] = {pt_median_kernel<16>, pt_median_kernel<32>, pt_median_kernel<64>};   // k <= 16, <= 32, beyond
+    const u32 g = k <= 16 ? 0 : k <= 32 ? 1 : 2;
+    const u32 per_pass = PT_THREADS / (16u << g), blocks_all = (n_cells + per_pass - 1) / per_pass;
+    hipLaunchKernelGGL(medians[g], dim3(std::min<u32>(blocks_all, 8u * (u32)e->grid_cus)), dim3(PT_THREADS), 0, s, d_idx, d_cnt, d_t, n_cells, k, d_est, d_valued);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "ptime medians");
+    return 0;
+} FASTF_CATCH_INT
+
+static_assert(PT_TILE == FASTF_PTIME_TILE && PT_OUT_WORDS == FASTF_PTIME_OUT_WORDS && PT_MAX_CELLS == FASTF_PTIME_MAX_CELLS, "the tile and the result block of pt_pairs_kernel and the ABI's");
+
+// --pseudotime: the order census of d_est against d_t over the cells that have both (pt_pairs_kernel): one workgroup per pair of tiles.
+// d_out: FASTF_PTIME_OUT_WORDS u64 (conc disc tie_e tie_t tie_both cells shift_sum), zeroed here.  Stream-ordered.
+extern "C" int fastf_dev_ptime_census(fastf_engine_t* e, const uint32_t* d_est, const uint32_t* d_t, uint32_t n_cells, uint64_t* d_out, void* stream) FASTF_TRY {
+    DEV_ENTRY(!e || !d_out, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_cells > PT_MAX_CELLS) return set_err("fastf_dev_ptime_census: %u cells, at most %u", n_cells, PT_MAX_CELLS);
+    HIP_OK(hipMemsetAsync(d_out, 0, PT_OUT_WORDS * sizeof(u64), s));
+    if (!n_cells) return 0;
+    if (!d_est || !d_t) return set_err("fastf_dev_ptime_census: null argument");
+    const u64 tiles = ((u64)n_cells + PT_TILE - 1) / PT_TILE;
+    hipLaunchKernelGGL(pt_pairs_kernel, dim3((u32)(tiles * (tiles + 1) / 2)), dim3(PT_THREADS), 0, s, d_est, d_t, n_cells, (u64*)d_out);
+    HIP_OK(hipGetLastError());
+    dbg_sync(s, "ptime census");
     return 0;
 } FASTF_CATCH_INT
 

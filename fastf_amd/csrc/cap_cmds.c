@@ -234,14 +234,22 @@ int fastf_cap_markers(const char *bam, const char *out_dir, const char *barcodes
     return fastf_res_check_markers("cap", markers, labels_path) || fastf_res_grid_run(&cap_verb, &job);
 }
 
-/* --mapping: the most general call — labels_path may be NULL and markers 0 */
+/* --mapping: labels_path may be NULL and markers 0 */
 int fastf_cap_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                        const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
                        uint32_t markers, uint32_t mapping)
 {
+    return fastf_cap_pseudotime(bam, out_dir, barcodes, features, rates_cell, n_c, caps, n_n, seeds, n_seeds, flags, seed, labels_path, markers, mapping, NULL);
+}
+
+/* --pseudotime FILE, the most general call: labels_path and pseudotime_path may be NULL, markers and mapping 0 */
+int fastf_cap_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers, uint32_t mapping, const char *pseudotime_path)
+{
     const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
                             .caps = caps, .n_list = n_n, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers, .mapping = mapping };
+                            .labels_path = labels_path, .markers = markers, .mapping = mapping, .ptime_path = pseudotime_path };
     if (mapping > 1) return fastf_res_err("cap: --mapping: %u, 0 or 1", mapping);
     return (markers && fastf_res_check_markers("cap", markers, labels_path)) || fastf_res_grid_run(&cap_verb, &job);
 }
@@ -287,6 +295,11 @@ static void usage_cap(FILE *f)
             "                          the 2000 most variable genes, decided in exact integers): cap_mapping.tsv and mapping.tsv.gz per point, with\n"
             "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
             "                          full-depth neighbours and, with --labels, the label they vote for\n"
+            "        --pseudotime=<file>\n"
+            "                          one `barcode<TAB>value` per line (a pseudotime or any per-cell score of the full-depth analysis): cap_pseudotime.tsv\n"
+            "                          and pseudotime.tsv.gz per point, with the value's rank estimated back per cell as the lower median over its 15\n"
+            "                          nearest neighbours, at full depth, at the point and, with --mapping, over the full-depth cells it maps among, and\n"
+            "                          Kendall's tau-b of the estimate against the value over all pairs of cells, counted exactly\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_n<N>_s<seed>/, one cap.tsv row each, and cap_reps.tsv with mean, sd, min and max\n"
             "                          of every metric per grid point (with --genes cap_genes_reps.tsv and cap_gene_reps.tsv.gz in\n"
@@ -311,7 +324,8 @@ int cmd_cap(int argc, const char **argv)
     }
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = fastf_res_args_flags(&A);
-    if (A.mapping ? fastf_cap_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
+    if (A.pseudotime ? fastf_cap_pseudotime(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, A.mapping, A.pseudotime) :
+        A.mapping ? fastf_cap_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
         A.markers ? fastf_cap_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
         A.labels ? fastf_cap_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_cap_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_n, A.seeds, A.n_seeds, flags)

@@ -40,6 +40,8 @@ int fastf_res_err(const char *fmt, ...)
     X(TB_MARKERS, markers, "seed\tlabel\tn_in\tn_out\ttop\tkept\tauc_full_mean\tauc_point_mean\n") \
     X(TB_COEXPR, coexpr, "seed\tn_cells\thvg_k\tk\tgenes_defined\tsum_k_full\tsum_k_point\tsum_shared\tmean_kept\tgenes_half_kept\n") \
     X(TB_MAPPING, mapping, "seed\tn_cells\thvg_k\tk\tcells_defined\tself_top1\tself_topk\tmedian_self_rank\tp90_self_rank\tmean_hood\tcells_labelled\taccuracy_map\n") \
+    X(TB_PTIME, pseudotime, "seed\tn_cells\tk\tcells_valued\tcells_full\tconc_full\tdisc_full\ttau_full\tshift_full\tcells_point\tconc_point\tdisc_point\ttau_point\tshift_point\t" \
+        "cells_map\tconc_map\tdisc_map\ttau_map\tshift_map\n") \
     X(TB_REPS, reps, "n_reps\tn_cells" REPS_STAT4("sampled_reads") REPS_STAT4("sampled_valid_reads") REPS_STAT4("nnz") REPS_STAT4("umis") \
         REPS_STAT4("saturation") REPS_STAT4("median_umis_per_cell") REPS_STAT4("median_genes_per_cell") "\n") \
     X(TB_GENES_REPS, genes_reps, "n_reps" REPS_STAT4("genes_detected") "\tgenes_in_all_reps\tgenes_in_any_rep\n")
@@ -830,6 +832,90 @@ int fastf_label_classes_row(float rate_cell, float rate_depth, uint64_t list_val
     const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%s\t%llu\t%u\t%u\t%llu\t%llu\n", (double)rate_cell, second, seed, label, (unsigned long long)cells,
                            conf_full[(size_t)(a - 1) * (n_labels + 1) + a], conf_point[(size_t)(a - 1) * (n_labels + 1) + a], (unsigned long long)pf, (unsigned long long)pp);
     return (n < 0 || (size_t)n >= cap) ? fastf_res_err("classes row too long") : 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* --pseudotime: the host twins, the rows                               */
+/* ------------------------------------------------------------------ */
+/* the lower median by insertion into a sorted run of at most k values */
+int fastf_ptime_medians(const uint32_t *idx, const uint32_t *cnt, const uint32_t *t, uint32_t n_cells, uint32_t k, uint32_t *est, uint32_t *valued)
+{
+    if (k < 1 || k > FASTF_NEIGHBORS_MAX_K) return fastf_res_err("ptime medians: k = %u, from 1 to %u", k, FASTF_NEIGHBORS_MAX_K);
+    if (n_cells && (!idx || !cnt || !t || !est || !valued)) return fastf_res_err("null argument");
+    for (uint32_t i = 0; i < n_cells; i++) {
+        uint32_t v[FASTF_NEIGHBORS_MAX_K], c = 0;
+        const uint32_t slots = cnt[i] < k ? cnt[i] : k;
+        for (uint32_t s = 0; s < slots; s++) {
+            const uint32_t j = idx[(size_t)i * k + s];
+            const uint32_t x = j < n_cells ? t[j] : 0;
+            if (!x) continue;
+            uint32_t at = c++;
+            while (at && v[at - 1] > x) { v[at] = v[at - 1]; at--; }
+            v[at] = x;
+        }
+        est[i] = c ? v[(c + 1) / 2 - 1] : 0; valued[i] = c;
+    }
+    return 0;
+}
+
+/* the definition, pair by pair */
+int fastf_ptime_census(const uint32_t *est, const uint32_t *t, uint32_t n_cells, uint64_t *out)
+{
+    if (!out || (n_cells && (!est || !t))) return fastf_res_err("null argument");
+    uint64_t conc = 0, disc = 0, tie_e = 0, tie_t = 0, tie_both = 0, cells = 0, shift = 0;
+    for (uint32_t i = 0; i < n_cells; i++) {
+        if (!t[i] || !est[i]) continue;
+        cells++; shift += est[i] > t[i] ? est[i] - t[i] : t[i] - est[i];
+        for (uint32_t j = i + 1; j < n_cells; j++) {
+            if (!t[j] || !est[j]) continue;
+            const int se = (est[i] > est[j]) - (est[i] < est[j]), st = (t[i] > t[j]) - (t[i] < t[j]);
+            if (se * st > 0) conc++; else if (se * st < 0) disc++; else if (!se && st) tie_e++; else if (se && !st) tie_t++; else tie_both++;
+        }
+    }
+    out[0] = conc; out[1] = disc; out[2] = tie_e; out[3] = tie_t; out[4] = tie_both; out[5] = cells; out[6] = shift;
+    return 0;
+}
+
+const char *fastf_ptime_header(void) { return "barcode\trank\test_full\tvalued_full\test_point\tvalued_point\test_map\tvalued_map\n"; }
+
+static void pt_rank(char *f, size_t cap, uint32_t v) { if (v) snprintf(f, cap, "%u", v); else snprintf(f, cap, "NA"); }
+
+int fastf_ptime_row(const char *barcode, uint32_t rank, uint32_t est_full, uint32_t valued_full, uint32_t est_point, uint32_t valued_point,
+                    uint32_t est_map, uint32_t valued_map, int mapping, char *buf, size_t cap)
+{
+    if (!barcode || !buf) return fastf_res_err("null argument");
+    char f[5][16];
+    pt_rank(f[0], sizeof f[0], rank); pt_rank(f[1], sizeof f[1], est_full); pt_rank(f[2], sizeof f[2], est_point);
+    pt_rank(f[3], sizeof f[3], mapping ? est_map : 0);
+    if (mapping) snprintf(f[4], sizeof f[4], "%u", valued_map); else snprintf(f[4], sizeof f[4], "NA");
+    const int n = snprintf(buf, cap, "%s\t%s\t%s\t%u\t%s\t%u\t%s\t%s\n", barcode, f[0], f[1], valued_full, f[2], valued_point, f[3], f[4]);
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("pseudotime row too long") : 0;
+}
+
+/* cells conc disc tau shift of one census (no leading tab); NULL: five NA */
+static int pt_census_text(char *f, size_t cap, const uint64_t *c, uint32_t cells_valued)
+{
+    if (!c) { const int n = snprintf(f, cap, "NA\tNA\tNA\tNA\tNA"); return n < 0 || (size_t)n >= cap; }
+    const uint64_t conc = c[0], disc = c[1], tie_e = c[2], tie_t = c[3], cells = c[5], shift = c[6];
+    char tau[40], sh[40];
+    if (conc + disc + tie_e == 0 || conc + disc + tie_t == 0) snprintf(tau, sizeof tau, "NA");
+    else snprintf(tau, sizeof tau, "%.6f", (double)(int64_t)(conc - disc) / sqrt((double)(conc + disc + tie_e) * (double)(conc + disc + tie_t)));
+    if (!cells_valued || !cells) snprintf(sh, sizeof sh, "NA");
+    else snprintf(sh, sizeof sh, "%.6f", (double)shift / ((double)(2 * (uint64_t)cells_valued) * (double)cells));
+    const int n = snprintf(f, cap, "%llu\t%llu\t%llu\t%s\t%s", (unsigned long long)cells, (unsigned long long)conc, (unsigned long long)disc, tau, sh);
+    return n < 0 || (size_t)n >= cap;
+}
+
+int fastf_ptime_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t k, uint32_t cells_valued,
+                            const uint64_t *census_full, const uint64_t *census_point, const uint64_t *census_map, char *buf, size_t cap)
+{
+    if (!buf || !census_full || !census_point) return fastf_res_err("null argument");
+    char f[3][160], second[32];
+    if (pt_census_text(f[0], sizeof f[0], census_full, cells_valued) || pt_census_text(f[1], sizeof f[1], census_point, cells_valued) ||
+        pt_census_text(f[2], sizeof f[2], census_map, cells_valued)) return fastf_res_err("summary row too long");
+    lab_second(second, sizeof second, rate_depth, list_value);
+    const int n = snprintf(buf, cap, "%.3f\t%s\t%u\t%u\t%u\t%u\t%s\t%s\t%s\n", (double)rate_cell, second, seed, n_cells, k, cells_valued, f[0], f[1], f[2]);
+    return (n < 0 || (size_t)n >= cap) ? fastf_res_err("summary row too long") : 0;
 }
 
 /* ------------------------------------------------------------------ */

@@ -38,6 +38,7 @@ static int grid_refuse(const res_verb_t *V, const res_job_t *job, int labels, in
     else if (labels) opt = "--labels";
     else if (f & FASTF_SWEEP_NEIGHBORS) opt = "--neighbors";
     else if (job->mapping) opt = "--mapping";
+    else if (job->ptime_path) opt = "--pseudotime";
     else if (f & FASTF_SWEEP_COEXPRESSION) opt = "--coexpression";
     else if (fallback && (f & FASTF_SWEEP_FIDELITY) && (f & FASTF_SWEEP_GENE_FIDELITY)) { opt = "--fidelity and --gene-fidelity"; needs = "need"; }
     else if (fallback && (f & FASTF_SWEEP_FIDELITY)) opt = "--fidelity";      /* (the full rows live on the device alone: bam2db() point by point has none) */
@@ -56,7 +57,7 @@ static void grid_close(res_tables_t *tb)
 }
 
 /* on failure the caller closes what was opened (grid_close) */
-static int grid_open(const res_verb_t *V, const res_job_t *job, const fastf_labels_t *labels, int device, res_tables_t *tb)
+static int grid_open(const res_verb_t *V, const res_job_t *job, const fastf_labels_t *labels, const fastf_ptime_t *ptime, int device, res_tables_t *tb)
 {
     const uint32_t f = job->flags;
     const int genes = (f & FASTF_SWEEP_GENES) != 0;
@@ -67,7 +68,7 @@ static int grid_open(const res_verb_t *V, const res_job_t *job, const fastf_labe
     return fastf_res_tsv_open(&tb->tsv, out, name, V->header()) ||
            fastf_res_genes_open(&tb->G, genes, V, out, job->n_c * job->n_list, job->reps) ||
            fastf_res_cells_open(&tb->C, (f & FASTF_SWEEP_CELLS) != 0, V, out) ||
-           fastf_res_cmp_open(&tb->Fd, V, out, f, labels, job->markers, job->mapping) ||
+           fastf_res_cmp_open(&tb->Fd, V, out, f, labels, job->markers, job->mapping, ptime) ||
            fastf_res_reps_open(&tb->P, job->reps, V, out, job->seeds, job->n_s, job->n_c, job->n_list, genes, device);
 }
 
@@ -200,6 +201,10 @@ static int grid_resident(const res_verb_t *V, const res_job_t *job, int device, 
         if (res_cmp_on(Fd, CMP_MAPPING)) fprintf(stderr, "[%s] --mapping: %sthe copy of the full planes, the mapping calls, the shared counts%s, their D2H, rows and files %.3f s\n", v,
                                                  nbr || res_cmp_on(Fd, CMP_LABELS) ? "" : "the neighbour sets of --neighbors and what they need, ", res_cmp_on(Fd, CMP_LABELS) ? " and votes" : "",
                                                  T.mapping + (nbr || res_cmp_on(Fd, CMP_LABELS) ? 0.0 : T.neighbors));
+        if (res_cmp_on(Fd, CMP_PTIME)) fprintf(stderr, "[%s] --pseudotime: %llu values, pseudotime_unknown %llu; %sthe ranks of every pair, the median and census calls, their D2H, rows and files %.3f s\n", v,
+                                               (unsigned long long)fastf_ptime_valued(Fd->ptime), (unsigned long long)fastf_ptime_unknown(Fd->ptime),
+                                               nbr || res_cmp_on(Fd, CMP_LABELS) || res_cmp_on(Fd, CMP_MAPPING) ? "" : "the neighbour sets of --neighbors and what they need, ",
+                                               T.ptime + (nbr || res_cmp_on(Fd, CMP_LABELS) || res_cmp_on(Fd, CMP_MAPPING) ? 0.0 : T.neighbors));
         if (res_cmp_on(Fd, CMP_COEXPR)) fprintf(stderr, "[%s] --coexpression: %sthe gene-major planes, the Gram sums and selections, the shared counts, their D2H, rows and files %.3f s\n", v,
                                                 fid || gene_fid || nbr || res_cmp_on(Fd, CMP_LABELS) ? "" : "the full-depth rows and per-gene sums of every pair, ", T.coexpr);
     }
@@ -215,7 +220,7 @@ done:
 /* the run of an entry point                                           */
 /* ------------------------------------------------------------------ */
 #define NOT_COVERED_WHY "keys wider than 64 bits or UMIs beyond what a 64-bit key holds"
-static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labels_t *labels)
+static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labels_t *labels, const fastf_ptime_t *ptime)
 {
     if (V->check_caps ? V->check_caps(job->rates_cell, job->n_c, job->caps, job->n_list) : fastf_sweep_check_grid(job->rates_cell, job->n_c, job->rates_depth, job->n_list)) return 1;
     if (job->flags & ~(uint32_t)GRID_FLAGS) return fastf_res_err("%s: unknown flags 0x%x", V->name, job->flags);
@@ -229,7 +234,7 @@ static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labe
     res_tables_t tb;
     char keep[512];
     int rc = RES_FAIL, ran = 0;                             /* ran: a failure of the run, not of an open — the replicate tables may have to go */
-    if (grid_open(V, job, labels, dev0, &tb)) goto fail;
+    if (grid_open(V, job, labels, ptime, dev0, &tb)) goto fail;
     ran = 1;
     rc = several ? RES_NOT_COVERED : grid_resident(V, job, dev0, &tb);
     if (rc == RES_NOT_COVERED && !grid_refuse(V, job, labels != NULL, 0, NOT_COVERED_WHY)) {
@@ -238,7 +243,7 @@ static int grid_run_(const res_verb_t *V, const res_job_t *job, const fastf_labe
         fprintf(stderr, "%s: this job is outside the resident form (%s): running bam2db point by point\n", V->name, several ? "several devices" : NOT_COVERED_WHY);
         grid_close(&tb);
         ran = 0;
-        if (grid_open(V, job, labels, dev0, &tb)) goto fail;
+        if (grid_open(V, job, labels, ptime, dev0, &tb)) goto fail;
         ran = 1;
         rc = V->point_by_point(job, (job->flags & FASTF_SWEEP_SUMMARY_ONLY) != 0, &tb);
     }
@@ -264,7 +269,12 @@ int fastf_res_grid_run(const res_verb_t *V, const res_job_t *asked)
         if (access(job.bam, R_OK) == -1) return fastf_res_err("bam file: %s does not exist.", job.bam);
         if (fastf_labels_load(job.labels_path, job.barcodes, &labels)) return 1;
     }
-    const int rc = grid_run_(V, &job, labels);
-    fastf_labels_free(labels);
+    fastf_ptime_t *ptime = NULL;                            /* the pseudotime file likewise */
+    if (job.ptime_path) {
+        if (access(job.bam, R_OK) == -1) { fastf_labels_free(labels); return fastf_res_err("bam file: %s does not exist.", job.bam); }
+        if (fastf_ptime_load(job.ptime_path, job.barcodes, &ptime)) { fastf_labels_free(labels); return 1; }
+    }
+    const int rc = grid_run_(V, &job, labels, ptime);
+    fastf_labels_free(labels); fastf_ptime_free(ptime);
     return rc;
 }

@@ -11,6 +11,8 @@
 #include "host_io.h"
 
 #include <errno.h>
+#include <locale.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -194,61 +196,50 @@ void fastf_lists_free(fastf_lists_t *l)
 }
 
 /* ------------------------------------------------------------------ */
-/* --labels: the labels file (include/fastf_amd.h)                     */
+/* --labels, --pseudotime: the per-barcode files (include/fastf_amd.h)  */
 /* ------------------------------------------------------------------ */
-typedef struct { const char *barcode; size_t line; uint32_t label; } lab_entry;   /* label: index into the labels as first seen, then the id; UINT32_MAX: NA */
-struct fastf_labels {
-    char *text;                          /* the file, fields cut in place */
-    lab_entry *e; size_t n;              /* ascending by barcode */
-    char (*name)[FASTF_LABEL_BYTES]; uint32_t n_labels;     /* name[0] = "NA", name[1 .. L] ascending */
-    uint64_t known, unknown;
-};
+/* What the two files share — `barcode<TAB>field`, one line a barcode — is read ONCE here: the file into memory, the gzip magic, the
+ * lines and their two fields cut in place, the header line, the length of the field, the barcode named twice, the barcode list.  What
+ * the field means is the caller's (bc_field_fn: the entry's label or value from the field's text; 1 — refused, the message set).
+ * what: the word the messages start with ("labels", "pseudotime"); field: what they call the second field ("label", "value") */
+typedef struct { const char *barcode; size_t line; uint32_t label; double value; uint8_t has, known; } bc_entry;   /* label: --labels (index into the labels as first seen, then the id; UINT32_MAX: NA); value, has: --pseudotime; known: the barcode is in the barcode list */
+typedef struct { char *text; bc_entry *e; size_t n; uint64_t known, unknown; } bc_file;      /* text: the file, fields cut in place; e: ascending by barcode */
+typedef int (*bc_field_fn)(void *ctx, bc_entry *e, const char *field, size_t len, const char *file, size_t line_no);
 
-static int cmp_lab_entry(const void *a, const void *b)
+static int cmp_bc_entry(const void *a, const void *b)
 {
-    const lab_entry *x = (const lab_entry *)a, *y = (const lab_entry *)b;
+    const bc_entry *x = (const bc_entry *)a, *y = (const bc_entry *)b;
     const int c = strcmp(x->barcode, y->barcode);
     return c ? c : (x->line < y->line ? -1 : x->line > y->line);
 }
 static int cmp_str_ptr(const void *a, const void *b) { return strcmp(*(const char *const *)a, *(const char *const *)b); }
-typedef struct { char name[FASTF_LABEL_BYTES]; uint32_t seen; } lab_name;
-/* (bytewise order: strcmp compares as unsigned char, and the shorter of two strings with a common prefix comes first) */
-static int cmp_lab_name(const void *a, const void *b) { return strcmp(((const lab_name *)a)->name, ((const lab_name *)b)->name); }
 
-void fastf_labels_free(fastf_labels_t *t)
-{
-    if (!t) return;
-    free(t->text); free(t->e); free(t->name); free(t);
-}
+static void bc_file_free(bc_file *t) { free(t->text); free(t->e); memset(t, 0, sizeof *t); }
 
-int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_labels_t **out)
+/* on failure nothing of *t is left */
+static int bc_file_load(const char *what, const char *field, const char *file, const char *barcodes_file, bc_field_fn fn, void *ctx, bc_file *t)
 {
-    if (out) *out = NULL;
-    if (!labels_file || !barcodes_file || !out) return io_err("labels: null argument");
-    FILE *f = fopen(labels_file, "rb");
-    if (!f) return io_err("labels file: %s does not exist.", labels_file);
-    fastf_labels_t *t = (fastf_labels_t *)calloc(1, sizeof *t);
-    lab_name *names = (lab_name *)calloc(FASTF_LABELS_MAX + 1, sizeof *names);
+    memset(t, 0, sizeof *t);
+    FILE *f = fopen(file, "rb");
+    if (!f) return io_err("%s file: %s does not exist.", what, file);
     char *btext = NULL, *barena = NULL; const char **blist = NULL;
-    uint32_t *id_of = NULL;
     size_t len = 0, cap = 1 << 16, blen = 0;
     int rc = 1;
-    if (!t || !names || !(t->text = (char *)malloc(cap + 1))) { io_err("labels: out of memory"); goto done; }
+    if (!(t->text = (char *)malloc(cap + 1))) { io_err("%s: out of memory", what); goto done; }
     for (;;) {
-        if (len == cap) { cap *= 2; char *nt = (char *)realloc(t->text, cap + 1); if (!nt) { io_err("labels: out of memory"); goto done; } t->text = nt; }
+        if (len == cap) { cap *= 2; char *nt = (char *)realloc(t->text, cap + 1); if (!nt) { io_err("%s: out of memory", what); goto done; } t->text = nt; }
         const size_t r = fread(t->text + len, 1, cap - len, f);
         if (!r) break;
         len += r;
     }
-    if (ferror(f)) { io_err("labels: read error on %s", labels_file); goto done; }
+    if (ferror(f)) { io_err("%s: read error on %s", what, file); goto done; }
     t->text[len] = '\0';
     if (len >= 2 && (unsigned char)t->text[0] == 0x1f && (unsigned char)t->text[1] == 0x8b) {
-        io_err("labels: %s starts with the gzip magic: a labels file is plain text", labels_file); goto done;
+        io_err("%s: %s starts with the gzip magic: a %s file is plain text", what, file, what); goto done;
     }
     {   size_t n_lines = 1;
         for (size_t i = 0; i < len; i++) n_lines += t->text[i] == '\n';
-        if (!(t->e = (lab_entry *)malloc(n_lines * sizeof *t->e))) { io_err("labels: out of memory"); goto done; } }
-    uint32_t n_names = 0;
+        if (!(t->e = (bc_entry *)calloc(n_lines, sizeof *t->e))) { io_err("%s: out of memory", what); goto done; } }
     size_t line_no = 0;
     for (size_t pos = 0; pos < len;) {
         char *ln = t->text + pos;
@@ -259,47 +250,33 @@ int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_
         if (ll && ln[ll - 1] == '\r') ll--;
         ln[ll] = '\0';
         if (!ll) continue;
-        if (memchr(ln, '\0', ll)) { io_err("labels: %s: line %zu holds a NUL byte", labels_file, line_no); goto done; }
+        if (memchr(ln, '\0', ll)) { io_err("%s: %s: line %zu holds a NUL byte", what, file, line_no); goto done; }
         size_t fields = 1;
         for (size_t i = 0; i < ll; i++) fields += ln[i] == '\t';
-        if (fields != 2) { io_err("labels: %s: line %zu has %zu fields, not barcode<TAB>label", labels_file, line_no, fields); goto done; }
+        if (fields != 2) { io_err("%s: %s: line %zu has %zu fields, not barcode<TAB>%s", what, file, line_no, fields, field); goto done; }
         char *tab = (char *)memchr(ln, '\t', ll);
         *tab = '\0';
-        const char *label = tab + 1;
-        const size_t lab_len = ll - (size_t)(label - ln);
+        const char *second = tab + 1;
+        const size_t second_len = ll - (size_t)(second - ln);
         if (line_no == 1 && strcmp(ln, "barcode") == 0) continue;
-        if (!lab_len) { io_err("labels: %s: line %zu: the label is empty", labels_file, line_no); goto done; }
-        if (lab_len >= FASTF_LABEL_BYTES) { io_err("labels: %s: line %zu: the label has %zu bytes, at most %u", labels_file, line_no, lab_len, FASTF_LABEL_BYTES - 1); goto done; }
-        uint32_t li = UINT32_MAX;
-        if (strcmp(label, "NA") != 0) {
-            for (li = 0; li < n_names && strcmp(names[li].name, label) != 0; li++) ;
-            if (li == n_names) {
-                if (n_names == FASTF_LABELS_MAX) {
-                    io_err("labels: %s: line %zu brings distinct label %u, at most %u (FASTF_LABELS_MAX)", labels_file, line_no, FASTF_LABELS_MAX + 1, FASTF_LABELS_MAX); goto done;
-                }
-                memcpy(names[n_names].name, label, lab_len + 1); names[n_names].seen = n_names; n_names++;
-            }
-        }
-        t->e[t->n].barcode = ln; t->e[t->n].line = line_no; t->e[t->n].label = li; t->n++;
+        if (!second_len) { io_err("%s: %s: line %zu: the %s is empty", what, file, line_no, field); goto done; }
+        if (second_len >= FASTF_LABEL_BYTES) { io_err("%s: %s: line %zu: the %s has %zu bytes, at most %u", what, file, line_no, field, second_len, FASTF_LABEL_BYTES - 1); goto done; }
+        bc_entry *const e = &t->e[t->n];
+        e->barcode = ln; e->line = line_no;
+        if (fn(ctx, e, second, second_len, file, line_no)) goto done;
+        t->n++;
     }
-    qsort(t->e, t->n, sizeof *t->e, cmp_lab_entry);
+    qsort(t->e, t->n, sizeof *t->e, cmp_bc_entry);
     {   size_t dup_line = 0, first_line = 0; const char *dup = NULL;
         for (size_t i = 1; i < t->n; i++)
             if (strcmp(t->e[i].barcode, t->e[i - 1].barcode) == 0 && (!dup_line || t->e[i].line < dup_line)) { dup_line = t->e[i].line; first_line = t->e[i - 1].line; dup = t->e[i].barcode; }
-        if (dup_line) { io_err("labels: %s: line %zu names barcode %s again (first on line %zu)", labels_file, dup_line, dup, first_line); goto done; } }
-    /* ids in bytewise order of the strings */
-    qsort(names, n_names, sizeof *names, cmp_lab_name);
-    if (!(id_of = (uint32_t *)malloc((n_names + 1) * sizeof *id_of)) || !(t->name = (char (*)[FASTF_LABEL_BYTES])calloc(n_names + 1, FASTF_LABEL_BYTES))) { io_err("labels: out of memory"); goto done; }
-    strcpy(t->name[0], "NA");
-    for (uint32_t k = 0; k < n_names; k++) { id_of[names[k].seen] = k + 1; memcpy(t->name[k + 1], names[k].name, FASTF_LABEL_BYTES); }
-    for (size_t i = 0; i < t->n; i++) t->e[i].label = t->e[i].label == UINT32_MAX ? 0 : id_of[t->e[i].label];
-    t->n_labels = n_names;
+        if (dup_line) { io_err("%s: %s: line %zu names barcode %s again (first on line %zu)", what, file, dup_line, dup, first_line); goto done; } }
     /* the barcode list, every line cut as fastf_lists_load_mem cuts it */
     if (slurp_gz(barcodes_file, &btext, &blen)) goto done;
     {   size_t pos = 0, n_b = 0, at = 0; char line[1024];
         while (next_line(btext, blen, &pos, line)) n_b++;
         barena = (char *)malloc(blen + n_b + 1); blist = (const char **)malloc((n_b + 1) * sizeof *blist);
-        if (!barena || !blist) { io_err("labels: out of memory"); goto done; }
+        if (!barena || !blist) { io_err("%s: out of memory", what); goto done; }
         pos = 0; n_b = 0;
         while (next_line(btext, blen, &pos, line)) {
             line[strcspn(line, "\n\r\t")] = '\0';
@@ -309,39 +286,174 @@ int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_
         qsort(blist, n_b, sizeof *blist, cmp_str_ptr);
         for (size_t i = 0; i < t->n; i++) {
             const char *key = t->e[i].barcode;
-            if (bsearch(&key, blist, n_b, sizeof *blist, cmp_str_ptr)) t->known++; else t->unknown++;
+            t->e[i].known = bsearch(&key, blist, n_b, sizeof *blist, cmp_str_ptr) != NULL;
+            if (t->e[i].known) t->known++; else t->unknown++;
         } }
-    if (!t->known) { io_err("labels: %s: no line names a barcode of %s", labels_file, barcodes_file); goto done; }
+    if (!t->known) { io_err("%s: %s: no line names a barcode of %s", what, file, barcodes_file); goto done; }
     rc = 0;
 done:
     fclose(f);
-    free(names); free(btext); free(barena); free(blist); free(id_of);
+    free(btext); free(barena); free(blist);
+    if (rc) bc_file_free(t);
+    return rc;
+}
+
+static const bc_entry *bc_file_find(const bc_file *t, const char *barcode)
+{
+    size_t lo = 0, hi = t->n;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        const int c = strcmp(t->e[mid].barcode, barcode);
+        if (!c) return &t->e[mid];
+        if (c < 0) lo = mid + 1; else hi = mid;
+    }
+    return NULL;
+}
+
+/* --labels */
+struct fastf_labels {
+    bc_file f;
+    char (*name)[FASTF_LABEL_BYTES]; uint32_t n_labels;     /* name[0] = "NA", name[1 .. L] ascending */
+};
+typedef struct { char name[FASTF_LABEL_BYTES]; uint32_t seen; } lab_name;
+typedef struct { lab_name *names; uint32_t n_names; } lab_names;
+/* (bytewise order: strcmp compares as unsigned char, and the shorter of two strings with a common prefix comes first) */
+static int cmp_lab_name(const void *a, const void *b) { return strcmp(((const lab_name *)a)->name, ((const lab_name *)b)->name); }
+
+static int lab_field(void *ctx, bc_entry *e, const char *label, size_t lab_len, const char *file, size_t line_no)
+{
+    lab_names *const N = (lab_names *)ctx;
+    uint32_t li = UINT32_MAX;
+    if (strcmp(label, "NA") != 0) {
+        for (li = 0; li < N->n_names && strcmp(N->names[li].name, label) != 0; li++) ;
+        if (li == N->n_names) {
+            if (N->n_names == FASTF_LABELS_MAX)
+                return io_err("labels: %s: line %zu brings distinct label %u, at most %u (FASTF_LABELS_MAX)", file, line_no, FASTF_LABELS_MAX + 1, FASTF_LABELS_MAX);
+            memcpy(N->names[N->n_names].name, label, lab_len + 1); N->names[N->n_names].seen = N->n_names; N->n_names++;
+        }
+    }
+    e->label = li;
+    return 0;
+}
+
+void fastf_labels_free(fastf_labels_t *t)
+{
+    if (!t) return;
+    bc_file_free(&t->f); free(t->name); free(t);
+}
+
+int fastf_labels_load(const char *labels_file, const char *barcodes_file, fastf_labels_t **out)
+{
+    if (out) *out = NULL;
+    if (!labels_file || !barcodes_file || !out) return io_err("labels: null argument");
+    fastf_labels_t *t = (fastf_labels_t *)calloc(1, sizeof *t);
+    lab_names N = { (lab_name *)calloc(FASTF_LABELS_MAX + 1, sizeof(lab_name)), 0 };
+    uint32_t *id_of = NULL;
+    int rc = 1;
+    if (!t || !N.names) { io_err("labels: out of memory"); goto done; }
+    if (bc_file_load("labels", "label", labels_file, barcodes_file, lab_field, &N, &t->f)) goto done;
+    /* ids in bytewise order of the strings */
+    qsort(N.names, N.n_names, sizeof *N.names, cmp_lab_name);
+    if (!(id_of = (uint32_t *)malloc((N.n_names + 1) * sizeof *id_of)) || !(t->name = (char (*)[FASTF_LABEL_BYTES])calloc(N.n_names + 1, FASTF_LABEL_BYTES))) { io_err("labels: out of memory"); goto done; }
+    strcpy(t->name[0], "NA");
+    for (uint32_t k = 0; k < N.n_names; k++) { id_of[N.names[k].seen] = k + 1; memcpy(t->name[k + 1], N.names[k].name, FASTF_LABEL_BYTES); }
+    for (size_t i = 0; i < t->f.n; i++) t->f.e[i].label = t->f.e[i].label == UINT32_MAX ? 0 : id_of[t->f.e[i].label];
+    t->n_labels = N.n_names;
+    rc = 0;
+done:
+    free(N.names); free(id_of);
     if (rc) fastf_labels_free(t); else *out = t;
     return rc;
 }
 
 uint32_t fastf_labels_count(const fastf_labels_t *t) { return t ? t->n_labels : 0; }
 const char *fastf_labels_name(const fastf_labels_t *t, uint32_t id) { return t && id <= t->n_labels ? t->name[id] : NULL; }
-uint64_t fastf_labels_unknown(const fastf_labels_t *t) { return t ? t->unknown : 0; }
-uint64_t fastf_labels_known(const fastf_labels_t *t) { return t ? t->known : 0; }
+uint64_t fastf_labels_unknown(const fastf_labels_t *t) { return t ? t->f.unknown : 0; }
+uint64_t fastf_labels_known(const fastf_labels_t *t) { return t ? t->f.known : 0; }
 
 uint32_t fastf_labels_id(const fastf_labels_t *t, const char *barcode)
 {
     if (!t || !barcode) return 0;
-    size_t lo = 0, hi = t->n;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo) / 2;
-        const int c = strcmp(t->e[mid].barcode, barcode);
-        if (!c) return t->e[mid].label;
-        if (c < 0) lo = mid + 1; else hi = mid;
-    }
-    return 0;
+    const bc_entry *e = bc_file_find(&t->f, barcode);
+    return e ? e->label : 0;
 }
 
 int fastf_labels_assign(const fastf_labels_t *t, char *const *barcodes, uint32_t n, uint8_t *lab)
 {
     if (!t || (n && (!barcodes || !lab))) return io_err("labels: null argument");
     for (uint32_t i = 0; i < n; i++) lab[i] = (uint8_t)fastf_labels_id(t, barcodes[i]);
+    return 0;
+}
+
+/* --pseudotime */
+struct fastf_ptime { bc_file f; uint64_t valued; };
+
+/* NA, or what strtod consumes whole in the C locale (whatever locale the process has set) and is finite */
+static int pt_field(void *ctx, bc_entry *e, const char *value, size_t len, const char *file, size_t line_no)
+{
+    const locale_t c_locale = *(const locale_t *)ctx;
+    if (strcmp(value, "NA") == 0) { e->has = 0; return 0; }
+    char *end = NULL;
+    const double v = strtod_l(value, &end, c_locale);
+    if (end != value + len) return io_err("pseudotime: %s: line %zu: the value `%s` is not a number", file, line_no, value);
+    if (!isfinite(v)) return io_err("pseudotime: %s: line %zu: the value `%s` is not finite", file, line_no, value);
+    e->value = v; e->has = 1;
+    return 0;
+}
+
+void fastf_ptime_free(fastf_ptime_t *t)
+{
+    if (!t) return;
+    bc_file_free(&t->f); free(t);
+}
+
+int fastf_ptime_load(const char *ptime_file, const char *barcodes_file, fastf_ptime_t **out)
+{
+    if (out) *out = NULL;
+    if (!ptime_file || !barcodes_file || !out) return io_err("pseudotime: null argument");
+    fastf_ptime_t *t = (fastf_ptime_t *)calloc(1, sizeof *t);
+    locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    int rc = 1;
+    if (!t || c_locale == (locale_t)0) { io_err("pseudotime: out of memory"); goto done; }
+    if (bc_file_load("pseudotime", "value", ptime_file, barcodes_file, pt_field, &c_locale, &t->f)) goto done;
+    for (size_t i = 0; i < t->f.n; i++) t->valued += t->f.e[i].known && t->f.e[i].has;
+    rc = 0;
+done:
+    if (c_locale != (locale_t)0) freelocale(c_locale);
+    if (rc) fastf_ptime_free(t); else *out = t;
+    return rc;
+}
+
+uint64_t fastf_ptime_known(const fastf_ptime_t *t) { return t ? t->f.known : 0; }
+uint64_t fastf_ptime_unknown(const fastf_ptime_t *t) { return t ? t->f.unknown : 0; }
+uint64_t fastf_ptime_valued(const fastf_ptime_t *t) { return t ? t->valued : 0; }
+
+static int cmp_double(const void *a, const void *b) { const double x = *(const double *)a, y = *(const double *)b; return x < y ? -1 : x > y; }
+
+/* the doubled midranks: the m values sorted once, then per cell the values below it and the values equal to it by two binary searches */
+int fastf_ptime_assign(const fastf_ptime_t *t, char *const *barcodes, uint32_t n, uint32_t *rank, uint32_t *m_out)
+{
+    if (!t || (n && (!barcodes || !rank))) return io_err("pseudotime: null argument");
+    double *const own = (double *)malloc(((size_t)n + 1) * sizeof *own), *const sorted = (double *)malloc(((size_t)n + 1) * sizeof *sorted);
+    if (!own || !sorted) { free(own); free(sorted); return io_err("pseudotime: out of memory"); }
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const bc_entry *e = barcodes[i] ? bc_file_find(&t->f, barcodes[i]) : NULL;
+        rank[i] = e && e->has;
+        if (rank[i]) { own[i] = e->value; sorted[m++] = e->value; }
+    }
+    qsort(sorted, m, sizeof *sorted, cmp_double);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!rank[i]) continue;
+        uint32_t lo = 0, hi = m, below, upto;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (sorted[mid] < own[i]) lo = mid + 1; else hi = mid; }
+        below = lo; hi = m;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (sorted[mid] <= own[i]) lo = mid + 1; else hi = mid; }
+        upto = lo;
+        rank[i] = 2 * below + (upto - below) + 1;
+    }
+    free(own); free(sorted);
+    if (m_out) *m_out = m;
     return 0;
 }
 

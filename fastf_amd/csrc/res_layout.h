@@ -128,6 +128,20 @@ static inline res_lab_v res_lab_layout(void *base, size_t lab_cells, size_t n_la
     v.half_bytes = (c.off - lab_cells) / 2; v.bytes = c.off; return v;
 }
 
+/* --pseudotime: t of the pair's cells, then one half for the full rows [0], one for the point [1] and one for the mapping list [2] — the
+ * census (8 u64: FASTF_PTIME_OUT_WORDS used), est and valued (u32 per cell); a half starts at its census and leaves in one copy of
+ * half_bytes.  pt_cells: res_pt_cells(cells), an even number, which keeps every census aligned.  The device block and its pinned copy alike */
+#define RES_PT_CENSUS_WORDS 8u
+static inline size_t res_pt_cells(size_t cells) { return (cells + 1) & ~(size_t)1; }
+typedef struct { uint32_t *t; struct { uint64_t *census; uint32_t *est, *valued; } half[3]; size_t half_bytes, bytes; } res_pt_v;
+static inline res_pt_v res_pt_layout(void *base, size_t pt_cells)
+{
+    res_carve_t c = { (char *)base, 0 }; res_pt_v v;
+    RES_CARVE(c, v.t, pt_cells);
+    for (int h = 0; h < 3; h++) { RES_CARVE(c, v.half[h].census, RES_PT_CENSUS_WORDS); RES_CARVE(c, v.half[h].est, pt_cells); RES_CARVE(c, v.half[h].valued, pt_cells); }
+    v.half_bytes = (c.off - pt_cells * sizeof *v.t) / 3; v.bytes = c.off; return v;
+}
+
 /* --markers: the four tables of ONE row set — s2u, sum (u64), det (u32), n_labels x K each, then n_per_label (u32, an even number of
  * entries) — which leave the device in one copy of .bytes.  The pinned block holds two sets, res_mk_set_bytes apart */
 typedef struct { uint64_t *s2u, *sum; uint32_t *det, *npl; size_t bytes; } res_mk_v;

@@ -391,11 +391,32 @@ static int map_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float r
     return 0;
 }
 
+/* --pseudotime: one row per barcode; the map columns from the third half with --mapping (C->on says so) */
+typedef struct { const res_rate_t *S; int mapping; } pt_lines_t;
+static int pt_line(gtext *t, const void *ctx, uint32_t c)
+{
+    const pt_lines_t *x = (const pt_lines_t *)ctx;
+    const res_rate_t *S = x->S;
+    char line[512];
+    return fastf_ptime_row(S->L->barcode[c], S->h_pt.t[c], S->h_pt.half[0].est[c], S->h_pt.half[0].valued[c], S->h_pt.half[1].est[c], S->h_pt.half[1].valued[c],
+                           x->mapping ? S->h_pt.half[2].est[c] : 0, x->mapping ? S->h_pt.half[2].valued[c] : 0, x->mapping, line, sizeof line) || fastf_gt_str(t, line);
+}
+static int pt_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value)
+{
+    const pt_lines_t lines = { S, res_cmp_on(C, CMP_MAPPING) };
+    char row[640];
+    if (fastf_ptime_summary_row(S->rate_cell, rate_depth, list_value, S->seed, S->n_cells, FASTF_NEIGHBORS_K, S->pt_m, S->h_pt.half[0].census, S->h_pt.half[1].census,
+                                lines.mapping ? S->h_pt.half[2].census : NULL, row, sizeof row)) return 1;
+    if (dir && flat_file(dir, "pseudotime.tsv.gz", fastf_ptime_header(), S->n_cells, pt_line, &lines)) return 1;
+    fputs(row, cmp_tsv(C, TB_PTIME));
+    return 0;
+}
+
 /* ------------------------------------------------------------------ */
 /* the comparisons against full depth: the descriptors, open, point, close */
 /* ------------------------------------------------------------------ */
 /* ONE descriptor per comparison, in the order a point writes them: the flag bit of the verbs' flag word that switches it on (0: --labels,
- * --markers and --mapping come with an argument of their own), its tables (-1: none), its timer in res_times_t, its point writer.  A further comparison
+ * --markers, --mapping and --pseudotime come with an argument of their own), its tables (-1: none), its timer in res_times_t, its point writer.  A further comparison
  * is an entry here, its writer above and its table in GRID_TABLES (grid_rows.c) */
 static const struct {
     uint32_t flag; int table[2]; size_t timer;
@@ -406,18 +427,20 @@ static const struct {
     [CMP_MARKERS]   = { 0,                         { TB_MARKERS, -1 },              offsetof(res_times_t, markers),   mk_point },
     [CMP_COEXPR]    = { FASTF_SWEEP_COEXPRESSION,  { TB_COEXPR, -1 },               offsetof(res_times_t, coexpr),    cx_point },
     [CMP_MAPPING]   = { 0,                         { TB_MAPPING, -1 },              offsetof(res_times_t, mapping),   map_point },
+    [CMP_PTIME]     = { 0,                         { TB_PTIME, -1 },                offsetof(res_times_t, ptime),     pt_point },
     [CMP_GENE_FID]  = { FASTF_SWEEP_GENE_FIDELITY, { TB_GENE_FIDELITY, -1 },        offsetof(res_times_t, gene_fid),  gene_fid_point },
     [CMP_FIDELITY]  = { FASTF_SWEEP_FIDELITY,      { TB_FIDELITY, -1 },             offsetof(res_times_t, fidelity),  fid_point },
 };
 
 /* the tables are opened in the order of their ids, which is the order of the renames */
-int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers, uint32_t mapping)
+int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers, uint32_t mapping,
+                       const fastf_ptime_t *ptime)
 {
     uint32_t want = 0;
     memset(C, 0, sizeof *C);
-    C->labels = labels; C->markers = markers;
+    C->labels = labels; C->markers = markers; C->ptime = ptime;
     for (int c = 0; c < CMP_N_; c++) {
-        if (!(c == CMP_LABELS ? labels != NULL : c == CMP_MARKERS ? markers != 0 : c == CMP_MAPPING ? mapping != 0 : (flags & cmp_desc[c].flag) != 0)) continue;
+        if (!(c == CMP_LABELS ? labels != NULL : c == CMP_MARKERS ? markers != 0 : c == CMP_MAPPING ? mapping != 0 : c == CMP_PTIME ? ptime != NULL : (flags & cmp_desc[c].flag) != 0)) continue;
         C->on |= 1u << c;
         for (int k = 0; k < 2; k++) if (cmp_desc[c].table[k] >= 0) want |= 1u << (cmp_desc[c].table[k] - TB_FIDELITY);
     }
@@ -426,14 +449,14 @@ int fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, u
     return 0;
 }
 
-/* what the device side computes for the comparisons that are on: the neighbour sets for --labels and --mapping too */
+/* what the device side computes for the comparisons that are on: the neighbour sets for --labels, --mapping and --pseudotime too */
 void fastf_res_cmp_cfg(const res_cmp_t *C, res_cfg_t *cfg)
 {
     cfg->fidelity = res_cmp_on(C, CMP_FIDELITY); cfg->gene_fid = res_cmp_on(C, CMP_GENE_FID); cfg->labels = res_cmp_on(C, CMP_LABELS);
-    cfg->mapping = res_cmp_on(C, CMP_MAPPING);
-    cfg->neighbors = res_cmp_on(C, CMP_NEIGHBORS) || cfg->labels || cfg->mapping;
+    cfg->mapping = res_cmp_on(C, CMP_MAPPING); cfg->ptime = res_cmp_on(C, CMP_PTIME);
+    cfg->neighbors = res_cmp_on(C, CMP_NEIGHBORS) || cfg->labels || cfg->mapping || cfg->ptime;
     cfg->coexpr = res_cmp_on(C, CMP_COEXPR);
-    cfg->lab_t = C->labels; cfg->markers = C->markers;
+    cfg->lab_t = C->labels; cfg->markers = C->markers; cfg->pt_t = C->ptime;
 }
 
 int fastf_res_cmp_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T)

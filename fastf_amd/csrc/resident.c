@@ -263,6 +263,14 @@ int fastf_res_rate_open(res_rate_t *S, const char *verb, const resident_t *R, co
         if (fastf_labels_assign(S->cfg.lab_t, L->barcode, n_cells, S->h_lab.lab) || (n_cells && fastf_devmem_copy(S->d_lab.lab, S->h_lab.lab, n_cells))) return RES_FAIL;
         T->labels += fastf_res_now() - tl;
     }
+    if (S->cfg.ptime) {                                     /* the pseudotime block and its pinned copy; t[] is ranked among the pair's cells and goes up once per pair */
+        const size_t pt_cells = res_pt_cells(room_cells), bytes = res_pt_layout(NULL, pt_cells).bytes;
+        if (res_room(&S->buf.pt, RES_DEV, bytes, device) || res_room(&S->buf.h_pt, RES_PIN, bytes, device)) return no_room(S, "the pseudotime arrays", bytes);
+        S->d_pt = res_pt_layout(S->buf.pt.p, pt_cells); S->h_pt = res_pt_layout(S->buf.h_pt.p, pt_cells);
+        const double tp = fastf_res_now();
+        if (fastf_ptime_assign(S->cfg.pt_t, L->barcode, n_cells, S->h_pt.t, &S->pt_m) || (n_cells && fastf_devmem_copy(S->d_pt.t, S->h_pt.t, (size_t)n_cells * 4))) return RES_FAIL;
+        T->ptime += fastf_res_now() - tp;
+    }
     if (S->cfg.mapping) {                                   /* the device and the pinned block of the mapping.  The copy of the full planes waits for P (fastf_res_full_keep) */
         const size_t lab_cells = S->cfg.labels ? res_lab_cells(room_cells) : 0, n_labels = S->cfg.labels ? S->n_labels : 0;
         const size_t dev_bytes = res_map_layout(NULL, FASTF_MAPPING_K, room_cells, lab_cells, n_labels, 0).bytes;
@@ -536,6 +544,27 @@ int fastf_res_point_labels(res_rate_t *S, const char *point_name, res_times_t *T
     return 0;
 }
 
+/* --pseudotime: the medians over one list of neighbours (the full sets: side 0, the point's: 1, the mapping list: 2) and their census,
+ * then that half of the block to the host in one copy */
+static int pt_side(res_rate_t *S, int side, const uint32_t *d_idx, const uint32_t *d_cnt, const char *where)
+{
+    if (fastf_dev_ptime_medians(S->e, d_idx, d_cnt, S->d_pt.t, S->n_cells, FASTF_NEIGHBORS_K, S->d_pt.half[side].est, S->d_pt.half[side].valued, NULL) ||
+        fastf_dev_ptime_census(S->e, S->d_pt.half[side].est, S->d_pt.t, S->n_cells, S->d_pt.half[side].census, NULL) || fastf_devmem_sync())
+        return fastf_res_err("%s: --pseudotime at %s: %s", S->verb, where, fastf_last_error_copy());
+    return fastf_devmem_copy(S->h_pt.half[side].census, S->d_pt.half[side].census, S->d_pt.half_bytes);
+}
+
+int fastf_res_point_ptime(res_rate_t *S, const char *point_name, res_times_t *T)
+{
+    if (!S->cfg.ptime) return 0;
+    char where[128];
+    const double tt = fastf_res_now();
+    snprintf(where, sizeof where, "point %s", point_name);
+    if (pt_side(S, 1, S->d_nbr.idx[1], S->d_nbr.cnt[1], where)) return 1;
+    T->ptime += fastf_res_now() - tt;
+    return 0;
+}
+
 _Static_assert(FASTF_MAPPING_K == FASTF_NEIGHBORS_K, "hood compares M(i) with the full neighbour set of the same k");
 int fastf_res_point_mapping(res_rate_t *S, const char *point_name, res_times_t *T)
 {
@@ -552,6 +581,13 @@ int fastf_res_point_mapping(res_rate_t *S, const char *point_name, res_times_t *
         return fastf_res_err("%s: --mapping at point %s: %s", S->verb, point_name, fastf_last_error_copy());
     if (S->n_cells && fastf_devmem_copy(S->h_map.sd, d.sd, d.out_bytes)) return 1;
     T->mapping += fastf_res_now() - tt;
+    if (S->cfg.ptime) {                                     /* the ranks M(i) carries, while the list is live: its cells are full-depth cells of the same pair */
+        char where[128];
+        const double tp = fastf_res_now();
+        snprintf(where, sizeof where, "point %s (the mapping list)", point_name);
+        if (pt_side(S, 2, d.idx, d.km, where)) return 1;
+        T->ptime += fastf_res_now() - tp;
+    }
     return 0;
 }
 
@@ -652,6 +688,12 @@ int fastf_res_full_keep(res_rate_t *S, res_times_t *T)
         if (lab_votes(S, 0)) return 1;
         T->labels += fastf_res_now() - tt; tt = fastf_res_now();
     }
+    if (S->cfg.ptime) {                                         /* the estimates and the census of the full sets, which stay for every point of the pair */
+        char where[96];
+        snprintf(where, sizeof where, "cell rate %.3f, seed %u", (double)S->rate_cell, S->seed);
+        if (pt_side(S, 0, S->d_nbr.idx[0], S->d_nbr.cnt[0], where)) return 1;
+        T->ptime += fastf_res_now() - tt; tt = fastf_res_now();
+    }
     if (S->cfg.markers) {                                       /* the tables and ranks of the full rows, while their planes are still in the plane buffer */
         if (mk_tables(S, 0)) return 1;
         T->markers += fastf_res_now() - tt; tt = fastf_res_now();
@@ -745,6 +787,7 @@ int fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *
     if (fastf_res_point_gene_fidelity(S, point_name, T)) return 1;
     if (fastf_res_point_neighbors(S, point_name, T)) return 1;
     if (fastf_res_point_labels(S, point_name, T)) return 1;       /* (directly behind the neighbour sets it votes with) */
+    if (fastf_res_point_ptime(S, point_name, T)) return 1;        /* (on the same sets) */
     if (fastf_res_point_mapping(S, point_name, T)) return 1;      /* (the point's byte planes against the full rows' planes) */
     if (fastf_res_point_markers(S, point_name, T)) return 1;      /* (on the byte planes those sets were made of) */
     return fastf_res_point_coexpr(S, point_name, T);             /* (on planes of its own) */
@@ -1066,11 +1109,11 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
 {
     const struct ropt opts[] = {
         {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'P', "mapping", 0}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'P', "mapping", 0}, {'T', "pseudotime", 1}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
-    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->mapping = 0; out->labels = NULL; out->markers = 0;
+    out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->mapping = 0; out->labels = NULL; out->pseudotime = NULL; out->markers = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const struct ropt *o = NULL;
@@ -1084,7 +1127,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                 if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
             if (o && eq) val = eq + 1;
         } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXPLMER", k->s)) { o = k; break; }
+            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXPTLMER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
         if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
@@ -1118,6 +1161,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         case 'X': out->coexpression = 1; break;
         case 'P': out->mapping = 1; break;
         case 'L': out->labels = val; break;
+        case 'T': out->pseudotime = val; break;
         case 'M': markers_text = val; break;
         case 'E': seeds_text = val; break;
         case 'R': reps_text = val; break;
@@ -1183,6 +1227,7 @@ void fastf_res_print_generated(const char *verb, const res_args_t *a)
     if (a->markers) printf("%s_markers.tsv is generated.\n", verb);
     if (a->coexpression) printf("%s_coexpr.tsv is generated.\n", verb);
     if (a->mapping) printf("%s_mapping.tsv is generated.\n", verb);
+    if (a->pseudotime) printf("%s_pseudotime.tsv is generated.\n", verb);
     if (a->n_seeds) printf("%s_reps.tsv is generated.\n", verb);
     printf("%s.tsv is generated.\n", verb);
 }

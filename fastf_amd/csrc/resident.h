@@ -24,6 +24,9 @@
  * --mapping looks every cell of the point up among ALL full-depth cells of the pair (fastf_res_point_mapping, directly behind
  * fastf_res_point_labels, while the point's byte planes are in the plane buffer); alone it switches on what --labels alone switches on, and
  * keeps a copy of the full rows' planes for the life of the pair.
+ * --pseudotime FILE estimates every cell's rank along the user's value back from its neighbour sets and counts the order of all pairs
+ * (fastf_res_point_ptime, directly behind fastf_res_point_labels; the mapping list's side inside fastf_res_point_mapping); alone it switches
+ * on what --labels alone switches on.
  * --coexpression compares the co-expression partners of the genes of A, at full depth and at the point (fastf_res_point_coexpr, behind
  * fastf_res_point_markers and before fastf_res_point_cells); alone it switches on the full-depth rows, the pair's per-gene sums and the
  * slot map, and nothing of the neighbour sets. */
@@ -48,7 +51,7 @@ enum { RES_OK = 0, RES_FAIL = 1, RES_NOT_COVERED = 2 };   /* NOT_COVERED: keys w
 /* layout of the small device block of one point (u64 words; atomics and plain loads on different 256-byte segments) */
 enum { SM_KEYS = 0, SM_CNT = 32, SM_NNZ = 64, SM_BASE = 96, SM_HITS = 128, SM_UROWS = 160, SM_LEVEL = 192, SM_FULL = 224, SM_WORDS_ = 256 };   /* SM_UROWS: --cells, K3u's row count; SM_LEVEL: level, the result block of a step (FASTF_LEVEL_OUT_WORDS); SM_FULL: --fidelity, the row count of the pair's full rows (no point clears it) */
 
-typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors, labels, markers, coexpr, mapping; uint32_t opens, relays, passes; } res_times_t;   /* mapping: --mapping alone — the copy of the full planes, the mapping calls, the shared counts and votes, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); coexpr: --coexpression alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when none of the three flags below is set; markers: --markers alone — the kernel calls on the planes, their D2H, the ranks, rows and files; labels: --labels alone — the label arrays of every pair, the vote calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
+typedef struct { double lists, decode, engine, block_k1a, planes, device, d2h, summary, write, genes, cells_dev, cells, reps, search, fidelity, gene_fid, neighbors, labels, markers, coexpr, mapping, ptime; uint32_t opens, relays, passes; } res_times_t;   /* ptime: --pseudotime alone — the ranks of every pair, the median and census calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); mapping: --mapping alone — the copy of the full planes, the mapping calls, the shared counts and votes, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); coexpr: --coexpression alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when none of the three flags below is set; markers: --markers alone — the kernel calls on the planes, their D2H, the ranks, rows and files; labels: --labels alone — the label arrays of every pair, the vote calls, their D2H, rows and files (the neighbour sets it switches on are booked under neighbors); neighbors: --neighbors alone — the planes, the Gram products and selections, the shared counts, their D2H, rows and files, and the full point and per-gene sums of every pair when neither flag above is set; gene_fid: --gene-fidelity alone — what fidelity books, and the full point of every pair when --fidelity is not set; fidelity: --fidelity alone — the full point of every pair, the joins, their D2H, rows and files; search, passes: level alone — the seconds and the number of its search passes; genes: --genes alone (D2H, rows, files); cells_dev, cells: --cells alone (full sort + K3u + summary + D2H; rows and files); reps: the replicate tables and the per-gene accumulators; opens, relays: fastf_res_rate_open calls, and those that laid the blocked copy out */
 
 /* the error message of the grid files, set as printf formats it; returns 1 (grid_rows.c) */
 int    fastf_res_err(const char *fmt, ...) __attribute__((format(printf, 1, 2))) FASTF_HIDDEN;
@@ -74,7 +77,7 @@ void fastf_res_free(resident_t *R) FASTF_HIDDEN;
 /* one (cell rate, seed) pair: the engine, the records in its layout, K1a (the cell scratch and the hit count H serve every point),
  * the buffers of a point.  DESIGN.md section 10q describes this state once; in short:
  * cfg   what the caller sets before the first open and no open or close touches: the comparisons that are on (fastf_res_cmp_cfg, from
- *       the mask of the run's res_cmp_t: neighbors is set with labels and with mapping too; markers = N needs labels), max_cells, the most cells any pair of the run samples (0: unknown), which the lists tell,
+ *       the mask of the run's res_cmp_t: neighbors is set with labels, with mapping and with ptime too; markers = N needs labels), max_cells, the most cells any pair of the run samples (0: unknown), which the lists tell,
  *       and no_reuse (the verbs read FASTF_RES_NO_REUSE=1 once per run): fresh buffers and a fresh blocked copy for every pair.
  * buf   the buffer table: every device, pinned or host buffer of the state.  The buffers outlive the pair: a run keeps ONE res_rate_t,
  *       zeroed before its first open, and every later fastf_res_rate_open on it ends the pair before (its engine) and takes its buffers
@@ -85,7 +88,7 @@ void fastf_res_free(resident_t *R) FASTF_HIDDEN;
  * the same word runs K1a alone */
 typedef struct { union { void *p; uint8_t *u8; uint32_t *u32; uint64_t *u64; }; size_t have, n; int kind; } res_buf_t;
 enum { RES_DEV = 1, RES_PIN, RES_HOST };             /* the kinds of a buffer: device, pinned, plain host memory */
-typedef struct { int fidelity, gene_fid, neighbors, labels, coexpr, mapping; const fastf_labels_t *lab_t; uint32_t markers, max_cells; int no_reuse; } res_cfg_t;
+typedef struct { int fidelity, gene_fid, neighbors, labels, coexpr, mapping, ptime; const fastf_labels_t *lab_t; const fastf_ptime_t *pt_t; uint32_t markers, max_cells; int no_reuse; } res_cfg_t;
 typedef struct {
     res_cfg_t cfg;
     const char *verb; const resident_t *R; const fastf_lists_t *L; int device; float rate_cell; uint32_t seed;
@@ -98,6 +101,7 @@ typedef struct {
     int cells, sorted_full; uint64_t *sorted, *sorted_other;
     uint64_t full_nnz;                   /* the pair's full rows in buf.full (their number in buf.small[SM_FULL] too) */
     size_t nbr_map_bytes, mk_set;        /* the bytes of the slot map; of one set of marker tables in buf.h_mk */
+    uint32_t pt_m;                       /* --pseudotime: the cells of the pair with a value */
     uint32_t hvg_k, nbr_planes, full_planes, n_labels;   /* the genes of A and the byte planes of the row set at hand (fastf_res_full_keep); full_planes: --mapping, those of the full rows in buf.fplanes */
     struct {
         res_buf_t blk, keys, tmp, small, rows, upc, gpc, h_small, h_upc, h_gpc, h_rows;   /* h_rows.n: the rows there is room for */
@@ -105,10 +109,11 @@ typedef struct {
         res_buf_t full, fid, h_fid, gx, gfid, h_gfid;   /* gx: the partner column, x of every point row (u32, R->n entries) */
         res_buf_t nbr, h_nbr, nplanes, lab, h_lab, mk, h_mk, mk_rank;   /* mk_rank: the ranks of the full rows and of the point (host) */
         res_buf_t map, h_map, fplanes;       /* --mapping: the device and the pinned block, the byte planes of the full rows for the life of the pair */
+        res_buf_t pt, h_pt;                  /* --pseudotime: the device and the pinned block */
         res_buf_t cx, h_cx, cxwork;          /* --coexpression: the device and the pinned block, the gene-major planes of the row set at hand */
     } buf;
     res_cellsum_v h_cs; res_level_v lv; res_fid_v d_fid, h_fid; res_gfid_v d_gfid, h_gfid;   /* with --genes h_gfid.sy and h_gfid.c are buf.h_upg and buf.h_cpg */
-    res_nbr_v d_nbr; res_nbr_pin_v h_nbr; res_lab_v d_lab, h_lab; res_map_v d_map, h_map; res_cx_v d_cx; res_cx_pin_v h_cx;
+    res_nbr_v d_nbr; res_nbr_pin_v h_nbr; res_lab_v d_lab, h_lab; res_map_v d_map, h_map; res_pt_v d_pt, h_pt; res_cx_v d_cx; res_cx_pin_v h_cx;
 } res_rate_t;
 static inline res_rows_t res_rows_point(const res_rate_t *S) { return res_rows(S->buf.rows.p, S->R->n); }   /* the rows of the last point */
 static inline res_rows_t res_rows_full(const res_rate_t *S) { return res_rows(S->buf.full.p, S->R->n); }     /* the full rows of the pair */
@@ -182,13 +187,19 @@ static inline const uint32_t *res_mk_rank(const res_rate_t *S, int point) { retu
  * shared counts with the full sets, with --labels the votes over M, then self_dot, self_rank, k_map, hood and the vote bytes to the host
  * in ONE copy (S->h_map).  A norm of 2^42 and beyond on either side fails the point by name.  Nothing without S->cfg.mapping */
 int  fastf_res_point_mapping(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
+/* --pseudotime (S->cfg.ptime; S->cfg.neighbors is on with it).  fastf_res_rate_open ranks the pair's cells (fastf_ptime_assign) and uploads
+ * t[] beside lab[].  One side is a median call and a census call on a list of neighbours, then its half of the block — the census, est,
+ * valued — to the host in ONE copy: the full sets in fastf_res_full_keep (half 0, which stays for every point of the pair), the point's
+ * sets in fastf_res_point_ptime (half 1), directly behind fastf_res_point_labels, and with --mapping the list M inside
+ * fastf_res_point_mapping (half 2), while that list is live.  Nothing without S->cfg.ptime */
+int  fastf_res_point_ptime(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 /* --coexpression (S->cfg.coexpr).  fastf_res_full_keep ranks A exactly as for --neighbors (alone it switches on the full rows, the pair's
  * per-gene sums and the slot map, and nothing of the neighbour sets), and leaves the partner sets of the full rows on the device and
  * k_full in S->h_cx.kf.  fastf_res_point_coexpr: directly behind fastf_res_point_markers — the gene-major planes, D, S and the partner sets
  * of the point's rows, the shared counts, k_point and shared to the host (S->h_cx.kp, S->h_cx.sh).  A count beyond three planes, sums
  * beyond 64 bits or n * max Q of 2^63 and beyond fail the pair or the point by name.  Nothing without S->cfg.coexpr */
 int  fastf_res_point_coexpr(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
-/* the seven above in their order (fidelity, gene fidelity, neighbors, labels, mapping, markers, co-expression), behind fastf_res_point_run and before
+/* the eight above in their order (fidelity, gene fidelity, neighbors, labels, pseudotime, mapping, markers, co-expression), behind fastf_res_point_run and before
  * fastf_res_point_write and fastf_res_point_cells: the one place a further comparison of a point is called from */
 int  fastf_res_point_compare(res_rate_t *S, const char *point_name, res_times_t *T) FASTF_HIDDEN;
 
@@ -204,7 +215,7 @@ int  fastf_res_point_cells(res_rate_t *S, const char *point_name, res_times_t *T
  * exported fastf_<verb>_<stem>_header getters come too) and looked up by (verb index, table id) */
 typedef struct res_verb res_verb_t;
 enum { VERB_SWEEP, VERB_CAP, VERB_LEVEL };
-enum { TB_GENES, TB_CELLS, TB_FIDELITY, TB_GENE_FIDELITY, TB_NEIGHBORS, TB_LABELS, TB_LABEL_CLASSES, TB_MARKERS, TB_COEXPR, TB_MAPPING, TB_REPS, TB_GENES_REPS, TB_N_ };
+enum { TB_GENES, TB_CELLS, TB_FIDELITY, TB_GENE_FIDELITY, TB_NEIGHBORS, TB_LABELS, TB_LABEL_CLASSES, TB_MARKERS, TB_COEXPR, TB_MAPPING, TB_PTIME, TB_REPS, TB_GENES_REPS, TB_N_ };
 const char *fastf_res_table_stem(int table) FASTF_HIDDEN;
 const char *fastf_res_table_header(int verb, int table) FASTF_HIDDEN;
 
@@ -247,21 +258,22 @@ int fastf_res_cells_open(res_cells_t *C, int on, const res_verb_t *V, const char
 int fastf_res_cells_point(res_cells_t *C, const res_rate_t *S, const char *dir, const char *row) FASTF_HIDDEN;
 int fastf_res_cells_close(res_cells_t *C, int ok) FASTF_HIDDEN;
 
-/* the comparisons of a point against full depth: --neighbors, --labels FILE, --markers N, --coexpression, --mapping, --gene-fidelity, --fidelity, in the order a
+/* the comparisons of a point against full depth: --neighbors, --labels FILE, --markers N, --coexpression, --mapping, --pseudotime FILE, --gene-fidelity, --fidelity, in the order a
  * point writes them.  Each is ONE descriptor in res_tables.c — its tables (labels has two: labels and label_classes), its timer in
  * res_times_t, its point writer, which puts the point's row(s) into the table(s) and, with a directory, <point dir>/<name>.tsv.gz
  * (labels: labels.tsv.gz and label_confusion.tsv.gz) from the host views of S.  on: bit c set — comparison c is on; tsv: the tables
- * TB_FIDELITY .. TB_MAPPING at [table - TB_FIDELITY], which is the order they are opened and renamed in.
- * fastf_res_cmp_open clears C and opens the tables of the comparisons the flag word (FASTF_SWEEP_*), labels != NULL, markers != 0 and
- * mapping != 0 switch on; on failure nothing of them is left.  fastf_res_cmp_cfg: what the device side is to compute for them (S->cfg).
+ * TB_FIDELITY .. TB_PTIME at [table - TB_FIDELITY], which is the order they are opened and renamed in.
+ * fastf_res_cmp_open clears C and opens the tables of the comparisons the flag word (FASTF_SWEEP_*), labels != NULL, markers != 0,
+ * mapping != 0 and ptime != NULL switch on; on failure nothing of them is left.  fastf_res_cmp_cfg: what the device side is to compute for them (S->cfg).
  * fastf_res_cmp_point: one point, behind fastf_res_point_compare — every writer that is on, timed into its timer (list_value == 0:
  * rate_depth in the second column).  fastf_res_cmp_close closes every table before it renames any, and where a rename fails no
  * table is left and the message names the file.  A C that is all zero is closed: every call on it does nothing */
-enum { CMP_NEIGHBORS, CMP_LABELS, CMP_MARKERS, CMP_COEXPR, CMP_MAPPING, CMP_GENE_FID, CMP_FIDELITY, CMP_N_ };
-#define RES_CMP_TABLES (TB_MAPPING - TB_FIDELITY + 1)
-typedef struct { uint32_t on; res_tsv_t tsv[RES_CMP_TABLES]; const fastf_labels_t *labels; uint32_t markers; } res_cmp_t;
+enum { CMP_NEIGHBORS, CMP_LABELS, CMP_MARKERS, CMP_COEXPR, CMP_MAPPING, CMP_PTIME, CMP_GENE_FID, CMP_FIDELITY, CMP_N_ };
+#define RES_CMP_TABLES (TB_PTIME - TB_FIDELITY + 1)
+typedef struct { uint32_t on; res_tsv_t tsv[RES_CMP_TABLES]; const fastf_labels_t *labels; uint32_t markers; const fastf_ptime_t *ptime; } res_cmp_t;
 static inline int res_cmp_on(const res_cmp_t *C, int c) { return (int)(C->on >> c & 1); }
-int  fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers, uint32_t mapping) FASTF_HIDDEN;
+int  fastf_res_cmp_open(res_cmp_t *C, const res_verb_t *V, const char *out_dir, uint32_t flags, const fastf_labels_t *labels, uint32_t markers, uint32_t mapping,
+                        const fastf_ptime_t *ptime) FASTF_HIDDEN;
 void fastf_res_cmp_cfg(const res_cmp_t *C, res_cfg_t *cfg) FASTF_HIDDEN;
 int  fastf_res_cmp_point(res_cmp_t *C, const res_rate_t *S, const char *dir, float rate_depth, uint64_t list_value, res_times_t *T) FASTF_HIDDEN;
 int  fastf_res_cmp_close(res_cmp_t *C, int ok) FASTF_HIDDEN;
@@ -301,13 +313,13 @@ void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_H
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
 
-/* the command line the three verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --coexpression --mapping --labels --markers --seeds --reps and ONE list option of the verb's own
+/* the command line the three verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --coexpression --mapping --labels --markers --pseudotime --seeds --reps and ONE list option of the verb's own
  * (list_short / list_long: -r/--depth, -n/--reads, -m/--umis).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
  * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
  * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given.
  * fastf_res_args_flags: the flag word of the options (the bits of FASTF_SWEEP_*, which FASTF_CAP_* and FASTF_LEVEL_* repeat);
  * fastf_res_print_generated: the "... is generated." lines of a run that succeeded */
-typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors, coexpression, mapping; const char *labels; uint32_t markers;   /* markers: N of --markers, 0 without */
+typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors, coexpression, mapping; const char *labels, *pseudotime; uint32_t markers;   /* markers: N of --markers, 0 without */
                  uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
 int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
                          res_args_t *a) FASTF_HIDDEN;
@@ -324,7 +336,7 @@ typedef struct {
     const float *rates_cell; uint32_t n_c;
     const float *rates_depth; const uint64_t *caps; uint32_t n_list;
     const uint32_t *seeds; uint32_t n_s; int reps;
-    uint32_t flags; const char *labels_path; uint32_t markers, mapping;
+    uint32_t flags; const char *labels_path; uint32_t markers, mapping; const char *ptime_path;
 } res_job_t;
 /* the tables of a run, zeroed before the first open: every close is safe on a table that was never opened */
 typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_cmp_t Fd; res_reps_t P; } res_tables_t;

@@ -327,14 +327,22 @@ int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcod
     return fastf_res_check_markers("sweep", markers, labels_path) || fastf_res_grid_run(&sweep_verb, &job);
 }
 
-/* --mapping: the most general call — labels_path may be NULL and markers 0 */
+/* --mapping: labels_path may be NULL and markers 0 */
 int fastf_sweep_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
                        uint32_t markers, uint32_t mapping)
 {
+    return fastf_sweep_pseudotime(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, flags, seed, labels_path, markers, mapping, NULL);
+}
+
+/* --pseudotime FILE, the most general call: labels_path and pseudotime_path may be NULL, markers and mapping 0 */
+int fastf_sweep_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                       uint32_t markers, uint32_t mapping, const char *pseudotime_path)
+{
     const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
                             .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers, .mapping = mapping };
+                            .labels_path = labels_path, .markers = markers, .mapping = mapping, .ptime_path = pseudotime_path };
     if (mapping > 1) return fastf_res_err("sweep: --mapping: %u, 0 or 1", mapping);
     return (markers && fastf_res_check_markers("sweep", markers, labels_path)) || fastf_res_grid_run(&sweep_verb, &job);
 }
@@ -382,6 +390,11 @@ static void usage_sweep(FILE *f)
             "                          the 2000 most variable genes, decided in exact integers): sweep_mapping.tsv and mapping.tsv.gz per point, with\n"
             "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
             "                          full-depth neighbours and, with --labels, the label they vote for; resident form only\n"
+            "        --pseudotime=<file>\n"
+            "                          one `barcode<TAB>value` per line (a pseudotime or any per-cell score of the full-depth analysis): sweep_pseudotime.tsv\n"
+            "                          and pseudotime.tsv.gz per point, with the value's rank estimated back per cell as the lower median over its 15\n"
+            "                          nearest neighbours, at full depth, at the point and, with --mapping, over the full-depth cells it maps among, and\n"
+            "                          Kendall's tau-b of the estimate against the value over all pairs of cells, counted exactly; resident form only\n"
             "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
             "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
             "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
@@ -405,7 +418,8 @@ int cmd_sweep(int argc, const char **argv)
     }
     if (fastf_res_check_inputs(&A)) return 1;
     const uint32_t flags = fastf_res_args_flags(&A);
-    if (A.mapping ? fastf_sweep_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
+    if (A.pseudotime ? fastf_sweep_pseudotime(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, A.mapping, A.pseudotime) :
+        A.mapping ? fastf_sweep_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
         A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
         A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
         A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)

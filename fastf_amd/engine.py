@@ -492,6 +492,16 @@ class Engine:
         check(self._L.fastf_dev_label_votes(self._h, d_idx or None, d_cnt or None, d_lab or None, n_cells, k, n_labels, d_pred or None, d_same or None,
                                             d_labelled or None, d_conf or None, stream))
 
+    def dev_ptime_medians(self, d_idx, d_cnt, d_t, n_cells, k, d_est, d_valued, stream=0):
+        """--pseudotime: the neighbour lists Engine.dev_neighbors or Engine.dev_mapping left (d_idx, d_cnt) and d_t (u32[n_cells], 0 without a
+        value) -> d_est (u32[n_cells], the lower median of the valued neighbours' t, 0 with none) and d_valued (u32[n_cells]); stream-ordered"""
+        check(self._L.fastf_dev_ptime_medians(self._h, d_idx or None, d_cnt or None, d_t or None, n_cells, k, d_est or None, d_valued or None, stream))
+
+    def dev_ptime_census(self, d_est, d_t, n_cells, d_out, stream=0):
+        """--pseudotime: the order census of d_est against d_t over the cells with both above 0 -> d_out (u64[7]: conc disc tie_e tie_t tie_both
+        cells shift_sum, zeroed by the call); one workgroup per pair of tiles of sweep.PTIME_TILE cells; stream-ordered"""
+        check(self._L.fastf_dev_ptime_census(self._h, d_est or None, d_t or None, n_cells, d_out or None, stream))
+
     def dev_marker_auc(self, d_planes, planes, n_cells, K, d_lab, n_labels, d_s2u, d_det, d_sum, d_n_per_label, stream=0):
         """--markers: the byte planes Engine.dev_neighbor_planes left (d_planes, `planes` of them) and d_lab (u8[n_cells]) -> d_s2u, d_sum
         (u64[n_labels * K]), d_det (u32[n_labels * K]) and d_n_per_label (u32[n_labels]), all cleared by the call; FASTF_MARKERS_LDS=0:

@@ -40,6 +40,8 @@ LABEL_CLASSES_COLUMNS = _renamed(_cap.LABEL_CLASSES_COLUMNS)
 MARKERS_COLUMNS = _renamed(_cap.MARKERS_COLUMNS)
 COEXPRESSION_COLUMNS = _renamed(_cap.COEXPRESSION_COLUMNS)
 MAPPING_COLUMNS = _renamed(_cap.MAPPING_COLUMNS)
+PSEUDOTIME_COLUMNS = _renamed(_cap.PSEUDOTIME_COLUMNS)
+read_point_pseudotime = _sweep.read_point_pseudotime
 POINT_MAPPING_COLUMNS = _sweep.POINT_MAPPING_COLUMNS
 mapping_from_coo, mapping_row, read_point_mapping = _sweep.mapping_from_coo, _sweep.mapping_row, _sweep.read_point_mapping
 read_point_coexpression = _sweep.read_point_coexpression
@@ -54,7 +56,8 @@ def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neig
 
 
 def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
-          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+          fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+        pseudotime=None):
     """`fastF level -b bam -a barcodes -f features -o out -c rates_cell -m umi_caps -s seed [--summary-only] [--genes] [--cells]`; returns
     the rows of out/level.tsv as dicts of strings (read_table); genes / cells: the files cap.cap() leaves, under the names level_*; fidelity:
     out/level_fidelity.tsv (read_fidelity_table) and a fidelity.tsv.gz per point directory; gene_fidelity: out/level_gene_fidelity.tsv
@@ -64,6 +67,12 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_level_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
+                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
+                                                int(bool(mapping)), enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if _sweep._mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
@@ -85,13 +94,21 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
 
 
 def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summary_only: bool = False, genes: bool = False, cells: bool = False,
-               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+               fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+        pseudotime=None):
     """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
     rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
     m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
     sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _sweep._pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_level_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
+                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
+                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
+                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
+                                                int(bool(mapping)), enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "level.tsv"))
     if _sweep._mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
                                                 m.ctypes.data, len(m), sd.ctypes.data, len(sd),
@@ -161,6 +178,11 @@ def gene_fidelity_summary_row(rate_cell, umi_cap, seed, n_cells, sum_x, sum_y, s
 
 def read_neighbors_table(path):
     return _sweep.read_cells_table(path, NEIGHBORS_COLUMNS)
+
+
+def read_pseudotime_table(path):
+    """the rows of level_pseudotime.tsv as dicts of strings"""
+    return _sweep.read_cells_table(path, PSEUDOTIME_COLUMNS)
 
 
 def read_mapping_table(path):

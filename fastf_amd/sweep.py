@@ -45,6 +45,11 @@ MAPPING_TAIL_COLUMNS = ("seed", "n_cells", "hvg_k", "k", "cells_defined", "self_
 MAPPING_COLUMNS = ("rate_cell", "rate_depth") + MAPPING_TAIL_COLUMNS
 POINT_MAPPING_COLUMNS = ("barcode", "self_dot", "self_rank", "k_map", "k_full", "hood", "pred_map")     # <point dir>/mapping.tsv.gz
 MAPPING_K = 15
+PSEUDOTIME_TAIL_COLUMNS = ("seed", "n_cells", "k", "cells_valued") + tuple("%s_%s" % (c, m) for m in ("full", "point", "map") for c in ("cells", "conc", "disc", "tau", "shift"))
+PSEUDOTIME_COLUMNS = ("rate_cell", "rate_depth") + PSEUDOTIME_TAIL_COLUMNS
+POINT_PSEUDOTIME_COLUMNS = ("barcode", "rank", "est_full", "valued_full", "est_point", "valued_point", "est_map", "valued_map")     # <point dir>/pseudotime.tsv.gz
+PTIME_TILE = 1024         # FASTF_PTIME_TILE: the tile edge of the device census
+PTIME_OUT_WORDS = 7       # conc disc tie_e tie_t tie_both cells shift_sum
 MAPPING_NO_RANK = 0xFFFFFFFF
 LABELS_TAIL_COLUMNS = ("seed", "n_cells", "k", "n_labels", "cells_labelled", "agree_full", "agree_point", "accuracy_full", "accuracy_point", "kept",
                        "purity_full", "purity_point")
@@ -74,6 +79,11 @@ def _mapping_call(mapping, markers) -> bool:
     return bool(mapping) and (markers is None or _markers_n(markers) != 0)
 
 
+def _pseudotime_call(pseudotime, markers) -> bool:
+    """the _pseudotime entry point is taken: pseudotime=<path>, unless markers=N is given and no N the C call takes"""
+    return pseudotime is not None and (markers is None or _markers_n(markers) != 0)
+
+
 def _markers_n(markers) -> int:
     """N of markers=N as the u32 the C call takes: what is no integer or does not fit goes over as 0, which the call refuses by name"""
     try:
@@ -84,7 +94,8 @@ def _markers_n(markers) -> int:
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
-          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+          cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+               pseudotime=None):
     """`fastF sweep -b bam -a barcodes -f features -o out -c rates_cell -r rates_depth -s seed [--summary-only] [--genes] [--cells]`;
     returns the rows of out/sweep.tsv as dicts of strings (read_table); genes=True also leaves out/sweep_genes.tsv
     (read_genes_table), out/sweep_gene_cells.tsv.gz and a genes.tsv.gz per point directory; cells=True also leaves
@@ -99,10 +110,18 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     markers.tsv.gz per point directory (read_point_markers); coexpression=True (`--coexpression`) the comparison between the genes:
     out/sweep_coexpr.tsv (read_coexpression_table) and a coexpr.tsv.gz per point directory (read_point_coexpression); mapping=True
     (`--mapping`) every point cell looked up among the full-depth cells: out/sweep_mapping.tsv (read_mapping_table) and a mapping.tsv.gz
-    per point directory (read_point_mapping)"""
+    per point directory (read_point_mapping); pseudotime=<path> (`--pseudotime`: one barcode<TAB>value per line) the order of the cells along
+    that value, estimated back from the neighbour sets: out/sweep_pseudotime.tsv (read_pseudotime_table) and a pseudotime.tsv.gz per point
+    directory (read_point_pseudotime)"""
     rc, prc = _floats(rates_cell)
     rd, prd = _floats(rates_depth)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_sweep_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
+                                                     _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
+                                                     None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), int(bool(mapping)),
+                                                     enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if _mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
                                                   _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
@@ -128,7 +147,8 @@ def _seeds(seeds):
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
-               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False):
+               cells: bool = False, fidelity: bool = False, gene_fidelity: bool = False, neighbors: bool = False, labels=None, markers=None, coexpression: bool = False, mapping: bool = False,
+               pseudotime=None):
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
@@ -136,6 +156,12 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     rd, prd = _floats(rates_depth)
     sd, psd = _seeds(seeds)
     enc = lambda p: os.fspath(p).encode()  # noqa: E731
+    if _pseudotime_call(pseudotime, markers):
+        _lib.check(_lib.lib().fastf_sweep_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
+                                                     _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
+                                                     None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), int(bool(mapping)),
+                                                     enc(pseudotime)))
+        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
     if _mapping_call(mapping, markers):
         _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
                                                   _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
@@ -618,6 +644,92 @@ def label_classes_row(rate_cell, rate_depth, seed, label, a, n_labels, lab, conf
     buf = C.create_string_buffer(640)
     _lib.check(_lib.lib().fastf_label_classes_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), _b(label), int(a), len(lab),
                                                   int(n_labels), lab.ctypes.data, cf.ctypes.data, cp.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def read_pseudotime_table(path, columns=None):
+    """the rows of sweep_pseudotime.tsv as dicts of strings"""
+    return read_cells_table(path, PSEUDOTIME_COLUMNS if columns is None else columns)
+
+
+def read_point_pseudotime(path):
+    """the rows of a point's pseudotime.tsv.gz as dicts of strings"""
+    import gzip
+    lines = gzip.decompress(open(path, "rb").read()).decode().split("\n")
+    assert lines[0].split("\t") == list(POINT_PSEUDOTIME_COLUMNS) and lines[-1] == ""
+    return [dict(zip(POINT_PSEUDOTIME_COLUMNS, ln.split("\t"))) for ln in lines[1:-1]]
+
+
+def pseudotime_header(verb: str = "") -> str:
+    """the header of pseudotime.tsv.gz, or with verb "sweep" / "cap" / "level" of <verb>_pseudotime.tsv"""
+    return getattr(_lib.lib(), "fastf_%s_pseudotime_header" % verb if verb else "fastf_ptime_header")().decode()
+
+
+class Pseudotime:
+    """a pseudotime file loaded against a barcode list file (fastf_ptime_load): known, unknown — the lines whose barcode is / is not
+    listed; valued — the lines of a listed barcode that carry a value"""
+
+    def __init__(self, ptime_file, barcodes_file):
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().fastf_ptime_load(os.fspath(ptime_file).encode(), os.fspath(barcodes_file).encode(), C.byref(self._h)))
+        L = _lib.lib()
+        self.known, self.unknown, self.valued = L.fastf_ptime_known(self._h), L.fastf_ptime_unknown(self._h), L.fastf_ptime_valued(self._h)
+
+    def assign(self, barcodes):
+        """(t u32[n], m): the doubled midranks of a list of barcodes among those of them with a value (0 without), and their number"""
+        b = [x.encode() if isinstance(x, str) else x for x in barcodes]
+        arr = (C.c_char_p * max(len(b), 1))(*b)
+        t = np.zeros(max(len(b), 1), np.uint32)
+        m = C.c_uint32()
+        _lib.check(_lib.lib().fastf_ptime_assign(self._h, arr, len(b), t.ctypes.data, C.byref(m)))
+        return t[:len(b)], m.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().fastf_ptime_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+def ptime_medians(idx, cnt, t, k: int):
+    """(est, valued u32[n]) of neighbour lists idx (u32[n, k]), cnt (u32[n]) and ranks t (u32[n]): the host form of Engine.dev_ptime_medians"""
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    n = len(cnt)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.uint32)
+    assert len(idx) == n * k and len(t) == n
+    out = [np.full(max(n, 1), 0xDEADBEEF, np.uint32) for _ in range(2)]
+    _lib.check(_lib.lib().fastf_ptime_medians(idx.ctypes.data, cnt.ctypes.data, t.ctypes.data, n, k, out[0].ctypes.data, out[1].ctypes.data))
+    return out[0][:n], out[1][:n]
+
+
+def ptime_census(est, t):
+    """u64[7] (conc disc tie_e tie_t tie_both cells shift_sum) of est against t: the host form of Engine.dev_ptime_census, O(n^2)"""
+    est, t = (np.ascontiguousarray(x, dtype=np.uint32) for x in (est, t))
+    assert len(est) == len(t)
+    out = np.full(PTIME_OUT_WORDS, 0xDEADBEEF, np.uint64)
+    _lib.check(_lib.lib().fastf_ptime_census(est.ctypes.data, t.ctypes.data, len(t), out.ctypes.data))
+    return out
+
+
+def ptime_row(barcode, rank, est_full, valued_full, est_point, valued_point, est_map=None, valued_map=None) -> str:
+    """one row of pseudotime.tsv.gz (with its newline); est_map None: a run without --mapping"""
+    buf = C.create_string_buffer(512)
+    mapping = est_map is not None
+    _lib.check(_lib.lib().fastf_ptime_row(_b(barcode), int(rank), int(est_full), int(valued_full), int(est_point), int(valued_point),
+                                          int(est_map) if mapping else 0, int(valued_map) if mapping else 0, int(mapping), buf, len(buf)))
+    return buf.value.decode()
+
+
+def ptime_summary_row(rate_cell, rate_depth, seed, n_cells, cells_valued, census_full, census_point, census_map=None, list_value: int = 0,
+                      k: int = NEIGHBORS_K) -> str:
+    """one row of <verb>_pseudotime.tsv (with its newline); census_map None: a run without --mapping; list_value >= 1: that integer in the second column"""
+    c = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64) for x in (census_full, census_point, census_map)]
+    assert all(x is None or len(x) == PTIME_OUT_WORDS for x in c)
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.lib().fastf_ptime_summary_row(float(rate_cell), float(rate_depth), int(list_value), int(seed) % (1 << 32), int(n_cells), int(k), int(cells_valued),
+                                                  *[None if x is None else x.ctypes.data for x in c], buf, len(buf)))
     return buf.value.decode()
 
 

@@ -116,7 +116,7 @@ int fastf_filter_draw_passes(uint32_t r, float rate);
  * count >= 1; the medians run over all n_cells sampled cells.  Two values of one list that print the same at %.3f are refused.
  * Keys wider than 64 bits, UMIs beyond what a 64-bit key holds and FASTF_DEVICES naming several devices run point by point through
  * bam2db() (one line on stderr says so); the results are the same bytes.  On failure no sweep.tsv is left. --- */
-int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
+int cmd_sweep(int argc, const char **argv);     /* argv[0] == "sweep"; -b -a -f -o -c <list> -r <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] [--pseudotime FILE] */
 #define FASTF_SWEEP_SUMMARY_ONLY 1u             /* sweep.tsv alone: no rows leave the device, no point directories */
 #define FASTF_SWEEP_GENES        2u             /* --genes: the per-gene files below, beside everything else */
 #define FASTF_SWEEP_CELLS        8u             /* --cells: the per-cell files below, beside everything else (resident form only); bit 4 is not assigned */
@@ -180,7 +180,7 @@ int fastf_cells_summary_row(float rate_cell, float rate_depth, uint64_t reads_pe
  * (cells with h > N) and realised_depth (%.6f) appended.  Refused: N < 1, an empty list, a value twice, and jobs outside the
  * resident form (keys wider than 64 bits, UMIs beyond what a 64-bit key holds, FASTF_DEVICES naming several devices) — bam2db cannot
  * express a cap, so there is no point-by-point fallback.  On failure no cap.tsv is left. --- */
-int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
+int cmd_cap(int argc, const char **argv);       /* argv[0] == "cap"; -b -a -f -o -c <list> -n <list> [-s] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] [--pseudotime FILE] */
 #define FASTF_CAP_SUMMARY_ONLY 1u               /* cap.tsv alone */
 #define FASTF_CAP_GENES        2u               /* --genes: cap_genes.tsv, cap_gene_cells.tsv.gz and genes.tsv.gz per point, as sweep writes them */
 #define FASTF_CAP_CELLS        8u               /* --cells: cap_cells.tsv and cells.tsv.gz per point, as sweep writes them; bit 4 is not assigned */
@@ -219,7 +219,7 @@ float fastf_cap_realised(uint64_t sampled, uint64_t hits);
  * level_gene_reps.tsv.gz and the per-point files as cap writes its own, the one column renamed.  Refused: what cap refuses (M < 1, an
  * empty list, a value twice, more than 64 values, -u, and jobs outside the resident form: several devices, keys wider than 64 bits,
  * UMIs beyond what a 64-bit key holds — there is no point-by-point form).  Every table goes through .partial; on failure none is left. --- */
-int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] */
+int cmd_level(int argc, const char **argv);     /* argv[0] == "level"; -b -a -f -o -c <list> -m|--umis <list> [-s | --seeds | --reps] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE] [--markers N] [--mapping] [--pseudotime FILE] */
 #define FASTF_LEVEL_SUMMARY_ONLY 1u             /* level.tsv (and the other tables) alone: no point directories */
 #define FASTF_LEVEL_GENES        2u             /* --genes, as cap's */
 #define FASTF_LEVEL_CELLS        8u             /* --cells, as cap's; bit 4 is not assigned */
@@ -659,6 +659,85 @@ int fastf_cap_mapping(const char *bam, const char *out_dir, const char *barcodes
 int fastf_level_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                         const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
                         uint32_t markers, uint32_t mapping);
+
+/* --- --pseudotime FILE on sweep, cap and level (fastf_sweep_pseudotime, fastf_cap_pseudotime, fastf_level_pseudotime; `pseudotime=` in
+ * Python; the long option alone; no flag bit): does a trajectory survive at this depth.  The user brings one number per barcode from the
+ * full-depth analysis (a pseudotime, or any per-cell score); the neighbour sets of --neighbors estimate it back, at full depth and at
+ * the point, and the order of the cells along the estimate is compared with the order along the value: the continuous counterpart of
+ * --labels.  Everything is integer until a ratio is printed.
+ * The file: plain text, one `barcode<TAB>value` per line, read under the rules of the labels file (one loader cuts the lines of both):
+ * lines end in LF, one trailing CR is dropped, empty lines are skipped, the first line is skipped iff its first field is exactly
+ * `barcode`, a barcode is the string barcodes.tsv.gz prints.  A value is 1 to 63 bytes: `NA` (no value), or a number that strtod in the C
+ * locale consumes whole and that is finite.  Refused by name, with the line number, before the output directory is made: a file that
+ * does not exist or is gzip-compressed, a line without exactly two fields, a value that is empty or 64 bytes or longer, a value strtod
+ * does not consume whole, nan and inf (an overflow to inf too), a barcode named twice, and a file of which no line names a barcode of the
+ * barcode list.  A barcode that is not in the barcode list is counted (pseudotime_unknown in the stage line) and ignored; a listed
+ * barcode without a line has no value.
+ * Per (cell rate, seed) pair, with its n sampled cells in the order of barcodes.tsv.gz; X, Y, A, N_M(i) and k = FASTF_NEIGHBORS_K are
+ * those of --neighbors; m = the cells of the pair that have a value (cells_valued).
+ *   t[i] (u32)  = the doubled midrank of cell i among those m cells:
+ *                 2 * #{j valued : v_j < v_i} + #{j valued : v_j == v_i} + 1   (i counts itself in the second term): 2 .. 2m, ties share a
+ *                 value; 0 without a value.  Doubles are compared as doubles: -0 equals 0.  Made on the host (fastf_ptime_assign), once a pair.
+ * For M in {X, Y}, and Z with --mapping (M(i) of that option: a list over the full-depth cells of the same pair):
+ *   V_M(i)      = the multiset { t[j] : j in N_M(i), t[j] > 0 };  c_M(i) = |V_M(i)|
+ *   e_M(i)      = the LOWER median of V_M(i), its ceil(c / 2)-th smallest element; 0 when c_M(i) == 0.  Cells without a value of their own
+ *                 are estimated too.  Slots from cnt[i] on and indices of n and beyond are never used, as in fastf_label_votes.
+ * Census: S_M = { i : t[i] > 0, e_M(i) > 0 }.  Every pair i < j of S_M falls in exactly one of five u64 counts:
+ *   conc      (e_i - e_j)(t_i - t_j) > 0          disc      (e_i - e_j)(t_i - t_j) < 0
+ *   tie_e     e_i == e_j, t_i != t_j              tie_t     t_i == t_j, e_i != e_j              tie_both  both equal
+ * and cells_M = |S_M|, shift_sum_M = sum over S_M of |e_M(i) - t[i]| (u64).
+ * Printed, %.6f, NA on a zero denominator:
+ *   tau_M   = (double)(int64)(conc - disc) / sqrt((double)(conc + disc + tie_e) * (double)(conc + disc + tie_t))    (Kendall's tau-b)
+ *   shift_M = (double)shift_sum_M / ((double)(2 m) * (double)cells_M)                 (the mean displacement as a share of the rank range)
+ *   <point dir>/pseudotime.tsv.gz (not with --summary-only): a header and one row per barcode in the order of barcodes.tsv.gz:
+ *     barcode rank est_full valued_full est_point valued_point est_map valued_map      (rank = t; rank and est_* print NA for 0; the two
+ *     map columns are NA without --mapping)
+ *   <out_dir>/<verb>_pseudotime.tsv: a header and one row per point — in replicate runs per (cell rate, seed, list value), in the row
+ *     order of <verb>_labels.tsv — through .partial, with --summary-only too: the verb's two leading columns, then
+ *     seed n_cells k cells_valued   and per M in full, point, map:   cells_M conc_M disc_M tau_M shift_M      (the map columns NA without
+ *     --mapping)
+ * The option switches on what --labels alone switches on and writes none of the files of --neighbors unless that option is given too;
+ * every other output is the bytes it is without it.  Jobs outside the resident form (several devices, the wide-UMI layout) are refused
+ * as --neighbors refuses them, naming --pseudotime.  No _reps aggregate. --- */
+#define FASTF_PTIME_TILE 1024u               /* the tile edge of the device census: cells per tile (PT_TILE) */
+#define FASTF_PTIME_OUT_WORDS 7u             /* conc disc tie_e tie_t tie_both cells shift_sum */
+#define FASTF_PTIME_MAX_CELLS (65535u * FASTF_PTIME_TILE)      /* the device census: the pairs of tiles stay below 2^31 workgroups */
+typedef struct fastf_ptime fastf_ptime_t;
+/* the pseudotime file against the barcode list file; on failure *out is NULL and fastf_last_error() names the file and the line */
+int fastf_ptime_load(const char *ptime_file, const char *barcodes_file, fastf_ptime_t **out);
+void fastf_ptime_free(fastf_ptime_t *t);
+uint64_t fastf_ptime_known(const fastf_ptime_t *t);                          /* lines whose barcode is in the barcode list */
+uint64_t fastf_ptime_unknown(const fastf_ptime_t *t);                        /* lines whose barcode is not */
+uint64_t fastf_ptime_valued(const fastf_ptime_t *t);                         /* lines of a listed barcode that carry a value (not NA) */
+/* rank[i] = t[i] of barcodes[i] among the n barcodes given, *m (may be NULL) = those of them with a value */
+int fastf_ptime_assign(const fastf_ptime_t *t, char *const *barcodes, uint32_t n, uint32_t *rank, uint32_t *m);
+/* the host twins of fastf_dev_ptime_medians and fastf_dev_ptime_census: the same arguments on host arrays.  idx: k slots a cell (k from 1
+ * to 64), cnt[i] of them valid (more than k counts as k); est, valued: u32[n_cells].  The census is the definition, O(n_cells^2);
+ * out: FASTF_PTIME_OUT_WORDS u64 */
+int fastf_ptime_medians(const uint32_t *idx, const uint32_t *cnt, const uint32_t *t, uint32_t n_cells, uint32_t k, uint32_t *est, uint32_t *valued);
+int fastf_ptime_census(const uint32_t *est, const uint32_t *t, uint32_t n_cells, uint64_t *out);
+const char *fastf_ptime_header(void);              /* the header of pseudotime.tsv.gz */
+const char *fastf_sweep_pseudotime_header(void);   /* the headers of <verb>_pseudotime.tsv */
+const char *fastf_cap_pseudotime_header(void);
+const char *fastf_level_pseudotime_header(void);
+/* one row of pseudotime.tsv.gz (with its newline); mapping == 0: est_map and valued_map are not read and print NA */
+int fastf_ptime_row(const char *barcode, uint32_t rank, uint32_t est_full, uint32_t valued_full, uint32_t est_point, uint32_t valued_point,
+                    uint32_t est_map, uint32_t valued_map, int mapping, char *buf, size_t cap);
+/* one row of <verb>_pseudotime.tsv (with its newline); the second column as fastf_genes_summary_row prints it (list_value == 0:
+ * rate_depth); census_*: FASTF_PTIME_OUT_WORDS u64 each; census_map == NULL: a run without --mapping */
+int fastf_ptime_summary_row(float rate_cell, float rate_depth, uint64_t list_value, uint32_t seed, uint32_t n_cells, uint32_t k, uint32_t cells_valued,
+                            const uint64_t *census_full, const uint64_t *census_point, const uint64_t *census_map, char *buf, size_t cap);
+/* sweep, cap and level with --pseudotime: the arguments of the verb's _mapping call, then pseudotime_path.  pseudotime_path == NULL:
+ * exactly the _mapping call of the same arguments */
+int fastf_sweep_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                           const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                           uint32_t markers, uint32_t mapping, const char *pseudotime_path);
+int fastf_cap_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                         const uint64_t *caps, uint32_t n_n, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                         uint32_t markers, uint32_t mapping, const char *pseudotime_path);
+int fastf_level_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
+                           const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                           uint32_t markers, uint32_t mapping, const char *pseudotime_path);
 
 /* --- replicate seeds of sweep and cap (--seeds a,b,c | --reps N; fastf_sweep_reps, fastf_cap_reps): the grid at several seeds from
  * ONE decode.  A replicate run is any run through these, one seed included; fastf_sweep() and fastf_cap() are what they were.
@@ -1212,6 +1291,17 @@ int fastf_dev_coexpr_select(fastf_engine_t *e, const uint64_t *d_D, const uint64
  * `stream` */
 int fastf_dev_label_votes(fastf_engine_t *e, const uint32_t *d_idx, const uint32_t *d_cnt, const uint8_t *d_lab, uint32_t n_cells, uint32_t k,
                           uint32_t n_labels, uint8_t *d_pred, uint8_t *d_same, uint8_t *d_labelled, uint32_t *d_conf, void *stream);
+
+/* --pseudotime (section above), on device pointers (ptime_kernels.hpp).
+ * fastf_dev_ptime_medians (pt_median_kernel): d_idx and d_cnt as fastf_dev_neighbors or fastf_dev_mapping writes them, k from 1 to 64;
+ * d_t: u32[n_cells]; d_est, d_valued: u32[n_cells].  A cell owns a lane group of 16, 32 or 64 lanes, the smallest that holds k; every
+ * valid lane finds its position under the order (value, slot) by shuffles inside the group, and the lane at ceil(c / 2) - 1 writes.
+ * fastf_dev_ptime_census (pt_pairs_kernel): d_est, d_t -> d_out, FASTF_PTIME_OUT_WORDS u64, zeroed by the call.  One workgroup per pair
+ * of tiles (a <= b) of FASTF_PTIME_TILE cells, n_cells^2 / 2 comparisons, nothing of size n x n is stored; n_cells beyond
+ * FASTF_PTIME_MAX_CELLS is refused.  Both asynchronous on `stream` */
+int fastf_dev_ptime_medians(fastf_engine_t *e, const uint32_t *d_idx, const uint32_t *d_cnt, const uint32_t *d_t, uint32_t n_cells, uint32_t k,
+                            uint32_t *d_est, uint32_t *d_valued, void *stream);
+int fastf_dev_ptime_census(fastf_engine_t *e, const uint32_t *d_est, const uint32_t *d_t, uint32_t n_cells, uint64_t *d_out, void *stream);
 
 /* --markers (section above), one call on device pointers (marker_labels_kernel, marker_auc_kernel).  d_planes: what
  * fastf_dev_neighbor_planes filled for (n_cells, K) with `planes` planes; d_lab: u8[n_cells].  d_s2u, d_sum: u64[n_labels * K]; d_det:

@@ -73,6 +73,16 @@ int main(void)
                 span_t a[] = { SPAN(v, map, nf + 1, 0), SPAN(v, kf, n, map), SPAN(v, kp, n, map + 4 * n), SPAN(v, sh, n, map + 8 * n), SPAN(v, genes, top, map + 12 * n) };
                 check("nbr pinned", base, bytes, map + n * 12 + top * 4, a, 5, map, n, top); free(base); }
         }
+        {   const size_t pc = (n + 1) & ~(size_t)1, half = 64 + 8 * pc;      /* --pseudotime: t, then three halves of census, est, valued */
+            if (res_pt_cells(n) != pc) fail("pt", "pt_cells moved", NULL, n, 0, 0);
+            const size_t bytes = res_pt_layout(NULL, pc).bytes; ALLOC(bytes);
+            res_pt_v v = res_pt_layout(base, pc);
+            span_t a[] = { SPAN(v, t, pc, 0),
+                           SPAN(v, half[0].census, 8, 4 * pc), SPAN(v, half[0].est, pc, 4 * pc + 64), SPAN(v, half[0].valued, pc, 4 * pc + 64 + 4 * pc),
+                           SPAN(v, half[1].census, 8, 4 * pc + half), SPAN(v, half[1].est, pc, 4 * pc + half + 64), SPAN(v, half[1].valued, pc, 4 * pc + half + 64 + 4 * pc),
+                           SPAN(v, half[2].census, 8, 4 * pc + 2 * half), SPAN(v, half[2].est, pc, 4 * pc + 2 * half + 64), SPAN(v, half[2].valued, pc, 4 * pc + 2 * half + 64 + 4 * pc) };
+            if (v.half_bytes != half) fail("pt", "the bytes of a half moved", NULL, pc, 0, 0);
+            check("pt", base, bytes, 4 * pc + 3 * half, a, 10, pc, 0, 0); free(base); }
         for (size_t li = 0; li < sizeof LABELS / sizeof *LABELS; li++) {
             const size_t L = LABELS[li], lc = (n + 3) & ~(size_t)3, conf = L * (L + 1) * 4, half = 3 * lc + conf;
             if (res_lab_cells(n) != lc) fail("lab", "lab_cells moved", NULL, n, 0, 0);

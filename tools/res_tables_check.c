@@ -264,7 +264,7 @@ typedef struct { res_tsv_t tsv; res_genes_t G; res_cells_t C; res_cmp_t Fd; } ta
 static void tables_open(tables_t *tb, const res_verb_t *V, const char *out, const state_t *st, uint32_t markers)
 {
     memset(tb, 0, sizeof *tb);
-    CHECK(!fastf_res_genes_open(&tb->G, 1, V, out, 2, 0) && !fastf_res_cells_open(&tb->C, 1, V, out) && !fastf_res_cmp_open(&tb->Fd, V, out, ALL_FLAGS, st->labels, markers, 0));
+    CHECK(!fastf_res_genes_open(&tb->G, 1, V, out, 2, 0) && !fastf_res_cells_open(&tb->C, 1, V, out) && !fastf_res_cmp_open(&tb->Fd, V, out, ALL_FLAGS, st->labels, markers, 0, NULL));
 }
 static void tables_point(tables_t *tb, const state_t *st, const char *name, const char *dir, float rd, uint64_t lv, res_times_t *T)
 {
@@ -341,7 +341,7 @@ static int run_case(const char *tmp, int verb, uint32_t nc, uint32_t nf, uint32_
     /* a failed rename: the third, of <verb>_neighbors.tsv */
     {   char block[4400], inside[4500];
         memset(&tb, 0, sizeof tb);
-        CHECK(!fastf_res_cmp_open(&tb.Fd, &V, out, ALL_FLAGS, st.labels, markers, 0));
+        CHECK(!fastf_res_cmp_open(&tb.Fd, &V, out, ALL_FLAGS, st.labels, markers, 0, NULL));
         CHECK(!fastf_res_cmp_point(&tb.Fd, &st.S, NULL, rd[0], lv[0], &T));
         snprintf(block, sizeof block, "%s/%s", out, table_name(&V, TB_NEIGHBORS, ""));
         snprintf(inside, sizeof inside, "%s/keep", block);
@@ -362,7 +362,7 @@ static int run_case(const char *tmp, int verb, uint32_t nc, uint32_t nf, uint32_
     for (size_t s = 0; s < sizeof sub / sizeof *sub; s++) {
         char names[256] = "";
         for (int k = 0; k < 3; k++) if (sub[s].table[k] >= 0) { strcat(names, names[0] ? " " : ""); strcat(names, table_name(&V, sub[s].table[k], ".partial")); }
-        CHECK(!fastf_res_cmp_open(&tb.Fd, &V, out, sub[s].flags, sub[s].labels ? st.labels : NULL, sub[s].markers ? markers : 0, 0));
+        CHECK(!fastf_res_cmp_open(&tb.Fd, &V, out, sub[s].flags, sub[s].labels ? st.labels : NULL, sub[s].markers ? markers : 0, 0, NULL));
         CHECK(!strcmp(listing(out), names));
         CHECK(!fastf_res_cmp_point(&tb.Fd, &st.S, NULL, rd[1], lv[1], &T));
         CHECK(!fastf_res_cmp_close(&tb.Fd, 0) && !strcmp(listing(out), ""));
@@ -387,7 +387,7 @@ int main(int argc, char **argv)
         snprintf(g_case, sizeof g_case, "an open that fails");
         snprintf(out, sizeof out, "%s/out", argv[1]); snprintf(block, sizeof block, "%s/sweep_neighbors.tsv.partial", out);
         CHECK(!mkdir(out, 0777) && !mkdir(block, 0777));
-        CHECK(fastf_res_cmp_open(&Fd, &V, out, ALL_FLAGS, NULL, 0, 0) == 1 && strstr(fastf_last_error(), "sweep_neighbors.tsv.partial"));
+        CHECK(fastf_res_cmp_open(&Fd, &V, out, ALL_FLAGS, NULL, 0, 0, NULL) == 1 && strstr(fastf_last_error(), "sweep_neighbors.tsv.partial"));
         CHECK(!strcmp(listing(out), "sweep_neighbors.tsv.partial") && !Fd.on);
         CHECK(!rmdir(block) && !rmdir(out));
     }
