@@ -317,7 +317,13 @@ def lib():
     L.extract_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.extract_bam.restype = None
     fp = C.POINTER(C.c_float)
-    L.fastf_sweep.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, u32, u32]
+    # the six entry points of a grid verb: the verb's list (depth rates: float *, caps: u64 *) is all that differs between the verbs
+    for verb, lp in (("sweep", fp), ("cap", vp), ("level", vp)):
+        grid = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, lp, u32]
+        opts = grid + [vp, u32, u32, u32, C.c_char_p]          # seeds, n_seeds, flags, seed, labels_path
+        for suffix, args in (("", grid + [u32, u32]), ("_reps", grid + [vp, u32, u32]), ("_labels", opts), ("_markers", opts + [u32]),
+                             ("_mapping", opts + [u32, u32]), ("_pseudotime", opts + [u32, u32, C.c_char_p])):
+            getattr(L, "fastf_" + verb + suffix).argtypes = args
     L.fastf_sweep_parse_rates.argtypes = [C.c_char_p, C.c_int, fp, u32, C.POINTER(u32)]
     L.fastf_sweep_check_grid.argtypes = [fp, u32, fp, u32]
     L.fastf_sweep_point_dir.argtypes = [C.c_float, C.c_float, C.c_char_p, sz]
@@ -336,7 +342,6 @@ def lib():
     L.fastf_cells_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, vp, vp, vp, u32, vp, C.c_char_p, sz]
     L.fastf_sweep_cells_header.restype = C.c_char_p
     L.fastf_cap_cells_header.restype = C.c_char_p
-    L.fastf_cap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
     L.fastf_cap_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.fastf_cap_check_grid.argtypes = [fp, u32, vp, u32]
     L.fastf_cap_point_dir.argtypes = [C.c_float, u64, C.c_char_p, sz]
@@ -349,8 +354,6 @@ def lib():
     L.fastf_dev_cell_decisions.argtypes = [vp, u64, vp, u32, u64, u64, vp, vp, vp]
     L.fastf_parse_seeds.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.fastf_reps_seeds.argtypes = [u32, u64, vp, u32, C.POINTER(u32)]
-    L.fastf_sweep_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32]
-    L.fastf_cap_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32]
     L.fastf_reps_point_dir.argtypes = [C.c_char_p, u32, C.c_char_p, sz]
     for name in ("fastf_sweep_reps_header", "fastf_cap_reps_header", "fastf_sweep_genes_reps_header", "fastf_cap_genes_reps_header"):
         getattr(L, name).restype = C.c_char_p
@@ -359,8 +362,6 @@ def lib():
     L.fastf_gene_reps_add_host.argtypes = [vp, u32, vp, vp, vp]
     L.fastf_dev_gene_reps_add.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     L.fastf_dev_block_layout.argtypes = [vp, u64, C.POINTER(u64)]
-    L.fastf_level.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, u32, u32]
-    L.fastf_level_reps.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32]
     L.fastf_level_parse_caps.argtypes = [C.c_char_p, vp, u32, C.POINTER(u32)]
     L.fastf_level_check_grid.argtypes = [fp, u32, vp, u32]
     L.fastf_level_point_dir.argtypes = [C.c_float, u64, C.c_char_p, sz]
@@ -423,9 +424,6 @@ def lib():
     L.fastf_label_confusion_row.argtypes = [C.c_char_p, u32, vp, u32, C.c_char_p, sz]
     L.fastf_labels_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, sz]
     L.fastf_label_classes_row.argtypes = [C.c_float, C.c_float, u64, u32, C.c_char_p, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
-    L.fastf_sweep_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p]
-    L.fastf_cap_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
-    L.fastf_level_labels.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p]
     L.fastf_dev_label_votes.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
     for name in ("fastf_ptime_header", "fastf_sweep_pseudotime_header", "fastf_cap_pseudotime_header", "fastf_level_pseudotime_header"):
         getattr(L, name).restype = C.c_char_p
@@ -441,9 +439,6 @@ def lib():
     L.fastf_ptime_census.argtypes = [vp, vp, u32, vp]
     L.fastf_ptime_row.argtypes = [C.c_char_p, u32, u32, u32, u32, u32, u32, u32, C.c_int, C.c_char_p, sz]
     L.fastf_ptime_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, C.c_char_p, sz]
-    L.fastf_sweep_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
-    L.fastf_cap_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
-    L.fastf_level_pseudotime.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32, C.c_char_p]
     L.fastf_dev_ptime_medians.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp]
     L.fastf_dev_ptime_census.argtypes = [vp, vp, vp, u32, vp, vp]
     for name in ("fastf_markers_header", "fastf_sweep_markers_header", "fastf_cap_markers_header", "fastf_level_markers_header"):
@@ -453,9 +448,6 @@ def lib():
     L.fastf_marker_rank.argtypes = [vp, vp, vp, u32, u32, vp]
     L.fastf_markers_row.argtypes = [C.c_char_p, C.c_char_p, u32, u32, u32, u32, u64, u64, u32, u32, u32, u32, u64, C.c_char_p, sz]
     L.fastf_markers_summary_rows.argtypes = [C.c_float, C.c_float, u64, u32, C.POINTER(C.c_char_p), u32, u32, u32, vp, vp, vp, vp, vp, C.c_char_p, sz]
-    L.fastf_sweep_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32]
-    L.fastf_cap_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
-    L.fastf_level_markers.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32]
     L.fastf_dev_marker_auc.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     for name in ("fastf_mapping_header", "fastf_sweep_mapping_header", "fastf_cap_mapping_header", "fastf_level_mapping_header"):
         getattr(L, name).restype = C.c_char_p
@@ -464,9 +456,6 @@ def lib():
     L.fastf_mapping_summary_row.argtypes = [C.c_float, C.c_float, u64, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, sz]
     L.fastf_mapping_from_coo.argtypes = [C.POINTER(Coo), C.POINTER(Coo), u32, vp, u32, u32, vp, vp, vp, vp]
     L.fastf_dev_mapping.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
-    L.fastf_sweep_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, fp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
-    L.fastf_cap_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
-    L.fastf_level_mapping.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, fp, u32, vp, u32, vp, u32, u32, u32, C.c_char_p, u32, u32]
     for name in ("fastf_coexpr_header", "fastf_sweep_coexpr_header", "fastf_cap_coexpr_header", "fastf_level_coexpr_header"):
         getattr(L, name).restype = C.c_char_p
     L.fastf_coexpr_check_range.argtypes = [u32, u64]

@@ -50,32 +50,8 @@ def cap(bam, out, barcodes, features, rates_cell, caps, seed: int = 926, summary
     neighbors=True out/cap_neighbors.tsv (read_neighbors_table) and a neighbors.tsv.gz per point directory; labels=<path> (`--labels`)
     out/cap_labels.tsv (read_labels_table), out/cap_label_classes.tsv (read_label_classes_table) and labels.tsv.gz,
     label_confusion.tsv.gz per point directory"""
-    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
-    n = np.ascontiguousarray(caps, dtype=np.uint64)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _sweep._pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_cap_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
-                                                int(bool(mapping)), enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if _sweep._mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_cap_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                               n.ctypes.data, len(n), None, 0, _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                               seed % (1 << 32), enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    _lib.check(_lib.lib().fastf_cap(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                    n.ctypes.data, len(n), seed % (1 << 32), _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _sweep._grid_call("cap", bam, out, barcodes, features, rates_cell, _sweep._caps(caps), None, seed,
+                      _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 
@@ -85,37 +61,8 @@ def cap_reps(bam, out, barcodes, features, rates_cell, caps, seeds, summary_only
     """`fastF cap ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of out/cap.tsv
     per (cell rate, seed, cap), which are returned (read_table), and out/cap_reps.tsv (read_reps_table); genes=True leaves
     out/cap_genes.tsv, out/cap_genes_reps.tsv (read_genes_reps_table) and out/cap_gene_reps.tsv.gz"""
-    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
-    n = np.ascontiguousarray(caps, dtype=np.uint64)
-    sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _sweep._pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_cap_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
-                                                int(bool(mapping)), enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if _sweep._mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_cap_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_cap_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                                _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), _sweep._markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_cap_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                               n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                               _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "cap.tsv"))
-    _lib.check(_lib.lib().fastf_cap_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                         n.ctypes.data, len(n), sd.ctypes.data, len(sd),
-                                         _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _sweep._grid_call("cap", bam, out, barcodes, features, rates_cell, _sweep._caps(caps), seeds, 0,
+                      _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "cap.tsv"))
 
 

@@ -1,6 +1,7 @@
 /*
- * grid_run.c — the driver of `fastF sweep`, `fastF cap` and `fastF level` (resident.h: res_job_t, res_verb_t): the checks of an entry
- * point, the tables of the run, the (cell rate, seed) pairs on ONE res_rate_t, the body of every point, the close.  A verb hands in
+ * grid_run.c — the driver of `fastF sweep`, `fastF cap` and `fastF level` (resident.h: res_job_t, res_verb_t): the one way in of the
+ * entry points (fastf_res_grid_entry, at the end), their checks, the tables of the run, the (cell rate, seed) pairs on ONE res_rate_t, the
+ * body of every point, the close.  A verb hands in
  * its descriptor; what it does by itself — making the decision plane of a point — it does in the hooks.  A further comparison of a
  * point against full depth is a descriptor and a writer in res_tables.c and a device stage in fastf_res_point_compare (resident.c);
  * here it has only its option and its profile line.
@@ -15,10 +16,20 @@
 
 #define GRID_FLAGS (FASTF_SWEEP_SUMMARY_ONLY | FASTF_SWEEP_GENES | FASTF_SWEEP_CELLS | FASTF_SWEEP_FIDELITY | FASTF_SWEEP_GENE_FIDELITY | FASTF_SWEEP_NEIGHBORS | FASTF_SWEEP_COEXPRESSION)
 
-int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path)
+/* the first two checks of --markers N */
+static int check_markers(const char *verb, uint32_t markers, const char *labels_path)
 {
     if (markers < 1 || markers > FASTF_MARKERS_MAX) return fastf_res_err("%s: --markers: N = %u, from 1 to %u", verb, markers, FASTF_MARKERS_MAX);
     return labels_path ? 0 : fastf_res_err("%s: --markers needs --labels", verb);
+}
+
+/* seeds[] of a replicate run: 1 .. FASTF_MAX_SEEDS distinct values */
+static int check_seeds(const char *verb, const uint32_t *seeds, uint32_t n_seeds)
+{
+    if (!seeds || n_seeds < 1 || n_seeds > FASTF_MAX_SEEDS) return fastf_res_err("%s: a replicate run takes 1 to %u seeds", verb, FASTF_MAX_SEEDS);
+    for (uint32_t k = 0; k < n_seeds; k++)
+        for (uint32_t j = 0; j < k; j++) if (seeds[j] == seeds[k]) return fastf_res_err("%s: seed %u is listed twice", verb, seeds[k]);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -261,7 +272,7 @@ fail:
 int fastf_res_grid_run(const res_verb_t *V, const res_job_t *asked)
 {
     res_job_t job = *asked;
-    if (job.reps && fastf_check_seeds_(V->name, job.seeds, job.n_s)) return 1;
+    if (job.reps && check_seeds(V->name, job.seeds, job.n_s)) return 1;
     if (!job.bam || !job.barcodes || !job.features) return fastf_res_err("%s: null argument", V->name);
     if (!job.out_dir) job.out_dir = ".";
     fastf_labels_t *labels = NULL;                          /* the labels file is read and checked before anything is written */
@@ -277,4 +288,24 @@ int fastf_res_grid_run(const res_verb_t *V, const res_job_t *asked)
     const int rc = grid_run_(V, &job, labels, ptime);
     fastf_labels_free(labels); fastf_ptime_free(ptime);
     return rc;
+}
+
+/* ------------------------------------------------------------------ */
+/* the one way in of the eighteen entry points                         */
+/* ------------------------------------------------------------------ */
+/* The union of their arguments, `seed` by value.  A replicate run: n_seeds != 0, or ENTRY_REPS (fastf_<verb>_reps, whose n_seeds == 0 the
+ * driver's seed check then refuses); otherwise the plain run at `seed`.  mapping beyond 1 is refused first; N of --markers and its labels
+ * path are checked where N != 0, and with ENTRY_MARKERS (fastf_<verb>_markers) always */
+int fastf_res_grid_entry(const res_verb_t *V, unsigned how, const char *bam, const char *out_dir, const char *barcodes, const char *features,
+                         const float *rates_cell, uint32_t n_c, const float *rates_depth, const uint64_t *caps, uint32_t n_list,
+                         const uint32_t *seeds, uint32_t n_seeds, uint32_t seed, uint32_t flags,
+                         const char *labels_path, uint32_t markers, uint32_t mapping, const char *ptime_path)
+{
+    const int reps = (how & ENTRY_REPS) || n_seeds != 0;
+    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
+                            .rates_depth = rates_depth, .caps = caps, .n_list = n_list, .seeds = reps ? seeds : &seed, .n_s = reps ? n_seeds : 1, .reps = reps,
+                            .flags = flags, .labels_path = labels_path, .markers = markers, .mapping = mapping, .ptime_path = ptime_path };
+    if (mapping > 1) return fastf_res_err("%s: --mapping: %u, 0 or 1", V->name, mapping);
+    if (((how & ENTRY_MARKERS) || markers) && check_markers(V->name, markers, labels_path)) return 1;
+    return fastf_res_grid_run(V, &job);
 }

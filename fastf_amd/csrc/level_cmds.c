@@ -2,9 +2,10 @@
  * level_cmds.c — `fastF level`: every cell downsampled to at most M UMIs, exactly, over a grid of (cell rate, UMI cap) points from
  * ONE decode of the BAM.
  *
- *   cmd_level()    -b -a -f -o -c <list> -m <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells]; -d accepted
- *                  and ignored, -u refused
- *   fastf_level()  the same in process; fastf_level_reps(): with a list of seeds, as cap takes them
+ *   cmd_level()    the command the three verbs share (resident.c: fastf_res_cmd) with this verb's res_cmd_t: its list option -m <list>,
+ *                  which has no default, its -u message and its words of the help text
+ *   fastf_level()  the same in process, and _reps, _labels, _markers, _mapping, _pseudotime: each ONE forwarding statement to
+ *                  fastf_res_grid_entry (grid_run.c), as sweep's (sweep_cmds.c)
  * Per point <out>/c<rate_cell>_m<M>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz, thresholds.tsv.gz} and one row of <out>/level.tsv.
  *
  * The resident pipeline of sweep and cap (resident.c), and cap's coupling: hit i owns draw i and is kept iff draw[i] < T[cell].  The
@@ -200,139 +201,55 @@ static const res_verb_t level_verb = {
 int fastf_level(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const uint64_t *umi_caps, uint32_t n_m, uint32_t seed, uint32_t flags)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .caps = umi_caps, .n_list = n_m, .seeds = &seed, .n_s = 1, .flags = flags };
-    return fastf_res_grid_run(&level_verb, &job);
+    return fastf_res_grid_entry(&level_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, NULL, 0, seed, flags, NULL, 0, 0, NULL);
 }
 
+/* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
 int fastf_level_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .caps = umi_caps, .n_list = n_m, .seeds = seeds, .n_s = n_seeds, .reps = 1, .flags = flags };
-    return fastf_res_grid_run(&level_verb, &job);
+    return fastf_res_grid_entry(&level_verb, ENTRY_REPS, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, seeds, n_seeds, 0, flags, NULL, 0, 0, NULL);
 }
 
 /* n_seeds == 0: the one seed `seed`, no replicate run */
 int fastf_level_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                     const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
+                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .caps = umi_caps, .n_list = n_m, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path };
-    return fastf_res_grid_run(&level_verb, &job);
+    return fastf_res_grid_entry(&level_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, seeds, n_seeds, seed, flags, labels_path, 0, 0, NULL);
 }
 
-/* --markers N: the labels run with the marker tables beside it */
+/* --markers N: the labels run with the marker tables beside it; N and the labels path are checked always */
 int fastf_level_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers)
+                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .caps = umi_caps, .n_list = n_m, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers };
-    return fastf_res_check_markers("level", markers, labels_path) || fastf_res_grid_run(&level_verb, &job);
+    return fastf_res_grid_entry(&level_verb, ENTRY_MARKERS, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, seeds, n_seeds, seed, flags, labels_path, markers, 0, NULL);
 }
 
 /* --mapping: labels_path may be NULL and markers 0 */
 int fastf_level_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers, uint32_t mapping)
+                        const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers, uint32_t mapping)
 {
-    return fastf_level_pseudotime(bam, out_dir, barcodes, features, rates_cell, n_c, umi_caps, n_m, seeds, n_seeds, flags, seed, labels_path, markers, mapping, NULL);
+    return fastf_res_grid_entry(&level_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, seeds, n_seeds, seed, flags, labels_path, markers, mapping, NULL);
 }
 
 /* --pseudotime FILE, the most general call: labels_path and pseudotime_path may be NULL, markers and mapping 0 */
 int fastf_level_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers, uint32_t mapping, const char *pseudotime_path)
+                           const uint64_t *umi_caps, uint32_t n_m, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                           uint32_t markers, uint32_t mapping, const char *pseudotime_path)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .caps = umi_caps, .n_list = n_m, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers, .mapping = mapping, .ptime_path = pseudotime_path };
-    if (mapping > 1) return fastf_res_err("level: --mapping: %u, 0 or 1", mapping);
-    return (markers && fastf_res_check_markers("level", markers, labels_path)) || fastf_res_grid_run(&level_verb, &job);
+    return fastf_res_grid_entry(&level_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, NULL, umi_caps, n_m, seeds, n_seeds, seed, flags, labels_path, markers, mapping, pseudotime_path);
 }
 
-static void usage_level(FILE *f)
-{
-    fprintf(f,
-            "Usage: fastF level [options]\n\n"
-            "every cell downsampled to at most M UMIs, exactly: the deepest read-level subsample of each cell whose UMI count does not\n"
-            "exceed M, over a grid of cell rates and UMI caps from one decode of the bam file: per point <out>/c<cell>_m<M>/ with the three\n"
-            "files of bam2db and thresholds.tsv.gz, and <out>/level.tsv with one summary row per point.\n\n"
-            "    -h, --help            show this help message and exit\n"
-            "    -b, --bam=<str>       path to bam file\n"
-            "    -f, --feature=<str>   path to feature list file\n"
-            "    -a, --barcode=<str>   path to barcode list file\n"
-            "    -d, --dbname=<str>    name of database (accepted for compatibility, ignored)\n"
-            "    -c, --cell=<list>     rates of cell barcode, comma separated (default 1.0)\n"
-            "    -m, --umis=<list>     UMIs per cell at most, comma separated integers >= 1\n"
-            "    -o, --out=<str>       path to output directory (default .)\n"
-            "    -s, --seed=<int>      seed for random number generator (default 926)\n"
-            "        --summary-only    write level.tsv alone\n"
-            "        --genes           per-gene detection too: level_genes.tsv, level_gene_cells.tsv.gz and genes.tsv.gz per point\n"
-            "        --cells           per-cell reads, saturation and UMI copy numbers too: level_cells.tsv and cells.tsv.gz per point\n"
-            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
-            "                          level_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
-            "                          over ALL genes per cell (not log-normalised)\n"
-            "        --gene-fidelity   every point against the full-depth data of the same cells, per GENE: level_gene_fidelity.tsv and\n"
-            "                          gene_fidelity.tsv.gz per point, with the Pearson of the RAW counts over ALL sampled cells per gene,\n"
-            "                          the dispersion (variance / mean) at full depth and at the point, and the overlap of the 2000\n"
-            "                          most variable genes\n"
-            "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: level_neighbors.tsv and\n"
-            "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
-            "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps\n"
-            "        --coexpression    every point against the full-depth data of the same cells, BETWEEN the genes: level_coexpr.tsv and\n"
-            "                          coexpr.tsv.gz per point, with the share of a gene's 15 strongest co-expression partners at full depth\n"
-            "                          (Pearson of the RAW counts among the 2000 most variable genes, decided in exact integers) that it keeps\n"
-            "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): level_labels.tsv,\n"
-            "                          level_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
-            "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point\n"
-            "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
-            "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
-            "                          level_markers.tsv and markers.tsv.gz per point\n"
-            "        --mapping         every cell of a point looked up among ALL full-depth cells of the same sample (cosine of the RAW counts over\n"
-            "                          the 2000 most variable genes, decided in exact integers): level_mapping.tsv and mapping.tsv.gz per point, with\n"
-            "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
-            "                          full-depth neighbours and, with --labels, the label they vote for\n"
-            "        --pseudotime=<file>\n"
-            "                          one `barcode<TAB>value` per line (a pseudotime or any per-cell score of the full-depth analysis): level_pseudotime.tsv\n"
-            "                          and pseudotime.tsv.gz per point, with the value's rank estimated back per cell as the lower median over its 15\n"
-            "                          nearest neighbours, at full depth, at the point and, with --mapping, over the full-depth cells it maps among, and\n"
-            "                          Kendall's tau-b of the estimate against the value over all pairs of cells, counted exactly\n"
-            "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
-            "                          seed <out>/c<cell>_m<M>_s<seed>/, one level.tsv row each, and level_reps.tsv with mean, sd, min and\n"
-            "                          max of every metric per grid point (with --genes level_genes_reps.tsv and level_gene_reps.tsv.gz\n"
-            "                          in place of level_gene_cells.tsv.gz); not with -s or --reps\n"
-            "        --reps=<int>      the same at the seeds s, s + 1, .. s + N - 1 (s: -s; N from 1 to 64)\n");
-}
-
-#define LEVEL_MAX_POINTS 64
-int cmd_level(int argc, const char **argv)
-{
-    res_args_t A;
-    const int prc = fastf_res_parse_args(argc, argv, 'm', "umis", usage_level, "level does not write umi.tsv.gz (-u).", &A);
-    if (prc) return prc == 2 ? 0 : 1;
-    float rc[LEVEL_MAX_POINTS]; uint64_t caps[LEVEL_MAX_POINTS];
-    uint32_t n_c = 0, n_m = 0;
-    if (!A.list) { fprintf(stderr, "\x1b[31mError:\x1b[0m level needs -m <list>: the UMIs per cell at most\n"); return 1; }
-    if (fastf_sweep_parse_rates(A.cells, 1, rc, LEVEL_MAX_POINTS, &n_c) || fastf_level_parse_caps(A.list, caps, LEVEL_MAX_POINTS, &n_m) ||
-        fastf_level_check_grid(rc, n_c, caps, n_m)) {
-        fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error());
-        return 1;
-    }
-    if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = fastf_res_args_flags(&A);
-    if (A.pseudotime ? fastf_level_pseudotime(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, A.mapping, A.pseudotime) :
-        A.mapping ? fastf_level_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
-        A.markers ? fastf_level_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
-        A.labels ? fastf_level_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
-        A.n_seeds ? fastf_level_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seeds, A.n_seeds, flags)
-                  : fastf_level(A.bam, A.out, A.bar, A.feat, rc, n_c, caps, n_m, A.seed, flags)) {
-        fprintf(stderr, "\x1b[31mError:\x1b[0m level failed: %s\n", fastf_last_error());
-        return 1;
-    }
-    fastf_res_print_generated("level", &A);
-    return 0;
-}
+/* the command: what it does not share with the other two (resident.h: res_cmd_t) */
+static const res_cmd_t level_cmd = {
+    .list_short = 'm', .list_long = "umis", .parse_caps = fastf_level_parse_caps,
+    .u_message = "level does not write umi.tsv.gz (-u).", .needs_list = "level needs -m <list>: the UMIs per cell at most",
+    .help_intro = "every cell downsampled to at most M UMIs, exactly: the deepest read-level subsample of each cell whose UMI count does not\n"
+                  "exceed M, over a grid of cell rates and UMI caps from one decode of the bam file: per point <out>/c<cell>_m<M>/ with the three\n"
+                  "files of bam2db and thresholds.tsv.gz, and <out>/level.tsv with one summary row per point.",
+    .help_list = "-m, --umis=<list>     UMIs per cell at most, comma separated integers >= 1",
+    .help_point = "m<M>", .help_resident = "",
+};
+int cmd_level(int argc, const char **argv) { return fastf_res_cmd(&level_verb, &level_cmd, argc, argv); }

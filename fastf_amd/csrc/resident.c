@@ -1103,12 +1103,67 @@ uint32_t fastf_res_lists_max_cells(const res_lists_t *l)
 /* ------------------------------------------------------------------ */
 /* the command line                                                    */
 /* ------------------------------------------------------------------ */
-struct ropt { char s; const char *l; int has_arg; };
-int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
-                         res_args_t *out)
+/* the help text of the three verbs: %1$s the verb, %2$s D->help_resident, %3$s D->help_point, %4$s D->help_intro, %5$s D->help_list */
+static void fastf_res_usage(const char *verb, const res_cmd_t *D, FILE *f)
 {
+    fprintf(f,
+            "Usage: fastF %1$s [options]\n\n"
+            "%4$s\n\n"
+            "    -h, --help            show this help message and exit\n"
+            "    -b, --bam=<str>       path to bam file\n"
+            "    -f, --feature=<str>   path to feature list file\n"
+            "    -a, --barcode=<str>   path to barcode list file\n"
+            "    -d, --dbname=<str>    name of database (accepted for compatibility, ignored)\n"
+            "    -c, --cell=<list>     rates of cell barcode, comma separated (default 1.0)\n"
+            "    %5$s\n"
+            "    -o, --out=<str>       path to output directory (default .)\n"
+            "    -s, --seed=<int>      seed for random number generator (default 926)\n"
+            "        --summary-only    write %1$s.tsv alone\n"
+            "        --genes           per-gene detection too: %1$s_genes.tsv, %1$s_gene_cells.tsv.gz and genes.tsv.gz per point\n"
+            "        --cells           per-cell reads, saturation and UMI copy numbers too: %1$s_cells.tsv and cells.tsv.gz per point\n"
+            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
+            "                          %1$s_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
+            "                          over ALL genes per cell (not log-normalised)%2$s\n"
+            "        --gene-fidelity   every point against the full-depth data of the same cells, per GENE: %1$s_gene_fidelity.tsv and\n"
+            "                          gene_fidelity.tsv.gz per point, with the Pearson of the RAW counts over ALL sampled cells per gene,\n"
+            "                          the dispersion (variance / mean) at full depth and at the point, and the overlap of the 2000\n"
+            "                          most variable genes%2$s\n"
+            "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: %1$s_neighbors.tsv and\n"
+            "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
+            "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps%2$s\n"
+            "        --coexpression    every point against the full-depth data of the same cells, BETWEEN the genes: %1$s_coexpr.tsv and\n"
+            "                          coexpr.tsv.gz per point, with the share of a gene's 15 strongest co-expression partners at full depth\n"
+            "                          (Pearson of the RAW counts among the 2000 most variable genes, decided in exact integers) that it keeps%2$s\n"
+            "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): %1$s_labels.tsv,\n"
+            "                          %1$s_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
+            "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point%2$s\n"
+            "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
+            "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
+            "                          %1$s_markers.tsv and markers.tsv.gz per point%2$s\n"
+            "        --mapping         every cell of a point looked up among ALL full-depth cells of the same sample (cosine of the RAW counts over\n"
+            "                          the 2000 most variable genes, decided in exact integers): %1$s_mapping.tsv and mapping.tsv.gz per point, with\n"
+            "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
+            "                          full-depth neighbours and, with --labels, the label they vote for%2$s\n"
+            "        --pseudotime=<file>\n"
+            "                          one `barcode<TAB>value` per line (a pseudotime or any per-cell score of the full-depth analysis): %1$s_pseudotime.tsv\n"
+            "                          and pseudotime.tsv.gz per point, with the value's rank estimated back per cell as the lower median over its 15\n"
+            "                          nearest neighbours, at full depth, at the point and, with --mapping, over the full-depth cells it maps among, and\n"
+            "                          Kendall's tau-b of the estimate against the value over all pairs of cells, counted exactly%2$s\n"
+            "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
+            "                          seed <out>/c<cell>_%3$s_s<seed>/, one %1$s.tsv row each, and %1$s_reps.tsv with mean, sd, min and max\n"
+            "                          of every metric per grid point (with --genes %1$s_genes_reps.tsv and %1$s_gene_reps.tsv.gz in\n"
+            "                          place of %1$s_gene_cells.tsv.gz); not with -s or --reps\n"
+            "        --reps=<int>      the same at the seeds s, s + 1, .. s + N - 1 (s: -s; N from 1 to 64)\n",
+            verb, D->help_resident, D->help_point, D->help_intro, D->help_list);
+}
+
+/* returns 0, 1 after an error message, 2 after the help text; -u prints D->u_message and fails */
+struct ropt { char s; const char *l; int has_arg; };
+static int fastf_res_parse_args(int argc, const char **argv, const char *verb, const res_cmd_t *D, res_args_t *out)
+{
+    const char list_short = D->list_short;
     const struct ropt opts[] = {
-        {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, list_long, 1},
+        {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, D->list_long, 1},
         {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'P', "mapping", 0}, {'T', "pseudotime", 1}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
@@ -1130,7 +1185,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
             for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXPTLMER", k->s)) { o = k; break; }
             if (o && o->has_arg && a[2]) val = a + 2;
         }
-        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage(stderr); return 1; }
+        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); fastf_res_usage(verb, D, stderr); return 1; }
         char oname[32];
         if (a[1] == '-') snprintf(oname, sizeof oname, "--%s", o->l); else snprintf(oname, sizeof oname, "-%c", o->s);
         if (o->has_arg && !val) {
@@ -1140,7 +1195,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
         char *end = NULL;
         if (o->s == list_short) { out->list = val; continue; }
         switch (o->s) {
-        case 'h': usage(stdout); return 2;
+        case 'h': fastf_res_usage(verb, D, stdout); return 2;
         case 'b': out->bam = val; break;
         case 'f': out->feat = val; break;
         case 'a': out->bar = val; break;
@@ -1151,7 +1206,7 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
                   if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); return 1; }
                   if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); return 1; }
                   break;
-        case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", u_message); return 1;
+        case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", D->u_message); return 1;
         case 'S': out->summary_only = 1; break;
         case 'G': out->genes = 1; break;
         case 'C': out->per_cell = 1; break;
@@ -1194,8 +1249,8 @@ int fastf_res_parse_args(int argc, const char **argv, char list_short, const cha
     }
     return 0;
 }
-/* (after the verb has parsed its lists: the order of the messages of cmd_sweep) */
-int fastf_res_check_inputs(const res_args_t *a)
+/* the three input files exist (after the lists are parsed: the order of the messages of the commands) */
+static int fastf_res_check_inputs(const res_args_t *a)
 {
     if (!a->bam || access(a->bam, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m bam file: %s does not exist.\n", a->bam ? a->bam : "(null)"); return 1; }
     if (!a->feat || access(a->feat, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m feature file: %s does not exist.\n", a->feat ? a->feat : "(null)"); return 1; }
@@ -1209,13 +1264,15 @@ _Static_assert(FASTF_CAP_SUMMARY_ONLY == FASTF_SWEEP_SUMMARY_ONLY && FASTF_LEVEL
                FASTF_LEVEL_GENE_FIDELITY == FASTF_SWEEP_GENE_FIDELITY && FASTF_CAP_NEIGHBORS == FASTF_SWEEP_NEIGHBORS && FASTF_LEVEL_NEIGHBORS == FASTF_SWEEP_NEIGHBORS &&
                FASTF_CAP_COEXPRESSION == FASTF_SWEEP_COEXPRESSION && FASTF_LEVEL_COEXPRESSION == FASTF_SWEEP_COEXPRESSION,
                "the three verbs share one flag word");
-uint32_t fastf_res_args_flags(const res_args_t *a)
+/* the flag word of the options (the bits of FASTF_SWEEP_*, which FASTF_CAP_* and FASTF_LEVEL_* repeat) */
+static uint32_t fastf_res_args_flags(const res_args_t *a)
 {
     return (a->summary_only ? FASTF_SWEEP_SUMMARY_ONLY : 0) | (a->genes ? FASTF_SWEEP_GENES : 0) | (a->per_cell ? FASTF_SWEEP_CELLS : 0) | (a->fidelity ? FASTF_SWEEP_FIDELITY : 0) |
            (a->gene_fidelity ? FASTF_SWEEP_GENE_FIDELITY : 0) | (a->neighbors ? FASTF_SWEEP_NEIGHBORS : 0) | (a->coexpression ? FASTF_SWEEP_COEXPRESSION : 0);
 }
 
-void fastf_res_print_generated(const char *verb, const res_args_t *a)
+/* the "... is generated." lines of a run that succeeded */
+static void fastf_res_print_generated(const char *verb, const res_args_t *a)
 {
     if (a->genes && a->n_seeds) printf("%s_genes.tsv, %s_genes_reps.tsv and %s_gene_reps.tsv.gz are generated.\n", verb, verb, verb);
     else if (a->genes) printf("%s_genes.tsv and %s_gene_cells.tsv.gz are generated.\n", verb, verb);
@@ -1230,4 +1287,32 @@ void fastf_res_print_generated(const char *verb, const res_args_t *a)
     if (a->pseudotime) printf("%s_pseudotime.tsv is generated.\n", verb);
     if (a->n_seeds) printf("%s_reps.tsv is generated.\n", verb);
     printf("%s.tsv is generated.\n", verb);
+}
+
+/* the command of a verb.  The ONE call below is the most general of a verb's six: the parser hands on markers only from 1 to
+ * FASTF_MARKERS_MAX and with labels, and mapping only as 0 or 1, so each narrower call it could name does the same */
+#define RES_MAX_POINTS 64
+int fastf_res_cmd(const res_verb_t *V, const res_cmd_t *D, int argc, const char **argv)
+{
+    res_args_t A;
+    const int prc = fastf_res_parse_args(argc, argv, V->name, D, &A);
+    if (prc) return prc == 2 ? 0 : 1;
+    const char *list = A.list ? A.list : D->list_default;
+    float rc[RES_MAX_POINTS], rd[RES_MAX_POINTS]; uint64_t caps[RES_MAX_POINTS];
+    uint32_t n_c = 0, n = 0;
+    if (!list) { fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", D->needs_list); return 1; }
+    if (fastf_sweep_parse_rates(A.cells, 1, rc, RES_MAX_POINTS, &n_c) ||
+        (D->parse_caps ? D->parse_caps(list, caps, RES_MAX_POINTS, &n) : fastf_sweep_parse_rates(list, 0, rd, RES_MAX_POINTS, &n)) ||
+        (V->check_caps ? V->check_caps(rc, n_c, caps, n) : fastf_sweep_check_grid(rc, n_c, rd, n))) {
+        fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error());
+        return 1;
+    }
+    if (fastf_res_check_inputs(&A)) return 1;
+    if (fastf_res_grid_entry(V, 0, A.bam, A.out, A.bar, A.feat, rc, n_c, D->parse_caps ? NULL : rd, D->parse_caps ? caps : NULL, n, A.seeds, A.n_seeds, A.seed,
+                             fastf_res_args_flags(&A), A.labels, A.markers, (uint32_t)A.mapping, A.pseudotime)) {
+        fprintf(stderr, "\x1b[31mError:\x1b[0m %s failed: %s\n", V->name, fastf_last_error());
+        return 1;
+    }
+    fastf_res_print_generated(V->name, &A);
+    return 0;
 }

@@ -3,8 +3,9 @@
  * decision plane, sort, reduce, the per-cell summary and — when the matrices are wanted — the rows gathered into pinned memory
  * for the writers of bam2db.  What differs between the verbs is how a point's decision plane is made: each verb describes itself in
  * ONE res_verb_t (its name, index, summary header, wording and the hooks that make the planes), and ONE driver (grid_run.c:
- * fastf_res_grid_run) runs the checks, the tables, the (cell rate, seed) pairs and the body of every point for all three.
- * The files: resident.c has the device side, the lists, the replicate accumulators and the command line; res_tables.c every table and
+ * fastf_res_grid_run) runs the checks, the tables, the (cell rate, seed) pairs and the body of every point for all three.  The way
+ * into it is ONE too: every exported entry point forwards to fastf_res_grid_entry, and the three commands are fastf_res_cmd.
+ * The files: resident.c has the device side, the lists, the replicate accumulators and the command; res_tables.c every table and
  * point file of a run — the comparisons against full depth below are ONE descriptor each there (res_cmp_t); grid_rows.c the host
  * analysis, the rows and the headers of the per-verb tables, defined once (fastf_res_table_header).  The last two touch no device.
  * --cells adds a stage of its own behind a point (fastf_res_point_cells): the point's keys sorted fully, K3u's rows, their per-cell
@@ -313,19 +314,30 @@ void fastf_res_reps_unlink_tables(const char *out_dir, const char *verb) FASTF_H
 /* the most cells any pair of the lists samples */
 uint32_t fastf_res_lists_max_cells(const res_lists_t *l) FASTF_HIDDEN;
 
-/* the command line the three verbs share: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity --gene-fidelity --neighbors --coexpression --mapping --labels --markers --pseudotime --seeds --reps and ONE list option of the verb's own
- * (list_short / list_long: -r/--depth, -n/--reads, -m/--umis).  Returns 0, 1 after an error message, 2 after the help text (usage(stdout)); -u prints
- * u_message and fails.  fastf_res_check_inputs: the three input files exist (called once the verb has parsed its lists).
- * n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given.
- * fastf_res_args_flags: the flag word of the options (the bits of FASTF_SWEEP_*, which FASTF_CAP_* and FASTF_LEVEL_* repeat);
- * fastf_res_print_generated: the "... is generated." lines of a run that succeeded */
+/* ---- the command (resident.c) ----
+ * ONE command line, ONE body and ONE help text for the three verbs: -h -b -f -a -d -c -o -s -u --summary-only --genes --cells --fidelity
+ * --gene-fidelity --neighbors --coexpression --mapping --labels --markers --pseudotime --seeds --reps and ONE list option of the verb's own.
+ * What a verb does not share is its res_cmd_t, ONE static const instance in its file:
+ *   list_short, list_long   its list option: -r/--depth, -n/--reads, -m/--umis
+ *   parse_caps              the parser of a caps list; NULL: the list holds depth rates (fastf_sweep_parse_rates)
+ *   u_message               what -u is refused with
+ *   needs_list              what a command line without the list is refused with; NULL: list_default stands in for it
+ *   help_*                  the help text's intro, the line of the list option, the list's part of a point directory's name, and what
+ *                           follows an option that a verb with a point-by-point form has in its resident form only ("" without one)
+ * fastf_res_cmd: the options, the missing list, the cell rates, the list and the grid (the verb's check_caps, or fastf_sweep_check_grid),
+ * the three input files, the run through fastf_res_grid_entry ("<verb> failed: ..."), the "... is generated." lines.  An option is
+ * added in the table and the switch of fastf_res_parse_args, in res_args_t, in the help template (fastf_res_usage) and, where it is
+ * no flag bit, in the call of fastf_res_cmd; fastf_res_print_generated names its table.
+ * res_args_t: n_seeds >= 1: a replicate run over seeds[] (--seeds as listed; --reps N: seed, seed + 1, ..); 0: neither option was given */
+typedef struct {
+    char list_short; const char *list_long, *list_default;
+    int (*parse_caps)(const char *text, uint64_t *out, uint32_t cap, uint32_t *n_out);
+    const char *u_message, *needs_list;
+    const char *help_intro, *help_list, *help_point, *help_resident;
+} res_cmd_t;
 typedef struct { const char *bam, *feat, *bar, *out, *cells, *list; unsigned int seed; int summary_only, genes, per_cell, fidelity, gene_fidelity, neighbors, coexpression, mapping; const char *labels, *pseudotime; uint32_t markers;   /* markers: N of --markers, 0 without */
                  uint32_t seeds[FASTF_MAX_SEEDS], n_seeds; } res_args_t;   /* cells: the -c list; per_cell: --cells */
-int fastf_res_parse_args(int argc, const char **argv, char list_short, const char *list_long, void (*usage)(FILE *), const char *u_message,
-                         res_args_t *a) FASTF_HIDDEN;
-int fastf_res_check_inputs(const res_args_t *a) FASTF_HIDDEN;
-uint32_t fastf_res_args_flags(const res_args_t *a) FASTF_HIDDEN;
-void fastf_res_print_generated(const char *verb, const res_args_t *a) FASTF_HIDDEN;
+int fastf_res_cmd(const res_verb_t *V, const res_cmd_t *D, int argc, const char **argv) FASTF_HIDDEN;
 
 /* ---- the grid driver (grid_run.c) ----
  * res_job_t: what an entry point of a verb was asked for.  The verb's list is rates_depth (sweep) or caps (cap, level), the other NULL —
@@ -380,8 +392,17 @@ struct res_verb {
 /* the run of an entry point: the seeds of a replicate run, null arguments, with labels_path the bam file and the labels (before anything
  * is written), the grid, the flags, the bam file, the devices, the output directory, the tables, the pairs, the close */
 int fastf_res_grid_run(const res_verb_t *V, const res_job_t *job) FASTF_HIDDEN;
-/* the first two checks of a fastf_*_markers entry point */
-int fastf_res_check_markers(const char *verb, uint32_t markers, const char *labels_path) FASTF_HIDDEN;
+/* the ONE way into it: each of the six exported calls of a verb (fastf_<verb>, _reps, _labels, _markers, _mapping, _pseudotime) and its
+ * command forward here with the union of their arguments — what a call does not take is NULL or 0, the verb's list is ONE of
+ * rates_depth / caps.  It fills the res_job_t — the ONE place a new option of a run is carried from an argument into the job — and
+ * checks what the entry points check before the driver: mapping beyond 1 first, then N of --markers and its labels path where N != 0.
+ * how: ENTRY_REPS — fastf_<verb>_reps: a replicate run whatever n_seeds is (0 is then refused by the driver's seed check); otherwise
+ * n_seeds == 0 is the plain run at `seed`.  ENTRY_MARKERS — fastf_<verb>_markers: N and the labels path are checked with N == 0 too */
+enum { ENTRY_REPS = 1, ENTRY_MARKERS = 2 };
+int fastf_res_grid_entry(const res_verb_t *V, unsigned how, const char *bam, const char *out_dir, const char *barcodes, const char *features,
+                         const float *rates_cell, uint32_t n_c, const float *rates_depth, const uint64_t *caps, uint32_t n_list,
+                         const uint32_t *seeds, uint32_t n_seeds, uint32_t seed, uint32_t flags,
+                         const char *labels_path, uint32_t markers, uint32_t mapping, const char *ptime_path) FASTF_HIDDEN;
 
 /* grid_rows.c: the columns of a summary row from `seed` on (no newline); metrics != NULL: the FASTF_REPS_METRICS numbers a replicate
  * table takes from the row (sampled_reads, sampled_valid_reads, nnz, umis, saturation, the two medians) as the row printed them */
@@ -396,8 +417,5 @@ int fastf_sweep_row_(float rate_cell, float rate_depth, uint32_t seed, const uin
 int fastf_cap_row_(float rate_cell, uint64_t list_value, uint32_t seed, const uint64_t counters[3], uint64_t nnz, uint64_t umis,
                    const uint64_t *umis_per_cell, const uint32_t *genes_per_cell, uint32_t n_cells, uint64_t hits, uint32_t cells_capped,
                    char *buf, size_t cap, double *metrics) FASTF_HIDDEN;
-
-/* sweep_cmds.c: the seeds of a _reps call — 1 .. FASTF_MAX_SEEDS distinct values */
-int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds) FASTF_HIDDEN;
 
 #endif

@@ -1,9 +1,10 @@
 /*
  * sweep_cmds.c — `fastF sweep`: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM.
  *
- *   cmd_sweep()    -b -a -f -o -c <list> -r <list> [-s seed | --seeds <list> | --reps N] [--summary-only] [--genes] [--cells] [--fidelity] [--gene-fidelity] [--neighbors] [--coexpression] [--labels FILE]; -d accepted
- *                  and ignored, -u refused
- *   fastf_sweep()  the same in process; fastf_sweep_reps(): with a list of seeds
+ *   cmd_sweep()    the command the three verbs share (resident.c: fastf_res_cmd) with this verb's res_cmd_t: its list option -r <list>,
+ *                  default 1, its -u message and its words of the help text
+ *   fastf_sweep()  the same in process, and _reps, _labels, _markers, _mapping, _pseudotime: each ONE forwarding statement to
+ *                  fastf_res_grid_entry (grid_run.c), which fills the job and runs the driver on this verb's res_verb_t
  * Per point <out>/c<rate_cell>_r<rate_depth>/{matrix.mtx.gz, barcodes.tsv.gz, features.tsv.gz} — the bytes `fastF bam2db`
  * writes for that point — and one row of <out>/sweep.tsv.
  *
@@ -284,149 +285,54 @@ static const res_verb_t sweep_verb = {
 int fastf_sweep(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                 const float *rates_depth, uint32_t n_r, uint32_t seed, uint32_t flags)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .rates_depth = rates_depth, .n_list = n_r, .seeds = &seed, .n_s = 1, .flags = flags };
-    return fastf_res_grid_run(&sweep_verb, &job);
+    return fastf_res_grid_entry(&sweep_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, NULL, 0, seed, flags, NULL, 0, 0, NULL);
 }
 
 /* seeds[]: 1 .. FASTF_MAX_SEEDS distinct values */
-int fastf_check_seeds_(const char *verb, const uint32_t *seeds, uint32_t n_seeds)
-{
-    if (!seeds || n_seeds < 1 || n_seeds > FASTF_MAX_SEEDS) return fastf_res_err("%s: a replicate run takes 1 to %u seeds", verb, FASTF_MAX_SEEDS);
-    for (uint32_t k = 0; k < n_seeds; k++)
-        for (uint32_t j = 0; j < k; j++) if (seeds[j] == seeds[k]) return fastf_res_err("%s: seed %u is listed twice", verb, seeds[k]);
-    return 0;
-}
-
 int fastf_sweep_reps(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                      const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .rates_depth = rates_depth, .n_list = n_r, .seeds = seeds, .n_s = n_seeds, .reps = 1, .flags = flags };
-    return fastf_res_grid_run(&sweep_verb, &job);
+    return fastf_res_grid_entry(&sweep_verb, ENTRY_REPS, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, seeds, n_seeds, 0, flags, NULL, 0, 0, NULL);
 }
 
 /* n_seeds == 0: the one seed `seed`, no replicate run */
 int fastf_sweep_labels(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path };
-    return fastf_res_grid_run(&sweep_verb, &job);
+    return fastf_res_grid_entry(&sweep_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, seeds, n_seeds, seed, flags, labels_path, 0, 0, NULL);
 }
 
-/* --markers N: the labels run with the marker tables beside it */
+/* --markers N: the labels run with the marker tables beside it; N and the labels path are checked always */
 int fastf_sweep_markers(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers)
+                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers };
-    return fastf_res_check_markers("sweep", markers, labels_path) || fastf_res_grid_run(&sweep_verb, &job);
+    return fastf_res_grid_entry(&sweep_verb, ENTRY_MARKERS, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, seeds, n_seeds, seed, flags, labels_path, markers, 0, NULL);
 }
 
 /* --mapping: labels_path may be NULL and markers 0 */
 int fastf_sweep_mapping(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers, uint32_t mapping)
+                        const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                        uint32_t markers, uint32_t mapping)
 {
-    return fastf_sweep_pseudotime(bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, n_r, seeds, n_seeds, flags, seed, labels_path, markers, mapping, NULL);
+    return fastf_res_grid_entry(&sweep_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, seeds, n_seeds, seed, flags, labels_path, markers, mapping, NULL);
 }
 
 /* --pseudotime FILE, the most general call: labels_path and pseudotime_path may be NULL, markers and mapping 0 */
 int fastf_sweep_pseudotime(const char *bam, const char *out_dir, const char *barcodes, const char *features, const float *rates_cell, uint32_t n_c,
-                       const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
-                       uint32_t markers, uint32_t mapping, const char *pseudotime_path)
+                           const float *rates_depth, uint32_t n_r, const uint32_t *seeds, uint32_t n_seeds, uint32_t flags, uint32_t seed, const char *labels_path,
+                           uint32_t markers, uint32_t mapping, const char *pseudotime_path)
 {
-    const res_job_t job = { .bam = bam, .out_dir = out_dir, .barcodes = barcodes, .features = features, .rates_cell = rates_cell, .n_c = n_c,
-                            .rates_depth = rates_depth, .n_list = n_r, .seeds = n_seeds ? seeds : &seed, .n_s = n_seeds ? n_seeds : 1, .reps = n_seeds != 0, .flags = flags,
-                            .labels_path = labels_path, .markers = markers, .mapping = mapping, .ptime_path = pseudotime_path };
-    if (mapping > 1) return fastf_res_err("sweep: --mapping: %u, 0 or 1", mapping);
-    return (markers && fastf_res_check_markers("sweep", markers, labels_path)) || fastf_res_grid_run(&sweep_verb, &job);
+    return fastf_res_grid_entry(&sweep_verb, 0, bam, out_dir, barcodes, features, rates_cell, n_c, rates_depth, NULL, n_r, seeds, n_seeds, seed, flags, labels_path, markers, mapping, pseudotime_path);
 }
 
-static void usage_sweep(FILE *f)
-{
-    fprintf(f,
-            "Usage: fastF sweep [options]\n\n"
-            "bam2db over a grid of cell and depth rates from one decode of the bam file: per point <out>/c<cell>_r<depth>/ with the\n"
-            "three files of bam2db, and <out>/sweep.tsv with one summary row per point.\n\n"
-            "    -h, --help            show this help message and exit\n"
-            "    -b, --bam=<str>       path to bam file\n"
-            "    -f, --feature=<str>   path to feature list file\n"
-            "    -a, --barcode=<str>   path to barcode list file\n"
-            "    -d, --dbname=<str>    name of database (accepted for compatibility, ignored)\n"
-            "    -c, --cell=<list>     rates of cell barcode, comma separated (default 1.0)\n"
-            "    -r, --depth=<list>    rates of depth, comma separated (default 1.0)\n"
-            "    -o, --out=<str>       path to output directory (default .)\n"
-            "    -s, --seed=<int>      seed for random number generator (default 926)\n"
-            "        --summary-only    write sweep.tsv alone\n"
-            "        --genes           per-gene detection too: sweep_genes.tsv, sweep_gene_cells.tsv.gz and genes.tsv.gz per point\n"
-            "        --cells           per-cell reads, saturation and UMI copy numbers too: sweep_cells.tsv and cells.tsv.gz per point\n"
-            "        --fidelity        every point against the full-depth data of the same cells (every read of the sampled cells kept):\n"
-            "                          sweep_fidelity.tsv and fidelity.tsv.gz per point, with the Pearson and the cosine of the RAW counts\n"
-            "                          over ALL genes per cell (not log-normalised); resident form only\n"
-            "        --gene-fidelity   every point against the full-depth data of the same cells, per GENE: sweep_gene_fidelity.tsv and\n"
-            "                          gene_fidelity.tsv.gz per point, with the Pearson of the RAW counts over ALL sampled cells per gene,\n"
-            "                          the dispersion (variance / mean) at full depth and at the point, and the overlap of the 2000\n"
-            "                          most variable genes; resident form only\n"
-            "        --neighbors       every point against the full-depth data of the same cells, BETWEEN the cells: sweep_neighbors.tsv and\n"
-            "                          neighbors.tsv.gz per point, with the share of a cell's 15 nearest neighbours at full depth (cosine of\n"
-            "                          the RAW counts over the 2000 most variable genes, decided in exact integers) that it keeps; resident form only\n"
-            "        --coexpression    every point against the full-depth data of the same cells, BETWEEN the genes: sweep_coexpr.tsv and\n"
-            "                          coexpr.tsv.gz per point, with the share of a gene's 15 strongest co-expression partners at full depth\n"
-            "                          (Pearson of the RAW counts among the 2000 most variable genes, decided in exact integers) that it keeps;\n"
-            "                          resident form only\n"
-            "        --labels=<file>   one `barcode<TAB>label` per line (cell types of the full-depth analysis): sweep_labels.tsv,\n"
-            "                          sweep_label_classes.tsv and labels.tsv.gz, label_confusion.tsv.gz per point, with the share of labelled\n"
-            "                          cells whose 15 nearest neighbours still vote for their own label, at full depth and at the point;\n"
-            "                          resident form only\n"
-            "        --markers=<N>     with --labels: per label the N (1 to 2000) best marker genes among the 2000 most variable, ranked by the\n"
-            "                          exact AUC of the label's cells against the other labelled cells, at full depth and at the point:\n"
-            "                          sweep_markers.tsv and markers.tsv.gz per point; resident form only\n"
-            "        --mapping         every cell of a point looked up among ALL full-depth cells of the same sample (cosine of the RAW counts over\n"
-            "                          the 2000 most variable genes, decided in exact integers): sweep_mapping.tsv and mapping.tsv.gz per point, with\n"
-            "                          the rank of the cell's own full-depth profile, the share of its 15 nearest full-depth cells that are its\n"
-            "                          full-depth neighbours and, with --labels, the label they vote for; resident form only\n"
-            "        --pseudotime=<file>\n"
-            "                          one `barcode<TAB>value` per line (a pseudotime or any per-cell score of the full-depth analysis): sweep_pseudotime.tsv\n"
-            "                          and pseudotime.tsv.gz per point, with the value's rank estimated back per cell as the lower median over its 15\n"
-            "                          nearest neighbours, at full depth, at the point and, with --mapping, over the full-depth cells it maps among, and\n"
-            "                          Kendall's tau-b of the estimate against the value over all pairs of cells, counted exactly; resident form only\n"
-            "        --seeds=<list>    replicates: the grid at each of 1 to 64 seeds, comma separated, from the one decode; per point and\n"
-            "                          seed <out>/c<cell>_r<depth>_s<seed>/, one sweep.tsv row each, and sweep_reps.tsv with mean, sd, min\n"
-            "                          and max of every metric per grid point (with --genes sweep_genes_reps.tsv and\n"
-            "                          sweep_gene_reps.tsv.gz in place of sweep_gene_cells.tsv.gz); not with -s or --reps\n"
-            "        --reps=<int>      the same at the seeds s, s + 1, .. s + N - 1 (s: -s; N from 1 to 64)\n");
-}
-
-#define SWEEP_MAX_RATES 64
-int cmd_sweep(int argc, const char **argv)
-{
-    res_args_t A;
-    const int prc = fastf_res_parse_args(argc, argv, 'r', "depth", usage_sweep, "sweep does not write umi.tsv.gz (-u): run bam2db -u for the points that need it.", &A);
-    if (prc) return prc == 2 ? 0 : 1;
-    const char *cells = A.cells, *depths = A.list ? A.list : "1";
-    float rc[SWEEP_MAX_RATES], rd[SWEEP_MAX_RATES];
-    uint32_t n_c = 0, n_r = 0;
-    if (fastf_sweep_parse_rates(cells, 1, rc, SWEEP_MAX_RATES, &n_c) || fastf_sweep_parse_rates(depths, 0, rd, SWEEP_MAX_RATES, &n_r) ||
-        fastf_sweep_check_grid(rc, n_c, rd, n_r)) {
-        fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error());
-        return 1;
-    }
-    if (fastf_res_check_inputs(&A)) return 1;
-    const uint32_t flags = fastf_res_args_flags(&A);
-    if (A.pseudotime ? fastf_sweep_pseudotime(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, A.mapping, A.pseudotime) :
-        A.mapping ? fastf_sweep_mapping(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers, 1) :
-        A.markers ? fastf_sweep_markers(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels, A.markers) :
-        A.labels ? fastf_sweep_labels(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags, A.seed, A.labels) :
-        A.n_seeds ? fastf_sweep_reps(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seeds, A.n_seeds, flags)
-                  : fastf_sweep(A.bam, A.out, A.bar, A.feat, rc, n_c, rd, n_r, A.seed, flags)) {
-        fprintf(stderr, "\x1b[31mError:\x1b[0m sweep failed: %s\n", fastf_last_error());
-        return 1;
-    }
-    fastf_res_print_generated("sweep", &A);
-    return 0;
-}
+/* the command: what it does not share with the other two (resident.h: res_cmd_t) */
+static const res_cmd_t sweep_cmd = {
+    .list_short = 'r', .list_long = "depth", .list_default = "1",
+    .u_message = "sweep does not write umi.tsv.gz (-u): run bam2db -u for the points that need it.",
+    .help_intro = "bam2db over a grid of cell and depth rates from one decode of the bam file: per point <out>/c<cell>_r<depth>/ with the\n"
+                  "three files of bam2db, and <out>/sweep.tsv with one summary row per point.",
+    .help_list = "-r, --depth=<list>    rates of depth, comma separated (default 1.0)",
+    .help_point = "r<depth>", .help_resident = "; resident form only",
+};
+int cmd_sweep(int argc, const char **argv) { return fastf_res_cmd(&sweep_verb, &sweep_cmd, argc, argv); }

@@ -48,11 +48,7 @@ read_point_coexpression = _sweep.read_point_coexpression
 neighbors_row, neighbors_from_coo, read_point_neighbors = _sweep.neighbors_row, _sweep.neighbors_from_coo, _sweep.read_point_neighbors
 THRESHOLDS_COLUMNS = ("barcode", "threshold", "umis_full", "umis")
 parse_seeds, reps_seeds, reps_point_dir = _sweep.parse_seeds, _sweep.reps_seeds, _sweep.reps_point_dir      # (one rule for the three verbs)
-
-
-def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neighbors=False, coexpression=False):
-    return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
-            | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0) | (COEXPRESSION if coexpression else 0))
+_flags = _sweep._flags      # (one flag word for the three verbs)
 
 
 def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, summary_only: bool = False, genes: bool = False, cells: bool = False,
@@ -64,32 +60,8 @@ def level(bam, out, barcodes, features, rates_cell, umi_caps, seed: int = 926, s
     (read_gene_fidelity_table) and a gene_fidelity.tsv.gz per point directory; neighbors: out/level_neighbors.tsv (read_neighbors_table)
     and a neighbors.tsv.gz per point directory; labels=<path> (`--labels`): out/level_labels.tsv (read_labels_table),
     out/level_label_classes.tsv (read_label_classes_table) and labels.tsv.gz, label_confusion.tsv.gz per point directory"""
-    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
-    m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _sweep._pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_level_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
-                                                int(bool(mapping)), enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if _sweep._mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                seed % (1 << 32), None if labels is None else enc(labels), _sweep._markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                 m.ctypes.data, len(m), None, 0, _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression),
-                                                 seed % (1 << 32), enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    _lib.check(_lib.lib().fastf_level(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                      m.ctypes.data, len(m), seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _sweep._grid_call("level", bam, out, barcodes, features, rates_cell, _sweep._caps(umi_caps), None, seed,
+                      _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "level.tsv"))
 
 
@@ -98,36 +70,8 @@ def level_reps(bam, out, barcodes, features, rates_cell, umi_caps, seeds, summar
         pseudotime=None):
     """`fastF level ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/level.tsv per (cell rate, seed, UMI cap), which are returned, and out/level_reps.tsv (read_reps_table)"""
-    rc = np.ascontiguousarray(rates_cell, dtype=np.float32)
-    m = np.ascontiguousarray(umi_caps, dtype=np.uint64)
-    sd = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _sweep._pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_level_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers),
-                                                int(bool(mapping)), enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if _sweep._mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_level_mapping(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), 0 if markers is None else _sweep._markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_level_markers(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                None if labels is None else enc(labels), _sweep._markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_level_labels(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                                 m.ctypes.data, len(m), sd.ctypes.data, len(sd),
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "level.tsv"))
-    _lib.check(_lib.lib().fastf_level_reps(enc(bam), enc(out), enc(barcodes), enc(features), rc.ctypes.data_as(C.POINTER(C.c_float)), len(rc),
-                                           m.ctypes.data, len(m), sd.ctypes.data, len(sd), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _sweep._grid_call("level", bam, out, barcodes, features, rates_cell, _sweep._caps(umi_caps), seeds, 0,
+                      _sweep._flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "level.tsv"))
 
 

@@ -69,19 +69,9 @@ def _floats(v):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _flags(summary_only, genes, cells, fidelity, gene_fidelity=False, neighbors=False, coexpression=False):
+def _flags(summary_only, genes, cells, fidelity=False, gene_fidelity=False, neighbors=False, coexpression=False):
     return ((SUMMARY_ONLY if summary_only else 0) | (GENES if genes else 0) | (CELLS if cells else 0) | (FIDELITY if fidelity else 0)
             | (GENE_FIDELITY if gene_fidelity else 0) | (NEIGHBORS if neighbors else 0) | (COEXPRESSION if coexpression else 0))
-
-
-def _mapping_call(mapping, markers) -> bool:
-    """the _mapping entry point is taken: mapping=True, unless markers=N is given and no N the C call takes (the _markers call refuses it by name)"""
-    return bool(mapping) and (markers is None or _markers_n(markers) != 0)
-
-
-def _pseudotime_call(pseudotime, markers) -> bool:
-    """the _pseudotime entry point is taken: pseudotime=<path>, unless markers=N is given and no N the C call takes"""
-    return pseudotime is not None and (markers is None or _markers_n(markers) != 0)
 
 
 def _markers_n(markers) -> int:
@@ -91,6 +81,32 @@ def _markers_n(markers) -> int:
     except (TypeError, ValueError):
         return 0
     return n if 0 <= n < (1 << 32) and n == markers else 0
+
+
+def _caps(values):
+    """a list of caps as the (array, pointer) pair _grid_call takes"""
+    a = np.ascontiguousarray(values, dtype=np.uint64)
+    return a, a.ctypes.data
+
+
+def _grid_call(verb, bam, out, barcodes, features, rates_cell, values, seeds, seed, flags, labels, markers, mapping, pseudotime):
+    """the C call of <verb>() (seeds None: the run at `seed`) and <verb>_reps() (the replicate run over seeds); values: the verb's list as
+    (array, pointer).  It is fastf_<verb>_pseudotime, the most general entry point, with None for a path that is absent.  Two requests
+    are refused through the call that names them: markers=N with no N the call takes goes to fastf_<verb>_markers as 0, and an empty
+    list of seeds with no option beside it to fastf_<verb>_reps (with one, n_seeds == 0 is the run at seed 0, as the header says)"""
+    L = _lib.lib()
+    enc = lambda p: None if p is None else os.fspath(p).encode()  # noqa: E731
+    rc, prc = _floats(rates_cell)
+    sd = None if seeds is None else np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
+    grid = (enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), values[1], len(values[0]), None if sd is None else sd.ctypes.data,
+            0 if sd is None else len(sd))
+    if markers is not None and _markers_n(markers) == 0:
+        _lib.check(getattr(L, "fastf_%s_markers" % verb)(*grid, flags, seed % (1 << 32), enc(labels), 0))
+    elif sd is not None and not len(sd) and labels is None and markers is None and not mapping and pseudotime is None:
+        _lib.check(getattr(L, "fastf_%s_reps" % verb)(*grid, flags))
+    else:
+        _lib.check(getattr(L, "fastf_%s_pseudotime" % verb)(*grid, flags, seed % (1 << 32), enc(labels), 0 if markers is None else _markers_n(markers),
+                                                            int(bool(mapping)), enc(pseudotime)))
 
 
 def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926, summary_only: bool = False, genes: bool = False,
@@ -113,37 +129,9 @@ def sweep(bam, out, barcodes, features, rates_cell, rates_depth, seed: int = 926
     per point directory (read_point_mapping); pseudotime=<path> (`--pseudotime`: one barcode<TAB>value per line) the order of the cells along
     that value, estimated back from the neighbour sets: out/sweep_pseudotime.tsv (read_pseudotime_table) and a pseudotime.tsv.gz per point
     directory (read_point_pseudotime)"""
-    rc, prc = _floats(rates_cell)
-    rd, prd = _floats(rates_depth)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_sweep_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                     _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
-                                                     None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), int(bool(mapping)),
-                                                     enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if _mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
-                                                  None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32),
-                                                  None if labels is None else enc(labels), _markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), None, 0,
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), seed % (1 << 32), enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    _lib.check(_lib.lib().fastf_sweep(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd),
-                                      seed % (1 << 32), _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _grid_call("sweep", bam, out, barcodes, features, rates_cell, _floats(rates_depth), None, seed,
+               _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-
-
-def _seeds(seeds):
-    a = np.ascontiguousarray([int(x) % (1 << 32) for x in seeds], dtype=np.uint32)
-    return a, a.ctypes.data
 
 
 def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, summary_only: bool = False, genes: bool = False,
@@ -152,32 +140,8 @@ def sweep_reps(bam, out, barcodes, features, rates_cell, rates_depth, seeds, sum
     """`fastF sweep ... --seeds seeds`: a replicate run (one seed included) — the points in out/<point>_s<seed>/, one row of
     out/sweep.tsv per (cell rate, seed, depth rate), which are returned (read_table), and out/sweep_reps.tsv (read_reps_table);
     genes=True leaves out/sweep_genes.tsv, out/sweep_genes_reps.tsv (read_genes_reps_table) and out/sweep_gene_reps.tsv.gz"""
-    rc, prc = _floats(rates_cell)
-    rd, prd = _floats(rates_depth)
-    sd, psd = _seeds(seeds)
-    enc = lambda p: os.fspath(p).encode()  # noqa: E731
-    if _pseudotime_call(pseudotime, markers):
-        _lib.check(_lib.lib().fastf_sweep_pseudotime(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                     _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                     None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), int(bool(mapping)),
-                                                     enc(pseudotime)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if _mapping_call(mapping, markers):
-        _lib.check(_lib.lib().fastf_sweep_mapping(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                  None if labels is None else enc(labels), 0 if markers is None else _markers_n(markers), 1))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if markers is not None:
-        _lib.check(_lib.lib().fastf_sweep_markers(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                  _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0,
-                                                  None if labels is None else enc(labels), _markers_n(markers)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    if labels is not None:
-        _lib.check(_lib.lib().fastf_sweep_labels(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                                 _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), 0, enc(labels)))
-        return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
-    _lib.check(_lib.lib().fastf_sweep_reps(enc(bam), enc(out), enc(barcodes), enc(features), prc, len(rc), prd, len(rd), psd, len(sd),
-                                           _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression)))
+    _grid_call("sweep", bam, out, barcodes, features, rates_cell, _floats(rates_depth), seeds, 0,
+               _flags(summary_only, genes, cells, fidelity, gene_fidelity, neighbors, coexpression), labels, markers, mapping, pseudotime)
     return read_table(os.path.join(os.fspath(out), "sweep.tsv"))
 
 
