@@ -3,15 +3,13 @@
  *
  *   bam2db()      same signature/return convention as the reference (bam2db_ds.h:62-70,
  *                 bam2db_ds.c:106-573); db_file is accepted and ignored.
- *   cmd_bam2db()  same flags as main.c:288-362 (-b -f -a -d -c -r -o -s -u), values as
- *                 `-x v`, `-xv`, `--long v`, `--long=v`; floats via strtof, ints via
- *                 strtol(s, &e, 0) like argparse.c:88-108.
+ *   cmd_bam2db()  same flags as main.c:288-362 (-b -f -a -d -c -r -o -s -u), scanned by cli_opts.c.
  * The device engine does the work; there is no CPU fallback.
  */
 #define _GNU_SOURCE
 #include "host_io.h"
+#include "cli_opts.h"
 
-#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -468,8 +466,7 @@ static void usage_bam2db(FILE *f)
             "    -u, --umicopies       whether to store umi.tsv.gz\n");
 }
 
-struct opt { char s; const char *l; int has_arg; };
-static const struct opt k_opts[] = {
+static const cli_opt k_opts[] = {
     {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1},
     {'c', "cell", 1}, {'r', "depth", 1}, {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {0, NULL, 0}};
 
@@ -480,46 +477,22 @@ int cmd_bam2db(int argc, const char **argv)
     float rate_cell = 1.0f, rate_depth = 1.0f;
     unsigned int seed = 926;
 
-    for (int i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        const struct opt *o = NULL;
-        const char *val = NULL;
-        if (a[0] != '-' || !a[1]) break;                       /* first non-option stops parsing */
-        if (a[1] == '-') {
-            if (!a[2]) break;                                  /* "--" */
-            const char *eq = strchr(a + 2, '=');
-            size_t nl = eq ? (size_t)(eq - a - 2) : strlen(a + 2);
-            for (const struct opt *k = k_opts; k->l; k++)
-                if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
-            if (o && eq) val = eq + 1;
-        } else {
-            for (const struct opt *k = k_opts; k->l; k++) if (k->s == a[1]) { o = k; break; }
-            if (o && o->has_arg && a[2]) val = a + 2;          /* -xVALUE */
-        }
-        /* messages and exit status as argparse.c:36-46, 274-277: the option is named by its own spelling (`--cell`,
-         * `-c`), never with the value glued to it, and the process ends with EXIT_FAILURE */
-        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); usage_bam2db(stderr); exit(EXIT_FAILURE); }
-        char oname[32];
-        if (a[1] == '-') snprintf(oname, sizeof oname, "--%s", o->l); else snprintf(oname, sizeof oname, "-%c", o->s);
-        if (o->has_arg && !val) {
-            if (i + 1 >= argc) { fprintf(stderr, "error: option `%s` requires a value\n", oname); exit(EXIT_FAILURE); }
-            val = argv[++i];
-        }
-        char *end = NULL;
+    cli_scan S = CLI_SCAN(argc, argv, k_opts, 0);
+    for (const cli_opt *o; (o = cli_next(&S));)
         switch (o->s) {
         case 'h': usage_bam2db(stdout); exit(0);
-        case 'b': bam = val; break;
-        case 'f': feat = val; break;
-        case 'a': bar = val; break;
-        case 'd': db = val; break;
-        case 'o': out = val; break;
-        /* argparse.c:88-108: ERANGE first, then trailing characters; an empty value parses as 0 */
-        case 'c': errno = 0; rate_cell = strtof(val, &end); if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); exit(EXIT_FAILURE); } if (*end) { fprintf(stderr, "error: option `%s` expects a numerical value\n", oname); exit(EXIT_FAILURE); } break;
-        case 'r': errno = 0; rate_depth = strtof(val, &end); if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); exit(EXIT_FAILURE); } if (*end) { fprintf(stderr, "error: option `%s` expects a numerical value\n", oname); exit(EXIT_FAILURE); } break;
-        case 's': errno = 0; seed = (unsigned int)strtol(val, &end, 0); if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); exit(EXIT_FAILURE); } if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); exit(EXIT_FAILURE); } break;
+        case 'b': bam = S.val; break;
+        case 'f': feat = S.val; break;
+        case 'a': bar = S.val; break;
+        case 'd': db = S.val; break;
+        case 'o': out = S.val; break;
+        case 'c': rate_cell = cli_float(&S); break;
+        case 'r': rate_depth = cli_float(&S); break;
+        case 's': seed = (unsigned int)cli_int(&S); break;
         case 'u': _umi_copies_flag = 1; break;
         }
-    }
+    /* exit status as argparse.c:36-46, 274-277 */
+    if (S.err) { if (S.err == CLI_UNKNOWN) usage_bam2db(stderr); exit(EXIT_FAILURE); }
 
     /* existence checks of main.c:323-345 */
     if (!bam || access(bam, F_OK) == -1) { fprintf(stderr, "\x1b[31mError:\x1b[0m bam file: %s does not exist.\n", bam ? bam : "(null)"); exit(1); }

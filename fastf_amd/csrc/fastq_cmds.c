@@ -18,6 +18,7 @@
  */
 #define _GNU_SOURCE
 #include "host_io.h"
+#include "cli_opts.h"
 #include "fastq_kernels.hpp"
 
 #include <errno.h>
@@ -581,14 +582,8 @@ node *cell_counts(gzFile R1_file, size_t len_cellbarcode, size_t len_umi)
 }
 
 /* ------------------------------------------------------------------ */
-/* CLI: main.c:30-92 with argparse.c's option syntax                    */
+/* CLI: main.c:30-92, the options scanned by cli_opts.c                 */
 /* ------------------------------------------------------------------ */
-static const char *fq_prefix_skip(const char *str, const char *prefix)
-{
-    const size_t len = strlen(prefix);
-    return strncmp(str, prefix, len) ? NULL : str + len;
-}
-
 static void fq_usage(void)
 {
     printf("Usage: fastF freq [options]\n\nFind all the cell barcode whitelist and their frequencies.\n\n"
@@ -599,77 +594,23 @@ static void fq_usage(void)
            "    -u, --umi=<int>   length of UMI\n\n");
 }
 
-/* argparse.c:48-117 for one option: the value of -R/-o (string) or -l/-u (integer into the low 4 bytes of a size_t) */
-static void fq_opt_value(char c, int is_long, const char **optvalue, int *argc, const char ***argv,
-                         const char **r1, const char **out, size_t *len_cb, size_t *len_umi)
-{
-    const char *lname = c == 'R' ? "R1" : c == 'o' ? "out" : c == 'l' ? "len" : "umi";
-    const char *v = NULL;
-    if (*optvalue) { v = *optvalue; *optvalue = NULL; }
-    else if (*argc > 1) { (*argc)--; v = *++(*argv); }
-    else {
-        if (is_long) fprintf(stderr, "error: option `--%s` requires a value\n", lname);
-        else fprintf(stderr, "error: option `-%c` requires a value\n", c);
-        exit(EXIT_FAILURE);
-    }
-    if (c == 'R') { *r1 = v; return; }
-    if (c == 'o') { *out = v; return; }
-    char *end = NULL;
-    errno = 0;
-    const int iv = (int)strtol(v, &end, 0);
-    size_t *dst = c == 'l' ? len_cb : len_umi;
-    memcpy(dst, &iv, sizeof iv);                                  /* *(int *)opt->value = ... (argparse.c:88-92) */
-    const char *reason = errno == ERANGE ? "numerical result out of range" : end[0] != '\0' ? "expects an integer value" : NULL;
-    if (reason) {
-        if (is_long) fprintf(stderr, "error: option `--%s` %s\n", lname, reason);
-        else fprintf(stderr, "error: option `-%c` %s\n", c, reason);
-        exit(EXIT_FAILURE);
-    }
-}
-
 int cmd_freq(int argc, const char **argv)
 {
+    static const cli_opt opts[] = {{'h', "help", 0}, {'R', "R1", 1}, {'o', "out", 1}, {'l', "len", 1}, {'u', "umi", 1}, {0, NULL, 0}};
     const char *r1 = NULL, *out = NULL;
     size_t len_cb = 16, len_umi = 10;
-    /* argparse_parse (argparse.c:221-287): non-options are skipped, `--` ends the options */
-    int ac = argc - 1;
-    const char **av = argv + 1;
-    for (; ac; ac--, av++) {
-        const char *arg = av[0];
-        if (arg[0] != '-' || !arg[1]) continue;
-        if (arg[1] != '-') {
-            const char *optvalue = arg + 1;
-            while (optvalue) {
-                const char c = *optvalue;
-                if (c == 'h') { fq_usage(); exit(0); }
-                if (c != 'R' && c != 'o' && c != 'l' && c != 'u') {
-                    fprintf(stderr, "error: unknown option `%s`\n", av[0]);
-                    fq_usage();
-                    exit(EXIT_FAILURE);
-                }
-                optvalue = optvalue[1] ? optvalue + 1 : NULL;
-                fq_opt_value(c, 0, &optvalue, &ac, &av, &r1, &out, &len_cb, &len_umi);
-            }
-            continue;
+    cli_scan S = CLI_SCAN(argc, argv, opts, CLI_ARGPARSE);
+    for (const cli_opt *o; (o = cli_next(&S));)
+        switch (o->s) {
+        case 'h': fq_usage(); exit(0);
+        case 'R': r1 = S.val; break;
+        case 'o': out = S.val; break;
+        case 'l': case 'u': {                                     /* an int into the low 4 bytes of a size_t: *(int *)opt->value = ... (argparse.c:88-92) */
+            const int iv = (int)cli_int(&S);
+            memcpy(o->s == 'l' ? &len_cb : &len_umi, &iv, sizeof iv);
+            break; }
         }
-        if (!arg[2]) break;
-        static const char *const longs[] = {"help", "R1", "out", "len", "umi"};
-        static const char shorts[] = {'h', 'R', 'o', 'l', 'u'};
-        int hit = 0;
-        for (int k = 0; k < 5 && !hit; k++) {
-            const char *rest = fq_prefix_skip(arg + 2, longs[k]);
-            if (!rest || (*rest && *rest != '=')) continue;
-            hit = 1;
-            if (shorts[k] == 'h') { fq_usage(); exit(0); }
-            const char *optvalue = *rest ? rest + 1 : NULL;
-            fq_opt_value(shorts[k], 1, &optvalue, &ac, &av, &r1, &out, &len_cb, &len_umi);
-        }
-        if (!hit) {
-            fprintf(stderr, "error: unknown option `%s`\n", av[0]);
-            fq_usage();
-            exit(EXIT_FAILURE);
-        }
-    }
+    if (S.err) { if (S.err == CLI_UNKNOWN) fq_usage(); exit(EXIT_FAILURE); }
     if (r1 == NULL) { fprintf(stderr, "Please specify the path to R1 fastq files.\n"); exit(1); }   /* main.c:56-60 */
     {   /* gzopen(path, "r") (main.c:62-68) */
         const int fd = open(r1, O_RDONLY);

@@ -22,6 +22,7 @@
  */
 #define _GNU_SOURCE
 #include "host_io.h"
+#include "cli_opts.h"
 #include "filter_kernels.hpp"
 
 #include <errno.h>
@@ -603,7 +604,7 @@ void fastF(gzFile file_in[3], gzFile file_out[3], node *tree_whitelist, unsigned
 }
 
 /* ------------------------------------------------------------------ */
-/* CLI: main.c:94-228 with argparse.c's option syntax                    */
+/* CLI: main.c:94-228, the options scanned by cli_opts.c                */
 /* ------------------------------------------------------------------ */
 static void fl_usage(void)
 {
@@ -622,44 +623,6 @@ static void fl_usage(void)
 
 typedef struct { const char *i1, *r1, *r2, *out, *wl; int32_t len; int32_t seed; float rate; int all; } fl_args;
 
-/* argparse.c:48-117 for one option */
-static void fl_opt_value(char c, int is_long, const char *lname, const char **optvalue, int *argc, const char ***argv, fl_args *A)
-{
-    if (c == 'a') { A->all++; return; }
-    const char *v = NULL;
-    if (*optvalue) { v = *optvalue; *optvalue = NULL; }
-    else if (*argc > 1) { (*argc)--; v = *++(*argv); }
-    else {
-        if (is_long) fprintf(stderr, "error: option `--%s` requires a value\n", lname);
-        else fprintf(stderr, "error: option `-%c` requires a value\n", c);
-        exit(EXIT_FAILURE);
-    }
-    switch (c) {
-    case 'I': A->i1 = v; return;
-    case 'R': A->r1 = v; return;
-    case 'r': A->r2 = v; return;
-    case 'o': A->out = v; return;
-    case 'w': A->wl = v; return;
-    default: break;
-    }
-    char *end = NULL;
-    errno = 0;
-    const char *reason = NULL;
-    if (c == 't') {
-        A->rate = strtof(v, &end);
-        reason = errno == ERANGE ? "numerical result out of range" : end[0] != '\0' ? "expects a numerical value" : NULL;
-    } else {
-        const int iv = (int)strtol(v, &end, 0);
-        if (c == 'l') A->len = iv; else A->seed = iv;
-        reason = errno == ERANGE ? "numerical result out of range" : end[0] != '\0' ? "expects an integer value" : NULL;
-    }
-    if (reason) {
-        if (is_long) fprintf(stderr, "error: option `--%s` %s\n", lname, reason);
-        else fprintf(stderr, "error: option `-%c` %s\n", c, reason);
-        exit(EXIT_FAILURE);
-    }
-}
-
 static int dir_writable(const char *dir, const char *const names[3], const int want[3])
 {
     struct stat st;
@@ -677,41 +640,23 @@ int cmd_filter(int argc, const char **argv)
 {
     fl_args A; memset(&A, 0, sizeof A);
     A.out = "."; A.len = 16; A.seed = 926; A.rate = 0.f;
-    static const char *const longs[] = {"help", "I1", "R1", "R2", "out", "whitelist", "len", "seed", "rate", "allcells"};
-    static const char shorts[] = {'h', 'I', 'R', 'r', 'o', 'w', 'l', 's', 't', 'a'};
-    const int nopt = (int)sizeof shorts;
-    int ac = argc - 1;
-    const char **av = argv + 1;
-    for (; ac; ac--, av++) {
-        const char *arg = av[0];
-        if (arg[0] != '-' || !arg[1]) continue;
-        if (arg[1] != '-') {
-            const char *optvalue = arg + 1;
-            while (optvalue) {
-                const char c = *optvalue;
-                int k = 0;
-                while (k < nopt && shorts[k] != c) k++;
-                if (k == nopt) { fprintf(stderr, "error: unknown option `%s`\n", av[0]); fl_usage(); exit(EXIT_FAILURE); }
-                if (c == 'h') { fl_usage(); exit(0); }
-                optvalue = optvalue[1] ? optvalue + 1 : NULL;
-                fl_opt_value(c, 0, longs[k], &optvalue, &ac, &av, &A);
-            }
-            continue;
+    static const cli_opt opts[] = {{'h', "help", 0}, {'I', "I1", 1}, {'R', "R1", 1}, {'r', "R2", 1}, {'o', "out", 1}, {'w', "whitelist", 1},
+                                   {'l', "len", 1}, {'s', "seed", 1}, {'t', "rate", 1}, {'a', "allcells", 0}, {0, NULL, 0}};
+    cli_scan S = CLI_SCAN(argc, argv, opts, CLI_ARGPARSE);
+    for (const cli_opt *o; (o = cli_next(&S));)
+        switch (o->s) {
+        case 'h': fl_usage(); exit(0);
+        case 'I': A.i1 = S.val; break;
+        case 'R': A.r1 = S.val; break;
+        case 'r': A.r2 = S.val; break;
+        case 'o': A.out = S.val; break;
+        case 'w': A.wl = S.val; break;
+        case 'l': A.len = (int)cli_int(&S); break;
+        case 's': A.seed = (int)cli_int(&S); break;
+        case 't': A.rate = cli_float(&S); break;
+        case 'a': A.all++; break;
         }
-        if (!arg[2]) break;
-        int hit = 0;
-        for (int k = 0; k < nopt && !hit; k++) {
-            const size_t ln = strlen(longs[k]);
-            if (strncmp(arg + 2, longs[k], ln)) continue;
-            const char *rest = arg + 2 + ln;
-            if (*rest && *rest != '=') continue;
-            hit = 1;
-            if (shorts[k] == 'h') { fl_usage(); exit(0); }
-            const char *optvalue = *rest ? rest + 1 : NULL;
-            fl_opt_value(shorts[k], 1, longs[k], &optvalue, &ac, &av, &A);
-        }
-        if (!hit) { fprintf(stderr, "error: unknown option `%s`\n", av[0]); fl_usage(); exit(EXIT_FAILURE); }
-    }
+    if (S.err) { if (S.err == CLI_UNKNOWN) fl_usage(); exit(EXIT_FAILURE); }
     printf("whitelist: %s\n", A.wl ? A.wl : "(null)");                                     /* main.c:140 */
     if (A.r1 == NULL) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m path to R1 fastq files can not been NULL while filtering .\n");

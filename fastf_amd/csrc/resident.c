@@ -6,6 +6,7 @@
  */
 #define _GNU_SOURCE
 #include "resident.h"
+#include "cli_opts.h"
 
 #include <errno.h>
 #include <math.h>
@@ -1158,70 +1159,47 @@ static void fastf_res_usage(const char *verb, const res_cmd_t *D, FILE *f)
 }
 
 /* returns 0, 1 after an error message, 2 after the help text; -u prints D->u_message and fails */
-struct ropt { char s; const char *l; int has_arg; };
 static int fastf_res_parse_args(int argc, const char **argv, const char *verb, const res_cmd_t *D, res_args_t *out)
 {
-    const char list_short = D->list_short;
-    const struct ropt opts[] = {
-        {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {list_short, D->list_long, 1},
-        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {'S', "summary-only", 0}, {'G', "genes", 0}, {'C', "cells", 0}, {'F', "fidelity", 0}, {'Q', "gene-fidelity", 0}, {'N', "neighbors", 0}, {'X', "coexpression", 0}, {'P', "mapping", 0}, {'T', "pseudotime", 1}, {'L', "labels", 1}, {'M', "markers", 1}, {'E', "seeds", 1}, {'R', "reps", 1}, {0, NULL, 0}};
+    /* the options from O_SUMMARY_ONLY on have no short form */
+    enum { O_HELP, O_BAM, O_FEATURE, O_BARCODE, O_DBNAME, O_CELL, O_LIST, O_OUT, O_SEED, O_UMICOPIES, O_SUMMARY_ONLY, O_GENES, O_CELLS, O_FIDELITY, O_GENE_FIDELITY,
+           O_NEIGHBORS, O_COEXPRESSION, O_MAPPING, O_PSEUDOTIME, O_LABELS, O_MARKERS, O_SEEDS, O_REPS };
+    const cli_opt opts[] = {
+        {'h', "help", 0}, {'b', "bam", 1}, {'f', "feature", 1}, {'a', "barcode", 1}, {'d', "dbname", 1}, {'c', "cell", 1}, {D->list_short, D->list_long, 1},
+        {'o', "out", 1}, {'s', "seed", 1}, {'u', "umicopies", 0}, {0, "summary-only", 0}, {0, "genes", 0}, {0, "cells", 0}, {0, "fidelity", 0}, {0, "gene-fidelity", 0},
+        {0, "neighbors", 0}, {0, "coexpression", 0}, {0, "mapping", 0}, {0, "pseudotime", 1}, {0, "labels", 1}, {0, "markers", 1}, {0, "seeds", 1}, {0, "reps", 1}, {0, NULL, 0}};
     const char *seeds_text = NULL, *reps_text = NULL, *markers_text = NULL;
     int have_s = 0;
     out->n_seeds = 0;
     out->bam = out->feat = out->bar = out->list = NULL; out->out = "."; out->cells = "1"; out->seed = 926; out->summary_only = 0; out->genes = 0; out->per_cell = 0; out->fidelity = 0; out->gene_fidelity = 0; out->neighbors = 0; out->coexpression = 0; out->mapping = 0; out->labels = NULL; out->pseudotime = NULL; out->markers = 0;
-    for (int i = 1; i < argc; i++) {
-        const char *a = argv[i];
-        const struct ropt *o = NULL;
-        const char *val = NULL;
-        if (a[0] != '-' || !a[1]) break;
-        if (a[1] == '-') {
-            if (!a[2]) break;
-            const char *eq = strchr(a + 2, '=');
-            const size_t nl = eq ? (size_t)(eq - a - 2) : strlen(a + 2);
-            for (const struct ropt *k = opts; k->l; k++)
-                if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
-            if (o && eq) val = eq + 1;
-        } else {
-            for (const struct ropt *k = opts; k->l; k++) if (k->s == a[1] && !strchr("SGCFQNXPTLMER", k->s)) { o = k; break; }
-            if (o && o->has_arg && a[2]) val = a + 2;
+    cli_scan S = CLI_SCAN(argc, argv, opts, 0);
+    for (const cli_opt *o; (o = cli_next(&S));)
+        switch (o - opts) {
+        case O_HELP: fastf_res_usage(verb, D, stdout); return 2;
+        case O_BAM: out->bam = S.val; break;
+        case O_FEATURE: out->feat = S.val; break;
+        case O_BARCODE: out->bar = S.val; break;
+        case O_DBNAME: break;
+        case O_CELL: out->cells = S.val; break;
+        case O_LIST: out->list = S.val; break;
+        case O_OUT: out->out = S.val; break;
+        case O_SEED: have_s = 1; out->seed = (unsigned int)cli_int(&S); break;
+        case O_UMICOPIES: fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", D->u_message); return 1;
+        case O_SUMMARY_ONLY: out->summary_only = 1; break;
+        case O_GENES: out->genes = 1; break;
+        case O_CELLS: out->per_cell = 1; break;
+        case O_FIDELITY: out->fidelity = 1; break;
+        case O_GENE_FIDELITY: out->gene_fidelity = 1; break;
+        case O_NEIGHBORS: out->neighbors = 1; break;
+        case O_COEXPRESSION: out->coexpression = 1; break;
+        case O_MAPPING: out->mapping = 1; break;
+        case O_PSEUDOTIME: out->pseudotime = S.val; break;
+        case O_LABELS: out->labels = S.val; break;
+        case O_MARKERS: markers_text = S.val; break;
+        case O_SEEDS: seeds_text = S.val; break;
+        case O_REPS: reps_text = S.val; break;
         }
-        if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); fastf_res_usage(verb, D, stderr); return 1; }
-        char oname[32];
-        if (a[1] == '-') snprintf(oname, sizeof oname, "--%s", o->l); else snprintf(oname, sizeof oname, "-%c", o->s);
-        if (o->has_arg && !val) {
-            if (i + 1 >= argc) { fprintf(stderr, "error: option `%s` requires a value\n", oname); return 1; }
-            val = argv[++i];
-        }
-        char *end = NULL;
-        if (o->s == list_short) { out->list = val; continue; }
-        switch (o->s) {
-        case 'h': fastf_res_usage(verb, D, stdout); return 2;
-        case 'b': out->bam = val; break;
-        case 'f': out->feat = val; break;
-        case 'a': out->bar = val; break;
-        case 'd': break;
-        case 'o': out->out = val; break;
-        case 'c': out->cells = val; break;
-        case 's': have_s = 1; errno = 0; out->seed = (unsigned int)strtol(val, &end, 0);
-                  if (errno == ERANGE) { fprintf(stderr, "error: option `%s` numerical result out of range\n", oname); return 1; }
-                  if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", oname); return 1; }
-                  break;
-        case 'u': fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", D->u_message); return 1;
-        case 'S': out->summary_only = 1; break;
-        case 'G': out->genes = 1; break;
-        case 'C': out->per_cell = 1; break;
-        case 'F': out->fidelity = 1; break;
-        case 'Q': out->gene_fidelity = 1; break;
-        case 'N': out->neighbors = 1; break;
-        case 'X': out->coexpression = 1; break;
-        case 'P': out->mapping = 1; break;
-        case 'L': out->labels = val; break;
-        case 'T': out->pseudotime = val; break;
-        case 'M': markers_text = val; break;
-        case 'E': seeds_text = val; break;
-        case 'R': reps_text = val; break;
-        }
-    }
+    if (S.err) { if (S.err == CLI_UNKNOWN) fastf_res_usage(verb, D, stderr); return 1; }
     if (markers_text) {                                     /* (refused here: before the verb makes its output directory) */
         char *end = NULL;
         errno = 0;

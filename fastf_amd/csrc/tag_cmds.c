@@ -19,6 +19,7 @@
  */
 #define _GNU_SOURCE
 #include "host_io.h"
+#include "cli_opts.h"
 
 #include <pthread.h>
 #include <stdio.h>
@@ -671,49 +672,14 @@ void free_CB_node(CB_node *root)                             /* extract.c:33-45,
 }
 
 /* ------------------------------------------------------------------ */
-/* CLI (option syntax of argparse.c:149-197: -x v, -xv, --long v, --long=v) */
+/* CLI (the options: cli_opts.c; a parse error ends with EXIT_FAILURE and no usage text) */
 /* ------------------------------------------------------------------ */
-struct topt { char s; const char *l; int has_arg; };
-
-/* returns the option matched for argv[*i] (value in *val), NULL at the first non-option; exits on errors */
-static const struct topt *next_opt(const struct topt *opts, int argc, const char **argv, int *i, const char **val)
-{
-    const char *a = argv[*i];
-    const struct topt *o = NULL;
-    *val = NULL;
-    if (a[0] != '-' || !a[1]) return NULL;
-    if (a[1] == '-') {
-        if (!a[2]) return NULL;
-        const char *eq = strchr(a + 2, '=');
-        size_t nl = eq ? (size_t)(eq - a - 2) : strlen(a + 2);
-        for (const struct topt *k = opts; k->l; k++)
-            if (strlen(k->l) == nl && strncmp(k->l, a + 2, nl) == 0) { o = k; break; }
-        if (o && eq) *val = eq + 1;
-    } else {
-        for (const struct topt *k = opts; k->l; k++) if (k->s == a[1]) { o = k; break; }
-        if (o && o->has_arg && a[2]) *val = a + 2;
-    }
-    /* messages and exit status as argparse.c:36-46, 274-277 */
-    if (!o) { fprintf(stderr, "error: unknown option `%s`\n", a); exit(EXIT_FAILURE); }
-    if (o->has_arg && !*val) {
-        if (*i + 1 >= argc) {
-            if (a[1] == '-') fprintf(stderr, "error: option `--%s` requires a value\n", o->l);
-            else fprintf(stderr, "error: option `-%c` requires a value\n", o->s);
-            exit(EXIT_FAILURE);
-        }
-        *val = argv[++*i];
-    }
-    return o;
-}
-
 int cmd_crb(int argc, const char **argv)                     /* main.c:231-286 */
 {
-    static const struct topt opts[] = {{'h', "help", 0}, {'b', "bam", 1}, {'o', "out", 1}, {0, NULL, 0}};
+    static const cli_opt opts[] = {{'h', "help", 0}, {'b', "bam", 1}, {'o', "out", 1}, {0, NULL, 0}};
     const char *bam = NULL, *out = ".";
-    for (int i = 1; i < argc; i++) {
-        const char *val;
-        const struct topt *o = next_opt(opts, argc, argv, &i, &val);
-        if (!o) break;
+    cli_scan S = CLI_SCAN(argc, argv, opts, 0);
+    for (const cli_opt *o; (o = cli_next(&S));)
         switch (o->s) {
         case 'h':
             printf("Usage: fastF crb [options]\n\nExtract CR and CB tags from bam file and summarize them with frequencies to a tsv file.\n\n"
@@ -721,10 +687,10 @@ int cmd_crb(int argc, const char **argv)                     /* main.c:231-286 *
                    "    -b, --bam=<str>   path to bam file\n"
                    "    -o, --out=<str>   path to output file\n");
             exit(0);
-        case 'b': bam = val; break;
-        case 'o': out = val; break;
+        case 'b': bam = S.val; break;
+        case 'o': out = S.val; break;
         }
-    }
+    if (S.err) exit(EXIT_FAILURE);
     if (bam == NULL) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m path to bam file can not been NULL while extracting .\n");          /* main.c:253 */
         exit(1);
@@ -750,15 +716,11 @@ int cmd_crb(int argc, const char **argv)                     /* main.c:231-286 *
 
 int cmd_extract(int argc, const char **argv)                  /* main.c:364-402 */
 {
-    static const struct topt opts[] = {{'h', "help", 0}, {'b', "bam", 1}, {'t', "tag", 1}, {'T', "type", 1}, {0, NULL, 0}};
+    static const cli_opt opts[] = {{'h', "help", 0}, {'b', "bam", 1}, {'t', "tag", 1}, {'T', "type", 1}, {0, NULL, 0}};
     const char *bam = NULL, *tag = NULL;
     int type = 0;
-    for (int i = 1; i < argc; i++) {
-        const char *val;
-        const struct topt *o = next_opt(opts, argc, argv, &i, &val);
-        if (!o) break;
-        char *end = NULL;
-        const int o_long = argv[i][1] == '-' || (i > 1 && val == argv[i] && argv[i - 1][1] == '-');
+    cli_scan S = CLI_SCAN(argc, argv, opts, CLI_NO_ERANGE);
+    for (const cli_opt *o; (o = cli_next(&S));)
         switch (o->s) {
         case 'h':
             printf("Usage: fastF extract [options]\n\nExtract the tag of bam file.\n\n"
@@ -767,14 +729,11 @@ int cmd_extract(int argc, const char **argv)                  /* main.c:364-402 
                    "    -t, --tag=<str>   tag of bam file\n"
                    "    -T, --type=<int>  type of tag, 0: string, 1: integer\n");
             exit(0);
-        case 'b': bam = val; break;
-        case 't': tag = val; break;
-        case 'T':
-            type = (int)strtol(val, &end, 0);                  /* argparse.c:88-92 */
-            if (*end) { fprintf(stderr, "error: option `%s` expects an integer value\n", o_long ? "--type" : "-T"); exit(EXIT_FAILURE); }
-            break;
+        case 'b': bam = S.val; break;
+        case 't': tag = S.val; break;
+        case 'T': type = (int)cli_int(&S); break;              /* argparse.c:88-92 */
         }
-    }
+    if (S.err) exit(EXIT_FAILURE);
     if (!bam || access(bam, F_OK) == -1) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m bam file: %s does not exist.\n", bam ? bam : "(null)");              /* main.c:386 */
         exit(1);

@@ -38,7 +38,7 @@ def test_reader_batch_path_is_clean_under_sanitizers(tmp_path, san):
     assert len(sums) == 1
 
 
-BAM2DB_SRC = [os.path.join(ROOT, "fastf_amd", "csrc", "bam2db_main.c")] + SRC
+BAM2DB_SRC = [os.path.join(ROOT, "fastf_amd", "csrc", f) for f in ("bam2db_main.c", "cli_opts.c")] + SRC
 
 
 @pytest.mark.parametrize("san", ["address,undefined", "thread"])
