@@ -1013,7 +1013,7 @@ typedef struct fastf_taghist_result {
     uint64_t n_valid;                /* records with key1 != 0 (pair mode: and key2 != 0)                   */
     uint64_t n_key1_present;         /* records with key1 != 0                                              */
     /* level 1: distinct key1, ascending key value.  Pair mode: count1/first1 cover valid records only, and an
-     * entry whose key1 never met a key2 has count1 == 0. */
+     * entry whose key1 never met a key2 has count1 == 0 and first1 == UINT64_MAX (it has no first valid record). */
     const uint64_t *key1, *count1, *first1; size_t n1;
     /* pair mode: distinct (key1, key2) of valid records, grouped by key1 in level-1 order */
     const uint32_t *pair_k1;         /* index into key1[]                                                   */
