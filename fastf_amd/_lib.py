@@ -106,6 +106,9 @@ ABI_SYMBOLS = [
     "fastf_freq_text", "fastf_taghist_reserve_device", "fastf_taghist_stream", "fastf_taghist_push_device",
     # filter
     "fastf_filter", "fastf_filter_draws", "fastf_filter_draws_host", "fastf_filter_rand_at", "fastf_filter_draw_passes",
+    # fqcap
+    "fastf_fqcap", "fastf_fqcap_rate", "fastf_fcpdev_begin", "fastf_fcpdev_count", "fastf_fcpdev_set_rates", "fastf_fcpdev_decide",
+    "fastf_fcpdev_draws", "fastf_fcpdev_read",
     # sweep
     "fastf_sweep", "fastf_sweep_parse_rates", "fastf_sweep_check_grid", "fastf_sweep_point_dir", "fastf_sweep_header",
     "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
@@ -301,6 +304,11 @@ def lib():
     L.fastf_filter_rand_at.argtypes = [C.c_uint32, u64]
     L.fastf_filter_rand_at.restype = C.c_uint32
     L.fastf_filter_draw_passes.argtypes = [C.c_uint32, C.c_float]
+    if hasattr(L, "fastf_fqcap") or not os.environ.get("FASTF_LIB_OVERRIDE"):           # (an A/B build from before fqcap)
+        L.fastf_fqcap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, u64,
+                                  C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.fastf_fqcap_rate.argtypes = [u64, u64, C.c_float]
+        L.fastf_fqcap_rate.restype = C.c_float
     L.fastf_taghist_reserve_device.argtypes = [vp, sz]
     L.fastf_taghist_reserve_device.restype = vp
     L.fastf_taghist_stream.argtypes = [vp]

@@ -21,9 +21,8 @@
  * -o directory that cannot be written are refused (exit 1).
  */
 #define _GNU_SOURCE
-#include "host_io.h"
+#include "filter_host.h"
 #include "cli_opts.h"
-#include "filter_kernels.hpp"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -40,7 +39,6 @@
 
 #define DEG FLT_RAND_DEG
 
-static double fl_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + t.tv_nsec * 1e-9; }
 static void fl_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 static void fl_err(const char *fmt, ...)
 {
@@ -107,8 +105,7 @@ static uint32_t poly_apply(const uint32_t *c, const uint32_t *r)
 }
 
 /* the generator's state at output q: S[k] = r_{q+344+k} = r_{3 + (q+341+k)}, k < 31 */
-typedef struct { uint32_t r0[DEG], S[DEG]; uint64_t q; } rand_gen;
-static void gen_seek(rand_gen *g, uint32_t seed, uint64_t q)
+void fl_gen_seek(rand_gen *g, uint32_t seed, uint64_t q)
 {
     rand_init(seed, g->r0);
     uint32_t c[DEG];
@@ -134,7 +131,7 @@ static void jump_init(void)
     for (unsigned k = 0; k < DEG; k++) { memcpy(g_jump[k], c, sizeof c); poly_mulx(c); }
 }
 /* start states of the ceil(n / FLT_CHUNK) chunks of outputs q .. q + n - 1 into cs; the generator moves on to q + n */
-static void gen_chunks(rand_gen *g, uint64_t n, uint32_t *cs)
+void fl_gen_chunks(rand_gen *g, uint64_t n, uint32_t *cs)
 {
     static pthread_once_t once = PTHREAD_ONCE_INIT;
     pthread_once(&once, jump_init);
@@ -153,7 +150,7 @@ static void gen_chunks(rand_gen *g, uint64_t n, uint32_t *cs)
 uint32_t fastf_filter_rand_at(uint32_t seed, uint64_t index)
 {
     rand_gen g;
-    gen_seek(&g, seed, index);
+    fl_gen_seek(&g, seed, index);
     return g.S[0] >> 1;
 }
 
@@ -161,7 +158,7 @@ int fastf_filter_draws_host(uint32_t seed, uint64_t first, uint64_t n, uint32_t 
 {
     if (!out && n) { fl_err("null argument"); return 1; }
     rand_gen g;
-    gen_seek(&g, seed, first);
+    fl_gen_seek(&g, seed, first);
     uint32_t S[2 * DEG];
     memcpy(S, g.S, sizeof g.S);
     for (uint64_t i = 0; i < n; i++) {                        /* the recurrence, one word at a time */
@@ -179,11 +176,11 @@ int fastf_filter_draws(uint32_t seed, uint64_t first, uint64_t n, uint32_t *out)
 {
     if (!out && n) { fl_err("null argument"); return 1; }
     rand_gen g;
-    gen_seek(&g, seed, first);
+    fl_gen_seek(&g, seed, first);
     const uint64_t nch = (n + FLT_CHUNK - 1) / FLT_CHUNK;
     uint32_t *cs = (uint32_t *)malloc((nch ? nch : 1) * DEG * sizeof *cs);
     if (!cs) { fl_err("out of memory"); return 1; }
-    gen_chunks(&g, n, cs);
+    fl_gen_chunks(&g, n, cs);
     const int rc = fastf_flt_draws_dev(0, cs, n, out);
     free(cs);
     return rc;
@@ -192,15 +189,7 @@ int fastf_filter_draws(uint32_t seed, uint64_t first, uint64_t n, uint32_t *out)
 /* ------------------------------------------------------------------ */
 /* whitelist: the first len bytes of every line (strncmp semantics)      */
 /* ------------------------------------------------------------------ */
-typedef struct { const char *p; uint32_t n; } fl_str;
-typedef struct {
-    uint64_t *dna; size_t n_dna;         /* DNA-form keys (exactly len <= 31 bases of ACGT), sorted, unique */
-    fl_str *esc; size_t n_esc;           /* every other prefix, sorted */
-    char *pool;
-    size_t nrow;
-} fl_wl;
-
-static int str_cmp(const void *a, const void *b)
+int fl_str_cmp(const void *a, const void *b)
 {
     const fl_str *x = (const fl_str *)a, *y = (const fl_str *)b;
     const uint32_t m = x->n < y->n ? x->n : y->n;
@@ -226,7 +215,7 @@ static uint64_t dna_key(const unsigned char *s, size_t n, uint32_t len)
     return FQ_DNA_TAG | v;
 }
 
-static void wl_free(fl_wl *w) { free(w->dna); free(w->esc); free(w->pool); memset(w, 0, sizeof *w); }
+void fl_wl_free(fl_wl *w) { free(w->dna); free(w->esc); free(w->pool); memset(w, 0, sizeof *w); }
 
 /* lines as fgets(buf, 100) of read_txt returns them (each keeps its '\n'), cut at the first NUL and at len */
 static int wl_add_lines(fl_wl *w, const char *const *lines, size_t n_lines, uint32_t len)
@@ -245,13 +234,13 @@ static int wl_add_lines(fl_wl *w, const char *const *lines, size_t n_lines, uint
     size_t u = 0;
     for (size_t i = 0; i < w->n_dna; i++) if (!u || w->dna[u - 1] != w->dna[i]) w->dna[u++] = w->dna[i];
     w->n_dna = u;
-    qsort(w->esc, w->n_esc, sizeof *w->esc, str_cmp);
+    qsort(w->esc, w->n_esc, sizeof *w->esc, fl_str_cmp);
     w->nrow = n_lines;
     return 0;
 }
 
 /* get_row + read_txt (filter.c:181-226) of a whitelist file; keys = 0: the row count and the line-length check only */
-static int wl_load(fl_wl *w, const char *path, uint32_t len, int keys)
+int fl_wl_load(fl_wl *w, const char *path, uint32_t len, int keys)
 {
     memset(w, 0, sizeof *w);
     FILE *f = fopen(path, "rb");
@@ -311,8 +300,6 @@ static void tree_walk(const node *t, const char ***v, size_t *n, size_t *cap)
 /* ------------------------------------------------------------------ */
 /* output: gzip members appended in order, or the caller's gzFile         */
 /* ------------------------------------------------------------------ */
-typedef struct { FILE *f; gzFile gz; const char *path; uint64_t bytes_in; int members; } fl_sink;
-
 #define GZ_PIECE ((size_t)1 << 20)
 typedef struct { const unsigned char *in; size_t len, n; unsigned char **out; size_t *out_len; size_t next; int err; } gz_job;
 static void gz_worker(void *vp, int w)
@@ -329,7 +316,7 @@ static void gz_worker(void *vp, int w)
         if (!j->out_len[i]) __atomic_store_n(&j->err, 1, __ATOMIC_RELAXED);
     }
 }
-static int sink_write(fl_sink *s, const unsigned char *p, size_t len, double *t_deflate)
+int fl_sink_write(fl_sink *s, const unsigned char *p, size_t len, double *t_deflate)
 {
     if (!s || (!len && (s->gz || s->members))) return 0;
     const double t0 = fl_now();
@@ -363,38 +350,29 @@ static int sink_write(fl_sink *s, const unsigned char *p, size_t len, double *t_
 /* ------------------------------------------------------------------ */
 /* one file through the device                                           */
 /* ------------------------------------------------------------------ */
-typedef struct {
-    fastf_fltdev_t *dev;
-    size_t W;
-    unsigned char *stage;                /* pinned: FLT_HDR + W + 64 */
-    uint32_t len; int all; float rate; uint32_t seed;
-    const fl_wl *wl;
-    uint64_t n_reads, n_kept;
-    double t_fill, t_deflate, t_host, dev_ms;
-    uint64_t n_escapes;
-} fl_run;
-
 static int esc_hit(const fl_wl *w, const unsigned char *p, size_t n)
 {
     fl_str k = { (const char *)p, (uint32_t)n };
-    return bsearch(&k, w->esc, w->n_esc, sizeof *w->esc, str_cmp) != NULL;
+    return bsearch(&k, w->esc, w->n_esc, sizeof *w->esc, fl_str_cmp) != NULL;
 }
 
-/* mode 0: R1 (decides, *n_reads out); mode 1: I1 / R2 against the bitmap, reads >= limit ignored.  `name` names the file in
- * messages. */
-static int fl_file(fl_run *R, fq_src *src, int mode, uint64_t limit, const char *name, fl_sink *sink)
+/* mode 0: R1 (decides, *n_reads out; R->hk: another command's decision in filter's place); mode 1: I1 / R2 against the bitmap,
+ * reads >= limit ignored.  `name` names the file in messages. */
+int fl_file(fl_run *R, fq_src *src, int mode, uint64_t limit, const char *name, fl_sink *sink)
 {
     fastf_fltdev_t *dev = R->dev;
     const size_t W = R->W;
     unsigned char *stage = R->stage;
+    const fl_hooks *hk = mode == 0 ? R->hk : NULL;
+    const int draws = mode == 0 && !(hk && hk->count_only);
     uint32_t *cs = NULL, *hits = NULL;
     size_t hits_cap = 0;
     rand_gen g;
     int rc = 1;
     uint64_t a = 0;
     if (fastf_fltdev_reset(dev)) return 1;
-    if (mode == 0) {
-        gen_seek(&g, R->seed, 0);
+    if (draws) {
+        fl_gen_seek(&g, R->seed, 0);
         cs = (uint32_t *)malloc(((W / 4 + 2) / FLT_CHUNK + 2) * DEG * sizeof *cs);
         if (!cs) { fl_err("out of memory"); return 1; }
     }
@@ -417,13 +395,14 @@ static int fl_file(fl_run *R, fq_src *src, int mode, uint64_t limit, const char 
         uint64_t r_lo = 0, n_rec = 0;
         if (fastf_fltdev_parse(dev, stage, len, a, tv, mode == 0 ? ~0ull : limit, &r_lo, &n_rec)) goto done;
         const fastf_flt_esc_t *e = NULL; uint32_t ne = 0;
-        if (mode == 0) {
+        if (draws) {
             if (g.q != r_lo) { fl_err("filter: draw stream out of step (%llu vs %llu)", (unsigned long long)g.q, (unsigned long long)r_lo); goto done; }
             const double th = fl_now();
-            gen_chunks(&g, n_rec, cs);
+            fl_gen_chunks(&g, n_rec, cs);
             R->t_host += fl_now() - th;
         }
-        if (fastf_fltdev_decide(dev, mode, R->all, R->len > 0xffffffffu ? 0xffffffffu : R->len, R->rate, cs, &e, &ne)) goto done;
+        if (hk ? hk->decide(hk->ctx, dev, R->len, cs, n_rec, &e, &ne)
+               : fastf_fltdev_decide(dev, mode, R->all, R->len > 0xffffffffu ? 0xffffffffu : R->len, R->rate, cs, &e, &ne)) goto done;
         uint32_t nh = 0;
         if (ne) {
             const double th = fl_now();
@@ -432,14 +411,18 @@ static int fl_file(fl_run *R, fq_src *src, int mode, uint64_t limit, const char 
                 const unsigned char *p = stage + e[k].s1;
                 const uint64_t gpos = a + e[k].s1 - FLT_HDR;
                 const uint32_t m = fq_escape_len(p, a + len - gpos, Lc);
-                if (esc_hit(R->wl, p, m)) hits[nh++] = e[k].i;
+                const int hit = hk ? hk->escape(hk->ctx, dev, p, m, e[k].i) : esc_hit(R->wl, p, m);
+                if (hit < 0) goto done;
+                if (hit) hits[nh++] = e[k].i;
             }
             R->n_escapes += ne;
             R->t_host += fl_now() - th;
         }
-        const unsigned char *out = NULL; size_t total = 0;
-        if (fastf_fltdev_emit(dev, hits, nh, &out, &total)) goto done;
-        if (total && sink_write(sink, out, total, &R->t_deflate)) goto done;
+        if (!(hk && hk->count_only)) {
+            const unsigned char *out = NULL; size_t total = 0;
+            if (fastf_fltdev_emit(dev, hits, nh, &out, &total)) goto done;
+            if (total && fl_sink_write(sink, out, total, &R->t_deflate)) goto done;
+        }
         memmove(stage, stage + len, FLT_HDR);                 /* the last FLT_HDR bytes of this window (len >= FLT_HDR or a zero prefix) */
         a += (uint64_t)n;
         if (mode == 1 && r_lo + n_rec >= limit) break;         /* the rest of the file is never read by the reference */
@@ -512,7 +495,7 @@ done:
 /* ------------------------------------------------------------------ */
 /* entry points                                                          */
 /* ------------------------------------------------------------------ */
-static int sink_open(fl_sink *s, const char *dir, const char *name, char *path, size_t path_cap)
+int fl_sink_open(fl_sink *s, const char *dir, const char *name, char *path, size_t path_cap)
 {
     memset(s, 0, sizeof *s);
     snprintf(path, path_cap, "%s/%s", dir, name);
@@ -521,13 +504,13 @@ static int sink_open(fl_sink *s, const char *dir, const char *name, char *path, 
     if (!s->f) { fl_err("cannot open %s for writing: %s", path, strerror(errno)); return 1; }
     return 0;
 }
-static int sink_close(fl_sink *s)
+int fl_sink_close(fl_sink *s)
 {
     if (!s->f) return 0;
     int rc = 0;
     if (!s->members) {                                        /* nothing kept: still a valid (empty) gzip file */
         double t = 0;
-        rc = sink_write(s, (const unsigned char *)"", 0, &t);
+        rc = fl_sink_write(s, (const unsigned char *)"", 0, &t);
     }
     if (fclose(s->f) != 0 && !rc) { fl_err("close error on %s", s->path); rc = 1; }
     s->f = NULL;
@@ -549,7 +532,7 @@ int fastf_filter(const char *r1, const char *i1, const char *r2, const char *out
     static const char *const outname[3] = {"I1.fastq.gz", "R1.fastq.gz", "R2.fastq.gz"};
     int rc = 1;
     memset(src_s, 0, sizeof src_s); memset(sink_s, 0, sizeof sink_s);
-    if (whitelist && wl_load(&wl, whitelist, len_cellbarcode, 1)) goto done;
+    if (whitelist && fl_wl_load(&wl, whitelist, len_cellbarcode, 1)) goto done;
     for (int f = 0; f < 3; f++) {
         if (!in[f]) continue;
         if (fastf_fq_src_open(&src_s[f], in[f])) goto done;
@@ -557,15 +540,15 @@ int fastf_filter(const char *r1, const char *i1, const char *r2, const char *out
     }
     for (int f = 0; f < 3; f++) {
         if (!in[f]) continue;
-        if (sink_open(&sink_s[f], dir, outname[f], paths[f], sizeof paths[f])) goto done;
+        if (fl_sink_open(&sink_s[f], dir, outname[f], paths[f], sizeof paths[f])) goto done;
         sink[f] = &sink_s[f];
     }
     if (fl_process(src, in, sink, &wl, len_cellbarcode, seed, rate, all_cells, n_reads, n_kept)) goto done;
     rc = 0;
-    for (int f = 0; f < 3; f++) if (sink[f] && sink_close(sink[f])) rc = 1;
+    for (int f = 0; f < 3; f++) if (sink[f] && fl_sink_close(sink[f])) rc = 1;
 done:
     for (int f = 0; f < 3; f++) { if (sink[f]) { if (sink[f]->f) fclose(sink[f]->f); } if (src[f]) fastf_fq_src_close(src[f]); }
-    wl_free(&wl);
+    fl_wl_free(&wl);
     return rc;
 }
 
@@ -600,7 +583,7 @@ void fastF(gzFile file_in[3], gzFile file_out[3], node *tree_whitelist, unsigned
         exit(1);
     }
     free(v);
-    wl_free(&wl);
+    fl_wl_free(&wl);
 }
 
 /* ------------------------------------------------------------------ */
@@ -623,11 +606,11 @@ static void fl_usage(void)
 
 typedef struct { const char *i1, *r1, *r2, *out, *wl; int32_t len; int32_t seed; float rate; int all; } fl_args;
 
-static int dir_writable(const char *dir, const char *const names[3], const int want[3])
+int fl_dir_writable(const char *dir, const char *const names[], const int want[], int n)
 {
     struct stat st;
     if (stat(dir, &st) != 0 || !S_ISDIR(st.st_mode) || access(dir, W_OK | X_OK) != 0) return 0;
-    for (int f = 0; f < 3; f++) {
+    for (int f = 0; f < n; f++) {
         if (!want[f]) continue;
         char p[4096];
         snprintf(p, sizeof p, "%s/%s", dir, names[f]);
@@ -675,7 +658,7 @@ int cmd_filter(int argc, const char **argv)
     const char *in[3] = {A.i1, A.r1, A.r2};
     static const char *const outname[3] = {"I1.fastq.gz", "R1.fastq.gz", "R2.fastq.gz"};
     const int want[3] = {A.i1 != NULL, 1, A.r2 != NULL};
-    if (!dir_writable(A.out, outname, want)) {
+    if (!fl_dir_writable(A.out, outname, want, 3)) {
         fprintf(stderr, "\x1b[31mError:\x1b[0m cannot write the outputs into directory %s (gzopen would return NULL; refused)\n", A.out);
         exit(1);
     }
@@ -689,11 +672,11 @@ int cmd_filter(int argc, const char **argv)
     if (A.wl != NULL) {
         printf("Reading whitelist...\n");
         fl_wl probe; memset(&probe, 0, sizeof probe);
-        const int r = wl_load(&probe, A.wl, (uint32_t)A.len, 0);
+        const int r = fl_wl_load(&probe, A.wl, (uint32_t)A.len, 0);
         if (r == 2) { printf("\x1b[31mError:\x1b[0m opening %s!\n", A.wl); exit(1); }                /* get_row, filter.c:186-190 */
         if (r) { fprintf(stderr, "\x1b[31mError:\x1b[0m %s\n", fastf_last_error()); exit(1); }
         printf("nrow = %d\n", (int)probe.nrow);
-        wl_free(&probe);
+        fl_wl_free(&probe);
     } else {
         printf("Subsample fastq files directly without cell barcode whitelist...\n");
     }

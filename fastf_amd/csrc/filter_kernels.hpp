@@ -109,6 +109,47 @@ __device__ __forceinline__ u64 flt_nl_at(const FltWin& w, const FltState* fs, u6
     return fs->carry[j & 3] + FLT_HDR - w.a;                 // wraps below zero only for a record that starts before the buffer
 }
 
+// the record of read r (its last '\n' lies in the window): buffer offsets of its four lines, the end of its qual line and its
+// output bytes.  false: the read begins before the buffer (the error word is set, *rc stays as it was)
+__device__ __forceinline__ bool flt_rec_lines(const FltWin& w, FltState* fs, u64 n0, u64 r, FltRec* rc) {
+    const u64 buf_end = FLT_HDR + w.len;
+    const u64 e0 = r ? flt_nl_at(w, fs, n0, 4 * r - 1) + 1 : FLT_HDR - w.a;   // read 0 begins at global offset 0 (a = 0)
+    const u64 e1 = flt_nl_at(w, fs, n0, 4 * r) + 1, e2 = flt_nl_at(w, fs, n0, 4 * r + 1) + 1;
+    const u64 e3 = flt_nl_at(w, fs, n0, 4 * r + 2) + 1, q = flt_nl_at(w, fs, n0, 4 * r + 3);
+    if (e0 > buf_end || e1 > buf_end || e2 > buf_end || e3 > buf_end) {   // wrapped: begins before the buffer
+        atomicOr(&fs->err, FLT_ERR_REC_START);
+        atomicMin((unsigned long long*)&fs->err_rec, (unsigned long long)r);
+        return false;
+    }
+    const u64 e = q + (q + w.a - FLT_HDR == w.tv ? 0 : 1);
+    *rc = FltRec{(u32)e0, (u32)e1, (u32)e2, (u32)e3, (u32)e, (u32)((e2 - e0) + 2 + (e - e3))};
+    return true;
+}
+
+// the DNA-form key of the first w.L bytes of the record's sequence line; 0: the read takes the escape path
+__device__ __forceinline__ u64 flt_rec_key(const FltWin& w, const FltRec& rc) {
+    if (w.L > FQ_MAX_DNA) return 0;
+    const u32* p = reinterpret_cast<const u32*>(w.buf + (rc.s1 & ~3u));
+    u32 x[9];
+#pragma unroll
+    for (int t = 0; t < 9; t++) x[t] = p[t];
+    return fq_pack_dna(x, rc.s1 & 3u, rc.s2 - rc.s1, w.L);
+}
+
+// where `key` stands among the sorted whitelist keys; w.n_wl: it is not among them
+__device__ __forceinline__ u64 flt_wl_find(const FltWin& w, u64 key) {
+    u64 lo = 0, hi = w.n_wl;
+    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (w.wl[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo < w.n_wl && w.wl[lo] == key ? lo : w.n_wl;
+}
+
+// record i of the window (sequence line at buffer offset s1) onto the host's list
+__device__ __forceinline__ void flt_escape(const FltWin& w, FltState* fs, u32 i, u32 s1) {
+    const u32 k = atomicAdd(&fs->n_esc, 1u);
+    if (k < w.esc_cap) w.esc[k] = FltEsc{i, s1};
+    else atomicOr(&fs->err, FLT_ERR_ESCAPES);
+}
+
 // one lane per read of the window: the record table, its output length and its keep decision
 __global__ __launch_bounds__(256) void flt_rec_kernel(FltWin w, FltState* __restrict__ fs) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
@@ -117,40 +158,15 @@ __global__ __launch_bounds__(256) void flt_rec_kernel(FltWin w, FltState* __rest
     const u64 n0 = fs->n0;
     u32 keep = 0;
     FltRec rc = {0, 0, 0, 0, 0, 0};
-    if (r < w.limit) {
-        const u64 buf_end = FLT_HDR + w.len;
-        const u64 e0 = r ? flt_nl_at(w, fs, n0, 4 * r - 1) + 1 : FLT_HDR - w.a;   // read 0 begins at global offset 0 (a = 0)
-        const u64 e1 = flt_nl_at(w, fs, n0, 4 * r) + 1, e2 = flt_nl_at(w, fs, n0, 4 * r + 1) + 1;
-        const u64 e3 = flt_nl_at(w, fs, n0, 4 * r + 2) + 1, q = flt_nl_at(w, fs, n0, 4 * r + 3);
-        if (e0 > buf_end || e1 > buf_end || e2 > buf_end || e3 > buf_end) {   // wrapped: begins before the buffer
-            atomicOr(&fs->err, FLT_ERR_REC_START);
-            atomicMin((unsigned long long*)&fs->err_rec, (unsigned long long)r);
-        } else {
-            const u64 e = q + (q + w.a - FLT_HDR == w.tv ? 0 : 1);
-            rc = FltRec{(u32)e0, (u32)e1, (u32)e2, (u32)e3, (u32)e, (u32)((e2 - e0) + 2 + (e - e3))};
-            if (w.mode == 1) {
-                keep = (w.bitmap[r >> 5] >> (r & 31)) & 1u;
-            } else if (flt_draw_passes(w.draws[i], w.rate)) {
-                if (w.all) keep = 1;
-                else {
-                    u64 key = 0;
-                    if (w.L <= FQ_MAX_DNA) {
-                        const u32* p = reinterpret_cast<const u32*>(w.buf + (e1 & ~3ull));
-                        u32 x[9];
-#pragma unroll
-                        for (int t = 0; t < 9; t++) x[t] = p[t];
-                        key = fq_pack_dna(x, (u32)(e1 & 3), e2 - e1, w.L);
-                    }
-                    if (key) {
-                        u64 lo = 0, hi = w.n_wl;
-                        while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (w.wl[mid] < key) lo = mid + 1; else hi = mid; }
-                        keep = lo < w.n_wl && w.wl[lo] == key;
-                    } else {
-                        const u32 k = atomicAdd(&fs->n_esc, 1u);
-                        if (k < w.esc_cap) w.esc[k] = FltEsc{(u32)i, (u32)e1};
-                        else atomicOr(&fs->err, FLT_ERR_ESCAPES);
-                    }
-                }
+    if (r < w.limit && flt_rec_lines(w, fs, n0, r, &rc)) {
+        if (w.mode == 1) {
+            keep = (w.bitmap[r >> 5] >> (r & 31)) & 1u;
+        } else if (flt_draw_passes(w.draws[i], w.rate)) {
+            if (w.all) keep = 1;
+            else {
+                const u64 key = flt_rec_key(w, rc);
+                if (key) keep = flt_wl_find(w, key) < w.n_wl;
+                else flt_escape(w, fs, (u32)i, rc.s1);
             }
         }
     }
@@ -260,7 +276,8 @@ struct fastf_fltdev {
     size_t window = 0; u32 n_tiles_max = 0; u64 rec_cap = 0;
     DevBuf d_buf, d_state, d_fstate, d_tile_cnt, d_tile_last, d_tile_base, d_tile_ls, d_pos, d_rec, d_len, d_off, d_bsum,
            d_draws, d_cs, d_esc, d_hit, d_wl, d_bitmap, d_out;
-    u64 n_wl = 0, bitmap_words = 0;
+    DevBuf d_hits, d_kept, d_cellrate;              // fqcap (fqcap_kernels.hpp): per whitelist key, guard words behind
+    u64 n_wl = 0, bitmap_words = 0, fcp_keys = ~0ull;   // fcp_keys: the key count hits / kept / rate were sized for
     unsigned char* h_out = nullptr;                 // pinned: the compacted window
     FltEsc* h_esc = nullptr;                        // pinned
     FqState* h_st = nullptr; FltState* h_fs = nullptr;   // pinned snapshots
@@ -276,7 +293,7 @@ extern "C" void fastf_fltdev_destroy(fastf_fltdev_t* p) FASTF_TRY {
     if (p->s) (void)hipStreamSynchronize(p->s);
     DevBuf* all[] = {&p->d_buf, &p->d_state, &p->d_fstate, &p->d_tile_cnt, &p->d_tile_last, &p->d_tile_base, &p->d_tile_ls, &p->d_pos,
                      &p->d_rec, &p->d_len, &p->d_off, &p->d_bsum, &p->d_draws, &p->d_cs, &p->d_esc, &p->d_hit, &p->d_wl,
-                     &p->d_bitmap, &p->d_out};
+                     &p->d_bitmap, &p->d_out, &p->d_hits, &p->d_kept, &p->d_cellrate};
     for (DevBuf* b : all) b->release();
     if (p->h_out) (void)hipHostFree(p->h_out);
     if (p->h_esc) (void)hipHostFree(p->h_esc);
@@ -408,9 +425,11 @@ static int flt_bitmap_cover(fastf_fltdev* p, u64 reads) {
 // The decisions of the parsed window.  mode 0 (R1): cs = the start states of its ceil(n_rec / FLT_CHUNK) draw chunks (31 words
 // each, the first at read r_lo); *esc / *n_esc: the reads whose barcode the host decides (pinned, valid until the next call).
 // mode 1 (I1 / R2): the keep bitmap decides.
-extern "C" int fastf_fltdev_decide(fastf_fltdev_t* p, int mode, int all, uint32_t L, float rate, const uint32_t* cs,
-                                   const fastf_flt_esc_t** esc, uint32_t* n_esc) FASTF_TRY {
-    if (!p) return set_err("null argument");
+// (launch_rec: the record kernel of the window onto the stream — filter's here, fqcap's in fqcap_kernels.hpp)
+template <typename LaunchRec>
+static int flt_decide_with(fastf_fltdev* p, int mode, int all, uint32_t L, float rate, const uint32_t* cs,
+                           const fastf_flt_esc_t** esc, uint32_t* n_esc, LaunchRec launch_rec) {
+    if (!p || !n_esc) return set_err("null argument");
     HIP_OK(hipSetDevice(p->device));
     FltWin& w = p->w;
     hipStream_t s = p->s;
@@ -426,7 +445,7 @@ extern "C" int fastf_fltdev_decide(fastf_fltdev_t* p, int mode, int all, uint32_
         HIP_OK(hipMemcpyAsync(p->d_cs.p, cs, nch * FLT_RAND_DEG * sizeof(u32), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(flt_draw_kernel, dim3((u32)((nch + 255) / 256)), dim3(256), 0, s, (const u32*)p->d_cs.p, w.n_rec, (u32*)p->d_draws.p);
     }
-    hipLaunchKernelGGL(flt_rec_kernel, dim3((u32)((w.n_rec + 255) / 256)), dim3(256), 0, s, w, fs);
+    launch_rec(w, fs, dim3((u32)((w.n_rec + 255) / 256)), s);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(p->h_fs, fs, sizeof(FltState), hipMemcpyDeviceToHost, s));
     if (flt_sync(p)) return 1;
@@ -438,6 +457,13 @@ extern "C" int fastf_fltdev_decide(fastf_fltdev_t* p, int mode, int all, uint32_
     }
     *n_esc = f.n_esc;
     return 0;
+}
+
+extern "C" int fastf_fltdev_decide(fastf_fltdev_t* p, int mode, int all, uint32_t L, float rate, const uint32_t* cs,
+                                   const fastf_flt_esc_t** esc, uint32_t* n_esc) FASTF_TRY {
+    return flt_decide_with(p, mode, all, L, rate, cs, esc, n_esc, [](const FltWin& w, FltState* fs, dim3 grid, hipStream_t s) {
+        hipLaunchKernelGGL(flt_rec_kernel, grid, dim3(256), 0, s, w, fs);
+    });
 } FASTF_CATCH_INT
 
 // The window's output: the host's hits (reads i of the window, pinned or not) join the kept reads; then scan, gather and the

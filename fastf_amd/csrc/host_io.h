@@ -138,8 +138,8 @@ int  fastf_fqparse_scatter(fastf_fqparse_t *p, const uint64_t *rk, size_t n, uin
 int  fastf_fqparse_fetch_keys(fastf_fqparse_t *p, uint64_t *dst, uint64_t r_lo, uint64_t n);
 
 /* filter (filter_cmds.c): the device path of FASTQ triples (filter_kernels.hpp) */
-typedef struct { uint32_t i, s1; } fastf_flt_esc_t;      /* read i of the window: its sequence line (buffer offset s1) goes to the host */
-typedef struct fastf_fltdev fastf_fltdev_t;
+/* (fastf_flt_esc_t — read i of the window: its sequence line (buffer offset s1) goes to the host — and fastf_fltdev_t are declared
+ * in fastf_amd.h, whose fqcap seam works on the same handle) */
 int  fastf_fltdev_create(int device, size_t window_bytes, fastf_fltdev_t **out);
 void fastf_fltdev_destroy(fastf_fltdev_t *p);
 int  fastf_fltdev_set_whitelist(fastf_fltdev_t *p, const uint64_t *keys, size_t n);

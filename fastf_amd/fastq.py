@@ -49,6 +49,28 @@ def filter(r1, i1=None, r2=None, out=".", whitelist=None, len_cb: int = 16, seed
     return nr.value, nk.value
 
 
+def fqcap(r1, i1=None, r2=None, out=".", whitelist=None, len_cb: int = 16, seed: int = 926, rate: float = 2.0, cap: int = 0):
+    """`fastF fqcap -R r1 [-I i1] [-r r2] -o out -w whitelist -n cap [-t rate] -l len_cb -s seed`: filter with every cell of the
+    whitelist capped at `cap` reads (in expectation; include/fastf_amd.h has the definition).  Writes out/R1.fastq.gz (and I1 /
+    R2) and out/fqcap_cells.tsv.gz and returns (reads in R1, reads matched, reads kept).  rate 2.0: no thinning beside the cap"""
+    if whitelist is None:
+        raise ValueError("fqcap needs a whitelist")
+    if int(cap) < 1 or int(cap) >= 1 << 64:
+        raise ValueError("cap must be a whole number of reads, at least 1")
+    if len_cb < 0:
+        raise ValueError("len_cb must not be negative")
+    enc = lambda p: None if p is None else os.fspath(p).encode()  # noqa: E731
+    nr, nm, nk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _lib.check(_lib.lib().fastf_fqcap(enc(r1), enc(i1), enc(r2), enc(out), enc(whitelist), len_cb, seed % (1 << 32), float(rate),
+                                      int(cap), C.byref(nr), C.byref(nm), C.byref(nk)))
+    return nr.value, nm.value, nk.value
+
+
+def fqcap_rate(cap: int, hits: int, rate: float = 2.0) -> float:
+    """the keep rate of a cell with `hits` matched reads under the cap and the global rate (fastf_fqcap_rate)"""
+    return float(_lib.lib().fastf_fqcap_rate(int(cap), int(hits), float(rate)))
+
+
 def filter_draws(seed: int, first: int, n: int, device: bool = True) -> np.ndarray:
     """rand() outputs first .. first + n - 1 after srand(seed) (uint32): as filter's device kernel computes them, or
     (device=False) by the host's jump-ahead and recurrence"""

@@ -106,6 +106,56 @@ int fastf_filter_draws_host(uint32_t seed, uint64_t first, uint64_t n, uint32_t 
 uint32_t fastf_filter_rand_at(uint32_t seed, uint64_t index);
 int fastf_filter_draw_passes(uint32_t r, float rate);
 
+/* --- fqcap: the FASTQ triple with every cell capped at N reads (fqcap_cmds.c, fqcap_kernels.hpp; not a command of the reference).
+ * filter with a rate per cell in place of the one global rate.  The definition:
+ *   cell of a read   the first len_cellbarcode bytes of its R1 sequence line exactly as filter's whitelist test sees them: strncmp
+ *                    semantics, a shorter line taken with its '\n', cut at a NUL.  A read is MATCHED iff `filter -w` would match
+ *                    it; two matched reads are of the same cell iff those bytes are equal.  Duplicate whitelist lines and lines
+ *                    that share their first len_cellbarcode bytes are one cell.
+ *   h[k]             the matched R1 reads of cell k, counted over the whole file before any draw (the order of cap, which counts
+ *                    before xf).
+ *   draw of read i   output i of rand() after srand(seed), consumed by every R1 read, matched or not: filter's stream, so that
+ *                    the two commands are coupled by the seed.
+ *   rate of cell k   t = the rate given, 2.0f when none is (every draw passes: no global thinning).  rate_k = t where h[k] <= N,
+ *                    min(t, (float)((double)N / (double)h[k])) otherwise: fastf_fqcap_rate(N, h[k], t).  Read i of cell k is kept
+ *                    iff fastf_filter_draw_passes(draw_i, rate_k), the draw that rounds to 1.0 included.  Bernoulli per read, as
+ *                    cap: "at most N" holds in expectation.
+ *   mates            I1 and R2 follow R1's keep bitmap exactly as in filter (shorter or longer mates, a last line without '\n').
+ *   outputs          <out_dir>/R1.fastq.gz (and I1 / R2 when given) as filter writes them, and <out_dir>/fqcap_cells.tsv.gz: the
+ *                    line "barcode\treads\tkept", then one row per cell with h > 0 — its bytes, h, reads kept — ascending by the
+ *                    bytes of the barcode (memcmp, the shorter first), DNA-form and other cells in one order.  A byte of a barcode
+ *                    outside 0x21 .. 0x7e, and the backslash, is written \xHH (upper-case hex).  sum(kept) = *n_kept.
+ * Consequences: with N >= max h the three FASTQ outputs hold the bytes of `filter -w ... -t t` with the same seed; for any N the
+ * kept reads are a subset of that filter's.
+ * Refused with a message (1 returned, the output directory untouched): no R1, no whitelist, cap 0, a negative length, a directory
+ * that cannot be written, filter's declared divergences in R1 (a line longer than 1023 bytes, a file that ends partway through a
+ * read, corrupt input) and an R1 of 2^32 reads or more (the per-cell counters are 32-bit).  A refusal that only a mate file
+ * shows comes after R1 was written: the outputs made so far are removed. --- */
+int cmd_fqcap(int argc, const char **argv);     /* argv[0] == "fqcap"; filter's option dialect, -n N required, no -a */
+int fastf_fqcap(const char *r1, const char *i1, const char *r2, const char *out_dir, const char *whitelist, uint32_t len_cellbarcode,
+                uint32_t seed, float rate, uint64_t cap, uint64_t *n_reads, uint64_t *n_matched, uint64_t *n_kept);
+float fastf_fqcap_rate(uint64_t cap, uint64_t hits, float t);
+/* The device seam of fqcap on filter's window handle (host_io.h: fastf_fltdev_create / set_whitelist / reset / parse / emit / end),
+ * one caller-supplied window at a time.  hits[], kept[] and rate[] hold one word per whitelist key and 16 guard words behind
+ * (0xa5a5a5a5), which no kernel touches.
+ *   begin      after set_whitelist: hits[] and kept[] cleared, rate[] and the guards filled with the guard word
+ *   count      pass 0 of the parsed window: hits[k] += its matched reads of key k; *esc / *n_esc: every read of the window whose
+ *              barcode is not DNA-form (pinned, valid until the next call); the window is done (no emit follows)
+ *   set_rates  n = the key count; kept[] cleared
+ *   decide     pass 1 of the parsed window: fastf_fltdev_decide's R1 mode with the draw tested against t, then against rate[k];
+ *              kept[k] += the reads kept; *esc: the reads that passed t and are not DNA-form; fastf_fltdev_emit follows
+ *   draws      the rand() outputs of the window decided last
+ *   read       which = 0 hits[], 1 kept[], 2 the bits of rate[]; n_words <= keys + 16 */
+typedef struct fastf_fltdev fastf_fltdev_t;
+typedef struct { uint32_t i, s1; } fastf_flt_esc_t;     /* read i of the window, its sequence line at buffer offset s1 */
+int fastf_fcpdev_begin(fastf_fltdev_t *p);
+int fastf_fcpdev_count(fastf_fltdev_t *p, uint32_t len_cellbarcode, const fastf_flt_esc_t **esc, uint32_t *n_esc);
+int fastf_fcpdev_set_rates(fastf_fltdev_t *p, const float *rate, size_t n);
+int fastf_fcpdev_decide(fastf_fltdev_t *p, uint32_t len_cellbarcode, float t, const uint32_t *chunk_states,
+                        const fastf_flt_esc_t **esc, uint32_t *n_esc);
+int fastf_fcpdev_draws(fastf_fltdev_t *p, uint32_t *out, uint64_t n);
+int fastf_fcpdev_read(fastf_fltdev_t *p, int which, uint32_t *out, size_t n_words);
+
 /* --- sweep: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM (sweep_cmds.c; not a command of the
  * reference).  Per point <out_dir>/c<rate_cell>_r<rate_depth>/ (rates printed %.3f) holds matrix.mtx.gz, barcodes.tsv.gz and
  * features.tsv.gz with the bytes bam2db() writes for that point; <out_dir>/sweep.tsv holds a header and one row per point, cell
