@@ -7,9 +7,9 @@ only plumbing here (device memory, streams, torch.distributed over RCCL).
 """
 from ._lib import build, lib, lib_path, FastfError  # noqa: F401
 from .engine import Engine, Lists, PinnedBatch, pack_records, draw_threshold, mt_draws  # noqa: F401
-from .fastq import freq, freq_text, filter, filter_draws, filter_rand_at, fqcap, fqcap_rate  # noqa: F401
+from .fastq import freq, freq_text, filter, filter_draws, filter_rand_at, fqcap, fqcap_rate, fqcells, fqcells_call  # noqa: F401
 from . import cap  # noqa: F401  (the module: cap.cap() is the command, as sweep.sweep() is)
 from . import level  # noqa: F401  (the module: level.level() is the command)
 
 __all__ = ["build", "lib", "lib_path", "FastfError", "Engine", "Lists", "PinnedBatch", "pack_records",
-           "draw_threshold", "mt_draws", "freq", "freq_text", "filter", "filter_draws", "filter_rand_at", "fqcap", "fqcap_rate", "cap", "level"]
+           "draw_threshold", "mt_draws", "freq", "freq_text", "filter", "filter_draws", "filter_rand_at", "fqcap", "fqcap_rate", "fqcells", "fqcells_call", "cap", "level"]

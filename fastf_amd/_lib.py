@@ -77,6 +77,11 @@ class TagHistResult(C.Structure):
                 ("pair_count", C.POINTER(C.c_uint64)), ("pair_first", C.POINTER(C.c_uint64)), ("n_pairs", C.c_size_t)]
 
 
+class FqcellsSummary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "counted", "other", "barcodes", "umis", "rule", "arg", "threshold", "called",
+                                          "called_reads", "called_umis")]
+
+
 class MT(C.Structure):
     _fields_ = [("s", C.c_uint32 * 624), ("idx", C.c_int)]
 
@@ -109,6 +114,8 @@ ABI_SYMBOLS = [
     # fqcap
     "fastf_fqcap", "fastf_fqcap_rate", "fastf_fcpdev_begin", "fastf_fcpdev_count", "fastf_fcpdev_set_rates", "fastf_fcpdev_decide",
     "fastf_fcpdev_draws", "fastf_fcpdev_read",
+    # fqcells
+    "fastf_fqcells", "fastf_fqcells_call", "fastf_fqcells_reduce", "fastf_fqcells_tile",
     # sweep
     "fastf_sweep", "fastf_sweep_parse_rates", "fastf_sweep_check_grid", "fastf_sweep_point_dir", "fastf_sweep_header",
     "fastf_sweep_cells_from_coo", "fastf_sweep_summary_row", "fastf_dev_mt_decisions_multi", "fastf_dev_cell_summary",
@@ -309,6 +316,12 @@ def lib():
                                   C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.fastf_fqcap_rate.argtypes = [u64, u64, C.c_float]
         L.fastf_fqcap_rate.restype = C.c_float
+    if hasattr(L, "fastf_fqcells") or not os.environ.get("FASTF_LIB_OVERRIDE"):         # (an A/B build from before fqcells)
+        L.fastf_fqcells.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, u64, C.POINTER(FqcellsSummary)]
+        L.fastf_fqcells_call.argtypes = [vp, vp, vp, sz, C.c_int, u64, vp, vp, C.POINTER(u64)]
+        L.fastf_fqcells_reduce.argtypes = [vp, vp, sz, C.c_uint32, vp, vp, vp, C.POINTER(sz)]
+        L.fastf_fqcells_tile.argtypes = []
+        L.fastf_fqcells_tile.restype = sz
     L.fastf_taghist_reserve_device.argtypes = [vp, sz]
     L.fastf_taghist_reserve_device.restype = vp
     L.fastf_taghist_stream.argtypes = [vp]

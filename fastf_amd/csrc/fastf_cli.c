@@ -1,5 +1,5 @@
 /* fastf_cli.c — `fastF` command line: dispatch table of the reference (main.c:404-443),
- * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract, sweep — bam2db over a grid of rates — cap — every cell downsampled to at most N reads — and level — every cell downsampled to at most M UMIs; the FASTQ ones: freq, filter and fqcap — filter with every cell capped at N reads). */
+ * with the subcommands this engine implements (the BAM ones: bam2db, crb, extract, sweep — bam2db over a grid of rates — cap — every cell downsampled to at most N reads — and level — every cell downsampled to at most M UMIs; the FASTQ ones: freq, filter, fqcap — filter with every cell capped at N reads — and fqcells — the cells of an R1 called by UMIs per barcode). */
 #include "fastf_amd.h"
 
 #include <stdio.h>
@@ -9,7 +9,7 @@
 
 extern int fastf_process_is_exiting_;
 struct cmd_struct { const char *cmd; int (*fn)(int, const char **); };
-static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"filter", cmd_filter}, {"fqcap", cmd_fqcap}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract}, {"sweep", cmd_sweep}, {"cap", cmd_cap}, {"level", cmd_level} };
+static const struct cmd_struct commands[] = { {"freq", cmd_freq}, {"filter", cmd_filter}, {"fqcap", cmd_fqcap}, {"fqcells", cmd_fqcells}, {"crb", cmd_crb}, {"bam2db", cmd_bam2db}, {"extract", cmd_extract}, {"sweep", cmd_sweep}, {"cap", cmd_cap}, {"level", cmd_level} };
 
 /* One command uses one GPU unless FASTF_DEVICES asks for more: hide the others from the HIP runtime before it loads,
  * so that its start-up (which opens every visible device) costs the same on an 8-GPU host as on a 1-GPU one.
@@ -31,6 +31,7 @@ int main(int argc, const char **argv)
                "    freq      cell barcode + UMI prefixes of an R1 FASTQ and their frequencies -> whitelist.txt\n"
                "    filter    FASTQ triples subsampled by cell barcode whitelist and read depth -> I1/R1/R2.fastq.gz\n"
                "    fqcap     FASTQ triples with every whitelisted cell capped at N reads -> I1/R1/R2.fastq.gz + fqcap_cells.tsv.gz\n"
+               "    fqcells   cells of an R1 FASTQ called by UMIs per cell barcode -> fqcells.tsv.gz + whitelist.txt for filter / fqcap -w\n"
                "    crb       CB/CR tags of a BAM and their frequencies -> gzip'ed rows\n"
                "    bam2db    BAM -> down-sampled, UMI-deduplicated gene x cell matrix (MI355X engine)\n"
                "    extract   frequencies of one BAM tag -> tag_summary.csv\n"

@@ -378,6 +378,30 @@ static void decode_dna_worker(void *vp, int w)
 
 static int tprof(void) { return getenv("FASTF_PROFILE") != NULL; }
 
+/* after the last window of a text of T bytes: the declared divergences (a line over FQ_MAX_LINE bytes, a file that ends after a header
+ * line) and the histogram's limit are refused; *n_reads = the reads of the file.  freq and fqcells (fastf_fq_dna_keys) share it. */
+static int fq_end_checks(fastf_fqparse_t *fp, uint64_t T, uint64_t *n_reads)
+{
+    uint64_t n_nl = 0, line_start = 0, err_rec = 0; uint32_t err = 0;
+    if (fastf_fqparse_end(fp, &n_nl, &line_start, &err, &err_rec)) return 1;
+    const int open_line = T > line_start;
+    if (!(err & FQ_ERR_LONG_LINE) && open_line && T - line_start > FQ_MAX_LINE) { err |= FQ_ERR_LONG_LINE; err_rec = n_nl / 4; }
+    if (err & FQ_ERR_LONG_LINE) {
+        fq_err("read %llu (line %llu of the file) has a line longer than %u bytes: gzgets(buf, 1024) would split it (refused)",
+               (unsigned long long)err_rec + 1, (unsigned long long)err_rec * 4 + 1, FQ_MAX_LINE);
+        return 1;
+    }
+    const uint64_t n_lines = n_nl + (uint64_t)open_line;
+    if (n_lines % 4 == 1) {
+        fq_err("the file ends after the header line of read %llu: it has no sequence line (the reference reads an "
+               "uninitialised buffer there; refused)", (unsigned long long)(n_lines / 4 + 1));
+        return 1;
+    }
+    *n_reads = (n_lines + 3) / 4;
+    if (*n_reads >= (1ull << 32) - 1) { fq_err("more than 2^32-2 reads"); return 1; }
+    return 0;
+}
+
 static int fq_run(fq_src *src, size_t len_cb, size_t len_umi, fq_result *res)
 {
     memset(res, 0, sizeof *res);
@@ -442,26 +466,7 @@ static int fq_run(fq_src *src, size_t len_cb, size_t len_umi, fq_result *res)
         }
     }
     const double t_parse_end = fq_now();
-    {
-        uint64_t n_nl = 0, line_start = 0, err_rec = 0; uint32_t err = 0;
-        if (fastf_fqparse_end(fp, &n_nl, &line_start, &err, &err_rec)) goto done;
-        const uint64_t T = a;
-        const int open_line = T > line_start;
-        if (!(err & FQ_ERR_LONG_LINE) && open_line && T - line_start > FQ_MAX_LINE) { err |= FQ_ERR_LONG_LINE; err_rec = n_nl / 4; }
-        if (err & FQ_ERR_LONG_LINE) {
-            fq_err("read %llu (line %llu of the file) has a line longer than %u bytes: gzgets(buf, 1024) would split it (refused)",
-                   (unsigned long long)err_rec + 1, (unsigned long long)err_rec * 4 + 1, FQ_MAX_LINE);
-            goto done;
-        }
-        const uint64_t n_lines = n_nl + (uint64_t)open_line;
-        if (n_lines % 4 == 1) {
-            fq_err("the file ends after the header line of read %llu: it has no sequence line (the reference reads an "
-                   "uninitialised buffer there; refused)", (unsigned long long)(n_lines / 4 + 1));
-            goto done;
-        }
-        res->n_reads = (n_lines + 3) / 4;
-        if (res->n_reads >= (1ull << 32) - 1) { fq_err("more than 2^32-2 reads"); goto done; }
-    }
+    if (fq_end_checks(fp, a, &res->n_reads)) goto done;
     const double th0 = fq_now();
     if (res->n_reads == 0) { rc = 0; goto done; }                   /* no reads: an empty whitelist */
     if (fastf_fqparse_scatter(fp, rk.rk, rk.n, res->n_reads)) goto done;
@@ -534,6 +539,68 @@ done:
     if (hist) fastf_taghist_destroy(hist);
     for (int i = 0; i < 2; i++) fastf_pinned_free(stage[i]);
     free(rk.rk);
+    return rc;
+}
+
+/* fq_run's windows for a caller that wants the DNA-form keys alone (fqcells): the same source, staging, device
+ * parse and end-of-file refusals (fq_end_checks), with L = len_cb + len_umi <= 31.  A read that is not DNA-form leaves key 0 in the histogram's key
+ * array: no escape list comes to the host, nothing is interned or scattered.  The n_reads keys are pushed into hist (single-tag
+ * mode); *n_other = the reads the device put on its escape lists.  t[0..4]: inflate/read, H2D, parse, pipeline wall, push (seconds). */
+int fastf_fq_dna_keys(fq_src *src, uint32_t L, fastf_taghist_t *hist, uint64_t *n_reads, uint64_t *n_other, uint64_t *n_bytes, double t[5])
+{
+    const double t0 = fq_now();
+    double t_fill = 0, h2d_ms = 0, parse_ms = 0;
+    const size_t W = fastf_fq_window_bytes();
+    unsigned char *stage[2] = {NULL, NULL};
+    fastf_fqparse_t *fp = NULL;
+    int rc = 1;
+    uint64_t win_len[2] = {0, 0};
+    uint64_t a = 0, known_nl = 0, b_known = 0, b_end[2] = {0, 0}, other = 0;
+    *n_reads = 0; *n_other = 0;
+    if (L < 1 || L > FQ_MAX_DNA) { fq_err("DNA-form keys hold 1 to %u bases, not %u", FQ_MAX_DNA, L); return 1; }
+    for (int i = 0; i < 2; i++) {
+        stage[i] = (unsigned char *)fastf_pinned_alloc(FQ_HDR + W + 64);
+        if (!stage[i]) goto done;
+        memset(stage[i], 0, FQ_HDR);
+    }
+    if (fastf_fqparse_create(hist, W, L, &fp)) goto done;
+    for (uint64_t k = 0, last = 0; !last; k++) {
+        const int par = (int)(k & 1);
+        uint32_t ne = 0; uint64_t nl = 0;
+        if (k >= 2) {                                                  /* window k - 2 had this staging */
+            if (fastf_fqparse_wait_count(fp, par, &ne, &nl, &h2d_ms, &parse_ms)) goto done;
+            other += ne; known_nl = nl; b_known = b_end[par];
+        }
+        if (k) memcpy(stage[par], stage[par ^ 1] + win_len[par ^ 1], FQ_HDR);
+        const double tf = fq_now();
+        const long n = fastf_fq_src_fill(src, stage[par] + FQ_HDR, W);
+        t_fill += fq_now() - tf;
+        if (n < 0) goto done;
+        last = (size_t)n < W;
+        const uint64_t bound = (known_nl + (a + (uint64_t)n - b_known)) / 4 + 2;    /* as fq_run: every read takes four '\n' */
+        if (fastf_fqparse_zero_keys(fp, bound) || fastf_fqparse_submit(fp, stage[par], (size_t)n, a, (int)last, bound)) goto done;
+        win_len[par] = (uint64_t)n;
+        a += (uint64_t)n;
+        b_end[par] = a;
+    }
+    for (int q = 0; q < 2; q++) {
+        uint32_t ne = 0;
+        if (fastf_fqparse_wait_count(fp, q, &ne, NULL, &h2d_ms, &parse_ms)) goto done;
+        other += ne;
+    }
+    const double t_parse_end = fq_now();
+    if (fq_end_checks(fp, a, n_reads)) goto done;
+    if (*n_reads) {
+        uint64_t *d = fastf_taghist_reserve_device(hist, *n_reads);
+        if (!d || fastf_taghist_push_device(hist, d, *n_reads)) goto done;
+    }
+    *n_other = other;
+    if (n_bytes) *n_bytes = a;
+    if (t) { t[0] = t_fill; t[1] = h2d_ms * 1e-3; t[2] = parse_ms * 1e-3; t[3] = t_parse_end - t0; t[4] = fq_now() - t_parse_end; }
+    rc = 0;
+done:
+    fastf_fqparse_destroy(fp);
+    for (int i = 0; i < 2; i++) fastf_pinned_free(stage[i]);
     return rc;
 }
 

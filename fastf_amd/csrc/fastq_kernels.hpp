@@ -274,6 +274,7 @@ struct fastf_fqparse {
     int submitted[2] = {0, 0};
     u32 next_parity = 0;
     u64 key_reserved = 0;                          // the last key_bound / key_cap the key array was reserved for
+    u64 key_zeroed = 0;                            // fastf_fqparse_zero_keys: keys [0, key_zeroed) were cleared before any parse wrote there
 };
 static constexpr size_t FQ_RK_CHUNK = (size_t)1 << 20;
 
@@ -442,5 +443,41 @@ extern "C" int fastf_fqparse_fetch_keys(fastf_fqparse_t* p, uint64_t* dst, uint6
     HIP_OK(hipStreamSynchronize(p->h->ws->s_compute));
     if (n == 0) return 0;
     return copy_d2h(dst, (const u64*)p->h->d_k1.p + p->h->n + r_lo, (size_t)n * sizeof(u64));
+} FASTF_CATCH_INT
+
+// ---- the DNA-form keys alone (fqcells): a read that is not DNA-form keeps key 0, "absent", and nothing goes to the host ----
+// Before fastf_fqparse_submit with the same key_bound: the keys up to key_bound that no earlier call cleared are set to 0 on the
+// histogram's stream, so that a read the parse puts on the escape list leaves 0 in the key array (freq overwrites those slots with
+// fastf_fqparse_scatter; here nobody does).  A growth of the key array carries the cleared keys along (th_grow keeps the reserved ones).
+extern "C" int fastf_fqparse_zero_keys(fastf_fqparse_t* p, uint64_t key_bound) FASTF_TRY {
+    if (!p) return set_err("null argument");
+    HIP_OK(hipSetDevice(p->device));
+    u64* keys = (u64*)fastf_taghist_reserve_device(p->h, key_bound);
+    if (!keys) return 1;
+    if (key_bound > p->key_zeroed) {
+        HIP_OK(hipMemsetAsync(keys + p->key_zeroed, 0, (size_t)(key_bound - p->key_zeroed) * sizeof(u64), p->h->ws->s_compute));
+        p->key_zeroed = key_bound;
+    }
+    return 0;
+} FASTF_CATCH_INT
+
+// fastf_fqparse_wait without the copy of the escape list: *n_esc = how many reads of that window were not DNA-form
+extern "C" int fastf_fqparse_wait_count(fastf_fqparse_t* p, int parity, uint32_t* n_esc, uint64_t* n_nl, double* h2d_ms,
+                                        double* parse_ms) FASTF_TRY {
+    if (!p || !n_esc || parity < 0 || parity > 1) return set_err("fastf_fqparse_wait_count: bad argument");
+    *n_esc = 0;
+    if (!p->submitted[parity]) return 0;
+    HIP_OK(hipSetDevice(p->device));
+    HIP_OK(hipEventSynchronize(p->ev_p1[parity]));
+    p->submitted[parity] = 0;
+    const FqState st = p->h_snap[parity];
+    if (n_nl) *n_nl = st.n_nl;
+    if (st.err & (FQ_ERR_PENDING | FQ_ERR_ESCAPES | FQ_ERR_KEY_CAP))
+        return set_err("fastq parse: internal capacity exceeded (error bits %#x)", st.err);
+    float ms = 0;
+    if (h2d_ms && hipEventElapsedTime(&ms, p->ev_h2d0[parity], p->ev_h2d1[parity]) == hipSuccess) *h2d_ms += ms;
+    if (parse_ms && hipEventElapsedTime(&ms, p->ev_p0[parity], p->ev_p1[parity]) == hipSuccess) *parse_ms += ms;
+    *n_esc = st.n_esc;
+    return 0;
 } FASTF_CATCH_INT
 #endif

@@ -136,6 +136,15 @@ int  fastf_fqparse_wait(fastf_fqparse_t *p, int parity, const fastf_fq_esc_t **e
 int  fastf_fqparse_end(fastf_fqparse_t *p, uint64_t *n_nl, uint64_t *line_start, uint32_t *err, uint64_t *err_rec);
 int  fastf_fqparse_scatter(fastf_fqparse_t *p, const uint64_t *rk, size_t n, uint64_t key_cap);
 int  fastf_fqparse_fetch_keys(fastf_fqparse_t *p, uint64_t *dst, uint64_t r_lo, uint64_t n);
+/* fqcells: the DNA-form keys alone — the key range cleared ahead of a submit, a wait that fetches no escape list */
+int  fastf_fqparse_zero_keys(fastf_fqparse_t *p, uint64_t key_bound);
+int  fastf_fqparse_wait_count(fastf_fqparse_t *p, int parity, uint32_t *n_esc, uint64_t *n_nl, double *h2d_ms, double *parse_ms);
+/* tag_hist.hpp: level 1 of a single-tag finish left on the device (ascending distinct keys, u32 counts; the handle's arrays) */
+int  fastf_taghist_finish_device(fastf_taghist_t *h, const uint64_t **d_keys, const uint32_t **d_counts, uint64_t *m1);
+/* fqcells_kernels.hpp: the histogram's distinct CB+UMI keys -> the per-barcode table in malloc'ed host arrays (*bc, *reads, *umis:
+ * n_rows entries, ascending by barcode key; the caller frees them).  *m1 = distinct keys, *reduce_ms = events around the whole reduce */
+int  fastf_fqcells_table(fastf_taghist_t *h, uint32_t len_umi, uint64_t **bc, uint64_t **reads, uint32_t **umis, size_t *n_rows,
+                         uint64_t *m1, double *reduce_ms);
 
 /* filter (filter_cmds.c): the device path of FASTQ triples (filter_kernels.hpp) */
 /* (fastf_flt_esc_t — read i of the window: its sequence line (buffer offset s1) goes to the host — and fastf_fltdev_t are declared
@@ -170,6 +179,9 @@ int    fastf_fq_src_open(fq_src *s, const char *path) __attribute__((visibility(
 void   fastf_fq_src_close(fq_src *s) __attribute__((visibility("hidden")));
 long   fastf_fq_src_fill(fq_src *s, unsigned char *out, size_t cap) __attribute__((visibility("hidden")));
 size_t fastf_fq_window_bytes(void) __attribute__((visibility("hidden")));
+/* fastq_cmds.c: freq's windows with the DNA-form keys alone, pushed into hist (fqcells) */
+int    fastf_fq_dna_keys(fq_src *s, uint32_t L, fastf_taghist_t *hist, uint64_t *n_reads, uint64_t *n_other, uint64_t *n_bytes,
+                         double t[5]) __attribute__((visibility("hidden")));
 
 /* count.c:3-21 — the reference's cell barcode + UMI tree of an R1 FASTQ, node for node (malloc'ed nodes; the reference's
  * free_tree_node releases it).  Declared here because of zlib's gzFile; the file is read with gzread on the calling thread. */

@@ -437,3 +437,46 @@ extern "C" int fastf_taghist_finish(fastf_taghist_t* h, fastf_taghist_result_t* 
     r->pair_first = (const uint64_t*)h->h_pair_first.data(); r->n_pairs = mp;
     return 0;
 } FASTF_CATCH_INT
+
+// ---- device-resident finish of a single-tag histogram (fqcells: the distinct table feeds a kernel, not the host) ----
+namespace fastf {
+// th_distinct counted the absent records under the fill key (the key of record fill_idx): take them off again.  One lane.
+__global__ __launch_bounds__(64) void th_unfill_kernel(const u64* __restrict__ keys, u64 fill_idx, const u64* __restrict__ u,
+                                                       const u64* __restrict__ m_ptr, u32* __restrict__ c, u64 n_absent,
+                                                       u64* __restrict__ lost) {
+    if (threadIdx.x) return;
+    const u32 m = (u32)*m_ptr;
+    const u64 fill = keys[fill_idx];
+    const u32 d = th_lower_bound(u, m, fill);
+    if (d < m && u[d] == fill && c[d] > n_absent) c[d] -= (u32)n_absent; else *lost = 1;
+}
+}  // namespace fastf
+
+// fastf_taghist_finish's level 1 and no further: *d_keys = the m1 distinct present keys, ascending, *d_counts = their records (u32),
+// both DEVICE arrays of the handle, valid until its next finish or its destruction; no first-occurrence index, no copy of the table
+// to the host.  A histogram whose records are all absent gives m1 = 0 and never reaches the sort.
+extern "C" int fastf_taghist_finish_device(fastf_taghist_t* h, const uint64_t** d_keys, const uint32_t** d_counts, uint64_t* m1_out) FASTF_TRY {
+    if (!h || !d_keys || !d_counts || !m1_out) return set_err("null argument");
+    if (h->pair) return set_err("fastf_taghist_finish_device: a single-tag histogram's finish");
+    *d_keys = nullptr; *d_counts = nullptr; *m1_out = 0;
+    if (h->n_valid == 0) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    hipStream_t s = h->ws->s_compute;
+    const u64 n = h->n;
+    if (h->d_a.ensure(n * sizeof(u64)) || h->d_b.ensure(n * sizeof(u64)) || h->d_u1.ensure(n * sizeof(u64)) ||
+        h->d_c1.ensure(n * sizeof(u32))) return 1;
+    u64* d_m1 = (u64*)h->d_small.p; u64* d_lost = d_m1 + 1;       // ([1]: the pair mode's m2, unused here)
+    if (th_distinct(h, (const u64*)h->d_k1.p, h->first_present1, h->or1 ^ h->and1, (u64*)h->d_u1.p, (u32*)h->d_c1.p, d_m1, s)) return 1;
+    const u64 n_absent = n - h->n_present1;
+    HIP_OK(hipMemsetAsync(d_lost, 0, sizeof(u64), s));
+    if (n_absent)
+        hipLaunchKernelGGL(th_unfill_kernel, dim3(1), dim3(64), 0, s, (const u64*)h->d_k1.p, h->first_present1, (const u64*)h->d_u1.p,
+                           (const u64*)d_m1, (u32*)h->d_c1.p, n_absent, d_lost);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    u64 w[2];
+    if (copy_d2h(w, d_m1, sizeof w)) return 1;
+    if (w[1] || w[0] == 0 || w[0] > n) return set_err("tag histogram: fill key lost");
+    *d_keys = (const uint64_t*)h->d_u1.p; *d_counts = (const uint32_t*)h->d_c1.p; *m1_out = w[0];
+    return 0;
+} FASTF_CATCH_INT

@@ -1598,7 +1598,7 @@ extern "C" int fastf_dev_clear_error_bits(fastf_engine_t* e, uint64_t mask, void
 extern "C" const char* fastf_kernel_names(void) FASTF_TRY {
     return "probe_cells_kernel,probe_cells_lds_kernel,probe_cells_filtered_kernel,scan_tiles_kernel,filter_pack_kernel,filter_pack_stream_kernel,"
            "block_records_kernel,tile_count_kernel,row_scan_kernel,scatter_kernel,reduce_windows_kernel,reduce_hashed_kernel,span_scan_kernel,"
-           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel,marker_labels_kernel,marker_auc_kernel,coex_planes_kernel,coex_gram_kernel,coex_sums_kernel,coex_var_kernel,coex_select_kernel,pt_median_kernel,pt_pairs_kernel,fcp_count_kernel,fcp_rec_kernel";
+           "giant_groups_kernel,rows_gather_kernel,draw_planes_kernel,cell_summary_kernel,cell_hits_kernel,cell_decisions_kernel,gene_summary_kernel,copy_summary_kernel,gene_reps_kernel,level_step_kernel,fidelity_kernel,partner_counts_kernel,gene_moments_kernel,nbr_max_count_kernel,nbr_planes_kernel,nbr_norms_kernel,nbr_gram_kernel,nbr_shared_kernel,label_votes_kernel,marker_labels_kernel,marker_auc_kernel,coex_planes_kernel,coex_gram_kernel,coex_sums_kernel,coex_var_kernel,coex_select_kernel,pt_median_kernel,pt_pairs_kernel,fcp_count_kernel,fcp_rec_kernel,fqc_heads_kernel,fqc_rows_kernel";
 } FASTF_CATCH_ZERO
 
 // ------------------------------------------------------------------------------------
@@ -2526,6 +2526,7 @@ extern "C" int fastf_dev_scan_tiles(fastf_engine_t* e, uint32_t* d_in, uint32_t 
 // ------------------------------------------------------------------------------------
 #include "filter_kernels.hpp"
 #include "fqcap_kernels.hpp"      // fqcap: the same windows, a rate per cell
+#include "fqcells_kernels.hpp"    // fqcells: the histogram's distinct CB+UMI keys -> one row per barcode
 
 // ------------------------------------------------------------------------------------
 // one process, several devices: same translation unit, drives sub-engines through the launch_* functions above

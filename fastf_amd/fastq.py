@@ -71,6 +71,45 @@ def fqcap_rate(cap: int, hits: int, rate: float = 2.0) -> float:
     return float(_lib.lib().fastf_fqcap_rate(int(cap), int(hits), float(rate)))
 
 
+def _fqcells_rule(expect, top, min_umis):
+    given = [(r, v) for r, v in (("e", expect), ("k", top), ("m", min_umis)) if v is not None]
+    if len(given) > 1:
+        raise ValueError("fqcells takes one calling rule: expect, top or min_umis")
+    rule, arg = given[0] if given else ("e", 3000)
+    if int(arg) < 1 or int(arg) >= 1 << 64:
+        raise ValueError("the rule's argument must be a whole number, at least 1")
+    return rule, int(arg)
+
+
+def fqcells(r1, out=".", len_cb: int = 16, len_umi: int = 10, expect=None, top=None, min_umis=None) -> dict:
+    """`fastF fqcells -R r1 -o out -l len_cb -u len_umi [-e expect | -k top | -m min_umis]` (none: -e 3000): the cells of an R1
+    FASTQ called by UMIs per barcode (include/fastf_amd.h has the definition).  Writes out/fqcells.tsv.gz, out/whitelist.txt and
+    out/fqcells_summary.tsv and returns the summary row as a dict (rule as its letter)"""
+    rule, arg = _fqcells_rule(expect, top, min_umis)
+    if len_cb < 1 or len_umi < 0 or len_cb + len_umi > 31:
+        raise ValueError("len_cb >= 1, len_umi >= 0 and len_cb + len_umi <= 31")
+    s = _lib.FqcellsSummary()
+    _lib.check(_lib.lib().fastf_fqcells(os.fspath(r1).encode(), os.fspath(out).encode(), len_cb, len_umi, ord(rule), arg, C.byref(s)))
+    d = {n: int(getattr(s, n)) for n, _ in s._fields_}
+    d["rule"] = chr(d["rule"])
+    return d
+
+
+def fqcells_call(bc, reads, umis, expect=None, top=None, min_umis=None):
+    """the order and the calling rule of fqcells on a table of barcodes (fastf_fqcells_call, on the host): bc = distinct barcodes
+    packed 2 bits a base (uint64), reads (uint64), umis (uint32).  Returns (rank uint32 1-based, called bool, threshold)"""
+    rule, arg = _fqcells_rule(expect, top, min_umis)
+    bc = np.ascontiguousarray(bc, dtype=np.uint64)
+    reads = np.ascontiguousarray(reads, dtype=np.uint64)
+    umis = np.ascontiguousarray(umis, dtype=np.uint32)
+    if not len(bc) == len(reads) == len(umis):
+        raise ValueError("bc, reads and umis are one table")
+    rank, called, thr = np.zeros(len(bc), dtype=np.uint32), np.zeros(len(bc), dtype=np.uint8), C.c_uint64()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _lib.check(_lib.lib().fastf_fqcells_call(ptr(bc), ptr(reads), ptr(umis), len(bc), ord(rule), arg, ptr(rank), ptr(called), C.byref(thr)))
+    return rank, called.astype(bool), thr.value
+
+
 def filter_draws(seed: int, first: int, n: int, device: bool = True) -> np.ndarray:
     """rand() outputs first .. first + n - 1 after srand(seed) (uint32): as filter's device kernel computes them, or
     (device=False) by the host's jump-ahead and recurrence"""

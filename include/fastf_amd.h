@@ -156,6 +156,52 @@ int fastf_fcpdev_decide(fastf_fltdev_t *p, uint32_t len_cellbarcode, float t, co
 int fastf_fcpdev_draws(fastf_fltdev_t *p, uint32_t *out, uint64_t n);
 int fastf_fcpdev_read(fastf_fltdev_t *p, int which, uint32_t *out, size_t n_words);
 
+/* --- fqcells: the cells of an R1 FASTQ, called by UMIs per barcode (fqcells_cmds.c, fqcells_kernels.hpp; not a command of the
+ * reference).  Its whitelist.txt is what `filter -w` and `fqcap -w` read with the same -l.  The definition:
+ *   counted reads    a read is COUNTED iff the first l + u bytes of its R1 sequence line are exactly l + u bytes of ACGT (freq's DNA
+ *                    form; l = len_cellbarcode >= 1, u = len_umi >= 0, l + u <= 31).  Its barcode is the first l of those bytes, its
+ *                    UMI the next u.  Every other read (a shorter line, N, lower case, '\r') is counted in `other` and belongs to no
+ *                    barcode.
+ *   per barcode b    reads[b] = its counted reads, umis[b] = the distinct UMIs among them (u = 0: 1 for every barcode).
+ *   order            by umis descending, then reads descending, then the barcode's bytes ascending; rank = the 1-based position in
+ *                    that order; B = the number of barcodes.
+ *   calling rule     exactly one of (none given: 'e' with 3000):
+ *                      'k' K   called iff rank <= K
+ *                      'm' M   called iff umis >= M
+ *                      'e' E   m = umis of the barcode at rank min(B, E / 100 + 1) (integer division), T = max(1, (m + 5) / 10),
+ *                              called iff umis >= T: Cell Ranger's order-of-magnitude rule in integers
+ *                    threshold = T, M, or for 'k' the umis of the last barcode called (0 when B = 0; 'e' with B = 0 has m = 0, T = 1).
+ *   outputs          <out_dir>/fqcells.tsv.gz: the line "barcode\treads\tumis\trank\tcalled", then one row per barcode ascending by
+ *                    its bytes, called written 0 or 1 (gzip members);
+ *                    <out_dir>/whitelist.txt: the called barcodes, one a line, ascending (plain text);
+ *                    <out_dir>/fqcells_summary.tsv: the line "reads\tcounted\tother\tbarcodes\tumis\trule\targ\tthreshold\tcalled\t
+ *                    called_reads\tcalled_umis" and one row: R1 reads, counted reads, other reads, B, distinct barcode+UMI pairs, the
+ *                    rule's letter, its argument, the threshold, barcodes called, their reads, their umis.
+ * Refused with a message (1 returned, the output directory untouched): no R1, l < 1, l or u negative, l + u > 31, a rule other than
+ * 'e', 'k', 'm', an argument of 0, a directory that cannot be written, freq's declared divergences (a line longer than 1023 bytes, a
+ * file that ends after a header line, corrupt input) and 2^32 - 1 reads or more (the histogram's limit).  An R1 with no counted
+ * read is no error: header-only tables and an empty whitelist. --- */
+typedef struct {
+    uint64_t reads, counted, other, barcodes, umis;
+    uint64_t rule;                              /* 'e', 'k' or 'm' */
+    uint64_t arg, threshold, called, called_reads, called_umis;
+} fastf_fqcells_summary_t;
+int cmd_fqcells(int argc, const char **argv);   /* argv[0] == "fqcells"; freq's option dialect: -R -o -l -u and one of -e -k -m */
+int fastf_fqcells(const char *r1, const char *out_dir, uint32_t len_cellbarcode, uint32_t len_umi, int rule, uint64_t arg,
+                  fastf_fqcells_summary_t *summary);
+/* The order and the rule on a table of n barcodes, on the host threads (no device).  bc[] need not be sorted; it holds distinct
+ * barcodes packed 2 bits a base (A < C < G < T, first base highest), so that its order is the order of the bytes.  rank[i]
+ * (1-based), called[i] (0 / 1) and *threshold as defined above; rank and called may be NULL.  1 for a rule or argument refused. */
+int fastf_fqcells_call(const uint64_t *bc, const uint64_t *reads, const uint32_t *umis, size_t n, int rule, uint64_t arg,
+                       uint32_t *rank, uint8_t *called, uint64_t *threshold);
+/* The device seam: m1 ascending DNA-form keys of l + u bases (bit 63 set or not: it is masked) with their counts, host arrays of
+ * the caller's, through the kernels of the per-barcode reduce.  Out: rows [0, *n_rows) of bc (the key without bit 63, >> 2 * len_umi),
+ * reads and umis, ascending, and 16 guard entries behind them as the device arrays carry them (every byte 0xa5), which no kernel
+ * touches: the three arrays hold m1 + 16 entries.  fastf_fqcells_tile: the keys one workgroup of the reduce takes. */
+int fastf_fqcells_reduce(const uint64_t *keys, const uint32_t *counts, size_t m1, uint32_t len_umi, uint64_t *bc, uint64_t *reads,
+                         uint32_t *umis, size_t *n_rows);
+size_t fastf_fqcells_tile(void);
+
 /* --- sweep: bam2db over a grid of (cell rate, depth rate) points from ONE decode of the BAM (sweep_cmds.c; not a command of the
  * reference).  Per point <out_dir>/c<rate_cell>_r<rate_depth>/ (rates printed %.3f) holds matrix.mtx.gz, barcodes.tsv.gz and
  * features.tsv.gz with the bytes bam2db() writes for that point; <out_dir>/sweep.tsv holds a header and one row per point, cell
